@@ -22,7 +22,8 @@ One rank per GPU.  `python bench.py --gpus N` with no WORLD_SIZE in the environm
 JSON line; under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.  The exchange is the
 library's own RCCL path (lb_gpu_comm_*, LB_BENCH_COMM=lib, default; =torch: torch.distributed's all-gather).
 Every run also carries a `strong_c3` leg (BASELINE config 3: a fixed 10M x 768 dot corpus over the N GPUs).
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes the headline's last timed step (labels and distances of
+every query) as DIR/*.npy; the inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -509,7 +510,7 @@ def timed_steps(job, idx, searcher, Q, steps, warmup):
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
-        step()
+        lab, dd = step()
         tm = idx.last_timing()
         gemm_launches += tm["gemm"][1]
         for c in cls_ms:
@@ -522,9 +523,29 @@ def timed_steps(job, idx, searcher, Q, steps, warmup):
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    lab, dd = step()
+    # labels / dist: what the LAST timed step returned (the buffers are not touched again before this copy)
     return {"elapsed": elapsed, "cls_ms": cls_ms, "gemm_launches": gemm_launches, "fallbacks": fallbacks,
             "labels": lab.cpu().numpy().copy(), "dist": dd.cpu().numpy().copy(), "step": step}
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each [B, ...] array as out_dir/<name>.npy, float32 stays float32 and everything else becomes float64
+    (labels: ids < 2^53, exact).  Past DUMP_MAX_BYTES in all, the same fixed, seeded sample of rows is taken from every
+    array and its row numbers are written as query_rows.npy."""
+    out = {n: np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64) for n, a in arrays.items()}
+    nrows = next(iter(out.values())).shape[0]
+    row_bytes = sum(a.nbytes // max(1, a.shape[0]) for a in out.values())
+    if row_bytes * nrows > DUMP_MAX_BYTES:
+        keep = DUMP_MAX_BYTES // (row_bytes + 8)  # (+ its query_rows entry)
+        sel = np.sort(np.random.default_rng(0).choice(nrows, size=keep, replace=False))
+        out = {n: a[sel] for n, a in out.items()}
+        out["query_rows"] = sel.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in out.items():
+        np.save(os.path.join(out_dir, n + ".npy"), a)
 
 
 def gather_rows(job, rows):
@@ -574,7 +595,14 @@ def main():
     ap.add_argument("--no-fast", action="store_true", help="skip the candidate-mode legs (auto path, split-bf16 image)")
     ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (sweep, strong C3, PQ, filtered hybrid)")
     ap.add_argument("--cpu-queries", type=int, default=0, help="CPU baseline sample size (0 = 16 per core)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (labels, distances) to DIR/<name>.npy, for output-for-output "
+                         "comparison of two builds on the same seeded inputs")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and os.environ.get("LB_BENCH_CHILD") != "1":
         sys.exit(launch_ranks(args, sys.argv[1:]))  # before torch / the GPU library are imported
@@ -621,6 +649,8 @@ def main():
     elapsed, cls_ms, step = r["elapsed"], r["cls_ms"], r["step"]
     gemm_ms, gemm_launches, fallbacks = cls_ms["gemm"], r["gemm_launches"], r["fallbacks"]
     lab_h, dist_h = r["labels"], r["dist"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"labels": lab_h, "distances": dist_h})
     shard_rows = gather_rows(job, rows)
     stream = torch.cuda.current_stream(dev).cuda_stream
 

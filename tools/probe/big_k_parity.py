@@ -1,7 +1,7 @@
 """Parity of long result lists (k = 600 .. LB_MAX_K) with the oracle on two small corpora, batch and single query.
 usage: python tools/probe/big_k_parity.py"""
 import os, sys
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import numpy as np
 from longbow_amd import gpu
 from oracle import oracle_c as oc

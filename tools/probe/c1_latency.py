@@ -2,7 +2,7 @@
 Five launches at this size (init, bootstrap chunk, select, rest, select + emit): 31 us of kernels in a 45 us search.
 usage: [N=rows] python tools/probe/c1_latency.py"""
 import os, sys, time
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
 import numpy as np, torch
 from longbow_amd import _lib, gpu
 lib = _lib.require_gpu(0)
