@@ -23,6 +23,7 @@
 // to a per-query scratch block with device-scope stores and the last workgroup to arrive (ticket) sorts, proves and emits.
 // Tiled (many queries: throughput): one workgroup per query, 256 members at a time staged through LDS in 128-B pieces.
 #include "lb_device.h"
+#include "lb_exact.h"
 #include "lb_select.h"
 
 #include <float.h>
@@ -41,26 +42,6 @@ constexpr int FN_DK = 32, FN_LDT = FN_DK + 4;                 // tiled: 256 rows
 #ifdef LB_DIAG
 __device__ unsigned long long g_finish_probe[8]; // [0] members summed over queries, [1] queries, [2] list entries summed, [3] largest member count
 #endif
-
-// four LDS-DMA requests of 1 KiB behind one M0 write: the instruction offset moves the LDS destination and the global address
-// alike (the caller pre-compensates the sources), as in the candidate kernels
-__device__ __forceinline__ void fn_dma16x4(const void *g0, const void *g1, const void *g2, const void *g3, uint32_t lds_addr)
-{
-    uint32_t save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\t"
-                 "global_load_lds_dwordx4 %2, off offset:1024\n\t"
-                 "global_load_lds_dwordx4 %3, off offset:2048\n\t"
-                 "global_load_lds_dwordx4 %4, off offset:3072\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(save) : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(lds_addr) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void fn_wait_vmcnt()
-{
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-    asm volatile("" ::: "memory");
-}
 
 struct FinishArgs {
     const float *X;
@@ -172,63 +153,12 @@ __device__ __forceinline__ uint64_t radix_kth_regs(const uint64_t (&e)[PER], uin
     return prefix;
 }
 
+// the exact result of a member: its distance and the value the proof compares (L2: the squared distance)
 template <int METRIC>
-__device__ __forceinline__ void exact_values(float t, float nbt, float na, int D, float &dist, float &cmp)
+__device__ __forceinline__ void member_values(float t, float nbt, float na, int D, float &dist, float &cmp)
 {
-    if (METRIC == METRIC_L2) {
-        dist = (float)sqrt((double)t);
-        cmp = t; // compare in d^2 space
-    } else if (METRIC == METRIC_COS) {
-        if (D == 0 || na == 0.0f || nbt == 0.0f) dist = 1.0f;
-        else dist = 1.0f - __fdiv_rn(t, (float)sqrt((double)na * (double)nbt));
-        cmp = dist;
-    } else {
-        dist = -t;
-        cmp = dist;
-    }
-}
-
-// one lane, one row, straight from memory in the reference's order (dimensions that are not multiples of 4, unaligned rows)
-template <int METRIC, int ORDER>
-__device__ __forceinline__ void exact_row_generic(const float *x, const float *q, int D, float na, float &dist, float &cmp)
-{
-    AccR<ORDER> acc, nb;
-    acc.zero();
-    nb.zero();
-    const int dmain = D & ~3;
-    for (int i = 0; i < dmain; i += 4) {
-        const float x0 = x[i], x1 = x[i + 1], x2 = x[i + 2], x3 = x[i + 3];
-        const float q0 = q[i], q1 = q[i + 1], q2 = q[i + 2], q3 = q[i + 3];
-        if (METRIC == METRIC_COS) {
-            nb.template add<0>(x0 * x0);
-            nb.template add<1>(x1 * x1);
-            nb.template add<2>(x2 * x2);
-            nb.template add<3>(x3 * x3);
-        }
-        if (METRIC == METRIC_L2) {
-            const float e0 = q0 - x0, e1 = q1 - x1, e2 = q2 - x2, e3 = q3 - x3;
-            acc.template add<0>(e0 * e0);
-            acc.template add<1>(e1 * e1);
-            acc.template add<2>(e2 * e2);
-            acc.template add<3>(e3 * e3);
-        } else {
-            acc.template add<0>(q0 * x0);
-            acc.template add<1>(q1 * x1);
-            acc.template add<2>(q2 * x2);
-            acc.template add<3>(q3 * x3);
-        }
-    }
-    for (int i = dmain; i < D; i++) {
-        const float xv = x[i], qv = q[i];
-        if (METRIC == METRIC_COS) nb.add_tail(xv * xv);
-        if (METRIC == METRIC_L2) {
-            const float e = qv - xv;
-            acc.add_tail(e * e);
-        } else {
-            acc.add_tail(qv * xv);
-        }
-    }
-    exact_values<METRIC>(acc.total(), nb.total(), na, D, dist, cmp);
+    dist = exact_distance<METRIC>(t, nbt, na, D, false);
+    cmp = METRIC == METRIC_L2 ? t : dist;
 }
 
 // What separates the exact (computed) value of a row from the value its candidate key stands for, one-sided: the proof
@@ -427,8 +357,9 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
 #endif
     if (!a.aligned) {
         for (uint32_t c = tid; c < nm; c += FN_THREADS) {
-            float dist, cmp;
-            exact_row_generic<METRIC, ORDER>(a.X + (int64_t)s_rows[c] * D, q, D, na, dist, cmp);
+            float t, nbt, dist, cmp;
+            exact_pair_sums<METRIC, ORDER>(a.X + (int64_t)s_rows[c] * D, q, D, t, nbt);
+            member_values<METRIC>(t, nbt, na, D, dist, cmp);
             skey[c] = pack_entry(dist, s_rows[c]);
             scmp[c] = cmp;
         }
@@ -538,7 +469,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
             const uint32_t c = c0 + (uint32_t)myr;
             if (worker && myt == 0 && c < nm) {
                 float dist, cmp;
-                exact_values<METRIC>(t, nbt, na, D, dist, cmp);
+                member_values<METRIC>(t, nbt, na, D, dist, cmp);
                 skey[c] = pack_entry(dist, s_rows[c]);
                 scmp[c] = cmp;
             }
@@ -555,7 +486,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
         const int nchunks = (D + FN_DK - 1) / FN_DK;
         for (uint32_t g0 = 0; g0 < nm; g0 += FN_THREADS) {
             __syncthreads(); // the tile is free (previous group done); sq is there
-            AccR<ORDER> acc, nb;
+            Acc<ORDER> acc, nb;
             acc.zero();
             nb.zero();
             f32x4 stg[8];
@@ -589,31 +520,15 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
                     if (gq < n4) {
                         const f32x4 xv = *reinterpret_cast<const f32x4 *>(&xr[gq * 4]);
                         const f32x4 qv = *reinterpret_cast<const f32x4 *>(&sq[d0 + gq * 4]);
-                        if (METRIC == METRIC_COS) {
-                            nb.template add<0>(xv.x * xv.x);
-                            nb.template add<1>(xv.y * xv.y);
-                            nb.template add<2>(xv.z * xv.z);
-                            nb.template add<3>(xv.w * xv.w);
-                        }
-                        if (METRIC == METRIC_L2) {
-                            const float e0 = qv.x - xv.x, e1 = qv.y - xv.y, e2 = qv.z - xv.z, e3 = qv.w - xv.w;
-                            acc.template add<0>(e0 * e0);
-                            acc.template add<1>(e1 * e1);
-                            acc.template add<2>(e2 * e2);
-                            acc.template add<3>(e3 * e3);
-                        } else {
-                            acc.template add<0>(qv.x * xv.x);
-                            acc.template add<1>(qv.y * xv.y);
-                            acc.template add<2>(qv.z * xv.z);
-                            acc.template add<3>(qv.w * xv.w);
-                        }
+                        if (METRIC == METRIC_COS) nb.add4_sq(xv);
+                        acc.template add4_pair<METRIC>(qv, xv);
                     }
                 }
             }
             const uint32_t c = g0 + (uint32_t)tid;
             if (c < nm) {
                 float dist, cmp;
-                exact_values<METRIC>(acc.total(), nb.total(), na, D, dist, cmp);
+                member_values<METRIC>(acc.total(), nb.total(), na, D, dist, cmp);
                 skey[c] = pack_entry(dist, s_rows[c]);
                 scmp[c] = cmp;
             }
@@ -658,8 +573,8 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
             int kx = rc * FN_DK + piece * 4;
             if (kx > D - 4) kx = D - 4; // pieces past D are never consumed
             const uint32_t dst = ring_base + (uint32_t)rslot * (FN_THREADS * 128u) + (uint32_t)wv * 8192u;
-            fn_dma16x4(rsrc[0] + kx * 4, rsrc[1] + kx * 4, rsrc[2] + kx * 4, rsrc[3] + kx * 4, dst);
-            fn_dma16x4(rsrc[4] + kx * 4, rsrc[5] + kx * 4, rsrc[6] + kx * 4, rsrc[7] + kx * 4, dst + 4096u);
+            lds_dma16x4<false>(rsrc[0] + kx * 4, rsrc[1] + kx * 4, rsrc[2] + kx * 4, rsrc[3] + kx * 4, dst);
+            lds_dma16x4<false>(rsrc[4] + kx * 4, rsrc[5] + kx * 4, rsrc[6] + kx * 4, rsrc[7] + kx * 4, dst + 4096u);
             rslot = rslot + 1 == nst ? 0 : rslot + 1;
             if (rc + 1 < nchunks) rc++;
             else if (rg + 1 < ngroups) { rg++; rc = 0; set_group(rg); }
@@ -667,16 +582,16 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
         __syncthreads(); // s_rows (posmap applied), sq
         set_group(0);
         for (int st = 0; st < dist; st++) request();
-        AccR<ORDER> acc, nb;
+        Acc<ORDER> acc, nb;
         acc.zero();
         nb.zero();
         int cslot = 0, cc = 0, cg = 0;
         for (int sidx = 0; sidx < total; sidx++) {
             // stage sidx has landed for this wave: at most the dist - 1 younger stages (8 requests each) are out; behind the
             // barrier it has landed for all, and everybody is done with the stage before -- whose slot the next request takes
-            if (dist >= 3) fn_wait_vmcnt<16>();
-            else if (dist == 2) fn_wait_vmcnt<8>();
-            else fn_wait_vmcnt<0>();
+            if (dist >= 3) wait_vmcnt<16>();
+            else if (dist == 2) wait_vmcnt<8>();
+            else wait_vmcnt<0>();
             __syncthreads();
             request();
             const int d0 = cc * FN_DK;
@@ -685,24 +600,8 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
             auto walk = [&](int gq) {
                 const f32x4 xv = *reinterpret_cast<const f32x4 *>(xr + ((gq ^ (tid & 7)) << 4));
                 const f32x4 qv = *reinterpret_cast<const f32x4 *>(&sq[d0 + gq * 4]);
-                if (METRIC == METRIC_COS) {
-                    nb.template add<0>(xv.x * xv.x);
-                    nb.template add<1>(xv.y * xv.y);
-                    nb.template add<2>(xv.z * xv.z);
-                    nb.template add<3>(xv.w * xv.w);
-                }
-                if (METRIC == METRIC_L2) {
-                    const float e0 = qv.x - xv.x, e1 = qv.y - xv.y, e2 = qv.z - xv.z, e3 = qv.w - xv.w;
-                    acc.template add<0>(e0 * e0);
-                    acc.template add<1>(e1 * e1);
-                    acc.template add<2>(e2 * e2);
-                    acc.template add<3>(e3 * e3);
-                } else {
-                    acc.template add<0>(qv.x * xv.x);
-                    acc.template add<1>(qv.y * xv.y);
-                    acc.template add<2>(qv.z * xv.z);
-                    acc.template add<3>(qv.w * xv.w);
-                }
+                if (METRIC == METRIC_COS) nb.add4_sq(xv);
+                acc.template add4_pair<METRIC>(qv, xv);
             };
             if (n4 == FN_DK / 4) { // a whole chunk: no guards, so that the eight pieces' LDS reads go out together
 #pragma unroll
@@ -715,7 +614,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
                 const uint32_t c = (uint32_t)cg * FN_THREADS + (uint32_t)tid;
                 if (c < nm) {
                     float dist_, cmp;
-                    exact_values<METRIC>(acc.total(), nb.total(), na, D, dist_, cmp);
+                    member_values<METRIC>(acc.total(), nb.total(), na, D, dist_, cmp);
                     skey[c] = pack_entry(dist_, s_rows[c]);
                     scmp[c] = cmp;
                 }
@@ -725,7 +624,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
                 cg++;
             }
         }
-        fn_wait_vmcnt<0>(); // the requests beyond the last stage: nothing may land in LDS once the ring is given up
+        wait_vmcnt<0>(); // the requests beyond the last stage: nothing may land in LDS once the ring is given up
     }
     __syncthreads();
 

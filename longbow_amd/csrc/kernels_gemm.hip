@@ -18,10 +18,6 @@
 
 namespace lb {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BM = 128; // corpus rows per tile (MFMA A operand, output rows)
 constexpr int BN = 128; // queries per tile   (MFMA B operand, output cols = lanes)
 constexpr int BK = 32;
@@ -491,16 +487,8 @@ void read_clock_probe(unsigned long long out[8], bool reset)
 __global__ __launch_bounds__(256) void split_bf16_kernel(const float *src, float *dst, int64_t n8)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
-        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + i * 8);
-        const f32x4 v1 = *reinterpret_cast<const f32x4 *>(src + i * 8 + 4);
-        const float x[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         bf16x8 hi, lo;
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const __bf16 hh = (__bf16)x[j];
-            hi[j] = hh;
-            lo[j] = (__bf16)(x[j] - (float)hh);
-        }
+        split_bf16x8(*reinterpret_cast<const f32x4 *>(src + i * 8), *reinterpret_cast<const f32x4 *>(src + i * 8 + 4), hi, lo);
         const int64_t grp = i >> 1; // 16-k group index over the flattened [rows*D/16]
         const int kb = (int)(i & 1);
         char *g = reinterpret_cast<char *>(dst) + grp * 64;

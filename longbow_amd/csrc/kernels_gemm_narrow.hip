@@ -21,25 +21,9 @@
 // inside the launch -- sample tiles, per-query threshold workgroups, corpus workgroups of two row
 // tiles that pick the thresholds up; see FusedSample in lb_device.h and LABNOTES.md 3.3).
 #include "lb_device.h"
+#include "lb_exact.h"
 
 namespace lb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-// x (8 consecutive f32 of one row) -> hi = bf16(x) (round to nearest even), lo = bf16(x - hi):
-// x = hi + lo + O(2^-18 |x|).  Same split as split_bf16_kernel (kernels_gemm.hip), done in registers.
-__device__ __forceinline__ void split8(const f32x4 x0, const f32x4 x1, bf16x8 &hi, bf16x8 &lo)
-{
-    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const __bf16 h = (__bf16)x[i];
-        hi[i] = h;
-        lo[i] = (__bf16)(x[i] - (float)h);
-    }
-}
 
 constexpr int NBK = 32;
 constexpr int NTHREADS = 256;
@@ -80,30 +64,6 @@ void read_fused_probe(unsigned long long out[8], bool reset)
 constexpr uint32_t kSpinLimit = 1500; // x ~0.6 us (s_sleep 8 + one L2 round trip) ~ 1 ms: a wait that long means the launch's workgroups are
                                       // not co-resident; the batch is then redone on the exact path and the give-up is counted
                                       // (lb_gpu_index_fused_giveups)
-
-// ||q||^2 in the reference's accumulation order (as kernels_scan.hip: exact_sq_norm_lds), q in LDS, one lane
-__device__ __forceinline__ float narrow_exact_sq_norm(const float *sq, int D, int order)
-{
-#pragma clang fp contract(off)
-    if (order == ORDER_UNROLL4) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        const int dmain = D & ~3;
-        for (int i = 0; i < dmain; i += 4) {
-            s0 = s0 + sq[i] * sq[i];
-            s1 = s1 + sq[i + 1] * sq[i + 1];
-            s2 = s2 + sq[i + 2] * sq[i + 2];
-            s3 = s3 + sq[i + 3] * sq[i + 3];
-        }
-        for (int i = dmain; i < D; i++) s0 = s0 + sq[i] * sq[i];
-        float t = s0 + s1;
-        t = t + s2;
-        t = t + s3;
-        return t;
-    }
-    float t = 0.f;
-    for (int i = 0; i < D; i++) t = t + sq[i] * sq[i];
-    return t;
-}
 
 // SPLIT: the inner products are computed as hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with both
 // operands split into bf16 pairs IN REGISTERS after the (unchanged) f32 LDS staging -- no second copy of
@@ -277,14 +237,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
 #pragma unroll
                     for (int t = 0; t < TM; t++) {
                         const int r = wave * WROWS + t * 32 + l31;
-                        split8(*reinterpret_cast<const f32x4 *>(&As[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&As[nswz(r, ch + 1)]),
-                               ah[t], al[t]);
+                        split_bf16x8(*reinterpret_cast<const f32x4 *>(&As[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&As[nswz(r, ch + 1)]),
+                                     ah[t], al[t]);
                     }
 #pragma unroll
                     for (int t = 0; t < TN; t++) {
                         const int r = t * 32 + l31;
-                        split8(*reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch + 1)]),
-                               bh[t], bl[t]);
+                        split_bf16x8(*reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch + 1)]),
+                                     bh[t], bl[t]);
                     }
 #pragma unroll
                     for (int tm = 0; tm < TM; tm++)
@@ -527,7 +487,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
         const float *q = a.Q + (int64_t)j * a.D;
         for (int i = tid; i < a.D; i += NTHREADS) sq[i] = q[i];
         __syncthreads();
-        if (tid == 0) a.fs.qna[j] = narrow_exact_sq_norm(sq, a.D, a.fs.order);
+        if (tid == 0) a.fs.qna[j] = exact_sq_norm_lds(sq, a.D, a.fs.order);
         __syncthreads();
     }
     if (tid == 0) {

@@ -33,14 +33,11 @@
 //                                with more query tiles than an XCD has workgroup slots
 // What each design decision bought is in LABNOTES.md 4.2 (measured with tools/experiments/dma_patterns.hip).
 #include "lb_device.h"
+#include "lb_exact.h"
 
 #include <type_traits>
 
 namespace lb {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 
@@ -150,69 +147,6 @@ __device__ __forceinline__ int haswz(int row, int chunk) { return row * 128 + ((
 // query rows: 64 B, four 16-B chunks, chunk c of row r at position c ^ ((r >> 2) & 3)      (byte offset in the B region)
 __device__ __forceinline__ int hbswz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
-// requests behind ONE M0 write; the instruction offset moves the LDS destination and the global address alike (the callers
-// pre-compensate the sources)
-template <bool NT>
-__device__ __forceinline__ void h_dma16x4(const void *g0, const void *g1, const void *g2, const void *g3, uint32_t lds_addr)
-{
-    uint32_t save;
-    if (NT) // non-temporal: a corpus line that only this workgroup will read (one or two query tiles per corpus tile)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, off nt\n\t"
-                     "global_load_lds_dwordx4 %2, off offset:1024 nt\n\t"
-                     "global_load_lds_dwordx4 %3, off offset:2048 nt\n\t"
-                     "global_load_lds_dwordx4 %4, off offset:3072 nt\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(save) : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(lds_addr) : "memory");
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, off\n\t"
-                     "global_load_lds_dwordx4 %2, off offset:1024\n\t"
-                     "global_load_lds_dwordx4 %3, off offset:2048\n\t"
-                     "global_load_lds_dwordx4 %4, off offset:3072\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(save) : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ void h_dma16x2(const void *g0, const void *g1, uint32_t lds_addr)
-{
-    uint32_t save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\t"
-                 "global_load_lds_dwordx4 %2, off offset:1024\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(save) : "v"(g0), "v"(g1), "s"(lds_addr) : "memory");
-}
-// ONE request (SPREAD: a stage's six requests are issued one at a time between the MFMAs of the step before)
-template <bool NT>
-__device__ __forceinline__ void h_dma16(const void *g, uint32_t lds_addr)
-{
-    uint32_t save;
-    if (NT)
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, off nt\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(save) : "v"(g), "s"(lds_addr));
-    else
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
-                     "global_load_lds_dwordx4 %1, off\n\t"
-                     "s_mov_b32 m0, %0"
-                     : "=&s"(save) : "v"(g), "s"(lds_addr));
-}
-template <int N>
-__device__ __forceinline__ void h_wait_vmcnt()
-{
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ f16x8 h_cvt8(const f32x4 x0, const f32x4 x1)
-{
-    f16x8 r; // round to nearest even (v_cvt_f16_f32 under the default rounding mode)
-    r[0] = (_Float16)x0.x; r[1] = (_Float16)x0.y; r[2] = (_Float16)x0.z; r[3] = (_Float16)x0.w;
-    r[4] = (_Float16)x1.x; r[5] = (_Float16)x1.y; r[6] = (_Float16)x1.z; r[7] = (_Float16)x1.w;
-    return r;
-}
-
 // NT: the corpus requests carry the non-temporal policy (few query tiles per corpus tile: the line is not read again)
 // SPREAD: the requests of stage k + 2 go out one by one between the MFMAs of step k instead of in one burst behind the barrier
 // (in a burst all eight waves queue on the CU's one address unit while the matrix pipe idles)
@@ -278,8 +212,8 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
         const uint32_t B = A + H_A_BYTES;
         const int ka = kt * (H_BK * 4);                       // byte offset along a corpus row
         const int64_t kb = kt * kb_stride;                    // the query image's K-block
-        h_dma16x4<NT>(srcA[0] + ka, srcA[1] + ka, srcA[2] + ka, srcA[3] + ka, A + (uint32_t)(wave * 32 * 128));
-        h_dma16x2(srcB[0] + kb, srcB[1] + kb, B + (uint32_t)(wave * 32 * 64));
+        lds_dma16x4<NT>(srcA[0] + ka, srcA[1] + ka, srcA[2] + ka, srcA[3] + ka, A + (uint32_t)(wave * 32 * 128));
+        lds_dma16x2(srcB[0] + kb, srcB[1] + kb, B + (uint32_t)(wave * 32 * 64));
     };
 
     f32x16 acc[2][4];
@@ -323,8 +257,8 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
         unsigned long long s0 = 0, s1 = 0;
         if (ABL == 5) s0 = __builtin_amdgcn_s_memtime();
         // stage kt has landed once at most the requests of stage kt + 1 are outstanding
-        if (kt + 1 < nk) h_wait_vmcnt<(ABL == 3 ? 4 : H_NI)>();
-        else h_wait_vmcnt<0>();
+        if (kt + 1 < nk) wait_vmcnt<(ABL == 3 ? 4 : H_NI)>();
+        else wait_vmcnt<0>();
         if (ABL == 5) s1 = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_barrier(); // everyone's part of stage kt is in; everyone is done reading stage kt - 1
         asm volatile("" ::: "memory");
@@ -346,7 +280,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
                     // lane half h supplies k = 16 kb + 8 h .. + 7: f32 chunks 4 kb + 2 h and the next
                     const f32x4 x0 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h));
                     const f32x4 x1 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h + 1));
-                    af[tm] = h_cvt8(x0, x1);
+                    af[tm] = cvt_f16x8(x0, x1);
                 }
             }
 #pragma unroll
@@ -361,10 +295,10 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
                 }
                 if (ISSUE && SPREAD) { // slots 0 1 2 . 4 5 6 . of the step's eight MFMA pairs: corpus 0..3, queries 0..1
                     const int slot = kb * 4 + tn;
-                    if (slot < 3) h_dma16<NT>(srcA[slot] + 1024 * slot + ka2, A2 + 1024u * slot);
-                    else if (slot == 4) h_dma16<NT>(srcA[3] + 1024 * 3 + ka2, A2 + 1024u * 3);
-                    else if (slot == 5 && ABL != 3) h_dma16<false>(srcB[0] + kb2, B2);
-                    else if (slot == 6 && ABL != 3) h_dma16<false>(srcB[1] + 1024 + kb2, B2 + 1024u);
+                    if (slot < 3) lds_dma16_noclobber<NT>(srcA[slot] + 1024 * slot + ka2, A2 + 1024u * slot);
+                    else if (slot == 4) lds_dma16_noclobber<NT>(srcA[3] + 1024 * 3 + ka2, A2 + 1024u * 3);
+                    else if (slot == 5 && ABL != 3) lds_dma16_noclobber<false>(srcB[0] + kb2, B2);
+                    else if (slot == 6 && ABL != 3) lds_dma16_noclobber<false>(srcB[1] + 1024 + kb2, B2 + 1024u);
                 }
             }
         }
@@ -629,8 +563,8 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
         const uint32_t B = ring_base + (uint32_t)islot * STAGE + A_BYTES + (uint32_t)(wave * 32 * 64);
         int ke = ik + krot; // (the sum over k does not care where it starts)
         if (ke >= nk) ke -= nk;
-        if (p < NPA) h_dma16<NT>(srcA[p] + (AIMG ? h_xoff(ke, plane_bytes) : (int64_t)ke * (H_BK * 4)), A + 1024u * p);
-        else h_dma16<false>(srcB[p - NPA] + ke * kb_stride, B + 1024u * (p - NPA));
+        if (p < NPA) lds_dma16_noclobber<NT>(srcA[p] + (AIMG ? h_xoff(ke, plane_bytes) : (int64_t)ke * (H_BK * 4)), A + 1024u * p);
+        else lds_dma16_noclobber<false>(srcB[p - NPA] + ke * kb_stride, B + 1024u * (p - NPA));
     };
     auto advance = [&]() { // (beyond the last stage the cursor stays on it)
         islot = islot == NST - 1 ? 0 : islot + 1;
@@ -659,7 +593,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
     if (MAPPED) { // the ids of the first two tiles, once, before anything depends on them
         rowid_request(0);
         if (n_my > 1) rowid_request(1);
-        h_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
@@ -724,7 +658,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
             } else {
                 const f32x4 x0 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h));
                 const f32x4 x1 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h + 1));
-                af[tm] = h_cvt8(x0, x1);
+                af[tm] = cvt_f16x8(x0, x1);
             }
         }
 #pragma unroll
@@ -749,7 +683,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
     int cslot = 0; // ring slot of the stage being computed
     f16x8 a0[2], b0[4];
     if (PIPE) {
-        h_wait_vmcnt<NPS *(DIST - 1)>(); // stage 0 has landed: at most the requests of the DIST - 1 younger stages are out
+        wait_vmcnt<NPS *(DIST - 1)>(); // stage 0 has landed: at most the requests of the DIST - 1 younger stages are out
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         load_frag(0, 0, a0, b0);
@@ -766,7 +700,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
 
         for (int kt = 0; kt < nk; kt++) {
             if (!PIPE) {
-                h_wait_vmcnt<NPS *(DIST - 1)>(); // this stage has landed: at most the requests of the DIST - 1 younger ones are out
+                wait_vmcnt<NPS *(DIST - 1)>(); // this stage has landed: at most the requests of the DIST - 1 younger ones are out
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 load_frag(cslot, 0, a0, b0);
@@ -791,7 +725,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
             if (!PIPE) load_frag(cslot, 1, a1, b1);
             if (PIPE) {
                 __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0), vmcnt / expcnt untouched
-                h_wait_vmcnt<NPS *(DIST - 2) + H1>();
+                wait_vmcnt<NPS *(DIST - 2) + H1>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 if (aux_now && nk == 1) aux_request(i + 1);
@@ -815,7 +749,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
         // K-steps' waits do not cover (they cover a stage asked for DIST steps earlier, and with it everything older).  By now
         // 2 NPS - H1 (+ 1) requests are newer than it; vmcnt retires in order, the barrier publishes the other waves' parts.
         if (PIPE && nk == 1) {
-            h_wait_vmcnt<2 * NPS - H1>();
+            wait_vmcnt<2 * NPS - H1>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
@@ -926,7 +860,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
             wcnt = 0;
         }
     }
-    h_wait_vmcnt<0>(); // the re-read stages behind the last tile: nothing may land in LDS after the workgroup has gone
+    wait_vmcnt<0>(); // the re-read stages behind the last tile: nothing may land in LDS after the workgroup has gone
 }
 
 // ---- up to 256 queries (one query tile) over the corpus's fp16 image: the pass is the image's HBM stream ---------------------
@@ -1058,28 +992,7 @@ __device__ __forceinline__ void tin_duty(const Tall16Args &a, int j, unsigned ch
             if (a.abl != 12) // (12: the threshold never comes out -- every wave's wait gives up; tests/test_gpu_thresholds_in_launch.py)
 #endif
             __hip_atomic_store(&a.cs.tau[j], tv, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.tin_qna) { // D dependent additions in the reference's order (nothing waits for them but this workgroup's rows)
-#pragma clang fp contract(off)
-                float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-                const int D = a.D, dmain = D & ~3;
-                if (a.tin_order == 1) { // ORDER_UNROLL4
-                    for (int i = 0; i < dmain; i += 4) {
-                        const float v0 = sq[i], v1 = sq[i + 1], v2 = sq[i + 2], v3 = sq[i + 3];
-                        s0 = s0 + v0 * v0;
-                        s1 = s1 + v1 * v1;
-                        s2 = s2 + v2 * v2;
-                        s3 = s3 + v3 * v3;
-                    }
-                    for (int i = dmain; i < D; i++) s0 = s0 + sq[i] * sq[i];
-                    float t = s0 + s1;
-                    t = t + s2;
-                    t = t + s3;
-                    a.tin_qna[j] = t;
-                } else {
-                    for (int i = 0; i < D; i++) s0 = s0 + sq[i] * sq[i];
-                    a.tin_qna[j] = s0;
-                }
-            }
+            if (a.tin_qna) a.tin_qna[j] = exact_sq_norm_lds(sq, a.D, a.tin_order); // (nothing waits for it but this workgroup's rows)
         }
     }
     __syncthreads();
@@ -1189,8 +1102,8 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
     auto piece = [&](int p) {
         const uint32_t A = ring_base + (uint32_t)islot * STAGE + (uint32_t)(wave * 32 * 64);
         const uint32_t B = ring_base + (uint32_t)islot * STAGE + A_BYTES + (uint32_t)(wave * (BN * 8));
-        if (p < 2) h_dma16<true>(srcA[p] + h_xoff(ik, plane_bytes), A + 1024u * p);
-        else if (BN != 64 || lane < 32) h_dma16<false>(srcB[p - 2] + ik * kb_stride, B + 1024u * (p - 2));
+        if (p < 2) lds_dma16_noclobber<true>(srcA[p] + h_xoff(ik, plane_bytes), A + 1024u * p);
+        else if (BN != 64 || lane < 32) lds_dma16_noclobber<false>(srcB[p - 2] + ik * kb_stride, B + 1024u * (p - 2));
     };
     auto advance = [&]() {
         islot = islot == NST - 1 ? 0 : islot + 1;
@@ -1219,7 +1132,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
     if (MAPPED) { // the ids of the first two tiles, once, before anything depends on them
         rowid_request(0);
         if (n_my > 1) rowid_request(1);
-        h_wait_vmcnt<0>();
+        wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     }
@@ -1282,7 +1195,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
     int cslot = 0;
     f16x8 a0, b0[TN];
     if (PIPE) {
-        h_wait_vmcnt<NPS *(DIST - 1)>();
+        wait_vmcnt<NPS *(DIST - 1)>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         load_frag(0, 0, a0, b0);
@@ -1297,7 +1210,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
 
         for (int kt = 0; kt < nk; kt++) {
             if (!PIPE) {
-                h_wait_vmcnt<NPS *(DIST - 1)>();
+                wait_vmcnt<NPS *(DIST - 1)>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 load_frag(cslot, 0, a0, b0);
@@ -1316,7 +1229,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
             if (!PIPE) load_frag(cslot, 1, a1, b1);
             if (PIPE) { // middle of the step (see the 256-query form): reads of stage kt complete, stage kt + 1 landed, barrier
                 __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0)
-                h_wait_vmcnt<NPS *(DIST - 2) + H1>();
+                wait_vmcnt<NPS *(DIST - 2) + H1>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 if (aux_now && nk == 1) aux_request(i + 1);
@@ -1337,8 +1250,8 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
         // tile (asked for in the middle of the step before), 3 NPS (+ 1) at two (at the top of the tile before's second step);
         // vmcnt retires in order, and the barrier publishes the other waves' parts.
         if (PIPE && nk <= 2) {
-            if (nk == 1) h_wait_vmcnt<2 * NPS - H1>();
-            else h_wait_vmcnt<3 * NPS>();
+            if (nk == 1) wait_vmcnt<2 * NPS - H1>();
+            else wait_vmcnt<3 * NPS>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
         }
@@ -1461,7 +1374,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
             wcnt = 0;
         }
     }
-    h_wait_vmcnt<0>();
+    wait_vmcnt<0>();
 }
 
 // f32 [nq][D] -> fp16 [D / 32][nq][32], each query scaled by the power of two that brings its norm into [1, 2); qinv[q] = 1 / scale.
@@ -1508,7 +1421,7 @@ __global__ __launch_bounds__(256) void corpus_to_f16_kernel(const float *X, int6
         for (int e = 0; e < 8; e++) v[e] = k0 + e < D ? (_Float16)(src[k0 + e] - center[k0 + e]) : (_Float16)0.f;
     } else if (k0 + 8 <= D && (D & 3) == 0) { // (rows are 16-B aligned when D % 4 == 0)
         const f32x4 *src = reinterpret_cast<const f32x4 *>(X + row * (int64_t)D + k0);
-        v = h_cvt8(src[0], src[1]);
+        v = cvt_f16x8(src[0], src[1]);
     } else { // the last block of a dimension that is not a multiple of 32 (zero beyond D), or unaligned rows
         const float *src = X + row * (int64_t)D;
 #pragma unroll

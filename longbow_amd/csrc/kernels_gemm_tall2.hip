@@ -33,10 +33,6 @@
 
 namespace lb {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ unsigned long long g_tall2_probe[8]; // diagnostic build, abl == 5: cycle stamps summed over waves
 
 namespace {
@@ -69,16 +65,10 @@ struct Tall2Args {
 // ds_read_b128 group (16 rows that are distinct mod 16, same chunk) over all 64 banks
 __device__ __forceinline__ int wswz(int row, int chunk) { return row * W_BK + ((chunk ^ ((row >> 1) & 7)) << 2); }
 
-// 16 B per lane straight into LDS (lane l lands at lds_addr + 16 l); default cache policy: the query rows are re-read by
-// every corpus tile, and a corpus line is shared by the query-tile workgroups that run side by side on the XCD
-__device__ __forceinline__ void w_dma16(const void *gsrc, uint32_t lds_addr)
-{
-    uint32_t save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(save) : "v"(gsrc), "s"(lds_addr) : "memory");
-}
-// the same under a wave-uniform EXEC mask (all ones or zero) set inside the asm: the request is part of every wave's
-// instruction stream but only the waves whose mask is set issue it.  (A wave-dependent BRANCH around the request -- or two
+// One LDS-DMA request, 16 B per lane (lane l lands at lds_addr + 16 l), under a wave-uniform EXEC mask (all ones or zero) set
+// inside the asm: the request is part of every wave's instruction stream but only the waves whose mask is set issue it.
+// Default cache policy: the query rows are re-read by every corpus tile, and a corpus line is shared by the query-tile
+// workgroups that run side by side on the XCD.  (A wave-dependent BRANCH around the request -- or two
 // copies of the loop -- keeps the accumulators from being promoted to registers: 380 "spills".)  No "memory" clobber: the
 // slot being filled is not touched by any compiler-visible access between the barriers that fence it.
 __device__ __forceinline__ void w_dma16_masked(const void *gsrc, uint32_t lds_addr, uint32_t mask32)
@@ -91,38 +81,6 @@ __device__ __forceinline__ void w_dma16_masked(const void *gsrc, uint32_t lds_ad
                  "s_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0\n\ts_mov_b64 exec, %1"
                  : "=&s"(save), "=&s"(sexec) : "v"(gsrc), "s"(lds_addr), "s"(mask32));
 }
-// Four requests behind ONE M0 write: the instruction offset moves the LDS destination (and the global address, which the
-// callers pre-compensate) by 1 KiB per request.  An M0 write behind a request has to wait until the vector-memory unit has
-// taken that request -- with one M0 value per request every request cost the wave its full acceptance time (~230 cycles
-// each by the in-kernel stamps), two M0 writes per stage let the four requests of a group queue back to back.
-__device__ __forceinline__ void w_dma16x4(const void *g0, const void *g1, const void *g2, const void *g3, uint32_t lds_addr)
-{
-    uint32_t save;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, off\n\t"
-                 "global_load_lds_dwordx4 %2, off offset:1024\n\t"
-                 "global_load_lds_dwordx4 %3, off offset:2048\n\t"
-                 "global_load_lds_dwordx4 %4, off offset:3072\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(save) : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(lds_addr) : "memory");
-}
-__device__ __forceinline__ void w_wait_vm0()
-{
-    __builtin_amdgcn_s_waitcnt((0 & 15) | (7 << 4) | (15 << 8) | ((0 >> 4) << 14));
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ void w_split8(const f32x4 x0, const f32x4 x1, bf16x8 &hi, bf16x8 &lo)
-{
-    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-    for (int i = 0; i < 8; i++) {
-        const __bf16 h = (__bf16)x[i];
-        hi[i] = h;
-        lo[i] = (__bf16)(x[i] - (float)h);
-    }
-}
-
 // LOADERS (compile time): 8 = every wave requests its share of the next stage, 4 = waves 0-3 request all of it (see the
 // DMA set-up in the kernel).
 // Tried on this kernel and dropped:
@@ -201,8 +159,8 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
         const uint32_t B = A + W_BM * W_BK * 4;
         if (LOADERS == 8) {
             const int k0 = kt * W_BK;
-            w_dma16x4(src[0] + k0, src[1] + k0, src[2] + k0, src[3] + k0, A + (uint32_t)(lw * RPW * W_BK * 4));
-            w_dma16x4(src[4] + k0, src[5] + k0, src[6] + k0, src[7] + k0, B + (uint32_t)(lw * RPW * W_BK * 4));
+            lds_dma16x4<false>(src[0] + k0, src[1] + k0, src[2] + k0, src[3] + k0, A + (uint32_t)(lw * RPW * W_BK * 4));
+            lds_dma16x4<false>(src[4] + k0, src[5] + k0, src[6] + k0, src[7] + k0, B + (uint32_t)(lw * RPW * W_BK * 4));
             return;
         }
 #pragma unroll
@@ -254,7 +212,7 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
         unsigned long long s0 = 0, s1 = 0, s2 = 0;
         if (probe) s0 = __builtin_amdgcn_s_memtime();
 #endif
-        w_wait_vm0();                 // this wave's part of stage kt has landed (issued one whole K-step ago)
+        wait_vmcnt<0>();                 // this wave's part of stage kt has landed (issued one whole K-step ago)
 #ifdef LB_DIAG
         if (probe) s1 = __builtin_amdgcn_s_memtime();
 #endif
@@ -295,7 +253,7 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
                 } else {
                     const f32x4 x0 = *reinterpret_cast<const f32x4 *>(&As[wswz(r, 4 * kb + 2 * h)]);
                     const f32x4 x1 = *reinterpret_cast<const f32x4 *>(&As[wswz(r, 4 * kb + 2 * h + 1)]);
-                    w_split8(x0, x1, ah[kb][tm], al[kb][tm]);
+                    split_bf16x8(x0, x1, ah[kb][tm], al[kb][tm]);
                 }
             }
         };

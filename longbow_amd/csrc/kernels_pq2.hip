@@ -23,8 +23,6 @@
 
 namespace lb {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
 // ---------------------------------------------------------------------------
 // Encode
 // ---------------------------------------------------------------------------

@@ -16,12 +16,11 @@
 // Also here: the sampled admission threshold (sample_scores_kernel, sample_tau_kernel,
 // sample_topm_kernel; see index.hip: sample_plan) that lets a search walk the corpus once.
 #include "lb_device.h"
+#include "lb_exact.h"
 
 #pragma clang fp contract(off)
 
 namespace lb {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SC_ROWS = 128;   // rows per tile == threads per workgroup
 constexpr int SC_DK = 64;      // floats per row per stage
@@ -44,34 +43,6 @@ struct ScanArgs {
     int aligned;
     int boot;
     int striped; // admissions go through cs.stripes (slot = position in the launch's slot list)
-};
-
-template <int ORDER>
-struct Acc {
-    float s[ORDER == ORDER_UNROLL4 ? 4 : 1];
-    __device__ __forceinline__ void zero()
-    {
-#pragma unroll
-        for (int i = 0; i < (ORDER == ORDER_UNROLL4 ? 4 : 1); i++) s[i] = 0.f;
-    }
-    // t = position within a group of 4 (compile-time); tail elements always use slot 0
-    template <int T>
-    __device__ __forceinline__ void add(float v)
-    {
-        if (ORDER == ORDER_UNROLL4) s[T] = s[T] + v;
-        else s[0] = s[0] + v;
-    }
-    __device__ __forceinline__ void add_tail(float v) { s[0] = s[0] + v; }
-    __device__ __forceinline__ float total() const
-    {
-        if (ORDER == ORDER_UNROLL4) {
-            float t = s[0] + s[1];
-            t = t + s[2];
-            t = t + s[3];
-            return t;
-        }
-        return s[0];
-    }
 };
 
 // MAPPED: positions [row_begin,row_end) index a.rowmap (the visible rows under a filter) instead of the corpus.
@@ -233,29 +204,10 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgs a)
 #pragma unroll 4
             for (int g = 0; g < nfull4; g++) {
                 const f32x4 xv = *reinterpret_cast<const f32x4 *>(&xr[g * 4]);
-                if (METRIC == METRIC_COS) {
-                    nb.template add<0>(xv.x * xv.x);
-                    nb.template add<1>(xv.y * xv.y);
-                    nb.template add<2>(xv.z * xv.z);
-                    nb.template add<3>(xv.w * xv.w);
-                }
+                if (METRIC == METRIC_COS) nb.add4_sq(xv);
 #pragma unroll
-                for (int j = 0; j < NQ; j++) {
-                    const f32x4 qv = *reinterpret_cast<const f32x4 *>(&lq[j * SC_DK + g * 4]);
-                    const float q0 = qv.x, q1 = qv.y, q2 = qv.z, q3 = qv.w;
-                    if (METRIC == METRIC_L2) {
-                        const float e0 = q0 - xv.x, e1 = q1 - xv.y, e2 = q2 - xv.z, e3 = q3 - xv.w;
-                        acc[j].template add<0>(e0 * e0);
-                        acc[j].template add<1>(e1 * e1);
-                        acc[j].template add<2>(e2 * e2);
-                        acc[j].template add<3>(e3 * e3);
-                    } else {
-                        acc[j].template add<0>(q0 * xv.x);
-                        acc[j].template add<1>(q1 * xv.y);
-                        acc[j].template add<2>(q2 * xv.z);
-                        acc[j].template add<3>(q3 * xv.w);
-                    }
-                }
+                for (int j = 0; j < NQ; j++)
+                    acc[j].template add4_pair<METRIC>(*reinterpret_cast<const f32x4 *>(&lq[j * SC_DK + g * 4]), xv);
             }
         }
         if (NBUF == 1) {
@@ -270,20 +222,7 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgs a)
 #pragma unroll
             for (int j = 0; j < NQ; j++) {
                 const float t = acc[j].total();
-                float dist;
-                if (METRIC == METRIC_L2) {
-                    dist = (float)sqrt((double)t);
-                } else if (METRIC == METRIC_COS) {
-                    const float na = a.qna[j < a.nsel ? j : 0];
-                    if (D == 0 || na == 0.0f || nbt == 0.0f) dist = 1.0f;
-                    else {
-                        const float den = (float)sqrt((double)na * (double)nbt);
-                        dist = 1.0f - __fdiv_rn(t, den);
-                    }
-                } else {
-                    dist = a.raw_dot ? t : -t;
-                }
-                pend_dist[j] = dist;
+                pend_dist[j] = exact_distance<METRIC>(t, nbt, METRIC == METRIC_COS ? a.qna[j < a.nsel ? j : 0] : 0.f, D, a.raw_dot);
             }
             pend_tile = tile;
         }
@@ -303,7 +242,6 @@ template <int METRIC, int ORDER>
 __global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a)
 {
     const int D = a.D;
-    const int dmain = D & ~3;
     for (int64_t pos = a.row_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < a.row_end;
          pos += (int64_t)gridDim.x * blockDim.x) {
         const int64_t row = a.rowmap ? (int64_t)a.rowmap[pos] : pos;
@@ -317,51 +255,9 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a)
         for (int j = 0; j < a.nsel; j++) {
             const int qj = a.qsel ? a.qsel[j] : j;
             const float *q = a.Q + (int64_t)qj * D;
-            Acc<ORDER> acc, nb;
-            acc.zero();
-            nb.zero();
-            for (int i = 0; i < dmain; i += 4) {
-                const float x0 = x[i], x1 = x[i + 1], x2 = x[i + 2], x3 = x[i + 3];
-                if (METRIC == METRIC_COS) {
-                    nb.template add<0>(x0 * x0);
-                    nb.template add<1>(x1 * x1);
-                    nb.template add<2>(x2 * x2);
-                    nb.template add<3>(x3 * x3);
-                }
-                if (METRIC == METRIC_L2) {
-                    const float e0 = q[i] - x0, e1 = q[i + 1] - x1, e2 = q[i + 2] - x2, e3 = q[i + 3] - x3;
-                    acc.template add<0>(e0 * e0);
-                    acc.template add<1>(e1 * e1);
-                    acc.template add<2>(e2 * e2);
-                    acc.template add<3>(e3 * e3);
-                } else {
-                    acc.template add<0>(q[i] * x0);
-                    acc.template add<1>(q[i + 1] * x1);
-                    acc.template add<2>(q[i + 2] * x2);
-                    acc.template add<3>(q[i + 3] * x3);
-                }
-            }
-            for (int i = dmain; i < D; i++) {
-                const float xv = x[i];
-                if (METRIC == METRIC_COS) nb.add_tail(xv * xv);
-                if (METRIC == METRIC_L2) {
-                    const float e = q[i] - xv;
-                    acc.add_tail(e * e);
-                } else {
-                    acc.add_tail(q[i] * xv);
-                }
-            }
-            const float t = acc.total();
-            float dist;
-            if (METRIC == METRIC_L2) {
-                dist = (float)sqrt((double)t);
-            } else if (METRIC == METRIC_COS) {
-                const float na = a.qna[j], nbt = nb.total();
-                if (D == 0 || na == 0.0f || nbt == 0.0f) dist = 1.0f;
-                else dist = 1.0f - __fdiv_rn(t, (float)sqrt((double)na * (double)nbt));
-            } else {
-                dist = a.raw_dot ? t : -t;
-            }
+            float t, nbt;
+            exact_pair_sums<METRIC, ORDER>(x, q, D, t, nbt);
+            const float dist = exact_distance<METRIC>(t, nbt, METRIC == METRIC_COS ? a.qna[j] : 0.f, D, a.raw_dot);
             if (a.all_out) {
                 a.all_out[(int64_t)j * a.ld + pos] = dist; // indexed by position (== row without a row map)
             } else {
@@ -397,19 +293,7 @@ __global__ __launch_bounds__(64) void query_norms_kernel(const float *Q, const i
     for (int i = threadIdx.x; i < Dpad; i += 64) sq[i] = i < D ? q[i] : 0.f;
     __syncthreads();
     if (threadIdx.x != 0) return;
-    Acc<ORDER> a;
-    a.zero();
-    const int dmain = D & ~3;
-#pragma unroll 8
-    for (int i = 0; i < dmain; i += 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(&sq[i]);
-        a.template add<0>(v.x * v.x);
-        a.template add<1>(v.y * v.y);
-        a.template add<2>(v.z * v.z);
-        a.template add<3>(v.w * v.w);
-    }
-    for (int i = dmain; i < D; i++) a.add_tail(sq[i] * sq[i]);
-    qna[j] = a.total();
+    qna[j] = exact_sq_norm_lds<ORDER>(sq, D);
 }
 
 void launch_query_norms(int order, const float *Q, const int *qsel, int nsel, int D, float *qna,
@@ -470,24 +354,6 @@ __device__ __forceinline__ float wave_sum(float v)
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
     return v;
-}
-
-template <int ORDER>
-__device__ __forceinline__ float exact_sq_norm_lds(const float *sq, int D)
-{
-    Acc<ORDER> a;
-    a.zero();
-    const int dmain = D & ~3;
-#pragma unroll 8
-    for (int i = 0; i < dmain; i += 4) {
-        const f32x4 v = *reinterpret_cast<const f32x4 *>(&sq[i]);
-        a.template add<0>(v.x * v.x);
-        a.template add<1>(v.y * v.y);
-        a.template add<2>(v.z * v.z);
-        a.template add<3>(v.w * v.w);
-    }
-    for (int i = dmain; i < D; i++) a.add_tail(sq[i] * sq[i]);
-    return a.total();
 }
 
 // Everything a batched search over the fp16 route needs from its queries, in one launch (one wave per query): the fp16
@@ -569,7 +435,7 @@ __device__ __forceinline__ void query_prep_body(const float *Q, int nq, int D, _
         }
         if (reset == 3) cs.tau[q] = 0ull; // "not out yet": the candidate launch computes the thresholds itself (TAUIN)
         if (reset == 1 || reset == 2) cs.flags[q] = 0;
-        if (qna) qna[q] = order == ORDER_UNROLL4 ? exact_sq_norm_lds<ORDER_UNROLL4>(sq, D) : exact_sq_norm_lds<ORDER_SEQ>(sq, D);
+        if (qna) qna[q] = exact_sq_norm_lds(sq, D, order);
     }
 }
 
@@ -741,7 +607,7 @@ __global__ __launch_bounds__(256) void sample_scores_kernel(SampleArgs a)
         for (int i = threadIdx.x; i < Dpad; i += 256) sq[i] = i < a.D ? q[i] : 0.f;
         __syncthreads();
         if (threadIdx.x == 0)
-            a.qna[j] = a.order == ORDER_UNROLL4 ? exact_sq_norm_lds<ORDER_UNROLL4>(sq, a.D) : exact_sq_norm_lds<ORDER_SEQ>(sq, a.D);
+            a.qna[j] = exact_sq_norm_lds(sq, a.D, a.order);
         return;
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -886,7 +752,7 @@ __global__ __launch_bounds__(ST_THREADS) void sample_tau_kernel(CandState cs, co
         cs.tau[q] = kth;
         cs.cnt[q] = 0;
     }
-    if (qna && tid == 64) qna[blockIdx.x] = order == ORDER_UNROLL4 ? exact_sq_norm_lds<ORDER_UNROLL4>(sq, D) : exact_sq_norm_lds<ORDER_SEQ>(sq, D);
+    if (qna && tid == 64) qna[blockIdx.x] = exact_sq_norm_lds(sq, D, order);
     if (zero_stripes && tid < LB_STRIPES) cs.stripes[(blockIdx.x * LB_STRIPES + tid) * LB_STRIPE_PAD] = 0;
 }
 

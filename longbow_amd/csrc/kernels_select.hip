@@ -49,14 +49,6 @@ static void allow_big_lds(K kernel, size_t bytes)
 //               entries are compacted and only those kc are sorted.
 // LDS: entries u64[P] | hist u32[256] | wave sums u32[4] | scalars
 // lane permutes on the DPP path (no LDS round trip): OR / AND of a u64 over the 64 lanes, result in lane 63
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint64_t dpp_u64(uint64_t v)
-{
-    const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
-    const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
-    const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    return ((uint64_t)(uint32_t)ohi << 32) | (uint64_t)(uint32_t)olo;
-}
 __device__ __forceinline__ void wave_or_and_u64(uint64_t &o, uint64_t &a)
 {
 #define LB_STEP(CTRL, RM)                 \

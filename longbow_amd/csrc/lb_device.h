@@ -107,14 +107,108 @@ constexpr int LB_STRIPES = 16;
 constexpr int LB_STRIPE_PAD = 32; // u32 words between counters (128 B)
 
 #ifdef __HIPCC__
-// u64 minimum over lanes on the DPP path (no LDS round trips); shared by the threshold kernels
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// ---- LDS-DMA (global_load_lds_dwordx4: 16 B per lane straight into LDS at M0 + 16 lane) -----------------------------
+// Several requests behind ONE M0 write: the instruction offset moves the LDS destination and the global address alike by
+// 1 KiB per request (the callers pre-compensate the sources).  An M0 write behind a request has to wait until the
+// vector-memory unit has taken that request -- with one M0 value per request every request cost the wave its full acceptance
+// time, one M0 write per group lets the requests of a group queue back to back.
+// NT: non-temporal (a corpus line that only this workgroup will read).  These carry a "memory" clobber.
+template <bool NT>
+__device__ __forceinline__ void lds_dma16x4(const void *g0, const void *g1, const void *g2, const void *g3, uint32_t lds_addr)
+{
+    uint32_t save;
+    if (NT)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, off nt\n\t"
+                     "global_load_lds_dwordx4 %2, off offset:1024 nt\n\t"
+                     "global_load_lds_dwordx4 %3, off offset:2048 nt\n\t"
+                     "global_load_lds_dwordx4 %4, off offset:3072 nt\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(save) : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(lds_addr) : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %5\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, off\n\t"
+                     "global_load_lds_dwordx4 %2, off offset:1024\n\t"
+                     "global_load_lds_dwordx4 %3, off offset:2048\n\t"
+                     "global_load_lds_dwordx4 %4, off offset:3072\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(save) : "v"(g0), "v"(g1), "v"(g2), "v"(g3), "s"(lds_addr) : "memory");
+}
+__device__ __forceinline__ void lds_dma16x2(const void *g0, const void *g1, uint32_t lds_addr)
+{
+    uint32_t save;
+    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
+                 "global_load_lds_dwordx4 %1, off\n\t"
+                 "global_load_lds_dwordx4 %2, off offset:1024\n\t"
+                 "s_mov_b32 m0, %0"
+                 : "=&s"(save) : "v"(g0), "v"(g1), "s"(lds_addr) : "memory");
+}
+// ONE request, WITHOUT a "memory" clobber (requests issued one at a time between the MFMAs of a step: a clobber there changes
+// how the compiler schedules those register-heavy loops; the slot being filled is fenced by barriers)
+template <bool NT>
+__device__ __forceinline__ void lds_dma16_noclobber(const void *g, uint32_t lds_addr)
+{
+    uint32_t save;
+    if (NT)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, off nt\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(save) : "v"(g), "s"(lds_addr));
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+                     "global_load_lds_dwordx4 %1, off\n\t"
+                     "s_mov_b32 m0, %0"
+                     : "=&s"(save) : "v"(g), "s"(lds_addr));
+}
+// wait until at most N vector-memory requests of this wave are outstanding (LDS-DMA requests are not tracked by the compiler)
+template <int N>
+__device__ __forceinline__ void wait_vmcnt()
+{
+    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
+    asm volatile("" ::: "memory");
+}
+
+// ---- conversions ------------------------------------------------------------------------------------------------------
+// x (8 consecutive f32 of one row) -> hi = bf16(x) (round to nearest even), lo = bf16(x - hi): x = hi + lo + O(2^-18 |x|).
+// The corpus's split image (kernels_gemm.hip: split_bf16_kernel) and the in-register splits of the candidate kernels are
+// this one function, so that they give the same bits.
+__device__ __forceinline__ void split_bf16x8(const f32x4 x0, const f32x4 x1, bf16x8 &hi, bf16x8 &lo)
+{
+    const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        const __bf16 h = (__bf16)x[i];
+        hi[i] = h;
+        lo[i] = (__bf16)(x[i] - (float)h);
+    }
+}
+__device__ __forceinline__ f16x8 cvt_f16x8(const f32x4 x0, const f32x4 x1)
+{
+    f16x8 r; // round to nearest even (v_cvt_f16_f32 under the default rounding mode)
+    r[0] = (_Float16)x0.x; r[1] = (_Float16)x0.y; r[2] = (_Float16)x0.z; r[3] = (_Float16)x0.w;
+    r[4] = (_Float16)x1.x; r[5] = (_Float16)x1.y; r[6] = (_Float16)x1.z; r[7] = (_Float16)x1.w;
+    return r;
+}
+
+// ---- lane moves on the DPP path (no LDS round trips) ------------------------------------------------------------------
 template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ uint64_t min_dpp_u64(uint64_t v)
+__device__ __forceinline__ uint64_t dpp_u64(uint64_t v)
 {
     const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
     const int olo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROW_MASK, 0xf, false);
     const int ohi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROW_MASK, 0xf, false);
-    const uint64_t o = ((uint64_t)(uint32_t)ohi << 32) | (uint64_t)(uint32_t)olo;
+    return ((uint64_t)(uint32_t)ohi << 32) | (uint64_t)(uint32_t)olo;
+}
+// u64 minimum over lanes; shared by the threshold kernels
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint64_t min_dpp_u64(uint64_t v)
+{
+    const uint64_t o = dpp_u64<CTRL, ROW_MASK>(v);
     return o < v ? o : v;
 }
 // minimum over each row of 16 lanes, left in every lane of the row

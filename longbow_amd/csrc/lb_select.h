@@ -2,13 +2,7 @@
 #pragma once
 #include "lb_device.h"
 
-// every f32 operation of the exact re-rank is one IEEE rounding, as the Go source spells it: no FMA contraction in the
-// helpers below nor in the files that include them
-#pragma clang fp contract(off)
-
 namespace lb {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int SEL_THREADS = 256;
 
@@ -47,35 +41,5 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v, int lane)
     }
     return v;
 }
-
-
-// exact-order accumulators (same as kernels_scan.hip)
-template <int ORDER>
-struct AccR {
-    float s[ORDER == ORDER_UNROLL4 ? 4 : 1];
-    __device__ __forceinline__ void zero()
-    {
-#pragma unroll
-        for (int i = 0; i < (ORDER == ORDER_UNROLL4 ? 4 : 1); i++) s[i] = 0.f;
-    }
-    template <int T>
-    __device__ __forceinline__ void add(float v)
-    {
-        if (ORDER == ORDER_UNROLL4) s[T] = s[T] + v;
-        else s[0] = s[0] + v;
-    }
-    __device__ __forceinline__ void add_tail(float v) { s[0] = s[0] + v; }
-    __device__ __forceinline__ float total() const
-    {
-        if (ORDER == ORDER_UNROLL4) {
-            float t = s[0] + s[1];
-            t = t + s[2];
-            t = t + s[3];
-            return t;
-        }
-        return s[0];
-    }
-};
-
 
 } // namespace lb

@@ -544,6 +544,29 @@ def test_fused_sample_launch_and_its_give_up_path(oracle):
         idx.Close()
 
 
+@pytest.mark.parametrize("order", [0, 1])
+def test_fused_sample_launch_cosine_norms_in_both_orders(oracle, order):
+    """cosine on the fused launch (5-32 queries, >= 131,072 rows, D % 32 == 0, a threshold rank <= 32, no fp16 image): its
+    threshold workgroups compute the exact ||q||^2 the re-rank divides by, in the requested accumulation order"""
+    gpu_or_skip()
+    rng = np.random.default_rng(131 + order)
+    n, d, k = 150_000, 64, 10
+    X = rng.standard_normal((n, d)).astype(F)
+    Q = np.ascontiguousarray(X[rng.integers(0, n, 32)] + rng.standard_normal((32, d)).astype(F) * F(0.3))
+    idx = new_index(d, 1, order)
+    idx.set_f16_image(0)
+    idx.Add(None, X)
+    for nq in (5, 9, 32):
+        oi, od = oracle.search_batch(1, Q[:nq], X, k, order=order, nthreads=8)
+        lab, dist = idx.SearchBatch(Q[:nq], k)
+        ctx = f"order={order} nq={nq} route {idx.last_route}"
+        assert idx.last_route[:2] in ((1, 2), (2, 2)), ctx  # a narrow tile on operands split in registers: the fused form
+        assert idx.last_fallbacks == 0, ctx
+        assert idx.fused_giveups == 0, ctx
+        assert_same(lab, dist, oi, od, ctx)
+    idx.Close()
+
+
 def test_growth_survives_a_refused_mapping(oracle):
     """the corpus grows in place through the virtual-memory API; when the driver refuses to extend the mapping
     (forced here) the rows move once into a hipMalloc buffer and the index keeps working, ids and all"""

@@ -12,8 +12,11 @@ pytestmark = pytest.mark.gpu
 F = np.float32
 
 
+@pytest.mark.parametrize("order", [0, 1])
 @pytest.mark.parametrize("metric", [0, 1, 2])
-def test_batches_whose_candidate_launch_computes_its_thresholds(oracle, metric):
+def test_batches_whose_candidate_launch_computes_its_thresholds(oracle, metric, order):
+    """order: the reference's accumulation order (SEQ / UNROLL4) -- under cosine the duty workgroups compute the exact ||q||^2
+    the re-rank divides by, in that order"""
     gpu_or_skip()
     rng = np.random.default_rng(77 + metric)
     n, d, k = 300_000, 256, 20
@@ -21,24 +24,24 @@ def test_batches_whose_candidate_launch_computes_its_thresholds(oracle, metric):
     if metric == 0:
         X += F(3.0)  # (a common offset: the centred image)
     Q = np.ascontiguousarray(X[rng.integers(0, n, 128)] + rng.standard_normal((128, d)).astype(F) * F(0.3))
-    idx = new_index(d, metric)
+    idx = new_index(d, metric, order)
     idx.Add(None, X)
     mask = (rng.random(n) < 0.5).astype(np.uint8)
     visible = np.flatnonzero(mask)
     for filtered in (False, True):
         idx.set_filter(mask if filtered else None)
         Xo = X[visible] if filtered else X
-        oi, od = oracle.search_batch(metric, Q[:6], Xo, k, nthreads=8)
+        oi, od = oracle.search_batch(metric, Q[:6], Xo, k, order=order, nthreads=8)
         if filtered:
             oi = np.where(oi >= 0, visible[np.clip(oi, 0, visible.size - 1)], -1)
         whole = idx.SearchBatch(Q, k)
-        assert idx.last_fallbacks == 0, (metric, filtered, idx.last_fallbacks)
+        assert idx.last_fallbacks == 0, (metric, order, filtered, idx.last_fallbacks)
         assert idx.fused_giveups == 0
-        assert_same(whole[0][:6], whole[1][:6], oi, od, f"metric {metric} filtered {filtered} nq 128 route {idx.last_route}")
+        assert_same(whole[0][:6], whole[1][:6], oi, od, f"metric {metric} order {order} filtered {filtered} nq 128 route {idx.last_route}")
         for nq in (1, 7, 8, 9, 33, 64, 65, 127):
             lab, dist = idx.SearchBatch(Q[:nq], k)
-            assert_same(lab, dist, whole[0][:nq], whole[1][:nq], f"metric {metric} filtered {filtered} nq {nq} route {idx.last_route}")
-            assert idx.last_fallbacks == 0, (metric, filtered, nq, idx.last_fallbacks)
+            assert_same(lab, dist, whole[0][:nq], whole[1][:nq], f"metric {metric} order {order} filtered {filtered} nq {nq} route {idx.last_route}")
+            assert idx.last_fallbacks == 0, (metric, order, filtered, nq, idx.last_fallbacks)
     idx.Close()
 
 
