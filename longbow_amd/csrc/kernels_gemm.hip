@@ -12,7 +12,8 @@
 // line per row per step), 4 waves (2x2), each wave 64x64 = 2x2 MFMA 32x32 tiles.
 // LDS: [128][32] f32 per operand per stage, 16-B chunks XOR-swizzled by
 // (row>>1)&7 so the ds_read_b128 fragment reads are bank-conflict free.
-#include "lb_device.h"
+// Candidate keys, thresholds, the tile's side inputs and the admission rule: lb_admit.h.
+#include "lb_admit.h"
 
 #include <cstdlib>
 
@@ -182,18 +183,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
     if (GLDS) glds_stage(0, 0);
     // one burst behind the DMA: side inputs of tile row (tid & 127) and this lane's two thresholds; nothing
     // is consumed before every load has been issued
-    const float side_aux = METRIC == METRIC_L2 ? a.norm2[side_ri] : (METRIC == METRIC_COS ? a.rnorm[side_ri] : 0.f);
+    const float aux_r = side_aux<METRIC>(a.norm2, a.rnorm, side_ri);
     uint8_t side_vis = 1;
     if (a.mask) side_vis = a.mask[side_ri];
     uint64_t tau_raw[2];
 #pragma unroll
     for (int tn = 0; tn < 2; tn++) {
         const int qj = q0 + wc * 64 + tn * 32 + l31;
-        tau_raw[tn] = a.boot ? 0ull : a.cs.tau[qj < a.nq ? qj : a.nq - 1];
-        if (qj >= a.nq) tau_raw[tn] = 0ull;
+        tau_raw[tn] = lane_tau(a.cs.tau, qj, a.nq, a.boot);
     }
     if (tid < BM) {
-        s_aux[tid] = side_aux;
+        s_aux[tid] = aux_r;
         s_vis[tid] = (row0 + tid <= last_row && side_vis) ? (uint8_t)1 : (uint8_t)0;
         s_rowid[tid] = (uint32_t)side_ri;
     }
@@ -377,22 +377,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
 #pragma unroll
     for (int tm = 0; tm < 2; tm++)
 #pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const int lr = wr * 64 + tm * 32 + 8 * g + 4 * h; // 4 consecutive local rows
-            const f32x4 av = *reinterpret_cast<const f32x4 *>(&s_aux[lr]);
-            const uint4 rv = *reinterpret_cast<const uint4 *>(&s_rowid[lr]);
-            rid[tm][g][0] = rv.x; rid[tm][g][1] = rv.y; rid[tm][g][2] = rv.z; rid[tm][g][3] = rv.w;
-            const uint32_t vv = *reinterpret_cast<const uint32_t *>(&s_vis[lr]); // 4 bytes of 0/1
-            aux[tm][g][0] = av.x; aux[tm][g][1] = av.y; aux[tm][g][2] = av.z; aux[tm][g][3] = av.w;
-            // gather the four 0/1 bytes into 4 adjacent bits
-            const uint32_t nib = (vv & 1u) | ((vv >> 7) & 2u) | ((vv >> 14) & 4u) | ((vv >> 21) & 8u);
-            vbits |= nib << (tm * 16 + g * 4);
-        }
-    auto key_of = [&](float dot, float ax) -> float {
-        if (METRIC == METRIC_L2) return fmaf(-2.0f, dot, ax);
-        if (METRIC == METRIC_COS) return -dot * ax;
-        return -dot;
-    };
+        for (int g = 0; g < 4; g++) // 4 consecutive local rows
+            vbits |= tile_rows4(s_aux, s_rowid, s_vis, wr * 64 + tm * 32 + 8 * g + 4 * h, aux[tm][g], rid[tm][g]) << (tm * 16 + g * 4);
 #pragma unroll
     for (int tn = 0; tn < 2; tn++) {
         const int qj = q0 + wc * 64 + tn * 32 + l31;
@@ -410,9 +396,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
                         uint64_t ent[4];
 #pragma unroll
                         for (int e = 0; e < 4; e++)
-                            ent[e] = ((vbits >> (tm * 16 + g * 4 + e)) & 1u)
-                                         ? pack_entry(key_of(acc[tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e])
-                                         : kEntryMax;
+                            ent[e] = ((vbits >> (tm * 16 + g * 4 + e)) & 1u) ? pack_entry(cand_key<METRIC>(acc[tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e]) : kEntryMax;
                         uint64_t *dst = list + (rbase - a.row_begin);
                         if (rbase + 3 < a.row_end) {
                             typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
@@ -428,24 +412,16 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
             }
             continue;
         }
-        // pass 1 (branch-free): which of this lane's 32 elements pass the admission test
-        //   entry < tau  <=>  key < tau_key, or equal keys and a lower row
-        // (float compares treat -0 == +0, matching the +0-canonical packed keys; tau of an
-        //  out-of-range query decodes to NaN, so nothing passes).
-        const float tk = tau_key[tn];
-        const uint32_t tr = tau_row[tn];
+        // pass 1 (branch-free): which of this lane's 32 elements pass the admission test (lb_admit.h:
+        // exact rule; tau of an out-of-range query decodes to NaN, so nothing passes)
         uint32_t bits = 0;
 #pragma unroll
         for (int tm = 0; tm < 2; tm++)
 #pragma unroll
             for (int g = 0; g < 4; g++)
 #pragma unroll
-                for (int e = 0; e < 4; e++) {
-                    const float key = key_of(acc[tm][tn][4 * g + e], aux[tm][g][e]);
-                    const uint32_t ri = rid[tm][g][e];
-                    const uint32_t lt = (uint32_t)(key < tk) | ((uint32_t)(key == tk) & (uint32_t)(ri < tr));
-                    bits |= lt << (tm * 16 + g * 4 + e);
-                }
+                for (int e = 0; e < 4; e++)
+                    bits |= admit_exact(cand_key<METRIC>(acc[tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e], tau_key[tn], tau_row[tn]) << (tm * 16 + g * 4 + e);
         bits &= vbits;
         if (ABL == 7) { asm volatile("" ::"v"(bits)); continue; }
         // ONE returning atomic per lane reserves the slots; the stores are fire-and-forget
@@ -456,14 +432,12 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
 #pragma unroll
                 for (int g = 0; g < 4; g++)
 #pragma unroll
-                    for (int e = 0; e < 4; e++) {
+                    for (int e = 0; e < 4; e++)
                         if (bits & (1u << (tm * 16 + g * 4 + e))) {
                             const uint32_t ri = rid[tm][g][e];
-                            if (pos < a.cs.cap)
-                                list[pos] = pack_entry(key_of(acc[tm][tn][4 * g + e], aux[tm][g][e]), ri);
+                            if (pos < a.cs.cap) list[pos] = pack_entry(cand_key<METRIC>(acc[tm][tn][4 * g + e], aux[tm][g][e]), ri);
                             pos++;
                         }
-                    }
         }
     }
     if (ABL == 5) {

@@ -20,7 +20,7 @@
 // registers: the default) and over FUSED (5..32 queries: the sampled threshold of the search rides
 // inside the launch -- sample tiles, per-query threshold workgroups, corpus workgroups of two row
 // tiles that pick the thresholds up; see FusedSample in lb_device.h and LABNOTES.md 3.3).
-#include "lb_device.h"
+#include "lb_admit.h"
 #include "lb_exact.h"
 
 namespace lb {
@@ -146,8 +146,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
 #pragma unroll
     for (int tn = 0; tn < TN; tn++) {
         const int qj = q0 + tn * 32 + l31;
-        uint64_t tau = (boot || FUSED) ? 0ull : a.cs.tau[qj < a.nq ? qj : a.nq - 1]; // (FUSED: fetched after the loops)
-        if (qj >= a.nq) tau = 0ull;
+        const uint64_t tau = lane_tau(a.cs.tau, qj, a.nq, boot || FUSED); // (FUSED: fetched after the loops)
         tk[tn] = tau_key_of(tau);
         tr[tn] = entry_row(tau);
     }
@@ -185,11 +184,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
         if (tp >= ntiles_here) continue; // (workgroup-uniform)
         const int64_t row0 = row_begin + (int64_t)(rt_first + tp) * NBM;
         const int64_t side_ri = corpus_row(row0 + (tid & (NBM - 1)));
-        const float side_aux = METRIC == METRIC_L2 ? a.norm2[side_ri] : (METRIC == METRIC_COS ? a.rnorm[side_ri] : 0.f);
+        const float aux_r = side_aux<METRIC>(a.norm2, a.rnorm, side_ri);
         uint8_t side_vis = 1;
         if (a.mask) side_vis = a.mask[side_ri];
         if (tid < NBM) {
-            s_aux[tp * NBM + tid] = side_aux;
+            s_aux[tp * NBM + tid] = aux_r;
             s_vis[tp * NBM + tid] = (row0 + tid <= last_row && side_vis) ? (uint8_t)1 : (uint8_t)0;
             s_rowid[tp * NBM + tid] = (uint32_t)side_ri;
         }
@@ -286,17 +285,10 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
     }
 
     // workgroup-local admission list (every non-bootstrap launch), carved from the (now free) stages behind s_tau
-    constexpr int FL_CAP = 2048;
-    uint32_t *s_lcnt = reinterpret_cast<uint32_t *>(lds_all) + 256;     // entries in the list
-    uint32_t *s_qcnt = s_lcnt + 1;                                      // [NBN] of them per query of the tile ...
-    uint32_t *s_qbase = s_qcnt + NBN;                                   // [NBN] ... and where they start in the query's list
-    uint64_t *s_lent = reinterpret_cast<uint64_t *>(lds_all + 512);
-    uint16_t *s_lq = reinterpret_cast<uint16_t *>(lds_all + 512 + 2 * FL_CAP);
-    uint16_t *s_lr = s_lq + FL_CAP;                                     // rank of the entry among its query's
+    const LocalList<2048, NBN, NTHREADS> fl(reinterpret_cast<uint32_t *>(lds_all) + 256, reinterpret_cast<uint64_t *>(lds_all + 512));
     if (FUSED && !is_sample) { // thresholds published by the sample workgroups of this launch
         uint64_t *s_tau = reinterpret_cast<uint64_t *>(lds_all); // (the stages are free: the loops ended with a barrier)
-        if (tid == 0) *s_lcnt = 0;
-        if (tid < NBN) s_qcnt[tid] = 0;
+        fl.reset(tid);
 #ifdef LB_DIAG
         const unsigned long long w0 = __builtin_amdgcn_s_memrealtime();
         if (tid == 0) {
@@ -337,17 +329,11 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
             tr[tn] = entry_row(tau);
         }
     } else if (!boot) {
-        if (tid == 0) *s_lcnt = 0;
-        if (tid < NBN) s_qcnt[tid] = 0;
+        fl.reset(tid);
         __syncthreads();
     }
 
     // ---- epilogue (as in gemm_filter_kernel), one row tile after the other --------------------------
-    auto key_of = [&](float dot, float ax) -> float {
-        if (METRIC == METRIC_L2) return fmaf(-2.0f, dot, ax);
-        if (METRIC == METRIC_COS) return -dot * ax;
-        return -dot;
-    };
 #pragma unroll
     for (int tp = 0; tp < TPW; tp++) {
         if (tp >= ntiles_here) continue;
@@ -358,16 +344,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
 #pragma unroll
         for (int tm = 0; tm < TM; tm++)
 #pragma unroll
-            for (int g = 0; g < 4; g++) {
-                const int lr = tp * NBM + wave * WROWS + tm * 32 + 8 * g + 4 * h;
-                const f32x4 av = *reinterpret_cast<const f32x4 *>(&s_aux[lr]);
-                const uint4 rv = *reinterpret_cast<const uint4 *>(&s_rowid[lr]);
-                rid[tm][g][0] = rv.x; rid[tm][g][1] = rv.y; rid[tm][g][2] = rv.z; rid[tm][g][3] = rv.w;
-                const uint32_t vv = *reinterpret_cast<const uint32_t *>(&s_vis[lr]);
-                aux[tm][g][0] = av.x; aux[tm][g][1] = av.y; aux[tm][g][2] = av.z; aux[tm][g][3] = av.w;
-                const uint32_t nib = (vv & 1u) | ((vv >> 7) & 2u) | ((vv >> 14) & 4u) | ((vv >> 21) & 8u);
-                vbits |= nib << (tm * 16 + g * 4);
-            }
+            for (int g = 0; g < 4; g++)
+                vbits |= tile_rows4(s_aux, s_rowid, s_vis, tp * NBM + wave * WROWS + tm * 32 + 8 * g + 4 * h, aux[tm][g], rid[tm][g])
+                         << (tm * 16 + g * 4);
 #pragma unroll
         for (int tn = 0; tn < TN; tn++) {
             const int qj = q0 + tn * 32 + l31;
@@ -384,7 +363,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
                             for (int e = 0; e < 4; e++)
                                 if (rbase + e < row_end) {
                                     const uint64_t ent = ((vbits >> (tm * 16 + g * 4 + e)) & 1u)
-                                                             ? pack_entry(key_of(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e])
+                                                             ? pack_entry(cand_key<METRIC>(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e])
                                                              : kEntryMax;
                                     if (FUSED) // read by another workgroup of this launch: device-scope store
                                         __hip_atomic_store(&list[rbase + e - row_begin], ent, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -401,21 +380,18 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
 #pragma unroll
                 for (int g = 0; g < 4; g++)
 #pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const float key = key_of(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]);
-                        const uint32_t ri = rid[tm][g][e];
-                        const uint32_t lt = (uint32_t)(key < tk[tn]) | ((uint32_t)(key == tk[tn]) & (uint32_t)(ri < tr[tn]));
-                        bits |= lt << (tm * 16 + g * 4 + e);
-                    }
+                    for (int e = 0; e < 4; e++)
+                        bits |= admit_exact(cand_key<METRIC>(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e], tk[tn], tr[tn])
+                                << (tm * 16 + g * 4 + e);
             bits &= vbits; // out-of-range rows and queries never pass (tau of a padded query decodes to NaN)
             if (bits) {
                 // admissions go to a workgroup-local list first (one LDS atomic per lane) and out to the per-query lists
                 // at the very end, every entry's returning global atomic in flight at once: at 32 queries a wave otherwise
                 // sits through ~7 of those round trips, one after the other, per pair of tiles
                 const uint32_t n = (uint32_t)__builtin_popcount(bits);
-                uint32_t lp = atomicAdd(s_lcnt, n);
-                if (lp + n <= (uint32_t)FL_CAP) {
-                    uint32_t lr = atomicAdd(&s_qcnt[qj - q0], n);
+                uint32_t lp = atomicAdd(fl.cnt, n);
+                if (lp + n <= (uint32_t)fl.CAP) {
+                    uint32_t lr = atomicAdd(&fl.qcnt[qj - q0], n);
 #pragma unroll
                     for (int tm = 0; tm < TM; tm++)
 #pragma unroll
@@ -423,15 +399,15 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
 #pragma unroll
                             for (int e = 0; e < 4; e++)
                                 if (bits & (1u << (tm * 16 + g * 4 + e))) {
-                                    s_lent[lp] = pack_entry(key_of(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e]);
-                                    s_lq[lp] = (uint16_t)(qj - q0);
-                                    s_lr[lp] = (uint16_t)lr;
+                                    fl.ent[lp] = pack_entry(cand_key<METRIC>(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e]);
+                                    fl.q[lp] = (uint16_t)(qj - q0);
+                                    fl.rk[lp] = (uint16_t)lr;
                                     lp++;
                                     lr++;
                                 }
                     bits = 0; // done
                 } else {
-                    for (uint32_t i = lp; i < lp + n && i < (uint32_t)FL_CAP; i++) s_lent[i] = kEntryMax; // reserved, unused
+                    fl.reserved_unused(lp, n);
                 }
             }
             if (bits) {
@@ -444,27 +420,14 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
                         for (int e = 0; e < 4; e++)
                             if (bits & (1u << (tm * 16 + g * 4 + e))) {
                                 const uint32_t ri = rid[tm][g][e];
-                                if (pos < a.cs.cap) list[pos] = pack_entry(key_of(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]), ri);
+                                if (pos < a.cs.cap) list[pos] = pack_entry(cand_key<METRIC>(acc[tp][tm][tn][4 * g + e], aux[tm][g][e]), ri);
                                 pos++;
                             }
             }
         }
     }
     if (!boot) { // flush the workgroup-local admissions: ONE returning global atomic per query of the tile, all in flight
-        __syncthreads();
-        if (tid < NBN) {
-            const uint32_t n = s_qcnt[tid];
-            s_qbase[tid] = n ? atomicAdd(&a.cs.cnt[q0 + tid], n) : 0u; // (n != 0 implies a real query)
-        }
-        __syncthreads();
-        const uint32_t total = *s_lcnt < (uint32_t)FL_CAP ? *s_lcnt : (uint32_t)FL_CAP;
-        for (uint32_t i = tid; i < total; i += NTHREADS) {
-            const uint64_t ent = s_lent[i];
-            if (ent == kEntryMax) continue;
-            const int ql = (int)s_lq[i];
-            const uint32_t pos = s_qbase[ql] + (uint32_t)s_lr[i];
-            if (pos < a.cs.cap) a.cs.lists[(size_t)(q0 + ql) * a.cs.cap + pos] = ent;
-        }
+        fl.flush(tid, a.cs, q0);
         return;
     }
     if (!is_sample) return;

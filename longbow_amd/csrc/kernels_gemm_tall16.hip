@@ -32,7 +32,7 @@
 //   gemm_filter_tall16_kernel    one workgroup per tile, f32 rows through a row map / mask: filtered searches, and batches
 //                                with more query tiles than an XCD has workgroup slots
 // What each design decision bought is in LABNOTES.md 4.2 (measured with tools/experiments/dma_patterns.hip).
-#include "lb_device.h"
+#include "lb_admit.h"
 #include "lb_exact.h"
 
 #include <type_traits>
@@ -228,7 +228,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
     issue(0);
     if (nk > 1) issue(1);
     // one burst behind the first stages (not needed before the epilogue): side inputs, thresholds, query scales
-    const float side_aux = METRIC == METRIC_L2 ? a.norm2[side_ri] : (METRIC == METRIC_COS ? a.rnorm[side_ri] : 0.f);
+    const float aux_r = side_aux<METRIC>(a.norm2, a.rnorm, side_ri);
     uint8_t side_vis = 1;
     if (a.mask) side_vis = a.mask[side_ri];
     float tk[4], qs[4];
@@ -236,13 +236,11 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
     for (int tn = 0; tn < 4; tn++) {
         const int qj = q0 + wc * 128 + tn * 32 + l31;
         const int qc = qj < a.nq ? qj : a.nq - 1;
-        uint64_t tau = a.boot ? 0ull : a.cs.tau[qc];
-        if (qj >= a.nq) tau = 0ull;
-        tk[tn] = tau_key_of(tau);
+        tk[tn] = tau_key_of(lane_tau(a.cs.tau, qj, a.nq, a.boot));
         qs[tn] = a.qinv[qc];
     }
     if (tid < H_BM) {
-        s_aux[tid] = side_aux;
+        s_aux[tid] = aux_r;
         s_vis[tid] = (row0 + tid <= last_row && side_vis) ? (uint8_t)1 : (uint8_t)0;
         s_rowid[tid] = (uint32_t)side_ri;
     }
@@ -321,26 +319,12 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
 
     // ---- epilogue: key + admission, one MFMA row tile (this lane's 16 rows of it) at a time ----------------
     // C layout (32x32): col = lane & 31 (query), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
-    // dot = acc * qs (the query's scale taken back out: exact, a power of two)
-    auto key_of = [&](float acc_v, float qsc, float ax) -> float {
-        const float dot = acc_v * qsc;
-        if (METRIC == METRIC_L2) return fmaf(-2.0f, dot, ax);
-        if (METRIC == METRIC_COS) return -dot * ax;
-        return -dot;
-    };
-    // workgroup-local admission list, carved from the ring (free: every wave is past the last K-step's reads once the
+    // dot = acc * qs (the query's scale taken back out: exact, a power of two); keys, side inputs and the workgroup-local
+    // admission list as in lb_admit.h.  The list is carved from the ring (free: every wave is past the last K-step's reads once the
     // barrier below is behind it)
-    constexpr int FL_CAP = 4096;
-    float *ringf = reinterpret_cast<float *>(ring);
-    uint32_t *s_lcnt = reinterpret_cast<uint32_t *>(ringf);             // entries in the list
-    uint32_t *s_qcnt = s_lcnt + 1;                                      // [H_BN] of them per query of the tile ...
-    uint32_t *s_qbase = s_qcnt + H_BN;                                  // [H_BN] ... and where they start in the query's list
-    uint64_t *s_lent = reinterpret_cast<uint64_t *>(ringf + 1024);
-    uint16_t *s_lq = reinterpret_cast<uint16_t *>(ringf + 1024 + 2 * FL_CAP);
-    uint16_t *s_lr = s_lq + FL_CAP;                                     // rank of the entry among its query's
+    const LocalList<4096, H_BN, H_THREADS> fl(reinterpret_cast<uint32_t *>(ring), reinterpret_cast<uint64_t *>(ring + 4096));
     __syncthreads();
-    if (tid == 0) *s_lcnt = 0;
-    if (tid < H_BN) s_qcnt[tid] = 0;
+    fl.reset(tid);
     __syncthreads();
 #pragma unroll
     for (int tm = 0; tm < 2; tm++) {
@@ -348,16 +332,8 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
         uint32_t rid[4][4];
         uint32_t vbits = 0; // bit (g*4 + e): row visible (in range and not masked out)
 #pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const int lr = wr * 64 + tm * 32 + 8 * g + 4 * h; // 4 consecutive local rows
-            const f32x4 av = *reinterpret_cast<const f32x4 *>(&s_aux[lr]);
-            const uint4 rv = *reinterpret_cast<const uint4 *>(&s_rowid[lr]);
-            const uint32_t vv = *reinterpret_cast<const uint32_t *>(&s_vis[lr]);
-            aux[g][0] = av.x; aux[g][1] = av.y; aux[g][2] = av.z; aux[g][3] = av.w;
-            rid[g][0] = rv.x; rid[g][1] = rv.y; rid[g][2] = rv.z; rid[g][3] = rv.w;
-            const uint32_t nib = (vv & 1u) | ((vv >> 7) & 2u) | ((vv >> 14) & 4u) | ((vv >> 21) & 8u);
-            vbits |= nib << (g * 4);
-        }
+        for (int g = 0; g < 4; g++) // 4 consecutive local rows
+            vbits |= tile_rows4(s_aux, s_rowid, s_vis, wr * 64 + tm * 32 + 8 * g + 4 * h, aux[g], rid[g]) << (g * 4);
 #pragma unroll
         for (int tn = 0; tn < 4; tn++) {
             const int qj = q0 + wc * 128 + tn * 32 + l31;
@@ -373,7 +349,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
                             if (rbase + e < a.row_end)
                                 list[rbase + e - a.row_begin] =
                                     ((vbits >> (g * 4 + e)) & 1u)
-                                        ? pack_entry(key_of(acc[tm][tn][4 * g + e], qs[tn], aux[g][e]), rid[g][e])
+                                        ? pack_entry(cand_key<METRIC>(acc[tm][tn][4 * g + e] * qs[tn], aux[g][e]), rid[g][e])
                                         : kEntryMax;
                     }
                 }
@@ -387,32 +363,31 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
             uint32_t rej = 0; // bit i: element i is beyond the threshold (or a padded query: tk NaN with the sign set)
 #pragma unroll
             for (int i = 15; i >= 0; i--) { // element 15 first: each step shifts the mask left, element i ends in bit i
-                const float key = key_of(acc[tm][tn][i], qs[tn], aux[i >> 2][i & 3]);
-                const float d = tk[tn] - key;
+                const float d = tk[tn] - cand_key<METRIC>(acc[tm][tn][i] * qs[tn], aux[i >> 2][i & 3]);
                 rej = __builtin_amdgcn_alignbit(rej, __builtin_bit_cast(uint32_t, d), 31); // (rej << 1) | sign(d)
             }
             uint32_t bits = ~rej & 0xffffu;
             if (!qok) bits = 0;
             bits &= vbits;
-            if (bits) { // workgroup-local list first: two LDS atomics per lane with admissions
+            if (bits) {
                 const uint32_t n = (uint32_t)__builtin_popcount(bits);
-                uint32_t lp = atomicAdd(s_lcnt, n);
-                if (lp + n <= (uint32_t)FL_CAP) {
-                    uint32_t lr = atomicAdd(&s_qcnt[qj - q0], n);
+                uint32_t lp = atomicAdd(fl.cnt, n);
+                if (lp + n <= (uint32_t)fl.CAP) {
+                    uint32_t lr = atomicAdd(&fl.qcnt[qj - q0], n);
 #pragma unroll
                     for (int g = 0; g < 4; g++)
 #pragma unroll
                         for (int e = 0; e < 4; e++)
                             if (bits & (1u << (g * 4 + e))) {
-                                s_lent[lp] = pack_entry(key_of(acc[tm][tn][4 * g + e], qs[tn], aux[g][e]), rid[g][e]);
-                                s_lq[lp] = (uint16_t)(qj - q0);
-                                s_lr[lp] = (uint16_t)lr;
+                                fl.ent[lp] = pack_entry(cand_key<METRIC>(acc[tm][tn][4 * g + e] * qs[tn], aux[g][e]), rid[g][e]);
+                                fl.q[lp] = (uint16_t)(qj - q0);
+                                fl.rk[lp] = (uint16_t)lr;
                                 lp++;
                                 lr++;
                             }
-                    bits = 0;
+                    bits = 0; // done
                 } else {
-                    for (uint32_t i = lp; i < lp + n && i < (uint32_t)FL_CAP; i++) s_lent[i] = kEntryMax; // reserved, unused
+                    fl.reserved_unused(lp, n);
                 }
             }
             if (bits) { // (local list full) one returning atomic reserves the lane's slots; the stores are fire-and-forget
@@ -422,29 +397,13 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
 #pragma unroll
                     for (int e = 0; e < 4; e++)
                         if (bits & (1u << (g * 4 + e))) {
-                            if (pos < a.cs.cap)
-                                list[pos] = pack_entry(key_of(acc[tm][tn][4 * g + e], qs[tn], aux[g][e]), rid[g][e]);
+                            if (pos < a.cs.cap) list[pos] = pack_entry(cand_key<METRIC>(acc[tm][tn][4 * g + e] * qs[tn], aux[g][e]), rid[g][e]);
                             pos++;
                         }
             }
         }
     }
-    if (!a.boot) { // flush the workgroup-local admissions: ONE returning global atomic per query of the tile, all in flight
-        __syncthreads();
-        if (tid < H_BN) {
-            const uint32_t n = s_qcnt[tid];
-            s_qbase[tid] = n ? atomicAdd(&a.cs.cnt[q0 + tid], n) : 0u; // (n != 0 implies a real query)
-        }
-        __syncthreads();
-        const uint32_t total = *s_lcnt < (uint32_t)FL_CAP ? *s_lcnt : (uint32_t)FL_CAP;
-        for (uint32_t i = tid; i < total; i += H_THREADS) {
-            const uint64_t ent = s_lent[i];
-            if (ent == kEntryMax) continue;
-            const int ql = (int)s_lq[i];
-            const uint32_t pos = s_qbase[ql] + (uint32_t)s_lr[i];
-            if (pos < a.cs.cap) a.cs.lists[(size_t)(q0 + ql) * a.cs.cap + pos] = ent;
-        }
-    }
+    if (!a.boot) fl.flush(tid, a.cs, q0);
 #ifdef LB_DIAG
     if (ABL == 5 && lane == 0) atomicAdd(&g_tall16_probe[6], __builtin_amdgcn_s_memtime() - pr_loop_end); // epilogue
 #endif

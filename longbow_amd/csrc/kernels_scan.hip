@@ -575,7 +575,7 @@ __device__ __forceinline__ void sample_wave(const SampleArgs &a, uint32_t i0, in
             for (int r = 0; r < R; r++) {
                 const float t = wave_sum(acc[j][r]);
                 float v;
-                if (a.keys) { // as gemm_filter_kernel's key_of
+                if (a.keys) { // as cand_key (lb_admit.h)
                     if (METRIC == METRIC_L2) v = fmaf(-2.0f, t, aux[r]);
                     else if (METRIC == METRIC_COS) v = -t * aux[r];
                     else v = -t;
