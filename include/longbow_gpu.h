@@ -156,6 +156,24 @@ int lb_gpu_index_search(lb_gpu_index *h, int64_t nq, const float *queries, int k
 int lb_gpu_index_search_device(lb_gpu_index *h, int64_t nq, const float *d_queries, int k,
                                float *d_dist, int64_t *d_labels, void *stream);
 
+/* ---- float16 indexes: VectorTypeFloat16 (internal/store/arrow_utils.go:67-80) --------------------------
+ * Rows live in HBM as IEEE binary16, 2 bytes per element; half values cross the ABI as uint16_t bit patterns (the layout of
+ * Arrow HalfFloat and Go float16.Num).  Distances are the reference's F16 functions (internal/simd/simd.go:767-848): f32
+ * arithmetic on the widened values, so results equal the f32 index's over the widened data bit for bit -- same lists, same
+ * ascending (distance, row) order, dot negated.  Default order LB_ORDER_UNROLL4 (the reference's only F16 order); SEQ works too.
+ * Batched searches take the fp16-image routes (last_route 63 / 73: the image is a relayout of the rows, exact) while they are
+ * on offer -- image kept, persistent kernels, no per-row mask -- and the exact scan over the fp16 rows otherwise (route 0).
+ * On an F16 handle reserve / ntotal / dim / set_filter / filter_* / set_f16_image / f16_image_bytes / last_* / profiling / free
+ * work as on an f32 one; set_candidate_mode takes AUTO and F16 only (else LB_ERR_UNSUPPORTED); rerank and comm searches
+ * return LB_ERR_UNSUPPORTED.  An f32 add / search on an F16 handle, or an _f16 call on an f32 handle, is LB_ERR_INVALID_ARG
+ * with a last_error text.  _f16 host searches are not combined. */
+lb_gpu_index *lb_gpu_index_new_f16(int device, int dim, int metric, int *out_status);
+int lb_gpu_index_dtype(const lb_gpu_index *h); /* 0 float32, 1 float16 (simd.DataType, internal/simd/registry.go) */
+int lb_gpu_index_add_f16(lb_gpu_index *h, int64_t n, const uint16_t *vectors, const int64_t *ids);
+int lb_gpu_index_add_f16_device(lb_gpu_index *h, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids);
+/* HBM the index holds now: rows (as mapped / allocated), the per-row side arrays, the row list and any accelerator image */
+int64_t lb_gpu_index_hbm_bytes(const lb_gpu_index *h);
+
 /* ---- cancellation: the ctx of SearchVectors(ctx, ...) ------------------------------------------
  * The reference's brute-force loop polls ctx.Err() every 1000 rows (internal/store/adaptive_index.go:182).
  * A cgo caller makes one lb_cancel per call, fires it from `go func(){ <-ctx.Done(); C.lb_cancel_fire(c) }()`
@@ -174,6 +192,12 @@ int lb_gpu_index_search_ctx(lb_gpu_index *h, int64_t nq, const float *queries, i
                             const lb_cancel *ctx);
 int lb_gpu_index_search_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
                                    int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* the float16 index's searches: fp16 queries (widened exactly on the device) */
+int lb_gpu_index_search_f16(lb_gpu_index *h, int64_t nq, const uint16_t *queries, int k, float *dist, int64_t *labels);
+int lb_gpu_index_search_f16_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *queries, int k, float *dist, int64_t *labels,
+                                const lb_cancel *ctx);
+int lb_gpu_index_search_f16_device_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *d_queries, int k, float *d_dist,
+                                       int64_t *d_labels, void *stream, const lb_cancel *ctx);
 
 /* Metadata predicate mask for filtered search (SURVEY f-3; byte-per-row 0/1 as
  * internal/query/filter_evaluator.go:79-115 produces).  mask has ntotal bytes;

@@ -74,6 +74,14 @@ SIGNATURES = [
     ("lb_gpu_index_add_device", _i, [_vp, _i64, _vp, _vp]),
     ("lb_gpu_index_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_index_search_device", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_index_new_f16", _vp, [_i, _i, _i, _ip]),
+    ("lb_gpu_index_dtype", _i, [_vp]),
+    ("lb_gpu_index_add_f16", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_index_add_f16_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_index_search_f16", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_index_search_f16_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_f16_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_index_hbm_bytes", _i64, [_vp]),
     ("lb_gpu_index_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_index_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_index_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),

@@ -66,7 +66,7 @@ struct Workspace {
     uint32_t *h_fail = nullptr;         // pinned: epoch of a launch whose waits gave up
     uint32_t *h_flags = nullptr; // pinned
     int *h_qsel = nullptr;       // pinned
-    // host-API staging (device side)
+    // an fp16 index's query batch widened to f32 (every query kernel downstream reads f32 queries)
     float *d_q = nullptr;
     size_t d_q_bytes = 0;
     float *d_dist = nullptr;
@@ -222,7 +222,10 @@ struct lb_gpu_index {
     std::shared_mutex mu;
     bool closed = false;
 
+    // rows, row-major: f32, or IEEE binary16 on an fp16 index (f16_rows; typed float * for the f32 code -- an fp16 index's rows
+    // are only ever read through rows_f16())
     float *d_X = nullptr;
+    bool f16_rows = false; // lb_gpu_index_new_f16: fixed for the handle's life
     VmmBuf vmm;             // backs d_X when vmm.ok (d_X == vmm.base): rows are appended in place
     int64_t x_rows_cap = 0; // rows d_X can hold (>= capacity of the side arrays when vmm.ok)
     int64_t n = 0, capacity = 0;
@@ -275,6 +278,7 @@ struct lb_gpu_index {
     // 0 = not measured (the per-element worst case 2^-11 stands in)
     uint32_t *d_xh_rho2 = nullptr;
     float xh_rho = 0.f;
+    bool xh_exact = false;       // fp16 rows, image not centred: the image IS the rows (rho_x = 0, measured)
     bool xh_offset_dom = false;  // |c|^2 is several times the largest centred |x - c|^2: plain L2 keys cancel on this data, so
                                  // AUTO keeps batched searches on the centred image whatever the cost model says of other routes
     int64_t xh_declined_n = 0;   // a centred image was out of fp16's range at this many rows: not tried again below twice that
@@ -302,6 +306,9 @@ struct lb_gpu_index {
     std::mutex prof_mu;
     float prof_ms[5] = {0, 0, 0, 0, 0};
     int prof_n[5] = {0, 0, 0, 0, 0};
+
+    size_t elem_bytes() const { return f16_rows ? 2 : sizeof(float); }
+    const _Float16 *rows_f16() const { return reinterpret_cast<const _Float16 *>(d_X); }
 
     void set_error(const char *fmt, ...)
     {
@@ -544,14 +551,22 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
         if (sp.on) {
             {   // sample scores (clear the flags; exact query norms ride along), threshold
                 ProfScope p(w, s, prof, 1);
-                launch_sample_scores(metric, order, h->d_X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel,
-                                     gn, w->cs, w->d_qna, s);
+                if (h->f16_rows)
+                    launch_sample_scores(metric, order, h->rows_f16(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel,
+                                         gn, w->cs, w->d_qna, s);
+                else
+                    launch_sample_scores(metric, order, h->d_X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel,
+                                         gn, w->cs, w->d_qna, s);
                 launch_sample_tau(w->cs, use_sel, gn, sp.count, sp.m, /*zero_stripes=*/true, s);
             }
             {   // one pass over the span
                 ProfScope p(w, s, prof, 3);
-                launch_scan(metric, order, false, h->d_X, 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna, mask,
-                            rv.rowmap, w->cs, /*boot=*/false, nullptr, 0, s, /*striped=*/true);
+                if (h->f16_rows)
+                    launch_scan(metric, order, false, h->rows_f16(), 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna, mask,
+                                rv.rowmap, w->cs, /*boot=*/false, nullptr, 0, s, /*striped=*/true);
+                else
+                    launch_scan(metric, order, false, h->d_X, 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna, mask,
+                                rv.rowmap, w->cs, /*boot=*/false, nullptr, 0, s, /*striped=*/true);
             }
             {
                 ProfScope p(w, s, prof, 1);
@@ -571,8 +586,12 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
             const bool boot = step == 0;
             {
                 ProfScope p(w, s, prof, 3);
-                launch_scan(metric, order, false, h->d_X, pos, end, h->dim, d_q, use_sel, gn, w->d_qna,
-                            mask, rv.rowmap, w->cs, boot, nullptr, 0, s);
+                if (h->f16_rows)
+                    launch_scan(metric, order, false, h->rows_f16(), pos, end, h->dim, d_q, use_sel, gn, w->d_qna,
+                                mask, rv.rowmap, w->cs, boot, nullptr, 0, s);
+                else
+                    launch_scan(metric, order, false, h->d_X, pos, end, h->dim, d_q, use_sel, gn, w->d_qna,
+                                mask, rv.rowmap, w->cs, boot, nullptr, 0, s);
             }
             {
                 ProfScope p(w, s, prof, 1);
@@ -695,7 +714,10 @@ inline double route_ms(const RouteCost &c, int64_t n, int D, int tiles)
     return (compute > stream ? compute : stream) + nd * (double)D * c.first + c.fixed;
 }
 
-static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, bool have_image, bool f16_ok, bool have_f16_image = false)
+// f32_rows false (an fp16 index): only the routes over the fp16 image are offered -- every other one stages f32 rows; with none
+// on offer the result has kind 0 (the exact scan)
+static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, bool have_image, bool f16_ok, bool have_f16_image = false,
+                          bool f32_rows = true)
 {
     static const int narrow_max = lb_tunable("LB_NARROW_MAXQ", 384);
     static const bool nsplit_on = lb_tunable("LB_NARROW_SPLIT", 1) != 0;
@@ -707,6 +729,7 @@ static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, b
     int nc = 0;
     auto add = [&](int kind, int split, double ms) { cand[nc].kind = kind; cand[nc].split = split; cand[nc].cost_ms = ms; nc++; };
     const bool image = cmode == LB_CAND_SPLIT_BF16 && have_image;
+    if (!f32_rows) narrow_ok = false;
     if (narrow_ok && !image && (cmode == LB_CAND_AUTO || nq <= narrow_max)) {
         const int nsp = nsplit_on ? 2 : 0;
         if (nq <= 32 || tiles32 <= 10) add(ROUTE_NARROW32, nsp, route_ms(kCostNarrow32, n, D, tiles32));
@@ -744,7 +767,8 @@ static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, b
         }
         else add(ROUTE_TALL16, 3, route_ms(have_f16_image ? kCostTall16Img : kCostTall16, n, D, tiles256));
     }
-    if (cmode == LB_CAND_F32_MFMA || cmode == LB_CAND_AUTO || nc == 0) add(ROUTE_WIDE, 0, route_ms(kCostWideF32, n, D, tiles128));
+    if (!f32_rows && nc == 0) return Route{0, 0, 0.0};
+    if (f32_rows && (cmode == LB_CAND_F32_MFMA || cmode == LB_CAND_AUTO || nc == 0)) add(ROUTE_WIDE, 0, route_ms(kCostWideF32, n, D, tiles128));
 #ifdef LB_DIAG
     { // A/B (tools/route_grid.py): force a route when it is available for this batch (read per call: the tool flips it)
         if (getenv("LB_TRACE_ROUTE")) {
@@ -788,7 +812,7 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
 
     // Path selection: <= 4 queries exact scan (0.50-0.55 ms at 1M x 768); from 5 queries a candidate route picked by
     // choose_route's cost model (narrow / tall / tall2 / fp16 / f32 tile), exact re-rank behind every one of them.
-    const bool narrow_ok = h->dim % 32 == 0 && ((reinterpret_cast<uintptr_t>(d_q) & 15) == 0);
+    const bool narrow_ok = !h->f16_rows && h->dim % 32 == 0 && ((reinterpret_cast<uintptr_t>(d_q) & 15) == 0);
     static const int narrow_min = lb_tunable("LB_NARROW_MINQ", 5);
     static const int narrow_max = lb_tunable("LB_NARROW_MAXQ", 384);
     // rows with inf / NaN components: the MFMA pipeline's keys and error bounds assume finite data;
@@ -798,7 +822,9 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     // dimensions from 256; under a per-row mask test the kernel stages f32 rows)
     const bool have_xh = h->d_Xh != nullptr && h->xh_rows == h->n && !mask && (!rv.rowmap || h->dim >= 256) &&
                          // (a centred image -- L2 -- is only ever read by the persistent kernels: nothing else knows the centre)
-                         (!h->xh_centred || tall16_runs_persistent(h->dim, nq, true, rv.rowmap != nullptr, false));
+                         (!h->xh_centred || tall16_runs_persistent(h->dim, nq, true, rv.rowmap != nullptr, false)) &&
+                         // (fp16 rows: only the persistent kernels read nothing but the image -- the one-tile form stages f32 rows)
+                         (!h->f16_rows || tall16_runs_persistent(h->dim, nq, true, rv.rowmap != nullptr, false));
     const bool centred = have_xh && h->xh_centred; // L2 keys about the image's centre (sync_f16_image)
     // within the fp16 contraction's range: the centred norms when the image is centred, the rows' own norms otherwise
     bool f16_range_ok = centred ? h->xh_c_ok : h->f16_ok;
@@ -816,14 +842,18 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     bool small_on_copy = false;
     if (!h->nonfinite && nq < narrow_min && have_xh && f16_range_ok && allow_f16 &&
         (cmode == LB_CAND_F16 || (cmode == LB_CAND_AUTO && h->f16_skip.load(std::memory_order_relaxed) == 0))) {
-        const double scan_ms = 0.04 + 1e-6 * (double)n * ((double)h->dim * 0.00066 + 0.04); // (0.04: sample, thresholds, select + emit)
+        const double scan_ms = 0.04 + 1e-6 * (double)n * ((double)h->dim * 0.00066 * (h->f16_rows ? 0.5 : 1.0) + 0.04); // (0.04: sample,
+                                                                                                                       // thresholds, select + emit)
         const double copy_ms = route_ms(kCostNarrow16, n, h->dim, 1) + (h->dim > 1024 ? 0.0008 : 0.0003) * nq;
         small_on_copy = cmode == LB_CAND_F16 || copy_ms < scan_ms;
     }
     // (dimensions that are not multiples of 32: the MFMA tiles over f32 rows do not apply; the fp16 copy does)
     const bool copy_route_ok = have_xh && f16_range_ok && allow_f16 &&
                                (cmode == LB_CAND_F16 || (cmode == LB_CAND_AUTO && h->f16_skip.load(std::memory_order_relaxed) == 0));
-    if (h->nonfinite || (nq < ((narrow_ok || copy_route_ok) ? narrow_min : kGemmMinQ) && !small_on_copy)) {
+    // (an fp16 index without the image route on offer -- no image, rows out of fp16's key range, a masked search, the
+    // batch beyond the persistent kernels: the exact scan over the fp16 rows, the floor)
+    if (h->nonfinite || (h->f16_rows && !copy_route_ok) ||
+        (nq < ((narrow_ok || copy_route_ok) ? narrow_min : kGemmMinQ) && !small_on_copy)) {
         h->last_route.store(0, std::memory_order_relaxed);
         std::vector<int> all(nq);
         for (int i = 0; i < nq; i++) all[i] = i;
@@ -842,7 +872,14 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     // lengths: only the lower-bound keys do)
     const bool keys_matter = (centred && h->xh_offset_dom) || (metric == LB_METRIC_DOT && h->norm_spread);
     const int cmode_route = (cmode == LB_CAND_AUTO && keys_matter && f16_offer) ? LB_CAND_F16 : cmode;
-    const Route route = choose_route(nq, n, h->dim, cmode_route, narrow_ok, have_image, f16_offer, have_xh);
+    const Route route = choose_route(nq, n, h->dim, cmode_route, narrow_ok, have_image, f16_offer, have_xh, !h->f16_rows);
+    if (route.kind == 0) { // (fp16 rows, the image route not offered for this batch)
+        h->last_route.store(0, std::memory_order_relaxed);
+        std::vector<int> all(nq);
+        for (int i = 0; i < nq; i++) all[i] = i;
+        scan_with_retry(h, w, s, d_q, nq, all, k, d_dist, d_lab, prof);
+        return LB_OK;
+    }
     h->last_route.store(route.kind * 10 + route.split, std::memory_order_relaxed);
 #ifdef LB_DIAG
     g_last_route.store(route.kind * 10 + route.split);
@@ -889,7 +926,8 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     // mantissa, subnormal effects included:  gamma(q) = 1.05 (rho_x + A (1 + rho_x) + 2^-21) + 1.05 (1 + rho_x)(1 + A) rho_q,
     // A = (D + 8) 2^-24 the f32 accumulation of D exact products
     static const bool rho_on = lb_tunable("LB_MEASURED_RHO", 1) != 0;
-    const bool measured = rho_on && route.split == 3 && have_xh && h->xh_rho > 0.f && h->xh_rho < 4.0e-4f; // (else the worst case is the better bound)
+    const bool measured = rho_on && route.split == 3 && have_xh && (h->xh_rho > 0.f || h->xh_exact) &&
+                          h->xh_rho < 4.0e-4f; // (else the worst case is the better bound)
     const float accA = (float)(h->dim + 8) * u24;
     const float qrho_k = measured ? 1.05f * (1.0f + h->xh_rho) * (1.0f + accA) : 0.f;
     const float gamma = route.split == 0   ? 1.05f * (float)(h->dim + 8) * u24
@@ -1038,9 +1076,14 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
             ProfScope p(w, s, prof, 1);
             // (centred keys: the same key about the image's centre, from the f32 rows)
             const SamplePrep sprep{w->d_qh, d_qinv, dot_lb ? d_qnrm : nullptr, centred ? h->d_center : nullptr, tauin, d_qrho, rho_gain};
-            launch_sample_scores(metric, order, h->d_X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, nullptr, nq,
-                                 w->cs, nullptr, s, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, centred ? h->d_center : nullptr,
-                                 prep_rides ? &sprep : nullptr);
+            if (h->f16_rows)
+                launch_sample_scores(metric, order, h->rows_f16(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, nullptr, nq,
+                                     w->cs, nullptr, s, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, centred ? h->d_center : nullptr,
+                                     prep_rides ? &sprep : nullptr);
+            else
+                launch_sample_scores(metric, order, h->d_X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, nullptr, nq,
+                                     w->cs, nullptr, s, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, centred ? h->d_center : nullptr,
+                                     prep_rides ? &sprep : nullptr);
             if (!tauin)
                 launch_sample_tau(w->cs, nullptr, nq, sp.count, sp.m, false, s, d_q, h->dim,
                                   norm_riders ? w->d_qna : nullptr, order);
@@ -1128,10 +1171,16 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
             // members a query may have: twice the results wanted, at least 1024 (the lists hold up to cap entries below tau)
             const uint32_t smax = std::min<uint32_t>(kFinishSmaxMax, std::max<uint32_t>(1024u, 2u * next_pow2_host((uint32_t)k)));
             const bool ckeys = centred && use_tall16; // (the keys of this search were taken about the image's centre)
-            launch_finish(metric, order, h->d_X, h->dim, d_q, nq, w->d_qna, w->cs, k, ckeys ? h->d_cstats : h->d_maxnorm2, gamma, finish_beta,
-                          h->has_ids ? h->d_ids : nullptr, entries_pos ? rv.rowmap : nullptr, d_dist, d_lab, s, w->h_flags, w->d_done, w->d_xcnt,
-                          w->d_xscratch, kFinishSplitMaxQ, smax, ckeys ? h->d_center : nullptr, dot_lb ? h->d_norm2 : nullptr, d_qnrm, gsum,
-                          dot_lb ? nullptr : d_qrho, qrho_k);
+            if (h->f16_rows)
+                launch_finish(metric, order, h->rows_f16(), h->dim, d_q, nq, w->d_qna, w->cs, k, ckeys ? h->d_cstats : h->d_maxnorm2, gamma,
+                              finish_beta, h->has_ids ? h->d_ids : nullptr, entries_pos ? rv.rowmap : nullptr, d_dist, d_lab, s, w->h_flags,
+                              w->d_done, w->d_xcnt, w->d_xscratch, kFinishSplitMaxQ, smax, ckeys ? h->d_center : nullptr,
+                              dot_lb ? h->d_norm2 : nullptr, d_qnrm, gsum, dot_lb ? nullptr : d_qrho, qrho_k);
+            else
+                launch_finish(metric, order, h->d_X, h->dim, d_q, nq, w->d_qna, w->cs, k, ckeys ? h->d_cstats : h->d_maxnorm2, gamma, finish_beta,
+                              h->has_ids ? h->d_ids : nullptr, entries_pos ? rv.rowmap : nullptr, d_dist, d_lab, s, w->h_flags, w->d_done, w->d_xcnt,
+                              w->d_xscratch, kFinishSplitMaxQ, smax, ckeys ? h->d_center : nullptr, dot_lb ? h->d_norm2 : nullptr, d_qnrm, gsum,
+                              dot_lb ? nullptr : d_qrho, qrho_k);
         }
     }
     std::vector<int> bad;
@@ -1277,7 +1326,7 @@ void drop_f16_image(lb_gpu_index *h);
 
 int grow(lb_gpu_index *h, int64_t need)
 {
-    const size_t row_bytes = (size_t)h->dim * sizeof(float);
+    const size_t row_bytes = (size_t)h->dim * h->elem_bytes();
     int64_t cap = std::max<int64_t>(need, h->capacity * 2);
     cap = std::max<int64_t>(cap, 1024);
     if (h->vmm.ok) {
@@ -1400,6 +1449,7 @@ void drop_f16_image(lb_gpu_index *h)
     h->xh_rows = h->xh_cap = 0;
     h->xh_centred = h->xh_c_ok = h->xh_offset_dom = false;
     h->xh_rho = 0.f;
+    h->xh_exact = false;
     if (h->d_xh_rho2) (void)hipMemset(h->d_xh_rho2, 0, sizeof(uint32_t));
 }
 
@@ -1451,8 +1501,11 @@ void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool ids_on_
 {
     hipStream_t s = h->add_stream;
     const int64_t start = h->n;
-    launch_row_norms(h->d_X + (size_t)start * h->dim, n, h->dim, h->d_norm2 + start, h->d_rnorm + start,
-                     h->d_maxnorm2, s);
+    if (h->f16_rows)
+        launch_row_norms(h->rows_f16() + (size_t)start * h->dim, n, h->dim, h->d_norm2 + start, h->d_rnorm + start, h->d_maxnorm2, s);
+    else
+        launch_row_norms(h->d_X + (size_t)start * h->dim, n, h->dim, h->d_norm2 + start, h->d_rnorm + start,
+                         h->d_maxnorm2, s);
     if (ids_src) {
         if (!h->has_ids && start > 0)
             hipLaunchKernelGGL(iota_ids_kernel, dim3((unsigned)((start + 255) / 256)), dim3(256), 0, s, h->d_ids,
@@ -1497,7 +1550,7 @@ void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool ids_on_
 // bring the split-bf16 mirror up to date with d_X (no-op unless the mode is enabled)
 void sync_split_image(lb_gpu_index *h)
 {
-    if (h->cand_mode.load() != 1 || h->dim % 32 != 0 || h->n == 0) return;
+    if (h->cand_mode.load() != 1 || h->dim % 32 != 0 || h->n == 0 || h->f16_rows) return;
     if (h->d_Xs == nullptr || h->xs_rows > h->n) {
         if (h->d_Xs) (void)hipFree(h->d_Xs);
         h->d_Xs = nullptr;
@@ -1557,16 +1610,24 @@ void sync_f16_image(lb_gpu_index *h)
                 const uint32_t init[2] = {0u, 0x7f800000u};
                 LB_HIP(hipMemcpyAsync(h->d_cstats, init, sizeof init, hipMemcpyHostToDevice, s));
                 Lease part(h->device, (size_t)256 * h->dim * sizeof(float));
-                launch_column_means(h->d_X, h->n, h->dim, part.as<float>(), h->d_center, dpad, s);
+                if (h->f16_rows) launch_column_means(h->rows_f16(), h->n, h->dim, part.as<float>(), h->d_center, dpad, s);
+                else launch_column_means(h->d_X, h->n, h->dim, part.as<float>(), h->d_center, dpad, s);
                 LB_HIP(hipStreamSynchronize(s)); // (the lease goes back to the pool)
                 h->xh_centred = true;
             }
         }
         if (h->xh_rows < h->n) {
-            launch_corpus_to_f16(h->d_X, h->xh_rows, h->n, h->dim, h->d_Xh, h->xh_cap, s, h->xh_centred ? h->d_center : nullptr);
+            if (h->f16_rows) // (a relayout of the rows, or their centred form)
+                launch_corpus_to_f16(h->rows_f16(), h->xh_rows, h->n, h->dim, h->d_Xh, h->xh_cap, s, h->xh_centred ? h->d_center : nullptr);
+            else
+                launch_corpus_to_f16(h->d_X, h->xh_rows, h->n, h->dim, h->d_Xh, h->xh_cap, s, h->xh_centred ? h->d_center : nullptr);
             if (h->xh_centred) {
-                launch_row_norms(h->d_X + (size_t)h->xh_rows * h->dim, h->n - h->xh_rows, h->dim, h->d_norm2c + h->xh_rows, nullptr,
-                                 h->d_cstats, s, h->d_center);
+                if (h->f16_rows)
+                    launch_row_norms(h->rows_f16() + (size_t)h->xh_rows * h->dim, h->n - h->xh_rows, h->dim, h->d_norm2c + h->xh_rows, nullptr,
+                                     h->d_cstats, s, h->d_center);
+                else
+                    launch_row_norms(h->d_X + (size_t)h->xh_rows * h->dim, h->n - h->xh_rows, h->dim, h->d_norm2c + h->xh_rows, nullptr,
+                                     h->d_cstats, s, h->d_center);
                 uint32_t cb[2] = {0, 0};
                 LB_HIP(hipMemcpyAsync(cb, h->d_cstats, sizeof cb, hipMemcpyDeviceToHost, s));
                 LB_HIP(hipStreamSynchronize(s));
@@ -1588,7 +1649,10 @@ void sync_f16_image(lb_gpu_index *h)
                     LB_HIP(hipMalloc(&h->d_xh_rho2, sizeof(uint32_t)));
                     LB_HIP(hipMemsetAsync(h->d_xh_rho2, 0, sizeof(uint32_t), s));
                 }
-                launch_f16_residual(h->d_X, h->xh_rows, h->n, h->dim, h->xh_centred ? h->d_center : nullptr, h->d_xh_rho2, s);
+                if (h->f16_rows)
+                    launch_f16_residual(h->rows_f16(), h->xh_rows, h->n, h->dim, h->xh_centred ? h->d_center : nullptr, h->d_xh_rho2, s);
+                else
+                    launch_f16_residual(h->d_X, h->xh_rows, h->n, h->dim, h->xh_centred ? h->d_center : nullptr, h->d_xh_rho2, s);
                 uint32_t rb = 0;
                 LB_HIP(hipMemcpyAsync(&rb, h->d_xh_rho2, sizeof rb, hipMemcpyDeviceToHost, s));
                 LB_HIP(hipStreamSynchronize(s));
@@ -1596,6 +1660,7 @@ void sync_f16_image(lb_gpu_index *h)
                 // (a ratio beyond the worst case of normal fp16 values, 2^-22, means elements in the subnormal range or flushed
                 // to zero carry weight: still a valid bound as long as it is finite and small enough to be of use)
                 h->xh_rho = (rb < 0x7f800000u && r2 <= 1.0e-4f) ? std::sqrt(r2) * 1.000001f : 0.f;
+                h->xh_exact = h->f16_rows && !h->xh_centred && rb == 0; // (the image is the rows: rho_x = 0)
             }
             LB_HIP(hipStreamSynchronize(s));
             h->xh_rows = h->n;
@@ -1711,7 +1776,7 @@ const char *lb_gpu_status_string(int status)
     }
 }
 
-lb_gpu_index *lb_gpu_index_new(int device, int dim, int metric, int *out_status)
+static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status, bool f16_rows)
 {
     auto st = [&](int v) { if (out_status) *out_status = v; };
     if (dim <= 0 || metric < 0 || metric > 2) { st(LB_ERR_INVALID_ARG); return nullptr; }
@@ -1722,6 +1787,9 @@ lb_gpu_index *lb_gpu_index_new(int device, int dim, int metric, int *out_status)
     auto *h = new (std::nothrow) lb_gpu_index();
     if (!h) { st(LB_ERR_OOM); return nullptr; }
     h->device = device; h->dim = dim; h->metric = metric;
+    h->f16_rows = f16_rows;
+    // (fp16 rows: UNROLL4 is the only order of the reference's F16 functions, internal/simd/simd.go:767-848)
+    if (f16_rows) h->order.store(LB_ORDER_UNROLL4);
     try {
         LB_HIP(hipSetDevice(device));
         LB_HIP(hipStreamCreateWithFlags(&h->add_stream, hipStreamNonBlocking));
@@ -1737,6 +1805,30 @@ lb_gpu_index *lb_gpu_index_new(int device, int dim, int metric, int *out_status)
     }
     st(LB_OK);
     return h;
+}
+
+lb_gpu_index *lb_gpu_index_new(int device, int dim, int metric, int *out_status)
+{
+    return index_new(device, dim, metric, out_status, false);
+}
+lb_gpu_index *lb_gpu_index_new_f16(int device, int dim, int metric, int *out_status)
+{
+    return index_new(device, dim, metric, out_status, true);
+}
+int lb_gpu_index_dtype(const lb_gpu_index *h) { return h && h->f16_rows ? 1 : 0; }
+
+int64_t lb_gpu_index_hbm_bytes(const lb_gpu_index *h)
+{
+    if (!h) return 0;
+    std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_index *>(h)->mu);
+    const int pd = corpus_f16_plane_dims();
+    int64_t b = h->vmm.ok ? (int64_t)h->vmm.mapped : h->x_rows_cap * (int64_t)h->dim * (int64_t)h->elem_bytes();
+    b += h->capacity * (int64_t)(2 * sizeof(float) + sizeof(int64_t) + 1); // norms, inverse norms, ids, mask
+    if (h->d_rowmap) b += h->rowmap_cap * (int64_t)sizeof(uint32_t);
+    if (h->d_Xs) b += h->capacity * (int64_t)h->dim * (int64_t)sizeof(float);
+    if (h->d_Xh) b += h->xh_cap * (int64_t)((h->dim + pd - 1) / pd * pd) * 2;
+    if (h->d_norm2c) b += h->xh_cap * (int64_t)sizeof(float);
+    return b;
 }
 
 void lb_gpu_index_free(lb_gpu_index *h)
@@ -1797,6 +1889,10 @@ int lb_gpu_index_set_candidate_mode(lb_gpu_index *h, int mode)
     if (!h || mode < LB_CAND_F32_MFMA || mode > LB_CAND_F16) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
     if (h->closed) return LB_ERR_CLOSED;
+    if (h->f16_rows && mode != LB_CAND_AUTO && mode != LB_CAND_F16) {
+        h->set_error("candidate mode %d needs f32 rows; an fp16 index takes AUTO or F16", mode);
+        return LB_ERR_UNSUPPORTED;
+    }
     if ((mode == LB_CAND_SPLIT_BF16 || mode == LB_CAND_SPLIT_BF16_INREG) && h->dim % 32 != 0) {
         h->set_error("split-bf16 candidates need dim %% 32 == 0 (dim = %d)", h->dim);
         return LB_ERR_UNSUPPORTED;
@@ -1860,11 +1956,19 @@ int lb_gpu_index_reserve(lb_gpu_index *h, int64_t n_total)
     }
 }
 
-int lb_gpu_index_add(lb_gpu_index *h, int64_t n, const float *vectors, const int64_t *ids)
+static int dtype_mismatch(lb_gpu_index *h, bool f16_call)
+{
+    if (h->f16_rows == f16_call) return LB_OK;
+    h->set_error(f16_call ? "this index holds float32 rows: use the float32 entry point" : "this index holds float16 rows: use the _f16 entry point");
+    return LB_ERR_INVALID_ARG;
+}
+
+static int add_host(lb_gpu_index *h, int64_t n, const void *vectors, const int64_t *ids, bool f16_call)
 {
     if (!h || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
+    if (const int rc = dtype_mismatch(h, f16_call)) return rc;
     if (n == 0) return LB_OK;
     if (h->n + n > (int64_t)0xffffffffll) { h->set_error("more than 2^32 rows per device"); return LB_ERR_UNSUPPORTED; }
     try {
@@ -1874,16 +1978,16 @@ int lb_gpu_index_add(lb_gpu_index *h, int64_t n, const float *vectors, const int
             if (!h->h_stage[i]) LB_HIP(hipHostMalloc(&h->h_stage[i], kStageBytes, hipHostMallocDefault));
             if (!h->stage_ev[i]) LB_HIP(hipEventCreateWithFlags(&h->stage_ev[i], hipEventDisableTiming));
         }
-        const size_t total = (size_t)n * h->dim * sizeof(float);
+        const size_t total = (size_t)n * h->dim * h->elem_bytes();
         const char *src = reinterpret_cast<const char *>(vectors);
-        char *dst = reinterpret_cast<char *>(h->d_X + (size_t)h->n * h->dim);
+        char *dst = reinterpret_cast<char *>(h->d_X) + (size_t)h->n * h->dim * h->elem_bytes();
         size_t off = 0;
         // Large batches: pin the caller's buffer (the Arrow values buffer) for the duration of the call and
         // DMA straight out of it -- no host-side copy (SURVEY 8b ownership row: "the shim hipHostRegisters
         // the Arrow values buffer for the duration of the call").  Small batches, or a buffer the driver
         // will not pin, go through the double-buffered pinned slabs below.
         if (total >= (size_t)g_add_register_min.load() && g_add_register_min.load() > 0) {
-            void *reg = const_cast<float *>(vectors);
+            void *reg = const_cast<void *>(vectors);
             if (hipHostRegister(reg, total, hipHostRegisterDefault) == hipSuccess) {
                 hipError_t e = hipSuccess;
                 const size_t piece = (size_t)256 << 20;
@@ -1917,23 +2021,42 @@ int lb_gpu_index_add(lb_gpu_index *h, int64_t n, const float *vectors, const int
     return LB_OK;
 }
 
-int lb_gpu_index_add_device(lb_gpu_index *h, int64_t n, const float *d_vectors, const int64_t *d_ids)
+int lb_gpu_index_add(lb_gpu_index *h, int64_t n, const float *vectors, const int64_t *ids)
+{
+    return add_host(h, n, vectors, ids, false);
+}
+int lb_gpu_index_add_f16(lb_gpu_index *h, int64_t n, const uint16_t *vectors, const int64_t *ids)
+{
+    return add_host(h, n, vectors, ids, true);
+}
+
+static int add_device(lb_gpu_index *h, int64_t n, const void *d_vectors, const int64_t *d_ids, bool f16_call)
 {
     if (!h || n < 0 || (n > 0 && !d_vectors)) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
+    if (const int rc = dtype_mismatch(h, f16_call)) return rc;
     if (n == 0) return LB_OK;
     if (h->n + n > (int64_t)0xffffffffll) { h->set_error("more than 2^32 rows per device"); return LB_ERR_UNSUPPORTED; }
     try {
         LB_HIP(hipSetDevice(h->device));
         grow_or_shed(h, h->n + n);
-        LB_HIP(hipMemcpyAsync(h->d_X + (size_t)h->n * h->dim, d_vectors, (size_t)n * h->dim * sizeof(float),
-                              hipMemcpyDeviceToDevice, h->add_stream));
+        LB_HIP(hipMemcpyAsync(reinterpret_cast<char *>(h->d_X) + (size_t)h->n * h->dim * h->elem_bytes(), d_vectors,
+                              (size_t)n * h->dim * h->elem_bytes(), hipMemcpyDeviceToDevice, h->add_stream));
         finish_add(h, n, d_ids, true);
     } catch (const HipErr &e) {
         return fail_hip(h, e);
     }
     return LB_OK;
+}
+
+int lb_gpu_index_add_device(lb_gpu_index *h, int64_t n, const float *d_vectors, const int64_t *d_ids)
+{
+    return add_device(h, n, d_vectors, d_ids, false);
+}
+int lb_gpu_index_add_f16_device(lb_gpu_index *h, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids)
+{
+    return add_device(h, n, d_vectors, d_ids, true);
 }
 
 int lb_gpu_index_set_filter(lb_gpu_index *h, const uint8_t *mask, int64_t n)
@@ -2000,12 +2123,13 @@ int64_t lb_gpu_index_last_fallbacks(const lb_gpu_index *h) { return h ? h->last_
 int64_t lb_gpu_index_fused_giveups(const lb_gpu_index *h) { return h ? h->fused_giveups.load() : 0; }
 int lb_gpu_index_last_route(const lb_gpu_index *h) { return h ? h->last_route.load() : 0; }
 
-int lb_gpu_index_search_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
-                                   int64_t *d_labels, void *stream, const lb_cancel *ctx)
+static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
+                         const lb_cancel *ctx, bool f16_call)
 {
     if (!h || nq < 0 || k <= 0 || (nq > 0 && (!d_queries || !d_dist || !d_labels))) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
+    if (const int rc = dtype_mismatch(h, f16_call)) return rc;
     if (nq == 0) return LB_OK;
     if (k > LB_MAX_K) { h->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
     if (const int st = ctx_state(ctx)) { h->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded"); return st; }
@@ -2030,7 +2154,22 @@ int lb_gpu_index_search_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_q
         } else {
             for (int64_t q0 = 0; q0 < nq; q0 += kMaxBatch) {
                 const int bq = (int)std::min<int64_t>(kMaxBatch, nq - q0);
-                int rc = search_batch_device(h, w.get(), s, bq, d_queries + (size_t)q0 * h->dim, k,
+                const float *bq_f32 = nullptr;
+                if (f16_call) { // fp16 queries: widened exactly into the workspace's f32 batch, then searched as any other
+                    const size_t need = (size_t)bq * h->dim * sizeof(float);
+                    if (w->d_q_bytes < need) {
+                        if (w->d_q) (void)hipFree(w->d_q);
+                        w->d_q = nullptr;
+                        w->d_q_bytes = 0;
+                        LB_HIP(hipMalloc(&w->d_q, need));
+                        w->d_q_bytes = need;
+                    }
+                    launch_widen_f16(static_cast<const uint16_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q, (int64_t)bq * h->dim, s);
+                    bq_f32 = w->d_q;
+                } else {
+                    bq_f32 = static_cast<const float *>(d_queries) + (size_t)q0 * h->dim;
+                }
+                int rc = search_batch_device(h, w.get(), s, bq, bq_f32, k,
                                              d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, kc, prof, fallbacks);
                 if (rc != LB_OK) { w->ctx = nullptr; release_ws(h, std::move(w)); return rc; }
             }
@@ -2063,6 +2202,17 @@ int lb_gpu_index_search_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_q
     return LB_OK;
 }
 
+int lb_gpu_index_search_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
+                                   int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, false);
+}
+int lb_gpu_index_search_f16_device_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *d_queries, int k, float *d_dist,
+                                       int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, true);
+}
+
 int lb_gpu_index_search_device(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
                                int64_t *d_labels, void *stream)
 {
@@ -2085,14 +2235,16 @@ int lb_cancel_state(const lb_cancel *c) { return ctx_state(c); }
 
 // Host-pointer search of one or several requests with the same k as ONE device batch: borrowed host buffers -> pooled pinned
 // slab -> HBM (async DMA on the call's own stream), and back; every request gets its rows of the result.
-static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, int k, const lb_cancel *ctx)
+// (f16_call: the requests' queries are fp16 -- 2 bytes an element; never combined)
+static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, int k, const lb_cancel *ctx, bool f16_call = false)
 {
+    const size_t qelem = f16_call ? 2 : sizeof(float);
     int64_t nq = 0;
     for (int i = 0; i < nreq; i++) nq += reqs[i]->nq;
     // (before any staging is sized: nq * k * 12 bytes of pinned + device memory per call)
     if (k > LB_MAX_K) { h->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
     if (nq > ((int64_t)1 << 40) / ((int64_t)h->dim + 3 * (int64_t)k)) { h->set_error("batch too large"); return LB_ERR_INVALID_ARG; }
-    const size_t qb = (size_t)nq * h->dim * sizeof(float);
+    const size_t qb = (size_t)nq * h->dim * qelem;
     const size_t db = (((size_t)nq * k * sizeof(float)) + 15) & ~(size_t)15;
     const size_t lb_ = (size_t)nq * k * sizeof(int64_t);
     const size_t qoff = 0, doff = (qb + 15) & ~(size_t)15, loff = doff + db, total = loff + lb_;
@@ -2121,7 +2273,7 @@ static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, in
         {
             size_t off = qoff;
             for (int i = 0; i < nreq; i++) {
-                const size_t b = (size_t)reqs[i]->nq * h->dim * sizeof(float);
+                const size_t b = (size_t)reqs[i]->nq * h->dim * qelem;
                 std::memcpy(hb + off, reqs[i]->q, b);
                 off += b;
             }
@@ -2132,9 +2284,8 @@ static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, in
         // synchronisation is what makes them visible.  Large results go through HBM and one DMA.
         const bool direct = db + lb_ <= ((size_t)64 << 10);
         char *obuf = direct ? hb : dbuf;
-        rc = lb_gpu_index_search_device_ctx(h, nq, reinterpret_cast<const float *>(dbuf + qoff), k,
-                                            reinterpret_cast<float *>(obuf + doff), reinterpret_cast<int64_t *>(obuf + loff),
-                                            st->stream, ctx);
+        rc = search_device(h, nq, dbuf + qoff, k, reinterpret_cast<float *>(obuf + doff), reinterpret_cast<int64_t *>(obuf + loff),
+                           st->stream, ctx, f16_call);
         if (rc == LB_OK) {
             if (!direct) {
                 LB_HIP(hipMemcpyAsync(hb + doff, dbuf + doff, db + lb_, hipMemcpyDeviceToHost, st->stream));
@@ -2167,6 +2318,7 @@ int lb_gpu_index_search_ctx(lb_gpu_index *h, int64_t nq, const float *queries, i
     {
         std::shared_lock<std::shared_mutex> g(h->mu);
         if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
+        if (const int rc = dtype_mismatch(h, false)) return rc;
     }
     // (a call with a cancellation context is searched on its own: its deadline is not its neighbours')
     HostReq me{queries, nq, dist, labels, k};
@@ -2174,6 +2326,25 @@ int lb_gpu_index_search_ctx(lb_gpu_index *h, int64_t nq, const float *queries, i
         return h->combiner.search(me, [h](HostReq *const *reqs, int n, int kk) { return host_search_multi(h, reqs, n, kk, nullptr); });
     HostReq *one = &me;
     return host_search_multi(h, &one, 1, k, ctx);
+}
+
+int lb_gpu_index_search_f16_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *queries, int k, float *dist, int64_t *labels,
+                                const lb_cancel *ctx)
+{
+    if (!h || nq < 0 || k <= 0 || (nq > 0 && (!queries || !dist || !labels))) return LB_ERR_INVALID_ARG;
+    if (nq == 0) return LB_OK;
+    {
+        std::shared_lock<std::shared_mutex> g(h->mu);
+        if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
+        if (const int rc = dtype_mismatch(h, true)) return rc;
+    }
+    HostReq me{reinterpret_cast<const float *>(queries), nq, dist, labels, k}; // (fp16 bits: host_search_multi copies bytes)
+    HostReq *one = &me;
+    return host_search_multi(h, &one, 1, k, ctx, /*f16_call=*/true);
+}
+int lb_gpu_index_search_f16(lb_gpu_index *h, int64_t nq, const uint16_t *queries, int k, float *dist, int64_t *labels)
+{
+    return lb_gpu_index_search_f16_ctx(h, nq, queries, k, dist, labels, nullptr);
 }
 
 int lb_gpu_index_set_search_combining(lb_gpu_index *h, int enable)
@@ -2254,6 +2425,7 @@ int lb_gpu_index_rerank_device(lb_gpu_index *h, const float *d_query, const int6
     if (n > (int64_t)0x7fffffff) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
+    if (h->f16_rows) { h->set_error("re-rank reads float32 rows: not available on a float16 index"); return LB_ERR_UNSUPPORTED; }
     try {
         LB_HIP(hipSetDevice(h->device));
         const int ord = order == -1 ? h->order.load() : order;
@@ -2291,6 +2463,7 @@ int lb_gpu_index_rerank(lb_gpu_index *h, const float *query, const int64_t *rows
     if (!h || n < 0) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     if (!query || !rows || !dist) return LB_ERR_INVALID_ARG;
+    if (h->f16_rows) { h->set_error("re-rank reads float32 rows: not available on a float16 index"); return LB_ERR_UNSUPPORTED; }
     try {
         LB_HIP(hipSetDevice(h->device));
         // [query | rows] up through one pinned block, [dist | score] back through another

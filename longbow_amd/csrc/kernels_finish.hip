@@ -43,8 +43,9 @@ constexpr int FN_DK = 32, FN_LDT = FN_DK + 4;                 // tiled: 256 rows
 __device__ unsigned long long g_finish_probe[8]; // [0] members summed over queries, [1] queries, [2] list entries summed, [3] largest member count
 #endif
 
-struct FinishArgs {
-    const float *X;
+template <typename T> // the row element: float, or _Float16 (an fp16 index)
+struct FinishArgsT {
+    const T *X;
     int D;
     const float *Q;
     const float *qna; // cosine: exact ||q||^2 per query in the requested order
@@ -78,6 +79,7 @@ struct FinishArgs {
     float *xcmp;      // [nq][smax] compare values
     int abl;          // diagnostic build: timing-only ablations (1 = no gather / exact sums, 2 = no radix select, 3 = return at once)
 };
+using FinishArgs = FinishArgsT<float>;
 
 // exactly `need` (>= 1) of the real entries held in registers are <= the returned pivot (entries are unique).
 // hist[256], wsum[4], scal[8], red[2]: LDS scratch.  All threads of the workgroup call it.
@@ -180,8 +182,10 @@ __device__ __forceinline__ float out_slack(float cutf, float dk, float nq2, floa
     return 1.1f * (ga + go) * nqn * xmax + 2e-6f * fabsf(cutf);
 }
 
-template <int METRIC, int ORDER, bool SPLIT, int PER>
-__global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
+// RowT = _Float16 (an fp16 index): every member is scored by one lane straight from its fp16 row, each element widened to f32
+// (exact) and summed in the reference's order -- the staged forms below are the f32 rows'.
+template <typename RowT, int METRIC, int ORDER, bool SPLIT, int PER>
+__global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t hist[256];
@@ -347,6 +351,15 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgs a)
     if (a.posmap) __syncthreads();
 
     // ---- exact values of the members: skey[c], scmp[c], c < nm --------------------------------------------------------
+    if constexpr (sizeof(RowT) == 2) {
+        for (uint32_t c = tid; c < nm; c += FN_THREADS) {
+            float t, nbt, dist, cmp;
+            exact_pair_sums<METRIC, ORDER>(a.X + (int64_t)s_rows[c] * D, q, D, t, nbt);
+            member_values<METRIC>(t, nbt, na, D, dist, cmp);
+            skey[c] = pack_entry(dist, s_rows[c]);
+            scmp[c] = cmp;
+        }
+    } else
 #ifdef LB_DIAG
     if (a.abl == 1) {
         for (uint32_t c = tid; c < nm; c += FN_THREADS) {
@@ -743,14 +756,15 @@ void read_finish_probe(unsigned long long out[8], bool reset)
 size_t finish_scratch_bytes(int nq_split_max, uint32_t smax) { return (size_t)nq_split_max * smax * 12; }
 
 // smax: members a query may have; the split form serves up to `nq_split_max` queries (scratch xent / xcmp sized for them)
-void launch_finish(int metric, int order, const float *X, int D, const float *Q, int nq, const float *qna, CandState cs, int k,
+template <typename T>
+static void launch_finish_rows(int metric, int order, const T *X, int D, const float *Q, int nq, const float *qna, CandState cs, int k,
                    const uint32_t *d_maxnorm2, float gamma, float beta, const int64_t *ids, const uint32_t *posmap, float *out_dist,
                    int64_t *out_labels, hipStream_t s, uint32_t *flags_host, uint32_t *done, uint32_t *xcnt, void *xscratch,
                    int nq_split_max, uint32_t smax, const float *center, const float *lb_norm2, const float *lb_qnrm, float lb_gsum,
                    const float *qrho, float qrho_k)
 {
     if (nq <= 0) return;
-    FinishArgs a;
+    FinishArgsT<T> a;
     a.qrho = qrho;
     a.qrho_k = qrho_k;
     a.center = metric == METRIC_L2 ? center : nullptr;
@@ -763,7 +777,7 @@ void launch_finish(int metric, int order, const float *X, int D, const float *Q,
     a.abl = lb_tunable("LB_FINISH_ABL", 0);
     a.xent = reinterpret_cast<uint64_t *>(xscratch);
     a.xcmp = reinterpret_cast<float *>(a.xent + (size_t)nq_split_max * smax);
-    a.aligned = (D % 4 == 0) && D >= 4 && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
+    a.aligned = sizeof(T) == 4 && (D % 4 == 0) && D >= 4 && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
     const bool big = cs.cap > 8192u; // list entries per thread: 32 (cap 8192) or 64 (k > 512: cap 16384)
     const size_t common = (size_t)smax * 16;
     const size_t sh_split = common + ((size_t)FN_R16 * FN_LD16 + FN_SD) * 4;
@@ -806,9 +820,9 @@ void launch_finish(int metric, int order, const float *X, int D, const float *Q,
 #define LB_FN(M, O, S, P)                                                                                  \
     do {                                                                                                   \
         if (shmem > 64 * 1024)                                                                             \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(finish_kernel<M, O, S, P>),          \
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(finish_kernel<T, M, O, S, P>),          \
                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);             \
-        hipLaunchKernelGGL((finish_kernel<M, O, S, P>), grid, dim3(FN_THREADS), shmem, s, a);              \
+        hipLaunchKernelGGL((finish_kernel<T, M, O, S, P>), grid, dim3(FN_THREADS), shmem, s, a);              \
     } while (0)
 #define LB_FN_O(M, O)                              \
     do {                                           \
@@ -831,6 +845,25 @@ void launch_finish(int metric, int order, const float *X, int D, const float *Q,
 #undef LB_FN_M
 #undef LB_FN_O
 #undef LB_FN
+}
+
+void launch_finish(int metric, int order, const float *X, int D, const float *Q, int nq, const float *qna, CandState cs, int k,
+                   const uint32_t *d_maxnorm2, float gamma, float beta, const int64_t *ids, const uint32_t *posmap, float *out_dist,
+                   int64_t *out_labels, hipStream_t s, uint32_t *flags_host, uint32_t *done, uint32_t *xcnt, void *xscratch,
+                   int nq_split_max, uint32_t smax, const float *center, const float *lb_norm2, const float *lb_qnrm, float lb_gsum,
+                   const float *qrho, float qrho_k)
+{
+    launch_finish_rows(metric, order, X, D, Q, nq, qna, cs, k, d_maxnorm2, gamma, beta, ids, posmap, out_dist, out_labels, s, flags_host, done, xcnt,
+                       xscratch, nq_split_max, smax, center, lb_norm2, lb_qnrm, lb_gsum, qrho, qrho_k);
+}
+void launch_finish(int metric, int order, const _Float16 *X, int D, const float *Q, int nq, const float *qna, CandState cs, int k,
+                   const uint32_t *d_maxnorm2, float gamma, float beta, const int64_t *ids, const uint32_t *posmap, float *out_dist,
+                   int64_t *out_labels, hipStream_t s, uint32_t *flags_host, uint32_t *done, uint32_t *xcnt, void *xscratch,
+                   int nq_split_max, uint32_t smax, const float *center, const float *lb_norm2, const float *lb_qnrm, float lb_gsum,
+                   const float *qrho, float qrho_k)
+{
+    launch_finish_rows(metric, order, X, D, Q, nq, qna, cs, k, d_maxnorm2, gamma, beta, ids, posmap, out_dist, out_labels, s, flags_host, done, xcnt,
+                       xscratch, nq_split_max, smax, center, lb_norm2, lb_qnrm, lb_gsum, qrho, qrho_k);
 }
 
 } // namespace lb

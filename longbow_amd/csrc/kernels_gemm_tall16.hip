@@ -1363,10 +1363,11 @@ __global__ __launch_bounds__(256) void queries_to_f16_kernel(const float *Q, int
     if (lane == 0) qinv[q] = inv;
 }
 
-// f32 corpus rows [row_begin, row_end) -> the blocked fp16 image Xh[Dp / H_XP][cap][H_XP] (round to nearest even, the conversion
+// corpus rows [row_begin, row_end) (f32, or fp16 on an fp16 index: a relayout, exact unless centred) -> the blocked fp16 image Xh[Dp / H_XP][cap][H_XP] (round to nearest even, the conversion
 // the kernels above apply in registers: both forms of the route see the same fp16 values; dimensions beyond D are zero).
 // One workgroup = 64 rows x 32 dimensions: whole 128-B lines in, 64-B pieces out.
-__global__ __launch_bounds__(256) void corpus_to_f16_kernel(const float *X, int64_t row_begin, int64_t row_end, int D, _Float16 *Xh, int64_t cap,
+template <typename T>
+__global__ __launch_bounds__(256) void corpus_to_f16_kernel(const T *X, int64_t row_begin, int64_t row_end, int D, _Float16 *Xh, int64_t cap,
                                                             const float *center)
 {
     const int64_t row = row_begin + (int64_t)blockIdx.x * 64 + (threadIdx.x >> 2);
@@ -1375,14 +1376,16 @@ __global__ __launch_bounds__(256) void corpus_to_f16_kernel(const float *X, int6
     const int k0 = kb * 32 + q * 8;
     f16x8 v;
     if (center) { // the centred image (L2): fp16(x - center), the subtraction in f32
-        const float *src = X + row * (int64_t)D;
+        const T *src = X + row * (int64_t)D;
 #pragma unroll
-        for (int e = 0; e < 8; e++) v[e] = k0 + e < D ? (_Float16)(src[k0 + e] - center[k0 + e]) : (_Float16)0.f;
-    } else if (k0 + 8 <= D && (D & 3) == 0) { // (rows are 16-B aligned when D % 4 == 0)
+        for (int e = 0; e < 8; e++) v[e] = k0 + e < D ? (_Float16)((float)src[k0 + e] - center[k0 + e]) : (_Float16)0.f;
+    } else if (sizeof(T) == 4 && k0 + 8 <= D && (D & 3) == 0) { // (rows are 16-B aligned when D % 4 == 0)
         const f32x4 *src = reinterpret_cast<const f32x4 *>(X + row * (int64_t)D + k0);
         v = cvt_f16x8(src[0], src[1]);
+    } else if (sizeof(T) == 2 && k0 + 8 <= D && (D & 7) == 0) { // fp16 rows: eight elements are one 16-B piece, copied
+        v = *reinterpret_cast<const f16x8 *>(X + row * (int64_t)D + k0);
     } else { // the last block of a dimension that is not a multiple of 32 (zero beyond D), or unaligned rows
-        const float *src = X + row * (int64_t)D;
+        const T *src = X + row * (int64_t)D;
 #pragma unroll
         for (int e = 0; e < 8; e++) v[e] = k0 + e < D ? (_Float16)src[k0 + e] : (_Float16)0.f;
     }
@@ -1394,16 +1397,18 @@ __global__ __launch_bounds__(256) void corpus_to_f16_kernel(const float *X, int6
 // measured ratios (~0.3 x 2^-11 for data that fills the mantissa) the candidate keys' rigorous error bound is a third to a half
 // of the per-element worst case 2^-11 + 2^-11 -- and with it the rows the finish launch has to score exactly.  (Elements that
 // fall into fp16's subnormal range or flush to zero are in the residual like everything else.)
-__global__ __launch_bounds__(256) void f16_residual_kernel(const float *X, int64_t row_begin, int64_t row_end, int D, const float *center,
+// (fp16 rows: without a centre the image IS the rows and the residual is 0)
+template <typename T>
+__global__ __launch_bounds__(256) void f16_residual_kernel(const T *X, int64_t row_begin, int64_t row_end, int D, const float *center,
                                                           uint32_t *stat)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = row_begin + (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= row_end) return;
-    const float *src = X + row * (int64_t)D;
+    const T *src = X + row * (int64_t)D;
     float r2 = 0.f, n2 = 0.f;
     for (int i = lane; i < D; i += 64) {
-        const float v = center ? src[i] - center[i] : src[i];
+        const float v = center ? (float)src[i] - center[i] : (float)src[i];
         const float d = v - (float)(_Float16)v; // (exact: the two are within a factor of two of each other, or the second is 0)
         r2 = fmaf(d, d, r2);
         n2 = fmaf(v, v, n2);
@@ -1425,7 +1430,13 @@ __global__ __launch_bounds__(256) void f16_residual_kernel(const float *X, int64
 void launch_f16_residual(const float *X, int64_t row_begin, int64_t row_end, int D, const float *center, uint32_t *stat, hipStream_t s)
 {
     if (row_end <= row_begin) return;
-    hipLaunchKernelGGL(f16_residual_kernel, dim3((unsigned)((row_end - row_begin + 3) / 4)), dim3(256), 0, s, X, row_begin, row_end, D, center, stat);
+    hipLaunchKernelGGL(f16_residual_kernel<float>, dim3((unsigned)((row_end - row_begin + 3) / 4)), dim3(256), 0, s, X, row_begin, row_end, D, center, stat);
+}
+void launch_f16_residual(const _Float16 *X, int64_t row_begin, int64_t row_end, int D, const float *center, uint32_t *stat, hipStream_t s)
+{
+    if (row_end <= row_begin) return;
+    hipLaunchKernelGGL(f16_residual_kernel<_Float16>, dim3((unsigned)((row_end - row_begin + 3) / 4)), dim3(256), 0, s, X, row_begin, row_end, D,
+                       center, stat);
 }
 
 #ifdef LB_DIAG
@@ -1446,7 +1457,15 @@ void launch_corpus_to_f16(const float *X, int64_t row_begin, int64_t row_end, in
 {
     if (row_end <= row_begin) return;
     dim3 grid((unsigned)((row_end - row_begin + 63) / 64), (unsigned)(((D + H_XP - 1) / H_XP) * (H_XP / 32))); // (whole planes: zero padding)
-    hipLaunchKernelGGL(corpus_to_f16_kernel, grid, dim3(256), 0, s, X, row_begin, row_end, D, reinterpret_cast<_Float16 *>(Xh), cap, center);
+    hipLaunchKernelGGL(corpus_to_f16_kernel<float>, grid, dim3(256), 0, s, X, row_begin, row_end, D, reinterpret_cast<_Float16 *>(Xh), cap, center);
+}
+void launch_corpus_to_f16(const _Float16 *X, int64_t row_begin, int64_t row_end, int D, void *Xh, int64_t cap, hipStream_t s,
+                          const float *center)
+{
+    if (row_end <= row_begin) return;
+    dim3 grid((unsigned)((row_end - row_begin + 63) / 64), (unsigned)(((D + H_XP - 1) / H_XP) * (H_XP / 32)));
+    hipLaunchKernelGGL(corpus_to_f16_kernel<_Float16>, grid, dim3(256), 0, s, X, row_begin, row_end, D, reinterpret_cast<_Float16 *>(Xh), cap,
+                       center);
 }
 
 void launch_queries_to_f16(const float *Q, int nq, int D, void *Qh, float *qinv, hipStream_t s)

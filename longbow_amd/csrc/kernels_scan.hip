@@ -26,8 +26,9 @@ constexpr int SC_ROWS = 128;   // rows per tile == threads per workgroup
 constexpr int SC_DK = 64;      // floats per row per stage
 constexpr int SC_LD = SC_DK + 4; // padded LDS row stride (floats): conflict-free ds_read_b128
 
-struct ScanArgs {
-    const float *X;
+template <typename T> // the row element: float, or _Float16 (an fp16 index's rows, widened to f32 after the load)
+struct ScanArgsT {
+    const T *X;
     int64_t row_begin, row_end;
     int D;
     const float *Q;
@@ -44,14 +45,21 @@ struct ScanArgs {
     int boot;
     int striped; // admissions go through cs.stripes (slot = position in the launch's slot list)
 };
+using ScanArgs = ScanArgsT<float>;
+
+// one 16-B load of row elements: four f32, or eight fp16
+template <typename T> struct RowPiece { typedef f32x4 type; };
+template <> struct RowPiece<_Float16> { typedef f16x8 type; };
 
 // MAPPED: positions [row_begin,row_end) index a.rowmap (the visible rows under a filter) instead of the corpus.
 // NBUF: LDS stages.  2 = write the next stage while the current one is read (69.6 KB, 2 workgroups/CU);
 // 1 = one stage + an extra barrier (34.8 KB, 4 workgroups/CU: twice the bytes in flight per CU).
 // The (tile, chunk) sequence of a workgroup is one flat pipeline: the first chunk of the next tile
 // is already in flight while the last chunk of the current tile is consumed.
-template <int METRIC, int ORDER, int NQ, bool MAPPED, int NBUF>
-__global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgs a)
+// T = _Float16 (an fp16 index): a row chunk of 64 elements is 8 loads of 16 B per thread instead of 16, widened to f32
+// (v_cvt_f32_f16, exact) as the stage is written; the LDS stage and everything after it are the f32 kernel's.
+template <typename T, int METRIC, int ORDER, int NQ, bool MAPPED, int NBUF>
+__global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgsT<T> a)
 {
     // one __shared__ object: [stage][rows | query chunk]
     constexpr int STAGE_F = SC_ROWS * SC_LD + NQ * SC_DK;
@@ -84,9 +92,13 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgs a)
         q_src = a.Q + (int64_t)(a.qsel ? a.qsel[j] : j) * D;
     }
 
-    f32x4 stg[16];
+    constexpr int EPP = 16 / (int)sizeof(T);   // row elements per 16-B piece
+    constexpr int PPR = SC_DK / EPP;           // pieces per row chunk == loads per thread per stage
+    constexpr int PSH = PPR == 16 ? 4 : 3;     // log2(PPR)
+    typedef typename RowPiece<T>::type Piece;
+    Piece stg[PPR];
     f32x4 stq = {0.f, 0.f, 0.f, 0.f};
-    uint32_t rid[MAPPED ? 16 : 1]; // MAPPED: corpus rows behind this thread's 16 staging slots of the tile being loaded
+    uint32_t rid[MAPPED ? PPR : 1]; // MAPPED: corpus rows behind this thread's PPR staging slots of the tile being loaded
     auto load_stage = [&](int64_t tile, int c) {
         const int64_t trow0 = a.row_begin + tile * SC_ROWS;
         const int d0 = c * SC_DK;
@@ -97,30 +109,37 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgs a)
         }
         if (MAPPED && c == 0) {
 #pragma unroll
-            for (int i = 0; i < 16; i++) {
-                int64_t pos = trow0 + ((tid + SC_ROWS * i) >> 4);
+            for (int i = 0; i < PPR; i++) {
+                int64_t pos = trow0 + ((tid + SC_ROWS * i) >> PSH);
                 if (pos >= a.row_end) pos = a.row_end - 1;
                 rid[MAPPED ? i : 0] = a.rowmap[pos];
             }
         }
 #pragma unroll
-        for (int i = 0; i < 16; i++) {
+        for (int i = 0; i < PPR; i++) {
             const int ch = tid + SC_ROWS * i;
-            const int r = ch >> 4, p = ch & 15;
+            const int r = ch >> PSH, p = ch & (PPR - 1);
             int64_t row = trow0 + r;
             if (row >= a.row_end) row = a.row_end - 1;
             if (MAPPED) row = rid[MAPPED ? i : 0];
-            int k = d0 + p * 4;
-            if (k > D - 4) k = D - 4; // D % 4 == 0 here; chunks past D are never consumed
-            stg[i] = __builtin_nontemporal_load(reinterpret_cast<const f32x4 *>(a.X + row * (int64_t)D + k)); // streamed once
+            int k = d0 + p * EPP;
+            if (k > D - EPP) k = D - EPP; // D % EPP == 0 here; chunks past D are never consumed
+            stg[i] = __builtin_nontemporal_load(reinterpret_cast<const Piece *>(a.X + row * (int64_t)D + k)); // streamed once
         }
     };
     auto write_stage = [&](int st) {
 #pragma unroll
-        for (int i = 0; i < 16; i++) {
+        for (int i = 0; i < PPR; i++) {
             const int ch = tid + SC_ROWS * i;
-            const int r = ch >> 4, p = ch & 15;
-            *reinterpret_cast<f32x4 *>(&lds[st][r * SC_LD + p * 4]) = stg[i];
+            const int r = ch >> PSH, p = ch & (PPR - 1);
+            if constexpr (EPP == 4) {
+                *reinterpret_cast<f32x4 *>(&lds[st][r * SC_LD + p * 4]) = stg[i];
+            } else {
+                const f32x4 lo = {(float)stg[i][0], (float)stg[i][1], (float)stg[i][2], (float)stg[i][3]};
+                const f32x4 hi = {(float)stg[i][4], (float)stg[i][5], (float)stg[i][6], (float)stg[i][7]};
+                *reinterpret_cast<f32x4 *>(&lds[st][r * SC_LD + p * 8]) = lo;
+                *reinterpret_cast<f32x4 *>(&lds[st][r * SC_LD + p * 8 + 4]) = hi;
+            }
         }
         if (q_loader)
             *reinterpret_cast<f32x4 *>(&lds[st][SC_ROWS * SC_LD + (tid >> 4) * SC_DK + (tid & 15) * 4]) = stq;
@@ -236,10 +255,10 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgs a)
 }
 
 
-// Generic fallback for D % 4 != 0 (or a misaligned base): one lane per row walks its row
+// Generic fallback for D % 4 != 0 (fp16 rows: D % 8 != 0) or a misaligned base: one lane per row walks its row
 // straight from global memory.  Same arithmetic, no staging; correctness path only.
-template <int METRIC, int ORDER>
-__global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a)
+template <typename T, int METRIC, int ORDER>
+__global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgsT<T> a)
 {
     const int D = a.D;
     for (int64_t pos = a.row_begin + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; pos < a.row_end;
@@ -251,7 +270,7 @@ __global__ __launch_bounds__(256) void scan_generic_kernel(ScanArgs a)
                     a.cs.lists[(size_t)(a.qsel ? a.qsel[j] : j) * a.cs.cap + (pos - a.row_begin)] = kEntryMax;
             continue;
         }
-        const float *x = a.X + row * (int64_t)D;
+        const T *x = a.X + row * (int64_t)D;
         for (int j = 0; j < a.nsel; j++) {
             const int qj = a.qsel ? a.qsel[j] : j;
             const float *q = a.Q + (int64_t)qj * D;
@@ -320,8 +339,9 @@ void launch_query_norms(int order, const float *Q, const int *qsel, int nsel, in
 constexpr int SS_MAXQ = 8;        // query slots scored together (register accumulators)
 constexpr int SS_MAX_SLOTS = 64;  // query slots per launch (groups of SS_MAXQ)
 
-struct SampleArgs {
-    const float *X;
+template <typename T> // the row element (as ScanArgsT)
+struct SampleArgsT {
+    const T *X;
     int D;
     int64_t span;
     uint32_t count;
@@ -348,6 +368,16 @@ struct SampleArgs {
     float *qrho = nullptr;
     float rho_gain = 0.f;
 };
+using SampleArgs = SampleArgsT<float>;
+
+// four row elements as f32 (fp16: one 8-B load, widened exactly)
+__device__ __forceinline__ f32x4 load_row4(const float *p) { return *reinterpret_cast<const f32x4 *>(p); }
+__device__ __forceinline__ f32x4 load_row4(const _Float16 *p)
+{
+    typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+    const f16x4 v = *reinterpret_cast<const f16x4 *>(p);
+    return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
+}
 
 __device__ __forceinline__ float wave_sum(float v)
 {
@@ -458,13 +488,13 @@ void launch_query_prep(const float *Q, int nq, int D, void *Qh, float *qinv, flo
 // R = sampled rows per wave: every query chunk fetched from L2 is used for R rows (with 32 query
 // slots and R = 1 the launch is bound by 8192 x 96 KB of L2 reads: 97 us; R = 4: a quarter of that)
 // one wave scores sample rows i0 .. i0 + R against every query slot
-template <int METRIC, int R>
-__device__ __forceinline__ void sample_wave(const SampleArgs &a, uint32_t i0, int lane)
+template <typename T, int METRIC, int R>
+__device__ __forceinline__ void sample_wave(const SampleArgsT<T> &a, uint32_t i0, int lane)
 {
     const int D = a.D;
     int64_t row[R];
     bool live[R], hidden[R];
-    const float *x[R];
+    const T *x[R];
 #pragma unroll
     for (int r = 0; r < R; r++) {
         uint32_t i = i0 + r;
@@ -502,7 +532,7 @@ __device__ __forceinline__ void sample_wave(const SampleArgs &a, uint32_t i0, in
                     const int k = k0 + 256 * u;
 #pragma unroll
                     for (int r = 0; r < R; r++)
-                        if (k < D) xw[u][r] = *reinterpret_cast<const f32x4 *>(x[r] + k);
+                        if (k < D) xw[u][r] = load_row4(x[r] + k);
                 }
 #pragma unroll
                 for (int u = 0; u < PF; u++) {
@@ -539,7 +569,7 @@ __device__ __forceinline__ void sample_wave(const SampleArgs &a, uint32_t i0, in
                 float xv[R];
 #pragma unroll
                 for (int r = 0; r < R; r++) {
-                    xv[r] = x[r][k];
+                    xv[r] = (float)x[r][k];
                     if (a.center) xv[r] -= a.center[k];
                     if (want_norms) xx[r] += xv[r] * xv[r];
                 }
@@ -595,8 +625,8 @@ __device__ __forceinline__ void sample_wave(const SampleArgs &a, uint32_t i0, in
     }
 }
 
-template <int METRIC, int R>
-__global__ __launch_bounds__(256) void sample_scores_kernel(SampleArgs a)
+template <typename T, int METRIC, int R>
+__global__ __launch_bounds__(256) void sample_scores_kernel(SampleArgsT<T> a)
 {
     extern __shared__ __attribute__((aligned(16))) float sq[];
     const uint32_t nnorm = a.qna ? (uint32_t)a.nsel : 0u; // the serial norm chains are dispatched first
@@ -621,16 +651,17 @@ __global__ __launch_bounds__(256) void sample_scores_kernel(SampleArgs a)
     if (blk == 0 && (int)threadIdx.x < a.nsel) a.cs.flags[a.qsel ? a.qsel[threadIdx.x] : threadIdx.x] = 0;
     const uint32_t i0 = (blk * 4u + (uint32_t)wave) * R; // this wave's first sample index
     if (i0 >= a.count) return;
-    sample_wave<METRIC, R>(a, i0, lane);
+    sample_wave<T, METRIC, R>(a, i0, lane);
 }
 
-void launch_sample_scores(int metric, int order, const float *X, int D, int64_t span, uint32_t count,
-                          const uint32_t *rowmap, const uint8_t *mask, const float *Q, const int *qsel, int nsel,
-                          CandState cs, float *qna, hipStream_t s, const float *norm2, const float *rnorm, const float *center,
-                          const SamplePrep *prep)
+template <typename T>
+static void launch_sample_scores_rows(int metric, int order, const T *X, int D, int64_t span, uint32_t count,
+                                      const uint32_t *rowmap, const uint8_t *mask, const float *Q, const int *qsel, int nsel,
+                                      CandState cs, float *qna, hipStream_t s, const float *norm2, const float *rnorm,
+                                      const float *center, const SamplePrep *prep)
 {
     if (count == 0 || nsel <= 0) return;
-    SampleArgs a;
+    SampleArgsT<T> a;
     if (prep && qsel == nullptr && nsel <= SS_MAX_SLOTS) {
         a.Qh = reinterpret_cast<_Float16 *>(prep->Qh);
         a.qinv = prep->qinv;
@@ -648,22 +679,37 @@ void launch_sample_scores(int metric, int order, const float *X, int D, int64_t 
     a.order = order;
     a.X = X; a.D = D; a.span = span; a.count = count; a.rowmap = rowmap; a.mask = mask;
     a.Q = Q; a.qsel = qsel; a.nsel = nsel < SS_MAX_SLOTS ? nsel : SS_MAX_SLOTS; a.cs = cs;
-    a.aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
+    a.aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & (4 * sizeof(T) - 1)) == 0) && ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
     static const int env_r = lb_tunable("LB_SAMPLE_ROWS_PER_WAVE", 0);
     const int R = (env_r == 1 || env_r == 2 || env_r == 4) ? env_r : (a.nsel > SS_MAXQ ? 4 : a.nsel > 4 ? 2 : 1); // measured at 8 slots: 61 -> 53 us for sample + threshold + select
     a.nblocks = (count + 4 * R - 1) / (4 * R);
     dim3 grid(a.nblocks + (a.qna ? (unsigned)a.nsel : 0u) + (a.Qh ? (unsigned)a.nsel : 0u)), block(256);
     const size_t shmem = (a.qna || a.Qh) ? (size_t)((D + 3) & ~3) * sizeof(float) : 0;
-#define LB_SS(M)                                                                                      \
-    do {                                                                                              \
-        if (R == 4) hipLaunchKernelGGL((sample_scores_kernel<M, 4>), grid, block, shmem, s, a);       \
-        else if (R == 2) hipLaunchKernelGGL((sample_scores_kernel<M, 2>), grid, block, shmem, s, a);  \
-        else hipLaunchKernelGGL((sample_scores_kernel<M, 1>), grid, block, shmem, s, a);              \
+#define LB_SS(M)                                                                                        \
+    do {                                                                                                \
+        if (R == 4) hipLaunchKernelGGL((sample_scores_kernel<T, M, 4>), grid, block, shmem, s, a);      \
+        else if (R == 2) hipLaunchKernelGGL((sample_scores_kernel<T, M, 2>), grid, block, shmem, s, a); \
+        else hipLaunchKernelGGL((sample_scores_kernel<T, M, 1>), grid, block, shmem, s, a);             \
     } while (0)
     if (metric == METRIC_L2) LB_SS(METRIC_L2);
     else if (metric == METRIC_COS) LB_SS(METRIC_COS);
     else LB_SS(METRIC_DOT);
 #undef LB_SS
+}
+
+void launch_sample_scores(int metric, int order, const float *X, int D, int64_t span, uint32_t count,
+                          const uint32_t *rowmap, const uint8_t *mask, const float *Q, const int *qsel, int nsel,
+                          CandState cs, float *qna, hipStream_t s, const float *norm2, const float *rnorm, const float *center,
+                          const SamplePrep *prep)
+{
+    launch_sample_scores_rows(metric, order, X, D, span, count, rowmap, mask, Q, qsel, nsel, cs, qna, s, norm2, rnorm, center, prep);
+}
+void launch_sample_scores(int metric, int order, const _Float16 *X, int D, int64_t span, uint32_t count,
+                          const uint32_t *rowmap, const uint8_t *mask, const float *Q, const int *qsel, int nsel,
+                          CandState cs, float *qna, hipStream_t s, const float *norm2, const float *rnorm, const float *center,
+                          const SamplePrep *prep)
+{
+    launch_sample_scores_rows(metric, order, X, D, span, count, rowmap, mask, Q, qsel, nsel, cs, qna, s, norm2, rnorm, center, prep);
 }
 
 // tau[q] = m-th smallest of the first `count` entries of list q (row bits saturated), cnt[q] = 0.
@@ -820,51 +866,65 @@ void launch_sample_tau(CandState cs, const int *qsel, int nsel, uint32_t count, 
 
 int g_scan_nbuf = lb_tunable("LB_SCAN_NBUF", 1);
 
-template <int METRIC, int ORDER, int NQ>
-static void launch_scan_variant(dim3 grid, hipStream_t s, const ScanArgs &a)
+template <typename T, int METRIC, int ORDER, int NQ, bool MAPPED, int NBUF>
+static void launch_scan_kernel(dim3 grid, hipStream_t s, const ScanArgsT<T> &a)
+{
+    hipLaunchKernelGGL((scan_kernel<T, METRIC, ORDER, NQ, MAPPED, NBUF>), grid, dim3(SC_ROWS), 0, s, a);
+}
+
+template <typename T, int METRIC, int ORDER, int NQ>
+static void launch_scan_variant(dim3 grid, hipStream_t s, const ScanArgsT<T> &a)
 {
     if (g_scan_nbuf == 1) {
-        if (a.rowmap) hipLaunchKernelGGL((scan_kernel<METRIC, ORDER, NQ, true, 1>), grid, dim3(SC_ROWS), 0, s, a);
-        else hipLaunchKernelGGL((scan_kernel<METRIC, ORDER, NQ, false, 1>), grid, dim3(SC_ROWS), 0, s, a);
+        if (a.rowmap) launch_scan_kernel<T, METRIC, ORDER, NQ, true, 1>(grid, s, a);
+        else launch_scan_kernel<T, METRIC, ORDER, NQ, false, 1>(grid, s, a);
     } else {
-        if (a.rowmap) hipLaunchKernelGGL((scan_kernel<METRIC, ORDER, NQ, true, 2>), grid, dim3(SC_ROWS), 0, s, a);
-        else hipLaunchKernelGGL((scan_kernel<METRIC, ORDER, NQ, false, 2>), grid, dim3(SC_ROWS), 0, s, a);
+        if (a.rowmap) launch_scan_kernel<T, METRIC, ORDER, NQ, true, 2>(grid, s, a);
+        else launch_scan_kernel<T, METRIC, ORDER, NQ, false, 2>(grid, s, a);
     }
 }
 
-template <int METRIC, int ORDER>
-static void launch_scan_nq(int nq_t, dim3 grid, hipStream_t s, const ScanArgs &a)
+template <typename T, int METRIC, int ORDER>
+static void launch_scan_nq(int nq_t, dim3 grid, hipStream_t s, const ScanArgsT<T> &a)
 {
     switch (nq_t) {
-    case 1: launch_scan_variant<METRIC, ORDER, 1>(grid, s, a); break;
-    case 2: launch_scan_variant<METRIC, ORDER, 2>(grid, s, a); break;
-    case 4: launch_scan_variant<METRIC, ORDER, 4>(grid, s, a); break;
-    default: launch_scan_variant<METRIC, ORDER, 8>(grid, s, a); break;
+    case 1: launch_scan_variant<T, METRIC, ORDER, 1>(grid, s, a); break;
+    case 2: launch_scan_variant<T, METRIC, ORDER, 2>(grid, s, a); break;
+    case 4: launch_scan_variant<T, METRIC, ORDER, 4>(grid, s, a); break;
+    default: launch_scan_variant<T, METRIC, ORDER, 8>(grid, s, a); break;
     }
 }
 
-void launch_scan(int metric, int order, bool raw_dot, const float *X, int64_t row_begin,
-                      int64_t row_end, int D, const float *Q, const int *qsel, int nsel,
-                      const float *qna, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
-                      float *all_out, int64_t ld, hipStream_t s, bool striped)
+template <typename T, int METRIC, int ORDER>
+static void launch_scan_generic(dim3 g, dim3 b, hipStream_t s, const ScanArgsT<T> &a)
+{
+    hipLaunchKernelGGL((scan_generic_kernel<T, METRIC, ORDER>), g, b, 0, s, a);
+}
+
+template <typename T>
+static void launch_scan_rows(int metric, int order, bool raw_dot, const T *X, int64_t row_begin,
+                             int64_t row_end, int D, const float *Q, const int *qsel, int nsel,
+                             const float *qna, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
+                             float *all_out, int64_t ld, hipStream_t s, bool striped)
 {
     if (row_end <= row_begin || nsel <= 0) return;
-    ScanArgs a;
+    ScanArgsT<T> a;
     a.striped = (striped && cs.stripes != nullptr && !boot) ? 1 : 0;
     a.rowmap = rowmap;
     a.boot = boot ? 1 : 0;
     a.X = X; a.row_begin = row_begin; a.row_end = row_end; a.D = D;
     a.Q = Q; a.qsel = qsel; a.nsel = nsel; a.qna = qna; a.mask = mask; a.cs = cs;
     a.all_out = all_out; a.ld = ld; a.raw_dot = raw_dot ? 1 : 0;
-    a.aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
+    constexpr int EPP = 16 / (int)sizeof(T); // the staged kernel loads rows in 16-B pieces
+    a.aligned = (D % EPP == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
     if (!a.aligned) {
         int64_t blocks = (row_end - row_begin + 255) / 256;
         if (blocks > 4096) blocks = 4096;
         dim3 g((unsigned)blocks), b(256);
 #define LB_GEN(M)                                                                          \
     do {                                                                                   \
-        if (order == ORDER_UNROLL4) hipLaunchKernelGGL((scan_generic_kernel<M, ORDER_UNROLL4>), g, b, 0, s, a); \
-        else hipLaunchKernelGGL((scan_generic_kernel<M, ORDER_SEQ>), g, b, 0, s, a);        \
+        if (order == ORDER_UNROLL4) launch_scan_generic<T, M, ORDER_UNROLL4>(g, b, s, a);  \
+        else launch_scan_generic<T, M, ORDER_SEQ>(g, b, s, a);                             \
     } while (0)
         if (metric == METRIC_L2) LB_GEN(METRIC_L2);
         else if (metric == METRIC_COS) LB_GEN(METRIC_COS);
@@ -878,10 +938,10 @@ void launch_scan(int metric, int order, bool raw_dot, const float *X, int64_t ro
     const int64_t maxgrid = 256 * (g_scan_nbuf == 1 ? 4 : 2) * waves_mult;
     dim3 grid((unsigned)(ntiles < maxgrid ? ntiles : maxgrid));
     int nq_t = nsel <= 1 ? 1 : nsel <= 2 ? 2 : nsel <= 4 ? 4 : 8;
-#define LB_SCAN(M)                                                                       \
-    do {                                                                                 \
-        if (order == ORDER_UNROLL4) launch_scan_nq<M, ORDER_UNROLL4>(nq_t, grid, s, a);   \
-        else launch_scan_nq<M, ORDER_SEQ>(nq_t, grid, s, a);                              \
+#define LB_SCAN(M)                                                                          \
+    do {                                                                                    \
+        if (order == ORDER_UNROLL4) launch_scan_nq<T, M, ORDER_UNROLL4>(nq_t, grid, s, a);   \
+        else launch_scan_nq<T, M, ORDER_SEQ>(nq_t, grid, s, a);                              \
     } while (0)
     if (metric == METRIC_L2) LB_SCAN(METRIC_L2);
     else if (metric == METRIC_COS) LB_SCAN(METRIC_COS);
@@ -889,32 +949,50 @@ void launch_scan(int metric, int order, bool raw_dot, const float *X, int64_t ro
 #undef LB_SCAN
 }
 
+void launch_scan(int metric, int order, bool raw_dot, const float *X, int64_t row_begin,
+                      int64_t row_end, int D, const float *Q, const int *qsel, int nsel,
+                      const float *qna, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
+                      float *all_out, int64_t ld, hipStream_t s, bool striped)
+{
+    launch_scan_rows(metric, order, raw_dot, X, row_begin, row_end, D, Q, qsel, nsel, qna, mask, rowmap, cs, boot, all_out, ld, s,
+                     striped);
+}
+void launch_scan(int metric, int order, bool raw_dot, const _Float16 *X, int64_t row_begin,
+                      int64_t row_end, int D, const float *Q, const int *qsel, int nsel,
+                      const float *qna, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
+                      float *all_out, int64_t ld, hipStream_t s, bool striped)
+{
+    launch_scan_rows(metric, order, raw_dot, X, row_begin, row_end, D, Q, qsel, nsel, qna, mask, rowmap, cs, boot, all_out, ld, s,
+                     striped);
+}
+
 // ---------------------------------------------------------------------------
 // Row norms at Add time: one wave per row, coalesced float4 reads, wave reduction.
 // Used only for candidate keys and error bounds (never for reported distances).
 // ---------------------------------------------------------------------------
 // center (or null): the norms of x - center (the L2 keys over the centred fp16 image, index.hip: sync_f16_image); rnorm may be null
-__global__ __launch_bounds__(256) void row_norms_kernel(const float *X, int64_t n, int D,
+template <typename T>
+__global__ __launch_bounds__(256) void row_norms_kernel(const T *X, int64_t n, int D,
                                                         float *norm2, float *rnorm,
                                                         uint32_t *maxnorm2, int aligned, const float *center)
 {
     const int lane = threadIdx.x & 63;
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= n) return;
-    const float *x = X + row * (int64_t)D;
+    const T *x = X + row * (int64_t)D;
     float s = 0.f;
     if (center) {
         for (int i = lane; i < D; i += 64) {
-            const float v = x[i] - center[i];
+            const float v = (float)x[i] - center[i];
             s += v * v;
         }
     } else if (aligned) {
         for (int i = lane * 4; i < D; i += 256) {
-            const f32x4 v = *reinterpret_cast<const f32x4 *>(x + i);
+            const f32x4 v = load_row4(x + i);
             s += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
         }
     } else {
-        for (int i = lane; i < D; i += 64) s += x[i] * x[i];
+        for (int i = lane; i < D; i += 64) s += (float)x[i] * (float)x[i];
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
@@ -936,20 +1014,42 @@ void launch_row_norms(const float *X, int64_t n, int D, float *norm2, float *rno
     if (n <= 0) return;
     const int aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0);
     dim3 grid((unsigned)((n + 3) / 4));
-    hipLaunchKernelGGL(row_norms_kernel, grid, dim3(256), 0, s, X, n, D, norm2, rnorm, d_maxnorm2,
+    hipLaunchKernelGGL(row_norms_kernel<float>, grid, dim3(256), 0, s, X, n, D, norm2, rnorm, d_maxnorm2,
                        aligned, center);
+}
+void launch_row_norms(const _Float16 *X, int64_t n, int D, float *norm2, float *rnorm, uint32_t *d_maxnorm2, hipStream_t s,
+                      const float *center)
+{
+    if (n <= 0) return;
+    const int aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 7) == 0);
+    hipLaunchKernelGGL(row_norms_kernel<_Float16>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, s, X, n, D, norm2, rnorm, d_maxnorm2,
+                       aligned, center);
+}
+
+// fp16 queries -> the workspace's f32 query buffer (every fp16 value is an f32 exactly)
+__global__ __launch_bounds__(256) void widen_f16_kernel(const _Float16 *src, float *dst, int64_t n)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) dst[i] = (float)src[i];
+}
+void launch_widen_f16(const void *src, float *dst, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return;
+    const int64_t blocks = (n + 255) / 256;
+    hipLaunchKernelGGL(widen_f16_kernel, dim3((unsigned)(blocks < 4096 ? blocks : 4096)), dim3(256), 0, s,
+                       static_cast<const _Float16 *>(src), dst, n);
 }
 
 // Column means of X[0 .. n) in a fixed summation order (two stages: 256 partial sums per column, then their sum): the centre
 // the L2 keys of the fp16 image are taken about.  Any fixed vector would do -- L2 distances do not move when both sides are
 // shifted -- the mean makes the shifted norms, and with them the key errors, as small as a shift can.
-__global__ __launch_bounds__(256) void column_sums_kernel(const float *X, int64_t n, int D, float *partial)
+template <typename T>
+__global__ __launch_bounds__(256) void column_sums_kernel(const T *X, int64_t n, int D, float *partial)
 {
     const int64_t per = (n + gridDim.x - 1) / gridDim.x;
     const int64_t r0 = (int64_t)blockIdx.x * per, r1 = r0 + per < n ? r0 + per : n;
     for (int c = threadIdx.x; c < D; c += 256) {
         float acc = 0.f;
-        for (int64_t r = r0; r < r1; r++) acc += X[r * (int64_t)D + c];
+        for (int64_t r = r0; r < r1; r++) acc += (float)X[r * (int64_t)D + c];
         partial[(int64_t)blockIdx.x * D + c] = acc;
     }
 }
@@ -962,12 +1062,21 @@ __global__ __launch_bounds__(256) void column_mean_kernel(const float *partial, 
         for (int p = 0; p < nparts; p++) acc += partial[(int64_t)p * D + c];
     center[c] = c < D ? acc / (float)n : 0.f;
 }
+template <typename T>
+static void launch_column_means_rows(const T *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s)
+{
+    if (n <= 0) return;
+    hipLaunchKernelGGL(column_sums_kernel<T>, dim3(256), dim3(256), 0, s, X, n, D, partial);
+    hipLaunchKernelGGL(column_mean_kernel, dim3((unsigned)((Dpad + 255) / 256)), dim3(256), 0, s, partial, 256, D, n, center, Dpad);
+}
 void launch_column_means(const float *X, int64_t n, int D, float *partial /* [256][D] */, float *center /* [Dpad] */, int Dpad,
                          hipStream_t s)
 {
-    if (n <= 0) return;
-    hipLaunchKernelGGL(column_sums_kernel, dim3(256), dim3(256), 0, s, X, n, D, partial);
-    hipLaunchKernelGGL(column_mean_kernel, dim3((unsigned)((Dpad + 255) / 256)), dim3(256), 0, s, partial, 256, D, n, center, Dpad);
+    launch_column_means_rows(X, n, D, partial, center, Dpad, s);
+}
+void launch_column_means(const _Float16 *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s)
+{
+    launch_column_means_rows(X, n, D, partial, center, Dpad, s);
 }
 
 // ---------------------------------------------------------------------------

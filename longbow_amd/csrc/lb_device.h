@@ -265,8 +265,14 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 // center (or null): norms of x - center instead (rnorm may then be null)
 void launch_row_norms(const float *X, int64_t n, int D, float *norm2, float *rnorm,
                       uint32_t *d_maxnorm2, hipStream_t s, const float *center = nullptr);
+// the same over an fp16 index's rows (each element widened to f32 exactly)
+void launch_row_norms(const _Float16 *X, int64_t n, int D, float *norm2, float *rnorm, uint32_t *d_maxnorm2, hipStream_t s,
+                      const float *center = nullptr);
+// n fp16 values (IEEE binary16 bit patterns) -> f32, exactly
+void launch_widen_f16(const void *src, float *dst, int64_t n, hipStream_t s);
 // column means of X[0 .. n) in a fixed order -> center[0 .. Dpad) (zero beyond D); partial: [256][D] scratch
 void launch_column_means(const float *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);
+void launch_column_means(const _Float16 *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);
 
 // candidate generation: f32 MFMA inner products of queries [nq][D] x rows [row_begin,row_end)
 // -> metric key -> admit (key,row) < tau[q] into the query's list.
@@ -351,10 +357,14 @@ void launch_gemm_filter_tall16(int metric, const float *X, const float *norm2, c
                                                       // of |q| (launch_query_prep) and gamma_a + gamma_o -- the lower-bound key
                                const struct Tall16Tin *tin = nullptr); // thresholds inside the launch (tall16_tin_ok)
 void launch_corpus_to_f16(const float *X, int64_t row_begin, int64_t row_end, int D, void *Xh, int64_t cap, hipStream_t s,
+                          const float *center = nullptr);
+// the same from an fp16 index's rows: a relayout (exact), or fp16(x - center) with the subtraction in f32
+void launch_corpus_to_f16(const _Float16 *X, int64_t row_begin, int64_t row_end, int D, void *Xh, int64_t cap, hipStream_t s,
                           const float *center = nullptr); // center (or null; [>= D + 8]): the image holds fp16(x - center)
 // *stat = max(*stat, max over the rows of |x - fp16(x)|^2 / |x|^2) as float bits (x - center for the centred image): the
 // measured loss of the image, from which the candidate keys' error bound is taken (index.hip: gamma)
 void launch_f16_residual(const float *X, int64_t row_begin, int64_t row_end, int D, const float *center, uint32_t *stat, hipStream_t s);
+void launch_f16_residual(const _Float16 *X, int64_t row_begin, int64_t row_end, int D, const float *center, uint32_t *stat, hipStream_t s);
 int corpus_f16_plane_dims(); // dimensions per plane of that image (its rows are zero-padded to a multiple of it)
 // under a row list (mapped) the persistent kernels gather out of the image and leave POSITIONS of the list in the candidate
 // entries (the finish launch maps them back: posmap); true when a launch with these parameters does so
@@ -399,6 +409,11 @@ void launch_sample_scores(int metric, int order, const float *X, int D, int64_t 
                           const float *rnorm = nullptr,
                           const float *center = nullptr,  // keys mode, L2: keys about this centre (norm2 = the centred norms)
                           const SamplePrep *prep = nullptr);
+// the same over an fp16 index's rows (each element widened to f32 exactly)
+void launch_sample_scores(int metric, int order, const _Float16 *X, int D, int64_t span, uint32_t count,
+                          const uint32_t *rowmap, const uint8_t *mask, const float *Q, const int *qsel, int nsel,
+                          CandState cs, float *qna, hipStream_t s, const float *norm2 = nullptr, const float *rnorm = nullptr,
+                          const float *center = nullptr, const SamplePrep *prep = nullptr);
 // tau[q] = m-th smallest of lists[q][0..count) with the row bits saturated, cnt[q] = 0
 bool sample_tau_supported(uint32_t count, int m);
 // zero_stripes: also reset the slots' striped admission counters (at most 8 slots: the scan path)
@@ -419,6 +434,14 @@ void launch_finish(int metric, int order, const float *X, int D, const float *Q,
                    int nq_split_max, uint32_t smax,
                    const float *center = nullptr, // L2 keys taken about this centre: d_maxnorm2 = the centred maximum norm
                    const float *lb_norm2 = nullptr, const float *lb_qnrm = nullptr, float lb_gsum = 0.f, // dot: lower-bound keys
+                   const float *qrho = nullptr, float qrho_k = 0.f);
+// the same over an fp16 index's rows (one lane per member, straight from the row)
+void launch_finish(int metric, int order, const _Float16 *X, int D, const float *Q, int nq, const float *qna, CandState cs, int k,
+                   const uint32_t *d_maxnorm2, float gamma, float beta, const int64_t *ids, const uint32_t *posmap, float *out_dist,
+                   int64_t *out_labels, hipStream_t s, uint32_t *flags_host, uint32_t *done, uint32_t *xcnt, void *xscratch,
+                   int nq_split_max, uint32_t smax,
+                   const float *center = nullptr,
+                   const float *lb_norm2 = nullptr, const float *lb_qnrm = nullptr, float lb_gsum = 0.f,
                    const float *qrho = nullptr, float qrho_k = 0.f); // gamma(q) = gamma + qrho_k * qrho[q] (launch_query_prep)
 
 // ||q||^2 per selected query slot in the requested accumulation order (cosine).
@@ -429,6 +452,11 @@ void launch_query_norms(int order, const float *Q, const int *qsel, int nsel, in
 // qsel[0..nsel) (indices into Q, or identity when qsel==nullptr), admitted against tau.
 // If all_out != nullptr writes every distance to all_out[slot*ld + row] instead (simd batch API).
 void launch_scan(int metric, int order, bool raw_dot, const float *X, int64_t row_begin,
+                 int64_t row_end, int D, const float *Q, const int *qsel, int nsel,
+                 const float *qna, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
+                 float *all_out, int64_t ld, hipStream_t s, bool striped = false);
+// the same over an fp16 index's rows: each element is widened to f32 (exact) and the reference's f32 arithmetic runs on it
+void launch_scan(int metric, int order, bool raw_dot, const _Float16 *X, int64_t row_begin,
                  int64_t row_end, int D, const float *Q, const int *qsel, int nsel,
                  const float *qna, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
                  float *all_out, int64_t ld, hipStream_t s, bool striped = false);

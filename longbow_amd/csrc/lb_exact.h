@@ -91,8 +91,9 @@ __device__ __forceinline__ float exact_sq_norm_lds(const float *sq, int D, int o
 
 // The sums of one (row, query) pair, one lane, straight from memory (any D, any alignment): t = the metric's pair sum,
 // nbt = ||x||^2 (cosine; 0 otherwise).  exact_distance turns them into the result.
-template <int METRIC, int ORDER>
-__device__ __forceinline__ void exact_pair_sums(const float *x, const float *q, int D, float &t, float &nbt)
+// (T = _Float16: an fp16 index's row, each element widened to f32 exactly)
+template <int METRIC, int ORDER, typename T>
+__device__ __forceinline__ void exact_pair_sums(const T *x, const float *q, int D, float &t, float &nbt)
 {
 #pragma clang fp contract(off)
     Acc<ORDER> acc, nb;
@@ -100,13 +101,13 @@ __device__ __forceinline__ void exact_pair_sums(const float *x, const float *q, 
     nb.zero();
     const int dmain = D & ~3;
     for (int i = 0; i < dmain; i += 4) {
-        const f32x4 xv = {x[i], x[i + 1], x[i + 2], x[i + 3]};
+        const f32x4 xv = {(float)x[i], (float)x[i + 1], (float)x[i + 2], (float)x[i + 3]};
         const f32x4 qv = {q[i], q[i + 1], q[i + 2], q[i + 3]};
         if (METRIC == METRIC_COS) nb.add4_sq(xv);
         acc.template add4_pair<METRIC>(qv, xv);
     }
     for (int i = dmain; i < D; i++) {
-        const float xv = x[i], qv = q[i];
+        const float xv = (float)x[i], qv = q[i];
         if (METRIC == METRIC_COS) nb.add_tail(xv * xv);
         if (METRIC == METRIC_L2) {
             const float e = qv - xv;

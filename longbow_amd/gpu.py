@@ -16,11 +16,18 @@ from .simd import MetricType, Order
 ErrGPUNotAvailable = GPUNotAvailable
 
 
+class DataType:
+    """simd.DataType (internal/simd/registry.go): the element type of the index's rows"""
+    Float32 = 0
+    Float16 = 1
+
+
 class GPUConfig:
-    def __init__(self, DeviceID=0, Dimension=128, Metric=MetricType.Euclidean):
+    def __init__(self, DeviceID=0, Dimension=128, Metric=MetricType.Euclidean, DataType=DataType.Float32):
         self.DeviceID = DeviceID
         self.Dimension = Dimension
         self.Metric = Metric
+        self.DataType = DataType
 
 
 class Cancel:
@@ -61,12 +68,16 @@ class Index:
     def __init__(self, cfg: GPUConfig, lib=None):
         if cfg.Dimension <= 0:
             raise ValueError(f"dimension must be positive, got {cfg.Dimension}")  # faiss_gpu.go:46-48
+        dtype = int(getattr(cfg, "DataType", DataType.Float32))
+        if dtype not in (DataType.Float32, DataType.Float16):
+            raise ValueError(f"unknown data type {dtype} (0 float32, 1 float16)")
         if lib is None:
             lib = _lib.require_gpu(cfg.DeviceID)
         elif lib.lb_gpu_device_count() <= cfg.DeviceID:
             raise GPUNotAvailable(3, f"device {cfg.DeviceID} requested")
         st = C.c_int(0)
-        h = lib.lb_gpu_index_new(cfg.DeviceID, cfg.Dimension, int(cfg.Metric), C.byref(st))
+        new = lib.lb_gpu_index_new_f16 if dtype == DataType.Float16 else lib.lb_gpu_index_new
+        h = new(cfg.DeviceID, cfg.Dimension, int(cfg.Metric), C.byref(st))
         if not h:
             _lib.check(st.value or 7)
         self._lib = lib
@@ -74,6 +85,8 @@ class Index:
         self.dim = cfg.Dimension
         self.device = cfg.DeviceID
         self.metric = MetricType(int(cfg.Metric))
+        self.data_type = dtype
+        self._np = np.float16 if dtype == DataType.Float16 else np.float32  # element type of Add / Search arguments
         self._lock = threading.Lock()
         self._closed = False
 
@@ -81,7 +94,7 @@ class Index:
     def Add(self, ids, vectors):
         """Add(ids []int64, vectors []float32) error  (faiss_gpu.go:75-104)"""
         self._live()
-        vectors = np.ascontiguousarray(vectors, np.float32).reshape(-1)
+        vectors = self._as_elems(vectors).reshape(-1)
         if vectors.size % self.dim != 0:
             raise ValueError(f"vector data length {vectors.size} not divisible by dimension {self.dim}")
         n = vectors.size // self.dim
@@ -91,12 +104,13 @@ class Index:
             if ids.size != n:
                 raise ValueError(f"id count {ids.size} does not match vector count {n}")
             idp = ids.ctypes.data
-        _lib.check(self._lib.lb_gpu_index_add(self._h, n, vectors.ctypes.data, idp), self._h, lib=self._lib)
+        add = self._lib.lb_gpu_index_add_f16 if self._np is np.float16 else self._lib.lb_gpu_index_add
+        _lib.check(add(self._h, n, vectors.ctypes.data, idp), self._h, lib=self._lib)
 
     def Search(self, vector, k, ctx=None):
         """Search(vector []float32, k int) (ids []int64, distances []float32, err)  (faiss_gpu.go:107-144)"""
         self._live()
-        vector = np.ascontiguousarray(vector, np.float32).reshape(-1)
+        vector = self._as_elems(vector).reshape(-1)
         if vector.size != self.dim:
             raise ValueError(f"query vector dimension {vector.size} does not match index dimension {self.dim}")
         ids, dist = self.SearchBatch(vector[None, :], k, ctx=ctx)
@@ -114,15 +128,36 @@ class Index:
     # -- superset ----------------------------------------------------------------
     def SearchBatch(self, queries, k, ctx=None):
         self._live()
-        queries = np.ascontiguousarray(queries, np.float32)
+        queries = self._as_elems(queries)
         if queries.ndim != 2 or queries.shape[1] != self.dim:
             raise ValueError(f"query vector dimension {queries.shape[-1]} does not match index dimension {self.dim}")
         nq = queries.shape[0]
         dist = np.empty((nq, k), np.float32)
         labels = np.empty((nq, k), np.int64)
-        _lib.check(self._lib.lb_gpu_index_search_ctx(self._h, nq, queries.ctypes.data, k, dist.ctypes.data,
-                                                     labels.ctypes.data, ctx._h if ctx is not None else None), self._h, lib=self._lib)
+        search = self._lib.lb_gpu_index_search_f16_ctx if self._np is np.float16 else self._lib.lb_gpu_index_search_ctx
+        _lib.check(search(self._h, nq, queries.ctypes.data, k, dist.ctypes.data,
+                          labels.ctypes.data, ctx._h if ctx is not None else None), self._h, lib=self._lib)
         return labels, dist
+
+    def _as_elems(self, a):
+        """The index's element type, contiguous.  A float16 index takes np.float16 arrays only: rounding float32 data to fp16
+        here would change the vectors silently."""
+        if self._np is np.float16:
+            a = np.asarray(a)
+            if a.dtype != np.float16:
+                raise TypeError(f"a float16 index takes np.float16 arrays, got {a.dtype}")
+            return np.ascontiguousarray(a)
+        return np.ascontiguousarray(a, np.float32)
+
+    def dtype(self):
+        """0 float32, 1 float16 (lb_gpu_index_dtype)"""
+        self._live()
+        return int(self._lib.lb_gpu_index_dtype(self._h))
+
+    def hbm_bytes(self):
+        """HBM the index holds now: rows, per-row side arrays, row list and any accelerator image"""
+        self._live()
+        return int(self._lib.lb_gpu_index_hbm_bytes(self._h))
 
     def Rerank(self, query, rows, order=Order.Unroll4, want_score=True):
         """The distance step of processChunkInternal (internal/store/parallel_search.go:274-364): distances of
@@ -146,13 +181,17 @@ class Index:
                                                         d_dist, d_score, stream), self._h, lib=self._lib)
 
     def add_device(self, n, d_vectors, d_ids=None):
+        """d_vectors: f32 rows, or fp16 rows on a float16 index"""
         self._live()
-        _lib.check(self._lib.lb_gpu_index_add_device(self._h, n, d_vectors, d_ids), self._h, lib=self._lib)
+        add = self._lib.lb_gpu_index_add_f16_device if self._np is np.float16 else self._lib.lb_gpu_index_add_device
+        _lib.check(add(self._h, n, d_vectors, d_ids), self._h, lib=self._lib)
 
     def search_device(self, nq, d_queries, k, d_dist, d_labels, stream=None, ctx=None):
+        """d_queries: f32, or fp16 on a float16 index"""
         self._live()
-        _lib.check(self._lib.lb_gpu_index_search_device_ctx(self._h, nq, d_queries, k, d_dist, d_labels, stream,
-                                                            ctx._h if ctx is not None else None), self._h, lib=self._lib)
+        search = self._lib.lb_gpu_index_search_f16_device_ctx if self._np is np.float16 else self._lib.lb_gpu_index_search_device_ctx
+        _lib.check(search(self._h, nq, d_queries, k, d_dist, d_labels, stream,
+                          ctx._h if ctx is not None else None), self._h, lib=self._lib)
 
     def reserve(self, n_total):
         self._live()
