@@ -168,7 +168,7 @@ int lb_gpu_index_search_device(lb_gpu_index *h, int64_t nq, const float *d_queri
  * return LB_ERR_UNSUPPORTED.  An f32 add / search on an F16 handle, or an _f16 call on an f32 handle, is LB_ERR_INVALID_ARG
  * with a last_error text.  _f16 host searches are not combined. */
 lb_gpu_index *lb_gpu_index_new_f16(int device, int dim, int metric, int *out_status);
-int lb_gpu_index_dtype(const lb_gpu_index *h); /* 0 float32, 1 float16 (simd.DataType, internal/simd/registry.go) */
+int lb_gpu_index_dtype(const lb_gpu_index *h); /* 0 float32, 1 float16, 2 int8 (simd.DataType, internal/simd/registry.go) */
 int lb_gpu_index_add_f16(lb_gpu_index *h, int64_t n, const uint16_t *vectors, const int64_t *ids);
 int lb_gpu_index_add_f16_device(lb_gpu_index *h, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids);
 /* HBM the index holds now: rows (as mapped / allocated), the per-row side arrays, the row list and any accelerator image */
@@ -199,6 +199,29 @@ int lb_gpu_index_search_f16_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *que
 int lb_gpu_index_search_f16_device_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *d_queries, int k, float *d_dist,
                                        int64_t *d_labels, void *stream, const lb_cancel *ctx);
 
+/* ---- int8 indexes: VectorTypeInt8 (internal/store/types/types.go; arrow_utils.go maps FixedSizeList<Int8> to it) ----------
+ * Rows live in HBM as signed int8, 1 byte per element, row-major; queries are int8 too.  Distances are the reference's
+ * DataTypeInt8 registry kernels (internal/simd/dispatch.go): L2 euclideanInt8AVX2Kernel (the exact int32 sum of the first
+ * 16 floor(D/16) squared differences, rounded once to f32, the tail added in f32 in order, sqrt correctly rounded), dot
+ * dotInt8Unrolled4x (four f32 chains over i mod 4, tail in chain 0, ((p0 + p1) + p2) + p3), negated.  Same lists and ascending
+ * (distance, row) order as the f32 index.  Metrics: L2 and dot; cosine (no int8 kernel in the reference) and dot with
+ * floor(D/4) + D mod 4 > 1024 (the chains would leave the exact integers) are NULL / LB_ERR_UNSUPPORTED at creation.
+ * Searches take the exact int8 scan (last_route 80) or, from 16 queries with D % 16 == 0 (dot: D <= 1024), the i8 MFMA pass
+ * (81); both compute every entry's exact value.  On an int8 handle reserve / ntotal / dim / set_filter / filter_* /
+ * last_* / profiling / free work as on an f32 one; set_order is accepted and changes nothing (the arithmetic has one form);
+ * set_candidate_mode takes AUTO only (else LB_ERR_UNSUPPORTED); set_f16_image is accepted and has no effect (no image is
+ * built: f16_image_bytes stays 0); rerank and comm searches return LB_ERR_UNSUPPORTED; dtype is 2.  A float32 / _f16 add or
+ * search on an int8 handle, or an _i8 call on another, is LB_ERR_INVALID_ARG with a last_error text.  _i8 host searches are
+ * not combined. */
+lb_gpu_index *lb_gpu_index_new_i8(int device, int dim, int metric, int *out_status);
+int lb_gpu_index_add_i8(lb_gpu_index *h, int64_t n, const int8_t *vectors, const int64_t *ids);
+int lb_gpu_index_add_i8_device(lb_gpu_index *h, int64_t n, const int8_t *d_vectors, const int64_t *d_ids);
+int lb_gpu_index_search_i8(lb_gpu_index *h, int64_t nq, const int8_t *queries, int k, float *dist, int64_t *labels);
+int lb_gpu_index_search_i8_ctx(lb_gpu_index *h, int64_t nq, const int8_t *queries, int k, float *dist, int64_t *labels,
+                               const lb_cancel *ctx);
+int lb_gpu_index_search_i8_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t *d_queries, int k, float *d_dist,
+                                      int64_t *d_labels, void *stream, const lb_cancel *ctx);
+
 /* Metadata predicate mask for filtered search (SURVEY f-3; byte-per-row 0/1 as
  * internal/query/filter_evaluator.go:79-115 produces).  mask has ntotal bytes;
  * NULL clears it.  Rows with mask 0 never appear in results. */
@@ -226,7 +249,8 @@ int64_t lb_gpu_index_last_fallbacks(const lb_gpu_index *h);
 int64_t lb_gpu_index_fused_giveups(const lb_gpu_index *h);
 /* Which kernel generated the candidates of the most recent batched search on this handle: kind * 10 + operand form.
  * kind: 0 exact scan path (<= 4 queries, non-finite data), 1 / 2 narrow tile (32 / 64 queries per pass), (3: retired
- * in round 4), 4 128 x 128 f32-MFMA tile, 5 256 x 256 split-bf16 tile, 6 256 x 256 fp16 single-product tile;
+ * in round 4), 4 128 x 128 f32-MFMA tile, 5 256 x 256 split-bf16 tile, 6 256 x 256 fp16 single-product tile, 8 the int8
+ * index (80: exact scan, 81: i8 MFMA pass);
  * form: 0 f32 operands, 1 pre-split corpus image, 2 split in registers, 3 fp16.  Telemetry only. */
 int lb_gpu_index_last_route(const lb_gpu_index *h);
 

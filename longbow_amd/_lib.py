@@ -82,6 +82,12 @@ SIGNATURES = [
     ("lb_gpu_index_search_f16_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
     ("lb_gpu_index_search_f16_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_index_hbm_bytes", _i64, [_vp]),
+    ("lb_gpu_index_new_i8", _vp, [_i, _i, _i, _ip]),
+    ("lb_gpu_index_add_i8", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_index_add_i8_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_index_search_i8", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_index_search_i8_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_i8_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_index_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_index_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_index_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),

@@ -36,9 +36,10 @@ class ExchangeError(Exception):
         super().__init__(f"{code}: {message}")
 
 
-def _vector_values(col, dim_expected=None, f16=False):
+def _vector_values(col, dim_expected=None, f16=False, i8=False):
     """(n, dim) float32 view/copy of a FixedSizeList column; f16: the float16 values of a FixedSizeList<HalfFloat> column
-    (VectorTypeFloat16, internal/store/arrow_utils.go:67-80), any other element type rejected"""
+    (VectorTypeFloat16, internal/store/arrow_utils.go:67-80), i8: the int8 values of a FixedSizeList<Int8> column
+    (VectorTypeInt8, arrow_utils.go:324,359); any other element type rejected"""
     if isinstance(col, pa.ChunkedArray):
         col = col.combine_chunks()
     t = col.type
@@ -52,9 +53,13 @@ def _vector_values(col, dim_expected=None, f16=False):
     values = col.flatten()  # accounts for the array offset
     if f16 and not pa.types.is_float16(values.type):
         raise ExchangeError("InvalidArgument", "'vector' elements must be float16 for a float16 index")
+    if i8 and not pa.types.is_int8(values.type):
+        raise ExchangeError("InvalidArgument", "'vector' elements must be int8 for an int8 index")
     arr = values.to_numpy(zero_copy_only=False)
     if f16:
         return np.ascontiguousarray(arr, np.float16).reshape(len(col), dim)
+    if i8:
+        return np.ascontiguousarray(arr, np.int8).reshape(len(col), dim)
     if arr.dtype != np.float32:
         arr = arr.astype(np.float32)  # ExtractVectorFromArrow up-cast
     return np.ascontiguousarray(arr).reshape(len(col), dim)
@@ -77,6 +82,7 @@ class GPUDataset:
         self.name = name
         self.dim = dim
         self.f16 = data_type == gpu.DataType.Float16
+        self.i8 = data_type == gpu.DataType.Int8
         self.index = gpu.NewIndexWithConfig(gpu.GPUConfig(DeviceID=device, Dimension=dim, Metric=metric, DataType=data_type))
         self._has_ids = False
         self._rows = 0
@@ -85,7 +91,7 @@ class GPUDataset:
         vidx = batch.schema.get_field_index("vector")
         if vidx == -1:
             raise ExchangeError("InvalidArgument", "missing 'vector' column")
-        X = _vector_values(batch.column(vidx), self.dim, f16=self.f16)
+        X = _vector_values(batch.column(vidx), self.dim, f16=self.f16, i8=self.i8)
         ids = _ids_from(batch)
         if ids is None and self._has_ids:
             ids = np.arange(self._rows, self._rows + len(X), dtype=np.int64)
@@ -154,6 +160,8 @@ def handle_vector_search_exchange(datasets, request_ipc):
         raise ExchangeError("NotFound", f"dataset not found: {name}")
     if getattr(ds, "f16", False):  # as the C exchange: its query column is float32
         raise ExchangeError("Unimplemented", "vector search over a float16 dataset is not implemented")
+    if getattr(ds, "i8", False):
+        raise ExchangeError("Unimplemented", "vector search over an int8 dataset is not implemented")
     if q.size != ds.dim:
         raise ExchangeError("InvalidArgument", f"dimension mismatch: expected {ds.dim}, got {q.size}")
     try:
@@ -183,6 +191,8 @@ def handle_vector_search_action(datasets, body):
         raise ExchangeError("NotFound", f"dataset not found: {req.get('dataset')}")
     if getattr(ds, "f16", False):
         raise ExchangeError("Unimplemented", "vector search over a float16 dataset is not implemented")
+    if getattr(ds, "i8", False):
+        raise ExchangeError("Unimplemented", "vector search over an int8 dataset is not implemented")
     for q in qs:
         if len(q) != ds.dim:
             raise ExchangeError("InvalidArgument", f"dimension mismatch: expected {ds.dim}, got {len(q)}")

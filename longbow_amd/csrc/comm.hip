@@ -312,8 +312,8 @@ int lb_gpu_comm_search_device(lb_gpu_comm *c, lb_gpu_index *h, int64_t nq, const
                               int64_t *d_labels, void *stream)
 {
     if (!c || !h || nq < 0 || k <= 0 || (nq > 0 && (!d_queries || !d_dist || !d_labels))) return LB_ERR_INVALID_ARG;
-    // (a float16 shard: the exchange takes f32 queries -- not supported; every rank of a job holds the same kind of index)
-    if (lb_gpu_index_dtype(h) != 0) { c->last_error = "sharded search over a float16 index is not supported"; return LB_ERR_UNSUPPORTED; }
+    // (a float16 or int8 shard: the exchange takes f32 queries -- not supported; every rank of a job holds the same kind of index)
+    if (lb_gpu_index_dtype(h) != 0) { c->last_error = "sharded search over a float16 or int8 index is not supported"; return LB_ERR_UNSUPPORTED; }
     if (c->mode == 2) return LB_ERR_INVALID_ARG; // use lb_gpu_comm_search_all
     if (nq == 0) return LB_OK;
     // (argument errors that every rank sees alike may return before the exchange; anything that can differ from
@@ -402,7 +402,7 @@ int lb_gpu_comm_search_all(lb_gpu_comm *c, lb_gpu_index *const *shards, int64_t 
     for (int i = 0; i < nd; i++)
         if (!shards[i]) return LB_ERR_INVALID_ARG;
     for (int i = 0; i < nd; i++)
-        if (lb_gpu_index_dtype(shards[i]) != 0) { c->last_error = "sharded search over a float16 index is not supported"; return LB_ERR_UNSUPPORTED; }
+        if (lb_gpu_index_dtype(shards[i]) != 0) { c->last_error = "sharded search over a float16 or int8 index is not supported"; return LB_ERR_UNSUPPORTED; }
     std::lock_guard<std::mutex> g(c->mu);
     const int dim = lb_gpu_index_dim(shards[0]);
     for (int i = 0; i < nd; i++) { // shard i must live on the communicator's i-th device and share the dimension

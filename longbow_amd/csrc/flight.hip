@@ -32,7 +32,9 @@ namespace {
 // harness, tests/cpp/flight_fuzz.cpp; there every handle is f32)
 #pragma weak lb_gpu_index_dtype
 #pragma weak lb_gpu_index_add_f16
+#pragma weak lb_gpu_index_add_i8
 static bool index_is_f16(const lb_gpu_index *h) { return lb_gpu_index_dtype != nullptr && lb_gpu_index_dtype(h) == 1; }
+static bool index_is_i8(const lb_gpu_index *h) { return lb_gpu_index_dtype != nullptr && lb_gpu_index_dtype(h) == 2; }
 
 enum { GRPC_OK = 0, GRPC_INVALID_ARGUMENT = 3, GRPC_NOT_FOUND = 5, GRPC_FAILED_PRECONDITION = 9, GRPC_UNIMPLEMENTED = 12, GRPC_INTERNAL = 13,
        GRPC_UNAVAILABLE = 14 };
@@ -754,8 +756,9 @@ static int exchange_body(lb_flight_datasets *reg, const uint8_t *ipc_in, size_t 
         if (it != reg->sets.end()) h = it->second;
     }
     if (!h) return finish(err(GRPC_NOT_FOUND, "dataset not found: %s", name.c_str()), errbuf, errcap);
-    // (the exchange's query column is float32: a float16 dataset is not searched through it)
+    // (the exchange's query column is float32: a float16 or int8 dataset is not searched through it)
     if (index_is_f16(h)) return finish(err(GRPC_UNIMPLEMENTED, "vector search over a float16 dataset is not implemented"), errbuf, errcap);
+    if (index_is_i8(h)) return finish(err(GRPC_UNIMPLEMENTED, "vector search over an int8 dataset is not implemented"), errbuf, errcap);
     const int dim = lb_gpu_index_dim(h);
     if (qlen != dim) return finish(err(GRPC_INVALID_ARGUMENT, "dimension mismatch: expected %d, got %lld", dim, (long long)qlen), errbuf, errcap);
     if (k < 1) return finish(err(GRPC_INVALID_ARGUMENT, "k must be at least 1"), errbuf, errcap);
@@ -793,6 +796,7 @@ static int add_ipc_body(lb_gpu_index *h, const uint8_t *ipc, size_t len, int64_t
     if (!h || (!ipc && len)) return finish(err(GRPC_INVALID_ARGUMENT, "null argument"), errbuf, errcap);
     const int dim = lb_gpu_index_dim(h);
     const bool f16 = index_is_f16(h);
+    const bool i8 = index_is_i8(h);
     std::vector<Field> fields;
     bool have_schema = false;
     int64_t added = 0;
@@ -821,15 +825,20 @@ static int add_ipc_body(lb_gpu_index *h, const uint8_t *ipc, size_t len, int64_t
         if (f->type != T_FSLIST || f->children.size() != 1)
             return err(GRPC_INVALID_ARGUMENT, "'vector' must be FixedSizeList");
         if (f->list_size != dim) return err(GRPC_INVALID_ARGUMENT, "dimension mismatch: expected %d, got %d", dim, f->list_size);
-        // element type: float32 for an f32 index, HalfFloat (precision 0) for a float16 one (arrow_utils.go:67-80,321)
-        const int want_prec = f16 ? 0 : 1;
-        if (f->children[0].type != T_FLOAT || f->children[0].precision != want_prec)
+        // element type: float32 for an f32 index, HalfFloat (precision 0) for a float16 one (arrow_utils.go:67-80,321), signed
+        // 8-bit Int for an int8 one (arrow_utils.go:324,359)
+        const Field &el = f->children[0];
+        if (i8) {
+            if (el.type != T_INT || el.bit_width != 8 || !el.is_signed)
+                return err(GRPC_INVALID_ARGUMENT, "'vector' elements must be int8 for an int8 index");
+        } else if (el.type != T_FLOAT || el.precision != (f16 ? 0 : 1)) {
             return err(GRPC_INVALID_ARGUMENT, f16 ? "'vector' elements must be float16 for a float16 index"
                                                   : "'vector' elements must be float32 in this entry point");
+        }
         if (pos.node < b.nodes.size() && b.nodes[pos.node].nulls != 0) return err(GRPC_INVALID_ARGUMENT, "null vectors are not supported");
         // the column's FieldNodes must agree with the batch: `rows` lists, rows * dim child values
         int64_t nvals = 0, vbytes = 0;
-        if (!mul_i64(b.rows, dim, nvals) || !mul_i64(nvals, f16 ? 2 : 4, vbytes)) return err(GRPC_INTERNAL, "'vector' values buffer is too short");
+        if (!mul_i64(b.rows, dim, nvals) || !mul_i64(nvals, i8 ? 1 : f16 ? 2 : 4, vbytes)) return err(GRPC_INTERNAL, "'vector' values buffer is too short");
         if ((node_len(b, pos.node) >= 0 && node_len(b, pos.node) != b.rows) ||
             (node_len(b, pos.node + 1) >= 0 && node_len(b, pos.node + 1) != nvals))
             return err(GRPC_INTERNAL, "failed to read record: 'vector' lengths disagree with the batch");
@@ -856,8 +865,10 @@ static int add_ipc_body(lb_gpu_index *h, const uint8_t *ipc, size_t len, int64_t
             for (int64_t i = 0; i < b.rows; i++) ids[(size_t)i] = base + i;
         }
         // the values buffer goes to the library as it lies in the IPC body: no repacking
-        const int rc = f16 ? lb_gpu_index_add_f16(h, b.rows, reinterpret_cast<const uint16_t *>(vals), ids.empty() ? nullptr : ids.data())
-                           : lb_gpu_index_add(h, b.rows, reinterpret_cast<const float *>(vals), ids.empty() ? nullptr : ids.data());
+        const int64_t *idp = ids.empty() ? nullptr : ids.data();
+        const int rc = i8    ? lb_gpu_index_add_i8(h, b.rows, reinterpret_cast<const int8_t *>(vals), idp)
+                       : f16 ? lb_gpu_index_add_f16(h, b.rows, reinterpret_cast<const uint16_t *>(vals), idp)
+                             : lb_gpu_index_add(h, b.rows, reinterpret_cast<const float *>(vals), idp);
         if (rc != LB_OK) return err(rc == LB_ERR_NO_DEVICE ? GRPC_UNAVAILABLE : GRPC_INTERNAL, "add failed: %s (%s)", lb_gpu_status_string(rc), lb_gpu_last_error(h));
         added += b.rows;
         return {};

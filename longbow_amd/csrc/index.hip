@@ -226,6 +226,7 @@ struct lb_gpu_index {
     // are only ever read through rows_f16())
     float *d_X = nullptr;
     bool f16_rows = false; // lb_gpu_index_new_f16: fixed for the handle's life
+    bool i8_rows = false;  // lb_gpu_index_new_i8: signed int8 rows, fixed for the handle's life (searched by kernels_i8.hip only)
     VmmBuf vmm;             // backs d_X when vmm.ok (d_X == vmm.base): rows are appended in place
     int64_t x_rows_cap = 0; // rows d_X can hold (>= capacity of the side arrays when vmm.ok)
     int64_t n = 0, capacity = 0;
@@ -307,8 +308,12 @@ struct lb_gpu_index {
     float prof_ms[5] = {0, 0, 0, 0, 0};
     int prof_n[5] = {0, 0, 0, 0, 0};
 
-    size_t elem_bytes() const { return f16_rows ? 2 : sizeof(float); }
+    size_t elem_bytes() const { return i8_rows ? 1 : f16_rows ? 2 : sizeof(float); }
+    int dtype() const { return i8_rows ? 2 : f16_rows ? 1 : 0; } // simd.DataType
     const _Float16 *rows_f16() const { return reinterpret_cast<const _Float16 *>(d_X); }
+    const int8_t *rows_i8() const { return reinterpret_cast<const int8_t *>(d_X); }
+    // an int8 index keeps its exact int32 row norms (the sum of x_i^2 over i < 16 floor(D / 16)) in d_norm2's words
+    int32_t *norm2_i8() const { return reinterpret_cast<int32_t *>(d_norm2); }
 
     void set_error(const char *fmt, ...)
     {
@@ -551,7 +556,9 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
         if (sp.on) {
             {   // sample scores (clear the flags; exact query norms ride along), threshold
                 ProfScope p(w, s, prof, 1);
-                if (h->f16_rows)
+                if (h->i8_rows)
+                    launch_sample_scores_i8(metric, h->rows_i8(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel, gn, w->cs, s);
+                else if (h->f16_rows)
                     launch_sample_scores(metric, order, h->rows_f16(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel,
                                          gn, w->cs, w->d_qna, s);
                 else
@@ -561,7 +568,10 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
             }
             {   // one pass over the span
                 ProfScope p(w, s, prof, 3);
-                if (h->f16_rows)
+                if (h->i8_rows)
+                    launch_scan_i8(metric, h->rows_i8(), 0, sp.span, h->dim, d_q, use_sel, gn, h->norm2_i8(), mask, rv.rowmap, w->cs,
+                                   /*boot=*/false, s, /*striped=*/true);
+                else if (h->f16_rows)
                     launch_scan(metric, order, false, h->rows_f16(), 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna, mask,
                                 rv.rowmap, w->cs, /*boot=*/false, nullptr, 0, s, /*striped=*/true);
                 else
@@ -586,7 +596,10 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
             const bool boot = step == 0;
             {
                 ProfScope p(w, s, prof, 3);
-                if (h->f16_rows)
+                if (h->i8_rows)
+                    launch_scan_i8(metric, h->rows_i8(), pos, end, h->dim, d_q, use_sel, gn, h->norm2_i8(), mask, rv.rowmap, w->cs,
+                                   boot, s, /*striped=*/false);
+                else if (h->f16_rows)
                     launch_scan(metric, order, false, h->rows_f16(), pos, end, h->dim, d_q, use_sel, gn, w->d_qna,
                                 mask, rv.rowmap, w->cs, boot, nullptr, 0, s);
                 else
@@ -798,6 +811,62 @@ static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, b
     for (int i = 1; i < nc; i++)
         if (cand[i].cost_ms < cand[best].cost_ms) best = i;
     return cand[best];
+}
+
+// An int8 index's batch (kernels_i8.hip).  Every kernel there computes the exact reference value of each (row, query) pair, so
+// the candidate entries are the results themselves: no candidate keys, no finish, no containment bound.
+//   route 80  the exact scan (run_scan_path): 8 queries a corpus pass, v_dot4c_i32_i8;
+//   route 81  the i8 MFMA pass: 128 queries a corpus pass.  Its sampled threshold comes from the same kernel over the sampled
+//             positions; the one select behind the pass emits.  A query whose list overflowed or ended short (flags 1 / 4) is
+//             redone by the scan.  Needs D % 16 == 0 (dot: D <= 1024), 16-B aligned query rows and a sampled span that covers
+//             the row view; batches from LB_I8_MFMA_MINQ queries.
+// d_q: the batch widened to f32 (the scan's input), d_q8: the same queries as int8 (the MFMA pass's).
+constexpr int kRouteI8Scan = 80, kRouteI8Mfma = 81;
+int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, const int8_t *d_q8, int k, float *d_dist,
+                    int64_t *d_lab, bool prof)
+{
+    static const int mfma_minq = lb_tunable("LB_I8_MFMA_MINQ", 16);
+    const RowView rv = row_view(h);
+    const int kkeep = std::max(k, 1);
+    std::vector<int> all(nq);
+    for (int i = 0; i < nq; i++) all[i] = i;
+    SamplePlan sp;
+    if (nq >= mfma_minq && mfma_i8_supported(h->metric, h->dim, h->d_X, d_q8)) sp = sample_plan(rv.n, kkeep, w->cap);
+    if (!sp.on || sp.span < rv.n) {
+        h->last_route.store(kRouteI8Scan, std::memory_order_relaxed);
+#ifdef LB_DIAG
+        g_last_route.store(kRouteI8Scan);
+#endif
+        scan_with_retry(h, w, s, d_q, nq, all, k, d_dist, d_lab, prof);
+        return LB_OK;
+    }
+    h->last_route.store(kRouteI8Mfma, std::memory_order_relaxed);
+#ifdef LB_DIAG
+    g_last_route.store(kRouteI8Mfma);
+#endif
+    int32_t *qn = reinterpret_cast<int32_t *>(w->d_qna); // (nq_cap words: the exact int32 |q|^2 here)
+    {
+        ProfScope p(w, s, prof, 1);
+        LB_HIP(hipMemsetAsync(w->cs.flags, 0, (size_t)nq * sizeof(uint32_t), s));
+        launch_query_norms_i8(d_q8, nq, h->dim, qn, s);
+        launch_mfma_i8(h->metric, h->rows_i8(), sp.count, h->dim, d_q8, nq, qn, h->norm2_i8(), rv.mask, rv.rowmap, w->cs,
+                       /*sample=*/true, sp.span, s);
+        launch_sample_tau(w->cs, nullptr, nq, sp.count, sp.m, /*zero_stripes=*/false, s);
+    }
+    {
+        ProfScope p(w, s, prof, 3);
+        launch_mfma_i8(h->metric, h->rows_i8(), rv.n, h->dim, d_q8, nq, qn, h->norm2_i8(), rv.mask, rv.rowmap, w->cs,
+                       /*sample=*/false, rv.n, s);
+    }
+    {
+        ProfScope p(w, s, prof, 1);
+        const EmitArgs em{k, h->has_ids ? h->d_ids : nullptr, d_dist, d_lab, w->h_flags};
+        launch_select(w->cs, nullptr, nq, kkeep, 0u, s, false, (uint32_t)kkeep, &em);
+    }
+    std::vector<int> redo;
+    if (collect_flagged(w, s, nq, 1u | 4u, all.data(), nq, redo, true) > 0)
+        scan_with_retry(h, w, s, d_q, nq, redo, k, d_dist, d_lab, prof);
+    return LB_OK;
 }
 
 int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, int k,
@@ -1501,7 +1570,9 @@ void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool ids_on_
 {
     hipStream_t s = h->add_stream;
     const int64_t start = h->n;
-    if (h->f16_rows)
+    if (h->i8_rows)
+        launch_row_norms_i8(h->rows_i8() + (size_t)start * h->dim, n, h->dim, h->norm2_i8() + start, s);
+    else if (h->f16_rows)
         launch_row_norms(h->rows_f16() + (size_t)start * h->dim, n, h->dim, h->d_norm2 + start, h->d_rnorm + start, h->d_maxnorm2, s);
     else
         launch_row_norms(h->d_X + (size_t)start * h->dim, n, h->dim, h->d_norm2 + start, h->d_rnorm + start,
@@ -1550,7 +1621,7 @@ void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool ids_on_
 // bring the split-bf16 mirror up to date with d_X (no-op unless the mode is enabled)
 void sync_split_image(lb_gpu_index *h)
 {
-    if (h->cand_mode.load() != 1 || h->dim % 32 != 0 || h->n == 0 || h->f16_rows) return;
+    if (h->cand_mode.load() != 1 || h->dim % 32 != 0 || h->n == 0 || h->f16_rows || h->i8_rows) return;
     if (h->d_Xs == nullptr || h->xs_rows > h->n) {
         if (h->d_Xs) (void)hipFree(h->d_Xs);
         h->d_Xs = nullptr;
@@ -1578,7 +1649,8 @@ void sync_f16_image(lb_gpu_index *h)
     const bool l2 = h->metric == LB_METRIC_EUCLIDEAN;
     // (L2: the image is centred, so what must fit fp16 are the centred norms -- known once the centre is)
     const bool range_ok = l2 ? (!h->nonfinite && (h->xh_declined_n == 0 || h->n >= 2 * h->xh_declined_n)) : h->f16_ok;
-    const bool want = h->xh_mode.load() != 0 && !h->xh_failed && range_ok && h->n > 0 &&
+    // (an int8 index has no image: its searches read the int8 rows)
+    const bool want = h->xh_mode.load() != 0 && !h->xh_failed && !h->i8_rows && range_ok && h->n > 0 &&
                       (cm == LB_CAND_F16 || (cm == LB_CAND_AUTO && h->n >= f16_image_min_rows));
     try {
         if (!want || (h->d_Xh && (h->xh_cap < h->n || h->xh_rows > h->n))) {
@@ -1776,20 +1848,29 @@ const char *lb_gpu_status_string(int status)
     }
 }
 
-static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status, bool f16_rows)
+// dtype: 0 float32, 1 float16, 2 int8 (simd.DataType)
+static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status, int dtype)
 {
     auto st = [&](int v) { if (out_status) *out_status = v; };
     if (dim <= 0 || metric < 0 || metric > 2) { st(LB_ERR_INVALID_ARG); return nullptr; }
     // the kernels stage one query row (and the re-rank a 256 x 64-float tile plus up to 4096 keys) in LDS:
     // LB_MAX_DIM keeps every launch inside the 160 KB a workgroup may declare
     if (dim > LB_MAX_DIM) { st(LB_ERR_UNSUPPORTED); return nullptr; }
+    if (dtype == 2) {
+        // int8: the reference registers no cosine kernel (DispatchDistance: "no kernel found"); its dot chains are exact
+        // integers only while floor(D / 4) + D mod 4 <= 1024 (kernels_i8.hip)
+        if (metric == LB_METRIC_COSINE) { st(LB_ERR_UNSUPPORTED); return nullptr; }
+        if (metric == LB_METRIC_DOT && dim / 4 + dim % 4 > 1024) { st(LB_ERR_UNSUPPORTED); return nullptr; }
+    }
     if (!device_ok(device)) { st(LB_ERR_NO_DEVICE); return nullptr; }
     auto *h = new (std::nothrow) lb_gpu_index();
     if (!h) { st(LB_ERR_OOM); return nullptr; }
     h->device = device; h->dim = dim; h->metric = metric;
-    h->f16_rows = f16_rows;
-    // (fp16 rows: UNROLL4 is the only order of the reference's F16 functions, internal/simd/simd.go:767-848)
-    if (f16_rows) h->order.store(LB_ORDER_UNROLL4);
+    h->f16_rows = dtype == 1;
+    h->i8_rows = dtype == 2;
+    // (fp16 rows: UNROLL4 is the only order of the reference's F16 functions, internal/simd/simd.go:767-848; int8 rows: the
+    // order is accepted and changes nothing, the int8 arithmetic has one form)
+    if (h->f16_rows || h->i8_rows) h->order.store(LB_ORDER_UNROLL4);
     try {
         LB_HIP(hipSetDevice(device));
         LB_HIP(hipStreamCreateWithFlags(&h->add_stream, hipStreamNonBlocking));
@@ -1809,13 +1890,17 @@ static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status,
 
 lb_gpu_index *lb_gpu_index_new(int device, int dim, int metric, int *out_status)
 {
-    return index_new(device, dim, metric, out_status, false);
+    return index_new(device, dim, metric, out_status, 0);
 }
 lb_gpu_index *lb_gpu_index_new_f16(int device, int dim, int metric, int *out_status)
 {
-    return index_new(device, dim, metric, out_status, true);
+    return index_new(device, dim, metric, out_status, 1);
 }
-int lb_gpu_index_dtype(const lb_gpu_index *h) { return h && h->f16_rows ? 1 : 0; }
+lb_gpu_index *lb_gpu_index_new_i8(int device, int dim, int metric, int *out_status)
+{
+    return index_new(device, dim, metric, out_status, 2);
+}
+int lb_gpu_index_dtype(const lb_gpu_index *h) { return h ? h->dtype() : 0; }
 
 int64_t lb_gpu_index_hbm_bytes(const lb_gpu_index *h)
 {
@@ -1893,6 +1978,10 @@ int lb_gpu_index_set_candidate_mode(lb_gpu_index *h, int mode)
         h->set_error("candidate mode %d needs f32 rows; an fp16 index takes AUTO or F16", mode);
         return LB_ERR_UNSUPPORTED;
     }
+    if (h->i8_rows && mode != LB_CAND_AUTO) {
+        h->set_error("candidate mode %d needs f32 rows; an int8 index takes AUTO only", mode);
+        return LB_ERR_UNSUPPORTED;
+    }
     if ((mode == LB_CAND_SPLIT_BF16 || mode == LB_CAND_SPLIT_BF16_INREG) && h->dim % 32 != 0) {
         h->set_error("split-bf16 candidates need dim %% 32 == 0 (dim = %d)", h->dim);
         return LB_ERR_UNSUPPORTED;
@@ -1956,19 +2045,23 @@ int lb_gpu_index_reserve(lb_gpu_index *h, int64_t n_total)
     }
 }
 
-static int dtype_mismatch(lb_gpu_index *h, bool f16_call)
+// call: the element type of the entry point (0 float32, 1 _f16, 2 _i8)
+static int dtype_mismatch(lb_gpu_index *h, int call)
 {
-    if (h->f16_rows == f16_call) return LB_OK;
-    h->set_error(f16_call ? "this index holds float32 rows: use the float32 entry point" : "this index holds float16 rows: use the _f16 entry point");
+    if (h->dtype() == call) return LB_OK;
+    static const char *const what[3] = {"this index holds float32 rows: use the float32 entry point",
+                                        "this index holds float16 rows: use the _f16 entry point",
+                                        "this index holds int8 rows: use the _i8 entry point"};
+    h->set_error("%s", what[h->dtype()]);
     return LB_ERR_INVALID_ARG;
 }
 
-static int add_host(lb_gpu_index *h, int64_t n, const void *vectors, const int64_t *ids, bool f16_call)
+static int add_host(lb_gpu_index *h, int64_t n, const void *vectors, const int64_t *ids, int dtype)
 {
     if (!h || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-    if (const int rc = dtype_mismatch(h, f16_call)) return rc;
+    if (const int rc = dtype_mismatch(h, dtype)) return rc;
     if (n == 0) return LB_OK;
     if (h->n + n > (int64_t)0xffffffffll) { h->set_error("more than 2^32 rows per device"); return LB_ERR_UNSUPPORTED; }
     try {
@@ -2023,19 +2116,23 @@ static int add_host(lb_gpu_index *h, int64_t n, const void *vectors, const int64
 
 int lb_gpu_index_add(lb_gpu_index *h, int64_t n, const float *vectors, const int64_t *ids)
 {
-    return add_host(h, n, vectors, ids, false);
+    return add_host(h, n, vectors, ids, 0);
 }
 int lb_gpu_index_add_f16(lb_gpu_index *h, int64_t n, const uint16_t *vectors, const int64_t *ids)
 {
-    return add_host(h, n, vectors, ids, true);
+    return add_host(h, n, vectors, ids, 1);
+}
+int lb_gpu_index_add_i8(lb_gpu_index *h, int64_t n, const int8_t *vectors, const int64_t *ids)
+{
+    return add_host(h, n, vectors, ids, 2);
 }
 
-static int add_device(lb_gpu_index *h, int64_t n, const void *d_vectors, const int64_t *d_ids, bool f16_call)
+static int add_device(lb_gpu_index *h, int64_t n, const void *d_vectors, const int64_t *d_ids, int dtype)
 {
     if (!h || n < 0 || (n > 0 && !d_vectors)) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-    if (const int rc = dtype_mismatch(h, f16_call)) return rc;
+    if (const int rc = dtype_mismatch(h, dtype)) return rc;
     if (n == 0) return LB_OK;
     if (h->n + n > (int64_t)0xffffffffll) { h->set_error("more than 2^32 rows per device"); return LB_ERR_UNSUPPORTED; }
     try {
@@ -2052,11 +2149,15 @@ static int add_device(lb_gpu_index *h, int64_t n, const void *d_vectors, const i
 
 int lb_gpu_index_add_device(lb_gpu_index *h, int64_t n, const float *d_vectors, const int64_t *d_ids)
 {
-    return add_device(h, n, d_vectors, d_ids, false);
+    return add_device(h, n, d_vectors, d_ids, 0);
 }
 int lb_gpu_index_add_f16_device(lb_gpu_index *h, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids)
 {
-    return add_device(h, n, d_vectors, d_ids, true);
+    return add_device(h, n, d_vectors, d_ids, 1);
+}
+int lb_gpu_index_add_i8_device(lb_gpu_index *h, int64_t n, const int8_t *d_vectors, const int64_t *d_ids)
+{
+    return add_device(h, n, d_vectors, d_ids, 2);
 }
 
 int lb_gpu_index_set_filter(lb_gpu_index *h, const uint8_t *mask, int64_t n)
@@ -2124,12 +2225,12 @@ int64_t lb_gpu_index_fused_giveups(const lb_gpu_index *h) { return h ? h->fused_
 int lb_gpu_index_last_route(const lb_gpu_index *h) { return h ? h->last_route.load() : 0; }
 
 static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
-                         const lb_cancel *ctx, bool f16_call)
+                         const lb_cancel *ctx, int dtype)
 {
     if (!h || nq < 0 || k <= 0 || (nq > 0 && (!d_queries || !d_dist || !d_labels))) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-    if (const int rc = dtype_mismatch(h, f16_call)) return rc;
+    if (const int rc = dtype_mismatch(h, dtype)) return rc;
     if (nq == 0) return LB_OK;
     if (k > LB_MAX_K) { h->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
     if (const int st = ctx_state(ctx)) { h->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded"); return st; }
@@ -2155,7 +2256,7 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
             for (int64_t q0 = 0; q0 < nq; q0 += kMaxBatch) {
                 const int bq = (int)std::min<int64_t>(kMaxBatch, nq - q0);
                 const float *bq_f32 = nullptr;
-                if (f16_call) { // fp16 queries: widened exactly into the workspace's f32 batch, then searched as any other
+                if (dtype != 0) { // fp16 / int8 queries: widened exactly into the workspace's f32 batch, then searched as any other
                     const size_t need = (size_t)bq * h->dim * sizeof(float);
                     if (w->d_q_bytes < need) {
                         if (w->d_q) (void)hipFree(w->d_q);
@@ -2164,13 +2265,18 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
                         LB_HIP(hipMalloc(&w->d_q, need));
                         w->d_q_bytes = need;
                     }
-                    launch_widen_f16(static_cast<const uint16_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q, (int64_t)bq * h->dim, s);
+                    if (dtype == 2)
+                        launch_widen_i8(static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q, (int64_t)bq * h->dim, s);
+                    else
+                        launch_widen_f16(static_cast<const uint16_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q, (int64_t)bq * h->dim, s);
                     bq_f32 = w->d_q;
                 } else {
                     bq_f32 = static_cast<const float *>(d_queries) + (size_t)q0 * h->dim;
                 }
-                int rc = search_batch_device(h, w.get(), s, bq, bq_f32, k,
-                                             d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, kc, prof, fallbacks);
+                int rc = h->i8_rows ? search_batch_i8(h, w.get(), s, bq, bq_f32, static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, k,
+                                                      d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
+                                    : search_batch_device(h, w.get(), s, bq, bq_f32, k, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k,
+                                                          kc, prof, fallbacks);
                 if (rc != LB_OK) { w->ctx = nullptr; release_ws(h, std::move(w)); return rc; }
             }
         }
@@ -2205,12 +2311,17 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
 int lb_gpu_index_search_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
                                    int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
-    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, false);
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 0);
 }
 int lb_gpu_index_search_f16_device_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *d_queries, int k, float *d_dist,
                                        int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
-    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, true);
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 1);
+}
+int lb_gpu_index_search_i8_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t *d_queries, int k, float *d_dist,
+                                      int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 2);
 }
 
 int lb_gpu_index_search_device(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
@@ -2235,10 +2346,10 @@ int lb_cancel_state(const lb_cancel *c) { return ctx_state(c); }
 
 // Host-pointer search of one or several requests with the same k as ONE device batch: borrowed host buffers -> pooled pinned
 // slab -> HBM (async DMA on the call's own stream), and back; every request gets its rows of the result.
-// (f16_call: the requests' queries are fp16 -- 2 bytes an element; never combined)
-static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, int k, const lb_cancel *ctx, bool f16_call = false)
+// (dtype: the requests' queries are fp16 -- 2 bytes an element -- or int8 -- 1 byte; those are never combined)
+static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, int k, const lb_cancel *ctx, int dtype = 0)
 {
-    const size_t qelem = f16_call ? 2 : sizeof(float);
+    const size_t qelem = dtype == 2 ? 1 : dtype == 1 ? 2 : sizeof(float);
     int64_t nq = 0;
     for (int i = 0; i < nreq; i++) nq += reqs[i]->nq;
     // (before any staging is sized: nq * k * 12 bytes of pinned + device memory per call)
@@ -2285,7 +2396,7 @@ static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, in
         const bool direct = db + lb_ <= ((size_t)64 << 10);
         char *obuf = direct ? hb : dbuf;
         rc = search_device(h, nq, dbuf + qoff, k, reinterpret_cast<float *>(obuf + doff), reinterpret_cast<int64_t *>(obuf + loff),
-                           st->stream, ctx, f16_call);
+                           st->stream, ctx, dtype);
         if (rc == LB_OK) {
             if (!direct) {
                 LB_HIP(hipMemcpyAsync(hb + doff, dbuf + doff, db + lb_, hipMemcpyDeviceToHost, st->stream));
@@ -2318,7 +2429,7 @@ int lb_gpu_index_search_ctx(lb_gpu_index *h, int64_t nq, const float *queries, i
     {
         std::shared_lock<std::shared_mutex> g(h->mu);
         if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-        if (const int rc = dtype_mismatch(h, false)) return rc;
+        if (const int rc = dtype_mismatch(h, 0)) return rc;
     }
     // (a call with a cancellation context is searched on its own: its deadline is not its neighbours')
     HostReq me{queries, nq, dist, labels, k};
@@ -2336,15 +2447,34 @@ int lb_gpu_index_search_f16_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *que
     {
         std::shared_lock<std::shared_mutex> g(h->mu);
         if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-        if (const int rc = dtype_mismatch(h, true)) return rc;
+        if (const int rc = dtype_mismatch(h, 1)) return rc;
     }
     HostReq me{reinterpret_cast<const float *>(queries), nq, dist, labels, k}; // (fp16 bits: host_search_multi copies bytes)
     HostReq *one = &me;
-    return host_search_multi(h, &one, 1, k, ctx, /*f16_call=*/true);
+    return host_search_multi(h, &one, 1, k, ctx, /*dtype=*/1);
 }
 int lb_gpu_index_search_f16(lb_gpu_index *h, int64_t nq, const uint16_t *queries, int k, float *dist, int64_t *labels)
 {
     return lb_gpu_index_search_f16_ctx(h, nq, queries, k, dist, labels, nullptr);
+}
+
+int lb_gpu_index_search_i8_ctx(lb_gpu_index *h, int64_t nq, const int8_t *queries, int k, float *dist, int64_t *labels,
+                               const lb_cancel *ctx)
+{
+    if (!h || nq < 0 || k <= 0 || (nq > 0 && (!queries || !dist || !labels))) return LB_ERR_INVALID_ARG;
+    if (nq == 0) return LB_OK;
+    {
+        std::shared_lock<std::shared_mutex> g(h->mu);
+        if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
+        if (const int rc = dtype_mismatch(h, 2)) return rc;
+    }
+    HostReq me{reinterpret_cast<const float *>(queries), nq, dist, labels, k}; // (int8 bytes: host_search_multi copies bytes)
+    HostReq *one = &me;
+    return host_search_multi(h, &one, 1, k, ctx, /*dtype=*/2);
+}
+int lb_gpu_index_search_i8(lb_gpu_index *h, int64_t nq, const int8_t *queries, int k, float *dist, int64_t *labels)
+{
+    return lb_gpu_index_search_i8_ctx(h, nq, queries, k, dist, labels, nullptr);
 }
 
 int lb_gpu_index_set_search_combining(lb_gpu_index *h, int enable)
@@ -2425,7 +2555,10 @@ int lb_gpu_index_rerank_device(lb_gpu_index *h, const float *d_query, const int6
     if (n > (int64_t)0x7fffffff) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(h->mu);
     if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-    if (h->f16_rows) { h->set_error("re-rank reads float32 rows: not available on a float16 index"); return LB_ERR_UNSUPPORTED; }
+    if (h->f16_rows || h->i8_rows) {
+        h->set_error("re-rank reads float32 rows: not available on a %s index", h->i8_rows ? "int8" : "float16");
+        return LB_ERR_UNSUPPORTED;
+    }
     try {
         LB_HIP(hipSetDevice(h->device));
         const int ord = order == -1 ? h->order.load() : order;
@@ -2463,7 +2596,10 @@ int lb_gpu_index_rerank(lb_gpu_index *h, const float *query, const int64_t *rows
     if (!h || n < 0) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     if (!query || !rows || !dist) return LB_ERR_INVALID_ARG;
-    if (h->f16_rows) { h->set_error("re-rank reads float32 rows: not available on a float16 index"); return LB_ERR_UNSUPPORTED; }
+    if (h->f16_rows || h->i8_rows) {
+        h->set_error("re-rank reads float32 rows: not available on a %s index", h->i8_rows ? "int8" : "float16");
+        return LB_ERR_UNSUPPORTED;
+    }
     try {
         LB_HIP(hipSetDevice(h->device));
         // [query | rows] up through one pinned block, [dist | score] back through another

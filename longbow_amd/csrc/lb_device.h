@@ -270,6 +270,27 @@ void launch_row_norms(const _Float16 *X, int64_t n, int D, float *norm2, float *
                       const float *center = nullptr);
 // n fp16 values (IEEE binary16 bit patterns) -> f32, exactly
 void launch_widen_f16(const void *src, float *dst, int64_t n, hipStream_t s);
+
+// ---- the int8 index (kernels_i8.hip): exact values of the reference's int8 registry kernels, candidate entries as the scan's
+// per row: the exact sum of x_i^2 over i < 16 floor(D / 16), as int32
+void launch_row_norms_i8(const int8_t *X, int64_t n, int D, int32_t *norm2, hipStream_t s);
+// n int8 values -> f32, exactly
+void launch_widen_i8(const void *src, float *dst, int64_t n, hipStream_t s);
+// the scan over int8 rows (launch_scan's contract; Q: int8 queries widened to f32; norm2: launch_row_norms_i8's)
+void launch_scan_i8(int metric, const int8_t *X, int64_t row_begin, int64_t row_end, int D, const float *Q, const int *qsel,
+                    int nsel, const int32_t *norm2, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
+                    hipStream_t s, bool striped);
+// launch_sample_scores over int8 rows: the sampled entries carry the exact values
+void launch_sample_scores_i8(int metric, const int8_t *X, int D, int64_t span, uint32_t count, const uint32_t *rowmap,
+                             const uint8_t *mask, const float *Q, const int *qsel, int nsel, CandState cs, hipStream_t s);
+// the i8 MFMA pass over npos positions for queries 0 .. nq (int8, Q8): sample = false admits exact entries below tau (row
+// view: rowmap / mask); sample = true writes every entry of the npos sampled positions of [0, span) to lists[q][position]
+bool mfma_i8_supported(int metric, int D, const void *X, const void *Q8);
+void launch_mfma_i8(int metric, const int8_t *X, int64_t npos, int D, const int8_t *Q8, int nq, const int32_t *qn,
+                    const int32_t *norm2, const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool sample, int64_t span,
+                    hipStream_t s);
+// exact |q|^2 of nq int8 queries
+void launch_query_norms_i8(const int8_t *Q8, int nq, int D, int32_t *qn, hipStream_t s);
 // column means of X[0 .. n) in a fixed order -> center[0 .. Dpad) (zero beyond D); partial: [256][D] scratch
 void launch_column_means(const float *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);
 void launch_column_means(const _Float16 *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);

@@ -20,6 +20,7 @@ class DataType:
     """simd.DataType (internal/simd/registry.go): the element type of the index's rows"""
     Float32 = 0
     Float16 = 1
+    Int8 = 2
 
 
 class GPUConfig:
@@ -69,14 +70,14 @@ class Index:
         if cfg.Dimension <= 0:
             raise ValueError(f"dimension must be positive, got {cfg.Dimension}")  # faiss_gpu.go:46-48
         dtype = int(getattr(cfg, "DataType", DataType.Float32))
-        if dtype not in (DataType.Float32, DataType.Float16):
-            raise ValueError(f"unknown data type {dtype} (0 float32, 1 float16)")
+        if dtype not in (DataType.Float32, DataType.Float16, DataType.Int8):
+            raise ValueError(f"unknown data type {dtype} (0 float32, 1 float16, 2 int8)")
         if lib is None:
             lib = _lib.require_gpu(cfg.DeviceID)
         elif lib.lb_gpu_device_count() <= cfg.DeviceID:
             raise GPUNotAvailable(3, f"device {cfg.DeviceID} requested")
         st = C.c_int(0)
-        new = lib.lb_gpu_index_new_f16 if dtype == DataType.Float16 else lib.lb_gpu_index_new
+        new = {DataType.Float16: lib.lb_gpu_index_new_f16, DataType.Int8: lib.lb_gpu_index_new_i8}.get(dtype, lib.lb_gpu_index_new)
         h = new(cfg.DeviceID, cfg.Dimension, int(cfg.Metric), C.byref(st))
         if not h:
             _lib.check(st.value or 7)
@@ -86,7 +87,7 @@ class Index:
         self.device = cfg.DeviceID
         self.metric = MetricType(int(cfg.Metric))
         self.data_type = dtype
-        self._np = np.float16 if dtype == DataType.Float16 else np.float32  # element type of Add / Search arguments
+        self._np = {DataType.Float16: np.float16, DataType.Int8: np.int8}.get(dtype, np.float32)  # element type of Add / Search arguments
         self._lock = threading.Lock()
         self._closed = False
 
@@ -104,8 +105,7 @@ class Index:
             if ids.size != n:
                 raise ValueError(f"id count {ids.size} does not match vector count {n}")
             idp = ids.ctypes.data
-        add = self._lib.lb_gpu_index_add_f16 if self._np is np.float16 else self._lib.lb_gpu_index_add
-        _lib.check(add(self._h, n, vectors.ctypes.data, idp), self._h, lib=self._lib)
+        _lib.check(self._entry("lb_gpu_index_add")(self._h, n, vectors.ctypes.data, idp), self._h, lib=self._lib)
 
     def Search(self, vector, k, ctx=None):
         """Search(vector []float32, k int) (ids []int64, distances []float32, err)  (faiss_gpu.go:107-144)"""
@@ -134,23 +134,28 @@ class Index:
         nq = queries.shape[0]
         dist = np.empty((nq, k), np.float32)
         labels = np.empty((nq, k), np.int64)
-        search = self._lib.lb_gpu_index_search_f16_ctx if self._np is np.float16 else self._lib.lb_gpu_index_search_ctx
+        search = self._entry("lb_gpu_index_search", "_ctx")
         _lib.check(search(self._h, nq, queries.ctypes.data, k, dist.ctypes.data,
                           labels.ctypes.data, ctx._h if ctx is not None else None), self._h, lib=self._lib)
         return labels, dist
 
     def _as_elems(self, a):
-        """The index's element type, contiguous.  A float16 index takes np.float16 arrays only: rounding float32 data to fp16
-        here would change the vectors silently."""
-        if self._np is np.float16:
+        """The index's element type, contiguous.  A float16 index takes np.float16 arrays only, an int8 index np.int8 arrays
+        only: converting other data here would change the vectors silently."""
+        if self._np is np.float16 or self._np is np.int8:
             a = np.asarray(a)
-            if a.dtype != np.float16:
-                raise TypeError(f"a float16 index takes np.float16 arrays, got {a.dtype}")
+            if a.dtype != self._np:
+                raise TypeError(f"a {np.dtype(self._np).name} index takes np.{np.dtype(self._np).name} arrays, got {a.dtype}")
             return np.ascontiguousarray(a)
         return np.ascontiguousarray(a, np.float32)
 
+    def _entry(self, name, suffix=""):
+        """the C entry point for this index's element type: name + ("" | "_f16" | "_i8") + suffix"""
+        tag = "_f16" if self._np is np.float16 else "_i8" if self._np is np.int8 else ""
+        return getattr(self._lib, name + tag + suffix)
+
     def dtype(self):
-        """0 float32, 1 float16 (lb_gpu_index_dtype)"""
+        """0 float32, 1 float16, 2 int8 (lb_gpu_index_dtype)"""
         self._live()
         return int(self._lib.lb_gpu_index_dtype(self._h))
 
@@ -181,15 +186,14 @@ class Index:
                                                         d_dist, d_score, stream), self._h, lib=self._lib)
 
     def add_device(self, n, d_vectors, d_ids=None):
-        """d_vectors: f32 rows, or fp16 rows on a float16 index"""
+        """d_vectors: f32 rows, fp16 rows on a float16 index, int8 rows on an int8 index"""
         self._live()
-        add = self._lib.lb_gpu_index_add_f16_device if self._np is np.float16 else self._lib.lb_gpu_index_add_device
-        _lib.check(add(self._h, n, d_vectors, d_ids), self._h, lib=self._lib)
+        _lib.check(self._entry("lb_gpu_index_add", "_device")(self._h, n, d_vectors, d_ids), self._h, lib=self._lib)
 
     def search_device(self, nq, d_queries, k, d_dist, d_labels, stream=None, ctx=None):
-        """d_queries: f32, or fp16 on a float16 index"""
+        """d_queries: f32, fp16 on a float16 index, int8 on an int8 index"""
         self._live()
-        search = self._lib.lb_gpu_index_search_f16_device_ctx if self._np is np.float16 else self._lib.lb_gpu_index_search_device_ctx
+        search = self._entry("lb_gpu_index_search", "_device_ctx")
         _lib.check(search(self._h, nq, d_queries, k, d_dist, d_labels, stream,
                           ctx._h if ctx is not None else None), self._h, lib=self._lib)
 
