@@ -189,6 +189,7 @@ DIAG_SIGNATURES = [
     ("lb_debug_search_fail_next", None, [_i]),
     ("lb_debug_set_add_register_min", None, [C.c_longlong]),
     ("lb_debug_sample_plan", None, [C.c_longlong, _i, C.c_uint, C.c_uint, C.POINTER(C.c_longlong)]),
+    ("lb_debug_cand_geometry", None, [_i, C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
 ]
 _diag = None
 

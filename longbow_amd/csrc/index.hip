@@ -2533,6 +2533,15 @@ void lb_debug_sample_plan(long long n, int keep, unsigned cap, unsigned count_ma
     out[2] = p.count;
     out[3] = p.m;
 }
+// host-only: the candidate-list geometry of a request of k (candidates kept per query, list capacity)
+void lb_debug_cand_geometry(int k, int *kc, unsigned *cap)
+{
+    int c;
+    uint32_t p;
+    cand_geometry(k, c, p);
+    *kc = c;
+    *cap = p;
+}
 // timing-only ablations whose results are wrong by design, the in-kernel clock probe, staging A/B
 void lb_debug_set_gemm_ablation(int v) { lb::g_gemm_ablation = v; }
 void lb_debug_set_gemm_glds(int v) { lb::g_gemm_glds = v; }

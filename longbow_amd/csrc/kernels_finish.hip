@@ -672,9 +672,11 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
         }
         __syncthreads();
         total = scal[6];
-        if (total > smax) {
+        // (each workgroup clips its own members to smax before the hand-in: one workgroup beyond smax while the others hold
+        // none sums to exactly smax.  ns_all counts every member of the query's list, whichever workgroup holds it.)
+        if (total > smax || ns_all > smax) {
             flags |= 2u;
-            total = smax;
+            total = total < smax ? total : smax;
         }
         ns = total;
         for (uint32_t c = tid; c < ns; c += FN_THREADS) {
