@@ -179,13 +179,14 @@ def load():
     return _lib
 
 
-# Test hooks and timing-only ablations exist ONLY in the diagnostic build (liblongbow_gpu_diag.so, -DLB_DIAG):
+# Test hooks exist ONLY in the diagnostic build (liblongbow_gpu_diag.so, -DLB_DIAG):
 # tests that force a fallback path create their handles on this library (Index(cfg, lib=load_diag())).
 DIAG_SO_PATH = os.path.join(_HERE, "liblongbow_gpu_diag.so")
 DIAG_SIGNATURES = [
     ("lb_debug_set_sample_tau", None, [_i]),
     ("lb_debug_vmm_fail_next", None, [_i]),
     ("lb_debug_fused_fail_next", None, [_i]),
+    ("lb_debug_tin_withhold_next", None, [_i]),
     ("lb_debug_search_fail_next", None, [_i]),
     ("lb_debug_set_add_register_min", None, [C.c_longlong]),
     ("lb_debug_sample_plan", None, [C.c_longlong, _i, C.c_uint, C.c_uint, C.POINTER(C.c_longlong)]),

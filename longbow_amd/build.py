@@ -28,8 +28,8 @@ def _stale(target, deps):
 
 
 def build(force=False, verbose=False, diag=False):
-    """diag=True builds liblongbow_gpu_diag.so with -DLB_DIAG: LB_* environment tunables, timing-only
-    ablation kernels and the clock probe (tools/ only; select it with LB_GPU_SO=<path>)."""
+    """diag=True builds liblongbow_gpu_diag.so with -DLB_DIAG: the LB_* numeric tunables read from the environment,
+    the lb_debug_* test hooks and the observing counters (tests/ and tools/; select it with LB_GPU_SO=<path>)."""
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     hdrs = [os.path.join(CSRC, h) for h in HEADERS]
     objs = []

@@ -27,7 +27,7 @@
 
 using namespace lb;
 
-namespace lb { extern int g_adc_ablation; extern int g_gemm_ablation; extern int g_gemm_glds; void read_clock_probe(unsigned long long out[8], bool reset); int debug_gemm_occupancy(); void read_fused_probe(unsigned long long out[8], bool reset); void read_tall2_probe(unsigned long long out[8], bool reset); void read_tall16_probe(unsigned long long out[8], bool reset); void read_finish_probe(unsigned long long out[8], bool reset); }
+namespace lb { void read_fused_probe(unsigned long long out[8], bool reset); void read_finish_probe(unsigned long long out[8], bool reset); }
 
 namespace {
 
@@ -482,8 +482,9 @@ struct SamplePlan {
     uint32_t count = 0; // sampled rows
     int m = 0;
 };
-std::atomic<int> g_sample_tau{lb_tunable("LB_SAMPLE_TAU", 1)};
+std::atomic<int> g_sample_tau{1}; // test hook (diagnostic build): 0 = the classic bootstrap schedule only
 std::atomic<int> g_fused_fail_next{0}; // test hook: treat the next fused launch as one whose waits gave up
+std::atomic<int> g_tin_withhold_next{0}; // test hook (diagnostic build): the next TAUIN launch's thresholds never come out
 std::atomic<int> g_last_route{0}; // diagnostic build: kind * 10 + split of the last batched search's route
 std::atomic<int> g_search_fail_next{0}; // test hook (diagnostic build): the next search on this process fails with LB_ERR_INTERNAL
 // Add batches of at least this many bytes pin the caller's buffer instead of staging it (0 = never)
@@ -733,7 +734,6 @@ static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, b
                           bool f32_rows = true)
 {
     static const int narrow_max = lb_tunable("LB_NARROW_MAXQ", 384);
-    static const bool nsplit_on = lb_tunable("LB_NARROW_SPLIT", 1) != 0;
     const int tiles32 = (nq + 31) / 32, tiles64 = (nq + 63) / 64, tiles128 = (nq + 127) / 128, tiles256 = (nq + 255) / 256;
     // (tall tiles only with enough of them to fill the chip a few times over: 512 workgroups run at once, and at 125k
     // visible rows x 256 queries the 978 tall tiles came out 5 % behind the 3908 smaller ones)
@@ -744,29 +744,27 @@ static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, b
     const bool image = cmode == LB_CAND_SPLIT_BF16 && have_image;
     if (!f32_rows) narrow_ok = false;
     if (narrow_ok && !image && (cmode == LB_CAND_AUTO || nq <= narrow_max)) {
-        const int nsp = nsplit_on ? 2 : 0;
-        if (nq <= 32 || tiles32 <= 10) add(ROUTE_NARROW32, nsp, route_ms(kCostNarrow32, n, D, tiles32));
-        if (nq > 32) add(ROUTE_NARROW64, nsp, route_ms(kCostNarrow64, n, D, tiles64));
+        if (nq <= 32 || tiles32 <= 10) add(ROUTE_NARROW32, 2, route_ms(kCostNarrow32, n, D, tiles32));
+        if (nq > 32) add(ROUTE_NARROW64, 2, route_ms(kCostNarrow64, n, D, tiles64));
     }
     // (round 4: the 256 x 128 tile -- ROUTE_TALL, kernels_gemm_tall.hip -- is gone: within 2-5 % of the 64-query narrow tile and of
     // this one wherever it was picked, profiles/r03_route_grid.txt, and never picked once the fp16 route is on offer)
     if (narrow_ok) {
         if (image) {
             add(ROUTE_TALL2, 1, route_ms(kCostTall2Image, n, D, tiles256));
-        } else if (nsplit_on && (cmode != LB_CAND_F32_MFMA || nq <= narrow_max)) {
+        } else if (cmode != LB_CAND_F32_MFMA || nq <= narrow_max) {
             const bool forced = cmode == LB_CAND_SPLIT_BF16_INREG;
             if (nq > 128 && (tall2_fills || forced)) add(ROUTE_TALL2, 2, route_ms(kCostTall2Inreg, n, D, tiles256));
         }
     }
     // one fp16 product instead of three bf16 ones (split code 3): AUTO and the explicit LB_CAND_F16, while the corpus norms
     // allow it (f16_ok) and there are enough tiles to fill the chip
-    static const int f16_on = lb_tunable("LB_F16", 1);
     // (a filtered view of a corpus that has its fp16 image: from the size a sampled threshold exists for, the cost model
     // decides -- round 3's gate of 128 Mi elements kept 100k x 768 views on the 64-query split tile: 0.21 / 0.30 / 0.50 ms at
     // 128 / 256 / 512 queries where the image serves them in 0.16 / 0.20 / 0.28)
     static const int64_t f16_view_min = lb_tunable("LB_F16_VIEW_MIN", 16384);
     // (over the fp16 copy the route needs neither dim % 32 == 0 nor aligned queries: both images are zero-padded planes)
-    if ((narrow_ok || have_f16_image) && f16_ok && f16_on && !image && (nq > 32 || have_f16_image) &&
+    if ((narrow_ok || have_f16_image) && f16_ok && !image && (nq > 32 || have_f16_image) &&
         (cmode == LB_CAND_F16 || (cmode == LB_CAND_AUTO && (n >= 262144 || (have_f16_image && n >= f16_view_min)))))
     { // (below: launch overheads decide, and the narrow tiles win; a filtered view of a large corpus counts by its elements)
         if (have_f16_image && nq <= 128) { // (one query tile: the 64- / 128-query form of the persistent kernel)
@@ -977,7 +975,6 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     const int split = route.split;                 // of the operands handed to the kernel: 0 f32, 1 images, 2 f32 split in registers
     const bool use_narrow = route.kind == ROUTE_NARROW32 || route.kind == ROUTE_NARROW64;
     const bool tile64 = route.kind == ROUTE_NARROW64;
-    const bool nsplit = use_narrow && route.split == 2;
     const bool use_tall = route.kind == ROUTE_TALL2 || route.kind == ROUTE_TALL16 || route.kind == ROUTE_NARROW16;
     const bool use_tall2 = route.kind == ROUTE_TALL2;
     const bool use_tall16 = route.kind == ROUTE_TALL16 || route.kind == ROUTE_NARROW16; // (the launcher takes the 64-query tile by itself)
@@ -994,8 +991,7 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     // query image is (rho_q per query, query_prep_body) -- a third to a half of the worst case for data that fills the
     // mantissa, subnormal effects included:  gamma(q) = 1.05 (rho_x + A (1 + rho_x) + 2^-21) + 1.05 (1 + rho_x)(1 + A) rho_q,
     // A = (D + 8) 2^-24 the f32 accumulation of D exact products
-    static const bool rho_on = lb_tunable("LB_MEASURED_RHO", 1) != 0;
-    const bool measured = rho_on && route.split == 3 && have_xh && (h->xh_rho > 0.f || h->xh_exact) &&
+    const bool measured = route.split == 3 && have_xh && (h->xh_rho > 0.f || h->xh_exact) &&
                           h->xh_rho < 4.0e-4f; // (else the worst case is the better bound)
     const float accA = (float)(h->dim + 8) * u24;
     const float qrho_k = measured ? 1.05f * (1.0f + h->xh_rho) * (1.0f + accA) : 0.f;
@@ -1052,28 +1048,26 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     // the batch redone exactly in 1 ms)
     // (and thresholds of rank up to 32: with k = 300 -- 1024 candidates, m = 48 -- the threshold workgroups outlast the waits of
     // the corpus workgroups: 200k x 768 at 32 queries gave up on every search, 1.5 ms)
-    const bool fused = sp.on && use_narrow && nsplit && nq <= fused_max && nq <= 64 && n >= 131072 && sp.m <= 32;
+    const bool fused = sp.on && use_narrow && nq <= fused_max && nq <= 64 && n >= 131072 && sp.m <= 32;
     // a search over a row list on the persistent fp16 kernels: its candidate entries carry positions of the list
     const bool entries_pos = use_tall16 && rv.rowmap != nullptr &&
                              tall16_entries_are_positions(h->dim, nq, have_xh, true, mask != nullptr);
     // over the fp16 copy the sample goes through the persistent kernel itself: 512 granules of 16 consecutive rows, evenly
     // spaced over the span (whole KiB of the K-blocked image; every workgroup takes a share of them)
-    static const bool granule_on = lb_tunable("LB_GRANULE_SAMPLE", 1) != 0;
     // (up to 8 queries the wave-per-row kernel over the f32 rows is 5 us quicker: every load of a row in flight at once)
     static const int light_max = lb_tunable("LB_LIGHT_SAMPLE_MAXQ", 8); // (also over a row list: at 32 queries the wave-per-row
                                                                         // kernel took 105 us against the granule sample's 40)
     // (dot product's lower-bound keys: the sample must come out of the same kernel; centred L2 keys the wave-per-row kernel
     // computes too, from the f32 rows about the same centre)
     const bool granule_sample = sp.on && use_tall16 && sp.count % 16 == 0 && (rv.rowmap == nullptr || entries_pos) &&
-                                ((have_xh && granule_on && nq > light_max) || dot_lb || (centred && nq > light_max));
+                                ((have_xh && nq > light_max) || dot_lb || (centred && nq > light_max));
     // (not in front of the split tiles: up to 32 queries they always ran fused, and the wave-per-row sample was never paired
     // with them -- L2, k = 300, 8 queries over 50k rows: every query flagged and scanned)
     const bool light_sample = sp.on && !fused && !granule_sample && nq <= light_max && !use_narrow;
     // Up to 128 queries on the one-tile kernel over the image, one span: the candidate launch turns the sample into the
     // thresholds ITSELF (its first nq workgroups, on shorter row ranges; kernels_gemm_tall16.hip, TAUIN) -- no threshold launch
     // and no gap behind it in front of the pass.
-    static const bool tauin_on = lb_tunable("LB_TAUIN", 1) != 0;
-    const bool tauin = tauin_on && sp.on && sp.span >= n && use_tall16 && route.kind == ROUTE_NARROW16 && !fused &&
+    const bool tauin = sp.on && sp.span >= n && use_tall16 && route.kind == ROUTE_NARROW16 && !fused &&
                        (light_sample || granule_sample) && prep_riders &&
                        tall16_tin_ok(h->dim, nq, sp.span, have_xh, rv.rowmap != nullptr, mask != nullptr, (prep_riders && metric == LB_METRIC_COSINE), sp.count, sp.m);
     Tall16Tin tin{};
@@ -1088,6 +1082,9 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
         tin.Q = d_q;
         tin.qna = (prep_riders && metric == LB_METRIC_COSINE) ? w->d_qna : nullptr;
         tin.order = order;
+#ifdef LB_DIAG
+        tin.withhold = g_tin_withhold_next.exchange(0);
+#endif
     }
     // (up to 8 queries: the query preparation rides in the sample launch -- one launch and one gap less in front of the pass)
     const bool prep_rides = use_tall16 && light_sample && prep_riders;
@@ -1103,7 +1100,6 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     static const float finish_beta = 0.01f * (float)lb_tunable("LB_FINISH_BETA_PCT", 25);
     if (!light_sample && !fused && !use_tall16) launch_init_cand(w->cs, nullptr, nq, s);
     if (metric == LB_METRIC_COSINE && !norm_riders && !use_tall16) launch_query_norms(order, d_q, nullptr, nq, h->dim, w->d_qna, s); // (fp16 route: query_prep)
-    static const bool sample_narrow = lb_tunable("LB_TALL_SAMPLE_NARROW", 1) != 0;
     // (fp16 route, several 256-query tiles: the sample goes through the fp16 kernel itself -- 32 row tiles x nq/256 workgroups
     // against nq/64 x 64 of the narrow tile; 1024 queries: 1.94 -> 1.88 ms, 512: 1.015 -> 1.00; tools/probe/sample_route_probe.py)
     static const int sample_narrow_maxq = lb_tunable("LB_TALL_SAMPLE_NARROW_MAXQ", 384);
@@ -1113,18 +1109,18 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
         ProfScope p(w, s, prof, 0);
         if (use_narrow)
             launch_gemm_filter_narrow(metric, gx, h->d_norm2, h->d_rnorm, b, e, h->dim, gq, nq, mask, rowmap,
-                                      w->cs, boot, s, tile64, nsplit);
+                                      w->cs, boot, s, tile64);
         else if (use_tall16 && h->dim % 32 != 0 && (rowmap || mask) && !entries_pos)
             // the sample of a search over the fp16 copy when the dimension is not a multiple of 32: the f32 tile takes any
             launch_gemm_filter(metric, h->d_X, h->d_norm2, h->d_rnorm, b, e, h->dim, d_q, nq, mask, rowmap, w->cs, boot, 0, s);
-        else if (use_tall && boot && (wsplit == 2 || wsplit == 3) && sample_narrow && narrow_ok && !entries_pos && !own_keys &&
+        else if (use_tall && boot && (wsplit == 2 || wsplit == 3) && narrow_ok && !entries_pos && !own_keys &&
                  !(use_tall16 && nq > sample_narrow_maxq))
             // the 8192-row sample of a tall-tile search: the 64-query tile of the narrow kernel (same contraction, f32
             // operands) gets through its 24 K-steps of 32 in 31-35 us, the tall tile through its 48 of 16 in 57
             // (narrow_ok: that kernel reads the f32 queries in 16-B pieces -- a batch pointer that is not 16-B aligned stays
             // on the fp16 kernel below, which reads its own image of the batch)
             launch_gemm_filter_narrow(metric, h->d_X, h->d_norm2, h->d_rnorm, b, e, h->dim, d_q, nq, mask, rowmap, w->cs,
-                                      true, s, /*tile64=*/true, /*split=*/true);
+                                      true, s, /*tile64=*/true);
         else if (use_tall16)
             launch_gemm_filter_tall16(metric, h->d_X, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, b, e, h->dim, w->d_qh, d_qinv, nq,
                                       mask, rowmap, w->cs, boot, s, have_xh ? h->d_Xh : nullptr, h->xh_cap, 0u, d_qnrm, gsum,
@@ -1207,7 +1203,6 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
             fs.qna = norm_riders ? w->d_qna : nullptr;
             fs.order = order;
             fs.fail_host = w->h_fail;
-            fs.relaxed = lb_tunable("LB_FUSED_RELAXED", 0);
             launch_gemm_filter_narrow_fused(metric, gx, h->d_norm2, h->d_rnorm, 0, sp.span, h->dim, gq, nq, mask, rv.rowmap,
                                             w->cs, s, tile64, fs);
             w->fs_base += fused_sample_blocks(sp.count, nq, tile64);
@@ -2520,6 +2515,7 @@ int lb_gpu_index_last_timing(const lb_gpu_index *hc, float ms[5], int n_launch[5
 void lb_debug_set_sample_tau(int v) { g_sample_tau.store(v); } // 0: classic bootstrap schedule only
 void lb_debug_vmm_fail_next(int v) { g_vmm_fail_next.store(v); } // the next in-place growth is refused (-> hipMalloc + copy)
 void lb_debug_fused_fail_next(int v) { g_fused_fail_next.store(v); } // the next fused sample launch counts as timed out (-> exact path for the batch)
+void lb_debug_tin_withhold_next(int v) { g_tin_withhold_next.store(v); } // the next TAUIN launch's waits give up in the kernel (-> exact path)
 int lb_debug_last_route(void) { return g_last_route.load(); } // RouteKind * 10 + split of the most recent batched search
 void lb_debug_search_fail_next(int v) { g_search_fail_next.store(v); } // the next search in this process returns LB_ERR_INTERNAL
 void lb_debug_set_add_register_min(long long bytes) { g_add_register_min.store(bytes); } // ingest A/B (tools/bench_add.py)
@@ -2542,15 +2538,8 @@ void lb_debug_cand_geometry(int k, int *kc, unsigned *cap)
     *kc = c;
     *cap = p;
 }
-// timing-only ablations whose results are wrong by design, the in-kernel clock probe, staging A/B
-void lb_debug_set_gemm_ablation(int v) { lb::g_gemm_ablation = v; }
-void lb_debug_set_gemm_glds(int v) { lb::g_gemm_glds = v; }
-void lb_debug_set_adc_ablation(int v) { lb::g_adc_ablation = v; }
-int lb_debug_gemm_occupancy(void) { return lb::debug_gemm_occupancy(); }
-void lb_debug_read_clock_probe(unsigned long long *out, int reset) { lb::read_clock_probe(out, reset != 0); }
+// counters of the fused launch and of the finish launch (they only observe)
 void lb_debug_read_fused_probe(unsigned long long *out, int reset) { lb::read_fused_probe(out, reset != 0); }
-void lb_debug_read_tall2_probe(unsigned long long *out, int reset) { lb::read_tall2_probe(out, reset != 0); }
-void lb_debug_read_tall16_probe(unsigned long long *out, int reset) { lb::read_tall16_probe(out, reset != 0); }
 void lb_debug_read_finish_probe(unsigned long long *out, int reset) { lb::read_finish_probe(out, reset != 0); }
 #endif
 

@@ -77,7 +77,6 @@ struct FinishArgsT {
     uint32_t *xcnt;   // [nq] members written to the scratch block (zero between launches)
     uint64_t *xent;   // [nq][smax] exact entries
     float *xcmp;      // [nq][smax] compare values
-    int abl;          // diagnostic build: timing-only ablations (1 = no gather / exact sums, 2 = no radix select, 3 = return at once)
 };
 using FinishArgs = FinishArgsT<float>;
 
@@ -206,9 +205,6 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
     float *scmp = reinterpret_cast<float *>(skey + smax);      // [smax] compare values
     float *work = scmp + smax;                                 // the scoring scheme's tile
 
-#ifdef LB_DIAG
-    if (a.abl == 3) return;
-#endif
     const uint32_t raw = a.cs.cnt[qi];
     const uint32_t n = raw < a.cs.cap ? raw : a.cs.cap;
     const uint64_t tau = a.cs.tau[qi];
@@ -267,11 +263,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
     const uint32_t kk = n < (uint32_t)k ? n : (uint32_t)k;
     const bool dot_lb = METRIC == METRIC_DOT && a.lb_norm2 != nullptr;
     // (lower-bound dot keys: the cut comes from the k-th smallest UPPER bound below, a_k is not used -- one selection less)
-#ifdef LB_DIAG
-    const uint64_t pivot = (a.abl == 2 || dot_lb) ? (e[0] | 0xffffffffull) : radix_kth_regs<PER>(e, kk, hist, wsum, scal, red, tid);
-#else
     const uint64_t pivot = dot_lb ? (e[0] | 0xffffffffull) : radix_kth_regs<PER>(e, kk, hist, wsum, scal, red, tid);
-#endif
 
     // ---- the cut ------------------------------------------------------------------------------------------------------
     const float ga = a.gamma + (a.qrho ? a.qrho_k * a.qrho[qi] : 0.f);
@@ -359,16 +351,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
             skey[c] = pack_entry(dist, s_rows[c]);
             scmp[c] = cmp;
         }
-    } else
-#ifdef LB_DIAG
-    if (a.abl == 1) {
-        for (uint32_t c = tid; c < nm; c += FN_THREADS) {
-            skey[c] = pack_entry(0.f, s_rows[c]);
-            scmp[c] = 0.f;
-        }
-    } else
-#endif
-    if (!a.aligned) {
+    } else if (!a.aligned) {
         for (uint32_t c = tid; c < nm; c += FN_THREADS) {
             float t, nbt, dist, cmp;
             exact_pair_sums<METRIC, ORDER>(a.X + (int64_t)s_rows[c] * D, q, D, t, nbt);
@@ -776,7 +759,6 @@ static void launch_finish_rows(int metric, int order, const T *X, int D, const f
     a.X = X; a.D = D; a.Q = Q; a.qna = qna; a.cs = cs; a.k = k; a.maxnorm2 = d_maxnorm2; a.gamma = gamma; a.beta = beta;
     a.ids = ids; a.posmap = posmap; a.out_dist = out_dist; a.out_labels = out_labels; a.flags_host = flags_host;
     a.smax = smax; a.done = done; a.xcnt = xcnt;
-    a.abl = lb_tunable("LB_FINISH_ABL", 0);
     a.xent = reinterpret_cast<uint64_t *>(xscratch);
     a.xcmp = reinterpret_cast<float *>(a.xent + (size_t)nq_split_max * smax);
     a.aligned = sizeof(T) == 4 && (D % 4 == 0) && D >= 4 && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) && ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
@@ -803,9 +785,8 @@ static void launch_finish_rows(int metric, int order, const T *X, int D, const f
     // to the last one to arrive as the split form does.  Config-5 share: finish 99 -> 67 us at 32 queries, 104 -> 74 at 128
     // (135 members a workgroup: one group of the ring instead of 256 + 14); at k = 100 x 768 dimensions (0.5 MB per query) it
     // is level, and stays one workgroup per query.
-    static const int split_ring_on = lb_tunable("LB_FINISH_SPLIT_RING", 1);
     static const int split_ring_maxq = lb_tunable("LB_FINISH_SPLIT_RING_MAXQ", 128);
-    const bool split_ring = G == 1 && split_ring_on && nq > 16 && nq <= split_ring_maxq && (int64_t)k * D >= 131072 && can_split &&
+    const bool split_ring = G == 1 && nq > 16 && nq <= split_ring_maxq && (int64_t)k * D >= 131072 && can_split &&
                             a.aligned && nst >= 2;
     if (split_ring) G = nq <= 32 ? 8 : (nq <= 64 ? 4 : 2);
     const bool split = G > 1;

@@ -24,8 +24,6 @@ constexpr int BN = 128; // queries per tile   (MFMA B operand, output cols = lan
 constexpr int BK = 32;
 constexpr int GEMM_THREADS = 256;
 
-__device__ unsigned long long g_clock_probe[8]; // profiling aid (ABL == 5 only)
-
 struct GemmArgs {
     const float *X;
     const float *norm2;
@@ -67,11 +65,7 @@ __device__ __forceinline__ f32x4 load_chunk(const float *base, int64_t row, int 
     return v;
 }
 
-// ABL: timing-only ablations for profiling (results are wrong unless ABL == 0):
-//   1 = no barriers, 2 = no global loads / LDS writes in the loop, 3 = no fragment reads in the loop,
-//   4 = MFMA only (1+2+3), 5 = normal + clock stamps (shader cycles vs 100 MHz real time),
-//   6 = no epilogue at all, 7 = epilogue pass 1 only (no atomics / stores)
-// GLDS: stage tiles with direct-to-LDS DMA loads (global_load_lds_dwordx4; needs ALIGNED == 2).
+// ALIGNED == 2 (GLDS): stage tiles with direct-to-LDS DMA loads (global_load_lds_dwordx4); the other modes stage through registers.
 // The LDS image is lane-linear per wave instruction (base + lane*16), so the chunk swizzle is
 // applied to the per-lane SOURCE address; the image is identical to the register-staged one.
 // SPLIT: X and Q are the split-bf16 images produced by split_bf16_kernel: per row and group of 16
@@ -79,14 +73,13 @@ __device__ __forceinline__ f32x4 load_chunk(const float *base, int64_t row, int 
 // 2^-18|x|).  The inner product is then hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 (exact
 // bf16 products, f32 accumulation): ~f32-accurate candidate keys at 3/16 of the f32 MFMA cycles.
 // Staging, LDS image and epilogue are shared with the f32 kernel (same bytes per row and K-step).
-template <int METRIC, int ALIGNED, int ABL = 0, bool GLDS = false, int SPLIT = 0>
+template <int METRIC, int ALIGNED, int SPLIT = 0>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a)
 {
+    constexpr bool GLDS = ALIGNED == 2;
     // XCD-aware tile order: blocks b and b+8 share an XCD (round-robin dispatch), so the
     // n_q_tiles query tiles of one corpus tile are issued back-to-back on ONE XCD and the
     // corpus tile is pulled from HBM into that XCD's L2 once.  Placement only affects speed.
-    uint64_t stamp_entry = 0;
-    if (ABL == 5) stamp_entry = __builtin_amdgcn_s_memtime();
     const int b = blockIdx.x;
     const int xcd = b & 7;
     const int in_xcd = b >> 3;
@@ -171,8 +164,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)(gsrcA[i] + k0),
                 (__attribute__((address_space(3))) void *)(&lds[stage][0][j * 8 * BK]), 16, 0,
-                (ABL == 8) ? 0 : 2); // aux 2 = nt: the corpus streams through once; keeps Q resident in L2
-                                     // (measured: L2-miss traffic 2.5x -> 1.8x algorithmic, same speed)
+                2); // aux 2 = nt: the corpus streams through once; keeps Q resident in L2
+                    // (measured: L2-miss traffic 2.5x -> 1.8x algorithmic, same speed)
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)(gsrcB[i] + k0),
                 (__attribute__((address_space(3))) void *)(&lds[stage][1][j * 8 * BK]), 16, 0, 0);
@@ -219,8 +212,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
     }
     __syncthreads();
 
-    uint64_t stamp_t0 = 0, stamp_r0 = 0;
-    if (ABL == 5) { stamp_t0 = __builtin_amdgcn_s_memtime(); stamp_r0 = __builtin_amdgcn_s_memrealtime(); }
     // Main loop.  Per K-step (BK = 32): the next stage's global loads are issued first, the
     // fragment reads of sub-step s+1 are issued before the 16 MFMAs of sub-step s (register
     // double buffer), and the LDS write of the next stage happens in the middle of the MFMA
@@ -228,7 +219,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
     // the only serial section left at the end of a K-step is the barrier itself.
     for (int kt = 0; kt < nk; kt++) {
         const int cur = kt & 1;
-        const bool has_next = (ABL == 2 || ABL == 4) ? false : (kt + 1 < nk);
+        const bool has_next = kt + 1 < nk;
         if (has_next) {
             const int k0 = (kt + 1) * BK;
             if (GLDS) {
@@ -306,23 +297,15 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
             }
         } else {
         f32x4 fa[2][2], fb[2][2];
-        if ((ABL != 3 && ABL != 4) || kt == 0) {
 #pragma unroll
-            for (int t = 0; t < 2; t++) {
-                fa[0][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, h)]);
-                fb[0][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, h)]);
-            }
-        } else {
-#pragma unroll
-            for (int t = 0; t < 2; t++) { fa[0][t] = ra[t]; fb[0][t] = rb[t]; }
+        for (int t = 0; t < 2; t++) {
+            fa[0][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, h)]);
+            fb[0][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, h)]);
         }
 #pragma unroll
         for (int s = 0; s < 4; s++) {
             const int cb = s & 1, nb = cb ^ 1;
-            if (ABL == 3 || ABL == 4) {
-#pragma unroll
-                for (int t = 0; t < 2; t++) { fa[nb][t] = fa[cb][t] + 1.0f; fb[nb][t] = fb[cb][t]; }
-            } else if (s < 3) {
+            if (s < 3) {
                 const int ch = 2 * (s + 1) + h; // the two lane halves take alternate 16-B chunks;
                                                 // the same k permutation is applied to A and B.
 #pragma unroll
@@ -349,28 +332,13 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
             }
         }
         }
-        if (ABL != 1 && ABL != 4) __syncthreads();
-    }
-    if (ABL == 5 && threadIdx.x == 0) {
-        const uint64_t t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        atomicAdd((unsigned long long *)&g_clock_probe[0], (unsigned long long)(t1 - stamp_t0));
-        atomicAdd((unsigned long long *)&g_clock_probe[1], (unsigned long long)(r1 - stamp_r0));
-        atomicAdd((unsigned long long *)&g_clock_probe[2], 1ull);
-        atomicAdd((unsigned long long *)&g_clock_probe[3], (unsigned long long)(stamp_t0 - stamp_entry));
-        stamp_t0 = t1; // reuse: epilogue start
+        __syncthreads();
     }
 
     // ---- epilogue: key + admission -------------------------------------------------
     // C layout (32x32): col = lane&31 (query), row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
     // All per-row side inputs (norm / mask) are fetched up front in one burst: a load per
     // element inside the admission loop would serialise 64 L2 round trips per lane.
-    if (ABL == 6) {
-#pragma unroll
-        for (int i = 0; i < 2; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) asm volatile("" ::"v"(acc[i][j]));
-        return;
-    }
     float aux[2][4][4];
     uint32_t rid[2][4][4]; // corpus row ids of this lane's 32 rows
     uint32_t vbits = 0; // bit (tm*16 + g*4 + e): row visible (in range and not masked out)
@@ -423,7 +391,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
                 for (int e = 0; e < 4; e++)
                     bits |= admit_exact(cand_key<METRIC>(acc[tm][tn][4 * g + e], aux[tm][g][e]), rid[tm][g][e], tau_key[tn], tau_row[tn]) << (tm * 16 + g * 4 + e);
         bits &= vbits;
-        if (ABL == 7) { asm volatile("" ::"v"(bits)); continue; }
         // ONE returning atomic per lane reserves the slots; the stores are fire-and-forget
         if (bits) {
             uint32_t pos = atomicAdd(&a.cs.cnt[qj], (uint32_t)__builtin_popcount(bits));
@@ -439,20 +406,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
                             pos++;
                         }
         }
-    }
-    if (ABL == 5) {
-        __syncthreads();
-        if (threadIdx.x == 0)
-            atomicAdd((unsigned long long *)&g_clock_probe[4], (unsigned long long)(__builtin_amdgcn_s_memtime() - stamp_t0));
-    }
-}
-
-void read_clock_probe(unsigned long long out[8], bool reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_clock_probe), 8 * sizeof(unsigned long long));
-    if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_clock_probe), z, sizeof z);
     }
 }
 
@@ -480,16 +433,6 @@ void launch_split_bf16(const float *src, float *dst, int64_t rows, int D, hipStr
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, dst, n8);
 }
 
-int debug_gemm_occupancy()
-{
-    int nb = -1;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, gemm_filter_kernel<METRIC_COS, 2, 0>, GEMM_THREADS, 0);
-    return nb;
-}
-
-int g_gemm_glds = 0;     // A/B switch (tools/ablate_gemm.py, diagnostic build): -1 = register staging
-int g_gemm_ablation = 0; // profiling aid (diagnostic build only); always 0 in the product build
-
 void launch_gemm_filter(int metric, const float *X, const float *norm2, const float *rnorm,
                         int64_t row_begin, int64_t row_end, int D, const float *Q, int nq,
                         const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot, int split,
@@ -509,65 +452,18 @@ void launch_gemm_filter(int metric, const float *X, const float *norm2, const fl
     const bool aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
                          ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
     const int mode = !aligned ? 0 : (D % BK == 0 ? 2 : 1);
-#ifdef LB_DIAG // timing-only ablations and the clock probe exist only in the diagnostic build
-    if (split == 1 && g_gemm_ablation > 0 && metric == METRIC_COS) {
-        switch (g_gemm_ablation) {
-        case 1: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 1, true, 1>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 2: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 2, true, 1>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 5: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 5, true, 1>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 6: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 6, true, 1>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        default: break;
-        }
-    }
-    static const int env_abl = lb_tunable("LB_GEMM_ABL", 0);
-    if (env_abl > 0 && g_gemm_ablation == 0) g_gemm_ablation = env_abl;
-    if (!split && g_gemm_ablation == 8 && metric == METRIC_COS && mode == 2) { // A/B: default cache policy on the corpus stream
-        hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 8, true, 0>), grid, dim3(GEMM_THREADS), 0, s, a);
-        return;
-    }
-    if (!split && g_gemm_ablation > 0 && metric == METRIC_COS && mode == 2) {
-        switch (g_gemm_ablation) {
-        case 1: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 1>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 2: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 2>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 3: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 3>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 4: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 4>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 5: {
-            // LB_GEMM_1WG=1: pad the LDS request so that only ONE workgroup fits a CU (diagnostic: main-loop
-            // cycles of a wave that has its SIMD to itself)
-            static const int one_wg = lb_tunable("LB_GEMM_1WG", 0);
-            const size_t pad = one_wg ? 40 * 1024 : 0;
-            if (pad) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_filter_kernel<METRIC_COS, 2, 5>),
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad);
-            hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 5>), grid, dim3(GEMM_THREADS), pad, s, a);
-            return;
-        }
-        case 6: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 6>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        case 7: hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 7>), grid, dim3(GEMM_THREADS), 0, s, a); return;
-        default: break;
-        }
-    }
-#endif
-    // direct-to-LDS staging is the default for the aligned, D % 32 == 0 case (LB_GEMM_GLDS=0 or
-    // g_gemm_glds = -1 selects the register-staged pipeline for A/B runs)
-    static const bool env_noglds = lb_tunable("LB_GEMM_GLDS", 1) == 0;
     if (split == 1) {
         // X / Q are split-bf16 images (caller guarantees D % 32 == 0 and 16-B alignment)
-        if (metric == METRIC_L2) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_L2, 2, 0, true, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else if (metric == METRIC_COS) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 0, true, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((gemm_filter_kernel<METRIC_DOT, 2, 0, true, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
+        if (metric == METRIC_L2) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_L2, 2, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
+        else if (metric == METRIC_COS) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((gemm_filter_kernel<METRIC_DOT, 2, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
         return;
     }
     if (split == 2) {
         // X / Q are the plain f32 operands, split in registers (D % 32 == 0, 16-B aligned)
-        if (metric == METRIC_L2) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_L2, 2, 0, true, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else if (metric == METRIC_COS) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 0, true, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((gemm_filter_kernel<METRIC_DOT, 2, 0, true, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
-        return;
-    }
-    if (g_gemm_glds >= 0 && !env_noglds && g_gemm_ablation == 0 && mode == 2) {
-        if (metric == METRIC_L2) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_L2, 2, 0, true>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else if (metric == METRIC_COS) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 0, true>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((gemm_filter_kernel<METRIC_DOT, 2, 0, true>), grid, dim3(GEMM_THREADS), 0, s, a);
+        if (metric == METRIC_L2) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_L2, 2, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
+        else if (metric == METRIC_COS) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
+        else hipLaunchKernelGGL((gemm_filter_kernel<METRIC_DOT, 2, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
         return;
     }
 #define LB_GEMM(M, AL) hipLaunchKernelGGL((gemm_filter_kernel<M, AL>), grid, dim3(GEMM_THREADS), 0, s, a)

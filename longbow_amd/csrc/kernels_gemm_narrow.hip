@@ -16,8 +16,7 @@
 // The kernel is a template over the tile: <256 rows, 32 queries> (above) and <128 rows, 64 queries>
 // for batches of 33..~200 queries (each wave 32 rows x 64 queries, again 2 MFMA tiles; LDS
 // 2 x (16 + 8) KiB, three workgroups per CU), which would otherwise pay a second corpus pass per
-// extra 32 queries; over SPLIT (the contraction on 3 x bf16 MFMA with both operands split in
-// registers: the default) and over FUSED (5..32 queries: the sampled threshold of the search rides
+// extra 32 queries; and over FUSED (5..32 queries: the sampled threshold of the search rides
 // inside the launch -- sample tiles, per-query threshold workgroups, corpus workgroups of two row
 // tiles that pick the thresholds up; see FusedSample in lb_device.h and LABNOTES.md 3.3).
 #include "lb_admit.h"
@@ -65,7 +64,7 @@ constexpr uint32_t kSpinLimit = 1500; // x ~0.6 us (s_sleep 8 + one L2 round tri
                                       // not co-resident; the batch is then redone on the exact path and the give-up is counted
                                       // (lb_gpu_index_fused_giveups)
 
-// SPLIT: the inner products are computed as hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with both
+// The inner products are computed as hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with both
 // operands split into bf16 pairs IN REGISTERS after the (unchanged) f32 LDS staging -- no second copy of
 // the corpus.  3/16 of the f32 MFMA cycles: at 32-64 queries the f32 contraction keeps the MFMA pipe 70 %
 // busy under the corpus stream (0.31 of 0.45 ms per pass at 1M x 768), which is what held this kernel at
@@ -74,7 +73,7 @@ constexpr uint32_t kSpinLimit = 1500; // x ~0.6 us (s_sleep 8 + one L2 round tri
 // FUSED: the launch starts with a.fs.n_blocks workgroups that score the sampled rows and publish the thresholds (see
 // FusedSample in lb_device.h); the corpus tiles fetch their thresholds in front of the epilogue instead of at entry.
 // The sample workgroups have the lowest block ids, so they are resident before any workgroup that waits for them.
-template <int METRIC, int NBM, int NBN, bool SPLIT, bool FUSED = false> // NBM corpus rows x NBN queries per tile: <256, 32> or <128, 64>
+template <int METRIC, int NBM, int NBN, bool FUSED = false> // NBM corpus rows x NBN queries per tile: <256, 32> or <128, 64>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowArgs a)
 {
     constexpr int WROWS = NBM / 4;   // corpus rows per wave
@@ -214,10 +213,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
                 // the first workgroups of a launch, and the two dependent device-scope loads then cost nothing at the end
                 const int qj = q0 + tid < a.nq ? q0 + tid : a.nq - 1;
                 // (the flag is read with ACQUIRE: pairs with the release store of the threshold workgroup)
-#ifdef LB_DIAG
-                if (kt == 0 && a.fs.relaxed) spec_ready = __hip_atomic_load(&a.fs.ready[qj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else
-#endif
                 if (kt == 0) spec_ready = __hip_atomic_load(&a.fs.ready[qj], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
                 if (kt == 3 && spec_ready == a.fs.epoch)
                     spec_tau = __hip_atomic_load(&a.cs.tau[qj], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -226,59 +221,32 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
             else if (tp + 1 < ntiles_here) stage_in(srcA[tp + 1 < TPW ? tp + 1 : tp], cur ^ 1, 0);
             const float *As = lds_all + cur * STAGE_F;
             const float *Bs = As + NBM * NBK;
-            if (SPLIT) {
-                // MFMA k-step ks covers floats [16 ks, 16 ks + 16) of the 32-float K-step; lane half h supplies
-                // k = 8h .. 8h+7 of it: two 16-B chunks (4 ks + 2h, 4 ks + 2h + 1) of the row's 128-B piece
+            // MFMA k-step ks covers floats [16 ks, 16 ks + 16) of the 32-float K-step; lane half h supplies
+            // k = 8h .. 8h+7 of it: two 16-B chunks (4 ks + 2h, 4 ks + 2h + 1) of the row's 128-B piece
 #pragma unroll
-                for (int ks = 0; ks < 2; ks++) {
-                    const int ch = 4 * ks + 2 * h;
-                    bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
+            for (int ks = 0; ks < 2; ks++) {
+                const int ch = 4 * ks + 2 * h;
+                bf16x8 ah[TM], al[TM], bh[TN], bl[TN];
 #pragma unroll
-                    for (int t = 0; t < TM; t++) {
-                        const int r = wave * WROWS + t * 32 + l31;
-                        split_bf16x8(*reinterpret_cast<const f32x4 *>(&As[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&As[nswz(r, ch + 1)]),
-                                     ah[t], al[t]);
-                    }
-#pragma unroll
-                    for (int t = 0; t < TN; t++) {
-                        const int r = t * 32 + l31;
-                        split_bf16x8(*reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch + 1)]),
-                                     bh[t], bl[t]);
-                    }
-#pragma unroll
-                    for (int tm = 0; tm < TM; tm++)
-#pragma unroll
-                        for (int tn = 0; tn < TN; tn++) {
-                            acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh[tn], acc[tp][tm][tn], 0, 0, 0);
-                            acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl[tn], acc[tp][tm][tn], 0, 0, 0);
-                            acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh[tn], acc[tp][tm][tn], 0, 0, 0);
-                        }
+                for (int t = 0; t < TM; t++) {
+                    const int r = wave * WROWS + t * 32 + l31;
+                    split_bf16x8(*reinterpret_cast<const f32x4 *>(&As[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&As[nswz(r, ch + 1)]),
+                                 ah[t], al[t]);
                 }
-            } else {
-                f32x4 fa[2][TM], fb[2][TN];
 #pragma unroll
-                for (int t = 0; t < TM; t++) fa[0][t] = *reinterpret_cast<const f32x4 *>(&As[nswz(wave * WROWS + t * 32 + l31, h)]);
-#pragma unroll
-                for (int t = 0; t < TN; t++) fb[0][t] = *reinterpret_cast<const f32x4 *>(&Bs[nswz(t * 32 + l31, h)]);
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const int cb = s & 1, nb = cb ^ 1;
-                    if (s < 3) {
-                        const int ch = 2 * (s + 1) + h;
-#pragma unroll
-                        for (int t = 0; t < TM; t++)
-                            fa[nb][t] = *reinterpret_cast<const f32x4 *>(&As[nswz(wave * WROWS + t * 32 + l31, ch)]);
-#pragma unroll
-                        for (int t = 0; t < TN; t++) fb[nb][t] = *reinterpret_cast<const f32x4 *>(&Bs[nswz(t * 32 + l31, ch)]);
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-#pragma unroll
-                        for (int tm = 0; tm < TM; tm++)
-#pragma unroll
-                            for (int tn = 0; tn < TN; tn++)
-                                acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cb][tm][e], fb[cb][tn][e], acc[tp][tm][tn], 0, 0, 0);
+                for (int t = 0; t < TN; t++) {
+                    const int r = t * 32 + l31;
+                    split_bf16x8(*reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch)]), *reinterpret_cast<const f32x4 *>(&Bs[nswz(r, ch + 1)]),
+                                 bh[t], bl[t]);
                 }
+#pragma unroll
+                for (int tm = 0; tm < TM; tm++)
+#pragma unroll
+                    for (int tn = 0; tn < TN; tn++) {
+                        acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh[tn], acc[tp][tm][tn], 0, 0, 0);
+                        acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl[tn], acc[tp][tm][tn], 0, 0, 0);
+                        acc[tp][tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh[tn], acc[tp][tm][tn], 0, 0, 0);
+                    }
             }
             __syncthreads();
         }
@@ -532,17 +500,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
         // publish: cnt / tau above, then ready[j] with RELEASE semantics at agent scope; the waiters read ready[j] with
         // ACQUIRE.  (The asm wait stays: ROCm 7.2 can drop the release fence's own vmcnt wait when the scoreboard looks
         // empty to it -- MI355X_MICROARCH.md "Compiler hazard".)
-#ifdef LB_DIAG
-        if (a.fs.relaxed) { // A/B only: what the release costs
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(&a.fs.ready[j], a.fs.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        } else
-#endif
-        {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(&a.fs.ready[j], a.fs.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __hip_atomic_store(&a.fs.ready[j], a.fs.epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
 #ifdef LB_DIAG
         atomicMax(&g_fused_probe[1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
 #endif
@@ -553,7 +513,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_filter_narrow_kernel(NarrowA
 void launch_gemm_filter_narrow(int metric, const float *X, const float *norm2, const float *rnorm,
                                int64_t row_begin, int64_t row_end, int D, const float *Q, int nq,
                                const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
-                               hipStream_t s, bool tile64, bool split)
+                               hipStream_t s, bool tile64)
 {
     if (row_end <= row_begin || nq <= 0) return;
     NarrowArgs a;
@@ -565,21 +525,15 @@ void launch_gemm_filter_narrow(int metric, const float *X, const float *norm2, c
     a.n_q_tiles = (nq + bn - 1) / bn;
     const int groups = (a.n_row_tiles + 7) / 8;
     dim3 grid((unsigned)(groups * 8 * a.n_q_tiles));
-#define LB_NARROW_S(M, SP)                                                                                          \
-    do {                                                                                                            \
-        if (tile64) hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 128, 64, SP>), grid, dim3(NTHREADS), 0, s, a); \
-        else hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 256, 32, SP>), grid, dim3(NTHREADS), 0, s, a);        \
-    } while (0)
-#define LB_NARROW(M)                        \
-    do {                                    \
-        if (split) LB_NARROW_S(M, true);    \
-        else LB_NARROW_S(M, false);         \
+#define LB_NARROW(M)                                                                                             \
+    do {                                                                                                         \
+        if (tile64) hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 128, 64>), grid, dim3(NTHREADS), 0, s, a); \
+        else hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 256, 32>), grid, dim3(NTHREADS), 0, s, a);        \
     } while (0)
     if (metric == METRIC_L2) LB_NARROW(METRIC_L2);
     else if (metric == METRIC_COS) LB_NARROW(METRIC_COS);
     else LB_NARROW(METRIC_DOT);
 #undef LB_NARROW
-#undef LB_NARROW_S
 }
 
 uint32_t fused_sample_blocks(uint32_t count, int nq, bool tile64)
@@ -605,10 +559,10 @@ void launch_gemm_filter_narrow_fused(int metric, const float *X, const float *no
     a.fs = fs;
     const int groups = ((a.n_row_tiles + 1) / 2 + 7) / 8; // a corpus workgroup contracts two row tiles
     dim3 grid((unsigned)(fs.n_blocks + (uint32_t)(groups * 8 * a.n_q_tiles)));
-#define LB_NARROW_F(M)                                                                                                    \
-    do {                                                                                                                  \
-        if (tile64) hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 128, 64, true, true>), grid, dim3(NTHREADS), 0, s, a); \
-        else hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 256, 32, true, true>), grid, dim3(NTHREADS), 0, s, a);        \
+#define LB_NARROW_F(M)                                                                                              \
+    do {                                                                                                            \
+        if (tile64) hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 128, 64, true>), grid, dim3(NTHREADS), 0, s, a); \
+        else hipLaunchKernelGGL((gemm_filter_narrow_kernel<M, 256, 32, true>), grid, dim3(NTHREADS), 0, s, a);        \
     } while (0)
     if (metric == METRIC_L2) LB_NARROW_F(METRIC_L2);
     else if (metric == METRIC_COS) LB_NARROW_F(METRIC_COS);

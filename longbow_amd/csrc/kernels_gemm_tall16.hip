@@ -63,10 +63,6 @@ constexpr int H_STAGE_BYTES = H_A_BYTES + H_B_BYTES;  // 48 KB
 constexpr int H_NST = 3;
 constexpr int H_NI = 6; // DMA requests per wave and stage: 4 x 8 corpus rows + 2 x 16 query rows
 
-#ifdef LB_DIAG
-__device__ unsigned long long g_tall16_probe[8]; // ABL == 5: cycle stamps summed over waves (tools/tall16_probe.py)
-#endif
-
 struct Tall16Args {
     const float *X;
     const float *norm2;
@@ -89,8 +85,6 @@ struct Tall16Args {
     CandState cs;
     int n_row_tiles, n_q_tiles;
     int boot;
-    int abl; // diagnostic build: timing-only ablations of the persistent form (6 = no epilogue, 7 = no flush)
-    int rot; // persistent form: the query tiles of a corpus tile walk K rotated by rot K-steps against each other
     const _Float16 *Xh; // or null: fp16 image of the corpus, [Dp / H_XP][xh_cap][H_XP] (index.hip: sync_f16_image)
     int64_t xh_cap;     // rows per K-block plane of Xh
     uint32_t gstride;   // persistent forms, sample pass: 0 = position p is row row_begin + p; else the positions are granules of 16
@@ -106,6 +100,9 @@ struct Tall16Args {
     float *tin_qna;
     int qsplit; // one-tile form, sample pass of a batch beyond 128 queries: 0, or the number of 128-query windows the launch's
                 // workgroups divide into
+#ifdef LB_DIAG
+    int tin_withhold; // TAUIN: the duty workgroups keep their thresholds (lb_debug_tin_withhold_next)
+#endif
 };
 
 // Persistent forms: the launch's positions [0, n_pos) are dealt to the workgroups (narrow form) / workgroup groups (256-query
@@ -148,11 +145,9 @@ __device__ __forceinline__ int haswz(int row, int chunk) { return row * 128 + ((
 __device__ __forceinline__ int hbswz(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
 
 // NT: the corpus requests carry the non-temporal policy (few query tiles per corpus tile: the line is not read again)
-// SPREAD: the requests of stage k + 2 go out one by one between the MFMAs of step k instead of in one burst behind the barrier
+// The requests of stage k + 2 go out one by one between the MFMAs of step k instead of in one burst behind the barrier
 // (in a burst all eight waves queue on the CU's one address unit while the matrix pipe idles)
-// ABL (diagnostic build; the product instantiates 0 only): timing-only ablations 1 = no requests inside the loop, 2 = requests,
-// waits and barriers only (no LDS reads, no MFMAs), 3 = corpus requests only; 5 = cycle stamps
-template <int METRIC, bool NT, bool SPREAD, int ABL = 0>
+template <int METRIC, bool NT>
 __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16Args a)
 {
     // XCD-aware order as in gemm_filter_kernel: the query tiles of one corpus tile run side by side on one XCD
@@ -163,8 +158,6 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
     const int rt = (in_xcd / a.n_q_tiles) * 8 + xcd;
     if (rt >= a.n_row_tiles) return;
 
-    unsigned long long pr_start = 0;
-    if (ABL == 5) pr_start = __builtin_amdgcn_s_memtime();
     extern __shared__ __attribute__((aligned(16))) unsigned char hlds[];
     unsigned char *ring = hlds;                                                        // [H_NST][A 32 KB | B 16 KB]
     float *s_aux = reinterpret_cast<float *>(ring + H_NST * H_STAGE_BYTES);            // [H_BM]
@@ -247,21 +240,14 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
     // (the loads above were waited for by the compiler before their use; from here on only the DMA requests are in flight,
     // H_NI per wave and stage, and the compiler sees none of them)
 
-    unsigned long long pr_wait = 0, pr_bar = 0, pr_t0 = 0, pr_r0 = 0;
-    if (ABL == 5) { pr_t0 = __builtin_amdgcn_s_memtime(); pr_r0 = __builtin_amdgcn_s_memrealtime(); }
-    // one K-step; ISSUE: the requests of stage kt + 2 are made during it
+    // one K-step; ISSUE: the requests of stage kt + 2 are made during it (into the slot read at step kt - 1)
     auto step = [&](int kt, auto issue_c) {
-        constexpr bool ISSUE = decltype(issue_c)::value && ABL != 1;
-        unsigned long long s0 = 0, s1 = 0;
-        if (ABL == 5) s0 = __builtin_amdgcn_s_memtime();
+        constexpr bool ISSUE = decltype(issue_c)::value;
         // stage kt has landed once at most the requests of stage kt + 1 are outstanding
-        if (kt + 1 < nk) wait_vmcnt<(ABL == 3 ? 4 : H_NI)>();
+        if (kt + 1 < nk) wait_vmcnt<H_NI>();
         else wait_vmcnt<0>();
-        if (ABL == 5) s1 = __builtin_amdgcn_s_memtime();
         __builtin_amdgcn_s_barrier(); // everyone's part of stage kt is in; everyone is done reading stage kt - 1
         asm volatile("" ::: "memory");
-        if (ABL == 5) { pr_wait += s1 - s0; pr_bar += __builtin_amdgcn_s_memtime() - s1; }
-        if (ISSUE && !SPREAD) issue(kt + 2); // into the slot read at step kt - 1
         const uint32_t A2 = ring_base + (uint32_t)((kt + 2) % H_NST) * H_STAGE_BYTES + (uint32_t)(wave * 32 * 128);
         const uint32_t B2 = ring_base + (uint32_t)((kt + 2) % H_NST) * H_STAGE_BYTES + H_A_BYTES + (uint32_t)(wave * 32 * 64);
         const int ka2 = (kt + 2) * (H_BK * 4);
@@ -271,32 +257,28 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
 #pragma unroll
         for (int kb = 0; kb < 2; kb++) { // the stage's two MFMA k-blocks of 16
             f16x8 af[2];
-            if (ABL != 2) {
 #pragma unroll
-                for (int tm = 0; tm < 2; tm++) {
-                    const int r = wr * 64 + tm * 32 + l31;
-                    // lane half h supplies k = 16 kb + 8 h .. + 7: f32 chunks 4 kb + 2 h and the next
-                    const f32x4 x0 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h));
-                    const f32x4 x1 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h + 1));
-                    af[tm] = cvt_f16x8(x0, x1);
-                }
+            for (int tm = 0; tm < 2; tm++) {
+                const int r = wr * 64 + tm * 32 + l31;
+                // lane half h supplies k = 16 kb + 8 h .. + 7: f32 chunks 4 kb + 2 h and the next
+                const f32x4 x0 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h));
+                const f32x4 x1 = *reinterpret_cast<const f32x4 *>(As + haswz(r, 4 * kb + 2 * h + 1));
+                af[tm] = cvt_f16x8(x0, x1);
             }
 #pragma unroll
             for (int tn = 0; tn < 4; tn++) {
-                if (ABL != 2) {
-                    const int r = wc * 128 + tn * 32 + l31;
-                    // 8 fp16 = one 16-B chunk: k = 16 kb + 8 h .. + 7 is chunk 2 kb + h of the 64-B row
-                    const f16x8 bf = __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4 *>(Bs + hbswz(r, 2 * kb + h)));
+                const int r = wc * 128 + tn * 32 + l31;
+                // 8 fp16 = one 16-B chunk: k = 16 kb + 8 h .. + 7 is chunk 2 kb + h of the 64-B row
+                const f16x8 bf = __builtin_bit_cast(f16x8, *reinterpret_cast<const f32x4 *>(Bs + hbswz(r, 2 * kb + h)));
 #pragma unroll
-                    for (int tm = 0; tm < 2; tm++)
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[tm], bf, acc[tm][tn], 0, 0, 0);
-                }
-                if (ISSUE && SPREAD) { // slots 0 1 2 . 4 5 6 . of the step's eight MFMA pairs: corpus 0..3, queries 0..1
+                for (int tm = 0; tm < 2; tm++)
+                    acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[tm], bf, acc[tm][tn], 0, 0, 0);
+                if (ISSUE) { // slots 0 1 2 . 4 5 6 . of the step's eight MFMA pairs: corpus 0..3, queries 0..1
                     const int slot = kb * 4 + tn;
                     if (slot < 3) lds_dma16_noclobber<NT>(srcA[slot] + 1024 * slot + ka2, A2 + 1024u * slot);
                     else if (slot == 4) lds_dma16_noclobber<NT>(srcA[3] + 1024 * 3 + ka2, A2 + 1024u * 3);
-                    else if (slot == 5 && ABL != 3) lds_dma16_noclobber<false>(srcB[0] + kb2, B2);
-                    else if (slot == 6 && ABL != 3) lds_dma16_noclobber<false>(srcB[1] + 1024 + kb2, B2 + 1024u);
+                    else if (slot == 5) lds_dma16_noclobber<false>(srcB[0] + kb2, B2);
+                    else if (slot == 6) lds_dma16_noclobber<false>(srcB[1] + 1024 + kb2, B2 + 1024u);
                 }
             }
         }
@@ -304,18 +286,6 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
     int kt = 0;
     for (; kt + 2 < nk; kt++) step(kt, std::true_type{});
     for (; kt < nk; kt++) step(kt, std::false_type{});
-#ifdef LB_DIAG
-    if (ABL == 5 && lane == 0) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        atomicAdd(&g_tall16_probe[0], t1 - pr_t0); // loop cycles
-        atomicAdd(&g_tall16_probe[1], r1 - pr_r0); // the same in 100 MHz ticks
-        atomicAdd(&g_tall16_probe[2], 1ull);       // waves
-        atomicAdd(&g_tall16_probe[3], pr_wait);    // in s_waitcnt vmcnt
-        atomicAdd(&g_tall16_probe[4], pr_bar);     // in s_barrier
-        atomicAdd(&g_tall16_probe[5], pr_t0 - pr_start); // prologue (kernel start -> loop start)
-    }
-    const unsigned long long pr_loop_end = ABL == 5 ? __builtin_amdgcn_s_memtime() : 0ull;
-#endif
 
     // ---- epilogue: key + admission, one MFMA row tile (this lane's 16 rows of it) at a time ----------------
     // C layout (32x32): col = lane & 31 (query), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
@@ -404,9 +374,6 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
         }
     }
     if (!a.boot) fl.flush(tid, a.cs, q0);
-#ifdef LB_DIAG
-    if (ABL == 5 && lane == 0) atomicAdd(&g_tall16_probe[6], __builtin_amdgcn_s_memtime() - pr_loop_end); // epilogue
-#endif
 }
 
 // ---- persistent form: one workgroup per CU walks its corpus tiles as ONE flat pipeline ------------------------------------
@@ -513,17 +480,14 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
     const int64_t kb_stride = (int64_t)a.q_stride * (H_BK * 2);
     const int nk = AIMG ? (a.D + H_BK - 1) / H_BK : a.D / H_BK; // (both images are zero-padded to a multiple of 32 dimensions)
 
-    const int krot = (qt * a.rot) % nk;
     // request cursor: the stage to be requested next = K-step ik of this workgroup's tile it, into ring slot islot
     int it = 0, ik = 0, islot = 0;
     bool cursor_new_tile = false;
     auto piece = [&](int p) { // request p of the cursor's stage: 0 .. NPA - 1 corpus, then two of queries
         const uint32_t A = ring_base + (uint32_t)islot * STAGE + (uint32_t)(wave * 32 * (AIMG ? 64 : 128));
         const uint32_t B = ring_base + (uint32_t)islot * STAGE + A_BYTES + (uint32_t)(wave * 32 * 64);
-        int ke = ik + krot; // (the sum over k does not care where it starts)
-        if (ke >= nk) ke -= nk;
-        if (p < NPA) lds_dma16_noclobber<NT>(srcA[p] + (AIMG ? h_xoff(ke, plane_bytes) : (int64_t)ke * (H_BK * 4)), A + 1024u * p);
-        else lds_dma16_noclobber<false>(srcB[p - NPA] + ke * kb_stride, B + 1024u * (p - NPA));
+        if (p < NPA) lds_dma16_noclobber<NT>(srcA[p] + (AIMG ? h_xoff(ik, plane_bytes) : (int64_t)ik * (H_BK * 4)), A + 1024u * p);
+        else lds_dma16_noclobber<false>(srcB[p - NPA] + ik * kb_stride, B + 1024u * (p - NPA));
     };
     auto advance = [&]() { // (beyond the last stage the cursor stays on it)
         islot = islot == NST - 1 ? 0 : islot + 1;
@@ -701,9 +665,6 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
             cslot = nslot;
         }
 
-#ifdef LB_DIAG
-        if (a.abl == 6) continue; // timing only: no epilogue
-#endif
         // One K-step per tile (D <= 32): this tile's side input was asked for in the middle of the step before, which the
         // K-steps' waits do not cover (they cover a stage asked for DIST steps earlier, and with it everything older).  By now
         // 2 NPS - H1 (+ 1) requests are newer than it; vmcnt retires in order, the barrier publishes the other waves' parts.
@@ -797,10 +758,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
         // counter per search, and their serialisation showed (0.1 ms at 128 queries).
         if (wcnt > WFLUSH && lane == 0) s_flag[i % 3] = 1;
         if (tid == 0) s_flag[(i + 1) % 3] = 0;
-        bool flush = !BOOT && (i + 1 == n_my || (i > 0 && s_flag[(i + 2) % 3] != 0));
-#ifdef LB_DIAG
-        if (a.abl == 7) flush = false;
-#endif
+        const bool flush = !BOOT && (i + 1 == n_my || (i > 0 && s_flag[(i + 2) % 3] != 0));
         if (flush) { // (all waves are here together) ONE returning global atomic per query with entries, then the stores
             const uint32_t total = wcnt < WCAP ? wcnt : WCAP;
             for (uint32_t z = lane; z < total; z += 64) s_rk[z] = (uint16_t)atomicAdd(&s_qn[s_q[z]], 1u);
@@ -948,7 +906,7 @@ __device__ __forceinline__ void tin_duty(const Tall16Args &a, int j, unsigned ch
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #ifdef LB_DIAG
-            if (a.abl != 12) // (12: the threshold never comes out -- every wave's wait gives up; tests/test_gpu_thresholds_in_launch.py)
+            if (!a.tin_withhold) // (lb_debug_tin_withhold_next: the threshold never comes out -- every wave's wait gives up)
 #endif
             __hip_atomic_store(&a.cs.tau[j], tv, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             if (a.tin_qna) a.tin_qna[j] = exact_sq_norm_lds(sq, a.D, a.tin_order); // (nothing waits for it but this workgroup's rows)
@@ -1125,9 +1083,6 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
         if (TAUIN) asm volatile("" : "+v"(qs[tn]), "+v"(m2qs[tn]));
         const float scale = __builtin_bit_cast(float, (254u << 23) - __builtin_bit_cast(uint32_t, qs[tn]));
         tkc[tn] = METRIC != METRIC_COS ? tk : tk * scale;
-#ifdef LB_DIAG
-        if (a.abl == 8) tkc[tn] = -__builtin_huge_valf(); // timing only: nothing is admitted
-#endif
     }
     // (what the ring leaves; MAPPED: 6 KB less, the row-id ring)
     constexpr uint32_t WCAP = BN == 256 ? 272 : (MAPPED ? 296 : 360), WFLUSH = BN == 256 ? 176 : (MAPPED ? 200 : 240), SEG_BYTES = WCAP * 12;
@@ -1247,9 +1202,6 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
                 const float tk = tau_key_of(tau);
                 const float scale = __builtin_bit_cast(float, (254u << 23) - __builtin_bit_cast(uint32_t, qs[tn]));
                 tkc[tn] = METRIC != METRIC_COS ? tk : tk * scale;
-#ifdef LB_DIAG
-                if (a.abl == 8) tkc[tn] = -__builtin_huge_valf();
-#endif
             }
         }
         // ---- epilogue of the tile (as the 256-query form: 2 VALU + 1 scalar branch per element, per-wave segments) ----------
@@ -1439,17 +1391,6 @@ void launch_f16_residual(const _Float16 *X, int64_t row_begin, int64_t row_end, 
                        center, stat);
 }
 
-#ifdef LB_DIAG
-void read_tall16_probe(unsigned long long out[8], bool reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tall16_probe), 8 * sizeof(unsigned long long));
-    if (reset) {
-        unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tall16_probe), z, sizeof z);
-    }
-}
-#endif
-
 int corpus_f16_plane_dims() { return H_XP; }
 
 void launch_corpus_to_f16(const float *X, int64_t row_begin, int64_t row_end, int D, void *Xh, int64_t cap, hipStream_t s,
@@ -1478,7 +1419,6 @@ void launch_queries_to_f16(const float *Q, int nq, int D, void *Qh, float *qinv,
 // do the persistent kernels serve this launch (and, under a row list, leave POSITIONS in the candidate entries)?
 static bool tall16_persistent_ok(int D, int nq, bool img, bool mapped, bool masked)
 {
-    static const int persist = lb_tunable("LB_F16_PERSIST", 1);
     static const int cus = [] {
         int dev = 0, n = 0;
         (void)hipGetDevice(&dev);
@@ -1493,17 +1433,15 @@ static bool tall16_persistent_ok(int D, int nq, bool img, bool mapped, bool mask
         (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMaxSharedMemoryPerBlock, dev);
         return n;
     }();
-    static const int mapped_on = lb_tunable("LB_F16_MAPPED", 1);
     const int spx = cus / 8;
-    if (!persist || masked || spx < 1 || (nq + H_BN - 1) / H_BN > spx || lds_max < 163840) return false;
+    if (masked || spx < 1 || (nq + H_BN - 1) / H_BN > spx || lds_max < 163840) return false;
     // a row list: gathered out of the image only, and with enough K-steps per tile for the row-id ring's hand-off (D >= 256)
-    if (mapped && !(img && mapped_on && (D + H_BK - 1) / H_BK >= 8)) return false;
+    if (mapped && !(img && (D + H_BK - 1) / H_BK >= 8)) return false;
     return true;
 }
 bool tall16_runs_persistent(int D, int nq, bool img, bool mapped, bool masked) { return tall16_persistent_ok(D, nq, img, mapped, masked); }
 bool tall16_tin_ok(int D, int nq, int64_t n_pos, bool img, bool mapped, bool masked, bool with_norm, uint32_t count, int m)
 {
-    static const int n16 = lb_tunable("LB_F16_NARROW", 1);
     static const int cus = [] {
         int dev = 0, n = 0;
         (void)hipGetDevice(&dev);
@@ -1511,7 +1449,7 @@ bool tall16_tin_ok(int D, int nq, int64_t n_pos, bool img, bool mapped, bool mas
         return n;
     }();
     uint32_t dr;
-    return img && n16 && nq <= 128 && tall16_persistent_ok(D, nq, img, mapped, masked) && tin_plan(D, nq, n_pos, (cus / 8) * 8, with_norm, count, m, dr);
+    return img && nq <= 128 && tall16_persistent_ok(D, nq, img, mapped, masked) && tin_plan(D, nq, n_pos, (cus / 8) * 8, with_norm, count, m, dr);
 }
 bool tall16_entries_are_positions(int D, int nq, bool img, bool mapped, bool masked)
 {
@@ -1538,8 +1476,6 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
     a.Qh = reinterpret_cast<const _Float16 *>(Qh); a.qinv = qinv; a.nq = nq; a.q_stride = q_stride; a.mask = mask; a.cs = cs; a.boot = boot ? 1 : 0;
     a.n_row_tiles = (int)((row_end - row_begin + H_BM - 1) / H_BM);
     a.n_q_tiles = (nq + H_BN - 1) / H_BN;
-    a.abl = lb_tunable("LB_F16_ABL", 0);
-    a.rot = lb_tunable("LB_F16_ROT", 0);
     a.Xh = reinterpret_cast<const _Float16 *>(Xh);
     a.xh_cap = xh_cap;
     const int groups = (a.n_row_tiles + 7) / 8;
@@ -1566,14 +1502,11 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
         // on; q_stride stays the batch's.
         const int tail = nq % H_BN;
         // (the sample of more than 128 queries: windows of 128 on the one-tile kernel in ONE launch, see the kernel)
-        static const int qsplit_on = lb_tunable("LB_F16_SAMPLE_QSPLIT", 1);
         static const int qsplit_maxq = lb_tunable("LB_F16_SAMPLE_QSPLIT_MAXQ", 1024);
-        static const int n16_on = lb_tunable("LB_F16_NARROW", 1);
-        const bool qsplit = img && n16_on && boot && gstride != 0 && nq > 128 && nq <= qsplit_maxq && (nq + 127) / 128 <= spx * 8 && qsplit_on && tin == nullptr;
+        const bool qsplit = img && boot && gstride != 0 && nq > 128 && nq <= qsplit_maxq && (nq + 127) / 128 <= spx * 8 && tin == nullptr;
         a.qsplit = qsplit ? (nq + 127) / 128 : 0;
-        static const int split_tail = lb_tunable("LB_F16_SPLIT_TAIL", 1);
         static const int split_tail_max = lb_tunable("LB_F16_SPLIT_TAIL_MAX", 128); // (65 .. 128 on the 128-query tile: 384 queries 0.90 -> 0.85 ms, 640: 1.39 -> 1.34)
-        if (img && may_split && split_tail && nq > H_BN && tail >= 1 && tail <= split_tail_max && !qsplit) {
+        if (img && may_split && nq > H_BN && tail >= 1 && tail <= split_tail_max && !qsplit) {
             const int head = nq - tail;
             tall16_window(metric, X, norm2, rnorm, row_begin, row_end, D, Qh, qinv, head, q_stride, mask, rowmap, cs, boot, s, Xh,
                           xh_cap, false, gstride, qnrm, gsum);
@@ -1585,10 +1518,9 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
                           qinv + head, tail, q_stride, mask, rowmap, ct, boot, s, Xh, xh_cap, false, gstride, qnrm ? qnrm + head : nullptr, gsum);
             return;
         }
-        static const int n16 = lb_tunable("LB_F16_NARROW", 1);
         // (the 256-query instance of this kernel measured level with the 4 x 2-wave tile below -- 0.43 ms per pass, bound by MFMA +
         // LDS work either way -- and is not built)
-        if (img && (nq <= 128 || qsplit) && n16) { // one query tile of 64 / 128: the pass is the image's HBM stream
+        if (img && (nq <= 128 || qsplit)) { // one query tile of 64 / 128: the pass is the image's HBM stream
             const int bn = (nq <= 64 && !qsplit) ? 64 : 128;
             const size_t ring_b = bn == 64 ? (size_t)6 * (H_BM * H_BK * 2 + 64 * H_BK * 2)
                                            : (bn == 128 ? (size_t)5 * (H_BM * H_BK * 2 + 128 * H_BK * 2) : (size_t)4 * (H_BM * H_BK * 2 + 256 * H_BK * 2));
@@ -1601,6 +1533,9 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
                 tauin = true; // thresholds inside the launch (see the kernel)
                 a.tin_count = tin->count; a.tin_m = tin->m; a.tin_tag = tin->tag;
                 a.tin_fail = tin->fail_host; a.tin_Q = tin->Q; a.tin_qna = tin->qna; a.tin_order = tin->order; a.tin_dr = dr;
+#ifdef LB_DIAG
+                a.tin_withhold = tin->withhold;
+#endif
             }
 #define LB_NARROW16T(M, N, P)                                                                                                  \
     do {                                                                                                                       \
@@ -1649,8 +1584,6 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
         const size_t pshmem = (img ? (size_t)4 * (H_BM * H_BK * 2 + H_B_BYTES) : (size_t)H_NST * H_STAGE_BYTES) + 2 * 512 * sizeof(float) +
                               16 + 2 * H_BN * 4 + 8 * (img ? 272 : 104) * 12; // ring, side inputs, flush flags + counters, admission segments
         const bool pnt = a.n_q_tiles <= 1;
-        static const int mapped_nt_on = lb_tunable("LB_F16_MAPPED_NT", 1); // (10 % visible, 256 queries: 243 -> 227 us; 50 %: 544 -> 535)
-        const bool mapped_nt = mapped_nt_on && pnt;
         dim3 pgrid((unsigned)(spx * 8));
 #define LB_TALL16P(M, N, I, B, P)                                                                                       \
     do {                                                                                                                \
@@ -1662,7 +1595,7 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
     do {                                                       \
         if (mapped) { /* (only over the image) */              \
             if (boot) LB_TALL16P(M, false, true, true, true);  \
-            else if (mapped_nt) LB_TALL16P(M, true, true, false, true); \
+            else if (pnt) LB_TALL16P(M, true, true, false, true); /* (10 % visible, 256 queries: 243 -> 227 us) */ \
             else LB_TALL16P(M, false, true, false, true);      \
         } else if (boot) { /* (a short launch: the cache policy does not matter) */ \
             if (img) LB_TALL16P(M, false, true, true, false);  \
@@ -1684,48 +1617,17 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
     }
     static const int nt_max_tiles = lb_tunable("LB_F16_NT_MAXTILES", 1);
     const bool nt = a.n_q_tiles <= nt_max_tiles;
-    static const int spread = lb_tunable("LB_F16_SPREAD", 1);
-    static const int abl = lb_tunable("LB_F16_ABL", 0);
-#define LB_TALL16(M, N, S, A)                                                                                    \
-    do {                                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_filter_tall16_kernel<M, N, S, A>),        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); /* per device */      \
-        hipLaunchKernelGGL((gemm_filter_tall16_kernel<M, N, S, A>), grid, dim3(H_THREADS), shmem, s, a);         \
+#define LB_TALL16(M, N)                                                                                    \
+    do {                                                                                                   \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_filter_tall16_kernel<M, N>),        \
+                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); /* per device */ \
+        hipLaunchKernelGGL((gemm_filter_tall16_kernel<M, N>), grid, dim3(H_THREADS), shmem, s, a);         \
     } while (0)
-#ifdef LB_DIAG
-    if (abl && metric == METRIC_COS) { // timing-only ablations / stamps (the bench metric only)
-        if (nt) {
-            if (abl == 1) LB_TALL16(METRIC_COS, true, true, 1);
-            else if (abl == 2) LB_TALL16(METRIC_COS, true, true, 2);
-            else if (abl == 3) LB_TALL16(METRIC_COS, true, true, 3);
-            else LB_TALL16(METRIC_COS, true, true, 5);
-        } else {
-            if (abl == 1) LB_TALL16(METRIC_COS, false, true, 1);
-            else if (abl == 2) LB_TALL16(METRIC_COS, false, true, 2);
-            else if (abl == 3) LB_TALL16(METRIC_COS, false, true, 3);
-            else LB_TALL16(METRIC_COS, false, true, 5);
-        }
-        return;
-    }
-#define LB_TALL16_M(M)                                   \
-    do {                                                 \
-        if (spread) {                                    \
-            if (nt) LB_TALL16(M, true, true, 0);         \
-            else LB_TALL16(M, false, true, 0);           \
-        } else {                                         \
-            if (nt) LB_TALL16(M, true, false, 0);        \
-            else LB_TALL16(M, false, false, 0);          \
-        }                                                \
+#define LB_TALL16_M(M)                \
+    do {                              \
+        if (nt) LB_TALL16(M, true);   \
+        else LB_TALL16(M, false);     \
     } while (0)
-#else
-#define LB_TALL16_M(M)                        \
-    do {                                      \
-        (void)spread;                         \
-        (void)abl;                            \
-        if (nt) LB_TALL16(M, true, true, 0);  \
-        else LB_TALL16(M, false, true, 0);    \
-    } while (0)
-#endif
     if (metric == METRIC_L2) LB_TALL16_M(METRIC_L2);
     else if (metric == METRIC_COS) LB_TALL16_M(METRIC_COS);
     else LB_TALL16_M(METRIC_DOT);

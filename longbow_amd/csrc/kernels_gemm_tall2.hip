@@ -34,8 +34,6 @@
 
 namespace lb {
 
-__device__ unsigned long long g_tall2_probe[8]; // diagnostic build, abl == 5: cycle stamps summed over waves
-
 namespace {
 
 constexpr int W_BM = 256, W_BN = 256, W_BK = 32; // tile rows, tile queries, floats per row and stage
@@ -43,7 +41,6 @@ constexpr int W_THREADS = 512;
 constexpr int W_STAGE_F = (W_BM + W_BN) * W_BK; // floats per stage (64 KB)
 constexpr int W_NST = 2;
 constexpr int W_NI = 8; // DMA instructions per wave and stage: 4 x 8 corpus rows + 4 x 8 query rows
-constexpr int W_DEFAULT_LOADERS = 8; // (see the LOADERS template parameter)
 
 struct Tall2Args {
     const float *X;
@@ -58,32 +55,12 @@ struct Tall2Args {
     CandState cs;
     int n_row_tiles, n_q_tiles;
     int boot;
-    int abl; // diagnostic build, timing only (results are wrong, nothing is admitted): 1 = no staging DMA behind the first
-             // stage, 2 = staging only (no LDS reads, no MFMAs)
 };
 
 // 128-B rows, eight 16-B chunks: chunk c of row r sits at position c ^ ((r >> 1) & 7), which spreads the 16 lanes of every
 // ds_read_b128 group (16 rows that are distinct mod 16, same chunk) over all 64 banks
 __device__ __forceinline__ int wswz(int row, int chunk) { return row * W_BK + ((chunk ^ ((row >> 1) & 7)) << 2); }
 
-// One LDS-DMA request, 16 B per lane (lane l lands at lds_addr + 16 l), under a wave-uniform EXEC mask (all ones or zero) set
-// inside the asm: the request is part of every wave's instruction stream but only the waves whose mask is set issue it.
-// Default cache policy: the query rows are re-read by every corpus tile, and a corpus line is shared by the query-tile
-// workgroups that run side by side on the XCD.  (A wave-dependent BRANCH around the request -- or two
-// copies of the loop -- keeps the accumulators from being promoted to registers: 380 "spills".)  No "memory" clobber: the
-// slot being filled is not touched by any compiler-visible access between the barriers that fence it.
-__device__ __forceinline__ void w_dma16_masked(const void *gsrc, uint32_t lds_addr, uint32_t mask32)
-{
-    uint32_t save;
-    uint64_t sexec;
-    mask32 = (uint32_t)__builtin_amdgcn_readfirstlane((int)mask32); // (wave-uniform by construction; makes it an SGPR)
-    lds_addr = (uint32_t)__builtin_amdgcn_readfirstlane((int)lds_addr);
-    asm volatile("s_mov_b64 %1, exec\n\ts_mov_b32 exec_lo, %4\n\ts_mov_b32 exec_hi, %4\n\ts_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\t"
-                 "s_nop 0\n\tglobal_load_lds_dwordx4 %2, off\n\ts_mov_b32 m0, %0\n\ts_mov_b64 exec, %1"
-                 : "=&s"(save), "=&s"(sexec) : "v"(gsrc), "s"(lds_addr), "s"(mask32));
-}
-// LOADERS (compile time): 8 = every wave requests its share of the next stage, 4 = waves 0-3 request all of it (see the
-// DMA set-up in the kernel).
 // Tried on this kernel and dropped:
 //  * the next stage's requests spread between the MFMAs of the step (two behind every 6 or 12 MFMAs): any inline-asm
 //    statement inside the unrolled MFMA block makes hipcc (ROCm 7.2) spill 130-230 registers -- and so do a wave-dependent
@@ -91,7 +68,7 @@ __device__ __forceinline__ void w_dma16_masked(const void *gsrc, uint32_t lds_ad
 //  * an L2 prefetch of the stage after next by a plain global_load_dword into a register nobody reads: the load lands after
 //    the asm statement has ended, the allocator has re-used the register by then and a pointer got overwritten (wrong
 //    candidates and a memory fault).  An in-flight load needs a destination the compiler cannot touch.
-template <int METRIC, int ASPLIT, int LOADERS>
+template <int METRIC, int ASPLIT>
 __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Args a)
 {
     // XCD-aware order as in gemm_filter_kernel: the query tiles of one corpus tile run side by side on one XCD
@@ -127,20 +104,13 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
 
     // DMA sources.  A request fills 8 rows (1 KiB): lane l lands at (row l / 8, chunk POSITION l % 8) and therefore fetches
     // the chunk that belongs there: position ^ ((row >> 1) & 7).
-    // LOADERS == 8: every wave requests its 32 corpus rows + 32 query rows (8 requests per stage).
-    // LOADERS == 4: waves 0-3 request 64 + 64 rows each (16 requests), waves 4-7 none.  Wave w and wave w + 4 share a SIMD:
-    //   while the loader sits in its requests (~1800 cycles per stage: the vector-memory path takes a 1-KiB request every
-    //   ~29 cycles per CU and both waves used to queue there at the same time) the other has the matrix pipe to itself,
-    //   and the loader then has it while the other waits at the barrier.  The requests are in every wave's instruction
-    //   stream, under an EXEC mask that is zero in waves 4-7 (a wave-dependent branch around them costs the accumulators
-    //   their registers).
-    constexpr int NI = LOADERS == 8 ? 8 : 16;
-    const int lw = LOADERS == 8 ? wave : (wave & 3);
-    constexpr int RPW = 256 / LOADERS; // rows of each operand a loader wave stages
+    // Every wave requests its 32 corpus rows + 32 query rows (8 requests per stage).
+    constexpr int NI = W_NI;
+    constexpr int RPW = 32; // rows of each operand a wave stages
     const float *src[NI];
 #pragma unroll
     for (int i = 0; i < NI; i++) {
-        const int row = lw * RPW + (i % (NI / 2)) * 8 + (lane >> 3);
+        const int row = wave * RPW + (i % (NI / 2)) * 8 + (lane >> 3);
         const int c = (lane & 7) ^ ((row >> 1) & 7);
         if (i < NI / 2) {
             src[i] = a.X + corpus_row(row0 + row) * (int64_t)a.D + 4 * c;
@@ -150,25 +120,15 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
             src[i] = a.Q + (int64_t)qr * a.D + 4 * c;
         }
     }
-    const uint32_t load_mask = (uint32_t)__builtin_amdgcn_readfirstlane((LOADERS == 8 || wave < 4) ? -1 : 0);
-    if (LOADERS == 8) { // grouped requests: the instruction offset (i & 3) KiB also moves the global address
+    // grouped requests: the instruction offset (i & 3) KiB also moves the global address
 #pragma unroll
-        for (int i = 0; i < NI; i++) src[i] -= (i & 3) * 256;
-    }
+    for (int i = 0; i < NI; i++) src[i] -= (i & 3) * 256;
     auto issue = [&](int kt) {
         const uint32_t A = ring_base + (uint32_t)(kt & 1) * (W_STAGE_F * 4);
         const uint32_t B = A + W_BM * W_BK * 4;
-        if (LOADERS == 8) {
-            const int k0 = kt * W_BK;
-            lds_dma16x4<false>(src[0] + k0, src[1] + k0, src[2] + k0, src[3] + k0, A + (uint32_t)(lw * RPW * W_BK * 4));
-            lds_dma16x4<false>(src[4] + k0, src[5] + k0, src[6] + k0, src[7] + k0, B + (uint32_t)(lw * RPW * W_BK * 4));
-            return;
-        }
-#pragma unroll
-        for (int i = 0; i < NI; i++) {
-            const uint32_t dst = (i < NI / 2 ? A : B) + (uint32_t)((lw * RPW + (i % (NI / 2)) * 8) * W_BK * 4);
-            w_dma16_masked(src[i] + kt * W_BK, dst, load_mask);
-        }
+        const int k0 = kt * W_BK;
+        lds_dma16x4<false>(src[0] + k0, src[1] + k0, src[2] + k0, src[3] + k0, A + (uint32_t)(wave * RPW * W_BK * 4));
+        lds_dma16x4<false>(src[4] + k0, src[5] + k0, src[6] + k0, src[7] + k0, B + (uint32_t)(wave * RPW * W_BK * 4));
     };
 
     f32x16 acc[2][4];
@@ -201,39 +161,13 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
     }
 
     // one K-step; MORE (compile time): there is a next stage to request
-#ifdef LB_DIAG
-    unsigned long long pr_wait = 0, pr_bar = 0, pr_issue = 0, pr_t0 = 0, pr_r0 = 0;
-    const bool probe = a.abl == 5;
-    if (probe) { pr_t0 = __builtin_amdgcn_s_memtime(); pr_r0 = __builtin_amdgcn_s_memrealtime(); }
-#endif
     auto step = [&](int kt, auto more_tag) {
         constexpr bool MORE = decltype(more_tag)::value;
-#ifdef LB_DIAG
-        unsigned long long s0 = 0, s1 = 0, s2 = 0;
-        if (probe) s0 = __builtin_amdgcn_s_memtime();
-#endif
         wait_vmcnt<0>();                 // this wave's part of stage kt has landed (issued one whole K-step ago)
-#ifdef LB_DIAG
-        if (probe) s1 = __builtin_amdgcn_s_memtime();
-#endif
         __builtin_amdgcn_s_barrier(); // everyone's part is in; everyone is done reading stage kt - 1 (and, at kt = 0, has
                                       // written its side inputs)
         asm volatile("" ::: "memory");
-#ifdef LB_DIAG
-        if (probe) { s2 = __builtin_amdgcn_s_memtime(); pr_wait += s1 - s0; pr_bar += s2 - s1; }
-#endif
-#ifdef LB_DIAG
-        const bool dma_on = a.abl != 1;
-#else
-        constexpr bool dma_on = true;
-#endif
-        if (MORE && dma_on) issue(kt + 1); // stage kt + 1 goes into the slot read at step kt - 1
-#ifdef LB_DIAG
-        if (probe) pr_issue += __builtin_amdgcn_s_memtime() - s2;
-#endif
-#ifdef LB_DIAG
-        if (a.abl == 2) return;
-#endif
+        if (MORE) issue(kt + 1); // stage kt + 1 goes into the slot read at step kt - 1
         const float *As = ring + (kt & 1) * W_STAGE_F;
         const float *Bs = As + W_BM * W_BK;
         // The stage's two MFMA k-blocks of 16.  Per k-block: both corpus fragments (split once, used by all four query
@@ -277,18 +211,6 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
     };
     for (int kt = 0; kt + 1 < nk; kt++) step(kt, std::true_type{});
     step(nk - 1, std::false_type{});
-#ifdef LB_DIAG
-    if (probe && lane == 0) {
-        const unsigned long long t1 = __builtin_amdgcn_s_memtime(), r1 = __builtin_amdgcn_s_memrealtime();
-        atomicAdd(&g_tall2_probe[0], t1 - pr_t0); // loop cycles
-        atomicAdd(&g_tall2_probe[1], r1 - pr_r0); // the same in 100 MHz ticks
-        atomicAdd(&g_tall2_probe[2], 1ull);       // waves
-        atomicAdd(&g_tall2_probe[3], pr_wait);    // in s_waitcnt vmcnt(0)
-        atomicAdd(&g_tall2_probe[4], pr_bar);     // in s_barrier
-        atomicAdd(&g_tall2_probe[5], pr_issue);   // issuing the next stage's requests
-    }
-    if (a.abl != 0 && a.abl != 5) return; // timing-only ablations admit nothing (their sums are not inner products)
-#endif
 
     // ---- epilogue: key + admission, one MFMA row tile (this lane's 16 rows of it) at a time ----------------
     // C layout (32x32): col = lane & 31 (query), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
@@ -372,15 +294,6 @@ __global__ __launch_bounds__(W_THREADS, 2) void gemm_filter_tall2_kernel(Tall2Ar
 
 } // namespace
 
-void read_tall2_probe(unsigned long long out[8], bool reset)
-{
-    (void)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_tall2_probe), 8 * sizeof(unsigned long long));
-    if (reset) {
-        const unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tall2_probe), z, sizeof z);
-    }
-}
-
 // Requires D % 32 == 0, 16-B aligned X / Q; Q is the split image of the batch; asplit: 1 = X is the split image of
 // the corpus, 2 = X is the plain f32 corpus.
 void launch_gemm_filter_tall2(int metric, const float *X, const float *norm2, const float *rnorm, int64_t row_begin,
@@ -392,41 +305,27 @@ void launch_gemm_filter_tall2(int metric, const float *X, const float *norm2, co
     a.rowmap = rowmap;
     a.X = X; a.norm2 = norm2; a.rnorm = rnorm; a.row_begin = row_begin; a.row_end = row_end; a.D = D;
     a.Q = Qs; a.nq = nq; a.mask = mask; a.cs = cs; a.boot = boot ? 1 : 0;
-    static const int abl = lb_tunable("LB_TALL2_ABL", 0);
-    a.abl = abl;
-    static const int opt = lb_tunable("LB_TALL2_LOADERS", W_DEFAULT_LOADERS);
     a.n_row_tiles = (int)((row_end - row_begin + W_BM - 1) / W_BM);
     a.n_q_tiles = (nq + W_BN - 1) / W_BN;
     const int groups = (a.n_row_tiles + 7) / 8;
     dim3 grid((unsigned)(groups * 8 * a.n_q_tiles));
     const size_t shmem = (size_t)W_NST * W_STAGE_F * 4 + W_BM * 4 + W_BM * 4 + W_BM;
-#define LB_TALL2(M, SP, O)                                                                                          \
+#define LB_TALL2(M, SP)                                                                                             \
     do {                                                                                                            \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_filter_tall2_kernel<M, SP, O>),              \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(gemm_filter_tall2_kernel<M, SP>),                 \
                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem); /* per device */         \
-        hipLaunchKernelGGL((gemm_filter_tall2_kernel<M, SP, O>), grid, dim3(W_THREADS), shmem, s, a);               \
+        hipLaunchKernelGGL((gemm_filter_tall2_kernel<M, SP>), grid, dim3(W_THREADS), shmem, s, a);                  \
     } while (0)
-#ifdef LB_DIAG
-#define LB_TALL2_O(M, SP)                    \
-    do {                                     \
-        if (opt == 4) LB_TALL2(M, SP, 4);    \
-        else LB_TALL2(M, SP, 8);             \
-    } while (0)
-#else
-#define LB_TALL2_O(M, SP) LB_TALL2(M, SP, W_DEFAULT_LOADERS)
-#endif
-#define LB_TALL2_M(M)                      \
-    do {                                   \
-        if (asplit == 1) LB_TALL2_O(M, 1); \
-        else LB_TALL2_O(M, 2);             \
+#define LB_TALL2_M(M)                    \
+    do {                                 \
+        if (asplit == 1) LB_TALL2(M, 1); \
+        else LB_TALL2(M, 2);             \
     } while (0)
     if (metric == METRIC_L2) LB_TALL2_M(METRIC_L2);
     else if (metric == METRIC_COS) LB_TALL2_M(METRIC_COS);
     else LB_TALL2_M(METRIC_DOT);
 #undef LB_TALL2_M
-#undef LB_TALL2_O
 #undef LB_TALL2
-    (void)opt;
 }
 
 } // namespace lb

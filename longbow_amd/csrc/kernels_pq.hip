@@ -99,8 +99,7 @@ struct AdcArgs {
     const int *skip_if_ok; // byte-table prefilter params {s_tau, ok}: ok != 0 -> nothing to do here
 };
 
-// ABL (profiling aid, wrong results): 1 = no LDS gathers, 2 = no global code loads
-template <bool VEC16, int ABL = 0>
+template <bool VEC16>
 __global__ __launch_bounds__(ADC_THREADS) void adc_scan_kernel(AdcArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float tab[];
@@ -116,17 +115,14 @@ __global__ __launch_bounds__(ADC_THREADS) void adc_scan_kernel(AdcArgs a)
         if (VEC16) {
             const uint4 *c4 = reinterpret_cast<const uint4 *>(c);
             for (int g = 0; g < M / 16; g++) {
-                uint4 v;
-                if (ABL == 2) v = make_uint4((uint32_t)row * 2654435761u, (uint32_t)row * 40503u + g, (uint32_t)(row >> 3) * 97u, (uint32_t)row ^ (g * 0x9e3779b9u));
-                else v = c4[g];
+                const uint4 v = c4[g];
                 const uint32_t w[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
                 for (int t = 0; t < 4; t++) {
 #pragma unroll
                     for (int b = 0; b < 4; b++) {
                         const int j = g * 16 + t * 4 + b;
-                        if (ABL == 1) sum = sum + (float)((w[t] >> (8 * b)) & 0xffu);
-                        else sum = sum + tab[j * 256 + ((w[t] >> (8 * b)) & 0xffu)];
+                        sum = sum + tab[j * 256 + ((w[t] >> (8 * b)) & 0xffu)];
                     }
                 }
             }
@@ -300,8 +296,6 @@ void launch_adc_sample(const float *table, int M, const uint8_t *codes, int64_t 
     hipLaunchKernelGGL(adc_sample_kernel, dim3(blocks), dim3(ADC_THREADS), shmem, s, table, M, codes, n, count, out, vec16);
 }
 
-int g_adc_ablation = 0; // profiling aid (diagnostic build only; always 0 in the product build)
-
 void launch_adc_scan(const float *table, int M, const uint8_t *codes, int64_t row_begin, int64_t row_end,
                      int slot, const uint8_t *mask, CandState cs, bool boot, float *all_out,
                      int64_t out_base, hipStream_t s, const int *skip_if_ok)
@@ -317,7 +311,7 @@ void launch_adc_scan(const float *table, int M, const uint8_t *codes, int64_t ro
     int64_t blocks = (nrows + ADC_THREADS - 1) / ADC_THREADS;
     if (blocks > 256) blocks = 256; // one 1024-thread workgroup per CU holds the table once
     const bool vec = (M % 16 == 0) && ((reinterpret_cast<uintptr_t>(codes) & 15) == 0);
-    if (vec && !g_adc_ablation && (a.row_end - a.row_begin) >= 4096) {
+    if (vec && (a.row_end - a.row_begin) >= 4096) {
         bool ok = false;
         switch (M / 16) {
         case 1: ok = try_launch_adc_dma<1>(a, s); break;
@@ -330,15 +324,6 @@ void launch_adc_scan(const float *table, int M, const uint8_t *codes, int64_t ro
         }
         if (ok) return;
     }
-#ifdef LB_DIAG
-    if (vec && g_adc_ablation) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(adc_scan_kernel<true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(adc_scan_kernel<true, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        if (g_adc_ablation == 1) hipLaunchKernelGGL((adc_scan_kernel<true, 1>), dim3((unsigned)blocks), dim3(ADC_THREADS), shmem, s, a);
-        else hipLaunchKernelGGL((adc_scan_kernel<true, 2>), dim3((unsigned)blocks), dim3(ADC_THREADS), shmem, s, a);
-        return;
-    }
-#endif
     if (vec) {
         if (shmem > 64 * 1024)
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(adc_scan_kernel<true>),

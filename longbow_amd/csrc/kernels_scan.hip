@@ -52,18 +52,17 @@ template <typename T> struct RowPiece { typedef f32x4 type; };
 template <> struct RowPiece<_Float16> { typedef f16x8 type; };
 
 // MAPPED: positions [row_begin,row_end) index a.rowmap (the visible rows under a filter) instead of the corpus.
-// NBUF: LDS stages.  2 = write the next stage while the current one is read (69.6 KB, 2 workgroups/CU);
-// 1 = one stage + an extra barrier (34.8 KB, 4 workgroups/CU: twice the bytes in flight per CU).
+// One LDS stage + an extra barrier (34.8 KB, 4 workgroups/CU).
 // The (tile, chunk) sequence of a workgroup is one flat pipeline: the first chunk of the next tile
 // is already in flight while the last chunk of the current tile is consumed.
 // T = _Float16 (an fp16 index): a row chunk of 64 elements is 8 loads of 16 B per thread instead of 16, widened to f32
 // (v_cvt_f32_f16, exact) as the stage is written; the LDS stage and everything after it are the f32 kernel's.
-template <typename T, int METRIC, int ORDER, int NQ, bool MAPPED, int NBUF>
+template <typename T, int METRIC, int ORDER, int NQ, bool MAPPED>
 __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgsT<T> a)
 {
-    // one __shared__ object: [stage][rows | query chunk]
+    // one __shared__ object: [rows | query chunk]
     constexpr int STAGE_F = SC_ROWS * SC_LD + NQ * SC_DK;
-    __shared__ __attribute__((aligned(16))) float lds[NBUF][STAGE_F];
+    __shared__ __attribute__((aligned(16))) float lds[STAGE_F];
     const int tid = threadIdx.x;
     const int D = a.D;
     const int nchunks = (D + SC_DK - 1) / SC_DK;
@@ -127,22 +126,22 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgsT<T> a)
             stg[i] = __builtin_nontemporal_load(reinterpret_cast<const Piece *>(a.X + row * (int64_t)D + k)); // streamed once
         }
     };
-    auto write_stage = [&](int st) {
+    auto write_stage = [&]() {
 #pragma unroll
         for (int i = 0; i < PPR; i++) {
             const int ch = tid + SC_ROWS * i;
             const int r = ch >> PSH, p = ch & (PPR - 1);
             if constexpr (EPP == 4) {
-                *reinterpret_cast<f32x4 *>(&lds[st][r * SC_LD + p * 4]) = stg[i];
+                *reinterpret_cast<f32x4 *>(&lds[r * SC_LD + p * 4]) = stg[i];
             } else {
                 const f32x4 lo = {(float)stg[i][0], (float)stg[i][1], (float)stg[i][2], (float)stg[i][3]};
                 const f32x4 hi = {(float)stg[i][4], (float)stg[i][5], (float)stg[i][6], (float)stg[i][7]};
-                *reinterpret_cast<f32x4 *>(&lds[st][r * SC_LD + p * 8]) = lo;
-                *reinterpret_cast<f32x4 *>(&lds[st][r * SC_LD + p * 8 + 4]) = hi;
+                *reinterpret_cast<f32x4 *>(&lds[r * SC_LD + p * 8]) = lo;
+                *reinterpret_cast<f32x4 *>(&lds[r * SC_LD + p * 8 + 4]) = hi;
             }
         }
         if (q_loader)
-            *reinterpret_cast<f32x4 *>(&lds[st][SC_ROWS * SC_LD + (tid >> 4) * SC_DK + (tid & 15) * 4]) = stq;
+            *reinterpret_cast<f32x4 *>(&lds[SC_ROWS * SC_LD + (tid >> 4) * SC_DK + (tid & 15) * 4]) = stq;
     };
 
     Acc<ORDER> acc[NQ]; // L2: sum (q-x)^2 ; cos/dot: sum q*x
@@ -194,9 +193,9 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgsT<T> a)
     };
 
     int64_t tile = blockIdx.x;
-    int c = 0, cur = 0;
+    int c = 0;
     load_stage(tile, 0);
-    write_stage(0);
+    write_stage();
     __syncthreads();
 
     while (true) {
@@ -215,8 +214,8 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgsT<T> a)
             nb.zero();
         }
         {
-            const float *xr = &lds[cur][tid * SC_LD];
-            const float *lq = &lds[cur][SC_ROWS * SC_LD];
+            const float *xr = &lds[tid * SC_LD];
+            const float *lq = &lds[SC_ROWS * SC_LD];
             const int d0 = c * SC_DK;
             const int nfull4 = (min(dmain, d0 + SC_DK) - d0) >> 2; // groups of 4 in the main loop
             // main loop: groups of 4 elements, positions 0..3 -> accumulators 0..3 (UNROLL4)
@@ -229,12 +228,8 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgsT<T> a)
                     acc[j].template add4_pair<METRIC>(*reinterpret_cast<const f32x4 *>(&lq[j * SC_DK + g * 4]), xv);
             }
         }
-        if (NBUF == 1) {
-            __syncthreads(); // every wave is done reading the single stage
-            if (has_next) write_stage(0);
-        } else if (has_next) {
-            write_stage(cur ^ 1);
-        }
+        __syncthreads(); // every wave is done reading the stage
+        if (has_next) write_stage();
 
         if (c == nchunks - 1) { // the tile's distances are complete: park them, admission runs under the next loads
             const float nbt = nb.total();
@@ -249,7 +244,6 @@ __global__ __launch_bounds__(SC_ROWS) void scan_kernel(ScanArgsT<T> a)
         if (!has_next) break;
         tile = ntile;
         c = nc;
-        if (NBUF == 2) cur ^= 1;
     }
     if (pend_tile >= 0) flush();
 }
@@ -864,24 +858,17 @@ void launch_sample_tau(CandState cs, const int *qsel, int nsel, uint32_t count, 
                        m, (zero_stripes && cs.stripes != nullptr) ? 1 : 0, Q, D, qna, order);
 }
 
-int g_scan_nbuf = lb_tunable("LB_SCAN_NBUF", 1);
-
-template <typename T, int METRIC, int ORDER, int NQ, bool MAPPED, int NBUF>
+template <typename T, int METRIC, int ORDER, int NQ, bool MAPPED>
 static void launch_scan_kernel(dim3 grid, hipStream_t s, const ScanArgsT<T> &a)
 {
-    hipLaunchKernelGGL((scan_kernel<T, METRIC, ORDER, NQ, MAPPED, NBUF>), grid, dim3(SC_ROWS), 0, s, a);
+    hipLaunchKernelGGL((scan_kernel<T, METRIC, ORDER, NQ, MAPPED>), grid, dim3(SC_ROWS), 0, s, a);
 }
 
 template <typename T, int METRIC, int ORDER, int NQ>
 static void launch_scan_variant(dim3 grid, hipStream_t s, const ScanArgsT<T> &a)
 {
-    if (g_scan_nbuf == 1) {
-        if (a.rowmap) launch_scan_kernel<T, METRIC, ORDER, NQ, true, 1>(grid, s, a);
-        else launch_scan_kernel<T, METRIC, ORDER, NQ, false, 1>(grid, s, a);
-    } else {
-        if (a.rowmap) launch_scan_kernel<T, METRIC, ORDER, NQ, true, 2>(grid, s, a);
-        else launch_scan_kernel<T, METRIC, ORDER, NQ, false, 2>(grid, s, a);
-    }
+    if (a.rowmap) launch_scan_kernel<T, METRIC, ORDER, NQ, true>(grid, s, a);
+    else launch_scan_kernel<T, METRIC, ORDER, NQ, false>(grid, s, a);
 }
 
 template <typename T, int METRIC, int ORDER>
@@ -933,9 +920,9 @@ static void launch_scan_rows(int metric, int order, bool raw_dot, const T *X, in
         return;
     }
     const int64_t ntiles = (row_end - row_begin + SC_ROWS - 1) / SC_ROWS;
-    // 69.6 KB (2 stages) / 34.8 KB (1 stage) LDS per workgroup -> 2 / 4 workgroups per CU; 256 CUs.
+    // 34.8 KB LDS per workgroup -> 4 workgroups per CU; 256 CUs.
     static const int waves_mult = lb_tunable("LB_SCAN_GRIDMULT", 4);
-    const int64_t maxgrid = 256 * (g_scan_nbuf == 1 ? 4 : 2) * waves_mult;
+    const int64_t maxgrid = 256 * 4 * waves_mult;
     dim3 grid((unsigned)(ntiles < maxgrid ? ntiles : maxgrid));
     int nq_t = nsel <= 1 ? 1 : nsel <= 2 ? 2 : nsel <= 4 ? 4 : 8;
 #define LB_SCAN(M)                                                                          \

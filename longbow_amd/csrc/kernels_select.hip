@@ -66,7 +66,7 @@ __device__ __forceinline__ void wave_or_and_u64(uint64_t &o, uint64_t &a)
 template <int NT> // threads per workgroup: 256 (throughput, many queries) or 1024 (latency, few queries)
 __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qsel, int kc,
                                                              uint32_t boot_rows, uint32_t tau_only,
-                                                             uint32_t need_at_least, uint32_t sort_max,
+                                                             uint32_t need_at_least,
                                                              EmitArgs em, uint32_t striped, uint32_t unsorted)
 {
     // tau_only: the list holds a *sample* of the rows; publish its kc-th entry (row bits saturated) as
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
     const uint32_t keep = n < (uint32_t)kc ? n : (uint32_t)kc;
     if (n < need_at_least && tid == 0) atomicOr(&cs.flags[q], 4u);
 
-    if (P <= 2u * next_pow2((uint32_t)kc) || n <= (uint32_t)kc || P <= sort_max) {
+    if (P <= 2u * next_pow2((uint32_t)kc) || n <= (uint32_t)kc) {
         bitonic_sort_u64(sh, P, tid, NT); // kEntryMax padding sorts last
         if (tau_only) {
             if (tid == 0) {
@@ -323,19 +323,16 @@ void launch_select(CandState cs, const int *qsel, int nsel, int kc, uint32_t boo
     if (emit) em = *emit;
     if (nsel <= 0) return;
     const size_t shmem = (size_t)next_pow2_host(cs.cap) * sizeof(uint64_t) + (256 + 4 + 8) * sizeof(uint32_t);
-    // lists up to this size are simply sorted (one 1024-thread workgroup); larger ones take the radix select
-    static const uint32_t sort_max_big = (uint32_t)lb_tunable("LB_SELECT_SORT_MAX", 0);
     static const int big_max = lb_tunable("LB_SELECT_BIG_MAXQ", 512); // (1024-thread selects: 10 us less than 256-thread ones at 128-384 queries)
-    const uint32_t sort_max = nsel <= big_max ? sort_max_big : 0u;
     if (nsel <= big_max) { // few queries: one big workgroup each, latency matters
         allow_big_lds(select_kernel<1024>, shmem);
         hipLaunchKernelGGL(select_kernel<1024>, dim3(nsel), dim3(1024), shmem, s, cs, qsel, kc, boot_rows,
-                           tau_only ? 1u : 0u, need_at_least, sort_max, em,
+                           tau_only ? 1u : 0u, need_at_least, em,
                            (striped && cs.stripes) ? 1u : 0u, (unsorted && emit == nullptr) ? 1u : 0u);
     } else {
         allow_big_lds(select_kernel<256>, shmem);
         hipLaunchKernelGGL(select_kernel<256>, dim3(nsel), dim3(256), shmem, s, cs, qsel, kc, boot_rows,
-                           tau_only ? 1u : 0u, need_at_least, sort_max, em,
+                           tau_only ? 1u : 0u, need_at_least, em,
                            (striped && cs.stripes) ? 1u : 0u, (unsorted && emit == nullptr) ? 1u : 0u);
     }
 }

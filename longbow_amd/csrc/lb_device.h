@@ -6,9 +6,9 @@
 
 namespace lb {
 
-// A/B tunables.  In the product build every tunable IS its compiled-in default (the measured winner);
-// only a -DLB_DIAG build (python -m longbow_amd.build --diag -> liblongbow_gpu_diag.so, used by tools/)
-// reads the LB_* environment variables and carries the timing-only ablation kernels.
+// Numeric tunables (thresholds and sizes).  In the product build every tunable IS its compiled-in default (the measured
+// winner); only a -DLB_DIAG build (python -m longbow_amd.build --diag -> liblongbow_gpu_diag.so, used by tests/ and tools/)
+// reads the LB_* environment variables.
 inline int lb_tunable(const char *name, int dflt)
 {
 #ifdef LB_DIAG
@@ -306,8 +306,7 @@ void launch_gemm_filter(int metric, const float *X, const float *norm2, const fl
 void launch_gemm_filter_narrow(int metric, const float *X, const float *norm2, const float *rnorm,
                                int64_t row_begin, int64_t row_end, int D, const float *Q, int nq,
                                const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot,
-                               hipStream_t s, bool tile64 = false, // tile64: 128 rows x 64 queries per workgroup
-                               bool split = false);                // split: 3 x bf16 MFMA on operands split in registers
+                               hipStream_t s, bool tile64 = false); // tile64: 128 rows x 64 queries per workgroup
 // Sampled threshold fused into the candidate pass (kernels_gemm_narrow.hip, FUSED): the first `n_blocks` workgroups of
 // the launch score `count` sampled rows (corpus rows smap[0..count)), then workgroup j < nq turns query j's sample keys
 // into tau[j] (the m-th smallest), zeroes cnt[j] / flags[j], writes the exact ||q_j||^2 (cosine) and publishes
@@ -325,7 +324,6 @@ struct FusedSample {
     float *qna = nullptr; // or null (not cosine)
     int order = 0;
     uint32_t *fail_host = nullptr; // pinned: set to `epoch` when a wait gave up (the host then redoes the batch exactly)
-    int relaxed = 0;               // diagnostic build only: hand-off without release / acquire (A/B of their cost)
 };
 void launch_gemm_filter_narrow_fused(int metric, const float *X, const float *norm2, const float *rnorm, int64_t row_begin,
                                      int64_t row_end, int D, const float *Q, int nq, const uint8_t *mask,
@@ -356,6 +354,9 @@ struct Tall16Tin {
     const float *Q;
     float *qna;
     int order;
+#ifdef LB_DIAG
+    int withhold; // the duty workgroups keep their thresholds: every wave's bounded wait gives up (lb_debug_tin_withhold_next)
+#endif
 };
 bool tall16_tin_ok(int D, int nq, int64_t n_pos, bool img, bool mapped, bool masked, bool with_norm, uint32_t count, int m);
 // the same image and scales, plus the exact ||q||^2 in `order` (qna, or null) and the reset of the queries' candidate state:

@@ -50,7 +50,6 @@ struct lb_gpu_pq {
     // instrumentation (bench.py): HIP events around the main code pass and the whole search of the last query
     std::atomic<int> profiling{0};
     std::atomic<int> prefilter{1}; // 0 = exact f32-table pass only (lb_gpu_pq_set_prefilter; both are exact)
-    std::atomic<int> pair_pass{1}; // 0 = one query per pass over the codes even in batches (A/B, diagnostic build)
     SearchCombiner combiner;       // concurrent host-pointer searches of a few queries each are combined (lb_host.h)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float prof_ms[2] = {0.f, 0.f};
@@ -527,11 +526,10 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         // the query is redone by the bootstrap schedule.  Two-level m-th minimum: the sample (195k entries at
         // 100M rows) is larger than one list.  Stride 512 with a 16384-entry list (mean + 5 sigma = 11.3k
         // admitted rows) instead of stride 256 / 8192 halves the sampling pass (49 -> 25 us at 100M rows).
-        static const int sample_on = lb_tunable("LB_SAMPLE_TAU", 1);
         uint32_t samp_count = 0;
         int samp_m = 0;
         uint32_t cap = std::max<uint32_t>(8192u, 4u * next_pow2_host((uint32_t)k));
-        if (sample_on && p->n >= 65536 && p->n < ((int64_t)1 << 32)) {
+        if (p->n >= 65536 && p->n < ((int64_t)1 << 32)) {
             const uint32_t cap_s = std::max<uint32_t>(16384u, cap);
             const int64_t stride = p->n >= ((int64_t)8192 * 512) ? 512 : 256;
             const int64_t cnt = std::max<int64_t>(8192, (p->n + stride - 1) / stride);
@@ -684,11 +682,11 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                     return st;
                 }
             }
-            if (q + 3 < nqi && p->pair_pass.load() != 0 && scan_quad(q)) {
+            if (q + 3 < nqi && scan_quad(q)) {
                 q += 3;
                 continue;
             }
-            if (q + 1 < nqi && p->pair_pass.load() != 0 && scan_pair(q)) {
+            if (q + 1 < nqi && scan_pair(q)) {
                 q++;
                 continue;
             }

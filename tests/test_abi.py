@@ -27,7 +27,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     bound = {s[0] for s in _lib.SIGNATURES}
     assert bound == set(declared), (bound ^ set(declared))
     _lib.load()
-    # the product library carries no test hook / ablation switch: those live in the -DLB_DIAG build only
+    # the product library carries no test hook: those live in the -DLB_DIAG build only
     out = __import__("subprocess").run(["nm", "-D", "--defined-only", _lib.SO_PATH], capture_output=True, text=True).stdout
     assert "lb_debug" not in out, [l for l in out.splitlines() if "lb_debug" in l]
     build.build(diag=True)

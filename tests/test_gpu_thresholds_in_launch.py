@@ -107,8 +107,8 @@ def test_batches_that_end_65_to_128_queries_into_a_256_query_tile(oracle, metric
     idx.Close()
 
 
-def test_a_wait_for_the_thresholds_that_gives_up_is_reported_and_the_batch_redone(oracle, monkeypatch):
-    """diagnostic build, LB_F16_ABL=12: the duty workgroups never publish their thresholds, every wave's bounded wait (~1 ms)
+def test_a_wait_for_withheld_thresholds_that_gives_up_is_reported_and_the_batch_redone(oracle):
+    """diagnostic build, lb_debug_tin_withhold_next: the duty workgroups never publish their thresholds, every wave's bounded wait (~1 ms)
     gives up, admits nothing and says so through the pinned word; the host redoes the batch on the exact path -- the lists
     are still the oracle's, and the give-up is counted."""
     from tests.gpu_util import diag_lib
@@ -123,9 +123,8 @@ def test_a_wait_for_the_thresholds_that_gives_up_is_reported_and_the_batch_redon
     lab, dist = idx.SearchBatch(Q[:6], k)
     assert_same(lab, dist, oi[:6], od[:6], "before")
     assert idx.fused_giveups == 0 and idx.last_fallbacks == 0
-    monkeypatch.setenv("LB_F16_ABL", "12")
+    lib.lb_debug_tin_withhold_next(1)
     lab, dist = idx.SearchBatch(Q[:6], k)
-    monkeypatch.delenv("LB_F16_ABL")
     assert_same(lab, dist, oi[:6], od[:6], "wait gave up")
     assert idx.fused_giveups == 1 and idx.last_fallbacks == 6, (idx.fused_giveups, idx.last_fallbacks)
     lab, dist = idx.SearchBatch(Q, k)
