@@ -63,15 +63,13 @@ struct Workspace {
     // fused sample (kernels_gemm_narrow.hip, FUSED): [0] = ticket counter that only grows, [1 ..] = ready epochs per slot
     uint32_t *d_fsync = nullptr;
     uint32_t fs_base = 0, fs_epoch = 0; // host mirror of the ticket counter; last epoch used
+    uint32_t next_epoch() { return ++fs_epoch != 0 ? fs_epoch : (fs_epoch = 1); } // (0 = "never published")
     uint32_t *h_fail = nullptr;         // pinned: epoch of a launch whose waits gave up
     uint32_t *h_flags = nullptr; // pinned
     int *h_qsel = nullptr;       // pinned
     // an fp16 index's query batch widened to f32 (every query kernel downstream reads f32 queries)
     float *d_q = nullptr;
     size_t d_q_bytes = 0;
-    float *d_dist = nullptr;
-    int64_t *d_lab = nullptr;
-    size_t d_out_n = 0;
     std::vector<Event> events;
     size_t ev_used = 0;
     const lb_cancel *ctx = nullptr; // the running call's cancellation context (or null)
@@ -98,8 +96,6 @@ struct Workspace {
         if (h_flags) (void)hipHostFree(h_flags);
         if (h_qsel) (void)hipHostFree(h_qsel);
         if (d_q) (void)hipFree(d_q);
-        if (d_dist) (void)hipFree(d_dist);
-        if (d_lab) (void)hipFree(d_lab);
         for (auto &e : events) {
             if (e.a) (void)hipEventDestroy(e.a);
             if (e.b) (void)hipEventDestroy(e.b);
@@ -336,6 +332,17 @@ int fail_hip(lb_gpu_index *h, const HipErr &e)
     return (e.e == hipErrorOutOfMemory) ? LB_ERR_OOM : LB_ERR_HIP;
 }
 
+// a workspace's device buffer of at least `need` bytes (re-allocated when short; the contents are not kept)
+template <class T> void grow_device(T *&p, size_t &bytes, size_t need)
+{
+    if (bytes >= need) return;
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    bytes = 0;
+    LB_HIP(hipMalloc(&p, need));
+    bytes = need;
+}
+
 // candidate-list geometry for a request of k
 void cand_geometry(int k, int &kc, uint32_t &cap)
 {
@@ -530,6 +537,14 @@ static SamplePlan sample_plan(int64_t n, int keep, uint32_t cap, uint32_t count_
     return best;
 }
 
+// f(X) with the index's rows typed as they are stored: f32, or fp16 on an fp16 index (the launchers overload on the row type;
+// an int8 index's launchers take other arguments and are called apart)
+template <class F> void with_rows(const lb_gpu_index *h, F &&f)
+{
+    if (h->f16_rows) f(h->rows_f16());
+    else f(static_cast<const float *>(h->d_X));
+}
+
 // Exact scan of all rows for the query slots sel[0..nsel) (indices into d_q rows).
 // mode 0: sampled first pass, 1: classic (bootstrap / growing chunks), 2: chunks that cannot overflow.
 bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_q, const int *d_sel,
@@ -559,12 +574,11 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                 ProfScope p(w, s, prof, 1);
                 if (h->i8_rows)
                     launch_sample_scores_i8(metric, h->rows_i8(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel, gn, w->cs, s);
-                else if (h->f16_rows)
-                    launch_sample_scores(metric, order, h->rows_f16(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel,
-                                         gn, w->cs, w->d_qna, s);
                 else
-                    launch_sample_scores(metric, order, h->d_X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel,
-                                         gn, w->cs, w->d_qna, s);
+                    with_rows(h, [&](auto X) {
+                        launch_sample_scores(metric, order, X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel, gn, w->cs,
+                                             w->d_qna, s);
+                    });
                 launch_sample_tau(w->cs, use_sel, gn, sp.count, sp.m, /*zero_stripes=*/true, s);
             }
             {   // one pass over the span
@@ -572,12 +586,11 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                 if (h->i8_rows)
                     launch_scan_i8(metric, h->rows_i8(), 0, sp.span, h->dim, d_q, use_sel, gn, h->norm2_i8(), mask, rv.rowmap, w->cs,
                                    /*boot=*/false, s, /*striped=*/true);
-                else if (h->f16_rows)
-                    launch_scan(metric, order, false, h->rows_f16(), 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna, mask,
-                                rv.rowmap, w->cs, /*boot=*/false, nullptr, 0, s, /*striped=*/true);
                 else
-                    launch_scan(metric, order, false, h->d_X, 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna, mask,
-                                rv.rowmap, w->cs, /*boot=*/false, nullptr, 0, s, /*striped=*/true);
+                    with_rows(h, [&](auto X) {
+                        launch_scan(metric, order, false, X, 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna, mask, rv.rowmap, w->cs,
+                                    /*boot=*/false, nullptr, 0, s, /*striped=*/true);
+                    });
             }
             {
                 ProfScope p(w, s, prof, 1);
@@ -600,12 +613,11 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                 if (h->i8_rows)
                     launch_scan_i8(metric, h->rows_i8(), pos, end, h->dim, d_q, use_sel, gn, h->norm2_i8(), mask, rv.rowmap, w->cs,
                                    boot, s, /*striped=*/false);
-                else if (h->f16_rows)
-                    launch_scan(metric, order, false, h->rows_f16(), pos, end, h->dim, d_q, use_sel, gn, w->d_qna,
-                                mask, rv.rowmap, w->cs, boot, nullptr, 0, s);
                 else
-                    launch_scan(metric, order, false, h->d_X, pos, end, h->dim, d_q, use_sel, gn, w->d_qna,
-                                mask, rv.rowmap, w->cs, boot, nullptr, 0, s);
+                    with_rows(h, [&](auto X) {
+                        launch_scan(metric, order, false, X, pos, end, h->dim, d_q, use_sel, gn, w->d_qna, mask, rv.rowmap, w->cs,
+                                    boot, nullptr, 0, s);
+                    });
             }
             {
                 ProfScope p(w, s, prof, 1);
@@ -647,23 +659,24 @@ void upload_sel(Workspace *w, hipStream_t s, const std::vector<int> &sel)
     LB_HIP(hipMemcpyAsync(w->d_qsel, w->h_qsel, sel.size() * sizeof(int), hipMemcpyHostToDevice, s));
 }
 
-void scan_with_retry(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_q, int nq_total,
-                     const std::vector<int> &sel, int k, float *d_dist, int64_t *d_lab, bool prof)
+// exact scan of the query slots in `sel` of a batch of nq, or (sel null) of every query of the batch
+void scan_with_retry(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_q, int nq,
+                     const std::vector<int> *sel, int k, float *d_dist, int64_t *d_lab, bool prof)
 {
-    if (sel.empty()) return;
-    bool identity = true; // "all queries": the prefilled list saves an upload on the latency path
-    for (size_t i = 0; i < sel.size() && identity; i++) identity = sel[i] == (int)i;
-    if (!identity) upload_sel(w, s, sel);
-    const bool sampled = run_scan_path(h, w, s, d_q, identity ? w->d_iota : w->d_qsel, (int)sel.size(), k, 0,
-                                       d_dist, d_lab, prof);
+    const int nsel = sel ? (int)sel->size() : nq;
+    if (nsel == 0) return;
+    bool identity = true; // slots 0, 1, ...: the prefilled list saves an upload on the latency path
+    for (int i = 0; sel && i < nsel && identity; i++) identity = (*sel)[(size_t)i] == i;
+    if (!identity) upload_sel(w, s, *sel);
+    const bool sampled = run_scan_path(h, w, s, d_q, identity ? w->d_iota : w->d_qsel, nsel, k, 0, d_dist, d_lab, prof);
     std::vector<int> redo, over;
-    if (collect_flagged(w, s, nq_total, 1u | 4u, sel.data(), (int)sel.size(), redo, true) > 0) {
+    if (collect_flagged(w, s, nq, 1u | 4u, sel ? sel->data() : nullptr, nsel, redo, true) > 0) {
         // the sampled threshold missed (or a list overflowed): classic schedule, then overflow-proof chunks
         if (sampled) {
             upload_sel(w, s, redo);
             run_scan_path(h, w, s, d_q, w->d_qsel, (int)redo.size(), k, 1, d_dist, d_lab, prof);
         }
-        if (!sampled || collect_flagged(w, s, nq_total, 1u, redo.data(), (int)redo.size(), over, true) > 0) {
+        if (!sampled || collect_flagged(w, s, nq, 1u, redo.data(), (int)redo.size(), over, true) > 0) {
             if (!sampled) over = redo;
             upload_sel(w, s, over);
             run_scan_path(h, w, s, d_q, w->d_qsel, (int)over.size(), k, 2, d_dist, d_lab, prof);
@@ -727,6 +740,25 @@ inline double route_ms(const RouteCost &c, int64_t n, int D, int tiles)
     const double stream = nd * (double)D * c.hbm;
     return (compute > stream ? compute : stream) + nd * (double)D * c.first + c.fixed;
 }
+// the one-tile fp16 route over the image for nq <= 128 queries: its stream + what it pays per query beside it -- twice (beyond 1024
+// dimensions four times) the candidates to select and re-rank
+// (round 4: 0.0016 -> 0.0008 beyond 1024 dimensions -- the finish launch re-ranks ~270 rows per query where select + re-rank scored
+// 1024; with 0.0016 a row list of 125k x 1536 went to the 64-query split tile at exactly 64 and 128 queries: 0.30 / 0.40 ms where
+// the image serves them in 0.24 / 0.31)
+inline double narrow16_ms(int64_t n, int D, int nq) { return route_ms(kCostNarrow16, n, D, 1) + (D > 1024 ? 0.0008 : 0.0003) * nq; }
+
+// Candidates the fp16 single-product route keeps per query for a list of kc (mult > 0: that many times kc instead).  Its keys are
+// good to ~1.1e-3 of |q||x|, and the containment proof needs the gap between the k-th and the LAST kept candidate to exceed about
+// 2.5x that -- on the benchmark data the gap to the 256th is 0.0019-0.0028 (most queries would fail), to the 512th 0.0039-0.0045.
+// (Uniform random data is the hard case: its distances concentrate like 1/sqrt(D), so the gap shrinks with the dimension while
+// the bound does not -- beyond 1024 dimensions four times as many candidates are kept.)
+// (since the finish launch prunes in key space, kc only sizes the admission threshold: the list must hold the rows within the
+// error bound of the k-th key -- 2-4 k of them with fp16 keys -- not a fixed number of rows to re-rank; capped so that a sampled
+// threshold of that depth still exists)
+inline int f16_kc(int kc, int D, uint32_t cap, int mult = 0)
+{
+    return std::min(std::min(kc * (mult > 0 ? mult : (D > 1024 ? 4 : 2)), std::max(1024, 2 * kc)), (int)(cap / 4));
+}
 
 // f32_rows false (an fp16 index): only the routes over the fp16 image are offered -- every other one stages f32 rows; with none
 // on offer the result has kind 0 (the exact scan)
@@ -767,15 +799,8 @@ static Route choose_route(int nq, int64_t n, int D, int cmode, bool narrow_ok, b
     if ((narrow_ok || have_f16_image) && f16_ok && !image && (nq > 32 || have_f16_image) &&
         (cmode == LB_CAND_F16 || (cmode == LB_CAND_AUTO && (n >= 262144 || (have_f16_image && n >= f16_view_min)))))
     { // (below: launch overheads decide, and the narrow tiles win; a filtered view of a large corpus counts by its elements)
-        if (have_f16_image && nq <= 128) { // (one query tile: the 64- / 128-query form of the persistent kernel)
-            // + what the route pays per query beside the stream: twice (beyond 1024 dimensions four times) the candidates to
-            // select and re-rank
-            // (round 4: 0.0016 -> 0.0008 beyond 1024 dimensions -- the finish launch re-ranks ~270 rows per query where select +
-            // re-rank scored 1024; with 0.0016 a row list of 125k x 1536 went to the 64-query split tile at exactly 64 and 128
-            // queries: 0.30 / 0.40 ms where the image serves them in 0.24 / 0.31)
-            const double q1 = D > 1024 ? 0.0008 : 0.0003;
-            add(ROUTE_NARROW16, 3, route_ms(kCostNarrow16, n, D, 1) + q1 * nq);
-        }
+        if (have_f16_image && nq <= 128) add(ROUTE_NARROW16, 3, narrow16_ms(n, D, nq)); // (one query tile: the 64- / 128-query
+                                                                                       // form of the persistent kernel)
         else add(ROUTE_TALL16, 3, route_ms(have_f16_image ? kCostTall16Img : kCostTall16, n, D, tiles256));
     }
     if (!f32_rows && nc == 0) return Route{0, 0, 0.0};
@@ -826,8 +851,6 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
     static const int mfma_minq = lb_tunable("LB_I8_MFMA_MINQ", 16);
     const RowView rv = row_view(h);
     const int kkeep = std::max(k, 1);
-    std::vector<int> all(nq);
-    for (int i = 0; i < nq; i++) all[i] = i;
     SamplePlan sp;
     if (nq >= mfma_minq && mfma_i8_supported(h->metric, h->dim, h->d_X, d_q8)) sp = sample_plan(rv.n, kkeep, w->cap);
     if (!sp.on || sp.span < rv.n) {
@@ -835,7 +858,7 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
 #ifdef LB_DIAG
         g_last_route.store(kRouteI8Scan);
 #endif
-        scan_with_retry(h, w, s, d_q, nq, all, k, d_dist, d_lab, prof);
+        scan_with_retry(h, w, s, d_q, nq, nullptr, k, d_dist, d_lab, prof);
         return LB_OK;
     }
     h->last_route.store(kRouteI8Mfma, std::memory_order_relaxed);
@@ -862,243 +885,190 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
         launch_select(w->cs, nullptr, nq, kkeep, 0u, s, false, (uint32_t)kkeep, &em);
     }
     std::vector<int> redo;
-    if (collect_flagged(w, s, nq, 1u | 4u, all.data(), nq, redo, true) > 0)
-        scan_with_retry(h, w, s, d_q, nq, redo, k, d_dist, d_lab, prof);
+    if (collect_flagged(w, s, nq, 1u | 4u, nullptr, 0, redo, true) > 0)
+        scan_with_retry(h, w, s, d_q, nq, &redo, k, d_dist, d_lab, prof);
     return LB_OK;
 }
 
-int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, int k,
-                        float *d_dist, int64_t *d_lab, int kc_in, bool prof, int64_t &fallbacks, bool allow_f16 = true, int attempt = 0)
+// Rounding-error bound of a route's candidate inner products, per unit of ||q|| ||x|| (the finish launch's containment proof):
+// a k-ordered f32 fma chain of length D, or (split contraction) 3D/16 MFMA accumulations + <=16-term block sums plus the dropped
+// lo*lo / residual terms
+// ... or (split 3) one fp16 product: 2^-11 per operand, the subnormal term under the route's norm conditions, and the
+// f32 accumulation of D products (kernels_gemm_tall16.hip)
+// ... with the index's fp16 image the operands' share is MEASURED instead: |q.x - q~.x~| <= |q||x - x~| + |q - q~||x~|, the
+// residual norms taken when the image was written (rho_x = max over rows of |x - x~| / |x|, sync_f16_image) and when the
+// query image is (rho_q per query, query_prep_body) -- a third to a half of the worst case for data that fills the
+// mantissa, subnormal effects included:  gamma(q) = 1.05 (rho_x + A (1 + rho_x) + 2^-21) + 1.05 (1 + rho_x)(1 + A) rho_q,
+// A = (D + 8) 2^-24 the f32 accumulation of D exact products
+struct KeyBound {
+    bool measured; // gamma(q) = gamma + qrho_k * rho_q
+    float gamma, qrho_k;
+    // dot product on the persistent fp16 kernels: LOWER-BOUND keys -(q.x)~ / G - |x|, G = (gamma_a + gamma_o) |q| = gsum |q| (a few
+    // very long rows then sort to the front of the lists and are scored exactly instead of widening every row's error bound)
+    float gsum, rho_gain; // (measured, dot: G(q) = (gsum + qrho_k rho_q) |q|, folded into qnrm)
+};
+KeyBound key_bound(const lb_gpu_index *h, int split, bool have_xh)
 {
-    const int metric = h->metric, order = h->order.load();
-    const RowView rv = row_view(h);
-    const int64_t n = rv.n; // positions to walk: corpus rows, or the visible-row list under a selective filter
-    const uint8_t *mask = rv.mask;
-    ctx_check(w->ctx);
-    ProfScope whole(w, s, prof, 4);
-
-    // Path selection: <= 4 queries exact scan (0.50-0.55 ms at 1M x 768); from 5 queries a candidate route picked by
-    // choose_route's cost model (narrow / tall / tall2 / fp16 / f32 tile), exact re-rank behind every one of them.
-    const bool narrow_ok = !h->f16_rows && h->dim % 32 == 0 && ((reinterpret_cast<uintptr_t>(d_q) & 15) == 0);
-    static const int narrow_min = lb_tunable("LB_NARROW_MINQ", 5);
-    static const int narrow_max = lb_tunable("LB_NARROW_MAXQ", 384);
-    // rows with inf / NaN components: the MFMA pipeline's keys and error bounds assume finite data;
-    // the scan path orders non-finite distances canonically (NaN last)
-    const int cmode = h->cand_mode.load();
-    // (the fp16 image serves unfiltered searches and searches over a row list -- the persistent kernels gather out of it,
-    // dimensions from 256; under a per-row mask test the kernel stages f32 rows)
-    const bool have_xh = h->d_Xh != nullptr && h->xh_rows == h->n && !mask && (!rv.rowmap || h->dim >= 256) &&
-                         // (a centred image -- L2 -- is only ever read by the persistent kernels: nothing else knows the centre)
-                         (!h->xh_centred || tall16_runs_persistent(h->dim, nq, true, rv.rowmap != nullptr, false)) &&
-                         // (fp16 rows: only the persistent kernels read nothing but the image -- the one-tile form stages f32 rows)
-                         (!h->f16_rows || tall16_runs_persistent(h->dim, nq, true, rv.rowmap != nullptr, false));
-    const bool centred = have_xh && h->xh_centred; // L2 keys about the image's centre (sync_f16_image)
-    // within the fp16 contraction's range: the centred norms when the image is centred, the rows' own norms otherwise
-    bool f16_range_ok = centred ? h->xh_c_ok : h->f16_ok;
-    // Mid-size corpora and views (below 262,144 rows: offered the fp16 routes since round 4): only while ONE sampled span covers
-    // the view with the candidate list the fp16 keys need (twice / four times the split tiles') -- with k = 300 that list is a
-    // quarter of the lists' capacity, the sampled span ends short of 200k rows and the rest runs the classic schedule:
-    // 0.45 ms where the split tiles over the f32 rows take 0.15.  (Larger corpora: as before.)
-    if (cmode == LB_CAND_AUTO && n < 262144 && kc_in > 0) {
-        const int kc16 = std::min(std::min(kc_in * (h->dim > 1024 ? 4 : 2), std::max(1024, 2 * kc_in)), (int)(w->cap / 4));
-        const SamplePlan sp16 = sample_plan(n, kc16, w->cap);
-        if (!(sp16.on && sp16.span >= n)) f16_range_ok = false;
-    }
-    // 1 .. 4 queries: the exact scan streams the f32 corpus (0.52 ms per 1M x 768); with the fp16 copy the candidate pass
-    // streams half the bytes and the exact re-rank of 512 candidates costs 0.03 ms -- taken when the model says it is cheaper
-    bool small_on_copy = false;
-    if (!h->nonfinite && nq < narrow_min && have_xh && f16_range_ok && allow_f16 &&
-        (cmode == LB_CAND_F16 || (cmode == LB_CAND_AUTO && h->f16_skip.load(std::memory_order_relaxed) == 0))) {
-        const double scan_ms = 0.04 + 1e-6 * (double)n * ((double)h->dim * 0.00066 * (h->f16_rows ? 0.5 : 1.0) + 0.04); // (0.04: sample,
-                                                                                                                       // thresholds, select + emit)
-        const double copy_ms = route_ms(kCostNarrow16, n, h->dim, 1) + (h->dim > 1024 ? 0.0008 : 0.0003) * nq;
-        small_on_copy = cmode == LB_CAND_F16 || copy_ms < scan_ms;
-    }
-    // (dimensions that are not multiples of 32: the MFMA tiles over f32 rows do not apply; the fp16 copy does)
-    const bool copy_route_ok = have_xh && f16_range_ok && allow_f16 &&
-                               (cmode == LB_CAND_F16 || (cmode == LB_CAND_AUTO && h->f16_skip.load(std::memory_order_relaxed) == 0));
-    // (an fp16 index without the image route on offer -- no image, rows out of fp16's key range, a masked search, the
-    // batch beyond the persistent kernels: the exact scan over the fp16 rows, the floor)
-    if (h->nonfinite || (h->f16_rows && !copy_route_ok) ||
-        (nq < ((narrow_ok || copy_route_ok) ? narrow_min : kGemmMinQ) && !small_on_copy)) {
-        h->last_route.store(0, std::memory_order_relaxed);
-        std::vector<int> all(nq);
-        for (int i = 0; i < nq; i++) all[i] = i;
-        scan_with_retry(h, w, s, d_q, nq, all, k, d_dist, d_lab, prof);
-        return LB_OK;
-    }
-
-    // ---- batched path: MFMA candidate generation + exact re-rank --------------------
-    const bool have_image = h->d_Xs != nullptr && h->xs_rows == h->n && h->dim % 32 == 0;
-    bool f16_offer = f16_range_ok && allow_f16;
-    if (f16_offer && cmode == LB_CAND_AUTO && h->f16_skip.load(std::memory_order_relaxed) > 0) {
-        h->f16_skip.fetch_sub(1, std::memory_order_relaxed);
-        f16_offer = false;
-    }
-    // (offset-dominated L2 data: only the centred image's keys resolve anything; dot product over rows of very different
-    // lengths: only the lower-bound keys do)
-    const bool keys_matter = (centred && h->xh_offset_dom) || (metric == LB_METRIC_DOT && h->norm_spread);
-    const int cmode_route = (cmode == LB_CAND_AUTO && keys_matter && f16_offer) ? LB_CAND_F16 : cmode;
-    const Route route = choose_route(nq, n, h->dim, cmode_route, narrow_ok, have_image, f16_offer, have_xh, !h->f16_rows);
-    if (route.kind == 0) { // (fp16 rows, the image route not offered for this batch)
-        h->last_route.store(0, std::memory_order_relaxed);
-        std::vector<int> all(nq);
-        for (int i = 0; i < nq; i++) all[i] = i;
-        scan_with_retry(h, w, s, d_q, nq, all, k, d_dist, d_lab, prof);
-        return LB_OK;
-    }
-    h->last_route.store(route.kind * 10 + route.split, std::memory_order_relaxed);
-#ifdef LB_DIAG
-    g_last_route.store(route.kind * 10 + route.split);
-#endif
-    // candidates kept per query.  The fp16 single-product route keeps twice as many: its keys are good to ~1.1e-3 of |q||x|,
-    // and the containment proof needs the gap between the k-th and the LAST kept candidate to exceed about 2.5x that --
-    // on the benchmark data the gap to the 256th is 0.0019-0.0028 (most queries would fail), to the 512th 0.0039-0.0045.
-    // (Uniform random data is the hard case: its distances concentrate like 1/sqrt(D), so the gap shrinks with the dimension
-    // while the bound does not -- beyond 1024 dimensions four times as many candidates are kept.)
-    static const int f16_kc_mult = lb_tunable("LB_F16_KC_MULT", 0);
-    if (attempt == 0 && h->kc_hint_left.load(std::memory_order_relaxed) > 0) { // (see the retries at the end)
-        h->kc_hint_left.fetch_sub(1, std::memory_order_relaxed);
-        kc_in = std::max(kc_in, std::min(h->kc_hint.load(std::memory_order_relaxed), (int)(w->cap / 4)));
-    }
-    int kc = kc_in;
-    // (since the finish launch prunes in key space, kc only sizes the admission threshold: the list must hold the rows within
-    // the error bound of the k-th key -- 2-4 k of them with fp16 keys -- not a fixed number of rows to re-rank; capped so that
-    // a sampled threshold of that depth still exists)
-    if (route.split == 3)
-        kc = std::min(std::min(kc_in * (f16_kc_mult > 0 ? f16_kc_mult : (h->dim > 1024 ? 4 : 2)), std::max(1024, 2 * kc_in)), (int)(w->cap / 4));
-    const SamplePlan sp = sample_plan(n, kc, w->cap);
-    // up to 8 queries the sample is scored by the wave-per-row kernel (candidate keys; 22-28 us against
-    // 44 us for 8192 rows through the 32-workgroup MFMA launch); larger batches sample through the MFMA
-    // kernel itself.  Up to 64 queries the exact query norms ride in the threshold launch.
-    // candidate contraction: exact f32 MFMA, or 3 x bf16 MFMA on split operands (choose_route)
-    const int split = route.split;                 // of the operands handed to the kernel: 0 f32, 1 images, 2 f32 split in registers
-    const bool use_narrow = route.kind == ROUTE_NARROW32 || route.kind == ROUTE_NARROW64;
-    const bool tile64 = route.kind == ROUTE_NARROW64;
-    const bool use_tall = route.kind == ROUTE_TALL2 || route.kind == ROUTE_TALL16 || route.kind == ROUTE_NARROW16;
-    const bool use_tall2 = route.kind == ROUTE_TALL2;
-    const bool use_tall16 = route.kind == ROUTE_TALL16 || route.kind == ROUTE_NARROW16; // (the launcher takes the 64-query tile by itself)
-    const int wsplit = use_narrow ? 0 : route.split;
-    const float *gx = h->d_X, *gq = d_q;
     const float u24 = 5.9604645e-8f;
-    // rounding-error bound of the candidate inner products, per unit of ||q|| ||x||: a k-ordered f32 fma chain of
-    // length D, or (split contraction) 3D/16 MFMA accumulations + <=16-term block sums plus the dropped lo*lo /
-    // residual terms
-    // ... or (split 3) one fp16 product: 2^-11 per operand, the subnormal term under the route's norm conditions, and the
-    // f32 accumulation of D products (kernels_gemm_tall16.hip)
-    // ... with the index's fp16 image the operands' share is MEASURED instead: |q.x - q~.x~| <= |q||x - x~| + |q - q~||x~|, the
-    // residual norms taken when the image was written (rho_x = max over rows of |x - x~| / |x|, sync_f16_image) and when the
-    // query image is (rho_q per query, query_prep_body) -- a third to a half of the worst case for data that fills the
-    // mantissa, subnormal effects included:  gamma(q) = 1.05 (rho_x + A (1 + rho_x) + 2^-21) + 1.05 (1 + rho_x)(1 + A) rho_q,
-    // A = (D + 8) 2^-24 the f32 accumulation of D exact products
-    const bool measured = route.split == 3 && have_xh && (h->xh_rho > 0.f || h->xh_exact) &&
-                          h->xh_rho < 4.0e-4f; // (else the worst case is the better bound)
+    KeyBound b;
+    b.measured = split == 3 && have_xh && (h->xh_rho > 0.f || h->xh_exact) &&
+                 h->xh_rho < 4.0e-4f; // (else the worst case is the better bound)
     const float accA = (float)(h->dim + 8) * u24;
-    const float qrho_k = measured ? 1.05f * (1.0f + h->xh_rho) * (1.0f + accA) : 0.f;
-    const float gamma = route.split == 0   ? 1.05f * (float)(h->dim + 8) * u24
-                        : measured         ? 1.05f * (h->xh_rho + accA * (1.0f + h->xh_rho) + 4.7683716e-7f)
-                        : route.split == 3 ? 1.05f * (9.765625e-4f + 4.7683716e-7f + (float)(h->dim + 8) * u24 +
-                                                      2.9802322e-8f * std::sqrt((float)h->dim) * 65.0f)
-                                           : 1.05f * ((float)(3 * h->dim / 16 + 24) * u24 + 3.0f * 3.8146973e-6f);
-    auto split_queries = [&]() { // hi / lo bf16 image of the batch (same bytes as the f32 rows)
-        const size_t need = (size_t)nq * h->dim * sizeof(float);
-        if (w->d_qs_bytes < need) {
-            if (w->d_qs) (void)hipFree(w->d_qs);
-            w->d_qs = nullptr;
-            w->d_qs_bytes = 0;
-            LB_HIP(hipMalloc(&w->d_qs, need));
-            w->d_qs_bytes = need;
+    b.qrho_k = b.measured ? 1.05f * (1.0f + h->xh_rho) * (1.0f + accA) : 0.f;
+    b.gamma = split == 0     ? 1.05f * (float)(h->dim + 8) * u24
+              : b.measured   ? 1.05f * (h->xh_rho + accA * (1.0f + h->xh_rho) + 4.7683716e-7f)
+              : split == 3   ? 1.05f * (9.765625e-4f + 4.7683716e-7f + (float)(h->dim + 8) * u24 +
+                                        2.9802322e-8f * std::sqrt((float)h->dim) * 65.0f)
+                             : 1.05f * ((float)(3 * h->dim / 16 + 24) * u24 + 3.0f * 3.8146973e-6f);
+    b.gsum = b.gamma + 1.05f * (float)(h->dim + 8) * u24;
+    b.rho_gain = (b.measured && b.gsum > 0.f) ? b.qrho_k / b.gsum : 0.f;
+    return b;
+}
+
+// the rows behind the plan's sampled positions: the index's shared map (built by the first search after a change), or when that
+// holds another plan, the workspace's own
+const uint32_t *sample_map(lb_gpu_index *h, Workspace *w, hipStream_t s, const RowView &rv, const SamplePlan &sp)
+{
+    {
+        std::lock_guard<std::mutex> g(h->smap_mu);
+        if (!h->smap_valid) {
+            if (h->smap_cap < sp.count) {
+                if (h->d_smap) (void)hipFree(h->d_smap);
+                h->d_smap = nullptr;
+                h->smap_cap = 0;
+                LB_HIP(hipMalloc(&h->d_smap, (size_t)sp.count * sizeof(uint32_t)));
+                h->smap_cap = sp.count;
+            }
+            launch_sample_map(rv.rowmap, sp.span, sp.count, h->d_smap, s);
+            LB_HIP(hipStreamSynchronize(s));
+            h->smap_span = sp.span;
+            h->smap_count = sp.count;
+            h->smap_valid = true;
         }
-        launch_split_bf16(d_q, w->d_qs, nq, h->dim, s);
-    };
-    if (!use_narrow && (route.split == 1 || route.split == 2)) split_queries(); // the tall / wide split kernels take the batch as an image
-    float *d_qinv = nullptr, *d_qnrm = nullptr, *d_qrho = nullptr;
-    // dot product on the persistent fp16 kernels: LOWER-BOUND keys -(q.x)~ / G - |x|, G = (gamma_a + gamma_o) |q| (a few very long
-    // rows then sort to the front of the lists and are scored exactly instead of widening every row's error bound)
-    const float gsum = gamma + 1.05f * (float)(h->dim + 8) * u24;
-    const float rho_gain = (measured && gsum > 0.f) ? qrho_k / gsum : 0.f; // (dot: G(q) = (gsum + qrho_k rho_q) |q|, folded into qnrm)
-    const bool dot_lb = metric == LB_METRIC_DOT && use_tall16 &&
-                        tall16_runs_persistent(h->dim, nq, have_xh, rv.rowmap != nullptr, mask != nullptr);
-    const bool own_keys = centred || dot_lb; // keys only the persistent kernels produce: sample and boot chunks must come from them
-    static const int riders_max = lb_tunable("LB_NORM_RIDERS_MAXQ", 384);
-    const bool prep_riders = sp.on && nq <= riders_max; // (cosine: the exact query norms come out of the threshold launch)
-    if (use_tall16) { // fp16 image of the batch (scaled per query) + the inverse scales
-        const size_t img = (((size_t)nq * (size_t)((h->dim + 31) & ~31) * 2) + 255) & ~(size_t)255, need = img + 3 * (size_t)nq * sizeof(float);
-        if (w->d_qh_bytes < need) {
-            if (w->d_qh) (void)hipFree(w->d_qh);
-            w->d_qh = nullptr;
-            w->d_qh_bytes = 0;
-            LB_HIP(hipMalloc(&w->d_qh, need));
-            w->d_qh_bytes = need;
-        }
-        d_qinv = reinterpret_cast<float *>(static_cast<char *>(w->d_qh) + img);
-        d_qnrm = d_qinv + nq;
-        d_qrho = measured ? d_qnrm + nq : nullptr;
+        if (h->smap_span == sp.span && h->smap_count == sp.count) return h->d_smap;
     }
-    if (!use_narrow && route.split == 1) {
-        gx = h->d_Xs;
-        gq = w->d_qs;
-    }
-    // Up to 64 queries on the narrow split tiles the sample and its thresholds ride INSIDE the candidate launch (FUSED
-    // in kernels_gemm_narrow.hip: 19-34 us of sample + 13 us of threshold kernel off the critical path).
+    launch_sample_map(rv.rowmap, sp.span, sp.count, w->d_smap, s);
+    return w->d_smap;
+}
+
+// How a batched search scores the sample of its thresholds (one way per search; NONE: no sampled threshold):
+//   FUSED    up to 64 queries on the narrow split tiles: the sample and its thresholds ride INSIDE the candidate launch
+//            (FUSED in kernels_gemm_narrow.hip: 19-34 us of sample + 13 us of threshold kernel off the critical path)
+//   GRANULE  over the fp16 copy: through the persistent kernel itself, 512 granules of 16 consecutive rows, evenly spaced over
+//            the span (whole KiB of the K-blocked image; every workgroup takes a share of them)
+//   LIGHT    up to 8 queries: the wave-per-row kernel (candidate keys; 22-28 us against 44 us for 8192 rows through the
+//            32-workgroup MFMA launch, and 5 us quicker than the granules: every load of a row in flight at once)
+//   MAPPED   the sampled rows' map (sample_map), scored by the candidate launch itself
+enum SampleKind { SAMPLE_NONE, SAMPLE_FUSED, SAMPLE_GRANULE, SAMPLE_LIGHT, SAMPLE_MAPPED };
+// narrow / tall16: the route's tiles (the narrow split tiles / the fp16 kernels); entries_pos: the pass's entries carry positions of
+// the row list (a row list on the persistent fp16 kernels); dot_lb: dot product's lower-bound keys (those kernels too)
+SampleKind sample_kind(const SamplePlan &sp, bool narrow, bool tall16, int nq, int64_t n, bool rowmap, bool entries_pos, bool have_xh,
+                       bool dot_lb)
+{
     static const int fused_max = lb_tunable("LB_FUSED_SAMPLE_MAXQ", 32); // (33-64 queries, the 64-query tile: measured level)
-    // (from 131,072 rows: the fused launch has a floor of ~115 us whatever the corpus -- 70k x 768 at 8 queries 0.156 ms fused,
+    static const int light_max = lb_tunable("LB_LIGHT_SAMPLE_MAXQ", 8); // (also over a row list: at 32 queries the wave-per-row
+                                                                        // kernel took 105 us against the granule sample's 40)
+    if (!sp.on) return SAMPLE_NONE;
+    // (fused from 131,072 rows: the fused launch has a floor of ~115 us whatever the corpus -- 70k x 768 at 8 queries 0.156 ms fused,
     // 0.124 with the sample and the thresholds as launches of their own, level at 150k-300k, 20 us ahead at 1M -- and on the
     // 16k-64k-row corpora that take a sampled threshold since round 4 its waits gave up: 17k rows at 16 queries, 40k at 32,
     // the batch redone exactly in 1 ms)
     // (and thresholds of rank up to 32: with k = 300 -- 1024 candidates, m = 48 -- the threshold workgroups outlast the waits of
     // the corpus workgroups: 200k x 768 at 32 queries gave up on every search, 1.5 ms)
-    const bool fused = sp.on && use_narrow && nq <= fused_max && nq <= 64 && n >= 131072 && sp.m <= 32;
+    if (narrow && nq <= fused_max && nq <= 64 && n >= 131072 && sp.m <= 32) return SAMPLE_FUSED;
+    // (dot product's lower-bound keys: the sample must come out of the same kernel; centred L2 keys the wave-per-row kernel
+    // computes too, from the f32 rows about the same centre)
+    if (tall16 && sp.count % 16 == 0 && (!rowmap || entries_pos) &&
+        ((have_xh && nq > light_max) || dot_lb))
+        return SAMPLE_GRANULE;
+    // (not in front of the split tiles: up to 32 queries they always ran fused, and the wave-per-row sample was never paired
+    // with them -- L2, k = 300, 8 queries over 50k rows: every query flagged and scanned)
+    return nq <= light_max && !narrow ? SAMPLE_LIGHT : SAMPLE_MAPPED;
+}
+
+// One attempt of a batched search on `route`, keeping kc candidates per query: the sampled threshold, the candidate pass over the
+// view and the finish (key-space pruning + exact re-rank + containment proof).  Returns how many queries it left unproven, their
+// slots in `bad` -- or, when a wait inside the fused launch gave up (gave_up), every query of the batch (`bad` is then not filled).
+int run_batch(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, int k, float *d_dist, int64_t *d_lab, bool prof,
+              const Route &route, int kc, bool narrow_ok, bool have_xh, std::vector<int> &bad, bool &gave_up)
+{
+    const int metric = h->metric, order = h->order.load();
+    const RowView rv = row_view(h);
+    const int64_t n = rv.n;
+    const uint8_t *mask = rv.mask;
+    const SamplePlan sp = sample_plan(n, kc, w->cap);
+    // candidate contraction: exact f32 MFMA, 3 x bf16 MFMA on split operands, or one fp16 product (choose_route)
+    const bool use_narrow = route.kind == ROUTE_NARROW32 || route.kind == ROUTE_NARROW64;
+    const bool tile64 = route.kind == ROUTE_NARROW64;
+    const bool use_tall2 = route.kind == ROUTE_TALL2;
+    const bool use_tall16 = route.kind == ROUTE_TALL16 || route.kind == ROUTE_NARROW16; // (the launcher takes the 64-query tile by itself)
+    const int wsplit = use_narrow ? 0 : route.split; // of the operands handed to the kernel: 0 f32, 1 images, 2 f32 split in registers
+    const bool centred = have_xh && h->xh_centred;   // L2 image about a centre (sync_f16_image)
+    // the keys of this search are taken about the image's centre: sample, pass and finish read the centred norms and the centre
+    const bool ckeys = centred && use_tall16;
+    const float *knorm2 = ckeys ? h->d_norm2c : h->d_norm2, *kcenter = ckeys ? h->d_center : nullptr;
+    const KeyBound kb = key_bound(h, route.split, have_xh);
+    const float *gx = h->d_X, *gq = d_q;
+    if (!use_narrow && (route.split == 1 || route.split == 2)) { // the tall / wide split kernels take the batch as an image
+        grow_device(w->d_qs, w->d_qs_bytes, (size_t)nq * h->dim * sizeof(float)); // (hi / lo bf16: the bytes of the f32 rows)
+        launch_split_bf16(d_q, w->d_qs, nq, h->dim, s);
+        if (route.split == 1) {
+            gx = h->d_Xs;
+            gq = w->d_qs;
+        }
+    }
+    float *d_qinv = nullptr, *d_qnrm = nullptr, *d_qrho = nullptr;
+    // dot product on the persistent fp16 kernels: LOWER-BOUND keys (KeyBound::gsum)
+    const bool dot_lb = metric == LB_METRIC_DOT && use_tall16 &&
+                        tall16_runs_persistent(h->dim, nq, have_xh, rv.rowmap != nullptr, mask != nullptr);
+    const bool own_keys = centred || dot_lb; // keys only the persistent kernels produce: sample and boot chunks must come from them
+    static const int riders_max = lb_tunable("LB_NORM_RIDERS_MAXQ", 384);
+    const bool prep_riders = sp.on && nq <= riders_max; // (cosine: the exact query norms come out of the threshold launch)
+    const bool norm_riders = prep_riders && metric == LB_METRIC_COSINE;
+    if (use_tall16) { // fp16 image of the batch (scaled per query) + the inverse scales
+        const size_t img = (((size_t)nq * (size_t)((h->dim + 31) & ~31) * 2) + 255) & ~(size_t)255;
+        grow_device(w->d_qh, w->d_qh_bytes, img + 3 * (size_t)nq * sizeof(float));
+        d_qinv = reinterpret_cast<float *>(static_cast<char *>(w->d_qh) + img);
+        d_qnrm = d_qinv + nq;
+        d_qrho = kb.measured ? d_qnrm + nq : nullptr;
+    }
     // a search over a row list on the persistent fp16 kernels: its candidate entries carry positions of the list
     const bool entries_pos = use_tall16 && rv.rowmap != nullptr &&
                              tall16_entries_are_positions(h->dim, nq, have_xh, true, mask != nullptr);
-    // over the fp16 copy the sample goes through the persistent kernel itself: 512 granules of 16 consecutive rows, evenly
-    // spaced over the span (whole KiB of the K-blocked image; every workgroup takes a share of them)
-    // (up to 8 queries the wave-per-row kernel over the f32 rows is 5 us quicker: every load of a row in flight at once)
-    static const int light_max = lb_tunable("LB_LIGHT_SAMPLE_MAXQ", 8); // (also over a row list: at 32 queries the wave-per-row
-                                                                        // kernel took 105 us against the granule sample's 40)
-    // (dot product's lower-bound keys: the sample must come out of the same kernel; centred L2 keys the wave-per-row kernel
-    // computes too, from the f32 rows about the same centre)
-    const bool granule_sample = sp.on && use_tall16 && sp.count % 16 == 0 && (rv.rowmap == nullptr || entries_pos) &&
-                                ((have_xh && nq > light_max) || dot_lb || (centred && nq > light_max));
-    // (not in front of the split tiles: up to 32 queries they always ran fused, and the wave-per-row sample was never paired
-    // with them -- L2, k = 300, 8 queries over 50k rows: every query flagged and scanned)
-    const bool light_sample = sp.on && !fused && !granule_sample && nq <= light_max && !use_narrow;
+    const SampleKind sample = sample_kind(sp, use_narrow, use_tall16, nq, n, rv.rowmap != nullptr, entries_pos, have_xh, dot_lb);
     // Up to 128 queries on the one-tile kernel over the image, one span: the candidate launch turns the sample into the
     // thresholds ITSELF (its first nq workgroups, on shorter row ranges; kernels_gemm_tall16.hip, TAUIN) -- no threshold launch
     // and no gap behind it in front of the pass.
-    const bool tauin = sp.on && sp.span >= n && use_tall16 && route.kind == ROUTE_NARROW16 && !fused &&
-                       (light_sample || granule_sample) && prep_riders &&
-                       tall16_tin_ok(h->dim, nq, sp.span, have_xh, rv.rowmap != nullptr, mask != nullptr, (prep_riders && metric == LB_METRIC_COSINE), sp.count, sp.m);
+    const bool tauin = (sample == SAMPLE_LIGHT || sample == SAMPLE_GRANULE) && sp.span >= n && route.kind == ROUTE_NARROW16 &&
+                       prep_riders &&
+                       tall16_tin_ok(h->dim, nq, sp.span, have_xh, rv.rowmap != nullptr, mask != nullptr, norm_riders, sp.count, sp.m);
     Tall16Tin tin{};
     uint32_t tin_epoch = 0;
     if (tauin) {
-        if (++w->fs_epoch == 0) w->fs_epoch = 1; // (0 = "never published")
-        tin_epoch = w->fs_epoch;
+        tin_epoch = w->next_epoch();
         tin.count = sp.count;
         tin.m = sp.m;
         tin.tag = tin_epoch;
         tin.fail_host = w->h_fail;
         tin.Q = d_q;
-        tin.qna = (prep_riders && metric == LB_METRIC_COSINE) ? w->d_qna : nullptr;
+        tin.qna = norm_riders ? w->d_qna : nullptr;
         tin.order = order;
 #ifdef LB_DIAG
         tin.withhold = g_tin_withhold_next.exchange(0);
 #endif
     }
     // (up to 8 queries: the query preparation rides in the sample launch -- one launch and one gap less in front of the pass)
-    const bool prep_rides = use_tall16 && light_sample && prep_riders;
+    const bool prep_rides = use_tall16 && sample == SAMPLE_LIGHT && prep_riders;
     if (use_tall16 && !prep_rides)
         // one launch: the image, the scales, the exact query norms (cosine) and the reset of the candidate state
         // (the exact norm is a serial chain of D additions, 3.5 us at 768: up to 384 queries it rides in the threshold launch
         // instead, where nothing waits for it)
         launch_query_prep(d_q, nq, h->dim, w->d_qh, d_qinv, (metric == LB_METRIC_COSINE && !prep_riders) ? w->d_qna : nullptr, order,
-                          w->cs, s, centred ? h->d_center : nullptr, dot_lb ? d_qnrm : nullptr, tauin, d_qrho, rho_gain);
-    const bool norm_riders = prep_riders && metric == LB_METRIC_COSINE;
+                          w->cs, s, kcenter, dot_lb ? d_qnrm : nullptr, tauin, d_qrho, kb.rho_gain);
     // the last launch: key-space pruning + exact re-rank + proof in one (kernels_finish.hip); beta: how far beyond one error
     // bound the cut lies (the proof itself never depends on it)
     static const float finish_beta = 0.01f * (float)lb_tunable("LB_FINISH_BETA_PCT", 25);
-    if (!light_sample && !fused && !use_tall16) launch_init_cand(w->cs, nullptr, nq, s);
+    if (sample != SAMPLE_LIGHT && sample != SAMPLE_FUSED && !use_tall16) launch_init_cand(w->cs, nullptr, nq, s);
     if (metric == LB_METRIC_COSINE && !norm_riders && !use_tall16) launch_query_norms(order, d_q, nullptr, nq, h->dim, w->d_qna, s); // (fp16 route: query_prep)
     // (fp16 route, several 256-query tiles: the sample goes through the fp16 kernel itself -- 32 row tiles x nq/256 workgroups
     // against nq/64 x 64 of the narrow tile; 1024 queries: 1.94 -> 1.88 ms, 512: 1.015 -> 1.00; tools/probe/sample_route_probe.py)
@@ -1113,7 +1083,7 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
         else if (use_tall16 && h->dim % 32 != 0 && (rowmap || mask) && !entries_pos)
             // the sample of a search over the fp16 copy when the dimension is not a multiple of 32: the f32 tile takes any
             launch_gemm_filter(metric, h->d_X, h->d_norm2, h->d_rnorm, b, e, h->dim, d_q, nq, mask, rowmap, w->cs, boot, 0, s);
-        else if (use_tall && boot && (wsplit == 2 || wsplit == 3) && narrow_ok && !entries_pos && !own_keys &&
+        else if (boot && (wsplit == 2 || wsplit == 3) && narrow_ok && !entries_pos && !own_keys &&
                  !(use_tall16 && nq > sample_narrow_maxq))
             // the 8192-row sample of a tall-tile search: the 64-query tile of the narrow kernel (same contraction, f32
             // operands) gets through its 24 K-steps of 32 in 31-35 us, the tall tile through its 48 of 16 in 57
@@ -1122,8 +1092,8 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
             launch_gemm_filter_narrow(metric, h->d_X, h->d_norm2, h->d_rnorm, b, e, h->dim, d_q, nq, mask, rowmap, w->cs,
                                       true, s, /*tile64=*/true);
         else if (use_tall16)
-            launch_gemm_filter_tall16(metric, h->d_X, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, b, e, h->dim, w->d_qh, d_qinv, nq,
-                                      mask, rowmap, w->cs, boot, s, have_xh ? h->d_Xh : nullptr, h->xh_cap, 0u, d_qnrm, gsum,
+            launch_gemm_filter_tall16(metric, h->d_X, knorm2, h->d_rnorm, b, e, h->dim, w->d_qh, d_qinv, nq,
+                                      mask, rowmap, w->cs, boot, s, have_xh ? h->d_Xh : nullptr, h->xh_cap, 0u, d_qnrm, kb.gsum,
                                       (tauin && !boot && b == 0 && e == sp.span) ? &tin : nullptr);
         else if (use_tall2)
             launch_gemm_filter_tall2(metric, gx, h->d_norm2, h->d_rnorm, b, e, h->dim, w->d_qs, nq, mask, rowmap, w->cs,
@@ -1136,60 +1106,8 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     int step = 0;
     uint32_t fused_epoch = tin_epoch; // (a wait inside a launch that gave up is reported through one pinned word, whichever launch it was)
     if (sp.on) { // sampled threshold, then one pass over the span (see sample_plan)
-        const uint32_t *smap = w->d_smap;
-        if (light_sample) {
-            ProfScope p(w, s, prof, 1);
-            // (centred keys: the same key about the image's centre, from the f32 rows)
-            const SamplePrep sprep{w->d_qh, d_qinv, dot_lb ? d_qnrm : nullptr, centred ? h->d_center : nullptr, tauin, d_qrho, rho_gain};
-            if (h->f16_rows)
-                launch_sample_scores(metric, order, h->rows_f16(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, nullptr, nq,
-                                     w->cs, nullptr, s, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, centred ? h->d_center : nullptr,
-                                     prep_rides ? &sprep : nullptr);
-            else
-                launch_sample_scores(metric, order, h->d_X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, nullptr, nq,
-                                     w->cs, nullptr, s, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, centred ? h->d_center : nullptr,
-                                     prep_rides ? &sprep : nullptr);
-            if (!tauin)
-                launch_sample_tau(w->cs, nullptr, nq, sp.count, sp.m, false, s, d_q, h->dim,
-                                  norm_riders ? w->d_qna : nullptr, order);
-        } else if (granule_sample) {
-            {
-                ctx_check(w->ctx);
-                ProfScope p(w, s, prof, 1); // (timing class "select": threshold work, so that class "gemm" is the corpus pass alone)
-                launch_gemm_filter_tall16(metric, h->d_X, centred ? h->d_norm2c : h->d_norm2, h->d_rnorm, 0, sp.count, h->dim, w->d_qh, d_qinv,
-                                          nq, nullptr, rv.rowmap, w->cs, /*boot=*/true, s, have_xh ? h->d_Xh : nullptr, h->xh_cap,
-                                          (uint32_t)(sp.span / (int64_t)(sp.count / 16)), d_qnrm, gsum);
-            }
-            ProfScope p(w, s, prof, 1);
-            if (!tauin) launch_sample_tau(w->cs, nullptr, nq, sp.count, sp.m, false, s, d_q, h->dim, norm_riders ? w->d_qna : nullptr, order);
-        } else {
-            {
-                std::lock_guard<std::mutex> g(h->smap_mu);
-                if (!h->smap_valid) {
-                    if (h->smap_cap < sp.count) {
-                        if (h->d_smap) (void)hipFree(h->d_smap);
-                        h->d_smap = nullptr;
-                        h->smap_cap = 0;
-                        LB_HIP(hipMalloc(&h->d_smap, (size_t)sp.count * sizeof(uint32_t)));
-                        h->smap_cap = sp.count;
-                    }
-                    launch_sample_map(rv.rowmap, sp.span, sp.count, h->d_smap, s);
-                    LB_HIP(hipStreamSynchronize(s));
-                    h->smap_span = sp.span;
-                    h->smap_count = sp.count;
-                    h->smap_valid = true;
-                }
-                if (h->smap_span == sp.span && h->smap_count == sp.count) smap = h->d_smap;
-            }
-            if (smap == w->d_smap) launch_sample_map(rv.rowmap, sp.span, sp.count, w->d_smap, s);
-            if (!fused) {
-                candidates(0, sp.count, smap, /*boot=*/true);
-                ProfScope p(w, s, prof, 1);
-                launch_sample_tau(w->cs, nullptr, nq, sp.count, sp.m, false, s, d_q, h->dim,
-                                  norm_riders ? w->d_qna : nullptr, order);
-            }
-        }
-        if (fused) {
+        if (sample == SAMPLE_FUSED) {
+            const uint32_t *smap = sample_map(h, w, s, rv, sp);
             ProfScope p(w, s, prof, 0);
             FusedSample fs;
             fs.smap = smap;
@@ -1198,8 +1116,7 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
             fs.ticket = w->d_fsync;
             fs.ticket_base = w->fs_base;
             fs.ready = w->d_fsync + 1;
-            if (++w->fs_epoch == 0) w->fs_epoch = 1; // (0 = "never published")
-            fs.epoch = w->fs_epoch;
+            fs.epoch = w->next_epoch();
             fs.qna = norm_riders ? w->d_qna : nullptr;
             fs.order = order;
             fs.fail_host = w->h_fail;
@@ -1208,6 +1125,26 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
             w->fs_base += fused_sample_blocks(sp.count, nq, tile64);
             fused_epoch = fs.epoch;
         } else {
+            if (sample == SAMPLE_GRANULE) {
+                ctx_check(w->ctx);
+                ProfScope p(w, s, prof, 1); // (timing class "select": threshold work, so that class "gemm" is the corpus pass alone)
+                launch_gemm_filter_tall16(metric, h->d_X, knorm2, h->d_rnorm, 0, sp.count, h->dim, w->d_qh, d_qinv,
+                                          nq, nullptr, rv.rowmap, w->cs, /*boot=*/true, s, have_xh ? h->d_Xh : nullptr, h->xh_cap,
+                                          (uint32_t)(sp.span / (int64_t)(sp.count / 16)), d_qnrm, kb.gsum);
+            } else if (sample == SAMPLE_MAPPED) {
+                candidates(0, sp.count, sample_map(h, w, s, rv, sp), /*boot=*/true);
+            }
+            {   // (LIGHT: the scores of the wave-per-row kernel) the thresholds -- unless the pass takes them itself (TAUIN)
+                ProfScope p(w, s, prof, 1);
+                if (sample == SAMPLE_LIGHT) {
+                    const SamplePrep sprep{w->d_qh, d_qinv, dot_lb ? d_qnrm : nullptr, kcenter, tauin, d_qrho, kb.rho_gain};
+                    with_rows(h, [&](auto X) {
+                        launch_sample_scores(metric, order, X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, nullptr, nq, w->cs, nullptr,
+                                             s, knorm2, h->d_rnorm, kcenter, prep_rides ? &sprep : nullptr);
+                    });
+                }
+                if (!tauin) launch_sample_tau(w->cs, nullptr, nq, sp.count, sp.m, false, s, d_q, h->dim, norm_riders ? w->d_qna : nullptr, order);
+            }
             candidates(0, sp.span, rv.rowmap, /*boot=*/false);
         }
         // (one span covers the view: the finish launch prunes the raw list itself -- everything below tau is in it)
@@ -1231,79 +1168,154 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     }
     {
         ProfScope p(w, s, prof, 2);
-        {
-            // members a query may have: twice the results wanted, at least 1024 (the lists hold up to cap entries below tau)
-            const uint32_t smax = std::min<uint32_t>(kFinishSmaxMax, std::max<uint32_t>(1024u, 2u * next_pow2_host((uint32_t)k)));
-            const bool ckeys = centred && use_tall16; // (the keys of this search were taken about the image's centre)
-            if (h->f16_rows)
-                launch_finish(metric, order, h->rows_f16(), h->dim, d_q, nq, w->d_qna, w->cs, k, ckeys ? h->d_cstats : h->d_maxnorm2, gamma,
-                              finish_beta, h->has_ids ? h->d_ids : nullptr, entries_pos ? rv.rowmap : nullptr, d_dist, d_lab, s, w->h_flags,
-                              w->d_done, w->d_xcnt, w->d_xscratch, kFinishSplitMaxQ, smax, ckeys ? h->d_center : nullptr,
-                              dot_lb ? h->d_norm2 : nullptr, d_qnrm, gsum, dot_lb ? nullptr : d_qrho, qrho_k);
-            else
-                launch_finish(metric, order, h->d_X, h->dim, d_q, nq, w->d_qna, w->cs, k, ckeys ? h->d_cstats : h->d_maxnorm2, gamma, finish_beta,
-                              h->has_ids ? h->d_ids : nullptr, entries_pos ? rv.rowmap : nullptr, d_dist, d_lab, s, w->h_flags, w->d_done, w->d_xcnt,
-                              w->d_xscratch, kFinishSplitMaxQ, smax, ckeys ? h->d_center : nullptr, dot_lb ? h->d_norm2 : nullptr, d_qnrm, gsum,
-                              dot_lb ? nullptr : d_qrho, qrho_k);
-        }
+        // members a query may have: twice the results wanted, at least 1024 (the lists hold up to cap entries below tau)
+        const uint32_t smax = std::min<uint32_t>(kFinishSmaxMax, std::max<uint32_t>(1024u, 2u * next_pow2_host((uint32_t)k)));
+        with_rows(h, [&](auto X) {
+            launch_finish(metric, order, X, h->dim, d_q, nq, w->d_qna, w->cs, k, ckeys ? h->d_cstats : h->d_maxnorm2, kb.gamma, finish_beta,
+                          h->has_ids ? h->d_ids : nullptr, entries_pos ? rv.rowmap : nullptr, d_dist, d_lab, s, w->h_flags, w->d_done,
+                          w->d_xcnt, w->d_xscratch, kFinishSplitMaxQ, smax, kcenter, dot_lb ? h->d_norm2 : nullptr, d_qnrm, kb.gsum,
+                          dot_lb ? nullptr : d_qrho, kb.qrho_k);
+        });
     }
-    std::vector<int> bad;
-    int nbad = collect_flagged(w, s, nq, 3u | 4u, nullptr, 0, bad, /*on_host=*/true);
-#ifdef LB_DIAG
-    if (getenv("LB_TRACE_RETRY")) {
-        uint32_t orf = 0;
-        int c1 = 0, c2 = 0, c4 = 0;
-        for (int i = 0; i < nq; i++) { orf |= w->h_flags[i]; c1 += (w->h_flags[i] & 1u) != 0; c2 += (w->h_flags[i] & 2u) != 0; c4 += (w->h_flags[i] & 4u) != 0; }
-        fprintf(stderr, "[retry] attempt %d route %d split %d kc %d sample %d m %d nbad %d flags|=%x (bit0 %d bit1 %d bit2 %d)\n", attempt, route.kind, route.split, kc,
-                (int)sp.on, sp.m, nbad, orf, c1, c2, c4);
-    }
-#endif
-    bool fused_gave_up = false;
-    if (fused_epoch != 0 && (*w->h_fail == fused_epoch || g_fused_fail_next.exchange(0) != 0)) {
-        fused_gave_up = true;
-        // a wait inside the fused launch gave up (its workgroups were not co-resident): every query goes the exact way,
-        // and the ticket counter is re-based in case the launch did not run to completion
-        bad.resize((size_t)nq);
-        for (int i = 0; i < nq; i++) bad[(size_t)i] = i;
-        nbad = nq;
-        h->fused_giveups.fetch_add(1);
-        LB_HIP(hipMemsetAsync(w->d_fsync, 0, sizeof(uint32_t), s));
-        w->fs_base = 0;
-    }
+    const int nbad = collect_flagged(w, s, nq, 3u | 4u, nullptr, 0, bad, /*on_host=*/true);
+    gave_up = fused_epoch != 0 && (*w->h_fail == fused_epoch || g_fused_fail_next.exchange(0) != 0);
+    if (!gave_up) return nbad;
+    // a wait inside the fused launch gave up (its workgroups were not co-resident): every query goes the exact way,
+    // and the ticket counter is re-based in case the launch did not run to completion
+    h->fused_giveups.fetch_add(1);
+    LB_HIP(hipMemsetAsync(w->d_fsync, 0, sizeof(uint32_t), s));
+    w->fs_base = 0;
+    return nq;
+}
+
+// A batch of queries of an f32 or fp16 index.  Path selection: <= 4 queries the exact scan (0.50-0.55 ms at 1M x 768); from 5
+// queries a candidate route picked by choose_route's cost model (narrow / tall / tall2 / fp16 / f32 tile), exact re-rank behind
+// every one of them.  A batch the route leaves unproven is redone (the recovery at the end of the loop); what is unproven after
+// that takes the exact scan and is counted in `fallbacks`.
+int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, int k,
+                        float *d_dist, int64_t *d_lab, int kc_in, bool prof, int64_t &fallbacks)
+{
+    static const int narrow_min = lb_tunable("LB_NARROW_MINQ", 5);
+    static const int f16_kc_mult = lb_tunable("LB_F16_KC_MULT", 0);
+    // the same for every attempt (the caller holds the index's shared lock)
+    const RowView rv = row_view(h);
+    const int64_t n = rv.n; // positions to walk: corpus rows, or the visible-row list under a selective filter
+    const int cmode = h->cand_mode.load();
+    const bool narrow_ok = !h->f16_rows && h->dim % 32 == 0 && ((reinterpret_cast<uintptr_t>(d_q) & 15) == 0);
+    // (the fp16 image serves unfiltered searches and searches over a row list -- the persistent kernels gather out of it,
+    // dimensions from 256; under a per-row mask test the kernel stages f32 rows)
+    const bool have_xh = h->d_Xh != nullptr && h->xh_rows == h->n && !rv.mask && (!rv.rowmap || h->dim >= 256) &&
+                         // (a centred image -- L2 -- is only ever read by the persistent kernels: nothing else knows the centre;
+                         // fp16 rows: only the persistent kernels read nothing but the image -- the one-tile form stages f32 rows)
+                         ((!h->xh_centred && !h->f16_rows) || tall16_runs_persistent(h->dim, nq, true, rv.rowmap != nullptr, false));
+    const bool centred = have_xh && h->xh_centred; // L2 keys about the image's centre (sync_f16_image)
+    const bool have_image = h->d_Xs != nullptr && h->xs_rows == h->n && h->dim % 32 == 0;
     const int kc_max = (int)(w->cap / 4);
-    const bool can_widen = attempt <= 2 && kc < kc_max && (int64_t)kc * 2 < n; // (up to three widenings: x4, x16, x64, capped)
-    if (route.split == 3 && cmode == LB_CAND_AUTO && attempt <= 3 && !(nbad > 8 && can_widen)) {
-        if (nbad * 8 > nq) { // the fp16 keys are too coarse for this data even with the widened list: leave the route alone
-            const int span = h->f16_span.load(); // for a while (doubling spans)
-            h->f16_skip.store(span);
-            h->f16_span.store(std::min(span * 2, 4096));
-        } else if (nbad == 0) {
-            h->f16_span.store(16);
+    ProfScope whole(w, s, prof, 4);
+    bool allow_f16 = true;
+    for (int attempt = 0;;) {
+        ctx_check(w->ctx);
+        // ---- path and route: re-decided by every attempt ----
+        // within the fp16 contraction's range: the centred norms when the image is centred, the rows' own norms otherwise
+        bool f16_range_ok = centred ? h->xh_c_ok : h->f16_ok;
+        // Mid-size corpora and views (below 262,144 rows: offered the fp16 routes since round 4): only while ONE sampled span covers
+        // the view with the candidate list the fp16 keys need (twice / four times the split tiles') -- with k = 300 that list is a
+        // quarter of the lists' capacity, the sampled span ends short of 200k rows and the rest runs the classic schedule:
+        // 0.45 ms where the split tiles over the f32 rows take 0.15.  (Larger corpora: as before.)
+        if (cmode == LB_CAND_AUTO && n < 262144 && kc_in > 0) {
+            const SamplePlan sp16 = sample_plan(n, f16_kc(kc_in, h->dim, w->cap), w->cap);
+            if (!(sp16.on && sp16.span >= n)) f16_range_ok = false;
         }
+        // the route over the fp16 copy is on offer (dimensions that are not multiples of 32 included: the MFMA tiles over f32 rows
+        // do not apply, the fp16 copy does)
+        const bool copy_ok = have_xh && f16_range_ok && allow_f16 &&
+                             (cmode == LB_CAND_F16 || (cmode == LB_CAND_AUTO && h->f16_skip.load(std::memory_order_relaxed) == 0));
+        // 1 .. 4 queries: the exact scan streams the f32 corpus (0.52 ms per 1M x 768); with the fp16 copy the candidate pass
+        // streams half the bytes and the exact re-rank of 512 candidates costs 0.03 ms -- taken when the model says it is cheaper
+        bool small_on_copy = false;
+        if (!h->nonfinite && nq < narrow_min && copy_ok) {
+            const double scan_ms = 0.04 + 1e-6 * (double)n * ((double)h->dim * 0.00066 * (h->f16_rows ? 0.5 : 1.0) + 0.04); // (0.04: sample,
+                                                                                                                           // thresholds, select + emit)
+            small_on_copy = cmode == LB_CAND_F16 || narrow16_ms(n, h->dim, nq) < scan_ms;
+        }
+        // the exact scan: rows with inf / NaN components (the MFMA pipeline's keys and error bounds assume finite data; the scan
+        // orders non-finite distances canonically, NaN last), an fp16 index without the image route on offer (no image, rows out
+        // of fp16's key range, a masked search, the batch beyond the persistent kernels: the exact scan over the fp16 rows, the
+        // floor), batches too small for a candidate route -- and an fp16 index's batch that choose_route offers nothing
+        const bool scan = h->nonfinite || (h->f16_rows && !copy_ok) ||
+                          (nq < ((narrow_ok || copy_ok) ? narrow_min : kGemmMinQ) && !small_on_copy);
+        Route route{0, 0, 0.0};
+        if (!scan) {
+            bool f16_offer = f16_range_ok && allow_f16;
+            if (f16_offer && cmode == LB_CAND_AUTO && h->f16_skip.load(std::memory_order_relaxed) > 0) {
+                h->f16_skip.fetch_sub(1, std::memory_order_relaxed);
+                f16_offer = false;
+            }
+            // (offset-dominated L2 data: only the centred image's keys resolve anything; dot product over rows of very different
+            // lengths: only the lower-bound keys do)
+            const bool keys_matter = (centred && h->xh_offset_dom) || (h->metric == LB_METRIC_DOT && h->norm_spread);
+            const int cmode_route = (cmode == LB_CAND_AUTO && keys_matter && f16_offer) ? LB_CAND_F16 : cmode;
+            route = choose_route(nq, n, h->dim, cmode_route, narrow_ok, have_image, f16_offer, have_xh, !h->f16_rows);
+        }
+        h->last_route.store(route.kind * 10 + route.split, std::memory_order_relaxed);
+        if (route.kind == 0) {
+            scan_with_retry(h, w, s, d_q, nq, nullptr, k, d_dist, d_lab, prof);
+            return LB_OK;
+        }
+#ifdef LB_DIAG
+        g_last_route.store(route.kind * 10 + route.split);
+#endif
+        if (attempt == 0 && h->kc_hint_left.load(std::memory_order_relaxed) > 0) { // (the widened-list hint, below)
+            h->kc_hint_left.fetch_sub(1, std::memory_order_relaxed);
+            kc_in = std::max(kc_in, std::min(h->kc_hint.load(std::memory_order_relaxed), kc_max));
+        }
+        // candidates kept per query: the fp16 single-product route keeps more (f16_kc)
+        const int kc = route.split == 3 ? f16_kc(kc_in, h->dim, w->cap, f16_kc_mult) : kc_in;
+        std::vector<int> bad;
+        bool gave_up = false;
+        const int nbad = run_batch(h, w, s, nq, d_q, k, d_dist, d_lab, prof, route, kc, narrow_ok, have_xh, bad, gave_up);
+
+        // ---- recovery ----
+        // More than a handful of unproven queries (each would cost an exact scan of the corpus: 0.5 ms per group of 8 at
+        // 1M x 768) and the batch is redone instead, cheapest remedy first:
+        //   1. the same route keeping FOUR TIMES the candidates (up to three times over, capped at a quarter of the list) -- the
+        //      usual cause is a tight cluster (hundreds of rows whose distances differ by less than the keys resolve): once the
+        //      whole cluster is inside the list, the gap to the first row outside it is wide and the proof goes through
+        //      (1M x 768 in clusters of ~1000: 1024 queries 93 ms -> a few ms);
+        //   2. (fp16 keys) the split-bf16 route, ~100x finer keys, with the widened list;
+        //   3. the exact scan for what is still unproven.
+        const bool can_widen = attempt <= 2 && kc < kc_max && (int64_t)kc * 2 < n; // (up to three widenings: x4, x16, x64, capped)
+        if (route.split == 3 && cmode == LB_CAND_AUTO && attempt <= 3 && !(nbad > 8 && can_widen)) {
+            if (nbad * 8 > nq) { // the fp16 keys are too coarse for this data even with the widened list: leave the route alone
+                const int span = h->f16_span.load(); // for a while (doubling spans)
+                h->f16_skip.store(span);
+                h->f16_span.store(std::min(span * 2, 4096));
+            } else if (nbad == 0) {
+                h->f16_span.store(16);
+            }
+        }
+        if (attempt >= 1 && attempt <= 3 && nbad <= 8) { // the widened list proved the batch: start the next searches there
+            h->kc_hint.store(kc_in, std::memory_order_relaxed);
+            h->kc_hint_left.store(256, std::memory_order_relaxed);
+        }
+        if (nbad > 8 && !gave_up && attempt < 4) {
+            if (can_widen) { // 1.
+                kc_in = std::min(kc_in * 4, kc_max);
+                attempt++;
+                continue;
+            }
+            if (route.split == 3 && allow_f16) { // 2. (one attempt, numbered 4: nothing follows it but the scan)
+                allow_f16 = false;
+                attempt = 4;
+                continue;
+            }
+        }
+        if (nbad > 0) { // 3.
+            fallbacks += nbad;
+            scan_with_retry(h, w, s, d_q, nq, gave_up ? nullptr : &bad, k, d_dist, d_lab, prof);
+        }
+        return LB_OK;
     }
-    if (attempt >= 1 && attempt <= 3 && nbad <= 8) { // the widened list proved the batch: start the next searches there
-        h->kc_hint.store(kc_in, std::memory_order_relaxed);
-        h->kc_hint_left.store(256, std::memory_order_relaxed);
-    }
-    // More than a handful of unproven queries (each would cost an exact scan of the corpus: 0.5 ms per group of 8 at
-    // 1M x 768) and the batch is redone instead, cheapest remedy first:
-    //   1. the same route keeping FOUR TIMES the candidates (up to three times over, capped at a quarter of the list) -- the usual cause is a tight cluster (hundreds of rows whose
-    //      distances differ by less than the keys resolve): once the whole cluster is inside the list, the gap to the first
-    //      row outside it is wide and the proof goes through (1M x 768 in clusters of ~1000: 1024 queries 93 ms -> a few ms);
-    //   2. (fp16 keys) the split-bf16 route, ~100x finer keys, with the widened list;
-    //   3. the exact scan for what is still unproven.
-    if (nbad > 8 && !fused_gave_up && attempt < 4) {
-        if (can_widen)
-            return search_batch_device(h, w, s, nq, d_q, k, d_dist, d_lab, std::min(kc_in * 4, kc_max), prof, fallbacks, allow_f16,
-                                       attempt + 1);
-        if (route.split == 3 && allow_f16)
-            return search_batch_device(h, w, s, nq, d_q, k, d_dist, d_lab, kc_in, prof, fallbacks, /*allow_f16=*/false, 4);
-    }
-    if (nbad > 0) {
-        fallbacks += (int64_t)bad.size();
-        scan_with_retry(h, w, s, d_q, nq, bad, k, d_dist, d_lab, prof);
-    }
-    return LB_OK;
 }
 
 // one wave per CU spins for `ticks` of the constant 100 MHz counter and adds (shader cycles, ticks) to out[0 .. 1]
@@ -1638,8 +1650,9 @@ void sync_split_image(lb_gpu_index *h)
 void sync_f16_image(lb_gpu_index *h)
 {
     const int cm = h->cand_mode.load();
-    // (round 4: from 65,536 rows -- the size from which a sampled threshold exists -- instead of 262,144: 100k x 768 at 256 queries
-    // 0.298 -> 0.163 ms, 1024: 0.82 -> 0.43; 200k x 768: 0.49 -> 0.21, 1.25 -> 0.57; +50 % of a corpus of this size is 0.15-0.4 GB)
+    // (from 16,384 rows -- the size from which a sampled threshold exists.  Round 4 brought it down from 262,144, to 65,536 first:
+    // 100k x 768 at 256 queries 0.298 -> 0.163 ms, 1024: 0.82 -> 0.43; 200k x 768: 0.49 -> 0.21, 1.25 -> 0.57; +50 % of a corpus
+    // of this size is 0.15-0.4 GB)
     static const int64_t f16_image_min_rows = lb_tunable("LB_F16_IMAGE_MIN_ROWS", 16384);
     const bool l2 = h->metric == LB_METRIC_EUCLIDEAN;
     // (L2: the image is centred, so what must fit fp16 are the centred norms -- known once the centre is)
@@ -1711,7 +1724,7 @@ void sync_f16_image(lb_gpu_index *h)
                 for (float v : hc) c2 += (double)v * (double)v;
                 h->xh_offset_dom = c2 > 4.0 * (double)mx;
             }
-            { // the loss of the new rows' images, measured (the candidate keys' error bound: search_batch_device, gamma)
+            { // the loss of the new rows' images, measured (the candidate keys' error bound: key_bound)
                 if (!h->d_xh_rho2) {
                     LB_HIP(hipMalloc(&h->d_xh_rho2, sizeof(uint32_t)));
                     LB_HIP(hipMemsetAsync(h->d_xh_rho2, 0, sizeof(uint32_t), s));
@@ -2252,14 +2265,7 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
                 const int bq = (int)std::min<int64_t>(kMaxBatch, nq - q0);
                 const float *bq_f32 = nullptr;
                 if (dtype != 0) { // fp16 / int8 queries: widened exactly into the workspace's f32 batch, then searched as any other
-                    const size_t need = (size_t)bq * h->dim * sizeof(float);
-                    if (w->d_q_bytes < need) {
-                        if (w->d_q) (void)hipFree(w->d_q);
-                        w->d_q = nullptr;
-                        w->d_q_bytes = 0;
-                        LB_HIP(hipMalloc(&w->d_q, need));
-                        w->d_q_bytes = need;
-                    }
+                    grow_device(w->d_q, w->d_q_bytes, (size_t)bq * h->dim * sizeof(float));
                     if (dtype == 2)
                         launch_widen_i8(static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q, (int64_t)bq * h->dim, s);
                     else
