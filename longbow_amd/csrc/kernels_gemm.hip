@@ -157,20 +157,30 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
             gsrcB[i] = a.Q + (int64_t)qr * a.D + 4 * c;
         }
     }
-    auto glds_stage = [&](int stage, int k0) {
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            const int j = wave * 4 + i;
+    // one staging piece p = 0..7 (A0 B0 A1 B1 .. A3 B3).  The LDS destination is built from a wave index the compiler
+    // can see is uniform, so m0 is scalar arithmetic (no v_readfirstlane per piece): a piece costs one 64-bit address
+    // add on top of its global_load_lds.
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    auto glds_piece = [&](int p, int stage, int k0) {
+        const int i = p >> 1;
+        const int j = wave_u * 4 + i;
+        if ((p & 1) == 0)
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)(gsrcA[i] + k0),
                 (__attribute__((address_space(3))) void *)(&lds[stage][0][j * 8 * BK]), 16, 0,
                 2); // aux 2 = nt: the corpus streams through once; keeps Q resident in L2
                     // (measured: L2-miss traffic 2.5x -> 1.8x algorithmic, same speed)
+        else
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) void *)(gsrcB[i] + k0),
                 (__attribute__((address_space(3))) void *)(&lds[stage][1][j * 8 * BK]), 16, 0, 0);
-        }
     };
+    auto glds_stage = [&](int stage, int k0) {
+#pragma unroll
+        for (int p = 0; p < 8; p++) glds_piece(p, stage, k0);
+    };
+    // the f32 GLDS tile (WIDE) runs its own K-loop below
+    constexpr bool WIDE = GLDS && SPLIT == 0;
 
     // prologue: stage 0
     if (GLDS) glds_stage(0, 0);
@@ -212,127 +222,215 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
     }
     __syncthreads();
 
-    // Main loop.  Per K-step (BK = 32): the next stage's global loads are issued first, the
-    // fragment reads of sub-step s+1 are issued before the 16 MFMAs of sub-step s (register
-    // double buffer), and the LDS write of the next stage happens in the middle of the MFMA
-    // stream (its target buffer was released by the barrier that ended the previous K-step), so
-    // the only serial section left at the end of a K-step is the barrier itself.
-    for (int kt = 0; kt < nk; kt++) {
-        const int cur = kt & 1;
-        const bool has_next = kt + 1 < nk;
-        if (has_next) {
-            const int k0 = (kt + 1) * BK;
-            if (GLDS) {
-                glds_stage(cur ^ 1, k0);
-            } else {
+    if constexpr (WIDE) {
+        // Main loop of the f32 GLDS tile, rotated by one sub-step so that no LDS or DMA issue sits outside the
+        // MFMA stream.  A K-step is 4 sub-steps of 16 MFMAs (2 k per MFMA, lane halves on alternate 16-B chunks).
+        // Two named fragment sets alternate: F0 feeds sub-steps 0 and 2, F1 sub-steps 1 and 3, and the reads of
+        // sub-step s+1 are issued after the first 2 of sub-step s's MFMAs, 14 MFMAs before their use.  (hipcc waits
+        // for them with lgkmcnt(0), which also waits for every younger read: reads issued ahead of those 2 MFMAs
+        // would be waited for in full before the sub-step could start.)  The barrier closes
+        // sub-step 2 (the last reads of the stage and the next stage's DMA have landed); sub-step 3 runs after it,
+        // together with the next K-step's sub-step-0 reads and the DMA of the stage after that into the buffer
+        // the barrier has just released.  Every accumulator sees the same k order as the other bodies.
+        struct Frag {
+            f32x4 a[2], b[2];
+        };
+        auto ldfrag = [&](Frag &f, int stage, int s) {
+            const float *As = lds[stage][0];
+            const float *Bs = lds[stage][1];
+            const int ch = 2 * s + h; // the two lane halves take alternate 16-B chunks (same k permutation for A and B)
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    ra[i] = load_chunk<ALIGNED>(a.X, st_xrow[i], a.D, k0 + st_ch[i] * 4);
-                    rb[i] = load_chunk<ALIGNED>(a.Q, st_qrow[i], a.D, k0 + st_ch[i] * 4);
-                }
+            for (int t = 0; t < 2; t++) {
+                f.a[t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, ch)]);
+                f.b[t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, ch)]);
             }
-        }
-        const float *As = lds[cur][0];
-        const float *Bs = lds[cur][1];
-        if (SPLIT == 2) {
-            // split in registers (as gemm_filter_narrow_kernel<.., SPLIT>): the LDS image is plain f32; MFMA k-step ks
-            // covers floats [16 ks, 16 ks + 16) of the K-step, lane half h supplies 8 of them = two 16-B chunks
-#pragma unroll
-            for (int ks = 0; ks < 2; ks++) {
-                const int ch = 4 * ks + 2 * h;
-                bf16x8 ah[2], al[2], bh[2], bl[2];
-#pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    const int ra_ = wr * 64 + t * 32 + l31, rb_ = wc * 64 + t * 32 + l31;
-                    const f32x4 a0 = *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, ch)]), a1 = *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, ch + 1)]);
-                    const f32x4 b0 = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, ch)]), b1 = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, ch + 1)]);
-                    const float xa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                    const float xb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                    for (int i = 0; i < 8; i++) {
-                        const __bf16 ha = (__bf16)xa[i], hb = (__bf16)xb[i];
-                        ah[t][i] = ha;
-                        al[t][i] = (__bf16)(xa[i] - (float)ha);
-                        bh[t][i] = hb;
-                        bl[t][i] = (__bf16)(xb[i] - (float)hb);
-                    }
-                }
-#pragma unroll
-                for (int tm = 0; tm < 2; tm++)
-#pragma unroll
-                    for (int tn = 0; tn < 2; tn++) {
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh[tn], acc[tm][tn], 0, 0, 0);
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl[tn], acc[tm][tn], 0, 0, 0);
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh[tn], acc[tm][tn], 0, 0, 0);
-                    }
-            }
-        } else if (SPLIT == 1) {
-            // a row's 128-B piece = two 16-k groups of [hi 32 B | lo 32 B]: for the 16-k step ks, lane half h supplies
-            // k = 8h .. 8h+7 of it: chunk 4 ks + h (hi) and 4 ks + 2 + h (lo)
-            bf16x8 ah[2][2], al[2][2], bh[2][2], bl[2][2]; // [buffer][tile]
-            auto ldfrag = [&](int buf, int ks) {
-                const int kb = 4 * ks + h;
-#pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    const int ra_ = wr * 64 + t * 32 + l31, rb_ = wc * 64 + t * 32 + l31;
-                    ah[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, kb)]));
-                    al[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, 2 + kb)]));
-                    bh[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, kb)]));
-                    bl[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, 2 + kb)]));
-                }
-            };
-            ldfrag(0, 0);
-#pragma unroll
-            for (int ks = 0; ks < 2; ks++) {
-                const int cb = ks & 1;
-                if (ks < 1) ldfrag(cb ^ 1, ks + 1);
-#pragma unroll
-                for (int tm = 0; tm < 2; tm++)
-#pragma unroll
-                    for (int tn = 0; tn < 2; tn++) {
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cb][tm], bh[cb][tn], acc[tm][tn], 0, 0, 0);
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cb][tm], bl[cb][tn], acc[tm][tn], 0, 0, 0);
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cb][tm], bh[cb][tn], acc[tm][tn], 0, 0, 0);
-                    }
-            }
-        } else {
-        f32x4 fa[2][2], fb[2][2];
-#pragma unroll
-        for (int t = 0; t < 2; t++) {
-            fa[0][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, h)]);
-            fb[0][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, h)]);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; s++) {
-            const int cb = s & 1, nb = cb ^ 1;
-            if (s < 3) {
-                const int ch = 2 * (s + 1) + h; // the two lane halves take alternate 16-B chunks;
-                                                // the same k permutation is applied to A and B.
-#pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    fa[nb][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, ch)]);
-                    fb[nb][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, ch)]);
-                }
-            }
+        };
+        auto mfma16 = [&](const Frag &f) {
 #pragma unroll
             for (int e = 0; e < 4; e++)
 #pragma unroll
                 for (int tm = 0; tm < 2; tm++)
 #pragma unroll
                     for (int tn = 0; tn < 2; tn++)
-                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cb][tm][e], fb[cb][tn][e],
-                                                                          acc[tm][tn], 0, 0, 0);
-            if (!GLDS && s == 1 && has_next) {
-                const int nxt = cur ^ 1;
+                        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tm][e], f.b[tn][e], acc[tm][tn], 0, 0, 0);
+        };
+        Frag F0, F1;
+        // sub-steps 0-2 of a K-step (F0 holds sub-step 0's fragments on entry, F1 holds sub-step 3's on exit)
+        auto steps012 = [&](int cur) {
+            ldfrag(F1, cur, 1);
+            mfma16(F0);
+            ldfrag(F0, cur, 2);
+            mfma16(F1);
+            ldfrag(F1, cur, 3);
+            mfma16(F0);
 #pragma unroll
-                for (int i = 0; i < 4; i++) {
-                    *reinterpret_cast<f32x4 *>(&lds[nxt][0][swz_off(st_row[i], st_ch[i])]) = ra[i];
-                    *reinterpret_cast<f32x4 *>(&lds[nxt][1][swz_off(st_row[i], st_ch[i])]) = rb[i];
+            for (int s = 0; s < 3; s++) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); // MFMA: sub-step s
+                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0); // DS_READ: sub-step s+1's fragments
+                __builtin_amdgcn_sched_group_barrier(0x008, 14, 0); // MFMA: sub-step s
+            }
+            __builtin_amdgcn_sched_barrier(0); // sub-step 2's MFMAs stay in front of the barrier
+        };
+        ldfrag(F0, 0, 0);
+        if (nk > 1) glds_stage(1, BK);
+        int kt = 0;
+        for (; kt + 2 < nk; kt++) {
+            const int cur = kt & 1;
+            steps012(cur);
+            __syncthreads();
+            // sub-step 3 + the next K-step's sub-step-0 reads + the 8 pieces of stage kt+2 (into the buffer the
+            // barrier has just released), one piece after every other MFMA; the pieces land before the next barrier
+            const int k0 = (kt + 2) * BK;
+            ldfrag(F0, cur ^ 1, 0);
+#pragma unroll
+            for (int p = 0; p < 8; p++) glds_piece(p, cur, k0);
+            mfma16(F1);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0); // DS_READ
+#pragma unroll
+            for (int p = 0; p < 7; p++) {
+                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); // VMEM_READ (global_load_lds)
+                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); // MFMA
+            }
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0); // VMEM_READ
+        }
+        if (kt + 1 < nk) { // the last K-step but one: nothing left to stage
+            const int cur = kt & 1;
+            steps012(cur);
+            __syncthreads();
+            ldfrag(F0, cur ^ 1, 0);
+            mfma16(F1);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0); // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x100, 4, 0); // DS_READ
+            __builtin_amdgcn_sched_group_barrier(0x008, 14, 0); // MFMA
+            kt++;
+        }
+        // the last K-step: no barrier, LDS is not written again
+        steps012(kt & 1);
+        mfma16(F1);
+    } else {
+        // Main loop.  Per K-step (BK = 32): the next stage's global loads are issued first, the
+        // fragment reads of sub-step s+1 are issued before the 16 MFMAs of sub-step s (register
+        // double buffer), and the LDS write of the next stage happens in the middle of the MFMA
+        // stream (its target buffer was released by the barrier that ended the previous K-step), so
+        // the only serial section left at the end of a K-step is the barrier itself.
+        for (int kt = 0; kt < nk; kt++) {
+            const int cur = kt & 1;
+            const bool has_next = kt + 1 < nk;
+            if (has_next) {
+                const int k0 = (kt + 1) * BK;
+                if (GLDS) {
+                    glds_stage(cur ^ 1, k0);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; i++) {
+                        ra[i] = load_chunk<ALIGNED>(a.X, st_xrow[i], a.D, k0 + st_ch[i] * 4);
+                        rb[i] = load_chunk<ALIGNED>(a.Q, st_qrow[i], a.D, k0 + st_ch[i] * 4);
+                    }
                 }
             }
+            const float *As = lds[cur][0];
+            const float *Bs = lds[cur][1];
+            if (SPLIT == 2) {
+                // split in registers (as gemm_filter_narrow_kernel<.., SPLIT>): the LDS image is plain f32; MFMA k-step ks
+                // covers floats [16 ks, 16 ks + 16) of the K-step, lane half h supplies 8 of them = two 16-B chunks
+#pragma unroll
+                for (int ks = 0; ks < 2; ks++) {
+                    const int ch = 4 * ks + 2 * h;
+                    bf16x8 ah[2], al[2], bh[2], bl[2];
+#pragma unroll
+                    for (int t = 0; t < 2; t++) {
+                        const int ra_ = wr * 64 + t * 32 + l31, rb_ = wc * 64 + t * 32 + l31;
+                        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, ch)]), a1 = *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, ch + 1)]);
+                        const f32x4 b0 = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, ch)]), b1 = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, ch + 1)]);
+                        const float xa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                        const float xb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+                        for (int i = 0; i < 8; i++) {
+                            const __bf16 ha = (__bf16)xa[i], hb = (__bf16)xb[i];
+                            ah[t][i] = ha;
+                            al[t][i] = (__bf16)(xa[i] - (float)ha);
+                            bh[t][i] = hb;
+                            bl[t][i] = (__bf16)(xb[i] - (float)hb);
+                        }
+                    }
+#pragma unroll
+                    for (int tm = 0; tm < 2; tm++)
+#pragma unroll
+                        for (int tn = 0; tn < 2; tn++) {
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh[tn], acc[tm][tn], 0, 0, 0);
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl[tn], acc[tm][tn], 0, 0, 0);
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh[tn], acc[tm][tn], 0, 0, 0);
+                        }
+                }
+            } else if (SPLIT == 1) {
+                // a row's 128-B piece = two 16-k groups of [hi 32 B | lo 32 B]: for the 16-k step ks, lane half h supplies
+                // k = 8h .. 8h+7 of it: chunk 4 ks + h (hi) and 4 ks + 2 + h (lo)
+                bf16x8 ah[2][2], al[2][2], bh[2][2], bl[2][2]; // [buffer][tile]
+                auto ldfrag = [&](int buf, int ks) {
+                    const int kb = 4 * ks + h;
+#pragma unroll
+                    for (int t = 0; t < 2; t++) {
+                        const int ra_ = wr * 64 + t * 32 + l31, rb_ = wc * 64 + t * 32 + l31;
+                        ah[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, kb)]));
+                        al[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, 2 + kb)]));
+                        bh[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, kb)]));
+                        bl[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, 2 + kb)]));
+                    }
+                };
+                ldfrag(0, 0);
+#pragma unroll
+                for (int ks = 0; ks < 2; ks++) {
+                    const int cb = ks & 1;
+                    if (ks < 1) ldfrag(cb ^ 1, ks + 1);
+#pragma unroll
+                    for (int tm = 0; tm < 2; tm++)
+#pragma unroll
+                        for (int tn = 0; tn < 2; tn++) {
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cb][tm], bh[cb][tn], acc[tm][tn], 0, 0, 0);
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cb][tm], bl[cb][tn], acc[tm][tn], 0, 0, 0);
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cb][tm], bh[cb][tn], acc[tm][tn], 0, 0, 0);
+                        }
+                }
+            } else {
+                f32x4 fa[2][2], fb[2][2];
+#pragma unroll
+                for (int t = 0; t < 2; t++) {
+                    fa[0][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, h)]);
+                    fb[0][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, h)]);
+                }
+#pragma unroll
+                for (int s = 0; s < 4; s++) {
+                    const int cb = s & 1, nb = cb ^ 1;
+                    if (s < 3) {
+                        const int ch = 2 * (s + 1) + h; // the two lane halves take alternate 16-B chunks;
+                                                        // the same k permutation is applied to A and B.
+#pragma unroll
+                        for (int t = 0; t < 2; t++) {
+                            fa[nb][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, ch)]);
+                            fb[nb][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, ch)]);
+                        }
+                    }
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+#pragma unroll
+                        for (int tm = 0; tm < 2; tm++)
+#pragma unroll
+                            for (int tn = 0; tn < 2; tn++)
+                                acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cb][tm][e], fb[cb][tn][e],
+                                                                                  acc[tm][tn], 0, 0, 0);
+                    if (!GLDS && s == 1 && has_next) {
+                        const int nxt = cur ^ 1;
+#pragma unroll
+                        for (int i = 0; i < 4; i++) {
+                            *reinterpret_cast<f32x4 *>(&lds[nxt][0][swz_off(st_row[i], st_ch[i])]) = ra[i];
+                            *reinterpret_cast<f32x4 *>(&lds[nxt][1][swz_off(st_row[i], st_ch[i])]) = rb[i];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
         }
-        }
-        __syncthreads();
     }
 
     // ---- epilogue: key + admission -------------------------------------------------
