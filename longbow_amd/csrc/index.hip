@@ -594,7 +594,7 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
             }
             {
                 ProfScope p(w, s, prof, 1);
-                launch_select(w->cs, use_sel, gn, kkeep, 0u, s, false, (uint32_t)kkeep, sp.span >= n ? &em : nullptr,
+                launch_select(w->cs, use_sel, gn, kkeep, 0u, s, (uint32_t)kkeep, sp.span >= n ? &em : nullptr,
                               /*striped=*/true);
             }
             pos = sp.span;
@@ -621,7 +621,7 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
             }
             {
                 ProfScope p(w, s, prof, 1);
-                launch_select(w->cs, use_sel, gn, kkeep, boot ? (uint32_t)(end - pos) : 0u, s, false, 0u,
+                launch_select(w->cs, use_sel, gn, kkeep, boot ? (uint32_t)(end - pos) : 0u, s, 0u,
                               end >= n ? &em : nullptr);
             }
             emitted = end >= n;
@@ -693,8 +693,7 @@ void scan_with_retry(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *
 //                        corpus split in registers (split 2)
 //   TALL16 / NARROW16    ONE fp16 product per element (kernels_gemm_tall16.hip): 256 x 256 tiles, or one 64- / 128-query
 //                        tile over the index's fp16 image (persistent workgroups, LDS-DMA ring)
-//   WIDE                 128 x 128 tile (kernels_gemm.hip): f32 MFMA (split 0: the strict mode's route beyond 384
-//                        queries), or the split contraction where the tall tiles cannot run
+//   WIDE                 128 x 128 tile (kernels_gemm.hip): f32 MFMA (split 0), the strict mode's route beyond 384 queries
 // Candidate modes (lb_gpu_index_set_candidate_mode):
 //   LB_CAND_AUTO (default)    the cheapest route by the cost model below -- with the fp16 image that is the single-product
 //                             route at every batch size, the split contraction where the data's range rules fp16 keys out
@@ -882,7 +881,7 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
     {
         ProfScope p(w, s, prof, 1);
         const EmitArgs em{k, h->has_ids ? h->d_ids : nullptr, d_dist, d_lab, w->h_flags};
-        launch_select(w->cs, nullptr, nq, kkeep, 0u, s, false, (uint32_t)kkeep, &em);
+        launch_select(w->cs, nullptr, nq, kkeep, 0u, s, (uint32_t)kkeep, &em);
     }
     std::vector<int> redo;
     if (collect_flagged(w, s, nq, 1u | 4u, nullptr, 0, redo, true) > 0)
@@ -1082,7 +1081,7 @@ int run_batch(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float 
                                       w->cs, boot, s, tile64);
         else if (use_tall16 && h->dim % 32 != 0 && (rowmap || mask) && !entries_pos)
             // the sample of a search over the fp16 copy when the dimension is not a multiple of 32: the f32 tile takes any
-            launch_gemm_filter(metric, h->d_X, h->d_norm2, h->d_rnorm, b, e, h->dim, d_q, nq, mask, rowmap, w->cs, boot, 0, s);
+            launch_gemm_filter(metric, h->d_X, h->d_norm2, h->d_rnorm, b, e, h->dim, d_q, nq, mask, rowmap, w->cs, boot, s);
         else if (boot && (wsplit == 2 || wsplit == 3) && narrow_ok && !entries_pos && !own_keys &&
                  !(use_tall16 && nq > sample_narrow_maxq))
             // the 8192-row sample of a tall-tile search: the 64-query tile of the narrow kernel (same contraction, f32
@@ -1099,8 +1098,7 @@ int run_batch(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float 
             launch_gemm_filter_tall2(metric, gx, h->d_norm2, h->d_rnorm, b, e, h->dim, w->d_qs, nq, mask, rowmap, w->cs,
                                      boot, wsplit, s);
         else
-            launch_gemm_filter(metric, gx, h->d_norm2, h->d_rnorm, b, e, h->dim, gq, nq, mask, rowmap, w->cs,
-                               boot, wsplit, s);
+            launch_gemm_filter(metric, gx, h->d_norm2, h->d_rnorm, b, e, h->dim, gq, nq, mask, rowmap, w->cs, boot, s);
     };
     int64_t pos = 0;
     int step = 0;
@@ -1150,7 +1148,7 @@ int run_batch(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float 
         // (one span covers the view: the finish launch prunes the raw list itself -- everything below tau is in it)
         if (sp.span < n) {
             ProfScope p(w, s, prof, 1);
-            launch_select(w->cs, nullptr, nq, kc, 0u, s, false, (uint32_t)kc, nullptr, false, /*unsorted=*/true);
+            launch_select(w->cs, nullptr, nq, kc, 0u, s, (uint32_t)kc, nullptr, false, /*unsorted=*/true);
         }
         pos = sp.span;
         step = 1;
@@ -1161,7 +1159,7 @@ int run_batch(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float 
         candidates(pos, end, rv.rowmap, boot);
         {
             ProfScope p(w, s, prof, 1);
-            launch_select(w->cs, nullptr, nq, kc, boot ? (uint32_t)(end - pos) : 0u, s, false, 0u, nullptr, false, /*unsorted=*/true);
+            launch_select(w->cs, nullptr, nq, kc, boot ? (uint32_t)(end - pos) : 0u, s, 0u, nullptr, false, /*unsorted=*/true);
         }
         pos = end;
         step++;

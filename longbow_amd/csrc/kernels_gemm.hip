@@ -68,12 +68,7 @@ __device__ __forceinline__ f32x4 load_chunk(const float *base, int64_t row, int 
 // ALIGNED == 2 (GLDS): stage tiles with direct-to-LDS DMA loads (global_load_lds_dwordx4); the other modes stage through registers.
 // The LDS image is lane-linear per wave instruction (base + lane*16), so the chunk swizzle is
 // applied to the per-lane SOURCE address; the image is identical to the register-staged one.
-// SPLIT: X and Q are the split-bf16 images produced by split_bf16_kernel: per row and group of 16
-// k, 32 B of bf16 "hi" values followed by 32 B of bf16 "lo" values (x ~ hi + lo, |x-hi-lo| <=
-// 2^-18|x|).  The inner product is then hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 (exact
-// bf16 products, f32 accumulation): ~f32-accurate candidate keys at 3/16 of the f32 MFMA cycles.
-// Staging, LDS image and epilogue are shared with the f32 kernel (same bytes per row and K-step).
-template <int METRIC, int ALIGNED, int SPLIT = 0>
+template <int METRIC, int ALIGNED>
 __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a)
 {
     constexpr bool GLDS = ALIGNED == 2;
@@ -179,9 +174,6 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
 #pragma unroll
         for (int p = 0; p < 8; p++) glds_piece(p, stage, k0);
     };
-    // the f32 GLDS tile (WIDE) runs its own K-loop below
-    constexpr bool WIDE = GLDS && SPLIT == 0;
-
     // prologue: stage 0
     if (GLDS) glds_stage(0, 0);
     // one burst behind the DMA: side inputs of tile row (tid & 127) and this lane's two thresholds; nothing
@@ -222,7 +214,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
     }
     __syncthreads();
 
-    if constexpr (WIDE) {
+    if constexpr (GLDS) {
         // Main loop of the f32 GLDS tile, rotated by one sub-step so that no LDS or DMA issue sits outside the
         // MFMA stream.  A K-step is 4 sub-steps of 16 MFMAs (2 k per MFMA, lane halves on alternate 16-B chunks).
         // Two named fragment sets alternate: F0 feeds sub-steps 0 and 2, F1 sub-steps 1 and 3, and the reads of
@@ -231,7 +223,7 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
         // would be waited for in full before the sub-step could start.)  The barrier closes
         // sub-step 2 (the last reads of the stage and the next stage's DMA have landed); sub-step 3 runs after it,
         // together with the next K-step's sub-step-0 reads and the DMA of the stage after that into the buffer
-        // the barrier has just released.  Every accumulator sees the same k order as the other bodies.
+        // the barrier has just released.  Every accumulator sees the same k order as in the register-staged loop.
         struct Frag {
             f32x4 a[2], b[2];
         };
@@ -309,9 +301,9 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
         steps012(kt & 1);
         mfma16(F1);
     } else {
-        // Main loop.  Per K-step (BK = 32): the next stage's global loads are issued first, the
-        // fragment reads of sub-step s+1 are issued before the 16 MFMAs of sub-step s (register
-        // double buffer), and the LDS write of the next stage happens in the middle of the MFMA
+        // Main loop of the register-staged tiles.  Per K-step (BK = 32): the next stage's global loads are
+        // issued first, the fragment reads of sub-step s+1 are issued before the 16 MFMAs of sub-step s
+        // (register double buffer), and the LDS write of the next stage happens in the middle of the MFMA
         // stream (its target buffer was released by the barrier that ended the previous K-step), so
         // the only serial section left at the end of a K-step is the barrier itself.
         for (int kt = 0; kt < nk; kt++) {
@@ -319,113 +311,46 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
             const bool has_next = kt + 1 < nk;
             if (has_next) {
                 const int k0 = (kt + 1) * BK;
-                if (GLDS) {
-                    glds_stage(cur ^ 1, k0);
-                } else {
 #pragma unroll
-                    for (int i = 0; i < 4; i++) {
-                        ra[i] = load_chunk<ALIGNED>(a.X, st_xrow[i], a.D, k0 + st_ch[i] * 4);
-                        rb[i] = load_chunk<ALIGNED>(a.Q, st_qrow[i], a.D, k0 + st_ch[i] * 4);
-                    }
+                for (int i = 0; i < 4; i++) {
+                    ra[i] = load_chunk<ALIGNED>(a.X, st_xrow[i], a.D, k0 + st_ch[i] * 4);
+                    rb[i] = load_chunk<ALIGNED>(a.Q, st_qrow[i], a.D, k0 + st_ch[i] * 4);
                 }
             }
             const float *As = lds[cur][0];
             const float *Bs = lds[cur][1];
-            if (SPLIT == 2) {
-                // split in registers (as gemm_filter_narrow_kernel<.., SPLIT>): the LDS image is plain f32; MFMA k-step ks
-                // covers floats [16 ks, 16 ks + 16) of the K-step, lane half h supplies 8 of them = two 16-B chunks
+            f32x4 fa[2][2], fb[2][2];
 #pragma unroll
-                for (int ks = 0; ks < 2; ks++) {
-                    const int ch = 4 * ks + 2 * h;
-                    bf16x8 ah[2], al[2], bh[2], bl[2];
+            for (int t = 0; t < 2; t++) {
+                fa[0][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, h)]);
+                fb[0][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, h)]);
+            }
+#pragma unroll
+            for (int s = 0; s < 4; s++) {
+                const int cb = s & 1, nb = cb ^ 1;
+                if (s < 3) {
+                    const int ch = 2 * (s + 1) + h; // the two lane halves take alternate 16-B chunks;
+                                                    // the same k permutation is applied to A and B.
 #pragma unroll
                     for (int t = 0; t < 2; t++) {
-                        const int ra_ = wr * 64 + t * 32 + l31, rb_ = wc * 64 + t * 32 + l31;
-                        const f32x4 a0 = *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, ch)]), a1 = *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, ch + 1)]);
-                        const f32x4 b0 = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, ch)]), b1 = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, ch + 1)]);
-                        const float xa[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
-                        const float xb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
-#pragma unroll
-                        for (int i = 0; i < 8; i++) {
-                            const __bf16 ha = (__bf16)xa[i], hb = (__bf16)xb[i];
-                            ah[t][i] = ha;
-                            al[t][i] = (__bf16)(xa[i] - (float)ha);
-                            bh[t][i] = hb;
-                            bl[t][i] = (__bf16)(xb[i] - (float)hb);
-                        }
+                        fa[nb][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, ch)]);
+                        fb[nb][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, ch)]);
                     }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; e++)
 #pragma unroll
                     for (int tm = 0; tm < 2; tm++)
 #pragma unroll
-                        for (int tn = 0; tn < 2; tn++) {
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[tm], bh[tn], acc[tm][tn], 0, 0, 0);
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bl[tn], acc[tm][tn], 0, 0, 0);
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[tm], bh[tn], acc[tm][tn], 0, 0, 0);
-                        }
-                }
-            } else if (SPLIT == 1) {
-                // a row's 128-B piece = two 16-k groups of [hi 32 B | lo 32 B]: for the 16-k step ks, lane half h supplies
-                // k = 8h .. 8h+7 of it: chunk 4 ks + h (hi) and 4 ks + 2 + h (lo)
-                bf16x8 ah[2][2], al[2][2], bh[2][2], bl[2][2]; // [buffer][tile]
-                auto ldfrag = [&](int buf, int ks) {
-                    const int kb = 4 * ks + h;
+                        for (int tn = 0; tn < 2; tn++)
+                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cb][tm][e], fb[cb][tn][e],
+                                                                              acc[tm][tn], 0, 0, 0);
+                if (s == 1 && has_next) {
+                    const int nxt = cur ^ 1;
 #pragma unroll
-                    for (int t = 0; t < 2; t++) {
-                        const int ra_ = wr * 64 + t * 32 + l31, rb_ = wc * 64 + t * 32 + l31;
-                        ah[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, kb)]));
-                        al[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&As[swz_off(ra_, 2 + kb)]));
-                        bh[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, kb)]));
-                        bl[buf][t] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const f32x4 *>(&Bs[swz_off(rb_, 2 + kb)]));
-                    }
-                };
-                ldfrag(0, 0);
-#pragma unroll
-                for (int ks = 0; ks < 2; ks++) {
-                    const int cb = ks & 1;
-                    if (ks < 1) ldfrag(cb ^ 1, ks + 1);
-#pragma unroll
-                    for (int tm = 0; tm < 2; tm++)
-#pragma unroll
-                        for (int tn = 0; tn < 2; tn++) {
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[cb][tm], bh[cb][tn], acc[tm][tn], 0, 0, 0);
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cb][tm], bl[cb][tn], acc[tm][tn], 0, 0, 0);
-                            acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[cb][tm], bh[cb][tn], acc[tm][tn], 0, 0, 0);
-                        }
-                }
-            } else {
-                f32x4 fa[2][2], fb[2][2];
-#pragma unroll
-                for (int t = 0; t < 2; t++) {
-                    fa[0][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, h)]);
-                    fb[0][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, h)]);
-                }
-#pragma unroll
-                for (int s = 0; s < 4; s++) {
-                    const int cb = s & 1, nb = cb ^ 1;
-                    if (s < 3) {
-                        const int ch = 2 * (s + 1) + h; // the two lane halves take alternate 16-B chunks;
-                                                        // the same k permutation is applied to A and B.
-#pragma unroll
-                        for (int t = 0; t < 2; t++) {
-                            fa[nb][t] = *reinterpret_cast<const f32x4 *>(&As[swz_off(wr * 64 + t * 32 + l31, ch)]);
-                            fb[nb][t] = *reinterpret_cast<const f32x4 *>(&Bs[swz_off(wc * 64 + t * 32 + l31, ch)]);
-                        }
-                    }
-#pragma unroll
-                    for (int e = 0; e < 4; e++)
-#pragma unroll
-                        for (int tm = 0; tm < 2; tm++)
-#pragma unroll
-                            for (int tn = 0; tn < 2; tn++)
-                                acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[cb][tm][e], fb[cb][tn][e],
-                                                                                  acc[tm][tn], 0, 0, 0);
-                    if (!GLDS && s == 1 && has_next) {
-                        const int nxt = cur ^ 1;
-#pragma unroll
-                        for (int i = 0; i < 4; i++) {
-                            *reinterpret_cast<f32x4 *>(&lds[nxt][0][swz_off(st_row[i], st_ch[i])]) = ra[i];
-                            *reinterpret_cast<f32x4 *>(&lds[nxt][1][swz_off(st_row[i], st_ch[i])]) = rb[i];
-                        }
+                    for (int i = 0; i < 4; i++) {
+                        *reinterpret_cast<f32x4 *>(&lds[nxt][0][swz_off(st_row[i], st_ch[i])]) = ra[i];
+                        *reinterpret_cast<f32x4 *>(&lds[nxt][1][swz_off(st_row[i], st_ch[i])]) = rb[i];
                     }
                 }
             }
@@ -533,8 +458,7 @@ void launch_split_bf16(const float *src, float *dst, int64_t rows, int D, hipStr
 
 void launch_gemm_filter(int metric, const float *X, const float *norm2, const float *rnorm,
                         int64_t row_begin, int64_t row_end, int D, const float *Q, int nq,
-                        const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot, int split,
-                        hipStream_t s)
+                        const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot, hipStream_t s)
 {
     if (row_end <= row_begin || nq <= 0) return;
     GemmArgs a;
@@ -550,20 +474,6 @@ void launch_gemm_filter(int metric, const float *X, const float *norm2, const fl
     const bool aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
                          ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
     const int mode = !aligned ? 0 : (D % BK == 0 ? 2 : 1);
-    if (split == 1) {
-        // X / Q are split-bf16 images (caller guarantees D % 32 == 0 and 16-B alignment)
-        if (metric == METRIC_L2) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_L2, 2, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else if (metric == METRIC_COS) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((gemm_filter_kernel<METRIC_DOT, 2, 1>), grid, dim3(GEMM_THREADS), 0, s, a);
-        return;
-    }
-    if (split == 2) {
-        // X / Q are the plain f32 operands, split in registers (D % 32 == 0, 16-B aligned)
-        if (metric == METRIC_L2) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_L2, 2, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else if (metric == METRIC_COS) hipLaunchKernelGGL((gemm_filter_kernel<METRIC_COS, 2, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
-        else hipLaunchKernelGGL((gemm_filter_kernel<METRIC_DOT, 2, 2>), grid, dim3(GEMM_THREADS), 0, s, a);
-        return;
-    }
 #define LB_GEMM(M, AL) hipLaunchKernelGGL((gemm_filter_kernel<M, AL>), grid, dim3(GEMM_THREADS), 0, s, a)
 #define LB_GEMM_M(M)                 \
     do {                             \

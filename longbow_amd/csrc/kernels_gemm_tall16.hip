@@ -47,14 +47,11 @@ constexpr int H_BM = 256, H_BN = 256, H_BK = 32;
 // K-steps of a plane taking half each) was built for row lists -- HBM is fetched in whole lines, so a filtered view pays for
 // the neighbouring row's half -- and measured (round 4, 1.25M x 1536, 10 % visible): the gather pass 119 -> 94 us at 32
 // queries, 234 -> 216 at 256, but the UNFILTERED stream 234 -> 339 us per 1M x 768 (half-line requests under the
-// non-temporal policy fetch every line twice).  Not worth it: 32 stays; -DLB_XH_PLANE=64 rebuilds the other.
-#ifndef LB_XH_PLANE
-#define LB_XH_PLANE 32
-#endif
-constexpr int H_XP = LB_XH_PLANE, H_XROW = H_XP * 2, H_KPP = H_XP / H_BK; // plane dims, bytes of a row's piece, K-steps per plane
+// non-temporal policy fetch every line twice).  Not worth it: 32 stays.
+constexpr int H_XP = 32, H_XROW = H_XP * 2; // plane dims (one plane per K-step), bytes of a row's piece
 __device__ __forceinline__ int64_t h_xoff(int ke, int64_t plane_bytes) // byte offset of K-step ke within a row's pieces
 {
-    return H_KPP == 1 ? ke * plane_bytes : (int64_t)(ke / H_KPP) * plane_bytes + (ke % H_KPP) * (H_BK * 2);
+    return ke * plane_bytes;
 }
 constexpr int H_THREADS = 512;
 constexpr int H_A_BYTES = H_BM * H_BK * 4;            // 32 KB: corpus rows as f32
@@ -393,6 +390,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16_kernel(Tall16
 template <int METRIC, bool NT, bool AIMG, bool BOOT, bool MAPPED = false>
 __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall16Args a, int spx)
 {
+    static_assert(!MAPPED || AIMG, "a row list is gathered out of the image only");
     constexpr int NST = AIMG ? 4 : 3;                       // ring stages
     constexpr int A_BYTES = AIMG ? H_BM * H_BK * 2 : H_A_BYTES;
     constexpr int STAGE = A_BYTES + H_B_BYTES;
@@ -459,8 +457,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
             const int c = AIMG ? (lane & 3) ^ ((row >> 2) & 3) : (lane & 7) ^ ((row >> 1) & 7);
             if (MAPPED) {
                 const int64_t rid = (int64_t)s_rowid[(t % 3) * 512 + row];
-                srcA[i] = AIMG ? reinterpret_cast<const unsigned char *>(a.Xh) + rid * H_XROW + 16 * c
-                               : reinterpret_cast<const unsigned char *>(a.X) + rid * row_bytes + 16 * c;
+                srcA[i] = reinterpret_cast<const unsigned char *>(a.Xh) + rid * H_XROW + 16 * c;
             } else {
                 uint32_t pos = rt + (uint32_t)row;
                 if (pos > last_pos) pos = last_pos;
@@ -780,11 +777,11 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_tall16p_kernel(Tall1
     wait_vmcnt<0>(); // the re-read stages behind the last tile: nothing may land in LDS after the workgroup has gone
 }
 
-// ---- up to 256 queries (one query tile) over the corpus's fp16 image: the pass is the image's HBM stream ---------------------
-// Same persistent pipeline, tile 256 rows x BN queries (64, 128 or 256): a wave owns 32 rows x BN queries (BN / 32 MFMA
+// ---- up to 128 queries (one query tile) over the corpus's fp16 image: the pass is the image's HBM stream ---------------------
+// Same persistent pipeline, tile 256 rows x BN queries (64 or 128): a wave owns 32 rows x BN queries (BN / 32 MFMA
 // tiles), stages exactly the corpus rows it consumes (2 requests per stage) and an eighth of the query tile (half a request
-// at BN = 64 -- lanes 0 .. 31 --, one at 128, two at 256); a stage is 16 KB + 4 / 8 / 16 KB, the ring SIX / FIVE / FOUR stages
-// deep (48-80 KB of corpus in flight per CU), loads non-temporal (every line is read once).  1M x 768: the image is 1.5 GB,
+// at BN = 64 -- lanes 0 .. 31 --, one at 128); a stage is 16 KB + 4 / 8 KB, the ring SIX / FIVE stages
+// deep (64-80 KB of corpus in flight per CU), loads non-temporal (every line is read once).  1M x 768: the image is 1.5 GB,
 // the pass 0.24-0.3 ms where the f32 rows take 0.49.
 // MAPPED: the positions index a.rowmap (the visible rows of a filtered view, ascending) -- the kernel gathers: the row ids of a
 // tile come in by their own LDS-DMA request one tile ahead of the request cursor (a ring of three tiles: a plain load inside
@@ -918,11 +915,10 @@ __device__ __forceinline__ void tin_duty(const Tall16Args &a, int j, unsigned ch
 template <int METRIC, int BN, bool BOOT, bool MAPPED, bool TAUIN = false>
 __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tall16Args a, int spx)
 {
+    static_assert(BN == 64 || BN == 128, "the 64- and 128-query tiles");
     constexpr int TN = BN / 32;
-    constexpr int NST = BN == 64 ? 6 : (BN == 128 ? 5 : 4), A_BYTES = H_BM * H_BK * 2, B_BYTES = BN * H_BK * 2, STAGE = A_BYTES + B_BYTES;
-    constexpr int NPB = BN == 256 ? 2 : 1; // query requests per wave and stage
-    constexpr int NPS = 2 + NPB, DIST = NST - 1, H1 = 2;
-    constexpr bool PIPE = BN != 256; // (at 256 queries there are no registers for a third set of fragments: barrier on top)
+    constexpr int NST = BN == 64 ? 6 : 5, A_BYTES = H_BM * H_BK * 2, B_BYTES = BN * H_BK * 2, STAGE = A_BYTES + B_BYTES;
+    constexpr int NPS = 3, DIST = NST - 1, H1 = 2; // requests per wave and stage: two of corpus, one of queries
     (void)spx;
     extern __shared__ __attribute__((aligned(16))) unsigned char hlds[];
     int bi = (int)blockIdx.x, ng = (int)gridDim.x;
@@ -984,7 +980,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
                        "s"(__builtin_amdgcn_readfirstlane((int)(rowid_base + (uint32_t)(t % 3) * 2048u + (uint32_t)wave * 256u))));
     };
 
-    const unsigned char *srcA[2], *srcB[NPB];
+    const unsigned char *srcA[2], *srcB;
     const unsigned char *Xhb = reinterpret_cast<const unsigned char *>(a.Xh) + a.row_begin * (int64_t)H_XROW;
     const int64_t plane_bytes = a.xh_cap * (int64_t)H_XROW;
     auto set_srcA = [&](int t) { // request sources of tile t
@@ -1003,13 +999,12 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
             }
         }
     };
-#pragma unroll
-    for (int j = 0; j < NPB; j++) {
-        // BN = 64: 8 query rows per wave, lanes 32 .. 63 do not take part in the request; 128: 16 rows; 256: 2 x 16 rows
-        const int row = BN == 64 ? wave * 8 + ((lane & 31) >> 2) : wave * (BN / 8) + j * 16 + (lane >> 2);
+    {
+        // BN = 64: 8 query rows per wave, lanes 32 .. 63 do not take part in the request; 128: 16 rows
+        const int row = BN == 64 ? wave * 8 + ((lane & 31) >> 2) : wave * (BN / 8) + (lane >> 2);
         const int c = (lane & 3) ^ ((row >> 2) & 3);
         const int qr = row > last_q ? last_q : row;
-        srcB[j] = reinterpret_cast<const unsigned char *>(a.Qh + (int64_t)qr * H_BK) + 16 * c;
+        srcB = reinterpret_cast<const unsigned char *>(a.Qh + (int64_t)qr * H_BK) + 16 * c;
     }
     const int64_t kb_stride = (int64_t)a.q_stride * (H_BK * 2);
     const int nk = (a.D + H_BK - 1) / H_BK; // (both images are zero-padded to a multiple of 32 dimensions)
@@ -1020,7 +1015,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
         const uint32_t A = ring_base + (uint32_t)islot * STAGE + (uint32_t)(wave * 32 * 64);
         const uint32_t B = ring_base + (uint32_t)islot * STAGE + A_BYTES + (uint32_t)(wave * (BN * 8));
         if (p < 2) lds_dma16_noclobber<true>(srcA[p] + h_xoff(ik, plane_bytes), A + 1024u * p);
-        else if (BN != 64 || lane < 32) lds_dma16_noclobber<false>(srcB[p - 2] + ik * kb_stride, B + 1024u * (p - 2));
+        else if (BN != 64 || lane < 32) lds_dma16_noclobber<false>(srcB + ik * kb_stride, B);
     };
     auto advance = [&]() {
         islot = islot == NST - 1 ? 0 : islot + 1;
@@ -1085,7 +1080,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
         tkc[tn] = METRIC != METRIC_COS ? tk : tk * scale;
     }
     // (what the ring leaves; MAPPED: 6 KB less, the row-id ring)
-    constexpr uint32_t WCAP = BN == 256 ? 272 : (MAPPED ? 296 : 360), WFLUSH = BN == 256 ? 176 : (MAPPED ? 200 : 240), SEG_BYTES = WCAP * 12;
+    constexpr uint32_t WCAP = MAPPED ? 296 : 360, WFLUSH = MAPPED ? 200 : 240, SEG_BYTES = WCAP * 12;
     uint32_t *s_flag = reinterpret_cast<uint32_t *>(s_auxp + 2 * 512 + (MAPPED ? 3 * 512 : 0)); // [3] "somebody wants a flush", by tile % 3 (see the 256-query form)
     uint32_t *s_qn = s_flag + 4, *s_qb = s_qn + 256;
     unsigned char *seg = reinterpret_cast<unsigned char *>(s_qb + 256) + wave * SEG_BYTES;
@@ -1108,12 +1103,10 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
 
     int cslot = 0;
     f16x8 a0, b0[TN];
-    if (PIPE) {
-        wait_vmcnt<NPS *(DIST - 1)>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        load_frag(0, 0, a0, b0);
-    }
+    wait_vmcnt<NPS *(DIST - 1)>();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    load_frag(0, 0, a0, b0);
     for (int i = 0; i < n_my; i++) {
         const uint32_t rt = rt_of(i);
         f32x16 acc[TN];
@@ -1123,36 +1116,28 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
             for (int r = 0; r < 16; r++) acc[y][r] = 0.f;
 
         for (int kt = 0; kt < nk; kt++) {
-            if (!PIPE) {
-                wait_vmcnt<NPS *(DIST - 1)>();
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                load_frag(cslot, 0, a0, b0);
-            }
             f16x8 a1, b1[TN];
-            if (PIPE) load_frag(cslot, 1, a1, b1);
+            load_frag(cslot, 1, a1, b1);
             if (cursor_new_tile) enter_tile();
             const bool aux_now = i + 1 < n_my && kt == (nk > 1 ? 1 : 0); // (see the 256-query form)
-            if (aux_now && !(PIPE && nk == 1)) aux_request(i + 1);
+            if (aux_now && nk != 1) aux_request(i + 1);
 #pragma unroll
             for (int tn = 0; tn < TN; tn++) {
                 acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a0, b0[tn], acc[tn], 0, 0, 0);
                 if (tn < 2) piece(tn);
             }
             const int nslot = cslot == NST - 1 ? 0 : cslot + 1;
-            if (!PIPE) load_frag(cslot, 1, a1, b1);
-            if (PIPE) { // middle of the step (see the 256-query form): reads of stage kt complete, stage kt + 1 landed, barrier
-                __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0)
-                wait_vmcnt<NPS *(DIST - 2) + H1>();
-                __builtin_amdgcn_s_barrier();
-                asm volatile("" ::: "memory");
-                if (aux_now && nk == 1) aux_request(i + 1);
-                load_frag(nslot, 0, a0, b0);
-            }
+            // middle of the step (see the 256-query form): reads of stage kt complete, stage kt + 1 landed, barrier
+            __builtin_amdgcn_s_waitcnt(0xc07f); // lgkmcnt(0)
+            wait_vmcnt<NPS *(DIST - 2) + H1>();
+            __builtin_amdgcn_s_barrier();
+            asm volatile("" ::: "memory");
+            if (aux_now && nk == 1) aux_request(i + 1);
+            load_frag(nslot, 0, a0, b0);
 #pragma unroll
             for (int tn = 0; tn < TN; tn++) {
                 acc[tn] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, b1[tn], acc[tn], 0, 0, 0);
-                if (tn < NPB) piece(2 + tn);
+                if (tn == 0) piece(2);
             }
             advance();
             cslot = nslot;
@@ -1163,7 +1148,7 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
         // than that stage: from three K-steps per tile on).  Requests newer than it by now: 2 NPS - H1 (+ 1) at one K-step per
         // tile (asked for in the middle of the step before), 3 NPS (+ 1) at two (at the top of the tile before's second step);
         // vmcnt retires in order, and the barrier publishes the other waves' parts.
-        if (PIPE && nk <= 2) {
+        if (nk <= 2) {
             if (nk == 1) wait_vmcnt<2 * NPS - H1>();
             else wait_vmcnt<3 * NPS>();
             __builtin_amdgcn_s_barrier();
@@ -1288,33 +1273,6 @@ __global__ __launch_bounds__(H_THREADS, 2) void gemm_filter_narrow16p_kernel(Tal
     wait_vmcnt<0>();
 }
 
-// f32 [nq][D] -> fp16 [D / 32][nq][32], each query scaled by the power of two that brings its norm into [1, 2); qinv[q] = 1 / scale.
-// One wave per query.  (A zero or non-finite query keeps scale 1: its search is answered by the exact scan anyway.)
-__global__ __launch_bounds__(256) void queries_to_f16_kernel(const float *Q, int nq, int D, _Float16 *Qh, float *qinv)
-{
-    const int lane = threadIdx.x & 63;
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (q >= nq) return;
-    const float *src = Q + (int64_t)q * D;
-    float s = 0.f;
-    for (int i = lane; i < D; i += 64) s += src[i] * src[i];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-    float scale = 1.f, inv = 1.f;
-    if (s > 0.f && s < 3.0e38f) {
-        const float nrm = sqrtf(s);
-        int e;
-        (void)frexpf(nrm, &e);       // nrm = m * 2^e, 0.5 <= m < 1  ->  nrm * 2^(1 - e) in [1, 2)
-        int sh = 1 - e;
-        sh = sh < -120 ? -120 : (sh > 120 ? 120 : sh);
-        scale = ldexpf(1.f, sh);
-        inv = ldexpf(1.f, -sh);
-    }
-    const int Dp = (D + 31) & ~31; // (dimensions beyond D: zero -- they add nothing to a product)
-    for (int i = lane; i < Dp; i += 64) Qh[((int64_t)(i >> 5) * nq + q) * 32 + (i & 31)] = i < D ? (_Float16)(src[i] * scale) : (_Float16)0.f;
-    if (lane == 0) qinv[q] = inv;
-}
-
 // corpus rows [row_begin, row_end) (f32, or fp16 on an fp16 index: a relayout, exact unless centred) -> the blocked fp16 image Xh[Dp / H_XP][cap][H_XP] (round to nearest even, the conversion
 // the kernels above apply in registers: both forms of the route see the same fp16 values; dimensions beyond D are zero).
 // One workgroup = 64 rows x 32 dimensions: whole 128-B lines in, 64-B pieces out.
@@ -1409,13 +1367,6 @@ void launch_corpus_to_f16(const _Float16 *X, int64_t row_begin, int64_t row_end,
                        center);
 }
 
-void launch_queries_to_f16(const float *Q, int nq, int D, void *Qh, float *qinv, hipStream_t s)
-{
-    if (nq <= 0) return;
-    hipLaunchKernelGGL(queries_to_f16_kernel, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, s, Q, nq, D,
-                       reinterpret_cast<_Float16 *>(Qh), qinv);
-}
-
 // do the persistent kernels serve this launch (and, under a row list, leave POSITIONS in the candidate entries)?
 static bool tall16_persistent_ok(int D, int nq, bool img, bool mapped, bool masked)
 {
@@ -1456,7 +1407,7 @@ bool tall16_entries_are_positions(int D, int nq, bool img, bool mapped, bool mas
     return mapped && tall16_persistent_ok(D, nq, img, true, masked);
 }
 
-// Requires D % 32 == 0, 16-B aligned X / Qh; Qh / qinv from launch_queries_to_f16; X is the plain f32 corpus.
+// Requires D % 32 == 0, 16-B aligned X / Qh; Qh / qinv from launch_query_prep; X is the plain f32 corpus.
 // One launch over a window of the batch: Qh, qinv and cs start at the window's first query, q_stride is the batch's row count
 // (the K-block planes of the query image are that far apart).
 static void tall16_window(int metric, const float *X, const float *norm2, const float *rnorm, int64_t row_begin, int64_t row_end,
@@ -1522,10 +1473,9 @@ static void tall16_window(int metric, const float *X, const float *norm2, const 
         // LDS work either way -- and is not built)
         if (img && (nq <= 128 || qsplit)) { // one query tile of 64 / 128: the pass is the image's HBM stream
             const int bn = (nq <= 64 && !qsplit) ? 64 : 128;
-            const size_t ring_b = bn == 64 ? (size_t)6 * (H_BM * H_BK * 2 + 64 * H_BK * 2)
-                                           : (bn == 128 ? (size_t)5 * (H_BM * H_BK * 2 + 128 * H_BK * 2) : (size_t)4 * (H_BM * H_BK * 2 + 256 * H_BK * 2));
+            const size_t ring_b = bn == 64 ? (size_t)6 * (H_BM * H_BK * 2 + 64 * H_BK * 2) : (size_t)5 * (H_BM * H_BK * 2 + 128 * H_BK * 2);
             // ring, side inputs, flush flags + counters, admission segments
-            const size_t nshmem = ring_b + 2 * 512 * sizeof(float) + 16 + 2 * 256 * 4 + 8 * (bn == 256 ? 272 : 360) * 12;
+            const size_t nshmem = ring_b + 2 * 512 * sizeof(float) + 16 + 2 * 256 * 4 + 8 * 360 * 12;
             dim3 ngrid((unsigned)(spx * 8));
             bool tauin = false;
             uint32_t dr = 0;

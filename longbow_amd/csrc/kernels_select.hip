@@ -65,13 +65,11 @@ __device__ __forceinline__ void wave_or_and_u64(uint64_t &o, uint64_t &a)
 
 template <int NT> // threads per workgroup: 256 (throughput, many queries) or 1024 (latency, few queries)
 __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qsel, int kc,
-                                                             uint32_t boot_rows, uint32_t tau_only,
-                                                             uint32_t need_at_least,
+                                                             uint32_t boot_rows, uint32_t need_at_least,
                                                              EmitArgs em, uint32_t striped, uint32_t unsorted)
 {
-    // tau_only: the list holds a *sample* of the rows; publish its kc-th entry (row bits saturated) as
-    // the admission threshold and leave the list empty.  need_at_least: a list shorter than this means a
-    // sampled threshold admitted too few rows -> flag bit 2, the query is redone without sampling.
+    // need_at_least: a list shorter than this means a sampled threshold admitted too few rows -> flag bit 2,
+    // the query is redone without sampling.
     extern __shared__ __attribute__((aligned(16))) uint64_t sh[];
     const int q = qsel ? qsel[blockIdx.x] : blockIdx.x;
     const int tid = threadIdx.x;
@@ -157,13 +155,6 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
 
     if (P <= 2u * next_pow2((uint32_t)kc) || n <= (uint32_t)kc) {
         bitonic_sort_u64(sh, P, tid, NT); // kEntryMax padding sorts last
-        if (tau_only) {
-            if (tid == 0) {
-                cs.cnt[q] = 0;
-                cs.tau[q] = n >= (uint32_t)kc ? (sh[kc - 1] | 0xffffffffull) : kEntryMax;
-            }
-            return;
-        }
         for (uint32_t i = tid; i < keep; i += NT) list[i] = sh[i];
         if (tid == 0) {
             cs.cnt[q] = keep;
@@ -241,13 +232,6 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
         }
     }
     const uint64_t pivot = prefix; // >= the kc-th smallest entry and < the (kc+1)-th: exactly kc entries are <= pivot
-    if (tau_only) {
-        if (tid == 0) {
-            cs.cnt[q] = 0;
-            cs.tau[q] = pivot | 0xffffffffull;
-        }
-        return;
-    }
     // compact the kc entries <= pivot (unordered), then sort them.  The staging area is the unused tail of
     // the LDS entry array when there is room, else the front of the global list.
     const uint32_t Pk = next_pow2((uint32_t)kc);
@@ -317,7 +301,7 @@ void launch_sample_map(const uint32_t *rowmap, int64_t span, uint32_t count, uin
 }
 
 void launch_select(CandState cs, const int *qsel, int nsel, int kc, uint32_t boot_rows, hipStream_t s,
-                   bool tau_only, uint32_t need_at_least, const EmitArgs *emit, bool striped, bool unsorted)
+                   uint32_t need_at_least, const EmitArgs *emit, bool striped, bool unsorted)
 {
     EmitArgs em{};
     if (emit) em = *emit;
@@ -327,12 +311,12 @@ void launch_select(CandState cs, const int *qsel, int nsel, int kc, uint32_t boo
     if (nsel <= big_max) { // few queries: one big workgroup each, latency matters
         allow_big_lds(select_kernel<1024>, shmem);
         hipLaunchKernelGGL(select_kernel<1024>, dim3(nsel), dim3(1024), shmem, s, cs, qsel, kc, boot_rows,
-                           tau_only ? 1u : 0u, need_at_least, em,
+                           need_at_least, em,
                            (striped && cs.stripes) ? 1u : 0u, (unsorted && emit == nullptr) ? 1u : 0u);
     } else {
         allow_big_lds(select_kernel<256>, shmem);
         hipLaunchKernelGGL(select_kernel<256>, dim3(nsel), dim3(256), shmem, s, cs, qsel, kc, boot_rows,
-                           tau_only ? 1u : 0u, need_at_least, em,
+                           need_at_least, em,
                            (striped && cs.stripes) ? 1u : 0u, (unsorted && emit == nullptr) ? 1u : 0u);
     }
 }

@@ -300,8 +300,7 @@ void launch_column_means(const _Float16 *X, int64_t n, int D, float *partial, fl
 // boot: every row is stored at list[row - row_begin] (no admission test, no atomics).
 void launch_gemm_filter(int metric, const float *X, const float *norm2, const float *rnorm,
                         int64_t row_begin, int64_t row_end, int D, const float *Q, int nq,
-                        const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot, int split,
-                        hipStream_t s); // split: 0 f32 MFMA, 1 pre-split bf16 images, 2 f32 operands split in registers
+                        const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot, hipStream_t s);
 // small/mid-size batches (5..384 queries): 256-row x 32-query tiles, HBM-bound; needs D % 32 == 0, 16-B aligned X/Q
 void launch_gemm_filter_narrow(int metric, const float *X, const float *norm2, const float *rnorm,
                                int64_t row_begin, int64_t row_end, int D, const float *Q, int nq,
@@ -337,9 +336,9 @@ void launch_gemm_filter_tall2(int metric, const float *X, const float *norm2, co
                               int64_t row_end, int D, const float *Qs, int nq, const uint8_t *mask, const uint32_t *rowmap,
                               CandState cs, bool boot, int asplit, hipStream_t s);
 
-// ONE fp16 product per (row, query, k) on 256 x 256 tiles (kernels_gemm_tall16.hip): Qh / qinv from launch_queries_to_f16
+// ONE fp16 product per (row, query, k) on 256 x 256 tiles (kernels_gemm_tall16.hip): Qh / qinv from launch_query_prep
 // (fp16 image of the batch, each query scaled by a power of two to a norm in [1, 2); qinv = 1 / scale); X = f32 corpus
-void launch_queries_to_f16(const float *Q, int nq, int D, void *Qh, float *qinv, hipStream_t s);
+//
 // The one-tile persistent kernel over the image (<= 128 queries) can turn the sample the launch before it left in
 // lists[q][0 .. count) into the thresholds ITSELF (its first nq workgroups do, on shorter row ranges; everybody picks the
 // thresholds up in front of its first epilogue): no threshold launch, no gap behind it.  The launch before must leave
@@ -359,7 +358,7 @@ struct Tall16Tin {
 #endif
 };
 bool tall16_tin_ok(int D, int nq, int64_t n_pos, bool img, bool mapped, bool masked, bool with_norm, uint32_t count, int m);
-// the same image and scales, plus the exact ||q||^2 in `order` (qna, or null) and the reset of the queries' candidate state:
+// that image and those scales, plus the exact ||q||^2 in `order` (qna, or null) and the reset of the queries' candidate state:
 // one launch for what a search over this route needs from its batch (kernels_scan.hip)
 void launch_query_prep(const float *Q, int nq, int D, void *Qh, float *qinv, float *qna, int order, CandState cs, hipStream_t s,
                        const float *center = nullptr, // center: the image of q - center (L2 over the centred corpus image)
@@ -396,7 +395,6 @@ bool tall16_runs_persistent(int D, int nq, bool img, bool mapped, bool masked); 
 // per query: sort the list, keep the best kc, tau = kc-th entry (or max), flag overflow.
 // qsel (nullable): only these query slots.  boot_rows > 0: the list was filled by a bootstrap
 // launch (one entry per row at index row - row_begin, no atomics; masked rows hold kEntryMax).
-// tau_only: the list is a row *sample*; publish its kc-th entry as threshold and empty the list.
 // need_at_least: flag bit 2 when fewer entries than this were admitted (sampled threshold too tight).
 // emit: the search's last select also writes the k results per slot (what launch_emit_lists would do)
 struct EmitArgs {
@@ -407,7 +405,7 @@ struct EmitArgs {
     uint32_t *flags_host;
 };
 void launch_select(CandState cs, const int *qsel, int nsel, int kc, uint32_t boot_rows, hipStream_t s,
-                   bool tau_only = false, uint32_t need_at_least = 0, const EmitArgs *emit = nullptr,
+                   uint32_t need_at_least = 0, const EmitArgs *emit = nullptr,
                    bool striped = false,
                    bool unsorted = false); // unsorted: the kept entries need not be ordered, only the worst one sits last
 // approximate distances of `count` evenly spaced positions of [0, span) for up to 8 query slots, written

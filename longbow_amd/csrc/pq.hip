@@ -588,7 +588,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[3], s);
                     }
                     // the search's last select also writes the k results (redone queries overwrite them below)
-                    launch_select(sc.cs, sc.d_slots + q, 1, k, 0u, s, false, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                    launch_select(sc.cs, sc.d_slots + q, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
                     return;
                 }
             }
@@ -599,7 +599,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                 const int64_t end = chunk_end_host(step, pos, p->n, k, cap, mode == 2, /*big_boot=*/true);
                 const bool boot = step == 0;
                 launch_adc_scan(tab, p->M, p->d_codes, pos, end, q, nullptr, sc.cs, boot, nullptr, 0, s);
-                launch_select(sc.cs, sc.d_slots + q, 1, k, boot ? (uint32_t)(end - pos) : 0u, s, false, 0u,
+                launch_select(sc.cs, sc.d_slots + q, 1, k, boot ? (uint32_t)(end - pos) : 0u, s, 0u,
                               end >= p->n ? &em : nullptr);
                 pos = end;
                 step++;
@@ -634,7 +634,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                 const float *tab = sc.d_tables + (size_t)qq * p->M * 256;
                 launch_adc_exact_candidates(tab, p->M, p->d_codes, sc.d_cand + (size_t)j * kCandCap, sc.d_cand_cnt + qq, kCandCap,
                                             prm[j], qq, sc.cs, s);
-                launch_select(sc.cs, sc.d_slots + qq, 1, k, 0u, s, false, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                launch_select(sc.cs, sc.d_slots + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
             }
             return true;
         };
@@ -669,7 +669,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                 const int qq = q + j;
                 const float *tab = sc.d_tables + (size_t)qq * p->M * 256;
                 launch_adc_exact_candidates(tab, p->M, p->d_codes, cand[j], ccnt[j], kCandCap, prm[j], qq, sc.cs, s);
-                launch_select(sc.cs, sc.d_slots + qq, 1, k, 0u, s, false, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                launch_select(sc.cs, sc.d_slots + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
             }
             return true;
         };

@@ -63,10 +63,9 @@ for k in sorted(set(fetch) | set(write)):
     big = max(fv) * 1024 * 2 if fv else 0
     lines.append(f"{k},{n},{fb:.0f},{wb:.0f},{big:.0f}")
     if k.startswith("lb::gemm_filter_kernel"):
-        tag = "gemm_filter_kernel_split" if k.rstrip(">").endswith("true") else "gemm_filter_kernel"
-        traffic[f"{tag}_hbm_bytes_per_launch"] = fb + wb
-        traffic[f"{tag}_largest_launch_bytes"] = big
-        traffic[f"{tag}_launches_profiled"] = n
+        traffic["gemm_filter_kernel_hbm_bytes_per_launch"] = fb + wb
+        traffic["gemm_filter_kernel_largest_launch_bytes"] = big
+        traffic["gemm_filter_kernel_launches_profiled"] = n
     if k.startswith("lb::scan_kernel"):
         traffic["scan_kernel_hbm_bytes_per_launch"] = fb + wb
         traffic["scan_kernel_launches_profiled"] = n
