@@ -357,6 +357,13 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
 /* 1 (default): the search runs the byte-table prefilter + exact survivors; 0: the exact f32-table
  * pass over every row.  Results are bit-identical; the switch exists for A/B timing and for the parity tests. */
 int lb_gpu_pq_set_prefilter(lb_gpu_pq *p, int enable);
+/* What served the queries of the last COMPLETED device batch on this handle (a refused, cancelled or failed search
+ * leaves the previous record; observing only, the PQ counterpart of
+ * lb_gpu_index_last_fallbacks / last_route), in queries: out[0] planned with a sampled threshold (nq or 0),
+ * out[1] served by a four-query prefilter pass, out[2] by a two-query pass, out[3] by a single prefilter pass
+ * (including quads and pairs whose M has no shared form), out[4] redone on the bootstrap schedule, out[5] redone
+ * on the schedule that cannot overflow.  Concurrent searches overwrite each other's record. */
+int lb_gpu_pq_last_search_stats(const lb_gpu_pq *p, int64_t out[6]);
 
 /* instrumentation (bench.py): HIP-event times of the most recent profiled search on this handle, recorded on the
  * search stream: ms[0] = the pass over the codes of the LAST query (prefilter kernel, or the exact kernel when

@@ -316,6 +316,8 @@ class PQEncoder {
         table.assign((size_t)M * 256, 0.f);
         return lb_gpu_pq_build_adc_table(p_, query.data(), table.data());
     }
+    // what served the last device batch of searches on this handle (lb_gpu_pq_last_search_stats)
+    int LastSearchStats(int64_t out[6]) const { return lb_gpu_pq_last_search_stats(p_, out); }
     int M = 0, Dims = 0;
 
   private:

@@ -203,12 +203,18 @@ void launch_pq_decode(const float *codebooks, int M, int K, int sub, const uint8
 //   real sum <= f32 sum * (1 + 2*gamma), gamma = 1.05 * M * 2^-24   (sequential f32 sum of M terms >= 0)
 //   real sum >= base + s * S - eps                 (floor quantisation; eps covers the roundings)
 //   => admitted rows satisfy S <= (U*(1+2 gamma) - base) / s + 2
+// The bound needs s and 1/s as normal f32 numbers.  Below rmax = 255 / FLT_MAX ~ 7.5e-37 the reciprocal 255 / rmax
+// overflows to +inf: every entry above its subtable's minimum would quantise to 255 and the minima to 0 * inf, and
+// rows the threshold admits would be dropped while worse ones pass.  A largest range in (0, kAdcMinRange) or a
+// non-finite 1/s therefore sets ok = 0 and the host's exact schedule serves the query (tests/test_adc_bound_semantics.py
+// restates this arithmetic and checks the bound at the floor).  rmax == 0 (constant subtables) stays served: S == 0.
+constexpr float kAdcMinRange = 0x1p-100f; // ~7.9e-31: s = rmax / 255 and 1 / s are both normal, with margin
 __global__ __launch_bounds__(256) void adc_quantise_kernel(const float *table, const float *minrng, int M, const uint64_t *tau_p,
                                                            uint8_t *qt, int *params)
 {
     __shared__ float s_inv, s_scale, s_mn;
     __shared__ double s_base;
-    __shared__ int s_bad;
+    __shared__ int s_bad, s_small;
     const int j = blockIdx.x, tid = threadIdx.x;
     if (tid < 64) { // one wave: max range, sum of minima, any bad entry
         float rmax = 0.f;
@@ -230,6 +236,7 @@ __global__ __launch_bounds__(256) void adc_quantise_kernel(const float *table, c
             s_inv = rmax > 0.f ? 255.0f / rmax : 0.f;
             s_base = base;
             s_bad = bad;
+            s_small = (rmax > 0.f && rmax < kAdcMinRange) || !(s_inv <= 3.0e38f) ? 1 : 0;
             s_mn = minrng[j * 4 + 0];
         }
     }
@@ -244,7 +251,7 @@ __global__ __launch_bounds__(256) void adc_quantise_kernel(const float *table, c
         qt[j * 256 + tid] = (uint8_t)qi;
     }
     if (j == 0 && tid == 0) {
-        int ok = s_bad ? 0 : 1;
+        int ok = (s_bad || s_small) ? 0 : 1;
         int s_tau = 0;
         const uint64_t tau = *tau_p;
         if (tau == kEntryMax) {

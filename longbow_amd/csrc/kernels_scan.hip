@@ -724,7 +724,11 @@ __device__ __forceinline__ uint64_t sample_tau_body(const uint64_t *list, uint32
     uint32_t e[ST_PER];
 #pragma unroll
     for (int i = 0; i < ST_PER; i++) {
-        const uint32_t idx = (uint32_t)tid + (uint32_t)ST_THREADS * i;
+        // Fewer entries than threads (the second level of the PQ search's threshold: groups * m of them) are dealt round
+        // the 16 waves, entry j to wave j % 16.  Read in thread order they would all sit in the first waves, whose runs of
+        // r1 < m keys the merge below exhausts: with count == m it then found NO threshold and every such search was redone.
+        const uint32_t idx = (count < (uint32_t)ST_THREADS && i == 0) ? (uint32_t)(tid >> 6) + 16u * (uint32_t)(tid & 63)
+                                                                     : (uint32_t)tid + (uint32_t)ST_THREADS * i;
         const uint64_t ent = idx >= count ? kEntryMax : list[idx];
         e[i] = (uint32_t)(ent >> 32);
     }

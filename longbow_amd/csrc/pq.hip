@@ -53,6 +53,9 @@ struct lb_gpu_pq {
     SearchCombiner combiner;       // concurrent host-pointer searches of a few queries each are combined (lb_host.h)
     hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
     float prof_ms[2] = {0.f, 0.f};
+    // what served the queries of the last COMPLETED device batch (lb_gpu_pq_last_search_stats): observing only
+    mutable std::mutex stats_mu;
+    int64_t last_stats[6] = {0, 0, 0, 0, 0, 0};
     void set_error(const char *fmt, ...)
     {
         char buf[512];
@@ -546,6 +549,8 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         PqScratch &sc = *scp;
         const bool prefilter = samp_count != 0 && p->prefilter.load() != 0;
         const bool prof = p->profiling.load() != 0;
+        // {sampled plan, four-query pass, two-query pass, single prefilter pass, bootstrap redo, safe redo} (queries)
+        int64_t stats[6] = {samp_count ? nqi : 0, 0, 0, 0, 0, 0};
         if (prof) {
             for (auto &e : p->ev)
                 if (!e) LBP_HIP(hipEventCreate(&e));
@@ -579,6 +584,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                         launch_adc_quantise(tab, sc.d_minrng + (size_t)q * p->M * 4, p->M, sc.cs.tau + q, qtab, prm, s);
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[2], s);
                         launch_adc_prefilter(qtab, prm, p->M, p->d_codes, p->n, sc.d_cand, kCandCap, sc.d_cand_cnt + q, s);
+                        stats[3]++;
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[3], s);
                         launch_adc_exact_candidates(tab, p->M, p->d_codes, sc.d_cand, sc.d_cand_cnt + q, kCandCap, prm, q,
                                                     sc.cs, s);
@@ -627,6 +633,9 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                 for (int j = 0; j < 2; j++)
                     launch_adc_prefilter(qtab[j], prm[j], p->M, p->d_codes, p->n, sc.d_cand + (size_t)j * kCandCap, kCandCap,
                                          sc.d_cand_cnt + q + j, s);
+                stats[3] += 2;
+            } else {
+                stats[2] += 2;
             }
             if (prof && last) (void)hipEventRecord(p->ev[3], s);
             for (int j = 0; j < 2; j++) {
@@ -660,9 +669,15 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             if (!launch_adc_prefilter4(qtab, prm, cand, ccnt, p->M, p->d_codes, p->n, kCandCap, s)) {
                 for (int j = 0; j < 4; j += 2)
                     if (!launch_adc_prefilter2(qtab[j], prm[j], cand[j], ccnt[j], qtab[j + 1], prm[j + 1], cand[j + 1], ccnt[j + 1], p->M,
-                                               p->d_codes, p->n, kCandCap, s))
+                                               p->d_codes, p->n, kCandCap, s)) {
                         for (int u = j; u < j + 2; u++)
                             launch_adc_prefilter(qtab[u], prm[u], p->M, p->d_codes, p->n, cand[u], kCandCap, ccnt[u], s);
+                        stats[3] += 2;
+                    } else {
+                        stats[2] += 2;
+                    }
+            } else {
+                stats[1] += 4;
             }
             if (prof && last) (void)hipEventRecord(p->ev[3], s);
             for (int j = 0; j < 4; j++) {
@@ -699,11 +714,11 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         if (samp_count) {
             bool any = false;
             for (int q = 0; q < nqi; q++)
-                if (sc.h_flags[q] & (1u | 4u)) { scan_query(q, 1); any = true; } // the sampled threshold missed
+                if (sc.h_flags[q] & (1u | 4u)) { scan_query(q, 1); stats[4]++; any = true; } // the sampled threshold missed
             if (any) read_flags();
         }
         for (int q = 0; q < nqi; q++)
-            if (sc.h_flags[q] & 1u) scan_query(q, 2); // chunks that cannot overflow the list
+            if (sc.h_flags[q] & 1u) { scan_query(q, 2); stats[5]++; } // chunks that cannot overflow the list
         LB_LAUNCH_CHECK();
         if (prof) LBP_HIP(hipEventRecord(p->ev[1], s));
         LBP_HIP(hipStreamSynchronize(s));
@@ -716,9 +731,21 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             p->prof_ms[1] = b;
         }
         release_scratch(p, std::move(scp));
+        {
+            std::lock_guard<std::mutex> gs(p->stats_mu);
+            std::copy(stats, stats + 6, p->last_stats);
+        }
     } catch (const HipErrP &e) {
         return pq_fail(p, e);
     }
+    return LB_OK;
+}
+
+int lb_gpu_pq_last_search_stats(const lb_gpu_pq *p, int64_t out[6])
+{
+    if (!p || !out) return LB_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->stats_mu);
+    std::copy(p->last_stats, p->last_stats + 6, out);
     return LB_OK;
 }
 

@@ -128,6 +128,15 @@ class PQEncoder:
         """True (default): byte-table prefilter + exact survivors; False: exact f32-table pass only.  Same results."""
         _lib.check(self._lib.lb_gpu_pq_set_prefilter(self._h, 1 if on else 0), self._h, pq=True, lib=self._lib)
 
+    @property
+    def last_search_stats(self):
+        """what served the last completed device batch, in queries (a refused or failed search leaves the record):
+        (planned with a sampled threshold, four-query passes, two-query passes, single prefilter passes,
+        redone on the bootstrap schedule, redone on the schedule that cannot overflow)"""
+        out = (C.c_int64 * 6)()
+        _lib.check(self._lib.lb_gpu_pq_last_search_stats(self._h, out), self._h, pq=True, lib=self._lib)
+        return tuple(int(v) for v in out)
+
     def set_search_combining(self, enable):
         """1 (default): concurrent Search calls of a few queries each are answered by one batch (pairs of queries share a pass
         over the codes); 0: every call on its own.  Same results."""
