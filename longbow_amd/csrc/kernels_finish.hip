@@ -7,7 +7,7 @@
 //   1. the query's candidate list (every row whose key passed the admission threshold tau: ~2,300 entries at 1M rows) is
 //      read into registers; a radix select finds its k-th smallest key a_k;
 //   2. cut = a_k + (1 + beta) E, E = the rigorous error bound of a candidate key against the exact value (the contraction's
-//      gamma of index.hip plus the exact sums' own rounding); S = { entries with key <= cut } -- a few hundred rows when the
+//      gamma of index_search.hip plus the exact sums' own rounding); S = { entries with key <= cut } -- a few hundred rows when the
 //      keys are coarse (fp16 products), k + a handful when they are fine (split-bf16, f32);
 //   3. the rows of S are gathered and scored in the reference's order (internal/simd/simd_test.go:13-33,
 //      simd.go:138-163,365-479; BruteForceIndex.SearchVectors' (distance, row) ranking, adaptive_index.go:200-222);
@@ -15,7 +15,7 @@
 //      then key(y) >= tau_key > cut (checked: otherwise the query is flagged).  Its exact value therefore exceeds
 //      T = f(cut) - E_out, with f the metric's map from key to exact value and E_out the one-sided bound.  If at least k
 //      members of S have an exact value < T (strictly), the k nearest rows are all in S and the sorted prefix is the answer;
-//      otherwise flag bit 1, and the host widens the list or takes the exact scan (index.hip: search_batch_device).
+//      otherwise flag bit 1, and the host widens the list or takes the exact scan (index_search.hip: search_batch_device).
 //      Correctness never depends on beta: it only decides how often the proof closes at the first attempt.
 //
 // Two forms.  SPLIT (a few queries: latency): G workgroups per query share the members (list position mod G), each scores

@@ -69,7 +69,7 @@ constexpr uint32_t kSpinLimit = 1500; // x ~0.6 us (s_sleep 8 + one L2 round tri
 // the corpus.  3/16 of the f32 MFMA cycles: at 32-64 queries the f32 contraction keeps the MFMA pipe 70 %
 // busy under the corpus stream (0.31 of 0.45 ms per pass at 1M x 768), which is what held this kernel at
 // 5.1 TB/s; split, the pipe is ~13 % busy and the kernel is a pure HBM stream.  Candidate keys carry the
-// split contraction's error bound (index.hip: gamma); reported results come from the exact re-rank.
+// split contraction's error bound (index_search.hip: gamma); reported results come from the exact re-rank.
 // FUSED: the launch starts with a.fs.n_blocks workgroups that score the sampled rows and publish the thresholds (see
 // FusedSample in lb_device.h); the corpus tiles fetch their thresholds in front of the epilogue instead of at entry.
 // The sample workgroups have the lowest block ids, so they are resident before any workgroup that waits for them.

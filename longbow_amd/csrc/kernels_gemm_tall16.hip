@@ -4,7 +4,7 @@
 // Same contract as the other candidate kernels (kernels_gemm_tall2.hip): S = X_tile . Q_tile^T, metric key and admission
 // test fused into the epilogue; ranking semantics of BruteForceIndex.SearchVectors
 // (internal/store/adaptive_index.go:161-225); the keys are CANDIDATE keys only -- every reported distance comes from the
-// exact f32 re-rank, and the re-rank's containment proof (index.hip) decides with THIS contraction's error bound whether
+// exact f32 re-rank, and the re-rank's containment proof (index_search.hip) decides with THIS contraction's error bound whether
 // the candidate list provably holds the true top-k; a query for which it does not is redone by the exact scan.
 //
 // Why one product is enough.  The split-bf16 contraction (three MFMA products, 2^-17 relative) is far more accurate than the

@@ -10,7 +10,7 @@
 // Reported: L2 the value, dot its negation (ascending lists), exactly as the f32 index reports its own metrics.
 //
 // Every lane computes the exact value of its (row, query) pairs, so the candidate entries ARE the results: the lists, the
-// sampled threshold, the selects and the emit of the scan path (index.hip: run_scan_path) work on them unchanged.
+// sampled threshold, the selects and the emit of the scan path (index_search.hip: run_scan_path) work on them unchanged.
 // The scan kernels read the queries widened to f32 (exact: they are int8 values) and narrow them back as they stage them; the
 // MFMA pass reads the int8 queries.
 #include "lb_device.h"

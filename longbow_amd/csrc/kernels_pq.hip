@@ -255,7 +255,7 @@ static bool try_launch_adc_dma(const AdcArgs &a, hipStream_t s)
 }
 
 // Exact ADC distances of `count` evenly spaced rows of [0, n) (sampled admission threshold, see
-// index.hip: sample_plan): the table sits in LDS as in the scan kernels, one lane per sampled row.
+// index_search.hip: sample_plan): the table sits in LDS as in the scan kernels, one lane per sampled row.
 __global__ __launch_bounds__(ADC_THREADS) void adc_sample_kernel(const float *table, int M, const uint8_t *codes, int64_t n,
                                                                  uint32_t count, uint64_t *out, int vec16)
 {

@@ -14,7 +14,7 @@
 // walks its own row.  No FMA contraction here.
 //
 // Also here: the sampled admission threshold (sample_scores_kernel, sample_tau_kernel,
-// sample_topm_kernel; see index.hip: sample_plan) that lets a search walk the corpus once.
+// sample_topm_kernel; see index_search.hip: sample_plan) that lets a search walk the corpus once.
 #include "lb_device.h"
 #include "lb_exact.h"
 
@@ -322,7 +322,7 @@ void launch_query_norms(int order, const float *Q, const int *qsel, int nsel, in
 }
 
 // ---------------------------------------------------------------------------
-// Sampled admission threshold (index.hip: sample_plan).  `count` evenly spaced positions of
+// Sampled admission threshold (index_search.hip: sample_plan).  `count` evenly spaced positions of
 // [0, span) are scored approximately -- one wave per sampled row, every load of the row in flight
 // at once, wave-shuffle reduction: the whole sample costs one HBM round trip instead of the exact
 // kernel's D/64 dependent stages -- and the m-th best of them becomes tau.  tau is only a filter

@@ -383,7 +383,7 @@ void launch_corpus_to_f16(const float *X, int64_t row_begin, int64_t row_end, in
 void launch_corpus_to_f16(const _Float16 *X, int64_t row_begin, int64_t row_end, int D, void *Xh, int64_t cap, hipStream_t s,
                           const float *center = nullptr); // center (or null; [>= D + 8]): the image holds fp16(x - center)
 // *stat = max(*stat, max over the rows of |x - fp16(x)|^2 / |x|^2) as float bits (x - center for the centred image): the
-// measured loss of the image, from which the candidate keys' error bound is taken (index.hip: gamma)
+// measured loss of the image, from which the candidate keys' error bound is taken (index_search.hip: gamma)
 void launch_f16_residual(const float *X, int64_t row_begin, int64_t row_end, int D, const float *center, uint32_t *stat, hipStream_t s);
 void launch_f16_residual(const _Float16 *X, int64_t row_begin, int64_t row_end, int D, const float *center, uint32_t *stat, hipStream_t s);
 int corpus_f16_plane_dims(); // dimensions per plane of that image (its rows are zero-padded to a multiple of it)
@@ -486,7 +486,7 @@ void launch_emit_lists(CandState cs, const int *qsel, int nsel, int k, const int
                        float *out_dist, int64_t *out_labels, uint32_t *flags_host, hipStream_t s);
 
 void launch_init_cand(CandState cs, const int *qsel, int nsel, hipStream_t s);
-// dist[0..n) = FLT_MAX, lab[0..n) = -1 (index.hip)
+// dist[0..n) = FLT_MAX, lab[0..n) = -1 (simd_api.hip)
 void launch_fill_empty(float *dist, int64_t *lab, int64_t n, hipStream_t s);
 
 // shard s's [nq][k] blocks start at dist_in + s*dist_stride and lab_in + s*lab_stride (elements)

@@ -1,5 +1,5 @@
-// lb_host.h -- host-side helpers shared by the C-ABI translation units (index.hip, pq.hip, comm.hip):
-// HIP error plumbing and a pooled device / pinned-host buffer cache.
+// lb_host.h -- host-side helpers shared by the C-ABI translation units (index.hip, index_search.hip, simd_api.hip, pq.hip,
+// comm.hip): HIP error plumbing, a pooled device / pinned-host buffer cache and the owners of a handle's own buffers.
 //
 // Why a pool: hipMalloc costs 0.1-0.3 ms and hipFree synchronises the whole device, so an entry
 // point that allocates per call stalls every concurrent search on the same GPU.  The host-pointer
@@ -13,6 +13,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <mutex>
+#include <utility>
 #include <vector>
 
 #include "lb_combine.h"
@@ -38,6 +39,9 @@ struct HipErr {
         hipError_t _e = hipGetLastError();                                 \
         if (_e != hipSuccess) throw ::lb::HipErr{_e, "kernel launch"};     \
     } while (0)
+
+// host-side types and functions shared between translation units that are no part of the library's ABI: kept out of its dynamic symbols
+#define LB_INTERNAL __attribute__((visibility("hidden")))
 
 class BufPool {
   public:
@@ -132,7 +136,7 @@ class BufPool {
     std::vector<Ent> free_, live_;
 };
 
-BufPool &buf_pool(); // one per process (index.hip)
+BufPool &buf_pool(); // one per process (simd_api.hip)
 
 // RAII lease from the pool
 struct Lease {
@@ -151,6 +155,63 @@ struct Lease {
     template <typename T>
     T *as() const { return static_cast<T *>(p); }
 };
+
+// An array of T from hipMalloc (Pinned: hipHostMalloc), freed by the destructor; move-only.  A handle or a pooled scratch struct
+// declares its buffers as members, and its own destructor only makes the device current: it runs before the members free
+// themselves.
+template <class T, bool Pinned> class LB_INTERNAL HipBuf {
+  public:
+    HipBuf() = default;
+    HipBuf(HipBuf &&o) noexcept : p_(std::exchange(o.p_, nullptr)), n_(std::exchange(o.n_, 0)) {}
+    HipBuf &operator=(HipBuf &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+            n_ = std::exchange(o.n_, 0);
+        }
+        return *this;
+    }
+    ~HipBuf() { reset(); }
+    T *get() const { return p_; }
+    size_t count() const { return n_; } // elements allocated
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset()
+    {
+        if (p_) (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr;
+        n_ = 0;
+    }
+    // exactly `count` elements, whatever was held before is freed first; throws HipErr and is then empty
+    void alloc(size_t count)
+    {
+        reset();
+        if (Pinned) LB_HIP(hipHostMalloc(&p_, count * sizeof(T), hipHostMallocDefault));
+        else LB_HIP(hipMalloc(&p_, count * sizeof(T)));
+        n_ = count;
+    }
+    // at least `count` elements; the contents are not kept when it has to re-allocate
+    void ensure(size_t count) { if (n_ < count) alloc(count); }
+    T *release() { n_ = 0; return std::exchange(p_, nullptr); }
+
+  private:
+    T *p_ = nullptr;
+    size_t n_ = 0;
+};
+template <class T> using DevBuf = HipBuf<T, false>;
+template <class T> using PinnedBuf = HipBuf<T, true>;
+
+// a stream or an event, destroyed with its owner; created in place through `h`
+template <class H, hipError_t (*Destroy)(H)> struct LB_INTERNAL HipHandle {
+    H h = nullptr;
+    HipHandle() = default;
+    HipHandle(HipHandle &&o) noexcept : h(std::exchange(o.h, nullptr)) {}
+    HipHandle &operator=(HipHandle &&) = delete;
+    ~HipHandle() { if (h) (void)Destroy(h); }
+    operator H() const { return h; }
+};
+using Stream = HipHandle<hipStream_t, hipStreamDestroy>;
+using EventH = HipHandle<hipEvent_t, hipEventDestroy>;
 
 } // namespace lb
 

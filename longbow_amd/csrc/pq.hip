@@ -37,10 +37,10 @@ struct PqScratch;
 struct lb_gpu_pq {
     int device = 0, dims = 0, M = 0, K = 0, sub = 0;
     std::shared_mutex mu;
-    float *d_codebooks = nullptr;
-    uint8_t *d_codes = nullptr;
+    DevBuf<float> d_codebooks;
+    DevBuf<uint8_t> d_codes;
     int64_t n = 0, capacity = 0;
-    hipStream_t stream = nullptr;
+    Stream stream;
     // per-search scratch (lists, tables, sample and candidate buffers) is pooled on the handle: a search
     // must not hipMalloc/hipFree (the latter synchronises the device under every concurrent search)
     std::mutex sc_mu;
@@ -51,7 +51,7 @@ struct lb_gpu_pq {
     std::atomic<int> profiling{0};
     std::atomic<int> prefilter{1}; // 0 = exact f32-table pass only (lb_gpu_pq_set_prefilter; both are exact)
     SearchCombiner combiner;       // concurrent host-pointer searches of a few queries each are combined (lb_host.h)
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    EventH ev[4];
     float prof_ms[2] = {0.f, 0.f};
     // what served the queries of the last COMPLETED device batch (lb_gpu_pq_last_search_stats): observing only
     mutable std::mutex stats_mu;
@@ -83,17 +83,13 @@ void pq_grow(lb_gpu_pq *p, int64_t need)
     if (need <= p->capacity) return;
     int64_t cap = std::max<int64_t>(std::max<int64_t>(need, p->capacity * 2), 4096);
     if ((size_t)p->capacity * p->M > ((size_t)1 << 30)) cap = std::max<int64_t>(need, p->capacity + p->capacity / 4);
-    uint8_t *nc = nullptr;
-    LBP_HIP(hipMalloc(&nc, (size_t)cap * p->M));
+    DevBuf<uint8_t> nc;
+    nc.alloc((size_t)cap * p->M);
     if (p->n > 0) {
-        hipError_t e = hipMemcpy(nc, p->d_codes, (size_t)p->n * p->M, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) {
-            (void)hipFree(nc);
-            throw HipErrP{e, "hipMemcpy (pq_grow)"};
-        }
+        const hipError_t e = hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice);
+        if (e != hipSuccess) throw HipErrP{e, "hipMemcpy (pq_grow)"};
     }
-    if (p->d_codes) (void)hipFree(p->d_codes);
-    p->d_codes = nc;
+    p->d_codes = std::move(nc);
     p->capacity = cap;
 }
 
@@ -104,34 +100,20 @@ struct PqScratch {
     int nq_cap = 0;
     uint32_t cap = 0;
     int M = 0;
+    // the candidate state as the kernels take it (by value): pointers into the four buffers below, filled once (acquire_scratch)
     CandState cs{};
-    float *d_tables = nullptr;   // [nq][M*256] f32
-    uint8_t *d_qtabs = nullptr;  // [nq][M*256] u8
-    float *d_minrng = nullptr;   // [nq][M][4]: subtable minimum, range, bad flag
-    int *d_params = nullptr;     // [nq][4]
-    uint32_t *d_cand = nullptr;  // [4][kCandCap] survivors of the (up to four) queries in flight
-    uint32_t *d_cand_cnt = nullptr; // [nq]
-    int *d_slots = nullptr;      // 0..nq-1
-    uint64_t *d_samp = nullptr;  // ADC entries of the sampled rows
-    size_t samp_entries = 0;
-    uint32_t *h_flags = nullptr; // pinned
-    ~PqScratch()
-    {
-        (void)hipSetDevice(device);
-        if (cs.lists) (void)hipFree(cs.lists);
-        if (cs.cnt) (void)hipFree(cs.cnt);
-        if (cs.tau) (void)hipFree(cs.tau);
-        if (cs.flags) (void)hipFree(cs.flags);
-        if (d_tables) (void)hipFree(d_tables);
-        if (d_qtabs) (void)hipFree(d_qtabs);
-        if (d_minrng) (void)hipFree(d_minrng);
-        if (d_params) (void)hipFree(d_params);
-        if (d_cand) (void)hipFree(d_cand);
-        if (d_cand_cnt) (void)hipFree(d_cand_cnt);
-        if (d_slots) (void)hipFree(d_slots);
-        if (d_samp) (void)hipFree(d_samp);
-        if (h_flags) (void)hipHostFree(h_flags);
-    }
+    DevBuf<uint64_t> d_lists, d_tau;
+    DevBuf<uint32_t> d_cnt, d_flags;
+    DevBuf<float> d_tables;      // [nq][M*256] f32
+    DevBuf<uint8_t> d_qtabs;     // [nq][M*256] u8
+    DevBuf<float> d_minrng;      // [nq][M][4]: subtable minimum, range, bad flag
+    DevBuf<int> d_params;        // [nq][4]
+    DevBuf<uint32_t> d_cand;     // [4][kCandCap] survivors of the (up to four) queries in flight
+    DevBuf<uint32_t> d_cand_cnt; // [nq]
+    DevBuf<int> d_slots;         // 0..nq-1
+    DevBuf<uint64_t> d_samp;     // ADC entries of the sampled rows
+    PinnedBuf<uint32_t> h_flags;
+    ~PqScratch() { (void)hipSetDevice(device); }
 };
 
 std::unique_ptr<PqScratch> acquire_scratch(lb_gpu_pq *p, int nq, uint32_t cap, size_t samp_entries)
@@ -154,29 +136,27 @@ std::unique_ptr<PqScratch> acquire_scratch(lb_gpu_pq *p, int nq, uint32_t cap, s
         sc->M = p->M;
         sc->cs.cap = cap;
         const size_t nqc = (size_t)sc->nq_cap;
-        LBP_HIP(hipMalloc(&sc->cs.lists, nqc * cap * 8));
-        LBP_HIP(hipMalloc(&sc->cs.cnt, nqc * 4));
-        LBP_HIP(hipMalloc(&sc->cs.tau, nqc * 8));
-        LBP_HIP(hipMalloc(&sc->cs.flags, nqc * 4));
-        LBP_HIP(hipMalloc(&sc->d_tables, nqc * p->M * 256 * 4));
-        LBP_HIP(hipMalloc(&sc->d_qtabs, nqc * p->M * 256));
-        LBP_HIP(hipMalloc(&sc->d_minrng, nqc * p->M * 4 * sizeof(float)));
-        LBP_HIP(hipMalloc(&sc->d_params, nqc * 4 * sizeof(int)));
-        LBP_HIP(hipMalloc(&sc->d_cand, (size_t)4 * kCandCap * 4));
-        LBP_HIP(hipMalloc(&sc->d_cand_cnt, nqc * 4));
-        LBP_HIP(hipMalloc(&sc->d_slots, nqc * sizeof(int)));
-        LBP_HIP(hipHostMalloc(&sc->h_flags, nqc * 4, hipHostMallocDefault));
+        sc->d_lists.alloc(nqc * cap);
+        sc->d_cnt.alloc(nqc);
+        sc->d_tau.alloc(nqc);
+        sc->d_flags.alloc(nqc);
+        sc->cs.lists = sc->d_lists.get();
+        sc->cs.cnt = sc->d_cnt.get();
+        sc->cs.tau = sc->d_tau.get();
+        sc->cs.flags = sc->d_flags.get();
+        sc->d_tables.alloc(nqc * p->M * 256);
+        sc->d_qtabs.alloc(nqc * p->M * 256);
+        sc->d_minrng.alloc(nqc * p->M * 4);
+        sc->d_params.alloc(nqc * 4);
+        sc->d_cand.alloc((size_t)4 * kCandCap);
+        sc->d_cand_cnt.alloc(nqc);
+        sc->d_slots.alloc(nqc);
+        sc->h_flags.alloc(nqc);
         std::vector<int> slots(nqc);
         for (size_t q = 0; q < nqc; q++) slots[q] = (int)q;
-        LBP_HIP(hipMemcpy(sc->d_slots, slots.data(), nqc * sizeof(int), hipMemcpyHostToDevice));
+        LBP_HIP(hipMemcpy(sc->d_slots.get(), slots.data(), nqc * sizeof(int), hipMemcpyHostToDevice));
     }
-    if (sc->samp_entries < samp_entries) {
-        if (sc->d_samp) (void)hipFree(sc->d_samp);
-        sc->d_samp = nullptr;
-        sc->samp_entries = 0;
-        LBP_HIP(hipMalloc(&sc->d_samp, samp_entries * sizeof(uint64_t)));
-        sc->samp_entries = samp_entries;
-    }
+    sc->d_samp.ensure(samp_entries);
     return sc;
 }
 
@@ -206,10 +186,10 @@ lb_gpu_pq *lb_gpu_pq_new(int device, const uint8_t *blob, size_t len, int *out_s
     p->device = device; p->dims = (int)dims; p->M = (int)M; p->K = (int)K; p->sub = (int)sub;
     try {
         LBP_HIP(hipSetDevice(device));
-        LBP_HIP(hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking));
-        LBP_HIP(hipMalloc(&p->d_codebooks, len - 12));
+        LBP_HIP(hipStreamCreateWithFlags(&p->stream.h, hipStreamNonBlocking));
+        p->d_codebooks.alloc((len - 12) / sizeof(float));
         // f32 little-endian on the wire == host/device layout on this platform
-        LBP_HIP(hipMemcpy(p->d_codebooks, blob + 12, len - 12, hipMemcpyHostToDevice));
+        LBP_HIP(hipMemcpy(p->d_codebooks.get(), blob + 12, len - 12, hipMemcpyHostToDevice));
     } catch (const HipErrP &e) {
         st(e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP);
         lb_gpu_pq_free(p);
@@ -230,11 +210,6 @@ void lb_gpu_pq_free(lb_gpu_pq *p)
             std::lock_guard<std::mutex> g2(p->sc_mu);
             p->sc_free.clear();
         }
-        if (p->d_codebooks) (void)hipFree(p->d_codebooks);
-        if (p->d_codes) (void)hipFree(p->d_codes);
-        for (auto &e : p->ev)
-            if (e) (void)hipEventDestroy(e);
-        if (p->stream) (void)hipStreamDestroy(p->stream);
     }
     delete p;
 }
@@ -277,7 +252,7 @@ static int add_codes_impl(lb_gpu_pq *p, int64_t n, const uint8_t *codes, bool on
     try {
         LBP_HIP(hipSetDevice(p->device));
         pq_grow(p, p->n + n);
-        LBP_HIP(hipMemcpy(p->d_codes + (size_t)p->n * p->M, codes, (size_t)n * p->M,
+        LBP_HIP(hipMemcpy(p->d_codes.get() + (size_t)p->n * p->M, codes, (size_t)n * p->M,
                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         p->n += n;
     } catch (const HipErrP &e) {
@@ -297,7 +272,7 @@ int lb_gpu_pq_get_codes(lb_gpu_pq *p, int64_t row0, int64_t n, uint8_t *codes)
     if (row0 + n > p->n) { p->set_error("rows [%lld, %lld) outside the %lld stored codes", (long long)row0, (long long)(row0 + n), (long long)p->n); return LB_ERR_INVALID_ARG; }
     try {
         LBP_HIP(hipSetDevice(p->device));
-        LBP_HIP(hipMemcpy(codes, p->d_codes + (size_t)row0 * p->M, (size_t)n * p->M, hipMemcpyDeviceToHost));
+        LBP_HIP(hipMemcpy(codes, p->d_codes.get() + (size_t)row0 * p->M, (size_t)n * p->M, hipMemcpyDeviceToHost));
     } catch (const HipErrP &e) {
         return pq_fail(p, e);
     }
@@ -313,7 +288,7 @@ int lb_gpu_pq_encode_device(lb_gpu_pq *p, int64_t n, const float *d_vectors, uin
     try {
         LBP_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
-        launch_pq_encode(p->d_codebooks, p->M, p->K, p->sub, d_vectors, n, d_codes, s);
+        launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_vectors, n, d_codes, s);
         LB_LAUNCH_CHECK();
         LBP_HIP(hipStreamSynchronize(s));
     } catch (const HipErrP &e) {
@@ -353,7 +328,7 @@ int lb_gpu_pq_add_vectors_device(lb_gpu_pq *p, int64_t n, const float *d_vectors
     try {
         LBP_HIP(hipSetDevice(p->device));
         pq_grow(p, p->n + n);
-        launch_pq_encode(p->d_codebooks, p->M, p->K, p->sub, d_vectors, n, p->d_codes + (size_t)p->n * p->M, p->stream);
+        launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_vectors, n, p->d_codes.get() + (size_t)p->n * p->M, p->stream);
         LB_LAUNCH_CHECK();
         LBP_HIP(hipStreamSynchronize(p->stream));
         p->n += n;
@@ -371,7 +346,7 @@ int lb_gpu_pq_decode_device(lb_gpu_pq *p, int64_t n, const uint8_t *d_codes, flo
     try {
         LBP_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
-        launch_pq_decode(p->d_codebooks, p->M, p->K, p->sub, d_codes, n, d_vectors, s);
+        launch_pq_decode(p->d_codebooks.get(), p->M, p->K, p->sub, d_codes, n, d_vectors, s);
         LB_LAUNCH_CHECK();
         LBP_HIP(hipStreamSynchronize(s));
     } catch (const HipErrP &e) {
@@ -410,7 +385,7 @@ int lb_gpu_pq_build_adc_table(lb_gpu_pq *p, const float *query, float *table)
         LBP_HIP(hipSetDevice(p->device));
         Lease dq(p->device, (size_t)p->dims * 4), dt(p->device, (size_t)p->M * p->K * 4);
         LBP_HIP(hipMemcpyAsync(dq.p, query, (size_t)p->dims * 4, hipMemcpyHostToDevice, p->stream));
-        launch_build_adc_table(p->d_codebooks, p->M, p->K, p->sub, dq.as<float>(), 1, dt.as<float>(), p->stream);
+        launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, dq.as<float>(), 1, dt.as<float>(), p->stream);
         LB_LAUNCH_CHECK();
         LBP_HIP(hipMemcpyAsync(table, dt.p, (size_t)p->M * p->K * 4, hipMemcpyDeviceToHost, p->stream));
         LBP_HIP(hipStreamSynchronize(p->stream));
@@ -432,7 +407,7 @@ int lb_gpu_pq_adc_distance_batch(lb_gpu_pq *p, const float *table, int64_t row0,
         Lease dt(p->device, (size_t)p->M * 256 * 4), dr(p->device, (size_t)n * 4);
         LBP_HIP(hipMemcpyAsync(dt.p, table, (size_t)p->M * 256 * 4, hipMemcpyHostToDevice, p->stream));
         CandState cs{};
-        launch_adc_scan(dt.as<float>(), p->M, p->d_codes, row0, row0 + n, 0, nullptr, cs, false, dr.as<float>(), row0,
+        launch_adc_scan(dt.as<float>(), p->M, p->d_codes.get(), row0, row0 + n, 0, nullptr, cs, false, dr.as<float>(), row0,
                         p->stream);
         LB_LAUNCH_CHECK();
         LBP_HIP(hipMemcpyAsync(results, dr.p, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
@@ -455,8 +430,8 @@ int lb_gpu_pq_rerank_device(lb_gpu_pq *p, const float *d_query, const int64_t *d
         LBP_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
         Lease dt(p->device, (size_t)p->M * 256 * 4);
-        launch_build_adc_table(p->d_codebooks, p->M, p->K, p->sub, d_query, 1, dt.as<float>(), s);
-        launch_adc_rerank(dt.as<float>(), p->M, p->d_codes, p->n, d_rows, n, d_dist, d_score, s);
+        launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, d_query, 1, dt.as<float>(), s);
+        launch_adc_rerank(dt.as<float>(), p->M, p->d_codes.get(), p->n, d_rows, n, d_dist, d_score, s);
         LB_LAUNCH_CHECK();
         LBP_HIP(hipStreamSynchronize(s));
     } catch (const HipErrP &e) {
@@ -523,7 +498,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         LBP_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
         const int nqi = (int)nq;
-        // Sampled admission threshold (same reasoning as index.hip: sample_plan): one row in `stride` is scored
+        // Sampled admission threshold (same reasoning as index_search.hip: sample_plan): one row in `stride` is scored
         // exactly, the m-th best sample entry becomes tau, and the codes are walked once.  About m*stride rows
         // pass (4096 at stride 512); fewer than k or more than the list holds is detected by the select and
         // the query is redone by the bootstrap schedule.  Two-level m-th minimum: the sample (195k entries at
@@ -553,25 +528,25 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         int64_t stats[6] = {samp_count ? nqi : 0, 0, 0, 0, 0, 0};
         if (prof) {
             for (auto &e : p->ev)
-                if (!e) LBP_HIP(hipEventCreate(&e));
+                if (!e) LBP_HIP(hipEventCreate(&e.h));
             LBP_HIP(hipEventRecord(p->ev[0], s));
         }
-        launch_build_adc_table(p->d_codebooks, p->M, p->K, p->sub, d_queries, nqi, sc.d_tables, s, prefilter ? sc.d_minrng : nullptr,
-                               sc.cs.flags, prefilter ? sc.d_cand_cnt : nullptr); // (also clears the slots' status words)
+        launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, d_queries, nqi, sc.d_tables.get(), s, prefilter ? sc.d_minrng.get() : nullptr,
+                               sc.cs.flags, prefilter ? sc.d_cand_cnt.get() : nullptr); // (also clears the slots' status words)
         // the search's last select writes the k results AND the slot's status word into pinned host memory (no D2H copy)
-        const EmitArgs em{k, nullptr, d_dist, d_labels, sc.h_flags};
+        const EmitArgs em{k, nullptr, d_dist, d_labels, sc.h_flags.get()};
         // sampled threshold of one query: sample -> m-th best -> tau (cnt = 0); false = no sampled pass for this search
         auto threshold = [&](int q) -> bool {
-            const float *tab = sc.d_tables + (size_t)q * p->M * 256;
-            launch_adc_sample(tab, p->M, p->d_codes, p->n, samp_count, sc.d_samp, s);
-            const uint32_t groups = launch_sample_topm(sc.d_samp, samp_count, samp_m, sc.cs, q, s);
+            const float *tab = sc.d_tables.get() + (size_t)q * p->M * 256;
+            launch_adc_sample(tab, p->M, p->d_codes.get(), p->n, samp_count, sc.d_samp.get(), s);
+            const uint32_t groups = launch_sample_topm(sc.d_samp.get(), samp_count, samp_m, sc.cs, q, s);
             if (!groups) return false;
-            launch_sample_tau(sc.cs, sc.d_slots + q, 1, groups * (uint32_t)samp_m, samp_m, false, s); // sets tau, cnt = 0
+            launch_sample_tau(sc.cs, sc.d_slots.get() + q, 1, groups * (uint32_t)samp_m, samp_m, false, s); // sets tau, cnt = 0
             return true;
         };
         // mode 0: sampled threshold (+ byte-table prefilter), 1: bootstrap chunks, 2: chunks that cannot overflow
         auto scan_query = [&](int q, int mode) {
-            const float *tab = sc.d_tables + (size_t)q * p->M * 256;
+            const float *tab = sc.d_tables.get() + (size_t)q * p->M * 256;
             if (mode == 0 && samp_count) {
                 if (threshold(q)) {
                     if (prefilter) {
@@ -579,38 +554,38 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                         // exactly.  params.ok == 0 (decided on the device: a table with NaN / negative / infinite
                         // entries): nothing is admitted, the select below flags the query (fewer than k entries) and
                         // the host redoes it on the exact schedule.
-                        int *prm = sc.d_params + q * 4;
-                        uint8_t *qtab = sc.d_qtabs + (size_t)q * p->M * 256;
-                        launch_adc_quantise(tab, sc.d_minrng + (size_t)q * p->M * 4, p->M, sc.cs.tau + q, qtab, prm, s);
+                        int *prm = sc.d_params.get() + q * 4;
+                        uint8_t *qtab = sc.d_qtabs.get() + (size_t)q * p->M * 256;
+                        launch_adc_quantise(tab, sc.d_minrng.get() + (size_t)q * p->M * 4, p->M, sc.cs.tau + q, qtab, prm, s);
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[2], s);
-                        launch_adc_prefilter(qtab, prm, p->M, p->d_codes, p->n, sc.d_cand, kCandCap, sc.d_cand_cnt + q, s);
+                        launch_adc_prefilter(qtab, prm, p->M, p->d_codes.get(), p->n, sc.d_cand.get(), kCandCap, sc.d_cand_cnt.get() + q, s);
                         stats[3]++;
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[3], s);
-                        launch_adc_exact_candidates(tab, p->M, p->d_codes, sc.d_cand, sc.d_cand_cnt + q, kCandCap, prm, q,
+                        launch_adc_exact_candidates(tab, p->M, p->d_codes.get(), sc.d_cand.get(), sc.d_cand_cnt.get() + q, kCandCap, prm, q,
                                                     sc.cs, s);
                     } else {
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[2], s);
-                        launch_adc_scan(tab, p->M, p->d_codes, 0, p->n, q, nullptr, sc.cs, false, nullptr, 0, s, nullptr);
+                        launch_adc_scan(tab, p->M, p->d_codes.get(), 0, p->n, q, nullptr, sc.cs, false, nullptr, 0, s, nullptr);
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[3], s);
                     }
                     // the search's last select also writes the k results (redone queries overwrite them below)
-                    launch_select(sc.cs, sc.d_slots + q, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                    launch_select(sc.cs, sc.d_slots.get() + q, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
                     return;
                 }
             }
-            launch_init_cand(sc.cs, sc.d_slots + q, 1, s);
+            launch_init_cand(sc.cs, sc.d_slots.get() + q, 1, s);
             int64_t pos = 0;
             int step = 0;
             while (pos < p->n) {
                 const int64_t end = chunk_end_host(step, pos, p->n, k, cap, mode == 2, /*big_boot=*/true);
                 const bool boot = step == 0;
-                launch_adc_scan(tab, p->M, p->d_codes, pos, end, q, nullptr, sc.cs, boot, nullptr, 0, s);
-                launch_select(sc.cs, sc.d_slots + q, 1, k, boot ? (uint32_t)(end - pos) : 0u, s, 0u,
+                launch_adc_scan(tab, p->M, p->d_codes.get(), pos, end, q, nullptr, sc.cs, boot, nullptr, 0, s);
+                launch_select(sc.cs, sc.d_slots.get() + q, 1, k, boot ? (uint32_t)(end - pos) : 0u, s, 0u,
                               end >= p->n ? &em : nullptr);
                 pos = end;
                 step++;
             }
-            if (p->n == 0) launch_emit_lists(sc.cs, sc.d_slots + q, 1, k, nullptr, d_dist, d_labels, sc.h_flags, s);
+            if (p->n == 0) launch_emit_lists(sc.cs, sc.d_slots.get() + q, 1, k, nullptr, d_dist, d_labels, sc.h_flags.get(), s);
         };
         // two queries share ONE pass over the codes: thresholds and byte tables for both, then the two-query
         // prefilter, then the exact survivors and the select of each.  false = not applicable (run them one by one)
@@ -620,19 +595,19 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             uint8_t *qtab[2];
             for (int j = 0; j < 2; j++) {
                 const int qq = q + j;
-                const float *tab = sc.d_tables + (size_t)qq * p->M * 256;
+                const float *tab = sc.d_tables.get() + (size_t)qq * p->M * 256;
                 if (!threshold(qq)) return false; // (never after the first of the pair succeeded: same counts)
-                prm[j] = sc.d_params + qq * 4;
-                qtab[j] = sc.d_qtabs + (size_t)qq * p->M * 256;
-                launch_adc_quantise(tab, sc.d_minrng + (size_t)qq * p->M * 4, p->M, sc.cs.tau + qq, qtab[j], prm[j], s);
+                prm[j] = sc.d_params.get() + qq * 4;
+                qtab[j] = sc.d_qtabs.get() + (size_t)qq * p->M * 256;
+                launch_adc_quantise(tab, sc.d_minrng.get() + (size_t)qq * p->M * 4, p->M, sc.cs.tau + qq, qtab[j], prm[j], s);
             }
             const bool last = q + 1 == nqi - 1;
             if (prof && last) (void)hipEventRecord(p->ev[2], s);
-            if (!launch_adc_prefilter2(qtab[0], prm[0], sc.d_cand, sc.d_cand_cnt + q, qtab[1], prm[1], sc.d_cand + kCandCap,
-                                       sc.d_cand_cnt + q + 1, p->M, p->d_codes, p->n, kCandCap, s)) {
+            if (!launch_adc_prefilter2(qtab[0], prm[0], sc.d_cand.get(), sc.d_cand_cnt.get() + q, qtab[1], prm[1], sc.d_cand.get() + kCandCap,
+                                       sc.d_cand_cnt.get() + q + 1, p->M, p->d_codes.get(), p->n, kCandCap, s)) {
                 for (int j = 0; j < 2; j++)
-                    launch_adc_prefilter(qtab[j], prm[j], p->M, p->d_codes, p->n, sc.d_cand + (size_t)j * kCandCap, kCandCap,
-                                         sc.d_cand_cnt + q + j, s);
+                    launch_adc_prefilter(qtab[j], prm[j], p->M, p->d_codes.get(), p->n, sc.d_cand.get() + (size_t)j * kCandCap, kCandCap,
+                                         sc.d_cand_cnt.get() + q + j, s);
                 stats[3] += 2;
             } else {
                 stats[2] += 2;
@@ -640,10 +615,10 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             if (prof && last) (void)hipEventRecord(p->ev[3], s);
             for (int j = 0; j < 2; j++) {
                 const int qq = q + j;
-                const float *tab = sc.d_tables + (size_t)qq * p->M * 256;
-                launch_adc_exact_candidates(tab, p->M, p->d_codes, sc.d_cand + (size_t)j * kCandCap, sc.d_cand_cnt + qq, kCandCap,
+                const float *tab = sc.d_tables.get() + (size_t)qq * p->M * 256;
+                launch_adc_exact_candidates(tab, p->M, p->d_codes.get(), sc.d_cand.get() + (size_t)j * kCandCap, sc.d_cand_cnt.get() + qq, kCandCap,
                                             prm[j], qq, sc.cs, s);
-                launch_select(sc.cs, sc.d_slots + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                launch_select(sc.cs, sc.d_slots.get() + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
             }
             return true;
         };
@@ -655,23 +630,23 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             uint32_t *cand[4], *ccnt[4];
             for (int j = 0; j < 4; j++) {
                 const int qq = q + j;
-                const float *tab = sc.d_tables + (size_t)qq * p->M * 256;
+                const float *tab = sc.d_tables.get() + (size_t)qq * p->M * 256;
                 if (!threshold(qq)) return false;
-                int *prm_w = sc.d_params + qq * 4;
-                uint8_t *qt = sc.d_qtabs + (size_t)qq * p->M * 256;
-                launch_adc_quantise(tab, sc.d_minrng + (size_t)qq * p->M * 4, p->M, sc.cs.tau + qq, qt, prm_w, s);
+                int *prm_w = sc.d_params.get() + qq * 4;
+                uint8_t *qt = sc.d_qtabs.get() + (size_t)qq * p->M * 256;
+                launch_adc_quantise(tab, sc.d_minrng.get() + (size_t)qq * p->M * 4, p->M, sc.cs.tau + qq, qt, prm_w, s);
                 prm[j] = prm_w; qtab[j] = qt;
-                cand[j] = sc.d_cand + (size_t)j * kCandCap;
-                ccnt[j] = sc.d_cand_cnt + qq;
+                cand[j] = sc.d_cand.get() + (size_t)j * kCandCap;
+                ccnt[j] = sc.d_cand_cnt.get() + qq;
             }
             const bool last = q + 3 == nqi - 1;
             if (prof && last) (void)hipEventRecord(p->ev[2], s);
-            if (!launch_adc_prefilter4(qtab, prm, cand, ccnt, p->M, p->d_codes, p->n, kCandCap, s)) {
+            if (!launch_adc_prefilter4(qtab, prm, cand, ccnt, p->M, p->d_codes.get(), p->n, kCandCap, s)) {
                 for (int j = 0; j < 4; j += 2)
                     if (!launch_adc_prefilter2(qtab[j], prm[j], cand[j], ccnt[j], qtab[j + 1], prm[j + 1], cand[j + 1], ccnt[j + 1], p->M,
-                                               p->d_codes, p->n, kCandCap, s)) {
+                                               p->d_codes.get(), p->n, kCandCap, s)) {
                         for (int u = j; u < j + 2; u++)
-                            launch_adc_prefilter(qtab[u], prm[u], p->M, p->d_codes, p->n, cand[u], kCandCap, ccnt[u], s);
+                            launch_adc_prefilter(qtab[u], prm[u], p->M, p->d_codes.get(), p->n, cand[u], kCandCap, ccnt[u], s);
                         stats[3] += 2;
                     } else {
                         stats[2] += 2;
@@ -682,9 +657,9 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             if (prof && last) (void)hipEventRecord(p->ev[3], s);
             for (int j = 0; j < 4; j++) {
                 const int qq = q + j;
-                const float *tab = sc.d_tables + (size_t)qq * p->M * 256;
-                launch_adc_exact_candidates(tab, p->M, p->d_codes, cand[j], ccnt[j], kCandCap, prm[j], qq, sc.cs, s);
-                launch_select(sc.cs, sc.d_slots + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                const float *tab = sc.d_tables.get() + (size_t)qq * p->M * 256;
+                launch_adc_exact_candidates(tab, p->M, p->d_codes.get(), cand[j], ccnt[j], kCandCap, prm[j], qq, sc.cs, s);
+                launch_select(sc.cs, sc.d_slots.get() + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
             }
             return true;
         };
@@ -714,11 +689,11 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         if (samp_count) {
             bool any = false;
             for (int q = 0; q < nqi; q++)
-                if (sc.h_flags[q] & (1u | 4u)) { scan_query(q, 1); stats[4]++; any = true; } // the sampled threshold missed
+                if (sc.h_flags.get()[q] & (1u | 4u)) { scan_query(q, 1); stats[4]++; any = true; } // the sampled threshold missed
             if (any) read_flags();
         }
         for (int q = 0; q < nqi; q++)
-            if (sc.h_flags[q] & 1u) { scan_query(q, 2); stats[5]++; } // chunks that cannot overflow the list
+            if (sc.h_flags.get()[q] & 1u) { scan_query(q, 2); stats[5]++; } // chunks that cannot overflow the list
         LB_LAUNCH_CHECK();
         if (prof) LBP_HIP(hipEventRecord(p->ev[1], s));
         LBP_HIP(hipStreamSynchronize(s));

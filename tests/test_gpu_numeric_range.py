@@ -139,7 +139,7 @@ def test_dot_product_with_a_few_very_long_rows_stays_on_the_matrix_cores(oracle)
 def test_rounding_errors_that_all_point_the_same_way(oracle, metric):
     """Every element of the corpus and of the queries sits just above a midpoint between two fp16 values, all positive: the image
     rounds every element UP by half an ulp, so the candidate keys' errors add coherently instead of cancelling -- the worst case
-    for an error bound taken from the measured residual NORMS (index.hip, key_bound: gamma(q) = ... rho_x ... rho_q).  The lists
+    for an error bound taken from the measured residual NORMS (index_search.hip, key_bound: gamma(q) = ... rho_x ... rho_q).  The lists
     must still be the oracle's; a bound that were only statistical would lose neighbours here."""
     gpu_or_skip()
     rng = np.random.default_rng(400 + metric)

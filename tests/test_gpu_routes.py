@@ -1,4 +1,4 @@
-"""Path selection is a cost choice between exact routes (index.hip: choose_route): on a sub-grid of dimensions, corpus
+"""Path selection is a cost choice between exact routes (index_search.hip: choose_route): on a sub-grid of dimensions, corpus
 sizes and batch sizes the route the library picks must be within 10 % (+ 40 us: launch noise on the small points) of the
 best route it can be forced onto.  Forcing a route is a diagnostic-build switch (LB_FORCE_ROUTE), so this test runs on
 liblongbow_gpu_diag.so; tools/route_grid.py prints the full grid the constants were fitted to."""

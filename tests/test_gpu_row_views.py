@@ -1,6 +1,6 @@
 """Predicate masks and row views at their edges: kernels_filter.hip (match, and-bytes, the three compaction kernels) and
-filter_column / lb_gpu_index_set_filter / rebuild_rowmap / finish_add / row_view in index.hip, against the oracle.  Inputs
-come from tests/row_view_cases.py; tests/test_row_view_semantics.py pins the oracle on the same inputs on the CPU.  Every
+filter_column / lb_gpu_index_set_filter / rebuild_rowmap / finish_add in index.hip and row_view in lb_index.h, against the
+oracle.  Inputs come from tests/row_view_cases.py; tests/test_row_view_semantics.py pins the oracle on the same inputs on the CPU.  Every
 comparison is exact: mask bytes, label sets, and result lists bit for bit."""
 import numpy as np
 import pytest
@@ -373,7 +373,7 @@ def route_masks(n):
             "98 % of any non-zero byte": rc.byte_mask(np.random.default_rng(9), n, 0.98)}
 
 
-# (mode, batch size, kinds of idx.last_route -- choose_route in index.hip)
+# (mode, batch size, kinds of idx.last_route -- choose_route in index_search.hip)
 ROUTES = [
     ("exact scan", CAND_AUTO, 3, (0,)),
     ("narrow 32", CAND_AUTO, 20, (1,)),

@@ -56,7 +56,7 @@ def test_calculate_adaptive_limit_matches_oracle(oracle):
 
 
 def test_sample_plan_invariants():
-    """the sampled-threshold plan (index.hip: sample_plan) over a grid of corpus sizes, k and list capacities:
+    """the sampled-threshold plan (index_search.hip: sample_plan) over a grid of corpus sizes, k and list capacities:
     the sample fits one list, m is in [8, 64], the too-tight tail is below 1e-6 and mean + 5 sigma admitted
     rows fit the list -- checked on the host, no GPU needed"""
     import ctypes as C

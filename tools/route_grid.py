@@ -2,7 +2,7 @@
 """Which kernel should generate the candidates of a batch?  Times every route the library can be forced onto
 (diagnostic build: LB_FORCE_ROUTE) over a grid of dimensions, corpus sizes and batch sizes, next to the route the
 library picks by itself, and prints how far the pick is from the best forced route.  The cost-model constants of
-index.hip (choose_route) are fitted to this table; tests/test_gpu_routes.py asserts the <= 10 % bound on a sub-grid.
+index_search.hip (choose_route) are fitted to this table; tests/test_gpu_routes.py asserts the <= 10 % bound on a sub-grid.
 usage: LB_GPU_SO=longbow_amd/liblongbow_gpu_diag.so python tools/route_grid.py [--quick] [--json out.json]"""
 import ctypes as C, json, os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
