@@ -371,6 +371,43 @@ int lb_gpu_pq_last_search_stats(const lb_gpu_pq *p, int64_t out[6]);
 int lb_gpu_pq_set_profiling(lb_gpu_pq *p, int enable);
 int lb_gpu_pq_last_timing(const lb_gpu_pq *p, float ms[2]);
 
+/* ---- PQ training --------------------------------------------------------------
+ * pq.(*PQEncoder).Train (encoder.go:38-73): TrainKMeans (kmeans.go:64-151) per subspace.  vectors: n rows of f32[dims];
+ * subspace m trains on the sub-vectors v_i = row_i[m*sub, (m+1)*sub), sub = dims / M, exactly as TrainKMeans(., n, sub, K,
+ * max_iter) does (TrainKMeans itself is the case M = 1):
+ *   init    centroid c = the copy of row init_rows[m*K + c]  (init_rows: HOST pointer in both entry points; duplicates allowed)
+ *   E-step  dist = simd.L2Squared(v_i, cent_c) (four f32 chains over i mod 4, tail in chain 0, ((s0+s1)+s2)+s3, no sqrt);
+ *           the row goes to the first c with dist < best, best starting at FLT_MAX.  (Not lb_gpu_pq_encode's argmin, which
+ *           compares the rounded square roots.)  A row with no such centroid (NaN, overflow) makes the reference panic;
+ *           here the call returns LB_ERR_INVALID_ARG and writes nothing.
+ *   M-step  sums[c][j] += v_i[j] as ONE f32 chain over the cluster's members in ascending row order, then
+ *           cent = sum / float32(count); an empty cluster takes the copy of a drawn row.
+ *   stop    after an iteration with iter > 0 && changed < n/1000 + 1 (rows whose assignment differs from the previous
+ *           iteration's, assignments starting at -1), or after max_iter iterations; max_iter == 0 returns the init rows.
+ *           Subspaces stop independently; iters_out[m] (nullable) = iterations subspace m ran.
+ * The reference draws from Go's unseeded global source, so its draws cannot be reproduced; they are restated counter-based:
+ *   mix64(z): z = (z ^ z>>30) * 0xBF58476D1CE4E5B9; z = (z ^ z>>27) * 0x94D049BB133111EB; z ^ z>>31   (splitmix64's finaliser)
+ *   draw(seed, m, t) = mix64(mix64(seed + m) + (t + 1) * 0x9E3779B97F4A7C15)                          (u64 arithmetic)
+ *   init_rows == NULL: subspace m's rows are the first K entries of a Fisher-Yates shuffle of [0, n):
+ *                      for i in 0..K-1: j = i + draw(seed, m, i) mod (n - i), swap entries i and j
+ *   empty cluster c in iteration it: row draw(seed, m, K + it*K + c) mod n
+ * blob receives the persistence.go layout that lb_gpu_pq_new reads; blob_len must equal lb_gpu_pq_blob_bytes(dims, M, K)
+ * (12 + M*K*(dims/M)*4; 0 for dims, M or K <= 0 or dims % M != 0).  K is a run-time bound in 1..256 (the reference's own
+ * tests train k = 3): a blob with K != 256 serialises correctly and is still refused by lb_gpu_pq_new.
+ * Checked before a device is touched, in this order: LB_ERR_INVALID_ARG (NULL vectors / blob, M <= 0, dims % M != 0, n < K,
+ * max_iter < 0, blob_len, an init_rows entry outside [0, n)); LB_ERR_UNSUPPORTED (K outside 1..256, dims > LB_MAX_DIM,
+ * n >= 2^31); LB_ERR_NO_DEVICE.  All rows stay resident for the iterations (n*dims*4 bytes, plus 8 bytes per row and
+ * subspace): LB_ERR_OOM if they do not fit.  ctx (nullable) is polled once per iteration. */
+int lb_gpu_pq_train(int device, int dims, int M, int K, int64_t n, const float *vectors, int max_iter, uint64_t seed,
+                    const int64_t *init_rows, uint8_t *blob, size_t blob_len, int32_t *iters_out, const lb_cancel *ctx);
+int lb_gpu_pq_train_device(int device, int dims, int M, int K, int64_t n, const float *d_vectors, int max_iter, uint64_t seed,
+                           const int64_t *init_rows, uint8_t *blob, size_t blob_len, int32_t *iters_out, void *stream,
+                           const lb_cancel *ctx);
+size_t lb_gpu_pq_blob_bytes(int dims, int M, int K);
+/* instrumentation (tools/pq_train_bench.py): HIP-event times of the first iteration of the last training call of this
+ * process that ran one: ms[0] E-step, ms[1] ordering (scan + scatter), ms[2] M-step. */
+int lb_gpu_pq_train_last_timing(float ms[3]);
+
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:
  * inputs [S][nq][k] ascending per (shard, query) (padding label -1 / FLT_MAX allowed),

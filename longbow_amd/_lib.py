@@ -125,6 +125,10 @@ SIGNATURES = [
     ("lb_gpu_pq_adc_distance_batch", _i, [_vp, _vp, _i64, _i64, _vp]),
     ("lb_gpu_pq_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_pq_search_device", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_pq_train", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp]),
+    ("lb_gpu_pq_train_device", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
+    ("lb_gpu_pq_blob_bytes", _sz, [_i, _i, _i]),
+    ("lb_gpu_pq_train_last_timing", _i, [_vp]),
     ("lb_gpu_merge_topk_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_packed_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_rrf_fuse_device", _i, [_i, _i64, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),

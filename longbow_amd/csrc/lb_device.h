@@ -521,6 +521,31 @@ void launch_pq_encode(const float *codebooks, int M, int K, int sub, const float
                       hipStream_t s);
 void launch_pq_decode(const float *codebooks, int M, int K, int sub, const uint8_t *codes, int64_t n, float *out,
                       hipStream_t s);
+// PQ training (kernels_pq_train.hip): Lloyd k-means per subspace, all M subspaces in every launch.  The state as the kernels
+// take it (by value); n < 2^31, K <= 256.
+constexpr int KM_CHUNK = 4096; // rows per unit of the stable ordering (a multiple of the E-step's 256 rows)
+struct KmState {
+    const float *X;       // [n][D] rows, resident for the whole call
+    int64_t n, nchunks;   // nchunks = ceil(n / KM_CHUNK)
+    int D, M, K, sub;
+    float *cent;          // [M][K][sub]
+    int32_t *assign;      // [M][n], -1 before the first iteration
+    uint32_t *order;      // [M][n] rows sorted by (assignment, row)
+    uint32_t *chunk_hist; // [M][nchunks][K] zero between iterations
+    uint32_t *count, *start; // [M][K]
+    uint32_t *changed;    // [M]
+    uint32_t *done;       // [M] 1 = the subspace has stopped: every launch skips it
+    int32_t *iters;       // [M] iterations run
+    uint32_t *bad;        // [1] a row had no centroid below FLT_MAX: the call fails
+};
+uint64_t km_draw(uint64_t seed, uint64_t m, uint64_t t);
+void launch_km_init(const KmState &st, const int64_t *d_init_rows, hipStream_t s);
+void launch_km_estep(const KmState &st, hipStream_t s);
+void launch_km_order(const KmState &st, hipStream_t s);
+void launch_km_mstep(const KmState &st, uint64_t seed, int it, hipStream_t s);
+// h_state (pinned): {subspaces that go on, bad}
+void launch_km_finish(const KmState &st, int it, uint32_t thr, uint32_t *h_state, hipStream_t s);
+
 // byte table + integer admission bound of one query: params = {s_tau, ok}; minrng from launch_build_adc_table
 void launch_adc_quantise(const float *table, const float *minrng, int M, const uint64_t *tau, uint8_t *qtab, int *params,
                          hipStream_t s);

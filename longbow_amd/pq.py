@@ -1,9 +1,9 @@
 """Mirror of internal/pq's query-side interface (the ADC path), computed by HIP kernels.
 
 PQEncoder.{BuildADCTable, ADCDistanceBatch, Serialize/Deserialize blob}
-(internal/pq/adc_table.go:15-72, persistence.go:9-73) and Encode / Decode (encoder.go:76-158).
-Training (k-means, unseeded) is an offline step in the reference and stays out of the GPU path:
-codebooks are an input.
+(internal/pq/adc_table.go:15-72, persistence.go:9-73), Encode / Decode (encoder.go:76-158) and Train
+(encoder.go:38-73: TrainKMeans per subspace, kmeans.go:64-151; the unseeded draws of the reference are
+restated as the counter-based ones include/longbow_gpu.h documents).
 """
 import ctypes as C
 import struct
@@ -20,8 +20,50 @@ def serialize_codebooks(codebooks):
     return struct.pack("<III", M * sub, M, K) + cb.astype("<f4").tobytes()
 
 
+def _train_args(dims, M, K, n, init_rows):
+    size = 12 + M * K * (dims // M) * 4 if M > 0 and K >= 0 and dims > 0 else 12
+    blob = np.zeros(size, np.uint8)
+    iters = np.zeros(max(M, 1), np.int32)
+    rows = None
+    if init_rows is not None:
+        rows = np.ascontiguousarray(init_rows, np.int64).reshape(-1)
+        if rows.size != M * K:
+            raise ValueError("init_rows must hold M*K rows")
+    return blob, iters, rows
+
+
+def train(vectors, M, K=256, max_iter=20, seed=0, init_rows=None, device=0, ctx=None):
+    """pq.(*PQEncoder).Train (encoder.go:38-73) on the GPU: exact Lloyd k-means per subspace (lb_gpu_pq_train).
+    vectors [n, dims] f32; init_rows [M, K] rows whose copies are the first centroids (None: drawn from seed).
+    Returns (blob, iters): the persistence.go blob and the iterations each subspace ran."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2 or v.shape[0] == 0:
+        raise ValueError("empty training data")  # encoder.go:40-42
+    n, dims = v.shape
+    lib = _lib.require_gpu(device)
+    blob, iters, rows = _train_args(dims, M, K, n, init_rows)
+    _lib.check(lib.lb_gpu_pq_train(device, dims, M, K, n, v.ctypes.data, max_iter, seed, rows.ctypes.data if rows is not None else None,
+                                   blob.ctypes.data, blob.size, iters.ctypes.data, ctx._h if ctx is not None else None))
+    return blob.tobytes(), iters[:M]
+
+
+def train_device(n, d_vectors, dims, M, K=256, max_iter=20, seed=0, init_rows=None, device=0, stream=None, ctx=None):
+    """train() over n rows already resident on the device (d_vectors: device address); init_rows stays a host array"""
+    lib = _lib.require_gpu(device)
+    blob, iters, rows = _train_args(dims, M, K, n, init_rows)
+    _lib.check(lib.lb_gpu_pq_train_device(device, dims, M, K, n, d_vectors, max_iter, seed, rows.ctypes.data if rows is not None else None,
+                                          blob.ctypes.data, blob.size, iters.ctypes.data, stream, ctx._h if ctx is not None else None))
+    return blob.tobytes(), iters[:M]
+
+
 class PQEncoder:
-    """Query-side PQEncoder on the GPU, built from the reference's serialised blob."""
+    """PQEncoder on the GPU, built from the reference's serialised blob (or trained: PQEncoder.Train)."""
+
+    @classmethod
+    def Train(cls, vectors, M, max_iter=20, seed=0, init_rows=None, device=0):
+        """NewPQEncoder(dims, M, 256) + Train(vectors): a ready encoder holding the trained codebooks"""
+        blob, _ = train(vectors, M, 256, max_iter, seed, init_rows, device)
+        return cls(blob, device)
 
     def __init__(self, blob, device=0, lib=None):
         lib = lib or _lib.require_gpu(device)
