@@ -408,6 +408,63 @@ size_t lb_gpu_pq_blob_bytes(int dims, int M, int K);
  * process that ran one: ms[0] E-step, ms[1] ordering (scan + scatter), ms[2] M-step. */
 int lb_gpu_pq_train_last_timing(float ms[3]);
 
+/* ---- binary quantisation: sign-bit codes and exact Hamming k-NN ------------------------
+ * store.BQEncoder (internal/store/binary_quantization.go) and simd.HammingDistance (internal/simd/simd_bitops.go:40-55),
+ * which the HNSW build and search use as float32(HammingDistance(q, t)) when BQEnabled is set
+ * (internal/store/arrow_hnsw_bulk.go:420-476).  Everything here is integer-exact: there is no tolerance and no fallback.
+ *   layout    W = (dims + 63) / 64 little-endian uint64 words per row, row-major; bit i % 64 of word i / 64 is dimension i
+ *             (binary_quantization.go:34-45).  CodeSize() is lb_gpu_bq_words.
+ *   encode    the bit is set iff v[i] > 0 as an f32 comparison (binary_quantization.go:41): +0, -0, NaN, every negative value
+ *             and -inf give 0, +inf and positive denormals give 1 (denormals are not flushed); pad bits of the last word are 0.
+ *   distance  sum over all W whole words of popcount(a[w] ^ b[w]) (simd_bitops.go:40-55): pad bits that a caller put into
+ *             codes passed to add_codes count.  Integer results are int32; searches and rerank report float32(distance),
+ *             exact because the distance is at most 8192.
+ *   score     1.0f - float32(h) / float32(dims) in f32 operations (ScoreToFloat32, binary_quantization.go:69-71).
+ *   decode    bit 1 -> 1.0f, bit 0 -> -1.0f, dims values per row (binary_quantization.go:80-92).
+ *   search    exact k-NN of each query over all stored codes, ascending by (distance, row position): the lowest position
+ *             wins every tie (as lb_gpu_index_search).  Labels are row positions.  Fewer than k rows: label -1, dist FLT_MAX.
+ *   limits    dims in 1..LB_MAX_DIM, k in 1..LB_MAX_K, fewer than 2^31 rows per handle: LB_ERR_UNSUPPORTED beyond.
+ * Argument checks answer before a device is touched: LB_ERR_INVALID_ARG (NULL handle or pointer, dims <= 0, k <= 0, negative
+ * counts, rows outside the stored ones) before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, the order of lb_gpu_pq_train.  A
+ * refused call writes nothing.  Host pointers are borrowed for the call; d_ pointers are device memory.  Searches, reads and
+ * rerank are thread-safe against each other and exclusive against reserve and the add calls. */
+typedef struct lb_gpu_bq lb_gpu_bq;
+lb_gpu_bq *lb_gpu_bq_new(int device, int dims, int *out_status);
+void lb_gpu_bq_free(lb_gpu_bq *p);
+const char *lb_gpu_bq_last_error(const lb_gpu_bq *p);
+int lb_gpu_bq_dims(const lb_gpu_bq *p);
+int lb_gpu_bq_words(const lb_gpu_bq *p);
+int64_t lb_gpu_bq_ntotal(const lb_gpu_bq *p);
+int lb_gpu_bq_reserve(lb_gpu_bq *p, int64_t n_total);
+/* append n codes u64[n*W] as they are (pad bits included) */
+int lb_gpu_bq_add_codes(lb_gpu_bq *p, int64_t n, const uint64_t *codes);
+int lb_gpu_bq_add_codes_device(lb_gpu_bq *p, int64_t n, const uint64_t *d_codes);
+/* stored rows [row0, row0+n) -> u64[n*W] */
+int lb_gpu_bq_get_codes(lb_gpu_bq *p, int64_t row0, int64_t n, uint64_t *codes);
+/* BQEncoder.Encode for n rows of f32[dims] -> u64[n*W]; nothing is stored */
+int lb_gpu_bq_encode(lb_gpu_bq *p, int64_t n, const float *vectors, uint64_t *codes);
+int lb_gpu_bq_encode_device(lb_gpu_bq *p, int64_t n, const float *d_vectors, uint64_t *d_codes, void *stream);
+/* encode n rows and append their codes */
+int lb_gpu_bq_add_vectors(lb_gpu_bq *p, int64_t n, const float *vectors);
+int lb_gpu_bq_add_vectors_device(lb_gpu_bq *p, int64_t n, const float *d_vectors);
+/* BQEncoder.Decode: u64[n*W] -> f32[n*dims] */
+int lb_gpu_bq_decode(lb_gpu_bq *p, int64_t n, const uint64_t *codes, float *vectors);
+/* BQEncoder.HammingDistanceBatch (binary_quantization.go:56-60) of qcode u64[W] over the stored rows [row0, row0+n) */
+int lb_gpu_bq_hamming_batch(lb_gpu_bq *p, const uint64_t *qcode, int64_t row0, int64_t n, int32_t *results);
+/* the stored rows rows[0..n): dist = float32(distance), score (nullable) = ScoreToFloat32; rows outside [0, ntotal) report
+ * FLT_MAX / 0, as lb_gpu_pq_rerank */
+int lb_gpu_bq_rerank(lb_gpu_bq *p, const uint64_t *qcode, const int64_t *rows, int64_t n, float *dist, float *score);
+int lb_gpu_bq_rerank_device(lb_gpu_bq *p, const uint64_t *d_qcode, const int64_t *d_rows, int64_t n, float *d_dist, float *d_score,
+                            void *stream);
+/* k-NN of nq query codes u64[nq*W] -> dist f32[nq*k], labels i64[nq*k] */
+int lb_gpu_bq_search_codes(lb_gpu_bq *p, int64_t nq, const uint64_t *qcodes, int k, float *dist, int64_t *labels);
+/* k-NN of nq queries f32[nq*dims], which are encoded on the device first.  ctx (nullable) is polled before every launch; one
+ * that has already fired returns LB_ERR_CANCELLED / LB_ERR_DEADLINE without launching anything. */
+int lb_gpu_bq_search(lb_gpu_bq *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels);
+int lb_gpu_bq_search_ctx(lb_gpu_bq *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_bq_search_device_ctx(lb_gpu_bq *p, int64_t nq, const float *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
+                                const lb_cancel *ctx);
+
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:
  * inputs [S][nq][k] ascending per (shard, query) (padding label -1 / FLT_MAX allowed),

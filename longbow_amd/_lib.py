@@ -129,6 +129,28 @@ SIGNATURES = [
     ("lb_gpu_pq_train_device", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("lb_gpu_pq_blob_bytes", _sz, [_i, _i, _i]),
     ("lb_gpu_pq_train_last_timing", _i, [_vp]),
+    ("lb_gpu_bq_new", _vp, [_i, _i, _ip]),
+    ("lb_gpu_bq_free", None, [_vp]),
+    ("lb_gpu_bq_last_error", C.c_char_p, [_vp]),
+    ("lb_gpu_bq_dims", _i, [_vp]),
+    ("lb_gpu_bq_words", _i, [_vp]),
+    ("lb_gpu_bq_ntotal", _i64, [_vp]),
+    ("lb_gpu_bq_reserve", _i, [_vp, _i64]),
+    ("lb_gpu_bq_add_codes", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_bq_add_codes_device", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_bq_get_codes", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_bq_encode", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_bq_encode_device", _i, [_vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_bq_add_vectors", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_bq_add_vectors_device", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_bq_decode", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_bq_hamming_batch", _i, [_vp, _vp, _i64, _i64, _vp]),
+    ("lb_gpu_bq_rerank", _i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    ("lb_gpu_bq_rerank_device", _i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_bq_search_codes", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_bq_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_bq_search_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_bq_search_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_packed_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_rrf_fuse_device", _i, [_i, _i64, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
@@ -215,13 +237,13 @@ def require_gpu(device=0):
     return lib
 
 
-def check(rc, handle=None, pq=False, lib=None):
+def check(rc, handle=None, pq=False, lib=None, bq=False):
     if rc == LB_OK:
         return
     msg = ""
     if handle:
         lib = lib or load()
-        raw = lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
+        raw = lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
         msg = raw.decode() if raw else ""
     if rc == 3:
         raise GPUNotAvailable(rc, msg)

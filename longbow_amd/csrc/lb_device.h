@@ -565,6 +565,38 @@ void launch_adc_exact_candidates(const float *table, int M, const uint8_t *codes
 void launch_adc_rerank(const float *table, int M, const uint8_t *codes, int64_t n, const int64_t *rows, int64_t nrows,
                        float *out_dist, float *out_score, hipStream_t s);
 
+// binary-quantised codes (kernels_bq.hip): W = (dims + 63) / 64 u64 words per row, bit i % 64 of word i / 64 is dimension i
+void launch_bq_encode(const float *X, int64_t n, int dims, uint64_t *codes, hipStream_t s);
+void launch_bq_decode(const uint64_t *codes, int64_t n, int dims, float *out, hipStream_t s);
+// out[i] = Hamming distance of stored row row0 + i to qcode, over whole words
+void launch_bq_batch(const uint64_t *codes, int W, const uint64_t *qcode, int64_t row0, int64_t n, int32_t *out, hipStream_t s);
+// gathered rows: dist = float32(distance), score = 1 - dist / dims (nullable); rows outside [0, ntotal): FLT_MAX / 0
+void launch_bq_rerank(const uint64_t *codes, int W, int dims, int64_t ntotal, const uint64_t *qcode, const int64_t *rows, int64_t n,
+                      float *dist, float *score, hipStream_t s);
+// exact k-NN by counting: the state of one batch of queries as the kernels take it (by value); n in 1..2^31-1, k <= 2048.
+// hist -> thresh -> count -> scan -> emit -> finish, each a launch; hist must be zero before the first.
+constexpr int BQ_MAX_BLOCKS = 2048; // workgroups that share the rows (each a contiguous range of whole 256-row tiles)
+struct BqSearch {
+    const uint64_t *codes; // [n][W]
+    int64_t n;
+    int W;
+    const uint64_t *Q;     // [nq][W]
+    int nq, k;
+    int nblk, tpb;         // bq_search_plan(n): workgroups and tiles per workgroup
+    uint32_t *hist;        // [nq][64*W + 1]
+    uint32_t *thr;         // [nq][2]: threshold t, rows at t that are still needed
+    uint32_t *cnt;         // [nq][nblk][2]: rows below t, rows at t; after the scan their exclusive prefixes
+    uint32_t *tot;         // [nq]: rows below t
+    uint64_t *keys;        // [nq][k]: d << 32 | row, unordered
+};
+void bq_search_plan(int64_t n, int *nblk, int *tpb);
+void launch_bq_hist(const BqSearch &a, hipStream_t s);
+void launch_bq_thresh(const BqSearch &a, hipStream_t s);
+void launch_bq_count(const BqSearch &a, hipStream_t s);
+void launch_bq_scan(const BqSearch &a, hipStream_t s);
+void launch_bq_emit(const BqSearch &a, hipStream_t s);
+void launch_bq_finish(const BqSearch &a, float *dist, int64_t *labels, hipStream_t s); // n == 0 allowed: all padding
+
 // predicate masks (kernels_filter.hip): op = simd.CompareOp value; validity = Arrow LSB bitmap or null
 void launch_match_int64(const int64_t *src, int64_t n, int64_t val, int op, const uint8_t *validity,
                         int64_t valid_offset, uint8_t *dst, int combine, hipStream_t s);
