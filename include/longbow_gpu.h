@@ -465,6 +465,77 @@ int lb_gpu_bq_search_ctx(lb_gpu_bq *p, int64_t nq, const float *queries, int k, 
 int lb_gpu_bq_search_device_ctx(lb_gpu_bq *p, int64_t nq, const float *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
                                 const lb_cancel *ctx);
 
+/* ---- scalar quantisation: uint8 codes and exact integer k-NN ----------------------------
+ * store.SQ8Encoder (internal/store/scalar_quantization.go) and simd.EuclideanDistanceSQ8 (internal/simd/sq8.go:45-66): one
+ * uint8 per dimension between per-dimension bounds.  Codes, integer distances and labels are exact: no tolerance, no fallback.
+ *   layout    dims bytes per row, row-major, in every buffer a caller passes or receives (the store pads rows to 16 bytes
+ *             with zero bytes internally; get_codes strips them).  Device code pointers are 16-byte aligned.
+ *   bounds    train = TrainSQ8Encoder (:89-134): per dimension min and max start at row 0 and later rows replace them through
+ *             v < min / v > max, so a NaN in a later row is ignored and a NaN in row 0 stays; min == max becomes
+ *             max = min + 1e-7f; then Validate (:29-52): min >= max in any dimension is LB_ERR_INVALID_ARG ("min must be less
+ *             than max for all dimensions": a constant column of magnitude 2.0 or more fails), NaN bounds pass.  No rows:
+ *             LB_ERR_INVALID_ARG.  Where a column holds both -0 and +0 a zero bound may carry either sign: it compares equal
+ *             to the reference's and changes no code and no decoded value.  The result is the same from run to run.
+ *             set_bounds = NewSQ8Encoder (:62-86) on given bounds.  scale = 255 / (max - min) and invScale = (max - min) / 255
+ *             are f32 divisions.  Bounds cannot change once the handle holds rows.
+ *   encode    EncodeInto (:155-170): v clamped by `if v < min: min, else if v > max: max` (a NaN passes both), then
+ *             uint8((v - min) * scale), subtraction and product each rounded once in f32, truncated toward zero.  Go leaves
+ *             the conversion of a value outside the target type to the platform; a NaN product gives code 0 on amd64 and
+ *             arm64 alike, and an infinite product (bounds so close that scale overflows) gives 0 as on amd64.
+ *   decode    DecodeInto (:180-184): min + float32(q) * invScale, the product rounded before the sum (the amd64 form).
+ *   distance  S = sum (a_i - b_i)^2 as int32 (EuclideanSQ8Generic == SQ8DistanceFast, :208-216); at most 65025 * 8192 < 2^31.
+ *             euclid = SQ8EuclideanDistance (:192-203): the sequential f32 sum of diff * diff over the decoded values, then
+ *             float32(sqrt(float64(sum))).
+ *   search    exact k-NN over all stored codes, ascending by (S, row position): the lowest position wins every tie.  The
+ *             reported distance is float32(S) (EuclideanDistanceSQ8Batch, internal/simd/simd.go:170-182): two different S may
+ *             round to one float, the order is the integers'.  Fewer than k rows: label -1, dist FLT_MAX.
+ *   limits    dims in 1..LB_MAX_DIM, k in 1..LB_MAX_K, fewer than 2^31 rows per handle: LB_ERR_UNSUPPORTED beyond.
+ * Calls on codes alone (add_codes, get_codes, distance_batch, rerank without euclid, search_codes) work on an untrained
+ * handle; whatever encodes or decodes answers LB_ERR_INVALID_ARG ("config must be trained ...") on one.  Argument checks
+ * answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a refused call
+ * writes nothing.  Host pointers are borrowed for the call; d_ pointers are device memory.  Searches, reads and the codec are
+ * thread-safe against each other and exclusive against reserve, the add calls, set_bounds and train. */
+typedef struct lb_gpu_sq8 lb_gpu_sq8;
+lb_gpu_sq8 *lb_gpu_sq8_new(int device, int dims, int *out_status); /* untrained */
+void lb_gpu_sq8_free(lb_gpu_sq8 *p);
+const char *lb_gpu_sq8_last_error(const lb_gpu_sq8 *p);
+int lb_gpu_sq8_dims(const lb_gpu_sq8 *p);
+int64_t lb_gpu_sq8_ntotal(const lb_gpu_sq8 *p);
+int lb_gpu_sq8_reserve(lb_gpu_sq8 *p, int64_t n_total);
+int lb_gpu_sq8_trained(const lb_gpu_sq8 *p);
+int lb_gpu_sq8_set_bounds(lb_gpu_sq8 *p, const float *min, const float *max); /* f32[dims] each */
+int lb_gpu_sq8_train(lb_gpu_sq8 *p, int64_t n, const float *vectors);         /* f32[n*dims] */
+int lb_gpu_sq8_train_device(lb_gpu_sq8 *p, int64_t n, const float *d_vectors);
+int lb_gpu_sq8_get_bounds(lb_gpu_sq8 *p, float *min, float *max);
+/* SQ8Encoder.Encode for n rows of f32[dims] -> u8[n*dims]; nothing is stored */
+int lb_gpu_sq8_encode(lb_gpu_sq8 *p, int64_t n, const float *vectors, uint8_t *codes);
+int lb_gpu_sq8_encode_device(lb_gpu_sq8 *p, int64_t n, const float *d_vectors, uint8_t *d_codes, void *stream);
+/* SQ8Encoder.Decode: u8[n*dims] -> f32[n*dims] */
+int lb_gpu_sq8_decode(lb_gpu_sq8 *p, int64_t n, const uint8_t *codes, float *vectors);
+/* append n codes u8[n*dims] as they are */
+int lb_gpu_sq8_add_codes(lb_gpu_sq8 *p, int64_t n, const uint8_t *codes);
+int lb_gpu_sq8_add_codes_device(lb_gpu_sq8 *p, int64_t n, const uint8_t *d_codes);
+/* encode n rows and append their codes */
+int lb_gpu_sq8_add_vectors(lb_gpu_sq8 *p, int64_t n, const float *vectors);
+int lb_gpu_sq8_add_vectors_device(lb_gpu_sq8 *p, int64_t n, const float *d_vectors);
+/* stored rows [row0, row0+n) -> u8[n*dims] */
+int lb_gpu_sq8_get_codes(lb_gpu_sq8 *p, int64_t row0, int64_t n, uint8_t *codes);
+/* S of qcode u8[dims] against the stored rows [row0, row0+n) */
+int lb_gpu_sq8_distance_batch(lb_gpu_sq8 *p, const uint8_t *qcode, int64_t row0, int64_t n, int32_t *out);
+/* the stored rows rows[0..n): s = S, euclid (nullable; needs a trained handle) = SQ8EuclideanDistance; rows outside
+ * [0, ntotal) report INT32_MAX / FLT_MAX */
+int lb_gpu_sq8_rerank(lb_gpu_sq8 *p, const uint8_t *qcode, const int64_t *rows, int64_t n, int32_t *s, float *euclid);
+int lb_gpu_sq8_rerank_device(lb_gpu_sq8 *p, const uint8_t *d_qcode, const int64_t *d_rows, int64_t n, int32_t *d_s, float *d_euclid,
+                             void *stream);
+/* k-NN of nq query codes u8[nq*dims] -> dist f32[nq*k], labels i64[nq*k] */
+int lb_gpu_sq8_search_codes(lb_gpu_sq8 *p, int64_t nq, const uint8_t *qcodes, int k, float *dist, int64_t *labels);
+/* k-NN of nq queries f32[nq*dims], which are encoded on the device first (a trained handle).  ctx (nullable) is polled before
+ * every launch; one that has already fired returns LB_ERR_CANCELLED / LB_ERR_DEADLINE without launching anything. */
+int lb_gpu_sq8_search(lb_gpu_sq8 *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels);
+int lb_gpu_sq8_search_ctx(lb_gpu_sq8 *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_sq8_search_device_ctx(lb_gpu_sq8 *p, int64_t nq, const float *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
+                                 const lb_cancel *ctx);
+
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:
  * inputs [S][nq][k] ascending per (shard, query) (padding label -1 / FLT_MAX allowed),

@@ -151,6 +151,32 @@ SIGNATURES = [
     ("lb_gpu_bq_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_bq_search_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
     ("lb_gpu_bq_search_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_sq8_new", _vp, [_i, _i, _ip]),
+    ("lb_gpu_sq8_free", None, [_vp]),
+    ("lb_gpu_sq8_last_error", C.c_char_p, [_vp]),
+    ("lb_gpu_sq8_dims", _i, [_vp]),
+    ("lb_gpu_sq8_ntotal", _i64, [_vp]),
+    ("lb_gpu_sq8_reserve", _i, [_vp, _i64]),
+    ("lb_gpu_sq8_trained", _i, [_vp]),
+    ("lb_gpu_sq8_set_bounds", _i, [_vp, _vp, _vp]),
+    ("lb_gpu_sq8_train", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_sq8_train_device", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_sq8_get_bounds", _i, [_vp, _vp, _vp]),
+    ("lb_gpu_sq8_encode", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_sq8_encode_device", _i, [_vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_sq8_decode", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_sq8_add_codes", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_sq8_add_codes_device", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_sq8_add_vectors", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_sq8_add_vectors_device", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_sq8_get_codes", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_sq8_distance_batch", _i, [_vp, _vp, _i64, _i64, _vp]),
+    ("lb_gpu_sq8_rerank", _i, [_vp, _vp, _vp, _i64, _vp, _vp]),
+    ("lb_gpu_sq8_rerank_device", _i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_sq8_search_codes", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_sq8_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_sq8_search_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_sq8_search_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_packed_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_rrf_fuse_device", _i, [_i, _i64, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
@@ -237,13 +263,13 @@ def require_gpu(device=0):
     return lib
 
 
-def check(rc, handle=None, pq=False, lib=None, bq=False):
+def check(rc, handle=None, pq=False, lib=None, bq=False, sq8=False):
     if rc == LB_OK:
         return
     msg = ""
     if handle:
         lib = lib or load()
-        raw = lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
+        raw = lib.lb_gpu_sq8_last_error(handle) if sq8 else lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
         msg = raw.decode() if raw else ""
     if rc == 3:
         raise GPUNotAvailable(rc, msg)

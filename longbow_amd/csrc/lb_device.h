@@ -597,6 +597,64 @@ void launch_bq_scan(const BqSearch &a, hipStream_t s);
 void launch_bq_emit(const BqSearch &a, hipStream_t s);
 void launch_bq_finish(const BqSearch &a, float *dist, int64_t *labels, hipStream_t s); // n == 0 allowed: all padding
 
+// scalar-quantised codes (kernels_sq8.hip): one uint8 per dimension, rows stored at `stride` = dims rounded up to 16 bytes with
+// zero pad bytes (which add nothing to any sum).  `cstride` arguments are the row stride of a caller's codes (dims when packed).
+constexpr int SQ8_MAX_BLOCKS = 1024; // workgroups that share the rows of a search (each a contiguous run of whole 256-row tiles)
+constexpr int SQ8_RADIX_BINS = 2048;
+inline int sq8_stride(int dims) { return (dims + 15) & ~15; }
+// state[2][dims] = {min, max}: seeded from row 0 of X (sq8_bounds_seed), then folded with n rows at a time (sq8_bounds_fold;
+// part: scratch of 2 * sq8_bounds_parts(n) * dims floats), in fixed order: reproducible run to run
+int sq8_bounds_parts(int64_t n);
+void launch_sq8_bounds_seed(const float *X, int dims, float *state, hipStream_t s);
+void launch_sq8_bounds_fold(const float *X, int64_t n, int dims, float *part, float *state, hipStream_t s);
+// EncodeInto: X f32[n][dims] -> codes u8[n][stride], pad bytes zero
+void launch_sq8_encode(const float *X, int64_t n, int dims, const float *mn, const float *mx, const float *scale, uint8_t *codes,
+                       hipStream_t s);
+// DecodeInto: codes u8[n][cstride] -> out f32[n][dims]
+void launch_sq8_decode(const uint8_t *codes, int64_t n, int dims, int cstride, const float *mn, const float *inv, float *out,
+                       hipStream_t s);
+// dst u8[n][dstride] = the first `width` bytes of each row of src u8[n][sstride], zero beyond them
+void launch_sq8_restride(const uint8_t *src, int sstride, uint8_t *dst, int dstride, int width, int64_t n, hipStream_t s);
+// norms[r] = sum of squares of the stride bytes of row r
+void launch_sq8_norms(const uint8_t *codes, int64_t n, int stride, int32_t *norms, hipStream_t s);
+// The distance pass: out[q][i] = S(row row0 + i, query q) for i in [0, n), q in [0, nq); Q u8[nq][stride], qn their norms.
+struct Sq8Dist {
+    const uint8_t *codes;  // [ntotal][stride]
+    const int32_t *norms;  // [ntotal]
+    int stride;
+    int64_t row0, n;
+    const uint8_t *Q;      // [nq][stride]
+    const int32_t *qn;     // [nq]
+    int nq;
+    int32_t *out;          // [nq][n]
+};
+void launch_sq8_dist(const Sq8Dist &a, hipStream_t s);
+// gathered rows, one query u8[dims]: s = S as int32, euclid (nullable) = SQ8EuclideanDistance; rows outside [0, ntotal):
+// INT32_MAX / FLT_MAX
+void launch_sq8_rerank(const uint8_t *codes, int stride, int dims, int64_t ntotal, const uint8_t *qcode, const int64_t *rows, int64_t n,
+                       const float *mn, const float *inv, int32_t *out_s, float *out_euclid, hipStream_t s);
+// exact k-NN by counting over the distances S[nq][n] of one batch of queries (n in 1..2^31-1, k <= 2048):
+// (hist, digit) x 3 -> count -> scan -> emit -> finish; hist must be zero before the first.
+struct Sq8Select {
+    const int32_t *S;  // [nq][n]
+    int64_t n;
+    int nq, k;
+    int nblk, tpb;     // sq8_select_plan(n): workgroups and tiles per workgroup
+    uint32_t *hist;    // [nq][SQ8_RADIX_BINS]
+    uint32_t *thr;     // [nq][2]: while selecting the digits found so far and the rank still wanted among them; then the
+                       // threshold t and the rows at t that are still needed (0x7fffffff, 0: fewer than k rows, all are below)
+    uint32_t *cnt;     // [nq][nblk][2]: rows below t, rows at t; after the scan their exclusive prefixes
+    uint32_t *tot;     // [nq]: rows below t
+    uint64_t *keys;    // [nq][k]: S << 32 | row, unordered
+};
+void sq8_select_plan(int64_t n, int *nblk, int *tpb);
+void launch_sq8_hist(const Sq8Select &a, int pass, hipStream_t s);
+void launch_sq8_digit(const Sq8Select &a, int pass, hipStream_t s);
+void launch_sq8_count(const Sq8Select &a, hipStream_t s);
+void launch_sq8_scan(const Sq8Select &a, hipStream_t s);
+void launch_sq8_emit(const Sq8Select &a, hipStream_t s);
+void launch_sq8_finish(const Sq8Select &a, float *dist, int64_t *labels, hipStream_t s); // n == 0 allowed: all padding
+
 // predicate masks (kernels_filter.hip): op = simd.CompareOp value; validity = Arrow LSB bitmap or null
 void launch_match_int64(const int64_t *src, int64_t n, int64_t val, int op, const uint8_t *validity,
                         int64_t valid_offset, uint8_t *dst, int combine, hipStream_t s);
