@@ -8,16 +8,10 @@
 // chunk (CW = 4, 8, 12 or 16: the words stay in registers for all QT queries); wider rows walk chunks of 8 words.  Words past
 // W are zero on both sides.  Distances sum whole words, so pad bits a caller stored count (as in the reference).
 //
-// Top-k needs no candidate list: the distance takes at most 64*W + 1 <= 8193 values.
-//   hist    per-query histogram of all distances: LDS per workgroup, flushed with one atomic per non-empty bin
-//   thresh  t = the smallest d with count(<= d) >= k, need = k - count(< t)
-//   count   rows below t and rows at t per (query, workgroup), workgroups owning contiguous row ranges
-//   scan    exclusive scan of those counts over the workgroups of a query
-//   emit    rows below t, and the `need` lowest-positioned rows at t, to their slot among the query's k keys (d << 32 | row)
-//   finish  sort the <= k keys of a query in LDS, write distances and labels, pad with -1 / FLT_MAX
-// Workgroups meet at launch boundaries only; every count is bounded by the data's size, whatever the data.
-#include "lb_device.h"
-#include "lb_select.h"
+// Top-k needs no candidate list: the distance takes at most 64*W + 1 <= 8193 values, so the search selects by counting
+// (lb_countsel.h states the method: hist, thresh, count, scan, emit, finish).  The hist, count and emit kernels here recompute
+// the distances tile by tile; the scan and the finish are kernels_countsel.hip's.
+#include "lb_countsel.h"
 
 #include <cfloat>
 #include <type_traits>
@@ -26,7 +20,7 @@ namespace lb {
 
 namespace {
 
-constexpr int BQ_ROWS = 256;
+constexpr int BQ_ROWS = COUNTSEL_ROWS;
 constexpr size_t BQ_LDS_BUDGET = 64 * 1024; // dynamic LDS a launch may ask for without opting in to more
 
 // ---- codec ------------------------------------------------------------------------------------------------------------
@@ -213,21 +207,8 @@ __global__ __launch_bounds__(256) void bq_thresh_kernel(BqSearch a)
     part[tid] = s;
     __syncthreads();
     if (tid == 0) {
-        uint32_t cum = 0, t = 0x7fffffffu, need = 0;
-        for (int seg = 0; seg < 256; seg++) {
-            if (cum + part[seg] >= (uint32_t)a.k) {
-                for (int b = seg * per;; b++) { // ends inside the segment: its bins sum to part[seg]
-                    if (cum + h[b] >= (uint32_t)a.k) {
-                        t = (uint32_t)b;
-                        need = (uint32_t)a.k - cum;
-                        break;
-                    }
-                    cum += h[b];
-                }
-                break;
-            }
-            cum += part[seg];
-        }
+        uint32_t t = 0x7fffffffu, need = 0;
+        countsel_find(h, part, per, (uint32_t)a.k, t, need);
         a.thr[2 * q] = t;
         a.thr[2 * q + 1] = need;
     }
@@ -273,45 +254,6 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_count_kernel(BqSearch a)
     }
     __syncthreads();
     if (tid < QT * 2 && q0 + (tid >> 1) < a.nq) a.cnt[((int64_t)(q0 + (tid >> 1)) * a.nblk + blockIdx.x) * 2 + (tid & 1)] = lc[tid];
-}
-
-// cnt[q][b][2] -> exclusive prefix over b, in place; tot[q] = rows below t
-__global__ __launch_bounds__(256) void bq_scan_kernel(BqSearch a)
-{
-    __shared__ uint32_t part[256][2];
-    const int tid = threadIdx.x, q = blockIdx.x;
-    const int per = (a.nblk + 255) / 256;
-    uint32_t *c = a.cnt + (int64_t)q * a.nblk * 2;
-    const int b0 = tid * per < a.nblk ? tid * per : a.nblk, b1 = b0 + per < a.nblk ? b0 + per : a.nblk;
-    uint32_t s0 = 0, s1 = 0;
-    for (int b = b0; b < b1; b++) {
-        s0 += c[2 * b];
-        s1 += c[2 * b + 1];
-    }
-    part[tid][0] = s0;
-    part[tid][1] = s1;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t r0 = 0, r1 = 0;
-        for (int i = 0; i < 256; i++) {
-            const uint32_t v0 = part[i][0], v1 = part[i][1];
-            part[i][0] = r0;
-            part[i][1] = r1;
-            r0 += v0;
-            r1 += v1;
-        }
-        a.tot[q] = r0;
-    }
-    __syncthreads();
-    s0 = part[tid][0];
-    s1 = part[tid][1];
-    for (int b = b0; b < b1; b++) {
-        const uint32_t v0 = c[2 * b], v1 = c[2 * b + 1];
-        c[2 * b] = s0;
-        c[2 * b + 1] = s1;
-        s0 += v0;
-        s1 += v1;
-    }
 }
 
 template <int CW, int QT>
@@ -361,17 +303,8 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_emit_kernel(BqSearch a)
             const bool on = mine && q0 + j < a.nq;
             const bool lt = on && (uint32_t)acc[j] < t[j], eq = on && (uint32_t)acc[j] == t[j];
             const unsigned long long blt = __ballot(lt), beq = __ballot(eq);
-            uint32_t olt = run[2 * j], oeq = run[2 * j + 1];
-            for (int w = 0; w < wave; w++) {
-                olt += wcnt[(j * 4 + w) * 2];
-                oeq += wcnt[(j * 4 + w) * 2 + 1];
-            }
-            olt += (uint32_t)__popcll(blt & lower);
-            oeq += (uint32_t)__popcll(beq & lower);
-            // rows at t: only the `need` lowest positions (oeq is the row's rank among them); nothing lands past slot k - 1
-            const uint32_t slot = lt ? olt : below[j] + oeq;
-            if ((lt || (eq && oeq < need[j])) && slot < (uint32_t)a.k)
-                a.keys[(int64_t)(q0 + j) * a.k + slot] = ((uint64_t)(uint32_t)acc[j] << 32) | pos;
+            const uint32_t slot = countsel_slot(lt, eq, blt, beq, run + 2 * j, wcnt + j * 8, wave, lower, below[j], need[j], a.k);
+            if (slot != COUNTSEL_NO_SLOT) a.keys[(int64_t)(q0 + j) * a.k + slot] = ((uint64_t)(uint32_t)acc[j] << 32) | pos;
         }
         __syncthreads();
         if (tid < QT * 2) {
@@ -382,35 +315,15 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_emit_kernel(BqSearch a)
     }
 }
 
-// the min(k, n) keys of a query, ascending by (distance, position) -> dist / labels, padded with FLT_MAX / -1
-__global__ __launch_bounds__(SEL_THREADS) void bq_finish_kernel(BqSearch a, float *dist, int64_t *labels)
-{
-    __shared__ uint64_t sh[2048];
-    const int tid = threadIdx.x, q = blockIdx.x;
-    const uint32_t have = a.n < (int64_t)a.k ? (uint32_t)a.n : (uint32_t)a.k;
-    const uint32_t P = next_pow2((uint32_t)a.k);
-    for (uint32_t i = tid; i < P; i += SEL_THREADS) sh[i] = i < have ? a.keys[(int64_t)q * a.k + i] : ~0ull;
-    __syncthreads();
-    bitonic_sort_u64(sh, P, tid, SEL_THREADS);
-    for (uint32_t i = tid; i < (uint32_t)a.k; i += SEL_THREADS) {
-        const uint64_t key = sh[i];
-        const bool pad = i >= have;
-        dist[(int64_t)q * a.k + i] = pad ? FLT_MAX : (float)(uint32_t)(key >> 32);
-        labels[(int64_t)q * a.k + i] = pad ? -1 : (int64_t)(key & 0xffffffffull);
-    }
-}
-
 // ---- launch plumbing --------------------------------------------------------------------------------------------------
 int bq_cw(int W) { return W <= 4 ? 4 : W <= 8 ? 8 : W <= 12 ? 12 : W <= 16 ? 16 : 8; }
 size_t bq_tile_lds(int W, int cw, int qt) { return ((size_t)BQ_ROWS * (cw + 1) + (size_t)qt * ((W + cw - 1) / cw) * cw) * 8; }
 
-// the query tile of a launch: the smallest of 1, 4, 8, 16 that holds nq (a single query pays for one), within the LDS budget
+// the query tile of a launch (pick_qt) within the LDS budget, lds_per_query being what the kernel adds to the tile per query
 int bq_qt(int nq, int W, size_t lds_per_query)
 {
     const int cw = bq_cw(W);
-    int qt = nq <= 1 ? 1 : nq <= 4 ? 4 : nq <= 8 ? 8 : 16;
-    while (qt > 1 && bq_tile_lds(W, cw, qt) + (size_t)qt * lds_per_query > BQ_LDS_BUDGET) qt = qt == 16 ? 8 : qt == 8 ? 4 : 1;
-    return qt;
+    return pick_qt(nq, [&](int qt) { return bq_tile_lds(W, cw, qt) + (size_t)qt * lds_per_query <= BQ_LDS_BUDGET; });
 }
 
 template <class F> void bq_with_cw(int cw, F &&f)
@@ -422,17 +335,6 @@ template <class F> void bq_with_cw(int cw, F &&f)
     default: f(std::integral_constant<int, 16>{}); break;
     }
 }
-template <class F> void bq_with_qt(int qt, F &&f)
-{
-    switch (qt) {
-    case 1: f(std::integral_constant<int, 1>{}); break;
-    case 4: f(std::integral_constant<int, 4>{}); break;
-    case 8: f(std::integral_constant<int, 8>{}); break;
-    default: f(std::integral_constant<int, 16>{}); break;
-    }
-}
-
-int64_t bq_grid(int64_t units, int64_t cap) { return units < 1 ? 1 : units < cap ? units : cap; }
 
 } // namespace
 
@@ -440,7 +342,7 @@ void launch_bq_encode(const float *X, int64_t n, int dims, uint64_t *codes, hipS
 {
     if (n <= 0) return;
     const int W = (dims + 63) / 64;
-    bq_encode_kernel<<<dim3((unsigned)bq_grid((n * W + 3) / 4, 1 << 20)), dim3(256), 0, s>>>(reinterpret_cast<const uint32_t *>(X), n, dims, W,
+    bq_encode_kernel<<<dim3((unsigned)grid_cap((n * W + 3) / 4, 1 << 20)), dim3(256), 0, s>>>(reinterpret_cast<const uint32_t *>(X), n, dims, W,
                                                                                             codes);
 }
 
@@ -448,7 +350,7 @@ void launch_bq_decode(const uint64_t *codes, int64_t n, int dims, float *out, hi
 {
     if (n <= 0) return;
     const int W = (dims + 63) / 64;
-    bq_decode_kernel<<<dim3((unsigned)bq_grid((n * dims + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(codes, n, dims, W, out);
+    bq_decode_kernel<<<dim3((unsigned)grid_cap((n * dims + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(codes, n, dims, W, out);
 }
 
 void launch_bq_batch(const uint64_t *codes, int W, const uint64_t *qcode, int64_t row0, int64_t n, int32_t *out, hipStream_t s)
@@ -456,7 +358,7 @@ void launch_bq_batch(const uint64_t *codes, int W, const uint64_t *qcode, int64_
     if (n <= 0) return;
     const int cw = bq_cw(W);
     const BqRows rows{codes, W, row0 + n, nullptr};
-    const unsigned grid = (unsigned)bq_grid((n + BQ_ROWS - 1) / BQ_ROWS, 1 << 16);
+    const unsigned grid = (unsigned)grid_cap((n + BQ_ROWS - 1) / BQ_ROWS, 1 << 16);
     bq_with_cw(cw, [&](auto c) {
         bq_batch_kernel<decltype(c)::value><<<dim3(grid), dim3(BQ_ROWS), bq_tile_lds(W, cw, 1), s>>>(rows, qcode, row0, n, out);
     });
@@ -468,18 +370,10 @@ void launch_bq_rerank(const uint64_t *codes, int W, int dims, int64_t ntotal, co
     if (n <= 0) return;
     const int cw = bq_cw(W);
     const BqRows r{codes, W, ntotal, rows};
-    const unsigned grid = (unsigned)bq_grid((n + BQ_ROWS - 1) / BQ_ROWS, 1 << 16);
+    const unsigned grid = (unsigned)grid_cap((n + BQ_ROWS - 1) / BQ_ROWS, 1 << 16);
     bq_with_cw(cw, [&](auto c) {
         bq_rerank_kernel<decltype(c)::value><<<dim3(grid), dim3(BQ_ROWS), bq_tile_lds(W, cw, 1), s>>>(r, qcode, n, dims, dist, score);
     });
-}
-
-void bq_search_plan(int64_t n, int *nblk, int *tpb)
-{
-    const int64_t ntiles = (n + BQ_ROWS - 1) / BQ_ROWS;
-    const int64_t per = (ntiles + BQ_MAX_BLOCKS - 1) / BQ_MAX_BLOCKS;
-    *tpb = (int)(per < 1 ? 1 : per);
-    *nblk = (int)((ntiles + *tpb - 1) / *tpb);
 }
 
 void launch_bq_hist(const BqSearch &a, hipStream_t s)
@@ -488,7 +382,7 @@ void launch_bq_hist(const BqSearch &a, hipStream_t s)
     const size_t lds = bq_tile_lds(a.W, cw, qt) + (size_t)qt * (64 * a.W + 1) * 4;
     const dim3 grid((unsigned)a.nblk, (unsigned)((a.nq + qt - 1) / qt));
     bq_with_cw(cw, [&](auto c) {
-        bq_with_qt(qt, [&](auto q) { bq_hist_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
+        with_qt(qt, [&](auto q) { bq_hist_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
     });
 }
 
@@ -500,11 +394,9 @@ void launch_bq_count(const BqSearch &a, hipStream_t s)
     const size_t lds = bq_tile_lds(a.W, cw, qt) + (size_t)qt * 8;
     const dim3 grid((unsigned)a.nblk, (unsigned)((a.nq + qt - 1) / qt));
     bq_with_cw(cw, [&](auto c) {
-        bq_with_qt(qt, [&](auto q) { bq_count_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
+        with_qt(qt, [&](auto q) { bq_count_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
     });
 }
-
-void launch_bq_scan(const BqSearch &a, hipStream_t s) { bq_scan_kernel<<<dim3((unsigned)a.nq), dim3(256), 0, s>>>(a); }
 
 void launch_bq_emit(const BqSearch &a, hipStream_t s)
 {
@@ -512,13 +404,8 @@ void launch_bq_emit(const BqSearch &a, hipStream_t s)
     const size_t lds = bq_tile_lds(a.W, cw, qt) + (size_t)qt * 40;
     const dim3 grid((unsigned)a.nblk, (unsigned)((a.nq + qt - 1) / qt));
     bq_with_cw(cw, [&](auto c) {
-        bq_with_qt(qt, [&](auto q) { bq_emit_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
+        with_qt(qt, [&](auto q) { bq_emit_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
     });
-}
-
-void launch_bq_finish(const BqSearch &a, float *dist, int64_t *labels, hipStream_t s)
-{
-    bq_finish_kernel<<<dim3((unsigned)a.nq), dim3(SEL_THREADS), 0, s>>>(a, dist, labels);
 }
 
 } // namespace lb

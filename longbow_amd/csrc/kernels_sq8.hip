@@ -9,19 +9,12 @@
 // distinct slots.  The QT queries' bytes lie in LDS and are read wave-uniform (broadcast).  x.q comes from v_dot4_u32_u8 and
 // S = |x|^2 + |q|^2 - 2 x.q in integers: at most 65025 * 8192 < 2^30, nothing wraps.
 //
-// A search writes S once, as int32 [nq][n], and selects on that array: a row is up to 8 KiB of codes and 4 bytes of S.
-//   hist x 3   per-query histogram of one digit of S (bits 31..21, 20..10, 9..0) over the rows whose higher digits equal the
-//              ones found so far: LDS per workgroup, flushed with one atomic per non-empty bin
-//   digit x 3  the digit at which the count reaches the wanted rank; after the third: t = the k-th smallest S and
-//              need = k - count(< t)
-//   count      rows below t and rows at t per (query, workgroup), workgroups owning contiguous runs of whole tiles
-//   scan       exclusive scan of those counts over the workgroups of a query
-//   emit       rows below t, and the `need` lowest-positioned rows at t, to their slot among the query's k keys (S << 32 | row)
-//   finish     sort the <= k keys of a query in LDS, write distances and labels, pad with -1 / FLT_MAX
-// Workgroups meet at launch boundaries only; nothing is written past slot k - 1 and no count depends on the data's values.
-#include "lb_device.h"
+// A search writes S once, as int32 [nq][n], and selects on that array by counting (lb_countsel.h states the method): a row is
+// up to 8 KiB of codes and 4 bytes of S.  The histogram is a radix one: three (hist, digit) rounds over the digits of S (bits
+// 31..21, 20..10, 9..0), each over the rows whose higher digits equal the ones found so far; after the third t is the k-th
+// smallest S.  The count and emit kernels here read S; the scan and the finish are kernels_countsel.hip's.
+#include "lb_countsel.h"
 #include "lb_exact.h"
-#include "lb_select.h"
 
 #include <cfloat>
 #include <climits>
@@ -33,12 +26,10 @@ namespace {
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int SQ8_ROWS = 256;
+constexpr int SQ8_ROWS = COUNTSEL_ROWS;
 constexpr int SQ8_CH = 4;                    // 16-byte pieces of a row per chunk
 constexpr int SQ8_LD = SQ8_CH + 1;           // LDS row stride in pieces
 constexpr size_t SQ8_LDS_BUDGET = 64 * 1024; // dynamic LDS a launch may ask for without opting in to more
-
-int64_t sq8_grid(int64_t units, int64_t cap) { return units < 1 ? 1 : units < cap ? units : cap; }
 
 // ---- bounds -----------------------------------------------------------------------------------------------------------
 // TrainSQ8Encoder (scalar_quantization.go:99-118): min and max start at row 0 and later rows replace them through v < min /
@@ -315,22 +306,9 @@ __global__ __launch_bounds__(256) void sq8_digit_kernel(Sq8Select a, int pass)
     part[tid] = s;
     __syncthreads();
     if (tid == 0) {
-        uint32_t cum = 0, t = 0x7fffffffu, need = 0;
-        for (int seg = 0; seg < 256; seg++) {
-            if (cum + part[seg] >= want) {
-                for (int b = seg * per;; b++) { // ends inside the segment: its bins sum to part[seg]
-                    if (cum + h[b] >= want) {
-                        t = (prefix << (pass == 2 ? 10 : 11)) | (uint32_t)b;
-                        need = want - cum;
-                        break;
-                    }
-                    cum += h[b];
-                }
-                break;
-            }
-            cum += part[seg];
-        }
-        a.thr[2 * q] = t;
+        uint32_t bin = 0, need = 0;
+        const bool found = countsel_find(h, part, per, want, bin, need);
+        a.thr[2 * q] = found ? (prefix << (pass == 2 ? 10 : 11)) | bin : 0x7fffffffu;
         a.thr[2 * q + 1] = need;
     }
     __syncthreads();
@@ -366,45 +344,6 @@ __global__ __launch_bounds__(SQ8_ROWS) void sq8_count_kernel(Sq8Select a)
     if (tid < 2) a.cnt[((int64_t)q * a.nblk + blockIdx.x) * 2 + tid] = lc[tid];
 }
 
-// cnt[q][b][2] -> exclusive prefix over b, in place; tot[q] = rows below t
-__global__ __launch_bounds__(256) void sq8_scan_kernel(Sq8Select a)
-{
-    __shared__ uint32_t part[256][2];
-    const int tid = threadIdx.x, q = blockIdx.x;
-    const int per = (a.nblk + 255) / 256;
-    uint32_t *c = a.cnt + (int64_t)q * a.nblk * 2;
-    const int b0 = tid * per < a.nblk ? tid * per : a.nblk, b1 = b0 + per < a.nblk ? b0 + per : a.nblk;
-    uint32_t s0 = 0, s1 = 0;
-    for (int b = b0; b < b1; b++) {
-        s0 += c[2 * b];
-        s1 += c[2 * b + 1];
-    }
-    part[tid][0] = s0;
-    part[tid][1] = s1;
-    __syncthreads();
-    if (tid == 0) {
-        uint32_t r0 = 0, r1 = 0;
-        for (int i = 0; i < 256; i++) {
-            const uint32_t v0 = part[i][0], v1 = part[i][1];
-            part[i][0] = r0;
-            part[i][1] = r1;
-            r0 += v0;
-            r1 += v1;
-        }
-        a.tot[q] = r0;
-    }
-    __syncthreads();
-    s0 = part[tid][0];
-    s1 = part[tid][1];
-    for (int b = b0; b < b1; b++) {
-        const uint32_t v0 = c[2 * b], v1 = c[2 * b + 1];
-        c[2 * b] = s0;
-        c[2 * b + 1] = s1;
-        s0 += v0;
-        s1 += v1;
-    }
-}
-
 __global__ __launch_bounds__(SQ8_ROWS) void sq8_emit_kernel(Sq8Select a)
 {
     __shared__ uint32_t run[2];     // slots used so far: below t, at t
@@ -428,37 +367,11 @@ __global__ __launch_bounds__(SQ8_ROWS) void sq8_emit_kernel(Sq8Select a)
             wcnt[wave][1] = (uint32_t)__popcll(beq);
         }
         __syncthreads();
-        uint32_t olt = run[0], oeq = run[1];
-        for (int w = 0; w < wave; w++) {
-            olt += wcnt[w][0];
-            oeq += wcnt[w][1];
-        }
-        olt += (uint32_t)__popcll(blt & lower);
-        oeq += (uint32_t)__popcll(beq & lower);
-        // rows at t: only the `need` lowest positions (oeq is the row's rank among them); nothing lands past slot k - 1
-        const uint32_t slot = lt ? olt : below + oeq;
-        if ((lt || (eq && oeq < need)) && slot < (uint32_t)a.k) a.keys[(int64_t)q * a.k + slot] = ((uint64_t)s << 32) | (uint64_t)pos;
+        const uint32_t slot = countsel_slot(lt, eq, blt, beq, run, &wcnt[0][0], wave, lower, below, need, a.k);
+        if (slot != COUNTSEL_NO_SLOT) a.keys[(int64_t)q * a.k + slot] = ((uint64_t)s << 32) | (uint64_t)pos;
         __syncthreads();
         if (tid < 2) run[tid] += wcnt[0][tid] + wcnt[1][tid] + wcnt[2][tid] + wcnt[3][tid];
         __syncthreads(); // the next tile rewrites wcnt
-    }
-}
-
-// the min(k, n) keys of a query, ascending by (S, position) -> float32(S) / labels, padded with FLT_MAX / -1
-__global__ __launch_bounds__(SEL_THREADS) void sq8_finish_kernel(Sq8Select a, float *dist, int64_t *labels)
-{
-    __shared__ uint64_t sh[2048];
-    const int tid = threadIdx.x, q = blockIdx.x;
-    const uint32_t have = a.n < (int64_t)a.k ? (uint32_t)a.n : (uint32_t)a.k;
-    const uint32_t P = next_pow2((uint32_t)a.k);
-    for (uint32_t i = tid; i < P; i += SEL_THREADS) sh[i] = i < have ? a.keys[(int64_t)q * a.k + i] : ~0ull;
-    __syncthreads();
-    bitonic_sort_u64(sh, P, tid, SEL_THREADS);
-    for (uint32_t i = tid; i < (uint32_t)a.k; i += SEL_THREADS) {
-        const uint64_t key = sh[i];
-        const bool pad = i >= have;
-        dist[(int64_t)q * a.k + i] = pad ? FLT_MAX : (float)(uint32_t)(key >> 32);
-        labels[(int64_t)q * a.k + i] = pad ? -1 : (int64_t)(key & 0xffffffffull);
     }
 }
 
@@ -468,17 +381,15 @@ size_t sq8_dist_lds(int stride, int qt)
     return ((size_t)SQ8_ROWS * SQ8_LD + (size_t)qt * Pq) * 16;
 }
 
-// the query tile of a launch: the smallest of 1, 4, 8, 16 that holds nq (a single query pays for one), within the LDS budget
+// the query tile of a launch (pick_qt) within the LDS budget
 int sq8_qt(int nq, int stride)
 {
-    int qt = nq <= 1 ? 1 : nq <= 4 ? 4 : nq <= 8 ? 8 : 16;
-    while (qt > 1 && sq8_dist_lds(stride, qt) > SQ8_LDS_BUDGET) qt = qt == 16 ? 8 : qt == 8 ? 4 : 1;
-    return qt;
+    return pick_qt(nq, [&](int qt) { return sq8_dist_lds(stride, qt) <= SQ8_LDS_BUDGET; });
 }
 
 } // namespace
 
-int sq8_bounds_parts(int64_t n) { return (int)sq8_grid((n + 63) / 64, 256); }
+int sq8_bounds_parts(int64_t n) { return (int)grid_cap((n + 63) / 64, 256); }
 
 void launch_sq8_bounds_seed(const float *X, int dims, float *state, hipStream_t s)
 {
@@ -500,7 +411,7 @@ void launch_sq8_encode(const float *X, int64_t n, int dims, const float *mn, con
 {
     if (n <= 0) return;
     const int stride = sq8_stride(dims);
-    sq8_encode_kernel<<<dim3((unsigned)sq8_grid((n * (stride >> 2) + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(
+    sq8_encode_kernel<<<dim3((unsigned)grid_cap((n * (stride >> 2) + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(
         X, n, dims, stride, mn, mx, scale, reinterpret_cast<uint32_t *>(codes));
 }
 
@@ -508,51 +419,38 @@ void launch_sq8_decode(const uint8_t *codes, int64_t n, int dims, int cstride, c
                        hipStream_t s)
 {
     if (n <= 0) return;
-    sq8_decode_kernel<<<dim3((unsigned)sq8_grid((n * dims + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(codes, n, dims, cstride, mn, inv, out);
+    sq8_decode_kernel<<<dim3((unsigned)grid_cap((n * dims + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(codes, n, dims, cstride, mn, inv, out);
 }
 
 void launch_sq8_restride(const uint8_t *src, int sstride, uint8_t *dst, int dstride, int width, int64_t n, hipStream_t s)
 {
     if (n <= 0) return;
-    sq8_restride_kernel<<<dim3((unsigned)sq8_grid((n * dstride + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(src, sstride, dst, dstride, width, n);
+    sq8_restride_kernel<<<dim3((unsigned)grid_cap((n * dstride + 255) / 256, 1 << 20)), dim3(256), 0, s>>>(src, sstride, dst, dstride, width, n);
 }
 
 void launch_sq8_norms(const uint8_t *codes, int64_t n, int stride, int32_t *norms, hipStream_t s)
 {
     if (n <= 0) return;
-    sq8_norms_kernel<<<dim3((unsigned)sq8_grid((n + 3) / 4, 1 << 16)), dim3(256), 0, s>>>(reinterpret_cast<const u32x4 *>(codes), n, stride >> 4,
+    sq8_norms_kernel<<<dim3((unsigned)grid_cap((n + 3) / 4, 1 << 16)), dim3(256), 0, s>>>(reinterpret_cast<const u32x4 *>(codes), n, stride >> 4,
                                                                                          norms);
-}
-
-void sq8_select_plan(int64_t n, int *nblk, int *tpb)
-{
-    const int64_t ntiles = (n + SQ8_ROWS - 1) / SQ8_ROWS;
-    const int64_t per = (ntiles + SQ8_MAX_BLOCKS - 1) / SQ8_MAX_BLOCKS;
-    *tpb = (int)(per < 1 ? 1 : per);
-    *nblk = (int)((ntiles + *tpb - 1) / *tpb);
 }
 
 void launch_sq8_dist(const Sq8Dist &a, hipStream_t s)
 {
     if (a.n <= 0 || a.nq <= 0) return;
     int nblk, tpb;
-    sq8_select_plan(a.n, &nblk, &tpb);
+    countsel_plan(a.n, SQ8_MAX_BLOCKS, &nblk, &tpb);
     const int qt = sq8_qt(a.nq, a.stride);
     const size_t lds = sq8_dist_lds(a.stride, qt);
     const dim3 grid((unsigned)nblk, (unsigned)((a.nq + qt - 1) / qt));
-    switch (qt) {
-    case 1: sq8_dist_kernel<1><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb); break;
-    case 4: sq8_dist_kernel<4><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb); break;
-    case 8: sq8_dist_kernel<8><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb); break;
-    default: sq8_dist_kernel<16><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb); break;
-    }
+    with_qt(qt, [&](auto q) { sq8_dist_kernel<decltype(q)::value><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb); });
 }
 
 void launch_sq8_rerank(const uint8_t *codes, int stride, int dims, int64_t ntotal, const uint8_t *qcode, const int64_t *rows, int64_t n,
                        const float *mn, const float *inv, int32_t *out_s, float *out_euclid, hipStream_t s)
 {
     if (n <= 0) return;
-    sq8_rerank_kernel<<<dim3((unsigned)sq8_grid((n + 255) / 256, 1 << 16)), dim3(256), 0, s>>>(codes, stride, dims, ntotal, qcode, rows, n, mn,
+    sq8_rerank_kernel<<<dim3((unsigned)grid_cap((n + 255) / 256, 1 << 16)), dim3(256), 0, s>>>(codes, stride, dims, ntotal, qcode, rows, n, mn,
                                                                                               inv, out_s, out_euclid);
 }
 
@@ -565,14 +463,9 @@ void launch_sq8_count(const Sq8Select &a, hipStream_t s)
 {
     sq8_count_kernel<<<dim3((unsigned)a.nblk, (unsigned)a.nq), dim3(SQ8_ROWS), 0, s>>>(a);
 }
-void launch_sq8_scan(const Sq8Select &a, hipStream_t s) { sq8_scan_kernel<<<dim3((unsigned)a.nq), dim3(256), 0, s>>>(a); }
 void launch_sq8_emit(const Sq8Select &a, hipStream_t s)
 {
     sq8_emit_kernel<<<dim3((unsigned)a.nblk, (unsigned)a.nq), dim3(SQ8_ROWS), 0, s>>>(a);
-}
-void launch_sq8_finish(const Sq8Select &a, float *dist, int64_t *labels, hipStream_t s)
-{
-    sq8_finish_kernel<<<dim3((unsigned)a.nq), dim3(SEL_THREADS), 0, s>>>(a, dist, labels);
 }
 
 } // namespace lb

@@ -565,6 +565,22 @@ void launch_adc_exact_candidates(const float *table, int M, const uint8_t *codes
 void launch_adc_rerank(const float *table, int M, const uint8_t *codes, int64_t n, const int64_t *rows, int64_t nrows,
                        float *out_dist, float *out_score, hipStream_t s);
 
+// The tail of a k-NN by counting (kernels_countsel.hip; the method is stated in lb_countsel.h): what the selections of
+// kernels_bq.hip and kernels_sq8.hip share once a per-query threshold is known.  Workgroup b of nblk owns the rows of tiles
+// [b * tpb, (b + 1) * tpb), 256 rows a tile.
+struct CountSel {
+    int64_t n;
+    int k, nq;
+    int nblk, tpb;     // countsel_plan(n, max_blocks): workgroups and tiles per workgroup
+    uint32_t *thr;     // [nq][2]: threshold t, rows at t that are still needed (0x7fffffff, 0: fewer than k rows, all are below)
+    uint32_t *cnt;     // [nq][nblk][2]: rows below t, rows at t; after the scan their exclusive prefixes
+    uint32_t *tot;     // [nq]: rows below t
+    uint64_t *keys;    // [nq][k]: distance << 32 | row, unordered
+};
+void countsel_plan(int64_t n, int max_blocks, int *nblk, int *tpb);
+void launch_countsel_scan(const CountSel &a, hipStream_t s);
+void launch_countsel_finish(const CountSel &a, float *dist, int64_t *labels, hipStream_t s); // n == 0 allowed: all padding
+
 // binary-quantised codes (kernels_bq.hip): W = (dims + 63) / 64 u64 words per row, bit i % 64 of word i / 64 is dimension i
 void launch_bq_encode(const float *X, int64_t n, int dims, uint64_t *codes, hipStream_t s);
 void launch_bq_decode(const uint64_t *codes, int64_t n, int dims, float *out, hipStream_t s);
@@ -573,29 +589,20 @@ void launch_bq_batch(const uint64_t *codes, int W, const uint64_t *qcode, int64_
 // gathered rows: dist = float32(distance), score = 1 - dist / dims (nullable); rows outside [0, ntotal): FLT_MAX / 0
 void launch_bq_rerank(const uint64_t *codes, int W, int dims, int64_t ntotal, const uint64_t *qcode, const int64_t *rows, int64_t n,
                       float *dist, float *score, hipStream_t s);
-// exact k-NN by counting: the state of one batch of queries as the kernels take it (by value); n in 1..2^31-1, k <= 2048.
-// hist -> thresh -> count -> scan -> emit -> finish, each a launch; hist must be zero before the first.
+// exact k-NN by counting (lb_countsel.h states the method): the state of one batch of queries as the kernels take it (by
+// value); n in 1..2^31-1, k <= 2048.  hist -> thresh -> count -> scan -> emit -> finish, each a launch; hist must be zero
+// before the first.
 constexpr int BQ_MAX_BLOCKS = 2048; // workgroups that share the rows (each a contiguous range of whole 256-row tiles)
-struct BqSearch {
+struct BqSearch : CountSel {
     const uint64_t *codes; // [n][W]
-    int64_t n;
     int W;
     const uint64_t *Q;     // [nq][W]
-    int nq, k;
-    int nblk, tpb;         // bq_search_plan(n): workgroups and tiles per workgroup
     uint32_t *hist;        // [nq][64*W + 1]
-    uint32_t *thr;         // [nq][2]: threshold t, rows at t that are still needed
-    uint32_t *cnt;         // [nq][nblk][2]: rows below t, rows at t; after the scan their exclusive prefixes
-    uint32_t *tot;         // [nq]: rows below t
-    uint64_t *keys;        // [nq][k]: d << 32 | row, unordered
 };
-void bq_search_plan(int64_t n, int *nblk, int *tpb);
 void launch_bq_hist(const BqSearch &a, hipStream_t s);
 void launch_bq_thresh(const BqSearch &a, hipStream_t s);
 void launch_bq_count(const BqSearch &a, hipStream_t s);
-void launch_bq_scan(const BqSearch &a, hipStream_t s);
 void launch_bq_emit(const BqSearch &a, hipStream_t s);
-void launch_bq_finish(const BqSearch &a, float *dist, int64_t *labels, hipStream_t s); // n == 0 allowed: all padding
 
 // scalar-quantised codes (kernels_sq8.hip): one uint8 per dimension, rows stored at `stride` = dims rounded up to 16 bytes with
 // zero pad bytes (which add nothing to any sum).  `cstride` arguments are the row stride of a caller's codes (dims when packed).
@@ -633,27 +640,17 @@ void launch_sq8_dist(const Sq8Dist &a, hipStream_t s);
 // INT32_MAX / FLT_MAX
 void launch_sq8_rerank(const uint8_t *codes, int stride, int dims, int64_t ntotal, const uint8_t *qcode, const int64_t *rows, int64_t n,
                        const float *mn, const float *inv, int32_t *out_s, float *out_euclid, hipStream_t s);
-// exact k-NN by counting over the distances S[nq][n] of one batch of queries (n in 1..2^31-1, k <= 2048):
-// (hist, digit) x 3 -> count -> scan -> emit -> finish; hist must be zero before the first.
-struct Sq8Select {
+// exact k-NN by counting (lb_countsel.h) over the distances S[nq][n] of one batch of queries (n in 1..2^31-1, k <= 2048):
+// (hist, digit) x 3 -> count -> scan -> emit -> finish; hist must be zero before the first.  While the digits are selected
+// thr holds the digits found so far and the rank still wanted among them.
+struct Sq8Select : CountSel {
     const int32_t *S;  // [nq][n]
-    int64_t n;
-    int nq, k;
-    int nblk, tpb;     // sq8_select_plan(n): workgroups and tiles per workgroup
     uint32_t *hist;    // [nq][SQ8_RADIX_BINS]
-    uint32_t *thr;     // [nq][2]: while selecting the digits found so far and the rank still wanted among them; then the
-                       // threshold t and the rows at t that are still needed (0x7fffffff, 0: fewer than k rows, all are below)
-    uint32_t *cnt;     // [nq][nblk][2]: rows below t, rows at t; after the scan their exclusive prefixes
-    uint32_t *tot;     // [nq]: rows below t
-    uint64_t *keys;    // [nq][k]: S << 32 | row, unordered
 };
-void sq8_select_plan(int64_t n, int *nblk, int *tpb);
 void launch_sq8_hist(const Sq8Select &a, int pass, hipStream_t s);
 void launch_sq8_digit(const Sq8Select &a, int pass, hipStream_t s);
 void launch_sq8_count(const Sq8Select &a, hipStream_t s);
-void launch_sq8_scan(const Sq8Select &a, hipStream_t s);
 void launch_sq8_emit(const Sq8Select &a, hipStream_t s);
-void launch_sq8_finish(const Sq8Select &a, float *dist, int64_t *labels, hipStream_t s); // n == 0 allowed: all padding
 
 // predicate masks (kernels_filter.hip): op = simd.CompareOp value; validity = Arrow LSB bitmap or null
 void launch_match_int64(const int64_t *src, int64_t n, int64_t val, int op, const uint8_t *validity,

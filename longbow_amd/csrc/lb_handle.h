@@ -1,0 +1,282 @@
+// lb_handle.h -- the host shell of a code-index handle (lb_gpu_pq, lb_gpu_bq, lb_gpu_sq8): what the three C-ABI translation
+// units pq.hip, bq.hip and sq8.hip share beyond lb_host.h.  Header-only, nothing exported.
+//
+// The rules every entry point of these handles keeps:
+//   * nothing but an lb_status leaves the library: the body of an entry point runs inside guard();
+//   * a pooled buffer (Lease) that a stream-enqueuing body uses is declared OUTSIDE guard() and the stream is passed to it: an
+//     error drains the stream before the buffer goes back to the pool, where a concurrent call could lease it (bq.hip and
+//     sq8.hip; pq.hip's entry points other than its host encode and decode are older and lease inside their bodies);
+//   * searches and reads take `mu` shared, adds and reserve take it alone.
+#pragma once
+#include "../../include/longbow_gpu.h"
+#include "lb_host.h"
+
+#include <algorithm>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <mutex>
+#include <new>
+#include <shared_mutex>
+#include <string>
+
+namespace lb {
+
+// What every code-index handle has; lb_gpu_bq, lb_gpu_sq8 and lb_gpu_pq derive from it and add their own buffers.  Those are
+// destroyed before `stream` (members of the derived struct go first): harmless, every *_free drains the device under the
+// writer lock before it deletes the handle.
+struct CodeHandle {
+    int device = 0, dims = 0;
+    std::shared_mutex mu;
+    int64_t n = 0, capacity = 0; // rows stored, rows allocated
+    Stream stream;
+    mutable std::mutex err_mu;
+    std::string last_error;
+    void set_error(const char *fmt, ...)
+    {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        std::lock_guard<std::mutex> g(err_mu);
+        try {
+            last_error = buf;
+        } catch (...) { // out of host memory: the status code still reaches the caller
+        }
+    }
+};
+
+// (unlike fail_hip of lb_index.h this leaves HIP's sticky error as it is)
+inline int hip_fail(CodeHandle *h, const HipErr &e)
+{
+    h->set_error("HIP error %d (%s) in %s", (int)e.e, hipGetErrorString(e.e), e.what);
+    return e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP;
+}
+
+inline int ctx_fail(CodeHandle *h, int st)
+{
+    h->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded");
+    return st;
+}
+
+// The shell of an entry point: nothing but an lb_status leaves the library.  `s`, where given, is the stream the body
+// enqueued on: it is drained before the answer, so that no kernel still runs on what the caller gets back.
+template <class F> int guard(CodeHandle *h, hipStream_t s, F &&body) noexcept
+{
+    try {
+        return body();
+    } catch (const HipErr &e) {
+        if (s) (void)hipStreamSynchronize(s);
+        return hip_fail(h, e);
+    } catch (const std::bad_alloc &) {
+        if (s) (void)hipStreamSynchronize(s);
+        h->set_error("out of host memory");
+        return LB_ERR_OOM;
+    } catch (...) {
+        if (s) (void)hipStreamSynchronize(s);
+        h->set_error("internal error (exception)");
+        return LB_ERR_INTERNAL;
+    }
+}
+
+constexpr size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// rows per staging piece of the host-pointer codec calls: at most 64 Mi elements, so that the pooled buffers stay small
+inline int64_t piece_rows(int dims) { return std::max<int64_t>(1, ((int64_t)64 << 20) / dims); }
+
+// Consecutive 16-byte-aligned pieces of one buffer.  A layout is a function of a Carve that take()s its pieces in order and
+// returns `off`; lease_layout runs it once to size the lease and once more to bind the pointers, which hold only then.
+struct Carve {
+    char *base;
+    size_t off = 0;
+    template <class T> T *take(size_t bytes)
+    {
+        T *p = reinterpret_cast<T *>(reinterpret_cast<uintptr_t>(base) + off);
+        off += up16(bytes);
+        return p;
+    }
+};
+template <class L> void lease_layout(Lease &sc, int device, L &&layout)
+{
+    sc.reset(device, layout(Carve{nullptr}));
+    layout(Carve{sc.as<char>()});
+}
+
+// The capacity a code buffer of `cap` rows of `row_bytes` grows to when `need` rows are asked for: geometric, at least 4096
+// rows; a buffer already beyond 1 GiB grows by at most 25 % (or to the request), so that no second copy of a large buffer is
+// ever transient.  Each handle's *_grow allocates and copies its own buffers.
+constexpr int64_t grow_capacity(int64_t cap, int64_t need, size_t row_bytes)
+{
+    if ((size_t)cap * row_bytes > ((size_t)1 << 30)) return std::max<int64_t>(need, cap + cap / 4);
+    return std::max<int64_t>(std::max<int64_t>(need, cap * 2), 4096);
+}
+static_assert(grow_capacity(0, 1, 8) == 4096, "first allocation");
+static_assert(grow_capacity(4096, 4097, 8) == 8192, "doubling");
+static_assert(grow_capacity(4096, 100000, 8) == 100000, "a request beyond the double");
+static_assert(grow_capacity((int64_t)1 << 27, ((int64_t)1 << 27) + 1, 8) == (int64_t)1 << 28, "exactly 1 GiB held still doubles");
+static_assert(grow_capacity(((int64_t)1 << 27) + 4, ((int64_t)1 << 27) + 5, 8) == 167772165, "beyond 1 GiB held: + 25 %");
+static_assert(grow_capacity(((int64_t)1 << 27) + 4, (int64_t)1 << 29, 8) == (int64_t)1 << 29, "beyond 1 GiB held: the request");
+
+// ---- refusals ---------------------------------------------------------------------------------------------------------
+// BQ and SQ8: a selection key holds the row in 32 bits and the counts are u32 (PQ has its own limit)
+constexpr int64_t kMaxRows = 0x7fffffffll;
+
+inline int rows_fit(CodeHandle *h, int64_t have, int64_t more)
+{
+    if (more <= kMaxRows - have) return LB_OK;
+    h->set_error("2^31 or more codes per handle");
+    return LB_ERR_UNSUPPORTED;
+}
+
+// rows [row0, row0 + n) of the stored ones; the caller holds `mu`
+inline int rows_in_range(CodeHandle *h, int64_t row0, int64_t n)
+{
+    if (n <= h->n && row0 <= h->n - n) return LB_OK;
+    h->set_error("rows [%lld, %lld) outside the %lld stored codes", (long long)row0, (long long)(row0 + n), (long long)h->n);
+    return LB_ERR_INVALID_ARG;
+}
+
+// INVALID_ARG, then whatever `ready` refuses (SQ8: an untrained handle), then UNSUPPORTED, then the context: what a k-NN
+// entry point answers before it touches the device
+template <class Ready>
+int knn_args(CodeHandle *h, int64_t nq, const void *queries, int k, const void *dist, const void *labels, const lb_cancel *ctx, Ready &&ready)
+{
+    if (!h || nq < 0 || k <= 0 || (nq > 0 && (!queries || !dist || !labels))) return LB_ERR_INVALID_ARG;
+    if (const int st = ready()) return st;
+    if (k > LB_MAX_K) { h->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
+    if (const int st = ctx_state(ctx)) return ctx_fail(h, st);
+    return LB_OK;
+}
+inline int knn_args(CodeHandle *h, int64_t nq, const void *queries, int k, const void *dist, const void *labels, const lb_cancel *ctx)
+{
+    return knn_args(h, nq, queries, k, dist, labels, ctx, [] { return (int)LB_OK; });
+}
+
+// ---- construction and the simple entry points -------------------------------------------------------------------------
+template <class T> void handle_free(T *p)
+{
+    if (!p) return;
+    {
+        std::unique_lock<std::shared_mutex> g(p->mu);
+        (void)hipSetDevice(p->device);
+        (void)hipDeviceSynchronize();
+    }
+    delete p;
+}
+
+// A handle on `device` with its stream; init(p) fills the index's own fields with the device current and may throw.
+// *out_status (nullable) says why nullptr comes back.
+template <class T, class Init> T *handle_open(int device, int *out_status, Init &&init)
+{
+    auto st = [&](int v) { if (out_status) *out_status = v; };
+    if (!device_ok(device)) { st(LB_ERR_NO_DEVICE); return nullptr; }
+    auto *p = new (std::nothrow) T();
+    if (!p) { st(LB_ERR_OOM); return nullptr; }
+    p->device = device;
+    try {
+        LB_HIP(hipSetDevice(device));
+        LB_HIP(hipStreamCreateWithFlags(&p->stream.h, hipStreamNonBlocking));
+        init(p);
+    } catch (const HipErr &e) {
+        st(e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP);
+        handle_free(p);
+        return nullptr;
+    } catch (...) {
+        st(LB_ERR_INTERNAL);
+        handle_free(p);
+        return nullptr;
+    }
+    st(LB_OK);
+    return p;
+}
+
+// BQ and SQ8: a handle of 1..LB_MAX_DIM dimensions
+template <class T, class Init> T *handle_new(int device, int dims, int *out_status, Init &&init)
+{
+    if (dims <= 0 || dims > LB_MAX_DIM) {
+        if (out_status) *out_status = dims <= 0 ? LB_ERR_INVALID_ARG : LB_ERR_UNSUPPORTED;
+        return nullptr;
+    }
+    return handle_open<T>(device, out_status, [&](T *p) {
+        p->dims = dims;
+        init(p);
+    });
+}
+
+inline const char *handle_last_error(const CodeHandle *h)
+{
+    if (!h) return "null handle";
+    std::lock_guard<std::mutex> g(h->err_mu);
+    return h->last_error.c_str();
+}
+
+inline int64_t handle_ntotal(const CodeHandle *h)
+{
+    if (!h) return 0;
+    std::shared_lock<std::shared_mutex> g(const_cast<CodeHandle *>(h)->mu); // (adds commit under the writer lock)
+    return h->n;
+}
+
+// BQ and SQ8: room for n_total rows, by the index's own grow(p, n_total)
+template <class T, class Grow> int handle_reserve(T *p, int64_t n_total, Grow &&grow)
+{
+    if (!p || n_total < 0) return LB_ERR_INVALID_ARG;
+    if (const int st = rows_fit(p, 0, n_total)) return st;
+    std::unique_lock<std::shared_mutex> g(p->mu);
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        grow(p, n_total);
+        return LB_OK;
+    });
+}
+
+// ---- k-NN of host queries -----------------------------------------------------------------------------------------------
+// Host queries -> pooled device buffers -> search -> results back, on the handle's stream under the reader lock; the caller
+// has answered knn_args and nq == 0.  put(dq, stage, s) enqueues what leaves the nq queries in dq (code_bytes each) as the
+// device codes the index searches, `stage` being a lease for whatever it stages; search(dq, d_dist, d_labels, s, scratch) is
+// the index's k-NN of device codes and returns its status with the stream drained.
+template <class Put, class Search>
+int host_knn(CodeHandle *h, int64_t nq, size_t code_bytes, int k, float *dist, int64_t *labels, Put &&put, Search &&search)
+{
+    std::shared_lock<std::shared_mutex> g(h->mu);
+    Lease dq, dout, stage, scratch;
+    return guard(h, h->stream, [&]() -> int {
+        LB_HIP(hipSetDevice(h->device));
+        hipStream_t s = h->stream;
+        const size_t db = up16((size_t)nq * k * 4), lb = (size_t)nq * k * 8;
+        dq.reset(h->device, (size_t)nq * code_bytes);
+        dout.reset(h->device, db + lb);
+        put(dq, stage, s);
+        float *d_dist = dout.as<float>();
+        int64_t *d_labels = reinterpret_cast<int64_t *>(dout.as<char>() + db);
+        const int rc = search(dq, d_dist, d_labels, s, scratch);
+        if (rc != LB_OK) return rc;
+        LB_HIP(hipMemcpy(dist, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
+        LB_HIP(hipMemcpy(labels, d_labels, lb, hipMemcpyDeviceToHost));
+        return LB_OK;
+    });
+}
+
+// ---- codec calls on host rows -------------------------------------------------------------------------------------------
+// n host rows of in_row bytes -> n host rows of out_row bytes, in pieces of piece_rows through two pooled buffers;
+// run(d_in, d_out, cnt) is the index's device-pointer form of the call: it returns its status with its stream drained.
+template <class Run> int host_codec(CodeHandle *h, int64_t n, const void *in, size_t in_row, void *out, size_t out_row, Run &&run)
+{
+    Lease din, dout;
+    return guard(h, h->stream, [&]() -> int {
+        LB_HIP(hipSetDevice(h->device));
+        const int64_t piece = std::min(n, piece_rows(h->dims));
+        din.reset(h->device, (size_t)piece * in_row);
+        dout.reset(h->device, (size_t)piece * out_row);
+        for (int64_t r0 = 0; r0 < n; r0 += piece) {
+            const int64_t cnt = std::min(piece, n - r0);
+            LB_HIP(hipMemcpy(din.p, static_cast<const char *>(in) + (size_t)r0 * in_row, (size_t)cnt * in_row, hipMemcpyHostToDevice));
+            if (const int rc = run(din.p, dout.p, cnt)) return rc;
+            LB_HIP(hipMemcpy(static_cast<char *>(out) + (size_t)r0 * out_row, dout.p, (size_t)cnt * out_row, hipMemcpyDeviceToHost));
+        }
+        return LB_OK;
+    });
+}
+
+} // namespace lb

@@ -1,5 +1,6 @@
 // lb_host.h -- host-side helpers shared by the C-ABI translation units (index.hip, index_search.hip, simd_api.hip, pq.hip,
-// comm.hip): HIP error plumbing, a pooled device / pinned-host buffer cache and the owners of a handle's own buffers.
+// pq_train.hip, bq.hip, sq8.hip, comm.hip): HIP error plumbing, a pooled device / pinned-host buffer cache and the owners of a
+// handle's own buffers.  lb_handle.h adds what the code-index handles (pq.hip, bq.hip, sq8.hip) share on top of it.
 //
 // Why a pool: hipMalloc costs 0.1-0.3 ms and hipFree synchronises the whole device, so an entry
 // point that allocates per call stalls every concurrent search on the same GPU.  The host-pointer

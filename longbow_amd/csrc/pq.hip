@@ -7,26 +7,17 @@
 // stride K (internal/pq/adc_table.go:46); they agree only at K = 256.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
-#include "lb_host.h"
+#include "lb_handle.h"
 
-#include <algorithm>
 #include <atomic>
-#include <cstdarg>
-#include <cstdio>
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <mutex>
-#include <shared_mutex>
-#include <string>
 #include <vector>
 
 using namespace lb;
 
 namespace {
-using HipErrP = lb::HipErr;
-#define LBP_HIP(call) LB_HIP(call)
-
 uint32_t rd_u32le(const uint8_t *p)
 {
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
@@ -34,19 +25,14 @@ uint32_t rd_u32le(const uint8_t *p)
 struct PqScratch;
 } // namespace
 
-struct lb_gpu_pq {
-    int device = 0, dims = 0, M = 0, K = 0, sub = 0;
-    std::shared_mutex mu;
+struct lb_gpu_pq : CodeHandle {
+    int M = 0, K = 0, sub = 0;
     DevBuf<float> d_codebooks;
     DevBuf<uint8_t> d_codes;
-    int64_t n = 0, capacity = 0;
-    Stream stream;
     // per-search scratch (lists, tables, sample and candidate buffers) is pooled on the handle: a search
     // must not hipMalloc/hipFree (the latter synchronises the device under every concurrent search)
     std::mutex sc_mu;
     std::vector<std::unique_ptr<PqScratch>> sc_free;
-    mutable std::mutex err_mu;
-    std::string last_error;
     // instrumentation (bench.py): HIP events around the main code pass and the whole search of the last query
     std::atomic<int> profiling{0};
     std::atomic<int> prefilter{1}; // 0 = exact f32-table pass only (lb_gpu_pq_set_prefilter; both are exact)
@@ -56,39 +42,18 @@ struct lb_gpu_pq {
     // what served the queries of the last COMPLETED device batch (lb_gpu_pq_last_search_stats): observing only
     mutable std::mutex stats_mu;
     int64_t last_stats[6] = {0, 0, 0, 0, 0, 0};
-    void set_error(const char *fmt, ...)
-    {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        std::lock_guard<std::mutex> g(err_mu);
-        last_error = buf;
-    }
 };
 
 namespace {
-int pq_fail(lb_gpu_pq *p, const HipErrP &e)
-{
-    p->set_error("HIP error %d (%s) in %s", (int)e.e, hipGetErrorString(e.e), e.what);
-    return e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP;
-}
-
-// Geometric growth without a transient second copy of a large code buffer: beyond 1 GiB the buffer grows
-// by at most 25 % + the request, and the copy runs in 256 MiB pieces (the peak is still old + new; a
-// caller that knows the final size avoids it with lb_gpu_pq_reserve).
+// The copy is one hipMemcpy: the peak is old + new (grow_capacity keeps the step small beyond 1 GiB); a caller that knows the
+// final size avoids it with lb_gpu_pq_reserve.
 void pq_grow(lb_gpu_pq *p, int64_t need)
 {
     if (need <= p->capacity) return;
-    int64_t cap = std::max<int64_t>(std::max<int64_t>(need, p->capacity * 2), 4096);
-    if ((size_t)p->capacity * p->M > ((size_t)1 << 30)) cap = std::max<int64_t>(need, p->capacity + p->capacity / 4);
+    const int64_t cap = grow_capacity(p->capacity, need, (size_t)p->M);
     DevBuf<uint8_t> nc;
     nc.alloc((size_t)cap * p->M);
-    if (p->n > 0) {
-        const hipError_t e = hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice);
-        if (e != hipSuccess) throw HipErrP{e, "hipMemcpy (pq_grow)"};
-    }
+    if (p->n > 0) LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice));
     p->d_codes = std::move(nc);
     p->capacity = cap;
 }
@@ -154,7 +119,7 @@ std::unique_ptr<PqScratch> acquire_scratch(lb_gpu_pq *p, int nq, uint32_t cap, s
         sc->h_flags.alloc(nqc);
         std::vector<int> slots(nqc);
         for (size_t q = 0; q < nqc; q++) slots[q] = (int)q;
-        LBP_HIP(hipMemcpy(sc->d_slots.get(), slots.data(), nqc * sizeof(int), hipMemcpyHostToDevice));
+        LB_HIP(hipMemcpy(sc->d_slots.get(), slots.data(), nqc * sizeof(int), hipMemcpyHostToDevice));
     }
     sc->d_samp.ensure(samp_entries);
     return sc;
@@ -180,67 +145,29 @@ lb_gpu_pq *lb_gpu_pq_new(int device, const uint8_t *blob, size_t len, int *out_s
     if (len != 12 + (size_t)M * K * sub * 4) { st(LB_ERR_INVALID_ARG); return nullptr; } // "size mismatch"
     if (K != 256) { st(LB_ERR_UNSUPPORTED); return nullptr; }
     if ((size_t)M * 256 * 4 > 160 * 1024 - 1024) { st(LB_ERR_UNSUPPORTED); return nullptr; } // table must fit LDS
-    if (!device_ok(device)) { st(LB_ERR_NO_DEVICE); return nullptr; }
-    auto *p = new (std::nothrow) lb_gpu_pq();
-    if (!p) { st(LB_ERR_OOM); return nullptr; }
-    p->device = device; p->dims = (int)dims; p->M = (int)M; p->K = (int)K; p->sub = (int)sub;
-    try {
-        LBP_HIP(hipSetDevice(device));
-        LBP_HIP(hipStreamCreateWithFlags(&p->stream.h, hipStreamNonBlocking));
+    return handle_open<lb_gpu_pq>(device, out_status, [&](lb_gpu_pq *p) {
+        p->dims = (int)dims; p->M = (int)M; p->K = (int)K; p->sub = (int)sub;
         p->d_codebooks.alloc((len - 12) / sizeof(float));
         // f32 little-endian on the wire == host/device layout on this platform
-        LBP_HIP(hipMemcpy(p->d_codebooks.get(), blob + 12, len - 12, hipMemcpyHostToDevice));
-    } catch (const HipErrP &e) {
-        st(e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP);
-        lb_gpu_pq_free(p);
-        return nullptr;
-    }
-    st(LB_OK);
-    return p;
+        LB_HIP(hipMemcpy(p->d_codebooks.get(), blob + 12, len - 12, hipMemcpyHostToDevice));
+    });
 }
 
-void lb_gpu_pq_free(lb_gpu_pq *p)
-{
-    if (!p) return;
-    {
-        std::unique_lock<std::shared_mutex> g(p->mu);
-        (void)hipSetDevice(p->device);
-        (void)hipDeviceSynchronize();
-        {
-            std::lock_guard<std::mutex> g2(p->sc_mu);
-            p->sc_free.clear();
-        }
-    }
-    delete p;
-}
-
-const char *lb_gpu_pq_last_error(const lb_gpu_pq *p)
-{
-    if (!p) return "null handle";
-    std::lock_guard<std::mutex> g(p->err_mu);
-    return p->last_error.c_str();
-}
-
+void lb_gpu_pq_free(lb_gpu_pq *p) { handle_free(p); } // (the pooled scratch frees itself with the handle)
+const char *lb_gpu_pq_last_error(const lb_gpu_pq *p) { return handle_last_error(p); }
 int lb_gpu_pq_m(const lb_gpu_pq *p) { return p ? p->M : 0; }
 int lb_gpu_pq_dims(const lb_gpu_pq *p) { return p ? p->dims : 0; }
-int64_t lb_gpu_pq_ntotal(const lb_gpu_pq *p)
-{
-    if (!p) return 0;
-    std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_pq *>(p)->mu); // (add_codes / add_vectors commit under the writer lock)
-    return p->n;
-}
+int64_t lb_gpu_pq_ntotal(const lb_gpu_pq *p) { return handle_ntotal(p); }
 
 int lb_gpu_pq_reserve(lb_gpu_pq *p, int64_t n_total)
 {
     if (!p || n_total < 0) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(p->mu);
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         pq_grow(p, n_total);
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 static int add_codes_impl(lb_gpu_pq *p, int64_t n, const uint8_t *codes, bool on_device)
@@ -249,16 +176,14 @@ static int add_codes_impl(lb_gpu_pq *p, int64_t n, const uint8_t *codes, bool on
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
     if (p->n + n > (int64_t)0xffffffffll) { p->set_error("more than 2^32 codes per device"); return LB_ERR_UNSUPPORTED; }
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         pq_grow(p, p->n + n);
-        LBP_HIP(hipMemcpy(p->d_codes.get() + (size_t)p->n * p->M, codes, (size_t)n * p->M,
+        LB_HIP(hipMemcpy(p->d_codes.get() + (size_t)p->n * p->M, codes, (size_t)n * p->M,
                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
         p->n += n;
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_add_codes(lb_gpu_pq *p, int64_t n, const uint8_t *codes) { return add_codes_impl(p, n, codes, false); }
@@ -269,14 +194,12 @@ int lb_gpu_pq_get_codes(lb_gpu_pq *p, int64_t row0, int64_t n, uint8_t *codes)
     if (!p || row0 < 0 || n < 0 || (n > 0 && !codes)) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     std::shared_lock<std::shared_mutex> g(p->mu);
-    if (row0 + n > p->n) { p->set_error("rows [%lld, %lld) outside the %lld stored codes", (long long)row0, (long long)(row0 + n), (long long)p->n); return LB_ERR_INVALID_ARG; }
-    try {
-        LBP_HIP(hipSetDevice(p->device));
-        LBP_HIP(hipMemcpy(codes, p->d_codes.get() + (size_t)row0 * p->M, (size_t)n * p->M, hipMemcpyDeviceToHost));
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+    if (const int st = rows_in_range(p, row0, n)) return st;
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        LB_HIP(hipMemcpy(codes, p->d_codes.get() + (size_t)row0 * p->M, (size_t)n * p->M, hipMemcpyDeviceToHost));
+        return LB_OK;
+    });
 }
 
 // ---- Encode / Decode -------------------------------------------------------------------
@@ -285,38 +208,23 @@ int lb_gpu_pq_encode_device(lb_gpu_pq *p, int64_t n, const float *d_vectors, uin
     if (!p || n < 0 || (n > 0 && (!d_vectors || !d_codes))) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     std::shared_lock<std::shared_mutex> g(p->mu);
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
         launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_vectors, n, d_codes, s);
         LB_LAUNCH_CHECK();
-        LBP_HIP(hipStreamSynchronize(s));
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        LB_HIP(hipStreamSynchronize(s));
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_encode(lb_gpu_pq *p, int64_t n, const float *vectors, uint8_t *codes)
 {
     if (!p || n < 0 || (n > 0 && (!vectors || !codes))) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
-    try {
-        LBP_HIP(hipSetDevice(p->device));
-        // in pieces of <= 64 Mi floats so that the staging buffers stay small and reusable
-        const int64_t piece = std::max<int64_t>(1, ((int64_t)64 << 20) / p->dims);
-        Lease dv(p->device, (size_t)std::min(n, piece) * p->dims * 4), dc(p->device, (size_t)std::min(n, piece) * p->M);
-        for (int64_t r0 = 0; r0 < n; r0 += piece) {
-            const int64_t cnt = std::min(piece, n - r0);
-            LBP_HIP(hipMemcpy(dv.p, vectors + (size_t)r0 * p->dims, (size_t)cnt * p->dims * 4, hipMemcpyHostToDevice));
-            const int rc = lb_gpu_pq_encode_device(p, cnt, dv.as<float>(), dc.as<uint8_t>(), nullptr);
-            if (rc != LB_OK) return rc;
-            LBP_HIP(hipMemcpy(codes + (size_t)r0 * p->M, dc.p, (size_t)cnt * p->M, hipMemcpyDeviceToHost));
-        }
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+    return host_codec(p, n, vectors, (size_t)p->dims * 4, codes, (size_t)p->M, [&](void *dv, void *dc, int64_t cnt) {
+        return lb_gpu_pq_encode_device(p, cnt, static_cast<float *>(dv), static_cast<uint8_t *>(dc), nullptr);
+    });
 }
 
 int lb_gpu_pq_add_vectors_device(lb_gpu_pq *p, int64_t n, const float *d_vectors)
@@ -325,17 +233,15 @@ int lb_gpu_pq_add_vectors_device(lb_gpu_pq *p, int64_t n, const float *d_vectors
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
     if (p->n + n > (int64_t)0xffffffffll) { p->set_error("more than 2^32 codes per device"); return LB_ERR_UNSUPPORTED; }
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         pq_grow(p, p->n + n);
         launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_vectors, n, p->d_codes.get() + (size_t)p->n * p->M, p->stream);
         LB_LAUNCH_CHECK();
-        LBP_HIP(hipStreamSynchronize(p->stream));
+        LB_HIP(hipStreamSynchronize(p->stream));
         p->n += n;
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_decode_device(lb_gpu_pq *p, int64_t n, const uint8_t *d_codes, float *d_vectors, void *stream)
@@ -343,37 +249,23 @@ int lb_gpu_pq_decode_device(lb_gpu_pq *p, int64_t n, const uint8_t *d_codes, flo
     if (!p || n < 0 || (n > 0 && (!d_vectors || !d_codes))) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     std::shared_lock<std::shared_mutex> g(p->mu);
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
         launch_pq_decode(p->d_codebooks.get(), p->M, p->K, p->sub, d_codes, n, d_vectors, s);
         LB_LAUNCH_CHECK();
-        LBP_HIP(hipStreamSynchronize(s));
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        LB_HIP(hipStreamSynchronize(s));
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_decode(lb_gpu_pq *p, int64_t n, const uint8_t *codes, float *vectors)
 {
     if (!p || n < 0 || (n > 0 && (!vectors || !codes))) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
-    try {
-        LBP_HIP(hipSetDevice(p->device));
-        const int64_t piece = std::max<int64_t>(1, ((int64_t)64 << 20) / p->dims);
-        Lease dv(p->device, (size_t)std::min(n, piece) * p->dims * 4), dc(p->device, (size_t)std::min(n, piece) * p->M);
-        for (int64_t r0 = 0; r0 < n; r0 += piece) {
-            const int64_t cnt = std::min(piece, n - r0);
-            LBP_HIP(hipMemcpy(dc.p, codes + (size_t)r0 * p->M, (size_t)cnt * p->M, hipMemcpyHostToDevice));
-            const int rc = lb_gpu_pq_decode_device(p, cnt, dc.as<uint8_t>(), dv.as<float>(), nullptr);
-            if (rc != LB_OK) return rc;
-            LBP_HIP(hipMemcpy(vectors + (size_t)r0 * p->dims, dv.p, (size_t)cnt * p->dims * 4, hipMemcpyDeviceToHost));
-        }
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+    return host_codec(p, n, codes, (size_t)p->M, vectors, (size_t)p->dims * 4, [&](void *dc, void *dv, int64_t cnt) {
+        return lb_gpu_pq_decode_device(p, cnt, static_cast<uint8_t *>(dc), static_cast<float *>(dv), nullptr);
+    });
 }
 
 // ---- ADC table / batch ----------------------------------------------------------------
@@ -381,18 +273,16 @@ int lb_gpu_pq_build_adc_table(lb_gpu_pq *p, const float *query, float *table)
 {
     if (!p || !query || !table) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(p->mu);
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         Lease dq(p->device, (size_t)p->dims * 4), dt(p->device, (size_t)p->M * p->K * 4);
-        LBP_HIP(hipMemcpyAsync(dq.p, query, (size_t)p->dims * 4, hipMemcpyHostToDevice, p->stream));
+        LB_HIP(hipMemcpyAsync(dq.p, query, (size_t)p->dims * 4, hipMemcpyHostToDevice, p->stream));
         launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, dq.as<float>(), 1, dt.as<float>(), p->stream);
         LB_LAUNCH_CHECK();
-        LBP_HIP(hipMemcpyAsync(table, dt.p, (size_t)p->M * p->K * 4, hipMemcpyDeviceToHost, p->stream));
-        LBP_HIP(hipStreamSynchronize(p->stream));
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        LB_HIP(hipMemcpyAsync(table, dt.p, (size_t)p->M * p->K * 4, hipMemcpyDeviceToHost, p->stream));
+        LB_HIP(hipStreamSynchronize(p->stream));
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_adc_distance_batch(lb_gpu_pq *p, const float *table, int64_t row0, int64_t n, float *results)
@@ -402,20 +292,18 @@ int lb_gpu_pq_adc_distance_batch(lb_gpu_pq *p, const float *table, int64_t row0,
     if (!table || !results) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(p->mu);
     if (row0 + n > p->n) { p->set_error("flatCodes buffer too small"); return LB_ERR_INVALID_ARG; } // adc_table.go:61-63
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         Lease dt(p->device, (size_t)p->M * 256 * 4), dr(p->device, (size_t)n * 4);
-        LBP_HIP(hipMemcpyAsync(dt.p, table, (size_t)p->M * 256 * 4, hipMemcpyHostToDevice, p->stream));
+        LB_HIP(hipMemcpyAsync(dt.p, table, (size_t)p->M * 256 * 4, hipMemcpyHostToDevice, p->stream));
         CandState cs{};
         launch_adc_scan(dt.as<float>(), p->M, p->d_codes.get(), row0, row0 + n, 0, nullptr, cs, false, dr.as<float>(), row0,
                         p->stream);
         LB_LAUNCH_CHECK();
-        LBP_HIP(hipMemcpyAsync(results, dr.p, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
-        LBP_HIP(hipStreamSynchronize(p->stream));
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        LB_HIP(hipMemcpyAsync(results, dr.p, (size_t)n * 4, hipMemcpyDeviceToHost, p->stream));
+        LB_HIP(hipStreamSynchronize(p->stream));
+        return LB_OK;
+    });
 }
 
 // ---- candidate re-rank (processChunkInternal, PQ branch) ----------------------------------
@@ -426,18 +314,16 @@ int lb_gpu_pq_rerank_device(lb_gpu_pq *p, const float *d_query, const int64_t *d
     if (n == 0) return LB_OK;
     if (!d_query || !d_rows || !d_dist) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(p->mu);
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
         Lease dt(p->device, (size_t)p->M * 256 * 4);
         launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, d_query, 1, dt.as<float>(), s);
         launch_adc_rerank(dt.as<float>(), p->M, p->d_codes.get(), p->n, d_rows, n, d_dist, d_score, s);
         LB_LAUNCH_CHECK();
-        LBP_HIP(hipStreamSynchronize(s));
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        LB_HIP(hipStreamSynchronize(s));
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_rerank(lb_gpu_pq *p, const float *query, const int64_t *rows, int64_t n, float *dist, float *score)
@@ -445,20 +331,18 @@ int lb_gpu_pq_rerank(lb_gpu_pq *p, const float *query, const int64_t *rows, int6
     if (!p || n < 0) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     if (!query || !rows || !dist) return LB_ERR_INVALID_ARG;
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         Lease dq(p->device, (size_t)p->dims * 4), drw(p->device, (size_t)n * 8), dd(p->device, (size_t)n * 4),
             ds(p->device, (size_t)n * 4);
-        LBP_HIP(hipMemcpy(dq.p, query, (size_t)p->dims * 4, hipMemcpyHostToDevice));
-        LBP_HIP(hipMemcpy(drw.p, rows, (size_t)n * 8, hipMemcpyHostToDevice));
+        LB_HIP(hipMemcpy(dq.p, query, (size_t)p->dims * 4, hipMemcpyHostToDevice));
+        LB_HIP(hipMemcpy(drw.p, rows, (size_t)n * 8, hipMemcpyHostToDevice));
         const int rc = lb_gpu_pq_rerank_device(p, dq.as<float>(), drw.as<int64_t>(), n, dd.as<float>(), ds.as<float>(), nullptr);
         if (rc != LB_OK) return rc;
-        LBP_HIP(hipMemcpy(dist, dd.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-        if (score) LBP_HIP(hipMemcpy(score, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        LB_HIP(hipMemcpy(dist, dd.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        if (score) LB_HIP(hipMemcpy(score, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_set_profiling(lb_gpu_pq *p, int enable)
@@ -489,13 +373,13 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
 {
     if (!p || nq < 0 || k <= 0 || (nq > 0 && (!d_queries || !d_dist || !d_labels))) return LB_ERR_INVALID_ARG;
     if (nq == 0) return LB_OK;
-    if (const int st = ctx_state(ctx)) { p->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded"); return st; }
+    if (const int st = ctx_state(ctx)) return ctx_fail(p, st);
     if (k > 4096) { p->set_error("k=%d exceeds the supported maximum 4096", k); return LB_ERR_UNSUPPORTED; }
     if (nq > 65536) { p->set_error("nq=%lld exceeds 65536 queries per call", (long long)nq); return LB_ERR_UNSUPPORTED; }
     std::shared_lock<std::shared_mutex> g(p->mu);
     std::unique_ptr<PqScratch> scp;
-    try {
-        LBP_HIP(hipSetDevice(p->device));
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
         const int nqi = (int)nq;
         // Sampled admission threshold (same reasoning as index_search.hip: sample_plan): one row in `stride` is scored
@@ -528,8 +412,8 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         int64_t stats[6] = {samp_count ? nqi : 0, 0, 0, 0, 0, 0};
         if (prof) {
             for (auto &e : p->ev)
-                if (!e) LBP_HIP(hipEventCreate(&e.h));
-            LBP_HIP(hipEventRecord(p->ev[0], s));
+                if (!e) LB_HIP(hipEventCreate(&e.h));
+            LB_HIP(hipEventRecord(p->ev[0], s));
         }
         launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, d_queries, nqi, sc.d_tables.get(), s, prefilter ? sc.d_minrng.get() : nullptr,
                                sc.cs.flags, prefilter ? sc.d_cand_cnt.get() : nullptr); // (also clears the slots' status words)
@@ -665,11 +549,10 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         };
         for (int q = 0; q < nqi; q++) {
             if (ctx && q > 0) { // a cancellable call waits for each pass before it enqueues the next (~10 us each)
-                LBP_HIP(hipStreamSynchronize(s));
+                LB_HIP(hipStreamSynchronize(s));
                 if (const int st = ctx_state(ctx)) {
                     release_scratch(p, std::move(scp));
-                    p->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded");
-                    return st;
+                    return ctx_fail(p, st);
                 }
             }
             if (q + 3 < nqi && scan_quad(q)) {
@@ -683,7 +566,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             scan_query(q, 0);
         }
         auto read_flags = [&]() { // (each query's last select wrote its status word into the pinned h_flags)
-            LBP_HIP(hipStreamSynchronize(s));
+            LB_HIP(hipStreamSynchronize(s));
         };
         read_flags();
         if (samp_count) {
@@ -695,8 +578,8 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         for (int q = 0; q < nqi; q++)
             if (sc.h_flags.get()[q] & 1u) { scan_query(q, 2); stats[5]++; } // chunks that cannot overflow the list
         LB_LAUNCH_CHECK();
-        if (prof) LBP_HIP(hipEventRecord(p->ev[1], s));
-        LBP_HIP(hipStreamSynchronize(s));
+        if (prof) LB_HIP(hipEventRecord(p->ev[1], s));
+        LB_HIP(hipStreamSynchronize(s));
         if (prof) {
             float a = 0.f, b = 0.f;
             if (samp_count && hipEventElapsedTime(&a, p->ev[2], p->ev[3]) != hipSuccess) a = 0.f;
@@ -710,10 +593,8 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             std::lock_guard<std::mutex> gs(p->stats_mu);
             std::copy(stats, stats + 6, p->last_stats);
         }
-    } catch (const HipErrP &e) {
-        return pq_fail(p, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_last_search_stats(const lb_gpu_pq *p, int64_t out[6])
@@ -744,11 +625,10 @@ static int pq_host_search_multi(lb_gpu_pq *p, HostReq *const *reqs, int nreq, in
     for (int i = 0; i < nreq; i++) nq += reqs[i]->nq;
     if (k > 4096) { p->set_error("k=%d exceeds the supported maximum 4096", k); return LB_ERR_UNSUPPORTED; }
     if (nq > 65536) { p->set_error("nq=%lld exceeds 65536 queries per call", (long long)nq); return LB_ERR_UNSUPPORTED; }
-    int rc = LB_OK;
-    try {
-        LBP_HIP(hipSetDevice(p->device));
-        const size_t qb = (size_t)nq * p->dims * 4, db = (((size_t)nq * k * 4) + 15) & ~(size_t)15, lbb = (size_t)nq * k * 8;
-        const size_t doff = (qb + 15) & ~(size_t)15, loff = doff + db, total = loff + lbb;
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        const size_t qb = (size_t)nq * p->dims * 4, db = up16((size_t)nq * k * 4), lbb = (size_t)nq * k * 8;
+        const size_t doff = up16(qb), loff = doff + db, total = loff + lbb;
         const bool direct = db + lbb <= ((size_t)64 << 10);
         Lease hs(p->device, total, /*pinned=*/true), dq(p->device, direct ? qb : total);
         char *hb = hs.as<char>(), *dbuf = dq.as<char>();
@@ -758,27 +638,21 @@ static int pq_host_search_multi(lb_gpu_pq *p, HostReq *const *reqs, int nreq, in
             std::memcpy(hb + off, reqs[i]->q, b);
             off += b;
         }
-        LBP_HIP(hipMemcpy(dbuf, hb, qb, hipMemcpyHostToDevice));
+        LB_HIP(hipMemcpy(dbuf, hb, qb, hipMemcpyHostToDevice));
         char *obuf = direct ? hb : dbuf;
-        rc = lb_gpu_pq_search_device_ctx(p, nq, reinterpret_cast<const float *>(dbuf), k, reinterpret_cast<float *>(obuf + doff),
-                                         reinterpret_cast<int64_t *>(obuf + loff), nullptr, ctx);
-        if (rc == LB_OK) {
-            if (!direct) LBP_HIP(hipMemcpy(hb + doff, dbuf + doff, db + lbb, hipMemcpyDeviceToHost));
-            size_t row = 0;
-            for (int i = 0; i < nreq; i++) {
-                const size_t n = (size_t)reqs[i]->nq * k;
-                std::memcpy(reqs[i]->dist, hb + doff + row * 4, n * 4);
-                std::memcpy(reqs[i]->labels, hb + loff + row * 8, n * 8);
-                row += n;
-            }
+        const int rc = lb_gpu_pq_search_device_ctx(p, nq, reinterpret_cast<const float *>(dbuf), k, reinterpret_cast<float *>(obuf + doff),
+                                                   reinterpret_cast<int64_t *>(obuf + loff), nullptr, ctx);
+        if (rc != LB_OK) return rc;
+        if (!direct) LB_HIP(hipMemcpy(hb + doff, dbuf + doff, db + lbb, hipMemcpyDeviceToHost));
+        size_t row = 0;
+        for (int i = 0; i < nreq; i++) {
+            const size_t n = (size_t)reqs[i]->nq * k;
+            std::memcpy(reqs[i]->dist, hb + doff + row * 4, n * 4);
+            std::memcpy(reqs[i]->labels, hb + loff + row * 8, n * 8);
+            row += n;
         }
-    } catch (const HipErrP &e) {
-        rc = pq_fail(p, e);
-    } catch (...) {
-        p->set_error("internal error (exception)");
-        rc = LB_ERR_INTERNAL;
-    }
-    return rc;
+        return LB_OK;
+    });
 }
 
 int lb_gpu_pq_search_ctx(lb_gpu_pq *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels,

@@ -3,68 +3,30 @@
 // kernels_sq8.hip.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
-#include "lb_host.h"
+#include "lb_handle.h"
 
-#include <algorithm>
 #include <atomic>
-#include <cstdarg>
-#include <cstdio>
-#include <mutex>
-#include <new>
-#include <shared_mutex>
-#include <string>
 #include <vector>
 
 using namespace lb;
 
-struct lb_gpu_sq8 {
-    int device = 0, dims = 0, stride = 0;
-    std::shared_mutex mu; // searches, reads and the codec share it; adds, reserve and the bounds take it alone
+struct lb_gpu_sq8 : CodeHandle { // searches, reads and the codec share mu; adds, reserve and the bounds take it alone
+    int stride = 0;
     DevBuf<uint8_t> d_codes;  // [capacity][stride], pad bytes zero
     DevBuf<int32_t> d_norms;  // [capacity]: sum of squares of each row, exact
-    int64_t n = 0, capacity = 0;
     std::atomic<bool> trained{false};
     std::vector<float> h_min, h_max;
     DevBuf<float> d_par;      // [4][dims]: min, max, scale, invScale
-    Stream stream;
-    mutable std::mutex err_mu;
-    std::string last_error;
     const float *dmin() const { return d_par.get(); }
     const float *dmax() const { return d_par.get() + dims; }
     const float *dscale() const { return d_par.get() + 2 * (size_t)dims; }
     const float *dinv() const { return d_par.get() + 3 * (size_t)dims; }
-    void set_error(const char *fmt, ...)
-    {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        std::lock_guard<std::mutex> g(err_mu);
-        try {
-            last_error = buf;
-        } catch (...) { // out of host memory: the status code still reaches the caller
-        }
-    }
 };
 
 namespace {
 
-constexpr int64_t kMaxRows = 0x7fffffffll;           // a key holds the row in 32 bits and the counts are u32
 constexpr int64_t kQueryBatch = 1024;                // queries per batch at most: bounds the histograms (8 MB) and the grid
 constexpr int64_t kDistScratch = (int64_t)1 << 30;   // bytes of S a batch may hold
-
-int sq8_fail(lb_gpu_sq8 *p, const HipErr &e)
-{
-    p->set_error("HIP error %d (%s) in %s", (int)e.e, hipGetErrorString(e.e), e.what);
-    return e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP;
-}
-
-int sq8_ctx_fail(lb_gpu_sq8 *p, int st)
-{
-    p->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded");
-    return st;
-}
 
 int untrained(lb_gpu_sq8 *p)
 {
@@ -72,32 +34,10 @@ int untrained(lb_gpu_sq8 *p)
     return LB_ERR_INVALID_ARG;
 }
 
-// The shell of an entry point: nothing but an lb_status leaves the library.  `s`, where given, is the stream the body
-// enqueued on: it is drained before the answer, so that no kernel still runs on what the caller gets back.
-template <class F> int sq8_guard(lb_gpu_sq8 *p, hipStream_t s, F &&body) noexcept
-{
-    try {
-        return body();
-    } catch (const HipErr &e) {
-        if (s) (void)hipStreamSynchronize(s);
-        return sq8_fail(p, e);
-    } catch (const std::bad_alloc &) {
-        if (s) (void)hipStreamSynchronize(s);
-        p->set_error("out of host memory");
-        return LB_ERR_OOM;
-    } catch (...) {
-        if (s) (void)hipStreamSynchronize(s);
-        p->set_error("internal error (exception)");
-        return LB_ERR_INTERNAL;
-    }
-}
-
-// geometric growth, as bq_grow: beyond 1 GiB by at most 25 % + the request
 void sq8_grow(lb_gpu_sq8 *p, int64_t need)
 {
     if (need <= p->capacity) return;
-    int64_t cap = std::max<int64_t>(std::max<int64_t>(need, p->capacity * 2), 4096);
-    if ((size_t)p->capacity * p->stride > ((size_t)1 << 30)) cap = std::max<int64_t>(need, p->capacity + p->capacity / 4);
+    const int64_t cap = grow_capacity(p->capacity, need, (size_t)p->stride);
     DevBuf<uint8_t> nc;
     DevBuf<int32_t> nn;
     nc.alloc((size_t)cap * p->stride);
@@ -110,11 +50,6 @@ void sq8_grow(lb_gpu_sq8 *p, int64_t need)
     p->d_norms = std::move(nn);
     p->capacity = cap;
 }
-
-size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
-
-// rows per staging piece of the host-pointer calls (<= 64 Mi elements)
-int64_t piece_rows(const lb_gpu_sq8 *p) { return std::max<int64_t>(1, ((int64_t)64 << 20) / p->dims); }
 
 // SQ8Config.Validate (scalar_quantization.go:44-49) and NewSQ8Encoder's scale / invScale (:75-79), in f32 on the host so
 // that no device division enters; the caller holds the writer lock.  NaN bounds pass, as there.
@@ -150,11 +85,11 @@ int train_impl(lb_gpu_sq8 *p, int64_t n, const float *vectors, bool on_device)
     std::unique_lock<std::shared_mutex> g(p->mu);
     if (p->n > 0) { p->set_error("the bounds cannot change once rows are stored"); return LB_ERR_INVALID_ARG; }
     Lease st, part, dv;
-    return sq8_guard(p, p->stream, [&]() -> int {
+    return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = p->stream;
         const int D = p->dims;
-        const int64_t piece = on_device ? n : std::min(n, piece_rows(p));
+        const int64_t piece = on_device ? n : std::min(n, piece_rows(p->dims));
         st.reset(p->device, (size_t)2 * D * 4);
         part.reset(p->device, (size_t)2 * sq8_bounds_parts(piece) * D * 4);
         if (!on_device) dv.reset(p->device, (size_t)piece * D * 4);
@@ -200,32 +135,30 @@ void codes_in(lb_gpu_sq8 *p, const uint8_t *codes, bool on_device, int64_t n, ui
 }
 
 // Exact k-NN of nq device-resident query codes u8[nq][stride]; the caller holds the reader lock, has made the device current
-// and has checked the arguments.  ctx is polled before every launch.  The scratch is leased into the caller's `sc`, which like
-// every pooled buffer of a search is declared outside the caller's sq8_guard: an error drains the stream before any of them
-// goes back to the pool, where a concurrent search could lease it.
+// and has checked the arguments.  ctx is polled before every launch.  The scratch is leased into the caller's `sc`, declared
+// outside the caller's guard as lb_handle.h asks of every pooled buffer.
 int sq8_search_codes_dev(lb_gpu_sq8 *p, int64_t nq, const uint8_t *d_Q, int k, float *d_dist, int64_t *d_labels, hipStream_t s,
                          const lb_cancel *ctx, Lease &sc)
 {
     Sq8Select a{};
     a.n = p->n;
     a.k = k;
-    sq8_select_plan(a.n, &a.nblk, &a.tpb);
+    countsel_plan(a.n, SQ8_MAX_BLOCKS, &a.nblk, &a.tpb);
     // the largest batch whose distances fit the scratch, at least one query
     const int64_t nb = std::min(std::min(nq, kQueryBatch), std::max<int64_t>(1, kDistScratch / 4 / std::max<int64_t>(a.n, 1)));
-    const size_t S_b = up16((size_t)nb * a.n * 4), qn_b = up16((size_t)nb * 4), hist_b = (size_t)nb * SQ8_RADIX_BINS * 4,
-                 thr_b = up16((size_t)nb * 8), cnt_b = up16((size_t)nb * std::max(a.nblk, 1) * 8), tot_b = up16((size_t)nb * 4),
-                 keys_b = (size_t)nb * k * 8;
+    int32_t *d_S = nullptr, *d_qn = nullptr;
+    auto layout = [&](Carve c) {
+        a.S = d_S = c.take<int32_t>((size_t)nb * a.n * 4);
+        d_qn = c.take<int32_t>((size_t)nb * 4);
+        a.hist = c.take<uint32_t>((size_t)nb * SQ8_RADIX_BINS * 4);
+        a.thr = c.take<uint32_t>((size_t)nb * 8);
+        a.cnt = c.take<uint32_t>((size_t)nb * std::max(a.nblk, 1) * 8);
+        a.tot = c.take<uint32_t>((size_t)nb * 4);
+        a.keys = c.take<uint64_t>((size_t)nb * k * 8);
+        return c.off;
+    };
+    lease_layout(sc, p->device, layout);
     int cancelled = 0;
-    sc.reset(p->device, S_b + qn_b + hist_b + thr_b + cnt_b + tot_b + keys_b);
-    char *base = sc.as<char>();
-    int32_t *d_S = reinterpret_cast<int32_t *>(base);
-    int32_t *d_qn = reinterpret_cast<int32_t *>(base + S_b);
-    a.S = d_S;
-    a.hist = reinterpret_cast<uint32_t *>(base + S_b + qn_b);
-    a.thr = reinterpret_cast<uint32_t *>(base + S_b + qn_b + hist_b);
-    a.cnt = reinterpret_cast<uint32_t *>(base + S_b + qn_b + hist_b + thr_b);
-    a.tot = reinterpret_cast<uint32_t *>(base + S_b + qn_b + hist_b + thr_b + cnt_b);
-    a.keys = reinterpret_cast<uint64_t *>(base + S_b + qn_b + hist_b + thr_b + cnt_b + tot_b);
     auto go = [&]() { // false: the context fired, nothing more is enqueued
         cancelled = ctx_state(ctx);
         return cancelled == 0;
@@ -248,57 +181,44 @@ int sq8_search_codes_dev(lb_gpu_sq8 *p, int64_t nq, const uint8_t *d_Q, int k, f
             if (cancelled || !go()) break;
             launch_sq8_count(a, s);
             if (!go()) break;
-            launch_sq8_scan(a, s);
+            launch_countsel_scan(a, s);
             if (!go()) break;
             launch_sq8_emit(a, s);
         }
         if (!go()) break;
-        launch_sq8_finish(a, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
+        launch_countsel_finish(a, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
     }
     LB_LAUNCH_CHECK();
     LB_HIP(hipStreamSynchronize(s));
-    return cancelled ? sq8_ctx_fail(p, cancelled) : LB_OK;
+    return cancelled ? ctx_fail(p, cancelled) : LB_OK;
 }
 
-// INVALID_ARG, then UNSUPPORTED, then the context: what every search entry point answers before it touches the device
+// knn_args with the untrained refusal of the entry points that encode their queries
 int search_args(lb_gpu_sq8 *p, int64_t nq, const void *queries, int k, const void *dist, const void *labels, bool encodes,
                 const lb_cancel *ctx)
 {
-    if (!p || nq < 0 || k <= 0 || (nq > 0 && (!queries || !dist || !labels))) return LB_ERR_INVALID_ARG;
-    if (encodes && !p->trained.load()) return untrained(p);
-    if (k > LB_MAX_K) { p->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
-    if (const int st = ctx_state(ctx)) return sq8_ctx_fail(p, st);
-    return LB_OK;
+    return knn_args(p, nq, queries, k, dist, labels, ctx, [&] { return encodes && !p->trained.load() ? untrained(p) : (int)LB_OK; });
 }
 
-// host queries (f32 rows, or packed codes when `coded`) -> pooled device buffers -> search -> results back
+// host queries (f32 rows, or packed codes when `coded`) -> search -> results back
 int host_search(lb_gpu_sq8 *p, int64_t nq, const void *queries, bool coded, int k, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
     const int rc = search_args(p, nq, queries, k, dist, labels, !coded, ctx);
     if (rc != LB_OK || nq == 0) return rc;
-    std::shared_lock<std::shared_mutex> g(p->mu);
-    Lease dq, dout, dv, sc;
-    return sq8_guard(p, p->stream, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        hipStream_t s = p->stream;
-        const size_t db = up16((size_t)nq * k * 4), lb = (size_t)nq * k * 8;
-        dq.reset(p->device, (size_t)nq * p->stride);
-        dout.reset(p->device, db + lb);
-        if (coded) {
-            codes_in(p, static_cast<const uint8_t *>(queries), false, nq, dq.as<uint8_t>(), dv, s);
-        } else {
+    return host_knn(
+        p, nq, (size_t)p->stride, k, dist, labels,
+        [&](Lease &dq, Lease &dv, hipStream_t s) {
+            if (coded) {
+                codes_in(p, static_cast<const uint8_t *>(queries), false, nq, dq.as<uint8_t>(), dv, s);
+                return;
+            }
             dv.reset(p->device, (size_t)nq * p->dims * 4);
             LB_HIP(hipMemcpyAsync(dv.p, queries, (size_t)nq * p->dims * 4, hipMemcpyHostToDevice, s));
             launch_sq8_encode(dv.as<float>(), nq, p->dims, p->dmin(), p->dmax(), p->dscale(), dq.as<uint8_t>(), s);
-        }
-        float *d_dist = dout.as<float>();
-        int64_t *d_labels = reinterpret_cast<int64_t *>(dout.as<char>() + db);
-        const int src = sq8_search_codes_dev(p, nq, dq.as<uint8_t>(), k, d_dist, d_labels, s, ctx, sc);
-        if (src != LB_OK) return src;
-        LB_HIP(hipMemcpy(dist, d_dist, (size_t)nq * k * 4, hipMemcpyDeviceToHost));
-        LB_HIP(hipMemcpy(labels, d_labels, lb, hipMemcpyDeviceToHost));
-        return LB_OK;
-    });
+        },
+        [&](Lease &dq, float *d_dist, int64_t *d_labels, hipStream_t s, Lease &sc) {
+            return sq8_search_codes_dev(p, nq, dq.as<uint8_t>(), k, d_dist, d_labels, s, ctx, sc);
+        });
 }
 
 int add_codes_impl(lb_gpu_sq8 *p, int64_t n, const uint8_t *codes, bool on_device)
@@ -306,9 +226,9 @@ int add_codes_impl(lb_gpu_sq8 *p, int64_t n, const uint8_t *codes, bool on_devic
     if (!p || n < 0 || (n > 0 && !codes)) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
-    if (n > kMaxRows - p->n) { p->set_error("2^31 or more codes per handle"); return LB_ERR_UNSUPPORTED; }
+    if (const int st = rows_fit(p, p->n, n)) return st;
     Lease tmp;
-    return sq8_guard(p, p->stream, [&]() -> int {
+    return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         sq8_grow(p, p->n + n);
         uint8_t *dst = p->d_codes.get() + (size_t)p->n * p->stride;
@@ -327,13 +247,13 @@ int add_vectors_impl(lb_gpu_sq8 *p, int64_t n, const float *vectors, bool on_dev
     if (n == 0) return LB_OK;
     if (!p->trained.load()) return untrained(p);
     std::unique_lock<std::shared_mutex> g(p->mu);
-    if (n > kMaxRows - p->n) { p->set_error("2^31 or more codes per handle"); return LB_ERR_UNSUPPORTED; }
+    if (const int st = rows_fit(p, p->n, n)) return st;
     Lease dv;
-    return sq8_guard(p, p->stream, [&]() -> int {
+    return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = p->stream;
         sq8_grow(p, p->n + n);
-        const int64_t piece = on_device ? n : std::min(n, piece_rows(p));
+        const int64_t piece = on_device ? n : std::min(n, piece_rows(p->dims));
         if (!on_device) dv.reset(p->device, (size_t)piece * p->dims * 4);
         for (int64_t r0 = 0; r0 < n; r0 += piece) { // the rows become visible (p->n) only once all are encoded
             const int64_t cnt = std::min(piece, n - r0);
@@ -359,69 +279,15 @@ extern "C" {
 
 lb_gpu_sq8 *lb_gpu_sq8_new(int device, int dims, int *out_status)
 {
-    auto st = [&](int v) { if (out_status) *out_status = v; };
-    if (dims <= 0) { st(LB_ERR_INVALID_ARG); return nullptr; }
-    if (dims > LB_MAX_DIM) { st(LB_ERR_UNSUPPORTED); return nullptr; }
-    if (!device_ok(device)) { st(LB_ERR_NO_DEVICE); return nullptr; }
-    auto *p = new (std::nothrow) lb_gpu_sq8();
-    if (!p) { st(LB_ERR_OOM); return nullptr; }
-    p->device = device;
-    p->dims = dims;
-    p->stride = sq8_stride(dims);
-    try {
-        LB_HIP(hipSetDevice(device));
-        LB_HIP(hipStreamCreateWithFlags(&p->stream.h, hipStreamNonBlocking));
-    } catch (const HipErr &e) {
-        st(e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP);
-        lb_gpu_sq8_free(p);
-        return nullptr;
-    } catch (...) {
-        st(LB_ERR_INTERNAL);
-        lb_gpu_sq8_free(p);
-        return nullptr;
-    }
-    st(LB_OK);
-    return p;
+    return handle_new<lb_gpu_sq8>(device, dims, out_status, [](lb_gpu_sq8 *p) { p->stride = sq8_stride(p->dims); });
 }
 
-void lb_gpu_sq8_free(lb_gpu_sq8 *p)
-{
-    if (!p) return;
-    {
-        std::unique_lock<std::shared_mutex> g(p->mu);
-        (void)hipSetDevice(p->device);
-        (void)hipDeviceSynchronize();
-    }
-    delete p;
-}
-
-const char *lb_gpu_sq8_last_error(const lb_gpu_sq8 *p)
-{
-    if (!p) return "null handle";
-    std::lock_guard<std::mutex> g(p->err_mu);
-    return p->last_error.c_str();
-}
-
+void lb_gpu_sq8_free(lb_gpu_sq8 *p) { handle_free(p); }
+const char *lb_gpu_sq8_last_error(const lb_gpu_sq8 *p) { return handle_last_error(p); }
 int lb_gpu_sq8_dims(const lb_gpu_sq8 *p) { return p ? p->dims : 0; }
 int lb_gpu_sq8_trained(const lb_gpu_sq8 *p) { return p && p->trained.load() ? 1 : 0; }
-int64_t lb_gpu_sq8_ntotal(const lb_gpu_sq8 *p)
-{
-    if (!p) return 0;
-    std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_sq8 *>(p)->mu);
-    return p->n;
-}
-
-int lb_gpu_sq8_reserve(lb_gpu_sq8 *p, int64_t n_total)
-{
-    if (!p || n_total < 0) return LB_ERR_INVALID_ARG;
-    if (n_total > kMaxRows) { p->set_error("2^31 or more codes per handle"); return LB_ERR_UNSUPPORTED; }
-    std::unique_lock<std::shared_mutex> g(p->mu);
-    return sq8_guard(p, nullptr, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        sq8_grow(p, n_total);
-        return LB_OK;
-    });
-}
+int64_t lb_gpu_sq8_ntotal(const lb_gpu_sq8 *p) { return handle_ntotal(p); }
+int lb_gpu_sq8_reserve(lb_gpu_sq8 *p, int64_t n_total) { return handle_reserve(p, n_total, sq8_grow); }
 
 // ---- bounds -----------------------------------------------------------------------------------------------------------
 int lb_gpu_sq8_set_bounds(lb_gpu_sq8 *p, const float *min, const float *max)
@@ -429,7 +295,7 @@ int lb_gpu_sq8_set_bounds(lb_gpu_sq8 *p, const float *min, const float *max)
     if (!p || !min || !max) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(p->mu);
     if (p->n > 0) { p->set_error("the bounds cannot change once rows are stored"); return LB_ERR_INVALID_ARG; }
-    return sq8_guard(p, nullptr, [&]() -> int { return commit_bounds(p, min, max); });
+    return guard(p, nullptr, [&]() -> int { return commit_bounds(p, min, max); });
 }
 
 int lb_gpu_sq8_train(lb_gpu_sq8 *p, int64_t n, const float *vectors) { return train_impl(p, n, vectors, false); }
@@ -456,12 +322,9 @@ int lb_gpu_sq8_get_codes(lb_gpu_sq8 *p, int64_t row0, int64_t n, uint8_t *codes)
     if (!p || row0 < 0 || n < 0 || (n > 0 && !codes)) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     std::shared_lock<std::shared_mutex> g(p->mu);
-    if (n > p->n || row0 > p->n - n) {
-        p->set_error("rows [%lld, %lld) outside the %lld stored codes", (long long)row0, (long long)(row0 + n), (long long)p->n);
-        return LB_ERR_INVALID_ARG;
-    }
+    if (const int st = rows_in_range(p, row0, n)) return st;
     Lease tmp;
-    return sq8_guard(p, p->stream, [&]() -> int {
+    return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         const uint8_t *src = p->d_codes.get() + (size_t)row0 * p->stride;
         if (p->stride != p->dims) { // strip the pad bytes
@@ -485,12 +348,12 @@ int lb_gpu_sq8_encode_device(lb_gpu_sq8 *p, int64_t n, const float *d_vectors, u
     std::shared_lock<std::shared_mutex> g(p->mu);
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
     Lease tmp;
-    return sq8_guard(p, s, [&]() -> int {
+    return guard(p, s, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         if (p->stride == p->dims) {
             launch_sq8_encode(d_vectors, n, p->dims, p->dmin(), p->dmax(), p->dscale(), d_codes, s);
         } else { // the kernel writes whole 16-byte strides: pack them behind it
-            const int64_t piece = std::min(n, piece_rows(p));
+            const int64_t piece = std::min(n, piece_rows(p->dims));
             tmp.reset(p->device, (size_t)piece * p->stride);
             for (int64_t r0 = 0; r0 < n; r0 += piece) {
                 const int64_t cnt = std::min(piece, n - r0);
@@ -509,18 +372,8 @@ int lb_gpu_sq8_encode(lb_gpu_sq8 *p, int64_t n, const float *vectors, uint8_t *c
     if (!p || n < 0 || (n > 0 && (!vectors || !codes))) return LB_ERR_INVALID_ARG;
     if (n == 0) return LB_OK;
     if (!p->trained.load()) return untrained(p);
-    return sq8_guard(p, nullptr, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        const int64_t piece = std::min(n, piece_rows(p));
-        Lease dv(p->device, (size_t)piece * p->dims * 4), dc(p->device, (size_t)piece * p->dims);
-        for (int64_t r0 = 0; r0 < n; r0 += piece) {
-            const int64_t cnt = std::min(piece, n - r0);
-            LB_HIP(hipMemcpy(dv.p, vectors + (size_t)r0 * p->dims, (size_t)cnt * p->dims * 4, hipMemcpyHostToDevice));
-            const int rc = lb_gpu_sq8_encode_device(p, cnt, dv.as<float>(), dc.as<uint8_t>(), nullptr);
-            if (rc != LB_OK) return rc;
-            LB_HIP(hipMemcpy(codes + (size_t)r0 * p->dims, dc.p, (size_t)cnt * p->dims, hipMemcpyDeviceToHost));
-        }
-        return LB_OK;
+    return host_codec(p, n, vectors, (size_t)p->dims * 4, codes, (size_t)p->dims, [&](void *dv, void *dc, int64_t cnt) {
+        return lb_gpu_sq8_encode_device(p, cnt, static_cast<float *>(dv), static_cast<uint8_t *>(dc), nullptr);
     });
 }
 
@@ -530,20 +383,10 @@ int lb_gpu_sq8_decode(lb_gpu_sq8 *p, int64_t n, const uint8_t *codes, float *vec
     if (n == 0) return LB_OK;
     if (!p->trained.load()) return untrained(p);
     std::shared_lock<std::shared_mutex> g(p->mu);
-    Lease dv, dc;
-    return sq8_guard(p, p->stream, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        const int64_t piece = std::min(n, piece_rows(p));
-        dv.reset(p->device, (size_t)piece * p->dims * 4);
-        dc.reset(p->device, (size_t)piece * p->dims);
-        for (int64_t r0 = 0; r0 < n; r0 += piece) {
-            const int64_t cnt = std::min(piece, n - r0);
-            LB_HIP(hipMemcpyAsync(dc.p, codes + (size_t)r0 * p->dims, (size_t)cnt * p->dims, hipMemcpyHostToDevice, p->stream));
-            launch_sq8_decode(dc.as<uint8_t>(), cnt, p->dims, p->dims, p->dmin(), p->dinv(), dv.as<float>(), p->stream);
-            LB_LAUNCH_CHECK();
-            LB_HIP(hipStreamSynchronize(p->stream));
-            LB_HIP(hipMemcpy(vectors + (size_t)r0 * p->dims, dv.p, (size_t)cnt * p->dims * 4, hipMemcpyDeviceToHost));
-        }
+    return host_codec(p, n, codes, (size_t)p->dims, vectors, (size_t)p->dims * 4, [&](void *dc, void *dv, int64_t cnt) -> int {
+        launch_sq8_decode(static_cast<uint8_t *>(dc), cnt, p->dims, p->dims, p->dmin(), p->dinv(), static_cast<float *>(dv), p->stream);
+        LB_LAUNCH_CHECK();
+        LB_HIP(hipStreamSynchronize(p->stream));
         return LB_OK;
     });
 }
@@ -555,12 +398,9 @@ int lb_gpu_sq8_distance_batch(lb_gpu_sq8 *p, const uint8_t *qcode, int64_t row0,
     if (n == 0) return LB_OK;
     if (!qcode || !results) return LB_ERR_INVALID_ARG;
     std::shared_lock<std::shared_mutex> g(p->mu);
-    if (n > p->n || row0 > p->n - n) {
-        p->set_error("rows [%lld, %lld) outside the %lld stored codes", (long long)row0, (long long)(row0 + n), (long long)p->n);
-        return LB_ERR_INVALID_ARG;
-    }
+    if (const int st = rows_in_range(p, row0, n)) return st;
     Lease dq, dr;
-    return sq8_guard(p, p->stream, [&]() -> int {
+    return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = p->stream;
         dq.reset(p->device, (size_t)p->stride + 16); // the query at its stride, then its norm
@@ -586,7 +426,7 @@ int lb_gpu_sq8_rerank_device(lb_gpu_sq8 *p, const uint8_t *d_qcode, const int64_
     if (d_euclid && !p->trained.load()) return untrained(p);
     std::shared_lock<std::shared_mutex> g(p->mu);
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
-    return sq8_guard(p, s, [&]() -> int {
+    return guard(p, s, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         launch_sq8_rerank(p->d_codes.get(), p->stride, p->dims, p->n, d_qcode, d_rows, n, d_euclid ? p->dmin() : nullptr,
                           d_euclid ? p->dinv() : nullptr, d_s, d_euclid, s);
@@ -602,7 +442,7 @@ int lb_gpu_sq8_rerank(lb_gpu_sq8 *p, const uint8_t *qcode, const int64_t *rows, 
     if (n == 0) return LB_OK;
     if (!qcode || !rows || !s_out) return LB_ERR_INVALID_ARG;
     if (euclid && !p->trained.load()) return untrained(p);
-    return sq8_guard(p, nullptr, [&]() -> int {
+    return guard(p, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         Lease dq(p->device, (size_t)p->dims), drw(p->device, (size_t)n * 8), ds(p->device, (size_t)n * 4), de(p->device, (size_t)n * 4);
         LB_HIP(hipMemcpy(dq.p, qcode, (size_t)p->dims, hipMemcpyHostToDevice));
@@ -625,7 +465,7 @@ int lb_gpu_sq8_search_device_ctx(lb_gpu_sq8 *p, int64_t nq, const float *d_queri
     std::shared_lock<std::shared_mutex> g(p->mu);
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
     Lease dq, sc;
-    return sq8_guard(p, s, [&]() -> int {
+    return guard(p, s, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         dq.reset(p->device, (size_t)nq * p->stride);
         launch_sq8_encode(d_queries, nq, p->dims, p->dmin(), p->dmax(), p->dscale(), dq.as<uint8_t>(), s);

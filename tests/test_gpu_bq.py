@@ -264,6 +264,35 @@ def test_search_two_tiles_per_workgroup(search_case, corpus, first, nq, k):
     assert np.array_equal(dist, odist[sel, :k])
 
 
+# The scan of the per-workgroup counts (countsel_scan_kernel, shared with the SQ8 index) gives each of its 256 threads
+# ceil(nblk / 256) workgroups.  70,145 rows are 275 tiles, one workgroup each: two per thread, and the last occupied thread owns
+# the single workgroup 274, whose tile holds one row.
+_SCAN_N = 70145
+assert -(-_SCAN_N // 256) == 275 and _SCAN_N % 256 == 1
+
+
+def _three_values_case(rng):
+    """Three distinct codes assigned at random, the last row among the first's: with the three as queries the rows at the
+    threshold (distance 0) lie in nearly every workgroup, and the last one is the last row of the corpus.  A fourth code on
+    about one row in 70 and as the fourth query: at k = 2048 its thousand rows are the rows BELOW the threshold, a few in most
+    workgroups, so the scan of both counts is pinned."""
+    four = _rand_codes(rng, 4, 64)
+    assert np.unique(four).size == 4
+    which = rng.integers(0, 3, _SCAN_N)
+    which[rng.random(_SCAN_N) < 1 / 70] = 3
+    which[-1] = 0
+    assert 100 < (which == 3).sum() < 2048 and np.unique(np.flatnonzero(which == 3) // 256).size > 200
+    return four[which], four
+
+
+@pytest.mark.parametrize("k", [100, 2048])
+def test_search_scan_gives_a_thread_two_workgroups(search_case, k):
+    enc, qcodes, olab, odist = search_case((64, _SCAN_N, "three values"), _three_values_case)
+    lab, dist = enc.search_codes(qcodes, k)
+    assert np.array_equal(lab, olab[:, :k]), np.argwhere(lab != olab[:, :k])[:5]
+    assert np.array_equal(dist, odist[:, :k])
+
+
 @pytest.mark.parametrize("nq", [1025, 2049])
 def test_search_more_queries_than_one_batch(nq):
     """the selection runs 1024 queries at a time over one scratch: the second and third batch reuse the histograms, counts and

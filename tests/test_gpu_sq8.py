@@ -409,6 +409,31 @@ def test_search_where_a_workgroup_walks_several_tiles():
     enc.Close()
 
 
+# The scan of the per-workgroup counts (countsel_scan_kernel, shared with the BQ index) gives each of its 256 threads
+# ceil(nblk / 256) workgroups.  70,145 rows are 275 tiles, one workgroup each: two per thread, and the last occupied thread owns
+# the single workgroup 274, whose tile holds one row.
+_SCAN_N = 70145
+assert -(-_SCAN_N // TILE) == 275 and _SCAN_N % TILE == 1 and 275 <= MAX_BLOCKS
+
+
+def test_search_scan_gives_a_thread_two_workgroups():
+    # Three distinct codes at dims 1 assigned at random, the last row among the first's: with the three as queries the rows at
+    # the threshold (S = 0) lie in nearly every workgroup, and the last one is the last row of the corpus.  A fourth code on
+    # about one row in 70 and as the fourth query: at k = 2048 its thousand rows are the rows BELOW the threshold, a few in
+    # most workgroups, so the scan of both counts is pinned.
+    rng = np.random.default_rng(_SCAN_N)
+    four = rng.choice(256, 4, replace=False).astype(np.uint8).reshape(4, 1)
+    which = rng.integers(0, 3, _SCAN_N)
+    which[rng.random(_SCAN_N) < 1 / 70] = 3
+    which[-1] = 0
+    assert 100 < (which == 3).sum() < 2048 and np.unique(np.flatnonzero(which == 3) // TILE).size > 200
+    codes = four[which]
+    enc = _enc(1)
+    enc.add_codes(codes)
+    _check_search(enc, four, codes, [100, 2048], ctx="three values and a sparse fourth")
+    enc.Close()
+
+
 # ---- the three radix digits -------------------------------------------------------------------------------------------------
 def _digit_rows(a, b, c):
     """rows at dims 8192 whose S against the zero query is a * 2^21 + b * 2^10 + c: 128 a bytes of 128, b bytes of 32, c of 1"""
