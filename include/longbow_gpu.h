@@ -423,11 +423,18 @@ int lb_gpu_pq_train_last_timing(float ms[3]);
  *   decode    bit 1 -> 1.0f, bit 0 -> -1.0f, dims values per row (binary_quantization.go:80-92).
  *   search    exact k-NN of each query over all stored codes, ascending by (distance, row position): the lowest position
  *             wins every tie (as lb_gpu_index_search).  Labels are row positions.  Fewer than k rows: label -1, dist FLT_MAX.
+ *   filter    a row filter on the handle, with the semantics of lb_gpu_index_set_filter / _filter_*: a row is visible iff its mask
+ *             byte is non-zero; a NULL mask clears the filter; n != ntotal is LB_ERR_INVALID_ARG with a last_error text and leaves
+ *             the filter as it was.  Rows added after a filter was set are visible.  With a filter, every search* call returns
+ *             the exact k-NN among the visible rows: the same distances, the same tie rule (the lowest rows win), labels are
+ *             corpus rows.  Fewer than k visible rows: they come first, then label -1 / dist FLT_MAX; no visible row: all padding.
+ *             hamming_batch, rerank*, get_codes and the codec address rows directly and ignore the filter.  Any filter, an
+ *             all-visible one too, searches the ascending list of visible rows, so the cost follows their number.
  *   limits    dims in 1..LB_MAX_DIM, k in 1..LB_MAX_K, fewer than 2^31 rows per handle: LB_ERR_UNSUPPORTED beyond.
  * Argument checks answer before a device is touched: LB_ERR_INVALID_ARG (NULL handle or pointer, dims <= 0, k <= 0, negative
  * counts, rows outside the stored ones) before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, the order of lb_gpu_pq_train.  A
  * refused call writes nothing.  Host pointers are borrowed for the call; d_ pointers are device memory.  Searches, reads and
- * rerank are thread-safe against each other and exclusive against reserve and the add calls. */
+ * rerank are thread-safe against each other and exclusive against reserve, the add calls and the filter calls. */
 typedef struct lb_gpu_bq lb_gpu_bq;
 lb_gpu_bq *lb_gpu_bq_new(int device, int dims, int *out_status);
 void lb_gpu_bq_free(lb_gpu_bq *p);
@@ -464,6 +471,17 @@ int lb_gpu_bq_search(lb_gpu_bq *p, int64_t nq, const float *queries, int k, floa
 int lb_gpu_bq_search_ctx(lb_gpu_bq *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx);
 int lb_gpu_bq_search_device_ctx(lb_gpu_bq *p, int64_t nq, const float *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
                                 const lb_cancel *ctx);
+/* the row filter: mask u8[ntotal] of the host (NULL clears it) */
+int lb_gpu_bq_set_filter(lb_gpu_bq *p, const uint8_t *mask, int64_t n);
+/* a predicate evaluated on the device into the mask: arguments, null rule and combine as lb_gpu_index_filter_int64 / _float32
+ * (column has ntotal host values, op is an lb_compare_op, validity an Arrow bitmap read from bit validity_offset on or NULL,
+ * nulls never match; combine 0 replaces the mask, 1 ANDs into it bytewise, and on a handle without a filter replaces it) */
+int lb_gpu_bq_filter_int64(lb_gpu_bq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                           int64_t validity_offset, int combine);
+int lb_gpu_bq_filter_float32(lb_gpu_bq *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                             int64_t validity_offset, int combine);
+/* rows a search sees: ntotal without a filter; 0 for a NULL handle */
+int64_t lb_gpu_bq_nvisible(const lb_gpu_bq *p);
 
 /* ---- scalar quantisation: uint8 codes and exact integer k-NN ----------------------------
  * store.SQ8Encoder (internal/store/scalar_quantization.go) and simd.EuclideanDistanceSQ8 (internal/simd/sq8.go:45-66): one
@@ -489,12 +507,19 @@ int lb_gpu_bq_search_device_ctx(lb_gpu_bq *p, int64_t nq, const float *d_queries
  *   search    exact k-NN over all stored codes, ascending by (S, row position): the lowest position wins every tie.  The
  *             reported distance is float32(S) (EuclideanDistanceSQ8Batch, internal/simd/simd.go:170-182): two different S may
  *             round to one float, the order is the integers'.  Fewer than k rows: label -1, dist FLT_MAX.
+ *   filter    a row filter on the handle, with the semantics of lb_gpu_index_set_filter / _filter_*: a row is visible iff its mask
+ *             byte is non-zero; a NULL mask clears the filter; n != ntotal is LB_ERR_INVALID_ARG with a last_error text and leaves
+ *             the filter as it was.  Rows added after a filter was set are visible.  With a filter, every search* call returns
+ *             the exact k-NN among the visible rows: the same distances, the same tie rule (the lowest rows win), labels are
+ *             corpus rows.  Fewer than k visible rows: they come first, then label -1 / dist FLT_MAX; no visible row: all padding.
+ *             distance_batch, rerank*, get_codes and the codec address rows directly and ignore the filter.  Any filter, an
+ *             all-visible one too, searches the ascending list of visible rows, so the cost follows their number.
  *   limits    dims in 1..LB_MAX_DIM, k in 1..LB_MAX_K, fewer than 2^31 rows per handle: LB_ERR_UNSUPPORTED beyond.
- * Calls on codes alone (add_codes, get_codes, distance_batch, rerank without euclid, search_codes) work on an untrained
- * handle; whatever encodes or decodes answers LB_ERR_INVALID_ARG ("config must be trained ...") on one.  Argument checks
+ * Calls on codes alone (add_codes, get_codes, distance_batch, rerank without euclid, search_codes, the filter calls) work on an
+ * untrained handle; whatever encodes or decodes answers LB_ERR_INVALID_ARG ("config must be trained ...") on one.  Argument checks
  * answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a refused call
  * writes nothing.  Host pointers are borrowed for the call; d_ pointers are device memory.  Searches, reads and the codec are
- * thread-safe against each other and exclusive against reserve, the add calls, set_bounds and train. */
+ * thread-safe against each other and exclusive against reserve, the add calls, set_bounds, train and the filter calls. */
 typedef struct lb_gpu_sq8 lb_gpu_sq8;
 lb_gpu_sq8 *lb_gpu_sq8_new(int device, int dims, int *out_status); /* untrained */
 void lb_gpu_sq8_free(lb_gpu_sq8 *p);
@@ -535,6 +560,13 @@ int lb_gpu_sq8_search(lb_gpu_sq8 *p, int64_t nq, const float *queries, int k, fl
 int lb_gpu_sq8_search_ctx(lb_gpu_sq8 *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx);
 int lb_gpu_sq8_search_device_ctx(lb_gpu_sq8 *p, int64_t nq, const float *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
                                  const lb_cancel *ctx);
+/* the row filter, as lb_gpu_bq_set_filter / _filter_int64 / _filter_float32 / _nvisible */
+int lb_gpu_sq8_set_filter(lb_gpu_sq8 *p, const uint8_t *mask, int64_t n);
+int lb_gpu_sq8_filter_int64(lb_gpu_sq8 *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                            int64_t validity_offset, int combine);
+int lb_gpu_sq8_filter_float32(lb_gpu_sq8 *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine);
+int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
 
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:

@@ -151,6 +151,10 @@ SIGNATURES = [
     ("lb_gpu_bq_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_bq_search_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
     ("lb_gpu_bq_search_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_bq_set_filter", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_bq_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
+    ("lb_gpu_bq_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
+    ("lb_gpu_bq_nvisible", _i64, [_vp]),
     ("lb_gpu_sq8_new", _vp, [_i, _i, _ip]),
     ("lb_gpu_sq8_free", None, [_vp]),
     ("lb_gpu_sq8_last_error", C.c_char_p, [_vp]),
@@ -177,6 +181,10 @@ SIGNATURES = [
     ("lb_gpu_sq8_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_sq8_search_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
     ("lb_gpu_sq8_search_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_sq8_set_filter", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_sq8_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
+    ("lb_gpu_sq8_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
+    ("lb_gpu_sq8_nvisible", _i64, [_vp]),
     ("lb_gpu_merge_topk_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_packed_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_rrf_fuse_device", _i, [_i, _i64, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),

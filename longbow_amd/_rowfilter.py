@@ -1,0 +1,44 @@
+"""The row filter of the code indexes, shared by bq.py and sq8.py."""
+import numpy as np
+
+
+class RowFilterMixin:
+    """The row filter of a code index (bq.BQEncoder, sq8.SQ8Encoder): what gpu.Index offers on the f32 index, on the
+    <_prefix>_set_filter / _filter_int64 / _filter_float32 / _nvisible entry points.  With a filter every search returns the
+    exact k-NN among the visible rows (labels stay corpus rows); rows added later are visible; the calls that address rows
+    directly ignore it."""
+    _prefix = None  # "lb_gpu_bq" / "lb_gpu_sq8"
+
+    def set_filter(self, mask):
+        """mask: ntotal bytes, a row is visible iff its byte is non-zero; None clears the filter"""
+        fn = getattr(self._lib, self._prefix + "_set_filter")
+        if mask is None:
+            self._check(fn(self._h, None, 0))
+            return
+        mask = np.ascontiguousarray(mask, np.uint8).reshape(-1)
+        self._check(fn(self._h, mask.ctypes.data, mask.size))
+
+    def filter_column(self, column, value, op, valid=None, combine=False, validity_offset=0):
+        """Evaluate `column OP value` on the device into the row mask.  column: int64 or float32, ntotal values; op: a
+        simd.CompareOp value or a query.Filter operator string; valid: an Arrow validity bitmap (LSB first, row i is bit
+        i + validity_offset; nulls never match) or None; combine=True ANDs into the current mask (replaces it when there is none)."""
+        from .simd import parse_operator
+        op = int(parse_operator(op))
+        column = np.ascontiguousarray(column).reshape(-1)
+        vptr = None
+        if valid is not None:
+            valid = np.ascontiguousarray(valid if isinstance(valid, np.ndarray) else np.frombuffer(valid, np.uint8), np.uint8)
+            vptr = valid.ctypes.data
+        if column.dtype == np.int64:
+            rc = getattr(self._lib, self._prefix + "_filter_int64")(self._h, column.ctypes.data, column.size, int(value), op, vptr,
+                                                                    validity_offset, 1 if combine else 0)
+        elif column.dtype == np.float32:
+            rc = getattr(self._lib, self._prefix + "_filter_float32")(self._h, column.ctypes.data, column.size, float(value), op, vptr,
+                                                                      validity_offset, 1 if combine else 0)
+        else:
+            raise TypeError(f"unsupported filter column type {column.dtype} (int64 / float32)")
+        self._check(rc)
+
+    def nvisible(self):
+        """rows a search sees: ntotal without a filter"""
+        return int(getattr(self._lib, self._prefix + "_nvisible")(self._h))

@@ -11,12 +11,14 @@ import math
 import numpy as np
 
 from . import _lib
+from ._rowfilter import RowFilterMixin
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 
 
-class BQEncoder:
+class BQEncoder(RowFilterMixin):
     """NewBQEncoder(dims) (binary_quantization.go:16-20) on the GPU."""
+    _prefix = "lb_gpu_bq"
 
     def __init__(self, dims, device=0, lib=None):
         if dims <= 0:
@@ -190,7 +192,9 @@ class BQEncoder:
 def search_rerank(bq, index, queries, k, oversample):
     """The two-stage use the codes exist for: a Hamming shortlist of k * oversample rows per query, then the exact distances
     of those rows on `index` (a float32 gpu.Index filled in the same row order; lb_gpu_index_rerank), sorted by
-    (distance, position) and cut to k.  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX."""
+    (distance, position) and cut to k.  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX.
+    Under a row filter on the encoder (set_filter / filter_column) the shortlist holds visible rows only, and the re-rank
+    addresses rows directly, so the result is the filtered one: nothing here changes, and `index` needs no filter."""
     v, _ = bq._vectors(queries)
     short, _ = bq.search(v, k * oversample)
     labels = np.full((v.shape[0], k), -1, np.int64)

@@ -6,7 +6,7 @@
 
 using namespace lb;
 
-struct lb_gpu_bq : CodeHandle { // searches and reads share mu, adds and reserve take it alone
+struct lb_gpu_bq : FilteredHandle { // searches and reads share mu; adds, reserve and the filter calls take it alone
     int W = 0;
     DevBuf<uint64_t> d_codes;
 };
@@ -22,19 +22,22 @@ void bq_grow(lb_gpu_bq *p, int64_t need)
     DevBuf<uint64_t> nc;
     nc.alloc((size_t)cap * p->W);
     if (p->n > 0) LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->W * 8, hipMemcpyDeviceToDevice));
+    p->filter.grow(p->n, cap);
     p->d_codes = std::move(nc);
     p->capacity = cap;
 }
 
-// Exact k-NN of nq device-resident query codes; the caller holds the reader lock, has made the device current and has checked
-// the arguments.  ctx is polled before every launch.  The scratch is leased into the caller's `sc`, declared outside the
+// Exact k-NN of nq device-resident query codes over the visible rows; the caller holds the reader lock, has made the device
+// current and has checked the arguments.  ctx is polled before every launch.  The scratch is leased into the caller's `sc`, declared outside the
 // caller's guard as lb_handle.h asks of every pooled buffer.
 int bq_search_codes_dev(lb_gpu_bq *p, int64_t nq, const uint64_t *d_Q, int k, float *d_dist, int64_t *d_labels, hipStream_t s,
                         const lb_cancel *ctx, Lease &sc)
 {
     BqSearch a{};
+    const RowView v = p->filter.view(p->n);
     a.codes = p->d_codes.get();
-    a.n = p->n;
+    a.n = v.n;
+    a.rowmap = v.rowmap;
     a.W = p->W;
     a.k = k;
     countsel_plan(a.n, BQ_MAX_BLOCKS, &a.nblk, &a.tpb);
@@ -71,7 +74,7 @@ int bq_search_codes_dev(lb_gpu_bq *p, int64_t nq, const uint64_t *d_Q, int k, fl
             launch_bq_emit(a, s);
         }
         if (!go()) break;
-        launch_countsel_finish(a, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
+        launch_countsel_finish(a, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s, v.rowmap);
     }
     LB_LAUNCH_CHECK();
     LB_HIP(hipStreamSynchronize(s));
@@ -105,11 +108,12 @@ int add_codes_impl(lb_gpu_bq *p, int64_t n, const uint64_t *codes, bool on_devic
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
     if (const int st = rows_fit(p, p->n, n)) return st;
-    return guard(p, nullptr, [&]() -> int {
+    return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         bq_grow(p, p->n + n);
         LB_HIP(hipMemcpy(p->d_codes.get() + (size_t)p->n * p->W, codes, (size_t)n * p->W * 8,
                          on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        p->filter.on_append(p->n, p->n + n, p->stream);
         p->n += n;
         return LB_OK;
     });
@@ -130,6 +134,20 @@ int lb_gpu_bq_dims(const lb_gpu_bq *p) { return p ? p->dims : 0; }
 int lb_gpu_bq_words(const lb_gpu_bq *p) { return p ? p->W : 0; }
 int64_t lb_gpu_bq_ntotal(const lb_gpu_bq *p) { return handle_ntotal(p); }
 int lb_gpu_bq_reserve(lb_gpu_bq *p, int64_t n_total) { return handle_reserve(p, n_total, bq_grow); }
+
+// ---- the row filter (lb_handle.h) ---------------------------------------------------------------------------------------
+int64_t lb_gpu_bq_nvisible(const lb_gpu_bq *p) { return filter_nvisible(p); }
+int lb_gpu_bq_set_filter(lb_gpu_bq *p, const uint8_t *mask, int64_t n) { return filter_set(p, mask, n); }
+int lb_gpu_bq_filter_int64(lb_gpu_bq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                           int64_t validity_offset, int combine)
+{
+    return filter_column<int64_t>(p, column, n, value, op, validity, validity_offset, combine);
+}
+int lb_gpu_bq_filter_float32(lb_gpu_bq *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                             int64_t validity_offset, int combine)
+{
+    return filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
+}
 
 int lb_gpu_bq_add_codes(lb_gpu_bq *p, int64_t n, const uint64_t *codes) { return add_codes_impl(p, n, codes, false); }
 int lb_gpu_bq_add_codes_device(lb_gpu_bq *p, int64_t n, const uint64_t *d_codes) { return add_codes_impl(p, n, d_codes, true); }
@@ -184,6 +202,7 @@ int lb_gpu_bq_add_vectors_device(lb_gpu_bq *p, int64_t n, const float *d_vectors
         launch_bq_encode(d_vectors, n, p->dims, p->d_codes.get() + (size_t)p->n * p->W, p->stream);
         LB_LAUNCH_CHECK();
         LB_HIP(hipStreamSynchronize(p->stream));
+        p->filter.on_append(p->n, p->n + n, p->stream);
         p->n += n;
         return LB_OK;
     });
@@ -208,6 +227,7 @@ int lb_gpu_bq_add_vectors(lb_gpu_bq *p, int64_t n, const float *vectors)
             LB_LAUNCH_CHECK();
             LB_HIP(hipStreamSynchronize(p->stream));
         }
+        p->filter.on_append(p->n, p->n + n, p->stream);
         p->n += n;
         return LB_OK;
     });

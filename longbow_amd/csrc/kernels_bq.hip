@@ -8,6 +8,11 @@
 // chunk (CW = 4, 8, 12 or 16: the words stay in registers for all QT queries); wider rows walk chunks of 8 words.  Words past
 // W are zero on both sides.  Distances sum whole words, so pad bits a caller stored count (as in the reference).
 //
+// Under a row filter a search walks the ascending uint32 list of visible rows: local position i of a tile is row
+// list[pos0 + i].  The tile's 256 row ids are staged into LDS first, one coalesced 1 KiB read of the list, and the chunk loop
+// takes them from there.  The gathers are then runs of CW (at most W) consecutive words per row, 96 B at 768 bits: partial 128-B
+// lines where the unmapped form reads whole ones.
+//
 // Top-k needs no candidate list: the distance takes at most 64*W + 1 <= 8193 values, so the search selects by counting
 // (lb_countsel.h states the method: hist, thresh, count, scan, emit, finish).  The hist, count and emit kernels here recompute
 // the distances tile by tile; the scan and the finish are kernels_countsel.hip's.
@@ -120,6 +125,53 @@ __device__ __forceinline__ bool bq_tile(const BqRows &a, int64_t pos0, int64_t p
     return mine;
 }
 
+constexpr int BQ_IDS_WORDS = BQ_ROWS / 2; // u64 words of LDS the staged row ids of a tile take, in front of the tile
+
+// bq_tile under a filtered search's list: local row pos0 + i is row list[pos0 + i], every entry a stored row.  The ids go to the
+// BQ_IDS_WORDS in front of lrow first; the chunk loop's barriers order their reads before the next tile's writes.  (A function
+// of its own, and bq_tile left as it is: the unmapped kernels then stay the code they were, instruction for instruction.  The
+// list is a parameter and not a field of BqRows, which is a kernel argument of bq_batch_kernel and bq_rerank_kernel.)
+template <int CW, int QT>
+__device__ __forceinline__ bool bq_tile_list(const BqRows &a, const uint32_t *list, int64_t pos0, int64_t pos_end, uint64_t *lrow,
+                                             const uint64_t *lq, int tid, int (&acc)[QT])
+{
+    constexpr int LD = CW + 1;
+    constexpr uint32_t NO_ROW = ~0u; // (rows are below 2^31)
+    uint32_t *lid = reinterpret_cast<uint32_t *>(lrow - BQ_IDS_WORDS);
+    const int W = a.W, nchunks = bq_nchunks(W, CW), Wq = nchunks * CW;
+#pragma unroll
+    for (int j = 0; j < QT; j++) acc[j] = 0;
+    const bool mine = pos0 + tid < pos_end;
+    lid[tid] = mine ? list[pos0 + tid] : NO_ROW;
+    __syncthreads();
+    for (int c = 0; c < nchunks; c++) {
+#pragma unroll
+        for (int i = 0; i < CW; i++) {
+            const int ch = tid + BQ_ROWS * i;
+            const int r = ch / CW, wv = ch - r * CW;
+            const int w = c * CW + wv;
+            const uint32_t id = lid[r]; // consecutive lanes: one word or consecutive ones (broadcast, no bank conflict)
+            uint64_t v = 0ull;
+            if (id != NO_ROW && w < W) v = a.codes[(int64_t)id * W + w];
+            lrow[r * LD + wv] = v;
+        }
+        __syncthreads();
+        uint64_t x[CW];
+#pragma unroll
+        for (int w = 0; w < CW; w++) x[w] = lrow[tid * LD + w];
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < QT; j++) {
+            const uint64_t *q = lq + j * Wq + c * CW;
+            int s = 0;
+#pragma unroll
+            for (int w = 0; w < CW; w++) s += __popcll(x[w] ^ q[w]);
+            acc[j] += s;
+        }
+    }
+    return mine;
+}
+
 // HammingDistanceBatch over stored rows [row0, row0 + n) (binary_quantization.go:56-60)
 template <int CW>
 __global__ __launch_bounds__(BQ_ROWS) void bq_batch_kernel(BqRows a, const uint64_t *qcode, int64_t row0, int64_t n, int32_t *out)
@@ -161,12 +213,14 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_rerank_kernel(BqRows a, const uint
 }
 
 // ---- top-k by counting ------------------------------------------------------------------------------------------------
-// workgroup b owns tiles [b*tpb, (b+1)*tpb): contiguous rows, so that positions order across workgroups
-template <int CW, int QT>
+// workgroup b owns tiles [b*tpb, (b+1)*tpb): contiguous rows, so that positions order across workgroups.  MAPPED: the rows are
+// the a.n positions of a.rowmap, and the keys carry positions (the finish maps them back)
+template <int CW, int QT, bool MAPPED>
 __global__ __launch_bounds__(BQ_ROWS) void bq_hist_kernel(BqSearch a)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t bq_smem[];
     uint64_t *lrow = bq_smem;
+    if constexpr (MAPPED) lrow += BQ_IDS_WORDS;
     uint64_t *lq = lrow + BQ_ROWS * (CW + 1);
     const int nbins = 64 * a.W + 1;
     uint32_t *lh = reinterpret_cast<uint32_t *>(lq + QT * bq_nchunks(a.W, CW) * CW);
@@ -180,7 +234,8 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_hist_kernel(BqSearch a)
     const int64_t t0 = (int64_t)blockIdx.x * a.tpb, t1 = t0 + a.tpb < ntiles ? t0 + a.tpb : ntiles;
     for (int64_t tile = t0; tile < t1; tile++) {
         int acc[QT];
-        if (bq_tile<CW, QT, false>(rows, tile * BQ_ROWS, a.n, lrow, lq, tid, acc)) {
+        if (MAPPED ? bq_tile_list<CW, QT>(rows, a.rowmap, tile * BQ_ROWS, a.n, lrow, lq, tid, acc)
+                   : bq_tile<CW, QT, false>(rows, tile * BQ_ROWS, a.n, lrow, lq, tid, acc)) {
 #pragma unroll
             for (int j = 0; j < QT; j++)
                 if (q0 + j < a.nq) atomicAdd(&lh[j * nbins + acc[j]], 1u);
@@ -214,11 +269,12 @@ __global__ __launch_bounds__(256) void bq_thresh_kernel(BqSearch a)
     }
 }
 
-template <int CW, int QT>
+template <int CW, int QT, bool MAPPED>
 __global__ __launch_bounds__(BQ_ROWS) void bq_count_kernel(BqSearch a)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t bq_smem[];
     uint64_t *lrow = bq_smem;
+    if constexpr (MAPPED) lrow += BQ_IDS_WORDS;
     uint64_t *lq = lrow + BQ_ROWS * (CW + 1);
     uint32_t *lc = reinterpret_cast<uint32_t *>(lq + QT * bq_nchunks(a.W, CW) * CW); // [QT][2]
     const int tid = threadIdx.x;
@@ -238,7 +294,8 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_count_kernel(BqSearch a)
     const int64_t t0 = (int64_t)blockIdx.x * a.tpb, t1 = t0 + a.tpb < ntiles ? t0 + a.tpb : ntiles;
     for (int64_t tile = t0; tile < t1; tile++) {
         int acc[QT];
-        const bool mine = bq_tile<CW, QT, false>(rows, tile * BQ_ROWS, a.n, lrow, lq, tid, acc);
+        const bool mine = MAPPED ? bq_tile_list<CW, QT>(rows, a.rowmap, tile * BQ_ROWS, a.n, lrow, lq, tid, acc)
+                                 : bq_tile<CW, QT, false>(rows, tile * BQ_ROWS, a.n, lrow, lq, tid, acc);
 #pragma unroll
         for (int j = 0; j < QT; j++) { // wave-uniform counts
             clt[j] += (uint32_t)__popcll(__ballot(mine && (uint32_t)acc[j] < t[j]));
@@ -256,11 +313,12 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_count_kernel(BqSearch a)
     if (tid < QT * 2 && q0 + (tid >> 1) < a.nq) a.cnt[((int64_t)(q0 + (tid >> 1)) * a.nblk + blockIdx.x) * 2 + (tid & 1)] = lc[tid];
 }
 
-template <int CW, int QT>
+template <int CW, int QT, bool MAPPED>
 __global__ __launch_bounds__(BQ_ROWS) void bq_emit_kernel(BqSearch a)
 {
     extern __shared__ __attribute__((aligned(16))) uint64_t bq_smem[];
     uint64_t *lrow = bq_smem;
+    if constexpr (MAPPED) lrow += BQ_IDS_WORDS;
     uint64_t *lq = lrow + BQ_ROWS * (CW + 1);
     uint32_t *run = reinterpret_cast<uint32_t *>(lq + QT * bq_nchunks(a.W, CW) * CW); // [QT][2] slots used so far: below t, at t
     uint32_t *wcnt = run + QT * 2;                                                     // [QT][4 waves][2]
@@ -286,7 +344,8 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_emit_kernel(BqSearch a)
     const unsigned long long lower = (1ull << lane) - 1ull;
     for (int64_t tile = t0; tile < t1; tile++) {
         int acc[QT];
-        const bool mine = bq_tile<CW, QT, false>(rows, tile * BQ_ROWS, a.n, lrow, lq, tid, acc);
+        const bool mine = MAPPED ? bq_tile_list<CW, QT>(rows, a.rowmap, tile * BQ_ROWS, a.n, lrow, lq, tid, acc)
+                                 : bq_tile<CW, QT, false>(rows, tile * BQ_ROWS, a.n, lrow, lq, tid, acc);
 #pragma unroll
         for (int j = 0; j < QT; j++) {
             const bool on = mine && q0 + j < a.nq;
@@ -317,14 +376,20 @@ __global__ __launch_bounds__(BQ_ROWS) void bq_emit_kernel(BqSearch a)
 
 // ---- launch plumbing --------------------------------------------------------------------------------------------------
 int bq_cw(int W) { return W <= 4 ? 4 : W <= 8 ? 8 : W <= 12 ? 12 : W <= 16 ? 16 : 8; }
-size_t bq_tile_lds(int W, int cw, int qt) { return ((size_t)BQ_ROWS * (cw + 1) + (size_t)qt * ((W + cw - 1) / cw) * cw) * 8; }
+// the tile and the queries, under a list the staged ids in front of them
+size_t bq_tile_lds(int W, int cw, int qt, bool mapped = false)
+{
+    return ((mapped ? (size_t)BQ_IDS_WORDS : 0) + (size_t)BQ_ROWS * (cw + 1) + (size_t)qt * ((W + cw - 1) / cw) * cw) * 8;
+}
 
 // the query tile of a launch (pick_qt) within the LDS budget, lds_per_query being what the kernel adds to the tile per query
-int bq_qt(int nq, int W, size_t lds_per_query)
+int bq_qt(int nq, int W, size_t lds_per_query, bool mapped)
 {
     const int cw = bq_cw(W);
-    return pick_qt(nq, [&](int qt) { return bq_tile_lds(W, cw, qt) + (size_t)qt * lds_per_query <= BQ_LDS_BUDGET; });
+    return pick_qt(nq, [&](int qt) { return bq_tile_lds(W, cw, qt, mapped) + (size_t)qt * lds_per_query <= BQ_LDS_BUDGET; });
 }
+// the widest single-query request: W = 128 (chunks of 8) with its histogram, under a list
+static_assert(((size_t)BQ_IDS_WORDS + BQ_ROWS * 9 + 128) * 8 + (64 * 128 + 1) * 4 <= BQ_LDS_BUDGET, "one query always fits");
 
 template <class F> void bq_with_cw(int cw, F &&f)
 {
@@ -334,6 +399,17 @@ template <class F> void bq_with_cw(int cw, F &&f)
     case 12: f(std::integral_constant<int, 12>{}); break;
     default: f(std::integral_constant<int, 16>{}); break;
     }
+}
+
+// f(CW, QT, MAPPED) as integral constants
+template <class F> void bq_with_form(int cw, int qt, bool mapped, F &&f)
+{
+    bq_with_cw(cw, [&](auto c) {
+        with_qt(qt, [&](auto q) {
+            if (mapped) f(c, q, std::true_type{});
+            else f(c, q, std::false_type{});
+        });
+    });
 }
 
 } // namespace
@@ -378,11 +454,12 @@ void launch_bq_rerank(const uint64_t *codes, int W, int dims, int64_t ntotal, co
 
 void launch_bq_hist(const BqSearch &a, hipStream_t s)
 {
-    const int cw = bq_cw(a.W), qt = bq_qt(a.nq, a.W, (size_t)(64 * a.W + 1) * 4);
-    const size_t lds = bq_tile_lds(a.W, cw, qt) + (size_t)qt * (64 * a.W + 1) * 4;
+    const bool mapped = a.rowmap != nullptr;
+    const int cw = bq_cw(a.W), qt = bq_qt(a.nq, a.W, (size_t)(64 * a.W + 1) * 4, mapped);
+    const size_t lds = bq_tile_lds(a.W, cw, qt, mapped) + (size_t)qt * (64 * a.W + 1) * 4;
     const dim3 grid((unsigned)a.nblk, (unsigned)((a.nq + qt - 1) / qt));
-    bq_with_cw(cw, [&](auto c) {
-        with_qt(qt, [&](auto q) { bq_hist_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
+    bq_with_form(cw, qt, mapped, [&](auto c, auto q, auto m) {
+        bq_hist_kernel<decltype(c)::value, decltype(q)::value, decltype(m)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a);
     });
 }
 
@@ -390,21 +467,23 @@ void launch_bq_thresh(const BqSearch &a, hipStream_t s) { bq_thresh_kernel<<<dim
 
 void launch_bq_count(const BqSearch &a, hipStream_t s)
 {
-    const int cw = bq_cw(a.W), qt = bq_qt(a.nq, a.W, 8);
-    const size_t lds = bq_tile_lds(a.W, cw, qt) + (size_t)qt * 8;
+    const bool mapped = a.rowmap != nullptr;
+    const int cw = bq_cw(a.W), qt = bq_qt(a.nq, a.W, 8, mapped);
+    const size_t lds = bq_tile_lds(a.W, cw, qt, mapped) + (size_t)qt * 8;
     const dim3 grid((unsigned)a.nblk, (unsigned)((a.nq + qt - 1) / qt));
-    bq_with_cw(cw, [&](auto c) {
-        with_qt(qt, [&](auto q) { bq_count_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
+    bq_with_form(cw, qt, mapped, [&](auto c, auto q, auto m) {
+        bq_count_kernel<decltype(c)::value, decltype(q)::value, decltype(m)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a);
     });
 }
 
 void launch_bq_emit(const BqSearch &a, hipStream_t s)
 {
-    const int cw = bq_cw(a.W), qt = bq_qt(a.nq, a.W, 40);
-    const size_t lds = bq_tile_lds(a.W, cw, qt) + (size_t)qt * 40;
+    const bool mapped = a.rowmap != nullptr;
+    const int cw = bq_cw(a.W), qt = bq_qt(a.nq, a.W, 40, mapped);
+    const size_t lds = bq_tile_lds(a.W, cw, qt, mapped) + (size_t)qt * 40;
     const dim3 grid((unsigned)a.nblk, (unsigned)((a.nq + qt - 1) / qt));
-    bq_with_cw(cw, [&](auto c) {
-        with_qt(qt, [&](auto q) { bq_emit_kernel<decltype(c)::value, decltype(q)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a); });
+    bq_with_form(cw, qt, mapped, [&](auto c, auto q, auto m) {
+        bq_emit_kernel<decltype(c)::value, decltype(q)::value, decltype(m)::value><<<grid, dim3(BQ_ROWS), lds, s>>>(a);
     });
 }
 

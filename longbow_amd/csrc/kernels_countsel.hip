@@ -47,8 +47,9 @@ __global__ __launch_bounds__(256) void countsel_scan_kernel(CountSel a)
     }
 }
 
-// the min(k, n) keys of a query, ascending by (distance, position) -> float32(distance) / labels, padded with FLT_MAX / -1
-__global__ __launch_bounds__(SEL_THREADS) void countsel_finish_kernel(CountSel a, float *dist, int64_t *labels)
+// the min(k, n) keys of a query, ascending by (distance, position) -> float32(distance) / labels, padded with FLT_MAX / -1;
+// under a list of visible rows (posmap) the label is the row behind the position
+__global__ __launch_bounds__(SEL_THREADS) void countsel_finish_kernel(CountSel a, float *dist, int64_t *labels, const uint32_t *posmap)
 {
     __shared__ uint64_t sh[2048];
     const int tid = threadIdx.x, q = blockIdx.x;
@@ -61,7 +62,12 @@ __global__ __launch_bounds__(SEL_THREADS) void countsel_finish_kernel(CountSel a
         const uint64_t key = sh[i];
         const bool pad = i >= have;
         dist[(int64_t)q * a.k + i] = pad ? FLT_MAX : (float)(uint32_t)(key >> 32);
-        labels[(int64_t)q * a.k + i] = pad ? -1 : (int64_t)(key & 0xffffffffull);
+        int64_t label = -1;
+        if (!pad) {
+            const uint32_t pos = (uint32_t)(key & 0xffffffffull);
+            label = posmap ? (int64_t)posmap[pos] : (int64_t)pos; // (the emit wrote all `have` keys: every position is below n)
+        }
+        labels[(int64_t)q * a.k + i] = label;
     }
 }
 
@@ -77,9 +83,9 @@ void countsel_plan(int64_t n, int max_blocks, int *nblk, int *tpb)
 
 void launch_countsel_scan(const CountSel &a, hipStream_t s) { countsel_scan_kernel<<<dim3((unsigned)a.nq), dim3(256), 0, s>>>(a); }
 
-void launch_countsel_finish(const CountSel &a, float *dist, int64_t *labels, hipStream_t s)
+void launch_countsel_finish(const CountSel &a, float *dist, int64_t *labels, hipStream_t s, const uint32_t *posmap)
 {
-    countsel_finish_kernel<<<dim3((unsigned)a.nq), dim3(SEL_THREADS), 0, s>>>(a, dist, labels);
+    countsel_finish_kernel<<<dim3((unsigned)a.nq), dim3(SEL_THREADS), 0, s>>>(a, dist, labels, posmap);
 }
 
 } // namespace lb

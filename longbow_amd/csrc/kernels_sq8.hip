@@ -7,7 +7,9 @@
 // tile's rows, fetched coalesced (consecutive lanes read consecutive pieces of the row-major codes) into an LDS tile whose row
 // stride is 5 pieces: odd in 16-byte slots, so the 16 lanes that one ds_read_b128 cycle serves (distinct modulo 16) fall on 16
 // distinct slots.  The QT queries' bytes lie in LDS and are read wave-uniform (broadcast).  x.q comes from v_dot4_u32_u8 and
-// S = |x|^2 + |q|^2 - 2 x.q in integers: at most 65025 * 8192 < 2^30, nothing wraps.
+// S = |x|^2 + |q|^2 - 2 x.q in integers: at most 65025 * 8192 < 2^30, nothing wraps.  Under a row list (a filtered search's
+// ascending uint32 list of visible rows) position i of a tile is row list[pos0 + i]: the tile's 256 ids are staged into LDS first,
+// one coalesced read of the list, and the pieces and the norm are gathered at them; S is then indexed by position.
 //
 // A search writes S once, as int32 [nq][n], and selects on that array by counting (lb_countsel.h states the method): a row is
 // up to 8 KiB of codes and 4 bytes of S.  The histogram is a radix one: three (hist, digit) rounds over the digits of S (bits
@@ -163,12 +165,17 @@ __global__ __launch_bounds__(256) void sq8_norms_kernel(const u32x4 *codes, int6
 }
 
 // ---- the distance pass ------------------------------------------------------------------------------------------------
-// workgroup (x, y): tiles [x * tpb, (x + 1) * tpb) of the rows [row0, row0 + n), queries [y * QT, (y + 1) * QT)
-template <int QT>
-__global__ __launch_bounds__(SQ8_ROWS) void sq8_dist_kernel(Sq8Dist a, int tpb)
+constexpr size_t sq8_ids_lds(bool mapped) { return mapped ? (size_t)SQ8_ROWS * 4 : 0; } // the staged ids, in front of the tile
+
+// workgroup (x, y): tiles [x * tpb, (x + 1) * tpb) of the rows [row0, row0 + n), queries [y * QT, (y + 1) * QT); MAPPED: of the
+// n positions of rowmap (row0 = 0).  The list is the last kernel argument, behind the parent's: the unmapped form never loads it
+// and its argument block, and with it its scalar register allocation, is what it was.
+template <int QT, bool MAPPED>
+__global__ __launch_bounds__(SQ8_ROWS) void sq8_dist_kernel(Sq8Dist a, int tpb, const uint32_t *rowmap)
 {
     extern __shared__ __attribute__((aligned(16))) u32x4 sq8_smem[];
     u32x4 *lrow = sq8_smem;                 // [SQ8_ROWS][SQ8_LD]
+    if constexpr (MAPPED) lrow += sq8_ids_lds(true) / 16; // the tile's row ids u32[SQ8_ROWS] lie in front of it
     u32x4 *lq = lrow + SQ8_ROWS * SQ8_LD;   // [QT][Pq], zero past P; a slot past nq repeats the last query
     const int tid = threadIdx.x;
     const int P = a.stride >> 4, nchunks = (P + SQ8_CH - 1) / SQ8_CH, Pq = nchunks * SQ8_CH;
@@ -192,6 +199,10 @@ __global__ __launch_bounds__(SQ8_ROWS) void sq8_dist_kernel(Sq8Dist a, int tpb)
         uint32_t acc[QT];
 #pragma unroll
         for (int j = 0; j < QT; j++) acc[j] = 0u;
+        if constexpr (MAPPED) { // (the chunk loop's barriers order the reads of the ids before the next tile's writes)
+            reinterpret_cast<uint32_t *>(sq8_smem)[tid] = pos0 + tid < a.n ? rowmap[pos0 + tid] : 0u;
+            __syncthreads();
+        }
         for (int c = 0; c < nchunks; c++) {
 #pragma unroll
             for (int i = 0; i < SQ8_CH; i++) {
@@ -199,7 +210,8 @@ __global__ __launch_bounds__(SQ8_ROWS) void sq8_dist_kernel(Sq8Dist a, int tpb)
                 const int r = ch / SQ8_CH, pv = ch - r * SQ8_CH;
                 const int p = c * SQ8_CH + pv;
                 u32x4 v = zero;
-                if (pos0 + r < a.n && p < P) v = codes[(a.row0 + pos0 + r) * P + p]; // a plain load: the other query tiles find the row in L2 / MALL
+                // a plain load: the other query tiles find the row in L2 / MALL
+                if (pos0 + r < a.n && p < P) v = codes[(MAPPED ? (int64_t)reinterpret_cast<const uint32_t *>(sq8_smem)[r] : a.row0 + pos0 + r) * P + p];
                 lrow[r * SQ8_LD + pv] = v;
             }
             __syncthreads();
@@ -215,7 +227,7 @@ __global__ __launch_bounds__(SQ8_ROWS) void sq8_dist_kernel(Sq8Dist a, int tpb)
             }
         }
         if (pos0 + tid < a.n) {
-            const int32_t xn = a.norms[a.row0 + pos0 + tid];
+            const int32_t xn = a.norms[MAPPED ? (int64_t)reinterpret_cast<const uint32_t *>(sq8_smem)[tid] : a.row0 + pos0 + tid];
 #pragma unroll
             for (int j = 0; j < QT; j++)
                 if (q0 + j < a.nq) a.out[(int64_t)(q0 + j) * a.n + pos0 + tid] = xn + qn[j] - 2 * (int32_t)acc[j];
@@ -375,16 +387,17 @@ __global__ __launch_bounds__(SQ8_ROWS) void sq8_emit_kernel(Sq8Select a)
     }
 }
 
-size_t sq8_dist_lds(int stride, int qt)
+// the staged ids (under a list), the tile and the queries
+size_t sq8_dist_lds(int stride, int qt, bool mapped)
 {
     const int P = stride >> 4, Pq = (P + SQ8_CH - 1) / SQ8_CH * SQ8_CH;
-    return ((size_t)SQ8_ROWS * SQ8_LD + (size_t)qt * Pq) * 16;
+    return sq8_ids_lds(mapped) + ((size_t)SQ8_ROWS * SQ8_LD + (size_t)qt * Pq) * 16;
 }
 
 // the query tile of a launch (pick_qt) within the LDS budget
-int sq8_qt(int nq, int stride)
+int sq8_qt(int nq, int stride, bool mapped)
 {
-    return pick_qt(nq, [&](int qt) { return sq8_dist_lds(stride, qt) <= SQ8_LDS_BUDGET; });
+    return pick_qt(nq, [&](int qt) { return sq8_dist_lds(stride, qt, mapped) <= SQ8_LDS_BUDGET; });
 }
 
 } // namespace
@@ -435,15 +448,19 @@ void launch_sq8_norms(const uint8_t *codes, int64_t n, int stride, int32_t *norm
                                                                                          norms);
 }
 
-void launch_sq8_dist(const Sq8Dist &a, hipStream_t s)
+void launch_sq8_dist(const Sq8Dist &a, hipStream_t s, const uint32_t *rowmap)
 {
     if (a.n <= 0 || a.nq <= 0) return;
     int nblk, tpb;
     countsel_plan(a.n, SQ8_MAX_BLOCKS, &nblk, &tpb);
-    const int qt = sq8_qt(a.nq, a.stride);
-    const size_t lds = sq8_dist_lds(a.stride, qt);
+    const bool mapped = rowmap != nullptr;
+    const int qt = sq8_qt(a.nq, a.stride, mapped);
+    const size_t lds = sq8_dist_lds(a.stride, qt, mapped);
     const dim3 grid((unsigned)nblk, (unsigned)((a.nq + qt - 1) / qt));
-    with_qt(qt, [&](auto q) { sq8_dist_kernel<decltype(q)::value><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb); });
+    with_qt(qt, [&](auto q) {
+        if (mapped) sq8_dist_kernel<decltype(q)::value, true><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb, rowmap);
+        else sq8_dist_kernel<decltype(q)::value, false><<<grid, dim3(SQ8_ROWS), lds, s>>>(a, tpb, nullptr);
+    });
 }
 
 void launch_sq8_rerank(const uint8_t *codes, int stride, int dims, int64_t ntotal, const uint8_t *qcode, const int64_t *rows, int64_t n,

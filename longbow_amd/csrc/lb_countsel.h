@@ -13,6 +13,8 @@
 //           (d << 32 | row): the tie rule is "the lowest positions win"                         [countsel_slot]
 //   finish  sort the <= k keys of a query in LDS, write distances and labels, pad with FLT_MAX / -1
 //                                                                                                [countsel_finish_kernel]
+// Under a row filter the rows above are the positions of the ascending list of visible rows (launch_countsel_finish's posmap): positions order
+// as rows do, so everything up to the emit runs over them unchanged, and the finish alone writes posmap[position] as the label.
 // Workgroups meet at launch boundaries only; nothing is written past slot k - 1 and every count is bounded by the data's size,
 // whatever the data.  Where the distance comes from (BQ recomputes it from LDS tiles in hist, count and emit; SQ8 reads its
 // matrix S) stays with each index, and so do the hist, count and emit kernels around these pieces.

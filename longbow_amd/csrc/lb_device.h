@@ -567,19 +567,23 @@ void launch_adc_rerank(const float *table, int M, const uint8_t *codes, int64_t 
 
 // The tail of a k-NN by counting (kernels_countsel.hip; the method is stated in lb_countsel.h): what the selections of
 // kernels_bq.hip and kernels_sq8.hip share once a per-query threshold is known.  Workgroup b of nblk owns the rows of tiles
-// [b * tpb, (b + 1) * tpb), 256 rows a tile.
+// [b * tpb, (b + 1) * tpb), 256 rows a tile.  Under a row filter the rows of a search are the positions of the ascending list of
+// visible rows: positions order as rows do, so the selection runs over them unchanged and only the finish maps them back.
 struct CountSel {
-    int64_t n;
+    int64_t n;         // rows the search walks: positions [0, n)
     int k, nq;
     int nblk, tpb;     // countsel_plan(n, max_blocks): workgroups and tiles per workgroup
     uint32_t *thr;     // [nq][2]: threshold t, rows at t that are still needed (0x7fffffff, 0: fewer than k rows, all are below)
     uint32_t *cnt;     // [nq][nblk][2]: rows below t, rows at t; after the scan their exclusive prefixes
     uint32_t *tot;     // [nq]: rows below t
-    uint64_t *keys;    // [nq][k]: distance << 32 | row, unordered
+    uint64_t *keys;    // [nq][k]: distance << 32 | position, unordered
 };
 void countsel_plan(int64_t n, int max_blocks, int *nblk, int *tpb);
 void launch_countsel_scan(const CountSel &a, hipStream_t s);
-void launch_countsel_finish(const CountSel &a, float *dist, int64_t *labels, hipStream_t s); // n == 0 allowed: all padding
+// n == 0 allowed: all padding.  posmap (nullable): the list of visible rows the search walked; the label of position i is
+// posmap[i], else i.  (An argument of the one launch that needs it and not a field of CountSel: the argument blocks of every
+// other kernel of the two selections, and with them their code, stay what they were.)
+void launch_countsel_finish(const CountSel &a, float *dist, int64_t *labels, hipStream_t s, const uint32_t *posmap = nullptr);
 
 // binary-quantised codes (kernels_bq.hip): W = (dims + 63) / 64 u64 words per row, bit i % 64 of word i / 64 is dimension i
 void launch_bq_encode(const float *X, int64_t n, int dims, uint64_t *codes, hipStream_t s);
@@ -594,10 +598,12 @@ void launch_bq_rerank(const uint64_t *codes, int W, int dims, int64_t ntotal, co
 // before the first.
 constexpr int BQ_MAX_BLOCKS = 2048; // workgroups that share the rows (each a contiguous range of whole 256-row tiles)
 struct BqSearch : CountSel {
-    const uint64_t *codes; // [n][W]
+    const uint64_t *codes; // [n][W]; under a list [ntotal][W]
     int W;
     const uint64_t *Q;     // [nq][W]
     uint32_t *hist;        // [nq][64*W + 1]
+    const uint32_t *rowmap; // nullable: position i is row rowmap[i] (ascending, n of them); last, so that the unmapped kernels'
+                            // arguments lie where they did
 };
 void launch_bq_hist(const BqSearch &a, hipStream_t s);
 void launch_bq_thresh(const BqSearch &a, hipStream_t s);
@@ -625,6 +631,7 @@ void launch_sq8_restride(const uint8_t *src, int sstride, uint8_t *dst, int dstr
 // norms[r] = sum of squares of the stride bytes of row r
 void launch_sq8_norms(const uint8_t *codes, int64_t n, int stride, int32_t *norms, hipStream_t s);
 // The distance pass: out[q][i] = S(row row0 + i, query q) for i in [0, n), q in [0, nq); Q u8[nq][stride], qn their norms.
+// Under a list (launch_sq8_dist's rowmap: n positions, row0 = 0) position i stands for row rowmap[i].
 struct Sq8Dist {
     const uint8_t *codes;  // [ntotal][stride]
     const int32_t *norms;  // [ntotal]
@@ -635,7 +642,9 @@ struct Sq8Dist {
     int nq;
     int32_t *out;          // [nq][n]
 };
-void launch_sq8_dist(const Sq8Dist &a, hipStream_t s);
+// rowmap (nullable): the ascending list of rows to walk.  An argument of its own and not a field of Sq8Dist: behind the struct
+// and tpb in the kernel's argument block it leaves the unmapped kernel's arguments, and its code, as they were
+void launch_sq8_dist(const Sq8Dist &a, hipStream_t s, const uint32_t *rowmap = nullptr);
 // gathered rows, one query u8[dims]: s = S as int32, euclid (nullable) = SQ8EuclideanDistance; rows outside [0, ntotal):
 // INT32_MAX / FLT_MAX
 void launch_sq8_rerank(const uint8_t *codes, int stride, int dims, int64_t ntotal, const uint8_t *qcode, const int64_t *rows, int64_t n,

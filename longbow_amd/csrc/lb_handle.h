@@ -6,9 +6,10 @@
 //   * a pooled buffer (Lease) that a stream-enqueuing body uses is declared OUTSIDE guard() and the stream is passed to it: an
 //     error drains the stream before the buffer goes back to the pool, where a concurrent call could lease it (bq.hip and
 //     sq8.hip; pq.hip's entry points other than its host encode and decode are older and lease inside their bodies);
-//   * searches and reads take `mu` shared, adds and reserve take it alone.
+//   * searches and reads take `mu` shared; adds, reserve and whatever changes the row filter take it alone.
 #pragma once
 #include "../../include/longbow_gpu.h"
+#include "lb_device.h"
 #include "lb_host.h"
 
 #include <algorithm>
@@ -227,6 +228,136 @@ template <class T, class Grow> int handle_reserve(T *p, int64_t n_total, Grow &&
     return guard(p, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         grow(p, n_total);
+        return LB_OK;
+    });
+}
+
+// ---- the row filter of a BQ or SQ8 handle -------------------------------------------------------------------------------
+// A byte per row (visible iff non-zero) and, built from it, the ascending list of the visible rows.  There is one form: with a
+// filter a search walks the n_visible positions of the list, whatever share of the rows it holds; the keys of the selection
+// carry positions, which order as rows do, and the finish maps them back.  The buffers are allocated by the first filter; while
+// `on` they hold room for `capacity` rows (the handle's *_grow keeps them in step through grow) and mask[0, n) are the stored
+// rows' bytes.  They are the handle's own, not pooled: they outlive every call.
+struct RowView {
+    const uint32_t *rowmap; // nullptr: rows [0, n) as they are
+    int64_t n;              // rows (positions) to search
+};
+
+struct RowFilter {
+    DevBuf<uint8_t> mask;     // [capacity]
+    DevBuf<uint32_t> rowmap;  // [capacity]; [0, n_visible) hold
+    DevBuf<uint32_t> scratch; // [compact_scratch_words(capacity)]: launch_compact_mask's
+    int64_t n_visible = 0;
+    bool on = false;
+
+    RowView view(int64_t n) const { return on ? RowView{rowmap.get(), n_visible} : RowView{nullptr, n}; }
+
+    // room for `cap` rows; an active filter's bytes of the n stored rows and its list are kept; all or nothing
+    void reserve(int64_t n, int64_t cap)
+    {
+        if (mask.count() >= (size_t)cap) return;
+        DevBuf<uint8_t> nm;
+        DevBuf<uint32_t> nr, ns;
+        nm.alloc((size_t)cap);
+        nr.alloc((size_t)cap);
+        ns.alloc((size_t)compact_scratch_words(cap));
+        if (on && n > 0) {
+            LB_HIP(hipMemcpy(nm.get(), mask.get(), (size_t)n, hipMemcpyDeviceToDevice));
+            LB_HIP(hipMemcpy(nr.get(), rowmap.get(), (size_t)n_visible * 4, hipMemcpyDeviceToDevice));
+        }
+        mask = std::move(nm);
+        rowmap = std::move(nr);
+        scratch = std::move(ns);
+    }
+    // the handle's *_grow: an active filter's buffers stay in step with the codes'
+    void grow(int64_t n, int64_t cap) { if (on) reserve(n, cap); }
+    // the list and n_visible from mask[0, n); drains s
+    void rebuild(int64_t n, hipStream_t s)
+    {
+        uint32_t total = 0;
+        if (n > 0) {
+            launch_compact_mask(mask.get(), n, rowmap.get(), scratch.get(), s);
+            LB_LAUNCH_CHECK();
+            LB_HIP(hipMemcpyAsync(&total, scratch.get() + (compact_scratch_words(n) - 1), 4, hipMemcpyDeviceToHost, s));
+            LB_HIP(hipStreamSynchronize(s));
+        }
+        n_visible = (int64_t)total;
+    }
+    // rows [n_old, n_new) are stored (room for them reserved) and about to be committed: they are visible
+    void on_append(int64_t n_old, int64_t n_new, hipStream_t s)
+    {
+        if (!on) return;
+        LB_HIP(hipMemsetAsync(mask.get() + n_old, 1, (size_t)(n_new - n_old), s));
+        rebuild(n_new, s);
+    }
+};
+
+struct FilteredHandle : CodeHandle {
+    RowFilter filter;
+};
+
+inline int64_t filter_nvisible(const FilteredHandle *h)
+{
+    if (!h) return 0;
+    std::shared_lock<std::shared_mutex> g(const_cast<FilteredHandle *>(h)->mu);
+    return h->filter.view(h->n).n;
+}
+
+// lb_gpu_*_set_filter: n bytes of the host, or nullptr to clear
+inline int filter_set(FilteredHandle *h, const uint8_t *mask, int64_t n)
+{
+    if (!h) return LB_ERR_INVALID_ARG;
+    std::unique_lock<std::shared_mutex> g(h->mu);
+    RowFilter &f = h->filter;
+    if (!mask) { f.on = false; return LB_OK; }
+    if (n != h->n) {
+        h->set_error("filter mask has %lld bytes, the handle holds %lld rows", (long long)n, (long long)h->n);
+        return LB_ERR_INVALID_ARG;
+    }
+    return guard(h, h->stream, [&]() -> int {
+        LB_HIP(hipSetDevice(h->device));
+        f.reserve(h->n, h->capacity);
+        f.on = false; // a failure from here on leaves the handle without a filter, not with half of one
+        if (n > 0) LB_HIP(hipMemcpy(f.mask.get(), mask, (size_t)n, hipMemcpyHostToDevice));
+        f.rebuild(n, h->stream);
+        f.on = true;
+        return LB_OK;
+    });
+}
+
+// lb_gpu_*_filter_int64 / _float32: the predicate evaluated on the device into the mask (launch_match_*)
+template <class T>
+int filter_column(FilteredHandle *h, const T *column, int64_t n, T value, int op, const uint8_t *validity, int64_t voff, int combine)
+{
+    if (!h || op < 0 || op > 5 || voff < 0) return LB_ERR_INVALID_ARG;
+    std::unique_lock<std::shared_mutex> g(h->mu);
+    RowFilter &f = h->filter;
+    if (n != h->n || (n > 0 && !column)) {
+        h->set_error("filter column has %lld values, the handle holds %lld rows", (long long)n, (long long)h->n);
+        return LB_ERR_INVALID_ARG;
+    }
+    Lease dcol, dval;
+    return guard(h, h->stream, [&]() -> int {
+        LB_HIP(hipSetDevice(h->device));
+        hipStream_t s = h->stream;
+        const int comb = combine && f.on ? 1 : 0; // AND into "no filter" replaces
+        f.reserve(h->n, h->capacity);
+        f.on = false; // as filter_set
+        if (n > 0) {
+            dcol.reset(h->device, (size_t)n * sizeof(T));
+            LB_HIP(hipMemcpyAsync(dcol.p, column, (size_t)n * sizeof(T), hipMemcpyHostToDevice, s));
+            const uint8_t *d_val = nullptr;
+            if (validity) {
+                const size_t vb = (size_t)((voff + n + 7) / 8);
+                dval.reset(h->device, vb);
+                LB_HIP(hipMemcpyAsync(dval.p, validity, vb, hipMemcpyHostToDevice, s));
+                d_val = dval.as<uint8_t>();
+            }
+            if constexpr (sizeof(T) == 8) launch_match_int64(dcol.as<int64_t>(), n, (int64_t)value, op, d_val, voff, f.mask.get(), comb, s);
+            else launch_match_float32(dcol.as<float>(), n, (float)value, op, d_val, voff, f.mask.get(), comb, s);
+        }
+        f.rebuild(n, s);
+        f.on = true;
         return LB_OK;
     });
 }

@@ -10,7 +10,7 @@
 
 using namespace lb;
 
-struct lb_gpu_sq8 : CodeHandle { // searches, reads and the codec share mu; adds, reserve and the bounds take it alone
+struct lb_gpu_sq8 : FilteredHandle { // searches, reads and the codec share mu; adds, reserve, the bounds and the filter calls take it alone
     int stride = 0;
     DevBuf<uint8_t> d_codes;  // [capacity][stride], pad bytes zero
     DevBuf<int32_t> d_norms;  // [capacity]: sum of squares of each row, exact
@@ -46,6 +46,7 @@ void sq8_grow(lb_gpu_sq8 *p, int64_t need)
         LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->stride, hipMemcpyDeviceToDevice));
         LB_HIP(hipMemcpy(nn.get(), p->d_norms.get(), (size_t)p->n * 4, hipMemcpyDeviceToDevice));
     }
+    p->filter.grow(p->n, cap);
     p->d_codes = std::move(nc);
     p->d_norms = std::move(nn);
     p->capacity = cap;
@@ -134,14 +135,16 @@ void codes_in(lb_gpu_sq8 *p, const uint8_t *codes, bool on_device, int64_t n, ui
     launch_sq8_restride(src, p->dims, d_dst, p->stride, p->dims, n, s);
 }
 
-// Exact k-NN of nq device-resident query codes u8[nq][stride]; the caller holds the reader lock, has made the device current
+// Exact k-NN of nq device-resident query codes u8[nq][stride] over the visible rows (S then holds a.n = n_visible positions per
+// query, so a selective filter takes more queries per batch); the caller holds the reader lock, has made the device current
 // and has checked the arguments.  ctx is polled before every launch.  The scratch is leased into the caller's `sc`, declared
 // outside the caller's guard as lb_handle.h asks of every pooled buffer.
 int sq8_search_codes_dev(lb_gpu_sq8 *p, int64_t nq, const uint8_t *d_Q, int k, float *d_dist, int64_t *d_labels, hipStream_t s,
                          const lb_cancel *ctx, Lease &sc)
 {
+    const RowView v = p->filter.view(p->n);
     Sq8Select a{};
-    a.n = p->n;
+    a.n = v.n;
     a.k = k;
     countsel_plan(a.n, SQ8_MAX_BLOCKS, &a.nblk, &a.tpb);
     // the largest batch whose distances fit the scratch, at least one query
@@ -171,7 +174,7 @@ int sq8_search_codes_dev(lb_gpu_sq8 *p, int64_t nq, const uint8_t *d_Q, int k, f
             LB_HIP(hipMemsetAsync(a.hist, 0, (size_t)a.nq * SQ8_RADIX_BINS * 4, s)); // (every digit launch leaves it zero again)
             launch_sq8_norms(Q, a.nq, p->stride, d_qn, s);
             if (!go()) break;
-            launch_sq8_dist(Sq8Dist{p->d_codes.get(), p->d_norms.get(), p->stride, 0, a.n, Q, d_qn, a.nq, d_S}, s);
+            launch_sq8_dist(Sq8Dist{p->d_codes.get(), p->d_norms.get(), p->stride, 0, a.n, Q, d_qn, a.nq, d_S}, s, v.rowmap);
             for (int pass = 0; pass < 3 && !cancelled; pass++) {
                 if (!go()) break;
                 launch_sq8_hist(a, pass, s);
@@ -186,7 +189,7 @@ int sq8_search_codes_dev(lb_gpu_sq8 *p, int64_t nq, const uint8_t *d_Q, int k, f
             launch_sq8_emit(a, s);
         }
         if (!go()) break;
-        launch_countsel_finish(a, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
+        launch_countsel_finish(a, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s, v.rowmap);
     }
     LB_LAUNCH_CHECK();
     LB_HIP(hipStreamSynchronize(s));
@@ -236,6 +239,7 @@ int add_codes_impl(lb_gpu_sq8 *p, int64_t n, const uint8_t *codes, bool on_devic
         launch_sq8_norms(dst, n, p->stride, p->d_norms.get() + p->n, p->stream);
         LB_LAUNCH_CHECK();
         LB_HIP(hipStreamSynchronize(p->stream));
+        p->filter.on_append(p->n, p->n + n, p->stream);
         p->n += n;
         return LB_OK;
     });
@@ -268,6 +272,7 @@ int add_vectors_impl(lb_gpu_sq8 *p, int64_t n, const float *vectors, bool on_dev
             LB_LAUNCH_CHECK();
             LB_HIP(hipStreamSynchronize(s));
         }
+        p->filter.on_append(p->n, p->n + n, s);
         p->n += n;
         return LB_OK;
     });
@@ -288,6 +293,20 @@ int lb_gpu_sq8_dims(const lb_gpu_sq8 *p) { return p ? p->dims : 0; }
 int lb_gpu_sq8_trained(const lb_gpu_sq8 *p) { return p && p->trained.load() ? 1 : 0; }
 int64_t lb_gpu_sq8_ntotal(const lb_gpu_sq8 *p) { return handle_ntotal(p); }
 int lb_gpu_sq8_reserve(lb_gpu_sq8 *p, int64_t n_total) { return handle_reserve(p, n_total, sq8_grow); }
+
+// ---- the row filter (lb_handle.h) ---------------------------------------------------------------------------------------
+int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p) { return filter_nvisible(p); }
+int lb_gpu_sq8_set_filter(lb_gpu_sq8 *p, const uint8_t *mask, int64_t n) { return filter_set(p, mask, n); }
+int lb_gpu_sq8_filter_int64(lb_gpu_sq8 *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                            int64_t validity_offset, int combine)
+{
+    return filter_column<int64_t>(p, column, n, value, op, validity, validity_offset, combine);
+}
+int lb_gpu_sq8_filter_float32(lb_gpu_sq8 *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine)
+{
+    return filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
+}
 
 // ---- bounds -----------------------------------------------------------------------------------------------------------
 int lb_gpu_sq8_set_bounds(lb_gpu_sq8 *p, const float *min, const float *max)

@@ -11,13 +11,15 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
+from ._rowfilter import RowFilterMixin
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 INT32_MAX = 0x7FFFFFFF
 
 
-class SQ8Encoder:
+class SQ8Encoder(RowFilterMixin):
     """store.SQ8Encoder on the GPU (untrained until set_bounds / train)."""
+    _prefix = "lb_gpu_sq8"
 
     def __init__(self, dims, device=0, lib=None):
         if dims <= 0:
@@ -248,7 +250,9 @@ def train(vectors, device=0, lib=None):
 def search_rerank(sq8, index, queries, k, oversample):
     """The two-stage use the codes exist for: a shortlist of k * oversample rows per query by the integer distance, then the
     exact distances of those rows on `index` (a float32 gpu.Index filled in the same row order; lb_gpu_index_rerank), sorted
-    by (distance, position) and cut to k.  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX."""
+    by (distance, position) and cut to k.  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX.
+    Under a row filter on the encoder (set_filter / filter_column) the shortlist holds visible rows only, and the re-rank
+    addresses rows directly, so the result is the filtered one: nothing here changes, and `index` needs no filter."""
     v, _ = sq8._vectors(queries)
     short, _ = sq8.search(v, k * oversample)
     labels = np.full((v.shape[0], k), -1, np.int64)

@@ -1,0 +1,57 @@
+"""lb_gpu_bq_* / lb_gpu_sq8_* row filters: the calls exist with their prototypes, and without a handle they answer before a
+device is touched (LB_ERR_INVALID_ARG; nvisible 0) and write nothing, in the order tests/test_bq_abi.py documents for the other
+calls of these handles.  All of this runs on a box without a GPU; the checks behind a live handle (a mask of the wrong length)
+are in tests/test_gpu_code_filters.py."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+INVALID = 1
+PREFIXES = ("lb_gpu_bq", "lb_gpu_sq8")
+
+
+@pytest.fixture(scope="module")
+def lib():
+    from longbow_amd import _lib
+    return _lib.load()
+
+
+@pytest.mark.parametrize("prefix", PREFIXES)
+def test_prototypes_mirror_the_f32_index(lib, prefix):
+    from longbow_amd import _lib
+    sig = {name: (res, args) for name, res, args in _lib.SIGNATURES}
+    for call in ("set_filter", "filter_int64", "filter_float32"):
+        assert sig[f"{prefix}_{call}"] == sig[f"lb_gpu_index_{call}"], call
+        fn = getattr(lib, f"{prefix}_{call}")
+        assert fn.restype is C.c_int and list(fn.argtypes) == sig[f"{prefix}_{call}"][1]
+    nv = getattr(lib, f"{prefix}_nvisible")
+    assert nv.restype is C.c_int64 and list(nv.argtypes) == [C.c_void_p]
+
+
+@pytest.mark.parametrize("prefix", PREFIXES)
+def test_null_handle_is_refused_and_nothing_is_written(lib, prefix):
+    n = 5
+    mask = np.full(n, 0xAB, np.uint8)
+    col64 = np.full(n, 77, np.int64)
+    col32 = np.full(n, 9.0, np.float32)
+    valid = np.full(2, 0x5A, np.uint8)
+    set_filter, f64, f32 = (getattr(lib, f"{prefix}_{c}") for c in ("set_filter", "filter_int64", "filter_float32"))
+    for nn in (n, 0, -1):
+        assert set_filter(None, mask.ctypes.data, nn) == INVALID
+        assert set_filter(None, None, nn) == INVALID
+        for op in (0, 5, -1, 6):
+            for voff in (0, 3, -1):
+                for combine in (0, 1):
+                    assert f64(None, col64.ctypes.data, nn, 5, op, valid.ctypes.data, voff, combine) == INVALID
+                    assert f32(None, col32.ctypes.data, nn, 0.25, op, None, voff, combine) == INVALID
+    assert getattr(lib, f"{prefix}_nvisible")(None) == 0
+    assert (mask == 0xAB).all() and (col64 == 77).all() and (col32 == 9.0).all() and (valid == 0x5A).all()
+
+
+def test_python_front_ends_offer_the_three_calls():
+    from longbow_amd import bq, sq8
+    for cls in (bq.BQEncoder, sq8.SQ8Encoder):
+        for name in ("set_filter", "filter_column", "nvisible"):
+            assert callable(getattr(cls, name)), (cls.__name__, name)
+    assert bq.BQEncoder._prefix == "lb_gpu_bq" and sq8.SQ8Encoder._prefix == "lb_gpu_sq8"

@@ -1,0 +1,100 @@
+"""Filtered searches on the BQ and SQ8 indexes: search time against the share of visible rows, one JSON line.
+
+    python tools/code_filter_bench.py --index bq|sq8 [--rows 1000000] [--dim 768] [--k 100] [--nq 1,64,1024]
+                                      [--visible-pct 100,50,10] [--runs 3] [--reps 10]
+
+Rows are drawn on the device (uniform in [-0.5, 0.5)) and added as vectors.  100 % means no filter (the unmapped kernels);
+every other share sets a random byte mask with that share of non-zero bytes, so the search walks the list of visible rows.
+Per (share, nq): `runs` runs, each the p50 of `reps` searches through the device-pointer entry point (the call returns when the
+results are on the device); the figure is the median of the runs, and the runs themselves are kept (their spread is the margin
+a comparison between two builds has to clear).  The runs of the shares alternate.  With --visible-pct 100 alone no filter call is
+made, so a copy of this file under tools/ of an older checkout times that checkout's unfiltered searches the same way.
+The shader clock is read before and after.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from longbow_amd import bq, gpu, sq8  # noqa: E402
+
+
+def p50(fn, reps):
+    fn()
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def clock_mhz():
+    try:
+        return float(gpu._lib.load().lb_gpu_shader_clock_mhz(0, 2000))
+    except Exception:
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--index", choices=("bq", "sq8"), required=True)
+    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--nq", default="1,64,1024")
+    ap.add_argument("--visible-pct", default="100,50,10")
+    ap.add_argument("--runs", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=10)
+    a = ap.parse_args()
+    nqs = [int(x) for x in a.nq.split(",")]
+    pcts = [int(x) for x in a.visible_pct.split(",")]
+    torch.manual_seed(0)
+    rng = np.random.default_rng(0)
+    enc = bq.BQEncoder(a.dim) if a.index == "bq" else sq8.SQ8Encoder(a.dim)
+    enc.reserve(a.rows)
+    out = {"index": a.index, "rows": a.rows, "dim": a.dim, "k": a.k, "runs": a.runs, "reps": a.reps,
+           "shader_clock_mhz_before": clock_mhz()}
+    piece = min(a.rows, 1_000_000)
+    for r0 in range(0, a.rows, piece):
+        cnt = min(piece, a.rows - r0)
+        V = torch.rand((cnt, a.dim), device="cuda") - 0.5
+        torch.cuda.synchronize()
+        if r0 == 0 and a.index == "sq8":
+            enc.train_device(cnt, V.data_ptr())
+        enc.add_vectors_device(cnt, V.data_ptr())
+        del V
+    masks = {p: (rng.random(a.rows) < p / 100.0).astype(np.uint8) for p in pcts if p != 100}
+    nqmax = max(nqs)
+    Q = torch.rand((nqmax, a.dim), device="cuda") - 0.5
+    D = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
+    L = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    runs = {p: {nq: [] for nq in nqs} for p in pcts}
+    visible = {}
+    for _ in range(a.runs):
+        for p in pcts:
+            if p == 100:
+                if masks:
+                    enc.set_filter(None)
+                visible[p] = a.rows
+            else:
+                enc.set_filter(masks[p])
+                visible[p] = enc.nvisible()
+            for nq in nqs:
+                runs[p][nq].append(p50(lambda: enc.search_device(nq, Q.data_ptr(), a.k, D.data_ptr(), L.data_ptr()), a.reps))
+    out["search"] = {f"visible_{p}": {"visible_rows": visible[p],
+                                      **{f"nq_{nq}": {"ms": float(np.median(runs[p][nq])), "runs_ms": runs[p][nq]} for nq in nqs}}
+                     for p in pcts}
+    out["shader_clock_mhz_after"] = clock_mhz()
+    print(json.dumps(out))
+    enc.Close()
+
+
+if __name__ == "__main__":
+    main()
