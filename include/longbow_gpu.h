@@ -364,6 +364,28 @@ int lb_gpu_pq_set_prefilter(lb_gpu_pq *p, int enable);
  * (including quads and pairs whose M has no shared form), out[4] redone on the bootstrap schedule, out[5] redone
  * on the schedule that cannot overflow.  Concurrent searches overwrite each other's record. */
 int lb_gpu_pq_last_search_stats(const lb_gpu_pq *p, int64_t out[6]);
+/* The row filter of a PQ handle, with the prototypes and the semantics of lb_gpu_bq_set_filter / _filter_int64 / _filter_float32 /
+ * _nvisible (and of lb_gpu_index_set_filter / _filter_*): a row is visible iff its mask byte is non-zero; a NULL mask clears the
+ * filter; n != ntotal is LB_ERR_INVALID_ARG with a last_error text and leaves the filter as it was.
+ *   search    with a filter every lb_gpu_pq_search* call (_device, _ctx and combined concurrent host searches too) returns the
+ *             exact ADC k-NN among the visible rows: the distances of the unfiltered search, ascending by (distance, row),
+ *             labels are corpus rows.  Fewer than k visible rows: they come first, then label -1 / dist FLT_MAX; no visible
+ *             row: all padding.  lb_gpu_pq_last_search_stats reports as without a filter; there is no four-query pass over a
+ *             list, so out[1] == 0.
+ *   adds      rows added under a filter are visible.
+ *   ignored   rerank*, adc_distance_batch, get_codes, encode and decode address rows directly and ignore the filter.
+ *   cost      any filter, an all-visible one too, searches the ascending list of visible rows, so the cost follows their number.
+ *   limits    the list holds fewer than 2^31 rows: a filter call on a handle with more, and an add that would take a filtered
+ *             handle there, answer LB_ERR_UNSUPPORTED with a last_error text before the device is touched.  A handle without
+ *             a filter keeps its 2^32 - 1 rows.
+ *   locking   the filter calls are exclusive against everything else on the handle; searches and reads share it. */
+int lb_gpu_pq_set_filter(lb_gpu_pq *p, const uint8_t *mask, int64_t n);
+int lb_gpu_pq_filter_int64(lb_gpu_pq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                           int64_t validity_offset, int combine);
+int lb_gpu_pq_filter_float32(lb_gpu_pq *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                             int64_t validity_offset, int combine);
+/* rows a search sees: ntotal without a filter; 0 for a NULL handle */
+int64_t lb_gpu_pq_nvisible(const lb_gpu_pq *p);
 
 /* instrumentation (bench.py): HIP-event times of the most recent profiled search on this handle, recorded on the
  * search stream: ms[0] = the pass over the codes of the LAST query (prefilter kernel, or the exact kernel when

@@ -125,6 +125,10 @@ SIGNATURES = [
     ("lb_gpu_pq_adc_distance_batch", _i, [_vp, _vp, _i64, _i64, _vp]),
     ("lb_gpu_pq_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_pq_search_device", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_pq_set_filter", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_pq_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
+    ("lb_gpu_pq_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
+    ("lb_gpu_pq_nvisible", _i64, [_vp]),
     ("lb_gpu_pq_train", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp]),
     ("lb_gpu_pq_train_device", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("lb_gpu_pq_blob_bytes", _sz, [_i, _i, _i]),

@@ -1,13 +1,13 @@
-"""The row filter of the code indexes, shared by bq.py and sq8.py."""
+"""The row filter of the code indexes, shared by bq.py, sq8.py and pq.py."""
 import numpy as np
 
 
 class RowFilterMixin:
-    """The row filter of a code index (bq.BQEncoder, sq8.SQ8Encoder): what gpu.Index offers on the f32 index, on the
+    """The row filter of a code index (bq.BQEncoder, sq8.SQ8Encoder, pq.PQEncoder): what gpu.Index offers on the f32 index, on the
     <_prefix>_set_filter / _filter_int64 / _filter_float32 / _nvisible entry points.  With a filter every search returns the
     exact k-NN among the visible rows (labels stay corpus rows); rows added later are visible; the calls that address rows
     directly ignore it."""
-    _prefix = None  # "lb_gpu_bq" / "lb_gpu_sq8"
+    _prefix = None  # "lb_gpu_bq" / "lb_gpu_sq8" / "lb_gpu_pq"
 
     def set_filter(self, mask):
         """mask: ntotal bytes, a row is visible iff its byte is non-zero; None clears the filter"""

@@ -565,6 +565,25 @@ void launch_adc_exact_candidates(const float *table, int M, const uint8_t *codes
 void launch_adc_rerank(const float *table, int M, const uint8_t *codes, int64_t n, const int64_t *rows, int64_t nrows,
                        float *out_dist, float *out_score, hipStream_t s);
 
+// The ADC search under a row filter (kernels_pq_list.hip): the forms of the sample, the exact scan and the prefilter that walk
+// POSITIONS of the ascending list of visible rows, rowmap[0, n_vis), and gather each position's code row.  The arithmetic is
+// that of the kernels above and the entries / candidates carry corpus rows, so launch_select, launch_adc_exact_candidates and
+// the emit follow unchanged.  A zero-length list launches nothing.
+constexpr int ADC_LIST_WAVES = 16; // waves per workgroup: a workgroup walks runs of ADC_LIST_WAVES * 64 positions
+// exact ADC entries of `count` evenly spaced positions of the list -> out[count] (as launch_adc_sample)
+void launch_adc_list_sample(const float *table, int M, const uint8_t *codes, const uint32_t *rowmap, int64_t n_vis,
+                            uint32_t count, uint64_t *out, hipStream_t s);
+// positions [pos_begin, pos_end) into cs slot `slot`: boot = every position's entry at lists[slot][pos - pos_begin],
+// otherwise the entries below the slot's threshold are appended (as launch_adc_scan)
+void launch_adc_list_scan(const float *table, int M, const uint8_t *codes, const uint32_t *rowmap, int64_t pos_begin,
+                          int64_t pos_end, int slot, CandState cs, bool boot, hipStream_t s);
+// as launch_adc_prefilter / launch_adc_prefilter2 over the list (false: no such form, as there)
+bool launch_adc_list_prefilter(const uint8_t *qtab, const int *params, int M, const uint8_t *codes, const uint32_t *rowmap,
+                               int64_t n_vis, uint32_t *cand, uint32_t cand_cap, uint32_t *cand_cnt, hipStream_t s);
+bool launch_adc_list_prefilter2(const uint8_t *qtab, const int *params, uint32_t *cand, uint32_t *cand_cnt, const uint8_t *qtab2,
+                                const int *params2, uint32_t *cand2, uint32_t *cand_cnt2, int M, const uint8_t *codes,
+                                const uint32_t *rowmap, int64_t n_vis, uint32_t cand_cap, hipStream_t s);
+
 // The tail of a k-NN by counting (kernels_countsel.hip; the method is stated in lb_countsel.h): what the selections of
 // kernels_bq.hip and kernels_sq8.hip share once a per-query threshold is known.  Workgroup b of nblk owns the rows of tiles
 // [b * tpb, (b + 1) * tpb), 256 rows a tile.  Under a row filter the rows of a search are the positions of the ascending list of

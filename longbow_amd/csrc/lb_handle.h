@@ -120,7 +120,8 @@ static_assert(grow_capacity(((int64_t)1 << 27) + 4, ((int64_t)1 << 27) + 5, 8) =
 static_assert(grow_capacity(((int64_t)1 << 27) + 4, (int64_t)1 << 29, 8) == (int64_t)1 << 29, "beyond 1 GiB held: the request");
 
 // ---- refusals ---------------------------------------------------------------------------------------------------------
-// BQ and SQ8: a selection key holds the row in 32 bits and the counts are u32 (PQ has its own limit)
+// BQ and SQ8: a selection key holds the row in 32 bits and the counts are u32.  PQ holds up to 2^32 - 1 rows without a row
+// filter and this many with one (the filter's list and the counts of its compaction are u32)
 constexpr int64_t kMaxRows = 0x7fffffffll;
 
 inline int rows_fit(CodeHandle *h, int64_t have, int64_t more)
@@ -232,10 +233,11 @@ template <class T, class Grow> int handle_reserve(T *p, int64_t n_total, Grow &&
     });
 }
 
-// ---- the row filter of a BQ or SQ8 handle -------------------------------------------------------------------------------
+// ---- the row filter of a code handle ------------------------------------------------------------------------------------
 // A byte per row (visible iff non-zero) and, built from it, the ascending list of the visible rows.  There is one form: with a
 // filter a search walks the n_visible positions of the list, whatever share of the rows it holds; the keys of the selection
-// carry positions, which order as rows do, and the finish maps them back.  The buffers are allocated by the first filter; while
+// carry positions, which order as rows do, and the finish maps them back (BQ, SQ8; the PQ handle's list kernels put the rows
+// themselves into their entries).  The buffers are allocated by the first filter; while
 // `on` they hold room for `capacity` rows (the handle's *_grow keeps them in step through grow) and mask[0, n) are the stored
 // rows' bytes.  They are the handle's own, not pooled: they outlive every call.
 struct RowView {
@@ -303,6 +305,15 @@ inline int64_t filter_nvisible(const FilteredHandle *h)
     return h->filter.view(h->n).n;
 }
 
+// A row filter covers at most kMaxRows rows: what a filter call answers on a larger handle, and an add that would take a
+// filtered handle beyond it, before the device is touched (only the PQ handle can hold that many)
+inline int filter_fits(CodeHandle *h, int64_t rows)
+{
+    if (rows <= kMaxRows) return LB_OK;
+    h->set_error("a row filter covers fewer than 2^31 rows, the handle would hold %lld", (long long)rows);
+    return LB_ERR_UNSUPPORTED;
+}
+
 // lb_gpu_*_set_filter: n bytes of the host, or nullptr to clear
 inline int filter_set(FilteredHandle *h, const uint8_t *mask, int64_t n)
 {
@@ -314,6 +325,7 @@ inline int filter_set(FilteredHandle *h, const uint8_t *mask, int64_t n)
         h->set_error("filter mask has %lld bytes, the handle holds %lld rows", (long long)n, (long long)h->n);
         return LB_ERR_INVALID_ARG;
     }
+    if (const int st = filter_fits(h, h->n)) return st;
     return guard(h, h->stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
         f.reserve(h->n, h->capacity);
@@ -336,6 +348,7 @@ int filter_column(FilteredHandle *h, const T *column, int64_t n, T value, int op
         h->set_error("filter column has %lld values, the handle holds %lld rows", (long long)n, (long long)h->n);
         return LB_ERR_INVALID_ARG;
     }
+    if (const int st = filter_fits(h, h->n)) return st;
     Lease dcol, dval;
     return guard(h, h->stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));

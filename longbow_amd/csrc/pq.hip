@@ -25,7 +25,7 @@ uint32_t rd_u32le(const uint8_t *p)
 struct PqScratch;
 } // namespace
 
-struct lb_gpu_pq : CodeHandle {
+struct lb_gpu_pq : FilteredHandle { // searches and reads share mu; adds, reserve and the filter calls take it alone
     int M = 0, K = 0, sub = 0;
     DevBuf<float> d_codebooks;
     DevBuf<uint8_t> d_codes;
@@ -54,6 +54,7 @@ void pq_grow(lb_gpu_pq *p, int64_t need)
     DevBuf<uint8_t> nc;
     nc.alloc((size_t)cap * p->M);
     if (p->n > 0) LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice));
+    p->filter.grow(p->n, cap);
     p->d_codes = std::move(nc);
     p->capacity = cap;
 }
@@ -176,11 +177,14 @@ static int add_codes_impl(lb_gpu_pq *p, int64_t n, const uint8_t *codes, bool on
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
     if (p->n + n > (int64_t)0xffffffffll) { p->set_error("more than 2^32 codes per device"); return LB_ERR_UNSUPPORTED; }
+    if (p->filter.on)
+        if (const int st = filter_fits(p, p->n + n)) return st;
     return guard(p, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         pq_grow(p, p->n + n);
         LB_HIP(hipMemcpy(p->d_codes.get() + (size_t)p->n * p->M, codes, (size_t)n * p->M,
                           on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice));
+        p->filter.on_append(p->n, p->n + n, p->stream);
         p->n += n;
         return LB_OK;
     });
@@ -188,6 +192,20 @@ static int add_codes_impl(lb_gpu_pq *p, int64_t n, const uint8_t *codes, bool on
 
 int lb_gpu_pq_add_codes(lb_gpu_pq *p, int64_t n, const uint8_t *codes) { return add_codes_impl(p, n, codes, false); }
 int lb_gpu_pq_add_codes_device(lb_gpu_pq *p, int64_t n, const uint8_t *d_codes) { return add_codes_impl(p, n, d_codes, true); }
+
+// ---- the row filter (lb_handle.h) ---------------------------------------------------------------------------------------
+int64_t lb_gpu_pq_nvisible(const lb_gpu_pq *p) { return filter_nvisible(p); }
+int lb_gpu_pq_set_filter(lb_gpu_pq *p, const uint8_t *mask, int64_t n) { return filter_set(p, mask, n); }
+int lb_gpu_pq_filter_int64(lb_gpu_pq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                           int64_t validity_offset, int combine)
+{
+    return filter_column<int64_t>(p, column, n, value, op, validity, validity_offset, combine);
+}
+int lb_gpu_pq_filter_float32(lb_gpu_pq *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                             int64_t validity_offset, int combine)
+{
+    return filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
+}
 
 int lb_gpu_pq_get_codes(lb_gpu_pq *p, int64_t row0, int64_t n, uint8_t *codes)
 {
@@ -233,12 +251,15 @@ int lb_gpu_pq_add_vectors_device(lb_gpu_pq *p, int64_t n, const float *d_vectors
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
     if (p->n + n > (int64_t)0xffffffffll) { p->set_error("more than 2^32 codes per device"); return LB_ERR_UNSUPPORTED; }
+    if (p->filter.on)
+        if (const int st = filter_fits(p, p->n + n)) return st;
     return guard(p, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         pq_grow(p, p->n + n);
         launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_vectors, n, p->d_codes.get() + (size_t)p->n * p->M, p->stream);
         LB_LAUNCH_CHECK();
         LB_HIP(hipStreamSynchronize(p->stream));
+        p->filter.on_append(p->n, p->n + n, p->stream);
         p->n += n;
         return LB_OK;
     });
@@ -382,6 +403,10 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = stream ? (hipStream_t)stream : p->stream;
         const int nqi = (int)nq;
+        // Under a row filter the search walks the v.n positions of the ascending list of visible rows (kernels_pq_list.hip)
+        // instead of the p->n rows: the plan, the chunk schedule and the selects count positions, the entries carry rows.
+        const RowView v = p->filter.view(p->n);
+        const uint8_t *codes = p->d_codes.get();
         // Sampled admission threshold (same reasoning as index_search.hip: sample_plan): one row in `stride` is scored
         // exactly, the m-th best sample entry becomes tau, and the codes are walked once.  About m*stride rows
         // pass (4096 at stride 512); fewer than k or more than the list holds is detected by the select and
@@ -391,13 +416,13 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         uint32_t samp_count = 0;
         int samp_m = 0;
         uint32_t cap = std::max<uint32_t>(8192u, 4u * next_pow2_host((uint32_t)k));
-        if (p->n >= 65536 && p->n < ((int64_t)1 << 32)) {
+        if (v.n >= 65536 && v.n < ((int64_t)1 << 32)) {
             const uint32_t cap_s = std::max<uint32_t>(16384u, cap);
-            const int64_t stride = p->n >= ((int64_t)8192 * 512) ? 512 : 256;
-            const int64_t cnt = std::max<int64_t>(8192, (p->n + stride - 1) / stride);
-            const double lambda = (double)k * (double)cnt / (double)p->n;
+            const int64_t stride = v.n >= ((int64_t)8192 * 512) ? 512 : 256;
+            const int64_t cnt = std::max<int64_t>(8192, (v.n + stride - 1) / stride);
+            const double lambda = (double)k * (double)cnt / (double)v.n;
             const int m = std::max(8, (int)std::ceil(lambda + 5.0 * std::sqrt(lambda) + 4.0));
-            const double loose = (double)m * ((double)p->n / (double)cnt) * (1.0 + 5.0 / std::sqrt((double)m));
+            const double loose = (double)m * ((double)v.n / (double)cnt) * (1.0 + 5.0 / std::sqrt((double)m));
             if (m <= 32 && loose <= (double)(cap_s - (uint32_t)k) && cnt <= (int64_t)8192 * (8192 / m)) {
                 samp_count = (uint32_t)cnt;
                 samp_m = m;
@@ -419,10 +444,27 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                                sc.cs.flags, prefilter ? sc.d_cand_cnt.get() : nullptr); // (also clears the slots' status words)
         // the search's last select writes the k results AND the slot's status word into pinned host memory (no D2H copy)
         const EmitArgs em{k, nullptr, d_dist, d_labels, sc.h_flags.get()};
+        const uint32_t k_have = (uint32_t)std::min<int64_t>(k, v.n);
+        // the passes over the rows or, under a filter, over the list
+        auto exact_scan = [&](const float *tab, int64_t begin, int64_t end, int q, bool boot) {
+            if (v.rowmap) launch_adc_list_scan(tab, p->M, codes, v.rowmap, begin, end, q, sc.cs, boot, s);
+            else launch_adc_scan(tab, p->M, codes, begin, end, q, nullptr, sc.cs, boot, nullptr, 0, s);
+        };
+        auto prefilter_one = [&](const uint8_t *qtab, const int *prm, uint32_t *cand, uint32_t *ccnt) {
+            if (v.rowmap) launch_adc_list_prefilter(qtab, prm, p->M, codes, v.rowmap, v.n, cand, kCandCap, ccnt, s);
+            else launch_adc_prefilter(qtab, prm, p->M, codes, v.n, cand, kCandCap, ccnt, s);
+        };
+        auto prefilter_two = [&](const uint8_t *qtab0, const int *prm0, uint32_t *cand0, uint32_t *ccnt0, const uint8_t *qtab1,
+                                 const int *prm1, uint32_t *cand1, uint32_t *ccnt1) -> bool {
+            if (v.rowmap)
+                return launch_adc_list_prefilter2(qtab0, prm0, cand0, ccnt0, qtab1, prm1, cand1, ccnt1, p->M, codes, v.rowmap, v.n, kCandCap, s);
+            return launch_adc_prefilter2(qtab0, prm0, cand0, ccnt0, qtab1, prm1, cand1, ccnt1, p->M, codes, v.n, kCandCap, s);
+        };
         // sampled threshold of one query: sample -> m-th best -> tau (cnt = 0); false = no sampled pass for this search
         auto threshold = [&](int q) -> bool {
             const float *tab = sc.d_tables.get() + (size_t)q * p->M * 256;
-            launch_adc_sample(tab, p->M, p->d_codes.get(), p->n, samp_count, sc.d_samp.get(), s);
+            if (v.rowmap) launch_adc_list_sample(tab, p->M, codes, v.rowmap, v.n, samp_count, sc.d_samp.get(), s);
+            else launch_adc_sample(tab, p->M, codes, v.n, samp_count, sc.d_samp.get(), s);
             const uint32_t groups = launch_sample_topm(sc.d_samp.get(), samp_count, samp_m, sc.cs, q, s);
             if (!groups) return false;
             launch_sample_tau(sc.cs, sc.d_slots.get() + q, 1, groups * (uint32_t)samp_m, samp_m, false, s); // sets tau, cnt = 0
@@ -442,34 +484,34 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                         uint8_t *qtab = sc.d_qtabs.get() + (size_t)q * p->M * 256;
                         launch_adc_quantise(tab, sc.d_minrng.get() + (size_t)q * p->M * 4, p->M, sc.cs.tau + q, qtab, prm, s);
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[2], s);
-                        launch_adc_prefilter(qtab, prm, p->M, p->d_codes.get(), p->n, sc.d_cand.get(), kCandCap, sc.d_cand_cnt.get() + q, s);
+                        prefilter_one(qtab, prm, sc.d_cand.get(), sc.d_cand_cnt.get() + q);
                         stats[3]++;
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[3], s);
                         launch_adc_exact_candidates(tab, p->M, p->d_codes.get(), sc.d_cand.get(), sc.d_cand_cnt.get() + q, kCandCap, prm, q,
                                                     sc.cs, s);
                     } else {
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[2], s);
-                        launch_adc_scan(tab, p->M, p->d_codes.get(), 0, p->n, q, nullptr, sc.cs, false, nullptr, 0, s, nullptr);
+                        exact_scan(tab, 0, v.n, q, false);
                         if (prof && q == nqi - 1) (void)hipEventRecord(p->ev[3], s);
                     }
                     // the search's last select also writes the k results (redone queries overwrite them below)
-                    launch_select(sc.cs, sc.d_slots.get() + q, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                    launch_select(sc.cs, sc.d_slots.get() + q, 1, k, 0u, s, k_have, &em);
                     return;
                 }
             }
             launch_init_cand(sc.cs, sc.d_slots.get() + q, 1, s);
             int64_t pos = 0;
             int step = 0;
-            while (pos < p->n) {
-                const int64_t end = chunk_end_host(step, pos, p->n, k, cap, mode == 2, /*big_boot=*/true);
+            while (pos < v.n) {
+                const int64_t end = chunk_end_host(step, pos, v.n, k, cap, mode == 2, /*big_boot=*/true);
                 const bool boot = step == 0;
-                launch_adc_scan(tab, p->M, p->d_codes.get(), pos, end, q, nullptr, sc.cs, boot, nullptr, 0, s);
+                exact_scan(tab, pos, end, q, boot);
                 launch_select(sc.cs, sc.d_slots.get() + q, 1, k, boot ? (uint32_t)(end - pos) : 0u, s, 0u,
-                              end >= p->n ? &em : nullptr);
+                              end >= v.n ? &em : nullptr);
                 pos = end;
                 step++;
             }
-            if (p->n == 0) launch_emit_lists(sc.cs, sc.d_slots.get() + q, 1, k, nullptr, d_dist, d_labels, sc.h_flags.get(), s);
+            if (v.n == 0) launch_emit_lists(sc.cs, sc.d_slots.get() + q, 1, k, nullptr, d_dist, d_labels, sc.h_flags.get(), s);
         };
         // two queries share ONE pass over the codes: thresholds and byte tables for both, then the two-query
         // prefilter, then the exact survivors and the select of each.  false = not applicable (run them one by one)
@@ -487,11 +529,10 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
             }
             const bool last = q + 1 == nqi - 1;
             if (prof && last) (void)hipEventRecord(p->ev[2], s);
-            if (!launch_adc_prefilter2(qtab[0], prm[0], sc.d_cand.get(), sc.d_cand_cnt.get() + q, qtab[1], prm[1], sc.d_cand.get() + kCandCap,
-                                       sc.d_cand_cnt.get() + q + 1, p->M, p->d_codes.get(), p->n, kCandCap, s)) {
+            if (!prefilter_two(qtab[0], prm[0], sc.d_cand.get(), sc.d_cand_cnt.get() + q, qtab[1], prm[1], sc.d_cand.get() + kCandCap,
+                               sc.d_cand_cnt.get() + q + 1)) {
                 for (int j = 0; j < 2; j++)
-                    launch_adc_prefilter(qtab[j], prm[j], p->M, p->d_codes.get(), p->n, sc.d_cand.get() + (size_t)j * kCandCap, kCandCap,
-                                         sc.d_cand_cnt.get() + q + j, s);
+                    prefilter_one(qtab[j], prm[j], sc.d_cand.get() + (size_t)j * kCandCap, sc.d_cand_cnt.get() + q + j);
                 stats[3] += 2;
             } else {
                 stats[2] += 2;
@@ -502,13 +543,13 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                 const float *tab = sc.d_tables.get() + (size_t)qq * p->M * 256;
                 launch_adc_exact_candidates(tab, p->M, p->d_codes.get(), sc.d_cand.get() + (size_t)j * kCandCap, sc.d_cand_cnt.get() + qq, kCandCap,
                                             prm[j], qq, sc.cs, s);
-                launch_select(sc.cs, sc.d_slots.get() + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                launch_select(sc.cs, sc.d_slots.get() + qq, 1, k, 0u, s, k_have, &em);
             }
             return true;
         };
         // four queries share ONE pass (interleaved byte tables: one LDS gather per code byte serves all four)
         auto scan_quad = [&](int q) -> bool {
-            if (!prefilter || !samp_count) return false;
+            if (!prefilter || !samp_count || v.rowmap) return false; // (no four-query form over a list: pairs serve it)
             const int *prm[4];
             const uint8_t *qtab[4];
             uint32_t *cand[4], *ccnt[4];
@@ -543,7 +584,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
                 const int qq = q + j;
                 const float *tab = sc.d_tables.get() + (size_t)qq * p->M * 256;
                 launch_adc_exact_candidates(tab, p->M, p->d_codes.get(), cand[j], ccnt[j], kCandCap, prm[j], qq, sc.cs, s);
-                launch_select(sc.cs, sc.d_slots.get() + qq, 1, k, 0u, s, (uint32_t)std::min<int64_t>(k, p->n), &em);
+                launch_select(sc.cs, sc.d_slots.get() + qq, 1, k, 0u, s, k_have, &em);
             }
             return true;
         };

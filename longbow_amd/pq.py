@@ -11,6 +11,7 @@ import struct
 import numpy as np
 
 from . import _lib
+from ._rowfilter import RowFilterMixin
 
 
 def serialize_codebooks(codebooks):
@@ -56,8 +57,10 @@ def train_device(n, d_vectors, dims, M, K=256, max_iter=20, seed=0, init_rows=No
     return blob.tobytes(), iters[:M]
 
 
-class PQEncoder:
-    """PQEncoder on the GPU, built from the reference's serialised blob (or trained: PQEncoder.Train)."""
+class PQEncoder(RowFilterMixin):
+    """PQEncoder on the GPU, built from the reference's serialised blob (or trained: PQEncoder.Train).  set_filter /
+    filter_column / nvisible (RowFilterMixin): with a row filter Search returns the exact ADC k-NN among the visible rows."""
+    _prefix = "lb_gpu_pq"
 
     @classmethod
     def Train(cls, vectors, M, max_iter=20, seed=0, init_rows=None, device=0):
@@ -80,6 +83,9 @@ class PQEncoder:
         self.Dims = lib.lb_gpu_pq_dims(self._h)
         self.K = 256
         self.SubDim = self.Dims // self.M
+
+    def _check(self, rc):
+        _lib.check(rc, self._h, pq=True, lib=self._lib)
 
     def add_codes(self, codes):
         codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)

@@ -1,9 +1,11 @@
-"""Filtered searches on the BQ and SQ8 indexes: search time against the share of visible rows, one JSON line.
+"""Filtered searches on the BQ, SQ8 and PQ indexes: search time against the share of visible rows, one JSON line.
 
-    python tools/code_filter_bench.py --index bq|sq8 [--rows 1000000] [--dim 768] [--k 100] [--nq 1,64,1024]
+    python tools/code_filter_bench.py --index bq|sq8|pq [--rows 1000000] [--dim 768] [--k 100] [--nq 1,64,1024]
                                       [--visible-pct 100,50,10] [--runs 3] [--reps 10]
 
-Rows are drawn on the device (uniform in [-0.5, 0.5)) and added as vectors.  100 % means no filter (the unmapped kernels);
+BQ and SQ8: rows are drawn on the device (uniform in [-0.5, 0.5)) and added as vectors.  PQ (defaults --rows 10000000,
+--nq 1,2,16, --visible-pct 100,50,10,1; M = dim / 8): code bytes uniform in [0, 256) are drawn on the device and added with
+add_codes_device, the codebooks are uniform in [0, 1) from seed 7 and so are the queries.  100 % means no filter (the unmapped kernels);
 every other share sets a random byte mask with that share of non-zero bytes, so the search walks the list of visible rows.
 Per (share, nq): `runs` runs, each the p50 of `reps` searches through the device-pointer entry point (the call returns when the
 results are on the device); the figure is the median of the runs, and the runs themselves are kept (their spread is the margin
@@ -21,7 +23,10 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from longbow_amd import bq, gpu, sq8  # noqa: E402
+from longbow_amd import bq, gpu, pq, sq8  # noqa: E402
+
+DEFAULTS = {"bq": (1_000_000, "1,64,1024", "100,50,10"), "sq8": (1_000_000, "1,64,1024", "100,50,10"),
+            "pq": (10_000_000, "1,2,16", "100,50,10,1")}  # rows, nq, visible-pct
 
 
 def p50(fn, reps):
@@ -43,26 +48,39 @@ def clock_mhz():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--index", choices=("bq", "sq8"), required=True)
-    ap.add_argument("--rows", type=int, default=1_000_000)
+    ap.add_argument("--index", choices=("bq", "sq8", "pq"), required=True)
+    ap.add_argument("--rows", type=int, default=None)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--k", type=int, default=100)
-    ap.add_argument("--nq", default="1,64,1024")
-    ap.add_argument("--visible-pct", default="100,50,10")
+    ap.add_argument("--nq", default=None)
+    ap.add_argument("--visible-pct", default=None)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--reps", type=int, default=10)
     a = ap.parse_args()
+    a.rows = a.rows if a.rows is not None else DEFAULTS[a.index][0]
+    a.nq = a.nq or DEFAULTS[a.index][1]
+    a.visible_pct = a.visible_pct or DEFAULTS[a.index][2]
     nqs = [int(x) for x in a.nq.split(",")]
     pcts = [int(x) for x in a.visible_pct.split(",")]
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
-    enc = bq.BQEncoder(a.dim) if a.index == "bq" else sq8.SQ8Encoder(a.dim)
+    if a.index == "pq":
+        M = a.dim // 8
+        enc = pq.PQEncoder(pq.serialize_codebooks(np.random.default_rng(7).random((M, 256, 8), dtype=np.float32)))
+    else:
+        enc = bq.BQEncoder(a.dim) if a.index == "bq" else sq8.SQ8Encoder(a.dim)
     enc.reserve(a.rows)
     out = {"index": a.index, "rows": a.rows, "dim": a.dim, "k": a.k, "runs": a.runs, "reps": a.reps,
            "shader_clock_mhz_before": clock_mhz()}
     piece = min(a.rows, 1_000_000)
     for r0 in range(0, a.rows, piece):
         cnt = min(piece, a.rows - r0)
+        if a.index == "pq":
+            V = torch.randint(0, 256, (cnt, enc.M), dtype=torch.uint8, device="cuda")
+            torch.cuda.synchronize()
+            enc.add_codes_device(cnt, V.data_ptr())
+            del V
+            continue
         V = torch.rand((cnt, a.dim), device="cuda") - 0.5
         torch.cuda.synchronize()
         if r0 == 0 and a.index == "sq8":
@@ -71,7 +89,7 @@ def main():
         del V
     masks = {p: (rng.random(a.rows) < p / 100.0).astype(np.uint8) for p in pcts if p != 100}
     nqmax = max(nqs)
-    Q = torch.rand((nqmax, a.dim), device="cuda") - 0.5
+    Q = torch.rand((nqmax, a.dim), device="cuda") - (0.0 if a.index == "pq" else 0.5)
     D = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
     L = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
     torch.cuda.synchronize()
