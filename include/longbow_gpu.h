@@ -590,6 +590,63 @@ int lb_gpu_sq8_filter_float32(lb_gpu_sq8 *p, const float *column, int64_t n, flo
                               int64_t validity_offset, int combine);
 int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
 
+/* ---- IVF-Flat: exact k-NN over the probed lists ---------------------------------------------
+ * The index type the reference names and leaves empty: IndexTypeIVFFlat = "ivf_flat" and IVFFlatConfig{NClusters, NProbe}
+ * (internal/store/pluggable_index.go:18-25,100-104); its adapter (pluggable_index_adapters.go:116-223) is a stub.  A coarse
+ * partition of the rows lets a query skip most of them.  Nothing is approximate except WHICH lists are probed: given the probed
+ * lists the result is the exact k-NN among their rows, bit for bit in the reference's distance arithmetic.
+ * A handle has a metric (0 L2, 1 cosine, 2 dot, as lb_gpu_index_new), an accumulation order (0 SEQ, 1 UNROLL4, as
+ * lb_gpu_index_set_order; fixed at creation because it decides which list a row goes to), nlist centroids C (f32 [nlist][dim],
+ * given by the caller) and rows X in insertion order.  Write d(a, b) for the distance lb_gpu_index_search reports for query a and
+ * row b under that metric and order (L2 with its square root, 1 - cos, -dot); the canonical order is ascending (distance,
+ * position), every NaN after +inf.
+ *   list of a row     the label of the k = 1 search of the row, as a query, over an f32 index that holds C: the first c in
+ *                     canonical order of (d(x, C_c), c).  Computed when the row is added; it never changes.
+ *   probes of a query the labels of the k = min(nprobe, nlist) search of the query over that same index.
+ *   result            the first k rows r, in canonical order of (d(q, X_r), r), among the rows whose list is a probe of q; the
+ *                     label is ids[r] when ids were given, else r; with fewer than k such rows they come first, then label -1 /
+ *                     distance FLT_MAX.  nprobe >= nlist gives lb_gpu_index_search over the same rows, bit for bit: labels,
+ *                     order and distances.
+ *   ids               given on every add or on none; a call that breaks this is LB_ERR_INVALID_ARG and adds nothing.
+ *   add               appends the rows, takes their lists and rebuilds the lists of ALL rows by a stable counting sort (each list
+ *                     holds its rows ascending): O(ntotal) per call, so add in large pieces.  The rows become visible only once
+ *                     all of it succeeded.
+ *   limits            dim in 1..LB_MAX_DIM, nlist in 1..65536, k in 1..LB_MAX_K, fewer than 2^31 rows: LB_ERR_UNSUPPORTED
+ *                     beyond.  nprobe <= 0 is LB_ERR_INVALID_ARG, nprobe > nlist is clamped.
+ * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
+ * refused call writes nothing.  Searches and reads share the handle; adds and reserve take it alone.  ctx (nullable) is polled
+ * before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here: fp16 / int8 rows, row
+ * filters, search combining, lb_gpu_comm_*, removing rows. */
+typedef struct lb_gpu_ivf lb_gpu_ivf;
+lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
+void lb_gpu_ivf_free(lb_gpu_ivf *p);
+const char *lb_gpu_ivf_last_error(const lb_gpu_ivf *p);
+int lb_gpu_ivf_dim(const lb_gpu_ivf *p);
+int lb_gpu_ivf_metric(const lb_gpu_ivf *p);
+int lb_gpu_ivf_order(const lb_gpu_ivf *p);
+int lb_gpu_ivf_nlist(const lb_gpu_ivf *p);
+int64_t lb_gpu_ivf_ntotal(const lb_gpu_ivf *p);
+int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p); /* rows, ids, lists and the coarse index */
+int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out); /* f32[nlist*dim] */
+int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total);
+int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids);
+int lb_gpu_ivf_add_device(lb_gpu_ivf *p, int64_t n, const float *d_vectors, const int64_t *d_ids);
+int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes); /* [nlist] */
+int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
+int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
+int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
+                          const lb_cancel *ctx);
+int lb_gpu_ivf_search_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
+                                 void *stream, const lb_cancel *ctx);
+/* telemetry of the last search only: out[0] queries, out[1] rows scanned summed over the queries, out[2] the largest per-query
+ * count, out[3] queries whose selection ran from LDS */
+int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]);
+/* instrumentation (tools/ivf_bench.py), as lb_gpu_pq_set_profiling: while on, a search records HIP events between its steps and
+ * drains the stream after every batch; last_timing gives the last such search's ms summed over its batches: ms[0] the probes
+ * (the coarse search), ms[1] the plan (and the query norms, cosine), ms[2] the list scan, ms[3] the selection. */
+int lb_gpu_ivf_set_profiling(lb_gpu_ivf *p, int enable);
+int lb_gpu_ivf_last_timing(lb_gpu_ivf *p, float ms[4]);
+
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:
  * inputs [S][nq][k] ascending per (shard, query) (padding label -1 / FLT_MAX allowed),

@@ -1,0 +1,47 @@
+// lb_ivf.h -- what ivf.hip (host) and kernels_ivf.hip (device) of the IVF-Flat index share: the argument blocks of the kernels
+// and their launchers.  The semantics are stated in include/longbow_gpu.h (lb_gpu_ivf_*).
+#pragma once
+#include "lb_device.h"
+
+namespace lb {
+
+// The inverted lists over rows kept in insertion order: list l is rows[off[l], off[l + 1]), ascending.
+struct IvfLists {
+    const uint32_t *off;  // [nlist + 1]
+    const uint32_t *rows; // [n]
+    int nlist;
+};
+
+// One batch of queries as the search kernels take it (by value).
+struct IvfBatch {
+    const float *X; // [n][D] rows, insertion order
+    int D;
+    IvfLists L;
+    const float *Q;        // [nq][D]
+    const float *qna;      // [nq] ||q||^2 in the handle's order (cosine; else unused)
+    int nq;
+    const int64_t *probes; // [nq][np] the coarse search's labels: distinct lists per query
+    int np;
+    uint32_t *seg;         // [nq][np + 1]: exclusive prefix of the probed lists' sizes, then their total P_q
+    uint64_t *keys;        // [nq][pmax]: pack_entry(distance, row) of every scanned row, list by list
+    int64_t pmax;          // keys per query: the sum of the np largest list sizes
+};
+
+constexpr int IVF_MAX_NLIST = 65536;
+constexpr uint32_t IVF_SELECT_LDS_KEYS = 16384; // a query with at most this many scanned rows is selected from an LDS copy
+
+// seg of every query; stats (u64[4], zero before a search's first batch): [1] += P_q, [2] = max P_q, [3] += P_q fits LDS
+void launch_ivf_plan(const IvfBatch &a, unsigned long long *stats, hipStream_t s);
+// keys[q][seg[q][p] + i] = entry of the i-th row of the p-th probed list; maxlen: the longest list of the handle
+void launch_ivf_scan(int metric, int order, const IvfBatch &a, int64_t maxlen, hipStream_t s);
+// the k smallest keys of each query, ascending -> dist / labels [nq][k] (ids nullable: the row itself), padded FLT_MAX / -1
+void launch_ivf_select(const IvfBatch &a, int k, const int64_t *ids, float *dist, int64_t *labels, hipStream_t s);
+
+// assign[i] = labels[i] (the coarse search's k = 1 labels)
+void launch_ivf_narrow(const int64_t *labels, int64_t n, uint32_t *assign, hipStream_t s);
+// Stable counting sort of rows [0, n) by assign: off[nlist + 1] and rows[n].  hist: scratch of ivf_sort_hist_words(n, nlist) u32.
+// Returns the error of the memset that clears hist (nothing is launched then).
+size_t ivf_sort_hist_words(int64_t n, int nlist);
+hipError_t launch_ivf_sort(const uint32_t *assign, int64_t n, int nlist, uint32_t *hist, uint32_t *off, uint32_t *rows, hipStream_t s);
+
+} // namespace lb

@@ -1,0 +1,258 @@
+"""IVF-Flat on the GPU (lb_gpu_ivf_*): the index type the reference names -- IndexTypeIVFFlat = "ivf_flat", IVFFlatConfig{NClusters,
+NProbe} (internal/store/pluggable_index.go:18-25,100-104) -- and leaves a stub (pluggable_index_adapters.go:116-223).
+
+A coarse partition of the rows lets a query skip most of them.  Nothing is approximate except which lists are probed: given the
+probed lists the result is the exact k-NN among their rows, bit for bit in the reference's distance arithmetic, and with every
+list probed it equals gpu.Index.Search.  include/longbow_gpu.h states the semantics.
+
+  IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats
+  IVFFlatIndex   the reference's PluggableVectorIndex surface over it: rows are buffered until Build()
+  train          TrainKMeans on the GPU (pq.train with M = 1): nlist centroids of f32 rows
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _lib, pq
+
+FLT_MAX = np.float32(3.4028234663852886e38)
+MAX_NLIST = 65536
+TRAIN_MAX_NLIST = 256  # lb_gpu_pq_train's K
+
+
+def train(vectors, nlist, max_iter=20, seed=0, init_rows=None, device=0):
+    """TrainKMeans(vectors, n, dims, nlist, max_iter) (internal/pq/kmeans.go:64-151) on the GPU -> centroids f32 [nlist, dims].
+    It is pq.train with M = 1 and K = nlist, the blob's 12-byte header stripped, and inherits that call's K <= 256; centroids
+    from elsewhere may have any nlist up to 65,536.  max_iter = 0 returns the init rows."""
+    if nlist > TRAIN_MAX_NLIST:
+        raise ValueError(f"ivf.train takes nlist <= {TRAIN_MAX_NLIST} (lb_gpu_pq_train's K), got {nlist}")
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2 or v.shape[0] == 0:
+        raise ValueError("empty training data")
+    rows = None if init_rows is None else np.ascontiguousarray(init_rows, np.int64).reshape(1, nlist)
+    blob, _ = pq.train(v, 1, nlist, max_iter, seed, rows, device)
+    return np.frombuffer(blob[12:], "<f4").reshape(nlist, v.shape[1]).copy()
+
+
+def train_device(n, d_vectors, dims, nlist, max_iter=20, seed=0, init_rows=None, device=0):
+    """train() over n rows already resident on the device (d_vectors: device address); init_rows stays a host array"""
+    if nlist > TRAIN_MAX_NLIST:
+        raise ValueError(f"ivf.train takes nlist <= {TRAIN_MAX_NLIST} (lb_gpu_pq_train's K), got {nlist}")
+    rows = None if init_rows is None else np.ascontiguousarray(init_rows, np.int64).reshape(1, nlist)
+    blob, _ = pq.train_device(n, d_vectors, dims, 1, nlist, max_iter, seed, rows, device)
+    return np.frombuffer(blob[12:], "<f4").reshape(nlist, dims).copy()
+
+
+class IVFFlat:
+    """lb_gpu_ivf: metric 0 L2 / 1 cosine / 2 dot, order 0 SEQ / 1 UNROLL4, centroids f32 [nlist, dims]"""
+
+    def __init__(self, centroids, metric=0, order=0, device=0, lib=None):
+        self._h = None  # (Close() and __del__ find this when creation fails below)
+        c = np.ascontiguousarray(centroids, np.float32)
+        if c.ndim != 2 or c.shape[0] == 0 or c.shape[1] == 0:
+            raise ValueError("centroids must be a non-empty [nlist, dims] array")
+        lib = lib or _lib.require_gpu(device)
+        st = C.c_int(0)
+        h = lib.lb_gpu_ivf_new(device, c.shape[1], metric, order, c.shape[0], c.ctypes.data, C.byref(st))
+        if not h:
+            _lib.check(st.value or 7)
+        self._lib = lib
+        self._h = C.c_void_p(h)
+        self.device = device
+        self.nlist, self.dims = c.shape
+        self.metric, self.order = metric, order
+
+    def _check(self, rc):
+        _lib.check(rc, self._h, lib=self._lib, ivf=True)
+
+    def _vectors(self, vectors):
+        v = np.ascontiguousarray(vectors, np.float32)
+        v = v.reshape(-1, v.shape[-1]) if v.size else v.reshape(0, self.dims)
+        if v.shape[1] != self.dims:
+            raise ValueError(f"vector dimension {v.shape[1]} does not match {self.dims}")
+        return v
+
+    @property
+    def ntotal(self):
+        return int(self._lib.lb_gpu_ivf_ntotal(self._h))
+
+    @property
+    def hbm_bytes(self):
+        return int(self._lib.lb_gpu_ivf_hbm_bytes(self._h))
+
+    def centroids(self):
+        out = np.empty((self.nlist, self.dims), np.float32)
+        self._check(self._lib.lb_gpu_ivf_get_centroids(self._h, out.ctypes.data))
+        return out
+
+    def reserve(self, n_total):
+        self._check(self._lib.lb_gpu_ivf_reserve(self._h, n_total))
+
+    def add(self, vectors, ids=None):
+        """append rows [n, dims]; ids (int64 [n]) on every add or on none.  Each add rebuilds the lists of all rows: O(ntotal)."""
+        v = self._vectors(vectors)
+        i = None
+        if ids is not None:
+            i = np.ascontiguousarray(ids, np.int64).reshape(-1)
+            if i.size != v.shape[0]:
+                raise ValueError(f"{i.size} ids for {v.shape[0]} rows")
+        self._check(self._lib.lb_gpu_ivf_add(self._h, v.shape[0], v.ctypes.data, i.ctypes.data if i is not None else None))
+
+    def add_device(self, n, d_vectors, d_ids=None):
+        self._check(self._lib.lb_gpu_ivf_add_device(self._h, n, d_vectors, d_ids))
+
+    def list_sizes(self):
+        out = np.empty(self.nlist, np.int64)
+        self._check(self._lib.lb_gpu_ivf_list_sizes(self._h, out.ctypes.data))
+        return out
+
+    def assignments(self, row0=0, n=None):
+        """the lists of rows [row0, row0 + n) -> int32 [n]"""
+        n = self.ntotal - row0 if n is None else n
+        out = np.empty(max(n, 0), np.int32)
+        self._check(self._lib.lb_gpu_ivf_assignments(self._h, row0, n, out.ctypes.data))
+        return out
+
+    def search(self, queries, k, nprobe, ctx=None):
+        """-> (labels [nq, k], dist [nq, k]): ascending (distance, row) among the rows of the probed lists, padded -1 / FLT_MAX"""
+        v = self._vectors(queries)
+        dist = np.empty((v.shape[0], k), np.float32)
+        labels = np.empty((v.shape[0], k), np.int64)
+        self._check(self._lib.lb_gpu_ivf_search_ctx(self._h, v.shape[0], v.ctypes.data, k, nprobe, dist.ctypes.data, labels.ctypes.data,
+                                                    ctx._h if ctx is not None else None))
+        return labels, dist
+
+    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None):
+        self._check(self._lib.lb_gpu_ivf_search_device_ctx(self._h, nq, d_queries, k, nprobe, d_dist, d_labels, stream,
+                                                           ctx._h if ctx is not None else None))
+
+    def last_search_stats(self):
+        """of the last search: (queries, rows scanned summed over them, the largest per-query count, queries selected from LDS)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._lib.lb_gpu_ivf_last_search_stats(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def set_profiling(self, on):
+        self._check(self._lib.lb_gpu_ivf_set_profiling(self._h, 1 if on else 0))
+
+    def last_timing(self):
+        """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
+        out = (C.c_float * 4)()
+        self._check(self._lib.lb_gpu_ivf_last_timing(self._h, out))
+        return tuple(float(x) for x in out)
+
+    def Close(self):
+        if self._h:
+            self._lib.lb_gpu_ivf_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass
+
+
+@dataclass
+class IVFFlatConfig:
+    """pluggable_index.go:100-104"""
+    NClusters: int = 256
+    NProbe: int = 8
+
+
+class IVFFlatIndex:
+    """The reference's IVFFlatIndex surface (pluggable_index_adapters.go:116-223) with an index behind it.  Before Build() rows are
+    buffered on the host, as the stub keeps them in its map; Build() takes the centroids as given, or trains them on the buffered
+    rows (ivf.train), creates the handle and adds the rows; after it, adds go straight to the handle."""
+
+    def __init__(self, dimension, config=None, metric=0, order=0, device=0, centroids=None, train_iters=20, seed=0):
+        if dimension <= 0:
+            raise ValueError(f"dimension must be positive, got {dimension}")
+        self.config = config or IVFFlatConfig()
+        if self.config.NClusters <= 0 or self.config.NProbe <= 0:
+            raise ValueError("NClusters and NProbe must be positive")
+        _lib.require_gpu(device)
+        self.dimension, self.metric, self.order, self.device = dimension, metric, order, device
+        self._centroids = None if centroids is None else np.ascontiguousarray(centroids, np.float32)
+        if self._centroids is not None and self._centroids.shape != (self.config.NClusters, dimension):
+            raise ValueError(f"centroids of shape {self._centroids.shape}, config asks for {(self.config.NClusters, dimension)}")
+        self._train_iters, self._seed = train_iters, seed
+        self._ids, self._rows = [], []
+        self._h = None
+
+    def Type(self):
+        return "ivf_flat"
+
+    def Dimension(self):
+        return self.dimension
+
+    def Size(self):
+        return self._h.ntotal if self._h is not None else sum(r.shape[0] for r in self._rows)
+
+    Len = Size
+
+    def NeedsBuild(self):
+        return True  # IVF requires training / clustering (pluggable_index_adapters.go:143-145)
+
+    def AddBatch(self, ids, vectors):
+        v = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
+        i = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        if i.size != v.shape[0]:
+            raise ValueError(f"{i.size} ids for {v.shape[0]} rows")
+        if self._h is not None:
+            self._h.add(v, i)
+        else:
+            self._ids.append(i.copy())
+            self._rows.append(v.copy())
+
+    def Add(self, id, vector):
+        self.AddBatch([id], np.asarray(vector, np.float32).reshape(1, -1))
+
+    def Build(self):
+        if self._h is not None:
+            return
+        rows = np.concatenate(self._rows) if self._rows else np.empty((0, self.dimension), np.float32)
+        ids = np.concatenate(self._ids) if self._ids else np.empty(0, np.int64)
+        if self._centroids is None:
+            self._centroids = train(rows, self.config.NClusters, self._train_iters, self._seed, device=self.device)
+        self._h = IVFFlat(self._centroids, self.metric, self.order, self.device)
+        if rows.shape[0]:
+            self._h.add(rows, ids)
+        self._ids, self._rows = [], []
+
+    def _built(self):
+        if self._h is None:
+            raise RuntimeError("ivf_flat: Build() before Search()")
+        return self._h
+
+    def SearchBatch(self, queries, k, nprobe=None):
+        """-> (ids [nq, k], distances [nq, k]), padded -1 / FLT_MAX"""
+        return self._built().search(queries, k, self.config.NProbe if nprobe is None else nprobe)
+
+    def Search(self, query, k, nprobe=None):
+        ids, dist = self.SearchBatch(np.asarray(query, np.float32).reshape(1, -1), k, nprobe)
+        return ids[0], dist[0]
+
+    def search_device(self, nq, d_queries, k, d_dist, d_labels, nprobe=None, stream=None, ctx=None):
+        self._built().search_device(nq, d_queries, k, self.config.NProbe if nprobe is None else nprobe, d_dist, d_labels, stream, ctx)
+
+    def list_sizes(self):
+        return self._built().list_sizes()
+
+    def assignments(self, row0=0, n=None):
+        return self._built().assignments(row0, n)
+
+    def last_search_stats(self):
+        return self._built().last_search_stats()
+
+    def Save(self, path):
+        raise NotImplementedError("ivf_flat: Save is not implemented (the reference's writes a marker file only)")
+
+    def Load(self, path):
+        raise NotImplementedError("ivf_flat: Load is not implemented (the reference's reads a marker file only)")
+
+    def Close(self):
+        if self._h is not None:
+            self._h.Close()
+            self._h = None
