@@ -611,12 +611,27 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *   add               appends the rows, takes their lists and rebuilds the lists of ALL rows by a stable counting sort (each list
  *                     holds its rows ascending): O(ntotal) per call, so add in large pieces.  The rows become visible only once
  *                     all of it succeeded.
+ *   filter            a row filter on the handle, with the mask, null and combine rules of lb_gpu_bq_set_filter / _filter_*: a
+ *                     row is visible iff its mask byte is non-zero; a NULL mask clears the filter; n != ntotal is
+ *                     LB_ERR_INVALID_ARG with a last_error text and leaves the filter as it was; a predicate's nulls never match;
+ *                     combine 0 replaces the mask, 1 ANDs into it and replaces when there is none.  The probes of a query do not
+ *                     change: a probed list with no visible row contributes nothing and no other list takes its place.  The
+ *                     result is the first k rows in canonical order among the VISIBLE rows whose list is a probe, with the same
+ *                     labels, padding and distances, bit for bit; nprobe >= nlist gives lb_gpu_index_search on an index that
+ *                     holds the same rows under the same mask (lb_gpu_index_set_filter).  Rows added after a filter was set are
+ *                     visible; such an add commits the rows, the lists and the visible lists together or not at all.
+ *                     list_sizes, assignments, get_centroids and ntotal ignore the filter; nvisible is the number of rows a search
+ *                     can see (ntotal without a filter).  Any filter, an all-visible one too, searches the visible lists (each
+ *                     list's visible rows, ascending, built on the device by every filter call and every add under a filter), so
+ *                     the cost follows the visible rows of the probed lists, and last_search_stats counts those.
  *   limits            dim in 1..LB_MAX_DIM, nlist in 1..65536, k in 1..LB_MAX_K, fewer than 2^31 rows: LB_ERR_UNSUPPORTED
- *                     beyond.  nprobe <= 0 is LB_ERR_INVALID_ARG, nprobe > nlist is clamped.
+ *                     beyond.  nprobe <= 0 is LB_ERR_INVALID_ARG, nprobe > nlist is clamped.  Fewer than all lists are at most
+ *                     LB_MAX_K probes (the coarse search's k; LB_ERR_UNSUPPORTED beyond); every list probed needs no coarse
+ *                     search and works for any nlist.
  * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
- * refused call writes nothing.  Searches and reads share the handle; adds and reserve take it alone.  ctx (nullable) is polled
- * before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here: fp16 / int8 rows, row
- * filters, search combining, lb_gpu_comm_*, removing rows. */
+ * refused call writes nothing.  Searches and reads share the handle; adds, reserve and the filter calls take it alone.  ctx
+ * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here:
+ * fp16 / int8 rows, a filter given per search call, search combining, lb_gpu_comm_*, removing rows. */
 typedef struct lb_gpu_ivf lb_gpu_ivf;
 lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
 void lb_gpu_ivf_free(lb_gpu_ivf *p);
@@ -626,7 +641,7 @@ int lb_gpu_ivf_metric(const lb_gpu_ivf *p);
 int lb_gpu_ivf_order(const lb_gpu_ivf *p);
 int lb_gpu_ivf_nlist(const lb_gpu_ivf *p);
 int64_t lb_gpu_ivf_ntotal(const lb_gpu_ivf *p);
-int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p); /* rows, ids, lists and the coarse index */
+int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p); /* rows, ids, lists, the coarse index and what a row filter holds */
 int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out); /* f32[nlist*dim] */
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total);
 int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids);
@@ -638,14 +653,24 @@ int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k
                           const lb_cancel *ctx);
 int lb_gpu_ivf_search_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                  void *stream, const lb_cancel *ctx);
+/* the row filter, as lb_gpu_bq_set_filter / _filter_int64 / _filter_float32 / _nvisible */
+int lb_gpu_ivf_set_filter(lb_gpu_ivf *p, const uint8_t *mask, int64_t n);
+int lb_gpu_ivf_filter_int64(lb_gpu_ivf *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                            int64_t validity_offset, int combine);
+int lb_gpu_ivf_filter_float32(lb_gpu_ivf *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine);
+int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p);
 /* telemetry of the last search only: out[0] queries, out[1] rows scanned summed over the queries, out[2] the largest per-query
- * count, out[3] queries whose selection ran from LDS */
+ * count, out[3] queries whose selection ran from LDS; under a row filter the rows are the visible ones of the probed lists */
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]);
 /* instrumentation (tools/ivf_bench.py), as lb_gpu_pq_set_profiling: while on, a search records HIP events between its steps and
  * drains the stream after every batch; last_timing gives the last such search's ms summed over its batches: ms[0] the probes
  * (the coarse search), ms[1] the plan (and the query norms, cosine), ms[2] the list scan, ms[3] the selection. */
 int lb_gpu_ivf_set_profiling(lb_gpu_ivf *p, int enable);
 int lb_gpu_ivf_last_timing(lb_gpu_ivf *p, float ms[4]);
+/* while profiling is on, a filter call or an add under a filter also records HIP events around the launches that build the
+ * visible lists: *ms is the last such build's time (tools/code_filter_bench.py --index ivf) */
+int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms);
 
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:

@@ -8,11 +8,12 @@
 
 #include <atomic>
 #include <functional>
+#include <stdexcept>
 #include <vector>
 
 using namespace lb;
 
-struct lb_gpu_ivf : CodeHandle { // searches and reads share mu; adds and reserve take it alone
+struct lb_gpu_ivf : FilteredHandle { // searches and reads share mu; adds, reserve and the filter calls take it alone
     int metric = 0, order = 0, nlist = 0;
     lb_gpu_index *coarse = nullptr; // the centroids: same device, dim, metric and order
     std::vector<float> h_cent;      // [nlist][dims]
@@ -25,11 +26,23 @@ struct lb_gpu_ivf : CodeHandle { // searches and reads share mu; adds and reserv
     DevBuf<uint32_t> d_list[2];     // [capacity]
     int cur = 0;
     std::vector<int64_t> h_sizes;   // [nlist]: sizes grids and scratch without a device round trip
+    // the row filter (lb_handle.h): a search under one walks the visible lists, the rows of each list whose mask byte is
+    // non-zero, in the list's order.  They are built by every filter call and by every add to a filtered handle, into the pair
+    // that is not in use; filter.n_visible is d_voff[vcur][nlist].  filter.rowmap is rebuilt by the filter calls only and
+    // nothing here reads it.
+    DevBuf<uint32_t> d_voff[2];     // [nlist + 1]
+    DevBuf<uint32_t> d_vlist[2];    // [capacity] from the first filter on
+    int vcur = 0;
+    std::vector<int64_t> h_vsizes;  // [nlist]: what h_sizes is to the lists
     int64_t stats[4] = {0, 0, 0, 0}; // of the last search (under err_mu)
     std::atomic<bool> profiling{false};
     float timing[4] = {0, 0, 0, 0};  // of the last profiled search (under err_mu): probes, plan, scan, select; ms summed over its batches
+    float build_ms = 0;              // of the last profiled build of the visible lists (under err_mu): its launches alone
     ~lb_gpu_ivf() { lb_gpu_index_free(coarse); }
-    IvfLists lists() const { return IvfLists{d_off[cur].get(), d_list[cur].get(), nlist}; }
+    IvfLists all_lists(int i) const { return IvfLists{d_off[i].get(), d_list[i].get(), nlist}; }
+    // what a search walks, and the sizes that go with it
+    IvfLists lists() const { return filter.on ? IvfLists{d_voff[vcur].get(), d_vlist[vcur].get(), nlist} : all_lists(cur); }
+    const std::vector<int64_t> &sizes() const { return filter.on ? h_vsizes : h_sizes; }
 };
 
 namespace {
@@ -49,15 +62,26 @@ void ivf_grow(lb_gpu_ivf *p, int64_t need, bool want_ids)
     }
     if (cap != p->capacity) {
         DevBuf<float> nr;
-        DevBuf<uint32_t> na, nl0, nl1;
+        DevBuf<uint32_t> na, nl0, nl1, nv0, nv1;
         nr.alloc((size_t)cap * p->dims);
         na.alloc((size_t)cap);
         nl0.alloc((size_t)cap);
         nl1.alloc((size_t)cap);
+        if (p->filter.on) { // an active filter keeps its visible lists
+            nv0.alloc((size_t)cap);
+            nv1.alloc((size_t)cap);
+        }
         if (p->n > 0) {
             LB_HIP(hipMemcpy(nr.get(), p->d_rows.get(), (size_t)p->n * p->dims * 4, hipMemcpyDeviceToDevice));
             LB_HIP(hipMemcpy(na.get(), p->d_assign.get(), (size_t)p->n * 4, hipMemcpyDeviceToDevice));
             LB_HIP(hipMemcpy((p->cur ? nl1 : nl0).get(), p->d_list[p->cur].get(), (size_t)p->n * 4, hipMemcpyDeviceToDevice));
+        }
+        if (p->filter.on && p->filter.n_visible > 0)
+            LB_HIP(hipMemcpy((p->vcur ? nv1 : nv0).get(), p->d_vlist[p->vcur].get(), (size_t)p->filter.n_visible * 4, hipMemcpyDeviceToDevice));
+        p->filter.grow(p->n, cap); // (the last step that can fail)
+        if (p->filter.on) {
+            p->d_vlist[0] = std::move(nv0);
+            p->d_vlist[1] = std::move(nv1);
         }
         p->d_rows = std::move(nr);
         p->d_assign = std::move(na);
@@ -66,6 +90,49 @@ void ivf_grow(lb_gpu_ivf *p, int64_t need, bool want_ids)
         p->capacity = cap;
     }
     if (want_ids) p->d_ids = std::move(ni);
+}
+
+// The visible lists of mask[0, n) over the lists `L` of those n rows, into pair `to`; drains s.  Nothing of the handle but that
+// pair's buffers is written: the caller commits vsizes, `to` and the count it gets back.  scratch: a lease declared outside the
+// caller's guard.
+int64_t build_visible(lb_gpu_ivf *p, const IvfLists &L, int64_t n, int to, Lease &scratch, std::vector<int64_t> &vsizes, hipStream_t s)
+{
+    std::vector<uint32_t> h_voff((size_t)p->nlist + 1);
+    vsizes.resize((size_t)p->nlist);
+    if (p->d_vlist[to].count() < (size_t)p->capacity) p->d_vlist[to].alloc((size_t)p->capacity);
+    scratch.reset(p->device, ivf_visible_scratch_bytes(n));
+    const bool prof = p->profiling.load();
+    EventH ev[2];
+    if (prof) {
+        for (EventH &e : ev) LB_HIP(hipEventCreate(&e.h));
+        LB_HIP(hipEventRecord(ev[0], s));
+    }
+    LB_HIP(launch_ivf_visible(p->filter.mask.get(), L, n, scratch.p, p->d_voff[to].get(), p->d_vlist[to].get(), s));
+    LB_LAUNCH_CHECK();
+    if (prof) LB_HIP(hipEventRecord(ev[1], s));
+    LB_HIP(hipMemcpyAsync(h_voff.data(), p->d_voff[to].get(), h_voff.size() * 4, hipMemcpyDeviceToHost, s));
+    LB_HIP(hipStreamSynchronize(s));
+    if (prof) {
+        float ms = 0.f;
+        LB_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        std::lock_guard<std::mutex> g(p->err_mu);
+        p->build_ms = ms;
+    }
+    for (int l = 0; l < p->nlist; l++) vsizes[l] = (int64_t)h_voff[l + 1] - (int64_t)h_voff[l];
+    return (int64_t)h_voff[p->nlist];
+}
+
+// what a filter call hands to the shell (lb_handle.h: `built`): the visible lists of the mask it has just written
+auto visible_builder(lb_gpu_ivf *p, Lease &scratch)
+{
+    return [p, &scratch](hipStream_t s) {
+        std::vector<int64_t> vsizes;
+        const int to = 1 - p->vcur;
+        const int64_t nv = build_visible(p, p->all_lists(p->cur), p->n, to, scratch, vsizes, s);
+        if (nv != p->filter.n_visible) throw std::logic_error("the visible lists do not hold the visible rows"); // (LB_ERR_INTERNAL)
+        p->h_vsizes.swap(vsizes);
+        p->vcur = to;
+    };
 }
 
 // the coarse index's own refusal becomes the handle's; what the call enqueued on s is drained before its pooled buffers go back
@@ -87,14 +154,15 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids,
         return LB_ERR_INVALID_ARG;
     }
     if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease lab, hist;
+    Lease lab, hist, vis;
     return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = p->stream;
         const int64_t total = p->n + n;
         const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         std::vector<uint32_t> h_off((size_t)p->nlist + 1);
-        std::vector<int64_t> sizes((size_t)p->nlist);
+        std::vector<int64_t> sizes((size_t)p->nlist), vsizes;
+        const bool filtered = p->filter.on;
         ivf_grow(p, total, ids != nullptr);
         // 1. the rows
         float *d_new = p->d_rows.get() + (size_t)p->n * p->dims;
@@ -119,7 +187,20 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids,
             return LB_ERR_INTERNAL;
         }
         for (int l = 0; l < p->nlist; l++) sizes[l] = (int64_t)h_off[l + 1] - (int64_t)h_off[l];
-        // 5. commit (nothing below throws)
+        // 5. under a filter the new rows are visible: the visible lists of all rows, from the new lists, into the pair not in use
+        //    (the mask bytes behind the stored rows belong to nobody until the commit)
+        const int vnxt = 1 - p->vcur;
+        int64_t nvis = 0;
+        if (filtered) {
+            LB_HIP(hipMemsetAsync(p->filter.mask.get() + p->n, 1, (size_t)n, s));
+            nvis = build_visible(p, p->all_lists(nxt), total, vnxt, vis, vsizes, s);
+        }
+        // 6. commit (nothing below throws)
+        if (filtered) {
+            p->h_vsizes.swap(vsizes);
+            p->vcur = vnxt;
+            p->filter.n_visible = nvis;
+        }
         p->h_sizes.swap(sizes);
         p->cur = nxt;
         p->has_ids = ids != nullptr;
@@ -148,7 +229,7 @@ int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprob
     }
     const int np = std::min(nprobe, p->nlist);
     // pmax: the rows a query can scan at most, the sum of the np largest lists
-    std::vector<int64_t> big(p->h_sizes);
+    std::vector<int64_t> big(p->sizes()); // (the visible lists' under a filter)
     std::partial_sort(big.begin(), big.begin() + np, big.end(), std::greater<int64_t>());
     int64_t pmax = 0;
     for (int i = 0; i < np; i++) pmax += big[i];
@@ -191,8 +272,10 @@ int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprob
         a.nq = (int)std::min(nb, nq - q0);
         a.Q = d_Q + (size_t)q0 * p->dims;
         mark(0);
-        // 1. the probes (the inner index polls ctx before its own launches)
-        if (const int rc = lb_gpu_index_search_device_ctx(p->coarse, a.nq, a.Q, np, d_pdist, d_probes, s, ctx)) return coarse_fail(p, rc, s);
+        // 1. the probes (the inner index polls ctx before its own launches).  More than LB_MAX_K of them is more than the coarse
+        //    search returns: with every list probed they are all the lists, and their order does not reach the result
+        if (np == p->nlist && np > LB_MAX_K) launch_ivf_all_probes(d_probes, a.nq, np, s);
+        else if (const int rc = lb_gpu_index_search_device_ctx(p->coarse, a.nq, a.Q, np, d_pdist, d_probes, s, ctx)) return coarse_fail(p, rc, s);
         mark(1);
         if (!go()) break;
         launch_ivf_plan(a, d_stats, s);                                      // 2.
@@ -256,9 +339,12 @@ lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist
         p->nlist = nlist;
         p->h_cent.assign(centroids, centroids + (size_t)nlist * dim);
         p->h_sizes.assign((size_t)nlist, 0);
+        p->h_vsizes.assign((size_t)nlist, 0);
         for (int i = 0; i < 2; i++) {
             p->d_off[i].alloc((size_t)nlist + 1);
             LB_HIP(hipMemset(p->d_off[i].get(), 0, ((size_t)nlist + 1) * 4));
+            p->d_voff[i].alloc((size_t)nlist + 1);
+            LB_HIP(hipMemset(p->d_voff[i].get(), 0, ((size_t)nlist + 1) * 4));
         }
         p->coarse = lb_gpu_index_new(device, dim, metric, &inner);
         if (!p->coarse) return;
@@ -286,8 +372,11 @@ int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivf *>(p)->mu);
+    const RowFilter &f = p->filter;
     return (int64_t)(p->d_rows.count() * 4 + p->d_ids.count() * 8 + (p->d_assign.count() + p->d_list[0].count() + p->d_list[1].count()) * 4 +
-                     (p->d_off[0].count() + p->d_off[1].count()) * 4) + lb_gpu_index_hbm_bytes(p->coarse);
+                     (p->d_off[0].count() + p->d_off[1].count()) * 4 +
+                     (p->d_voff[0].count() + p->d_voff[1].count() + p->d_vlist[0].count() + p->d_vlist[1].count()) * 4 +
+                     f.mask.count() + (f.rowmap.count() + f.scratch.count()) * 4) + lb_gpu_index_hbm_bytes(p->coarse);
 }
 
 int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out)
@@ -300,6 +389,26 @@ int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out)
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total)
 {
     return handle_reserve(p, n_total, [](lb_gpu_ivf *h, int64_t need) { ivf_grow(h, need, h->has_ids); });
+}
+
+// ---- the row filter (lb_handle.h) ---------------------------------------------------------------------------------------
+int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p) { return filter_nvisible(p); }
+int lb_gpu_ivf_set_filter(lb_gpu_ivf *p, const uint8_t *mask, int64_t n)
+{
+    Lease vis;
+    return filter_set(p, mask, n, visible_builder(p, vis));
+}
+int lb_gpu_ivf_filter_int64(lb_gpu_ivf *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                            int64_t validity_offset, int combine)
+{
+    Lease vis;
+    return filter_column<int64_t>(p, column, n, value, op, validity, validity_offset, combine, visible_builder(p, vis));
+}
+int lb_gpu_ivf_filter_float32(lb_gpu_ivf *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine)
+{
+    Lease vis;
+    return filter_column<float>(p, column, n, value, op, validity, validity_offset, combine, visible_builder(p, vis));
 }
 
 int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false); }
@@ -377,6 +486,14 @@ int lb_gpu_ivf_last_timing(lb_gpu_ivf *p, float ms[4])
     if (!p || !ms) return LB_ERR_INVALID_ARG;
     std::lock_guard<std::mutex> g(p->err_mu);
     std::copy(p->timing, p->timing + 4, ms);
+    return LB_OK;
+}
+
+int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms)
+{
+    if (!p || !ms) return LB_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->err_mu);
+    *ms = p->build_ms;
     return LB_OK;
 }
 

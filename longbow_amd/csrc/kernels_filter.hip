@@ -168,6 +168,11 @@ __global__ __launch_bounds__(CP_THREADS) void compact_scatter_kernel(const uint8
 
 int64_t compact_scratch_words(int64_t n) { return (n + CP_ROWS - 1) / CP_ROWS + 1; }
 
+void launch_compact_offsets(uint32_t *block_counts, int64_t nb, hipStream_t s)
+{
+    hipLaunchKernelGGL(compact_offsets_kernel, dim3(1), dim3(CP_THREADS), 0, s, block_counts, nb);
+}
+
 void launch_compact_mask(const uint8_t *mask, int64_t n, uint32_t *rowmap, uint32_t *scratch, hipStream_t s)
 {
     const int64_t nb = (n + CP_ROWS - 1) / CP_ROWS;
@@ -176,7 +181,7 @@ void launch_compact_mask(const uint8_t *mask, int64_t n, uint32_t *rowmap, uint3
         return;
     }
     hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nb), dim3(CP_THREADS), 0, s, mask, n, scratch);
-    hipLaunchKernelGGL(compact_offsets_kernel, dim3(1), dim3(CP_THREADS), 0, s, scratch, nb);
+    launch_compact_offsets(scratch, nb, s);
     hipLaunchKernelGGL(compact_scatter_kernel, dim3((unsigned)nb), dim3(CP_THREADS), 0, s, mask, n, scratch, rowmap);
 }
 

@@ -1,5 +1,6 @@
 // kernels_ivf.hip -- the IVF-Flat index (ivf.hip; semantics in include/longbow_gpu.h, lb_gpu_ivf_*): the scan of the probed lists,
-// the selection of the k smallest of a query's keys, the plan of a batch, and the stable counting sort that builds the lists.
+// the selection of the k smallest of a query's keys, the plan of a batch, the stable counting sort that builds the lists, and the
+// segmented compaction that builds the visible lists of a row filter.
 //
 // The rows stay in insertion order and a list is an ascending array of row numbers, so the list scan is scan_kernel's walk of a
 // row list (kernels_scan.hip, MAPPED) with a list per (query, probe slot): each lane owns one row and carries that row's f32
@@ -235,6 +236,19 @@ __global__ __launch_bounds__(64) void ivf_plan_kernel(IvfBatch a, unsigned long 
         atomicMax(&stats[2], (unsigned long long)total);
         if (total <= IVF_SELECT_LDS_KEYS) atomicAdd(&stats[3], 1ull);
     }
+}
+
+// every list probed, in list order: what the coarse search's labels are as a set when np == nlist
+__global__ void ivf_all_probes_kernel(int64_t *probes, int64_t total, int np)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) probes[i] = i % np;
+}
+
+void launch_ivf_all_probes(int64_t *probes, int nq, int np, hipStream_t s)
+{
+    const int64_t total = (int64_t)nq * np;
+    if (total <= 0) return;
+    hipLaunchKernelGGL(ivf_all_probes_kernel, dim3((unsigned)std::min<int64_t>((total + 255) / 256, 4096)), dim3(256), 0, s, probes, total, np);
 }
 
 void launch_ivf_plan(const IvfBatch &a, unsigned long long *stats, hipStream_t s)
@@ -551,6 +565,151 @@ hipError_t launch_ivf_sort(const uint32_t *assign, int64_t n, int nlist, uint32_
     hipLaunchKernelGGL(ivf_colscan_kernel, dim3((unsigned)((nlist + 255) / 256)), dim3(256), 0, s, a);
     hipLaunchKernelGGL(ivf_offsets_kernel, dim3(1), dim3(1024), 0, s, off, nlist);
     if (n > 0) hipLaunchKernelGGL(ivf_scatter_kernel, dim3((unsigned)a.nchunks), dim3(64), 0, s, a);
+    return hipSuccess;
+}
+
+// ---- the visible lists: a segmented compaction of the lists under a row mask ------------------------------------------------
+// The n list positions are walked as one array, VIS_ROWS to a workgroup and eight to a thread, so every list keeps its order.
+//   count    bit i of a thread's byte = mask[rows[position i]] != 0 (the only gather); the byte is kept, the workgroup's sum too
+//   offsets  launch_compact_offsets over the workgroups' sums
+//   place    the visible rows of each workgroup go behind those before it; in the same launch one wave per list boundary
+//            counts the visible positions below off[l]: the sum of the workgroups before its own, plus the bits below it in that
+//            workgroup's 64 words (a lane a word)
+// Integer only; no workgroup waits for another.
+constexpr int VIS_THREADS = 256;
+constexpr int VIS_PER = 8;
+constexpr int VIS_ROWS = VIS_THREADS * VIS_PER;
+constexpr int VIS_WORDS = VIS_ROWS / 32; // == 64: one wave reads a workgroup's bits
+
+struct IvfVisible {
+    const uint8_t *mask; // [n]
+    IvfLists L;          // the lists of all n rows
+    int64_t n, nblk;
+    uint32_t *blk;       // [nblk + 1]: visible positions per workgroup, then their exclusive prefix and the total
+    uint32_t *bits;      // [nblk][VIS_WORDS]: position p is bit p % 32 of word p / 32; positions past n are 0
+    uint32_t *voff;      // [nlist + 1]
+    uint32_t *vrows;     // [n]
+};
+
+// the sum of v over the workgroup's four waves, in every thread; `before`: the sum over the waves below this one
+__device__ __forceinline__ uint32_t vis_block_sum(uint32_t wave_total, uint32_t *s_wave, uint32_t &before)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 63) s_wave[wave] = wave_total;
+    __syncthreads();
+    uint32_t tot = 0;
+    before = 0;
+#pragma unroll
+    for (int w = 0; w < VIS_THREADS / 64; w++) {
+        const uint32_t t = s_wave[w];
+        if (w < wave) before += t;
+        tot += t;
+    }
+    return tot;
+}
+
+// the eight rows at positions [base, base + 8), base % 8 == 0 and base + 8 <= n (rows is 32-byte aligned)
+__device__ __forceinline__ void vis_load8(const uint32_t *rows, int64_t base, uint32_t r[VIS_PER])
+{
+    const uint4 a = *reinterpret_cast<const uint4 *>(rows + base), b = *reinterpret_cast<const uint4 *>(rows + base + 4);
+    r[0] = a.x, r[1] = a.y, r[2] = a.z, r[3] = a.w;
+    r[4] = b.x, r[5] = b.y, r[6] = b.z, r[7] = b.w;
+}
+
+__global__ __launch_bounds__(VIS_THREADS) void ivf_visible_count_kernel(IvfVisible a)
+{
+    __shared__ uint32_t s_wave[VIS_THREADS / 64];
+    const int64_t t = (int64_t)blockIdx.x * VIS_THREADS + threadIdx.x, base = t * VIS_PER;
+    uint32_t b = 0;
+    if (base + VIS_PER <= a.n) {
+        uint32_t r[VIS_PER];
+        vis_load8(a.L.rows, base, r);
+#pragma unroll
+        for (int i = 0; i < VIS_PER; i++)
+            if ((int64_t)r[i] < a.n && a.mask[r[i]]) b |= 1u << i;
+    } else {
+        for (int i = 0; i < VIS_PER && base + i < a.n; i++) {
+            const uint32_t r = a.L.rows[base + i];
+            if ((int64_t)r < a.n && a.mask[r]) b |= 1u << i;
+        }
+    }
+    reinterpret_cast<uint8_t *>(a.bits)[t] = (uint8_t)b; // (every thread of the grid: the bytes past n are zero)
+    uint32_t before;
+    const uint32_t tot = vis_block_sum(wave_incl_scan((uint32_t)__popc(b), threadIdx.x & 63), s_wave, before);
+    if (threadIdx.x == 0) a.blk[blockIdx.x] = tot;
+}
+
+// workgroups [0, nblk) place the rows; the ones behind them take four list boundaries each, a wave a boundary
+__global__ __launch_bounds__(VIS_THREADS) void ivf_visible_place_kernel(IvfVisible a)
+{
+    __shared__ uint32_t s_wave[VIS_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if ((int64_t)blockIdx.x >= a.nblk) {
+        const int64_t l = ((int64_t)blockIdx.x - a.nblk) * (VIS_THREADS / 64) + wave;
+        if (l > a.L.nlist) return;
+        const int64_t p = std::min<int64_t>(a.L.off[l], a.n);
+        const int64_t blk = p / VIS_ROWS; // <= nblk
+        const uint32_t w = (uint32_t)(p % VIS_ROWS), lo = (uint32_t)lane * 32u;
+        uint32_t c = 0;
+        if (blk < a.nblk) { // (else p == n at the end of the last workgroup: blk[nblk] is the answer)
+            const uint32_t below = w >= lo + 32u ? 0xffffffffu : w > lo ? (1u << (w - lo)) - 1u : 0u;
+            c = (uint32_t)__popc(a.bits[blk * VIS_WORDS + lane] & below);
+        }
+        c = wave_incl_scan(c, lane);
+        if (lane == 63) a.voff[l] = a.blk[blk] + c;
+        return;
+    }
+    const int64_t t = (int64_t)blockIdx.x * VIS_THREADS + threadIdx.x, base = t * VIS_PER;
+    const uint32_t b = reinterpret_cast<const uint8_t *>(a.bits)[t];
+    const uint32_t c = (uint32_t)__popc(b);
+    const uint32_t incl = wave_incl_scan(c, lane);
+    uint32_t before;
+    (void)vis_block_sum(incl, s_wave, before);
+    if (b == 0) return;
+    uint64_t at = (uint64_t)a.blk[blockIdx.x] + before + incl - c;
+    if (base + VIS_PER <= a.n) {
+        uint32_t r[VIS_PER];
+        vis_load8(a.L.rows, base, r);
+#pragma unroll
+        for (int i = 0; i < VIS_PER; i++)
+            if ((b >> i) & 1u) {
+                if (at < (uint64_t)a.n) a.vrows[at] = r[i];
+                at++;
+            }
+    } else {
+        for (int i = 0; i < VIS_PER; i++)
+            if ((b >> i) & 1u) { // (set only for positions below n)
+                if (at < (uint64_t)a.n) a.vrows[at] = a.L.rows[base + i];
+                at++;
+            }
+    }
+}
+
+static int64_t vis_blocks(int64_t n) { return (n + VIS_ROWS - 1) / VIS_ROWS; }
+static size_t vis_bits_at(int64_t nb) { return (((size_t)nb + 1) * 4 + 15) & ~(size_t)15; } // behind blk, 16-byte aligned
+
+size_t ivf_visible_scratch_bytes(int64_t n)
+{
+    const int64_t nb = vis_blocks(n);
+    return vis_bits_at(nb) + (size_t)nb * VIS_WORDS * 4;
+}
+
+hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, void *scratch, uint32_t *voff, uint32_t *vrows, hipStream_t s)
+{
+    if (n <= 0) return hipMemsetAsync(voff, 0, ((size_t)L.nlist + 1) * 4, s);
+    IvfVisible a{};
+    a.mask = mask;
+    a.L = L;
+    a.n = n;
+    a.nblk = vis_blocks(n);
+    a.blk = static_cast<uint32_t *>(scratch);
+    a.bits = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + vis_bits_at(a.nblk));
+    a.voff = voff;
+    a.vrows = vrows;
+    const int64_t bounds = ((int64_t)L.nlist + 1 + VIS_THREADS / 64 - 1) / (VIS_THREADS / 64);
+    hipLaunchKernelGGL(ivf_visible_count_kernel, dim3((unsigned)a.nblk), dim3(VIS_THREADS), 0, s, a);
+    launch_compact_offsets(a.blk, a.nblk, s);
+    hipLaunchKernelGGL(ivf_visible_place_kernel, dim3((unsigned)(a.nblk + bounds)), dim3(VIS_THREADS), 0, s, a);
     return hipSuccess;
 }
 

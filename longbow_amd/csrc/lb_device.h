@@ -690,6 +690,8 @@ void launch_and_bytes(uint8_t *dst, const uint8_t *src, int64_t n, hipStream_t s
 // compact_scratch_words(n) u32 and ends with the visible-row count at [words-1]
 int64_t compact_scratch_words(int64_t n);
 void launch_compact_mask(const uint8_t *mask, int64_t n, uint32_t *rowmap, uint32_t *scratch, hipStream_t s);
+// its middle step alone: counts[0, nb) -> their exclusive prefix in place, counts[nb] = the total (one workgroup)
+void launch_compact_offsets(uint32_t *counts, int64_t nb, hipStream_t s);
 // reciprocal-rank fusion of two ranked id lists per query (kernels_filter.hip)
 void launch_rrf(int64_t nq, int kd, const int64_t *dense, int ks, const int64_t *sparse, int k, int limit,
                 int64_t *out_ids, float *out_scores, hipStream_t s);

@@ -1,5 +1,5 @@
-// lb_handle.h -- the host shell of a code-index handle (lb_gpu_pq, lb_gpu_bq, lb_gpu_sq8): what the three C-ABI translation
-// units pq.hip, bq.hip and sq8.hip share beyond lb_host.h.  Header-only, nothing exported.
+// lb_handle.h -- the host shell of a code-index handle (lb_gpu_pq, lb_gpu_bq, lb_gpu_sq8) and of lb_gpu_ivf: what the C-ABI
+// translation units pq.hip, bq.hip, sq8.hip and ivf.hip share beyond lb_host.h.  Header-only, nothing exported.
 //
 // The rules every entry point of these handles keeps:
 //   * nothing but an lb_status leaves the library: the body of an entry point runs inside guard();
@@ -314,8 +314,14 @@ inline int filter_fits(CodeHandle *h, int64_t rows)
     return LB_ERR_UNSUPPORTED;
 }
 
+// What a handle derives from the filter beyond the list (the IVF handle's visible lists): built(s) runs after rebuild and before
+// the filter is on, enqueues on s, and throws like any body of guard(); the code handles have nothing to build.
+struct NothingToBuild {
+    void operator()(hipStream_t) const {}
+};
+
 // lb_gpu_*_set_filter: n bytes of the host, or nullptr to clear
-inline int filter_set(FilteredHandle *h, const uint8_t *mask, int64_t n)
+template <class Built = NothingToBuild> int filter_set(FilteredHandle *h, const uint8_t *mask, int64_t n, Built &&built = Built())
 {
     if (!h) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
@@ -332,14 +338,16 @@ inline int filter_set(FilteredHandle *h, const uint8_t *mask, int64_t n)
         f.on = false; // a failure from here on leaves the handle without a filter, not with half of one
         if (n > 0) LB_HIP(hipMemcpy(f.mask.get(), mask, (size_t)n, hipMemcpyHostToDevice));
         f.rebuild(n, h->stream);
+        built(h->stream);
         f.on = true;
         return LB_OK;
     });
 }
 
 // lb_gpu_*_filter_int64 / _float32: the predicate evaluated on the device into the mask (launch_match_*)
-template <class T>
-int filter_column(FilteredHandle *h, const T *column, int64_t n, T value, int op, const uint8_t *validity, int64_t voff, int combine)
+template <class T, class Built = NothingToBuild>
+int filter_column(FilteredHandle *h, const T *column, int64_t n, T value, int op, const uint8_t *validity, int64_t voff, int combine,
+                  Built &&built = Built())
 {
     if (!h || op < 0 || op > 5 || voff < 0) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
@@ -370,6 +378,7 @@ int filter_column(FilteredHandle *h, const T *column, int64_t n, T value, int op
             else launch_match_float32(dcol.as<float>(), n, (float)value, op, d_val, voff, f.mask.get(), comb, s);
         }
         f.rebuild(n, s);
+        built(s);
         f.on = true;
         return LB_OK;
     });

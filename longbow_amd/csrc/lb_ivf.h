@@ -30,6 +30,8 @@ struct IvfBatch {
 constexpr int IVF_MAX_NLIST = 65536;
 constexpr uint32_t IVF_SELECT_LDS_KEYS = 16384; // a query with at most this many scanned rows is selected from an LDS copy
 
+// probes[q][p] = p: every list, for a search that probes them all without asking the coarse index
+void launch_ivf_all_probes(int64_t *probes, int nq, int np, hipStream_t s);
 // seg of every query; stats (u64[4], zero before a search's first batch): [1] += P_q, [2] = max P_q, [3] += P_q fits LDS
 void launch_ivf_plan(const IvfBatch &a, unsigned long long *stats, hipStream_t s);
 // keys[q][seg[q][p] + i] = entry of the i-th row of the p-th probed list; maxlen: the longest list of the handle
@@ -43,5 +45,12 @@ void launch_ivf_narrow(const int64_t *labels, int64_t n, uint32_t *assign, hipSt
 // Returns the error of the memset that clears hist (nothing is launched then).
 size_t ivf_sort_hist_words(int64_t n, int nlist);
 hipError_t launch_ivf_sort(const uint32_t *assign, int64_t n, int nlist, uint32_t *hist, uint32_t *off, uint32_t *rows, hipStream_t s);
+
+// The visible lists of a row filter: visible list l is the rows of L's list l whose mask byte is non-zero, in the same order.
+// voff[nlist + 1] and vrows[voff[nlist]] (room for n) are written, voff[nlist] being the number of visible rows; scratch holds
+// ivf_visible_scratch_bytes(n) bytes, 16-byte aligned.  Three launches, or with n == 0 the memset of voff alone, whose error is
+// returned.
+size_t ivf_visible_scratch_bytes(int64_t n);
+hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, void *scratch, uint32_t *voff, uint32_t *vrows, hipStream_t s);
 
 } // namespace lb

@@ -5,7 +5,8 @@ A coarse partition of the rows lets a query skip most of them.  Nothing is appro
 probed lists the result is the exact k-NN among their rows, bit for bit in the reference's distance arithmetic, and with every
 list probed it equals gpu.Index.Search.  include/longbow_gpu.h states the semantics.
 
-  IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats
+  IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats, and the
+                 row filter (set_filter / filter_column / nvisible)
   IVFFlatIndex   the reference's PluggableVectorIndex surface over it: rows are buffered until Build()
   train          TrainKMeans on the GPU (pq.train with M = 1): nlist centroids of f32 rows
 """
@@ -15,6 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib, pq
+from ._rowfilter import RowFilterMixin
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 MAX_NLIST = 65536
@@ -44,8 +46,10 @@ def train_device(n, d_vectors, dims, nlist, max_iter=20, seed=0, init_rows=None,
     return np.frombuffer(blob[12:], "<f4").reshape(nlist, dims).copy()
 
 
-class IVFFlat:
-    """lb_gpu_ivf: metric 0 L2 / 1 cosine / 2 dot, order 0 SEQ / 1 UNROLL4, centroids f32 [nlist, dims]"""
+class IVFFlat(RowFilterMixin):
+    """lb_gpu_ivf: metric 0 L2 / 1 cosine / 2 dot, order 0 SEQ / 1 UNROLL4, centroids f32 [nlist, dims].  Under a row filter
+    (RowFilterMixin) the probes stay as they are and a search sees the visible rows of the probed lists alone."""
+    _prefix = "lb_gpu_ivf"
 
     def __init__(self, centroids, metric=0, order=0, device=0, lib=None):
         self._h = None  # (Close() and __del__ find this when creation fails below)
@@ -141,6 +145,12 @@ class IVFFlat:
         out = (C.c_float * 4)()
         self._check(self._lib.lb_gpu_ivf_last_timing(self._h, out))
         return tuple(float(x) for x in out)
+
+    def last_build_timing(self):
+        """ms of the last profiled build of the visible lists (a filter call or an add under a filter): its launches alone"""
+        out = C.c_float(0)
+        self._check(self._lib.lb_gpu_ivf_last_build_timing(self._h, C.byref(out)))
+        return float(out.value)
 
     def Close(self):
         if self._h:
@@ -245,6 +255,15 @@ class IVFFlatIndex:
 
     def last_search_stats(self):
         return self._built().last_search_stats()
+
+    def set_filter(self, mask):
+        self._built().set_filter(mask)
+
+    def filter_column(self, column, value, op, valid=None, combine=False, validity_offset=0):
+        self._built().filter_column(column, value, op, valid=valid, combine=combine, validity_offset=validity_offset)
+
+    def nvisible(self):
+        return self._built().nvisible()
 
     def Save(self, path):
         raise NotImplementedError("ivf_flat: Save is not implemented (the reference's writes a marker file only)")

@@ -1,7 +1,7 @@
-"""Filtered searches on the BQ, SQ8 and PQ indexes: search time against the share of visible rows, one JSON line.
+"""Filtered searches on the BQ, SQ8, PQ and IVF-Flat indexes: search time against the share of visible rows, one JSON line.
 
-    python tools/code_filter_bench.py --index bq|sq8|pq [--rows 1000000] [--dim 768] [--k 100] [--nq 1,64,1024]
-                                      [--visible-pct 100,50,10] [--runs 3] [--reps 10]
+    python tools/code_filter_bench.py --index bq|sq8|pq|ivf [--rows 1000000] [--dim 768] [--k 100] [--nq 1,64,1024]
+                                      [--visible-pct 100,50,10] [--runs 3] [--reps 10] [--nlist 256] [--nprobe 8,32]
 
 BQ and SQ8: rows are drawn on the device (uniform in [-0.5, 0.5)) and added as vectors.  PQ (defaults --rows 10000000,
 --nq 1,2,16, --visible-pct 100,50,10,1; M = dim / 8): code bytes uniform in [0, 256) are drawn on the device and added with
@@ -12,6 +12,14 @@ results are on the device); the figure is the median of the runs, and the runs t
 a comparison between two builds has to clear).  The runs of the shares alternate.  With --visible-pct 100 alone no filter call is
 made, so a copy of this file under tools/ of an older checkout times that checkout's unfiltered searches the same way.
 The shader clock is read before and after.
+
+IVF-Flat (defaults --nq 1,8, --nprobe 8,32, --visible-pct 100,50,10,1; rows, queries and centroids as tools/ivf_bench.py): here
+100 % is a filter too, the all-visible one, because the comparison is another: per (share, nq, nprobe) the search under the
+filter, and beside it, in the same run, the same handle with the filter cleared, which is the search of a handle that never had
+one.  Each is the p50 of `reps` searches with the HIP-event times of its steps from one more, profiled, search (probes, plan,
+list scan, selection) and the rows it scanned.  Per share also the filter call: its wall time (the mask comes from host
+memory), the build of the visible lists alone by HIP events, and the bytes that build moves (per list position: the row read
+twice, a mask byte gathered, a bit written and read; per visible row 4 bytes written).
 """
 import argparse
 import json
@@ -23,10 +31,10 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from longbow_amd import bq, gpu, pq, sq8  # noqa: E402
+from longbow_amd import _lib, bq, gpu, ivf, pq, sq8  # noqa: E402
 
 DEFAULTS = {"bq": (1_000_000, "1,64,1024", "100,50,10"), "sq8": (1_000_000, "1,64,1024", "100,50,10"),
-            "pq": (10_000_000, "1,2,16", "100,50,10,1")}  # rows, nq, visible-pct
+            "pq": (10_000_000, "1,2,16", "100,50,10,1"), "ivf": (1_000_000, "1,8", "100,50,10,1")}  # rows, nq, visible-pct
 
 
 def p50(fn, reps):
@@ -46,9 +54,84 @@ def clock_mhz():
         return None
 
 
+def ivf_main(a, nqs, pcts):
+    lib = _lib.require_gpu(0)
+    nprobes = [int(x) for x in a.nprobe.split(",")]
+    out = {"index": "ivf", "rows": a.rows, "dim": a.dim, "nlist": a.nlist, "k": a.k, "runs": a.runs, "reps": a.reps,
+           "shader_clock_mhz_before": clock_mhz()}
+    nqmax = max(nqs)
+    X = torch.empty((a.rows, a.dim), dtype=torch.float32, device="cuda")
+    Q = torch.empty((nqmax, a.dim), dtype=torch.float32, device="cuda")
+    _lib.check(lib.lb_gpu_fill_uniform_device(0, X.data_ptr(), a.rows * a.dim, 1, 0, None))
+    _lib.check(lib.lb_gpu_fill_uniform_device(0, Q.data_ptr(), nqmax * a.dim, 2, 0, None))
+    torch.cuda.synchronize()
+    h = ivf.IVFFlat(ivf.train_device(a.rows, X.data_ptr(), a.dim, a.nlist, max_iter=0))
+    h.reserve(a.rows)
+    h.add_device(a.rows, X.data_ptr())
+    del X
+    rng = np.random.default_rng(0)
+    masks = {p: np.ones(a.rows, np.uint8) if p == 100 else (rng.random(a.rows) < p / 100.0).astype(np.uint8) for p in pcts}
+    D = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
+    L = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+
+    def cell(nq, nprobe):
+        run = lambda: h.search_device(nq, Q.data_ptr(), a.k, nprobe, D.data_ptr(), L.data_ptr())  # noqa: E731
+        ms = p50(run, a.reps)
+        h.set_profiling(True)
+        run()
+        h.set_profiling(False)
+        st = h.last_search_stats()
+        return {"ms": ms, "steps_ms": list(h.last_timing()), "rows_scanned": st[1], "max_rows_per_query": st[2], "selected_from_lds": st[3]}
+
+    grid = [(nq, nprobe) for nq in nqs for nprobe in nprobes]
+    runs = {p: {"filter_call_ms": [], "build_ms": [], "cells": {g: {"filtered": [], "unfiltered": []} for g in grid}} for p in pcts}
+    for _ in range(a.runs):
+        for p in pcts:
+            r = runs[p]
+            h.set_filter(None)
+            for g in grid:
+                r["cells"][g]["unfiltered"].append(cell(*g))
+            h.set_filter(masks[p])  # (warm: the buffers exist from here on)
+            h.set_filter(None)
+            t0 = time.perf_counter()
+            h.set_filter(masks[p])
+            r["filter_call_ms"].append((time.perf_counter() - t0) * 1e3)
+            h.set_profiling(True)
+            h.set_filter(masks[p])
+            h.set_profiling(False)
+            r["build_ms"].append(h.last_build_timing())
+            r["visible_rows"] = h.nvisible()
+            for g in grid:
+                r["cells"][g]["filtered"].append(cell(*g))
+    med = lambda xs: float(np.median(xs))  # noqa: E731
+
+    def summary(cs):
+        return {"ms": med([c["ms"] for c in cs]), "runs_ms": [c["ms"] for c in cs],
+                "steps_ms": [med([c["steps_ms"][i] for c in cs]) for i in range(4)],
+                "rows_scanned": cs[-1]["rows_scanned"], "max_rows_per_query": cs[-1]["max_rows_per_query"],
+                "selected_from_lds": cs[-1]["selected_from_lds"]}
+
+    out["filter"] = {}
+    for p in pcts:
+        r = runs[p]
+        build_bytes = a.rows * (4 + 1 + 4) + a.rows // 4 + r["visible_rows"] * 4
+        out["filter"][f"visible_{p}"] = {
+            "visible_rows": r["visible_rows"], "filter_call_ms": med(r["filter_call_ms"]), "filter_call_runs_ms": r["filter_call_ms"],
+            "build_ms": med(r["build_ms"]), "build_runs_ms": r["build_ms"], "build_bytes": build_bytes,
+            "build_gb_per_s": build_bytes / max(med(r["build_ms"]), 1e-6) / 1e6,
+            "search": {f"nq_{nq}_nprobe_{nprobe}": {k: summary(v) for k, v in r["cells"][(nq, nprobe)].items()} for nq, nprobe in grid}}
+    out["hbm_bytes"] = h.hbm_bytes
+    out["shader_clock_mhz_after"] = clock_mhz()
+    print(json.dumps(out))
+    h.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--index", choices=("bq", "sq8", "pq"), required=True)
+    ap.add_argument("--index", choices=("bq", "sq8", "pq", "ivf"), required=True)
+    ap.add_argument("--nlist", type=int, default=256)
+    ap.add_argument("--nprobe", default="8,32")
     ap.add_argument("--rows", type=int, default=None)
     ap.add_argument("--dim", type=int, default=768)
     ap.add_argument("--k", type=int, default=100)
@@ -62,6 +145,8 @@ def main():
     a.visible_pct = a.visible_pct or DEFAULTS[a.index][2]
     nqs = [int(x) for x in a.nq.split(",")]
     pcts = [int(x) for x in a.visible_pct.split(",")]
+    if a.index == "ivf":
+        return ivf_main(a, nqs, pcts)
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
     if a.index == "pq":
