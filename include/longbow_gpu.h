@@ -70,7 +70,7 @@ const char *lb_gpu_status_string(int status);
  * the reason.  dim > LB_MAX_DIM -> NULL / LB_ERR_UNSUPPORTED (the kernels stage one query row in LDS;
  * the reference has no cap, embedding widths in practice are <= 4096). */
 #define LB_MAX_DIM 8192
-#define LB_MAX_K 2048 /* largest k of any search entry point (LB_ERR_UNSUPPORTED beyond) */
+#define LB_MAX_K 2048 /* largest k of a search entry point (LB_ERR_UNSUPPORTED beyond); lb_gpu_pq_search* alone take k up to 4096 */
 lb_gpu_index *lb_gpu_index_new(int device, int dim, int metric, int *out_status);
 
 /* Close (faiss_gpu.go:147-167): frees HBM; idempotent on NULL.  Must not race with any other call on the same

@@ -4,8 +4,7 @@
 // The rules every entry point of these handles keeps:
 //   * nothing but an lb_status leaves the library: the body of an entry point runs inside guard();
 //   * a pooled buffer (Lease) that a stream-enqueuing body uses is declared OUTSIDE guard() and the stream is passed to it: an
-//     error drains the stream before the buffer goes back to the pool, where a concurrent call could lease it (bq.hip and
-//     sq8.hip; pq.hip's entry points other than its host encode and decode are older and lease inside their bodies);
+//     error drains the stream before the buffer goes back to the pool, where a concurrent call could lease it;
 //   * searches and reads take `mu` shared; adds, reserve and whatever changes the row filter take it alone.
 #pragma once
 #include "../../include/longbow_gpu.h"

@@ -19,7 +19,7 @@ def next_pow2(v):
 
 
 def plan(n, k):
-    """lb_gpu_pq_search_device_ctx's sampled-threshold plan -> (samp_count, m, stride, cap); samp_count 0 = bootstrap"""
+    """pq.hip's sample_plan, the sampled-threshold plan of a PQ search -> (samp_count, m, stride, cap); samp_count 0 = bootstrap"""
     cap = max(8192, 4 * next_pow2(k))
     if 65536 <= n < (1 << 32):
         cap_s = max(16384, cap)

@@ -1,8 +1,8 @@
 """Every ADC search and PQ codec kernel form against the oracle, bit for bit, with lb_gpu_pq_last_search_stats proving
 which form served each query (a results-only test cannot see a broken prefilter: the exact redo would hide it).
 
-Which form a batch takes (launchers in kernels_pq2.hip, ladders in pq.hip: scan_quad / scan_pair / scan_query), for a
-sampled plan with the prefilter on and a corpus of >= 4096 rows:
+Which form a batch takes (launchers in kernels_pq2.hip, the walk in pq.hip: PqSearch::walk / sampled_group /
+prefilter_group), for a sampled plan with the prefilter on and a corpus of >= 4096 rows:
 
     M            four-query form              two-query form               single form
     16 32 48 64  <M/16, 16>: tables M KiB +   <M/16, 16, 2>: M/2 + M KiB   <M/16, 16>: M/4 + M KiB
@@ -68,6 +68,8 @@ def test_expected_stats_examples():
     assert expected_stats(128, 7) == (7, 0, 0, 7, 0, 0)
     assert expected_stats(16, 4) == (4, 4, 0, 0, 0, 0)
     assert expected_stats(20, 2) == (2, 0, 0, 2, 0, 0)
+    assert expected_stats(16, 6) == (6, 4, 2, 0, 0, 0)
+    assert expected_stats(128, 3) == (3, 0, 0, 3, 0, 0)
 
 
 def _encoder(cb, codes=None):
@@ -119,14 +121,15 @@ def grid_case(oracle, M, k=10, nq=7):
 
 @pytest.mark.parametrize("M", [16, 32, 48, 64, 80, 96, 112, 128, 144, 159, 20, 100])
 def test_form_grid(oracle, M):
-    """nq = 1, 2, 4, 7 at every M: oracle equality, batch == single == prefilter off, the split of the module docstring
-    asserted exactly, and no query redone (the precondition is asserted in grid_case, not assumed)"""
+    """nq = 1 .. 7 at every M (every group boundary: pair + single, quad + single, quad + pair, quad + pair + single):
+    oracle equality, batch == single == prefilter off, the split of the module docstring asserted exactly, and no query
+    redone (the precondition is asserted in grid_case, not assumed)"""
     gpu_or_skip()
     k = 10
     cb, codes, Q, want = grid_case(oracle, M, k)
     enc = _encoder(cb, codes)
     assert enc.ntotal == N_GRID and N_GRID % 64 != 0
-    for nq in (1, 2, 4, 7):
+    for nq in (1, 2, 3, 4, 5, 6, 7):
         lab, dist = enc.Search(Q[:nq], k)
         stats = enc.last_search_stats
         _assert_lists(lab, dist, want, (M, nq))
