@@ -2,10 +2,10 @@
 """bench.py -- the reference's headline metric on MI355X.
 
 Metric (BASELINE.json): k-NN queries/sec at batch = 1024, k = 100 on 1M x 768 f32 (cosine, brute force),
-plus p50 single-query latency.  One "step" = one batch of 1024 queries searched over the whole job's corpus,
+plus (--full) p50 single-query latency.  One "step" = one batch of 1024 queries searched over the whole job's corpus,
 inputs resident in HBM.
 
-  N = 1 (default)      BASELINE config 2: 1M x 768 cosine on one GPU.  Secondary legs on the same line:
+  N = 1 (default)      BASELINE config 2: 1M x 768 cosine on one GPU.  With --full, secondary legs on the same line:
                        split-bf16 candidates, p50 latency + scan roofline, batch sweep, PQ/ADC (config 4,
                        100M x m=96), filtered hybrid (config 5, one GPU's share), oracle parity, CPU baseline.
   N > 1, weak          (default) the corpus grows with N: N x 1M rows with ids 0 .. N*1M-1, partitioned by the
@@ -21,9 +21,17 @@ One rank per GPU.  `python bench.py --gpus N` with no WORLD_SIZE in the environm
 (torch.distributed.run as a child process, BEFORE this process imports torch or touches the GPU) and relays rank 0's
 JSON line; under `python -m torch.distributed.run ... bench.py --gpus N` it is one of the ranks.  The exchange is the
 library's own RCCL path (lb_gpu_comm_*, LB_BENCH_COMM=lib, default; =torch: torch.distributed's all-gather).
-Every run also carries a `strong_c3` leg (BASELINE config 3: a fixed 10M x 768 dot corpus over the N GPUs).
-Prints ONE JSON line on rank 0.  --dump-outputs DIR also writes the headline's last timed step (labels and distances of
-every query) as DIR/*.npy; the inputs are generated from fixed seeds, so two builds can be compared output for output.
+Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing else: it builds the index, warms up, times the steps and prints
+the line (metric, value, ms_per_step, the configuration, and the roofline of the timed steps' own HIP events).  --full
+adds everything else to the same line: the chip's clock behind the steps, the other candidate modes, single-query
+latency, the batch sweep, concurrent callers, the oracle parity gate, the CPU baseline, the `strong_c3` leg (BASELINE
+config 3: a fixed 10M x 768 dot corpus over the N GPUs) and configs 1, 4 and 5.  --no-fast, --no-legs, --no-cpu-baseline
+and --cpu-queries trim a --full run; without --full there is nothing for them to trim.
+
+--dump-outputs DIR also writes the headline's last timed step (labels and distances of every query) as DIR/*.npy; the
+inputs are generated from fixed seeds, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -87,7 +95,7 @@ def rank_ids(part, rank, global_rows):
 
 
 # ---------------------------------------------------------------------------------------------------
-# secondary legs (N = 1 only)
+# secondary legs (--full, N = 1 only)
 # ---------------------------------------------------------------------------------------------------
 def route_roof_ms(kind, form, B, rows):
     """time the route's contraction needs at the dense MFMA peak of its operand type, and what it is called"""
@@ -591,10 +599,14 @@ def main():
     ap.add_argument("--rows", type=int, default=N_ROWS, help="rows per GPU (weak) / global rows (strong: default 10M)")
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-fast", action="store_true", help="skip the candidate-mode legs (auto path, split-bf16 image)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the secondary legs (sweep, strong C3, PQ, filtered hybrid)")
-    ap.add_argument("--cpu-queries", type=int, default=0, help="CPU baseline sample size (0 = 16 per core)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, run every other measurement and check (clock probe, candidate modes, latency, "
+                         "sweep, concurrent callers, oracle parity, CPU baseline, strong C3, configs 1, 4 and 5)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-fast", action="store_true", help="with --full: skip the candidate-mode legs (auto path, split-bf16 image)")
+    ap.add_argument("--no-legs", action="store_true",
+                    help="with --full: skip the secondary legs (sweep, strong C3, PQ, filtered hybrid)")
+    ap.add_argument("--cpu-queries", type=int, default=0, help="with --full: CPU baseline sample size (0 = 16 per core)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step returned (labels, distances) to DIR/<name>.npy, for output-for-output "
                          "comparison of two builds on the same seeded inputs")
@@ -669,7 +681,7 @@ def main():
     result = {
         "metric": metric_name, "value": round(value, 1),
         "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling,
+        "ms_per_step": round(ms_per_step, 4), "higher_is_better": True, "scaling": args.scaling, "full": args.full,
         "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": workload, "dim": DIM, "batch": B, "k": K, "metric": "dot" if strong else "cosine",
                    "global_rows": global_rows, "candidate_mode": "LB_CAND_F32_MFMA (strict; the library default is AUTO: auto_path leg)",
@@ -696,14 +708,16 @@ def main():
             "hbm_algorithmic_bytes_per_step": bytes_per_step,
             "hbm_frac_of_8TBs_at_step_rate": round(bytes_per_step / (ms_per_step * 1e-3) / 1e9 / PEAK_HBM_GBS, 4),
         }
+    # ---- everything below this line is --full: a plain run has its line and goes straight to the print ----------
     # the chip's clock state right behind the timed steps (the same search runs 1.67-1.95 ms by clock state on one box)
-    try:
-        mhz = float(lib.lb_gpu_shader_clock_mhz(local_rank, 2000))
-        result["shader_clock_mhz_after_steps"] = round(mhz, 1) if mhz > 0 else None
-    except Exception:
-        result["shader_clock_mhz_after_steps"] = None
+    if args.full:
+        try:
+            mhz = float(lib.lb_gpu_shader_clock_mhz(local_rank, 2000))
+            result["shader_clock_mhz_after_steps"] = round(mhz, 1) if mhz > 0 else None
+        except Exception:
+            result["shader_clock_mhz_after_steps"] = None
 
-    single = world == 1 and not use_dist and not strong and X is not None
+    single = args.full and world == 1 and not use_dist and not strong and X is not None
 
     def mode_leg(mode, note):
         """the same batch in another candidate mode: identical results required, own roofline"""
@@ -881,7 +895,7 @@ def main():
     if hasattr(searcher, "close"):
         searcher.close()
     searcher = None
-    if not args.no_legs and not strong:
+    if args.full and not args.no_legs and not strong:
         idx.Close()
         idx = None
         X = None

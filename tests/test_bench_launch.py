@@ -29,6 +29,15 @@ def test_launcher_command_is_built_before_anything_touches_the_gpu():
     assert cmd[i + 1:] == ["--gpus", "8", "--steps", "3", "--warmup", "1"]  # the ranks get the caller's arguments
 
 
+def test_full_is_an_option_and_reaches_the_ranks():
+    r = run(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"], {"LB_BENCH_LAUNCH_ECHO": "1"})
+    assert r.returncode == 0, r.stderr
+    cmd = json.loads(r.stdout.strip().splitlines()[-1])["cmd"]
+    assert cmd[cmd.index(os.path.join(ROOT, "bench.py")) + 1:] == ["--gpus", "2", "--steps", "3", "--warmup", "1", "--full"]
+    h = run(["--help"], {})
+    assert h.returncode == 0 and "--full" in h.stdout
+
+
 def test_launcher_relays_the_childs_failure():
     """no GPU here: every rank fails (GPU not available / no HIP device) and the launcher exits non-zero instead of
     printing a line"""

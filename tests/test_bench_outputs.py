@@ -1,5 +1,5 @@
 """bench.py --dump-outputs DIR: what the timed path returned in its last step, as DIR/<name>.npy (float32 / float64, at most
-64 MB in all), and --steps as the number of timed steps behind ms_per_step."""
+64 MB in all), --steps as the number of timed steps behind ms_per_step, and what a plain run's line holds beside one with --full."""
 import json
 import os
 import subprocess
@@ -65,7 +65,7 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     from tests.gpu_util import gpu_or_skip
     gpu_or_skip()
     out = tmp_path / "dump"
-    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "20000", "--batch", "64", "--no-legs", "--no-fast",
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "20000", "--batch", "64", "--full", "--no-legs", "--no-fast",
               "--no-cpu-baseline", "--dump-outputs", str(out)], timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -76,3 +76,30 @@ def test_bench_dumps_the_last_timed_step(tmp_path):
     assert lab.shape == dist.shape == (64, 100)
     assert np.all((lab >= 0) & (lab < 20000) & (lab == np.round(lab)))
     assert np.all(np.diff(dist, axis=1) >= 0)
+
+
+# what a run without --full prints: the headline, its configuration, and what the timed steps' own HIP events give
+PLAIN_KEYS = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "full",
+              "vs_baseline", "dtype", "data", "config", "fallback_queries", "device_ms_per_step", "roofline"}
+
+
+@pytest.mark.gpu
+def test_a_plain_run_prints_the_headline_and_runs_no_other_leg(tmp_path):
+    from tests.gpu_util import gpu_or_skip
+    gpu_or_skip()
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", "20000", "--batch", "64", "--dump-outputs", str(out)],
+             timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    res = json.loads(lines[0])
+    assert set(res) <= PLAIN_KEYS, sorted(set(res) - PLAIN_KEYS)  # no parity, latency, sweep, CPU baseline, strong C3, configs 1 / 4 / 5
+    assert res["full"] is False and res["steps"] == 3 and res["warmup"] == 1
+    assert res["metric"].startswith("k-NN queries/sec") and res["unit"] == "queries/s" and res["dtype"] == "f32"
+    assert res["higher_is_better"] is True and res["ms_per_step"] > 0
+    # value is in queries over 1M rows; ms_per_step is printed to 1e-4 ms and a step of several launches takes over 0.02 ms
+    assert res["value"] == pytest.approx(64 * (20000 / 1e6) * 1e3 / res["ms_per_step"], rel=5e-3)
+    lab, dist = np.load(out / "labels.npy"), np.load(out / "distances.npy")  # the dump does not wait for --full
+    assert lab.dtype == np.float64 and dist.dtype == np.float32 and lab.shape == dist.shape == (64, 100)
+    assert np.all((lab >= 0) & (lab < 20000) & (lab == np.round(lab))) and np.all(np.diff(dist, axis=1) >= 0)

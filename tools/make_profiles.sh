@@ -11,13 +11,13 @@ OUT=$ROOT/gpurun_out/prof_$R
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 echo "[profiles] kernel stats (whole bench line, all legs)"
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --steps 8 --warmup 2 --no-cpu-baseline > $OUT/stats.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o bench -- python3 $ROOT/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline > $OUT/stats.log 2>&1
 echo "[profiles] FETCH_SIZE"
-rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o bench -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-legs > $OUT/fetch.log 2>&1
+rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o bench -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-legs > $OUT/fetch.log 2>&1
 echo "[profiles] WRITE_SIZE"
-rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o bench -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-legs > $OUT/write.log 2>&1
+rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/write -o bench -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-legs > $OUT/write.log 2>&1
 echo "[profiles] SQ busy / LDS conflicts"
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $OUT/sq -o bench -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fast --no-legs > $OUT/sq.log 2>&1 || echo "[profiles] SQ pass failed (counter set not available); see $OUT/sq.log"
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE --kernel-trace --output-format csv -d $OUT/sq -o bench -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fast --no-legs > $OUT/sq.log 2>&1 || echo "[profiles] SQ pass failed (counter set not available); see $OUT/sq.log"
 echo "[profiles] PQ / ADC (config 4): kernel stats, SQ counters, FETCH_SIZE"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/pq_stats -o pq -- python3 $ROOT/tools/bench_pq.py 100 1 > $OUT/pq_stats.log 2>&1
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAIT_INST_LDS --kernel-trace --output-format csv -d $OUT/pq_sq1 -o pq -- python3 $ROOT/tools/bench_pq.py 100 1 > $OUT/pq_sq1.log 2>&1 || echo "[profiles] pq_sq1 failed"

@@ -12,5 +12,5 @@ echo "mempath rc=$?" >> gpurun_out/progress_final.txt
 timeout -k 10 500 python tools/route_grid.py > gpurun_out/route_grid_final.txt 2>&1
 echo "route grid rc=$?" >> gpurun_out/progress_final.txt
 unset LB_GPU_SO
-timeout -k 10 600 python bench.py > gpurun_out/r3_bench_final.log 2> gpurun_out/r3_bench_final.err
+timeout -k 10 600 python bench.py --full > "${TMPDIR:-/tmp}/r3_bench_final.log" 2> "${TMPDIR:-/tmp}/r3_bench_final.err"
 echo "bench rc=$?" >> gpurun_out/progress_final.txt

@@ -49,7 +49,7 @@ fetch, write = counter_sums("fetch"), counter_sums("write")
 traffic = {"source": f"profiles/{R}_pmc_hbm_traffic.csv (rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE, separate passes; "
                      "FETCH corrected x2 per MI355X_MICROARCH.md)",
            "note": "per-launch average over a batch's gemm launches (like roofline.achieved); counts L2 misses incl. Infinity-Cache hits"}
-lines = ["# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of: bench.py --steps 2 --warmup 1 --no-cpu-baseline",
+lines = ["# rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of: bench.py --full --steps 2 --warmup 1 --no-cpu-baseline",
          "# FETCH_SIZE is in KB and counts 1/2 of the bytes of wide coalesced reads on gfx950 (MI355X_MICROARCH.md, HBM): corrected = KB*1024*2",
          "kernel,launches,fetch_bytes_corrected_per_launch,write_bytes_per_launch,largest_launch_fetch_bytes_corrected"]
 for k in sorted(set(fetch) | set(write)):
@@ -90,7 +90,7 @@ if f:
         c = per[d]
         grid, dur = meta[d]
         out = ["rocprofv3 --pmc " + " ".join(sorted(c)),
-               "largest gemm_filter_kernel launch of a batch (bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-fast)"]
+               "largest gemm_filter_kernel launch of a batch (bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-fast)"]
         out += [f"{k} = {int(v)}" for k, v in sorted(c.items())]
         out += [f"dur = {dur}", f"grid = {grid}"]
         if dur > 0 and "SQ_BUSY_CYCLES" in c:
