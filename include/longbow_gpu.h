@@ -672,6 +672,76 @@ int lb_gpu_ivf_last_timing(lb_gpu_ivf *p, float ms[4]);
  * visible lists: *ms is the last such build's time (tools/code_filter_bench.py --index ivf) */
 int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms);
 
+/* ---- IVF-PQ: exact ADC k-NN over the codes of the probed lists ---------------------------------
+ * The coarse partition of lb_gpu_ivf_* over the codes of lb_gpu_pq_*: a query skips most rows, and a row costs M bytes instead of
+ * 4 * dims.  Nothing is approximate beyond the PQ codes themselves and WHICH lists are probed: given the codes and the probed
+ * lists the result is the exact ADC k-NN among their rows, bit for bit in the reference's BuildADCTable / ADCDistanceBatch
+ * arithmetic.
+ * A handle has PQ codebooks (the reference's serialised blob, as for lb_gpu_pq_new and with its limits: K = 256, M * 1024 bytes
+ * fit LDS, dims <= LB_MAX_DIM), nlist centroids C (f32 [nlist][dims], given by the caller), an accumulation order for the coarse
+ * quantiser (0 SEQ, 1 UNROLL4, as lb_gpu_index_set_order; fixed at creation because it decides which list a row goes to) and
+ * rows in insertion order, of which only the codes are kept.  The coarse metric is L2 (metric 0); ADC is an L2 quantity and the
+ * handle takes no metric argument.
+ *   code of a row     lb_gpu_pq_encode of the row under the handle's codebooks.
+ *   list of a row     as on the IVF-Flat handle: the label of the k = 1 L2 search of the f32 row, as a query, over an f32 index
+ *                     that holds C, in the handle's order.  Computed from the vector when the row is added, before the vector is
+ *                     dropped; it never changes.
+ *   probes of a query the labels of the k = min(nprobe, nlist) search of the query over that same index.
+ *   distance          float32(sqrt(float64(sum_j table[j * 256 + code[j]]))), table = BuildADCTable(query), the f32 sum in j
+ *                     order: what lb_gpu_pq_search reports.  These are NOT residual codes: a row is encoded as it is, not as
+ *                     its difference from its centroid, and the query's one table serves every list.
+ *   result            the first k rows r, in ascending (distance, r) order, every NaN after +inf, among the rows whose list is a
+ *                     probe of q; the label is ids[r] when ids were given, else r; with fewer than k such rows they come first,
+ *                     then label -1 / distance FLT_MAX.  nprobe >= nlist gives lb_gpu_pq_search over the same codes, bit for
+ *                     bit: labels, order and distances.
+ *   ids               given on every add or on none; a call that breaks this is LB_ERR_INVALID_ARG and adds nothing.
+ *   add               assigns and encodes the vectors (in pieces of at most 64 Mi floats, so the staging of host vectors stays
+ *                     below 256 MB; the vectors are not kept), rebuilds the lists of ALL rows by a stable counting sort (each
+ *                     list holds its rows ascending) and copies all codes into list order: O(ntotal) per call, so add in large
+ *                     pieces.  Codes, lists and the list-major copy are committed together, or nothing is.
+ *   memory            the codes are held in insertion order (what get_codes returns) and, beside each of the two pairs of lists
+ *                     an add alternates between, once more in list order, so that a probed list is one contiguous run of
+ *                     size * M bytes: 3 * M bytes a row, plus 12 bytes a row of lists and 8 of ids.  hbm_bytes reports it.
+ *   limits            nlist in 1..65536, k in 1..LB_MAX_K, fewer than 2^31 rows: LB_ERR_UNSUPPORTED beyond.  nprobe <= 0 is
+ *                     LB_ERR_INVALID_ARG, nprobe > nlist is clamped.  Fewer than all lists are at most LB_MAX_K probes (the
+ *                     coarse search's k; LB_ERR_UNSUPPORTED beyond); every list probed needs no coarse search and works for any
+ *                     nlist.
+ * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
+ * refused call writes nothing.  Searches and reads share the handle; adds and reserve take it alone.  ctx (nullable) is polled
+ * before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here: row filters, residual
+ * codes, adding ready-made codes with caller-given lists, search combining, lb_gpu_comm_*, removing rows, Save / Load, and the Go
+ * and C++ mirrors. */
+typedef struct lb_gpu_ivfpq lb_gpu_ivfpq;
+lb_gpu_ivfpq *lb_gpu_ivfpq_new(int device, const uint8_t *codebook_blob, size_t len, int order, int nlist, const float *centroids,
+                               int *out_status);
+void lb_gpu_ivfpq_free(lb_gpu_ivfpq *p);
+const char *lb_gpu_ivfpq_last_error(const lb_gpu_ivfpq *p);
+int lb_gpu_ivfpq_dims(const lb_gpu_ivfpq *p);
+int lb_gpu_ivfpq_m(const lb_gpu_ivfpq *p);
+int lb_gpu_ivfpq_order(const lb_gpu_ivfpq *p);
+int lb_gpu_ivfpq_nlist(const lb_gpu_ivfpq *p);
+int64_t lb_gpu_ivfpq_ntotal(const lb_gpu_ivfpq *p);
+int64_t lb_gpu_ivfpq_hbm_bytes(const lb_gpu_ivfpq *p); /* codes (three times), ids, lists, codebooks and the coarse index */
+int lb_gpu_ivfpq_get_centroids(lb_gpu_ivfpq *p, float *out); /* f32[nlist*dims] */
+int lb_gpu_ivfpq_reserve(lb_gpu_ivfpq *p, int64_t n_total);
+int lb_gpu_ivfpq_add(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *ids); /* assign, encode, append */
+int lb_gpu_ivfpq_add_device(lb_gpu_ivfpq *p, int64_t n, const float *d_vectors, const int64_t *d_ids);
+int lb_gpu_ivfpq_get_codes(lb_gpu_ivfpq *p, int64_t row0, int64_t n, uint8_t *codes); /* u8[n*M], insertion order */
+int lb_gpu_ivfpq_list_sizes(lb_gpu_ivfpq *p, int64_t *sizes); /* [nlist] */
+int lb_gpu_ivfpq_assignments(lb_gpu_ivfpq *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
+int lb_gpu_ivfpq_search(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
+int lb_gpu_ivfpq_search_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
+                            const lb_cancel *ctx);
+int lb_gpu_ivfpq_search_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist,
+                                   int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* telemetry of the last search only, as lb_gpu_ivf_last_search_stats: out[0] queries, out[1] rows scanned summed over the
+ * queries, out[2] the largest per-query count, out[3] queries whose selection ran from LDS */
+int lb_gpu_ivfpq_last_search_stats(lb_gpu_ivfpq *p, int64_t out[4]);
+/* instrumentation (tools/ivfpq_bench.py), as lb_gpu_ivf_set_profiling: ms[0] the probes (the coarse search), ms[1] the plan,
+ * ms[2] the ADC tables, ms[3] the scan of the probed lists' codes, ms[4] the selection; summed over the search's batches */
+int lb_gpu_ivfpq_set_profiling(lb_gpu_ivfpq *p, int enable);
+int lb_gpu_ivfpq_last_timing(lb_gpu_ivfpq *p, float ms[5]);
+
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:
  * inputs [S][nq][k] ascending per (shard, query) (padding label -1 / FLT_MAX allowed),

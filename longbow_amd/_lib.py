@@ -215,6 +215,28 @@ SIGNATURES = [
     ("lb_gpu_ivf_set_profiling", _i, [_vp, _i]),
     ("lb_gpu_ivf_last_timing", _i, [_vp, _vp]),
     ("lb_gpu_ivf_last_build_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq_new", _vp, [_i, _vp, _sz, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivfpq_free", None, [_vp]),
+    ("lb_gpu_ivfpq_last_error", C.c_char_p, [_vp]),
+    ("lb_gpu_ivfpq_dims", _i, [_vp]),
+    ("lb_gpu_ivfpq_m", _i, [_vp]),
+    ("lb_gpu_ivfpq_order", _i, [_vp]),
+    ("lb_gpu_ivfpq_nlist", _i, [_vp]),
+    ("lb_gpu_ivfpq_ntotal", _i64, [_vp]),
+    ("lb_gpu_ivfpq_hbm_bytes", _i64, [_vp]),
+    ("lb_gpu_ivfpq_get_centroids", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq_reserve", _i, [_vp, _i64]),
+    ("lb_gpu_ivfpq_add", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivfpq_add_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivfpq_get_codes", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_ivfpq_list_sizes", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq_assignments", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_ivfpq_search", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+    ("lb_gpu_ivfpq_search_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq_search_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq_last_search_stats", _i, [_vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq_set_profiling", _i, [_vp, _i]),
+    ("lb_gpu_ivfpq_last_timing", _i, [_vp, _vp]),
     ("lb_gpu_merge_topk_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_packed_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_rrf_fuse_device", _i, [_i, _i64, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
@@ -301,13 +323,13 @@ def require_gpu(device=0):
     return lib
 
 
-def check(rc, handle=None, pq=False, lib=None, bq=False, sq8=False, ivf=False):
+def check(rc, handle=None, pq=False, lib=None, bq=False, sq8=False, ivf=False, ivfpq=False):
     if rc == LB_OK:
         return
     msg = ""
     if handle:
         lib = lib or load()
-        raw = lib.lb_gpu_ivf_last_error(handle) if ivf else lib.lb_gpu_sq8_last_error(handle) if sq8 else lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
+        raw = lib.lb_gpu_ivfpq_last_error(handle) if ivfpq else lib.lb_gpu_ivf_last_error(handle) if ivf else lib.lb_gpu_sq8_last_error(handle) if sq8 else lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
         msg = raw.decode() if raw else ""
     if rc == 3:
         raise GPUNotAvailable(rc, msg)

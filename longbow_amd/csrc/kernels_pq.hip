@@ -8,6 +8,7 @@
 // The whole M x 256 f32 table (98,304 B at M = 96) lives in LDS for the duration of the
 // scan; each lane streams one code row (M bytes) from HBM and does M LDS gathers.
 #include "lb_device.h"
+#include "lb_exact.h"
 
 #pragma clang fp contract(off)
 
@@ -114,22 +115,11 @@ __global__ __launch_bounds__(ADC_THREADS) void adc_scan_kernel(AdcArgs a)
         float sum = 0.f;
         if (VEC16) {
             const uint4 *c4 = reinterpret_cast<const uint4 *>(c);
-            for (int g = 0; g < M / 16; g++) {
-                const uint4 v = c4[g];
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-#pragma unroll
-                    for (int b = 0; b < 4; b++) {
-                        const int j = g * 16 + t * 4 + b;
-                        sum = sum + tab[j * 256 + ((w[t] >> (8 * b)) & 0xffu)];
-                    }
-                }
-            }
+            for (int g = 0; g < M / 16; g++) sum = adc_add16(sum, tab, g, c4[g]);
         } else {
-            for (int j = 0; j < M; j++) sum = sum + tab[j * 256 + c[j]];
+            for (int j = 0; j < M; j++) sum = sum + tab[j * 256 + c[j]]; // (adc_add_bytes, kept in place: the code generated here stays as it was)
         }
-        const float dist = (float)sqrt((double)sum);
+        const float dist = adc_distance(sum);
         if (a.all_out) {
             a.all_out[row - a.out_base] = dist;
         } else {
@@ -213,16 +203,9 @@ __global__ __launch_bounds__(ADC_DMA_WAVES * 64) void adc_scan_dma_kernel(AdcArg
         const int64_t row = a.row_begin + tile * 64 + lane;
         float sum = 0.f;
 #pragma unroll
-        for (int g = 0; g < MCH; g++) {
-            const uint32_t w[4] = {c[g].x, c[g].y, c[g].z, c[g].w};
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-#pragma unroll
-                for (int b = 0; b < 4; b++)
-                    sum = sum + tab[(g * 16 + t * 4 + b) * 256 + ((w[t] >> (8 * b)) & 0xffu)];
-        }
+        for (int g = 0; g < MCH; g++) sum = adc_add16(sum, tab, g, c[g]);
         if (row < a.row_end) {
-            const float dist = (float)sqrt((double)sum);
+            const float dist = adc_distance(sum);
             if (a.all_out) {
                 a.all_out[row - a.out_base] = dist;
             } else {
@@ -265,21 +248,8 @@ __global__ __launch_bounds__(ADC_THREADS) void adc_sample_kernel(const float *ta
     for (uint32_t i = blockIdx.x * ADC_THREADS + threadIdx.x; i < count; i += gridDim.x * ADC_THREADS) {
         const int64_t row = (int64_t)(((uint64_t)i * (uint64_t)n) / count); // i, n < 2^32
         const uint8_t *c = codes + row * (int64_t)M;
-        float sum = 0.f;
-        if (vec16) {
-            for (int g = 0; g < M / 16; g++) {
-                const uint4 v = *reinterpret_cast<const uint4 *>(c + g * 16);
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-#pragma unroll
-                    for (int b2 = 0; b2 < 4; b2++)
-                        sum = sum + tab[(g * 16 + t * 4 + b2) * 256 + ((w[t] >> (8 * b2)) & 0xffu)];
-            }
-        } else {
-            for (int j = 0; j < M; j++) sum = sum + tab[j * 256 + c[j]];
-        }
-        out[i] = pack_entry((float)sqrt((double)sum), (uint32_t)row);
+        const float sum = vec16 ? adc_row_sum<true>(tab, c, M) : adc_row_sum<false>(tab, c, M);
+        out[i] = pack_entry(adc_distance(sum), (uint32_t)row);
     }
 }
 

@@ -20,6 +20,7 @@
 // These are separate kernels, not a mapped mode of the streaming ones: sharing a body with the unmapped kernels costs those
 // registers (LABNOTES: the BQ filter work), and the kernels an unfiltered search launches stay what they were.
 #include "lb_device.h"
+#include "lb_exact.h"
 
 #pragma clang fp contract(off)
 
@@ -27,25 +28,6 @@ namespace lb {
 
 constexpr int ADC_LIST_THREADS = ADC_LIST_WAVES * 64;
 constexpr int ADC_LIST_MAX_BLOCKS = 256; // one workgroup per CU holds the table once (as the streaming kernels)
-
-// one row's exact sum: 16-B loads (runtime M / 16 of them) or single bytes
-template <bool VEC16> __device__ __forceinline__ float adc_row_sum(const float *tab, const uint8_t *c, int M)
-{
-    float sum = 0.f;
-    if (VEC16) {
-        for (int g = 0; g < M / 16; g++) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(c + g * 16);
-            const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-#pragma unroll
-                for (int b = 0; b < 4; b++) sum = sum + tab[(g * 16 + t * 4 + b) * 256 + ((w[t] >> (8 * b)) & 0xffu)];
-        }
-    } else {
-        for (int j = 0; j < M; j++) sum = sum + tab[j * 256 + c[j]];
-    }
-    return sum;
-}
 
 // ---- sampled threshold ----------------------------------------------------------------------------------------------
 // adc_sample_kernel over the list: sample i is position i * n_vis / count
@@ -61,7 +43,7 @@ __global__ __launch_bounds__(ADC_LIST_THREADS) void adc_list_sample_kernel(const
         const uint64_t pos = ((uint64_t)i * (uint64_t)n_vis) / count; // i < count, n_vis < 2^31: pos < n_vis
         const uint32_t row = rowmap[pos];
         const float sum = adc_row_sum<VEC16>(tab, codes + (int64_t)row * M, M);
-        out[i] = pack_entry((float)sqrt((double)sum), row);
+        out[i] = pack_entry(adc_distance(sum), row);
     }
 }
 
@@ -112,7 +94,7 @@ __global__ __launch_bounds__(ADC_LIST_THREADS) void adc_list_scan_kernel(AdcList
          pos += (int64_t)gridDim.x * ADC_LIST_THREADS) {
         const uint32_t row = a.rowmap[pos];
         const float sum = adc_row_sum<VEC16>(tab, a.codes + (int64_t)row * M, M);
-        const uint64_t ent = pack_entry((float)sqrt((double)sum), row);
+        const uint64_t ent = pack_entry(adc_distance(sum), row);
         if (a.boot) {
             list[pos - a.pos_begin] = ent; // (the host keeps a boot chunk within the list: chunk_end_host)
         } else if (ent < tau) {

@@ -138,4 +138,41 @@ __device__ __forceinline__ float exact_distance(float t, float nbt, float na, in
     return dist;
 }
 
+// ---- ADC (simd.adcBatchGeneric, internal/simd/simd.go:345-355) ------------------------------------------------------------------
+// out = float32(sqrt(float64(sum_j table[j * 256 + code[j]]))): an f32 sum in j order, one rounding per addition.  Every kernel
+// that reports an exact ADC distance (kernels_pq.hip, kernels_pq_list.hip, kernels_ivfpq.hip) sums and roots through these.
+// sixteen code bytes, j = g * 16 .. g * 16 + 15, as one 16-byte piece of the row
+__device__ __forceinline__ float adc_add16(float sum, const float *tab, int g, const uint4 v)
+{
+#pragma clang fp contract(off)
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int b = 0; b < 4; b++) sum = sum + tab[(g * 16 + t * 4 + b) * 256 + ((w[t] >> (8 * b)) & 0xffu)];
+    return sum;
+}
+
+// the M code bytes at c, one at a time
+__device__ __forceinline__ float adc_add_bytes(float sum, const float *tab, const uint8_t *c, int M)
+{
+#pragma clang fp contract(off)
+    for (int j = 0; j < M; j++) sum = sum + tab[j * 256 + c[j]];
+    return sum;
+}
+
+// one row's sum straight from its M code bytes at c: 16-byte loads (M % 16 == 0, c 16-byte aligned) or single bytes
+template <bool VEC16> __device__ __forceinline__ float adc_row_sum(const float *tab, const uint8_t *c, int M)
+{
+    float sum = 0.f;
+    if (VEC16) {
+        for (int g = 0; g < M / 16; g++) sum = adc_add16(sum, tab, g, *reinterpret_cast<const uint4 *>(c + g * 16));
+    } else {
+        sum = adc_add_bytes(sum, tab, c, M);
+    }
+    return sum;
+}
+
+__device__ __forceinline__ float adc_distance(float sum) { return (float)sqrt((double)sum); }
+
 } // namespace lb

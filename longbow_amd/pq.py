@@ -79,6 +79,7 @@ class PQEncoder(RowFilterMixin):
             _lib.check(st.value or 7)
         self._lib = lib
         self._h = C.c_void_p(h)
+        self.blob = buf  # the codebooks as given (ivfpq.IVFPQ takes an encoder for its codebooks)
         self.M = lib.lb_gpu_pq_m(self._h)
         self.Dims = lib.lb_gpu_pq_dims(self._h)
         self.K = 256

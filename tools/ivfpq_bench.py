@@ -1,0 +1,141 @@
+"""IVF-PQ index (exact ADC k-NN over the codes of the probed lists) against the flat ADC search of a PQ handle on the same codes:
+one JSON line.
+
+    python tools/ivfpq_bench.py [--rows 10000000] [--dim 768] [--m 96] [--nlist 1024] [--k 100]
+
+Rows and queries come from the seeded device fill (uniform in [-0.5, 0.5)), the rows in pieces of --piece rows that are added
+with add_device and never held together; the codebooks are config 4's of bench.py (the seeded fill, seed 7); the centroids are
+nlist of the rows (evenly spaced).  The same codes go to a pq.PQEncoder.  Per cell (nq x nprobe): the median of three runs, each
+the p50 of ten searches after a warm-up, through the device-pointer entry point by wall clock (the call returns when the results
+are on the device); the HIP-event time of each step from one more, profiled, run (probes, plan, tables, scan, selection); rows
+scanned and the scan's bytes (rows * (M + 4): a code row and its row number) over its time; recall@k against lb_gpu_pq_search
+over the same codes, which is the full ADC ranking, not the exact f32 one; and that search's own p50 at the same nq, in the
+same run.  Also: the add rate in rows/s and hbm_bytes against its per-row terms.  The shader clock is read before and after.  A
+run that finds no GPU fails.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from longbow_amd import _lib, ivfpq, pq  # noqa: E402
+
+
+def p50_ms(fn, reps=10):
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(ts))
+
+
+def median_of_p50s(fn, runs=3):
+    fn()
+    fn()
+    return float(np.median([p50_ms(fn) for _ in range(runs)]))
+
+
+def clock_mhz(lib):
+    try:
+        return float(lib.lb_gpu_shader_clock_mhz(0, 2000))
+    except Exception:
+        return None
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rows", type=int, default=10_000_000)
+    ap.add_argument("--dim", type=int, default=768)
+    ap.add_argument("--m", type=int, default=96)
+    ap.add_argument("--nlist", type=int, default=1024)
+    ap.add_argument("--k", type=int, default=100)
+    ap.add_argument("--piece", type=int, default=1_000_000)
+    ap.add_argument("--nprobe", type=int, nargs="*", default=[1, 8, 32, 1024])
+    ap.add_argument("--nq", type=int, nargs="*", default=[1, 8, 64])
+    a = ap.parse_args()
+    lib = _lib.require_gpu(0)  # (raises without a GPU: nothing here falls back)
+    n, dim, M = a.rows, a.dim, a.m
+    out = {"rows": n, "dim": dim, "m": M, "nlist": a.nlist, "k": a.k, "shader_clock_mhz_before": clock_mhz(lib)}
+
+    cb = torch.empty(M * 256 * (dim // M), dtype=torch.float32, device="cuda")
+    _lib.check(lib.lb_gpu_fill_uniform_device(0, cb.data_ptr(), cb.numel(), 7, 0, None))
+    torch.cuda.synchronize()
+    blob = pq.serialize_codebooks(cb.cpu().numpy().reshape(M, 256, dim // M))
+    # the centroids: rows 0, n / nlist, 2 n / nlist, ... of the same fill
+    rows = torch.arange(a.nlist, dtype=torch.int64, device="cuda") * (n // a.nlist)
+    cent = torch.empty((a.nlist, dim), dtype=torch.float32, device="cuda")
+    _lib.check(lib.lb_gpu_fill_uniform_rows_device(0, cent.data_ptr(), rows.data_ptr(), a.nlist, dim, 12345, None))
+    torch.cuda.synchronize()
+
+    h = ivfpq.IVFPQ(blob, cent.cpu().numpy())
+    h.reserve(n)
+    buf = torch.empty((min(a.piece, n), dim), dtype=torch.float32, device="cuda")
+    torch.cuda.synchronize()
+    add_s = 0.0
+    for r0 in range(0, n, a.piece):
+        cnt = min(a.piece, n - r0)
+        _lib.check(lib.lb_gpu_fill_uniform_device(0, buf.data_ptr(), cnt * dim, 12345, r0 * dim, None))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h.add_device(cnt, buf.data_ptr())
+        add_s += time.perf_counter() - t0
+    del buf
+    sizes = h.list_sizes()
+    out["add"] = {"seconds": add_s, "rows_per_s": n / add_s, "pieces": -(-n // a.piece)}
+    out["lists"] = {"min": int(sizes.min()), "median": int(np.median(sizes)), "max": int(sizes.max()), "empty": int((sizes == 0).sum())}
+    per_row = 3 * M + 4 * 3  # the codes three times; assign and the two lists
+    out["hbm_bytes"] = h.hbm_bytes
+    out["hbm_bytes_per_row_terms"] = n * per_row
+    out["hbm_bytes_beyond_rows"] = h.hbm_bytes - n * per_row  # codebooks, offsets, the coarse index
+
+    enc = pq.PQEncoder(blob)
+    enc.reserve(n)
+    step = 1_000_000
+    for r0 in range(0, n, step):
+        enc.add_codes(h.codes(r0, min(step, n - r0)))
+
+    nqmax = max(a.nq)
+    Q = torch.empty((nqmax, dim), dtype=torch.float32, device="cuda")
+    _lib.check(lib.lb_gpu_fill_uniform_device(0, Q.data_ptr(), nqmax * dim, 42, 0, None))
+    D = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
+    L = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
+    FD = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
+    FL = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
+    torch.cuda.synchronize()
+    cells = []
+    for nq in a.nq:
+        flat_ms = median_of_p50s(lambda: enc.search_device(nq, Q.data_ptr(), a.k, FD.data_ptr(), FL.data_ptr()))
+        truth, truth_d = FL[:nq].cpu().numpy(), FD[:nq].cpu().numpy()
+        for nprobe in a.nprobe:
+            run = lambda: h.search_device(nq, Q.data_ptr(), a.k, nprobe, D.data_ptr(), L.data_ptr())  # noqa: E731
+            ms = median_of_p50s(run)
+            h.set_profiling(True)
+            run()
+            h.set_profiling(False)
+            steps = h.last_timing()
+            st = h.last_search_stats()
+            got = L[:nq].cpu().numpy()
+            recall = float(np.mean([np.intersect1d(got[j], truth[j]).size / a.k for j in range(nq)]))
+            cell = {"nq": nq, "nprobe": nprobe, "p50_ms": ms, "flat_adc_p50_ms": flat_ms,
+                    "probes_ms": steps[0], "plan_ms": steps[1], "tables_ms": steps[2], "scan_ms": steps[3], "select_ms": steps[4],
+                    "rows_scanned": st[1], "max_rows_per_query": st[2], "selected_from_lds": st[3],
+                    "scan_bytes": st[1] * (M + 4), "scan_gb_per_s": st[1] * (M + 4) / max(steps[3], 1e-6) / 1e6,
+                    "recall_at_k_vs_full_adc": recall}
+            if nprobe >= a.nlist:  # every list probed: the flat ADC search's own result, bit for bit
+                cell["equals_flat_adc"] = bool(np.array_equal(got, truth) and np.array_equal(D[:nq].cpu().numpy(), truth_d))
+            cells.append(cell)
+    out["cells"] = cells
+    out["shader_clock_mhz_after"] = clock_mhz(lib)
+    print(json.dumps(out))
+    enc.Close()
+    h.Close()
+
+
+if __name__ == "__main__":
+    main()
