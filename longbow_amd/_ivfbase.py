@@ -1,0 +1,106 @@
+"""What the IVF handles share on the <_prefix>_* entry points: ivf.IVFFlat (rows) and ivfpq.IVFPQ (codes) over one coarse partition."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+
+
+class IVFBase:
+    """A handle with centroids f32 [nlist, dims] given at creation.  A subclass sets _prefix and _timing_slots, and in its __init__
+    self._lib, self._h, self.nlist and self.dims (self._h = None first: Close() and __del__ find that when creation fails)."""
+    _prefix = None  # "lb_gpu_ivf" / "lb_gpu_ivfpq"
+    _timing_slots = 0
+
+    def _fn(self, name):
+        return getattr(self._lib, self._prefix + "_" + name)
+
+    def _check(self, rc):
+        _lib.check(rc, self._h, lib=self._lib, prefix=self._prefix)
+
+    def _vectors(self, vectors):
+        v = np.ascontiguousarray(vectors, np.float32)
+        v = v.reshape(-1, v.shape[-1]) if v.size else v.reshape(0, self.dims)
+        if v.shape[1] != self.dims:
+            raise ValueError(f"vector dimension {v.shape[1]} does not match {self.dims}")
+        return v
+
+    @property
+    def ntotal(self):
+        return int(self._fn("ntotal")(self._h))
+
+    @property
+    def hbm_bytes(self):
+        return int(self._fn("hbm_bytes")(self._h))
+
+    def centroids(self):
+        out = np.empty((self.nlist, self.dims), np.float32)
+        self._check(self._fn("get_centroids")(self._h, out.ctypes.data))
+        return out
+
+    def reserve(self, n_total):
+        self._check(self._fn("reserve")(self._h, n_total))
+
+    def add(self, vectors, ids=None):
+        """append rows [n, dims]; ids (int64 [n]) on every add or on none.  Each add rebuilds the lists of all rows: O(ntotal)."""
+        v = self._vectors(vectors)
+        i = None
+        if ids is not None:
+            i = np.ascontiguousarray(ids, np.int64).reshape(-1)
+            if i.size != v.shape[0]:
+                raise ValueError(f"{i.size} ids for {v.shape[0]} rows")
+        self._check(self._fn("add")(self._h, v.shape[0], v.ctypes.data, i.ctypes.data if i is not None else None))
+
+    def add_device(self, n, d_vectors, d_ids=None):
+        self._check(self._fn("add_device")(self._h, n, d_vectors, d_ids))
+
+    def list_sizes(self):
+        out = np.empty(self.nlist, np.int64)
+        self._check(self._fn("list_sizes")(self._h, out.ctypes.data))
+        return out
+
+    def assignments(self, row0=0, n=None):
+        """the lists of rows [row0, row0 + n) -> int32 [n]"""
+        n = self.ntotal - row0 if n is None else n
+        out = np.empty(max(n, 0), np.int32)
+        self._check(self._fn("assignments")(self._h, row0, n, out.ctypes.data))
+        return out
+
+    def search(self, queries, k, nprobe, ctx=None):
+        """-> (labels [nq, k], dist [nq, k]): ascending (distance, row) among the rows of the probed lists, padded -1 / FLT_MAX"""
+        v = self._vectors(queries)
+        dist = np.empty((v.shape[0], k), np.float32)
+        labels = np.empty((v.shape[0], k), np.int64)
+        self._check(self._fn("search_ctx")(self._h, v.shape[0], v.ctypes.data, k, nprobe, dist.ctypes.data, labels.ctypes.data,
+                                           ctx._h if ctx is not None else None))
+        return labels, dist
+
+    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None):
+        self._check(self._fn("search_device_ctx")(self._h, nq, d_queries, k, nprobe, d_dist, d_labels, stream,
+                                                  ctx._h if ctx is not None else None))
+
+    def last_search_stats(self):
+        """of the last search: (queries, rows scanned summed over them, the largest per-query count, queries selected from LDS)"""
+        out = (C.c_int64 * 4)()
+        self._check(self._fn("last_search_stats")(self._h, out))
+        return tuple(int(x) for x in out)
+
+    def set_profiling(self, on):
+        self._check(self._fn("set_profiling")(self._h, 1 if on else 0))
+
+    def last_timing(self):
+        """ms of the last profiled search, summed over its batches: _timing_slots values, named by the subclass"""
+        out = (C.c_float * self._timing_slots)()
+        self._check(self._fn("last_timing")(self._h, out))
+        return tuple(float(x) for x in out)
+
+    def Close(self):
+        if self._h:
+            self._fn("free")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.Close()
+        except Exception:
+            pass

@@ -323,13 +323,14 @@ def require_gpu(device=0):
     return lib
 
 
-def check(rc, handle=None, pq=False, lib=None, bq=False, sq8=False, ivf=False, ivfpq=False):
+def check(rc, handle=None, pq=False, lib=None, bq=False, sq8=False, prefix=None):
+    """prefix: the handle's family ("lb_gpu_ivf", ...), whose <prefix>_last_error is asked for the message"""
     if rc == LB_OK:
         return
     msg = ""
     if handle:
         lib = lib or load()
-        raw = lib.lb_gpu_ivfpq_last_error(handle) if ivfpq else lib.lb_gpu_ivf_last_error(handle) if ivf else lib.lb_gpu_sq8_last_error(handle) if sq8 else lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
+        raw = getattr(lib, prefix + "_last_error")(handle) if prefix else lib.lb_gpu_sq8_last_error(handle) if sq8 else lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
         msg = raw.decode() if raw else ""
     if rc == 3:
         raise GPUNotAvailable(rc, msg)

@@ -1,5 +1,6 @@
-// lb_handle.h -- the host shell of a code-index handle (lb_gpu_pq, lb_gpu_bq, lb_gpu_sq8) and of lb_gpu_ivf: what the C-ABI
-// translation units pq.hip, bq.hip, sq8.hip and ivf.hip share beyond lb_host.h.  Header-only, nothing exported.
+// lb_handle.h -- the host shell of a code-index handle (lb_gpu_pq, lb_gpu_bq, lb_gpu_sq8) and of the IVF handles (lb_gpu_ivf,
+// lb_gpu_ivfpq): what the C-ABI translation units pq.hip, bq.hip, sq8.hip, ivf.hip and ivfpq.hip share beyond lb_host.h; what
+// the last two share beyond it is in lb_ivf_host.h.  Header-only, nothing exported.
 //
 // The rules every entry point of these handles keeps:
 //   * nothing but an lb_status leaves the library: the body of an entry point runs inside guard();

@@ -1,0 +1,386 @@
+// lb_ivf_host.h -- the host side that the IVF handles share: what ivf.hip (lb_gpu_ivf, rows) and ivfpq.hip (lb_gpu_ivfpq, codes)
+// have in common beyond lb_handle.h.  Header-only, host-only, nothing exported.
+//
+// The contract:
+//   * IvfPartition is the coarse partition of a handle's rows: the inner exact f32 index over the centroids, the list of each row
+//     and the inverted lists over them.  It is a plain member named `part` of a handle that derives from CodeHandle; the functions
+//     here take (CodeHandle *h, IvfPartition &P, ...), the entry-point templates a T *p with p->part and p->timing;
+//   * the rules at the head of lb_handle.h hold: every pooled Lease that a function here enqueues work on is the caller's, declared
+//     outside its guard(); coarse_fail drains the stream before leases go back; searches and reads take `mu` shared, adds and
+//     reserve take it alone.  Everything that takes a stream runs inside the caller's guard() and throws as its body does;
+//   * growth is all or nothing (IvfGrowth): stage() allocates and fills and may throw, commit() moves and cannot;
+//   * an add writes behind the stored rows and into the pair of lists that is not in use, and commits last: sizes, pair, ids flag
+//     and n, by the handle's add_impl, with nothing that throws after it;
+//   * ivf_search is the one search loop.  A handle supplies its scratch pieces and the launches between the plan and the
+//     selection; ctx is polled before every launch, a cancelled search publishes no stats, and the events of a profiled search
+//     fall where the handle's timing slots say.
+#pragma once
+#include "lb_handle.h"
+#include "lb_ivf.h"
+
+#include <atomic>
+#include <functional>
+#include <vector>
+
+namespace lb {
+#pragma GCC visibility push(hidden) // the instantiations over the handles' types stay out of the library's exports
+
+constexpr int64_t kQueryBatch = 1024;              // queries per batch at most
+constexpr int64_t kKeyScratch = (int64_t)1 << 30;  // bytes of keys a batch may hold
+constexpr int kMaxTimingSlots = 5;
+
+struct IvfPartition {
+    int nlist = 0;
+    lb_gpu_index *coarse = nullptr; // the centroids: same device, dims and order as the handle
+    std::vector<float> h_cent;      // [nlist][dims]
+    DevBuf<int64_t> d_ids;          // [capacity] when ids were given
+    bool has_ids = false;
+    DevBuf<uint32_t> d_assign;      // [capacity]: list of each row
+    // the lists are built for all rows by every add, into the pair that is not in use: a failed add leaves the old ones
+    DevBuf<uint32_t> d_off[2];      // [nlist + 1]
+    DevBuf<uint32_t> d_list[2];     // [capacity]
+    int cur = 0;
+    std::vector<int64_t> h_sizes;   // [nlist]: sizes grids and scratch without a device round trip
+    int64_t stats[4] = {0, 0, 0, 0}; // of the last search (under err_mu)
+    std::atomic<bool> profiling{false};
+    ~IvfPartition() { lb_gpu_index_free(coarse); }
+    IvfLists all_lists(int i) const { return IvfLists{d_off[i].get(), d_list[i].get(), nlist}; }
+    int64_t hbm_bytes() const
+    {
+        return (int64_t)(d_ids.count() * 8 + (d_assign.count() + d_list[0].count() + d_list[1].count() + d_off[0].count() + d_off[1].count()) * 4) +
+               lb_gpu_index_hbm_bytes(coarse);
+    }
+};
+
+// ---- opening ----------------------------------------------------------------------------------------------------------------
+// A handle of `dims` dimensions over `nlist` centroids, the caller having checked its arguments: the partition's host fields and
+// offsets, init(p) for the handle's own, then the inner index of `metric` and `order` with the centroids in it.
+template <class T, class Init>
+T *ivf_open(int device, int dims, int metric, int order, int nlist, const float *centroids, int *out_status, Init &&init)
+{
+    int inner = LB_OK;
+    T *h = handle_open<T>(device, out_status, [&](T *p) {
+        IvfPartition &P = p->part;
+        p->dims = dims;
+        P.nlist = nlist;
+        P.h_cent.assign(centroids, centroids + (size_t)nlist * dims);
+        P.h_sizes.assign((size_t)nlist, 0);
+        for (DevBuf<uint32_t> &off : P.d_off) {
+            off.alloc((size_t)nlist + 1);
+            LB_HIP(hipMemset(off.get(), 0, ((size_t)nlist + 1) * 4));
+        }
+        init(p);
+        P.coarse = lb_gpu_index_new(device, dims, metric, &inner);
+        if (!P.coarse) return;
+        inner = lb_gpu_index_set_order(P.coarse, order);
+        if (inner == LB_OK) inner = lb_gpu_index_add(P.coarse, nlist, centroids, nullptr);
+        LB_HIP(hipSetDevice(device));
+    });
+    if (h && inner != LB_OK) { // the centroids did not get onto the device
+        handle_free(h);
+        if (out_status) *out_status = inner;
+        return nullptr;
+    }
+    return h;
+}
+
+// ---- growth -----------------------------------------------------------------------------------------------------------------
+// The capacity that room for `need` rows (and for ids, if wanted) asks for: the present one when only the ids are missing, -1 when
+// nothing is.
+inline int64_t ivf_grow_to(const CodeHandle *h, const IvfPartition &P, int64_t need, bool want_ids, size_t row_bytes)
+{
+    const bool ids_missing = want_ids && P.d_ids.count() < (size_t)std::max<int64_t>(h->capacity, 1);
+    if (need <= h->capacity && !ids_missing) return -1;
+    return need <= h->capacity ? h->capacity : grow_capacity(h->capacity, need, row_bytes);
+}
+
+// The partition's share of a handle's *_grow to `cap` rows.  The handle stages its own buffers beside it and commits them with it:
+// no old buffer is replaced before every new one is allocated and filled.
+struct IvfGrowth {
+    DevBuf<int64_t> ids;
+    DevBuf<uint32_t> assign, list[2];
+    bool want_ids = false, resize = false;
+    void stage(const CodeHandle *h, const IvfPartition &P, int64_t cap, bool with_ids)
+    {
+        want_ids = with_ids;
+        resize = cap != h->capacity;
+        if (want_ids) {
+            ids.alloc((size_t)cap);
+            if (h->n > 0 && P.has_ids) LB_HIP(hipMemcpy(ids.get(), P.d_ids.get(), (size_t)h->n * 8, hipMemcpyDeviceToDevice));
+        }
+        if (!resize) return;
+        assign.alloc((size_t)cap);
+        for (DevBuf<uint32_t> &l : list) l.alloc((size_t)cap);
+        if (h->n > 0) { // (of the lists the pair in use alone)
+            LB_HIP(hipMemcpy(assign.get(), P.d_assign.get(), (size_t)h->n * 4, hipMemcpyDeviceToDevice));
+            LB_HIP(hipMemcpy(list[P.cur].get(), P.d_list[P.cur].get(), (size_t)h->n * 4, hipMemcpyDeviceToDevice));
+        }
+    }
+    void commit(IvfPartition &P) noexcept
+    {
+        if (want_ids) P.d_ids = std::move(ids);
+        if (!resize) return;
+        P.d_assign = std::move(assign);
+        for (int i = 0; i < 2; i++) P.d_list[i] = std::move(list[i]);
+    }
+};
+
+// ---- the steps of an add ----------------------------------------------------------------------------------------------------
+inline int ivf_ids_consistent(CodeHandle *h, const IvfPartition &P, const int64_t *ids)
+{
+    if (h->n == 0 || (ids != nullptr) == P.has_ids) return LB_OK;
+    h->set_error("ids are given on every add or on none: the handle's rows have %s", P.has_ids ? "ids" : "none");
+    return LB_ERR_INVALID_ARG;
+}
+
+// the coarse index's own refusal becomes the handle's; what the call enqueued on s is drained before its pooled buffers go back
+inline int coarse_fail(CodeHandle *h, const IvfPartition &P, int rc, hipStream_t s)
+{
+    (void)hipStreamSynchronize(s);
+    if (rc == LB_ERR_CANCELLED || rc == LB_ERR_DEADLINE) return ctx_fail(h, rc);
+    h->set_error("coarse quantiser: %s", lb_gpu_last_error(P.coarse));
+    return rc;
+}
+
+// bytes of `lab` for ivf_assign of up to `rows` rows: their labels and distances
+inline size_t ivf_assign_bytes(int64_t rows) { return up16((size_t)rows * 8) + (size_t)rows * 4; }
+
+// The lists of the `cnt` device rows d_rows, to be stored as rows [row0, row0 + cnt): the k = 1 search of each over the centroids,
+// narrowed into assign.  Enqueues on s and does not drain it, except to refuse.
+inline int ivf_assign(CodeHandle *h, IvfPartition &P, int64_t row0, int64_t cnt, const float *d_rows, Lease &lab, hipStream_t s)
+{
+    int64_t *d_lab = lab.as<int64_t>();
+    float *d_dist = reinterpret_cast<float *>(lab.as<char>() + up16((size_t)cnt * 8));
+    if (const int rc = lb_gpu_index_search_device(P.coarse, cnt, d_rows, 1, d_dist, d_lab, s)) return coarse_fail(h, P, rc, s);
+    launch_ivf_narrow(d_lab, cnt, P.d_assign.get() + row0, s);
+    return LB_OK;
+}
+
+// The lists of rows [0, total) from assign, into the pair not in use, in two halves, so that a handle can enqueue what it derives
+// from the new lists between them.  The launches:
+inline void ivf_sort_lists(CodeHandle *h, IvfPartition &P, int64_t total, Lease &hist, hipStream_t s)
+{
+    const int nxt = 1 - P.cur;
+    hist.reset(h->device, ivf_sort_hist_words(total, P.nlist) * 4);
+    LB_HIP(launch_ivf_sort(P.d_assign.get(), total, P.nlist, hist.as<uint32_t>(), P.d_off[nxt].get(), P.d_list[nxt].get(), s));
+}
+// The read-back of the new lists' sizes: drains s.  The caller commits `sizes` and the pair.
+inline int ivf_read_lists(CodeHandle *h, IvfPartition &P, int64_t total, std::vector<int64_t> &sizes, hipStream_t s)
+{
+    std::vector<uint32_t> h_off((size_t)P.nlist + 1);
+    sizes.resize((size_t)P.nlist);
+    LB_LAUNCH_CHECK();
+    LB_HIP(hipMemcpyAsync(h_off.data(), P.d_off[1 - P.cur].get(), h_off.size() * 4, hipMemcpyDeviceToHost, s));
+    LB_HIP(hipStreamSynchronize(s));
+    if ((int64_t)h_off[P.nlist] != total) {
+        h->set_error("the lists hold %lld of %lld rows", (long long)h_off[P.nlist], (long long)total);
+        return LB_ERR_INTERNAL;
+    }
+    for (int l = 0; l < P.nlist; l++) sizes[l] = (int64_t)h_off[l + 1] - (int64_t)h_off[l];
+    return LB_OK;
+}
+
+// ---- the search loop --------------------------------------------------------------------------------------------------------
+// Exact k-NN of nq device-resident queries among the rows of their probed lists, the lists being L with `sizes`; the caller holds
+// the reader lock, has made the device current and has checked the arguments.  `a` comes with the handle's own fields set.  The
+// scratch is leased into the caller's `sc`.  Per batch: the probes, launch_ivf_plan, the handle's middle steps, launch_ivf_select.
+//   extra(c, a, nb)               take()s the handle's scratch pieces for a batch of nb queries from the Carve c (it runs twice)
+//   middle(a, maxlen, poll, next) enqueues what fills a.keys; poll() is false once ctx fired, next() ends a timing slot and then
+//                                 polls; after either's false it enqueues nothing more and returns false.  maxlen: the longest list
+// timing[slots] (under err_mu) gets the ms of a profiled search summed over its batches: probes, plan (up to middle's first next()),
+// a slot per further next(), selection.  Profiling costs a drain per batch.
+template <class Extra, class Middle>
+int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vector<int64_t> &sizes, IvfBatch a, int64_t nq, const float *d_Q,
+               int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s, const lb_cancel *ctx, Lease &sc, float *timing, int slots,
+               Extra &&extra, Middle &&middle)
+{
+    int64_t st[4] = {nq, 0, 0, 0};
+    auto publish = [&]() {
+        std::lock_guard<std::mutex> g(h->err_mu);
+        std::copy(st, st + 4, P.stats);
+    };
+    if (h->n == 0) { // all padding, without a launch
+        LB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_dist), 0x7f7fffff /* FLT_MAX */, (size_t)nq * k, s));
+        LB_HIP(hipMemsetAsync(d_labels, 0xff, (size_t)nq * k * 8, s));
+        LB_HIP(hipStreamSynchronize(s));
+        publish();
+        return LB_OK;
+    }
+    const int np = std::min(nprobe, P.nlist);
+    // pmax: the rows a query can scan at most, the sum of the np largest lists
+    std::vector<int64_t> big(sizes);
+    std::partial_sort(big.begin(), big.begin() + np, big.end(), std::greater<int64_t>());
+    int64_t pmax = 0;
+    for (int i = 0; i < np; i++) pmax += big[i];
+    const int64_t maxlen = big[0];
+    pmax = std::max<int64_t>(pmax, 1);
+    const int64_t nb = std::min(std::min(nq, kQueryBatch), std::max<int64_t>(1, kKeyScratch / 8 / pmax));
+    a.L = L;
+    a.np = np;
+    a.pmax = pmax;
+    int64_t *d_probes = nullptr;
+    float *d_pdist = nullptr;
+    unsigned long long *d_stats = nullptr;
+    auto layout = [&](Carve c) {
+        a.probes = d_probes = c.take<int64_t>((size_t)nb * np * 8);
+        d_pdist = c.take<float>((size_t)nb * np * 4);
+        a.seg = c.take<uint32_t>((size_t)nb * (np + 1) * 4);
+        d_stats = c.take<unsigned long long>(4 * 8);
+        extra(c, a, nb);
+        a.keys = c.take<uint64_t>((size_t)nb * pmax * 8);
+        return c.off;
+    };
+    lease_layout(sc, h->device, layout);
+    int cancelled = 0;
+    auto go = [&]() { // false: the context fired, nothing more is enqueued
+        cancelled = ctx_state(ctx);
+        return cancelled == 0;
+    };
+    if (go()) LB_HIP(hipMemsetAsync(d_stats, 0, 4 * 8, s));
+    const bool prof = P.profiling.load();
+    EventH ev[kMaxTimingSlots + 1];
+    float tms[kMaxTimingSlots] = {0, 0, 0, 0, 0};
+    if (prof)
+        for (int i = 0; i <= slots; i++) LB_HIP(hipEventCreate(&ev[i].h));
+    int e = 0; // the next event of the batch
+    auto mark = [&]() { if (prof) LB_HIP(hipEventRecord(ev[e++], s)); };
+    auto next = [&]() { mark(); return go(); };
+    for (int64_t q0 = 0; q0 < nq && !cancelled; q0 += nb) {
+        a.nq = (int)std::min(nb, nq - q0);
+        a.Q = d_Q + (size_t)q0 * h->dims;
+        e = 0;
+        mark();
+        // the probes (the inner index polls ctx before its own launches).  More than LB_MAX_K of them is more than the coarse
+        // search returns: with every list probed they are all the lists, and their order does not reach the result
+        if (np == P.nlist && np > LB_MAX_K) launch_ivf_all_probes(d_probes, a.nq, np, s);
+        else if (const int rc = lb_gpu_index_search_device_ctx(P.coarse, a.nq, a.Q, np, d_pdist, d_probes, s, ctx)) return coarse_fail(h, P, rc, s);
+        if (!next()) break;
+        launch_ivf_plan(a, d_stats, s);
+        if (!middle(a, maxlen, go, next)) break;
+        if (!next()) break;
+        launch_ivf_select(a, k, P.has_ids ? P.d_ids.get() : nullptr, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
+        mark();
+        if (prof) {
+            LB_HIP(hipEventSynchronize(ev[slots]));
+            for (int i = 0; i < slots; i++) {
+                float ms = 0.f;
+                LB_HIP(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
+                tms[i] += ms;
+            }
+        }
+    }
+    LB_LAUNCH_CHECK();
+    unsigned long long h_stats[4] = {0, 0, 0, 0};
+    if (!cancelled) LB_HIP(hipMemcpyAsync(h_stats, d_stats, sizeof h_stats, hipMemcpyDeviceToHost, s));
+    LB_HIP(hipStreamSynchronize(s));
+    if (cancelled) return ctx_fail(h, cancelled);
+    for (int i = 1; i < 4; i++) st[i] = (int64_t)h_stats[i];
+    publish();
+    if (prof) {
+        std::lock_guard<std::mutex> g(h->err_mu);
+        std::copy(tms, tms + slots, timing);
+    }
+    return LB_OK;
+}
+
+// ---- the entry points -------------------------------------------------------------------------------------------------------
+// T: a handle with `part` and `timing[]`.  dev(p, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc) is the handle's call of
+// ivf_search.  Argument checks answer before a device is touched.
+template <class T>
+int ivf_search_args(T *p, int64_t nq, const void *queries, int k, int nprobe, const void *dist, const void *labels, const lb_cancel *ctx)
+{
+    return knn_args(p, nq, queries, k, dist, labels, ctx, [&]() -> int {
+        const int nlist = p->part.nlist;
+        if (nprobe <= 0) {
+            p->set_error("nprobe=%d: at least one list is probed", nprobe);
+            return LB_ERR_INVALID_ARG;
+        }
+        if (nprobe < nlist && nprobe > LB_MAX_K) { // (more probes than the coarse search returns)
+            p->set_error("nprobe=%d: fewer than all %d lists are at most %d probes", nprobe, nlist, LB_MAX_K);
+            return LB_ERR_UNSUPPORTED;
+        }
+        return LB_OK;
+    });
+}
+
+template <class T, class Dev>
+int ivf_search_device_ctx(T *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels, void *stream,
+                          const lb_cancel *ctx, Dev &&dev)
+{
+    const int rc = ivf_search_args(p, nq, d_queries, k, nprobe, d_dist, d_labels, ctx);
+    if (rc != LB_OK || nq == 0) return rc;
+    std::shared_lock<std::shared_mutex> g(p->mu);
+    hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+    Lease sc;
+    return guard(p, s, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        return dev(p, nq, d_queries, k, nprobe, d_dist, d_labels, s, ctx, sc);
+    });
+}
+
+template <class T, class Dev>
+int ivf_search_ctx(T *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx, Dev &&dev)
+{
+    const int rc = ivf_search_args(p, nq, queries, k, nprobe, dist, labels, ctx);
+    if (rc != LB_OK || nq == 0) return rc;
+    return host_knn(
+        p, nq, (size_t)p->dims * 4, k, dist, labels,
+        [&](Lease &dq, Lease &, hipStream_t s) { LB_HIP(hipMemcpyAsync(dq.p, queries, (size_t)nq * p->dims * 4, hipMemcpyHostToDevice, s)); },
+        [&](Lease &dq, float *d_dist, int64_t *d_labels, hipStream_t s, Lease &sc) {
+            return dev(p, nq, dq.as<float>(), k, nprobe, d_dist, d_labels, s, ctx, sc);
+        });
+}
+
+template <class T> int ivf_list_sizes(T *p, int64_t *sizes)
+{
+    if (!p || !sizes) return LB_ERR_INVALID_ARG;
+    std::shared_lock<std::shared_mutex> g(p->mu);
+    std::copy(p->part.h_sizes.begin(), p->part.h_sizes.end(), sizes);
+    return LB_OK;
+}
+
+template <class T> int ivf_assignments(T *p, int64_t row0, int64_t n, int32_t *lists)
+{
+    if (!p || row0 < 0 || n < 0 || (n > 0 && !lists)) return LB_ERR_INVALID_ARG;
+    if (n == 0) return LB_OK;
+    std::shared_lock<std::shared_mutex> g(p->mu);
+    if (const int st = rows_in_range(p, row0, n)) return st;
+    return guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        LB_HIP(hipMemcpy(lists, p->part.d_assign.get() + row0, (size_t)n * 4, hipMemcpyDeviceToHost)); // (list numbers are below 2^16)
+        return LB_OK;
+    });
+}
+
+template <class T> int ivf_get_centroids(T *p, float *out)
+{
+    if (!p || !out) return LB_ERR_INVALID_ARG;
+    std::copy(p->part.h_cent.begin(), p->part.h_cent.end(), out); // (fixed at creation)
+    return LB_OK;
+}
+
+template <class T> int ivf_last_search_stats(T *p, int64_t out[4])
+{
+    if (!p || !out) return LB_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->err_mu);
+    std::copy(p->part.stats, p->part.stats + 4, out);
+    return LB_OK;
+}
+
+template <class T> int ivf_set_profiling(T *p, int enable)
+{
+    if (!p) return LB_ERR_INVALID_ARG;
+    p->part.profiling.store(enable != 0);
+    return LB_OK;
+}
+
+template <class T> int ivf_last_timing(T *p, float *ms)
+{
+    if (!p || !ms) return LB_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->err_mu);
+    std::copy(std::begin(p->timing), std::end(p->timing), ms);
+    return LB_OK;
+}
+
+#pragma GCC visibility pop
+} // namespace lb

@@ -16,6 +16,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _lib, pq
+from ._ivfbase import IVFBase
 from ._rowfilter import RowFilterMixin
 
 FLT_MAX = np.float32(3.4028234663852886e38)
@@ -46,10 +47,11 @@ def train_device(n, d_vectors, dims, nlist, max_iter=20, seed=0, init_rows=None,
     return np.frombuffer(blob[12:], "<f4").reshape(nlist, dims).copy()
 
 
-class IVFFlat(RowFilterMixin):
+class IVFFlat(RowFilterMixin, IVFBase):
     """lb_gpu_ivf: metric 0 L2 / 1 cosine / 2 dot, order 0 SEQ / 1 UNROLL4, centroids f32 [nlist, dims].  Under a row filter
     (RowFilterMixin) the probes stay as they are and a search sees the visible rows of the probed lists alone."""
     _prefix = "lb_gpu_ivf"
+    _timing_slots = 4
 
     def __init__(self, centroids, metric=0, order=0, device=0, lib=None):
         self._h = None  # (Close() and __del__ find this when creation fails below)
@@ -67,101 +69,15 @@ class IVFFlat(RowFilterMixin):
         self.nlist, self.dims = c.shape
         self.metric, self.order = metric, order
 
-    def _check(self, rc):
-        _lib.check(rc, self._h, lib=self._lib, ivf=True)
-
-    def _vectors(self, vectors):
-        v = np.ascontiguousarray(vectors, np.float32)
-        v = v.reshape(-1, v.shape[-1]) if v.size else v.reshape(0, self.dims)
-        if v.shape[1] != self.dims:
-            raise ValueError(f"vector dimension {v.shape[1]} does not match {self.dims}")
-        return v
-
-    @property
-    def ntotal(self):
-        return int(self._lib.lb_gpu_ivf_ntotal(self._h))
-
-    @property
-    def hbm_bytes(self):
-        return int(self._lib.lb_gpu_ivf_hbm_bytes(self._h))
-
-    def centroids(self):
-        out = np.empty((self.nlist, self.dims), np.float32)
-        self._check(self._lib.lb_gpu_ivf_get_centroids(self._h, out.ctypes.data))
-        return out
-
-    def reserve(self, n_total):
-        self._check(self._lib.lb_gpu_ivf_reserve(self._h, n_total))
-
-    def add(self, vectors, ids=None):
-        """append rows [n, dims]; ids (int64 [n]) on every add or on none.  Each add rebuilds the lists of all rows: O(ntotal)."""
-        v = self._vectors(vectors)
-        i = None
-        if ids is not None:
-            i = np.ascontiguousarray(ids, np.int64).reshape(-1)
-            if i.size != v.shape[0]:
-                raise ValueError(f"{i.size} ids for {v.shape[0]} rows")
-        self._check(self._lib.lb_gpu_ivf_add(self._h, v.shape[0], v.ctypes.data, i.ctypes.data if i is not None else None))
-
-    def add_device(self, n, d_vectors, d_ids=None):
-        self._check(self._lib.lb_gpu_ivf_add_device(self._h, n, d_vectors, d_ids))
-
-    def list_sizes(self):
-        out = np.empty(self.nlist, np.int64)
-        self._check(self._lib.lb_gpu_ivf_list_sizes(self._h, out.ctypes.data))
-        return out
-
-    def assignments(self, row0=0, n=None):
-        """the lists of rows [row0, row0 + n) -> int32 [n]"""
-        n = self.ntotal - row0 if n is None else n
-        out = np.empty(max(n, 0), np.int32)
-        self._check(self._lib.lb_gpu_ivf_assignments(self._h, row0, n, out.ctypes.data))
-        return out
-
-    def search(self, queries, k, nprobe, ctx=None):
-        """-> (labels [nq, k], dist [nq, k]): ascending (distance, row) among the rows of the probed lists, padded -1 / FLT_MAX"""
-        v = self._vectors(queries)
-        dist = np.empty((v.shape[0], k), np.float32)
-        labels = np.empty((v.shape[0], k), np.int64)
-        self._check(self._lib.lb_gpu_ivf_search_ctx(self._h, v.shape[0], v.ctypes.data, k, nprobe, dist.ctypes.data, labels.ctypes.data,
-                                                    ctx._h if ctx is not None else None))
-        return labels, dist
-
-    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None):
-        self._check(self._lib.lb_gpu_ivf_search_device_ctx(self._h, nq, d_queries, k, nprobe, d_dist, d_labels, stream,
-                                                           ctx._h if ctx is not None else None))
-
-    def last_search_stats(self):
-        """of the last search: (queries, rows scanned summed over them, the largest per-query count, queries selected from LDS)"""
-        out = (C.c_int64 * 4)()
-        self._check(self._lib.lb_gpu_ivf_last_search_stats(self._h, out))
-        return tuple(int(x) for x in out)
-
-    def set_profiling(self, on):
-        self._check(self._lib.lb_gpu_ivf_set_profiling(self._h, 1 if on else 0))
-
     def last_timing(self):
         """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
-        out = (C.c_float * 4)()
-        self._check(self._lib.lb_gpu_ivf_last_timing(self._h, out))
-        return tuple(float(x) for x in out)
+        return super().last_timing()
 
     def last_build_timing(self):
         """ms of the last profiled build of the visible lists (a filter call or an add under a filter): its launches alone"""
         out = C.c_float(0)
         self._check(self._lib.lb_gpu_ivf_last_build_timing(self._h, C.byref(out)))
         return float(out.value)
-
-    def Close(self):
-        if self._h:
-            self._lib.lb_gpu_ivf_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.Close()
-        except Exception:
-            pass
 
 
 @dataclass

@@ -222,6 +222,53 @@ def test_batches_and_concurrent_searches(oracle, parity):
     h.Close()
 
 
+def test_profiled_search_over_two_batches(oracle):
+    """1025 queries run as two batches.  A profiled search records an event between the steps of each and drains after each: it
+    returns what the unprofiled search returns, and the four slots (probes, plan, scan, select) sum over the batches."""
+    X, Q, C_ = io.parity_case(3000, 16, 8, 1025, seed=1238)  # (the rows of tests/test_gpu_ivfpq.py's eight_lists)
+    lists = io.assign(oracle, 0, 0, X, C_)
+    h = _handle(X, C_)
+    want = h.search(Q, 10, 3)
+    stats = h.last_search_stats()
+    assert h.last_timing() == (0.0, 0.0, 0.0, 0.0) and h.last_build_timing() == 0.0
+    h.set_profiling(True)
+    scanned = _check_search(oracle, h, 0, 0, Q, X, C_, lists, 10, 3, ctx="profiled")
+    assert scanned.size == 1025
+    assert_same(*h.search(Q, 10, 3), *want, "profiled against unprofiled")
+    assert h.last_search_stats() == stats
+    ms = h.last_timing()
+    assert len(ms) == 4 and all(np.isfinite(t) and t >= 0 for t in ms) and sum(ms) > 0, ms
+    h.set_filter((np.arange(X.shape[0]) % 2 == 0).astype(np.uint8))  # the visible lists are built under profiling too
+    assert h.nvisible() == X.shape[0] // 2
+    ms = h.last_build_timing()
+    assert np.isfinite(ms) and ms > 0, ms
+    h.Close()
+
+
+def test_more_probes_than_the_coarse_search_returns(oracle):
+    """2100 lists are more than the LB_MAX_K probes the coarse search returns: fewer than all of them is refused before the device
+    is touched, and with all of them probed the probes are the lists"""
+    X, Q, C_ = io.parity_case(5000, 8, 2100, 5, seed=90)
+    lists = io.assign(oracle, 0, 0, X, C_)
+    h = _handle(X, C_)
+    assert np.array_equal(h.assignments(), lists) and np.array_equal(h.list_sizes(), np.bincount(lists, minlength=2100))
+    dist = np.full((5, 10), 9.0, F)
+    lab = np.full((5, 10), 77, np.int64)
+    assert h._lib.lb_gpu_ivf_search(h._h, 5, Q.ctypes.data, 10, 2099, dist.ctypes.data, lab.ctypes.data) == UNSUPPORTED
+    assert b"nprobe" in h._lib.lb_gpu_ivf_last_error(h._h)
+    assert (dist == 9.0).all() and (lab == 77).all()
+    flat = new_index(8, 0, 0)
+    flat.Add(None, X)
+    fl, fd = flat.SearchBatch(Q, 10)
+    flat.Close()
+    for nprobe in (2100, 5000):
+        lab, dist = h.search(Q, 10, nprobe)
+        assert_same(lab, dist, fl, fd, f"nprobe {nprobe}")
+        assert h.last_search_stats() == (5, 5 * 5000, 5000, 5)
+    _check_search(oracle, h, 0, 0, Q, X, C_, lists, 10, 40, ctx="nprobe 40 of 2100")
+    h.Close()
+
+
 def test_more_pairs_than_one_grid_dimension(oracle):
     """1024 queries x 33 probes = 33,792 (query, probe) pairs: more than the 32,768 the list scan lays along grid dimension y,
     so the rest go along z.  64 lists of ten rows: the grid is the point, not the rows."""

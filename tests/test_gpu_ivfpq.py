@@ -243,6 +243,56 @@ def test_batches_and_concurrent_searches(oracle, parity):
     h.Close()
 
 
+@pytest.fixture(scope="module")
+def eight_lists(oracle):
+    """3000 rows of 16 dimensions over 8 lists, M = 4, with the oracle's lists at order 0 and codes: the rows of
+    tests/test_gpu_ivf.py's profiled search"""
+    X, _, C_, cb = pqo.parity_case(16, 4, n=3000, nlist=8)
+    return X, C_, cb, pqo.assign(oracle, 0, X, C_), pqo.encode(oracle, cb, X)
+
+
+def test_profiled_search_over_two_batches(oracle, eight_lists):
+    """1025 queries run as two batches.  A profiled search records an event between the steps of each and drains after each: it
+    returns what the unprofiled search returns, and the five slots (probes, plan, tables, scan, select) sum over the batches."""
+    X, C_, cb, lists, codes = eight_lists
+    Q = np.random.default_rng(8).standard_normal((1025, X.shape[1])).astype(F)
+    h = _handle(X, C_, cb)
+    want = h.search(Q, 10, 3)
+    stats = h.last_search_stats()
+    assert h.last_timing() == (0.0,) * 5
+    h.set_profiling(True)
+    scanned = _check_search(oracle, h, cb, 0, Q, C_, lists, codes, 10, 3, ctx="profiled")
+    assert scanned.size == 1025
+    assert_same(*h.search(Q, 10, 3), *want, "profiled against unprofiled")
+    assert h.last_search_stats() == stats
+    ms = h.last_timing()
+    assert len(ms) == 5 and all(np.isfinite(t) and t >= 0 for t in ms) and sum(ms) > 0, ms
+    h.Close()
+
+
+@pytest.mark.parametrize("order", [0, 1])
+def test_the_partition_is_the_ivf_flat_handle_s(oracle, eight_lists, order):
+    """the same centroids and rows, added in three pieces with ids: both handles hold the partition the oracle assigns"""
+    from longbow_amd import ivf
+    X, C_, cb, lists, _ = eight_lists
+    if order:
+        lists = pqo.assign(oracle, order, X, C_)
+    ids = np.random.default_rng(12).permutation(1 << 20)[:X.shape[0]].astype(np.int64) + (1 << 41)
+    codes_h = _handle(X[:0], C_, cb, order)
+    rows_h = ivf.IVFFlat(C_, 0, order)
+    r0 = 0
+    for cnt in (127, 1000, 1873):
+        for h in (codes_h, rows_h):
+            h.add(X[r0:r0 + cnt], ids[r0:r0 + cnt])
+        r0 += cnt
+    assert r0 == X.shape[0] and codes_h.ntotal == rows_h.ntotal == r0
+    assert np.array_equal(codes_h.assignments(), lists) and np.array_equal(rows_h.assignments(), lists)
+    sizes = np.bincount(lists, minlength=C_.shape[0])
+    assert np.array_equal(codes_h.list_sizes(), sizes) and np.array_equal(rows_h.list_sizes(), sizes)
+    for h in (codes_h, rows_h):
+        h.Close()
+
+
 # 9 ---------------------------------------------------------------------------------------------------------------------------
 def test_every_list_probed_without_the_coarse_search(oracle):
     """2100 lists are more than the LB_MAX_K probes the coarse search returns: with all of them probed the probes are the lists"""
