@@ -126,6 +126,38 @@ def order_sensitive_rows(n=3000, dims=4, seed=7):
     return (10.0 ** rng.uniform(-3.0, 4.0, (n, dims))).astype(F)
 
 
+def few_pattern_rows(seed=77, n=1000, dims=24, patterns=5):
+    """n rows, each one of `patterns` integer-valued patterns in [-8, 8]: every sum is exact, so the mean of a cluster that holds
+    one pattern is that pattern, bit for bit.  With more centroids than patterns most clusters are empty after every iteration
+    and are re-seeded from draw(seed, m, K + it*K + c); a re-seeded centroid ties with the holder of its pattern and the lower
+    index takes the rows, so the result depends on every term of the draw."""
+    return few_pattern_case(1, 1, seed, n, dims, patterns)[0]
+
+
+def few_pattern_case(M, K, seed=77, n=1000, dims=24, patterns=5):
+    """-> (few_pattern_rows(seed), init rows [M, K] as permutations from the same generator).  Train it with `seed` as well."""
+    rng = np.random.default_rng(seed)
+    P = rng.integers(-8, 9, (patterns, dims))
+    X = P[rng.integers(0, patterns, n)].astype(F)
+    rows = np.stack([rng.permutation(n)[:K] for _ in range(M)]).astype(np.int64)
+    return X, rows
+
+
+FEW_PATTERN_CASES = ((1, 16), (2, 16), (3, 40))  # (M, K) at 24 dimensions: sub = 24 (the generic E-step), 12 and 8 (templated)
+
+
+def chain_order_rows(sub, K=256, levels=64, seed=9):
+    """K rows that are permutations of one vector (the init rows: train with init rows 0 .. K-1), then `levels` rows a * (1, ..., 1).
+    The differences of such a row to every centroid are one multiset in K orders, so its K sums are equal in exact arithmetic and
+    a few ulp apart in f32: which centroid is the first strict minimum depends on the order in which the E-step adds -- which
+    chain an element goes to, and how the chains combine."""
+    rng = np.random.default_rng(seed)
+    v = (rng.choice([-1.0, 1.0], sub) * 10.0 ** rng.uniform(-1.0, 1.0, sub)).astype(F)
+    cent = np.stack([v[rng.permutation(sub)] for _ in range(K)])
+    a = rng.uniform(-1.0, 1.0, levels).astype(F)
+    return np.concatenate((cent, a[:, None] * np.ones((1, sub), F)))
+
+
 def sqrt_tie_rows():
     """rows 0, 1 (the init rows) and 2 = the origin, sub = 2: row 2's sums to the two centroids are 1 + 3 ulp and 1 + 2 ulp,
     whose float32(sqrt(float64(.))) are equal.  The squared compare takes centroid 1, the sqrt compare (encode) centroid 0."""

@@ -401,6 +401,7 @@ def test_python_mirror(oracle, parity):
 
 
 def test_train_is_train_kmeans():
+    """the templated 16 form; tests/test_gpu_coarse_train.py holds ivf.train at the shapes a coarse quantiser has"""
     from longbow_amd import ivf
     gpu_or_skip()
     rng = np.random.default_rng(11)

@@ -1,6 +1,10 @@
 """lb_gpu_pq_train on the GPU against tests/kmeans_oracle.py: the blob bytes and iters_out must equal the helper's exactly
-(Lloyd's iteration is deterministic once the draws are fixed).  Shapes: every templated SubDim and the generic form (5),
-row counts around the 256-row workgroup and the 4096-row ordering chunk, small K, empty clusters, skew, the stop rule."""
+(Lloyd's iteration is deterministic once the draws are fixed).  Shapes: every templated SubDim (1, 2, 4, 8, 12, 16, 32) and the
+generic form (no 4-wide step: 3; tails of 1, 2, 3: 5, 6, 7; multiples of 4 without a template: 20, 24, 100), row counts around the
+256-row workgroup, the 4096-row ordering chunk and the 64-row steps past a chunk, K from 1 to 256 on and off the 64-lane wave over
+several chunks, clusters that stay empty in every iteration of every subspace, rows whose assignment is decided by the order of
+the E-step's additions, skew, the stop rule, a caller's stream.  tests/test_gpu_coarse_train.py holds the coarse quantiser's
+shapes (M = 1, sub = dims up to 8192)."""
 import numpy as np
 import pytest
 
@@ -36,6 +40,58 @@ def test_k256_shapes(sub, n, M):
     rng = np.random.default_rng(1000 * sub + n + M)
     X = rng.standard_normal((n, M * sub)).astype(F)
     _check(X, M, 256, 3, _rows(rng, M, 256, n))
+
+
+@pytest.mark.parametrize("M,n", [(1, 257), (1, 1000), (3, 257), (3, 1000)])
+def test_k256_sub32(M, n):
+    """km_estep_kernel<32>: the largest codebook in LDS, 32 KB"""
+    rng = np.random.default_rng(32000 + n + M)
+    X = rng.standard_normal((n, M * 32)).astype(F)
+    _check(X, M, 256, 3, _rows(rng, M, 256, n))
+
+
+def test_k100_sub32_two_chunks():
+    rng = np.random.default_rng(32100)
+    X = rng.standard_normal((4099, 32)).astype(F)
+    _check(X, 1, 100, 3, _rows(rng, 1, 100, 4099))
+
+
+@pytest.mark.parametrize("M", [1, 2])
+@pytest.mark.parametrize("sub", [3, 6, 7, 20, 24, 100])
+def test_k256_generic_shapes(sub, M):
+    """km_estep_generic_kernel: no main block (3), tails of 2 and 3 (6, 7), multiples of 4 without a template (20, 24, 100)"""
+    rng = np.random.default_rng(7000 + 10 * sub + M)
+    X = rng.standard_normal((300, M * sub)).astype(F)
+    _check(X, M, 256, 3, _rows(rng, M, 256, 300))
+
+
+@pytest.mark.parametrize("K,n,sub,M", [(65, 4500, 8, 1), (65, 4500, 8, 2), (100, 8193, 5, 1), (100, 8193, 5, 2), (200, 5000, 100, 1),
+                                       (255, 4500, 20, 1)])
+def test_k_off_the_wave_over_several_chunks(K, n, sub, M):
+    """km_scan_kernel's idle lanes c >= K and km_scatter_kernel's eight-ballot rank with keys that stop short of a bit pattern"""
+    rng = np.random.default_rng(K * 10000 + n + M)
+    X = rng.standard_normal((n, M * sub)).astype(F)
+    _check(X, M, K, 3, _rows(rng, M, K, n))
+
+
+@pytest.mark.parametrize("n", [4096, 4097, 4159, 4160, 4161, 8192, 8193])
+def test_chunk_and_wave_edges(n):
+    """a full last chunk, one row past it, and the 64-row steps past a chunk where km_scatter_kernel leaves its step loop"""
+    rng = np.random.default_rng(n)
+    X = rng.standard_normal((n, 8)).astype(F)
+    _check(X, 2, 16, 3, _rows(rng, 2, 16, n))
+
+
+@pytest.mark.parametrize("seed", [77, 78])
+@pytest.mark.parametrize("M,K,dims", [(M, K, 24) for M, K in ko.FEW_PATTERN_CASES] + [(1, 16, 20)])
+def test_clusters_empty_in_every_iteration_of_every_subspace(M, K, dims, seed):
+    """ko.few_pattern_case (tests/test_kmeans_semantics.py holds its properties): at least K - 5 clusters of every subspace are
+    re-seeded in every iteration, and the result changes with the iteration, the seed and the subspace of the draw.  dims 24 at
+    M = 1 and dims 20 go through the generic E-step, M = 2 and 3 through the templated 12 and 8."""
+    X, rows = ko.few_pattern_case(M, K, seed)
+    X = np.ascontiguousarray(X[:, :dims])
+    for max_iter in (1, 2, 3, 6):
+        _check(X, M, K, max_iter, rows, seed=seed)
 
 
 def test_config4_geometry():
@@ -81,6 +137,16 @@ def test_e_step_is_not_encode():
     X = ko.sqrt_tie_rows()
     cb, _ = _check(X, 1, 2, 1, np.array([[0, 1]], np.int64))
     assert cb[0, 0].tobytes() == X[0].tobytes()  # (the sqrt compare would have moved row 2 to centroid 0)
+
+
+@pytest.mark.parametrize("sub", [7, 12, 32, 100])
+def test_e_step_adds_in_the_reference_order(sub):
+    """ko.chain_order_rows: every centroid is the same distance from a row in exact arithmetic, so the assignment is decided by
+    which chain each element is added to and how the four chains combine (tests/test_kmeans_semantics.py: a sequential sum, the
+    last 4-wide step in chain 0 or a pairwise total move at least a quarter of the rows)"""
+    X = ko.chain_order_rows(sub)
+    _check(X, 1, 256, 2, np.arange(256, dtype=np.int64)[None])
+    _check(np.concatenate((X[:, ::-1], X), axis=1), 2, 256, 2, np.stack((np.arange(256), np.arange(256))).astype(np.int64))
 
 
 def test_skew_across_workgroups_and_chunks():
@@ -168,6 +234,48 @@ def test_rows_without_an_admissible_centroid_are_refused():
     X[311, 5] = 0.0
     rc, blob = run(X, 2, 8, rows)
     assert rc == 0 and blob.tobytes() == ko.blob(ko.train_pq(X, 2, 8, 3, 0, rows)[0])
+
+
+def test_rows_without_an_admissible_centroid_are_refused_by_the_generic_form():
+    lib = gpu_or_skip()
+    rng = np.random.default_rng(62)
+    X = rng.standard_normal((600, 100)).astype(F)
+    X[311, 97] = np.nan
+    rows = np.arange(8, dtype=np.int64).reshape(1, 8)
+
+    def run():
+        blob = np.full(12 + 8 * 100 * 4, 0xAB, np.uint8)
+        iters = np.zeros(1, np.int32)
+        rc = lib.lb_gpu_pq_train(0, 100, 1, 8, 600, X.ctypes.data, 3, 0, rows.ctypes.data, blob.ctypes.data, blob.size, iters.ctypes.data,
+                                 None)
+        return rc, blob
+
+    rc, blob = run()
+    assert rc == 1 and (blob == 0xAB).all()
+    X[311, 97] = 0.0
+    rc, blob = run()
+    assert rc == 0 and blob.tobytes() == ko.blob(ko.train_pq(X, 1, 8, 3, 0, rows)[0])
+
+
+def test_a_callers_stream():
+    """the rows' upload is enqueued on the caller's stream and nothing waits for it before the call: the training runs behind it"""
+    import torch
+    from longbow_amd import pq
+    gpu_or_skip()
+    rng = np.random.default_rng(52)
+    n = 100000  # (a 9.6 MB upload: still in flight when the call is made)
+    X = rng.standard_normal((n, 24)).astype(F)
+    rows = _rows(rng, 3, 16, n)
+    want, wit = pq.train(X, 3, 16, 2, 9, rows)
+    cb, iters = ko.train_pq(X, 3, 16, 2, 9, rows)
+    assert want == ko.blob(cb) and wit.tolist() == iters.tolist()
+    host = torch.from_numpy(X).pin_memory()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        dX = host.to("cuda", non_blocking=True)
+        blob, git = pq.train_device(n, dX.data_ptr(), 24, 3, 16, 2, 9, rows, stream=s.cuda_stream)
+    assert blob == want and git.tolist() == wit.tolist()
+    torch.cuda.synchronize()
 
 
 def test_a_cancelled_token_stops_the_call():

@@ -172,3 +172,96 @@ def test_a_row_without_an_admissible_centroid_is_refused():
     W[4] = 3e38
     with pytest.raises(ko.NoCentroid):
         ko.train_kmeans(W, 2, 2, rows=[0, 1])
+
+
+# ---- what tests/test_gpu_pq_train.py and tests/test_gpu_coarse_train.py rely on in their inputs ---------------------------------
+@pytest.mark.parametrize("sub", [3, 6, 7, 20])
+def test_helper_equals_a_scalar_lloyd_loop_at_the_generic_shapes(sub):
+    """no 4-wide step (3), a 2- and a 3-element tail (6, 7), five 4-wide steps and no tail (20)"""
+    rng = np.random.default_rng(100 + sub)
+    V = rng.standard_normal((40, sub)).astype(F)
+    rows = ko.init_rows(5, 0, 3, 40)
+    want, wit = _lloyd_scalar(V, 3, 2, rows, 5, 0)
+    got, git = ko.train_kmeans(V, 3, 2, seed=5)
+    assert git == wit == 2 and got.tobytes() == want.tobytes()
+
+
+# iterations run at max_iter = 6, per subspace, of ko.few_pattern_case(M, K, seed) trained with the same seed
+FEW_PATTERN_ITERS = {(1, 16, 77): [3], (2, 16, 77): [3, 3], (3, 40, 77): [2, 3, 3],
+                     (1, 16, 78): [4], (2, 16, 78): [4, 4], (3, 40, 78): [4, 3, 4]}
+
+
+@pytest.mark.parametrize("seed", [77, 78])
+@pytest.mark.parametrize("M,K", ko.FEW_PATTERN_CASES)
+def test_few_pattern_rows_keep_clusters_empty_in_every_iteration(M, K, seed):
+    X, rows = ko.few_pattern_case(M, K, seed)
+    assert X.shape == (1000, 24) and X.tobytes() == ko.few_pattern_rows(seed).tobytes()
+    assert np.unique(X, axis=0).shape[0] == 5 and (X == np.rint(X)).all() and np.abs(X).max() <= 8
+    sub = 24 // M
+    by_iter = [ko.train_pq(X, M, K, mi, seed, rows) for mi in range(7)]
+    assert by_iter[6][1].tolist() == FEW_PATTERN_ITERS[M, K, seed]
+    for m in range(M):
+        V = X[:, m * sub:(m + 1) * sub]
+        for it in range(by_iter[6][1][m]):  # the E-step of iteration `it` sees the centroids of max_iter = it
+            assert by_iter[it][1][m] == it
+            counts = np.bincount(ko.estep(V, by_iter[it][0][m]), minlength=K)
+            assert (counts == 0).sum() >= K - 5 >= 1, (m, it, counts)
+        # exact sums: a centroid is a pattern, and several centroids are the same pattern
+        final = by_iter[6][0][m]
+        assert {c.tobytes() for c in final} <= {v.tobytes() for v in V}
+        assert np.unique(final, axis=0).shape[0] < K
+        # the draw's `it` term, its seed and its m are all observable
+        assert by_iter[1][0][m].tobytes() != by_iter[2][0][m].tobytes()
+        assert ko.train_kmeans(V, K, 6, rows[m], seed + 1, m)[0].tobytes() != final.tobytes()
+        assert ko.train_kmeans(V, K, 6, rows[m], seed, m + 1)[0].tobytes() != final.tobytes()
+    if M >= 2:  # subspaces with equal rows and equal init rows differ by the m of their draws alone
+        V2 = np.concatenate((X[:, :sub], X[:, :sub]), axis=1)
+        for mi in (1, 2, 6):
+            cb, _ = ko.train_pq(V2, 2, K, mi, seed, np.stack((rows[0], rows[0])))
+            assert cb[0].tobytes() == by_iter[mi][0][0].tobytes() and cb[1].tobytes() != cb[0].tobytes()
+
+
+def test_few_pattern_rows_through_the_generic_width():
+    """the first 20 columns (five 4-wide steps, no template) keep the five patterns apart and the clusters empty"""
+    for seed in (77, 78):
+        X, rows = ko.few_pattern_case(1, 16, seed)
+        V = X[:, :20]
+        assert np.unique(V, axis=0).shape[0] == 5
+        one, two = ko.train_kmeans(V, 16, 1, rows[0], seed)[0], ko.train_kmeans(V, 16, 2, rows[0], seed)[0]
+        assert one.tobytes() != two.tobytes()
+        assert (np.bincount(ko.estep(V, one), minlength=16) == 0).sum() >= 11
+
+
+def _unroll4_variant(q, X, last4_in_chain0=False, pairwise_total=False):
+    """l2sq_unroll4 with one thing changed: the last full 4-wide step added to chain 0, or the chains combined as a tree"""
+    n = X.shape[1]
+    main = (n & ~3) - (4 if last4_in_chain0 else 0)
+    acc = [np.zeros(X.shape[0], F) for _ in range(4)]
+    for i in range(n):
+        d = q[i] - X[:, i]
+        u = i % 4 if i < main else 0
+        acc[u] = acc[u] + d * d
+    return (acc[0] + acc[1]) + (acc[2] + acc[3]) if pairwise_total else ((acc[0] + acc[1]) + acc[2]) + acc[3]
+
+
+@pytest.mark.parametrize("sub", [7, 12, 32, 100])
+def test_chain_order_rows_tell_the_summation_orders_apart(sub):
+    X = ko.chain_order_rows(sub)
+    cent, level = X[:256], X[256:]
+    assert X.shape == (320, sub) and all(sorted(c.tolist()) == sorted(cent[0].tolist()) for c in cent)
+    assert all(np.array_equal(_unroll4_variant(c, level), oracle_np.l2sq_unroll4(c, level)) for c in cent[:8])
+    want = ko.estep(level, cent)
+    assert np.unique(want).size >= 16  # no one centroid is the minimum of every row
+
+    def estep(l2sq):
+        best, assign = np.full(64, ko.FLT_MAX, F), np.full(64, -1)
+        for c in range(256):
+            d = l2sq(cent[c], level)
+            lt = d < best
+            best[lt], assign[lt] = d[lt], c
+        return assign
+
+    assert np.array_equal(estep(oracle_np.l2sq_unroll4), want)
+    for other in (oracle_np.l2sq_seq, lambda q, V: _unroll4_variant(q, V, last4_in_chain0=True),
+                  lambda q, V: _unroll4_variant(q, V, pairwise_total=True)):
+        assert (estep(other) != want).sum() >= 16  # a quarter of the rows; 38 to 64 of them do
