@@ -323,14 +323,14 @@ def require_gpu(device=0):
     return lib
 
 
-def check(rc, handle=None, pq=False, lib=None, bq=False, sq8=False, prefix=None):
-    """prefix: the handle's family ("lb_gpu_ivf", ...), whose <prefix>_last_error is asked for the message"""
+def check(rc, handle=None, lib=None, prefix=None):
+    """prefix: the handle's family ("lb_gpu_pq", ...), whose <prefix>_last_error has the message; none: a flat index's lb_gpu_last_error"""
     if rc == LB_OK:
         return
     msg = ""
     if handle:
         lib = lib or load()
-        raw = getattr(lib, prefix + "_last_error")(handle) if prefix else lib.lb_gpu_sq8_last_error(handle) if sq8 else lib.lb_gpu_bq_last_error(handle) if bq else lib.lb_gpu_pq_last_error(handle) if pq else lib.lb_gpu_last_error(handle)
+        raw = getattr(lib, prefix + "_last_error" if prefix else "lb_gpu_last_error")(handle)
         msg = raw.decode() if raw else ""
     if rc == 3:
         raise GPUNotAvailable(rc, msg)

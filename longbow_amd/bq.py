@@ -35,7 +35,7 @@ class BQEncoder(RowFilterMixin):
         self.W = lib.lb_gpu_bq_words(self._h)
 
     def _check(self, rc):
-        _lib.check(rc, self._h, lib=self._lib, bq=True)
+        _lib.check(rc, self._h, lib=self._lib, prefix=self._prefix)
 
     def _codes(self, codes):
         c = np.ascontiguousarray(codes, np.uint64)

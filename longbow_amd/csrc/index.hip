@@ -347,17 +347,15 @@ static int filter_column(lb_gpu_index *h, const T *column, int64_t n, T value, i
 {
     if (!h || op < 0 || op > 5 || voff < 0) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
-    if (h->closed) return LB_ERR_CLOSED;
     if (n != h->n || (n > 0 && !column)) {
         h->set_error("filter column has %lld values, index has %lld rows", (long long)n, (long long)h->n);
         return LB_ERR_INVALID_ARG;
     }
     if (n == 0) { h->has_mask = true; h->rowmap_on = false; return LB_OK; }
-    int rc = LB_OK;
-    try {
+    Lease dcol, dval; // column (and validity bitmap) go up through pooled buffers on the index's own stream
+    return guard(h, h->add_stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
-        // column (and validity bitmap) go up through pooled buffers on the index's own stream
-        Lease dcol(h->device, (size_t)n * sizeof(T)), dval;
+        dcol.reset(h->device, (size_t)n * sizeof(T));
         T *d_col = dcol.as<T>();
         uint8_t *d_val = nullptr;
         LB_HIP(hipMemcpyAsync(d_col, column, (size_t)n * sizeof(T), hipMemcpyHostToDevice, h->add_stream));
@@ -376,10 +374,8 @@ static int filter_column(lb_gpu_index *h, const T *column, int64_t n, T value, i
         LB_HIP(hipStreamSynchronize(h->add_stream));
         h->has_mask = true;
         rebuild_rowmap(h);
-    } catch (const HipErr &e) {
-        rc = fail_hip(h, e);
-    }
-    return rc;
+        return LB_OK;
+    });
 }
 
 int dtype_mismatch(lb_gpu_index *h, int call)
@@ -446,7 +442,7 @@ static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status,
     // (fp16 rows: UNROLL4 is the only order of the reference's F16 functions, internal/simd/simd.go:767-848; int8 rows: the
     // order is accepted and changes nothing, the int8 arithmetic has one form)
     if (h->f16_rows || h->i8_rows) h->order.store(LB_ORDER_UNROLL4);
-    try {
+    const int rc = guard(h, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(device));
         LB_HIP(hipStreamCreateWithFlags(&h->add_stream.h, hipStreamNonBlocking));
         h->d_maxnorm2.alloc(2);
@@ -454,13 +450,12 @@ static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status,
         LB_HIP(hipMemcpy(h->d_maxnorm2.get(), norm_init, sizeof norm_init, hipMemcpyHostToDevice));
         static const int use_vmm = lb_tunable("LB_VMM", 1);
         if (use_vmm) (void)h->vmm.init(device); // on failure: geometric hipMalloc + copy
-    } catch (const HipErr &e) {
-        st(e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP);
-        lb_gpu_index_free(h);
-        return nullptr;
-    }
-    st(LB_OK);
-    return h;
+        return LB_OK;
+    });
+    st(rc);
+    if (rc == LB_OK) return h;
+    lb_gpu_index_free(h);
+    return nullptr;
 }
 
 lb_gpu_index *lb_gpu_index_new(int device, int dim, int metric, int *out_status)
@@ -493,12 +488,9 @@ int64_t lb_gpu_index_hbm_bytes(const lb_gpu_index *h)
 
 void lb_gpu_index_free(lb_gpu_index *h)
 {
-    if (!h) return;
-    {
-        std::unique_lock<std::shared_mutex> g(h->mu);
-        h->closed = true;
-        (void)hipSetDevice(h->device);
-        (void)hipDeviceSynchronize();
+    // the device drained under the writer lock, then what is the flat index's own: the two pools and the corpus buffer; every
+    // other buffer, the streams and the events go with their members
+    handle_free(h, [](lb_gpu_index *h) {
         {
             std::lock_guard<std::mutex> g2(h->ws_mu);
             h->ws_free.clear();
@@ -507,16 +499,10 @@ void lb_gpu_index_free(lb_gpu_index *h)
         if (h->vmm.ok) h->vmm.destroy();
         else if (h->d_X) (void)hipFree(h->d_X);
         h->d_X = nullptr;
-    }
-    delete h; // (every other buffer, the streams and the events go with their members)
+    });
 }
 
-const char *lb_gpu_last_error(const lb_gpu_index *h)
-{
-    if (!h) return "null handle";
-    std::lock_guard<std::mutex> g(h->err_mu);
-    return h->last_error.c_str();
-}
+const char *lb_gpu_last_error(const lb_gpu_index *h) { return handle_last_error(h); }
 
 int lb_gpu_index_set_order(lb_gpu_index *h, int order)
 {
@@ -529,7 +515,6 @@ int lb_gpu_index_set_candidate_mode(lb_gpu_index *h, int mode)
 {
     if (!h || mode < LB_CAND_F32_MFMA || mode > LB_CAND_F16) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
-    if (h->closed) return LB_ERR_CLOSED;
     if (h->f16_rows && mode != LB_CAND_AUTO && mode != LB_CAND_F16) {
         h->set_error("candidate mode %d needs f32 rows; an fp16 index takes AUTO or F16", mode);
         return LB_ERR_UNSUPPORTED;
@@ -542,33 +527,29 @@ int lb_gpu_index_set_candidate_mode(lb_gpu_index *h, int mode)
         h->set_error("split-bf16 candidates need dim %% 32 == 0 (dim = %d)", h->dim);
         return LB_ERR_UNSUPPORTED;
     }
-    try {
+    const int rc = guard(h, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
         h->cand_mode.store(mode);
         if (mode == 1) sync_split_image(h);
         else drop_split_image(h);
         sync_f16_image(h);
-    } catch (const HipErr &e) {
-        h->cand_mode.store(LB_CAND_AUTO);
-        return fail_hip(h, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
+    if (rc != LB_OK) h->cand_mode.store(LB_CAND_AUTO);
+    return rc;
 }
 
 int lb_gpu_index_set_f16_image(lb_gpu_index *h, int mode)
 {
     if (!h || mode < 0 || mode > 1) return LB_ERR_INVALID_ARG;
-    try {
-        std::unique_lock<std::shared_mutex> g(h->mu);
-        if (h->closed) return LB_ERR_CLOSED;
-        if (hipSetDevice(h->device) != hipSuccess) { (void)hipGetLastError(); return LB_ERR_HIP; }
+    std::unique_lock<std::shared_mutex> g(h->mu);
+    return guard(h, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(h->device));
         h->xh_mode.store(mode);
         if (mode) { h->xh_failed = h->xh_shed = false; h->xh_declined_n = 0; }
         sync_f16_image(h);
-    } catch (...) {
-        return LB_ERR_INTERNAL;
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 int64_t lb_gpu_index_f16_image_bytes(const lb_gpu_index *h)
@@ -592,24 +573,20 @@ int lb_gpu_index_reserve(lb_gpu_index *h, int64_t n_total)
 {
     if (!h || n_total < 0) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
-    if (h->closed) return LB_ERR_CLOSED;
-    try {
+    return guard(h, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
         return grow_or_shed(h, n_total);
-    } catch (const HipErr &e) {
-        return fail_hip(h, e);
-    }
+    });
 }
 
 static int add_host(lb_gpu_index *h, int64_t n, const void *vectors, const int64_t *ids, int dtype)
 {
     if (!h || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
-    if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
     if (const int rc = dtype_mismatch(h, dtype)) return rc;
     if (n == 0) return LB_OK;
     if (h->n + n > (int64_t)0xffffffffll) { h->set_error("more than 2^32 rows per device"); return LB_ERR_UNSUPPORTED; }
-    try {
+    return guard(h, h->add_stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
         grow_or_shed(h, h->n + n);
         for (int i = 0; i < 2; i++) {
@@ -653,10 +630,8 @@ static int add_host(lb_gpu_index *h, int64_t n, const void *vectors, const int64
             off += len;
         }
         finish_add(h, n, ids, false);
-    } catch (const HipErr &e) {
-        return fail_hip(h, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 int lb_gpu_index_add(lb_gpu_index *h, int64_t n, const float *vectors, const int64_t *ids)
@@ -676,20 +651,17 @@ static int add_device(lb_gpu_index *h, int64_t n, const void *d_vectors, const i
 {
     if (!h || n < 0 || (n > 0 && !d_vectors)) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
-    if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
     if (const int rc = dtype_mismatch(h, dtype)) return rc;
     if (n == 0) return LB_OK;
     if (h->n + n > (int64_t)0xffffffffll) { h->set_error("more than 2^32 rows per device"); return LB_ERR_UNSUPPORTED; }
-    try {
+    return guard(h, h->add_stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
         grow_or_shed(h, h->n + n);
         LB_HIP(hipMemcpyAsync(reinterpret_cast<char *>(h->d_X) + (size_t)h->n * h->dim * h->elem_bytes(), d_vectors,
                               (size_t)n * h->dim * h->elem_bytes(), hipMemcpyDeviceToDevice, h->add_stream));
         finish_add(h, n, d_ids, true);
-    } catch (const HipErr &e) {
-        return fail_hip(h, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 int lb_gpu_index_add_device(lb_gpu_index *h, int64_t n, const float *d_vectors, const int64_t *d_ids)
@@ -709,18 +681,15 @@ int lb_gpu_index_set_filter(lb_gpu_index *h, const uint8_t *mask, int64_t n)
 {
     if (!h) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
-    if (h->closed) return LB_ERR_CLOSED;
     if (!mask) { h->has_mask = false; h->rowmap_on = false; h->smap_valid = false; return LB_OK; }
     if (n != h->n) { h->set_error("filter mask has %lld bytes, index has %lld rows", (long long)n, (long long)h->n); return LB_ERR_INVALID_ARG; }
-    try {
+    return guard(h, h->add_stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
         if (n > 0) LB_HIP(hipMemcpy(h->d_mask.get(), mask, (size_t)n, hipMemcpyHostToDevice));
         h->has_mask = true;
         rebuild_rowmap(h);
-    } catch (const HipErr &e) {
-        return fail_hip(h, e);
-    }
-    return LB_OK;
+        return LB_OK;
+    });
 }
 
 int lb_gpu_index_filter_int64(lb_gpu_index *h, const int64_t *column, int64_t n, int64_t value, int op,

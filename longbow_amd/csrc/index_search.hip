@@ -214,7 +214,7 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                    int nsel, int k, int mode, float *d_dist, int64_t *d_lab, bool prof)
 {
     const int metric = h->metric, order = h->order.load();
-    const RowView rv = row_view(h);
+    const IndexRowView rv = row_view(h);
     const int64_t n = rv.n;
     const uint8_t *mask = rv.mask;
     const int kkeep = std::max(k, 1);
@@ -520,7 +520,7 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
                     int64_t *d_lab, bool prof)
 {
     static const int mfma_minq = lb_tunable("LB_I8_MFMA_MINQ", 16);
-    const RowView rv = row_view(h);
+    const IndexRowView rv = row_view(h);
     const int kkeep = std::max(k, 1);
     SamplePlan sp;
     if (nq >= mfma_minq && mfma_i8_supported(h->metric, h->dim, h->d_X, d_q8)) sp = sample_plan(rv.n, kkeep, w->cap);
@@ -592,7 +592,7 @@ KeyBound key_bound(const lb_gpu_index *h, int split, bool have_xh)
 
 // the rows behind the plan's sampled positions: the index's shared map (built by the first search after a change), or when that
 // holds another plan, the workspace's own
-const uint32_t *sample_map(lb_gpu_index *h, Workspace *w, hipStream_t s, const RowView &rv, const SamplePlan &sp)
+const uint32_t *sample_map(lb_gpu_index *h, Workspace *w, hipStream_t s, const IndexRowView &rv, const SamplePlan &sp)
 {
     {
         std::lock_guard<std::mutex> g(h->smap_mu);
@@ -652,7 +652,7 @@ int run_batch(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float 
               const Route &route, int kc, bool narrow_ok, bool have_xh, std::vector<int> &bad, bool &gave_up)
 {
     const int metric = h->metric, order = h->order.load();
-    const RowView rv = row_view(h);
+    const IndexRowView rv = row_view(h);
     const int64_t n = rv.n;
     const uint8_t *mask = rv.mask;
     const SamplePlan sp = sample_plan(n, kc, w->cap);
@@ -856,7 +856,7 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     static const int narrow_min = lb_tunable("LB_NARROW_MINQ", 5);
     static const int f16_kc_mult = lb_tunable("LB_F16_KC_MULT", 0);
     // the same for every attempt (the caller holds the index's shared lock)
-    const RowView rv = row_view(h);
+    const IndexRowView rv = row_view(h);
     const int64_t n = rv.n; // positions to walk: corpus rows, or the visible-row list under a selective filter
     const int cmode = h->cand_mode.load();
     const bool narrow_ok = !h->f16_rows && h->dim % 32 == 0 && ((reinterpret_cast<uintptr_t>(d_q) & 15) == 0);
@@ -993,6 +993,26 @@ void finish_profile(lb_gpu_index *h, Workspace *w)
     }
 }
 
+// What a search entry point answers before it touches the device, in this order: LB_ERR_INVALID_ARG, a call of another element
+// type than the index's, LB_OK for no queries (neither k nor the context is looked at), k beyond LB_MAX_K, the context.
+int search_args(lb_gpu_index *h, int64_t nq, const void *queries, int k, const void *dist, const void *labels, const lb_cancel *ctx, int dtype)
+{
+    if (h && nq == 0 && k > 0) return dtype_mismatch(h, dtype);
+    return knn_args(h, nq, queries, k, dist, labels, ctx, [&] { return dtype_mismatch(h, dtype); });
+}
+
+// A search's workspace: it goes back to the pool when the call ends, unless the call dropped it.
+struct WsLoan {
+    lb_gpu_index *h;
+    std::unique_ptr<Workspace> w;
+    ~WsLoan()
+    {
+        if (!w) return;
+        w->ctx = nullptr;
+        release_ws(h, std::move(w));
+    }
+};
+
 } // namespace
 
 extern "C" {
@@ -1004,25 +1024,25 @@ int lb_gpu_index_last_route(const lb_gpu_index *h) { return h ? h->last_route.lo
 static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
                          const lb_cancel *ctx, int dtype)
 {
-    if (!h || nq < 0 || k <= 0 || (nq > 0 && (!d_queries || !d_dist || !d_labels))) return LB_ERR_INVALID_ARG;
+    int rc = search_args(h, nq, d_queries, k, d_dist, d_labels, ctx, dtype);
+    if (rc != LB_OK || nq == 0) return rc;
     std::shared_lock<std::shared_mutex> g(h->mu);
-    if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-    if (const int rc = dtype_mismatch(h, dtype)) return rc;
-    if (nq == 0) return LB_OK;
-    if (k > LB_MAX_K) { h->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
-    if (const int st = ctx_state(ctx)) { h->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded"); return st; }
 #ifdef LB_DIAG
     if (g_search_fail_next.exchange(0) != 0) { h->set_error("search failure forced by lb_debug_search_fail_next"); return LB_ERR_INTERNAL; }
 #endif
-    std::unique_ptr<Workspace> w;
-    hipStream_t s = nullptr;
-    try {
+    WsLoan loan{h, nullptr};
+    int kc = 0;
+    rc = guard(h, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
-        int kc;
         uint32_t cap;
         cand_geometry(k, kc, cap);
-        w = acquire_ws(h, (int)std::min<int64_t>(nq, kMaxBatch), cap);
-        s = stream ? (hipStream_t)stream : w->stream;
+        loan.w = acquire_ws(h, (int)std::min<int64_t>(nq, kMaxBatch), cap);
+        return LB_OK;
+    });
+    if (rc != LB_OK) return rc;
+    Workspace *w = loan.w.get();
+    hipStream_t s = stream ? (hipStream_t)stream : w->stream;
+    rc = guard(h, s, [&]() -> int {
         const bool prof = h->profiling.load() != 0;
         w->ev_used = 0;
         w->ctx = ctx;
@@ -1043,39 +1063,32 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
                 } else {
                     bq_f32 = static_cast<const float *>(d_queries) + (size_t)q0 * h->dim;
                 }
-                int rc = h->i8_rows ? search_batch_i8(h, w.get(), s, bq, bq_f32, static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, k,
-                                                      d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
-                                    : search_batch_device(h, w.get(), s, bq, bq_f32, k, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k,
-                                                          kc, prof, fallbacks);
-                if (rc != LB_OK) { w->ctx = nullptr; release_ws(h, std::move(w)); return rc; }
+                const int brc = h->i8_rows ? search_batch_i8(h, w, s, bq, bq_f32, static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, k,
+                                                             d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
+                                           : search_batch_device(h, w, s, bq, bq_f32, k, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k,
+                                                                 kc, prof, fallbacks);
+                if (brc != LB_OK) return brc;
             }
         }
         LB_LAUNCH_CHECK();
         LB_HIP(hipStreamSynchronize(s));
         h->last_fallbacks.store(fallbacks);
-        if (prof) finish_profile(h, w.get());
-        w->ctx = nullptr;
-        release_ws(h, std::move(w));
-    } catch (const HipErr &e) {
-        return fail_hip(h, e);
-    } catch (const CtxErr &c) {
-        // stop enqueuing, let what is already on the stream finish (it writes into the caller's buffers), report.
-        // The output buffers hold unspecified values, as after any failed call.
-        (void)hipStreamSynchronize(s);
+        if (prof) finish_profile(h, w);
+        return LB_OK;
+    });
+    if (rc == LB_ERR_CANCELLED || rc == LB_ERR_DEADLINE) {
+        // The context stopped the enqueuing and guard() let what was already on the stream finish (it writes into the caller's
+        // buffers, which hold unspecified values as after any failed call).  A fused launch may have been skipped between its
+        // host-side bookkeeping and the device: re-base the ticket
         (void)hipGetLastError();
-        if (w) {
-            w->ctx = nullptr;
-            w->ev_used = 0;
-            // a fused launch may have been skipped between its host-side bookkeeping and the device: re-base the ticket
-            (void)hipMemsetAsync(w->d_fsync.get(), 0, sizeof(uint32_t), s);
-            (void)hipStreamSynchronize(s);
-            w->fs_base = 0;
-            release_ws(h, std::move(w));
-        }
-        h->set_error(c.code == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded");
-        return c.code;
+        w->ev_used = 0;
+        (void)hipMemsetAsync(w->d_fsync.get(), 0, sizeof(uint32_t), s);
+        (void)hipStreamSynchronize(s);
+        w->fs_base = 0;
+    } else if (rc == LB_ERR_HIP || rc == LB_ERR_OOM || rc == LB_ERR_INTERNAL) {
+        loan.w.reset(); // what the workspace holds on the device is unknown: it is freed, not pooled
     }
-    return LB_OK;
+    return rc;
 }
 
 int lb_gpu_index_search_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
@@ -1119,24 +1132,18 @@ int lb_cancel_state(const lb_cancel *c) { return ctx_state(c); }
 // (dtype: the requests' queries are fp16 -- 2 bytes an element -- or int8 -- 1 byte; those are never combined)
 static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, int k, const lb_cancel *ctx, int dtype = 0)
 {
-    const size_t qelem = dtype == 2 ? 1 : dtype == 1 ? 2 : sizeof(float);
     int64_t nq = 0;
     for (int i = 0; i < nreq; i++) nq += reqs[i]->nq;
-    // (before any staging is sized: nq * k * 12 bytes of pinned + device memory per call)
-    if (k > LB_MAX_K) { h->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
+    // (before any staging is sized: nq * k * 12 bytes of pinned + device memory per call; the caller has answered k)
     if (nq > ((int64_t)1 << 40) / ((int64_t)h->dim + 3 * (int64_t)k)) { h->set_error("batch too large"); return LB_ERR_INVALID_ARG; }
-    const size_t qb = (size_t)nq * h->dim * qelem;
-    const size_t db = (((size_t)nq * k * sizeof(float)) + 15) & ~(size_t)15;
-    const size_t lb_ = (size_t)nq * k * sizeof(int64_t);
-    const size_t qoff = 0, doff = (qb + 15) & ~(size_t)15, loff = doff + db, total = loff + lb_;
+    const HostSlab sl(nq, (size_t)h->dim * h->elem_bytes(), k);
     std::unique_ptr<HostStage> st;
-    int rc = LB_OK;
-    try {
+    return guard(h, nullptr, [&]() -> int { // (the staging is the call's own, not pooled while it is in use: nothing to drain for)
         LB_HIP(hipSetDevice(h->device));
         {
             std::lock_guard<std::mutex> g(h->ws_mu);
             for (size_t i = 0; i < h->hs_free.size(); i++)
-                if (h->hs_free[i]->d_buf.count() >= total) {
+                if (h->hs_free[i]->d_buf.count() >= sl.total) {
                     st = std::move(h->hs_free[i]);
                     h->hs_free.erase(h->hs_free.begin() + (long)i);
                     break;
@@ -1146,63 +1153,38 @@ static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, in
             st = std::make_unique<HostStage>();
             st->device = h->device;
             LB_HIP(hipStreamCreateWithFlags(&st->stream.h, hipStreamNonBlocking));
-            st->d_buf.alloc(std::max<size_t>(total, 1u << 20));
+            st->d_buf.alloc(std::max<size_t>(sl.total, 1u << 20));
             st->h_buf.alloc(st->d_buf.count());
         }
         char *hb = st->h_buf.get(), *dbuf = st->d_buf.get();
-        {
-            size_t off = qoff;
-            for (int i = 0; i < nreq; i++) {
-                const size_t b = (size_t)reqs[i]->nq * h->dim * qelem;
-                std::memcpy(hb + off, reqs[i]->q, b);
-                off += b;
-            }
-        }
-        LB_HIP(hipMemcpyAsync(dbuf + qoff, hb + qoff, qb, hipMemcpyHostToDevice, st->stream));
-        // Small results (a few queries: the latency path) are written by the last kernel straight into the pinned slab -- no
-        // device-to-host copy and no second wait behind it (~20 us of a 0.35 ms call); the search's own stream
-        // synchronisation is what makes them visible.  Large results go through HBM and one DMA.
-        const bool direct = db + lb_ <= ((size_t)64 << 10);
-        char *obuf = direct ? hb : dbuf;
-        rc = search_device(h, nq, dbuf + qoff, k, reinterpret_cast<float *>(obuf + doff), reinterpret_cast<int64_t *>(obuf + loff),
-                           st->stream, ctx, dtype);
+        sl.gather(reqs, nreq, hb);
+        LB_HIP(hipMemcpyAsync(dbuf, hb, sl.qb, hipMemcpyHostToDevice, st->stream));
+        // (direct results: the search's own stream synchronisation is what makes them visible; large ones go through HBM and one DMA)
+        char *obuf = sl.direct ? hb : dbuf;
+        const int rc = search_device(h, nq, dbuf, k, reinterpret_cast<float *>(obuf + sl.doff), reinterpret_cast<int64_t *>(obuf + sl.loff),
+                                     st->stream, ctx, dtype);
         if (rc == LB_OK) {
-            if (!direct) {
-                LB_HIP(hipMemcpyAsync(hb + doff, dbuf + doff, db + lb_, hipMemcpyDeviceToHost, st->stream));
+            if (!sl.direct) {
+                LB_HIP(hipMemcpyAsync(hb + sl.doff, dbuf + sl.doff, sl.db + sl.lb, hipMemcpyDeviceToHost, st->stream));
                 LB_HIP(hipStreamSynchronize(st->stream));
             }
-            size_t row = 0;
-            for (int i = 0; i < nreq; i++) {
-                const size_t n = (size_t)reqs[i]->nq * k;
-                std::memcpy(reqs[i]->dist, hb + doff + row * sizeof(float), n * sizeof(float));
-                std::memcpy(reqs[i]->labels, hb + loff + row * sizeof(int64_t), n * sizeof(int64_t));
-                row += n;
-            }
+            sl.scatter(reqs, nreq, hb, k);
         }
         std::lock_guard<std::mutex> g(h->ws_mu);
         if (h->hs_free.size() < 8) h->hs_free.push_back(std::move(st));
-    } catch (const HipErr &e) {
-        rc = fail_hip(h, e);
-    } catch (...) {
-        h->set_error("internal error (exception)");
-        rc = LB_ERR_INTERNAL;
-    }
-    return rc;
+        return rc;
+    });
 }
 
 // the host-pointer entry points; dtype: the element type of `queries` (0 float32, 1 fp16 bits, 2 int8: host_search_multi copies bytes)
 static int host_search(lb_gpu_index *h, int64_t nq, const void *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx, int dtype)
 {
-    if (!h || nq < 0 || k <= 0 || (nq > 0 && (!queries || !dist || !labels))) return LB_ERR_INVALID_ARG;
-    if (nq == 0) return LB_OK;
-    {
-        std::shared_lock<std::shared_mutex> g(h->mu);
-        if (h->closed) { h->set_error("index is closed"); return LB_ERR_CLOSED; }
-        if (const int rc = dtype_mismatch(h, dtype)) return rc;
-    }
+    if (h && nq == 0 && k > 0) return LB_OK; // (a host call of no queries does not look at the index's element type either)
+    // (without the context: a host call answers it after the size of its batch, in the device search)
+    if (const int rc = search_args(h, nq, queries, k, dist, labels, nullptr, dtype)) return rc;
     // (a call with a cancellation context is searched on its own: its deadline is not its neighbours'; fp16 and int8 calls too)
     HostReq me{static_cast<const float *>(queries), nq, dist, labels, k};
-    if (dtype == 0 && !ctx && nq <= SearchCombiner::kMaxNq && k <= LB_MAX_K && h->combiner.on.load() != 0)
+    if (dtype == 0 && !ctx && nq <= SearchCombiner::kMaxNq && h->combiner.on.load() != 0)
         return h->combiner.search(me, [h](HostReq *const *reqs, int n, int kk) { return host_search_multi(h, reqs, n, kk, nullptr); });
     HostReq *one = &me;
     return host_search_multi(h, &one, 1, k, ctx, dtype);
@@ -1232,20 +1214,8 @@ int lb_gpu_index_search_i8(lb_gpu_index *h, int64_t nq, const int8_t *queries, i
     return lb_gpu_index_search_i8_ctx(h, nq, queries, k, dist, labels, nullptr);
 }
 
-int lb_gpu_index_set_search_combining(lb_gpu_index *h, int enable)
-{
-    if (!h) return LB_ERR_INVALID_ARG;
-    h->combiner.on.store(enable ? 1 : 0);
-    return LB_OK;
-}
-
-int lb_gpu_index_combining_stats(const lb_gpu_index *h, int64_t out[2])
-{
-    if (!h || !out) return LB_ERR_INVALID_ARG;
-    out[0] = h->combiner.batches.load();
-    out[1] = h->combiner.requests.load();
-    return LB_OK;
-}
+int lb_gpu_index_set_search_combining(lb_gpu_index *h, int enable) { return combining_set(h, enable); }
+int lb_gpu_index_combining_stats(const lb_gpu_index *h, int64_t out[2]) { return combining_stats(h, out); }
 
 int lb_gpu_index_search(lb_gpu_index *h, int64_t nq, const float *queries, int k, float *dist, int64_t *labels)
 {

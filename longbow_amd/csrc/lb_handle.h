@@ -1,10 +1,12 @@
-// lb_handle.h -- the host shell of a code-index handle (lb_gpu_pq, lb_gpu_bq, lb_gpu_sq8) and of the IVF handles (lb_gpu_ivf,
-// lb_gpu_ivfpq): what the C-ABI translation units pq.hip, bq.hip, sq8.hip, ivf.hip and ivfpq.hip share beyond lb_host.h; what
-// the last two share beyond it is in lb_ivf_host.h.  Header-only, nothing exported.
+// lb_handle.h -- the host shell of every handle behind the C ABI: the flat index (lb_gpu_index: index.hip, index_search.hip,
+// simd_api.hip, through lb_index.h), the code-index handles (lb_gpu_pq, lb_gpu_bq, lb_gpu_sq8) and the IVF handles (lb_gpu_ivf,
+// lb_gpu_ivfpq; what those two share beyond this is in lb_ivf_host.h).  HandleCore, the error functions, guard() and HostSlab
+// serve all of them and the handle-less calls of simd_api.hip (guard_device); CodeHandle and what follows it serve the code and
+// IVF handles.  Header-only, nothing exported.
 //
-// The rules every entry point of these handles keeps:
-//   * nothing but an lb_status leaves the library: the body of an entry point runs inside guard();
-//   * a pooled buffer (Lease) that a stream-enqueuing body uses is declared OUTSIDE guard() and the stream is passed to it: an
+// The rules every entry point keeps:
+//   * nothing but an lb_status leaves the library: the body of an entry point runs inside guard() or guard_device();
+//   * a pooled buffer (Lease) that a stream-enqueuing body uses is declared OUTSIDE the guard and the stream is passed to it: an
 //     error drains the stream before the buffer goes back to the pool, where a concurrent call could lease it;
 //   * searches and reads take `mu` shared; adds, reserve and whatever changes the row filter take it alone.
 #pragma once
@@ -16,21 +18,19 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <mutex>
 #include <new>
 #include <shared_mutex>
 #include <string>
 
 namespace lb {
+#pragma GCC visibility push(hidden) // nothing here, the instantiations over the handles' types included, is exported
 
-// What every code-index handle has; lb_gpu_bq, lb_gpu_sq8 and lb_gpu_pq derive from it and add their own buffers.  Those are
-// destroyed before `stream` (members of the derived struct go first): harmless, every *_free drains the device under the
-// writer lock before it deletes the handle.
-struct CodeHandle {
-    int device = 0, dims = 0;
+// What every handle has: its device, the reader / writer lock of its entry points and the text of its last failure.
+struct HandleCore {
+    int device = 0;
     std::shared_mutex mu;
-    int64_t n = 0, capacity = 0; // rows stored, rows allocated
-    Stream stream;
     mutable std::mutex err_mu;
     std::string last_error;
     void set_error(const char *fmt, ...)
@@ -48,40 +48,107 @@ struct CodeHandle {
     }
 };
 
-// (unlike fail_hip of lb_index.h this leaves HIP's sticky error as it is)
-inline int hip_fail(CodeHandle *h, const HipErr &e)
+// What every code-index handle has; lb_gpu_bq, lb_gpu_sq8 and lb_gpu_pq derive from it and add their own buffers.  Those are
+// destroyed before `stream` (members of the derived struct go first): harmless, every *_free drains the device under the
+// writer lock before it deletes the handle.
+struct CodeHandle : HandleCore {
+    int dims = 0;
+    int64_t n = 0, capacity = 0; // rows stored, rows allocated
+    Stream stream;
+};
+
+// A failed HIP call as a status and, on a handle (h is null in the handle-less calls), its text.  The failure is reported through
+// the return code: HIP's per-thread last error is cleared, so that the thread's next entry point does not find it in its
+// LB_LAUNCH_CHECK and report a kernel launch that never failed.
+inline int hip_fail(HandleCore *h, const HipErr &e)
 {
-    h->set_error("HIP error %d (%s) in %s", (int)e.e, hipGetErrorString(e.e), e.what);
+    (void)hipGetLastError();
+    if (h) h->set_error("HIP error %d (%s) in %s", (int)e.e, hipGetErrorString(e.e), e.what);
     return e.e == hipErrorOutOfMemory ? LB_ERR_OOM : LB_ERR_HIP;
 }
 
-inline int ctx_fail(CodeHandle *h, int st)
+inline int ctx_fail(HandleCore *h, int st)
 {
-    h->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded");
+    if (h) h->set_error(st == LB_ERR_CANCELLED ? "context canceled" : "context deadline exceeded");
     return st;
 }
 
 // The shell of an entry point: nothing but an lb_status leaves the library.  `s`, where given, is the stream the body
-// enqueued on: it is drained before the answer, so that no kernel still runs on what the caller gets back.
-template <class F> int guard(CodeHandle *h, hipStream_t s, F &&body) noexcept
+// enqueued on (hipStreamLegacy for the null stream): it is drained before the answer, so that no kernel still runs on what the
+// caller gets back or on a pooled buffer that returns.
+template <class F> int guard(HandleCore *h, hipStream_t s, F &&body) noexcept
 {
     try {
         return body();
     } catch (const HipErr &e) {
         if (s) (void)hipStreamSynchronize(s);
         return hip_fail(h, e);
+    } catch (const CtxErr &c) { // a context polled between launches: what is already on the stream finishes first
+        if (s) (void)hipStreamSynchronize(s);
+        return ctx_fail(h, c.code);
     } catch (const std::bad_alloc &) {
         if (s) (void)hipStreamSynchronize(s);
-        h->set_error("out of host memory");
+        if (h) h->set_error("out of host memory");
         return LB_ERR_OOM;
     } catch (...) {
         if (s) (void)hipStreamSynchronize(s);
-        h->set_error("internal error (exception)");
+        if (h) h->set_error("internal error (exception)");
         return LB_ERR_INTERNAL;
     }
 }
+// the same for a call that has a device and no handle: the status alone
+template <class F> int guard_device(hipStream_t s, F &&body) noexcept { return guard(nullptr, s, std::forward<F>(body)); }
 
 constexpr size_t up16(size_t b) { return (b + 15) & ~(size_t)15; }
+
+// The slab of a host-pointer search of nq queries (row_bytes each) for k results: [queries | dist | labels], the same bytes in
+// pinned host memory and on the device.  Small results (a few queries: the latency path) are written by the last kernel
+// straight into the pinned slab (`direct`): no device-to-host copy and no second wait behind it.  Each handle stages it its
+// own way (the flat index: a pooled HostStage with a stream per caller; PQ: leases on the handle's stream).
+struct HostSlab {
+    size_t row_bytes, qb, db, lb, doff, loff, total;
+    bool direct;
+    HostSlab(int64_t nq, size_t row_bytes_, int k)
+        : row_bytes(row_bytes_), qb((size_t)nq * row_bytes_), db(up16((size_t)nq * k * 4)), lb((size_t)nq * k * 8), doff(up16(qb)),
+          loff(doff + db), total(loff + lb), direct(db + lb <= ((size_t)64 << 10))
+    {
+    }
+    // the requests' queries, one after the other, into the slab at hb
+    void gather(HostReq *const *reqs, int nreq, char *hb) const
+    {
+        for (int i = 0; i < nreq; i++) {
+            const size_t b = (size_t)reqs[i]->nq * row_bytes;
+            std::memcpy(hb, reqs[i]->q, b);
+            hb += b;
+        }
+    }
+    // every request's rows of the result out of the slab at hb
+    void scatter(HostReq *const *reqs, int nreq, const char *hb, int k) const
+    {
+        size_t row = 0;
+        for (int i = 0; i < nreq; i++) {
+            const size_t n = (size_t)reqs[i]->nq * k;
+            std::memcpy(reqs[i]->dist, hb + doff + row * 4, n * 4);
+            std::memcpy(reqs[i]->labels, hb + loff + row * 8, n * 8);
+            row += n;
+        }
+    }
+};
+
+// lb_gpu_*_set_search_combining / _combining_stats of a handle with a `combiner` (lb_combine.h)
+template <class H> int combining_set(H *h, int enable)
+{
+    if (!h) return LB_ERR_INVALID_ARG;
+    h->combiner.on.store(enable ? 1 : 0);
+    return LB_OK;
+}
+template <class H> int combining_stats(const H *h, int64_t out[2])
+{
+    if (!h || !out) return LB_ERR_INVALID_ARG;
+    out[0] = h->combiner.batches.load();
+    out[1] = h->combiner.requests.load();
+    return LB_OK;
+}
 
 // rows per staging piece of the host-pointer codec calls: at most 64 Mi elements, so that the pooled buffers stay small
 inline int64_t piece_rows(int dims) { return std::max<int64_t>(1, ((int64_t)64 << 20) / dims); }
@@ -142,7 +209,7 @@ inline int rows_in_range(CodeHandle *h, int64_t row0, int64_t n)
 // INVALID_ARG, then whatever `ready` refuses (SQ8: an untrained handle), then UNSUPPORTED, then the context: what a k-NN
 // entry point answers before it touches the device
 template <class Ready>
-int knn_args(CodeHandle *h, int64_t nq, const void *queries, int k, const void *dist, const void *labels, const lb_cancel *ctx, Ready &&ready)
+int knn_args(HandleCore *h, int64_t nq, const void *queries, int k, const void *dist, const void *labels, const lb_cancel *ctx, Ready &&ready)
 {
     if (!h || nq < 0 || k <= 0 || (nq > 0 && (!queries || !dist || !labels))) return LB_ERR_INVALID_ARG;
     if (const int st = ready()) return st;
@@ -150,22 +217,26 @@ int knn_args(CodeHandle *h, int64_t nq, const void *queries, int k, const void *
     if (const int st = ctx_state(ctx)) return ctx_fail(h, st);
     return LB_OK;
 }
-inline int knn_args(CodeHandle *h, int64_t nq, const void *queries, int k, const void *dist, const void *labels, const lb_cancel *ctx)
+inline int knn_args(HandleCore *h, int64_t nq, const void *queries, int k, const void *dist, const void *labels, const lb_cancel *ctx)
 {
     return knn_args(h, nq, queries, k, dist, labels, ctx, [] { return (int)LB_OK; });
 }
 
 // ---- construction and the simple entry points -------------------------------------------------------------------------
-template <class T> void handle_free(T *p)
+// The device drained under the writer lock, then own(p), what a handle must give back by hand before its members go (the flat
+// index's pools and corpus buffer), then the handle.
+template <class T, class Own> void handle_free(T *p, Own &&own)
 {
     if (!p) return;
     {
         std::unique_lock<std::shared_mutex> g(p->mu);
         (void)hipSetDevice(p->device);
         (void)hipDeviceSynchronize();
+        own(p);
     }
     delete p;
 }
+template <class T> void handle_free(T *p) { handle_free(p, [](T *) {}); }
 
 // A handle on `device` with its stream; init(p) fills the index's own fields with the device current and may throw.
 // *out_status (nullable) says why nullptr comes back.
@@ -206,7 +277,7 @@ template <class T, class Init> T *handle_new(int device, int dims, int *out_stat
     });
 }
 
-inline const char *handle_last_error(const CodeHandle *h)
+inline const char *handle_last_error(const HandleCore *h)
 {
     if (!h) return "null handle";
     std::lock_guard<std::mutex> g(h->err_mu);
@@ -432,4 +503,5 @@ template <class Run> int host_codec(CodeHandle *h, int64_t n, const void *in, si
     });
 }
 
+#pragma GCC visibility pop
 } // namespace lb

@@ -1,6 +1,7 @@
 // lb_host.h -- host-side helpers shared by the C-ABI translation units (index.hip, index_search.hip, simd_api.hip, pq.hip,
 // pq_train.hip, bq.hip, sq8.hip, comm.hip): HIP error plumbing, a pooled device / pinned-host buffer cache and the owners of a
-// handle's own buffers.  lb_handle.h adds what the code-index handles (pq.hip, bq.hip, sq8.hip) share on top of it.
+// handle's own buffers.  lb_handle.h adds the shell every handle shares on top of it (the core of a handle, the guard an entry
+// point runs in, the slab of a host-pointer search) and what the code-index handles (pq.hip, bq.hip, sq8.hip) share beyond that.
 //
 // Why a pool: hipMalloc costs 0.1-0.3 ms and hipFree synchronises the whole device, so an entry
 // point that allocates per call stalls every concurrent search on the same GPU.  The host-pointer
@@ -44,7 +45,7 @@ struct HipErr {
 // host-side types and functions shared between translation units that are no part of the library's ABI: kept out of its dynamic symbols
 #define LB_INTERNAL __attribute__((visibility("hidden")))
 
-class BufPool {
+class LB_INTERNAL BufPool {
   public:
     // device memory (pinned == false) on `device`, or pinned host memory; at least `bytes` long
     void *get(int device, size_t bytes, bool pinned)
@@ -140,7 +141,7 @@ class BufPool {
 BufPool &buf_pool(); // one per process (simd_api.hip)
 
 // RAII lease from the pool
-struct Lease {
+struct LB_INTERNAL Lease {
     void *p = nullptr;
     Lease() = default;
     Lease(int device, size_t bytes, bool pinned = false) : p(buf_pool().get(device, bytes, pinned)) {}

@@ -1,18 +1,16 @@
 // lb_index.h -- what the translation units behind the index's C ABI share (index.hip: the handle and its storage;
 // index_search.hip: workspaces, routes and the search drivers; simd_api.hip: the re-rank entry points): the handle, the pooled
-// per-search structs, the row view and the few functions that cross files.  Internal: nothing here is part of the ABI.
+// per-search structs, the row view and the few functions that cross files.  The handle's lock, error text and the shell of its
+// entry points (guard) are lb_handle.h's, as for every other handle.  Internal: nothing here is part of the ABI.
 #pragma once
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
+#include "lb_handle.h"
 #include "lb_host.h"
 
 #include <atomic>
-#include <cstdarg>
-#include <cstdio>
 #include <memory>
 #include <mutex>
-#include <shared_mutex>
-#include <string>
 #include <vector>
 
 using namespace lb;
@@ -156,11 +154,9 @@ struct VmmBuf {
     }
 };
 
-struct lb_gpu_index {
-    int device = 0, dim = 0, metric = 0;
+struct lb_gpu_index : HandleCore {
+    int dim = 0, metric = 0;
     std::atomic<int> order{LB_ORDER_SEQ};
-    std::shared_mutex mu;
-    bool closed = false;
 
     // rows, row-major: f32, or IEEE binary16 on an fp16 index (f16_rows; typed float * for the f32 code -- an fp16 index's rows
     // are only ever read through rows_f16())
@@ -236,9 +232,6 @@ struct lb_gpu_index {
 
     SearchCombiner combiner; // concurrent host-pointer searches of a few queries each are combined (lb_host.h)
 
-    mutable std::mutex err_mu;
-    std::string last_error;
-
     std::atomic<int64_t> last_fallbacks{0};
     std::atomic<int> last_route{0}; // RouteKind * 10 + operand form of the most recent batched search (0: exact scan path)
     std::atomic<int64_t> fused_giveups{0}; // fused sample launches whose waits gave up (batch redone on the exact path)
@@ -253,34 +246,16 @@ struct lb_gpu_index {
     const int8_t *rows_i8() const { return reinterpret_cast<const int8_t *>(d_X); }
     // an int8 index keeps its exact int32 row norms (the sum of x_i^2 over i < 16 floor(D / 16)) in d_norm2's words
     int32_t *norm2_i8() const { return reinterpret_cast<int32_t *>(d_norm2.get()); }
-
-    void set_error(const char *fmt, ...)
-    {
-        char buf[512];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        std::lock_guard<std::mutex> g(err_mu);
-        last_error = buf;
-    }
 };
-
-static inline int fail_hip(lb_gpu_index *h, const HipErr &e)
-{
-    (void)hipGetLastError(); // the failure is reported through the return code; leave no sticky error behind
-    h->set_error("HIP error %d (%s) in %s", (int)e.e, hipGetErrorString(e.e), e.what);
-    return (e.e == hipErrorOutOfMemory) ? LB_ERR_OOM : LB_ERR_HIP;
-}
 
 // What a search walks: all corpus rows (optionally testing the mask per row), or the compacted
 // list of visible rows (rebuild_rowmap decides).
-struct RowView {
+struct IndexRowView { // (lb::RowView is the code handles': a list or nothing)
     const uint8_t *mask;
     const uint32_t *rowmap;
     int64_t n;
 };
-static RowView row_view(const lb_gpu_index *h)
+static IndexRowView row_view(const lb_gpu_index *h)
 {
     if (!h->has_mask) return {nullptr, nullptr, h->n};
     if (h->rowmap_on) return {nullptr, h->d_rowmap.get(), h->n_visible};

@@ -649,34 +649,21 @@ static int pq_host_search_multi(lb_gpu_pq *p, HostReq *const *reqs, int nreq, in
 {
     int64_t nq = 0;
     for (int i = 0; i < nreq; i++) nq += reqs[i]->nq;
+    const HostSlab sl(nq, (size_t)p->dims * 4, k);
     Lease hs, dq;
     return guard(p, p->stream, [&]() -> int { // (the device search below runs on p->stream)
         LB_HIP(hipSetDevice(p->device));
-        const size_t qb = (size_t)nq * p->dims * 4, db = up16((size_t)nq * k * 4), lbb = (size_t)nq * k * 8;
-        const size_t doff = up16(qb), loff = doff + db, total = loff + lbb;
-        const bool direct = db + lbb <= ((size_t)64 << 10);
-        hs.reset(p->device, total, /*pinned=*/true);
-        dq.reset(p->device, direct ? qb : total);
+        hs.reset(p->device, sl.total, /*pinned=*/true);
+        dq.reset(p->device, sl.direct ? sl.qb : sl.total);
         char *hb = hs.as<char>(), *dbuf = dq.as<char>();
-        size_t off = 0;
-        for (int i = 0; i < nreq; i++) {
-            const size_t b = (size_t)reqs[i]->nq * p->dims * 4;
-            std::memcpy(hb + off, reqs[i]->q, b);
-            off += b;
-        }
-        LB_HIP(hipMemcpy(dbuf, hb, qb, hipMemcpyHostToDevice));
-        char *obuf = direct ? hb : dbuf;
-        const int rc = lb_gpu_pq_search_device_ctx(p, nq, reinterpret_cast<const float *>(dbuf), k, reinterpret_cast<float *>(obuf + doff),
-                                                   reinterpret_cast<int64_t *>(obuf + loff), nullptr, ctx);
+        sl.gather(reqs, nreq, hb);
+        LB_HIP(hipMemcpy(dbuf, hb, sl.qb, hipMemcpyHostToDevice));
+        char *obuf = sl.direct ? hb : dbuf;
+        const int rc = lb_gpu_pq_search_device_ctx(p, nq, reinterpret_cast<const float *>(dbuf), k, reinterpret_cast<float *>(obuf + sl.doff),
+                                                   reinterpret_cast<int64_t *>(obuf + sl.loff), nullptr, ctx);
         if (rc != LB_OK) return rc;
-        if (!direct) LB_HIP(hipMemcpy(hb + doff, dbuf + doff, db + lbb, hipMemcpyDeviceToHost));
-        size_t row = 0;
-        for (int i = 0; i < nreq; i++) {
-            const size_t n = (size_t)reqs[i]->nq * k;
-            std::memcpy(reqs[i]->dist, hb + doff + row * 4, n * 4);
-            std::memcpy(reqs[i]->labels, hb + loff + row * 8, n * 8);
-            row += n;
-        }
+        if (!sl.direct) LB_HIP(hipMemcpy(hb + sl.doff, dbuf + sl.doff, sl.db + sl.lb, hipMemcpyDeviceToHost));
+        sl.scatter(reqs, nreq, hb, k);
         return LB_OK;
     });
 }
@@ -696,19 +683,7 @@ int lb_gpu_pq_search_ctx(lb_gpu_pq *p, int64_t nq, const float *queries, int k, 
     return pq_host_search_multi(p, &one, 1, k, ctx);
 }
 
-int lb_gpu_pq_set_search_combining(lb_gpu_pq *p, int enable)
-{
-    if (!p) return LB_ERR_INVALID_ARG;
-    p->combiner.on.store(enable ? 1 : 0);
-    return LB_OK;
-}
-
-int lb_gpu_pq_combining_stats(const lb_gpu_pq *p, int64_t out[2])
-{
-    if (!p || !out) return LB_ERR_INVALID_ARG;
-    out[0] = p->combiner.batches.load();
-    out[1] = p->combiner.requests.load();
-    return LB_OK;
-}
+int lb_gpu_pq_set_search_combining(lb_gpu_pq *p, int enable) { return combining_set(p, enable); }
+int lb_gpu_pq_combining_stats(const lb_gpu_pq *p, int64_t out[2]) { return combining_stats(p, out); }
 
 } // extern "C"

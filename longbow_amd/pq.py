@@ -86,29 +86,29 @@ class PQEncoder(RowFilterMixin):
         self.SubDim = self.Dims // self.M
 
     def _check(self, rc):
-        _lib.check(rc, self._h, pq=True, lib=self._lib)
+        _lib.check(rc, self._h, lib=self._lib, prefix=self._prefix)
 
     def add_codes(self, codes):
         codes = np.ascontiguousarray(codes, np.uint8).reshape(-1)
         if codes.size % self.M:
             raise ValueError("code length mismatch")
-        _lib.check(self._lib.lb_gpu_pq_add_codes(self._h, codes.size // self.M, codes.ctypes.data), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_add_codes(self._h, codes.size // self.M, codes.ctypes.data))
 
     def add_codes_device(self, n, d_codes):
-        _lib.check(self._lib.lb_gpu_pq_add_codes_device(self._h, n, d_codes), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_add_codes_device(self._h, n, d_codes))
 
     @property
     def ntotal(self):
         return int(self._lib.lb_gpu_pq_ntotal(self._h))
 
     def reserve(self, n_total):
-        _lib.check(self._lib.lb_gpu_pq_reserve(self._h, n_total), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_reserve(self._h, n_total))
 
     def get_codes(self, row0=0, n=None):
         """stored codes rows [row0, row0+n) -> uint8 [n, M]"""
         n = self.ntotal - row0 if n is None else n
         out = np.empty((n, self.M), np.uint8)
-        _lib.check(self._lib.lb_gpu_pq_get_codes(self._h, row0, n, out.ctypes.data), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_get_codes(self._h, row0, n, out.ctypes.data))
         return out
 
     def Encode(self, vector):
@@ -119,7 +119,7 @@ class PQEncoder(RowFilterMixin):
         if v.shape[1] != self.Dims:
             raise ValueError("vector dimension mismatch")  # encoder.go:77-79
         codes = np.empty((v.shape[0], self.M), np.uint8)
-        _lib.check(self._lib.lb_gpu_pq_encode(self._h, v.shape[0], v.ctypes.data, codes.ctypes.data), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_encode(self._h, v.shape[0], v.ctypes.data, codes.ctypes.data))
         return codes[0] if single else codes
 
     def Decode(self, codes):
@@ -130,15 +130,15 @@ class PQEncoder(RowFilterMixin):
         if c.shape[1] != self.M:
             raise ValueError("code length mismatch")  # encoder.go:140-142
         out = np.empty((c.shape[0], self.Dims), np.float32)
-        _lib.check(self._lib.lb_gpu_pq_decode(self._h, c.shape[0], c.ctypes.data, out.ctypes.data), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_decode(self._h, c.shape[0], c.ctypes.data, out.ctypes.data))
         return out[0] if single else out
 
     def encode_device(self, n, d_vectors, d_codes, stream=None):
-        _lib.check(self._lib.lb_gpu_pq_encode_device(self._h, n, d_vectors, d_codes, stream), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_encode_device(self._h, n, d_vectors, d_codes, stream))
 
     def add_vectors_device(self, n, d_vectors):
         """encode n device-resident vectors and append their codes"""
-        _lib.check(self._lib.lb_gpu_pq_add_vectors_device(self._h, n, d_vectors), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_add_vectors_device(self._h, n, d_vectors))
 
     def Rerank(self, query, rows):
         """processChunkInternal's PQ branch (parallel_search.go:292-345): ADC distance of the stored code rows
@@ -149,8 +149,8 @@ class PQEncoder(RowFilterMixin):
         rows = np.ascontiguousarray(rows, np.int64).reshape(-1)
         dist = np.empty(rows.size, np.float32)
         score = np.empty(rows.size, np.float32)
-        _lib.check(self._lib.lb_gpu_pq_rerank(self._h, query.ctypes.data, rows.ctypes.data, rows.size, dist.ctypes.data,
-                                              score.ctypes.data), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_rerank(self._h, query.ctypes.data, rows.ctypes.data, rows.size, dist.ctypes.data,
+                                               score.ctypes.data))
         return dist, score
 
     def BuildADCTable(self, query):
@@ -158,7 +158,7 @@ class PQEncoder(RowFilterMixin):
         if query.size != self.Dims:
             raise ValueError("query dimension mismatch")  # adc_table.go:16-18
         table = np.empty(self.M * self.K, np.float32)
-        _lib.check(self._lib.lb_gpu_pq_build_adc_table(self._h, query.ctypes.data, table.ctypes.data), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_build_adc_table(self._h, query.ctypes.data, table.ctypes.data))
         return table
 
     def ADCDistanceBatch(self, table, results, row0=0):
@@ -170,12 +170,12 @@ class PQEncoder(RowFilterMixin):
             raise ValueError("invalid table size")  # adc_table.go:64-66
         if row0 + results.size > self.ntotal:
             raise ValueError("flatCodes buffer too small")  # adc_table.go:61-63
-        _lib.check(self._lib.lb_gpu_pq_adc_distance_batch(self._h, table.ctypes.data, row0, results.size,
-                                                           results.ctypes.data), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_adc_distance_batch(self._h, table.ctypes.data, row0, results.size,
+                                                            results.ctypes.data))
 
     def set_prefilter(self, on):
         """True (default): byte-table prefilter + exact survivors; False: exact f32-table pass only.  Same results."""
-        _lib.check(self._lib.lb_gpu_pq_set_prefilter(self._h, 1 if on else 0), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_set_prefilter(self._h, 1 if on else 0))
 
     @property
     def last_search_stats(self):
@@ -183,20 +183,20 @@ class PQEncoder(RowFilterMixin):
         (planned with a sampled threshold, four-query passes, two-query passes, single prefilter passes,
         redone on the bootstrap schedule, redone on the schedule that cannot overflow)"""
         out = (C.c_int64 * 6)()
-        _lib.check(self._lib.lb_gpu_pq_last_search_stats(self._h, out), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_last_search_stats(self._h, out))
         return tuple(int(v) for v in out)
 
     def set_search_combining(self, enable):
         """1 (default): concurrent Search calls of a few queries each are answered by one batch (pairs of queries share a pass
         over the codes); 0: every call on its own.  Same results."""
-        _lib.check(self._lib.lb_gpu_pq_set_search_combining(self._h, 1 if enable else 0), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_set_search_combining(self._h, 1 if enable else 0))
 
     @property
     def combining_stats(self):
         """(combined batches run, requests they answered)"""
         import ctypes as C
         out = (C.c_int64 * 2)()
-        _lib.check(self._lib.lb_gpu_pq_combining_stats(self._h, out), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_combining_stats(self._h, out))
         return int(out[0]), int(out[1])
 
     def Search(self, queries, k, ctx=None):
@@ -208,23 +208,21 @@ class PQEncoder(RowFilterMixin):
         nq = queries.shape[0]
         dist = np.empty((nq, k), np.float32)
         labels = np.empty((nq, k), np.int64)
-        _lib.check(self._lib.lb_gpu_pq_search_ctx(self._h, nq, queries.ctypes.data, k, dist.ctypes.data,
-                                                  labels.ctypes.data, ctx._h if ctx is not None else None),
-                   self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_search_ctx(self._h, nq, queries.ctypes.data, k, dist.ctypes.data,
+                                                   labels.ctypes.data, ctx._h if ctx is not None else None))
         return labels, dist
 
     def search_device(self, nq, d_queries, k, d_dist, d_labels, stream=None, ctx=None):
-        _lib.check(self._lib.lb_gpu_pq_search_device_ctx(self._h, nq, d_queries, k, d_dist, d_labels, stream,
-                                                         ctx._h if ctx is not None else None),
-                   self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_search_device_ctx(self._h, nq, d_queries, k, d_dist, d_labels, stream,
+                                                          ctx._h if ctx is not None else None))
 
     def set_profiling(self, on):
-        _lib.check(self._lib.lb_gpu_pq_set_profiling(self._h, 1 if on else 0), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_set_profiling(self._h, 1 if on else 0))
 
     def last_timing(self):
         """(ms of the last query's pass over the codes, ms of the whole search on the device)"""
         ms = (C.c_float * 2)()
-        _lib.check(self._lib.lb_gpu_pq_last_timing(self._h, ms), self._h, pq=True, lib=self._lib)
+        self._check(self._lib.lb_gpu_pq_last_timing(self._h, ms))
         return float(ms[0]), float(ms[1])
 
     def Close(self):

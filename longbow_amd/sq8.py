@@ -35,7 +35,7 @@ class SQ8Encoder(RowFilterMixin):
         self.Dimensions = dims
 
     def _check(self, rc):
-        _lib.check(rc, self._h, lib=self._lib, sq8=True)
+        _lib.check(rc, self._h, lib=self._lib, prefix=self._prefix)
 
     def _codes(self, codes):
         c = np.ascontiguousarray(codes, np.uint8)
