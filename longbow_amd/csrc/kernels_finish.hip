@@ -80,78 +80,15 @@ struct FinishArgsT {
 };
 using FinishArgs = FinishArgsT<float>;
 
-// exactly `need` (>= 1) of the real entries held in registers are <= the returned pivot (entries are unique).
-// hist[256], wsum[4], scal[8], red[2]: LDS scratch.  All threads of the workgroup call it.
+// radix_kth (lb_select.h) over the entries a thread holds in registers; kEntryMax fills the slots beyond the list.
 template <int PER>
-__device__ __forceinline__ uint64_t radix_kth_regs(const uint64_t (&e)[PER], uint32_t need, uint32_t *hist, uint32_t *wsum,
-                                                   uint32_t *scal, unsigned long long *red, int tid)
+__device__ __forceinline__ uint64_t radix_kth_regs(const uint64_t (&e)[PER], uint32_t need, RadixScratch &s, int tid)
 {
-    const int lane = tid & 63, wave = tid >> 6;
-    if (tid == 0) { red[0] = 0ull; red[1] = ~0ull; }
-    __syncthreads();
-    {
-        uint64_t o = 0, an = ~0ull;
+    return radix_kth<FN_THREADS>([&](auto f) {
 #pragma unroll
         for (int j = 0; j < PER; j++)
-            if (e[j] != kEntryMax) { o |= e[j]; an &= e[j]; }
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            o |= __shfl_xor(o, off);
-            an &= __shfl_xor(an, off);
-        }
-        if (lane == 0) {
-            atomicOr(&red[0], (unsigned long long)o);
-            atomicAnd(&red[1], (unsigned long long)an);
-        }
-    }
-    __syncthreads();
-    const uint64_t diff = red[0] ^ red[1];
-    const uint64_t common = red[1];
-    __syncthreads();
-    if (diff == 0ull) return common | 0xffffffffull; // one real entry (or none): it is the pivot
-    int first_shift = 56;
-    uint64_t prefix = 0, mask = 0;
-    {
-        const int same_bytes = __builtin_clzll(diff) >> 3;
-        first_shift = 56 - 8 * same_bytes;
-        if (same_bytes > 0) {
-            mask = ~0ull << (64 - 8 * same_bytes);
-            prefix = common & mask;
-        }
-    }
-    for (int shift = first_shift; shift >= 0; shift -= 8) {
-        hist[tid] = 0; // (FN_THREADS == 256 bins)
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < PER; j++)
-            if (e[j] != kEntryMax && (e[j] & mask) == prefix) atomicAdd(&hist[(uint32_t)(e[j] >> shift) & 0xffu], 1u);
-        __syncthreads();
-        const uint32_t h = hist[tid];
-        uint32_t incl = wave_incl_scan(h, lane);
-        if (lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        uint32_t base = 0;
-#pragma unroll
-        for (int w = 0; w < 4; w++) base += (w < wave) ? wsum[w] : 0u;
-        incl += base;
-        const uint32_t excl = incl - h;
-        if (excl < need && need <= incl) {
-            scal[0] = (uint32_t)tid;
-            scal[1] = need - excl;
-            scal[4] = (need == incl) ? 1u : 0u;
-        }
-        __syncthreads();
-        prefix |= (uint64_t)scal[0] << shift;
-        mask |= 0xffull << shift;
-        need = scal[1];
-        const bool whole_bucket = scal[4] != 0u;
-        __syncthreads();
-        if (whole_bucket) {
-            prefix |= ~mask;
-            break;
-        }
-    }
-    return prefix;
+            if (e[j] != kEntryMax) f(e[j]);
+    }, need, s, tid);
 }
 
 // the exact result of a member: its distance and the value the proof compares (L2: the squared distance)
@@ -187,10 +124,8 @@ template <typename RowT, int METRIC, int ORDER, bool SPLIT, int PER>
 __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    __shared__ uint32_t hist[256];
-    __shared__ uint32_t wsum[4];
-    __shared__ uint32_t scal[8];
-    __shared__ unsigned long long red[2];
+    __shared__ SelectScratch ss; // out_count: members handed a slot; valid_count: members of the whole list, later the proof's count
+    __shared__ uint32_t s_xbase, s_xtotal; // SPLIT: this workgroup's offset into the query's scratch block; the block's fill
     __shared__ float fred[4];
     __shared__ int s_last;
 
@@ -212,18 +147,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
     uint32_t flags = raw > a.cs.cap ? 1u : 0u;
 
     auto emit = [&](const uint64_t *sorted, uint32_t nsorted, uint32_t fl) { // the sorted prefix -> the query's k results
-        for (int r = tid; r < k; r += FN_THREADS) {
-            float d = FLT_MAX;
-            int64_t lab = -1;
-            if ((uint32_t)r < nsorted) {
-                const uint64_t en = sorted[r];
-                d = entry_key(en);
-                const uint32_t row = entry_row(en);
-                lab = a.ids ? a.ids[row] : (int64_t)row;
-            }
-            a.out_dist[(int64_t)qi * k + r] = d;
-            a.out_labels[(int64_t)qi * k + r] = lab;
-        }
+        emit_sorted(sorted, nsorted, k, qi, a.ids, a.out_dist, a.out_labels, tid, FN_THREADS);
         if (tid == 0) {
             const uint32_t all = fl ? (atomicOr(&a.cs.flags[qi], fl) | fl) : atomicOr(&a.cs.flags[qi], 0u);
             if (a.flags_host) a.flags_host[qi] = all;
@@ -252,7 +176,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
         for (int off = 32; off > 0; off >>= 1) nq2 += __shfl_xor(nq2, off);
         if (lane == 0) fred[wave] = nq2;
     }
-    if (tid == 0) { scal[2] = 0; scal[3] = 0; }
+    if (tid == 0) { ss.out_count = 0; ss.valid_count = 0; }
     __syncthreads();
     const float na = METRIC == METRIC_COS ? a.qna[qi] : 0.f;
     if (METRIC != METRIC_COS) nq2 = (fred[0] + fred[1]) + (fred[2] + fred[3]);
@@ -263,7 +187,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
     const uint32_t kk = n < (uint32_t)k ? n : (uint32_t)k;
     const bool dot_lb = METRIC == METRIC_DOT && a.lb_norm2 != nullptr;
     // (lower-bound dot keys: the cut comes from the k-th smallest UPPER bound below, a_k is not used -- one selection less)
-    const uint64_t pivot = dot_lb ? (e[0] | 0xffffffffull) : radix_kth_regs<PER>(e, kk, hist, wsum, scal, red, tid);
+    const uint64_t pivot = dot_lb ? (e[0] | 0xffffffffull) : radix_kth_regs<PER>(e, kk, ss.radix, tid);
 
     // ---- the cut ------------------------------------------------------------------------------------------------------
     const float ga = a.gamma + (a.qrho ? a.qrho_k * a.qrho[qi] : 0.f);
@@ -294,10 +218,10 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
                 u[j] = pack_entry(up, (uint32_t)tid + (uint32_t)FN_THREADS * j);
             }
         }
-        const float uk = entry_key(radix_kth_regs<PER>(u, kk, hist, wsum, scal, red, tid));
+        const float uk = entry_key(radix_kth_regs<PER>(u, kk, ss.radix, tid));
         cutk = uk + fabsf(uk) * 1.0e-5f + 1.0e-30f;
         if (!(cutk >= uk)) cutk = FLT_MAX;
-        if (tid == 0) { scal[2] = 0; scal[3] = 0; }
+        if (tid == 0) { ss.out_count = 0; ss.valid_count = 0; }
         __syncthreads();
     }
     if (kk < (uint32_t)k) cutk = FLT_MAX; // fewer entries than results wanted: all of them
@@ -316,17 +240,17 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
         const bool mem = e[j] != kEntryMax && (uint32_t)(e[j] >> 32) <= cut_s;
         all_members += mem ? 1u : 0u;
         if (mem && mine) {
-            const uint32_t slot = atomicAdd(&scal[2], 1u);
+            const uint32_t slot = atomicAdd(&ss.out_count, 1u);
             if (slot < smax) s_rows[slot] = entry_row(e[j]);
         }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) all_members += __shfl_xor(all_members, off);
-    if (lane == 0 && all_members) atomicAdd(&scal[3], all_members);
+    if (lane == 0 && all_members) atomicAdd(&ss.valid_count, all_members);
     __syncthreads();
-    const uint32_t nm_raw = scal[2];
+    const uint32_t nm_raw = ss.out_count;
     const uint32_t nm = nm_raw < smax ? nm_raw : smax;
-    const uint32_t ns_all = scal[3];
+    const uint32_t ns_all = ss.valid_count;
     // every row there is was admitted and is a member: nothing lies outside S
     const bool complete = tau == kEntryMax && ns_all == n && raw <= a.cs.cap && ns_all <= smax;
 #ifdef LB_DIAG
@@ -627,9 +551,9 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
     // ---- SPLIT: hand the block in; the last workgroup of the query to arrive goes on ------------------------------------
     uint32_t ns = nm;
     if (SPLIT) {
-        if (tid == 0) scal[5] = nm ? atomicAdd(&a.xcnt[qi], nm) : 0u;
+        if (tid == 0) s_xbase = nm ? atomicAdd(&a.xcnt[qi], nm) : 0u;
         __syncthreads();
-        const uint32_t base = scal[5];
+        const uint32_t base = s_xbase;
         uint64_t *xe = a.xent + (size_t)qi * smax;
         float *xc = a.xcmp + (size_t)qi * smax;
         for (uint32_t c = tid; c < nm; c += FN_THREADS)
@@ -649,12 +573,12 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
         uint32_t total = 0;
         if (tid == 0) {
             total = __hip_atomic_load(&a.xcnt[qi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            scal[6] = total;
+            s_xtotal = total;
             a.done[qi] = 0; // ready for the next launch on this workspace
             a.xcnt[qi] = 0;
         }
         __syncthreads();
-        total = scal[6];
+        total = s_xtotal;
         // (each workgroup clips its own members to smax before the hand-in: one workgroup beyond smax while the others hold
         // none sums to exactly smax.  ns_all counts every member of the query's list, whichever workgroup holds it.)
         if (total > smax || ns_all > smax) {
@@ -672,7 +596,7 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
     // order the members by (distance, row).  Up to 512: every thread ranks two entries against all (broadcast LDS reads, no
     // barrier per stage: 2 us where the 45 stages of a bitonic sort take 4.5) and scatters them; beyond: bitonic sort.
     const uint64_t *sorted = skey;
-    if (tid == 0) scal[3] = 0;
+    if (tid == 0) ss.valid_count = 0;
     if (ns <= 512u) {
         uint64_t *srt = reinterpret_cast<uint64_t *>(s_rows); // (the row list is not needed any more; smax >= 1024: 4 KB)
         __syncthreads();
@@ -718,9 +642,9 @@ __global__ __launch_bounds__(FN_THREADS) void finish_kernel(FinishArgsT<RowT> a)
         for (uint32_t c = tid; c < ns; c += FN_THREADS) local += (scmp[c] < T) ? 1u : 0u;
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) local += __shfl_xor(local, off);
-        if (lane == 0 && local) atomicAdd(&scal[3], local);
+        if (lane == 0 && local) atomicAdd(&ss.valid_count, local);
         __syncthreads();
-        if (!skip && scal[3] < (unsigned int)k) flags |= 2u;
+        if (!skip && ss.valid_count < (unsigned int)k) flags |= 2u;
     }
     emit(sorted, ns, flags);
 }
@@ -802,9 +726,7 @@ static void launch_finish_rows(int metric, int order, const T *X, int D, const f
     dim3 grid = split ? dim3((unsigned)G, (unsigned)nq) : dim3((unsigned)nq);
 #define LB_FN(M, O, S, P)                                                                                  \
     do {                                                                                                   \
-        if (shmem > 64 * 1024)                                                                             \
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(finish_kernel<T, M, O, S, P>),          \
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);             \
+        allow_big_lds(finish_kernel<T, M, O, S, P>, shmem);                                                \
         hipLaunchKernelGGL((finish_kernel<T, M, O, S, P>), grid, dim3(FN_THREADS), shmem, s, a);              \
     } while (0)
 #define LB_FN_O(M, O)                              \

@@ -264,21 +264,12 @@ void launch_ivf_plan(const IvfBatch &a, unsigned long long *stats, hipStream_t s
 //   copy, or the keys in global memory when they do not fit), compaction of the k keys at or below it into LDS, a sort of those.
 // Keys are unique (the row is part of the key), so exactly k keys are at or below the pivot.
 // LDS: keys u64[cap] | stage u64[Pk] | hist u32[256] | wave sums u32[4] | scalars u32[8]
+// (the tail has SelectScratch's size.)  This kernel keeps its own text of the radix walk, the compaction and the emit, in step
+// with lb_select.h's radix_kth / compact_le / emit_sorted by hand.  Its time depends on where its three loops over the keys fall
+// in the code: this very text with the loops moved by 12, 40 or 52 bytes is 1 - 3 % slower, by 24 bytes it is level.  Built over
+// the shared pieces the loops came out instruction for instruction the same but elsewhere, in every arrangement tried on a slow
+// spot (0.7 - 2 % on the select slot).  Until the loops are made indifferent to their placement, the text stays (LABNOTES R23.1).
 constexpr int IVS_THREADS = 1024;
-
-__device__ __forceinline__ void ivs_or_and_u64(uint64_t &o, uint64_t &a)
-{
-#define LB_STEP(CTRL, RM)      \
-    o |= dpp_u64<CTRL, RM>(o); \
-    a &= dpp_u64<CTRL, RM>(a);
-    LB_STEP(0xB1, 0xf)  // quad_perm [1,0,3,2]
-    LB_STEP(0x4E, 0xf)  // quad_perm [2,3,0,1]
-    LB_STEP(0x141, 0xf) // row_half_mirror
-    LB_STEP(0x140, 0xf) // row_mirror
-    LB_STEP(0x142, 0xa) // row_bcast15 -> rows 1,3
-    LB_STEP(0x143, 0xc) // row_bcast31 -> rows 2,3: lane 63 holds the result
-#undef LB_STEP
-}
 
 __global__ __launch_bounds__(IVS_THREADS) void ivf_select_kernel(IvfBatch a, int k, uint32_t cap, uint32_t Pk, const int64_t *ids,
                                                                  float *out_dist, int64_t *out_labels)
@@ -340,7 +331,7 @@ __global__ __launch_bounds__(IVS_THREADS) void ivf_select_kernel(IvfBatch a, int
             o |= e;
             an &= e;
         }
-        ivs_or_and_u64(o, an); // one pair of LDS atomics per wave
+        wave_or_and_u64(o, an); // one pair of LDS atomics per wave
         if (lane == 63) {
             atomicOr(&red[0], (unsigned long long)o);
             atomicAnd(&red[1], (unsigned long long)an);
@@ -416,9 +407,8 @@ void launch_ivf_select(const IvfBatch &a, int k, const int64_t *ids, float *dist
     const uint32_t Pk = next_pow2_host((uint32_t)k);
     // room for the LDS copy: what the largest query of the handle needs, up to IVF_SELECT_LDS_KEYS
     const uint32_t cap = a.pmax >= (int64_t)IVF_SELECT_LDS_KEYS ? IVF_SELECT_LDS_KEYS : next_pow2_host((uint32_t)std::max<int64_t>(a.pmax, 2));
-    const size_t shmem = ((size_t)cap + Pk) * sizeof(uint64_t) + (256 + 4 + 8) * sizeof(uint32_t);
-    if (shmem > 64 * 1024) // (at most 148.5 KB of the 160 KB a workgroup may hold)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ivf_select_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
+    const size_t shmem = ((size_t)cap + Pk) * sizeof(uint64_t) + sizeof(SelectScratch);
+    allow_big_lds(ivf_select_kernel, shmem); // (at most 148.5 KB of the 160 KB a workgroup may hold)
     hipLaunchKernelGGL(ivf_select_kernel, dim3((unsigned)a.nq), dim3(IVS_THREADS), shmem, s, a, k, cap, Pk, ids, dist, labels);
 }
 

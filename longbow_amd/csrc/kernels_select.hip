@@ -32,37 +32,13 @@ void launch_init_cand(CandState cs, const int *qsel, int nsel, hipStream_t s)
     hipLaunchKernelGGL(init_cand_kernel, dim3((nsel + 255) / 256), dim3(256), 0, s, cs, qsel, nsel);
 }
 
-// Kernels that carve more than 64 KB of dynamic LDS must opt in once.
-template <typename K>
-static void allow_big_lds(K kernel, size_t bytes)
-{
-    if (bytes > 64 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 // ---------------------------------------------------------------------------
 // select: keep the kc smallest of n unique u64 entries, sorted.
 //   n <= 2*kc : bitonic sort of everything.
 //   otherwise : MSB radix select (8 passes of 8 bits over the LDS copy) finds the kc-th smallest
 //               entry exactly (entries are unique: the row is part of the key), the <= pivot
-//               entries are compacted and only those kc are sorted.
-// LDS: entries u64[P] | hist u32[256] | wave sums u32[4] | scalars
-// lane permutes on the DPP path (no LDS round trip): OR / AND of a u64 over the 64 lanes, result in lane 63
-__device__ __forceinline__ void wave_or_and_u64(uint64_t &o, uint64_t &a)
-{
-#define LB_STEP(CTRL, RM)                 \
-    o |= dpp_u64<CTRL, RM>(o);            \
-    a &= dpp_u64<CTRL, RM>(a);
-    LB_STEP(0xB1, 0xf)  // quad_perm [1,0,3,2]
-    LB_STEP(0x4E, 0xf)  // quad_perm [2,3,0,1]
-    LB_STEP(0x141, 0xf) // row_half_mirror
-    LB_STEP(0x140, 0xf) // row_mirror
-    LB_STEP(0x142, 0xa) // row_bcast15 -> rows 1,3 (disabled rows keep their own value: x|x, x&x)
-    LB_STEP(0x143, 0xc) // row_bcast31 -> rows 2,3
-#undef LB_STEP
-}
-
+//               entries are compacted and only those kc are sorted (lb_select.h: radix_kth, compact_le).
+// LDS: entries u64[next_pow2(cap)] | SelectScratch
 template <int NT> // threads per workgroup: 256 (throughput, many queries) or 1024 (latency, few queries)
 __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qsel, int kc,
                                                              uint32_t boot_rows, uint32_t need_at_least,
@@ -73,7 +49,7 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
     extern __shared__ __attribute__((aligned(16))) uint64_t sh[];
     const int q = qsel ? qsel[blockIdx.x] : blockIdx.x;
     const int tid = threadIdx.x;
-    const int lane = tid & 63, wave = tid >> 6;
+    const int lane = tid & 63;
     // boot_rows > 0: the bootstrap chunk stored one entry per row without atomics
     // striped: positions s, s+16, ... of the list were handed out by 16 counters (slot = blockIdx.x);
     // the list then has holes, which are read as kEntryMax exactly like masked rows of a bootstrap chunk
@@ -96,18 +72,7 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
     // memory) from the sorted prefix sorted[0..nsorted) instead of launching emit_lists_kernel
     auto emit = [&](const uint64_t *sorted, uint32_t nsorted) {
         if (em.out_dist == nullptr) return;
-        for (int r = tid; r < em.k; r += NT) {
-            float d = FLT_MAX;
-            int64_t lab = -1;
-            if ((uint32_t)r < nsorted) {
-                const uint64_t e = sorted[r];
-                d = entry_key(e);
-                const uint32_t row = entry_row(e);
-                lab = em.ids ? em.ids[row] : (int64_t)row;
-            }
-            em.out_dist[(int64_t)q * em.k + r] = d;
-            em.out_labels[(int64_t)q * em.k + r] = lab;
-        }
+        emit_sorted(sorted, nsorted, em.k, q, em.ids, em.out_dist, em.out_labels, tid, NT);
         if (em.flags_host && tid == 0) em.flags_host[q] = atomicOr(&cs.flags[q], 0u);
     };
     if (n == 0) {
@@ -120,11 +85,9 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
         return;
     }
     const uint32_t P = next_pow2(n);
-    uint32_t *hist = reinterpret_cast<uint32_t *>(sh + next_pow2(cs.cap));
-    uint32_t *wsum = hist + 256;
-    uint32_t *scal = wsum + 4; // [0]=bucket [1]=need [2]=out counter [3]=valid count [4]=take the whole bucket
+    SelectScratch &ss = *reinterpret_cast<SelectScratch *>(sh + next_pow2(cs.cap));
 
-    if (tid == 0) { scal[2] = 0; scal[3] = 0; }
+    if (tid == 0) { ss.out_count = 0; ss.valid_count = 0; }
     uint32_t myvalid = 0;
     for (uint32_t i = tid; i < P; i += NT) { // (NT is a multiple of 16: a thread stays in one stripe)
         const bool there = i < n && (!striped || (i / LB_STRIPES) < my_stripe_cnt);
@@ -136,9 +99,9 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
     if (boot_rows) { // masked-out rows of the bootstrap chunk hold kEntryMax: count the real ones
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) myvalid += __shfl_xor(myvalid, off); // one LDS atomic per wave
-        if (lane == 0 && myvalid) atomicAdd(&scal[3], myvalid);
+        if (lane == 0 && myvalid) atomicAdd(&ss.valid_count, myvalid);
         __syncthreads();
-        n = scal[3];
+        n = ss.valid_count;
         __syncthreads();
         if (n == 0) {
             if (tid == 0) {
@@ -164,91 +127,24 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
         return;
     }
 
-    // ---- radix select of the kc-th smallest (1-based rank `need`) ----
-    // Leading bytes shared by every real entry (distances live in a narrow range) need no pass.
-    unsigned long long *red = reinterpret_cast<unsigned long long *>(hist); // [0] = OR, [1] = AND of real entries
-    if (tid == 0) { red[0] = 0ull; red[1] = ~0ull; }
-    __syncthreads();
-    {
-        uint64_t o = 0, an = ~0ull;
+    // ---- radix select of the kc-th smallest, over the LDS copy (its padding and holes are not entries) ----
+    auto each = [&](auto f) {
         for (uint32_t i = tid; i < P; i += NT) {
             const uint64_t e = sh[i];
-            if (e != kEntryMax) { o |= e; an &= e; }
+            if (e != kEntryMax) f(e);
         }
-        wave_or_and_u64(o, an); // one pair of LDS atomics per wave, not per thread
-        if (lane == 63) {
-            atomicOr(&red[0], (unsigned long long)o);
-            atomicAnd(&red[1], (unsigned long long)an);
-        }
-    }
-    __syncthreads();
-    const uint64_t diff = red[0] ^ red[1]; // bit positions that differ among real entries
-    const uint64_t common = red[1];
-    __syncthreads();
-    int first_shift = 56;
-    uint64_t prefix = 0, mask = 0;
-    if (diff != 0ull) {
-        const int same_bytes = __builtin_clzll(diff) >> 3; // whole leading bytes identical
-        first_shift = 56 - 8 * same_bytes;
-        if (same_bytes > 0) {
-            mask = ~0ull << (64 - 8 * same_bytes);
-            prefix = common & mask;
-        }
-    }
-    uint32_t need = (uint32_t)kc;
-    for (int shift = first_shift; shift >= 0; shift -= 8) {
-        if (tid < 256) hist[tid] = 0; // 256 bins
-        __syncthreads();
-        for (uint32_t i = tid; i < P; i += NT) {
-            const uint64_t e = sh[i];
-            if ((e & mask) == prefix) atomicAdd(&hist[(uint32_t)(e >> shift) & 0xffu], 1u);
-        }
-        __syncthreads();
-        const uint32_t h = tid < 256 ? hist[tid] : 0u;
-        uint32_t incl = wave_incl_scan(h, lane);
-        if (tid < 256 && lane == 63) wsum[wave] = incl;
-        __syncthreads();
-        if (tid < 256) {
-            uint32_t base = 0;
-#pragma unroll
-            for (int w = 0; w < 4; w++) base += (w < wave) ? wsum[w] : 0u;
-            incl += base;
-            const uint32_t excl = incl - h;
-            if (excl < need && need <= incl) {
-                scal[0] = (uint32_t)tid;
-                scal[1] = need - excl;
-                scal[4] = (need == incl) ? 1u : 0u; // the whole bucket is wanted: no need to split it further
-            }
-        }
-        __syncthreads();
-        prefix |= (uint64_t)scal[0] << shift;
-        mask |= 0xffull << shift;
-        need = scal[1];
-        const bool whole_bucket = scal[4] != 0u;
-        __syncthreads();
-        if (whole_bucket) { // (entries are unique, so the row bytes are rarely ever walked)
-            prefix |= ~mask; // every entry sharing the resolved bytes is kept; this bound is >= the kc-th entry
-            break;
-        }
-    }
-    const uint64_t pivot = prefix; // >= the kc-th smallest entry and < the (kc+1)-th: exactly kc entries are <= pivot
+    };
+    const uint64_t pivot = radix_kth<NT>(each, (uint32_t)kc, ss.radix, tid); // exactly kc entries are <= pivot
     // compact the kc entries <= pivot (unordered), then sort them.  The staging area is the unused tail of
     // the LDS entry array when there is room, else the front of the global list.
     const uint32_t Pk = next_pow2((uint32_t)kc);
     uint64_t *stage = (P + Pk <= next_pow2(cs.cap)) ? sh + P : list;
-    __syncthreads();
-    for (uint32_t i = tid; i < P; i += NT) {
-        const uint64_t e = sh[i];
-        if (e <= pivot) {
-            const uint32_t pos = atomicAdd(&scal[2], 1u);
-            stage[pos] = e; // pos < kc by construction
-        }
-    }
+    compact_le<NT>(each, pivot, stage, (uint32_t)kc, Pk, &ss.out_count, tid);
     __syncthreads();
     if (unsorted) {
         // the caller re-ranks the kept entries anyway and only needs to know which one has the worst key: it goes to
         // position kc - 1 (one swap), the other kc - 1 stay as the compaction left them -- no sort (-4 us)
-        unsigned long long *mx = reinterpret_cast<unsigned long long *>(hist);
+        unsigned long long *mx = reinterpret_cast<unsigned long long *>(ss.radix.bins);
         if (tid == 0) mx[0] = 0ull;
         __syncthreads();
         unsigned long long m = 0ull;
@@ -273,7 +169,7 @@ __global__ __launch_bounds__(NT) void select_kernel(CandState cs, const int *qse
         return; // (no emit on this route: the re-rank writes the results)
     }
     // (this path has P > 2 * Pk, so sh[0..Pk) and the staging tail sh[P..P+Pk) do not overlap)
-    for (uint32_t i = tid; i < Pk; i += NT) sh[i] = i < (uint32_t)kc ? stage[i] : kEntryMax;
+    for (uint32_t i = tid; i < Pk; i += NT) sh[i] = stage[i];
     __syncthreads();
     bitonic_sort_u64(sh, Pk, tid, NT);
     for (uint32_t i = tid; i < (uint32_t)kc; i += NT) list[i] = sh[i];
@@ -306,7 +202,7 @@ void launch_select(CandState cs, const int *qsel, int nsel, int kc, uint32_t boo
     EmitArgs em{};
     if (emit) em = *emit;
     if (nsel <= 0) return;
-    const size_t shmem = (size_t)next_pow2_host(cs.cap) * sizeof(uint64_t) + (256 + 4 + 8) * sizeof(uint32_t);
+    const size_t shmem = (size_t)next_pow2_host(cs.cap) * sizeof(uint64_t) + sizeof(SelectScratch);
     static const int big_max = lb_tunable("LB_SELECT_BIG_MAXQ", 512); // (1024-thread selects: 10 us less than 256-thread ones at 128-384 queries)
     if (nsel <= big_max) { // few queries: one big workgroup each, latency matters
         allow_big_lds(select_kernel<1024>, shmem);
@@ -332,20 +228,7 @@ __global__ void emit_lists_kernel(CandState cs, const int *qsel, int nsel, int k
     const int q = qsel ? qsel[j] : j;
     // the slot's status word goes straight to pinned host memory: no separate D2H copy after the search
     if (flags_host && threadIdx.x == 0) flags_host[q] = cs.flags[q];
-    const uint32_t n = cs.cnt[q];
-    const uint64_t *list = cs.lists + (size_t)q * cs.cap;
-    for (int r = threadIdx.x; r < k; r += blockDim.x) {
-        float d = FLT_MAX;
-        int64_t lab = -1;
-        if ((uint32_t)r < n) {
-            const uint64_t e = list[r];
-            d = entry_key(e);
-            const uint32_t row = entry_row(e);
-            lab = ids ? ids[row] : (int64_t)row;
-        }
-        out_dist[(int64_t)q * k + r] = d;
-        out_labels[(int64_t)q * k + r] = lab;
-    }
+    emit_sorted(cs.lists + (size_t)q * cs.cap, cs.cnt[q], k, q, ids, out_dist, out_labels, threadIdx.x, blockDim.x);
 }
 
 void launch_emit_lists(CandState cs, const int *qsel, int nsel, int k, const int64_t *ids,
