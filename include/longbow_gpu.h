@@ -699,18 +699,34 @@ int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms);
  *                     below 256 MB; the vectors are not kept), rebuilds the lists of ALL rows by a stable counting sort (each
  *                     list holds its rows ascending) and copies all codes into list order: O(ntotal) per call, so add in large
  *                     pieces.  Codes, lists and the list-major copy are committed together, or nothing is.
+ *   filter            a row filter on the handle, with the mask, null and combine rules of lb_gpu_ivf_set_filter / _filter_*: a
+ *                     row is visible iff its mask byte is non-zero; a NULL mask clears the filter; n != ntotal is
+ *                     LB_ERR_INVALID_ARG with a last_error text and leaves the filter as it was; a predicate's nulls never match;
+ *                     combine 0 replaces the mask, 1 ANDs into it and replaces when there is none; op outside 0..5 or a negative
+ *                     validity_offset is LB_ERR_INVALID_ARG.  The probes of a query do not change: a probed list with no visible
+ *                     row contributes nothing and no other list takes its place.  The result is the first k rows in ascending
+ *                     (distance, r) order among the VISIBLE rows whose list is a probe, with the same labels, padding and
+ *                     distances, bit for bit; nprobe >= nlist gives lb_gpu_pq_search over the same codes under the same mask
+ *                     (lb_gpu_pq_set_filter).  Rows added after a filter was set are visible; such an add commits the codes, the
+ *                     lists, the list-major copy, the mask bytes and the visible lists together or not at all.  list_sizes,
+ *                     assignments, get_codes, get_centroids and ntotal ignore the filter; nvisible is the number of rows a search
+ *                     can see (ntotal without a filter).  Any filter, an all-visible one too, searches the visible lists (of each
+ *                     list the positions of its visible rows in the list-major copy, ascending, built on the device by every
+ *                     filter call and every add under a filter: a list's reads stay inside its run of codes), so the cost follows
+ *                     the visible rows of the probed lists, and last_search_stats counts those.
  *   memory            the codes are held in insertion order (what get_codes returns) and, beside each of the two pairs of lists
  *                     an add alternates between, once more in list order, so that a probed list is one contiguous run of
- *                     size * M bytes: 3 * M bytes a row, plus 12 bytes a row of lists and 8 of ids.  hbm_bytes reports it.
+ *                     size * M bytes: 3 * M bytes a row, plus 12 bytes a row of lists and 8 of ids; from the first filter on 13
+ *                     more (the mask byte, the filter's own list, two visible lists).  hbm_bytes reports it.
  *   limits            nlist in 1..65536, k in 1..LB_MAX_K, fewer than 2^31 rows: LB_ERR_UNSUPPORTED beyond.  nprobe <= 0 is
  *                     LB_ERR_INVALID_ARG, nprobe > nlist is clamped.  Fewer than all lists are at most LB_MAX_K probes (the
  *                     coarse search's k; LB_ERR_UNSUPPORTED beyond); every list probed needs no coarse search and works for any
  *                     nlist.
  * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
- * refused call writes nothing.  Searches and reads share the handle; adds and reserve take it alone.  ctx (nullable) is polled
- * before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here: row filters, residual
- * codes, adding ready-made codes with caller-given lists, search combining, lb_gpu_comm_*, removing rows, Save / Load, and the Go
- * and C++ mirrors. */
+ * refused call writes nothing.  Searches and reads share the handle; adds, reserve and the filter calls take it alone.  ctx
+ * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here:
+ * residual codes, a filter given per search call, adding ready-made codes with caller-given lists, search combining,
+ * lb_gpu_comm_*, removing rows, Save / Load, and the Go and C++ mirrors. */
 typedef struct lb_gpu_ivfpq lb_gpu_ivfpq;
 lb_gpu_ivfpq *lb_gpu_ivfpq_new(int device, const uint8_t *codebook_blob, size_t len, int order, int nlist, const float *centroids,
                                int *out_status);
@@ -721,7 +737,8 @@ int lb_gpu_ivfpq_m(const lb_gpu_ivfpq *p);
 int lb_gpu_ivfpq_order(const lb_gpu_ivfpq *p);
 int lb_gpu_ivfpq_nlist(const lb_gpu_ivfpq *p);
 int64_t lb_gpu_ivfpq_ntotal(const lb_gpu_ivfpq *p);
-int64_t lb_gpu_ivfpq_hbm_bytes(const lb_gpu_ivfpq *p); /* codes (three times), ids, lists, codebooks and the coarse index */
+int64_t lb_gpu_ivfpq_hbm_bytes(const lb_gpu_ivfpq *p); /* codes (three times), ids, lists, codebooks, the coarse index and what a
+                                                          row filter holds */
 int lb_gpu_ivfpq_get_centroids(lb_gpu_ivfpq *p, float *out); /* f32[nlist*dims] */
 int lb_gpu_ivfpq_reserve(lb_gpu_ivfpq *p, int64_t n_total);
 int lb_gpu_ivfpq_add(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *ids); /* assign, encode, append */
@@ -734,13 +751,23 @@ int lb_gpu_ivfpq_search_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, i
                             const lb_cancel *ctx);
 int lb_gpu_ivfpq_search_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist,
                                    int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* the row filter, as lb_gpu_ivf_set_filter / _filter_int64 / _filter_float32 / _nvisible */
+int lb_gpu_ivfpq_set_filter(lb_gpu_ivfpq *p, const uint8_t *mask, int64_t n);
+int lb_gpu_ivfpq_filter_int64(lb_gpu_ivfpq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine);
+int lb_gpu_ivfpq_filter_float32(lb_gpu_ivfpq *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                                int64_t validity_offset, int combine);
+int64_t lb_gpu_ivfpq_nvisible(const lb_gpu_ivfpq *p);
 /* telemetry of the last search only, as lb_gpu_ivf_last_search_stats: out[0] queries, out[1] rows scanned summed over the
- * queries, out[2] the largest per-query count, out[3] queries whose selection ran from LDS */
+ * queries, out[2] the largest per-query count, out[3] queries whose selection ran from LDS; under a row filter the rows are the
+ * visible ones of the probed lists */
 int lb_gpu_ivfpq_last_search_stats(lb_gpu_ivfpq *p, int64_t out[4]);
 /* instrumentation (tools/ivfpq_bench.py), as lb_gpu_ivf_set_profiling: ms[0] the probes (the coarse search), ms[1] the plan,
  * ms[2] the ADC tables, ms[3] the scan of the probed lists' codes, ms[4] the selection; summed over the search's batches */
 int lb_gpu_ivfpq_set_profiling(lb_gpu_ivfpq *p, int enable);
 int lb_gpu_ivfpq_last_timing(lb_gpu_ivfpq *p, float ms[5]);
+/* as lb_gpu_ivf_last_build_timing: the last profiled build of the visible lists (tools/code_filter_bench.py --index ivfpq) */
+int lb_gpu_ivfpq_last_build_timing(lb_gpu_ivfpq *p, float *ms);
 
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:

@@ -234,9 +234,14 @@ SIGNATURES = [
     ("lb_gpu_ivfpq_search", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     ("lb_gpu_ivfpq_search_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
     ("lb_gpu_ivfpq_search_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq_set_filter", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_ivfpq_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
+    ("lb_gpu_ivfpq_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
+    ("lb_gpu_ivfpq_nvisible", _i64, [_vp]),
     ("lb_gpu_ivfpq_last_search_stats", _i, [_vp, C.POINTER(C.c_int64)]),
     ("lb_gpu_ivfpq_set_profiling", _i, [_vp, _i]),
     ("lb_gpu_ivfpq_last_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq_last_build_timing", _i, [_vp, _vp]),
     ("lb_gpu_merge_topk_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_packed_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_rrf_fuse_device", _i, [_i, _i64, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),

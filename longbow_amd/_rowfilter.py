@@ -1,4 +1,4 @@
-"""The row filter of the code indexes and of the IVF-Flat index, shared by bq.py, sq8.py, pq.py and ivf.py."""
+"""The row filter of the code indexes and of the IVF indexes, shared by bq.py, sq8.py, pq.py, ivf.py and ivfpq.py."""
 import numpy as np
 
 
@@ -7,7 +7,8 @@ class RowFilterMixin:
     <_prefix>_set_filter / _filter_int64 / _filter_float32 / _nvisible entry points.  With a filter every search returns the
     exact k-NN among the visible rows (labels stay corpus rows); rows added later are visible; the calls that address rows
     directly ignore it."""
-    _prefix = None  # "lb_gpu_bq" / "lb_gpu_sq8" / "lb_gpu_pq" / "lb_gpu_ivf" (ivf.IVFFlat: the visible rows of the probed lists)
+    _prefix = None  # "lb_gpu_bq" / "lb_gpu_sq8" / "lb_gpu_pq" / "lb_gpu_ivf" / "lb_gpu_ivfpq" (ivf.IVFFlat, ivfpq.IVFPQ: the visible rows
+    #                 of the probed lists)
 
     def set_filter(self, mask):
         """mask: ntotal bytes, a row is visible iff its byte is non-zero; None clears the filter"""

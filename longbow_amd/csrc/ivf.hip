@@ -5,27 +5,12 @@
 #include "lb_device.h"
 #include "lb_ivf_host.h"
 
-#include <stdexcept>
-
 using namespace lb;
 
-struct lb_gpu_ivf : FilteredHandle { // searches and reads share mu; adds, reserve and the filter calls take it alone
+struct lb_gpu_ivf : IvfHandle { // the partition, and under a row filter the visible lists of rows (lb_ivf_host.h)
     int metric = 0, order = 0;
-    IvfPartition part;              // the centroids (the handle's metric and order) and the lists of all rows (lb_ivf_host.h)
     DevBuf<float> d_rows;           // [capacity][dims], insertion order
-    // the row filter (lb_handle.h): a search under one walks the visible lists, the rows of each list whose mask byte is
-    // non-zero, in the list's order.  They are built by every filter call and by every add to a filtered handle, into the pair
-    // that is not in use; filter.n_visible is d_voff[vcur][nlist].  filter.rowmap is rebuilt by the filter calls only and
-    // nothing here reads it.
-    DevBuf<uint32_t> d_voff[2];     // [nlist + 1]
-    DevBuf<uint32_t> d_vlist[2];    // [capacity] from the first filter on
-    int vcur = 0;
-    std::vector<int64_t> h_vsizes;  // [nlist]: what part.h_sizes is to the lists
     float timing[4] = {0, 0, 0, 0};  // of the last profiled search (under err_mu): probes, plan, scan, select; ms summed over its batches
-    float build_ms = 0;              // of the last profiled build of the visible lists (under err_mu): its launches alone
-    // what a search walks, and the sizes that go with it
-    IvfLists lists() const { return filter.on ? IvfLists{d_voff[vcur].get(), d_vlist[vcur].get(), part.nlist} : part.all_lists(part.cur); }
-    const std::vector<int64_t> &sizes() const { return filter.on ? h_vsizes : part.h_sizes; }
 };
 
 namespace {
@@ -37,68 +22,16 @@ void ivf_grow(lb_gpu_ivf *p, int64_t need, bool want_ids)
     if (cap < 0) return;
     IvfGrowth g;                                                                       // 2.
     DevBuf<float> nr;
-    DevBuf<uint32_t> nv[2];
-    g.stage(p, p->part, cap, want_ids);
+    g.stage(p, cap, want_ids);
     if (g.resize) {
         nr.alloc((size_t)cap * p->dims);
         if (p->n > 0) LB_HIP(hipMemcpy(nr.get(), p->d_rows.get(), (size_t)p->n * p->dims * 4, hipMemcpyDeviceToDevice));
-        if (p->filter.on) { // an active filter keeps its visible lists
-            for (DevBuf<uint32_t> &v : nv) v.alloc((size_t)cap);
-            if (p->filter.n_visible > 0)
-                LB_HIP(hipMemcpy(nv[p->vcur].get(), p->d_vlist[p->vcur].get(), (size_t)p->filter.n_visible * 4, hipMemcpyDeviceToDevice));
-        }
         p->filter.grow(p->n, cap);                                                     // 3. (the last step that can fail)
     }
-    g.commit(p->part);                                                                 // 4.
+    g.commit(p);                                                                       // 4.
     if (!g.resize) return;
-    if (p->filter.on)
-        for (int i = 0; i < 2; i++) p->d_vlist[i] = std::move(nv[i]);
     p->d_rows = std::move(nr);
     p->capacity = cap;
-}
-
-// The visible lists of mask[0, n) over the lists `L` of those n rows, into pair `to`; drains s.  Nothing of the handle but that
-// pair's buffers is written: the caller commits vsizes, `to` and the count it gets back.  scratch: a lease declared outside the
-// caller's guard.
-int64_t build_visible(lb_gpu_ivf *p, const IvfLists &L, int64_t n, int to, Lease &scratch, std::vector<int64_t> &vsizes, hipStream_t s)
-{
-    const int nlist = p->part.nlist;
-    std::vector<uint32_t> h_voff((size_t)nlist + 1);
-    vsizes.resize((size_t)nlist);
-    if (p->d_vlist[to].count() < (size_t)p->capacity) p->d_vlist[to].alloc((size_t)p->capacity);
-    scratch.reset(p->device, ivf_visible_scratch_bytes(n));
-    const bool prof = p->part.profiling.load();
-    EventH ev[2];
-    if (prof) {
-        for (EventH &e : ev) LB_HIP(hipEventCreate(&e.h));
-        LB_HIP(hipEventRecord(ev[0], s));
-    }
-    LB_HIP(launch_ivf_visible(p->filter.mask.get(), L, n, scratch.p, p->d_voff[to].get(), p->d_vlist[to].get(), s));
-    LB_LAUNCH_CHECK();
-    if (prof) LB_HIP(hipEventRecord(ev[1], s));
-    LB_HIP(hipMemcpyAsync(h_voff.data(), p->d_voff[to].get(), h_voff.size() * 4, hipMemcpyDeviceToHost, s));
-    LB_HIP(hipStreamSynchronize(s));
-    if (prof) {
-        float ms = 0.f;
-        LB_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        std::lock_guard<std::mutex> g(p->err_mu);
-        p->build_ms = ms;
-    }
-    for (int l = 0; l < nlist; l++) vsizes[l] = (int64_t)h_voff[l + 1] - (int64_t)h_voff[l];
-    return (int64_t)h_voff[nlist];
-}
-
-// what a filter call hands to the shell (lb_handle.h: `built`): the visible lists of the mask it has just written
-auto visible_builder(lb_gpu_ivf *p, Lease &scratch)
-{
-    return [p, &scratch](hipStream_t s) {
-        std::vector<int64_t> vsizes;
-        const int to = 1 - p->vcur;
-        const int64_t nv = build_visible(p, p->part.all_lists(p->part.cur), p->n, to, scratch, vsizes, s);
-        if (nv != p->filter.n_visible) throw std::logic_error("the visible lists do not hold the visible rows"); // (LB_ERR_INTERNAL)
-        p->h_vsizes.swap(vsizes);
-        p->vcur = to;
-    };
 }
 
 int add_impl(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids, bool on_device)
@@ -130,18 +63,9 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids,
         const int nxt = 1 - P.cur;
         // 4. under a filter the new rows are visible: the visible lists of all rows, from the new lists, into the pair not in use
         //    (the mask bytes behind the stored rows belong to nobody until the commit)
-        const int vnxt = 1 - p->vcur;
-        int64_t nvis = 0;
-        if (filtered) {
-            LB_HIP(hipMemsetAsync(p->filter.mask.get() + p->n, 1, (size_t)n, s));
-            nvis = build_visible(p, P.all_lists(nxt), total, vnxt, vis, vsizes, s);
-        }
+        const int64_t nvis = filtered ? ivf_add_visible(p, total, vis, vsizes, s) : 0;
         // 5. commit (nothing below throws)
-        if (filtered) {
-            p->h_vsizes.swap(vsizes);
-            p->vcur = vnxt;
-            p->filter.n_visible = nvis;
-        }
+        if (filtered) ivf_commit_visible(p, vsizes, nvis);
         P.h_sizes.swap(sizes);
         P.cur = nxt;
         P.has_ids = ids != nullptr;
@@ -185,11 +109,6 @@ lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist
     return ivf_open<lb_gpu_ivf>(device, dim, metric, order, nlist, centroids, out_status, [&](lb_gpu_ivf *p) {
         p->metric = metric;
         p->order = order;
-        p->h_vsizes.assign((size_t)nlist, 0);
-        for (DevBuf<uint32_t> &voff : p->d_voff) {
-            voff.alloc((size_t)nlist + 1);
-            LB_HIP(hipMemset(voff.get(), 0, ((size_t)nlist + 1) * 4));
-        }
     });
 }
 
@@ -205,9 +124,7 @@ int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivf *>(p)->mu);
-    const RowFilter &f = p->filter;
-    return (int64_t)(p->d_rows.count() * 4 + (p->d_voff[0].count() + p->d_voff[1].count() + p->d_vlist[0].count() + p->d_vlist[1].count()) * 4 +
-                     f.mask.count() + (f.rowmap.count() + f.scratch.count()) * 4) + p->part.hbm_bytes();
+    return (int64_t)(p->d_rows.count() * 4) + p->visible_bytes() + p->part.hbm_bytes();
 }
 
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total)
@@ -217,31 +134,18 @@ int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total)
 
 // ---- the row filter (lb_handle.h) ---------------------------------------------------------------------------------------
 int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p) { return filter_nvisible(p); }
-int lb_gpu_ivf_set_filter(lb_gpu_ivf *p, const uint8_t *mask, int64_t n)
-{
-    Lease vis;
-    return filter_set(p, mask, n, visible_builder(p, vis));
-}
+int lb_gpu_ivf_set_filter(lb_gpu_ivf *p, const uint8_t *mask, int64_t n) { return ivf_set_filter(p, mask, n); }
 int lb_gpu_ivf_filter_int64(lb_gpu_ivf *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
                             int64_t validity_offset, int combine)
 {
-    Lease vis;
-    return filter_column<int64_t>(p, column, n, value, op, validity, validity_offset, combine, visible_builder(p, vis));
+    return ivf_filter_column<int64_t>(p, column, n, value, op, validity, validity_offset, combine);
 }
 int lb_gpu_ivf_filter_float32(lb_gpu_ivf *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
                               int64_t validity_offset, int combine)
 {
-    Lease vis;
-    return filter_column<float>(p, column, n, value, op, validity, validity_offset, combine, visible_builder(p, vis));
+    return ivf_filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
 }
-
-int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms)
-{
-    if (!p || !ms) return LB_ERR_INVALID_ARG;
-    std::lock_guard<std::mutex> g(p->err_mu);
-    *ms = p->build_ms;
-    return LB_OK;
-}
+int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms) { return ivf_last_build_timing(p, ms); }
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
 int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false); }

@@ -9,9 +9,8 @@
 
 using namespace lb;
 
-struct lb_gpu_ivfpq : CodeHandle { // searches and reads share mu; adds and reserve take it alone
+struct lb_gpu_ivfpq : IvfHandle { // the partition (L2), and under a row filter the visible lists of positions (lb_ivf_host.h)
     int M = 0, K = 0, sub = 0, order = 0;
-    IvfPartition part;              // the centroids (L2, the handle's order) and the lists of all rows (lb_ivf_host.h)
     DevBuf<float> d_codebooks;      // [M][K][sub]
     DevBuf<uint8_t> d_codes;        // [capacity][M], insertion order: what get_codes returns
     // the list-major codes are built for all rows by every add, with the lists, into the pair that is not in use
@@ -34,7 +33,7 @@ void ivfpq_grow(lb_gpu_ivfpq *p, int64_t need, bool want_ids)
     IvfGrowth g;                                                                // 2.
     DevBuf<uint8_t> nc, nlc[2];
     const int cur = p->part.cur;
-    g.stage(p, p->part, cap, want_ids);
+    g.stage(p, cap, want_ids);
     if (g.resize) {
         nc.alloc((size_t)cap * p->M);
         for (DevBuf<uint8_t> &l : nlc) l.alloc((size_t)cap * p->M);
@@ -42,8 +41,9 @@ void ivfpq_grow(lb_gpu_ivfpq *p, int64_t need, bool want_ids)
             LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice));
             LB_HIP(hipMemcpy(nlc[cur].get(), p->d_lcodes[cur].get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice));
         }
+        p->filter.grow(p->n, cap);                                              // 3. (the last step that can fail)
     }
-    g.commit(p->part);                                                          // 4. (no row filter: there is no step 3)
+    g.commit(p);                                                                // 4.
     if (!g.resize) return;
     p->d_codes = std::move(nc);
     for (int i = 0; i < 2; i++) p->d_lcodes[i] = std::move(nlc[i]);
@@ -61,13 +61,14 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
     IvfPartition &P = p->part;
     if (const int st = ivf_ids_consistent(p, P, ids)) return st;
     if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease vec, lab, hist;
+    Lease vec, lab, hist, vis;
     return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = p->stream;
         const int64_t total = p->n + n;
         const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        std::vector<int64_t> sizes;
+        std::vector<int64_t> sizes, vsizes;
+        const bool filtered = p->filter.on;
         ivfpq_grow(p, total, ids != nullptr);
         if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, kind, s));
         // 1. the vectors, a piece at a time: 2. their lists, 3. their codes
@@ -91,7 +92,11 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
         ivf_sort_lists(p, P, total, hist, s);
         launch_ivfpq_permute(p->d_codes.get(), P.d_list[nxt].get(), total, p->M, p->d_lcodes[nxt].get(), s);
         if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
-        // 6. commit (nothing below throws)
+        // 6. under a filter the new rows are visible: the visible lists of all rows, from the new lists (every position changes
+        //    with them), into the pair not in use
+        const int64_t nvis = filtered ? ivf_add_visible(p, total, vis, vsizes, s) : 0;
+        // 7. commit (nothing below throws)
+        if (filtered) ivf_commit_visible(p, vsizes, nvis);
         P.h_sizes.swap(sizes);
         P.cur = nxt;
         P.has_ids = ids != nullptr;
@@ -100,8 +105,8 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
     });
 }
 
-// The handle's call of the search loop (lb_ivf_host.h): exact ADC k-NN.  Its middle steps are the queries' tables, a timing
-// slot of their own, and the scan of the list-major codes.
+// The handle's call of the search loop (lb_ivf_host.h): exact ADC k-NN; under a filter it walks the visible lists.  Its middle steps
+// are the queries' tables, a timing slot of their own, and the scan of the list-major codes.
 int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
                      const lb_cancel *ctx, Lease &sc)
 {
@@ -112,13 +117,14 @@ int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int n
     const uint8_t *lcodes = p->d_lcodes[P.cur].get();
     float *d_tables = nullptr;
     return ivf_search(
-        p, p->part, P.all_lists(P.cur), P.h_sizes, a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
+        p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
         [&](Carve &c, IvfBatch &, int64_t nb) { d_tables = c.take<float>((size_t)nb * p->M * 256 * 4); },
         [&](const IvfBatch &b, int64_t, auto &&, auto &&next) {
             if (!next()) return false; // (the plan's slot ends here)
             launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, b.Q, b.nq, d_tables, s);
             if (!next()) return false;
-            launch_ivfpq_scan(b, d_tables, p->M, lcodes, p->n, s);
+            if (p->filter.on) launch_ivfpq_scan_visible(b, d_tables, p->M, lcodes, p->n, P.d_list[P.cur].get(), p->filter.n_visible, s);
+            else launch_ivfpq_scan(b, d_tables, p->M, lcodes, p->n, s);
             return true;
         });
 }
@@ -142,6 +148,7 @@ lb_gpu_ivfpq *lb_gpu_ivfpq_new(int device, const uint8_t *blob, size_t len, int 
         p->K = (int)K;
         p->sub = (int)sub;
         p->order = order;
+        p->positions = true; // a visible list addresses the list-major codes
         p->d_codebooks.alloc((len - 12) / sizeof(float));
         LB_HIP(hipMemcpy(p->d_codebooks.get(), blob + 12, len - 12, hipMemcpyHostToDevice)); // (f32 little-endian on the wire, as pq.hip)
     });
@@ -159,7 +166,8 @@ int64_t lb_gpu_ivfpq_hbm_bytes(const lb_gpu_ivfpq *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivfpq *>(p)->mu);
-    return (int64_t)(p->d_codes.count() + p->d_lcodes[0].count() + p->d_lcodes[1].count() + p->d_codebooks.count() * 4) + p->part.hbm_bytes();
+    return (int64_t)(p->d_codes.count() + p->d_lcodes[0].count() + p->d_lcodes[1].count() + p->d_codebooks.count() * 4) + p->visible_bytes() +
+           p->part.hbm_bytes();
 }
 
 int lb_gpu_ivfpq_reserve(lb_gpu_ivfpq *p, int64_t n_total)
@@ -179,6 +187,21 @@ int lb_gpu_ivfpq_get_codes(lb_gpu_ivfpq *p, int64_t row0, int64_t n, uint8_t *co
         return LB_OK;
     });
 }
+
+// ---- the row filter (lb_handle.h, lb_ivf_host.h) ------------------------------------------------------------------------
+int64_t lb_gpu_ivfpq_nvisible(const lb_gpu_ivfpq *p) { return filter_nvisible(p); }
+int lb_gpu_ivfpq_set_filter(lb_gpu_ivfpq *p, const uint8_t *mask, int64_t n) { return ivf_set_filter(p, mask, n); }
+int lb_gpu_ivfpq_filter_int64(lb_gpu_ivfpq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine)
+{
+    return ivf_filter_column<int64_t>(p, column, n, value, op, validity, validity_offset, combine);
+}
+int lb_gpu_ivfpq_filter_float32(lb_gpu_ivfpq *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                                int64_t validity_offset, int combine)
+{
+    return ivf_filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
+}
+int lb_gpu_ivfpq_last_build_timing(lb_gpu_ivfpq *p, float *ms) { return ivf_last_build_timing(p, ms); }
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
 int lb_gpu_ivfpq_add(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false); }

@@ -562,7 +562,8 @@ hipError_t launch_ivf_sort(const uint32_t *assign, int64_t n, int nlist, uint32_
 // The n list positions are walked as one array, VIS_ROWS to a workgroup and eight to a thread, so every list keeps its order.
 //   count    bit i of a thread's byte = mask[rows[position i]] != 0 (the only gather); the byte is kept, the workgroup's sum too
 //   offsets  launch_compact_offsets over the workgroups' sums
-//   place    the visible rows of each workgroup go behind those before it; in the same launch one wave per list boundary
+//   place    the visible rows of each workgroup (POS: their positions instead, which need no load) go behind those before it; in
+//            the same launch one wave per list boundary
 //            counts the visible positions below off[l]: the sum of the workgroups before its own, plus the bits below it in that
 //            workgroup's 64 words (a lane a word)
 // Integer only; no workgroup waits for another.
@@ -578,7 +579,7 @@ struct IvfVisible {
     uint32_t *blk;       // [nblk + 1]: visible positions per workgroup, then their exclusive prefix and the total
     uint32_t *bits;      // [nblk][VIS_WORDS]: position p is bit p % 32 of word p / 32; positions past n are 0
     uint32_t *voff;      // [nlist + 1]
-    uint32_t *vrows;     // [n]
+    uint32_t *vrows;     // [n]: the visible rows, or their positions in L.rows
 };
 
 // the sum of v over the workgroup's four waves, in every thread; `before`: the sum over the waves below this one
@@ -630,6 +631,7 @@ __global__ __launch_bounds__(VIS_THREADS) void ivf_visible_count_kernel(IvfVisib
 }
 
 // workgroups [0, nblk) place the rows; the ones behind them take four list boundaries each, a wave a boundary
+template <bool POS>
 __global__ __launch_bounds__(VIS_THREADS) void ivf_visible_place_kernel(IvfVisible a)
 {
     __shared__ uint32_t s_wave[VIS_THREADS / 64];
@@ -657,7 +659,13 @@ __global__ __launch_bounds__(VIS_THREADS) void ivf_visible_place_kernel(IvfVisib
     (void)vis_block_sum(incl, s_wave, before);
     if (b == 0) return;
     uint64_t at = (uint64_t)a.blk[blockIdx.x] + before + incl - c;
-    if (base + VIS_PER <= a.n) {
+    if (POS) {
+        for (int i = 0; i < VIS_PER; i++)
+            if ((b >> i) & 1u) { // (set only for positions below n < 2^31)
+                if (at < (uint64_t)a.n) a.vrows[at] = (uint32_t)(base + i);
+                at++;
+            }
+    } else if (base + VIS_PER <= a.n) {
         uint32_t r[VIS_PER];
         vis_load8(a.L.rows, base, r);
 #pragma unroll
@@ -684,7 +692,8 @@ size_t ivf_visible_scratch_bytes(int64_t n)
     return vis_bits_at(nb) + (size_t)nb * VIS_WORDS * 4;
 }
 
-hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, void *scratch, uint32_t *voff, uint32_t *vrows, hipStream_t s)
+hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, bool positions, void *scratch, uint32_t *voff, uint32_t *vrows,
+                              hipStream_t s)
 {
     if (n <= 0) return hipMemsetAsync(voff, 0, ((size_t)L.nlist + 1) * 4, s);
     IvfVisible a{};
@@ -699,7 +708,8 @@ hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n,
     const int64_t bounds = ((int64_t)L.nlist + 1 + VIS_THREADS / 64 - 1) / (VIS_THREADS / 64);
     hipLaunchKernelGGL(ivf_visible_count_kernel, dim3((unsigned)a.nblk), dim3(VIS_THREADS), 0, s, a);
     launch_compact_offsets(a.blk, a.nblk, s);
-    hipLaunchKernelGGL(ivf_visible_place_kernel, dim3((unsigned)(a.nblk + bounds)), dim3(VIS_THREADS), 0, s, a);
+    if (positions) hipLaunchKernelGGL(ivf_visible_place_kernel<true>, dim3((unsigned)(a.nblk + bounds)), dim3(VIS_THREADS), 0, s, a);
+    else hipLaunchKernelGGL(ivf_visible_place_kernel<false>, dim3((unsigned)(a.nblk + bounds)), dim3(VIS_THREADS), 0, s, a);
     return hipSuccess;
 }
 

@@ -1,6 +1,7 @@
 // kernels_ivfpq.hip -- the IVF-PQ index (ivfpq.hip; semantics in include/longbow_gpu.h, lb_gpu_ivfpq_*): the list-major copy of
-// the codes and the exact ADC scan of a query's probed lists.  The plan, the selection and the counting sort are the IVF-Flat
-// index's (kernels_ivf.hip), the table and the codec the PQ handle's (kernels_pq.hip, kernels_pq2.hip).
+// the codes and the exact ADC scan of a query's probed lists, or under a row filter of their visible entries.  The plan, the
+// selection, the counting sort and the build of the visible lists are the IVF-Flat index's (kernels_ivf.hip), the table and the
+// codec the PQ handle's (kernels_pq.hip, kernels_pq2.hip).
 //
 // The arithmetic is adc_scan_kernel's, through the same device functions (lb_exact.h): the f32 sum of table[j * 256 + code[j]]
 // in j order, float(sqrt(double(sum))), pack_entry(distance, row).  Nothing is admitted against a threshold: every scanned
@@ -62,8 +63,14 @@ void launch_ivfpq_permute(const uint8_t *codes, const uint32_t *rows, int64_t n,
 // position t: slot s = the last one with seg[s] <= t, pos = off[probe[s]] + (t - seg[s]), the code row lcodes[pos], the row
 // number rows[pos].  Plain loads: other queries of the batch probe the same lists.  No atomics, no waits on other workgroups.
 // MCH: M / 16 at compile time (the row's 16-byte loads are issued together); 0: M % 16 == 0 at run time; -1: single bytes.
-template <int MCH, bool SEG_LDS>
-__global__ __launch_bounds__(IPQ_TILE) void ivfpq_scan_kernel(IvfBatch a, const float *tables, int M_rt, const uint8_t *lcodes, int64_t n)
+// VIS: the search runs under a row filter.  a.L is then the visible lists, whose entries are positions into the lists of all
+// rows: the t-th visible entry is vp = voff[probe[s]] + (t - seg[s]), one coalesced 4-byte load gives pos = vlist[vp], and from
+// there on the lane does what it does without a filter, at a position that stays inside the probed list's run of lcodes; the
+// row number comes from `rows`, the rows of all lists (unused without VIS, where a.L.rows is that array).  vp and pos are
+// checked against nvis and n before they index anything.
+template <int MCH, bool SEG_LDS, bool VIS>
+__global__ __launch_bounds__(IPQ_TILE) void ivfpq_scan_kernel(IvfBatch a, const float *tables, int M_rt, const uint8_t *lcodes, int64_t n,
+                                                              const uint32_t *rows, int64_t nvis)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     const int M = MCH > 0 ? MCH * 16 : M_rt;
@@ -105,7 +112,8 @@ __global__ __launch_bounds__(IPQ_TILE) void ivfpq_scan_kernel(IvfBatch a, const 
             const int64_t l = gprobe[lo];
             base = l >= 0 && l < a.L.nlist ? a.L.off[l] : 0xffffffffu;
         }
-        const uint64_t pos = (uint64_t)base + (t - seg[lo]);
+        uint64_t pos = (uint64_t)base + (t - seg[lo]);
+        if (VIS) pos = pos < (uint64_t)nvis ? a.L.rows[pos] : ~0ull; // (the visible entry -> its position)
         uint64_t key = kEntryMax;
         if (pos < (uint64_t)n) { // always: a non-empty slot is a list of the handle
             const uint8_t *c = lcodes + pos * (uint64_t)M;
@@ -121,14 +129,15 @@ __global__ __launch_bounds__(IPQ_TILE) void ivfpq_scan_kernel(IvfBatch a, const 
             } else {
                 sum = adc_row_sum<false>(smem, c, M);
             }
-            key = pack_entry(adc_distance(sum), a.L.rows[pos]);
+            key = pack_entry(adc_distance(sum), VIS ? rows[pos] : a.L.rows[pos]);
         }
         keys[t] = key;
     }
 }
 
-template <int MCH>
-static void launch_ivfpq_scan_m(const IvfBatch &a, const float *tables, int M, const uint8_t *lcodes, int64_t n, hipStream_t s)
+template <int MCH, bool VIS>
+static void launch_ivfpq_scan_m(const IvfBatch &a, const float *tables, int M, const uint8_t *lcodes, int64_t n, const uint32_t *rows,
+                                int64_t nvis, hipStream_t s)
 {
     const size_t table = (size_t)M * 256 * sizeof(float), segs = ((size_t)2 * a.np + 1) * sizeof(uint32_t);
     const bool seg_lds = table + segs <= (size_t)160 * 1024;
@@ -136,29 +145,45 @@ static void launch_ivfpq_scan_m(const IvfBatch &a, const float *tables, int M, c
     const dim3 grid((unsigned)ivfpq_scan_groups(a.nq, a.pmax), (unsigned)a.nq);
     if (seg_lds) {
         if (shmem > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ivfpq_scan_kernel<MCH, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((ivfpq_scan_kernel<MCH, true>), grid, dim3(IPQ_TILE), shmem, s, a, tables, M, lcodes, n);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ivfpq_scan_kernel<MCH, true, VIS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)shmem);
+        hipLaunchKernelGGL((ivfpq_scan_kernel<MCH, true, VIS>), grid, dim3(IPQ_TILE), shmem, s, a, tables, M, lcodes, n, rows, nvis);
     } else {
         if (shmem > 64 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ivfpq_scan_kernel<MCH, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem);
-        hipLaunchKernelGGL((ivfpq_scan_kernel<MCH, false>), grid, dim3(IPQ_TILE), shmem, s, a, tables, M, lcodes, n);
+            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ivfpq_scan_kernel<MCH, false, VIS>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)shmem);
+        hipLaunchKernelGGL((ivfpq_scan_kernel<MCH, false, VIS>), grid, dim3(IPQ_TILE), shmem, s, a, tables, M, lcodes, n, rows, nvis);
+    }
+}
+
+template <bool VIS>
+static void launch_ivfpq_scan_v(const IvfBatch &a, const float *tables, int M, const uint8_t *lcodes, int64_t n, const uint32_t *rows, int64_t nvis,
+                                hipStream_t s)
+{
+    if (a.nq <= 0 || n <= 0) return;
+    const bool vec = M % 16 == 0 && (reinterpret_cast<uintptr_t>(lcodes) & 15) == 0; // (tables: 16-byte aligned in every form)
+    if (!vec) return launch_ivfpq_scan_m<-1, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
+    switch (M / 16) { // the forms adc_scan_dma_kernel has
+    case 1: return launch_ivfpq_scan_m<1, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
+    case 2: return launch_ivfpq_scan_m<2, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
+    case 3: return launch_ivfpq_scan_m<3, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
+    case 4: return launch_ivfpq_scan_m<4, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
+    case 6: return launch_ivfpq_scan_m<6, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
+    case 8: return launch_ivfpq_scan_m<8, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
+    default: return launch_ivfpq_scan_m<0, VIS>(a, tables, M, lcodes, n, rows, nvis, s);
     }
 }
 
 void launch_ivfpq_scan(const IvfBatch &a, const float *tables, int M, const uint8_t *lcodes, int64_t n, hipStream_t s)
 {
-    if (a.nq <= 0 || n <= 0) return;
-    const bool vec = M % 16 == 0 && (reinterpret_cast<uintptr_t>(lcodes) & 15) == 0; // (tables: 16-byte aligned in every form)
-    if (!vec) return launch_ivfpq_scan_m<-1>(a, tables, M, lcodes, n, s);
-    switch (M / 16) { // the forms adc_scan_dma_kernel has
-    case 1: return launch_ivfpq_scan_m<1>(a, tables, M, lcodes, n, s);
-    case 2: return launch_ivfpq_scan_m<2>(a, tables, M, lcodes, n, s);
-    case 3: return launch_ivfpq_scan_m<3>(a, tables, M, lcodes, n, s);
-    case 4: return launch_ivfpq_scan_m<4>(a, tables, M, lcodes, n, s);
-    case 6: return launch_ivfpq_scan_m<6>(a, tables, M, lcodes, n, s);
-    case 8: return launch_ivfpq_scan_m<8>(a, tables, M, lcodes, n, s);
-    default: return launch_ivfpq_scan_m<0>(a, tables, M, lcodes, n, s);
-    }
+    launch_ivfpq_scan_v<false>(a, tables, M, lcodes, n, nullptr, 0, s);
+}
+
+void launch_ivfpq_scan_visible(const IvfBatch &a, const float *tables, int M, const uint8_t *lcodes, int64_t n, const uint32_t *rows, int64_t nvis,
+                               hipStream_t s)
+{
+    if (nvis <= 0) return; // (every seg is 0: no key is read)
+    launch_ivfpq_scan_v<true>(a, tables, M, lcodes, n, rows, nvis, s);
 }
 
 } // namespace lb

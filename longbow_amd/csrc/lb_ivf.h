@@ -46,11 +46,13 @@ void launch_ivf_narrow(const int64_t *labels, int64_t n, uint32_t *assign, hipSt
 size_t ivf_sort_hist_words(int64_t n, int nlist);
 hipError_t launch_ivf_sort(const uint32_t *assign, int64_t n, int nlist, uint32_t *hist, uint32_t *off, uint32_t *rows, hipStream_t s);
 
-// The visible lists of a row filter: visible list l is the rows of L's list l whose mask byte is non-zero, in the same order.
+// The visible lists of a row filter: visible list l is the rows of L's list l whose mask byte is non-zero, in the same order; with
+// `positions` it holds, in place of each such row, its position in L.rows (ascending in [off[l], off[l + 1])).
 // voff[nlist + 1] and vrows[voff[nlist]] (room for n) are written, voff[nlist] being the number of visible rows; scratch holds
 // ivf_visible_scratch_bytes(n) bytes, 16-byte aligned.  Three launches, or with n == 0 the memset of voff alone, whose error is
 // returned.
 size_t ivf_visible_scratch_bytes(int64_t n);
-hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, void *scratch, uint32_t *voff, uint32_t *vrows, hipStream_t s);
+hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, bool positions, void *scratch, uint32_t *voff, uint32_t *vrows,
+                              hipStream_t s);
 
 } // namespace lb

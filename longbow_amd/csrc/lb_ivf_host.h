@@ -3,14 +3,19 @@
 //
 // The contract:
 //   * IvfPartition is the coarse partition of a handle's rows: the inner exact f32 index over the centroids, the list of each row
-//     and the inverted lists over them.  It is a plain member named `part` of a handle that derives from CodeHandle; the functions
-//     here take (CodeHandle *h, IvfPartition &P, ...), the entry-point templates a T *p with p->part and p->timing;
+//     and the inverted lists over them.  It is the member `part` of IvfHandle, which both handles derive from and which also
+//     holds what the row filter (lb_handle.h) adds to a partition: the visible lists.  The functions here take
+//     (CodeHandle *h, IvfPartition &P, ...) or an IvfHandle *p, the entry-point templates a T *p with p->part and p->timing;
 //   * the rules at the head of lb_handle.h hold: every pooled Lease that a function here enqueues work on is the caller's, declared
 //     outside its guard(); coarse_fail drains the stream before leases go back; searches and reads take `mu` shared, adds and
 //     reserve take it alone.  Everything that takes a stream runs inside the caller's guard() and throws as its body does;
-//   * growth is all or nothing (IvfGrowth): stage() allocates and fills and may throw, commit() moves and cannot;
+//   * growth is all or nothing (IvfGrowth): stage() allocates and fills and may throw, then the handle's own buffers, then
+//     filter.grow (the last step that can fail), then commit(), which moves and cannot throw;
 //   * an add writes behind the stored rows and into the pair of lists that is not in use, and commits last: sizes, pair, ids flag
-//     and n, by the handle's add_impl, with nothing that throws after it;
+//     and n, by the handle's add_impl, with nothing that throws after it.  Under a filter the new rows are visible: the add also
+//     builds the visible lists of all rows into their pair not in use (ivf_add_visible) and commits them with the rest
+//     (ivf_commit_visible);
+//   * the filter calls rebuild the visible lists through ivf_visible_builder, the `built` hook of filter_set / filter_column;
 //   * ivf_search is the one search loop.  A handle supplies its scratch pieces and the launches between the plan and the
 //     selection; ctx is polled before every launch, a cancelled search publishes no stats, and the events of a profiled search
 //     fall where the handle's timing slots say.
@@ -20,6 +25,7 @@
 
 #include <atomic>
 #include <functional>
+#include <stdexcept>
 #include <vector>
 
 namespace lb {
@@ -52,9 +58,33 @@ struct IvfPartition {
     }
 };
 
+// What both IVF handles are: a partition and, for the row filter, the visible lists.  A search under a filter walks the visible
+// lists: of each list the entries whose row's mask byte is non-zero, in the list's order.  An entry is the row itself (IVF-Flat)
+// or, with `positions`, its position in the lists of all rows (IVF-PQ: the list-major codes are addressed by it, and the pair of
+// all lists gives its row).  They are built by every filter call and by every add to a filtered handle, into the pair that is not
+// in use; filter.n_visible is d_voff[vcur][nlist].  filter.rowmap is rebuilt by the filter calls only and nothing here reads it.
+struct IvfHandle : FilteredHandle { // searches and reads share mu; adds, reserve and the filter calls take it alone
+    IvfPartition part;              // the centroids and the lists of all rows
+    bool positions = false;         // what a visible list holds; fixed at creation
+    DevBuf<uint32_t> d_voff[2];     // [nlist + 1]
+    DevBuf<uint32_t> d_vlist[2];    // [capacity] from the first filter on
+    int vcur = 0;
+    std::vector<int64_t> h_vsizes;  // [nlist]: what part.h_sizes is to the lists
+    float build_ms = 0;             // of the last profiled build of the visible lists (under err_mu): its launches alone
+    // what a search walks, and the sizes that go with it
+    IvfLists lists() const { return filter.on ? IvfLists{d_voff[vcur].get(), d_vlist[vcur].get(), part.nlist} : part.all_lists(part.cur); }
+    const std::vector<int64_t> &sizes() const { return filter.on ? h_vsizes : part.h_sizes; }
+    int64_t visible_bytes() const // what the row filter holds on the device
+    {
+        return (int64_t)((d_voff[0].count() + d_voff[1].count() + d_vlist[0].count() + d_vlist[1].count()) * 4 + filter.mask.count() +
+                         (filter.rowmap.count() + filter.scratch.count()) * 4);
+    }
+};
+
 // ---- opening ----------------------------------------------------------------------------------------------------------------
-// A handle of `dims` dimensions over `nlist` centroids, the caller having checked its arguments: the partition's host fields and
-// offsets, init(p) for the handle's own, then the inner index of `metric` and `order` with the centroids in it.
+// A handle (T: an IvfHandle) of `dims` dimensions over `nlist` centroids, the caller having checked its arguments: the host fields
+// and offsets of the partition and of the visible lists, init(p) for the handle's own, then the inner index of `metric` and `order`
+// with the centroids in it.
 template <class T, class Init>
 T *ivf_open(int device, int dims, int metric, int order, int nlist, const float *centroids, int *out_status, Init &&init)
 {
@@ -65,10 +95,12 @@ T *ivf_open(int device, int dims, int metric, int order, int nlist, const float 
         P.nlist = nlist;
         P.h_cent.assign(centroids, centroids + (size_t)nlist * dims);
         P.h_sizes.assign((size_t)nlist, 0);
-        for (DevBuf<uint32_t> &off : P.d_off) {
-            off.alloc((size_t)nlist + 1);
-            LB_HIP(hipMemset(off.get(), 0, ((size_t)nlist + 1) * 4));
-        }
+        p->h_vsizes.assign((size_t)nlist, 0);
+        for (DevBuf<uint32_t> *offs : {P.d_off, p->d_voff})
+            for (int i = 0; i < 2; i++) {
+                offs[i].alloc((size_t)nlist + 1);
+                LB_HIP(hipMemset(offs[i].get(), 0, ((size_t)nlist + 1) * 4));
+            }
         init(p);
         P.coarse = lb_gpu_index_new(device, dims, metric, &inner);
         if (!P.coarse) return;
@@ -94,16 +126,18 @@ inline int64_t ivf_grow_to(const CodeHandle *h, const IvfPartition &P, int64_t n
     return need <= h->capacity ? h->capacity : grow_capacity(h->capacity, need, row_bytes);
 }
 
-// The partition's share of a handle's *_grow to `cap` rows.  The handle stages its own buffers beside it and commits them with it:
-// no old buffer is replaced before every new one is allocated and filled.
+// The share of the partition and of the visible lists in a handle's *_grow to `cap` rows.  The handle stages its own buffers beside
+// it, calls filter.grow and commits them with it: no old buffer is replaced before every new one is allocated and filled.
 struct IvfGrowth {
     DevBuf<int64_t> ids;
-    DevBuf<uint32_t> assign, list[2];
-    bool want_ids = false, resize = false;
-    void stage(const CodeHandle *h, const IvfPartition &P, int64_t cap, bool with_ids)
+    DevBuf<uint32_t> assign, list[2], vlist[2];
+    bool want_ids = false, resize = false, filtered = false;
+    void stage(const IvfHandle *h, int64_t cap, bool with_ids)
     {
+        const IvfPartition &P = h->part;
         want_ids = with_ids;
         resize = cap != h->capacity;
+        filtered = h->filter.on;
         if (want_ids) {
             ids.alloc((size_t)cap);
             if (h->n > 0 && P.has_ids) LB_HIP(hipMemcpy(ids.get(), P.d_ids.get(), (size_t)h->n * 8, hipMemcpyDeviceToDevice));
@@ -115,13 +149,20 @@ struct IvfGrowth {
             LB_HIP(hipMemcpy(assign.get(), P.d_assign.get(), (size_t)h->n * 4, hipMemcpyDeviceToDevice));
             LB_HIP(hipMemcpy(list[P.cur].get(), P.d_list[P.cur].get(), (size_t)h->n * 4, hipMemcpyDeviceToDevice));
         }
+        if (!filtered) return; // an active filter keeps its visible lists
+        for (DevBuf<uint32_t> &v : vlist) v.alloc((size_t)cap);
+        if (h->filter.n_visible > 0)
+            LB_HIP(hipMemcpy(vlist[h->vcur].get(), h->d_vlist[h->vcur].get(), (size_t)h->filter.n_visible * 4, hipMemcpyDeviceToDevice));
     }
-    void commit(IvfPartition &P) noexcept
+    void commit(IvfHandle *h) noexcept
     {
+        IvfPartition &P = h->part;
         if (want_ids) P.d_ids = std::move(ids);
         if (!resize) return;
         P.d_assign = std::move(assign);
         for (int i = 0; i < 2; i++) P.d_list[i] = std::move(list[i]);
+        if (filtered)
+            for (int i = 0; i < 2; i++) h->d_vlist[i] = std::move(vlist[i]);
     }
 };
 
@@ -178,6 +219,78 @@ inline int ivf_read_lists(CodeHandle *h, IvfPartition &P, int64_t total, std::ve
     }
     for (int l = 0; l < P.nlist; l++) sizes[l] = (int64_t)h_off[l + 1] - (int64_t)h_off[l];
     return LB_OK;
+}
+
+// ---- the visible lists ------------------------------------------------------------------------------------------------------
+// The visible lists of mask[0, n) over the lists `L` of those n rows, into pair `to`; drains s.  Nothing of the handle but that
+// pair's buffers is written: the caller commits vsizes, `to` and the count it gets back.  scratch: a lease declared outside the
+// caller's guard.
+inline int64_t ivf_build_visible(IvfHandle *p, const IvfLists &L, int64_t n, int to, Lease &scratch, std::vector<int64_t> &vsizes, hipStream_t s)
+{
+    const int nlist = p->part.nlist;
+    std::vector<uint32_t> h_voff((size_t)nlist + 1);
+    vsizes.resize((size_t)nlist);
+    if (p->d_vlist[to].count() < (size_t)p->capacity) p->d_vlist[to].alloc((size_t)p->capacity);
+    scratch.reset(p->device, ivf_visible_scratch_bytes(n));
+    const bool prof = p->part.profiling.load();
+    EventH ev[2];
+    if (prof) {
+        for (EventH &e : ev) LB_HIP(hipEventCreate(&e.h));
+        LB_HIP(hipEventRecord(ev[0], s));
+    }
+    LB_HIP(launch_ivf_visible(p->filter.mask.get(), L, n, p->positions, scratch.p, p->d_voff[to].get(), p->d_vlist[to].get(), s));
+    LB_LAUNCH_CHECK();
+    if (prof) LB_HIP(hipEventRecord(ev[1], s));
+    LB_HIP(hipMemcpyAsync(h_voff.data(), p->d_voff[to].get(), h_voff.size() * 4, hipMemcpyDeviceToHost, s));
+    LB_HIP(hipStreamSynchronize(s));
+    if (prof) {
+        float ms = 0.f;
+        LB_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        std::lock_guard<std::mutex> g(p->err_mu);
+        p->build_ms = ms;
+    }
+    for (int l = 0; l < nlist; l++) vsizes[l] = (int64_t)h_voff[l + 1] - (int64_t)h_voff[l];
+    return (int64_t)h_voff[nlist];
+}
+
+// what a filter call hands to the shell (lb_handle.h: `built`): the visible lists of the mask it has just written
+inline auto ivf_visible_builder(IvfHandle *p, Lease &scratch)
+{
+    return [p, &scratch](hipStream_t s) {
+        std::vector<int64_t> vsizes;
+        const int to = 1 - p->vcur;
+        const int64_t nv = ivf_build_visible(p, p->part.all_lists(p->part.cur), p->n, to, scratch, vsizes, s);
+        if (nv != p->filter.n_visible) throw std::logic_error("the visible lists do not hold the visible rows"); // (LB_ERR_INTERNAL)
+        p->h_vsizes.swap(vsizes);
+        p->vcur = to;
+    };
+}
+
+// the filter calls of a handle: lb_handle.h's with the visible lists built behind the mask
+inline int ivf_set_filter(IvfHandle *p, const uint8_t *mask, int64_t n)
+{
+    Lease vis;
+    return filter_set(p, mask, n, ivf_visible_builder(p, vis));
+}
+template <class T> int ivf_filter_column(IvfHandle *p, const T *column, int64_t n, T value, int op, const uint8_t *validity, int64_t voff, int combine)
+{
+    Lease vis;
+    return filter_column<T>(p, column, n, value, op, validity, voff, combine, ivf_visible_builder(p, vis));
+}
+
+// An add's step under a filter, after the lists of all `total` rows are in the partition's pair not in use: the new rows
+// [p->n, total) are visible (their mask bytes belong to nobody until the commit), and the visible lists of all rows are built from
+// the new lists into the pair not in use.  Drains s; -> the visible rows, for ivf_commit_visible
+inline int64_t ivf_add_visible(IvfHandle *p, int64_t total, Lease &scratch, std::vector<int64_t> &vsizes, hipStream_t s)
+{
+    LB_HIP(hipMemsetAsync(p->filter.mask.get() + p->n, 1, (size_t)(total - p->n), s));
+    return ivf_build_visible(p, p->part.all_lists(1 - p->part.cur), total, 1 - p->vcur, scratch, vsizes, s);
+}
+inline void ivf_commit_visible(IvfHandle *p, std::vector<int64_t> &vsizes, int64_t nvis) noexcept
+{
+    p->h_vsizes.swap(vsizes);
+    p->vcur = 1 - p->vcur;
+    p->filter.n_visible = nvis;
 }
 
 // ---- the search loop --------------------------------------------------------------------------------------------------------
@@ -371,6 +484,14 @@ template <class T> int ivf_set_profiling(T *p, int enable)
 {
     if (!p) return LB_ERR_INVALID_ARG;
     p->part.profiling.store(enable != 0);
+    return LB_OK;
+}
+
+inline int ivf_last_build_timing(IvfHandle *p, float *ms)
+{
+    if (!p || !ms) return LB_ERR_INVALID_ARG;
+    std::lock_guard<std::mutex> g(p->err_mu);
+    *ms = p->build_ms;
     return LB_OK;
 }
 

@@ -1,6 +1,6 @@
 // lb_ivfpq.h -- what ivfpq.hip (host) and kernels_ivfpq.hip (device) of the IVF-PQ index share beyond lb_ivf.h: the launchers of
-// the list-major copy of the codes and of the ADC scan over a query's probed lists.  The semantics are stated in
-// include/longbow_gpu.h (lb_gpu_ivfpq_*).
+// the list-major copy of the codes and of the ADC scan over a query's probed lists, without and under a row filter.  The
+// semantics are stated in include/longbow_gpu.h (lb_gpu_ivfpq_*).
 #pragma once
 #include "lb_ivf.h"
 
@@ -23,5 +23,9 @@ void launch_ivfpq_permute(const uint8_t *codes, const uint32_t *rows, int64_t n,
 // keys[q][t] = pack_entry(ADC distance, row) of the t-th position of the concatenation of q's probed lists, t in [0, seg[q][np]):
 // a.X, a.Q and a.qna are not read; tables is [a.nq][M][256] f32, lcodes the list-major codes of a.L, n the rows they hold
 void launch_ivfpq_scan(const IvfBatch &a, const float *tables, int M, const uint8_t *lcodes, int64_t n, hipStream_t s);
+// the same under a row filter: a.L is the visible lists, which hold positions into `rows`, the rows of the lists of all n rows that
+// lcodes follows; nvis is what they hold in all (voff[nlist]).  t runs over the concatenation of q's probed visible lists
+void launch_ivfpq_scan_visible(const IvfBatch &a, const float *tables, int M, const uint8_t *lcodes, int64_t n, const uint32_t *rows, int64_t nvis,
+                               hipStream_t s);
 
 } // namespace lb

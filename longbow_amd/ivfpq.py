@@ -5,7 +5,8 @@ exact ADC k-NN among the rows of the probed lists, bit for bit in the reference'
 with every list probed it equals pq.PQEncoder.Search over the same codes.  The codes are plain, not residual: a query's one table
 serves every list.  include/longbow_gpu.h states the semantics.
 
-  IVFPQ   the handle: codebooks and centroids given at creation, add / search / codes / list_sizes / assignments / last_search_stats
+  IVFPQ   the handle: codebooks and centroids given at creation, add / search / codes / list_sizes / assignments / last_search_stats,
+          and the row filter (set_filter / filter_column / nvisible)
   train   (centroids, codebook blob) from ivf.train and pq.train
 """
 import ctypes as C
@@ -14,6 +15,7 @@ import numpy as np
 
 from . import _lib, ivf, pq
 from ._ivfbase import IVFBase
+from ._rowfilter import RowFilterMixin
 
 FLT_MAX = ivf.FLT_MAX
 
@@ -26,9 +28,10 @@ def train(vectors, nlist, M, max_iter=20, seed=0, device=0):
     return centroids, blob
 
 
-class IVFPQ(IVFBase):
+class IVFPQ(RowFilterMixin, IVFBase):
     """lb_gpu_ivfpq: codebooks (the reference's serialised blob, or a pq.PQEncoder whose blob is taken), centroids f32
-    [nlist, dims], order 0 SEQ / 1 UNROLL4 of the coarse quantiser (L2)"""
+    [nlist, dims], order 0 SEQ / 1 UNROLL4 of the coarse quantiser (L2).  Under a row filter (RowFilterMixin) the probes stay as
+    they are and a search sees the visible rows of the probed lists alone."""
     _prefix = "lb_gpu_ivfpq"
     _timing_slots = 5
 
@@ -73,3 +76,9 @@ class IVFPQ(IVFBase):
     def last_timing(self):
         """ms of the last profiled search, summed over its batches: (probes, plan, ADC tables, scan, selection)"""
         return super().last_timing()
+
+    def last_build_timing(self):
+        """ms of the last profiled build of the visible lists (a filter call or an add under a filter): its launches alone"""
+        out = C.c_float(0)
+        self._check(self._lib.lb_gpu_ivfpq_last_build_timing(self._h, C.byref(out)))
+        return float(out.value)

@@ -1,7 +1,7 @@
-"""Filtered searches on the BQ, SQ8, PQ and IVF-Flat indexes: search time against the share of visible rows, one JSON line.
+"""Filtered searches on the BQ, SQ8, PQ, IVF-Flat and IVF-PQ indexes: search time against the share of visible rows, one JSON line.
 
-    python tools/code_filter_bench.py --index bq|sq8|pq|ivf [--rows 1000000] [--dim 768] [--k 100] [--nq 1,64,1024]
-                                      [--visible-pct 100,50,10] [--runs 3] [--reps 10] [--nlist 256] [--nprobe 8,32]
+    python tools/code_filter_bench.py --index bq|sq8|pq|ivf|ivfpq [--rows 1000000] [--dim 768] [--k 100] [--nq 1,64,1024]
+                                      [--visible-pct 100,50,10] [--runs 3] [--reps 10] [--nlist 256] [--nprobe 8,32] [--m 96]
 
 BQ and SQ8: rows are drawn on the device (uniform in [-0.5, 0.5)) and added as vectors.  PQ (defaults --rows 10000000,
 --nq 1,2,16, --visible-pct 100,50,10,1; M = dim / 8): code bytes uniform in [0, 256) are drawn on the device and added with
@@ -20,6 +20,10 @@ one.  Each is the p50 of `reps` searches with the HIP-event times of its steps f
 list scan, selection) and the rows it scanned.  Per share also the filter call: its wall time (the mask comes from host
 memory), the build of the visible lists alone by HIP events, and the bytes that build moves (per list position: the row read
 twice, a mask byte gathered, a bit written and read; per visible row 4 bytes written).
+
+IVF-PQ (defaults --rows 10000000, --nlist 1024, --m 96, otherwise as IVF-Flat; rows in pieces of 1M, codebooks and centroids as
+tools/ivfpq_bench.py, its queries too): the same comparison and the same figures, with five steps to a search (probes, plan, ADC
+tables, scan, selection).  The build reads each row number once (the place step writes positions and loads none).
 """
 import argparse
 import json
@@ -31,10 +35,12 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from longbow_amd import _lib, bq, gpu, ivf, pq, sq8  # noqa: E402
+from longbow_amd import _lib, bq, gpu, ivf, ivfpq, pq, sq8  # noqa: E402
 
 DEFAULTS = {"bq": (1_000_000, "1,64,1024", "100,50,10"), "sq8": (1_000_000, "1,64,1024", "100,50,10"),
-            "pq": (10_000_000, "1,2,16", "100,50,10,1"), "ivf": (1_000_000, "1,8", "100,50,10,1")}  # rows, nq, visible-pct
+            "pq": (10_000_000, "1,2,16", "100,50,10,1"), "ivf": (1_000_000, "1,8", "100,50,10,1"),
+            "ivfpq": (10_000_000, "1,8", "100,50,10,1")}  # rows, nq, visible-pct
+NLIST = {"ivf": 256, "ivfpq": 1024}
 
 
 def p50(fn, reps):
@@ -54,12 +60,8 @@ def clock_mhz():
         return None
 
 
-def ivf_main(a, nqs, pcts):
-    lib = _lib.require_gpu(0)
-    nprobes = [int(x) for x in a.nprobe.split(",")]
-    out = {"index": "ivf", "rows": a.rows, "dim": a.dim, "nlist": a.nlist, "k": a.k, "runs": a.runs, "reps": a.reps,
-           "shader_clock_mhz_before": clock_mhz()}
-    nqmax = max(nqs)
+def ivf_handle(a, lib, nqmax):
+    """-> (IVFFlat with a.rows rows, queries [nqmax, dim] on the device): rows, queries and centroids as tools/ivf_bench.py"""
     X = torch.empty((a.rows, a.dim), dtype=torch.float32, device="cuda")
     Q = torch.empty((nqmax, a.dim), dtype=torch.float32, device="cuda")
     _lib.check(lib.lb_gpu_fill_uniform_device(0, X.data_ptr(), a.rows * a.dim, 1, 0, None))
@@ -68,7 +70,45 @@ def ivf_main(a, nqs, pcts):
     h = ivf.IVFFlat(ivf.train_device(a.rows, X.data_ptr(), a.dim, a.nlist, max_iter=0))
     h.reserve(a.rows)
     h.add_device(a.rows, X.data_ptr())
-    del X
+    return h, Q
+
+
+def ivfpq_handle(a, lib, nqmax):
+    """-> (IVFPQ with a.rows rows, queries [nqmax, dim] on the device): rows, codebooks, centroids and queries as
+    tools/ivfpq_bench.py"""
+    n, dim, M, piece = a.rows, a.dim, a.m, 1_000_000
+    cb = torch.empty(M * 256 * (dim // M), dtype=torch.float32, device="cuda")
+    _lib.check(lib.lb_gpu_fill_uniform_device(0, cb.data_ptr(), cb.numel(), 7, 0, None))
+    rows = torch.arange(a.nlist, dtype=torch.int64, device="cuda") * (n // a.nlist)
+    cent = torch.empty((a.nlist, dim), dtype=torch.float32, device="cuda")
+    _lib.check(lib.lb_gpu_fill_uniform_rows_device(0, cent.data_ptr(), rows.data_ptr(), a.nlist, dim, 12345, None))
+    torch.cuda.synchronize()
+    h = ivfpq.IVFPQ(pq.serialize_codebooks(cb.cpu().numpy().reshape(M, 256, dim // M)), cent.cpu().numpy())
+    h.reserve(n)
+    buf = torch.empty((min(piece, n), dim), dtype=torch.float32, device="cuda")
+    for r0 in range(0, n, piece):
+        cnt = min(piece, n - r0)
+        _lib.check(lib.lb_gpu_fill_uniform_device(0, buf.data_ptr(), cnt * dim, 12345, r0 * dim, None))
+        torch.cuda.synchronize()
+        h.add_device(cnt, buf.data_ptr())
+    Q = torch.empty((nqmax, dim), dtype=torch.float32, device="cuda")
+    _lib.check(lib.lb_gpu_fill_uniform_device(0, Q.data_ptr(), nqmax * dim, 42, 0, None))
+    torch.cuda.synchronize()
+    return h, Q
+
+
+def ivf_main(a, nqs, pcts):
+    lib = _lib.require_gpu(0)
+    nprobes = [int(x) for x in a.nprobe.split(",")]
+    out = {"index": a.index, "rows": a.rows, "dim": a.dim, "nlist": a.nlist, "k": a.k, "runs": a.runs, "reps": a.reps,
+           "shader_clock_mhz_before": clock_mhz()}
+    nqmax = max(nqs)
+    if a.index == "ivfpq":
+        out["m"] = a.m
+        h, Q = ivfpq_handle(a, lib, nqmax)
+    else:
+        h, Q = ivf_handle(a, lib, nqmax)
+    slots = h._timing_slots
     rng = np.random.default_rng(0)
     masks = {p: np.ones(a.rows, np.uint8) if p == 100 else (rng.random(a.rows) < p / 100.0).astype(np.uint8) for p in pcts}
     D = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
@@ -108,14 +148,14 @@ def ivf_main(a, nqs, pcts):
 
     def summary(cs):
         return {"ms": med([c["ms"] for c in cs]), "runs_ms": [c["ms"] for c in cs],
-                "steps_ms": [med([c["steps_ms"][i] for c in cs]) for i in range(4)],
+                "steps_ms": [med([c["steps_ms"][i] for c in cs]) for i in range(slots)],
                 "rows_scanned": cs[-1]["rows_scanned"], "max_rows_per_query": cs[-1]["max_rows_per_query"],
                 "selected_from_lds": cs[-1]["selected_from_lds"]}
 
     out["filter"] = {}
     for p in pcts:
         r = runs[p]
-        build_bytes = a.rows * (4 + 1 + 4) + a.rows // 4 + r["visible_rows"] * 4
+        build_bytes = a.rows * (4 + 1 + (0 if a.index == "ivfpq" else 4)) + a.rows // 4 + r["visible_rows"] * 4
         out["filter"][f"visible_{p}"] = {
             "visible_rows": r["visible_rows"], "filter_call_ms": med(r["filter_call_ms"]), "filter_call_runs_ms": r["filter_call_ms"],
             "build_ms": med(r["build_ms"]), "build_runs_ms": r["build_ms"], "build_bytes": build_bytes,
@@ -129,8 +169,9 @@ def ivf_main(a, nqs, pcts):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--index", choices=("bq", "sq8", "pq", "ivf"), required=True)
-    ap.add_argument("--nlist", type=int, default=256)
+    ap.add_argument("--index", choices=("bq", "sq8", "pq", "ivf", "ivfpq"), required=True)
+    ap.add_argument("--nlist", type=int, default=None)
+    ap.add_argument("--m", type=int, default=96)
     ap.add_argument("--nprobe", default="8,32")
     ap.add_argument("--rows", type=int, default=None)
     ap.add_argument("--dim", type=int, default=768)
@@ -145,7 +186,8 @@ def main():
     a.visible_pct = a.visible_pct or DEFAULTS[a.index][2]
     nqs = [int(x) for x in a.nq.split(",")]
     pcts = [int(x) for x in a.visible_pct.split(",")]
-    if a.index == "ivf":
+    if a.index in NLIST:
+        a.nlist = a.nlist or NLIST[a.index]
         return ivf_main(a, nqs, pcts)
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
