@@ -688,8 +688,9 @@ int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms);
  *                     dropped; it never changes.
  *   probes of a query the labels of the k = min(nprobe, nlist) search of the query over that same index.
  *   distance          float32(sqrt(float64(sum_j table[j * 256 + code[j]]))), table = BuildADCTable(query), the f32 sum in j
- *                     order: what lb_gpu_pq_search reports.  These are NOT residual codes: a row is encoded as it is, not as
- *                     its difference from its centroid, and the query's one table serves every list.
+ *                     order: what lb_gpu_pq_search reports.  On a handle from lb_gpu_ivfpq_new these are NOT residual codes: a
+ *                     row is encoded as it is, not as its difference from its centroid, and the query's one table serves every
+ *                     list.  (Residual codes: lb_gpu_ivfpq_new_residual, below.)
  *   result            the first k rows r, in ascending (distance, r) order, every NaN after +inf, among the rows whose list is a
  *                     probe of q; the label is ids[r] when ids were given, else r; with fewer than k such rows they come first,
  *                     then label -1 / distance FLT_MAX.  nprobe >= nlist gives lb_gpu_pq_search over the same codes, bit for
@@ -725,11 +726,38 @@ int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms);
  * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
  * refused call writes nothing.  Searches and reads share the handle; adds, reserve and the filter calls take it alone.  ctx
  * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here:
- * residual codes, a filter given per search call, adding ready-made codes with caller-given lists, search combining,
- * lb_gpu_comm_*, removing rows, Save / Load, and the Go and C++ mirrors. */
+ * a filter given per search call, adding ready-made codes with caller-given lists, search combining, lb_gpu_comm_*, removing
+ * rows, Save / Load, and the Go and C++ mirrors.
+ *
+ * Residual codes.  lb_gpu_ivfpq_new_residual makes a RESIDUAL handle: its arguments, limits, order of checks and status codes
+ * are exactly lb_gpu_ivfpq_new's, lb_gpu_ivfpq_residual answers 1 for it (0 for a plain handle, 0 for no handle), and every
+ * lb_gpu_ivfpq_* call, the lists, probes, ids, padding, stats, filters and LB_MAX_K are as above.  Three definitions differ:
+ *   res(v, l)         res(v, l)[i] = v[i] - C[l][i]: one IEEE f32 subtraction a component, stored rounded to f32, contracted with
+ *                     nothing after it.
+ *   code of a row     lb_gpu_pq_encode(res(x, list(x))), list(x) being the same k = 1 coarse search; the vector is dropped after
+ *                     the add, as on a plain handle.  The codebooks are meant to be trained on such residuals.
+ *   distance          of query q to a row r of probed list l: float32(sqrt(float64(sum_j table_l[j * 256 + code_r[j]]))) with
+ *                     table_l = BuildADCTable(res(q, l)): lb_gpu_pq_search's arithmetic over a table per probed list.  The result
+ *                     is the first k rows in ascending (distance, r) order among the rows, under a filter the visible rows, of
+ *                     the probed lists.  Given the codes and the probed lists nothing is approximate.
+ * Consequences: get_codes returns residual codes; "nprobe >= nlist gives lb_gpu_pq_search over the same codes" does NOT hold for
+ * a residual handle; it does hold, bit for bit, that a residual handle whose rows all fall in a list with an all-zero centroid
+ * equals the plain handle over the same input (x - 0 = x).
+ *   memory            a residual handle keeps the centroids once more, as a device f32 [nlist][dims] array of its own (the coarse
+ *                     index keeps its rows to itself); hbm_bytes counts it.
+ *   scratch           a search holds one table (M * 1024 bytes) per pair (query, probed list) of a batch.  The tables of a batch
+ *                     are bounded by 1 GiB: a batch is at most nb queries with nb * np * M * 1024 <= 2^30 (np = min(nprobe,
+ *                     nlist); at M = 96 room for 10,922 tables).  Only when ONE query's np tables exceed 1 GiB (at M = 159 from
+ *                     6,595 probes) its probed lists are scanned in rounds of as many as fit, all into the query's one run of
+ *                     keys, and the selection runs once.  Neither changes a result.
+ *   last_timing       ms[2] is the residual queries and their tables, ms[3] the scan; when a query's tables go in several
+ *                     rounds, the rounds after the first are whole in ms[3]. */
 typedef struct lb_gpu_ivfpq lb_gpu_ivfpq;
 lb_gpu_ivfpq *lb_gpu_ivfpq_new(int device, const uint8_t *codebook_blob, size_t len, int order, int nlist, const float *centroids,
                                int *out_status);
+lb_gpu_ivfpq *lb_gpu_ivfpq_new_residual(int device, const uint8_t *codebook_blob, size_t len, int order, int nlist,
+                                        const float *centroids, int *out_status);
+int lb_gpu_ivfpq_residual(const lb_gpu_ivfpq *p); /* 1: residual codes; 0: plain, or no handle */
 void lb_gpu_ivfpq_free(lb_gpu_ivfpq *p);
 const char *lb_gpu_ivfpq_last_error(const lb_gpu_ivfpq *p);
 int lb_gpu_ivfpq_dims(const lb_gpu_ivfpq *p);
@@ -737,8 +765,8 @@ int lb_gpu_ivfpq_m(const lb_gpu_ivfpq *p);
 int lb_gpu_ivfpq_order(const lb_gpu_ivfpq *p);
 int lb_gpu_ivfpq_nlist(const lb_gpu_ivfpq *p);
 int64_t lb_gpu_ivfpq_ntotal(const lb_gpu_ivfpq *p);
-int64_t lb_gpu_ivfpq_hbm_bytes(const lb_gpu_ivfpq *p); /* codes (three times), ids, lists, codebooks, the coarse index and what a
-                                                          row filter holds */
+int64_t lb_gpu_ivfpq_hbm_bytes(const lb_gpu_ivfpq *p); /* codes (three times), ids, lists, codebooks, the coarse index, what a
+                                                          row filter holds and a residual handle's copy of the centroids */
 int lb_gpu_ivfpq_get_centroids(lb_gpu_ivfpq *p, float *out); /* f32[nlist*dims] */
 int lb_gpu_ivfpq_reserve(lb_gpu_ivfpq *p, int64_t n_total);
 int lb_gpu_ivfpq_add(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *ids); /* assign, encode, append */

@@ -216,6 +216,8 @@ SIGNATURES = [
     ("lb_gpu_ivf_last_timing", _i, [_vp, _vp]),
     ("lb_gpu_ivf_last_build_timing", _i, [_vp, _vp]),
     ("lb_gpu_ivfpq_new", _vp, [_i, _vp, _sz, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivfpq_new_residual", _vp, [_i, _vp, _sz, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivfpq_residual", _i, [_vp]),
     ("lb_gpu_ivfpq_free", None, [_vp]),
     ("lb_gpu_ivfpq_last_error", C.c_char_p, [_vp]),
     ("lb_gpu_ivfpq_dims", _i, [_vp]),

@@ -1,7 +1,8 @@
 // ivfpq.hip -- host side of the lb_gpu_ivfpq_* entry points of include/longbow_gpu.h: the IVF-PQ index, the coarse partition of
 // the IVF-Flat handle (ivf.hip) over the codes of the PQ handle (pq.hip).  The new kernels are in kernels_ivfpq.hip; the coarse
 // quantiser is an inner exact f32 index over the centroids, the lists are kernels_ivf.hip's, the codec and the table
-// kernels_pq.hip's and kernels_pq2.hip's.
+// kernels_pq.hip's and kernels_pq2.hip's.  A handle is plain or residual (lb_gpu_ivfpq_new_residual): a residual handle encodes a
+// row less its list's centroid and searches under a table per probed list (ivfpq_rsearch_dev); everything else is shared.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
 #include "lb_ivf_host.h"
@@ -15,7 +16,9 @@ struct lb_gpu_ivfpq : IvfHandle { // the partition (L2), and under a row filter 
     DevBuf<uint8_t> d_codes;        // [capacity][M], insertion order: what get_codes returns
     // the list-major codes are built for all rows by every add, with the lists, into the pair that is not in use
     DevBuf<uint8_t> d_lcodes[2];    // [capacity][M]: lcodes[pos] = codes[list[pos]]
-    float timing[5] = {0, 0, 0, 0, 0}; // of the last profiled search (under err_mu): probes, plan, tables, scan, select; ms summed over its batches
+    bool residual = false;          // the codes are of res(row, list(row)) and a search builds a table per probed list; fixed at creation
+    DevBuf<float> d_cent;           // [nlist][dims], a residual handle's own copy of the centroids (the coarse index keeps its rows to itself)
+    float timing[5] = {0, 0, 0, 0, 0}; // of the last profiled search (under err_mu): probes, plan, tables, scan, select; ms summed over its batches (residual: ivfpq_rsearch_dev)
 };
 
 namespace {
@@ -61,7 +64,7 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
     IvfPartition &P = p->part;
     if (const int st = ivf_ids_consistent(p, P, ids)) return st;
     if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease vec, lab, hist, vis;
+    Lease vec, lab, hist, vis, res;
     return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = p->stream;
@@ -75,6 +78,7 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
         const int64_t piece = std::min(n, piece_rows(p->dims));
         lab.reset(p->device, ivf_assign_bytes(piece));
         if (!on_device) vec.reset(p->device, (size_t)piece * p->dims * 4);
+        if (p->residual) res.reset(p->device, (size_t)piece * p->dims * 4);
         for (int64_t r0 = 0; r0 < n; r0 += piece) {
             const int64_t cnt = std::min(piece, n - r0);
             const float *d_new = vectors + (size_t)r0 * p->dims;
@@ -83,6 +87,10 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
                 d_new = vec.as<float>();
             }
             if (const int rc = ivf_assign(p, P, p->n + r0, cnt, d_new, lab, s)) return rc;
+            if (p->residual) { // the piece's rows less their lists' centroids are what is encoded
+                launch_ivfpq_residual_rows(d_new, P.d_assign.get() + p->n + r0, p->d_cent.get(), cnt, p->dims, P.nlist, res.as<float>(), s);
+                d_new = res.as<float>();
+            }
             launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_new, cnt, p->d_codes.get() + (size_t)(p->n + r0) * p->M, s);
             LB_LAUNCH_CHECK();
             LB_HIP(hipStreamSynchronize(s)); // (the staging buffer and the labels are reused by the next piece)
@@ -105,6 +113,53 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
     });
 }
 
+// The residual handle's call of the search loop.  A query has a table per probed list, so the middle steps run over the pairs
+// (query, slot) of the batch: the residual queries and their tables, in one timing slot, then the scan.  The batch is shrunk so
+// that its nb * np tables fit kTableScratch (ivfpq_table_plan); only when one query's np tables do not, the middle steps go in
+// rounds of slots, each residual queries -> tables -> scan of those slots, all into the one keys[q][.], and the selection runs
+// once.  Timing: slot 3 is the first round's residual queries and tables, slot 4 its scan and every further round whole.
+constexpr int64_t kTableLaunch = 65535; // pairs a launch_build_adc_table call takes: its queries are on grid.y
+
+int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfBatch &a, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels,
+                      hipStream_t s, const lb_cancel *ctx, Lease &sc)
+{
+    const IvfPartition &P = p->part;
+    const uint8_t *lcodes = p->d_lcodes[P.cur].get();
+    const int np = std::min(nprobe, P.nlist);
+    const IvfpqTablePlan tp = ivfpq_table_plan(np, p->M, kTableScratch);
+    float *d_rq = nullptr, *d_tables = nullptr;
+    uint32_t *d_items = nullptr; // the scan's work list, where it runs from one (ivfpq_rscan_plan)
+    return ivf_search(
+        p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
+        [&](Carve &c, IvfBatch &, int64_t nb) {
+            const size_t pairs = (size_t)nb * (size_t)tp.slots; // of a round
+            d_rq = c.take<float>(pairs * p->dims * 4);
+            d_tables = c.take<float>(pairs * p->M * 256 * 4);
+            d_items = c.take<uint32_t>((pairs + 1) * 4);
+        },
+        [&](const IvfBatch &b, int64_t maxlen, auto &&poll, auto &&next) {
+            if (!next()) return false; // (the plan's slot ends here)
+            for (int s0 = 0; s0 < np; s0 += (int)tp.slots) {
+                const int ns = (int)std::min<int64_t>(tp.slots, np - s0);
+                const int64_t pairs = (int64_t)b.nq * ns;
+                if (s0 > 0 && !poll()) return false;
+                launch_ivfpq_residual_queries(b, s0, ns, p->d_cent.get(), d_rq, s);
+                for (int64_t p0 = 0; p0 < pairs; p0 += kTableLaunch) {
+                    if (!poll()) return false;
+                    launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, d_rq + (size_t)p0 * p->dims,
+                                           (int)std::min(kTableLaunch, pairs - p0), d_tables + (size_t)p0 * p->M * 256, s);
+                }
+                if (s0 == 0 ? !next() : !poll()) return false;
+                if (p->filter.on)
+                    launch_ivfpq_rscan_visible(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, P.d_list[P.cur].get(),
+                                               p->filter.n_visible, s);
+                else launch_ivfpq_rscan(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, s);
+            }
+            return true;
+        },
+        tp.nb);
+}
+
 // The handle's call of the search loop (lb_ivf_host.h): exact ADC k-NN; under a filter it walks the visible lists.  Its middle steps
 // are the queries' tables, a timing slot of their own, and the scan of the list-major codes.
 int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
@@ -116,6 +171,7 @@ int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int n
     a.D = p->dims;
     const uint8_t *lcodes = p->d_lcodes[P.cur].get();
     float *d_tables = nullptr;
+    if (p->residual) return ivfpq_rsearch_dev(p, a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc);
     return ivf_search(
         p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
         [&](Carve &c, IvfBatch &, int64_t nb) { d_tables = c.take<float>((size_t)nb * p->M * 256 * 4); },
@@ -129,11 +185,8 @@ int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int n
         });
 }
 
-} // namespace
-
-extern "C" {
-
-lb_gpu_ivfpq *lb_gpu_ivfpq_new(int device, const uint8_t *blob, size_t len, int order, int nlist, const float *centroids, int *out_status)
+// both constructors: the same arguments, limits, order of checks and status codes
+lb_gpu_ivfpq *ivfpq_new(int device, const uint8_t *blob, size_t len, int order, int nlist, const float *centroids, int *out_status, bool residual)
 {
     auto st = [&](int v) { if (out_status) *out_status = v; };
     // the blob, as lb_gpu_pq_new reads it (DeserializePQEncoder, internal/pq/persistence.go:38-73)
@@ -151,8 +204,28 @@ lb_gpu_ivfpq *lb_gpu_ivfpq_new(int device, const uint8_t *blob, size_t len, int 
         p->positions = true; // a visible list addresses the list-major codes
         p->d_codebooks.alloc((len - 12) / sizeof(float));
         LB_HIP(hipMemcpy(p->d_codebooks.get(), blob + 12, len - 12, hipMemcpyHostToDevice)); // (f32 little-endian on the wire, as pq.hip)
+        p->residual = residual;
+        if (residual) {
+            p->d_cent.alloc((size_t)nlist * dims);
+            LB_HIP(hipMemcpy(p->d_cent.get(), centroids, (size_t)nlist * dims * 4, hipMemcpyHostToDevice));
+        }
     });
 }
+
+} // namespace
+
+extern "C" {
+
+lb_gpu_ivfpq *lb_gpu_ivfpq_new(int device, const uint8_t *blob, size_t len, int order, int nlist, const float *centroids, int *out_status)
+{
+    return ivfpq_new(device, blob, len, order, nlist, centroids, out_status, false);
+}
+lb_gpu_ivfpq *lb_gpu_ivfpq_new_residual(int device, const uint8_t *blob, size_t len, int order, int nlist, const float *centroids,
+                                        int *out_status)
+{
+    return ivfpq_new(device, blob, len, order, nlist, centroids, out_status, true);
+}
+int lb_gpu_ivfpq_residual(const lb_gpu_ivfpq *p) { return p && p->residual ? 1 : 0; }
 
 void lb_gpu_ivfpq_free(lb_gpu_ivfpq *p) { handle_free(p); }
 const char *lb_gpu_ivfpq_last_error(const lb_gpu_ivfpq *p) { return handle_last_error(p); }
@@ -166,7 +239,7 @@ int64_t lb_gpu_ivfpq_hbm_bytes(const lb_gpu_ivfpq *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivfpq *>(p)->mu);
-    return (int64_t)(p->d_codes.count() + p->d_lcodes[0].count() + p->d_lcodes[1].count() + p->d_codebooks.count() * 4) + p->visible_bytes() +
+    return (int64_t)(p->d_codes.count() + p->d_lcodes[0].count() + p->d_lcodes[1].count() + (p->d_codebooks.count() + p->d_cent.count()) * 4) + p->visible_bytes() +
            p->part.hbm_bytes();
 }
 

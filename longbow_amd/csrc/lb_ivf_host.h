@@ -33,6 +33,9 @@ namespace lb {
 
 constexpr int64_t kQueryBatch = 1024;              // queries per batch at most
 constexpr int64_t kKeyScratch = (int64_t)1 << 30;  // bytes of keys a batch may hold
+// bytes of ADC tables a batch of a residual IVF-PQ search may hold (a table per probed list of each query): one pooled lease,
+// at M = 96 room for 10,922 tables
+constexpr int64_t kTableScratch = (int64_t)1 << 30;
 constexpr int kMaxTimingSlots = 5;
 
 struct IvfPartition {
@@ -301,11 +304,12 @@ inline void ivf_commit_visible(IvfHandle *p, std::vector<int64_t> &vsizes, int64
 //   middle(a, maxlen, poll, next) enqueues what fills a.keys; poll() is false once ctx fired, next() ends a timing slot and then
 //                                 polls; after either's false it enqueues nothing more and returns false.  maxlen: the longest list
 // timing[slots] (under err_mu) gets the ms of a profiled search summed over its batches: probes, plan (up to middle's first next()),
-// a slot per further next(), selection.  Profiling costs a drain per batch.
+// a slot per further next(), selection.  Profiling costs a drain per batch.  batch_cap: queries per batch at most, for a handle
+// whose own scratch grows with the batch (the residual IVF-PQ handle's tables); the others leave it at kQueryBatch.
 template <class Extra, class Middle>
 int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vector<int64_t> &sizes, IvfBatch a, int64_t nq, const float *d_Q,
                int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s, const lb_cancel *ctx, Lease &sc, float *timing, int slots,
-               Extra &&extra, Middle &&middle)
+               Extra &&extra, Middle &&middle, int64_t batch_cap = kQueryBatch)
 {
     int64_t st[4] = {nq, 0, 0, 0};
     auto publish = [&]() {
@@ -327,7 +331,7 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
     for (int i = 0; i < np; i++) pmax += big[i];
     const int64_t maxlen = big[0];
     pmax = std::max<int64_t>(pmax, 1);
-    const int64_t nb = std::min(std::min(nq, kQueryBatch), std::max<int64_t>(1, kKeyScratch / 8 / pmax));
+    const int64_t nb = std::min(std::min(nq, std::max<int64_t>(1, std::min(batch_cap, kQueryBatch))), std::max<int64_t>(1, kKeyScratch / 8 / pmax));
     a.L = L;
     a.np = np;
     a.pmax = pmax;

@@ -2,40 +2,59 @@
 
 A query skips most rows and a row costs M bytes.  Given the codes and the probed lists nothing is approximate: the result is the
 exact ADC k-NN among the rows of the probed lists, bit for bit in the reference's BuildADCTable / ADCDistanceBatch arithmetic, and
-with every list probed it equals pq.PQEncoder.Search over the same codes.  The codes are plain, not residual: a query's one table
-serves every list.  include/longbow_gpu.h states the semantics.
+with every list probed a plain handle equals pq.PQEncoder.Search over the same codes.
+
+A handle holds one of two kinds of codes, fixed at creation.  Plain (the default): a row is encoded as it is and a query's one
+table serves every list.  Residual (residual=True): a row is encoded as its f32 difference from its list's centroid, so the
+codebooks spend their words on the spread inside a list; a query then has a table per probed list, built from q - C[l], and the
+result is as exact over those tables.  include/longbow_gpu.h states the semantics of both.
 
   IVFPQ   the handle: codebooks and centroids given at creation, add / search / codes / list_sizes / assignments / last_search_stats,
           and the row filter (set_filter / filter_column / nvisible)
-  train   (centroids, codebook blob) from ivf.train and pq.train
+  train   (centroids, codebook blob) from ivf.train and pq.train; with residual=True the codebooks are trained on the residuals
 """
 import ctypes as C
 
 import numpy as np
 
-from . import _lib, ivf, pq
+from . import _lib, gpu, ivf, pq
 from ._ivfbase import IVFBase
 from ._rowfilter import RowFilterMixin
 
 FLT_MAX = ivf.FLT_MAX
 
 
-def train(vectors, nlist, M, max_iter=20, seed=0, device=0):
+def train(vectors, nlist, M, max_iter=20, seed=0, device=0, residual=False):
     """-> (centroids f32 [nlist, dims], codebook blob): ivf.train for the coarse quantiser, pq.train (K = 256) for the codebooks,
-    both over the same rows"""
+    both over the same rows.  With residual=True the codebooks are pq.train of vectors - centroids[a] (numpy f32 on the host,
+    one subtraction a component, as the handle's), a being the k = 1 L2 labels of the rows over a gpu.Index of the centroids in
+    order 0 (SEQ).  A handle created with order = 1 may put a row that lies on a boundary between two lists into the other one:
+    that row's code is then of a residual the codebooks were not trained on, which bears on quality only, never on exactness."""
     centroids = ivf.train(vectors, nlist, max_iter, seed, device=device)
-    blob, _ = pq.train(vectors, M, 256, max_iter, seed, device=device)
+    v = np.ascontiguousarray(vectors, np.float32)
+    if residual:
+        coarse = gpu.Index(gpu.GPUConfig(DeviceID=device, Dimension=v.shape[1]))
+        try:
+            coarse.set_order(0)
+            coarse.Add(None, centroids)
+            a = np.concatenate([coarse.SearchBatch(v[r0:r0 + 65536], 1)[0][:, 0] for r0 in range(0, v.shape[0], 65536)])
+        finally:
+            coarse.Close()
+        v = v - centroids[a]
+    blob, _ = pq.train(v, M, 256, max_iter, seed, device=device)
     return centroids, blob
 
 
 class IVFPQ(RowFilterMixin, IVFBase):
     """lb_gpu_ivfpq: codebooks (the reference's serialised blob, or a pq.PQEncoder whose blob is taken), centroids f32
     [nlist, dims], order 0 SEQ / 1 UNROLL4 of the coarse quantiser (L2).  Under a row filter (RowFilterMixin) the probes stay as
-    they are and a search sees the visible rows of the probed lists alone."""
+    they are and a search sees the visible rows of the probed lists alone.  residual=True makes a residual handle
+    (lb_gpu_ivfpq_new_residual): codes() are then the codes of the rows' residuals, and the codebooks should come from
+    train(..., residual=True)."""
     _prefix = "lb_gpu_ivfpq"
     _timing_slots = 5
 
-    def __init__(self, codebooks, centroids, order=0, device=0, lib=None):
+    def __init__(self, codebooks, centroids, order=0, device=0, lib=None, residual=False):
         self._h = None  # (Close() and __del__ find this when creation fails below)
         buf = bytes(codebooks.blob if isinstance(codebooks, pq.PQEncoder) else codebooks)
         c = np.ascontiguousarray(centroids, np.float32)
@@ -45,7 +64,8 @@ class IVFPQ(RowFilterMixin, IVFBase):
             raise ValueError(f"centroids of {c.shape[1]} dimensions, codebooks of {int.from_bytes(buf[:4], 'little')}")
         lib = lib or _lib.require_gpu(device)
         st = C.c_int(0)
-        h = lib.lb_gpu_ivfpq_new(device, buf, len(buf), order, c.shape[0], c.ctypes.data, C.byref(st))
+        new = lib.lb_gpu_ivfpq_new_residual if residual else lib.lb_gpu_ivfpq_new
+        h = new(device, buf, len(buf), order, c.shape[0], c.ctypes.data, C.byref(st))
         if not h:
             if st.value == 1:
                 raise ValueError("invalid PQ data")  # persistence.go:39-56 error cases, as pq.PQEncoder
@@ -56,10 +76,11 @@ class IVFPQ(RowFilterMixin, IVFBase):
         self.nlist, self.dims = c.shape
         self.m = lib.lb_gpu_ivfpq_m(self._h)
         self.order = order
+        self.residual = bool(lib.lb_gpu_ivfpq_residual(self._h))
 
     def add(self, vectors, ids=None):
-        """assign, encode and append rows [n, dims]; ids (int64 [n]) on every add or on none.  Each add rebuilds the lists and
-        the list-major codes of all rows: O(ntotal)."""
+        """assign, encode (on a residual handle: the row less its list's centroid) and append rows [n, dims]; ids (int64 [n]) on
+        every add or on none.  Each add rebuilds the lists and the list-major codes of all rows: O(ntotal)."""
         super().add(vectors, ids)
 
     def codes(self, row0=0, n=None):
@@ -74,7 +95,9 @@ class IVFPQ(RowFilterMixin, IVFBase):
         return super().search(queries, k, nprobe, ctx)
 
     def last_timing(self):
-        """ms of the last profiled search, summed over its batches: (probes, plan, ADC tables, scan, selection)"""
+        """ms of the last profiled search, summed over its batches: (probes, plan, ADC tables, scan, selection).  On a residual
+        handle the third is the residual queries and their tables; when one query's tables go in several rounds of slots, the
+        rounds after the first are whole in the fourth."""
         return super().last_timing()
 
     def last_build_timing(self):
