@@ -269,6 +269,38 @@ int lb_gpu_index_rerank(lb_gpu_index *h, const float *query, const int64_t *rows
 int lb_gpu_index_rerank_device(lb_gpu_index *h, const float *d_query, const int64_t *d_rows, int64_t n, int order,
                                float *d_dist, float *d_score, void *stream);
 
+/* Batched exact refine of shortlists: nq queries x c candidate rows each -> the exact top k of every shortlist, on the device,
+ * over the rows of a float32 or a float16 index.  The second stage behind a code index (BQ, SQ8, PQ, IVF-Flat, IVF-PQ), whose
+ * k-NN under the codes is a shortlist and not the answer; the reference's hybrid hand-off searches k * 10 and keeps k
+ * (hnsw_gpu.go:84-123).
+ *   queries   f32[nq][dim], on a float16 index too: the arithmetic is the f32 arithmetic on the widened rows, so the result is
+ *             that of a float32 index holding the same values.
+ *   rows      int64[nq][c] row POSITIONS, as for rerank.  The candidate set S_q of query q is the set of values of rows[q][.]
+ *             inside [0, ntotal): anything else (the -1 padding of a short shortlist) is skipped, a value that occurs more than
+ *             once counts once, and the order of the entries does not matter.  The index's row filter is ignored, as rerank
+ *             ignores it (a filter on the code handle has already shaped the shortlist).
+ *   result    dist / labels [nq][k]: the first k members of S_q in ascending (distance, row) order, the distance being the
+ *             index metric's in `order` (-1: the index's own) -- L2 with the square root, cosine 1 - cos, dot negated: bit for
+ *             bit what lb_gpu_index_search reports for those rows.  labels are ids[row] when the index holds ids, else the row;
+ *             FLT_MAX / -1 beyond |S_q|.
+ *   limits    1 <= k <= LB_MAX_K, 1 <= c <= LB_REFINE_MAX_C (k > c is allowed and gives padding); nq is unlimited (the host
+ *             walks it in batches under a scratch bound) and nq == 0 is LB_OK.
+ *   errors    null pointers, nq < 0, a bad order, c out of range or k <= 0: LB_ERR_INVALID_ARG; k > LB_MAX_K:
+ *             LB_ERR_UNSUPPORTED; an int8 index: LB_ERR_UNSUPPORTED with a last_error text.  An empty index gives all padding.
+ * Thread-safe against each other and against searches (shared lock), exclusive against add, reserve and the filter calls.
+ * The _device form enqueues on `stream`, or on a private stream when it is null; ctx (nullable) is polled before every launch
+ * (LB_ERR_CANCELLED / LB_ERR_DEADLINE, the outputs then hold unspecified values).  Results are complete on return. */
+#define LB_REFINE_MAX_C 16384
+int lb_gpu_index_refine(lb_gpu_index *h, int64_t nq, const float *queries, int64_t c, const int64_t *rows, int k, int order,
+                        float *dist, int64_t *labels);
+int lb_gpu_index_refine_ctx(lb_gpu_index *h, int64_t nq, const float *queries, int64_t c, const int64_t *rows, int k, int order,
+                            float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_index_refine_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int64_t c, const int64_t *d_rows, int k,
+                                   int order, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* ms of the last refine that ran while lb_gpu_index_set_profiling was on, summed over its batches: the preparation of the lists,
+ * the scan (with a cosine index's query norms), the selection.  Profiling costs a drain per batch.  Telemetry only. */
+int lb_gpu_index_refine_last_timing(lb_gpu_index *h, float ms[3]);
+
 /* ---- internal/simd batch interface on the GPU --------------------------------
  * simd.EuclideanDistanceBatchFlat / CosineDistanceBatch / DotProductBatch
  * (internal/simd/batch_operations.go:64-87,131-157): one query x n rows of

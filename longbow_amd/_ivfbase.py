@@ -11,6 +11,7 @@ class IVFBase:
     self._lib, self._h, self.nlist and self.dims (self._h = None first: Close() and __del__ find that when creation fails)."""
     _prefix = None  # "lb_gpu_ivf" / "lb_gpu_ivfpq"
     _timing_slots = 0
+    _has_ids = False  # an add gave ids: the searches then return those and not row positions (search_refine needs positions)
 
     def _fn(self, name):
         return getattr(self._lib, self._prefix + "_" + name)
@@ -50,9 +51,11 @@ class IVFBase:
             if i.size != v.shape[0]:
                 raise ValueError(f"{i.size} ids for {v.shape[0]} rows")
         self._check(self._fn("add")(self._h, v.shape[0], v.ctypes.data, i.ctypes.data if i is not None else None))
+        self._has_ids = self._has_ids or i is not None
 
     def add_device(self, n, d_vectors, d_ids=None):
         self._check(self._fn("add_device")(self._h, n, d_vectors, d_ids))
+        self._has_ids = self._has_ids or d_ids is not None
 
     def list_sizes(self):
         out = np.empty(self.nlist, np.int64)

@@ -97,6 +97,10 @@ SIGNATURES = [
     ("lb_gpu_index_last_route", _i, [_vp]),
     ("lb_gpu_index_rerank", _i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
     ("lb_gpu_index_rerank_device", _i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
+    ("lb_gpu_index_refine", _i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _vp]),
+    ("lb_gpu_index_refine_ctx", _i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    ("lb_gpu_index_refine_device_ctx", _i, [_vp, _i64, _vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_index_refine_last_timing", _i, [_vp, C.POINTER(C.c_float)]),
     ("lb_simd_match_int64", _i, [_i, _vp, _i64, _i64, _i, _vp]),
     ("lb_simd_match_float32", _i, [_i, _vp, _i64, C.c_float, _i, _vp]),
     ("lb_simd_and_bytes", _i, [_i, _vp, _vp, _i64]),

@@ -239,6 +239,7 @@ struct lb_gpu_index : HandleCore {
     std::mutex prof_mu;
     float prof_ms[5] = {0, 0, 0, 0, 0};
     int prof_n[5] = {0, 0, 0, 0, 0};
+    float refine_ms[3] = {0, 0, 0}; // the last profiled refine, summed over its batches: prepare, scan (with the query norms), selection
 
     size_t elem_bytes() const { return i8_rows ? 1 : f16_rows ? 2 : sizeof(float); }
     int dtype() const { return i8_rows ? 2 : f16_rows ? 1 : 0; } // simd.DataType

@@ -185,6 +185,42 @@ class Index:
         _lib.check(self._lib.lb_gpu_index_rerank_device(self._h, d_query, d_rows, n, -1 if order is None else int(Order(order)),
                                                         d_dist, d_score, stream), self._h, lib=self._lib)
 
+    def Refine(self, queries, rows, k, order=None, ctx=None):
+        """The exact top k of every query's shortlist, in one call (lb_gpu_index_refine): queries f32 [nq, dim] (on a float16
+        index too), rows int64 [nq, c] row positions in any order, entries outside [0, ntotal) skipped (the -1 padding of a
+        short shortlist) and repeats counted once -> (labels [nq, k], dist [nq, k]) in ascending (distance, row) order, the
+        distances bit for bit what SearchBatch reports for those rows; -1 / FLT_MAX beyond the shortlist.  order=None: the
+        index's own."""
+        self._live()
+        queries = np.ascontiguousarray(queries, np.float32)
+        if queries.ndim != 2 or queries.shape[1] != self.dim:
+            raise ValueError(f"query vector dimension {queries.shape[-1]} does not match index dimension {self.dim}")
+        rows = np.ascontiguousarray(rows, np.int64)
+        if rows.ndim != 2 or rows.shape[0] != queries.shape[0]:
+            raise ValueError(f"rows {rows.shape} is not one shortlist per query ({queries.shape[0]} queries)")
+        nq = queries.shape[0]
+        dist = np.empty((nq, k), np.float32)
+        labels = np.empty((nq, k), np.int64)
+        _lib.check(self._lib.lb_gpu_index_refine_ctx(self._h, nq, queries.ctypes.data, rows.shape[1], rows.ctypes.data, k,
+                                                     -1 if order is None else int(Order(order)), dist.ctypes.data, labels.ctypes.data,
+                                                     ctx._h if ctx is not None else None), self._h, lib=self._lib)
+        return labels, dist
+
+    def refine_device(self, nq, d_queries, c, d_rows, k, d_dist, d_labels, order=None, stream=None, ctx=None):
+        """Refine on device pointers (d_queries f32 [nq, dim], d_rows int64 [nq, c] -> d_dist f32 / d_labels int64 [nq, k]),
+        enqueued on `stream` (None: a private one); complete on return"""
+        self._live()
+        _lib.check(self._lib.lb_gpu_index_refine_device_ctx(self._h, nq, d_queries, c, d_rows, k,
+                                                            -1 if order is None else int(Order(order)), d_dist, d_labels, stream,
+                                                            ctx._h if ctx is not None else None), self._h, lib=self._lib)
+
+    def refine_last_timing(self):
+        """ms of the last refine run under set_profiling(True), summed over its batches: (prepare, scan, selection)"""
+        self._live()
+        ms = (C.c_float * 3)()
+        _lib.check(self._lib.lb_gpu_index_refine_last_timing(self._h, ms), self._h, lib=self._lib)
+        return float(ms[0]), float(ms[1]), float(ms[2])
+
     def add_device(self, n, d_vectors, d_ids=None):
         """d_vectors: f32 rows, fp16 rows on a float16 index, int8 rows on an int8 index"""
         self._live()

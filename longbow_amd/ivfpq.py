@@ -94,6 +94,18 @@ class IVFPQ(RowFilterMixin, IVFBase):
         """-> (labels [nq, k], dist [nq, k]): ascending (ADC distance, row) among the rows of the probed lists, padded -1 / FLT_MAX"""
         return super().search(queries, k, nprobe, ctx)
 
+    def search_refine(self, index, queries, k, shortlist, nprobe, order=None):
+        """The two-stage use the codes exist for, on the device: the ADC k-NN of `shortlist` rows per query among the probed
+        lists, then the exact top k of every shortlist on `index` in one call (gpu.Index.Refine; a float32 or float16
+        gpu.Index filled in the same row order).  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX.  The shortlist
+        must hold row positions: a handle that was given ids raises ValueError.  A row filter on this handle shapes the
+        shortlist, so the result holds visible rows only; `index` needs no filter."""
+        if self._has_ids:
+            raise ValueError("search_refine needs row positions: this handle was given ids, which its searches return instead")
+        v = self._vectors(queries)
+        short, _ = self.search(v, shortlist, nprobe)
+        return index.Refine(v, short, k, order)
+
     def last_timing(self):
         """ms of the last profiled search, summed over its batches: (probes, plan, ADC tables, scan, selection).  On a residual
         handle the third is the residual queries and their tables; when one query's tables go in several rounds of slots, the

@@ -216,6 +216,14 @@ class PQEncoder(RowFilterMixin):
         self._check(self._lib.lb_gpu_pq_search_device_ctx(self._h, nq, d_queries, k, d_dist, d_labels, stream,
                                                           ctx._h if ctx is not None else None))
 
+    def search_refine(self, index, queries, k, shortlist, order=None):
+        """The two-stage use the codes exist for, on the device: the ADC k-NN of `shortlist` rows per query, then the exact top
+        k of every shortlist on `index` in one call (gpu.Index.Refine; a float32 or float16 gpu.Index filled in the same row
+        order).  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX.  A row filter on this handle shapes the
+        shortlist, so the result holds visible rows only; `index` needs no filter."""
+        short, _ = self.Search(queries, shortlist)
+        return index.Refine(np.ascontiguousarray(queries, np.float32).reshape(short.shape[0], -1), short, k, order)
+
     def set_profiling(self, on):
         self._check(self._lib.lb_gpu_pq_set_profiling(self._h, 1 if on else 0))
 

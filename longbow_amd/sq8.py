@@ -219,6 +219,15 @@ class SQ8Encoder(RowFilterMixin):
     def search_rerank(self, index, queries, k, oversample):
         return search_rerank(self, index, queries, k, oversample)
 
+    def search_refine(self, index, queries, k, shortlist, order=None):
+        """search_rerank's two stages with the second on the device: a shortlist of `shortlist` rows per query by the integer
+        distance, then the exact top k of every shortlist on `index` in one call (gpu.Index.Refine; a float32 or float16
+        gpu.Index filled in the same row order).  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX.  A row filter
+        on this handle shapes the shortlist, so the result holds visible rows only; `index` needs no filter."""
+        v, _ = self._vectors(queries)
+        short, _ = self.search(v, shortlist)
+        return index.Refine(v, short, k, order)
+
     def Close(self):
         if self._h:
             self._lib.lb_gpu_sq8_free(self._h)

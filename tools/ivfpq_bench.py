@@ -21,6 +21,11 @@ tables, scan, selection), rows scanned and the pairs (nq * nprobe) its scan ran 
 centre per list, queries drawn the same way; centroids and codebooks come from ivfpq.train over a sample of --train-rows rows
 (the residual handle's codebooks from ivfpq.train(..., residual=True)), so --nlist is at most ivf.train's 256.  The rows are also
 kept in an exact f32 gpu.Index, and every cell gains recall@k against its search of all rows ("recall_at_k_vs_exact_f32").
+
+--refine C (with --clustered) adds the second stage to every cell, for the plain handle and, with --residual, the residual one:
+the handle's search for C rows into device buffers, then lb_gpu_index_refine on the exact index's rows for k of them, on the same
+stream.  The cell gains "refine": the p50 of the search for C, of the refine alone and of the two chained, and recall@k of the
+refined result against the exact f32 search.
 """
 import argparse
 import json
@@ -71,7 +76,10 @@ def main():
     ap.add_argument("--clustered", action="store_true", help="rows around one centre per list; trained centroids and codebooks")
     ap.add_argument("--spread", type=float, default=3.0)
     ap.add_argument("--train-rows", type=int, default=65536)
+    ap.add_argument("--refine", type=int, default=0, metavar="C", help="with --clustered: refine a shortlist of C rows on the exact f32 rows")
     a = ap.parse_args()
+    if a.refine and not a.clustered:
+        ap.error("--refine needs --clustered (the exact f32 index)")
     lib = _lib.require_gpu(0)  # (raises without a GPU: nothing here falls back)
     n, dim, M = a.rows, a.dim, a.m
     out = {"rows": n, "dim": dim, "m": M, "nlist": a.nlist, "k": a.k, "shader_clock_mhz_before": clock_mhz(lib)}
@@ -170,6 +178,22 @@ def main():
     L = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
     FD = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
     FL = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
+    if a.refine:
+        SD = torch.empty((nqmax, a.refine), dtype=torch.float32, device="cuda")
+        SL = torch.empty((nqmax, a.refine), dtype=torch.int64, device="cuda")
+
+    def refined(handle, nq, nprobe, f32_truth):
+        """the shortlist search, the refine and both chained: p50s and the refined recall"""
+        short = lambda: handle.search_device(nq, Q.data_ptr(), a.refine, nprobe, SD.data_ptr(), SL.data_ptr())  # noqa: E731
+        fine = lambda: exact.refine_device(nq, Q.data_ptr(), a.refine, SL.data_ptr(), a.k, D.data_ptr(), L.data_ptr())  # noqa: E731
+        both = lambda: (short(), fine())  # noqa: E731
+        short_ms = median_of_p50s(short)
+        fine_ms = median_of_p50s(fine)
+        both_ms = median_of_p50s(both)
+        got = L[:nq].cpu().numpy()
+        return {"c": a.refine, "shortlist_p50_ms": short_ms, "refine_p50_ms": fine_ms, "chained_p50_ms": both_ms,
+                "recall_at_k_vs_exact_f32": float(np.mean([np.intersect1d(got[j], f32_truth[j]).size / a.k for j in range(nq)]))}
+
     torch.cuda.synchronize()
     cells = []
     for nq in a.nq:
@@ -198,6 +222,8 @@ def main():
                 cell["equals_flat_adc"] = bool(np.array_equal(got, truth) and np.array_equal(D[:nq].cpu().numpy(), truth_d))
             if exact is not None:
                 cell["recall_at_k_vs_exact_f32"] = float(np.mean([np.intersect1d(got[j], f32_truth[j]).size / a.k for j in range(nq)]))
+            if a.refine:
+                cell["refine"] = refined(h, nq, nprobe, f32_truth)
             if hr is not None:
                 rrun = lambda: hr.search_device(nq, Q.data_ptr(), a.k, nprobe, D.data_ptr(), L.data_ptr())  # noqa: E731
                 rms = median_of_p50s(rrun)
@@ -213,6 +239,8 @@ def main():
                        "scan_gb_per_s": (rst[1] * (M + 4) + pairs * M * 1024) / max(rsteps[3], 1e-6) / 1e6}
                 if exact is not None:
                     res["recall_at_k_vs_exact_f32"] = float(np.mean([np.intersect1d(rgot[j], f32_truth[j]).size / a.k for j in range(nq)]))
+                if a.refine:
+                    res["refine"] = refined(hr, nq, nprobe, f32_truth)
                 cell["residual"] = res
             cells.append(cell)
     out["cells"] = cells
