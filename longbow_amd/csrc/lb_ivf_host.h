@@ -1,5 +1,5 @@
-// lb_ivf_host.h -- the host side that the IVF handles share: what ivf.hip (lb_gpu_ivf, rows) and ivfpq.hip (lb_gpu_ivfpq, codes)
-// have in common beyond lb_handle.h.  Header-only, host-only, nothing exported.
+// lb_ivf_host.h -- the host side that the IVF handles share: what ivf.hip (lb_gpu_ivf, rows), ivfpq.hip (lb_gpu_ivfpq, PQ codes)
+// and ivfsq8.hip (lb_gpu_ivfsq8, SQ8 codes) have in common beyond lb_handle.h.  Header-only, host-only, nothing exported.
 //
 // The contract:
 //   * IvfPartition is the coarse partition of a handle's rows: the inner exact f32 index over the centroids, the list of each row
@@ -299,17 +299,20 @@ inline void ivf_commit_visible(IvfHandle *p, std::vector<int64_t> &vsizes, int64
 // ---- the search loop --------------------------------------------------------------------------------------------------------
 // Exact k-NN of nq device-resident queries among the rows of their probed lists, the lists being L with `sizes`; the caller holds
 // the reader lock, has made the device current and has checked the arguments.  `a` comes with the handle's own fields set.  The
-// scratch is leased into the caller's `sc`.  Per batch: the probes, launch_ivf_plan, the handle's middle steps, launch_ivf_select.
+// scratch is leased into the caller's `sc`.  Per batch: the probes, launch_ivf_plan, the handle's middle steps, the selection.
 //   extra(c, a, nb)               take()s the handle's scratch pieces for a batch of nb queries from the Carve c (it runs twice)
 //   middle(a, maxlen, poll, next) enqueues what fills a.keys; poll() is false once ctx fired, next() ends a timing slot and then
 //                                 polls; after either's false it enqueues nothing more and returns false.  maxlen: the longest list
 // timing[slots] (under err_mu) gets the ms of a profiled search summed over its batches: probes, plan (up to middle's first next()),
 // a slot per further next(), selection.  Profiling costs a drain per batch.  batch_cap: queries per batch at most, for a handle
-// whose own scratch grows with the batch (the residual IVF-PQ handle's tables); the others leave it at kQueryBatch.
+// whose own scratch grows with the batch (the residual IVF-PQ handle's tables); the others leave it at kQueryBatch.  select: the
+// selection's launcher, for a handle whose keys are not pack_entry's (the IVF-SQ8 handle's integer keys); launch_ivf_select's
+// arguments and meaning.
+using IvfSelectFn = void (*)(const IvfBatch &, int, const int64_t *, float *, int64_t *, hipStream_t);
 template <class Extra, class Middle>
 int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vector<int64_t> &sizes, IvfBatch a, int64_t nq, const float *d_Q,
                int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s, const lb_cancel *ctx, Lease &sc, float *timing, int slots,
-               Extra &&extra, Middle &&middle, int64_t batch_cap = kQueryBatch)
+               Extra &&extra, Middle &&middle, int64_t batch_cap = kQueryBatch, IvfSelectFn select = launch_ivf_select)
 {
     int64_t st[4] = {nq, 0, 0, 0};
     auto publish = [&]() {
@@ -375,7 +378,7 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
         launch_ivf_plan(a, d_stats, s);
         if (!middle(a, maxlen, go, next)) break;
         if (!next()) break;
-        launch_ivf_select(a, k, P.has_ids ? P.d_ids.get() : nullptr, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
+        select(a, k, P.has_ids ? P.d_ids.get() : nullptr, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
         mark();
         if (prof) {
             LB_HIP(hipEventSynchronize(ev[slots]));

@@ -1,7 +1,8 @@
 // lb_select.h -- the one definition of "one workgroup finds the k-th smallest of its unique u64 entries and writes the k
 // results": the MSB radix select, the compaction of what lies at or below its pivot, and the result emit.  Used by
-// select_kernel / emit_lists_kernel (kernels_select.hip) and the finish kernels (kernels_finish.hip), which differ only in where
-// their entries live (LDS, registers).  ivf_select_kernel (kernels_ivf.hip) takes wave_or_and_u64, the scratch's size and
+// select_kernel / emit_lists_kernel (kernels_select.hip), the finish kernels (kernels_finish.hip) and ivfsq8_select_kernel
+// (kernels_ivfsq8.hip: 1024 threads, integer keys, an emit of its own), which differ only in where their entries live (LDS,
+// registers, global memory).  ivf_select_kernel (kernels_ivf.hip) takes wave_or_and_u64, the scratch's size and
 // allow_big_lds from here and keeps its own text of the walk, for a measured reason given there.
 //
 // What the shared form does that one of the three earlier copies did not, and why no result moves:
