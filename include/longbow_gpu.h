@@ -929,6 +929,102 @@ int lb_gpu_ivfsq8_last_timing(lb_gpu_ivfsq8 *p, float ms[5]);
 /* as lb_gpu_ivf_last_build_timing: the last profiled build of the visible lists */
 int lb_gpu_ivfsq8_last_build_timing(lb_gpu_ivfsq8 *p, float *ms);
 
+/* ---- IVF-BQ: exact Hamming k-NN over the codes of the probed lists -----------------------------
+ * The coarse partition of lb_gpu_ivf_* over the sign-bit codes of lb_gpu_bq_*: a query skips most rows, and a row costs
+ * 8 * ceil(dims / 64) bytes instead of 4 * dims.  Nothing is approximate beyond the codes themselves and WHICH lists are probed:
+ * given the codes and the probed lists the result is the exact k-NN among their rows by the Hamming distance, bit for bit.
+ * A handle has dims, an accumulation order for the coarse quantiser (0 SEQ, 1 UNROLL4, as lb_gpu_index_set_order; fixed at
+ * creation because it decides which list a row goes to), nlist centroids C (f32 [nlist][dims], given by the caller) and rows in
+ * insertion order, of which only the codes are kept.  The coarse metric is L2 (metric 0) and the handle takes no metric argument.
+ *   code of a row     lb_gpu_bq_encode of the row: W = (dims + 63) / 64 little-endian words, bit i % 64 of word i / 64 set iff
+ *                     v[i] > 0, compared on the bit pattern (binary_quantization.go:34-45); pad bits are zero.  Only vectors are
+ *                     added, so a stored code never has a pad bit set.
+ *   list of a row     as on the other IVF handles: the label of the k = 1 L2 search of the f32 row, as a query, over an f32 index
+ *                     that holds C, in the handle's order.  Computed from the vector when the row is added, before the vector is
+ *                     dropped; it never changes.
+ *   probes of a query the labels of the k = min(nprobe, nlist) search of the f32 query over that same index.
+ *   distance          h = sum_w popcount(a[w] ^ b[w]) over all W words as int32 (simd.HammingDistance), a the code of the f32 query
+ *                     (encoded on the device per batch, as lb_gpu_bq_search does; a NaN component gives bit 0), b the row's code.
+ *   result            the first k rows r in ascending (h, r) order among the rows whose list is a probe of q; the reported
+ *                     distance is float32(h), exact because h <= 8192; the label is ids[r] when ids were given, else r; with fewer
+ *                     than k such rows they come first, then label -1 / distance FLT_MAX.  nprobe >= nlist gives lb_gpu_bq_search
+ *                     over the same codes, bit for bit: labels, order and distances.
+ *   ids               given on every add or on none; a call that breaks this is LB_ERR_INVALID_ARG and adds nothing.
+ *   add               assigns and encodes the vectors (in pieces of at most 64 Mi floats, so the staging of host vectors stays
+ *                     below 256 MB; the vectors are not kept) and rebuilds the lists of ALL rows by a stable counting sort (each
+ *                     list holds its rows ascending) and the list-major copy of their codes: O(ntotal) per call, so add in large
+ *                     pieces.  Codes, lists and list-major codes are committed together, or nothing is.
+ *   filter            a row filter on the handle, with the mask, null and combine rules of lb_gpu_ivf_set_filter / _filter_*: a
+ *                     row is visible iff its mask byte is non-zero; a NULL mask clears the filter; n != ntotal is
+ *                     LB_ERR_INVALID_ARG with a last_error text and leaves the filter as it was; a predicate's nulls never match;
+ *                     combine 0 replaces the mask, 1 ANDs into it and replaces when there is none; op outside 0..5 or a negative
+ *                     validity_offset is LB_ERR_INVALID_ARG.  The probes of a query do not change: a probed list with no visible
+ *                     row contributes nothing and no other list takes its place.  The result is the first k rows in ascending
+ *                     (h, r) order among the VISIBLE rows whose list is a probe, with the same labels, padding and distances, bit
+ *                     for bit; nprobe >= nlist gives lb_gpu_bq_search over the same codes under the same mask
+ *                     (lb_gpu_bq_set_filter).  Rows added after a filter was set are visible; such an add commits the codes, the
+ *                     lists, the list-major codes, the mask bytes and the visible lists together or not at all.  list_sizes,
+ *                     assignments, get_codes, get_centroids and ntotal ignore the filter; nvisible is the number of rows a search
+ *                     can see (ntotal without a filter).  Any filter, an all-visible one too, searches the visible lists (each
+ *                     list's visible entries as positions into the lists of all rows, ascending, built on the device by every
+ *                     filter call and every add under a filter), so the cost follows the visible rows of the probed lists, and
+ *                     last_search_stats counts those.
+ *   memory            the codes are held three times: once in insertion order (what get_codes returns, and what every add
+ *                     permutes from) and list-major once for each of the two list pairs an add alternates between, so a probed
+ *                     list is one contiguous run.  A row costs 24 * W + 12 bytes (codes and lists), 8 more with ids, and from the
+ *                     first filter on 13 more (the mask byte, the filter's own list, two visible lists).  hbm_bytes reports it.
+ *   limits            dims in 1..LB_MAX_DIM, nlist in 1..65536, k in 1..LB_MAX_K, fewer than 2^31 rows: LB_ERR_UNSUPPORTED
+ *                     beyond.  nprobe <= 0 is LB_ERR_INVALID_ARG, nprobe > nlist is clamped.  Fewer than all lists are at most
+ *                     LB_MAX_K probes (the coarse search's k; LB_ERR_UNSUPPORTED beyond); every list probed needs no coarse
+ *                     search and works for any nlist.
+ * lb_gpu_ivfbq_new checks dims <= 0, NULL centroids, order outside 0..1 and nlist <= 0 (LB_ERR_INVALID_ARG), then
+ * dims > LB_MAX_DIM and nlist > 65536 (LB_ERR_UNSUPPORTED), then the device (LB_ERR_NO_DEVICE).
+ * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
+ * refused call writes nothing.  Searches and reads share the handle; adds, reserve and the filter calls take it alone.  ctx
+ * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here:
+ * adding ready-made codes (a list needs the vector), a multi-query tile that shares a list's rows between the queries that probe
+ * it, a counting selection over the at most 8,193 distinct distances, search combining, lb_gpu_comm_*, removing rows,
+ * Save / Load, and the Go and C++ mirrors. */
+typedef struct lb_gpu_ivfbq lb_gpu_ivfbq;
+lb_gpu_ivfbq *lb_gpu_ivfbq_new(int device, int dims, int order, int nlist, const float *centroids, int *out_status);
+void lb_gpu_ivfbq_free(lb_gpu_ivfbq *p);
+const char *lb_gpu_ivfbq_last_error(const lb_gpu_ivfbq *p);
+int lb_gpu_ivfbq_dims(const lb_gpu_ivfbq *p);
+int lb_gpu_ivfbq_words(const lb_gpu_ivfbq *p); /* W = (dims + 63) / 64 */
+int lb_gpu_ivfbq_order(const lb_gpu_ivfbq *p);
+int lb_gpu_ivfbq_nlist(const lb_gpu_ivfbq *p);
+int64_t lb_gpu_ivfbq_ntotal(const lb_gpu_ivfbq *p);
+int64_t lb_gpu_ivfbq_hbm_bytes(const lb_gpu_ivfbq *p); /* codes three times, ids, lists, the coarse index and what a row filter holds */
+int lb_gpu_ivfbq_get_centroids(lb_gpu_ivfbq *p, float *out); /* f32[nlist*dims] */
+int lb_gpu_ivfbq_reserve(lb_gpu_ivfbq *p, int64_t n_total);
+int lb_gpu_ivfbq_add(lb_gpu_ivfbq *p, int64_t n, const float *vectors, const int64_t *ids); /* assign, encode, append */
+int lb_gpu_ivfbq_add_device(lb_gpu_ivfbq *p, int64_t n, const float *d_vectors, const int64_t *d_ids);
+int lb_gpu_ivfbq_get_codes(lb_gpu_ivfbq *p, int64_t row0, int64_t n, uint64_t *codes); /* u64[n*W], insertion order */
+int lb_gpu_ivfbq_list_sizes(lb_gpu_ivfbq *p, int64_t *sizes); /* [nlist] */
+int lb_gpu_ivfbq_assignments(lb_gpu_ivfbq *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
+int lb_gpu_ivfbq_search(lb_gpu_ivfbq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
+int lb_gpu_ivfbq_search_ctx(lb_gpu_ivfbq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
+                            const lb_cancel *ctx);
+int lb_gpu_ivfbq_search_device_ctx(lb_gpu_ivfbq *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist,
+                                   int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* the row filter, as lb_gpu_ivf_set_filter / _filter_int64 / _filter_float32 / _nvisible */
+int lb_gpu_ivfbq_set_filter(lb_gpu_ivfbq *p, const uint8_t *mask, int64_t n);
+int lb_gpu_ivfbq_filter_int64(lb_gpu_ivfbq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine);
+int lb_gpu_ivfbq_filter_float32(lb_gpu_ivfbq *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                                int64_t validity_offset, int combine);
+int64_t lb_gpu_ivfbq_nvisible(const lb_gpu_ivfbq *p);
+/* telemetry of the last search only, as lb_gpu_ivf_last_search_stats: out[0] queries, out[1] rows scanned summed over the
+ * queries, out[2] the largest per-query count, out[3] queries whose selection ran from LDS; under a row filter the rows are the
+ * visible ones of the probed lists */
+int lb_gpu_ivfbq_last_search_stats(lb_gpu_ivfbq *p, int64_t out[4]);
+/* instrumentation (tools/ivfbq_bench.py), as lb_gpu_ivf_set_profiling: ms[0] the probes (the coarse search), ms[1] the plan,
+ * ms[2] the queries' codes, ms[3] the scan of the probed lists' codes, ms[4] the selection; summed over the search's batches */
+int lb_gpu_ivfbq_set_profiling(lb_gpu_ivfbq *p, int enable);
+int lb_gpu_ivfbq_last_timing(lb_gpu_ivfbq *p, float ms[5]);
+/* as lb_gpu_ivf_last_build_timing: the last profiled build of the visible lists */
+int lb_gpu_ivfbq_last_build_timing(lb_gpu_ivfbq *p, float *ms);
+
 /* ---- cross-shard merge ---------------------------------------------------------
  * store.MergeSortedStreams (internal/store/result_merger.go:34-101) for S shards:
  * inputs [S][nq][k] ascending per (shard, query) (padding label -1 / FLT_MAX allowed),

@@ -11,6 +11,7 @@ library drops in behind:
   longbow_amd.ivf   <->  internal/store IVFFlatConfig / "ivf_flat" (a stub there): exact k-NN over the probed lists
   longbow_amd.ivfpq      the coarse partition of ivf over the codes of pq: exact ADC k-NN over the codes of the probed lists
   longbow_amd.ivfsq8     the coarse partition of ivf over the codes of sq8: exact integer k-NN over the codes of the probed lists
+  longbow_amd.ivfbq      the coarse partition of ivf over the codes of bq: exact Hamming k-NN over the codes of the probed lists
   longbow_amd.sharded    RingSharder partition + RCCL all-gather merge (one process per GPU)
   longbow_amd.arrow_io   Arrow RecordBatch ingestion + DoExchange / DoAction("VectorSearch") framing
   longbow_amd.hybrid     ReciprocalRankFusion + the GPU -> HNSW candidate hand-off rule
@@ -22,4 +23,4 @@ is missing.
 from . import _lib  # noqa: F401
 from .simd import MetricType  # noqa: F401
 
-__all__ = ["gpu", "simd", "pq", "bq", "sq8", "ivf", "ivfpq", "ivfsq8", "sharded", "arrow_io", "hybrid", "MetricType"]
+__all__ = ["gpu", "simd", "pq", "bq", "sq8", "ivf", "ivfpq", "ivfsq8", "ivfbq", "sharded", "arrow_io", "hybrid", "MetricType"]

@@ -275,6 +275,33 @@ SIGNATURES = [
     ("lb_gpu_ivfsq8_set_profiling", _i, [_vp, _i]),
     ("lb_gpu_ivfsq8_last_timing", _i, [_vp, _vp]),
     ("lb_gpu_ivfsq8_last_build_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfbq_new", _vp, [_i, _i, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivfbq_free", None, [_vp]),
+    ("lb_gpu_ivfbq_last_error", C.c_char_p, [_vp]),
+    ("lb_gpu_ivfbq_dims", _i, [_vp]),
+    ("lb_gpu_ivfbq_words", _i, [_vp]),
+    ("lb_gpu_ivfbq_order", _i, [_vp]),
+    ("lb_gpu_ivfbq_nlist", _i, [_vp]),
+    ("lb_gpu_ivfbq_ntotal", _i64, [_vp]),
+    ("lb_gpu_ivfbq_hbm_bytes", _i64, [_vp]),
+    ("lb_gpu_ivfbq_get_centroids", _i, [_vp, _vp]),
+    ("lb_gpu_ivfbq_reserve", _i, [_vp, _i64]),
+    ("lb_gpu_ivfbq_add", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivfbq_add_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivfbq_get_codes", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_ivfbq_list_sizes", _i, [_vp, _vp]),
+    ("lb_gpu_ivfbq_assignments", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_ivfbq_search", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+    ("lb_gpu_ivfbq_search_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    ("lb_gpu_ivfbq_search_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivfbq_set_filter", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_ivfbq_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
+    ("lb_gpu_ivfbq_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
+    ("lb_gpu_ivfbq_nvisible", _i64, [_vp]),
+    ("lb_gpu_ivfbq_last_search_stats", _i, [_vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfbq_set_profiling", _i, [_vp, _i]),
+    ("lb_gpu_ivfbq_last_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfbq_last_build_timing", _i, [_vp, _vp]),
     ("lb_gpu_merge_topk_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     ("lb_gpu_merge_topk_packed_device", _i, [_i, _i, _i64, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_rrf_fuse_device", _i, [_i, _i64, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
