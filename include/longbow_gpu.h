@@ -462,6 +462,35 @@ size_t lb_gpu_pq_blob_bytes(int dims, int M, int K);
  * process that ran one: ms[0] E-step, ms[1] ordering (scan + scatter), ms[2] M-step. */
 int lb_gpu_pq_train_last_timing(float ms[3]);
 
+/* ---- coarse quantiser training ---------------------------------------------------
+ * pq.TrainKMeans(vectors, n, dims, nlist, max_iter) (kmeans.go:64-151) for the centroids of the IVF handles, nlist in 1..65,536.
+ * It is the lb_gpu_pq_train block above with M = 1, m = 0, sub = dims and K = nlist, the centroids returned as plain f32
+ * instead of a blob:
+ *   init    centroid c = the copy of row init_rows[c] (HOST pointer in both entry points; duplicates allowed).  init_rows ==
+ *           NULL: the first nlist entries of the Fisher-Yates shuffle of [0, n) stated above, with draw(seed, 0, i).
+ *   E-step  s = simd.L2Squared(row, cent_c): four f32 chains over i mod 4, tail elements in chain 0, ((s0+s1)+s2)+s3, no sqrt,
+ *           no FMA contraction; the row goes to the first c with s < best, best starting at FLT_MAX.  A row with no such
+ *           centroid (NaN, overflow) makes the call return LB_ERR_INVALID_ARG and write nothing.
+ *   M-step  ONE sequential f32 chain per (cluster, element) over the members in ascending row order, then
+ *           sum / float32(count); an empty cluster c in iteration it takes the copy of row draw(seed, 0, nlist + it*nlist + c) mod n.
+ *   stop    after an iteration with it > 0 && changed < n/1000 + 1, or after max_iter iterations; max_iter == 0 returns the
+ *           init rows.  *iters_out (nullable, one value) = iterations run.
+ * centroids: HOST pointer in both entry points, f32[nlist * dims].  For nlist <= 256 the result equals
+ * lb_gpu_pq_train(device, dims, 1, nlist, ...) byte for byte (that blob's bytes 12 onwards), with equal iteration counts.
+ * Checked before a device is touched, in this order: LB_ERR_INVALID_ARG (NULL vectors / centroids, dims <= 0, nlist <= 0,
+ * n < nlist, max_iter < 0, an init_rows entry outside [0, n)); LB_ERR_UNSUPPORTED (nlist > 65536, dims > LB_MAX_DIM,
+ * n >= 2^31); LB_ERR_NO_DEVICE.  A refused or cancelled call writes neither centroids nor iters_out.  All rows stay resident
+ * for the iterations (n*dims*4 bytes); beside them the call holds 8 bytes per row, the ordering's histogram (at most 2^24
+ * counters) and nlist*dims*4 bytes: LB_ERR_OOM if they do not fit.  ctx (nullable) is polled before every launch of an
+ * iteration (E-step, ordering, M-step, finish), since one iteration can be long at this shape. */
+int lb_gpu_ivf_train(int device, int dims, int nlist, int64_t n, const float *vectors, int max_iter, uint64_t seed,
+                     const int64_t *init_rows, float *centroids, int32_t *iters_out, const lb_cancel *ctx);
+int lb_gpu_ivf_train_device(int device, int dims, int nlist, int64_t n, const float *d_vectors, int max_iter, uint64_t seed,
+                            const int64_t *init_rows, float *centroids, int32_t *iters_out, void *stream, const lb_cancel *ctx);
+/* instrumentation (tools/ivf_train_bench.py): HIP-event times of the first iteration of the last lb_gpu_ivf_train* call of this
+ * process that ran one: ms[0] E-step, ms[1] ordering (sort + counts), ms[2] M-step. */
+int lb_gpu_ivf_train_last_timing(float ms[3]);
+
 /* ---- binary quantisation: sign-bit codes and exact Hamming k-NN ------------------------
  * store.BQEncoder (internal/store/binary_quantization.go) and simd.HammingDistance (internal/simd/simd_bitops.go:40-55),
  * which the HNSW build and search use as float32(HammingDistance(q, t)) when BQEnabled is set

@@ -137,6 +137,9 @@ SIGNATURES = [
     ("lb_gpu_pq_train_device", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("lb_gpu_pq_blob_bytes", _sz, [_i, _i, _i]),
     ("lb_gpu_pq_train_last_timing", _i, [_vp]),
+    ("lb_gpu_ivf_train", _i, [_i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_train_device", _i, [_i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_train_last_timing", _i, [_vp]),
     ("lb_gpu_bq_new", _vp, [_i, _i, _ip]),
     ("lb_gpu_bq_free", None, [_vp]),
     ("lb_gpu_bq_last_error", C.c_char_p, [_vp]),

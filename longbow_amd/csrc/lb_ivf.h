@@ -55,4 +55,11 @@ size_t ivf_visible_scratch_bytes(int64_t n);
 hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, bool positions, void *scratch, uint32_t *voff, uint32_t *vrows,
                               hipStream_t s);
 
+// Coarse-quantiser training (kernels_ivf_train.hip; host side ivf_train.hip).  st.M == 1, st.sub == st.D, st.K <= IVF_MAX_NLIST.
+// E-step: st.assign[row] = the first strict minimum of simd.L2Squared over st.cent (-1 and *st.bad: none below FLT_MAX),
+// st.changed[0] += rows whose assignment changed.  chunk_hist, count, start and order are not touched.
+void launch_ivt_estep(const KmState &st, hipStream_t s);
+// count[c] = off[c + 1] - off[c] of launch_ivf_sort's offsets (which are the M-step's starts as they are)
+void launch_ivt_counts(const uint32_t *off, int K, uint32_t *count, hipStream_t s);
+
 } // namespace lb

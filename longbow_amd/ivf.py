@@ -8,7 +8,9 @@ list probed it equals gpu.Index.Search.  include/longbow_gpu.h states the semant
   IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats, and the
                  row filter (set_filter / filter_column / nvisible)
   IVFFlatIndex   the reference's PluggableVectorIndex surface over it: rows are buffered until Build()
-  train          TrainKMeans on the GPU (pq.train with M = 1): nlist centroids of f32 rows
+  train          TrainKMeans on the GPU (pq.train with M = 1): nlist <= 256 centroids of f32 rows
+  train_coarse   the same TrainKMeans for any nlist up to 65,536 (lb_gpu_ivf_train): a tiled exact f32 E-step over whole rows,
+                 the lists' own counting sort for the ordering; equal to train bit for bit where both apply
 """
 import ctypes as C
 from dataclasses import dataclass
@@ -45,6 +47,55 @@ def train_device(n, d_vectors, dims, nlist, max_iter=20, seed=0, init_rows=None,
     rows = None if init_rows is None else np.ascontiguousarray(init_rows, np.int64).reshape(1, nlist)
     blob, _ = pq.train_device(n, d_vectors, dims, 1, nlist, max_iter, seed, rows, device)
     return np.frombuffer(blob[12:], "<f4").reshape(nlist, dims).copy()
+
+
+def _coarse_args(n, dims, nlist, init_rows):
+    """what needs no device: the ValueErrors of train_coarse* and the call's host buffers"""
+    if not 1 <= nlist <= MAX_NLIST:
+        raise ValueError(f"ivf.train_coarse takes nlist in 1..{MAX_NLIST}, got {nlist}")
+    if n <= 0 or dims <= 0:
+        raise ValueError("empty training data")
+    rows = None
+    if init_rows is not None:
+        rows = np.ascontiguousarray(init_rows, np.int64)
+        if rows.shape != (nlist,):
+            raise ValueError(f"init_rows of shape {rows.shape}, want ({nlist},)")
+    return np.empty((nlist, dims), np.float32), np.zeros(1, np.int32), rows
+
+
+def train_coarse(vectors, nlist, max_iter=20, seed=0, init_rows=None, device=0, ctx=None, return_iters=False):
+    """TrainKMeans(vectors, n, dims, nlist, max_iter) on the GPU for any nlist in 1..65,536 (lb_gpu_ivf_train) -> centroids f32
+    [nlist, dims], with return_iters the pair (centroids, iterations run).  The contract is train()'s; for nlist <= 256 the
+    bytes and the iteration count equal train()'s.  init_rows [nlist]: rows whose copies are the first centroids (None: drawn
+    from seed).  max_iter = 0 returns the init rows."""
+    v = np.ascontiguousarray(vectors, np.float32)
+    if v.ndim != 2 or v.shape[0] == 0:
+        raise ValueError("empty training data")
+    n, dims = v.shape
+    cent, iters, rows = _coarse_args(n, dims, nlist, init_rows)
+    lib = _lib.require_gpu(device)
+    _lib.check(lib.lb_gpu_ivf_train(device, dims, nlist, n, v.ctypes.data, max_iter, seed, rows.ctypes.data if rows is not None else None,
+                                    cent.ctypes.data, iters.ctypes.data, ctx._h if ctx is not None else None))
+    return (cent, int(iters[0])) if return_iters else cent
+
+
+def train_coarse_device(n, d_vectors, dims, nlist, max_iter=20, seed=0, init_rows=None, device=0, ctx=None, return_iters=False,
+                        stream=None):
+    """train_coarse() over n rows already resident on the device (d_vectors: device address); init_rows stays a host array and
+    the centroids come back to the host"""
+    cent, iters, rows = _coarse_args(n, dims, nlist, init_rows)
+    lib = _lib.require_gpu(device)
+    _lib.check(lib.lb_gpu_ivf_train_device(device, dims, nlist, n, d_vectors, max_iter, seed, rows.ctypes.data if rows is not None else None,
+                                           cent.ctypes.data, iters.ctypes.data, stream, ctx._h if ctx is not None else None))
+    return (cent, int(iters[0])) if return_iters else cent
+
+
+def check_centroids(centroids, nlist, dims):
+    """centroids given to a train(..., centroids=) in place of the coarse step -> f32 [nlist, dims], the array itself when it is one"""
+    c = np.ascontiguousarray(centroids, np.float32)
+    if c.shape != (nlist, dims):
+        raise ValueError(f"centroids of shape {c.shape}, want {(nlist, dims)}")
+    return c
 
 
 class IVFFlat(RowFilterMixin, IVFBase):
@@ -90,7 +141,8 @@ class IVFFlatConfig:
 class IVFFlatIndex:
     """The reference's IVFFlatIndex surface (pluggable_index_adapters.go:116-223) with an index behind it.  Before Build() rows are
     buffered on the host, as the stub keeps them in its map; Build() takes the centroids as given, or trains them on the buffered
-    rows (ivf.train), creates the handle and adds the rows; after it, adds go straight to the handle."""
+    rows (ivf.train up to 256 lists, ivf.train_coarse beyond), creates the handle and adds the rows; after it, adds go straight
+    to the handle."""
 
     def __init__(self, dimension, config=None, metric=0, order=0, device=0, centroids=None, train_iters=20, seed=0):
         if dimension <= 0:
@@ -141,7 +193,8 @@ class IVFFlatIndex:
         rows = np.concatenate(self._rows) if self._rows else np.empty((0, self.dimension), np.float32)
         ids = np.concatenate(self._ids) if self._ids else np.empty(0, np.int64)
         if self._centroids is None:
-            self._centroids = train(rows, self.config.NClusters, self._train_iters, self._seed, device=self.device)
+            fit = train if self.config.NClusters <= TRAIN_MAX_NLIST else train_coarse
+            self._centroids = fit(rows, self.config.NClusters, self._train_iters, self._seed, device=self.device)
         self._h = IVFFlat(self._centroids, self.metric, self.order, self.device)
         if rows.shape[0]:
             self._h.add(rows, ids)

@@ -24,14 +24,19 @@ from ._rowfilter import RowFilterMixin
 FLT_MAX = ivf.FLT_MAX
 
 
-def train(vectors, nlist, M, max_iter=20, seed=0, device=0, residual=False):
+def train(vectors, nlist, M, max_iter=20, seed=0, device=0, residual=False, centroids=None):
     """-> (centroids f32 [nlist, dims], codebook blob): ivf.train for the coarse quantiser, pq.train (K = 256) for the codebooks,
     both over the same rows.  With residual=True the codebooks are pq.train of vectors - centroids[a] (numpy f32 on the host,
     one subtraction a component, as the handle's), a being the k = 1 L2 labels of the rows over a gpu.Index of the centroids in
     order 0 (SEQ).  A handle created with order = 1 may put a row that lies on a boundary between two lists into the other one:
-    that row's code is then of a residual the codebooks were not trained on, which bears on quality only, never on exactness."""
-    centroids = ivf.train(vectors, nlist, max_iter, seed, device=device)
+    that row's code is then of a residual the codebooks were not trained on, which bears on quality only, never on exactness.
+    centroids [nlist, dims] (say from ivf.train_coarse, which goes past 256 lists) are used as given in place of the coarse
+    step, by the residual branch too."""
     v = np.ascontiguousarray(vectors, np.float32)
+    if centroids is None:
+        centroids = ivf.train(vectors, nlist, max_iter, seed, device=device)
+    else:
+        centroids = ivf.check_centroids(centroids, nlist, v.shape[-1])
     if residual:
         coarse = gpu.Index(gpu.GPUConfig(DeviceID=device, Dimension=v.shape[1]))
         try:

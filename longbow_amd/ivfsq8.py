@@ -20,10 +20,14 @@ from ._rowfilter import RowFilterMixin
 FLT_MAX = ivf.FLT_MAX
 
 
-def train(vectors, nlist, max_iter=20, seed=0, device=0):
+def train(vectors, nlist, max_iter=20, seed=0, device=0, centroids=None):
     """-> (centroids f32 [nlist, dims], min f32 [dims], max f32 [dims]): ivf.train for the coarse quantiser, sq8.train
-    (TrainSQ8Encoder) for the bounds, both over the same rows"""
-    centroids = ivf.train(vectors, nlist, max_iter, seed, device=device)
+    (TrainSQ8Encoder) for the bounds, both over the same rows.  centroids [nlist, dims] (say from ivf.train_coarse, which goes
+    past 256 lists) are used as given in place of the coarse step."""
+    if centroids is None:
+        centroids = ivf.train(vectors, nlist, max_iter, seed, device=device)
+    else:
+        centroids = ivf.check_centroids(centroids, nlist, np.shape(vectors)[-1])
     enc = sq8.train(vectors, device=device)
     try:
         mn, mx = enc.GetBounds()

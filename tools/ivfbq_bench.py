@@ -15,8 +15,8 @@ and after.  A run that finds no GPU fails.
 
 --clustered replaces the uniform fill: rows are centres[owner] + unit noise, centres spread * N(0, 1) (--spread, default 3), one
 centre per list, queries drawn the same way (tools/ivfsq8_bench.py --clustered's data: the same generator and seed); the centroids
-come from ivfbq.train over a sample of --train-rows rows, so --nlist is at most ivf.train's 256.  The rows are also kept in an
-exact f32 gpu.Index, and every cell gains recall@k against its search of all rows ("recall_at_k_vs_exact_f32").
+come from ivfbq.train over a sample of --train-rows rows, past ivf.train's 256 lists from ivf.train_coarse, so --nlist goes up to
+65,536.  The rows are also kept in an exact f32 gpu.Index, and every cell gains recall@k against its search of all rows ("recall_at_k_vs_exact_f32").
 
 --refine C (with --clustered) adds the second stage to every cell: the handle's search for C rows into device buffers, then
 lb_gpu_index_refine on the exact index's rows for k of them, on the same stream.  The cell gains "refine": the p50 of the search
@@ -32,7 +32,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from longbow_amd import _lib, bq, gpu, ivfbq  # noqa: E402
+from longbow_amd import _lib, bq, gpu, ivf, ivfbq  # noqa: E402
 
 STEPS = ("probes_ms", "plan_ms", "codes_ms", "scan_ms", "select_ms")
 
@@ -96,7 +96,7 @@ def main():
         torch.cuda.synchronize()
         sample = sample.cpu().numpy()
         t0 = time.perf_counter()
-        cent_np = ivfbq.train(sample, a.nlist)
+        cent_np = (ivf.train_coarse if a.nlist > ivf.TRAIN_MAX_NLIST else ivfbq.train)(sample, a.nlist)
         out["train"] = {"rows": int(sample.shape[0]), "seconds": time.perf_counter() - t0, "spread": a.spread}
         del sample
     else:

@@ -19,8 +19,8 @@ tables, scan, selection), rows scanned and the pairs (nq * nprobe) its scan ran 
 
 --clustered replaces the uniform fill: rows are centres[owner] + unit noise, centres spread * N(0, 1) (--spread, default 3), one
 centre per list, queries drawn the same way; centroids and codebooks come from ivfpq.train over a sample of --train-rows rows
-(the residual handle's codebooks from ivfpq.train(..., residual=True)), so --nlist is at most ivf.train's 256.  The rows are also
-kept in an exact f32 gpu.Index, and every cell gains recall@k against its search of all rows ("recall_at_k_vs_exact_f32").
+(the residual handle's codebooks from ivfpq.train(..., residual=True)); past ivf.train's 256 lists the centroids come from
+ivf.train_coarse over the same sample and are handed to ivfpq.train, so --nlist goes up to 65,536.  The rows are also kept in an exact f32 gpu.Index, and every cell gains recall@k against its search of all rows ("recall_at_k_vs_exact_f32").
 
 --refine C (with --clustered) adds the second stage to every cell, for the plain handle and, with --residual, the residual one:
 the handle's search for C rows into device buffers, then lb_gpu_index_refine on the exact index's rows for k of them, on the same
@@ -37,7 +37,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from longbow_amd import _lib, gpu, ivfpq, pq  # noqa: E402
+from longbow_amd import _lib, gpu, ivf, ivfpq, pq  # noqa: E402
 
 
 def p50_ms(fn, reps=10):
@@ -101,9 +101,10 @@ def main():
         torch.cuda.synchronize()
         sample = sample.cpu().numpy()
         t0 = time.perf_counter()
-        cent_np, blob = ivfpq.train(sample, a.nlist, M)
+        coarse = ivf.train_coarse(sample, a.nlist) if a.nlist > ivf.TRAIN_MAX_NLIST else None
+        cent_np, blob = ivfpq.train(sample, a.nlist, M, centroids=coarse)
         if a.residual:
-            _, rblob = ivfpq.train(sample, a.nlist, M, residual=True)
+            _, rblob = ivfpq.train(sample, a.nlist, M, residual=True, centroids=coarse)
         out["train"] = {"rows": int(sample.shape[0]), "seconds": time.perf_counter() - t0, "spread": a.spread}
         del sample
     else:

@@ -16,8 +16,8 @@ finds no GPU fails.
 
 --clustered replaces the uniform fill: rows are centres[owner] + unit noise, centres spread * N(0, 1) (--spread, default 3), one
 centre per list, queries drawn the same way (tools/ivfpq_bench.py --clustered's data: the same generator and seed); centroids and
-bounds come from ivfsq8.train over a sample of --train-rows rows, so --nlist is at most ivf.train's 256.  The rows are also kept
-in an exact f32 gpu.Index, and every cell gains recall@k against its search of all rows ("recall_at_k_vs_exact_f32").
+bounds come from ivfsq8.train over a sample of --train-rows rows; past ivf.train's 256 lists the centroids come from
+ivf.train_coarse over the same sample and are handed to it, so --nlist goes up to 65,536.  The rows are also kept in an exact f32 gpu.Index, and every cell gains recall@k against its search of all rows ("recall_at_k_vs_exact_f32").
 
 --refine C (with --clustered) adds the second stage to every cell: the handle's search for C rows into device buffers, then
 lb_gpu_index_refine on the exact index's rows for k of them, on the same stream.  The cell gains "refine": the p50 of the search
@@ -33,7 +33,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from longbow_amd import _lib, gpu, ivfsq8, sq8  # noqa: E402
+from longbow_amd import _lib, gpu, ivf, ivfsq8, sq8  # noqa: E402
 
 STEPS = ("probes_ms", "plan_ms", "codes_ms", "scan_ms", "select_ms")
 
@@ -97,7 +97,8 @@ def main():
         torch.cuda.synchronize()
         sample = sample.cpu().numpy()
         t0 = time.perf_counter()
-        cent_np, mn, mx = ivfsq8.train(sample, a.nlist)
+        coarse = ivf.train_coarse(sample, a.nlist) if a.nlist > ivf.TRAIN_MAX_NLIST else None
+        cent_np, mn, mx = ivfsq8.train(sample, a.nlist, centroids=coarse)
         out["train"] = {"rows": int(sample.shape[0]), "seconds": time.perf_counter() - t0, "spread": a.spread}
         del sample
     else:
