@@ -691,10 +691,24 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     search and works for any nlist.
  * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
  * refused call writes nothing.  Searches and reads share the handle; adds, reserve and the filter calls take it alone.  ctx
- * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here:
- * fp16 / int8 rows, a filter given per search call, search combining, lb_gpu_comm_*, removing rows. */
+ * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.
+ *   float16 rows      lb_gpu_ivf_new_f16 takes what lb_gpu_ivf_new takes, with the same checks in the same order, and makes a
+ *                     handle whose rows are IEEE binary16, 2 bytes an element and no f32 copy of them (simd.VectorTypeFloat16).
+ *                     They cross the ABI as uint16_t bit patterns through lb_gpu_ivf_add_f16 / _add_f16_device, as on
+ *                     lb_gpu_index_add_f16; lb_gpu_ivf_add / _add_device on such a handle, and the _f16 adds on a float32
+ *                     handle, are LB_ERR_INVALID_ARG with a last_error text that names the handle's element type.  The
+ *                     centroids, the coarse index and the QUERIES stay f32 on both handle types: a caller with fp16 queries
+ *                     widens them, which is exact.  Every element is widened to f32 and enters the f32 arithmetic above (the
+ *                     reference's *F16Unrolled4x functions do the same), so every call on such a handle gives what the same call
+ *                     gives on a float32 handle that holds the widened rows, bit for bit: labels, distances, assignments, list
+ *                     sizes, search stats.  With fp16-representable queries the distances are the reference's F16 functions',
+ *                     and nprobe >= nlist gives lb_gpu_index_search of a float16 index (lb_gpu_index_new_f16) over the same
+ *                     rows.  Every other lb_gpu_ivf_* entry point works on both handle types.
+ * Not here: int8 rows, fp16 queries or centroids, a filter given per search call, search combining, lb_gpu_comm_*, removing rows. */
 typedef struct lb_gpu_ivf lb_gpu_ivf;
 lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
+lb_gpu_ivf *lb_gpu_ivf_new_f16(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
+int lb_gpu_ivf_dtype(const lb_gpu_ivf *p); /* 0 float32, 1 float16 (as lb_gpu_index_dtype); 0 on NULL */
 void lb_gpu_ivf_free(lb_gpu_ivf *p);
 const char *lb_gpu_ivf_last_error(const lb_gpu_ivf *p);
 int lb_gpu_ivf_dim(const lb_gpu_ivf *p);
@@ -702,11 +716,13 @@ int lb_gpu_ivf_metric(const lb_gpu_ivf *p);
 int lb_gpu_ivf_order(const lb_gpu_ivf *p);
 int lb_gpu_ivf_nlist(const lb_gpu_ivf *p);
 int64_t lb_gpu_ivf_ntotal(const lb_gpu_ivf *p);
-int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p); /* rows, ids, lists, the coarse index and what a row filter holds */
+int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p); /* rows (4 or 2 bytes an element), ids, lists, the coarse index and what a row filter holds */
 int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out); /* f32[nlist*dim] */
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total);
 int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids);
 int lb_gpu_ivf_add_device(lb_gpu_ivf *p, int64_t n, const float *d_vectors, const int64_t *d_ids);
+int lb_gpu_ivf_add_f16(lb_gpu_ivf *p, int64_t n, const uint16_t *vectors, const int64_t *ids); /* a float16 handle's add */
+int lb_gpu_ivf_add_f16_device(lb_gpu_ivf *p, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids);
 int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes); /* [nlist] */
 int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);

@@ -44,13 +44,16 @@ class IVFBase:
 
     def add(self, vectors, ids=None):
         """append rows [n, dims]; ids (int64 [n]) on every add or on none.  Each add rebuilds the lists of all rows: O(ntotal)."""
-        v = self._vectors(vectors)
+        self._add(self._vectors(vectors), ids, "add")
+
+    def _add(self, v, ids, entry):
+        """rows v [n, dims], contiguous and of the element type that the entry point `entry` takes"""
         i = None
         if ids is not None:
             i = np.ascontiguousarray(ids, np.int64).reshape(-1)
             if i.size != v.shape[0]:
                 raise ValueError(f"{i.size} ids for {v.shape[0]} rows")
-        self._check(self._fn("add")(self._h, v.shape[0], v.ctypes.data, i.ctypes.data if i is not None else None))
+        self._check(self._fn(entry)(self._h, v.shape[0], v.ctypes.data, i.ctypes.data if i is not None else None))
         self._has_ids = self._has_ids or i is not None
 
     def add_device(self, n, d_vectors, d_ids=None):

@@ -197,6 +197,10 @@ SIGNATURES = [
     ("lb_gpu_sq8_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
     ("lb_gpu_sq8_nvisible", _i64, [_vp]),
     ("lb_gpu_ivf_new", _vp, [_i, _i, _i, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivf_new_f16", _vp, [_i, _i, _i, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivf_dtype", _i, [_vp]),
+    ("lb_gpu_ivf_add_f16", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivf_add_f16_device", _i, [_vp, _i64, _vp, _vp]),
     ("lb_gpu_ivf_free", None, [_vp]),
     ("lb_gpu_ivf_last_error", C.c_char_p, [_vp]),
     ("lb_gpu_ivf_dim", _i, [_vp]),

@@ -1,48 +1,74 @@
 // ivf.hip -- host side of the lb_gpu_ivf_* entry points of include/longbow_gpu.h: the IVF-Flat index the reference names as
 // a plug-point (internal/store/pluggable_index.go:18-25,100-104; its adapter, pluggable_index_adapters.go:116-223, is a stub).
-// The kernels are in kernels_ivf.hip; the coarse quantiser is an inner exact f32 index over the centroids.
+// The kernels are in kernels_ivf.hip, the list scan over float16 rows in kernels_ivf_f16.hip; the coarse quantiser is an inner
+// exact f32 index over the centroids, whatever the rows' element type.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
+#include "lb_ivf_f16.h"
 #include "lb_ivf_host.h"
 
 using namespace lb;
 
 struct lb_gpu_ivf : IvfHandle { // the partition, and under a row filter the visible lists of rows (lb_ivf_host.h)
     int metric = 0, order = 0;
-    DevBuf<float> d_rows;           // [capacity][dims], insertion order
+    bool f16 = false;               // the rows' element type, fixed at creation: float32, or IEEE binary16 (lb_gpu_ivf_new_f16)
+    DevBuf<float> d_rows;           // [capacity][dims], insertion order (a float32 handle)
+    DevBuf<uint16_t> d_rows_f16;    // the same of a float16 handle, which holds no f32 copy of its rows
+    size_t elem_bytes() const { return f16 ? 2 : 4; }
     float timing[4] = {0, 0, 0, 0};  // of the last profiled search (under err_mu): probes, plan, scan, select; ms summed over its batches
 };
 
 namespace {
 
+// rows of an add to a float16 handle that are widened to f32 and assigned at a time: an add never needs an f32 copy of itself
+constexpr int64_t IVF_F16_ASSIGN_ROWS = 65536;
+
 // All or nothing: every new buffer is allocated and filled before the first one replaces an old one.
 void ivf_grow(lb_gpu_ivf *p, int64_t need, bool want_ids)
 {
-    const int64_t cap = ivf_grow_to(p, p->part, need, want_ids, (size_t)p->dims * 4); // 1.
+    const int64_t cap = ivf_grow_to(p, p->part, need, want_ids, (size_t)p->dims * p->elem_bytes()); // 1.
     if (cap < 0) return;
     IvfGrowth g;                                                                       // 2.
     DevBuf<float> nr;
+    DevBuf<uint16_t> nh;
     g.stage(p, cap, want_ids);
     if (g.resize) {
-        nr.alloc((size_t)cap * p->dims);
-        if (p->n > 0) LB_HIP(hipMemcpy(nr.get(), p->d_rows.get(), (size_t)p->n * p->dims * 4, hipMemcpyDeviceToDevice));
+        if (p->f16) {
+            nh.alloc((size_t)cap * p->dims);
+            if (p->n > 0) LB_HIP(hipMemcpy(nh.get(), p->d_rows_f16.get(), (size_t)p->n * p->dims * 2, hipMemcpyDeviceToDevice));
+        } else {
+            nr.alloc((size_t)cap * p->dims);
+            if (p->n > 0) LB_HIP(hipMemcpy(nr.get(), p->d_rows.get(), (size_t)p->n * p->dims * 4, hipMemcpyDeviceToDevice));
+        }
         p->filter.grow(p->n, cap);                                                     // 3. (the last step that can fail)
     }
     g.commit(p);                                                                       // 4.
     if (!g.resize) return;
-    p->d_rows = std::move(nr);
+    if (p->f16) p->d_rows_f16 = std::move(nh);
+    else p->d_rows = std::move(nr);
     p->capacity = cap;
 }
 
-int add_impl(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids, bool on_device)
+// f16: the element type of the entry point; the error a handle of the other type reports, as the flat index does (index.hip)
+int dtype_mismatch(lb_gpu_ivf *p, bool f16)
+{
+    if (p->f16 == f16) return LB_OK;
+    p->set_error("%s", p->f16 ? "this index holds float16 rows: use the _f16 entry point"
+                              : "this index holds float32 rows: use the float32 entry point");
+    return LB_ERR_INVALID_ARG;
+}
+
+// vectors: n rows of the entry point's element type (f16: uint16_t bit patterns), on the host or on the device
+int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, bool on_device, bool f16)
 {
     if (!p || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
+    if (const int st = dtype_mismatch(p, f16)) return st;
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
     IvfPartition &P = p->part;
     if (const int st = ivf_ids_consistent(p, P, ids)) return st;
     if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease lab, hist, vis;
+    Lease lab, wide, hist, vis;
     return guard(p, p->stream, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
         hipStream_t s = p->stream;
@@ -52,12 +78,29 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids,
         const bool filtered = p->filter.on;
         ivf_grow(p, total, ids != nullptr);
         // 1. the rows
-        float *d_new = p->d_rows.get() + (size_t)p->n * p->dims;
-        LB_HIP(hipMemcpyAsync(d_new, vectors, (size_t)n * p->dims * 4, kind, s));
+        void *d_new = f16 ? static_cast<void *>(p->d_rows_f16.get() + (size_t)p->n * p->dims)
+                          : static_cast<void *>(p->d_rows.get() + (size_t)p->n * p->dims);
+        LB_HIP(hipMemcpyAsync(d_new, vectors, (size_t)n * p->dims * p->elem_bytes(), kind, s));
         if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, kind, s));
-        // 2. their lists, 3. the lists of all rows, into the pair not in use
-        lab.reset(p->device, ivf_assign_bytes(n));
-        if (const int rc = ivf_assign(p, P, p->n, n, d_new, lab, s)) return rc;
+        // 2. their lists (float16 rows a piece at a time, each widened into an f32 scratch that the coarse search reads),
+        // 3. the lists of all rows, into the pair not in use
+        if (f16) {
+            const int64_t piece = std::min(n, IVF_F16_ASSIGN_ROWS);
+            lab.reset(p->device, ivf_assign_bytes(piece));
+            wide.reset(p->device, (size_t)piece * p->dims * 4);
+            for (int64_t r0 = 0; r0 < n; r0 += piece) {
+                const int64_t cnt = std::min(piece, n - r0);
+                launch_widen_f16(static_cast<const uint16_t *>(d_new) + (size_t)r0 * p->dims, wide.as<float>(), cnt * p->dims, s);
+                if (const int rc = ivf_assign(p, P, p->n + r0, cnt, wide.as<float>(), lab, s)) return rc;
+                if (r0 + piece < n) { // (the scratch and the labels are reused by the next piece)
+                    LB_LAUNCH_CHECK();
+                    LB_HIP(hipStreamSynchronize(s));
+                }
+            }
+        } else {
+            lab.reset(p->device, ivf_assign_bytes(n));
+            if (const int rc = ivf_assign(p, P, p->n, n, static_cast<const float *>(d_new), lab, s)) return rc;
+        }
         ivf_sort_lists(p, P, total, hist, s);
         if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
         const int nxt = 1 - P.cur;
@@ -80,7 +123,7 @@ int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprob
                    const lb_cancel *ctx, Lease &sc)
 {
     IvfBatch a{};
-    a.X = p->d_rows.get();
+    a.X = p->f16 ? nullptr : p->d_rows.get(); // (the plan and the selection read no rows)
     a.D = p->dims;
     float *d_qna = nullptr;
     return ivf_search(
@@ -92,7 +135,8 @@ int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprob
                 launch_query_norms(p->order, b.Q, nullptr, b.nq, p->dims, d_qna, s);
             }
             if (!next()) return false;
-            launch_ivf_scan(p->metric, p->order, b, maxlen, s);
+            if (p->f16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, reinterpret_cast<const _Float16 *>(p->d_rows_f16.get())}, maxlen, s);
+            else launch_ivf_scan(p->metric, p->order, b, maxlen, s);
             return true;
         });
 }
@@ -101,7 +145,7 @@ int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprob
 
 extern "C" {
 
-lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status)
+static lb_gpu_ivf *ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status, bool f16)
 {
     auto st = [&](int v) { if (out_status) *out_status = v; };
     if (dim <= 0 || metric < 0 || metric > 2 || order < 0 || order > 1 || nlist <= 0 || !centroids) { st(LB_ERR_INVALID_ARG); return nullptr; }
@@ -109,8 +153,19 @@ lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist
     return ivf_open<lb_gpu_ivf>(device, dim, metric, order, nlist, centroids, out_status, [&](lb_gpu_ivf *p) {
         p->metric = metric;
         p->order = order;
+        p->f16 = f16;
     });
 }
+
+lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status)
+{
+    return ivf_new(device, dim, metric, order, nlist, centroids, out_status, false);
+}
+lb_gpu_ivf *lb_gpu_ivf_new_f16(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status)
+{
+    return ivf_new(device, dim, metric, order, nlist, centroids, out_status, true);
+}
+int lb_gpu_ivf_dtype(const lb_gpu_ivf *p) { return p && p->f16 ? 1 : 0; }
 
 void lb_gpu_ivf_free(lb_gpu_ivf *p) { handle_free(p); }
 const char *lb_gpu_ivf_last_error(const lb_gpu_ivf *p) { return handle_last_error(p); }
@@ -124,7 +179,7 @@ int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivf *>(p)->mu);
-    return (int64_t)(p->d_rows.count() * 4) + p->visible_bytes() + p->part.hbm_bytes();
+    return (int64_t)(p->d_rows.count() * 4 + p->d_rows_f16.count() * 2) + p->visible_bytes() + p->part.hbm_bytes();
 }
 
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total)
@@ -148,8 +203,13 @@ int lb_gpu_ivf_filter_float32(lb_gpu_ivf *p, const float *column, int64_t n, flo
 int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms) { return ivf_last_build_timing(p, ms); }
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
-int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false); }
-int lb_gpu_ivf_add_device(lb_gpu_ivf *p, int64_t n, const float *d_vectors, const int64_t *d_ids) { return add_impl(p, n, d_vectors, d_ids, true); }
+int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, false); }
+int lb_gpu_ivf_add_device(lb_gpu_ivf *p, int64_t n, const float *d_vectors, const int64_t *d_ids) { return add_impl(p, n, d_vectors, d_ids, true, false); }
+int lb_gpu_ivf_add_f16(lb_gpu_ivf *p, int64_t n, const uint16_t *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, true); }
+int lb_gpu_ivf_add_f16_device(lb_gpu_ivf *p, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids)
+{
+    return add_impl(p, n, d_vectors, d_ids, true, true);
+}
 int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out) { return ivf_get_centroids(p, out); }
 int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes) { return ivf_list_sizes(p, sizes); }
 int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *lists) { return ivf_assignments(p, row0, n, lists); }

@@ -6,7 +6,8 @@ probed lists the result is the exact k-NN among their rows, bit for bit in the r
 list probed it equals gpu.Index.Search.  include/longbow_gpu.h states the semantics.
 
   IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats, and the
-                 row filter (set_filter / filter_column / nvisible)
+                 row filter (set_filter / filter_column / nvisible); dtype=DataType.Float16 holds the rows as float16, 2 bytes an
+                 element, and answers as a float32 handle over the widened rows does, bit for bit
   IVFFlatIndex   the reference's PluggableVectorIndex surface over it: rows are buffered until Build()
   train          TrainKMeans on the GPU (pq.train with M = 1): nlist <= 256 centroids of f32 rows
   train_coarse   the same TrainKMeans for any nlist up to 65,536 (lb_gpu_ivf_train): a tiled exact f32 E-step over whole rows,
@@ -20,6 +21,7 @@ import numpy as np
 from . import _lib, pq
 from ._ivfbase import IVFBase
 from ._rowfilter import RowFilterMixin
+from .gpu import DataType
 
 FLT_MAX = np.float32(3.4028234663852886e38)
 MAX_NLIST = 65536
@@ -98,20 +100,39 @@ def check_centroids(centroids, nlist, dims):
     return c
 
 
+def rows_f16(vectors, dims):
+    """rows for a float16 handle -> np.float16 [n, dims], contiguous; np.float16 arrays only"""
+    v = np.asarray(vectors)
+    if v.dtype != np.float16:
+        raise TypeError(f"a float16 index takes np.float16 arrays, got {v.dtype}")
+    v = np.ascontiguousarray(v)
+    v = v.reshape(-1, v.shape[-1]) if v.size else v.reshape(0, dims)
+    if v.shape[1] != dims:
+        raise ValueError(f"vector dimension {v.shape[1]} does not match {dims}")
+    return v
+
+
 class IVFFlat(RowFilterMixin, IVFBase):
     """lb_gpu_ivf: metric 0 L2 / 1 cosine / 2 dot, order 0 SEQ / 1 UNROLL4, centroids f32 [nlist, dims].  Under a row filter
-    (RowFilterMixin) the probes stay as they are and a search sees the visible rows of the probed lists alone."""
+    (RowFilterMixin) the probes stay as they are and a search sees the visible rows of the probed lists alone.
+    dtype: DataType.Float32, or DataType.Float16 (lb_gpu_ivf_new_f16): the rows are held as float16.  Such a handle's add takes
+    np.float16 arrays only, as gpu.Index does for its Float16 type (converting other data here would change the vectors
+    silently), and add_device fp16 rows; the centroids and the queries stay float32 (float16 queries are widened here, which
+    is exact)."""
     _prefix = "lb_gpu_ivf"
     _timing_slots = 4
 
-    def __init__(self, centroids, metric=0, order=0, device=0, lib=None):
+    def __init__(self, centroids, metric=0, order=0, device=0, lib=None, dtype=DataType.Float32):
         self._h = None  # (Close() and __del__ find this when creation fails below)
         c = np.ascontiguousarray(centroids, np.float32)
         if c.ndim != 2 or c.shape[0] == 0 or c.shape[1] == 0:
             raise ValueError("centroids must be a non-empty [nlist, dims] array")
+        if dtype not in (DataType.Float32, DataType.Float16):
+            raise ValueError(f"an IVF-Flat handle holds float32 (0) or float16 (1) rows, got data type {dtype}")
         lib = lib or _lib.require_gpu(device)
         st = C.c_int(0)
-        h = lib.lb_gpu_ivf_new(device, c.shape[1], metric, order, c.shape[0], c.ctypes.data, C.byref(st))
+        new = lib.lb_gpu_ivf_new_f16 if dtype == DataType.Float16 else lib.lb_gpu_ivf_new
+        h = new(device, c.shape[1], metric, order, c.shape[0], c.ctypes.data, C.byref(st))
         if not h:
             _lib.check(st.value or 7)
         self._lib = lib
@@ -119,6 +140,22 @@ class IVFFlat(RowFilterMixin, IVFBase):
         self.device = device
         self.nlist, self.dims = c.shape
         self.metric, self.order = metric, order
+        self._f16 = dtype == DataType.Float16
+
+    @property
+    def dtype(self):
+        """0 float32, 1 float16 (lb_gpu_ivf_dtype)"""
+        return int(self._lib.lb_gpu_ivf_dtype(self._h))
+
+    def add(self, vectors, ids=None):
+        if not self._f16:
+            return super().add(vectors, ids)
+        self._add(rows_f16(vectors, self.dims), ids, "add_f16")
+
+    def add_device(self, n, d_vectors, d_ids=None):
+        """d_vectors: f32 rows, fp16 rows on a float16 handle"""
+        self._check(self._fn("add_f16_device" if self._f16 else "add_device")(self._h, n, d_vectors, d_ids))
+        self._has_ids = self._has_ids or d_ids is not None
 
     def last_timing(self):
         """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
@@ -142,11 +179,17 @@ class IVFFlatIndex:
     """The reference's IVFFlatIndex surface (pluggable_index_adapters.go:116-223) with an index behind it.  Before Build() rows are
     buffered on the host, as the stub keeps them in its map; Build() takes the centroids as given, or trains them on the buffered
     rows (ivf.train up to 256 lists, ivf.train_coarse beyond), creates the handle and adds the rows; after it, adds go straight
-    to the handle."""
+    to the handle.  data_type=DataType.Float16: the rows are np.float16 arrays, buffered and stored as such; Build() trains on the
+    widened rows."""
 
-    def __init__(self, dimension, config=None, metric=0, order=0, device=0, centroids=None, train_iters=20, seed=0):
+    def __init__(self, dimension, config=None, metric=0, order=0, device=0, centroids=None, train_iters=20, seed=0,
+                 data_type=DataType.Float32):
         if dimension <= 0:
             raise ValueError(f"dimension must be positive, got {dimension}")
+        if data_type not in (DataType.Float32, DataType.Float16):
+            raise ValueError(f"an IVF-Flat handle holds float32 (0) or float16 (1) rows, got data type {data_type}")
+        self.data_type = data_type
+        self._np = np.float16 if data_type == DataType.Float16 else np.float32
         self.config = config or IVFFlatConfig()
         if self.config.NClusters <= 0 or self.config.NProbe <= 0:
             raise ValueError("NClusters and NProbe must be positive")
@@ -174,7 +217,10 @@ class IVFFlatIndex:
         return True  # IVF requires training / clustering (pluggable_index_adapters.go:143-145)
 
     def AddBatch(self, ids, vectors):
-        v = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
+        if self._np is np.float16:
+            v = rows_f16(vectors, self.dimension)
+        else:
+            v = np.ascontiguousarray(vectors, np.float32).reshape(-1, self.dimension)
         i = np.ascontiguousarray(ids, np.int64).reshape(-1)
         if i.size != v.shape[0]:
             raise ValueError(f"{i.size} ids for {v.shape[0]} rows")
@@ -185,17 +231,17 @@ class IVFFlatIndex:
             self._rows.append(v.copy())
 
     def Add(self, id, vector):
-        self.AddBatch([id], np.asarray(vector, np.float32).reshape(1, -1))
+        self.AddBatch([id], np.asarray(vector, None if self._np is np.float16 else np.float32).reshape(1, -1))
 
     def Build(self):
         if self._h is not None:
             return
-        rows = np.concatenate(self._rows) if self._rows else np.empty((0, self.dimension), np.float32)
+        rows = np.concatenate(self._rows) if self._rows else np.empty((0, self.dimension), self._np)
         ids = np.concatenate(self._ids) if self._ids else np.empty(0, np.int64)
         if self._centroids is None:
             fit = train if self.config.NClusters <= TRAIN_MAX_NLIST else train_coarse
-            self._centroids = fit(rows, self.config.NClusters, self._train_iters, self._seed, device=self.device)
-        self._h = IVFFlat(self._centroids, self.metric, self.order, self.device)
+            self._centroids = fit(np.ascontiguousarray(rows, np.float32), self.config.NClusters, self._train_iters, self._seed, device=self.device)
+        self._h = IVFFlat(self._centroids, self.metric, self.order, self.device, dtype=self.data_type)
         if rows.shape[0]:
             self._h.add(rows, ids)
         self._ids, self._rows = [], []
