@@ -704,11 +704,30 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     sizes, search stats.  With fp16-representable queries the distances are the reference's F16 functions',
  *                     and nprobe >= nlist gives lb_gpu_index_search of a float16 index (lb_gpu_index_new_f16) over the same
  *                     rows.  Every other lb_gpu_ivf_* entry point works on both handle types.
- * Not here: int8 rows, fp16 queries or centroids, a filter given per search call, search combining, lb_gpu_comm_*, removing rows. */
+ *   int8 rows         lb_gpu_ivf_new_i8 makes a handle whose rows are signed int8, one byte an element, row-major in insertion
+ *                     order, and no wider copy of them (simd.VectorTypeInt8).  Metrics L2 (0) and dot (2) only: cosine, and dot
+ *                     with floor(dim / 4) + dim mod 4 > 1024, are LB_ERR_UNSUPPORTED, the rules of lb_gpu_index_new_i8 for its
+ *                     reasons, answered with the other limits (after LB_ERR_INVALID_ARG, before LB_ERR_NO_DEVICE).  Rows go in
+ *                     through lb_gpu_ivf_add_i8 / _add_i8_device and the QUERIES are int8 too, through lb_gpu_ivf_search_i8 /
+ *                     _search_i8_ctx / _search_i8_device_ctx, each taking what its float32 counterpart takes.  The float32 and
+ *                     _f16 adds and the float32 searches on such a handle, and the _i8 adds and searches on a float32 or
+ *                     float16 handle, are LB_ERR_INVALID_ARG with a last_error text that names the handle's element type, and
+ *                     write nothing.  The centroids and the coarse index stay f32 and `order` is the coarse index's: the list
+ *                     of a row and the probes of a query are those of the row / query widened to f32, which is exact, so
+ *                     assignments and list sizes equal those of a float32 handle over the widened rows, bit for bit.  `order`
+ *                     does not reach the row distances: d(q, x) is the one lb_gpu_index_search_i8 reports, in the reference's
+ *                     DataTypeInt8 arithmetic (L2: euclideanInt8AVX2Kernel, the sum over the first 16 floor(dim / 16) elements
+ *                     an exact int32 rounded once to f32, the tail added in f32 in order, sqrt correctly rounded; dot:
+ *                     dotInt8Unrolled4x, negated).  Result, labels, padding, ids, filters and stats are as stated above, and
+ *                     nprobe >= nlist gives lb_gpu_index_search_i8 of an int8 index (lb_gpu_index_new_i8) over the same rows,
+ *                     bit for bit.  Every other lb_gpu_ivf_* entry point works on all three handle types.
+ * Not here: fp16 or int8 centroids, fp16 queries, f32 queries on an int8 handle, a filter given per search call, search combining,
+ * lb_gpu_comm_*, removing rows. */
 typedef struct lb_gpu_ivf lb_gpu_ivf;
 lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
 lb_gpu_ivf *lb_gpu_ivf_new_f16(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
-int lb_gpu_ivf_dtype(const lb_gpu_ivf *p); /* 0 float32, 1 float16 (as lb_gpu_index_dtype); 0 on NULL */
+lb_gpu_ivf *lb_gpu_ivf_new_i8(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
+int lb_gpu_ivf_dtype(const lb_gpu_ivf *p); /* 0 float32, 1 float16, 2 int8 (as lb_gpu_index_dtype); 0 on NULL */
 void lb_gpu_ivf_free(lb_gpu_ivf *p);
 const char *lb_gpu_ivf_last_error(const lb_gpu_ivf *p);
 int lb_gpu_ivf_dim(const lb_gpu_ivf *p);
@@ -716,13 +735,15 @@ int lb_gpu_ivf_metric(const lb_gpu_ivf *p);
 int lb_gpu_ivf_order(const lb_gpu_ivf *p);
 int lb_gpu_ivf_nlist(const lb_gpu_ivf *p);
 int64_t lb_gpu_ivf_ntotal(const lb_gpu_ivf *p);
-int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p); /* rows (4 or 2 bytes an element), ids, lists, the coarse index and what a row filter holds */
+int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p); /* rows (4, 2 or 1 bytes an element), ids, lists, the coarse index and what a row filter holds */
 int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out); /* f32[nlist*dim] */
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total);
 int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids);
 int lb_gpu_ivf_add_device(lb_gpu_ivf *p, int64_t n, const float *d_vectors, const int64_t *d_ids);
 int lb_gpu_ivf_add_f16(lb_gpu_ivf *p, int64_t n, const uint16_t *vectors, const int64_t *ids); /* a float16 handle's add */
 int lb_gpu_ivf_add_f16_device(lb_gpu_ivf *p, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids);
+int lb_gpu_ivf_add_i8(lb_gpu_ivf *p, int64_t n, const int8_t *vectors, const int64_t *ids); /* an int8 handle's add */
+int lb_gpu_ivf_add_i8_device(lb_gpu_ivf *p, int64_t n, const int8_t *d_vectors, const int64_t *d_ids);
 int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes); /* [nlist] */
 int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
@@ -730,6 +751,12 @@ int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k
                           const lb_cancel *ctx);
 int lb_gpu_ivf_search_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                  void *stream, const lb_cancel *ctx);
+/* an int8 handle's searches: int8 queries */
+int lb_gpu_ivf_search_i8(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels);
+int lb_gpu_ivf_search_i8_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels,
+                             const lb_cancel *ctx);
+int lb_gpu_ivf_search_i8_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, float *d_dist,
+                                    int64_t *d_labels, void *stream, const lb_cancel *ctx);
 /* the row filter, as lb_gpu_bq_set_filter / _filter_int64 / _filter_float32 / _nvisible */
 int lb_gpu_ivf_set_filter(lb_gpu_ivf *p, const uint8_t *mask, int64_t n);
 int lb_gpu_ivf_filter_int64(lb_gpu_ivf *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,

@@ -201,6 +201,9 @@ SIGNATURES = [
     ("lb_gpu_ivf_dtype", _i, [_vp]),
     ("lb_gpu_ivf_add_f16", _i, [_vp, _i64, _vp, _vp]),
     ("lb_gpu_ivf_add_f16_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivf_new_i8", _vp, [_i, _i, _i, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivf_add_i8", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivf_add_i8_device", _i, [_vp, _i64, _vp, _vp]),
     ("lb_gpu_ivf_free", None, [_vp]),
     ("lb_gpu_ivf_last_error", C.c_char_p, [_vp]),
     ("lb_gpu_ivf_dim", _i, [_vp]),
@@ -218,6 +221,9 @@ SIGNATURES = [
     ("lb_gpu_ivf_search", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     ("lb_gpu_ivf_search_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
     ("lb_gpu_ivf_search_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_i8", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+    ("lb_gpu_ivf_search_i8_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_i8_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_ivf_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivf_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_ivf_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),

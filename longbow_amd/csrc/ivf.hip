@@ -1,27 +1,37 @@
 // ivf.hip -- host side of the lb_gpu_ivf_* entry points of include/longbow_gpu.h: the IVF-Flat index the reference names as
 // a plug-point (internal/store/pluggable_index.go:18-25,100-104; its adapter, pluggable_index_adapters.go:116-223, is a stub).
-// The kernels are in kernels_ivf.hip, the list scan over float16 rows in kernels_ivf_f16.hip; the coarse quantiser is an inner
-// exact f32 index over the centroids, whatever the rows' element type.
+// The kernels are in kernels_ivf.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
+// kernels_ivf_i8.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
 #include "lb_ivf_f16.h"
 #include "lb_ivf_host.h"
+#include "lb_ivf_i8.h"
 
 using namespace lb;
 
+enum { DT_F32 = 0, DT_F16 = 1, DT_I8 = 2 }; // simd.DataType, what lb_gpu_ivf_dtype returns
+
 struct lb_gpu_ivf : IvfHandle { // the partition, and under a row filter the visible lists of rows (lb_ivf_host.h)
     int metric = 0, order = 0;
-    bool f16 = false;               // the rows' element type, fixed at creation: float32, or IEEE binary16 (lb_gpu_ivf_new_f16)
+    int dtype = DT_F32;             // the rows' element type, fixed at creation (lb_gpu_ivf_new, _new_f16, _new_i8)
     DevBuf<float> d_rows;           // [capacity][dims], insertion order (a float32 handle)
-    DevBuf<uint16_t> d_rows_f16;    // the same of a float16 handle, which holds no f32 copy of its rows
-    size_t elem_bytes() const { return f16 ? 2 : 4; }
+    DevBuf<uint16_t> d_rows_f16;    // the same of a float16 handle (IEEE binary16), which holds no f32 copy of its rows
+    DevBuf<int8_t> d_rows_i8;       // the same of an int8 handle, which holds no wider copy of its rows either
+    size_t elem_bytes() const { return dtype == DT_I8 ? 1 : dtype == DT_F16 ? 2 : 4; }
+    char *rows() const // the buffer of the handle's element type
+    {
+        return dtype == DT_I8    ? reinterpret_cast<char *>(d_rows_i8.get())
+               : dtype == DT_F16 ? reinterpret_cast<char *>(d_rows_f16.get())
+                                 : reinterpret_cast<char *>(d_rows.get());
+    }
     float timing[4] = {0, 0, 0, 0};  // of the last profiled search (under err_mu): probes, plan, scan, select; ms summed over its batches
 };
 
 namespace {
 
-// rows of an add to a float16 handle that are widened to f32 and assigned at a time: an add never needs an f32 copy of itself
-constexpr int64_t IVF_F16_ASSIGN_ROWS = 65536;
+// rows of an add to a float16 or int8 handle that are widened to f32 and assigned at a time: an add never needs an f32 copy of itself
+constexpr int64_t IVF_WIDEN_ASSIGN_ROWS = 65536;
 
 // All or nothing: every new buffer is allocated and filled before the first one replaces an old one.
 void ivf_grow(lb_gpu_ivf *p, int64_t need, bool want_ids)
@@ -31,38 +41,48 @@ void ivf_grow(lb_gpu_ivf *p, int64_t need, bool want_ids)
     IvfGrowth g;                                                                       // 2.
     DevBuf<float> nr;
     DevBuf<uint16_t> nh;
+    DevBuf<int8_t> nb;
     g.stage(p, cap, want_ids);
     if (g.resize) {
-        if (p->f16) {
-            nh.alloc((size_t)cap * p->dims);
-            if (p->n > 0) LB_HIP(hipMemcpy(nh.get(), p->d_rows_f16.get(), (size_t)p->n * p->dims * 2, hipMemcpyDeviceToDevice));
-        } else {
-            nr.alloc((size_t)cap * p->dims);
-            if (p->n > 0) LB_HIP(hipMemcpy(nr.get(), p->d_rows.get(), (size_t)p->n * p->dims * 4, hipMemcpyDeviceToDevice));
-        }
+        const size_t elems = (size_t)cap * p->dims;
+        if (p->dtype == DT_I8) nb.alloc(elems);
+        else if (p->dtype == DT_F16) nh.alloc(elems);
+        else nr.alloc(elems);
+        void *to = p->dtype == DT_I8 ? (void *)nb.get() : p->dtype == DT_F16 ? (void *)nh.get() : (void *)nr.get();
+        if (p->n > 0) LB_HIP(hipMemcpy(to, p->rows(), (size_t)p->n * p->dims * p->elem_bytes(), hipMemcpyDeviceToDevice));
         p->filter.grow(p->n, cap);                                                     // 3. (the last step that can fail)
     }
     g.commit(p);                                                                       // 4.
     if (!g.resize) return;
-    if (p->f16) p->d_rows_f16 = std::move(nh);
+    if (p->dtype == DT_I8) p->d_rows_i8 = std::move(nb);
+    else if (p->dtype == DT_F16) p->d_rows_f16 = std::move(nh);
     else p->d_rows = std::move(nr);
     p->capacity = cap;
 }
 
-// f16: the element type of the entry point; the error a handle of the other type reports, as the flat index does (index.hip)
-int dtype_mismatch(lb_gpu_ivf *p, bool f16)
+// the error a handle reports to an entry point of another element type, as the flat index does (index.hip)
+int wrong_dtype(lb_gpu_ivf *p)
 {
-    if (p->f16 == f16) return LB_OK;
-    p->set_error("%s", p->f16 ? "this index holds float16 rows: use the _f16 entry point"
-                              : "this index holds float32 rows: use the float32 entry point");
+    p->set_error("%s", p->dtype == DT_I8    ? "this index holds int8 rows: use the _i8 entry point"
+                       : p->dtype == DT_F16 ? "this index holds float16 rows: use the _f16 entry point"
+                                            : "this index holds float32 rows: use the float32 entry point");
     return LB_ERR_INVALID_ARG;
 }
+// dtype: the element type of the rows an add entry point takes
+int dtype_mismatch(lb_gpu_ivf *p, int dtype) { return p->dtype == dtype ? (int)LB_OK : wrong_dtype(p); }
+// i8: the element type of the queries a search entry point takes.  An int8 handle takes int8 queries and nothing else; the
+// other two take f32 queries.
+int query_mismatch(lb_gpu_ivf *p, bool i8)
+{
+    if (!p) return LB_ERR_INVALID_ARG;
+    return (p->dtype == DT_I8) == i8 ? (int)LB_OK : wrong_dtype(p);
+}
 
-// vectors: n rows of the entry point's element type (f16: uint16_t bit patterns), on the host or on the device
-int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, bool on_device, bool f16)
+// vectors: n rows of the entry point's element type (DT_F16: uint16_t bit patterns), on the host or on the device
+int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, bool on_device, int dtype)
 {
     if (!p || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
-    if (const int st = dtype_mismatch(p, f16)) return st;
+    if (const int st = dtype_mismatch(p, dtype)) return st;
     if (n == 0) return LB_OK;
     std::unique_lock<std::shared_mutex> g(p->mu);
     IvfPartition &P = p->part;
@@ -78,19 +98,19 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
         const bool filtered = p->filter.on;
         ivf_grow(p, total, ids != nullptr);
         // 1. the rows
-        void *d_new = f16 ? static_cast<void *>(p->d_rows_f16.get() + (size_t)p->n * p->dims)
-                          : static_cast<void *>(p->d_rows.get() + (size_t)p->n * p->dims);
-        LB_HIP(hipMemcpyAsync(d_new, vectors, (size_t)n * p->dims * p->elem_bytes(), kind, s));
+        const size_t eb = p->elem_bytes();
+        char *d_new = p->rows() + (size_t)p->n * p->dims * eb;
+        LB_HIP(hipMemcpyAsync(d_new, vectors, (size_t)n * p->dims * eb, kind, s));
         if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, kind, s));
-        // 2. their lists (float16 rows a piece at a time, each widened into an f32 scratch that the coarse search reads),
+        // 2. their lists (float16 and int8 rows a piece at a time, each widened into an f32 scratch that the coarse search reads),
         // 3. the lists of all rows, into the pair not in use
-        if (f16) {
-            const int64_t piece = std::min(n, IVF_F16_ASSIGN_ROWS);
+        if (dtype != DT_F32) {
+            const int64_t piece = std::min(n, IVF_WIDEN_ASSIGN_ROWS);
             lab.reset(p->device, ivf_assign_bytes(piece));
             wide.reset(p->device, (size_t)piece * p->dims * 4);
             for (int64_t r0 = 0; r0 < n; r0 += piece) {
                 const int64_t cnt = std::min(piece, n - r0);
-                launch_widen_f16(static_cast<const uint16_t *>(d_new) + (size_t)r0 * p->dims, wide.as<float>(), cnt * p->dims, s);
+                (dtype == DT_I8 ? launch_widen_i8 : launch_widen_f16)(d_new + (size_t)r0 * p->dims * eb, wide.as<float>(), cnt * p->dims, s);
                 if (const int rc = ivf_assign(p, P, p->n + r0, cnt, wide.as<float>(), lab, s)) return rc;
                 if (r0 + piece < n) { // (the scratch and the labels are reused by the next piece)
                     LB_LAUNCH_CHECK();
@@ -99,7 +119,7 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
             }
         } else {
             lab.reset(p->device, ivf_assign_bytes(n));
-            if (const int rc = ivf_assign(p, P, p->n, n, static_cast<const float *>(d_new), lab, s)) return rc;
+            if (const int rc = ivf_assign(p, P, p->n, n, reinterpret_cast<const float *>(d_new), lab, s)) return rc;
         }
         ivf_sort_lists(p, P, total, hist, s);
         if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
@@ -118,12 +138,13 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
 }
 
 // The handle's call of the search loop (lb_ivf_host.h): under a filter it walks the visible lists; its middle steps are the
-// queries' norms under cosine, inside the plan's timing slot, and the scan of the rows.
-int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                   const lb_cancel *ctx, Lease &sc)
+// queries' norms under cosine, inside the plan's timing slot, and the scan of the rows.  d_q8: on an int8 handle the call's int8
+// queries, d_Q being those widened to f32; the scan reads the int8 ones, a batch's at the offset of its b.Q in d_Q.
+int ivf_search_rows(lb_gpu_ivf *p, int64_t nq, const float *d_Q, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels,
+                    hipStream_t s, const lb_cancel *ctx, Lease &sc)
 {
     IvfBatch a{};
-    a.X = p->f16 ? nullptr : p->d_rows.get(); // (the plan and the selection read no rows)
+    a.X = p->dtype == DT_F32 ? p->d_rows.get() : nullptr; // (the plan and the selection read no rows)
     a.D = p->dims;
     float *d_qna = nullptr;
     return ivf_search(
@@ -135,37 +156,62 @@ int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprob
                 launch_query_norms(p->order, b.Q, nullptr, b.nq, p->dims, d_qna, s);
             }
             if (!next()) return false;
-            if (p->f16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, reinterpret_cast<const _Float16 *>(p->d_rows_f16.get())}, maxlen, s);
+            if (p->dtype == DT_I8) launch_ivf_scan_i8(p->metric, IvfI8Scan{b, p->d_rows_i8.get(), d_q8 + (b.Q - d_Q)}, maxlen, s);
+            else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, reinterpret_cast<const _Float16 *>(p->d_rows_f16.get())}, maxlen, s);
             else launch_ivf_scan(p->metric, p->order, b, maxlen, s);
             return true;
         });
+}
+
+// A float32 or float16 handle's search of f32 queries
+int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
+                   const lb_cancel *ctx, Lease &sc)
+{
+    return ivf_search_rows(p, nq, d_Q, nullptr, k, nprobe, d_dist, d_labels, s, ctx, sc);
+}
+
+// An int8 handle's: the call's int8 queries are widened once into `wide` (the caller's lease, declared outside its guard), which
+// is what the coarse index probes with; ctx is polled before that launch as before every other.
+int ivf_search_i8_dev(lb_gpu_ivf *p, int64_t nq, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
+                      const lb_cancel *ctx, Lease &sc, Lease &wide)
+{
+    wide.reset(p->device, (size_t)nq * p->dims * 4);
+    if (const int st = ctx_state(ctx)) return ctx_fail(p, st);
+    launch_widen_i8(d_q8, wide.as<float>(), nq * p->dims, s);
+    return ivf_search_rows(p, nq, wide.as<float>(), d_q8, k, nprobe, d_dist, d_labels, s, ctx, sc);
 }
 
 } // namespace
 
 extern "C" {
 
-static lb_gpu_ivf *ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status, bool f16)
+static lb_gpu_ivf *ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status, int dtype)
 {
     auto st = [&](int v) { if (out_status) *out_status = v; };
     if (dim <= 0 || metric < 0 || metric > 2 || order < 0 || order > 1 || nlist <= 0 || !centroids) { st(LB_ERR_INVALID_ARG); return nullptr; }
     if (dim > LB_MAX_DIM || nlist > IVF_MAX_NLIST) { st(LB_ERR_UNSUPPORTED); return nullptr; }
+    // int8 rows: lb_gpu_index_new_i8's rules, for its reasons (no cosine kernel in the reference; exact dot chains)
+    if (dtype == DT_I8 && (metric == LB_METRIC_COSINE || (metric == LB_METRIC_DOT && dim / 4 + dim % 4 > 1024))) { st(LB_ERR_UNSUPPORTED); return nullptr; }
     return ivf_open<lb_gpu_ivf>(device, dim, metric, order, nlist, centroids, out_status, [&](lb_gpu_ivf *p) {
         p->metric = metric;
         p->order = order;
-        p->f16 = f16;
+        p->dtype = dtype;
     });
 }
 
 lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status)
 {
-    return ivf_new(device, dim, metric, order, nlist, centroids, out_status, false);
+    return ivf_new(device, dim, metric, order, nlist, centroids, out_status, DT_F32);
 }
 lb_gpu_ivf *lb_gpu_ivf_new_f16(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status)
 {
-    return ivf_new(device, dim, metric, order, nlist, centroids, out_status, true);
+    return ivf_new(device, dim, metric, order, nlist, centroids, out_status, DT_F16);
 }
-int lb_gpu_ivf_dtype(const lb_gpu_ivf *p) { return p && p->f16 ? 1 : 0; }
+lb_gpu_ivf *lb_gpu_ivf_new_i8(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status)
+{
+    return ivf_new(device, dim, metric, order, nlist, centroids, out_status, DT_I8);
+}
+int lb_gpu_ivf_dtype(const lb_gpu_ivf *p) { return p ? p->dtype : 0; }
 
 void lb_gpu_ivf_free(lb_gpu_ivf *p) { handle_free(p); }
 const char *lb_gpu_ivf_last_error(const lb_gpu_ivf *p) { return handle_last_error(p); }
@@ -179,7 +225,7 @@ int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivf *>(p)->mu);
-    return (int64_t)(p->d_rows.count() * 4 + p->d_rows_f16.count() * 2) + p->visible_bytes() + p->part.hbm_bytes();
+    return (int64_t)(p->d_rows.count() * 4 + p->d_rows_f16.count() * 2 + p->d_rows_i8.count()) + p->visible_bytes() + p->part.hbm_bytes();
 }
 
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total)
@@ -203,12 +249,17 @@ int lb_gpu_ivf_filter_float32(lb_gpu_ivf *p, const float *column, int64_t n, flo
 int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms) { return ivf_last_build_timing(p, ms); }
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
-int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, false); }
-int lb_gpu_ivf_add_device(lb_gpu_ivf *p, int64_t n, const float *d_vectors, const int64_t *d_ids) { return add_impl(p, n, d_vectors, d_ids, true, false); }
-int lb_gpu_ivf_add_f16(lb_gpu_ivf *p, int64_t n, const uint16_t *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, true); }
+int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, DT_F32); }
+int lb_gpu_ivf_add_device(lb_gpu_ivf *p, int64_t n, const float *d_vectors, const int64_t *d_ids) { return add_impl(p, n, d_vectors, d_ids, true, DT_F32); }
+int lb_gpu_ivf_add_f16(lb_gpu_ivf *p, int64_t n, const uint16_t *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, DT_F16); }
 int lb_gpu_ivf_add_f16_device(lb_gpu_ivf *p, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids)
 {
-    return add_impl(p, n, d_vectors, d_ids, true, true);
+    return add_impl(p, n, d_vectors, d_ids, true, DT_F16);
+}
+int lb_gpu_ivf_add_i8(lb_gpu_ivf *p, int64_t n, const int8_t *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, DT_I8); }
+int lb_gpu_ivf_add_i8_device(lb_gpu_ivf *p, int64_t n, const int8_t *d_vectors, const int64_t *d_ids)
+{
+    return add_impl(p, n, d_vectors, d_ids, true, DT_I8);
 }
 int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out) { return ivf_get_centroids(p, out); }
 int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes) { return ivf_list_sizes(p, sizes); }
@@ -216,15 +267,35 @@ int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *list
 int lb_gpu_ivf_search_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                  void *stream, const lb_cancel *ctx)
 {
+    if (const int st = query_mismatch(p, false)) return st;
     return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivf_search_dev);
 }
 int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
+    if (const int st = query_mismatch(p, false)) return st;
     return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivf_search_dev);
 }
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
     return lb_gpu_ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, nullptr);
+}
+// the int8 handle's searches: int8 queries, widened once for the coarse index
+int lb_gpu_ivf_search_i8_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
+                                    void *stream, const lb_cancel *ctx)
+{
+    if (const int st = query_mismatch(p, true)) return st;
+    Lease wide;
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, [&](auto &&...args) { return ivf_search_i8_dev(args..., wide); });
+}
+int lb_gpu_ivf_search_i8_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    if (const int st = query_mismatch(p, true)) return st;
+    Lease wide;
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivf_search_i8_dev(args..., wide); });
+}
+int lb_gpu_ivf_search_i8(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels)
+{
+    return lb_gpu_ivf_search_i8_ctx(p, nq, queries, k, nprobe, dist, labels, nullptr);
 }
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
 int lb_gpu_ivf_set_profiling(lb_gpu_ivf *p, int enable) { return ivf_set_profiling(p, enable); }

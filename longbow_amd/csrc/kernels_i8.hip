@@ -14,6 +14,7 @@
 // The scan kernels read the queries widened to f32 (exact: they are int8 values) and narrow them back as they stage them; the
 // MFMA pass reads the int8 queries.
 #include "lb_device.h"
+#include "lb_i8_exact.h"
 
 #pragma clang fp contract(off)
 
@@ -21,40 +22,7 @@ namespace lb {
 
 typedef int i32x4 __attribute__((ext_vector_type(4)));
 
-// ---- the reference value of one pair, one lane, straight from memory (any D) ----------------------------------------
-// returns the reported distance: L2 the value, dot -value
-template <int METRIC>
-__device__ __forceinline__ float i8_pair_distance(const int8_t *x, const float *q, int D)
-{
-    if (METRIC == METRIC_L2) {
-        const int m = D & ~15;
-        int s = 0;
-        for (int i = 0; i < m; i++) {
-            const int e = (int)x[i] - (int)q[i];
-            s += e * e;
-        }
-        float f = (float)s; // VCVTDQ2PS: round to nearest
-        for (int i = m; i < D; i++) {
-            const int e = (int)x[i] - (int)q[i];
-            f = f + (float)(e * e); // CVTSI2SS + ADDSS, in order
-        }
-        return (float)sqrt((double)f); // VSQRTSS: correctly rounded
-    } else {
-        int p0 = 0, p1 = 0, p2 = 0, p3 = 0; // the four f32 chains, exact integers (|p| <= 2^24 by the dimension limit)
-        const int m4 = D & ~3;
-        for (int i = 0; i < m4; i += 4) {
-            p0 += (int)x[i] * (int)q[i];
-            p1 += (int)x[i + 1] * (int)q[i + 1];
-            p2 += (int)x[i + 2] * (int)q[i + 2];
-            p3 += (int)x[i + 3] * (int)q[i + 3];
-        }
-        for (int i = m4; i < D; i++) p0 += (int)x[i] * (int)q[i];
-        float t = (float)p0 + (float)p1;
-        t = t + (float)p2;
-        t = t + (float)p3;
-        return -t;
-    }
-}
+// (the reference value of one pair, one lane, straight from memory, any D: i8_pair_distance of lb_i8_exact.h)
 
 // ---- admission of one finished (position, slot) value: the f32 scan's rules (kernels_scan.hip: scan_kernel) ---------
 struct ScanI8Args {

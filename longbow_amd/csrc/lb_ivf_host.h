@@ -423,8 +423,8 @@ int ivf_search_args(T *p, int64_t nq, const void *queries, int k, int nprobe, co
     });
 }
 
-template <class T, class Dev>
-int ivf_search_device_ctx(T *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels, void *stream,
+template <class T, class Q, class Dev> // Q: the queries' element type, f32 but for the IVF-Flat handle over int8 rows
+int ivf_search_device_ctx(T *p, int64_t nq, const Q *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels, void *stream,
                           const lb_cancel *ctx, Dev &&dev)
 {
     const int rc = ivf_search_args(p, nq, d_queries, k, nprobe, d_dist, d_labels, ctx);
@@ -438,16 +438,16 @@ int ivf_search_device_ctx(T *p, int64_t nq, const float *d_queries, int k, int n
     });
 }
 
-template <class T, class Dev>
-int ivf_search_ctx(T *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx, Dev &&dev)
+template <class T, class Q, class Dev>
+int ivf_search_ctx(T *p, int64_t nq, const Q *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx, Dev &&dev)
 {
     const int rc = ivf_search_args(p, nq, queries, k, nprobe, dist, labels, ctx);
     if (rc != LB_OK || nq == 0) return rc;
     return host_knn(
-        p, nq, (size_t)p->dims * 4, k, dist, labels,
-        [&](Lease &dq, Lease &, hipStream_t s) { LB_HIP(hipMemcpyAsync(dq.p, queries, (size_t)nq * p->dims * 4, hipMemcpyHostToDevice, s)); },
+        p, nq, (size_t)p->dims * sizeof(Q), k, dist, labels,
+        [&](Lease &dq, Lease &, hipStream_t s) { LB_HIP(hipMemcpyAsync(dq.p, queries, (size_t)nq * p->dims * sizeof(Q), hipMemcpyHostToDevice, s)); },
         [&](Lease &dq, float *d_dist, int64_t *d_labels, hipStream_t s, Lease &sc) {
-            return dev(p, nq, dq.as<float>(), k, nprobe, d_dist, d_labels, s, ctx, sc);
+            return dev(p, nq, dq.as<Q>(), k, nprobe, d_dist, d_labels, s, ctx, sc);
         });
 }
 

@@ -8,6 +8,8 @@ list probed it equals gpu.Index.Search.  include/longbow_gpu.h states the semant
   IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats, and the
                  row filter (set_filter / filter_column / nvisible); dtype=DataType.Float16 holds the rows as float16, 2 bytes an
                  element, and answers as a float32 handle over the widened rows does, bit for bit
+  IVFFlatInt8    the same handle over signed int8 rows (lb_gpu_ivf_new_i8), one byte an element, searched with int8 queries in
+                 the reference's DataTypeInt8 arithmetic (L2 and dot); with every list probed it equals the flat int8 index
   IVFFlatIndex   the reference's PluggableVectorIndex surface over it: rows are buffered until Build()
   train          TrainKMeans on the GPU (pq.train with M = 1): nlist <= 256 centroids of f32 rows
   train_coarse   the same TrainKMeans for any nlist up to 65,536 (lb_gpu_ivf_train): a tiled exact f32 E-step over whole rows,
@@ -128,7 +130,8 @@ class IVFFlat(RowFilterMixin, IVFBase):
         if c.ndim != 2 or c.shape[0] == 0 or c.shape[1] == 0:
             raise ValueError("centroids must be a non-empty [nlist, dims] array")
         if dtype not in (DataType.Float32, DataType.Float16):
-            raise ValueError(f"an IVF-Flat handle holds float32 (0) or float16 (1) rows, got data type {dtype}")
+            raise ValueError(f"an IVF-Flat handle holds float32 (0) or float16 (1) rows, got data type {dtype}"
+                             + (": int8 rows are IVFFlatInt8's" if dtype == DataType.Int8 else ""))
         lib = lib or _lib.require_gpu(device)
         st = C.c_int(0)
         new = lib.lb_gpu_ivf_new_f16 if dtype == DataType.Float16 else lib.lb_gpu_ivf_new
@@ -168,6 +171,83 @@ class IVFFlat(RowFilterMixin, IVFBase):
         return float(out.value)
 
 
+def rows_i8(vectors, dims):
+    """rows or queries for an int8 handle -> np.int8 [n, dims], contiguous; np.int8 arrays only"""
+    v = np.asarray(vectors)
+    if v.dtype != np.int8:
+        raise TypeError(f"an int8 index takes np.int8 arrays, got {v.dtype}")
+    v = np.ascontiguousarray(v)
+    v = v.reshape(-1, v.shape[-1]) if v.size else v.reshape(0, dims)
+    if v.shape[1] != dims:
+        raise ValueError(f"vector dimension {v.shape[1]} does not match {dims}")
+    return v
+
+
+class IVFFlatInt8(RowFilterMixin, IVFBase):
+    """lb_gpu_ivf over signed int8 rows (lb_gpu_ivf_new_i8): metric 0 L2 / 2 dot, centroids f32 [nlist, dims]; order 0 SEQ /
+    1 UNROLL4 is the coarse index's and decides lists and probes alone.  add, search and their device-pointer forms take int8
+    rows and int8 queries, np.int8 arrays only (converting other data here would change the vectors silently).  The distances are
+    the flat int8 index's (gpu.Index with DataType.Int8), and with every list probed so is the result.  Row filters as on
+    IVFFlat."""
+    _prefix = "lb_gpu_ivf"
+    _timing_slots = 4
+
+    def __init__(self, centroids, metric=0, order=0, device=0, lib=None):
+        self._h = None  # (Close() and __del__ find this when creation fails below)
+        c = np.ascontiguousarray(centroids, np.float32)
+        if c.ndim != 2 or c.shape[0] == 0 or c.shape[1] == 0:
+            raise ValueError("centroids must be a non-empty [nlist, dims] array")
+        if metric == 1:
+            raise ValueError("an int8 IVF-Flat handle takes metric 0 (L2) or 2 (dot): the reference has no int8 cosine kernel")
+        lib = lib or _lib.require_gpu(device)
+        st = C.c_int(0)
+        h = lib.lb_gpu_ivf_new_i8(device, c.shape[1], metric, order, c.shape[0], c.ctypes.data, C.byref(st))
+        if not h:
+            _lib.check(st.value or 7)
+        self._lib = lib
+        self._h = C.c_void_p(h)
+        self.device = device
+        self.nlist, self.dims = c.shape
+        self.metric, self.order = metric, order
+
+    @property
+    def dtype(self):
+        """2 (lb_gpu_ivf_dtype)"""
+        return int(self._lib.lb_gpu_ivf_dtype(self._h))
+
+    def add(self, vectors, ids=None):
+        self._add(rows_i8(vectors, self.dims), ids, "add_i8")
+
+    def add_device(self, n, d_vectors, d_ids=None):
+        """d_vectors: int8 rows"""
+        self._check(self._fn("add_i8_device")(self._h, n, d_vectors, d_ids))
+        self._has_ids = self._has_ids or d_ids is not None
+
+    def search(self, queries, k, nprobe, ctx=None):
+        """int8 queries -> (labels [nq, k], dist [nq, k]), as IVFBase.search"""
+        v = rows_i8(queries, self.dims)
+        dist = np.empty((v.shape[0], k), np.float32)
+        labels = np.empty((v.shape[0], k), np.int64)
+        self._check(self._fn("search_i8_ctx")(self._h, v.shape[0], v.ctypes.data, k, nprobe, dist.ctypes.data, labels.ctypes.data,
+                                              ctx._h if ctx is not None else None))
+        return labels, dist
+
+    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None):
+        """d_queries: int8 [nq, dims]"""
+        self._check(self._fn("search_i8_device_ctx")(self._h, nq, d_queries, k, nprobe, d_dist, d_labels, stream,
+                                                     ctx._h if ctx is not None else None))
+
+    def last_timing(self):
+        """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
+        return super().last_timing()
+
+    def last_build_timing(self):
+        """ms of the last profiled build of the visible lists (a filter call or an add under a filter): its launches alone"""
+        out = C.c_float(0)
+        self._check(self._lib.lb_gpu_ivf_last_build_timing(self._h, C.byref(out)))
+        return float(out.value)
+
+
 @dataclass
 class IVFFlatConfig:
     """pluggable_index.go:100-104"""
@@ -187,7 +267,8 @@ class IVFFlatIndex:
         if dimension <= 0:
             raise ValueError(f"dimension must be positive, got {dimension}")
         if data_type not in (DataType.Float32, DataType.Float16):
-            raise ValueError(f"an IVF-Flat handle holds float32 (0) or float16 (1) rows, got data type {data_type}")
+            raise ValueError(f"an IVF-Flat handle holds float32 (0) or float16 (1) rows, got data type {data_type}"
+                             + (": int8 rows are IVFFlatInt8's, outside this float-only surface" if data_type == DataType.Int8 else ""))
         self.data_type = data_type
         self._np = np.float16 if data_type == DataType.Float16 else np.float32
         self.config = config or IVFFlatConfig()

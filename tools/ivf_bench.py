@@ -1,6 +1,6 @@
 """IVF-Flat index (exact k-NN over the probed lists) against the brute-force f32 index on the same rows: one JSON line.
 
-    python tools/ivf_bench.py [--rows 1000000] [--dim 768] [--nlist 256] [--k 100] [--dtype {f32,f16,both}] [--profile-reps 1]
+    python tools/ivf_bench.py [--rows 1000000] [--dim 768] [--nlist 256] [--k 100] [--dtype {f32,f16,both,int8}] [--profile-reps 1]
 
 Rows and queries come from the seeded device fill (uniform in [-0.5, 0.5)); the centroids are nlist of the rows (ivf.train with
 max_iter = 0 returns its init rows).  Per cell (nprobe x nq): the p50 of the whole search through the device-pointer entry point
@@ -16,6 +16,12 @@ rounded to float16 first (and widened again for the f32 handle, the flat index a
 values.  f16 measures the float16 handle (lb_gpu_ivf_new_f16) alone.  both fills a float32 and a float16 handle in one process,
 alternates their profiled runs, asserts that their labels and distances are equal in every cell, and prints per cell both
 handles' four timing slots with the spread (min, max) of the scan slot, and the scan's bytes per second on each.
+
+--dtype int8 rounds rows and queries into int8 (254 steps over [-0.5, 0.5)) and runs the int8 handle (lb_gpu_ivf_new_i8, int8
+queries) beside the float32 handle over the same values widened, in one process, their profiled runs taking turns.  The two
+handles' distances are different arithmetic (the reference's DataTypeInt8 kernels against its f32 chains), so what is asserted in
+every cell is what must be equal: assignments, list sizes and search stats (the same lists probed).  For every nq the int8 handle
+with every list probed is also asserted equal, labels and distances, to a flat int8 index over the same rows.
 """
 import argparse
 import ctypes as C
@@ -31,7 +37,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from longbow_amd import _lib, gpu, ivf  # noqa: E402
 
 HBM_BYTES_PER_S = 8e12
-ELEM_BYTES = {"f32": 4, "f16": 2}
+ELEM_BYTES = {"f32": 4, "f16": 2, "i8": 1}
 
 
 def p50_ms(fn, reps=3):
@@ -71,7 +77,7 @@ def main():
     ap.add_argument("--nprobe", type=int, nargs="*", default=[1, 8, 32, 256])
     ap.add_argument("--nq", type=int, nargs="*", default=[1, 8, 64, 1024])
     ap.add_argument("--train-rows", type=int, default=100_000)
-    ap.add_argument("--dtype", choices=("f32", "f16", "both"), default="f32")
+    ap.add_argument("--dtype", choices=("f32", "f16", "both", "int8"), default="f32")
     ap.add_argument("--profile-reps", type=int, default=1, help="profiled searches per cell and handle (the slots are their medians)")
     a = ap.parse_args()
     lib = _lib.require_gpu(0)  # (raises without a GPU: nothing here falls back)
@@ -82,8 +88,13 @@ def main():
     Q = torch.empty((nqmax, a.dim), dtype=torch.float32, device="cuda")
     _lib.check(lib.lb_gpu_fill_uniform_device(0, X.data_ptr(), a.rows * a.dim, 1, 0, None))
     _lib.check(lib.lb_gpu_fill_uniform_device(0, Q.data_ptr(), nqmax * a.dim, 2, 0, None))
-    X16 = None
-    if a.dtype != "f32":  # fp16-representable rows: both handles, the flat index and the centroids see the same values
+    X16 = X8 = Q8 = None
+    if a.dtype == "int8":  # int8 values: the float32 handle, the flat f32 index and the centroids see them widened
+        X8 = (X * 254).round_().clamp_(-128, 127).to(torch.int8)
+        Q8 = (Q * 254).round_().clamp_(-128, 127).to(torch.int8)
+        X.copy_(X8)
+        Q.copy_(Q8)
+    elif a.dtype != "f32":  # fp16-representable rows: both handles, the flat index and the centroids see the same values
         X16 = X.to(torch.float16)
         X.copy_(X16)
     torch.cuda.synchronize()
@@ -99,26 +110,37 @@ def main():
                            "estep_ms": float(ms3[0]), "order_ms": float(ms3[1]), "mstep_ms": float(ms3[2])}
 
     cent = ivf.train_device(a.rows, X.data_ptr(), a.dim, a.nlist, max_iter=0)  # nlist of the rows
-    names = ("f32", "f16") if a.dtype == "both" else (a.dtype,)
+    names = {"both": ("f32", "f16"), "int8": ("f32", "i8")}.get(a.dtype, (a.dtype,))
+    pair = len(names) == 2
+    other = names[-1]
     handles = {}
     for name in names:
-        h = ivf.IVFFlat(cent, dtype=gpu.DataType.Float16 if name == "f16" else gpu.DataType.Float32)
+        if name == "i8":
+            h = ivf.IVFFlatInt8(cent)
+        else:
+            h = ivf.IVFFlat(cent, dtype=gpu.DataType.Float16 if name == "f16" else gpu.DataType.Float32)
         h.reserve(a.rows)
         t0 = time.perf_counter()
-        h.add_device(a.rows, (X16 if name == "f16" else X).data_ptr())
+        h.add_device(a.rows, {"f16": X16, "i8": X8}.get(name, X).data_ptr())
         add_s = time.perf_counter() - t0
         handles[name] = h
         info = {"seconds": add_s, "rows_per_s": a.rows / add_s}
-        if a.dtype == "both":
+        if pair:
             out.setdefault("add", {})[name] = info
             out.setdefault("hbm_bytes", {})[name] = h.hbm_bytes
         else:
             out["add"], out["hbm_bytes"] = info, h.hbm_bytes
     first = handles[names[0]]
     sizes = first.list_sizes()
-    if a.dtype == "both":
-        assert np.array_equal(sizes, handles["f16"].list_sizes()), "the two handles' lists differ"
+    if pair:
+        assert np.array_equal(sizes, handles[other].list_sizes()), "the two handles' lists differ"
         X16 = None  # (the handle holds its own copy)
+    flat8 = None
+    if a.dtype == "int8":
+        flat8 = gpu.NewIndexWithConfig(gpu.GPUConfig(DeviceID=0, Dimension=a.dim, Metric=0, DataType=gpu.DataType.Int8))
+        flat8.reserve(a.rows)
+        flat8.add_device(a.rows, X8.data_ptr())
+        X8 = None
     out["lists"] = {"min": int(sizes.min()), "median": int(np.median(sizes)), "max": int(sizes.max()), "empty": int((sizes == 0).sum())}
 
     flat = gpu.NewIndexWithConfig(gpu.GPUConfig(DeviceID=0, Dimension=a.dim, Metric=0))
@@ -134,9 +156,16 @@ def main():
     for nq in a.nq:
         flat_ms = p50_ms(lambda: flat.search_device(nq, Q.data_ptr(), a.k, FD.data_ptr(), FL.data_ptr()))
         truth = FL[:nq].cpu().numpy()
+        if flat8 is not None:  # every list probed: the flat int8 index, bit for bit
+            D8, L8 = res["i8"]
+            flat8.search_device(nq, Q8.data_ptr(), a.k, FD.data_ptr(), FL.data_ptr())
+            handles["i8"].search_device(nq, Q8.data_ptr(), a.k, a.nlist, D8.data_ptr(), L8.data_ptr())
+            assert torch.equal(L8[:nq], FL[:nq]), f"every list probed: labels differ from the flat int8 index at nq {nq}"
+            assert torch.equal(D8[:nq], FD[:nq]), f"every list probed: distances differ from the flat int8 index at nq {nq}"
         for nprobe in a.nprobe:
             run = {name: (lambda h=handles[name], D=res[name][0], L=res[name][1]:
-                          h.search_device(nq, Q.data_ptr(), a.k, nprobe, D.data_ptr(), L.data_ptr())) for name in names}
+                          h.search_device(nq, (Q8 if h.dtype == 2 else Q).data_ptr(), a.k, nprobe, D.data_ptr(), L.data_ptr()))
+                   for name in names}
             ms = {name: p50_ms(run[name]) for name in names}
             steps = {name: [] for name in names}
             for _ in range(max(1, a.profile_reps)):  # the handles take turns
@@ -159,6 +188,14 @@ def main():
                 for name in names:
                     cell[name] = dict(measured(steps[name], st[1], a.dim, ELEM_BYTES[name]), p50_ms=ms[name])
                 cell["scan_f16_over_f32"] = cell["f16"]["scan_ms"] / max(cell["f32"]["scan_ms"], 1e-9)
+            elif a.dtype == "int8":
+                assert handles["i8"].last_search_stats() == st, f"search stats differ at nq {nq} nprobe {nprobe}"
+                assert np.array_equal(handles["i8"].list_sizes(), sizes), f"list sizes differ at nq {nq} nprobe {nprobe}"
+                assert np.array_equal(handles["i8"].assignments(), first.assignments()), f"assignments differ at nq {nq} nprobe {nprobe}"
+                cell["equal_lists"] = cell["equal_flat_i8"] = True
+                for name in names:
+                    cell[name] = dict(measured(steps[name], st[1], a.dim, ELEM_BYTES[name]), p50_ms=ms[name])
+                cell["scan_i8_over_f32"] = cell["i8"]["scan_ms"] / max(cell["f32"]["scan_ms"], 1e-9)
             else:
                 m = measured(steps[names[0]], st[1], a.dim, ELEM_BYTES[names[0]])
                 if a.profile_reps <= 1:
@@ -169,6 +206,8 @@ def main():
     out["shader_clock_mhz_after"] = clock_mhz(lib)
     print(json.dumps(out))
     flat.Close()
+    if flat8 is not None:
+        flat8.Close()
     for h in handles.values():
         h.Close()
 
