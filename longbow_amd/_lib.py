@@ -382,6 +382,8 @@ DIAG_SIGNATURES = [
     ("lb_debug_set_add_register_min", None, [C.c_longlong]),
     ("lb_debug_sample_plan", None, [C.c_longlong, _i, C.c_uint, C.c_uint, C.POINTER(C.c_longlong)]),
     ("lb_debug_cand_geometry", None, [_i, C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
+    ("lb_debug_last_wide_rows", _i, []),
+    ("lb_debug_set_wide256_min_tiles", None, [_i]),
 ]
 _diag = None
 

@@ -12,9 +12,13 @@
 // line per row per step), 4 waves (2x2), each wave 64x64 = 2x2 MFMA 32x32 tiles.
 // LDS: [128][32] f32 per operand per stage, 16-B chunks XOR-swizzled by
 // (row>>1)&7 so the ds_read_b128 fragment reads are bank-conflict free.
+// Large non-boot passes with D % 32 == 0 and 16-B rows run a second body of the same contraction,
+// gemm_filter_wide256_kernel below: 256 rows x 128 queries per workgroup on a ring of three 16-k
+// stages, same k order per accumulator, bit-identical keys (selection: launch_gemm_filter).
 // Candidate keys, thresholds, the tile's side inputs and the admission rule: lb_admit.h.
 #include "lb_admit.h"
 
+#include <atomic>
 #include <cstdlib>
 
 namespace lb {
@@ -432,6 +436,306 @@ __global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_kernel(GemmArgs a
     }
 }
 
+// ---- the 256-row body of the f32 GLDS tile -------------------------------------------------------------------------------
+// gemm_filter_wide256_kernel: 256 corpus rows x 128 queries per workgroup, 4 waves (2x2), each wave 128 rows x 64 queries =
+// 4x2 MFMA 32x32 tiles (128 accumulator registers), two workgroups per CU.  Per product it stages three quarters of the
+// 128-row tile's bytes and DMA pieces (24 KB per 256 x 128 x 16 against 32 KB per 128 x 128 x 32), issues 12 fragment
+// reads per 64 MFMAs in place of 16, and pays prologue, epilogue and dispatch half as often.
+// K-step: 16 floats (64 B per row), two sub-steps of 32 MFMAs; the lane halves take chunks 2s and 2s+1 of sub-step s, so
+// every accumulator sees k in the order the 128-row tile gives it and the candidate keys are bit-identical.
+// LDS: a ring of three stages [A 256x16 | B 128x16] f32 (24 KB each, 16-B chunks XOR-swizzled by (row>>2)&3 so that the
+// 16 rows of a ds_read_b128 group cover all 64 banks), then the side inputs of the 256 rows: 76,032 B, twice per CU.
+// Staging: direct-to-LDS DMA as inline asm with counted vmcnt waits -- with the builtin the compiler's wait pass puts
+// vmcnt(0) in front of every later LDS read, which would wait for the stage that has just been requested.  Stage j+3 is
+// requested behind the barrier of step j into the slot stage j was read from (its last fragments are in registers by then)
+// and has to be in by the barrier of step j+2: two K-steps of prefetch.  Schedule as in the 128-row loop: the reads of the
+// next sub-step sit behind the first 2 MFMAs of the current one, the 6 DMA pieces one per 4 MFMAs from the 8th MFMA behind
+// the barrier on, the last three steps are peeled (nothing left to request; the last one has no barrier).
+// Launched for non-boot passes only (launch_gemm_filter); D % 32 == 0, X and Q 16-B aligned.
+constexpr int WBM = 256;                        // corpus rows per tile
+constexpr int WBK = 16;                         // floats per K-step
+constexpr int WNST = 3;                         // ring stages
+constexpr int W_STAGE_F = (WBM + BN) * WBK;     // floats per stage
+constexpr int W_NI = 6;                         // DMA instructions per wave and stage: 4 x 16 corpus rows + 2 x 16 query rows
+
+// 64-B rows: the 16-B chunk of row r lands at position chunk ^ ((r >> 2) & 3)
+__device__ __forceinline__ int wswz(int row, int chunk) { return row * WBK + ((chunk ^ ((row >> 2) & 3)) << 2); }
+
+// 16 B per lane straight into LDS (lane l lands at lds_addr + 16 l).  NT: the corpus' cache policy, see kWide256CorpusNT.
+template <bool NT>
+__device__ __forceinline__ void wide_dma16(const void *gsrc, uint32_t lds_addr)
+{
+    uint32_t save;
+    if (NT)
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                     : "=&s"(save) : "v"(gsrc), "s"(lds_addr) : "memory");
+    else
+        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                     : "=&s"(save) : "v"(gsrc), "s"(lds_addr) : "memory");
+}
+// s_waitcnt vmcnt(VM) lgkmcnt(LGKM) (gfx9 encoding: vmcnt[3:0] | expcnt[6:4] | lgkmcnt[11:8] | vmcnt[5:4] << 14)
+template <int VM, int LGKM>
+__device__ __forceinline__ void wide_wait()
+{
+    __builtin_amdgcn_s_waitcnt((VM & 15) | (7 << 4) | (LGKM << 8) | ((VM >> 4) << 14));
+    asm volatile("" ::: "memory");
+}
+// A row's 128-B line is consumed over two K-steps, so it has to survive in L2 in between: default policy
+// (nt measured level on the headline shape, LABNOTES R32.1).
+constexpr bool kWide256CorpusNT = false;
+
+// the barrier of a step: this wave's part of the next stage is in once only the VM requests behind it are outstanding,
+// and its reads of the current stage have landed (that slot is requested into right behind the barrier)
+template <int VM>
+__device__ __forceinline__ void wide_step_barrier()
+{
+    wide_wait<VM, 0>();
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
+
+struct WideFrag {
+    f32x4 a[4], b[2];
+};
+// MFMAs FROM .. TO-1 of a sub-step's 32: i -> element i / 8 of the chunk pair, row tile (i / 2) % 4, query tile i % 2
+template <int FROM, int TO>
+__device__ __forceinline__ void wide_mfma(f32x16 (&acc)[4][2], const WideFrag &f)
+{
+#pragma unroll
+    for (int i = FROM; i < TO; i++) {
+        const int e = i >> 3, tm = (i >> 1) & 3, tn = i & 1;
+        acc[tm][tn] = __builtin_amdgcn_mfma_f32_32x32x2f32(f.a[tm][e], f.b[tn][e], acc[tm][tn], 0, 0, 0);
+    }
+}
+
+template <int METRIC>
+__global__ __launch_bounds__(GEMM_THREADS, 2) void gemm_filter_wide256_kernel(GemmArgs a)
+{
+    // XCD-aware tile order as in gemm_filter_kernel
+    const int b = blockIdx.x;
+    const int xcd = b & 7;
+    const int in_xcd = b >> 3;
+    const int qt = in_xcd % a.n_q_tiles;
+    const int rt = (in_xcd / a.n_q_tiles) * 8 + xcd;
+    if (rt >= a.n_row_tiles) return;
+
+    __shared__ __attribute__((aligned(16))) float lds_all[WNST * W_STAGE_F + WBM + WBM + WBM / 4];
+    float *ring = lds_all; // [WNST][A 256x16 | B 128x16]
+    float *s_aux = ring + WNST * W_STAGE_F;
+    uint32_t *s_rowid = reinterpret_cast<uint32_t *>(s_aux + WBM);
+    uint8_t *s_vis = reinterpret_cast<uint8_t *>(s_rowid + WBM);
+    const uint32_t ring_base = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) float *)ring;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave >> 1, wc = wave & 1;
+    const int l31 = lane & 31, h = lane >> 5;
+
+    const int64_t row0 = a.row_begin + (int64_t)rt * WBM;
+    const int q0 = qt * BN;
+    const int64_t last_row = a.row_end - 1;
+    const int last_q = a.nq - 1;
+
+    auto corpus_row = [&](int64_t pos) -> int64_t { // positions index the (possibly compacted) row list
+        if (pos > last_row) pos = last_row;
+        return a.rowmap ? (int64_t)a.rowmap[pos] : pos;
+    };
+    const int64_t side_ri = corpus_row(row0 + tid); // one side input per thread
+
+    // DMA sources.  Instruction i of this wave fills 16 rows (1 KiB): corpus rows 64 wave + 16 i .. +15, query rows
+    // 32 wave + 16 i .. +15; lane l lands at (row l / 4, chunk position l % 4) and fetches source chunk (l % 4) ^ ((row>>2)&3).
+    const float *srcA[4], *srcB[2];
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        const int row = wave * 64 + i * 16 + (lane >> 2);
+        const int c = (lane & 3) ^ ((row >> 2) & 3);
+        srcA[i] = a.X + corpus_row(row0 + row) * (int64_t)a.D + 4 * c;
+    }
+#pragma unroll
+    for (int i = 0; i < 2; i++) {
+        const int row = wave * 32 + i * 16 + (lane >> 2);
+        const int c = (lane & 3) ^ ((row >> 2) & 3);
+        int qr = q0 + row;
+        if (qr > last_q) qr = last_q;
+        srcB[i] = a.Q + (int64_t)qr * a.D + 4 * c;
+    }
+    // one staging piece p = 0..5 (A0 .. A3 B0 B1) of the stage at k0 into ring slot `slot`
+    auto piece = [&](int p, int slot, int k0) {
+        const uint32_t A = ring_base + (uint32_t)slot * (W_STAGE_F * 4);
+        if (p < 4)
+            wide_dma16<kWide256CorpusNT>(srcA[p] + k0, A + (uint32_t)((wave * 64 + p * 16) * WBK * 4));
+        else
+            wide_dma16<false>(srcB[p - 4] + k0, A + (uint32_t)(WBM * WBK * 4 + (wave * 32 + (p - 4) * 16) * WBK * 4));
+    };
+    auto issue = [&](int slot, int k0) {
+#pragma unroll
+        for (int p = 0; p < W_NI; p++) piece(p, slot, k0);
+    };
+
+    f32x16 acc[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int j = 0; j < 2; j++)
+#pragma unroll
+            for (int r = 0; r < 16; r++) acc[i][j][r] = 0.f;
+
+    const int nk = a.D / WBK; // D % 32 == 0 (launcher): an even count, at least 2
+    issue(0, 0);
+    issue(1, WBK);
+    if (nk > 2) issue(2, 2 * WBK);
+    // one burst behind the first stages: side inputs of tile row tid and this lane's two thresholds
+    const float aux_r = side_aux<METRIC>(a.norm2, a.rnorm, side_ri);
+    uint8_t side_vis = 1;
+    if (a.mask) side_vis = a.mask[side_ri];
+    uint64_t tau_raw[2];
+#pragma unroll
+    for (int tn = 0; tn < 2; tn++) tau_raw[tn] = lane_tau(a.cs.tau, q0 + wc * 64 + tn * 32 + l31, a.nq, false);
+    s_aux[tid] = aux_r;
+    s_vis[tid] = (row0 + tid <= last_row && side_vis) ? (uint8_t)1 : (uint8_t)0;
+    s_rowid[tid] = (uint32_t)side_ri;
+    float tau_key[2];
+    uint32_t tau_row[2];
+#pragma unroll
+    for (int tn = 0; tn < 2; tn++) {
+        tau_key[tn] = tau_key_of(tau_raw[tn]);
+        tau_row[tn] = entry_row(tau_raw[tn]);
+    }
+    wide_wait<0, 0>(); // the stages requested and every load above (the compiler cannot count the DMA)
+    __syncthreads();   // side inputs written (the loop below uses bare barriers: no LDS writes of its own)
+
+    WideFrag F0, F1;
+    auto ldfrag = [&](WideFrag &f, int slot, int s) {
+        const float *As = ring + slot * W_STAGE_F;
+        const float *Bs = As + WBM * WBK;
+        const int ch = 2 * s + h; // the two lane halves take alternate 16-B chunks (same k permutation for A and B)
+#pragma unroll
+        for (int t = 0; t < 4; t++) f.a[t] = *reinterpret_cast<const f32x4 *>(&As[wswz(wr * 128 + t * 32 + l31, ch)]);
+#pragma unroll
+        for (int t = 0; t < 2; t++) f.b[t] = *reinterpret_cast<const f32x4 *>(&Bs[wswz(wc * 64 + t * 32 + l31, ch)]);
+    };
+    // sub-step 0 of the stage in `slot` (F0 holds its fragments on entry, F1 sub-step 1's on exit).  The scheduling fences
+    // pin the order written here: the DMA is inline asm, which the scheduler's instruction groups do not see.
+    auto sub0 = [&](int slot) {
+        wide_mfma<0, 2>(acc, F0);
+        __builtin_amdgcn_sched_barrier(0);
+        ldfrag(F1, slot, 1);
+        __builtin_amdgcn_sched_barrier(0);
+        wide_mfma<2, 32>(acc, F0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // sub-step 1 + the next stage's sub-step-0 reads, without / with the 6 pieces of the stage at k0 into dma_slot
+    auto sub1 = [&](int next_slot) {
+        wide_mfma<0, 2>(acc, F1);
+        __builtin_amdgcn_sched_barrier(0);
+        ldfrag(F0, next_slot, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        wide_mfma<2, 32>(acc, F1);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto sub1_dma = [&](int next_slot, int dma_slot, int k0) {
+        wide_mfma<0, 2>(acc, F1);
+        __builtin_amdgcn_sched_barrier(0);
+        ldfrag(F0, next_slot, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        wide_mfma<2, 8>(acc, F1); // (a piece right behind the reads costs 0.7 % of the headline, LABNOTES R32.1)
+        __builtin_amdgcn_sched_barrier(0);
+#define LB_W256_PIECE(P)                                \
+    piece(P, dma_slot, k0);                             \
+    __builtin_amdgcn_sched_barrier(0);                  \
+    wide_mfma<8 + 4 * (P), 12 + 4 * (P)>(acc, F1);      \
+    __builtin_amdgcn_sched_barrier(0);
+        LB_W256_PIECE(0) LB_W256_PIECE(1) LB_W256_PIECE(2) LB_W256_PIECE(3) LB_W256_PIECE(4) LB_W256_PIECE(5)
+#undef LB_W256_PIECE
+    };
+    ldfrag(F0, 0, 0);
+    int slot = 0; // ring slot of stage j
+    int j = 0;
+    for (; j + 3 < nk; j++) {
+        const int next = slot == WNST - 1 ? 0 : slot + 1;
+        sub0(slot);
+        wide_step_barrier<W_NI>(); // stage j+1 is in, stage j+2 may be on its way
+        sub1_dma(next, slot, (j + 3) * WBK);
+        slot = next;
+    }
+    if (j + 2 < nk) { // the last step but two: nothing left to request
+        const int next = slot == WNST - 1 ? 0 : slot + 1;
+        sub0(slot);
+        wide_step_barrier<W_NI>();
+        sub1(next);
+        slot = next;
+    }
+    { // the last step but one: the last stage is the only one outstanding
+        const int next = slot == WNST - 1 ? 0 : slot + 1;
+        sub0(slot);
+        wide_step_barrier<0>();
+        sub1(next);
+        slot = next;
+    }
+    // the last step: no barrier, the ring is not written again
+    sub0(slot);
+    wide_mfma<0, 32>(acc, F1);
+    __builtin_amdgcn_sched_barrier(0); // (the epilogue's keys stay behind the fragments' last use: both do not fit the registers)
+
+    // ---- epilogue: key + admission -------------------------------------------------
+    // C layout (32x32): col = lane&31 (query), row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).  A lane holds 64 rows per query.
+    // Pass 1 (branch-free) builds a 64-bit admission word per query, the side inputs of one 32-row block at a time; then ONE
+    // returning atomic per lane and query reserves the slots, and the blocks with admissions are walked again (side inputs
+    // read again from LDS, keys computed again: kept next to the 128 accumulators they would not fit the registers).
+    uint64_t bits[2] = {0ull, 0ull};
+#pragma unroll
+    for (int tm = 0; tm < 4; tm++) {
+        float aux[4][4];
+        uint32_t rid[4][4];
+        uint32_t vb = 0; // bit (g*4 + e): row visible (in range and not masked out)
+#pragma unroll
+        for (int g = 0; g < 4; g++) vb |= tile_rows4(s_aux, s_rowid, s_vis, wr * 128 + tm * 32 + 8 * g + 4 * h, aux[g], rid[g]) << (g * 4);
+#pragma unroll
+        for (int tn = 0; tn < 2; tn++) {
+            uint32_t bb = 0;
+#pragma unroll
+            for (int g = 0; g < 4; g++)
+#pragma unroll
+                for (int e = 0; e < 4; e++) {
+                    bb |= admit_exact(cand_key<METRIC>(acc[tm][tn][4 * g + e], aux[g][e]), rid[g][e], tau_key[tn], tau_row[tn]) << (g * 4 + e);
+                }
+            bits[tn] |= (uint64_t)(bb & vb) << (tm * 16);
+        }
+        __builtin_amdgcn_sched_barrier(0); // one block's side inputs at a time (hoisted, the four blocks' loads spill)
+    }
+    // (opaque to the compiler: both admission words exist here -- the second query's test does not sink behind the first
+    // query's stores with all its side inputs -- and the second pass reads its side inputs again, behind its branches)
+    int lr2 = wr * 128 + 4 * h;
+    asm volatile("" : "+v"(lr2), "+v"(bits[0]), "+v"(bits[1]));
+#pragma unroll
+    for (int tn = 0; tn < 2; tn++) {
+        if (!bits[tn]) continue;
+        const int qj = q0 + wc * 64 + tn * 32 + l31; // (a query beyond nq admits nothing: its tau decodes to NaN)
+        uint64_t *list = a.cs.lists + (size_t)qj * a.cs.cap;
+        uint32_t pos = atomicAdd(&a.cs.cnt[qj], (uint32_t)__builtin_popcountll(bits[tn]));
+#pragma unroll
+        for (int tm = 0; tm < 4; tm++) {
+            const uint32_t bb = (uint32_t)(bits[tn] >> (tm * 16)) & 0xffffu;
+            if (!bb) continue;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const uint32_t nib = (bb >> (g * 4)) & 15u;
+                if (!nib) continue;
+                float aux[4];
+                uint32_t rid[4];
+                (void)tile_rows4(s_aux, s_rowid, s_vis, lr2 + tm * 32 + 8 * g, aux, rid);
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    if (nib & (1u << e)) {
+                        if (pos < a.cs.cap) list[pos] = pack_entry(cand_key<METRIC>(acc[tm][tn][4 * g + e], aux[e]), rid[e]);
+                        pos++;
+                    }
+            }
+        }
+    }
+}
+
 // f32 [rows][D] -> split-bf16 image of the same byte shape (D % 32 == 0): per row and 16-k group,
 // 16 bf16 hi values (x rounded to nearest even) then 16 bf16 lo values (x - hi rounded): one MFMA k-block per 64 B.
 __global__ __launch_bounds__(256) void split_bf16_kernel(const float *src, float *dst, int64_t n8)
@@ -456,6 +760,14 @@ void launch_split_bf16(const float *src, float *dst, int64_t rows, int D, hipStr
     hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, dst, n8);
 }
 
+// The 256-row body takes a non-boot pass of at least this many of its workgroups (below that the 128-row tile fills the chip
+// better: level at 3,900, ahead by 1.3 % at 7,800; sweep in LABNOTES R32.1).
+constexpr int kWide256MinTiles = 6144;
+#ifdef LB_DIAG
+static std::atomic<int> g_wide256_min_tiles{kWide256MinTiles}; // lb_debug_set_wide256_min_tiles
+static std::atomic<int> g_last_wide_rows{0};                   // lb_debug_last_wide_rows
+#endif
+
 void launch_gemm_filter(int metric, const float *X, const float *norm2, const float *rnorm,
                         int64_t row_begin, int64_t row_end, int D, const float *Q, int nq,
                         const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot, hipStream_t s)
@@ -467,17 +779,28 @@ void launch_gemm_filter(int metric, const float *X, const float *norm2, const fl
     a.X = X; a.norm2 = norm2; a.rnorm = rnorm;
     a.row_begin = row_begin; a.row_end = row_end; a.D = D;
     a.Q = Q; a.nq = nq; a.mask = mask; a.cs = cs;
-    a.n_row_tiles = (int)((row_end - row_begin + BM - 1) / BM);
     a.n_q_tiles = (nq + BN - 1) / BN;
-    const int groups = (a.n_row_tiles + 7) / 8;
-    dim3 grid((unsigned)(groups * 8 * a.n_q_tiles));
     const bool aligned = (D % 4 == 0) && ((reinterpret_cast<uintptr_t>(X) & 15) == 0) &&
                          ((reinterpret_cast<uintptr_t>(Q) & 15) == 0);
     const int mode = !aligned ? 0 : (D % BK == 0 ? 2 : 1);
+#ifdef LB_DIAG
+    const int wide256_min = g_wide256_min_tiles.load(std::memory_order_relaxed);
+#else
+    const int wide256_min = kWide256MinTiles;
+#endif
+    const int64_t tiles256 = (row_end - row_begin + WBM - 1) / WBM;
+    const bool wide256 = !boot && mode == 2 && tiles256 * a.n_q_tiles >= wide256_min;
+#ifdef LB_DIAG
+    if (!boot) g_last_wide_rows.store(wide256 ? WBM : BM, std::memory_order_relaxed);
+#endif
+    a.n_row_tiles = wide256 ? (int)tiles256 : (int)((row_end - row_begin + BM - 1) / BM);
+    const int groups = (a.n_row_tiles + 7) / 8;
+    dim3 grid((unsigned)(groups * 8 * a.n_q_tiles));
 #define LB_GEMM(M, AL) hipLaunchKernelGGL((gemm_filter_kernel<M, AL>), grid, dim3(GEMM_THREADS), 0, s, a)
 #define LB_GEMM_M(M)                 \
     do {                             \
-        if (mode == 2) LB_GEMM(M, 2); \
+        if (wide256) hipLaunchKernelGGL((gemm_filter_wide256_kernel<M>), grid, dim3(GEMM_THREADS), 0, s, a); \
+        else if (mode == 2) LB_GEMM(M, 2); \
         else if (mode == 1) LB_GEMM(M, 1); \
         else LB_GEMM(M, 0);           \
     } while (0)
@@ -489,3 +812,15 @@ void launch_gemm_filter(int metric, const float *X, const float *norm2, const fl
 }
 
 } // namespace lb
+
+#ifdef LB_DIAG
+extern "C" {
+int lb_debug_last_wide_rows(void) { return lb::g_last_wide_rows.load(); } // 128 or 256: the tile of the most recent non-boot launch_gemm_filter (0: none yet)
+// workgroups from which the 256-row body runs (negative: the compiled-in default); forgets the last launch's tile
+void lb_debug_set_wide256_min_tiles(int v)
+{
+    lb::g_wide256_min_tiles.store(v < 0 ? lb::kWide256MinTiles : v);
+    lb::g_last_wide_rows.store(0);
+}
+}
+#endif
