@@ -309,6 +309,40 @@ func (idx *HIPIndex) SetFilter(mask []byte) error {
 	return nil
 }
 
+// Remove takes the rows with these labels out of every later search: the ids given to Add, or row
+// positions when Add got none (ArrowHNSW.Delete / DeleteBatch, internal/store/arrow_hnsw.go:468-513).
+// Unknown ids, repeats and rows already removed are ignored.  It returns the number of rows newly
+// removed.  An index that was told needs no k*10 over-fetch (internal/store/hnsw_gpu.go:84-123).
+func (idx *HIPIndex) Remove(ids []int64) (int, error) {
+	idx.mu.Lock()
+	defer idx.mu.Unlock()
+	if idx.closed {
+		return 0, fmt.Errorf("index is closed")
+	}
+	if len(ids) == 0 {
+		return 0, nil
+	}
+	var removed C.int64_t
+	if rc := C.lb_gpu_index_remove(idx.h, C.int64_t(len(ids)), (*C.int64_t)(unsafe.Pointer(&ids[0])), &removed); rc != C.LB_OK {
+		return 0, hipError(idx.h, "remove", rc)
+	}
+	return int(removed), nil
+}
+
+// Compact gives the removed rows' HBM back to later Adds.  The survivors keep their order and their
+// ids; an index that was filled without ids labels by the new positions afterwards.
+func (idx *HIPIndex) Compact() error {
+	idx.mu.Lock()
+	defer idx.mu.Unlock()
+	if idx.closed {
+		return fmt.Errorf("index is closed")
+	}
+	if rc := C.lb_gpu_index_compact(idx.h, nil, 0); rc != C.LB_OK {
+		return hipError(idx.h, "compact", rc)
+	}
+	return nil
+}
+
 // Close releases HBM; idempotent.
 func (idx *HIPIndex) Close() error {
 	idx.mu.Lock()

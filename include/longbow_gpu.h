@@ -240,6 +240,52 @@ int lb_gpu_index_filter_int64(lb_gpu_index *h, const int64_t *column, int64_t n,
 int lb_gpu_index_filter_float32(lb_gpu_index *h, const float *column, int64_t n, float value, int op,
                                 const uint8_t *validity, int64_t validity_offset, int combine);
 
+/* Removal: rows leave the index, as ArrowHNSW.Delete / DeleteBatch put ids on a tombstone set (internal/store/arrow_hnsw.go:468-513),
+ * and the index knows: no search has to over-fetch and drop afterwards (SearchHybrid's k * 10, hnsw_gpu.go:84-123).  A removed row
+ * keeps its position (and its HBM) until lb_gpu_index_compact; it is live no more, and nothing but compaction undoes that.
+ *   remove       labels, the values Search returns: ids[row] when the index holds ids, else the row position.  With ids EVERY live
+ *                row whose id is in the set goes (two rows added under one id both go).  _device: the labels are in device
+ *                memory (on an index with ids they make a round trip through the host to be sorted; n is small beside ntotal).
+ *   remove_rows  row POSITIONS whether or not the index holds ids: the currency of rerank, refine and the code handles.
+ *   ignored      an unknown label, a position outside [0, ntotal), -1 (the padding of a result list), a label given twice and a
+ *                row already removed are ignored, not errors: the reference's Delete never fails.
+ *   n_removed    nullable; the number of rows this call newly removed.
+ *   errors       n == 0 is LB_OK; a NULL handle, n < 0, or n > 0 with a null pointer: LB_ERR_INVALID_ARG, answered before a device
+ *                is touched and with nothing written.
+ *   searches     every search entry point of the handle (host and device forms, _ctx, _f16, _i8, combined concurrent host
+ *                searches) answers the exact k-NN among the rows that are live AND pass the filter, in ascending (distance, row
+ *                position) order: bit for bit what a fresh index holding only the live rows, in their order, with ids = the old
+ *                labels and the same filter restricted to them would answer.  Fewer such rows than k: -1 / FLT_MAX padding.
+ *   filters      set_filter / filter_* keep taking ntotal values (removed rows included: positions do not move) and never
+ *                resurrect a removed row; set_filter(NULL) leaves the live rows visible.  Rows added later are live.
+ *   refine       treats a removed position as outside the index (it joins the -1 padding): a code handle's shortlist cannot
+ *                resurrect a deleted row.  It keeps ignoring the filter.
+ *   rerank       is left alone: it reports one distance per given position over the stored bytes, removed or not.
+ *   types        float32, float16 and int8 handles alike; no element data is touched.  The accelerator images stay as they are.
+ *   cost         a pass over the labels (positions) or over the index's ids (labels of an index with ids), then the row list is
+ *                rebuilt as after a filter call; searches then cost what they cost under a filter with the same visible rows.
+ * Exclusive against everything else on the handle, as add and the filter calls. */
+int lb_gpu_index_remove(lb_gpu_index *h, int64_t n, const int64_t *labels, int64_t *n_removed);
+int lb_gpu_index_remove_device(lb_gpu_index *h, int64_t n, const int64_t *d_labels, int64_t *n_removed);
+int lb_gpu_index_remove_rows(lb_gpu_index *h, int64_t n, const int64_t *rows, int64_t *n_removed);
+/* ntotal - ndeleted; 0 for a NULL handle */
+int64_t lb_gpu_index_nlive(const lb_gpu_index *h);
+/* removed rows the index still holds (ntotal counts them); 0 for a NULL handle */
+int64_t lb_gpu_index_ndeleted(const lb_gpu_index *h);
+
+/* Compaction: the removed rows leave physically and stably, survivor j being the j-th live row of before.  Afterwards
+ * ntotal == nlive and ndeleted == 0; an index with ids keeps every label; an index WITHOUT ids labels by the new positions, as
+ * FAISS's flat remove_ids does: the caller renumbers through old_rows.  A filter in force survives, its bytes move with the rows.
+ *   old_rows  nullable, room for cap >= nlive entries (else LB_ERR_INVALID_ARG with a last_error text and nothing changed):
+ *             receives each survivor's former position, ascending, for a code handle or a location table kept beside the index.
+ *   nothing removed: LB_OK and nothing changes (old_rows: 0, 1, ...).  Everything removed: the index is empty and takes adds again.
+ *   memory    mapped memory is kept and reused by later adds (hbm_bytes need not shrink).  The gather runs in place, in rounds
+ *             through a bounded scratch: no second copy of the corpus is ever resident.  The accelerator images are rebuilt.
+ *   failure   a refusal before the rows move (an allocation) leaves the index as it was; once they are in place nothing fails
+ *             the call.  A device fault while they move leaves the handle unusable, as it leaves the device.
+ * Exclusive against everything else on the handle. */
+int lb_gpu_index_compact(lb_gpu_index *h, int64_t *old_rows, int64_t cap);
+
 /* Per-search telemetry of the most recent search on this handle (for benches):
  * number of queries that needed the exact-scan fallback. */
 int64_t lb_gpu_index_last_fallbacks(const lb_gpu_index *h);
@@ -276,7 +322,8 @@ int lb_gpu_index_rerank_device(lb_gpu_index *h, const float *d_query, const int6
  *   queries   f32[nq][dim], on a float16 index too: the arithmetic is the f32 arithmetic on the widened rows, so the result is
  *             that of a float32 index holding the same values.
  *   rows      int64[nq][c] row POSITIONS, as for rerank.  The candidate set S_q of query q is the set of values of rows[q][.]
- *             inside [0, ntotal): anything else (the -1 padding of a short shortlist) is skipped, a value that occurs more than
+ *             inside [0, ntotal) that name a live row: anything else (the -1 padding of a short shortlist, a row that
+ *             lb_gpu_index_remove* has removed) is skipped, a value that occurs more than
  *             once counts once, and the order of the entries does not matter.  The index's row filter is ignored, as rerank
  *             ignores it (a filter on the code handle has already shaped the shortlist).
  *   result    dist / labels [nq][k]: the first k members of S_q in ascending (distance, row) order, the distance being the

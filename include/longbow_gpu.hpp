@@ -135,6 +135,43 @@ class Index {
                                                   dist.data(), score.data()));
     }
 
+    // Removal (lb_gpu_index_remove / _remove_rows): labels as Search returns them, or row positions.  Unknown values, repeats
+    // and rows already removed are ignored; *removed (nullable) gets the number of rows newly removed.
+    Error Remove(const std::vector<int64_t> &ids, int64_t *removed = nullptr)
+    {
+        std::unique_lock<std::shared_mutex> g(mu_);
+        if (closed_) return {LB_ERR_CLOSED, "index is closed"};
+        if (removed) *removed = 0;
+        if (ids.empty()) return {};
+        return wrap("remove", lb_gpu_index_remove(h_, (int64_t)ids.size(), ids.data(), removed));
+    }
+    Error RemoveRows(const std::vector<int64_t> &rows, int64_t *removed = nullptr)
+    {
+        std::unique_lock<std::shared_mutex> g(mu_);
+        if (closed_) return {LB_ERR_CLOSED, "index is closed"};
+        if (removed) *removed = 0;
+        if (rows.empty()) return {};
+        return wrap("remove_rows", lb_gpu_index_remove_rows(h_, (int64_t)rows.size(), rows.data(), removed));
+    }
+    // The removed rows leave physically; old_rows: every survivor's former position (an index without ids labels by the new ones)
+    Error Compact(std::vector<int64_t> &old_rows)
+    {
+        std::unique_lock<std::shared_mutex> g(mu_);
+        if (closed_) return {LB_ERR_CLOSED, "index is closed"};
+        old_rows.assign((size_t)lb_gpu_index_nlive(h_), 0);
+        return wrap("compact", lb_gpu_index_compact(h_, old_rows.data(), (int64_t)old_rows.size()));
+    }
+    int64_t NLive()
+    {
+        std::shared_lock<std::shared_mutex> g(mu_);
+        return closed_ ? 0 : lb_gpu_index_nlive(h_);
+    }
+    int64_t NDeleted()
+    {
+        std::shared_lock<std::shared_mutex> g(mu_);
+        return closed_ ? 0 : lb_gpu_index_ndeleted(h_);
+    }
+
     Error Close() // idempotent
     {
         std::unique_lock<std::shared_mutex> g(mu_);

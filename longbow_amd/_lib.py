@@ -92,6 +92,12 @@ SIGNATURES = [
     ("lb_gpu_index_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_index_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_index_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
+    ("lb_gpu_index_remove", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_index_remove_device", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_index_remove_rows", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_index_nlive", _i64, [_vp]),
+    ("lb_gpu_index_ndeleted", _i64, [_vp]),
+    ("lb_gpu_index_compact", _i, [_vp, _vp, _i64]),
     ("lb_gpu_index_last_fallbacks", _i64, [_vp]),
     ("lb_gpu_index_fused_giveups", _i64, [_vp]),
     ("lb_gpu_index_last_route", _i, [_vp]),
@@ -384,6 +390,7 @@ DIAG_SIGNATURES = [
     ("lb_debug_cand_geometry", None, [_i, C.POINTER(C.c_int), C.POINTER(C.c_uint)]),
     ("lb_debug_last_wide_rows", _i, []),
     ("lb_debug_set_wide256_min_tiles", None, [_i]),
+    ("lb_debug_set_compact_round_rows", None, [C.c_longlong]),
 ]
 _diag = None
 

@@ -26,6 +26,8 @@ constexpr size_t kStageBytes = 32u << 20; // pinned staging slab (x2)
 // Add batches of at least this many bytes pin the caller's buffer instead of staging it (0 = never)
 std::atomic<long long> g_add_register_min{(long long)lb_tunable("LB_ADD_REGISTER_MIN_MB", 64) << 20};
 
+} // namespace
+
 void drop_f16_image(lb_gpu_index *h)
 {
     h->d_Xh.reset();
@@ -44,9 +46,9 @@ void drop_split_image(lb_gpu_index *h)
 }
 
 // Make room for `need` rows.  The corpus itself grows in place (VmmBuf); only the small per-row side
-// arrays (norms, ids, mask: 17 B per row) are reallocated geometrically and copied.  Without VMM the
+// arrays (norms, ids, mask, liveness: 18 B per row) are reallocated geometrically and copied.  Without VMM the
 // corpus follows the same malloc + copy scheme (needs old + new resident at once).
-int grow(lb_gpu_index *h, int64_t need)
+static int grow(lb_gpu_index *h, int64_t need)
 {
     const size_t row_bytes = (size_t)h->dim * h->elem_bytes();
     int64_t cap = std::max<int64_t>(need, h->capacity * 2);
@@ -80,7 +82,7 @@ int grow(lb_gpu_index *h, int64_t need)
     DevBuf<char> nx;
     DevBuf<float> n2, rn;
     DevBuf<int64_t> ni;
-    DevBuf<uint8_t> nm;
+    DevBuf<uint8_t> nm, nl;
     const bool grow_x = !h->vmm.ok && cap > h->x_rows_cap;
     const bool grow_side = cap > h->capacity;
     if (grow_x) nx.alloc((size_t)cap * row_bytes);
@@ -89,6 +91,7 @@ int grow(lb_gpu_index *h, int64_t need)
         rn.alloc((size_t)cap);
         ni.alloc((size_t)cap);
         nm.alloc((size_t)cap);
+        nl.alloc(((size_t)cap + 3) & ~(size_t)3); // (whole words: launch_remove_rows)
     }
     if (h->n > 0) {
         if (nx) LB_HIP(hipMemcpyAsync(nx.get(), h->d_X, (size_t)h->n * row_bytes, hipMemcpyDeviceToDevice, h->add_stream));
@@ -97,6 +100,7 @@ int grow(lb_gpu_index *h, int64_t need)
             LB_HIP(hipMemcpyAsync(rn.get(), h->d_rnorm.get(), (size_t)h->n * sizeof(float), hipMemcpyDeviceToDevice, h->add_stream));
             LB_HIP(hipMemcpyAsync(ni.get(), h->d_ids.get(), (size_t)h->n * sizeof(int64_t), hipMemcpyDeviceToDevice, h->add_stream));
             LB_HIP(hipMemcpyAsync(nm.get(), h->d_mask.get(), (size_t)h->n, hipMemcpyDeviceToDevice, h->add_stream));
+            LB_HIP(hipMemcpyAsync(nl.get(), h->d_live.get(), (size_t)h->n, hipMemcpyDeviceToDevice, h->add_stream));
         }
         LB_HIP(hipStreamSynchronize(h->add_stream));
     }
@@ -110,6 +114,7 @@ int grow(lb_gpu_index *h, int64_t need)
         h->d_rnorm = std::move(rn);
         h->d_ids = std::move(ni);
         h->d_mask = std::move(nm);
+        h->d_live = std::move(nl);
         h->capacity = cap;
     }
     drop_split_image(h); // the mirror is rebuilt at the new capacity by the next sync_split_image
@@ -117,14 +122,11 @@ int grow(lb_gpu_index *h, int64_t need)
     return LB_OK;
 }
 
-void sync_split_image(lb_gpu_index *h);
-void sync_f16_image(lb_gpu_index *h);
-
 // grow(), giving the accelerator copies back first when the device is full.  The fp16 copy (half the corpus's bytes again)
 // and the split-bf16 image (all of them again) only speed searches up; the rows are the index.  An Add / reserve that runs
 // out of memory while either is resident frees them and tries once more before it reports LB_ERR_OOM; the copy is then
 // taken again only when twice the usual margin is free (sync_f16_image), so an index at the edge does not rebuild it per Add.
-int grow_or_shed(lb_gpu_index *h, int64_t need)
+static int grow_or_shed(lb_gpu_index *h, int64_t need)
 {
     try {
         return grow(h, need);
@@ -168,14 +170,26 @@ void rebuild_rowmap(lb_gpu_index *h)
     h->rowmap_on = h->n_visible * 100 <= h->n * (int64_t)max_pct;
 }
 
-__global__ void iota_ids_kernel(int64_t *ids, int64_t start, int64_t n)
+static __global__ void iota_ids_kernel(int64_t *ids, int64_t start, int64_t n)
 {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) ids[start + i] = start + i;
 }
 
-// Rows [h->n, h->n + n) are already in d_X; finish the append (norms, ids, mask).
-void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool ids_on_device)
+// what the norm statistics (d_maxnorm2's two words: max ||x||^2 and the smallest non-zero ||x||^2, as float bits) say of the rows
+void set_norm_flags(lb_gpu_index *h, const uint32_t nbits[2])
+{
+    const uint32_t maxbits = nbits[0]; // >= +inf <=> a row with an inf or NaN component
+    h->nonfinite = maxbits >= 0x7f800000u;
+    // fp16 single-product candidates: no element may overflow fp16 (|x_i| <= ||x|| <= 2^13) and the smallest non-zero
+    // row norm bounds the subnormal rounding term of the contraction's error bound (>= 2^-6: kernels_gemm_tall16.hip)
+    const float mx = __builtin_bit_cast(float, maxbits), mn = __builtin_bit_cast(float, nbits[1]);
+    h->f16_ok = !h->nonfinite && mx <= 67108864.0f /* 2^26 */ && (nbits[1] == 0x7f800000u || mn >= 0.000244140625f /* 2^-12 */);
+    h->norm_spread = !h->nonfinite && nbits[1] != 0x7f800000u && mx > 256.0f * mn;
+}
+
+// Rows [h->n, h->n + n) are already in d_X; finish the append (norms, ids, mask, liveness).
+static void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool ids_on_device)
 {
     hipStream_t s = h->add_stream;
     const int64_t start = h->n;
@@ -196,18 +210,12 @@ void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool ids_on_
         hipLaunchKernelGGL(iota_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->d_ids.get(), start, n);
     }
     LB_HIP(hipMemsetAsync(h->d_mask.get() + start, 1, (size_t)n, s));
-    uint32_t nbits[2] = {0, 0}; // max ||x||^2 so far, as float bits: >= +inf <=> a row with an inf or NaN component
+    LB_HIP(hipMemsetAsync(h->d_live.get() + start, 0xff, (size_t)n, s)); // appended rows are live
+    uint32_t nbits[2] = {0, 0};
     LB_HIP(hipMemcpyAsync(nbits, h->d_maxnorm2.get(), sizeof nbits, hipMemcpyDeviceToHost, s));
     LB_HIP(hipStreamSynchronize(s));
     LB_LAUNCH_CHECK();
-    const uint32_t maxbits = nbits[0];
-    h->nonfinite = maxbits >= 0x7f800000u;
-    {   // fp16 single-product candidates: no element may overflow fp16 (|x_i| <= ||x|| <= 2^13) and the smallest non-zero
-        // row norm bounds the subnormal rounding term of the contraction's error bound (>= 2^-6: kernels_gemm_tall16.hip)
-        const float mx = __builtin_bit_cast(float, maxbits), mn = __builtin_bit_cast(float, nbits[1]);
-        h->f16_ok = !h->nonfinite && mx <= 67108864.0f /* 2^26 */ && (nbits[1] == 0x7f800000u || mn >= 0.000244140625f /* 2^-12 */);
-        h->norm_spread = !h->nonfinite && nbits[1] != 0x7f800000u && mx > 256.0f * mn;
-    }
+    set_norm_flags(h, nbits);
     h->n += n; // the rows are committed from here on: nothing below may fail the call (a retry would duplicate them)
     try {
         sync_split_image(h);
@@ -339,8 +347,6 @@ void sync_f16_image(lb_gpu_index *h)
     }
 }
 
-} // namespace
-
 template <typename T>
 static int filter_column(lb_gpu_index *h, const T *column, int64_t n, T value, int op, const uint8_t *validity,
                          int64_t voff, int combine)
@@ -351,7 +357,7 @@ static int filter_column(lb_gpu_index *h, const T *column, int64_t n, T value, i
         h->set_error("filter column has %lld values, index has %lld rows", (long long)n, (long long)h->n);
         return LB_ERR_INVALID_ARG;
     }
-    if (n == 0) { h->has_mask = true; h->rowmap_on = false; return LB_OK; }
+    if (n == 0) { h->has_mask = h->has_filter = true; h->rowmap_on = false; return LB_OK; }
     Lease dcol, dval; // column (and validity bitmap) go up through pooled buffers on the index's own stream
     return guard(h, h->add_stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
@@ -370,9 +376,11 @@ static int filter_column(lb_gpu_index *h, const T *column, int64_t n, T value, i
             launch_match_int64(reinterpret_cast<const int64_t *>(d_col), n, (int64_t)value, op, d_val, voff, h->d_mask.get(), comb, h->add_stream);
         else
             launch_match_float32(reinterpret_cast<const float *>(d_col), n, (float)value, op, d_val, voff, h->d_mask.get(), comb, h->add_stream);
+        // (a replaced mask knows nothing of the removed rows; one that was ANDed into held them as zeros already)
+        if (!comb && h->n_dead > 0) launch_and_bytes(h->d_mask.get(), h->d_live.get(), n, h->add_stream);
         LB_LAUNCH_CHECK();
         LB_HIP(hipStreamSynchronize(h->add_stream));
-        h->has_mask = true;
+        h->has_mask = h->has_filter = true;
         rebuild_rowmap(h);
         return LB_OK;
     });
@@ -478,7 +486,7 @@ int64_t lb_gpu_index_hbm_bytes(const lb_gpu_index *h)
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_index *>(h)->mu);
     const int pd = corpus_f16_plane_dims();
     int64_t b = h->vmm.ok ? (int64_t)h->vmm.mapped : h->x_rows_cap * (int64_t)h->dim * (int64_t)h->elem_bytes();
-    b += h->capacity * (int64_t)(2 * sizeof(float) + sizeof(int64_t) + 1); // norms, inverse norms, ids, mask
+    b += h->capacity * (int64_t)(2 * sizeof(float) + sizeof(int64_t) + 2); // norms, inverse norms, ids, mask, liveness
     if (h->d_rowmap) b += (int64_t)h->d_rowmap.count() * (int64_t)sizeof(uint32_t);
     if (h->d_Xs) b += h->capacity * (int64_t)h->dim * (int64_t)sizeof(float);
     if (h->d_Xh) b += h->xh_cap * (int64_t)((h->dim + pd - 1) / pd * pd) * 2;
@@ -681,12 +689,26 @@ int lb_gpu_index_set_filter(lb_gpu_index *h, const uint8_t *mask, int64_t n)
 {
     if (!h) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
-    if (!mask) { h->has_mask = false; h->rowmap_on = false; h->smap_valid = false; return LB_OK; }
+    if (!mask && h->n_dead == 0) { h->has_mask = h->has_filter = false; h->rowmap_on = false; h->smap_valid = false; return LB_OK; }
+    if (!mask) { // removed rows stay hidden: the view is the live rows (d_mask holds a cleared filter's bytes: recomposed)
+        return guard(h, h->add_stream, [&]() -> int {
+            LB_HIP(hipSetDevice(h->device));
+            LB_HIP(hipMemcpyAsync(h->d_mask.get(), h->d_live.get(), (size_t)h->n, hipMemcpyDeviceToDevice, h->add_stream));
+            h->has_filter = false;
+            h->has_mask = true;
+            rebuild_rowmap(h);
+            return LB_OK;
+        });
+    }
     if (n != h->n) { h->set_error("filter mask has %lld bytes, index has %lld rows", (long long)n, (long long)h->n); return LB_ERR_INVALID_ARG; }
     return guard(h, h->add_stream, [&]() -> int {
         LB_HIP(hipSetDevice(h->device));
         if (n > 0) LB_HIP(hipMemcpy(h->d_mask.get(), mask, (size_t)n, hipMemcpyHostToDevice));
-        h->has_mask = true;
+        if (h->n_dead > 0) { // the effective mask: the caller's bytes AND live
+            launch_and_bytes(h->d_mask.get(), h->d_live.get(), n, h->add_stream);
+            LB_LAUNCH_CHECK();
+        }
+        h->has_mask = h->has_filter = true;
         rebuild_rowmap(h);
         return LB_OK;
     });

@@ -45,7 +45,7 @@ __device__ __forceinline__ void bitonic_sort_u32(uint32_t *sh, uint32_t P, int t
     }
 }
 
-// One workgroup per query: the c entries, those outside [0, ntotal) as RF_NONE, are sorted in LDS (P = next_pow2(c) words, RF_NONE
+// One workgroup per query: the c entries, those outside [0, ntotal) or removed (a.live) as RF_NONE, are sorted in LDS (P = next_pow2(c) words, RF_NONE
 // sorts last); a position is kept when it holds a row and differs from the one before it; the kept ones go to list[q] in order,
 // each thread placing the run of positions it owns behind the count of those before it.  len[q] <= c.
 // LDS: u32[P] | wave sums u32[NT / 64]
@@ -61,7 +61,7 @@ __global__ __launch_bounds__(NT) void refine_prepare_kernel(RefineBatch a, uint3
         uint32_t v = RF_NONE;
         if (i < (uint32_t)a.c) {
             const int64_t r = rows[i];
-            if (r >= 0 && r < a.ntotal) v = (uint32_t)r;
+            if (r >= 0 && r < a.ntotal && (!a.live || a.live[r])) v = (uint32_t)r;
         }
         rsh[i] = v;
     }

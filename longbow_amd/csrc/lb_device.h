@@ -692,6 +692,18 @@ int64_t compact_scratch_words(int64_t n);
 void launch_compact_mask(const uint8_t *mask, int64_t n, uint32_t *rowmap, uint32_t *scratch, hipStream_t s);
 // its middle step alone: counts[0, nb) -> their exclusive prefix in place, counts[nb] = the total (one workgroup)
 void launch_compact_offsets(uint32_t *counts, int64_t nb, hipStream_t s);
+// removal and compaction of the flat index (kernels_remove.hip).  live: a byte per row, non-zero = live, held in whole words;
+// mask: the index's effective mask.  Both lose the bytes of the rows a call removes; *removed (zero before the launch) gains the
+// number of rows that were live before it, each counted once however often it is named.
+// rows[cnt]: positions; anything outside [0, ntotal) is skipped
+void launch_remove_rows(const int64_t *rows, int64_t cnt, int64_t ntotal, uint8_t *live, uint8_t *mask, uint32_t *removed, hipStream_t s);
+// set[nset]: ids, ascending and distinct; every live row r with ids[r] in the set goes
+void launch_remove_ids(const int64_t *ids, int64_t ntotal, const int64_t *set, int64_t nset, uint8_t *live, uint8_t *mask,
+                       uint32_t *removed, hipStream_t s);
+// *out (0xffffffff before the launch) = the first row whose live byte is zero
+void launch_first_dead(const uint8_t *live, int64_t ntotal, uint32_t *out, hipStream_t s);
+// dst row j = src row map[j] for j < cnt, rows of row_bytes bytes; dst and src must not overlap
+void launch_gather_rows(const void *src, const uint32_t *map, int64_t cnt, size_t row_bytes, void *dst, int device, hipStream_t s);
 // reciprocal-rank fusion of two ranked id lists per query (kernels_filter.hip)
 void launch_rrf(int64_t nq, int kd, const int64_t *dense, int ks, const int64_t *sparse, int k, int limit,
                 int64_t *out_ids, float *out_scores, hipStream_t s);

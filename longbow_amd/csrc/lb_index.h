@@ -1,5 +1,6 @@
 // lb_index.h -- what the translation units behind the index's C ABI share (index.hip: the handle and its storage;
-// index_search.hip: workspaces, routes and the search drivers; simd_api.hip: the re-rank entry points): the handle, the pooled
+// index_remove.hip: removal and compaction; index_search.hip: workspaces, routes and the search drivers; simd_api.hip: the re-rank
+// entry points): the handle, the pooled
 // per-search structs, the row view and the few functions that cross files.  The handle's lock, error text and the shell of its
 // entry points (guard) are lb_handle.h's, as for every other handle.  Internal: nothing here is part of the ABI.
 #pragma once
@@ -177,8 +178,15 @@ struct lb_gpu_index : HandleCore {
     std::atomic<int> f16_skip{0}, f16_span{16};
     DevBuf<int64_t> d_ids;
     bool has_ids = false;
+    // d_mask is the EFFECTIVE mask, (the caller's filter) AND live: row_view and every search read it alone.  has_filter: a
+    // caller's filter is set; has_mask: there is one, or rows have been removed (n_dead > 0)
     DevBuf<uint8_t> d_mask;
-    bool has_mask = false;
+    bool has_mask = false, has_filter = false;
+    // removal (index_remove.hip): a byte per row, 0xff = live, 0 = removed (all ones, so that the bytewise AND with a filter keeps
+    // whatever non-zero byte the caller gave); removed rows keep their positions until lb_gpu_index_compact.  No filter call
+    // writes it.  Allocated in whole words: the position form clears its bytes by atomics on the words
+    DevBuf<uint8_t> d_live;
+    int64_t n_dead = 0;
     // ascending list of the rows the mask leaves visible (rebuilt whenever the mask or the corpus
     // changes); searches walk it instead of the corpus when the filter is selective enough
     DevBuf<uint32_t> d_rowmap, d_cscratch;
@@ -284,5 +292,13 @@ LB_INTERNAL void cand_geometry(int k, int &kc, uint32_t &cap);
 // the index's workspace pool (index_search.hip)
 LB_INTERNAL std::unique_ptr<Workspace> acquire_ws(lb_gpu_index *h, int nq, uint32_t cap);
 LB_INTERNAL void release_ws(lb_gpu_index *h, std::unique_ptr<Workspace> w);
+// index.hip, for index_remove.hip: the row list from d_mask, the accelerator images, and the flags finish_add derives from the
+// norm statistics in d_maxnorm2 (the caller holds the exclusive lock)
+LB_INTERNAL void rebuild_rowmap(lb_gpu_index *h);
+LB_INTERNAL void drop_f16_image(lb_gpu_index *h);
+LB_INTERNAL void drop_split_image(lb_gpu_index *h);
+LB_INTERNAL void sync_split_image(lb_gpu_index *h);
+LB_INTERNAL void sync_f16_image(lb_gpu_index *h);
+LB_INTERNAL void set_norm_flags(lb_gpu_index *h, const uint32_t nbits[2]);
 // call: the element type of the entry point (0 float32, 1 _f16, 2 _i8); LB_OK, or the error an index of another type reports (index.hip)
 LB_INTERNAL int dtype_mismatch(lb_gpu_index *h, int call);

@@ -15,9 +15,10 @@ struct RefineBatch {
     int nq;
     const int64_t *rows; // [nq][c] the caller's shortlists: any values, any order
     int c;
-    uint32_t *list;      // [nq][c]: list[q][0 .. len[q]) = the distinct entries of rows[q] inside [0, ntotal), ascending
+    uint32_t *list;      // [nq][c]: list[q][0 .. len[q]) = the distinct entries of rows[q] inside [0, ntotal) (and live), ascending
     uint32_t *len;       // [nq]
     uint64_t *keys;      // [nq][c]: keys[q][i] = pack_entry(distance, list[q][i]) for i < len[q]
+    const uint8_t *live; // nullable: [ntotal], a row with a zero byte has been removed and counts as outside the index
 };
 
 // list and len of every query from rows

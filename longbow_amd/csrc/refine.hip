@@ -79,6 +79,7 @@ int lb_gpu_index_refine_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_q
         a.X = h->d_X;
         a.D = h->dim;
         a.ntotal = h->n;
+        a.live = h->n_dead > 0 ? h->d_live.get() : nullptr; // a removed position joins the padding
         a.c = (int)c;
         float *d_qna = nullptr;
         lease_layout(sc, h->device, [&](Carve cv) {

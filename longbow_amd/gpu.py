@@ -301,6 +301,51 @@ class Index:
             raise TypeError(f"unsupported filter column type {column.dtype} (int64 / float32)")
         _lib.check(rc, self._h, lib=self._lib)
 
+    # -- removal (lb_gpu_index_remove*, lb_gpu_index_compact) -------------------------
+    def _remove(self, entry, values):
+        values = np.ascontiguousarray(values, np.int64).reshape(-1)
+        removed = C.c_int64(0)
+        _lib.check(entry(self._h, values.size, values.ctypes.data if values.size else None, C.byref(removed)), self._h, lib=self._lib)
+        return int(removed.value)
+
+    def Remove(self, ids):
+        """Remove the rows with these labels (the values Search returns: the ids given to Add, else row positions) -> the number
+        of rows newly removed.  Every live row under a given id goes; unknown labels, -1, repeats and rows already removed are
+        ignored (ArrowHNSW.Delete never fails).  Searches stop returning them at once; the rows keep their positions and their
+        memory until Compact()."""
+        self._live()
+        return self._remove(self._lib.lb_gpu_index_remove, ids)
+
+    def remove_rows(self, rows):
+        """Remove by row position, whether or not the index holds ids (the currency of Rerank, Refine and the code handles)"""
+        self._live()
+        return self._remove(self._lib.lb_gpu_index_remove_rows, rows)
+
+    def remove_device(self, n, d_labels):
+        """Remove() of n int64 labels in device memory"""
+        self._live()
+        removed = C.c_int64(0)
+        _lib.check(self._lib.lb_gpu_index_remove_device(self._h, n, d_labels, C.byref(removed)), self._h, lib=self._lib)
+        return int(removed.value)
+
+    def Compact(self):
+        """Drop the removed rows physically, keeping the survivors' order -> old_rows int64 [nlive]: each survivor's former
+        position.  ids are kept; an index without ids labels by the new positions from here on."""
+        self._live()
+        old = np.empty(self.nlive(), np.int64)
+        _lib.check(self._lib.lb_gpu_index_compact(self._h, old.ctypes.data, old.size), self._h, lib=self._lib)
+        return old
+
+    def nlive(self):
+        """rows a search can return without a filter: ntotal - ndeleted()"""
+        self._live()
+        return int(self._lib.lb_gpu_index_nlive(self._h))
+
+    def ndeleted(self):
+        """removed rows the index still holds, until Compact()"""
+        self._live()
+        return int(self._lib.lb_gpu_index_ndeleted(self._h))
+
     def set_profiling(self, on):
         self._live()
         _lib.check(self._lib.lb_gpu_index_set_profiling(self._h, 1 if on else 0), self._h, lib=self._lib)

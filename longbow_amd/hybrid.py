@@ -41,7 +41,8 @@ def fuse_batch(dense_ids, sparse_ids, k=60, limit=10, device=0):
 
 
 def search_hybrid_candidates(index, query, k, is_live=None):
-    """candidateCount = min(k*10, Len); first k live candidates, GPU order trusted (hnsw_gpu.go:84-123)"""
+    """candidateCount = min(k*10, Len); first k live candidates, GPU order trusted (hnsw_gpu.go:84-123).  An index that was told
+    of the deletions (gpu.Index.Remove) needs no over-fetch: its Search(query, k) is the exact k nearest live rows."""
     count = min(k * 10, index.ntotal)
     if count <= 0:
         return np.empty(0, np.int64), np.empty(0, np.float32)
