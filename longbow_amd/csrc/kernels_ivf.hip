@@ -5,11 +5,14 @@
 // The rows stay in insertion order and a list is an ascending array of row numbers, so the list scan is scan_kernel's walk of a
 // row list (kernels_scan.hip, MAPPED) with a list per (query, probe slot): each lane owns one row and carries that row's f32
 // accumulator chain(s) across D in the reference's order (lb_exact.h), rows staged through LDS in coalesced 16-byte pieces.
+// The work lookup and the grid rule are lb_list_scan.h's, shared with the other list scans; the walk over (tile, chunk) is stated
+// there too and restated in ivf_scan_kernel for the reason given at its loop.
 // Nothing is admitted against a threshold: every scanned row leaves one key, and ivf_select_kernel takes the k smallest.
 // No FMA contraction here.
 #include "lb_device.h"
 #include "lb_exact.h"
 #include "lb_ivf.h"
+#include "lb_list_scan.h"
 #include "lb_select.h"
 
 #include <float.h>
@@ -23,43 +26,17 @@ constexpr int IV_ROWS = 128;       // rows per tile == threads per workgroup
 constexpr int IV_DK = 64;          // floats per row per stage
 constexpr int IV_LD = IV_DK + 4;   // padded LDS row stride (floats): conflict-free ds_read_b128
 constexpr int IV_GEN_ROWS = 256;   // rows per tile of the generic form
-constexpr unsigned IV_PAIRS_Y = 32768; // (query, probe) pairs along grid dimension y; the rest along z (both < 65536)
 
-// What a workgroup of the list scan works on: pair = (query, probe slot), wave-uniform.  false: nothing to do.
-struct IvfWork {
-    int q;
-    uint32_t len;         // rows of the list
-    const uint32_t *rmap; // the list's rows, ascending
-    uint64_t *out;        // the list's keys of this query
-};
-__device__ __forceinline__ bool ivf_work(const IvfBatch &a, int tile_rows, IvfWork &w)
-{
-    const int64_t pair = (int64_t)blockIdx.y + (int64_t)blockIdx.z * gridDim.y;
-    if (pair >= (int64_t)a.nq * a.np) return false;
-    w.q = (int)(pair / a.np);
-    const int p = (int)(pair % a.np);
-    const int64_t l = a.probes[pair];
-    if (l < 0 || l >= a.L.nlist) return false;
-    const uint32_t off = a.L.off[l];
-    w.len = a.L.off[l + 1] - off;
-    if ((uint64_t)blockIdx.x * (uint32_t)tile_rows >= w.len) return false; // (an empty list among them)
-    const uint32_t seg = a.seg[(int64_t)w.q * (a.np + 1) + p];
-    if ((int64_t)seg + w.len > a.pmax) return false; // never with distinct probes: the keys of a query stay inside its pmax
-    w.rmap = a.L.rows + off;
-    w.out = a.keys + (int64_t)w.q * a.pmax + seg;
-    return true;
-}
-
-// Work = (query, probe slot, 128-row tile of that list); a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of
-// its list.  The (tile, chunk) sequence is one flat pipeline: one LDS stage [rows | query chunk] plus a register-held prefetch
-// of the next one (34.6 KB, 4 workgroups per CU).  D % 4 == 0, X and Q 16-byte aligned.
+// Work = (query, probe slot, 128-row tile of that list), found as lb_list_scan.h states and walked as it states, in this
+// kernel's own text (below).  A stage is [rows | query chunk] (34.6 KB with the register-held prefetch of the next one, 4
+// workgroups per CU).  D % 4 == 0, X and Q 16-byte aligned.
 template <int METRIC, int ORDER>
 __global__ __launch_bounds__(IV_ROWS) void ivf_scan_kernel(IvfBatch a)
 {
     constexpr int STAGE_F = IV_ROWS * IV_LD + IV_DK;
     __shared__ __attribute__((aligned(16))) float lds[STAGE_F];
-    IvfWork w;
-    if (!ivf_work(a, IV_ROWS, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a, IV_ROWS, w)) return;
     const int tid = threadIdx.x;
     const int D = a.D;
     const int nchunks = (D + IV_DK - 1) / IV_DK;
@@ -118,6 +95,10 @@ __global__ __launch_bounds__(IV_ROWS) void ivf_scan_kernel(IvfBatch a)
         pending = false;
     };
 
+    // walk_list_tiles' walk (lb_list_scan.h) in this kernel's own text, kept in step with it by hand.  Built over the shared
+    // walk the six instantiations came out 4 - 68 instructions different (same registers, LDS and occupancy), and three of 24
+    // scan-slot rows missed the rule of LABNOTES R34.1, each by less than 1 us or 0.3 %: <L2, SEQ> and <cos, SEQ> at 1 query x
+    // 8 probes, <dot, UNROLL4> at 1024 x 8.
     uint32_t tile = blockIdx.x;
     int c = 0;
     load_stage(tile, 0);
@@ -168,8 +149,8 @@ __global__ __launch_bounds__(IV_ROWS) void ivf_scan_kernel(IvfBatch a)
 template <int METRIC, int ORDER>
 __global__ __launch_bounds__(IV_GEN_ROWS) void ivf_scan_generic_kernel(IvfBatch a)
 {
-    IvfWork w;
-    if (!ivf_work(a, IV_GEN_ROWS, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a, IV_GEN_ROWS, w)) return;
     const int D = a.D;
     const float *q = a.Q + (int64_t)w.q * D;
     const float na = METRIC == METRIC_COS ? a.qna[w.q] : 0.f;
@@ -181,34 +162,16 @@ __global__ __launch_bounds__(IV_GEN_ROWS) void ivf_scan_generic_kernel(IvfBatch 
     }
 }
 
-template <int METRIC, int ORDER>
-static void launch_ivf_scan_mo(const IvfBatch &a, bool staged, dim3 grid, hipStream_t s)
-{
-    if (staged) hipLaunchKernelGGL((ivf_scan_kernel<METRIC, ORDER>), grid, dim3(IV_ROWS), 0, s, a);
-    else hipLaunchKernelGGL((ivf_scan_generic_kernel<METRIC, ORDER>), grid, dim3(IV_GEN_ROWS), 0, s, a);
-}
-
 void launch_ivf_scan(int metric, int order, const IvfBatch &a, int64_t maxlen, hipStream_t s)
 {
     const int64_t pairs = (int64_t)a.nq * a.np;
     if (pairs <= 0 || maxlen <= 0) return;
     const bool staged = a.D % 4 == 0 && ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.Q)) & 15) == 0;
-    // tiles along x: enough workgroups to fill the chip (256 CUs, 4 workgroups each) four times over and no more; a workgroup
-    // walks the rest of its list's tiles itself
-    const int64_t tiles = (maxlen + (staged ? IV_ROWS : IV_GEN_ROWS) - 1) / (staged ? IV_ROWS : IV_GEN_ROWS);
-    const int64_t gx = std::min<int64_t>(tiles, std::max<int64_t>(1, (4096 + pairs - 1) / pairs));
-    const unsigned gy = (unsigned)std::min<int64_t>(pairs, IV_PAIRS_Y);
-    const unsigned gz = (unsigned)((pairs + gy - 1) / gy); // <= 1024 queries x 65536 lists / 32768 = 2048
-    const dim3 grid((unsigned)gx, gy, gz);
-#define LB_IVF(M)                                                               \
-    do {                                                                        \
-        if (order == ORDER_UNROLL4) launch_ivf_scan_mo<M, ORDER_UNROLL4>(a, staged, grid, s); \
-        else launch_ivf_scan_mo<M, ORDER_SEQ>(a, staged, grid, s);              \
-    } while (0)
-    if (metric == METRIC_L2) LB_IVF(METRIC_L2);
-    else if (metric == METRIC_COS) LB_IVF(METRIC_COS);
-    else LB_IVF(METRIC_DOT);
-#undef LB_IVF
+    const dim3 grid = ivf_scan_grid(pairs, maxlen, staged ? IV_ROWS : IV_GEN_ROWS);
+    with_metric_order(metric, order, [&](auto m, auto o) {
+        if (staged) hipLaunchKernelGGL((ivf_scan_kernel<decltype(m)::value, decltype(o)::value>), grid, dim3(IV_ROWS), 0, s, a);
+        else hipLaunchKernelGGL((ivf_scan_generic_kernel<decltype(m)::value, decltype(o)::value>), grid, dim3(IV_GEN_ROWS), 0, s, a);
+    });
 }
 
 // ---- plan -----------------------------------------------------------------------------------------------------------------

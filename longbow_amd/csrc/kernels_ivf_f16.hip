@@ -1,13 +1,15 @@
 // kernels_ivf_f16.hip -- the list scan of an IVF-Flat handle whose rows are float16 (ivf.hip; semantics in include/longbow_gpu.h,
-// lb_gpu_ivf_new_f16).  The work decomposition is ivf_scan_kernel's (kernels_ivf.hip): a workgroup takes a (query, probe slot)
+// lb_gpu_ivf_new_f16).  The work decomposition is the list scans' (lb_list_scan.h): a workgroup takes a (query, probe slot)
 // pair and walks 128-row tiles of that list, one lane owns one row and carries that row's f32 accumulator chain(s) across D in the
-// reference's order (lb_exact.h).  The staging differs: a stage holds 128 elements of every row, which is the f32 kernel's 256 B
-// of a row and so its bytes in flight, and the rows stay fp16 in LDS; a lane widens its row's elements to f32 as it reads them,
-// which is exact, so the chains see what they see over the widened rows and the keys are the f32 scan's bit for bit.
+// reference's order (lb_exact.h).  The staging differs from ivf_scan_kernel's (kernels_ivf.hip): a stage holds 128 elements of
+// every row, which is the f32 kernel's 256 B of a row and so its bytes in flight, and the rows stay fp16 in LDS; a lane widens
+// its row's elements to f32 as it reads them, which is exact, so the chains see what they see over the widened rows and the
+// keys are the f32 scan's bit for bit.
 // No FMA contraction here.
 #include "lb_device.h"
 #include "lb_exact.h"
 #include "lb_ivf_f16.h"
+#include "lb_list_scan.h"
 #include "lb_select.h"
 
 #include <algorithm>
@@ -20,44 +22,18 @@ constexpr int IH_ROWS = 128;       // rows per tile == threads per workgroup
 constexpr int IH_DK = 128;         // halves per row per stage: 256 B
 constexpr int IH_LD = IH_DK + 8;   // padded LDS row stride (halves): 68 dwords, the f32 tile's, conflict-free ds_read_b128
 constexpr int IH_GEN_ROWS = 256;   // rows per tile of the generic form
-constexpr unsigned IH_PAIRS_Y = 32768; // (query, probe) pairs along grid dimension y; the rest along z (both < 65536)
 
-// What a workgroup of the list scan works on: pair = (query, probe slot), wave-uniform.  false: nothing to do.
-struct IvfF16Work {
-    int q;
-    uint32_t len;         // rows of the list
-    const uint32_t *rmap; // the list's rows, ascending
-    uint64_t *out;        // the list's keys of this query
-};
-__device__ __forceinline__ bool ivf_f16_work(const IvfBatch &a, int tile_rows, IvfF16Work &w)
-{
-    const int64_t pair = (int64_t)blockIdx.y + (int64_t)blockIdx.z * gridDim.y;
-    if (pair >= (int64_t)a.nq * a.np) return false;
-    w.q = (int)(pair / a.np);
-    const int p = (int)(pair % a.np);
-    const int64_t l = a.probes[pair];
-    if (l < 0 || l >= a.L.nlist) return false;
-    const uint32_t off = a.L.off[l];
-    w.len = a.L.off[l + 1] - off;
-    if ((uint64_t)blockIdx.x * (uint32_t)tile_rows >= w.len) return false; // (an empty list among them)
-    const uint32_t seg = a.seg[(int64_t)w.q * (a.np + 1) + p];
-    if ((int64_t)seg + w.len > a.pmax) return false; // never with distinct probes: the keys of a query stay inside its pmax
-    w.rmap = a.L.rows + off;
-    w.out = a.keys + (int64_t)w.q * a.pmax + seg;
-    return true;
-}
-
-// Work = (query, probe slot, 128-row tile of that list); a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of
-// its list.  The (tile, chunk) sequence is one flat pipeline: one LDS stage [rows fp16 | query chunk f32] plus a register-held
-// prefetch of the next one (128 x 272 + 128 x 4 = 35,328 B, 4 workgroups per CU).  D % 8 == 0, X and Q 16-byte aligned.
+// Work = (query, probe slot, 128-row tile of that list), found and walked as lb_list_scan.h states.  A stage is [rows fp16 |
+// query chunk f32] (128 x 272 + 128 x 4 = 35,328 B with the register-held prefetch of the next one, 4 workgroups per CU).
+// D % 8 == 0, X and Q 16-byte aligned.
 template <int METRIC, int ORDER>
 __global__ __launch_bounds__(IH_ROWS) void ivf_scan_f16_kernel(IvfF16Scan s)
 {
     __shared__ __attribute__((aligned(16))) _Float16 lds_x[IH_ROWS * IH_LD];
     __shared__ __attribute__((aligned(16))) float lds_q[IH_DK];
     const IvfBatch &a = s.b;
-    IvfF16Work w;
-    if (!ivf_f16_work(a, IH_ROWS, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a, IH_ROWS, w)) return;
     const int tid = threadIdx.x;
     const int D = a.D;
     const int nchunks = (D + IH_DK - 1) / IH_DK;
@@ -106,63 +82,32 @@ __global__ __launch_bounds__(IH_ROWS) void ivf_scan_f16_kernel(IvfF16Scan s)
 
     Acc<ORDER> acc; // L2: sum (q-x)^2 ; cos/dot: sum q*x
     Acc<ORDER> nb;  // cos: sum x*x
-    // a finished tile's key is written right after the next stage's loads are issued
     float pend_dist = 0.f;
-    bool pending = false;
-    uint32_t pend_tile = 0;
-    auto flush = [&]() {
-        const uint32_t pos = pend_tile * IH_ROWS + tid;
-        if (pos < w.len) w.out[pos] = pack_entry(pend_dist, w.rmap[pos]);
-        pending = false;
-    };
-
-    uint32_t tile = blockIdx.x;
-    int c = 0;
-    load_stage(tile, 0);
-    write_stage();
-    __syncthreads();
-    while (true) {
-        uint32_t ntile = tile;
-        int nc = c + 1;
-        if (nc == nchunks) {
-            nc = 0;
-            ntile = tile + gridDim.x;
-        }
-        const bool has_next = ntile < ntiles;
-        if (has_next) load_stage(ntile, nc);
-        if (pending) flush();
+    auto consume = [&](int c) {
         if (c == 0) {
             acc.zero();
             nb.zero();
         }
-        {
-            const _Float16 *xr = &lds_x[tid * IH_LD];
-            const int d0 = c * IH_DK;
-            const int npieces = (min(D, d0 + IH_DK) - d0) >> 3;
+        const _Float16 *xr = &lds_x[tid * IH_LD];
+        const int d0 = c * IH_DK;
+        const int npieces = (min(D, d0 + IH_DK) - d0) >> 3;
 #pragma unroll 2
-            for (int g = 0; g < npieces; g++) {
-                const f16x8 xh = *reinterpret_cast<const f16x8 *>(&xr[g * 8]);
-                const f32x4 lo = {(float)xh[0], (float)xh[1], (float)xh[2], (float)xh[3]};
-                const f32x4 hi = {(float)xh[4], (float)xh[5], (float)xh[6], (float)xh[7]};
-                if (METRIC == METRIC_COS) nb.add4_sq(lo);
-                acc.template add4_pair<METRIC>(*reinterpret_cast<const f32x4 *>(&lds_q[g * 8]), lo);
-                if (METRIC == METRIC_COS) nb.add4_sq(hi);
-                acc.template add4_pair<METRIC>(*reinterpret_cast<const f32x4 *>(&lds_q[g * 8 + 4]), hi);
-            }
+        for (int g = 0; g < npieces; g++) {
+            const f16x8 xh = *reinterpret_cast<const f16x8 *>(&xr[g * 8]);
+            const f32x4 lo = {(float)xh[0], (float)xh[1], (float)xh[2], (float)xh[3]};
+            const f32x4 hi = {(float)xh[4], (float)xh[5], (float)xh[6], (float)xh[7]};
+            if (METRIC == METRIC_COS) nb.add4_sq(lo);
+            acc.template add4_pair<METRIC>(*reinterpret_cast<const f32x4 *>(&lds_q[g * 8]), lo);
+            if (METRIC == METRIC_COS) nb.add4_sq(hi);
+            acc.template add4_pair<METRIC>(*reinterpret_cast<const f32x4 *>(&lds_q[g * 8 + 4]), hi);
         }
-        __syncthreads(); // every wave is done reading the stage
-        if (has_next) write_stage();
-        if (c == nchunks - 1) {
-            pend_dist = exact_distance<METRIC>(acc.total(), nb.total(), na, D, false);
-            pend_tile = tile;
-            pending = true;
-        }
-        __syncthreads();
-        if (!has_next) break;
-        tile = ntile;
-        c = nc;
-    }
-    if (pending) flush();
+    };
+    auto finish = [&]() { pend_dist = exact_distance<METRIC>(acc.total(), nb.total(), na, D, false); };
+    auto flush = [&](uint32_t tile) {
+        const uint32_t pos = tile * IH_ROWS + tid;
+        if (pos < w.len) w.out[pos] = pack_entry(pend_dist, w.rmap[pos]);
+    };
+    walk_list_tiles(ntiles, nchunks, load_stage, write_stage, consume, finish, flush);
 }
 
 // D % 8 != 0 or a misaligned base: one lane per row walks its row straight from global memory.  Same arithmetic.
@@ -170,8 +115,8 @@ template <int METRIC, int ORDER>
 __global__ __launch_bounds__(IH_GEN_ROWS) void ivf_scan_f16_generic_kernel(IvfF16Scan s)
 {
     const IvfBatch &a = s.b;
-    IvfF16Work w;
-    if (!ivf_f16_work(a, IH_GEN_ROWS, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a, IH_GEN_ROWS, w)) return;
     const int D = a.D;
     const float *q = a.Q + (int64_t)w.q * D;
     const float na = METRIC == METRIC_COS ? a.qna[w.q] : 0.f;
@@ -183,34 +128,16 @@ __global__ __launch_bounds__(IH_GEN_ROWS) void ivf_scan_f16_generic_kernel(IvfF1
     }
 }
 
-template <int METRIC, int ORDER>
-static void launch_ivf_scan_f16_mo(const IvfF16Scan &a, bool staged, dim3 grid, hipStream_t s)
-{
-    if (staged) hipLaunchKernelGGL((ivf_scan_f16_kernel<METRIC, ORDER>), grid, dim3(IH_ROWS), 0, s, a);
-    else hipLaunchKernelGGL((ivf_scan_f16_generic_kernel<METRIC, ORDER>), grid, dim3(IH_GEN_ROWS), 0, s, a);
-}
-
 void launch_ivf_scan_f16(int metric, int order, const IvfF16Scan &a, int64_t maxlen, hipStream_t s)
 {
     const int64_t pairs = (int64_t)a.b.nq * a.b.np;
     if (pairs <= 0 || maxlen <= 0) return;
     const bool staged = a.b.D % 8 == 0 && ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.b.Q)) & 15) == 0;
-    // launch_ivf_scan's grid: tiles along x, enough workgroups to fill the chip (256 CUs, 4 workgroups each) four times over
-    // and no more; a workgroup walks the rest of its list's tiles itself
-    const int64_t tiles = (maxlen + (staged ? IH_ROWS : IH_GEN_ROWS) - 1) / (staged ? IH_ROWS : IH_GEN_ROWS);
-    const int64_t gx = std::min<int64_t>(tiles, std::max<int64_t>(1, (4096 + pairs - 1) / pairs));
-    const unsigned gy = (unsigned)std::min<int64_t>(pairs, IH_PAIRS_Y);
-    const unsigned gz = (unsigned)((pairs + gy - 1) / gy); // <= 1024 queries x 65536 lists / 32768 = 2048
-    const dim3 grid((unsigned)gx, gy, gz);
-#define LB_IVF_F16(M)                                                           \
-    do {                                                                        \
-        if (order == ORDER_UNROLL4) launch_ivf_scan_f16_mo<M, ORDER_UNROLL4>(a, staged, grid, s); \
-        else launch_ivf_scan_f16_mo<M, ORDER_SEQ>(a, staged, grid, s);          \
-    } while (0)
-    if (metric == METRIC_L2) LB_IVF_F16(METRIC_L2);
-    else if (metric == METRIC_COS) LB_IVF_F16(METRIC_COS);
-    else LB_IVF_F16(METRIC_DOT);
-#undef LB_IVF_F16
+    const dim3 grid = ivf_scan_grid(pairs, maxlen, staged ? IH_ROWS : IH_GEN_ROWS);
+    with_metric_order(metric, order, [&](auto m, auto o) {
+        if (staged) hipLaunchKernelGGL((ivf_scan_f16_kernel<decltype(m)::value, decltype(o)::value>), grid, dim3(IH_ROWS), 0, s, a);
+        else hipLaunchKernelGGL((ivf_scan_f16_generic_kernel<decltype(m)::value, decltype(o)::value>), grid, dim3(IH_GEN_ROWS), 0, s, a);
+    });
 }
 
 } // namespace lb

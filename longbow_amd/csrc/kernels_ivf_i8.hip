@@ -1,8 +1,8 @@
 // kernels_ivf_i8.hip -- the list scan of an IVF-Flat handle whose rows are int8 (ivf.hip; semantics in include/longbow_gpu.h,
-// lb_gpu_ivf_new_i8).  The work decomposition is ivf_scan_f16_kernel's (kernels_ivf_f16.hip): a workgroup takes a (query, probe
-// slot) pair and walks 128-row tiles of that list, one lane owns one row.  A stage holds 256 B of every row, the fp16 kernel's
-// bytes of a row and so its bytes in flight, gathered by row number in 16-byte pieces into an LDS tile whose row stride is 17
-// such pieces.  The arithmetic is the flat int8 index's (kernels_i8.hip): x.q by v_dot4_i32_i8 in exact int32; for L2 |x|^2 comes
+// lb_gpu_ivf_new_i8).  The work decomposition is the list scans' (lb_list_scan.h): a workgroup takes a (query, probe slot) pair
+// and walks 128-row tiles of that list, one lane owns one row.  A stage holds 256 B of every row, the fp16 kernel's
+// (kernels_ivf_f16.hip) bytes of a row and so its bytes in flight, gathered by row number in 16-byte pieces into an LDS tile
+// whose row stride is 17 such pieces.  The arithmetic is the flat int8 index's (kernels_i8.hip): x.q by v_dot4_i32_i8 in exact int32; for L2 |x|^2 comes
 // from the same instruction over the row's own bytes in the same loop, so the handle keeps no norm array and an add has no pass
 // over the rows, and S = |x|^2 + |q|^2 - 2 x.q is the exact integer sum of (x_i - q_i)^2, rounded once to f32.  The scan reads the
 // int8 queries of the batch themselves; the widened ones are the coarse index's.
@@ -10,6 +10,7 @@
 #include "lb_device.h"
 #include "lb_i8_exact.h"
 #include "lb_ivf_i8.h"
+#include "lb_list_scan.h"
 #include "lb_select.h"
 
 #include <algorithm>
@@ -24,37 +25,10 @@ constexpr int I8L_ROWS = 128;          // rows per tile == threads per workgroup
 constexpr int I8L_CK = 256;            // bytes per row per stage
 constexpr int I8L_LD = I8L_CK + 16;    // LDS row stride (bytes): 17 16-byte slots, conflict-free ds_read_b128 by rows
 constexpr int I8L_GEN_ROWS = 256;      // rows per tile of the generic form
-constexpr unsigned I8L_PAIRS_Y = 32768; // (query, probe) pairs along grid dimension y; the rest along z (both < 65536)
 
-// What a workgroup of the list scan works on: pair = (query, probe slot), wave-uniform.  false: nothing to do.
-struct IvfI8Work {
-    int q;
-    uint32_t len;         // rows of the list
-    const uint32_t *rmap; // the list's rows, ascending
-    uint64_t *out;        // the list's keys of this query
-};
-__device__ __forceinline__ bool ivf_i8_work(const IvfBatch &a, int tile_rows, IvfI8Work &w)
-{
-    const int64_t pair = (int64_t)blockIdx.y + (int64_t)blockIdx.z * gridDim.y;
-    if (pair >= (int64_t)a.nq * a.np) return false;
-    w.q = (int)(pair / a.np);
-    const int p = (int)(pair % a.np);
-    const int64_t l = a.probes[pair];
-    if (l < 0 || l >= a.L.nlist) return false;
-    const uint32_t off = a.L.off[l];
-    w.len = a.L.off[l + 1] - off;
-    if ((uint64_t)blockIdx.x * (uint32_t)tile_rows >= w.len) return false; // (an empty list among them)
-    const uint32_t seg = a.seg[(int64_t)w.q * (a.np + 1) + p];
-    if ((int64_t)seg + w.len > a.pmax) return false; // never with distinct probes: the keys of a query stay inside its pmax
-    w.rmap = a.L.rows + off;
-    w.out = a.keys + (int64_t)w.q * a.pmax + seg;
-    return true;
-}
-
-// Work = (query, probe slot, 128-row tile of that list); a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of
-// its list.  The (tile, chunk) sequence is one flat pipeline: one LDS stage [rows | query chunk] plus a register-held prefetch of
-// the next one (128 x 272 + 256 + 4 = 35,076 B, 4 workgroups per CU).  D % 16 == 0, X and Q 16-byte aligned; dot: D <= 1024, so
-// that the total is the exact integer the four chains of dotInt8Unrolled4x sum to.
+// Work = (query, probe slot, 128-row tile of that list), found and walked as lb_list_scan.h states.  A stage is [rows | query
+// chunk] (128 x 272 + 256 + 4 = 35,076 B with the register-held prefetch of the next one, 4 workgroups per CU).  D % 16 == 0, X
+// and Q 16-byte aligned; dot: D <= 1024, so that the total is the exact integer the four chains of dotInt8Unrolled4x sum to.
 template <int METRIC>
 __global__ __launch_bounds__(I8L_ROWS) void ivf_scan_i8_kernel(IvfI8Scan s)
 {
@@ -62,8 +36,8 @@ __global__ __launch_bounds__(I8L_ROWS) void ivf_scan_i8_kernel(IvfI8Scan s)
     __shared__ __attribute__((aligned(16))) int8_t lds_q[I8L_CK];
     __shared__ int lds_qn;
     const IvfBatch &a = s.b;
-    IvfI8Work w;
-    if (!ivf_i8_work(a, I8L_ROWS, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a, I8L_ROWS, w)) return;
     const int tid = threadIdx.x;
     const int D = a.D;
     const int nchunks = (D + I8L_CK - 1) / I8L_CK;
@@ -127,71 +101,42 @@ __global__ __launch_bounds__(I8L_ROWS) void ivf_scan_i8_kernel(IvfI8Scan s)
 
     int acc = 0; // sum x*q
     int nx = 0;  // L2: sum x*x
-    // a finished tile's key is written right after the next stage's loads are issued
     float pend_dist = 0.f;
-    bool pending = false;
-    uint32_t pend_tile = 0;
-    auto flush = [&]() {
-        const uint32_t pos = pend_tile * I8L_ROWS + tid;
-        if (pos < w.len) w.out[pos] = pack_entry(pend_dist, w.rmap[pos]);
-        pending = false;
-    };
-
-    uint32_t tile = blockIdx.x;
-    int c = 0;
-    load_stage(tile, 0);
-    write_stage();
-    __syncthreads();
-    while (true) {
-        uint32_t ntile = tile;
-        int nc = c + 1;
-        if (nc == nchunks) {
-            nc = 0;
-            ntile = tile + gridDim.x;
-        }
-        const bool has_next = ntile < ntiles;
-        if (has_next) load_stage(ntile, nc);
-        if (pending) flush();
+    auto consume = [&](int c) {
         if (c == 0) {
             acc = 0;
             nx = 0;
         }
-        {
-            const i32x4 *xr = reinterpret_cast<const i32x4 *>(&lds_x[tid * I8L_LD]);
-            const i32x4 *qr = reinterpret_cast<const i32x4 *>(lds_q);
-            const int d0 = c * I8L_CK;
-            const int npieces = (min(D, d0 + I8L_CK) - d0) >> 4;
+        const i32x4 *xr = reinterpret_cast<const i32x4 *>(&lds_x[tid * I8L_LD]);
+        const i32x4 *qr = reinterpret_cast<const i32x4 *>(lds_q);
+        const int d0 = c * I8L_CK;
+        const int npieces = (min(D, d0 + I8L_CK) - d0) >> 4;
 #pragma unroll 4
-            for (int g = 0; g < npieces; g++) {
-                const i32x4 x = xr[g];
-                const i32x4 q = qr[g];
-                acc = __builtin_amdgcn_sdot4(x.x, q.x, acc, false);
-                acc = __builtin_amdgcn_sdot4(x.y, q.y, acc, false);
-                acc = __builtin_amdgcn_sdot4(x.z, q.z, acc, false);
-                acc = __builtin_amdgcn_sdot4(x.w, q.w, acc, false);
-                if (METRIC == METRIC_L2) {
-                    nx = __builtin_amdgcn_sdot4(x.x, x.x, nx, false);
-                    nx = __builtin_amdgcn_sdot4(x.y, x.y, nx, false);
-                    nx = __builtin_amdgcn_sdot4(x.z, x.z, nx, false);
-                    nx = __builtin_amdgcn_sdot4(x.w, x.w, nx, false);
-                }
+        for (int g = 0; g < npieces; g++) {
+            const i32x4 x = xr[g];
+            const i32x4 q = qr[g];
+            acc = __builtin_amdgcn_sdot4(x.x, q.x, acc, false);
+            acc = __builtin_amdgcn_sdot4(x.y, q.y, acc, false);
+            acc = __builtin_amdgcn_sdot4(x.z, q.z, acc, false);
+            acc = __builtin_amdgcn_sdot4(x.w, q.w, acc, false);
+            if (METRIC == METRIC_L2) {
+                nx = __builtin_amdgcn_sdot4(x.x, x.x, nx, false);
+                nx = __builtin_amdgcn_sdot4(x.y, x.y, nx, false);
+                nx = __builtin_amdgcn_sdot4(x.z, x.z, nx, false);
+                nx = __builtin_amdgcn_sdot4(x.w, x.w, nx, false);
             }
         }
-        __syncthreads(); // every wave is done reading the stage
-        if (has_next) write_stage();
-        if (c == nchunks - 1) {
-            // L2: S <= 8192 * 65025 < 2^31, converted once to f32, sqrt correctly rounded; dot: |x.q| <= 2^24, exact
-            if (METRIC == METRIC_L2) pend_dist = (float)sqrt((double)(float)(nx + qn - 2 * acc));
-            else pend_dist = -(float)acc;
-            pend_tile = tile;
-            pending = true;
-        }
-        __syncthreads();
-        if (!has_next) break;
-        tile = ntile;
-        c = nc;
-    }
-    if (pending) flush();
+    };
+    auto finish = [&]() {
+        // L2: S <= 8192 * 65025 < 2^31, converted once to f32, sqrt correctly rounded; dot: |x.q| <= 2^24, exact
+        if (METRIC == METRIC_L2) pend_dist = (float)sqrt((double)(float)(nx + qn - 2 * acc));
+        else pend_dist = -(float)acc;
+    };
+    auto flush = [&](uint32_t tile) {
+        const uint32_t pos = tile * I8L_ROWS + tid;
+        if (pos < w.len) w.out[pos] = pack_entry(pend_dist, w.rmap[pos]);
+    };
+    walk_list_tiles(ntiles, nchunks, load_stage, write_stage, consume, finish, flush);
 }
 
 // Any other D, a misaligned base, or dot beyond 1024 dimensions: one lane per row walks its row straight from global memory, in
@@ -200,8 +145,8 @@ template <int METRIC>
 __global__ __launch_bounds__(I8L_GEN_ROWS) void ivf_scan_i8_generic_kernel(IvfI8Scan s)
 {
     const IvfBatch &a = s.b;
-    IvfI8Work w;
-    if (!ivf_i8_work(a, I8L_GEN_ROWS, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a, I8L_GEN_ROWS, w)) return;
     const int D = a.D;
     const int8_t *q = s.Q + (int64_t)w.q * D;
     for (uint64_t pos = (uint64_t)blockIdx.x * I8L_GEN_ROWS + threadIdx.x; pos < w.len; pos += (uint64_t)gridDim.x * I8L_GEN_ROWS) {
@@ -223,13 +168,7 @@ void launch_ivf_scan_i8(int metric, const IvfI8Scan &a, int64_t maxlen, hipStrea
     if (pairs <= 0 || maxlen <= 0) return;
     const bool staged = a.b.D % 16 == 0 && (metric == METRIC_L2 || a.b.D <= 1024) &&
                         ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.Q)) & 15) == 0;
-    // launch_ivf_scan's grid: tiles along x, enough workgroups to fill the chip (256 CUs, 4 workgroups each) four times over
-    // and no more; a workgroup walks the rest of its list's tiles itself
-    const int64_t tiles = (maxlen + (staged ? I8L_ROWS : I8L_GEN_ROWS) - 1) / (staged ? I8L_ROWS : I8L_GEN_ROWS);
-    const int64_t gx = std::min<int64_t>(tiles, std::max<int64_t>(1, (4096 + pairs - 1) / pairs));
-    const unsigned gy = (unsigned)std::min<int64_t>(pairs, I8L_PAIRS_Y);
-    const unsigned gz = (unsigned)((pairs + gy - 1) / gy); // <= 1024 queries x 65536 lists / 32768 = 2048
-    const dim3 grid((unsigned)gx, gy, gz);
+    const dim3 grid = ivf_scan_grid(pairs, maxlen, staged ? I8L_ROWS : I8L_GEN_ROWS);
     if (metric == METRIC_L2) launch_ivf_scan_i8_m<METRIC_L2>(a, staged, grid, s);
     else launch_ivf_scan_i8_m<METRIC_DOT>(a, staged, grid, s);
 }

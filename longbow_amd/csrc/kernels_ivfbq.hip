@@ -3,7 +3,7 @@
 // kernels_ivf.hip's, the codec kernels_bq.hip's, the list-major copy kernels_ivfpq.hip's, the selection kernels_ivfsq8.hip's.
 //
 // The codes lie list-major (lcodes[pos] = codes[rows[pos]]), so a probed list is one contiguous run of len * W words.  The scan is
-// ivf_scan_kernel's walk (kernels_ivf.hip) over the tile of kernels_bq.hip, restated here: a list per (query, probe slot), a
+// the list scans' walk (lb_list_scan.h) over the tile of kernels_bq.hip, restated here: a list per (query, probe slot), a
 // tile is 256 rows, one lane owns a row.  A chunk is CW words of each of the tile's rows, fetched as coalesced 8-byte words
 // (consecutive lanes read consecutive words of the run) into an LDS tile whose row stride is CW + 2 words: CW / 2 + 1 slots of
 // 16 bytes, an odd number, so the rows are 16-byte aligned and the 16 lanes one ds_read_b128 cycle serves fall on 16 distinct
@@ -21,6 +21,7 @@
 // consecutive words per position.
 #include "lb_device.h"
 #include "lb_ivfbq.h"
+#include "lb_list_scan.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -31,38 +32,11 @@ namespace {
 
 typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
 
-constexpr unsigned IBQ_PAIRS_Y = 32768; // (query, probe) pairs along grid dimension y; the rest along z (both < 65536)
-
-// What a workgroup of the list scan works on, found as ivf_work finds it (kernels_ivf.hip): pair = (query, probe slot),
-// wave-uniform.  false: nothing to do.
-struct IbqWork {
-    int q;
-    uint32_t off;  // the list's first entry in L.rows
-    uint32_t len;  // entries of the list
-    uint64_t *out; // the list's keys of this query
-};
-__device__ __forceinline__ bool ibq_work(const IvfBatch &a, IbqWork &w)
-{
-    const int64_t pair = (int64_t)blockIdx.y + (int64_t)blockIdx.z * gridDim.y;
-    if (pair >= (int64_t)a.nq * a.np) return false;
-    w.q = (int)(pair / a.np);
-    const int p = (int)(pair % a.np);
-    const int64_t l = a.probes[pair];
-    if (l < 0 || l >= a.L.nlist) return false;
-    w.off = a.L.off[l];
-    w.len = a.L.off[l + 1] - w.off;
-    if ((uint64_t)blockIdx.x * (uint32_t)IBQ_ROWS >= w.len) return false; // (an empty list among them)
-    const uint32_t seg = a.seg[(int64_t)w.q * (a.np + 1) + p];
-    if ((int64_t)seg + w.len > a.pmax) return false; // never with distinct probes: the keys of a query stay inside its pmax
-    w.out = a.keys + (int64_t)w.q * a.pmax + seg;
-    return true;
-}
-
 } // namespace
 
-// Work = (query, probe slot, 256-row tile of that list); a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of
-// its list.  The (tile, chunk) sequence is one flat pipeline: one LDS stage of 256 rows x CW words plus a register-held prefetch
-// of the next one; the query's whole code lies behind the stage, zero past its last word.
+// Work = (query, probe slot, 256-row tile of that list), found as lb_list_scan.h states and walked as it states, in this
+// kernel's own text (below); of the work this scan takes the list's place in L.rows (off), not its rows.  A stage is 256 rows x CW words, with a register-held prefetch of the next
+// one; the query's whole code lies behind the stage, zero past its last word.
 // LDS: tile u64[IBQ_ROWS][CW + 2] | query u64[nchunks * CW]
 template <int CW, bool VIS>
 __global__ __launch_bounds__(IBQ_ROWS) void ivfbq_scan_kernel(IvfBqScan a)
@@ -71,8 +45,8 @@ __global__ __launch_bounds__(IBQ_ROWS) void ivfbq_scan_kernel(IvfBqScan a)
     constexpr int LD = CW + 2; // an odd number of 16-byte slots
     uint64_t *lrow = ibq_smem;
     uint64_t *lq = lrow + IBQ_ROWS * LD;
-    IbqWork w;
-    if (!ibq_work(a.b, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a.b, IBQ_ROWS, w)) return;
     const int tid = threadIdx.x;
     const int W = a.W, nchunks = (W + CW - 1) / CW;
     const uint32_t ntiles = (w.len + IBQ_ROWS - 1) / IBQ_ROWS;
@@ -125,6 +99,10 @@ __global__ __launch_bounds__(IBQ_ROWS) void ivfbq_scan_kernel(IvfBqScan a)
         pending = false;
     };
 
+    // walk_list_tiles' walk (lb_list_scan.h) in this kernel's own text, kept in step with it by hand.  Built over the shared
+    // walk the eight instantiations came out the same length with 37 - 64 instructions different (same registers and
+    // occupancy), and three of 32 scan-slot rows missed the rule of LABNOTES R34.1, each by 0.2 % or 0.3 us: <8, plain> at
+    // 1024 queries x 32 probes, <12, visible> at 1 x 8, <16, visible> at 1024 x 8.
     uint32_t tile = blockIdx.x;
     int c = 0;
     load_stage(tile, 0);
@@ -176,13 +154,7 @@ template <bool VIS> void launch_ivfbq_scan_v(const IvfBqScan &a, int64_t maxlen,
 {
     const int64_t pairs = (int64_t)a.b.nq * a.b.np;
     if (pairs <= 0 || maxlen <= 0 || a.n <= 0 || a.W <= 0) return;
-    // tiles along x, as launch_ivf_scan sizes them: enough workgroups to fill the chip four times over and no more; a workgroup
-    // walks the rest of its list's tiles itself
-    const int64_t tiles = (maxlen + IBQ_ROWS - 1) / IBQ_ROWS;
-    const int64_t gx = std::min<int64_t>(tiles, std::max<int64_t>(1, (4096 + pairs - 1) / pairs));
-    const unsigned gy = (unsigned)std::min<int64_t>(pairs, IBQ_PAIRS_Y);
-    const unsigned gz = (unsigned)((pairs + gy - 1) / gy); // <= 1024 queries x 65536 lists / 32768 = 2048
-    const dim3 grid((unsigned)gx, gy, gz);
+    const dim3 grid = ivf_scan_grid(pairs, maxlen, IBQ_ROWS);
     const int cw = ibq_cw(a.W);
     const size_t lds = ((size_t)IBQ_ROWS * (cw + 2) + (size_t)((a.W + cw - 1) / cw) * cw) * 8; // at most 36,992 B (W = 16)
     auto go = [&](auto c) { hipLaunchKernelGGL((ivfbq_scan_kernel<decltype(c)::value, VIS>), grid, dim3(IBQ_ROWS), lds, s, a); };

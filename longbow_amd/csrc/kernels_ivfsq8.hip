@@ -3,7 +3,7 @@
 // the visible lists are kernels_ivf.hip's, the codec and the norms kernels_sq8.hip's.
 //
 // The codes stay in insertion order at a stride of dims rounded up to 16 bytes, pad bytes zero, and a list is an ascending array
-// of row numbers, so the list scan is ivf_scan_kernel's walk (kernels_ivf.hip) over the tile body of sq8_dist_kernel<QT, true>
+// of row numbers, so the list scan is the list scans' walk (lb_list_scan.h) over the tile body of sq8_dist_kernel<QT, true>
 // (kernels_sq8.hip): a list per (query, probe slot), one lane per row, the rows' bytes gathered by row number in coalesced
 // 16-byte pieces into an LDS tile whose row stride is an odd number of 16-byte slots, the query's code in LDS and read
 // wave-uniform.  x.q and |x|^2 both come from v_dot4_u32_u8 on the piece a lane holds, and S = |x|^2 + |q|^2 - 2 x.q in
@@ -11,6 +11,7 @@
 // u64 order of the keys is the (S, row) order of the integers and kEntryMax padding sorts last.  Integer only.
 #include "lb_device.h"
 #include "lb_ivfsq8.h"
+#include "lb_list_scan.h"
 #include "lb_select.h"
 
 #include <float.h>
@@ -24,7 +25,6 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int ISQ_CH = 8;                // 16-byte pieces of a row per stage: one 128-byte line of the row
 constexpr int ISQ_LD = ISQ_CH + 1;       // LDS row stride in pieces: odd, so the 16 lanes of a ds_read_b128 group fall on 16 slots
-constexpr unsigned ISQ_PAIRS_Y = 32768;  // (query, probe) pairs along grid dimension y; the rest along z (both < 65536)
 
 __device__ __forceinline__ uint32_t isq_dot16(const u32x4 a, const u32x4 b, uint32_t acc)
 {
@@ -35,45 +35,19 @@ __device__ __forceinline__ uint32_t isq_dot16(const u32x4 a, const u32x4 b, uint
     return acc;
 }
 
-// What a workgroup of the list scan works on, found as ivf_work finds it (kernels_ivf.hip): pair = (query, probe slot),
-// wave-uniform.  false: nothing to do.
-struct IsqWork {
-    int q;
-    uint32_t len;         // rows of the list
-    const uint32_t *rmap; // the list's rows, ascending
-    uint64_t *out;        // the list's keys of this query
-};
-__device__ __forceinline__ bool isq_work(const IvfBatch &a, IsqWork &w)
-{
-    const int64_t pair = (int64_t)blockIdx.y + (int64_t)blockIdx.z * gridDim.y;
-    if (pair >= (int64_t)a.nq * a.np) return false;
-    w.q = (int)(pair / a.np);
-    const int p = (int)(pair % a.np);
-    const int64_t l = a.probes[pair];
-    if (l < 0 || l >= a.L.nlist) return false;
-    const uint32_t off = a.L.off[l];
-    w.len = a.L.off[l + 1] - off;
-    if ((uint64_t)blockIdx.x * (uint32_t)ISQ_ROWS >= w.len) return false; // (an empty list among them)
-    const uint32_t seg = a.seg[(int64_t)w.q * (a.np + 1) + p];
-    if ((int64_t)seg + w.len > a.pmax) return false; // never with distinct probes: the keys of a query stay inside its pmax
-    w.rmap = a.L.rows + off;
-    w.out = a.keys + (int64_t)w.q * a.pmax + seg;
-    return true;
-}
-
 } // namespace
 
-// Work = (query, probe slot, 128-row tile of that list); a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of
-// its list.  The (tile, chunk) sequence is one flat pipeline: one LDS stage of 128 rows x 8 pieces plus a register-held prefetch
-// of the next one; the query's whole code lies behind the stage, zero past its last piece.
+// Work = (query, probe slot, 128-row tile of that list), found as lb_list_scan.h states and walked as it states, in this
+// kernel's own text (below).  A stage is 128 rows x 8 pieces, with a register-held prefetch of the next one; the query's whole
+// code lies behind the stage, zero past its last piece.
 // LDS: tile u32x4[ISQ_ROWS][ISQ_LD] | query u32x4[nchunks * ISQ_CH]
 __global__ __launch_bounds__(ISQ_ROWS) void ivfsq8_scan_kernel(IvfSq8Scan a)
 {
     extern __shared__ __attribute__((aligned(16))) u32x4 isq_smem[];
     u32x4 *lrow = isq_smem;
     u32x4 *lq = lrow + ISQ_ROWS * ISQ_LD;
-    IsqWork w;
-    if (!isq_work(a.b, w)) return;
+    ListWork w;
+    if (!ivf_list_work(a.b, ISQ_ROWS, w)) return;
     const int tid = threadIdx.x;
     const int P = a.stride >> 4, nchunks = (P + ISQ_CH - 1) / ISQ_CH;
     const uint32_t ntiles = (w.len + ISQ_ROWS - 1) / ISQ_ROWS;
@@ -122,6 +96,9 @@ __global__ __launch_bounds__(ISQ_ROWS) void ivfsq8_scan_kernel(IvfSq8Scan a)
         pending = false;
     };
 
+    // walk_list_tiles' walk (lb_list_scan.h) in this kernel's own text, kept in step with it by hand.  Built over the shared
+    // walk the kernel came out nine instructions longer (same registers and occupancy) and its scan slot at 1024 queries x 32
+    // probes 0.5 % slower in all three runs, four times the parent's spread (LABNOTES R34.1).
     uint32_t tile = blockIdx.x;
     int c = 0;
     load_stage(tile, 0);
@@ -170,15 +147,9 @@ void launch_ivfsq8_scan(const IvfSq8Scan &a, int64_t maxlen, hipStream_t s)
 {
     const int64_t pairs = (int64_t)a.b.nq * a.b.np;
     if (pairs <= 0 || maxlen <= 0 || a.n <= 0) return;
-    // tiles along x, as launch_ivf_scan sizes them: enough workgroups to fill the chip four times over and no more; a workgroup
-    // walks the rest of its list's tiles itself
-    const int64_t tiles = (maxlen + ISQ_ROWS - 1) / ISQ_ROWS;
-    const int64_t gx = std::min<int64_t>(tiles, std::max<int64_t>(1, (4096 + pairs - 1) / pairs));
-    const unsigned gy = (unsigned)std::min<int64_t>(pairs, ISQ_PAIRS_Y);
-    const unsigned gz = (unsigned)((pairs + gy - 1) / gy); // <= 1024 queries x 65536 lists / 32768 = 2048
     const int P = a.stride >> 4, Pq = (P + ISQ_CH - 1) / ISQ_CH * ISQ_CH;
     const size_t lds = ((size_t)ISQ_ROWS * ISQ_LD + (size_t)Pq) * 16; // at most 26,752 B (dims 8192)
-    hipLaunchKernelGGL(ivfsq8_scan_kernel, dim3((unsigned)gx, gy, gz), dim3(ISQ_ROWS), lds, s, a);
+    hipLaunchKernelGGL(ivfsq8_scan_kernel, ivf_scan_grid(pairs, maxlen, ISQ_ROWS), dim3(ISQ_ROWS), lds, s, a);
 }
 
 // ---- select ---------------------------------------------------------------------------------------------------------------

@@ -2,13 +2,15 @@
 // c candidate rows each become, per query, the ascending list of the distinct valid rows (refine_prepare_kernel) and one key per
 // list position (refine_scan_kernel); launch_ivf_select (kernels_ivf.hip) then takes the k smallest keys of every query.
 //
-// The scan is ivf_scan_kernel's method (kernels_ivf.hip) over these per-query lists: each lane owns one row and carries that row's
-// f32 accumulator chain(s) across D in the reference's order (lb_exact.h), rows staged through LDS in coalesced 16-byte pieces;
-// the rows of a float16 index are widened to f32 (exact) as the stage is written, as scan_kernel does (kernels_scan.hip).  Every
-// list position leaves one key.  Plain vector loads and stores, no atomics, no workgroup waits for another.
+// The scan is ivf_scan_kernel's method (kernels_ivf.hip) over these per-query lists, on the walk and the grid rule that
+// lb_list_scan.h states for every list scan: each lane owns one row and carries that row's f32 accumulator chain(s) across D in
+// the reference's order (lb_exact.h), rows staged through LDS in coalesced 16-byte pieces; the rows of a float16 index are
+// widened to f32 (exact) as the stage is written, as scan_kernel does (kernels_scan.hip).  Every list position leaves one key.
+// Plain vector loads and stores, no atomics, no workgroup waits for another.
 // No FMA contraction here.
 #include "lb_device.h"
 #include "lb_exact.h"
+#include "lb_list_scan.h"
 #include "lb_refine.h"
 #include "lb_select.h"
 
@@ -132,9 +134,9 @@ __device__ __forceinline__ bool refine_work(const RefineBatch &a, int tile_rows,
     return true;
 }
 
-// Work = (query, 128-row tile of its list); a workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its query.
-// The (tile, chunk) sequence is one flat pipeline: one LDS stage [rows | query chunk] of f32 plus a register-held prefetch of
-// the next one (34.3 KB, 4 workgroups per CU).  D % 4 == 0 (f32 rows) or D % 8 == 0 (fp16 rows), X and Q 16-byte aligned.
+// Work = (query, 128-row tile of its list), walked as lb_list_scan.h states, in this kernel's own text (below).  A stage is [rows | query chunk] of f32 (34.3 KB
+// with the register-held prefetch of the next one, 4 workgroups per CU).  D % 4 == 0 (f32 rows) or D % 8 == 0 (fp16 rows), X and
+// Q 16-byte aligned.
 template <typename T, int METRIC, int ORDER>
 __global__ __launch_bounds__(RF_ROWS) void refine_scan_kernel(RefineBatch a)
 {
@@ -213,6 +215,10 @@ __global__ __launch_bounds__(RF_ROWS) void refine_scan_kernel(RefineBatch a)
         pending = false;
     };
 
+    // walk_list_tiles' walk (lb_list_scan.h) in this kernel's own text, kept in step with it by hand.  Built over the shared
+    // walk <cos, UNROLL4> took 30 more VGPRs (176 -> 206 on f32 rows, 120 -> 150 on fp16 rows) and its scan slot was 8 - 10 %
+    // slower (fp16 rows at 1 and at 1024 queries, f32 rows at 1 query); four more of the twelve instantiations missed the rule
+    // of LABNOTES R34.1 by 0.4 - 2.4 %.
     uint32_t tile = blockIdx.x;
     int c = 0;
     load_stage(tile, 0);
@@ -278,32 +284,17 @@ __global__ __launch_bounds__(RF_GEN_ROWS) void refine_scan_generic_kernel(Refine
     }
 }
 
-template <typename T, int METRIC, int ORDER>
-static void launch_refine_scan_tmo(const RefineBatch &a, bool staged, dim3 grid, hipStream_t s)
-{
-    if (staged) hipLaunchKernelGGL((refine_scan_kernel<T, METRIC, ORDER>), grid, dim3(RF_ROWS), 0, s, a);
-    else hipLaunchKernelGGL((refine_scan_generic_kernel<T, METRIC, ORDER>), grid, dim3(RF_GEN_ROWS), 0, s, a);
-}
-
 template <typename T>
 static void launch_refine_scan_t(int metric, int order, const RefineBatch &a, hipStream_t s)
 {
     const bool staged = a.D % (16 / (int)sizeof(T)) == 0 && ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.Q)) & 15) == 0;
-    // tiles along x: enough workgroups to fill the chip (256 CUs, 4 workgroups each) four times over and no more; a workgroup
-    // walks the rest of its query's tiles itself.  Queries along y (a batch holds at most 1024).
+    // tiles of a query's list along x (list_scan_gx), queries along y (a batch holds at most 1024)
     const int rows = staged ? RF_ROWS : RF_GEN_ROWS;
-    const int64_t tiles = ((int64_t)a.c + rows - 1) / rows;
-    const int64_t gx = std::min<int64_t>(tiles, std::max<int64_t>(1, (4096 + a.nq - 1) / a.nq));
-    const dim3 grid((unsigned)gx, (unsigned)a.nq, 1);
-#define LB_RF(M)                                                                                  \
-    do {                                                                                          \
-        if (order == ORDER_UNROLL4) launch_refine_scan_tmo<T, M, ORDER_UNROLL4>(a, staged, grid, s); \
-        else launch_refine_scan_tmo<T, M, ORDER_SEQ>(a, staged, grid, s);                         \
-    } while (0)
-    if (metric == METRIC_L2) LB_RF(METRIC_L2);
-    else if (metric == METRIC_COS) LB_RF(METRIC_COS);
-    else LB_RF(METRIC_DOT);
-#undef LB_RF
+    const dim3 grid((unsigned)list_scan_gx(a.nq, ((int64_t)a.c + rows - 1) / rows), (unsigned)a.nq, 1);
+    with_metric_order(metric, order, [&](auto m, auto o) {
+        if (staged) hipLaunchKernelGGL((refine_scan_kernel<T, decltype(m)::value, decltype(o)::value>), grid, dim3(RF_ROWS), 0, s, a);
+        else hipLaunchKernelGGL((refine_scan_generic_kernel<T, decltype(m)::value, decltype(o)::value>), grid, dim3(RF_GEN_ROWS), 0, s, a);
+    });
 }
 
 void launch_refine_scan(int metric, int order, bool f16, const RefineBatch &a, hipStream_t s)

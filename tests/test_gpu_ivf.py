@@ -1,6 +1,7 @@
 """lb_gpu_ivf_* on the GPU against tests/ivf_oracle.py (the semantics restated over the C oracle's batch_flat and
 topk_canonical): labels and distances must be equal, bit for bit.  The shapes are the smallest at which the kernels can still go
-wrong: lists around the 128-row tile, a list that needs the tile stride loop, selections within LDS and beyond it, the staged scan
+wrong: lists around the 128-row tile, a list that needs the tile stride loop, a workgroup that walks several tiles of several
+chunks, selections within LDS and beyond it, the staged scan
 with one chunk, a partial last chunk and twelve, the one-lane-per-row form, more queries than a batch."""
 import ctypes as C
 import threading
@@ -104,6 +105,26 @@ def test_list_length_edges(oracle):
     lab, dist = h.search(Q, 10, 1)
     assert (lab[0] == -1).all() and (dist[0] == io.FLT_MAX).all()  # an empty probed list: all padding
     assert lab[1, 0] == np.flatnonzero(owner == 1)[0] and (lab[1, 1:] == -1).all() and (dist[1, 1:] == io.FLT_MAX).all()
+    h.Close()
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("metric", [0, 1])
+def test_one_workgroup_walks_several_tiles_and_chunks(oracle, metric, order):
+    """1024 queries x 4 probes = 4,096 pairs, so the scan's grid has one workgroup per (query, list): it walks the three or more
+    128-row tiles of the longest list, the last one partial, in three chunks each (136 dims: 64 + 64 + 8), and the pipeline wraps
+    from a tile's last chunk to the next tile's first"""
+    TILE, CHUNK, GRID = 128, 64, 4096
+    nq, nprobe, dim = 1024, 4, 136
+    X, Q, C_ = io.parity_case(2400, dim, 8, nq, seed=136)
+    lists = io.assign(oracle, metric, order, X, C_)
+    big = int(np.bincount(lists, minlength=8).max())
+    assert max(1, -(-GRID // (nq * nprobe))) == 1  # grid.x
+    assert big > 2 * TILE and big % TILE != 0, big
+    assert -(-dim // CHUNK) >= 2 and dim % CHUNK != 0
+    h = _handle(X, C_, metric, order)
+    assert np.array_equal(h.assignments(), lists)
+    _check_search(oracle, h, metric, order, Q, X, C_, lists, 10, nprobe, ctx=f"several tiles and chunks, metric {metric} order {order}")
     h.Close()
 
 

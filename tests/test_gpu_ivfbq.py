@@ -332,6 +332,30 @@ def test_row_filter_on_wide_rows(oracle, dims):
     h.Close()
 
 
+@pytest.mark.parametrize("filtered", [False, True])
+def test_one_workgroup_walks_several_tiles_and_chunks(oracle, filtered):
+    """1024 queries x 4 probes = 4,096 pairs, so the scan's grid has one workgroup per (query, list): it walks the three or more
+    256-row tiles of the longest list, the last one partial, in three chunks each (1088 dims: 17 words, 8 + 8 + 1), and the
+    pipeline wraps from a tile's last chunk to the next tile's first.  Without a filter, and with every third row hidden (the scan
+    of the visible lists)"""
+    nq, nprobe, dims, n = 1024, 4, 1088, 6000
+    X, Q, C_ = bqo.parity_case(dims, n=n, nlist=8, nq=nq)
+    lists, codes = bqo.assign(oracle, 0, X, C_), bqo.encode(X)
+    mask = (np.arange(n) % 3 != 0).astype(np.uint8) if filtered else None
+    big = int(np.bincount(lists if mask is None else lists[mask != 0], minlength=8).max())
+    W = bo.words(dims)
+    assert bqo.scan_tiles_x(nq * nprobe, big) == 1
+    assert big > 2 * bqo.TILE and big % bqo.TILE != 0, big
+    assert bqo.chunks(W) >= 2 and W % bqo.chunk_words(W) != 0
+    h = _handle(X, C_)
+    assert np.array_equal(h.assignments(), lists) and np.array_equal(h.codes(), codes)
+    if filtered:
+        h.set_filter(mask)
+        assert h.nvisible() == np.count_nonzero(mask)
+    _check_search(oracle, h, 0, Q, C_, lists, codes, 10, nprobe, mask=mask, ctx=f"several tiles and chunks, filtered {filtered}")
+    h.Close()
+
+
 def test_filter_column_and_combine(oracle, parity):
     X, Q, C_, lists, codes = parity
     n = X.shape[0]

@@ -152,6 +152,24 @@ def test_list_length_edges(oracle):
     h.Close()
 
 
+def test_one_workgroup_walks_several_tiles_and_chunks(oracle):
+    """1024 queries x 4 probes = 4,096 pairs, so the scan's grid has one workgroup per (query, list): it walks the three or more
+    128-row tiles of the longest list, the last one partial, in two chunks each (136 dims at a stride of 144 bytes: nine pieces,
+    8 + 1), and the pipeline wraps from a tile's last chunk to the next tile's first"""
+    nq, nprobe, dims = 1024, 4, 136
+    X, Q, C_, mn, mx = sqo.parity_case(dims, n=2400, nlist=8, nq=nq)
+    lists, codes = sqo.assign(oracle, 0, X, C_), sqo.encode(X, mn, mx)
+    big = int(np.bincount(lists, minlength=8).max())
+    pieces = -(-dims // 16)
+    assert sqo.scan_tiles_x(nq * nprobe, big) == 1
+    assert big > 2 * sqo.TILE and big % sqo.TILE != 0, big
+    assert -(-pieces // sqo.CHUNK) >= 2 and pieces % sqo.CHUNK != 0
+    h = _handle(X, C_, mn, mx)
+    assert np.array_equal(h.assignments(), lists) and np.array_equal(h.codes(), codes)
+    _check_search(oracle, h, 0, Q, C_, lists, codes, mn, mx, 10, nprobe, ctx="several tiles and chunks")
+    h.Close()
+
+
 # 6 ---------------------------------------------------------------------------------------------------------------------------
 def test_the_long_selection(oracle):
     X, Q, C_, mn, mx = sqo.skew_case()

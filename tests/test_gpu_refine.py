@@ -125,6 +125,31 @@ def test_the_largest_shortlist_and_k(f16, dim, nq):
         idx.Close()
 
 
+@pytest.mark.parametrize("metric,order", [(0, 0), (1, 1)])
+@pytest.mark.parametrize("f16", [False, True])
+def test_one_workgroup_walks_several_tiles_and_chunks(f16, metric, order):
+    """1,024 queries (one batch) with shortlists of 1,100 distinct rows: nine 128-row tiles, the last one partial, over four
+    workgroups a query, so the first of them walks tiles 0, 4 and 8, in three chunks each (136 dims: 64 + 64 + 8), and the
+    pipeline wraps from a tile's last chunk to the next tile's first"""
+    TILE, CHUNK, GRID = 128, 64, 4096
+    n, dim, nq, c, k = 3000, 136, 1024, 1100, 10
+    tiles = -(-c // TILE)
+    gx = min(tiles, max(1, -(-GRID // nq)))
+    assert tiles >= 2 * gx + 1 and c % TILE != 0, (tiles, gx)
+    assert -(-dim // CHUNK) >= 2 and dim % CHUNK != 0
+    X, Xf = corpus(136 + f16, n, dim, f16)
+    rng = np.random.default_rng(137)
+    Q = rng.standard_normal((nq, dim)).astype(F)
+    rows = shortlists(rng, nq, c, n)
+    idx = new_index(dim, metric, f16)
+    try:
+        idx.Add(None, X)
+        lab, dist = idx.Refine(Q, rows, k, order)
+        assert_same(lab, dist, *fo.refine(oc, metric, Q, Xf, rows, k, order), f"f16 {f16} metric {metric} order {order}")
+    finally:
+        idx.Close()
+
+
 def test_more_queries_than_a_batch_and_than_a_host_piece():
     """1,030 queries go in two device batches of at most 1,024; 600 shortlists of 16,384 entries go in two host pieces"""
     n, dim = 20000, 4
