@@ -769,7 +769,7 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     nprobe >= nlist gives lb_gpu_index_search_i8 of an int8 index (lb_gpu_index_new_i8) over the same rows,
  *                     bit for bit.  Every other lb_gpu_ivf_* entry point works on all three handle types.
  * Not here: fp16 or int8 centroids, fp16 queries, f32 queries on an int8 handle, a filter given per search call, search combining,
- * lb_gpu_comm_*, removing rows. */
+ * lb_gpu_comm_*. */
 typedef struct lb_gpu_ivf lb_gpu_ivf;
 lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
 lb_gpu_ivf *lb_gpu_ivf_new_f16(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
@@ -822,6 +822,58 @@ int lb_gpu_ivf_last_timing(lb_gpu_ivf *p, float ms[4]);
 /* while profiling is on, a filter call or an add under a filter also records HIP events around the launches that build the
  * visible lists: *ms is the last such build's time (tools/code_filter_bench.py --index ivf) */
 int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms);
+
+/* Removal: rows leave the handle, with the semantics of lb_gpu_index_remove* word for word where they apply.  A removed row keeps
+ * its position, its list and its HBM until lb_gpu_ivf_compact; it is live no more, and nothing but compaction undoes that.
+ *   remove       labels, the values a search returns: ids[row] when the handle holds ids, else the row position.  With ids EVERY
+ *                live row whose id is in the set goes.  _device: the labels are in device memory (on a handle with ids they make a
+ *                round trip through the host to be sorted).
+ *   remove_rows  row POSITIONS whether or not the handle holds ids.
+ *   ignored      an unknown label, a position outside [0, ntotal), -1, a label given twice and a row already removed are ignored,
+ *                not errors.
+ *   n_removed    nullable; the number of rows this call newly removed.
+ *   errors       n == 0 is LB_OK; a NULL handle, n < 0, or n > 0 with a null pointer: LB_ERR_INVALID_ARG, answered before a device
+ *                is touched and with nothing written.
+ *   searches     every lb_gpu_ivf_search* entry point (host and device forms, _ctx, _i8; float32, float16 and int8 handles)
+ *                answers the exact k-NN among the rows of the probed lists that are live AND pass the filter, in ascending
+ *                (distance, row position) order: bit for bit what a fresh handle with the same centroids holding only the live
+ *                rows, in their order, with ids = the old labels and the same filter restricted to them would answer (without ids
+ *                its labels are the survivors' new positions, which old_rows takes back).  The probes do not change: they come
+ *                from the centroids alone.  nprobe >= nlist gives lb_gpu_index_search of a flat index over the same rows after the
+ *                same removals.  Fewer such rows than k: -1 / FLT_MAX padding.  last_search_stats counts the rows scanned, live
+ *                and visible ones only.
+ *   filters      set_filter / filter_* keep taking ntotal values (positions do not move) and never resurrect a removed row;
+ *                set_filter(NULL) leaves exactly the live rows visible; nvisible counts the rows a search can see, live and
+ *                filter-visible.  Should a filter call fail on the device after a removal, searches answer LB_ERR_INTERNAL until
+ *                a filter call succeeds, rather than show a removed row.
+ *   adds         rows added later are live; an add to a handle with removed rows commits rows, lists, live bytes and visible lists
+ *                together or not at all.
+ *   list_sizes, assignments, ntotal keep counting removed rows until compaction; nlive = ntotal - ndeleted.
+ *   cost         a pass over the labels (positions) or over the handle's ids (labels of a handle with ids), then the row list and
+ *                the visible lists are rebuilt as after a filter call; searches then cost what they cost under a filter with the
+ *                same visible rows.
+ * Exclusive against everything else on the handle, as add and the filter calls. */
+int lb_gpu_ivf_remove(lb_gpu_ivf *p, int64_t n, const int64_t *labels, int64_t *n_removed);
+int lb_gpu_ivf_remove_device(lb_gpu_ivf *p, int64_t n, const int64_t *d_labels, int64_t *n_removed);
+int lb_gpu_ivf_remove_rows(lb_gpu_ivf *p, int64_t n, const int64_t *rows, int64_t *n_removed);
+/* ntotal - ndeleted; 0 for a NULL handle */
+int64_t lb_gpu_ivf_nlive(const lb_gpu_ivf *p);
+/* removed rows the handle still holds (ntotal, list_sizes and assignments count them); 0 for a NULL handle */
+int64_t lb_gpu_ivf_ndeleted(const lb_gpu_ivf *p);
+
+/* Compaction: the removed rows leave physically and stably, survivor j being the j-th live row of before, in place (rounds through
+ * a bounded scratch: no second copy of the rows is ever resident).  Afterwards ntotal == nlive and ndeleted == 0; a handle with ids
+ * keeps every label; a handle WITHOUT ids labels by the new positions.  A filter in force survives, its bytes move with the rows.
+ * The handle is then what lb_gpu_ivf_add of the survivors would have made: the same assignments, list sizes and lists, the same
+ * results on every search entry point, the same visible lists under the surviving filter.  No row is assigned again: the list of
+ * a row depends on the row and the centroids alone, so the stored assignments move with the rows.
+ *   old_rows  nullable, room for cap >= nlive entries (else LB_ERR_INVALID_ARG with a last_error text and nothing changed):
+ *             receives each survivor's former position, ascending.
+ *   nothing removed: LB_OK and nothing changes (old_rows: 0, 1, ...).  Everything removed: the handle is empty and takes adds again.
+ *   failure   a refusal before the rows move (an allocation, a list count that does not add up) leaves the handle as it was; once
+ *             they move nothing but a device fault fails the call.
+ * Exclusive against everything else on the handle. */
+int lb_gpu_ivf_compact(lb_gpu_ivf *p, int64_t *old_rows, int64_t cap);
 
 /* ---- IVF-PQ: exact ADC k-NN over the codes of the probed lists ---------------------------------
  * The coarse partition of lb_gpu_ivf_* over the codes of lb_gpu_pq_*: a query skips most rows, and a row costs M bytes instead of

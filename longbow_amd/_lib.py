@@ -238,6 +238,12 @@ SIGNATURES = [
     ("lb_gpu_ivf_set_profiling", _i, [_vp, _i]),
     ("lb_gpu_ivf_last_timing", _i, [_vp, _vp]),
     ("lb_gpu_ivf_last_build_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivf_remove", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivf_remove_device", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivf_remove_rows", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivf_nlive", _i64, [_vp]),
+    ("lb_gpu_ivf_ndeleted", _i64, [_vp]),
+    ("lb_gpu_ivf_compact", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivfpq_new", _vp, [_i, _vp, _sz, _i, _i, _vp, _ip]),
     ("lb_gpu_ivfpq_new_residual", _vp, [_i, _vp, _sz, _i, _i, _vp, _ip]),
     ("lb_gpu_ivfpq_residual", _i, [_vp]),

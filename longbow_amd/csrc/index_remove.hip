@@ -9,6 +9,7 @@
 #include "lb_device.h"
 #include "lb_host.h"
 #include "lb_index.h"
+#include "lb_remove.h"
 
 #include <algorithm>
 #include <vector>
@@ -16,18 +17,6 @@
 using namespace lb;
 
 namespace {
-
-// bytes of gather scratch a round of the compaction may lease; a round's rows follow from it (compact_round_rows)
-constexpr size_t kCompactScratch = (size_t)256 << 20;
-std::atomic<long long> g_compact_round_rows{0}; // test hook: rows per round at most (0: what the scratch bound gives)
-
-int64_t compact_round_rows(size_t per_row)
-{
-    int64_t r = std::max<int64_t>(1, (int64_t)(kCompactScratch / per_row));
-    const long long forced = g_compact_round_rows.load();
-    if (forced > 0) r = std::min<int64_t>(r, forced);
-    return r;
-}
 
 // After the kernel that cleared the bytes: the count, the handle's state and the row list.  d_cnt: the launch's counter.
 int64_t commit_removed(lb_gpu_index *h, const uint32_t *d_cnt)
@@ -50,10 +39,12 @@ int64_t commit_removed(lb_gpu_index *h, const uint32_t *d_cnt)
     return removed;
 }
 
-// d_mask as the kernels will clear it: without a mask in force it holds a cleared filter's bytes, so "every row" is written first
-void mask_for_removal(lb_gpu_index *h)
+// d_live and d_mask as the kernels will clear them (lb_remove.h: `ready`): without a mask in force d_mask holds a cleared filter's
+// bytes, so "every row" is written first
+RemovalArrays arrays_for_removal(lb_gpu_index *h)
 {
     if (!h->has_mask && h->n > 0) LB_HIP(hipMemsetAsync(h->d_mask.get(), 1, (size_t)h->n, h->add_stream));
+    return RemovalArrays{h->d_live.get(), h->d_mask.get()};
 }
 
 // n positions (host or device memory) -> *n_removed; the caller holds the exclusive lock
@@ -64,19 +55,8 @@ int remove_positions(lb_gpu_index *h, int64_t n, const int64_t *rows, bool on_de
         int64_t removed = 0;
         if (h->n > 0) {
             LB_HIP(hipSetDevice(h->device));
-            hipStream_t s = h->add_stream;
-            buf.reset(h->device, 16 + (on_device ? 0 : (size_t)n * sizeof(int64_t)));
-            uint32_t *d_cnt = buf.as<uint32_t>();
-            const int64_t *d_rows = rows;
-            LB_HIP(hipMemsetAsync(d_cnt, 0, 16, s));
-            if (!on_device) {
-                int64_t *up = reinterpret_cast<int64_t *>(buf.as<char>() + 16);
-                LB_HIP(hipMemcpyAsync(up, rows, (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, s));
-                d_rows = up;
-            }
-            mask_for_removal(h);
-            launch_remove_rows(d_rows, n, h->n, h->d_live.get(), h->d_mask.get(), d_cnt, s);
-            removed = commit_removed(h, d_cnt);
+            removed = remove_by_position(h->device, h->add_stream, buf, n, rows, on_device, h->n, [&] { return arrays_for_removal(h); },
+                                         [&](const uint32_t *d_cnt) { return commit_removed(h, d_cnt); });
         }
         if (n_removed) *n_removed = removed;
         return LB_OK;
@@ -91,24 +71,9 @@ int remove_labels(lb_gpu_index *h, int64_t n, const int64_t *labels, int64_t *n_
     return guard(h, h->add_stream, [&]() -> int {
         int64_t removed = 0;
         if (h->n > 0) {
-            // the set: ascending and distinct, without -1 (the padding of a result list names no row)
-            std::vector<int64_t> set(labels, labels + n);
-            std::sort(set.begin(), set.end());
-            set.erase(std::unique(set.begin(), set.end()), set.end());
-            const auto pad = std::lower_bound(set.begin(), set.end(), (int64_t)-1);
-            if (pad != set.end() && *pad == -1) set.erase(pad);
-            if (!set.empty()) {
-                LB_HIP(hipSetDevice(h->device));
-                hipStream_t s = h->add_stream;
-                buf.reset(h->device, 16 + set.size() * sizeof(int64_t));
-                uint32_t *d_cnt = buf.as<uint32_t>();
-                int64_t *d_set = reinterpret_cast<int64_t *>(buf.as<char>() + 16);
-                LB_HIP(hipMemsetAsync(d_cnt, 0, 16, s));
-                LB_HIP(hipMemcpyAsync(d_set, set.data(), set.size() * sizeof(int64_t), hipMemcpyHostToDevice, s));
-                mask_for_removal(h);
-                launch_remove_ids(h->d_ids.get(), h->n, d_set, (int64_t)set.size(), h->d_live.get(), h->d_mask.get(), d_cnt, s);
-                removed = commit_removed(h, d_cnt); // (drains the stream: `set` may go)
-            }
+            LB_HIP(hipSetDevice(h->device));
+            removed = remove_by_id(h->device, h->add_stream, buf, n, labels, h->d_ids.get(), h->n, [&] { return arrays_for_removal(h); },
+                                   [&](const uint32_t *d_cnt) { return commit_removed(h, d_cnt); });
         }
         if (n_removed) *n_removed = removed;
         return LB_OK;
@@ -189,9 +154,6 @@ int lb_gpu_index_compact(lb_gpu_index *h, int64_t *old_rows, int64_t cap)
         const size_t idb = h->has_ids ? sizeof(int64_t) : 0, mb = h->has_filter ? 1 : 0;
         const int64_t R = std::min<int64_t>(compact_round_rows(row_bytes + idb + mb), std::max<int64_t>(nlive, 1));
         // every buffer before the first launch: a refusal leaves the index as it was
-        const int64_t words = compact_scratch_words(n_old);
-        lmap.reset(h->device, (size_t)n_old * sizeof(uint32_t)); // (room for every row: the count is checked below, after the fact)
-        lscr.reset(h->device, (size_t)(words + 1) * sizeof(uint32_t));
         char *gx = nullptr, *gi = nullptr, *gm = nullptr;
         lease_layout(lgather, h->device, [&](Carve cv) {
             gx = cv.take<char>((size_t)R * row_bytes);
@@ -200,33 +162,12 @@ int lb_gpu_index_compact(lb_gpu_index *h, int64_t *old_rows, int64_t cap)
             return cv.off;
         });
         std::vector<uint32_t> hmap(old_rows ? (size_t)nlive : 0);
-        uint32_t *map = lmap.as<uint32_t>(), *scr = lscr.as<uint32_t>();
         // 1. the ascending survivor list, map[j] >= j, and the first removed row: the rows before it stay where they are
-        launch_compact_mask(h->d_live.get(), n_old, map, scr, s);
-        LB_HIP(hipMemsetAsync(scr + words, 0xff, sizeof(uint32_t), s));
-        launch_first_dead(h->d_live.get(), n_old, scr + words, s);
-        uint32_t tail[2] = {0, 0}; // survivors counted, first removed row
-        LB_HIP(hipMemcpyAsync(tail, scr + (words - 1), sizeof tail, hipMemcpyDeviceToHost, s));
-        if (old_rows && nlive > 0) LB_HIP(hipMemcpyAsync(hmap.data(), map, (size_t)nlive * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-        LB_LAUNCH_CHECK();
-        LB_HIP(hipStreamSynchronize(s));
-        if ((int64_t)tail[0] != nlive || (int64_t)tail[1] >= n_old) {
-            h->set_error("compact: %u rows live on the device, %lld on the host", tail[0], (long long)nlive);
-            return LB_ERR_INTERNAL;
-        }
-        // 2. rounds of R destination rows: a launch gathers map[r0, r0 + cnt) into the scratch, a copy puts the scratch at
-        // [r0, r0 + cnt).  No launch reads what it writes, and the sources of every later round lie at or beyond r0 + cnt
-        // (map[j] >= j), which the copy before them on the stream has not touched.
-        char *X = reinterpret_cast<char *>(h->d_X);
-        for (int64_t r0 = (int64_t)tail[1]; r0 < nlive; r0 += R) {
-            const int64_t cnt = std::min(R, nlive - r0);
-            launch_gather_rows(X, map + r0, cnt, row_bytes, gx, h->device, s);
-            if (idb) launch_gather_rows(h->d_ids.get(), map + r0, cnt, idb, gi, h->device, s);
-            if (mb) launch_gather_rows(h->d_mask.get(), map + r0, cnt, mb, gm, h->device, s);
-            LB_HIP(hipMemcpyAsync(X + (size_t)r0 * row_bytes, gx, (size_t)cnt * row_bytes, hipMemcpyDeviceToDevice, s));
-            if (idb) LB_HIP(hipMemcpyAsync(h->d_ids.get() + r0, gi, (size_t)cnt * idb, hipMemcpyDeviceToDevice, s));
-            if (mb) LB_HIP(hipMemcpyAsync(h->d_mask.get() + r0, gm, (size_t)cnt * mb, hipMemcpyDeviceToDevice, s));
-        }
+        int64_t first = 0;
+        if (const int rc = compact_survivors(h, h->device, h->d_live.get(), n_old, nlive, lmap, lscr, hmap, &first, s)) return rc;
+        // 2. the rounds of R destination rows (lb_remove.h: compact_walk)
+        const CompactArray arrays[3] = {{h->d_X, row_bytes, gx}, {h->d_ids.get(), idb, gi}, {h->d_mask.get(), mb, gm}};
+        compact_walk(arrays, 3, lmap.as<uint32_t>(), first, nlive, R, h->device, s);
         // the norms of the rows where they now lie, and with them the statistics over the rows that are left (launch_row_norms
         // gives a row the bits it gave it at Add: one wave per row, whatever the row's position)
         const uint32_t norm_init[2] = {0u, 0x7f800000u};

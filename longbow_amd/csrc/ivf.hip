@@ -121,6 +121,7 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
             lab.reset(p->device, ivf_assign_bytes(n));
             if (const int rc = ivf_assign(p, P, p->n, n, reinterpret_cast<const float *>(d_new), lab, s)) return rc;
         }
+        ivf_add_live(p, total, s); // (a handle that has removed rows: the new ones are live)
         ivf_sort_lists(p, P, total, hist, s);
         if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
         const int nxt = 1 - P.cur;
@@ -143,6 +144,7 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
 int ivf_search_rows(lb_gpu_ivf *p, int64_t nq, const float *d_Q, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels,
                     hipStream_t s, const lb_cancel *ctx, Lease &sc)
 {
+    if (const int st = ivf_live_ok(p)) return st;
     IvfBatch a{};
     a.X = p->dtype == DT_F32 ? p->d_rows.get() : nullptr; // (the plan and the selection read no rows)
     a.D = p->dims;
@@ -247,6 +249,22 @@ int lb_gpu_ivf_filter_float32(lb_gpu_ivf *p, const float *column, int64_t n, flo
     return ivf_filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
 }
 int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms) { return ivf_last_build_timing(p, ms); }
+
+// ---- removal and compaction (lb_ivf_host.h, lb_remove.h) ----------------------------------------------------------------
+int lb_gpu_ivf_remove(lb_gpu_ivf *p, int64_t n, const int64_t *labels, int64_t *n_removed) { return ivf_remove(p, n, labels, n_removed); }
+int lb_gpu_ivf_remove_device(lb_gpu_ivf *p, int64_t n, const int64_t *d_labels, int64_t *n_removed)
+{
+    return ivf_remove_device(p, n, d_labels, n_removed);
+}
+int lb_gpu_ivf_remove_rows(lb_gpu_ivf *p, int64_t n, const int64_t *rows, int64_t *n_removed) { return ivf_remove_rows(p, n, rows, n_removed); }
+int64_t lb_gpu_ivf_nlive(const lb_gpu_ivf *p) { return ivf_nlive(p); }
+int64_t lb_gpu_ivf_ndeleted(const lb_gpu_ivf *p) { return ivf_ndeleted(p); }
+// (the rows of the handle's element type move as bytes; rows() is read under the lock that ivf_compact takes: through the getter)
+int lb_gpu_ivf_compact(lb_gpu_ivf *p, int64_t *old_rows, int64_t cap)
+{
+    if (!p) return LB_ERR_INVALID_ARG;
+    return ivf_compact(p, [p] { return static_cast<void *>(p->rows()); }, (size_t)p->dims * p->elem_bytes(), old_rows, cap);
+}
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
 int lb_gpu_ivf_add(lb_gpu_ivf *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false, DT_F32); }

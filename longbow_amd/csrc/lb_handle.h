@@ -311,6 +311,9 @@ template <class T, class Grow> int handle_reserve(T *p, int64_t n_total, Grow &&
 // themselves into their entries).  The buffers are allocated by the first filter; while
 // `on` they hold room for `capacity` rows (the handle's *_grow keeps them in step through grow) and mask[0, n) are the stored
 // rows' bytes.  They are the handle's own, not pooled: they outlive every call.
+// A handle that can forget rows (lb_ivf_host.h) sets `live` once a row is removed: a byte per row, zero for a removed one.  The
+// mask is then the EFFECTIVE mask, the caller's filter AND live: a filter call ANDs `live` into what it has written before the
+// list is built, and clearing the filter leaves mask = live in force.  For every other handle it stays null and changes nothing.
 struct RowView {
     const uint32_t *rowmap; // nullptr: rows [0, n) as they are
     int64_t n;              // rows (positions) to search
@@ -322,6 +325,7 @@ struct RowFilter {
     DevBuf<uint32_t> scratch; // [compact_scratch_words(capacity)]: launch_compact_mask's
     int64_t n_visible = 0;
     bool on = false;
+    const uint8_t *live = nullptr; // [capacity], the handle's; null: no row has been removed
 
     RowView view(int64_t n) const { return on ? RowView{rowmap.get(), n_visible} : RowView{nullptr, n}; }
 
@@ -397,8 +401,8 @@ template <class Built = NothingToBuild> int filter_set(FilteredHandle *h, const 
     if (!h) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(h->mu);
     RowFilter &f = h->filter;
-    if (!mask) { f.on = false; return LB_OK; }
-    if (n != h->n) {
+    if (!mask && !f.live) { f.on = false; return LB_OK; }
+    if (mask && n != h->n) {
         h->set_error("filter mask has %lld bytes, the handle holds %lld rows", (long long)n, (long long)h->n);
         return LB_ERR_INVALID_ARG;
     }
@@ -407,7 +411,13 @@ template <class Built = NothingToBuild> int filter_set(FilteredHandle *h, const 
         LB_HIP(hipSetDevice(h->device));
         f.reserve(h->n, h->capacity);
         f.on = false; // a failure from here on leaves the handle without a filter, not with half of one
-        if (n > 0) LB_HIP(hipMemcpy(f.mask.get(), mask, (size_t)n, hipMemcpyHostToDevice));
+        if (!mask) { // removed rows stay hidden: the live rows are what is visible
+            n = h->n;
+            if (n > 0) LB_HIP(hipMemcpyAsync(f.mask.get(), f.live, (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+        } else if (n > 0) {
+            LB_HIP(hipMemcpy(f.mask.get(), mask, (size_t)n, hipMemcpyHostToDevice));
+            if (f.live) launch_and_bytes(f.mask.get(), f.live, n, h->stream);
+        }
         f.rebuild(n, h->stream);
         built(h->stream);
         f.on = true;
@@ -447,6 +457,7 @@ int filter_column(FilteredHandle *h, const T *column, int64_t n, T value, int op
             }
             if constexpr (sizeof(T) == 8) launch_match_int64(dcol.as<int64_t>(), n, (int64_t)value, op, d_val, voff, f.mask.get(), comb, s);
             else launch_match_float32(dcol.as<float>(), n, (float)value, op, d_val, voff, f.mask.get(), comb, s);
+            if (f.live && !comb) launch_and_bytes(f.mask.get(), f.live, n, s); // (a mask that is ANDed into holds `live` already)
         }
         f.rebuild(n, s);
         built(s);

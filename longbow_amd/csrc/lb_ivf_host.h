@@ -16,12 +16,21 @@
 //     builds the visible lists of all rows into their pair not in use (ivf_add_visible) and commits them with the rest
 //     (ivf_commit_visible);
 //   * the filter calls rebuild the visible lists through ivf_visible_builder, the `built` hook of filter_set / filter_column;
+//   * rows can be removed (ivf_remove_*, ivf_compact; entry points on lb_gpu_ivf so far).  IvfHandle::live is a second per-row state
+//     beside the caller's filter, allocated at the first removal, which no filter call writes.  From then on filter.mask is the
+//     EFFECTIVE mask, the caller's filter AND live, and filter.on says that an effective mask is in force, a caller's filter or
+//     removed rows or both (has_filter tells which); lists() and sizes() read what they always read.  A removal clears the rows'
+//     bytes in both arrays and rebuilds the row list and the visible lists as a filter call does; the filter calls AND `live`
+//     into the mask they write (filter.live, lb_handle.h); an add makes its rows live; IvfGrowth carries the bytes.  Compaction
+//     gathers the survivors to the front in place (lb_remove.h) and derives the lists from the stored assignments, which move with
+//     the rows: nothing is assigned again;
 //   * ivf_search is the one search loop.  A handle supplies its scratch pieces and the launches between the plan and the
 //     selection; ctx is polled before every launch, a cancelled search publishes no stats, and the events of a profiled search
 //     fall where the handle's timing slots say.
 #pragma once
 #include "lb_handle.h"
 #include "lb_ivf.h"
+#include "lb_remove.h"
 
 #include <atomic>
 #include <functional>
@@ -74,12 +83,17 @@ struct IvfHandle : FilteredHandle { // searches and reads share mu; adds, reserv
     int vcur = 0;
     std::vector<int64_t> h_vsizes;  // [nlist]: what part.h_sizes is to the lists
     float build_ms = 0;             // of the last profiled build of the visible lists (under err_mu): its launches alone
+    // removal: live[r] is zero for a removed row (whole words: launch_remove_rows); n_dead of the n rows are removed.  While
+    // n_dead > 0 filter.live points here and filter.on holds.  has_filter (read while filter.on): a caller's filter is in force
+    DevBuf<uint8_t> live;           // [capacity] from the first removal on
+    int64_t n_dead = 0;
+    bool has_filter = false;
     // what a search walks, and the sizes that go with it
     IvfLists lists() const { return filter.on ? IvfLists{d_voff[vcur].get(), d_vlist[vcur].get(), part.nlist} : part.all_lists(part.cur); }
     const std::vector<int64_t> &sizes() const { return filter.on ? h_vsizes : part.h_sizes; }
     int64_t visible_bytes() const // what the row filter holds on the device
     {
-        return (int64_t)((d_voff[0].count() + d_voff[1].count() + d_vlist[0].count() + d_vlist[1].count()) * 4 + filter.mask.count() +
+        return (int64_t)((d_voff[0].count() + d_voff[1].count() + d_vlist[0].count() + d_vlist[1].count()) * 4 + filter.mask.count() + live.count() +
                          (filter.rowmap.count() + filter.scratch.count()) * 4);
     }
 };
@@ -131,9 +145,12 @@ inline int64_t ivf_grow_to(const CodeHandle *h, const IvfPartition &P, int64_t n
 
 // The share of the partition and of the visible lists in a handle's *_grow to `cap` rows.  The handle stages its own buffers beside
 // it, calls filter.grow and commits them with it: no old buffer is replaced before every new one is allocated and filled.
+constexpr size_t live_bytes(int64_t cap) { return ((size_t)cap + 3) & ~(size_t)3; } // (whole words: launch_remove_rows)
+
 struct IvfGrowth {
     DevBuf<int64_t> ids;
     DevBuf<uint32_t> assign, list[2], vlist[2];
+    DevBuf<uint8_t> live;
     bool want_ids = false, resize = false, filtered = false;
     void stage(const IvfHandle *h, int64_t cap, bool with_ids)
     {
@@ -152,6 +169,10 @@ struct IvfGrowth {
             LB_HIP(hipMemcpy(assign.get(), P.d_assign.get(), (size_t)h->n * 4, hipMemcpyDeviceToDevice));
             LB_HIP(hipMemcpy(list[P.cur].get(), P.d_list[P.cur].get(), (size_t)h->n * 4, hipMemcpyDeviceToDevice));
         }
+        if (h->live) { // a handle that has removed rows keeps their state
+            live.alloc(live_bytes(cap));
+            if (h->n > 0) LB_HIP(hipMemcpy(live.get(), h->live.get(), (size_t)h->n, hipMemcpyDeviceToDevice));
+        }
         if (!filtered) return; // an active filter keeps its visible lists
         for (DevBuf<uint32_t> &v : vlist) v.alloc((size_t)cap);
         if (h->filter.n_visible > 0)
@@ -164,6 +185,10 @@ struct IvfGrowth {
         if (!resize) return;
         P.d_assign = std::move(assign);
         for (int i = 0; i < 2; i++) P.d_list[i] = std::move(list[i]);
+        if (live) {
+            h->live = std::move(live);
+            if (h->filter.live) h->filter.live = h->live.get();
+        }
         if (filtered)
             for (int i = 0; i < 2; i++) h->d_vlist[i] = std::move(vlist[i]);
     }
@@ -257,15 +282,17 @@ inline int64_t ivf_build_visible(IvfHandle *p, const IvfLists &L, int64_t n, int
 }
 
 // what a filter call hands to the shell (lb_handle.h: `built`): the visible lists of the mask it has just written
-inline auto ivf_visible_builder(IvfHandle *p, Lease &scratch)
+// has_filter: what the handle's flag becomes when the build has succeeded
+inline auto ivf_visible_builder(IvfHandle *p, Lease &scratch, bool has_filter)
 {
-    return [p, &scratch](hipStream_t s) {
+    return [p, &scratch, has_filter](hipStream_t s) {
         std::vector<int64_t> vsizes;
         const int to = 1 - p->vcur;
         const int64_t nv = ivf_build_visible(p, p->part.all_lists(p->part.cur), p->n, to, scratch, vsizes, s);
         if (nv != p->filter.n_visible) throw std::logic_error("the visible lists do not hold the visible rows"); // (LB_ERR_INTERNAL)
         p->h_vsizes.swap(vsizes);
         p->vcur = to;
+        p->has_filter = has_filter;
     };
 }
 
@@ -273,12 +300,12 @@ inline auto ivf_visible_builder(IvfHandle *p, Lease &scratch)
 inline int ivf_set_filter(IvfHandle *p, const uint8_t *mask, int64_t n)
 {
     Lease vis;
-    return filter_set(p, mask, n, ivf_visible_builder(p, vis));
+    return filter_set(p, mask, n, ivf_visible_builder(p, vis, mask != nullptr));
 }
 template <class T> int ivf_filter_column(IvfHandle *p, const T *column, int64_t n, T value, int op, const uint8_t *validity, int64_t voff, int combine)
 {
     Lease vis;
-    return filter_column<T>(p, column, n, value, op, validity, voff, combine, ivf_visible_builder(p, vis));
+    return filter_column<T>(p, column, n, value, op, validity, voff, combine, ivf_visible_builder(p, vis, true));
 }
 
 // An add's step under a filter, after the lists of all `total` rows are in the partition's pair not in use: the new rows
@@ -294,6 +321,230 @@ inline void ivf_commit_visible(IvfHandle *p, std::vector<int64_t> &vsizes, int64
     p->h_vsizes.swap(vsizes);
     p->vcur = 1 - p->vcur;
     p->filter.n_visible = nvis;
+}
+
+// ---- removal ----------------------------------------------------------------------------------------------------------------
+// An add's step on a handle that holds live bytes: the new rows [p->n, total) are live (their bytes belong to nobody until the
+// commit).  Enqueues on s, ahead of a step of the add that drains it.
+inline void ivf_add_live(IvfHandle *p, int64_t total, hipStream_t s)
+{
+    if (p->live && total > p->n) LB_HIP(hipMemsetAsync(p->live.get() + p->n, 0xff, (size_t)(total - p->n), s));
+}
+
+// Removed rows are hidden by the effective mask alone.  A filter call or a removal that failed half way (lb_handle.h: "leaves the
+// handle without a filter") must not show them again: a search refuses until a filter call has put the mask back.
+inline int ivf_live_ok(IvfHandle *p)
+{
+    if (p->n_dead == 0 || p->filter.on) return LB_OK;
+    p->set_error("a failed call left the handle's %lld removed rows without their mask: set_filter puts it back", (long long)p->n_dead);
+    return LB_ERR_INTERNAL;
+}
+
+// lb_remove.h's `ready`: the live bytes (allocated by the first removal), the mask as the kernel will clear it (without one in
+// force, "every row" is written first) and every buffer of the rebuild behind the kernel, so that once bytes are cleared nothing
+// but a device fault fails the call.  vis: the caller's lease for ivf_build_visible.
+inline RemovalArrays ivf_removal_ready(IvfHandle *p, Lease &vis, hipStream_t s)
+{
+    RowFilter &f = p->filter;
+    if (!p->live) {
+        DevBuf<uint8_t> nl;
+        nl.alloc(live_bytes(p->capacity));
+        LB_HIP(hipMemsetAsync(nl.get(), 0xff, (size_t)p->n, s));
+        p->live = std::move(nl);
+    }
+    if (!f.on) {
+        f.reserve(p->n, p->capacity);
+        LB_HIP(hipMemsetAsync(f.mask.get(), 1, (size_t)p->n, s));
+    }
+    const int to = 1 - p->vcur;
+    if (p->d_vlist[to].count() < (size_t)p->capacity) p->d_vlist[to].alloc((size_t)p->capacity);
+    vis.reset(p->device, ivf_visible_scratch_bytes(p->n));
+    return RemovalArrays{p->live.get(), f.mask.get()};
+}
+
+// lb_remove.h's `commit`: the count; if rows went, the handle's state, then the row list and the visible lists as a filter call
+// builds them, into the pair not in use.  A call that removes nothing commits nothing.
+inline int64_t ivf_commit_removed(IvfHandle *p, const uint32_t *d_cnt, Lease &vis, hipStream_t s)
+{
+    uint32_t removed = 0;
+    LB_LAUNCH_CHECK();
+    LB_HIP(hipMemcpyAsync(&removed, d_cnt, sizeof removed, hipMemcpyDeviceToHost, s));
+    LB_HIP(hipStreamSynchronize(s));
+    if (removed == 0) return 0;
+    RowFilter &f = p->filter;
+    const bool had_filter = f.on && p->has_filter;
+    p->n_dead += removed;
+    f.live = p->live.get();
+    f.on = false; // as filter_set: a failure from here on leaves the handle without its mask (ivf_live_ok)
+    f.rebuild(p->n, s);
+    ivf_visible_builder(p, vis, had_filter)(s);
+    f.on = true;
+    return removed;
+}
+
+// n positions (host or device memory) -> *n_removed; the caller holds the exclusive lock
+inline int ivf_remove_positions(IvfHandle *p, int64_t n, const int64_t *rows, bool on_device, int64_t *n_removed)
+{
+    Lease buf, vis;
+    return guard(p, p->stream, [&]() -> int {
+        int64_t removed = 0;
+        if (p->n > 0) {
+            LB_HIP(hipSetDevice(p->device));
+            hipStream_t s = p->stream;
+            removed = remove_by_position(p->device, s, buf, n, rows, on_device, p->n, [&] { return ivf_removal_ready(p, vis, s); },
+                                         [&](const uint32_t *d_cnt) { return ivf_commit_removed(p, d_cnt, vis, s); });
+        }
+        if (n_removed) *n_removed = removed;
+        return LB_OK;
+    });
+}
+
+// n labels of the host; the caller holds the exclusive lock
+inline int ivf_remove_labels(IvfHandle *p, int64_t n, const int64_t *labels, int64_t *n_removed)
+{
+    if (!p->part.has_ids) return ivf_remove_positions(p, n, labels, false, n_removed); // the labels of such a handle are its positions
+    Lease buf, vis;
+    return guard(p, p->stream, [&]() -> int {
+        int64_t removed = 0;
+        if (p->n > 0) {
+            LB_HIP(hipSetDevice(p->device));
+            hipStream_t s = p->stream;
+            removed = remove_by_id(p->device, s, buf, n, labels, p->part.d_ids.get(), p->n, [&] { return ivf_removal_ready(p, vis, s); },
+                                   [&](const uint32_t *d_cnt) { return ivf_commit_removed(p, d_cnt, vis, s); });
+        }
+        if (n_removed) *n_removed = removed;
+        return LB_OK;
+    });
+}
+
+// The entry points (the statement is include/longbow_gpu.h's, above lb_gpu_ivf_remove).  Argument checks answer before a device
+// is touched.
+inline int ivf_remove(IvfHandle *p, int64_t n, const int64_t *labels, int64_t *n_removed)
+{
+    if (!p || n < 0 || (n > 0 && !labels)) return LB_ERR_INVALID_ARG;
+    if (n == 0) { if (n_removed) *n_removed = 0; return LB_OK; }
+    std::unique_lock<std::shared_mutex> g(p->mu);
+    return ivf_remove_labels(p, n, labels, n_removed);
+}
+inline int ivf_remove_rows(IvfHandle *p, int64_t n, const int64_t *rows, int64_t *n_removed)
+{
+    if (!p || n < 0 || (n > 0 && !rows)) return LB_ERR_INVALID_ARG;
+    if (n == 0) { if (n_removed) *n_removed = 0; return LB_OK; }
+    std::unique_lock<std::shared_mutex> g(p->mu);
+    return ivf_remove_positions(p, n, rows, false, n_removed);
+}
+inline int ivf_remove_device(IvfHandle *p, int64_t n, const int64_t *d_labels, int64_t *n_removed)
+{
+    if (!p || n < 0 || (n > 0 && !d_labels)) return LB_ERR_INVALID_ARG;
+    if (n == 0) { if (n_removed) *n_removed = 0; return LB_OK; }
+    std::unique_lock<std::shared_mutex> g(p->mu);
+    if (!p->part.has_ids) return ivf_remove_positions(p, n, d_labels, true, n_removed);
+    // ids: the set is sorted on the host (n is small beside ntotal, and this is on no search's path)
+    std::vector<int64_t> host;
+    const int rc = guard(p, nullptr, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        host.resize((size_t)n);
+        LB_HIP(hipMemcpy(host.data(), d_labels, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToHost));
+        return LB_OK;
+    });
+    return rc != LB_OK ? rc : ivf_remove_labels(p, n, host.data(), n_removed);
+}
+inline int64_t ivf_nlive(const IvfHandle *p)
+{
+    if (!p) return 0;
+    std::shared_lock<std::shared_mutex> g(const_cast<IvfHandle *>(p)->mu);
+    return p->n - p->n_dead;
+}
+inline int64_t ivf_ndeleted(const IvfHandle *p)
+{
+    if (!p) return 0;
+    std::shared_lock<std::shared_mutex> g(const_cast<IvfHandle *>(p)->mu);
+    return p->n_dead;
+}
+
+// Compaction of a handle whose rows are row_bytes each (any element type) at rows(), which is called under the handle's lock.
+// Everything that can be refused happens before the first row
+// moves: every buffer and lease, the survivor list, the survivors' assignments gathered into a scratch, the new lists sorted from
+// it into the pair not in use, their sizes read back and checked.  Then the rounds (lb_remove.h) move rows, ids and, under a
+// caller's filter, the mask bytes; the assignments are copied in, `live` is reset, the visible lists of a surviving filter are
+// built from the new lists, and the commit comes last.  No row is assigned again: its list moves with it.
+template <class Rows> int ivf_compact(IvfHandle *p, Rows &&rows, size_t row_bytes, int64_t *old_rows, int64_t cap)
+{
+    if (!p) return LB_ERR_INVALID_ARG;
+    std::unique_lock<std::shared_mutex> g(p->mu);
+    IvfPartition &P = p->part;
+    const int64_t n_old = p->n, nlive = p->n - p->n_dead;
+    if (old_rows && cap < nlive) {
+        p->set_error("old_rows has room for %lld rows, the handle holds %lld live ones", (long long)cap, (long long)nlive);
+        return LB_ERR_INVALID_ARG;
+    }
+    if (p->n_dead == 0) { // nothing to do: every row stays where it is
+        if (old_rows)
+            for (int64_t j = 0; j < nlive; j++) old_rows[j] = j;
+        return LB_OK;
+    }
+    // the survivor list, launch_compact_mask's scratch, a round's rows, the survivors' assignments, the sort's and the visible lists'
+    Lease lmap, lscr, lgather, lassign, hist, vis;
+    return guard(p, p->stream, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        hipStream_t s = p->stream;
+        RowFilter &f = p->filter;
+        const bool keep_filter = f.on && p->has_filter; // a caller's filter survives, its bytes move with the rows
+        const size_t idb = P.has_ids ? sizeof(int64_t) : 0, mb = keep_filter ? 1 : 0;
+        const int64_t R = std::min<int64_t>(compact_round_rows(row_bytes + idb + mb), std::max<int64_t>(nlive, 1));
+        const int nxt = 1 - P.cur, vto = 1 - p->vcur;
+        // 0. every buffer before the first launch
+        char *gx = nullptr, *gi = nullptr, *gm = nullptr;
+        lease_layout(lgather, p->device, [&](Carve cv) {
+            gx = cv.take<char>((size_t)R * row_bytes);
+            gi = cv.take<char>((size_t)R * idb);
+            gm = cv.take<char>((size_t)R * mb);
+            return cv.off;
+        });
+        lassign.reset(p->device, (size_t)std::max<int64_t>(nlive, 1) * sizeof(uint32_t));
+        hist.reset(p->device, ivf_sort_hist_words(nlive, P.nlist) * 4);
+        if (keep_filter) {
+            if (p->d_vlist[vto].count() < (size_t)p->capacity) p->d_vlist[vto].alloc((size_t)p->capacity);
+            vis.reset(p->device, ivf_visible_scratch_bytes(nlive));
+        }
+        std::vector<uint32_t> hmap(old_rows ? (size_t)nlive : 0);
+        std::vector<int64_t> sizes, vsizes;
+        // 1. the ascending survivor list, map[j] >= j, and the first removed row
+        int64_t first = 0;
+        if (const int rc = compact_survivors(p, p->device, p->live.get(), n_old, nlive, lmap, lscr, hmap, &first, s)) return rc;
+        const uint32_t *map = lmap.as<uint32_t>();
+        // 2. the survivors' lists, in their new order; 3. the lists over them, into the pair not in use; 4. their sizes, checked
+        uint32_t *d_newassign = lassign.as<uint32_t>();
+        launch_gather_rows(P.d_assign.get(), map, nlive, sizeof(uint32_t), d_newassign, p->device, s);
+        LB_HIP(launch_ivf_sort(d_newassign, nlive, P.nlist, hist.as<uint32_t>(), P.d_off[nxt].get(), P.d_list[nxt].get(), s));
+        if (const int rc = ivf_read_lists(p, P, nlive, sizes, s)) return rc;
+        // 5. the rows move, in place: from here on nothing but a device fault fails the call
+        const CompactArray arrays[3] = {{rows(), row_bytes, gx}, {P.d_ids.get(), idb, gi}, {f.mask.get(), mb, gm}};
+        compact_walk(arrays, 3, map, first, nlive, R, p->device, s);
+        if (nlive > 0) {
+            LB_HIP(hipMemcpyAsync(P.d_assign.get(), d_newassign, (size_t)nlive * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+            LB_HIP(hipMemsetAsync(p->live.get(), 0xff, (size_t)nlive, s));
+        }
+        int64_t nvis = 0;
+        if (keep_filter) { // the row list and the visible lists of the mask where it now lies, from the new lists
+            f.rebuild(nlive, s);
+            nvis = ivf_build_visible(p, P.all_lists(nxt), nlive, vto, vis, vsizes, s);
+            if (nvis != f.n_visible) throw std::logic_error("the visible lists do not hold the visible rows");
+        }
+        LB_LAUNCH_CHECK();
+        LB_HIP(hipStreamSynchronize(s));
+        // 6. commit
+        P.h_sizes.swap(sizes);
+        P.cur = nxt;
+        p->n = nlive;
+        p->n_dead = 0;
+        f.live = nullptr;
+        f.on = keep_filter; // (without a caller's filter there is no mask any more)
+        p->has_filter = keep_filter;
+        if (keep_filter) ivf_commit_visible(p, vsizes, nvis);
+        for (int64_t j = 0; j < (int64_t)hmap.size(); j++) old_rows[j] = (int64_t)hmap[(size_t)j];
+        return LB_OK;
+    });
 }
 
 // ---- the search loop --------------------------------------------------------------------------------------------------------

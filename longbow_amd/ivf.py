@@ -6,7 +6,8 @@ probed lists the result is the exact k-NN among their rows, bit for bit in the r
 list probed it equals gpu.Index.Search.  include/longbow_gpu.h states the semantics.
 
   IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats, and the
-                 row filter (set_filter / filter_column / nvisible); dtype=DataType.Float16 holds the rows as float16, 2 bytes an
+                 row filter (set_filter / filter_column / nvisible), removal (remove / remove_rows / remove_device / nlive /
+                 ndeleted) and compact(); dtype=DataType.Float16 holds the rows as float16, 2 bytes an
                  element, and answers as a float32 handle over the widened rows does, bit for bit
   IVFFlatInt8    the same handle over signed int8 rows (lb_gpu_ivf_new_i8), one byte an element, searched with int8 queries in
                  the reference's DataTypeInt8 arithmetic (L2 and dot); with every list probed it equals the flat int8 index
@@ -114,7 +115,50 @@ def rows_f16(vectors, dims):
     return v
 
 
-class IVFFlat(RowFilterMixin, IVFBase):
+class RemovalMixin:
+    """lb_gpu_ivf_remove* / _nlive / _ndeleted / _compact on a handle of IVFBase: written once for IVFFlat and IVFFlatInt8"""
+
+    def _remove(self, entry, values):
+        values = np.ascontiguousarray(values, np.int64).reshape(-1)
+        removed = C.c_int64(0)
+        self._check(self._fn(entry)(self._h, values.size, values.ctypes.data if values.size else None, C.byref(removed)))
+        return int(removed.value)
+
+    def remove(self, labels):
+        """Remove the rows with these labels (the values search returns: the ids given to add, else row positions) -> the number
+        of rows newly removed.  Every live row under a given id goes; unknown labels, -1, repeats and rows already removed are
+        ignored.  Searches stop returning them at once; the rows keep their positions, their lists and their memory until
+        compact()."""
+        return self._remove("remove", labels)
+
+    def remove_rows(self, rows):
+        """Remove by row position, whether or not the handle holds ids"""
+        return self._remove("remove_rows", rows)
+
+    def remove_device(self, n, d_labels):
+        """remove() of n int64 labels in device memory"""
+        removed = C.c_int64(0)
+        self._check(self._fn("remove_device")(self._h, n, d_labels, C.byref(removed)))
+        return int(removed.value)
+
+    def compact(self):
+        """Drop the removed rows physically, keeping the survivors' order and their lists -> old_rows int64 [nlive]: each
+        survivor's former position.  ids are kept; a handle without ids labels by the new positions from here on.  A filter in
+        force survives."""
+        old = np.empty(self.nlive(), np.int64)
+        self._check(self._fn("compact")(self._h, old.ctypes.data, old.size))
+        return old
+
+    def nlive(self):
+        """rows a search can return without a filter: ntotal - ndeleted()"""
+        return int(self._fn("nlive")(self._h))
+
+    def ndeleted(self):
+        """removed rows the handle still holds; ntotal, list_sizes and assignments count them until compact()"""
+        return int(self._fn("ndeleted")(self._h))
+
+
+class IVFFlat(RemovalMixin, RowFilterMixin, IVFBase):
     """lb_gpu_ivf: metric 0 L2 / 1 cosine / 2 dot, order 0 SEQ / 1 UNROLL4, centroids f32 [nlist, dims].  Under a row filter
     (RowFilterMixin) the probes stay as they are and a search sees the visible rows of the probed lists alone.
     dtype: DataType.Float32, or DataType.Float16 (lb_gpu_ivf_new_f16): the rows are held as float16.  Such a handle's add takes
@@ -183,7 +227,7 @@ def rows_i8(vectors, dims):
     return v
 
 
-class IVFFlatInt8(RowFilterMixin, IVFBase):
+class IVFFlatInt8(RemovalMixin, RowFilterMixin, IVFBase):
     """lb_gpu_ivf over signed int8 rows (lb_gpu_ivf_new_i8): metric 0 L2 / 2 dot, centroids f32 [nlist, dims]; order 0 SEQ /
     1 UNROLL4 is the coarse index's and decides lists and probes alone.  add, search and their device-pointer forms take int8
     rows and int8 queries, np.int8 arrays only (converting other data here would change the vectors silently).  The distances are
@@ -360,6 +404,21 @@ class IVFFlatIndex:
 
     def nvisible(self):
         return self._built().nvisible()
+
+    def Remove(self, ids):
+        """the reference's Delete / DeleteBatch: the rows under these ids go -> the number newly removed.  Size() keeps counting
+        them until Compact()."""
+        return self._built().remove(ids)
+
+    def Compact(self):
+        """-> each survivor's former position"""
+        return self._built().compact()
+
+    def nlive(self):
+        return self._built().nlive()
+
+    def ndeleted(self):
+        return self._built().ndeleted()
 
     def Save(self, path):
         raise NotImplementedError("ivf_flat: Save is not implemented (the reference's writes a marker file only)")
