@@ -1,6 +1,7 @@
 """Inputs of the IVF-Flat removal tests (tests/test_gpu_ivf_remove.py on the GPU, tests/test_ivf_remove_semantics.py on the CPU),
 built from tests/ivf_oracle.py (parity_case, edge_case, skew_case), tests/ivf_filter_cases.py (keep_per_list) and
-tests/remove_cases.py (fractions, ids, overlap sets).  Seeded, never written to.
+tests/remove_cases.py (fractions, ids, overlap sets).  Seeded, never written to.  Also same_handles, the comparison of a handle
+with a fresh one of its survivors that the GPU file shares with tests/test_gpu_lifecycle.py.
 
 The expected result needs no oracle of its own: a removed row is a row in no list.  ivf_oracle.search with the removed rows' lists
 set to -1, as ivf_filter_cases.search_filtered does for hidden rows, probes the same lists (the probes come from the centroids
@@ -13,6 +14,7 @@ from tests import ivf_filter_cases as fc
 from tests import ivf_i8_oracle as o8
 from tests import ivf_oracle as io
 from tests import remove_cases as rc
+from tests.gpu_util import assert_same
 
 F = np.float32
 NPROBES = (1, 4, 16)
@@ -38,6 +40,20 @@ def search_live(oracle, metric, order, Q, X, C, lists, live, k, nprobe, ids=None
 
 def search_live_i8(oracle, metric, order, Q8, X8, C, lists, live, k, nprobe, ids=None, mask=None):
     return o8.search(oracle, metric, order, Q8, X8, C, lists, k, nprobe, ids=ids, mask=visible(live, mask).astype(np.uint8))
+
+
+def counts(h):
+    return h.ntotal, h.nlive(), h.ndeleted()
+
+
+def same_handles(h, fresh, Q, ctx, ks=KS, nprobes=NPROBES):
+    """two IVF-Flat handles on a GPU answer alike: h (compacted) is what an add of the survivors (fresh) would have made"""
+    assert counts(h) == counts(fresh) and h.nvisible() == fresh.nvisible(), ctx
+    assert np.array_equal(h.assignments(), fresh.assignments()) and np.array_equal(h.list_sizes(), fresh.list_sizes()), ctx
+    for nprobe in nprobes:
+        for k in ks:
+            assert_same(*h.search(Q, k, nprobe), *fresh.search(Q, k, nprobe), f"{ctx} nprobe {nprobe} k {k}")
+            assert h.last_search_stats() == fresh.last_search_stats(), ctx
 
 
 @functools.lru_cache(maxsize=None)

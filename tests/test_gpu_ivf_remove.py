@@ -66,8 +66,7 @@ def _check(oracle, h, kind, metric, order, Q, W, C_, lists, live, ks, nprobe, id
     return scanned
 
 
-def _counts(h):
-    return h.ntotal, h.nlive(), h.ndeleted()
+_counts = vc.counts
 
 
 def _flat(kind, dim, metric, order, rows):
@@ -332,16 +331,6 @@ def test_ids(oracle):
 
 
 # ---- f. compaction ----------------------------------------------------------------------------------------------------------
-def _same_handles(h, fresh, Q, ctx, ks=vc.KS, nprobes=vc.NPROBES):
-    """the compacted handle is what an add of the survivors would have made"""
-    assert _counts(h) == _counts(fresh) and h.nvisible() == fresh.nvisible(), ctx
-    assert np.array_equal(h.assignments(), fresh.assignments()) and np.array_equal(h.list_sizes(), fresh.list_sizes()), ctx
-    for nprobe in nprobes:
-        for k in ks:
-            assert_same(*h.search(Q, k, nprobe), *fresh.search(Q, k, nprobe), f"{ctx} nprobe {nprobe} k {k}")
-            assert h.last_search_stats() == fresh.last_search_stats(), ctx
-
-
 def _search_device(h, Q, k, nprobe):
     import torch
     dQ = torch.from_numpy(np.array(Q, F)).cuda()  # (a copy: the shared inputs are read-only)
@@ -377,22 +366,22 @@ def test_compact(oracle, name, with_ids, with_filter):
         assert np.array_equal(old, keep)
         assert _counts(h) == (keep.size, keep.size, 0)
         assert np.array_equal(h.assignments(), lists[keep]) and np.array_equal(h.list_sizes(), np.bincount(lists[keep], minlength=C_.shape[0]))
-        _same_handles(h, fresh, Q, f"{name} compacted")
+        vc.same_handles(h, fresh, Q, f"{name} compacted")
         _check(oracle, h, "f32", 0, 0, Q, X[keep], C_, lists[keep], np.ones(keep.size, np.uint8), (10,), 4, ids=ls, mask=ms, ctx=f"{name}: the oracle over the survivors")
         assert_same(*_search_device(h, Q, 10, 4), *fresh.search(Q, 10, 4), f"{name}: the device-pointer search")
         assert np.array_equal(h.compact(), np.arange(keep.size)) and _counts(h) == (keep.size, keep.size, 0)  # a second one: a no-op
-        _same_handles(h, fresh, Q, f"{name} compacted twice", ks=(10,), nprobes=(4,))
+        vc.same_handles(h, fresh, Q, f"{name} compacted twice", ks=(10,), nprobes=(4,))
         if with_filter:  # the filter that came along can be cleared and replaced
             h.set_filter(None)
             fresh.set_filter(None)
-            _same_handles(h, fresh, Q, f"{name} filter cleared", ks=(10,), nprobes=(4,))
+            vc.same_handles(h, fresh, Q, f"{name} filter cleared", ks=(10,), nprobes=(4,))
         # adds work afterwards, and removals again
         extra = np.random.default_rng(11).standard_normal((700, X.shape[1])).astype(F)
         eids = None if ids is None else np.arange(700, dtype=np.int64) + 7 * 10 ** 12
         for x in (h, fresh):
             x.add(extra, eids)
             assert x.remove_rows([0, keep.size + 5]) == 2
-        _same_handles(h, fresh, Q, f"{name}: add and remove after compaction", ks=(10,), nprobes=(4, 16))
+        vc.same_handles(h, fresh, Q, f"{name}: add and remove after compaction", ks=(10,), nprobes=(4, 16))
         X3 = np.concatenate([X[keep], extra])
         l3 = np.concatenate([lists[keep], io.assign(oracle, 0, 0, extra, C_)])
         live3 = vc.live_mask(X3.shape[0], [0, keep.size + 5])
@@ -468,10 +457,10 @@ def test_compact_rounds(oracle, kind, name, round_rows):
             lib.lb_debug_set_compact_round_rows(0)
         assert np.array_equal(old, keep) and _counts(h) == (keep.size, keep.size, 0)
         fresh.set_filter(m[keep])
-        _same_handles(h, fresh, Q, f"{kind} {name} rounds of {round_rows}, filtered", ks=(10,), nprobes=(2, C_.shape[0]))
+        vc.same_handles(h, fresh, Q, f"{kind} {name} rounds of {round_rows}, filtered", ks=(10,), nprobes=(2, C_.shape[0]))
         h.set_filter(None)
         fresh.set_filter(None)
-        _same_handles(h, fresh, Q, f"{kind} {name} rounds of {round_rows}", ks=(10, 2048), nprobes=(C_.shape[0],))  # every row arrived
+        vc.same_handles(h, fresh, Q, f"{kind} {name} rounds of {round_rows}", ks=(10, 2048), nprobes=(C_.shape[0],))  # every row arrived
     finally:
         h.Close()
         fresh.Close()
