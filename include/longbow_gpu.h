@@ -1000,6 +1000,26 @@ int lb_gpu_ivfpq_last_timing(lb_gpu_ivfpq *p, float ms[5]);
 /* as lb_gpu_ivf_last_build_timing: the last profiled build of the visible lists (tools/code_filter_bench.py --index ivfpq) */
 int lb_gpu_ivfpq_last_build_timing(lb_gpu_ivfpq *p, float *ms);
 
+/* Removal and compaction: the statement above lb_gpu_ivf_remove and lb_gpu_ivf_compact holds word for word, "rows" being the
+ * handle's codes; plain and residual handles alike.  What differs:
+ *   searches     every lb_gpu_ivfpq_search* entry point answers the exact ADC k-NN (on a residual handle under the table of each
+ *                probed list) among the rows of the probed lists that are live AND pass the filter: bit for bit what a fresh
+ *                handle with the same codebooks and centroids answers when it holds only the survivors' codes, in their order,
+ *                with ids = the old labels.  With every list probed a plain handle equals lb_gpu_pq_search over the surviving
+ *                codes.  last_search_stats counts live, visible rows only.
+ *   codes        are kept, never recomputed: a removed row keeps its position, its list and its M code bytes until compaction, and
+ *                get_codes, list_sizes, assignments and ntotal keep counting it.  Compaction moves codes, ids, assignments and a
+ *                surviving filter's bytes together and then writes the list-major copy from the moved codes and the new lists; no
+ *                row is assigned or encoded again.  A residual code is of the row less ITS list's centroid, and the list moves
+ *                with the row, so it stays the code lb_gpu_ivfpq_add of the survivor's vector would produce.  Afterwards
+ *                get_codes equals the old codes taken at old_rows. */
+int lb_gpu_ivfpq_remove(lb_gpu_ivfpq *p, int64_t n, const int64_t *labels, int64_t *n_removed);
+int lb_gpu_ivfpq_remove_device(lb_gpu_ivfpq *p, int64_t n, const int64_t *d_labels, int64_t *n_removed);
+int lb_gpu_ivfpq_remove_rows(lb_gpu_ivfpq *p, int64_t n, const int64_t *rows, int64_t *n_removed);
+int64_t lb_gpu_ivfpq_nlive(const lb_gpu_ivfpq *p);
+int64_t lb_gpu_ivfpq_ndeleted(const lb_gpu_ivfpq *p);
+int lb_gpu_ivfpq_compact(lb_gpu_ivfpq *p, int64_t *old_rows, int64_t cap);
+
 /* ---- IVF-SQ8: exact integer k-NN over the codes of the probed lists ----------------------------
  * The coarse partition of lb_gpu_ivf_* over the codes of lb_gpu_sq8_* (FAISS's "IVF...,SQ8"): a query skips most rows, and a row
  * costs dims bytes instead of 4 * dims.  Nothing is approximate beyond the SQ8 codes themselves and WHICH lists are probed: given
@@ -1099,6 +1119,23 @@ int lb_gpu_ivfsq8_set_profiling(lb_gpu_ivfsq8 *p, int enable);
 int lb_gpu_ivfsq8_last_timing(lb_gpu_ivfsq8 *p, float ms[5]);
 /* as lb_gpu_ivf_last_build_timing: the last profiled build of the visible lists */
 int lb_gpu_ivfsq8_last_build_timing(lb_gpu_ivfsq8 *p, float *ms);
+
+/* Removal and compaction: the statement above lb_gpu_ivf_remove and lb_gpu_ivf_compact holds word for word, "rows" being the
+ * handle's codes.  What differs:
+ *   searches     every lb_gpu_ivfsq8_search* entry point answers the exact k-NN under the integer S among the rows of the probed
+ *                lists that are live AND pass the filter: bit for bit what a fresh handle with the same bounds and centroids
+ *                answers when it holds only the survivors' codes, in their order, with ids = the old labels.  With every list
+ *                probed it equals lb_gpu_sq8_search over the surviving codes.  last_search_stats counts live, visible rows only.
+ *   codes        are kept, never recomputed: a removed row keeps its position, its list and its dims code bytes until compaction,
+ *                and get_codes, list_sizes, assignments and ntotal keep counting it.  Compaction moves codes, ids, assignments
+ *                and a surviving filter's bytes together; no row is assigned or encoded again.  Afterwards get_codes equals the
+ *                old codes taken at old_rows. */
+int lb_gpu_ivfsq8_remove(lb_gpu_ivfsq8 *p, int64_t n, const int64_t *labels, int64_t *n_removed);
+int lb_gpu_ivfsq8_remove_device(lb_gpu_ivfsq8 *p, int64_t n, const int64_t *d_labels, int64_t *n_removed);
+int lb_gpu_ivfsq8_remove_rows(lb_gpu_ivfsq8 *p, int64_t n, const int64_t *rows, int64_t *n_removed);
+int64_t lb_gpu_ivfsq8_nlive(const lb_gpu_ivfsq8 *p);
+int64_t lb_gpu_ivfsq8_ndeleted(const lb_gpu_ivfsq8 *p);
+int lb_gpu_ivfsq8_compact(lb_gpu_ivfsq8 *p, int64_t *old_rows, int64_t cap);
 
 /* ---- IVF-BQ: exact Hamming k-NN over the codes of the probed lists -----------------------------
  * The coarse partition of lb_gpu_ivf_* over the sign-bit codes of lb_gpu_bq_*: a query skips most rows, and a row costs

@@ -273,6 +273,12 @@ SIGNATURES = [
     ("lb_gpu_ivfpq_set_profiling", _i, [_vp, _i]),
     ("lb_gpu_ivfpq_last_timing", _i, [_vp, _vp]),
     ("lb_gpu_ivfpq_last_build_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq_remove", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq_remove_device", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq_remove_rows", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq_nlive", _i64, [_vp]),
+    ("lb_gpu_ivfpq_ndeleted", _i64, [_vp]),
+    ("lb_gpu_ivfpq_compact", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivfsq8_new", _vp, [_i, _i, _vp, _vp, _i, _i, _vp, _ip]),
     ("lb_gpu_ivfsq8_free", None, [_vp]),
     ("lb_gpu_ivfsq8_last_error", C.c_char_p, [_vp]),
@@ -300,6 +306,12 @@ SIGNATURES = [
     ("lb_gpu_ivfsq8_set_profiling", _i, [_vp, _i]),
     ("lb_gpu_ivfsq8_last_timing", _i, [_vp, _vp]),
     ("lb_gpu_ivfsq8_last_build_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfsq8_remove", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfsq8_remove_device", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfsq8_remove_rows", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfsq8_nlive", _i64, [_vp]),
+    ("lb_gpu_ivfsq8_ndeleted", _i64, [_vp]),
+    ("lb_gpu_ivfsq8_compact", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivfbq_new", _vp, [_i, _i, _i, _i, _vp, _ip]),
     ("lb_gpu_ivfbq_free", None, [_vp]),
     ("lb_gpu_ivfbq_last_error", C.c_char_p, [_vp]),

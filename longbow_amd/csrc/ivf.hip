@@ -263,7 +263,7 @@ int64_t lb_gpu_ivf_ndeleted(const lb_gpu_ivf *p) { return ivf_ndeleted(p); }
 int lb_gpu_ivf_compact(lb_gpu_ivf *p, int64_t *old_rows, int64_t cap)
 {
     if (!p) return LB_ERR_INVALID_ARG;
-    return ivf_compact(p, [p] { return static_cast<void *>(p->rows()); }, (size_t)p->dims * p->elem_bytes(), old_rows, cap);
+    return ivf_compact(p, [p] { return static_cast<void *>(p->rows()); }, (size_t)p->dims * p->elem_bytes(), old_rows, cap, ivf_no_relist);
 }
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------

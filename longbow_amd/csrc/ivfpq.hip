@@ -97,6 +97,7 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
         }
         // 4. the lists of all rows and 5. their codes in list order, into the pair not in use
         const int nxt = 1 - P.cur;
+        ivf_add_live(p, total, s); // (a handle that has removed rows: the new ones are live)
         ivf_sort_lists(p, P, total, hist, s);
         launch_ivfpq_permute(p->d_codes.get(), P.d_list[nxt].get(), total, p->M, p->d_lcodes[nxt].get(), s);
         if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
@@ -165,6 +166,7 @@ int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfBatch &a, int64_t nq, const floa
 int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
                      const lb_cancel *ctx, Lease &sc)
 {
+    if (const int st = ivf_live_ok(p)) return st;
     const IvfPartition &P = p->part;
     IvfBatch a{};
     a.X = nullptr; // (only the plan and the selection take the batch as the IVF-Flat kernels do: neither reads rows)
@@ -275,6 +277,26 @@ int lb_gpu_ivfpq_filter_float32(lb_gpu_ivfpq *p, const float *column, int64_t n,
     return ivf_filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
 }
 int lb_gpu_ivfpq_last_build_timing(lb_gpu_ivfpq *p, float *ms) { return ivf_last_build_timing(p, ms); }
+
+// ---- removal and compaction (lb_ivf_host.h, lb_remove.h) ----------------------------------------------------------------
+int lb_gpu_ivfpq_remove(lb_gpu_ivfpq *p, int64_t n, const int64_t *labels, int64_t *n_removed) { return ivf_remove(p, n, labels, n_removed); }
+int lb_gpu_ivfpq_remove_device(lb_gpu_ivfpq *p, int64_t n, const int64_t *d_labels, int64_t *n_removed)
+{
+    return ivf_remove_device(p, n, d_labels, n_removed);
+}
+int lb_gpu_ivfpq_remove_rows(lb_gpu_ivfpq *p, int64_t n, const int64_t *rows, int64_t *n_removed) { return ivf_remove_rows(p, n, rows, n_removed); }
+int64_t lb_gpu_ivfpq_nlive(const lb_gpu_ivfpq *p) { return ivf_nlive(p); }
+int64_t lb_gpu_ivfpq_ndeleted(const lb_gpu_ivfpq *p) { return ivf_ndeleted(p); }
+// (the codes in insertion order are the rows that move, M bytes each; the list-major copy of the pair not in use is written from
+// them and the new lists, as an add writes it, before the commit flips part.cur: no row is encoded again, a residual code included,
+// for the list it was taken against moves with it)
+int lb_gpu_ivfpq_compact(lb_gpu_ivfpq *p, int64_t *old_rows, int64_t cap)
+{
+    if (!p) return LB_ERR_INVALID_ARG;
+    return ivf_compact(p, [p] { return static_cast<void *>(p->d_codes.get()); }, (size_t)p->M, old_rows, cap, [p](int nxt, int64_t nlive, hipStream_t s) {
+        launch_ivfpq_permute(p->d_codes.get(), p->part.d_list[nxt].get(), nlive, p->M, p->d_lcodes[nxt].get(), s);
+    });
+}
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
 int lb_gpu_ivfpq_add(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false); }

@@ -79,6 +79,7 @@ int add_impl(lb_gpu_ivfsq8 *p, int64_t n, const float *vectors, const int64_t *i
             LB_HIP(hipStreamSynchronize(s)); // (the staging buffer and the labels are reused by the next piece)
         }
         // 4. the lists of all rows, into the pair not in use
+        ivf_add_live(p, total, s); // (a handle that has removed rows: the new ones are live)
         ivf_sort_lists(p, P, total, hist, s);
         if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
         const int nxt = 1 - P.cur;
@@ -101,6 +102,7 @@ int add_impl(lb_gpu_ivfsq8 *p, int64_t n, const float *vectors, const int64_t *i
 int ivfsq8_search_dev(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
                       const lb_cancel *ctx, Lease &sc)
 {
+    if (const int st = ivf_live_ok(p)) return st;
     IvfBatch a{};
     a.X = nullptr; // (the plan and the selection take the batch as the IVF-Flat kernels do: neither reads rows)
     a.D = p->dims;
@@ -218,6 +220,23 @@ int lb_gpu_ivfsq8_filter_float32(lb_gpu_ivfsq8 *p, const float *column, int64_t 
     return ivf_filter_column<float>(p, column, n, value, op, validity, validity_offset, combine);
 }
 int lb_gpu_ivfsq8_last_build_timing(lb_gpu_ivfsq8 *p, float *ms) { return ivf_last_build_timing(p, ms); }
+
+// ---- removal and compaction (lb_ivf_host.h, lb_remove.h) ----------------------------------------------------------------
+int lb_gpu_ivfsq8_remove(lb_gpu_ivfsq8 *p, int64_t n, const int64_t *labels, int64_t *n_removed) { return ivf_remove(p, n, labels, n_removed); }
+int lb_gpu_ivfsq8_remove_device(lb_gpu_ivfsq8 *p, int64_t n, const int64_t *d_labels, int64_t *n_removed)
+{
+    return ivf_remove_device(p, n, d_labels, n_removed);
+}
+int lb_gpu_ivfsq8_remove_rows(lb_gpu_ivfsq8 *p, int64_t n, const int64_t *rows, int64_t *n_removed) { return ivf_remove_rows(p, n, rows, n_removed); }
+int64_t lb_gpu_ivfsq8_nlive(const lb_gpu_ivfsq8 *p) { return ivf_nlive(p); }
+int64_t lb_gpu_ivfsq8_ndeleted(const lb_gpu_ivfsq8 *p) { return ivf_ndeleted(p); }
+// (the codes are the rows that move, `stride` bytes each with their zero pad bytes; the scan reads them in insertion order, so
+// nothing else is derived from them)
+int lb_gpu_ivfsq8_compact(lb_gpu_ivfsq8 *p, int64_t *old_rows, int64_t cap)
+{
+    if (!p) return LB_ERR_INVALID_ARG;
+    return ivf_compact(p, [p] { return static_cast<void *>(p->d_codes.get()); }, (size_t)p->stride, old_rows, cap, ivf_no_relist);
+}
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
 int lb_gpu_ivfsq8_add(lb_gpu_ivfsq8 *p, int64_t n, const float *vectors, const int64_t *ids) { return add_impl(p, n, vectors, ids, false); }

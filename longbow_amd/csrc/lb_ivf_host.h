@@ -1,5 +1,6 @@
-// lb_ivf_host.h -- the host side that the IVF handles share: what ivf.hip (lb_gpu_ivf, rows), ivfpq.hip (lb_gpu_ivfpq, PQ codes)
-// and ivfsq8.hip (lb_gpu_ivfsq8, SQ8 codes) have in common beyond lb_handle.h.  Header-only, host-only, nothing exported.
+// lb_ivf_host.h -- the host side that the IVF handles share: what ivf.hip (lb_gpu_ivf, rows), ivfpq.hip (lb_gpu_ivfpq, PQ codes),
+// ivfsq8.hip (lb_gpu_ivfsq8, SQ8 codes) and ivfbq.hip (lb_gpu_ivfbq, BQ codes) have in common beyond lb_handle.h.  Header-only,
+// host-only, nothing exported.
 //
 // The contract:
 //   * IvfPartition is the coarse partition of a handle's rows: the inner exact f32 index over the centroids, the list of each row
@@ -16,14 +17,18 @@
 //     builds the visible lists of all rows into their pair not in use (ivf_add_visible) and commits them with the rest
 //     (ivf_commit_visible);
 //   * the filter calls rebuild the visible lists through ivf_visible_builder, the `built` hook of filter_set / filter_column;
-//   * rows can be removed (ivf_remove_*, ivf_compact; entry points on lb_gpu_ivf so far).  IvfHandle::live is a second per-row state
-//     beside the caller's filter, allocated at the first removal, which no filter call writes.  From then on filter.mask is the
-//     EFFECTIVE mask, the caller's filter AND live, and filter.on says that an effective mask is in force, a caller's filter or
-//     removed rows or both (has_filter tells which); lists() and sizes() read what they always read.  A removal clears the rows'
-//     bytes in both arrays and rebuilds the row list and the visible lists as a filter call does; the filter calls AND `live`
-//     into the mask they write (filter.live, lb_handle.h); an add makes its rows live; IvfGrowth carries the bytes.  Compaction
-//     gathers the survivors to the front in place (lb_remove.h) and derives the lists from the stored assignments, which move with
-//     the rows: nothing is assigned again;
+//   * rows can be removed (ivf_remove_*, ivf_compact; entry points on lb_gpu_ivf, lb_gpu_ivfpq and lb_gpu_ivfsq8; lb_gpu_ivfbq has
+//     none yet and never holds a removed row).  IvfHandle::live is a second per-row state beside the caller's filter, allocated
+//     at the first removal, which no filter call writes.  From then on filter.mask is the EFFECTIVE mask, the caller's filter AND
+//     live, and filter.on says that an effective mask is in force, a caller's filter or removed rows or both (has_filter tells
+//     which); lists() and sizes() read what they always read.  A removal clears the rows' bytes in both arrays and rebuilds the
+//     row list and the visible lists as a filter call does; the filter calls AND `live` into the mask they write (filter.live,
+//     lb_handle.h); an add makes its rows live; IvfGrowth carries the bytes.  Compaction gathers the survivors to the front in
+//     place (lb_remove.h) and derives the lists from the stored assignments, which move with the rows: nothing is assigned
+//     again, and on the code handles nothing is encoded again, the codes being the rows that move.  A handle with `positions`
+//     keeps a list-major copy of its codes beside the lists: a removal leaves that copy alone (the visible lists it builds hold
+//     positions into the copy of ALL rows), and compaction writes the copy of the pair not in use from the compacted codes and
+//     the new lists through ivf_compact's `relist` hook;
 //   * ivf_search is the one search loop.  A handle supplies its scratch pieces and the launches between the plan and the
 //     selection; ctx is polled before every launch, a cancelled search publishes no stats, and the events of a profiled search
 //     fall where the handle's timing slots say.
@@ -462,13 +467,16 @@ inline int64_t ivf_ndeleted(const IvfHandle *p)
     return p->n_dead;
 }
 
-// Compaction of a handle whose rows are row_bytes each (any element type) at rows(), which is called under the handle's lock.
-// Everything that can be refused happens before the first row
+// Compaction of a handle whose rows are row_bytes each (any element type; a code handle's rows are its codes in insertion order)
+// at rows(), which is called under the handle's lock.  Everything that can be refused happens before the first row
 // moves: every buffer and lease, the survivor list, the survivors' assignments gathered into a scratch, the new lists sorted from
 // it into the pair not in use, their sizes read back and checked.  Then the rounds (lb_remove.h) move rows, ids and, under a
-// caller's filter, the mask bytes; the assignments are copied in, `live` is reset, the visible lists of a surviving filter are
-// built from the new lists, and the commit comes last.  No row is assigned again: its list moves with it.
-template <class Rows> int ivf_compact(IvfHandle *p, Rows &&rows, size_t row_bytes, int64_t *old_rows, int64_t cap)
+// caller's filter, the mask bytes; relist(nxt, nlive, s) enqueues what the handle derives from the moved rows and the new lists
+// d_list[nxt] (the list-major codes of a handle with `positions`: into buffers that exist at `capacity` already, so it allocates
+// nothing and refuses nothing; the others pass ivf_no_relist); the assignments are copied in, `live` is reset, the visible lists
+// of a surviving filter are built from the new lists, and the commit comes last.  No row is assigned again: its list moves with it.
+inline void ivf_no_relist(int, int64_t, hipStream_t) {}
+template <class Rows, class Relist> int ivf_compact(IvfHandle *p, Rows &&rows, size_t row_bytes, int64_t *old_rows, int64_t cap, Relist &&relist)
 {
     if (!p) return LB_ERR_INVALID_ARG;
     std::unique_lock<std::shared_mutex> g(p->mu);
@@ -521,6 +529,7 @@ template <class Rows> int ivf_compact(IvfHandle *p, Rows &&rows, size_t row_byte
         // 5. the rows move, in place: from here on nothing but a device fault fails the call
         const CompactArray arrays[3] = {{rows(), row_bytes, gx}, {P.d_ids.get(), idb, gi}, {f.mask.get(), mb, gm}};
         compact_walk(arrays, 3, map, first, nlive, R, p->device, s);
+        relist(nxt, nlive, s);
         if (nlive > 0) {
             LB_HIP(hipMemcpyAsync(P.d_assign.get(), d_newassign, (size_t)nlive * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
             LB_HIP(hipMemsetAsync(p->live.get(), 0xff, (size_t)nlive, s));

@@ -116,7 +116,8 @@ def rows_f16(vectors, dims):
 
 
 class RemovalMixin:
-    """lb_gpu_ivf_remove* / _nlive / _ndeleted / _compact on a handle of IVFBase: written once for IVFFlat and IVFFlatInt8"""
+    """<prefix>_remove* / _nlive / _ndeleted / _compact on a handle of IVFBase, resolved by the handle's prefix: written once for
+    IVFFlat, IVFFlatInt8 and the code handles ivfpq.IVFPQ and ivfsq8.IVFSQ8 (whose "rows" are their codes)"""
 
     def _remove(self, entry, values):
         values = np.ascontiguousarray(values, np.int64).reshape(-1)

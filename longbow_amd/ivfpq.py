@@ -10,7 +10,8 @@ codebooks spend their words on the spread inside a list; a query then has a tabl
 result is as exact over those tables.  include/longbow_gpu.h states the semantics of both.
 
   IVFPQ   the handle: codebooks and centroids given at creation, add / search / codes / list_sizes / assignments / last_search_stats,
-          and the row filter (set_filter / filter_column / nvisible)
+          the row filter (set_filter / filter_column / nvisible), removal (remove / remove_rows / remove_device / nlive /
+          ndeleted) and compact(): codes are kept until compaction and move with their lists, nothing is encoded again
   train   (centroids, codebook blob) from ivf.train and pq.train; with residual=True the codebooks are trained on the residuals
 """
 import ctypes as C
@@ -50,7 +51,7 @@ def train(vectors, nlist, M, max_iter=20, seed=0, device=0, residual=False, cent
     return centroids, blob
 
 
-class IVFPQ(RowFilterMixin, IVFBase):
+class IVFPQ(ivf.RemovalMixin, RowFilterMixin, IVFBase):
     """lb_gpu_ivfpq: codebooks (the reference's serialised blob, or a pq.PQEncoder whose blob is taken), centroids f32
     [nlist, dims], order 0 SEQ / 1 UNROLL4 of the coarse quantiser (L2).  Under a row filter (RowFilterMixin) the probes stay as
     they are and a search sees the visible rows of the probed lists alone.  residual=True makes a residual handle
@@ -104,7 +105,10 @@ class IVFPQ(RowFilterMixin, IVFBase):
         lists, then the exact top k of every shortlist on `index` in one call (gpu.Index.Refine; a float32 or float16
         gpu.Index filled in the same row order).  -> (labels [nq, k], dist [nq, k]), padded with -1 / FLT_MAX.  The shortlist
         must hold row positions: a handle that was given ids raises ValueError.  A row filter on this handle shapes the
-        shortlist, so the result holds visible rows only; `index` needs no filter."""
+        shortlist, so the result holds visible rows only; `index` needs no filter.  Removed rows never enter the shortlist
+        (it holds live rows only), and `index` treats a position it has removed itself as outside the index.  After compact()
+        the positions of this handle are the survivors' new ones: `index` must be compacted over the same removals
+        (gpu.Index.Compact is stable too), or the positions no longer correspond."""
         if self._has_ids:
             raise ValueError("search_refine needs row positions: this handle was given ids, which its searches return instead")
         v = self._vectors(queries)

@@ -6,7 +6,8 @@ order of the integers and reported as float32(S), and with every list probed it 
 include/longbow_gpu.h states the semantics.
 
   IVFSQ8  the handle: bounds and centroids given at creation, add / search / codes / bounds / list_sizes / assignments /
-          last_search_stats, and the row filter (set_filter / filter_column / nvisible)
+          last_search_stats, the row filter (set_filter / filter_column / nvisible), removal (remove / remove_rows /
+          remove_device / nlive / ndeleted) and compact()
   train   (centroids, min, max) from ivf.train and sq8.train
 """
 import ctypes as C
@@ -36,7 +37,7 @@ def train(vectors, nlist, max_iter=20, seed=0, device=0, centroids=None):
     return centroids, mn, mx
 
 
-class IVFSQ8(RowFilterMixin, IVFBase):
+class IVFSQ8(ivf.RemovalMixin, RowFilterMixin, IVFBase):
     """lb_gpu_ivfsq8: SQ8 bounds min / max f32 [dims] (min < max in every dimension, as SQ8Config.Validate asks; NaN bounds pass),
     centroids f32 [nlist, dims], order 0 SEQ / 1 UNROLL4 of the coarse quantiser (L2).  Under a row filter (RowFilterMixin) the
     probes stay as they are and a search sees the visible rows of the probed lists alone."""
@@ -97,7 +98,10 @@ class IVFSQ8(RowFilterMixin, IVFBase):
         query among the probed lists, then the exact top k of every shortlist on `index` in one call (gpu.Index.Refine; a
         float32 or float16 gpu.Index filled in the same row order).  -> (labels [nq, k], dist [nq, k]), padded with -1 /
         FLT_MAX.  The shortlist must hold row positions: a handle that was given ids raises ValueError.  A row filter on this
-        handle shapes the shortlist, so the result holds visible rows only; `index` needs no filter."""
+        handle shapes the shortlist, so the result holds visible rows only; `index` needs no filter.
+        Removed rows never enter the shortlist (it holds live rows only), and `index` treats a position it has removed itself as outside the index.  After compact()
+        the positions of this handle are the survivors' new ones: `index` must be compacted over the same removals
+        (gpu.Index.Compact is stable too), or the positions no longer correspond."""
         if self._has_ids:
             raise ValueError("search_refine needs row positions: this handle was given ids, which its searches return instead")
         v = self._vectors(queries)
