@@ -768,8 +768,31 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     dotInt8Unrolled4x, negated).  Result, labels, padding, ids, filters and stats are as stated above, and
  *                     nprobe >= nlist gives lb_gpu_index_search_i8 of an int8 index (lb_gpu_index_new_i8) over the same rows,
  *                     bit for bit.  Every other lb_gpu_ivf_* entry point works on all three handle types.
- * Not here: fp16 or int8 centroids, fp16 queries, f32 queries on an int8 handle, a filter given per search call, search combining,
- * lb_gpu_comm_*. */
+ *   call bitmap       lb_gpu_ivf_search_bitmap_ctx / _bitmap_device_ctx and, on an int8 handle, _search_i8_bitmap_ctx /
+ *                     _i8_bitmap_device_ctx take what their plain counterparts take, and behind nprobe a row filter of THIS CALL
+ *                     alone: (bitmap, nbits, stride_bytes).  One bit per row POSITION, as the handle filter's mask is by position,
+ *                     least significant bit first as in an Arrow validity buffer: row r is visible to the call iff
+ *                     bitmap[r >> 3] >> (r & 7) & 1.  It is read byte by byte: no alignment is owed and no padding beyond
+ *                     ceil(nbits / 8) bytes, and nothing past bit nbits - 1 is read as a row.  stride_bytes 0: one bitmap serves
+ *                     every query of the call; otherwise query q reads bitmap + q * stride_bytes (a batch of requests that each
+ *                     bring their own filter), and stride_bytes >= ceil(nbits / 8).  The result is the exact k-NN among the rows of
+ *                     the probed lists that are live, pass the handle's filter if one is set AND have their bit set; order, labels,
+ *                     padding and distances as stated above.  It is bit for bit what the same handle answers after set_filter
+ *                     (combined with its own filter) with the mask bit(r) != 0, and last_search_stats agrees in all four values.
+ *                     The probes do not change; nprobe >= nlist gives lb_gpu_index_search of a flat index under the same mask.
+ *                     The handle is not changed and is held shared, like any search: calls with different bitmaps run
+ *                     concurrently, and nvisible, the handle's filter and every later call are untouched.  A NULL bitmap is the
+ *                     plain search through the plain path; nbits and stride_bytes are then ignored.  A non-NULL bitmap with
+ *                     nbits != ntotal (the n != ntotal rule of set_filter), nbits < 0, a negative stride or a stride in
+ *                     (0, ceil(nbits / 8)) is LB_ERR_INVALID_ARG with a last_error text, answered before any launch and with
+ *                     nothing written; the other checks, their order and the element-type texts are the plain entry points', and
+ *                     they come first.  On the device the probed lists of each batch are compacted under the bitmap into lists of
+ *                     the call's own (over the handle's visible lists when it has a filter or removed rows, so the AND costs
+ *                     nothing), which the plan, the scan and the selection then walk; scratch is sized by the handle's list sizes,
+ *                     nothing returns to the host in between, and the cost of the scan and the selection follows the rows that
+ *                     pass.  ctx is polled before these launches as before every other; under profiling they fall into ms[1].
+ * Not here: fp16 or int8 centroids, fp16 queries, f32 queries on an int8 handle, predicates (filter_int64 / _float32) given per
+ * search call, search combining, lb_gpu_comm_*. */
 typedef struct lb_gpu_ivf lb_gpu_ivf;
 lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
 lb_gpu_ivf *lb_gpu_ivf_new_f16(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
@@ -804,6 +827,17 @@ int lb_gpu_ivf_search_i8_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, i
                              const lb_cancel *ctx);
 int lb_gpu_ivf_search_i8_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, float *d_dist,
                                     int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* the same searches under a row bitmap given with the call ("call bitmap" above); d_bitmap is device memory */
+int lb_gpu_ivf_search_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
+                                 int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_ivf_search_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                        int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
+                                        const lb_cancel *ctx);
+int lb_gpu_ivf_search_i8_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, const uint8_t *bitmap,
+                                    int64_t nbits, int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_ivf_search_i8_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                           int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
+                                           const lb_cancel *ctx);
 /* the row filter, as lb_gpu_bq_set_filter / _filter_int64 / _filter_float32 / _nvisible */
 int lb_gpu_ivf_set_filter(lb_gpu_ivf *p, const uint8_t *mask, int64_t n);
 int lb_gpu_ivf_filter_int64(lb_gpu_ivf *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
@@ -816,7 +850,8 @@ int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p);
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]);
 /* instrumentation (tools/ivf_bench.py), as lb_gpu_pq_set_profiling: while on, a search records HIP events between its steps and
  * drains the stream after every batch; last_timing gives the last such search's ms summed over its batches: ms[0] the probes
- * (the coarse search), ms[1] the plan (and the query norms, cosine), ms[2] the list scan, ms[3] the selection. */
+ * (the coarse search), ms[1] the plan (and the query norms, cosine; and the compaction under a call's bitmap), ms[2] the list
+ * scan, ms[3] the selection. */
 int lb_gpu_ivf_set_profiling(lb_gpu_ivf *p, int enable);
 int lb_gpu_ivf_last_timing(lb_gpu_ivf *p, float ms[4]);
 /* while profiling is on, a filter call or an add under a filter also records HIP events around the launches that build the

@@ -74,16 +74,39 @@ class IVFBase:
 
     def search(self, queries, k, nprobe, ctx=None):
         """-> (labels [nq, k], dist [nq, k]): ascending (distance, row) among the rows of the probed lists, padded -1 / FLT_MAX"""
-        v = self._vectors(queries)
-        dist = np.empty((v.shape[0], k), np.float32)
-        labels = np.empty((v.shape[0], k), np.int64)
-        self._check(self._fn("search_ctx")(self._h, v.shape[0], v.ctypes.data, k, nprobe, dist.ctypes.data, labels.ctypes.data,
-                                           ctx._h if ctx is not None else None))
-        return labels, dist
+        return self._search_host("search", self._vectors(queries), k, nprobe, ctx)
 
     def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None):
-        self._check(self._fn("search_device_ctx")(self._h, nq, d_queries, k, nprobe, d_dist, d_labels, stream,
-                                                  ctx._h if ctx is not None else None))
+        self._search_dev("search", nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx)
+
+    def _search_host(self, entry, v, k, nprobe, ctx, bitmap=None, bitmap_stride=0):
+        """queries v [nq, dims] of the element type that <entry>_ctx takes; bitmap: None, or the LSB-first bits of ntotal row
+        positions as uint8 (ivf.pack_bitmap), one bitmap for every query (bitmap_stride 0) or query q's at q * bitmap_stride bytes:
+        <entry>_bitmap_ctx, on the handles that have it"""
+        dist = np.empty((v.shape[0], k), np.float32)
+        labels = np.empty((v.shape[0], k), np.int64)
+        c = ctx._h if ctx is not None else None
+        if bitmap is None:
+            self._check(self._fn(entry + "_ctx")(self._h, v.shape[0], v.ctypes.data, k, nprobe, dist.ctypes.data, labels.ctypes.data, c))
+            return labels, dist
+        b = np.ascontiguousarray(bitmap, np.uint8).reshape(-1)
+        n = self.ntotal
+        need = (max(v.shape[0], 1) - 1) * bitmap_stride + (n + 7) // 8 if bitmap_stride > 0 else (n + 7) // 8
+        if b.size < need or (bitmap_stride == 0 and b.size != need):  # (the bits of ntotal rows, no more: an old length is caught)
+            raise ValueError(f"a bitmap of {b.size} bytes, {need} are read for {n} rows at stride {bitmap_stride}")
+        if b.size == 0:
+            b = np.zeros(1, np.uint8)  # (an empty handle: a bitmap that is there, and of which nothing is read)
+        self._check(self._fn(entry + "_bitmap_ctx")(self._h, v.shape[0], v.ctypes.data, k, nprobe, b.ctypes.data, n, bitmap_stride,
+                                                    dist.ctypes.data, labels.ctypes.data, c))
+        return labels, dist
+
+    def _search_dev(self, entry, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, d_bitmap=None, nbits=0, bitmap_stride=0):
+        c = ctx._h if ctx is not None else None
+        if d_bitmap is None:
+            self._check(self._fn(entry + "_device_ctx")(self._h, nq, d_queries, k, nprobe, d_dist, d_labels, stream, c))
+        else:
+            self._check(self._fn(entry + "_bitmap_device_ctx")(self._h, nq, d_queries, k, nprobe, d_bitmap, nbits, bitmap_stride,
+                                                               d_dist, d_labels, stream, c))
 
     def last_search_stats(self):
         """of the last search: (queries, rows scanned summed over them, the largest per-query count, queries selected from LDS)"""

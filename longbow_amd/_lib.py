@@ -230,6 +230,10 @@ SIGNATURES = [
     ("lb_gpu_ivf_search_i8", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     ("lb_gpu_ivf_search_i8_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
     ("lb_gpu_ivf_search_i8_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_i8_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_i8_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_ivf_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivf_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_ivf_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),

@@ -1,6 +1,6 @@
 // ivf.hip -- host side of the lb_gpu_ivf_* entry points of include/longbow_gpu.h: the IVF-Flat index the reference names as
 // a plug-point (internal/store/pluggable_index.go:18-25,100-104; its adapter, pluggable_index_adapters.go:116-223, is a stub).
-// The kernels are in kernels_ivf.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
+// The kernels are in kernels_ivf.hip, those of a row bitmap given with a search call in kernels_ivf_call.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
 // kernels_ivf_i8.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
@@ -141,8 +141,10 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
 // The handle's call of the search loop (lb_ivf_host.h): under a filter it walks the visible lists; its middle steps are the
 // queries' norms under cosine, inside the plan's timing slot, and the scan of the rows.  d_q8: on an int8 handle the call's int8
 // queries, d_Q being those widened to f32; the scan reads the int8 ones, a batch's at the offset of its b.Q in d_Q.
+// filter: the call's own row bitmap (the *_bitmap entry points), compacted per batch over the lists walked here, so that it is
+// ANDed with the handle's filter and with liveness.
 int ivf_search_rows(lb_gpu_ivf *p, int64_t nq, const float *d_Q, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels,
-                    hipStream_t s, const lb_cancel *ctx, Lease &sc)
+                    hipStream_t s, const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter = IvfCallFilter{})
 {
     if (const int st = ivf_live_ok(p)) return st;
     IvfBatch a{};
@@ -162,7 +164,8 @@ int ivf_search_rows(lb_gpu_ivf *p, int64_t nq, const float *d_Q, const int8_t *d
             else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, reinterpret_cast<const _Float16 *>(p->d_rows_f16.get())}, maxlen, s);
             else launch_ivf_scan(p->metric, p->order, b, maxlen, s);
             return true;
-        });
+        },
+        kQueryBatch, launch_ivf_select, filter);
 }
 
 // A float32 or float16 handle's search of f32 queries
@@ -175,12 +178,67 @@ int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprob
 // An int8 handle's: the call's int8 queries are widened once into `wide` (the caller's lease, declared outside its guard), which
 // is what the coarse index probes with; ctx is polled before that launch as before every other.
 int ivf_search_i8_dev(lb_gpu_ivf *p, int64_t nq, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                      const lb_cancel *ctx, Lease &sc, Lease &wide)
+                      const lb_cancel *ctx, Lease &sc, Lease &wide, const IvfCallFilter &filter = IvfCallFilter{})
 {
     wide.reset(p->device, (size_t)nq * p->dims * 4);
     if (const int st = ctx_state(ctx)) return ctx_fail(p, st);
     launch_widen_i8(d_q8, wide.as<float>(), nq * p->dims, s);
-    return ivf_search_rows(p, nq, wide.as<float>(), d_q8, k, nprobe, d_dist, d_labels, s, ctx, sc);
+    return ivf_search_rows(p, nq, wide.as<float>(), d_q8, k, nprobe, d_dist, d_labels, s, ctx, sc, filter);
+}
+
+// ---- a row bitmap given with the call ----------------------------------------------------------------------------------------
+// The bitmap as an entry point got it: host or device memory, one bit per row position, least significant bit first.
+struct CallBitmap {
+    const uint8_t *bits;
+    int64_t nbits, stride;
+    bool on_device;
+};
+
+// The call's filter from its bitmap, under the reader lock and before anything is launched: the refusals (set_filter's n != ntotal
+// rule, and the stride), then a host bitmap's bytes go into `lease` (the caller's, declared outside its guard) ahead of the
+// search on s.  A NULL bitmap is no filter: the plain search.
+int call_filter(lb_gpu_ivf *p, int64_t nq, const CallBitmap &b, Lease &lease, hipStream_t s, IvfCallFilter &f)
+{
+    f = IvfCallFilter{};
+    if (!b.bits) return LB_OK;
+    if (b.nbits < 0 || b.nbits != p->n) {
+        p->set_error("a bitmap of %lld bits for %lld rows", (long long)b.nbits, (long long)p->n);
+        return LB_ERR_INVALID_ARG;
+    }
+    const int64_t bytes = (b.nbits + 7) / 8;
+    if (b.stride < 0 || (b.stride > 0 && b.stride < bytes)) {
+        p->set_error("bitmap stride %lld: 0 (one bitmap for every query) or at least the %lld bytes of %lld bits", (long long)b.stride,
+                     (long long)bytes, (long long)b.nbits);
+        return LB_ERR_INVALID_ARG;
+    }
+    if (bytes == 0) return LB_OK; // (an empty handle: all padding with or without it)
+    f.d_bits = b.bits;
+    if (!b.on_device) {
+        const size_t total = (size_t)(b.stride > 0 ? (nq - 1) * b.stride : 0) + (size_t)bytes;
+        lease.reset(p->device, total);
+        LB_HIP(hipMemcpyAsync(lease.p, b.bits, total, hipMemcpyHostToDevice, s));
+        f.d_bits = lease.as<uint8_t>();
+    }
+    f.stride = b.stride;
+    f.nbits = b.nbits;
+    f.on = true;
+    return LB_OK;
+}
+
+int ivf_search_bitmap_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
+                          const lb_cancel *ctx, Lease &sc, const CallBitmap &b, Lease &bits)
+{
+    IvfCallFilter f;
+    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
+    return ivf_search_rows(p, nq, d_Q, nullptr, k, nprobe, d_dist, d_labels, s, ctx, sc, f);
+}
+
+int ivf_search_i8_bitmap_dev(lb_gpu_ivf *p, int64_t nq, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
+                             const lb_cancel *ctx, Lease &sc, Lease &wide, const CallBitmap &b, Lease &bits)
+{
+    IvfCallFilter f;
+    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
+    return ivf_search_i8_dev(p, nq, d_q8, k, nprobe, d_dist, d_labels, s, ctx, sc, wide, f);
 }
 
 } // namespace
@@ -314,6 +372,43 @@ int lb_gpu_ivf_search_i8_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, i
 int lb_gpu_ivf_search_i8(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
     return lb_gpu_ivf_search_i8_ctx(p, nq, queries, k, nprobe, dist, labels, nullptr);
+}
+// the same searches under a row bitmap given with the call (a NULL bitmap: the plain search)
+int lb_gpu_ivf_search_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                        int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    if (const int st = query_mismatch(p, false)) return st;
+    Lease bits;
+    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
+                                 [&](auto &&...args) { return ivf_search_bitmap_dev(args..., b, bits); });
+}
+int lb_gpu_ivf_search_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
+                                 int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    if (const int st = query_mismatch(p, false)) return st;
+    Lease bits;
+    const CallBitmap b{bitmap, nbits, stride_bytes, false};
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivf_search_bitmap_dev(args..., b, bits); });
+}
+int lb_gpu_ivf_search_i8_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                           int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
+                                           const lb_cancel *ctx)
+{
+    if (const int st = query_mismatch(p, true)) return st;
+    Lease wide, bits;
+    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
+                                 [&](auto &&...args) { return ivf_search_i8_bitmap_dev(args..., wide, b, bits); });
+}
+int lb_gpu_ivf_search_i8_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
+                                    int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    if (const int st = query_mismatch(p, true)) return st;
+    Lease wide, bits;
+    const CallBitmap b{bitmap, nbits, stride_bytes, false};
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx,
+                          [&](auto &&...args) { return ivf_search_i8_bitmap_dev(args..., wide, b, bits); });
 }
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
 int lb_gpu_ivf_set_profiling(lb_gpu_ivf *p, int enable) { return ivf_set_profiling(p, enable); }

@@ -1,5 +1,5 @@
-// lb_ivf.h -- what ivf.hip (host) and kernels_ivf.hip (device) of the IVF-Flat index share: the argument blocks of the kernels
-// and their launchers.  The semantics are stated in include/longbow_gpu.h (lb_gpu_ivf_*).
+// lb_ivf.h -- what ivf.hip (host) and kernels_ivf.hip / kernels_ivf_call.hip (device) of the IVF-Flat index share: the argument
+// blocks of the kernels and their launchers.  The semantics are stated in include/longbow_gpu.h (lb_gpu_ivf_*).
 #pragma once
 #include "lb_device.h"
 
@@ -54,6 +54,32 @@ hipError_t launch_ivf_sort(const uint32_t *assign, int64_t n, int nlist, uint32_
 size_t ivf_visible_scratch_bytes(int64_t n);
 hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n, bool positions, void *scratch, uint32_t *voff, uint32_t *vrows,
                               hipStream_t s);
+
+// A row bitmap given with a search call (kernels_ivf_call.hip): the probed lists of a batch, compacted under the call's bitmap
+// into synthetic lists that the plan, the scans and the selection walk in place of L and probes.  Row r passes iff
+// bits[q stride + (r >> 3)] >> (r & 7) & 1 (stride 0: one bitmap for every query); rows at or beyond nbits never pass.
+//   soff    [2 nq np + 1]  list 2 (q np + p) holds the passing rows of the list probed in slot p of query q, ascending, and
+//                          starts at q pmax + the sizes of the lists probed in the slots before p; list 2 (q np + p) + 1 is the
+//                          gap up to the next start and is never probed.  Monotone, soff[2 nq np] = nq pmax
+//   sprobes [nq][np]       2 (q np + p)
+//   srows   [nq][pmax]     the rows of the synthetic lists
+// pmax: at least the rows of any np distinct lists of L, and nq pmax < 2^32.  An invalid probe gives an empty list.
+struct IvfCallLists {
+    IvfLists L;            // the handle's lists: the visible ones under a handle filter or removals
+    uint32_t rows_len;     // entries of L.rows that may be read: at least L.off[L.nlist]
+    const int64_t *probes; // [nq][np] the coarse search's labels
+    int nq, np;
+    int64_t pmax;
+    const uint8_t *bits;
+    int64_t stride, nbits;
+    uint32_t *soff;
+    int64_t *sprobes;
+    uint32_t *srows;
+    IvfLists lists() const { return IvfLists{soff, srows, 2 * nq * np}; }
+};
+constexpr int IVF_CALL_STEP_ROWS = 2048; // list positions a workgroup of the compaction takes per step
+// two launches: the starts and the synthetic probes (a wave per query), then the compaction (a workgroup per probe slot)
+void launch_ivf_call_lists(const IvfCallLists &a, hipStream_t s);
 
 // Coarse-quantiser training (kernels_ivf_train.hip; host side ivf_train.hip).  st.M == 1, st.sub == st.D, st.K <= IVF_MAX_NLIST.
 // E-step: st.assign[row] = the first strict minimum of simd.L2Squared over st.cent (-1 and *st.bad: none below FLT_MAX),

@@ -567,12 +567,22 @@ template <class Rows, class Relist> int ivf_compact(IvfHandle *p, Rows &&rows, s
 // a slot per further next(), selection.  Profiling costs a drain per batch.  batch_cap: queries per batch at most, for a handle
 // whose own scratch grows with the batch (the residual IVF-PQ handle's tables); the others leave it at kQueryBatch.  select: the
 // selection's launcher, for a handle whose keys are not pack_entry's (the IVF-SQ8 handle's integer keys); launch_ivf_select's
-// arguments and meaning.
+// arguments and meaning.  filter: a row bitmap given with this call (IvfCallFilter; the IVF-Flat handle's *_bitmap entry points).
+// When it is on, the scratch also takes the synthetic lists of a batch (lb_ivf.h: offsets, probes and 4 bytes of rows per key), and
+// behind the probes of each batch launch_ivf_call_lists compacts the probed lists of L under the bitmap; the plan, the middle
+// steps and the selection are handed those lists and probes in place of L and the coarse search's.  Its launches fall into the
+// plan's timing slot, the host keeps sizing by `sizes`, and nothing comes back to it in between.
+struct IvfCallFilter {
+    const uint8_t *d_bits = nullptr; // device memory; query q of the call reads d_bits + q stride
+    int64_t stride = 0, nbits = 0;
+    bool on = false;
+};
 using IvfSelectFn = void (*)(const IvfBatch &, int, const int64_t *, float *, int64_t *, hipStream_t);
 template <class Extra, class Middle>
 int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vector<int64_t> &sizes, IvfBatch a, int64_t nq, const float *d_Q,
                int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s, const lb_cancel *ctx, Lease &sc, float *timing, int slots,
-               Extra &&extra, Middle &&middle, int64_t batch_cap = kQueryBatch, IvfSelectFn select = launch_ivf_select)
+               Extra &&extra, Middle &&middle, int64_t batch_cap = kQueryBatch, IvfSelectFn select = launch_ivf_select,
+               const IvfCallFilter &filter = IvfCallFilter{})
 {
     int64_t st[4] = {nq, 0, 0, 0};
     auto publish = [&]() {
@@ -601,11 +611,17 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
     int64_t *d_probes = nullptr;
     float *d_pdist = nullptr;
     unsigned long long *d_stats = nullptr;
+    IvfCallLists cl{};
     auto layout = [&](Carve c) {
         a.probes = d_probes = c.take<int64_t>((size_t)nb * np * 8);
         d_pdist = c.take<float>((size_t)nb * np * 4);
         a.seg = c.take<uint32_t>((size_t)nb * (np + 1) * 4);
         d_stats = c.take<unsigned long long>(4 * 8);
+        if (filter.on) {
+            cl.soff = c.take<uint32_t>(((size_t)nb * np * 2 + 1) * 4);
+            cl.sprobes = c.take<int64_t>((size_t)nb * np * 8);
+            cl.srows = c.take<uint32_t>((size_t)nb * pmax * 4);
+        }
         extra(c, a, nb);
         a.keys = c.take<uint64_t>((size_t)nb * pmax * 8);
         return c.off;
@@ -635,6 +651,21 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
         if (np == P.nlist && np > LB_MAX_K) launch_ivf_all_probes(d_probes, a.nq, np, s);
         else if (const int rc = lb_gpu_index_search_device_ctx(P.coarse, a.nq, a.Q, np, d_pdist, d_probes, s, ctx)) return coarse_fail(h, P, rc, s);
         if (!next()) break;
+        if (filter.on) { // the lists of this batch under the call's bitmap, then everything below walks those
+            cl.L = L;
+            cl.rows_len = (uint32_t)h->n; // (both list arrays hold room for every row, all of it written or allocated)
+            cl.probes = d_probes;
+            cl.nq = a.nq;
+            cl.np = np;
+            cl.pmax = pmax;
+            cl.bits = filter.d_bits + (size_t)q0 * filter.stride;
+            cl.stride = filter.stride;
+            cl.nbits = filter.nbits;
+            if (!go()) break;
+            launch_ivf_call_lists(cl, s);
+            a.L = cl.lists();
+            a.probes = cl.sprobes;
+        }
         launch_ivf_plan(a, d_stats, s);
         if (!middle(a, maxlen, go, next)) break;
         if (!next()) break;

@@ -8,7 +8,9 @@ list probed it equals gpu.Index.Search.  include/longbow_gpu.h states the semant
   IVFFlat        the handle: centroids given at creation, add / search / list_sizes / assignments / last_search_stats, and the
                  row filter (set_filter / filter_column / nvisible), removal (remove / remove_rows / remove_device / nlive /
                  ndeleted) and compact(); dtype=DataType.Float16 holds the rows as float16, 2 bytes an
-                 element, and answers as a float32 handle over the widened rows does, bit for bit
+                 element, and answers as a float32 handle over the widened rows does, bit for bit.  search(..., bitmap=) and
+                 search_device(..., d_bitmap=) take a row filter of that call alone, which leaves the handle as it is
+  pack_bitmap    a byte or bool mask [n] or [nq, n] -> the LSB-first bits such a call takes, and their stride
   IVFFlatInt8    the same handle over signed int8 rows (lb_gpu_ivf_new_i8), one byte an element, searched with int8 queries in
                  the reference's DataTypeInt8 arithmetic (L2 and dot); with every list probed it equals the flat int8 index
   IVFFlatIndex   the reference's PluggableVectorIndex surface over it: rows are buffered until Build()
@@ -205,8 +207,20 @@ class IVFFlat(RemovalMixin, RowFilterMixin, IVFBase):
         self._check(self._fn("add_f16_device" if self._f16 else "add_device")(self._h, n, d_vectors, d_ids))
         self._has_ids = self._has_ids or d_ids is not None
 
+    def search(self, queries, k, nprobe, ctx=None, bitmap=None, bitmap_stride=0):
+        """As IVFBase.search.  bitmap: a row filter of this call alone (lb_gpu_ivf_search_bitmap_ctx), the LSB-first bits of
+        pack_bitmap over the ntotal row positions; bitmap_stride 0: one bitmap for every query, else query q's bits start at byte
+        q * bitmap_stride.  The handle, its own filter and nvisible() stay as they are; searches with different bitmaps may run
+        at the same time."""
+        return self._search_host("search", self._vectors(queries), k, nprobe, ctx, bitmap, bitmap_stride)
+
+    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None, d_bitmap=None, nbits=0, bitmap_stride=0):
+        """d_bitmap: the call's bitmap in device memory, of nbits == ntotal bits (any byte address)"""
+        self._search_dev("search", nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, d_bitmap, nbits, bitmap_stride)
+
     def last_timing(self):
-        """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
+        """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection); the compaction under a
+        call's bitmap falls into the plan's"""
         return super().last_timing()
 
     def last_build_timing(self):
@@ -214,6 +228,17 @@ class IVFFlat(RemovalMixin, RowFilterMixin, IVFBase):
         out = C.c_float(0)
         self._check(self._lib.lb_gpu_ivf_last_build_timing(self._h, C.byref(out)))
         return float(out.value)
+
+
+def pack_bitmap(mask):
+    """A byte or bool mask over the row positions, [n] or [nq, n] (a row is visible iff its value is non-zero) -> (bits, stride):
+    the bits least significant first as in an Arrow validity buffer, row r at bits[r >> 3] >> (r & 7) & 1, as uint8 [ceil(n / 8)]
+    with stride 0, or [nq, ceil(n / 8)] with the bytes of one row as the stride.  What search(bitmap=, bitmap_stride=) takes."""
+    m = np.asarray(mask) != 0
+    if m.ndim not in (1, 2):
+        raise ValueError(f"a mask is [n] or [nq, n], got {m.ndim} dimensions")
+    bits = np.ascontiguousarray(np.packbits(m, axis=-1, bitorder="little"))
+    return bits, (0 if m.ndim == 1 else bits.shape[1])
 
 
 def rows_i8(vectors, dims):
@@ -268,19 +293,13 @@ class IVFFlatInt8(RemovalMixin, RowFilterMixin, IVFBase):
         self._check(self._fn("add_i8_device")(self._h, n, d_vectors, d_ids))
         self._has_ids = self._has_ids or d_ids is not None
 
-    def search(self, queries, k, nprobe, ctx=None):
-        """int8 queries -> (labels [nq, k], dist [nq, k]), as IVFBase.search"""
-        v = rows_i8(queries, self.dims)
-        dist = np.empty((v.shape[0], k), np.float32)
-        labels = np.empty((v.shape[0], k), np.int64)
-        self._check(self._fn("search_i8_ctx")(self._h, v.shape[0], v.ctypes.data, k, nprobe, dist.ctypes.data, labels.ctypes.data,
-                                              ctx._h if ctx is not None else None))
-        return labels, dist
+    def search(self, queries, k, nprobe, ctx=None, bitmap=None, bitmap_stride=0):
+        """int8 queries -> (labels [nq, k], dist [nq, k]), as IVFFlat.search (bitmap: lb_gpu_ivf_search_i8_bitmap_ctx)"""
+        return self._search_host("search_i8", rows_i8(queries, self.dims), k, nprobe, ctx, bitmap, bitmap_stride)
 
-    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None):
-        """d_queries: int8 [nq, dims]"""
-        self._check(self._fn("search_i8_device_ctx")(self._h, nq, d_queries, k, nprobe, d_dist, d_labels, stream,
-                                                     ctx._h if ctx is not None else None))
+    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None, d_bitmap=None, nbits=0, bitmap_stride=0):
+        """d_queries: int8 [nq, dims]; d_bitmap as IVFFlat.search_device"""
+        self._search_dev("search_i8", nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, d_bitmap, nbits, bitmap_stride)
 
     def last_timing(self):
         """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
@@ -377,12 +396,13 @@ class IVFFlatIndex:
             raise RuntimeError("ivf_flat: Build() before Search()")
         return self._h
 
-    def SearchBatch(self, queries, k, nprobe=None):
-        """-> (ids [nq, k], distances [nq, k]), padded -1 / FLT_MAX"""
-        return self._built().search(queries, k, self.config.NProbe if nprobe is None else nprobe)
+    def SearchBatch(self, queries, k, nprobe=None, bitmap=None, bitmap_stride=0):
+        """-> (ids [nq, k], distances [nq, k]), padded -1 / FLT_MAX.  bitmap: the reference's SearchVectorsWithBitmap, a filter of
+        this call alone over the row positions (pack_bitmap), one for every query or with bitmap_stride one a query"""
+        return self._built().search(queries, k, self.config.NProbe if nprobe is None else nprobe, bitmap=bitmap, bitmap_stride=bitmap_stride)
 
-    def Search(self, query, k, nprobe=None):
-        ids, dist = self.SearchBatch(np.asarray(query, np.float32).reshape(1, -1), k, nprobe)
+    def Search(self, query, k, nprobe=None, bitmap=None):
+        ids, dist = self.SearchBatch(np.asarray(query, np.float32).reshape(1, -1), k, nprobe, bitmap=bitmap)
         return ids[0], dist[0]
 
     def search_device(self, nq, d_queries, k, d_dist, d_labels, nprobe=None, stream=None, ctx=None):
