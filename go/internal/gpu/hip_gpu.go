@@ -158,6 +158,51 @@ func (idx *HIPIndex) SearchBatch(queries []float32, nq, k int) ([]int64, []float
 	return labels, distances, nil
 }
 
+// SearchWithBitmap is Search under a row filter that travels with the request (BruteForceIndex.SearchVectorsWithBitmap):
+// bitmap holds one bit per row position, least significant bit first as in an Arrow validity buffer, in exactly
+// ceil(ntotal / 8) bytes.  The index is not changed and is held shared: requests with different bitmaps search at the same
+// time.  A nil bitmap is the plain Search.
+func (idx *HIPIndex) SearchWithBitmap(vector []float32, k int, bitmap []byte) ([]int64, []float32, error) {
+	if bitmap == nil {
+		return idx.Search(vector, k)
+	}
+	idx.mu.RLock()
+	defer idx.mu.RUnlock()
+	if idx.closed {
+		return nil, nil, fmt.Errorf("index is closed")
+	}
+	if len(vector) != idx.dim {
+		return nil, nil, fmt.Errorf("query vector dimension %d does not match index dimension %d", len(vector), idx.dim)
+	}
+	if k <= 0 {
+		return nil, nil, nil
+	}
+	ntotal := int64(C.lb_gpu_index_ntotal(idx.h))
+	if int64(len(bitmap)) != (ntotal+7)/8 {
+		return nil, nil, fmt.Errorf("a bitmap of %d bytes, %d are read for %d rows", len(bitmap), (ntotal+7)/8, ntotal)
+	}
+	if ntotal == 0 {
+		return []int64{}, []float32{}, nil
+	}
+	distances := make([]float32, k)
+	labels := make([]int64, k)
+	start := time.Now()
+	rc := C.lb_gpu_index_search_bitmap_ctx(idx.h, 1, (*C.float)(unsafe.Pointer(&vector[0])), C.int(k),
+		(*C.uint8_t)(unsafe.Pointer(&bitmap[0])), C.int64_t(ntotal),
+		(*C.float)(unsafe.Pointer(&distances[0])), (*C.int64_t)(unsafe.Pointer(&labels[0])), nil)
+	if rc != C.LB_OK {
+		metrics.VectorSearchGPUOperationsTotal.WithLabelValues("search", "error").Inc()
+		return nil, nil, hipError(idx.h, "search", rc)
+	}
+	metrics.VectorSearchGPULatencySeconds.WithLabelValues("search").Observe(time.Since(start).Seconds())
+	metrics.VectorSearchGPUOperationsTotal.WithLabelValues("search", "success").Inc()
+	n := k
+	for n > 0 && labels[n-1] < 0 {
+		n--
+	}
+	return labels[:n], distances[:n], nil
+}
+
 // SearchBatchContext is SearchBatch under a context.Context: the reference's brute-force loop polls ctx.Err() every
 // 1000 rows (internal/store/adaptive_index.go:182); here the context's cancellation and deadline are handed to the
 // library through an lb_cancel, which it polls before every kernel launch of the search (one launch covers at most

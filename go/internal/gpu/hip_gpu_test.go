@@ -77,3 +77,26 @@ func TestSearchBatchContextCanceledBeforeCall(t *testing.T) {
 		t.Fatalf("want context.Canceled, got %v", err)
 	}
 }
+
+// SearchVectorsWithBitmap on the HIP index: the filter comes with the request.  Row 0, the query's nearest, is hidden by the
+// bitmap of this call and visible again in the next plain Search: the index is left as it was.
+func TestSearchWithBitmapLeavesTheIndexAlone(t *testing.T) {
+	idx := newTestIndex(t, 10, 128)
+	defer idx.Close()
+	q := make([]float32, 128)
+	bitmap := []byte{0xFE, 0xFF} // rows 1..9; the six bits behind row 9 are no rows
+	ids, _, err := idx.SearchWithBitmap(q, 5, bitmap)
+	if err != nil {
+		t.Fatalf("SearchWithBitmap: %v", err)
+	}
+	if len(ids) != 5 || ids[0] != 1 {
+		t.Fatalf("got ids %v", ids)
+	}
+	if _, _, err := idx.SearchWithBitmap(q, 5, bitmap[:1]); err == nil {
+		t.Fatalf("a bitmap of 1 byte for 10 rows was taken")
+	}
+	ids, _, err = idx.Search(q, 5)
+	if err != nil || len(ids) != 5 || ids[0] != 0 {
+		t.Fatalf("plain Search after a bitmap search: ids %v err %v", ids, err)
+	}
+}

@@ -226,6 +226,59 @@ int lb_gpu_index_search_i8_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t 
  * internal/query/filter_evaluator.go:79-115 produces).  mask has ntotal bytes;
  * NULL clears it.  Rows with mask 0 never appear in results. */
 int lb_gpu_index_set_filter(lb_gpu_index *h, const uint8_t *mask, int64_t n);
+/* rows a plain search sees: the live rows that pass the handle's filter (ntotal without a filter and with nothing removed), as
+ * lb_gpu_bq_nvisible; a bitmap given with a search call does not move it; 0 on NULL */
+int64_t lb_gpu_index_nvisible(const lb_gpu_index *h);
+
+/* ---- call bitmap: a row filter given with the search call ------------------------------------------------------------------
+ * The reference brings the filter with the request (SearchVectorsWithBitmap, SearchVectors(..., filters, ...), every
+ * VectorSearchRequest), from many goroutines at once; set_filter is a property of the handle, set under the exclusive lock.
+ * The six entry points below take exactly what their plain counterparts take and, behind k, a row filter of THIS CALL alone:
+ * (bitmap, nbits).
+ *   bit layout    one bit per row POSITION (as set_filter's mask is by position), least significant bit first as in an Arrow
+ *                 validity buffer: row r is visible to the call iff bitmap[r >> 3] >> (r & 7) & 1.
+ *   reading       byte by byte at any byte address: no alignment is owed, nothing past bit nbits - 1 is read as a row and
+ *                 nothing beyond ceil(nbits / 8) bytes is read at all.  The host forms take a host pointer, the _device forms
+ *                 device memory, read on `stream`.
+ *   one bitmap    per call, shared by all nq queries; there is no stride: a flat batch walks the corpus once for all its
+ *                 queries, so a view per query would be nq searches -- which a caller can issue concurrently itself.
+ *   result        the exact k-NN among the rows that are live, pass the handle's filter if one is set AND have their bit set:
+ *                 labels and distances are bit for bit what the same index answers after lb_gpu_index_set_filter with the mask
+ *                 bit(r) != 0 (ANDed with its filter and liveness); label -1 / dist FLT_MAX padding when fewer than k rows
+ *                 pass; labels are ids when the index holds ids.
+ *   handle state  not changed, and held shared like any search: calls with different bitmaps run concurrently.  nvisible, the
+ *                 handle's filter, its mask, its row list and its shared sample of the view are neither read as the call's view
+ *                 nor written, and every later call answers as before.  (The adaptive hints any search may move -- the fp16
+ *                 route's back-off and the widened candidate list -- may move.)
+ *   arguments     a NULL bitmap is the plain search through the plain path, combining included; nbits is then ignored.  A
+ *                 non-NULL bitmap with nbits != ntotal (the n != ntotal rule of set_filter) is LB_ERR_INVALID_ARG with both
+ *                 numbers in last_error, answered before any launch -- behind the plain entry point's own checks, which come
+ *                 first and in their order (so nq == 0 is LB_OK whatever the bitmap).  An empty index answers all padding.  An
+ *                 index never holds more rows than a row list can name (Add refuses beyond 2^32), so no size is refused here
+ *                 that set_filter takes.
+ *   combining     a call with a bitmap is never combined with other requests: it is its own device search, as a call with a
+ *                 ctx is.  Plain calls running beside it keep being combined.
+ *   cancellation  ctx is polled before the view is built, and then as in every search.
+ *   device work   the view is built once per call on the call's stream, into the call's pooled workspace (ntotal bytes of mask,
+ *                 4 ntotal of row list): one pass turns the bits, ANDed with the handle's effective mask, into the call's byte
+ *                 mask and a count per 2,048 rows, a one-workgroup scan and a scatter leave the ascending row list, and four
+ *                 bytes (the visible count) return to the host in one synchronisation.  From that count set_filter's rule: at
+ *                 most 95 % visible and the search walks the list, above it tests the call's mask per row, and with every bit
+ *                 set and no handle mask it is the unmasked search.  Under profiling these three launches fall into ms[1] /
+ *                 n_launch[1] of lb_gpu_index_last_timing.
+ * Not here: a bitmap per query, predicates (filter_int64 / _float32) given per call, the IVF code handles. */
+int lb_gpu_index_search_bitmap_ctx(lb_gpu_index *h, int64_t nq, const float *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                   float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_index_search_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, const uint8_t *d_bitmap,
+                                          int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx);
+int lb_gpu_index_search_f16_bitmap_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                       float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_index_search_f16_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *d_queries, int k, const uint8_t *d_bitmap,
+                                              int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx);
+int lb_gpu_index_search_i8_bitmap_ctx(lb_gpu_index *h, int64_t nq, const int8_t *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                      float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_index_search_i8_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t *d_queries, int k, const uint8_t *d_bitmap,
+                                             int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx);
 
 /* simd.CompareOp values (internal/simd/simd.go:38-45) */
 typedef enum { LB_CMP_EQ = 0, LB_CMP_NEQ = 1, LB_CMP_GT = 2, LB_CMP_GE = 3, LB_CMP_LT = 4, LB_CMP_LE = 5 } lb_compare_op;
@@ -1376,7 +1429,8 @@ double lb_gpu_shader_clock_mhz(int device, int spin_us);
  * HIP-event timing of the dominant kernels of the most recent search on this handle,
  * recorded on the stream the kernels ran on.  Enable before the search. */
 int lb_gpu_index_set_profiling(lb_gpu_index *h, int enable);
-/* ms spent in: [0] candidate GEMM kernels, [1] select kernels, [2] re-rank, [3] scan
+/* ms spent in: [0] candidate GEMM kernels, [1] select kernels (and the three launches that build the view of a call with a
+ * row bitmap, "call bitmap" above), [2] re-rank, [3] scan
  * kernels, [4] whole search (device side).  n_launch[i] = launches of that class. */
 int lb_gpu_index_last_timing(const lb_gpu_index *h, float ms[5], int n_launch[5]);
 

@@ -93,6 +93,43 @@ class Index {
         return wrap("search", lb_gpu_index_search_ctx(h_, nq, queries, k, distances, ids, ctx));
     }
 
+    // Search under a row bitmap given with the call (SearchVectorsWithBitmap; "call bitmap" in longbow_gpu.h): one bit per row
+    // position, least significant bit first, exactly ceil(ntotal / 8) bytes.  The index is left as it is, and calls with
+    // different bitmaps run concurrently.
+    Error SearchBitmap(const std::vector<float> &vector, int k, const std::vector<uint8_t> &bitmap, std::vector<int64_t> &ids,
+                       std::vector<float> &distances)
+    {
+        std::shared_lock<std::shared_mutex> g(mu_);
+        if (closed_) return {LB_ERR_CLOSED, "index is closed"};
+        if ((int)vector.size() != dim_)
+            return {LB_ERR_INVALID_ARG, "query vector dimension " + std::to_string(vector.size()) +
+                                            " does not match index dimension " + std::to_string(dim_)};
+        const int64_t n = lb_gpu_index_ntotal(h_);
+        if ((int64_t)bitmap.size() != (n + 7) / 8)
+            return {LB_ERR_INVALID_ARG, "a bitmap of " + std::to_string(bitmap.size()) + " bytes, " + std::to_string((n + 7) / 8) +
+                                            " are read for " + std::to_string(n) + " rows"};
+        ids.assign((size_t)k, -1);
+        distances.assign((size_t)k, 0.f);
+        const uint8_t none = 0; // (an empty index: a bitmap that is there, and of which nothing is read)
+        Error e = wrap("search", lb_gpu_index_search_bitmap_ctx(h_, 1, vector.data(), k, bitmap.empty() ? &none : bitmap.data(), n,
+                                                                distances.data(), ids.data(), nullptr));
+        if (e) return e;
+        size_t m = (size_t)k;
+        while (m > 0 && ids[m - 1] < 0) m--;
+        ids.resize(m);
+        distances.resize(m);
+        return {};
+    }
+
+    // batched: one bitmap of nbits == ntotal bits for all nq queries; bitmap null: the plain search (padding kept)
+    Error SearchBatchBitmap(const float *queries, int64_t nq, int k, const uint8_t *bitmap, int64_t nbits, int64_t *ids, float *distances,
+                            const lb_cancel *ctx = nullptr)
+    {
+        std::shared_lock<std::shared_mutex> g(mu_);
+        if (closed_) return {LB_ERR_CLOSED, "index is closed"};
+        return wrap("search", lb_gpu_index_search_bitmap_ctx(h_, nq, queries, k, bitmap, nbits, distances, ids, ctx));
+    }
+
     // lb_candidate_mode: LB_CAND_AUTO (default), LB_CAND_F32_MFMA (strict), LB_CAND_SPLIT_BF16[_INREG]; same results
     Error SetCandidateMode(int mode)
     {

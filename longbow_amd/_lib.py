@@ -89,7 +89,14 @@ SIGNATURES = [
     ("lb_gpu_index_search_i8", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_index_search_i8_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
     ("lb_gpu_index_search_i8_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_f16_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_f16_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_i8_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_i8_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_index_set_filter", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_index_nvisible", _i64, [_vp]),
     ("lb_gpu_index_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_index_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
     ("lb_gpu_index_remove", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),

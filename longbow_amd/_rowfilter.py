@@ -1,5 +1,18 @@
-"""The row filter of the code indexes and of the IVF indexes, shared by bq.py, sq8.py, pq.py, ivf.py and ivfpq.py."""
+"""The row filter of the code indexes and of the IVF indexes, shared by bq.py, sq8.py, pq.py, ivf.py and ivfpq.py, and the packing
+of a row bitmap given with a search call (gpu.pack_bitmap, ivf.pack_bitmap)."""
 import numpy as np
+
+
+def pack_bitmap(mask):
+    """A byte or bool mask over the row positions, [n] or [nq, n] (a row is visible iff its value is non-zero) -> (bits, stride):
+    the bits least significant first as in an Arrow validity buffer, row r at bits[r >> 3] >> (r & 7) & 1, as uint8 [ceil(n / 8)]
+    with stride 0, or [nq, ceil(n / 8)] with the bytes of one row as the stride.  What ivf.IVFFlat.search(bitmap=, bitmap_stride=)
+    takes; gpu.Index.Search / SearchBatch(bitmap=) take the bits of the [n] form (one bitmap per call, no stride)."""
+    m = np.asarray(mask) != 0
+    if m.ndim not in (1, 2):
+        raise ValueError(f"a mask is [n] or [nq, n], got {m.ndim} dimensions")
+    bits = np.ascontiguousarray(np.packbits(m, axis=-1, bitorder="little"))
+    return bits, (0 if m.ndim == 1 else bits.shape[1])
 
 
 class RowFilterMixin:

@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "liblongbow_gpu.so")
 OUT_DIAG = os.path.join(HERE, "liblongbow_gpu_diag.so")
 SOURCES = ["index.hip", "index_remove.hip", "index_search.hip", "simd_api.hip", "refine.hip", "pq.hip", "pq_train.hip", "bq.hip", "sq8.hip", "ivf.hip", "ivf_train.hip", "ivfpq.hip", "ivfsq8.hip", "ivfbq.hip", "comm.hip", "flight.hip", "kernels_gemm.hip", "kernels_gemm_narrow.hip", "kernels_gemm_tall2.hip", "kernels_gemm_tall16.hip", "kernels_scan.hip", "kernels_select.hip", "kernels_finish.hip",
-           "kernels_pq.hip", "kernels_pq2.hip", "kernels_pq_list.hip", "kernels_pq_train.hip", "kernels_filter.hip", "kernels_i8.hip", "kernels_bq.hip", "kernels_sq8.hip", "kernels_countsel.hip", "kernels_ivf.hip", "kernels_ivf_call.hip", "kernels_ivf_f16.hip", "kernels_ivf_i8.hip", "kernels_ivf_train.hip", "kernels_ivfpq.hip", "kernels_ivfsq8.hip", "kernels_ivfbq.hip", "kernels_refine.hip", "kernels_remove.hip"]
+           "kernels_pq.hip", "kernels_pq2.hip", "kernels_pq_list.hip", "kernels_pq_train.hip", "kernels_filter.hip", "kernels_i8.hip", "kernels_bq.hip", "kernels_sq8.hip", "kernels_countsel.hip", "kernels_index_call.hip", "kernels_ivf.hip", "kernels_ivf_call.hip", "kernels_ivf_f16.hip", "kernels_ivf_i8.hip", "kernels_ivf_train.hip", "kernels_ivfpq.hip", "kernels_ivfsq8.hip", "kernels_ivfbq.hip", "kernels_refine.hip", "kernels_remove.hip"]
 HEADERS = ["lb_device.h", "lb_exact.h", "lb_admit.h", "lb_host.h", "lb_handle.h", "lb_index.h", "lb_combine.h", "lb_select.h", "lb_countsel.h", "lb_ivf.h", "lb_ivf_f16.h", "lb_ivf_i8.h", "lb_i8_exact.h", "lb_ivf_host.h", "lb_list_scan.h", "lb_ivfpq.h", "lb_ivfsq8.h", "lb_ivfbq.h", "lb_refine.h", "lb_remove.h", os.path.join("..", "..", "include", "longbow_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -574,6 +574,12 @@ int64_t lb_gpu_index_ntotal(const lb_gpu_index *h)
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_index *>(h)->mu); // (Add commits its rows under the writer lock)
     return h->n;
 }
+int64_t lb_gpu_index_nvisible(const lb_gpu_index *h)
+{
+    if (!h) return 0;
+    std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_index *>(h)->mu);
+    return h->has_mask ? h->n_visible : h->n; // (rebuild_rowmap's count: every filter call, removal and add brings it up to date)
+}
 int lb_gpu_index_dim(const lb_gpu_index *h) { return h ? h->dim : 0; }
 int lb_gpu_index_device(const lb_gpu_index *h) { return h ? h->device : -1; }
 

@@ -1,5 +1,6 @@
 // index_search.hip -- searching an index: the workspace pool, the exact-scan driver, route choice and the batched-search driver,
-// the host-pointer staging and combining path, and every lb_gpu_index_search* entry point of include/longbow_gpu.h.
+// the host-pointer staging and combining path, the view of a call that brings its own row bitmap (build_call_view; kernels in
+// kernels_index_call.hip), and every lb_gpu_index_search* entry point of include/longbow_gpu.h.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
 #include "lb_host.h"
@@ -214,7 +215,7 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                    int nsel, int k, int mode, float *d_dist, int64_t *d_lab, bool prof)
 {
     const int metric = h->metric, order = h->order.load();
-    const IndexRowView rv = row_view(h);
+    const IndexRowView rv = row_view(h, w);
     const int64_t n = rv.n;
     const uint8_t *mask = rv.mask;
     const int kkeep = std::max(k, 1);
@@ -520,7 +521,7 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
                     int64_t *d_lab, bool prof)
 {
     static const int mfma_minq = lb_tunable("LB_I8_MFMA_MINQ", 16);
-    const IndexRowView rv = row_view(h);
+    const IndexRowView rv = row_view(h, w);
     const int kkeep = std::max(k, 1);
     SamplePlan sp;
     if (nq >= mfma_minq && mfma_i8_supported(h->metric, h->dim, h->d_X, d_q8)) sp = sample_plan(rv.n, kkeep, w->cap);
@@ -591,10 +592,11 @@ KeyBound key_bound(const lb_gpu_index *h, int split, bool have_xh)
 }
 
 // the rows behind the plan's sampled positions: the index's shared map (built by the first search after a change), or when that
-// holds another plan, the workspace's own
+// holds another plan, the workspace's own -- always the workspace's own under a call's view (Workspace::call_view): the shared
+// map is the handle's view's, neither read nor published by a call that brought its own bitmap
 const uint32_t *sample_map(lb_gpu_index *h, Workspace *w, hipStream_t s, const IndexRowView &rv, const SamplePlan &sp)
 {
-    {
+    if (!w->call_view) {
         std::lock_guard<std::mutex> g(h->smap_mu);
         if (!h->smap_valid) {
             h->d_smap.ensure(sp.count);
@@ -652,7 +654,7 @@ int run_batch(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float 
               const Route &route, int kc, bool narrow_ok, bool have_xh, std::vector<int> &bad, bool &gave_up)
 {
     const int metric = h->metric, order = h->order.load();
-    const IndexRowView rv = row_view(h);
+    const IndexRowView rv = row_view(h, w);
     const int64_t n = rv.n;
     const uint8_t *mask = rv.mask;
     const SamplePlan sp = sample_plan(n, kc, w->cap);
@@ -856,7 +858,7 @@ int search_batch_device(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, co
     static const int narrow_min = lb_tunable("LB_NARROW_MINQ", 5);
     static const int f16_kc_mult = lb_tunable("LB_F16_KC_MULT", 0);
     // the same for every attempt (the caller holds the index's shared lock)
-    const IndexRowView rv = row_view(h);
+    const IndexRowView rv = row_view(h, w);
     const int64_t n = rv.n; // positions to walk: corpus rows, or the visible-row list under a selective filter
     const int cmode = h->cand_mode.load();
     const bool narrow_ok = !h->f16_rows && h->dim % 32 == 0 && ((reinterpret_cast<uintptr_t>(d_q) & 15) == 0);
@@ -1001,6 +1003,59 @@ int search_args(lb_gpu_index *h, int64_t nq, const void *queries, int k, const v
     return knn_args(h, nq, queries, k, dist, labels, ctx, [&] { return dtype_mismatch(h, dtype); });
 }
 
+// ---- a row bitmap given with the call (lb_gpu_index_search*_bitmap*) ------------------------------------------------------------
+// The bitmap as an entry point got it: host or device memory, one bit per row position, least significant bit first; bits null:
+// the plain search.  lease: where a host bitmap's bytes go on the device -- the entry point's, declared outside every guard, so
+// that the stream is drained before the bytes return to the pool.
+struct CallBits {
+    const uint8_t *bits = nullptr;
+    int64_t nbits = 0;
+    bool on_device = true;
+    Lease *lease = nullptr;
+};
+
+// The view of a call from its bitmap (kernels_index_call.hip), on the call's stream and into the call's workspace: the bits ANDed
+// with the handle's effective mask, the ascending list of the rows that pass, and their number -- the four bytes and the one
+// synchronisation the build costs.  From that number rebuild_rowmap's rule, with the same LB_ROWMAP_MAX_PCT: the list at or
+// below it, the per-row test of the call's mask above it, and the unmasked view when nothing is hidden at all.  The caller holds
+// the shared lock and has checked nbits == h->n >= 1; the handle is only read (d_mask, has_mask).
+void build_call_view(lb_gpu_index *h, Workspace *w, hipStream_t s, const CallBits &b, bool prof)
+{
+    static const int max_pct = lb_tunable("LB_ROWMAP_MAX_PCT", 95);
+    const int64_t n = h->n, blocks = index_call_blocks(n);
+    const uint8_t *d_bits = b.bits;
+    if (!b.on_device) {
+        const size_t bytes = (size_t)((n + 7) / 8);
+        b.lease->reset(h->device, bytes);
+        LB_HIP(hipMemcpyAsync(b.lease->p, b.bits, bytes, hipMemcpyHostToDevice, s));
+        d_bits = b.lease->as<uint8_t>();
+    }
+    w->d_cmask.ensure((size_t)blocks * INDEX_CALL_BLOCK_ROWS);
+    w->d_crows.ensure((size_t)n);
+    w->d_cscratch.ensure((size_t)compact_scratch_words(n));
+    if (!w->h_ctotal) w->h_ctotal.alloc(1);
+    {
+        ProfScope p(w, s, prof, 1);
+        launch_index_call_bits(d_bits, h->has_mask ? h->d_mask.get() : nullptr, n, w->d_cmask.get(), w->d_cscratch.get(), s);
+    }
+    {
+        ProfScope p(w, s, prof, 1);
+        launch_compact_offsets(w->d_cscratch.get(), blocks, s);
+    }
+    {
+        ProfScope p(w, s, prof, 1);
+        launch_index_call_scatter(w->d_cmask.get(), n, w->d_cscratch.get(), w->d_crows.get(), s);
+    }
+    LB_LAUNCH_CHECK();
+    LB_HIP(hipMemcpyAsync(w->h_ctotal.get(), w->d_cscratch.get() + blocks, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    LB_HIP(hipStreamSynchronize(s));
+    const int64_t visible = (int64_t)*w->h_ctotal.get();
+    if (max_pct > 0 && visible * 100 <= n * (int64_t)max_pct) w->cv = IndexRowView{nullptr, w->d_crows.get(), visible};
+    else if (visible == n && !h->has_mask) w->cv = IndexRowView{nullptr, nullptr, n};
+    else w->cv = IndexRowView{w->d_cmask.get(), nullptr, n};
+    w->call_view = true;
+}
+
 // A search's workspace: it goes back to the pool when the call ends, unless the call dropped it.
 struct WsLoan {
     lb_gpu_index *h;
@@ -1009,6 +1064,7 @@ struct WsLoan {
     {
         if (!w) return;
         w->ctx = nullptr;
+        w->call_view = false;
         release_ws(h, std::move(w));
     }
 };
@@ -1022,11 +1078,15 @@ int64_t lb_gpu_index_fused_giveups(const lb_gpu_index *h) { return h ? h->fused_
 int lb_gpu_index_last_route(const lb_gpu_index *h) { return h ? h->last_route.load() : 0; }
 
 static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int k, float *d_dist, int64_t *d_labels, void *stream,
-                         const lb_cancel *ctx, int dtype)
+                         const lb_cancel *ctx, int dtype, const CallBits &call = CallBits{})
 {
     int rc = search_args(h, nq, d_queries, k, d_dist, d_labels, ctx, dtype);
     if (rc != LB_OK || nq == 0) return rc;
     std::shared_lock<std::shared_mutex> g(h->mu);
+    if (call.bits && call.nbits != h->n) { // (set_filter's n != ntotal rule)
+        h->set_error("a bitmap of %lld bits for %lld rows", (long long)call.nbits, (long long)h->n);
+        return LB_ERR_INVALID_ARG;
+    }
 #ifdef LB_DIAG
     if (g_search_fail_next.exchange(0) != 0) { h->set_error("search failure forced by lb_debug_search_fail_next"); return LB_ERR_INTERNAL; }
 #endif
@@ -1050,6 +1110,10 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
         if (h->n == 0) {
             launch_fill_empty(d_dist, d_labels, nq * k, s);
         } else {
+            if (call.bits) { // the call's view, once for all its batches
+                ctx_check(ctx);
+                build_call_view(h, w, s, call, prof);
+            }
             for (int64_t q0 = 0; q0 < nq; q0 += kMaxBatch) {
                 const int bq = (int)std::min<int64_t>(kMaxBatch, nq - q0);
                 const float *bq_f32 = nullptr;
@@ -1130,7 +1194,9 @@ int lb_cancel_state(const lb_cancel *c) { return ctx_state(c); }
 // Host-pointer search of one or several requests with the same k as ONE device batch: borrowed host buffers -> pooled pinned
 // slab -> HBM (async DMA on the call's own stream), and back; every request gets its rows of the result.
 // (dtype: the requests' queries are fp16 -- 2 bytes an element -- or int8 -- 1 byte; those are never combined)
-static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, int k, const lb_cancel *ctx, int dtype = 0)
+// (call: the row bitmap of a call that brought one -- such a call is one request, never combined)
+static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, int k, const lb_cancel *ctx, int dtype = 0,
+                             const CallBits &call = CallBits{})
 {
     int64_t nq = 0;
     for (int i = 0; i < nreq; i++) nq += reqs[i]->nq;
@@ -1162,7 +1228,7 @@ static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, in
         // (direct results: the search's own stream synchronisation is what makes them visible; large ones go through HBM and one DMA)
         char *obuf = sl.direct ? hb : dbuf;
         const int rc = search_device(h, nq, dbuf, k, reinterpret_cast<float *>(obuf + sl.doff), reinterpret_cast<int64_t *>(obuf + sl.loff),
-                                     st->stream, ctx, dtype);
+                                     st->stream, ctx, dtype, call);
         if (rc == LB_OK) {
             if (!sl.direct) {
                 LB_HIP(hipMemcpyAsync(hb + sl.doff, dbuf + sl.doff, sl.db + sl.lb, hipMemcpyDeviceToHost, st->stream));
@@ -1177,17 +1243,19 @@ static int host_search_multi(lb_gpu_index *h, HostReq *const *reqs, int nreq, in
 }
 
 // the host-pointer entry points; dtype: the element type of `queries` (0 float32, 1 fp16 bits, 2 int8: host_search_multi copies bytes)
-static int host_search(lb_gpu_index *h, int64_t nq, const void *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx, int dtype)
+static int host_search(lb_gpu_index *h, int64_t nq, const void *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx, int dtype,
+                       const CallBits &call = CallBits{})
 {
     if (h && nq == 0 && k > 0) return LB_OK; // (a host call of no queries does not look at the index's element type either)
     // (without the context: a host call answers it after the size of its batch, in the device search)
     if (const int rc = search_args(h, nq, queries, k, dist, labels, nullptr, dtype)) return rc;
     // (a call with a cancellation context is searched on its own: its deadline is not its neighbours'; fp16 and int8 calls too)
     HostReq me{static_cast<const float *>(queries), nq, dist, labels, k};
-    if (dtype == 0 && !ctx && nq <= SearchCombiner::kMaxNq && h->combiner.on.load() != 0)
+    // (and a call with a row bitmap of its own: its view is not its neighbours')
+    if (dtype == 0 && !ctx && !call.bits && nq <= SearchCombiner::kMaxNq && h->combiner.on.load() != 0)
         return h->combiner.search(me, [h](HostReq *const *reqs, int n, int kk) { return host_search_multi(h, reqs, n, kk, nullptr); });
     HostReq *one = &me;
-    return host_search_multi(h, &one, 1, k, ctx, dtype);
+    return host_search_multi(h, &one, 1, k, ctx, dtype, call);
 }
 
 int lb_gpu_index_search_ctx(lb_gpu_index *h, int64_t nq, const float *queries, int k, float *dist, int64_t *labels,
@@ -1212,6 +1280,46 @@ int lb_gpu_index_search_i8_ctx(lb_gpu_index *h, int64_t nq, const int8_t *querie
 int lb_gpu_index_search_i8(lb_gpu_index *h, int64_t nq, const int8_t *queries, int k, float *dist, int64_t *labels)
 {
     return lb_gpu_index_search_i8_ctx(h, nq, queries, k, dist, labels, nullptr);
+}
+
+// the same searches under a row bitmap given with the call (include/longbow_gpu.h, "call bitmap"); a NULL bitmap: the plain search
+// through the plain path.  The host forms' bitmap bytes travel in `bits`, declared here, outside every guard.
+static int host_search_bitmap(lb_gpu_index *h, int64_t nq, const void *queries, int k, const uint8_t *bitmap, int64_t nbits, float *dist,
+                              int64_t *labels, const lb_cancel *ctx, int dtype)
+{
+    if (!bitmap) return host_search(h, nq, queries, k, dist, labels, ctx, dtype);
+    Lease bits;
+    return host_search(h, nq, queries, k, dist, labels, ctx, dtype, CallBits{bitmap, nbits, false, &bits});
+}
+int lb_gpu_index_search_bitmap_ctx(lb_gpu_index *h, int64_t nq, const float *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                   float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    return host_search_bitmap(h, nq, queries, k, bitmap, nbits, dist, labels, ctx, 0);
+}
+int lb_gpu_index_search_f16_bitmap_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                       float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    return host_search_bitmap(h, nq, queries, k, bitmap, nbits, dist, labels, ctx, 1);
+}
+int lb_gpu_index_search_i8_bitmap_ctx(lb_gpu_index *h, int64_t nq, const int8_t *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                      float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    return host_search_bitmap(h, nq, queries, k, bitmap, nbits, dist, labels, ctx, 2);
+}
+int lb_gpu_index_search_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, const uint8_t *d_bitmap,
+                                          int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 0, CallBits{d_bitmap, nbits, true, nullptr});
+}
+int lb_gpu_index_search_f16_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const uint16_t *d_queries, int k, const uint8_t *d_bitmap,
+                                              int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 1, CallBits{d_bitmap, nbits, true, nullptr});
+}
+int lb_gpu_index_search_i8_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t *d_queries, int k, const uint8_t *d_bitmap,
+                                             int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 2, CallBits{d_bitmap, nbits, true, nullptr});
 }
 
 int lb_gpu_index_set_search_combining(lb_gpu_index *h, int enable) { return combining_set(h, enable); }

@@ -692,6 +692,15 @@ int64_t compact_scratch_words(int64_t n);
 void launch_compact_mask(const uint8_t *mask, int64_t n, uint32_t *rowmap, uint32_t *scratch, hipStream_t s);
 // its middle step alone: counts[0, nb) -> their exclusive prefix in place, counts[nb] = the total (one workgroup)
 void launch_compact_offsets(uint32_t *counts, int64_t nb, hipStream_t s);
+// the view of a search call that brings its own row bitmap (kernels_index_call.hip).  d_bits: [ceil(n / 8)] bytes at any address,
+// bit r & 7 of byte r >> 3 is row r; hmask: the index's effective mask or null; cmask: the call's mask, 1 where the bit is set and
+// hmask (if any) is non-zero, written in whole blocks of INDEX_CALL_BLOCK_ROWS bytes (0 behind row n - 1); scratch:
+// compact_scratch_words(n) words.  _bits leaves a count per block in scratch; launch_compact_offsets(scratch, blocks) turns them
+// into offsets with the total at scratch[blocks]; _scatter then writes the ascending row list (total entries).
+constexpr int INDEX_CALL_BLOCK_ROWS = 2048;
+inline int64_t index_call_blocks(int64_t n) { return (n + INDEX_CALL_BLOCK_ROWS - 1) / INDEX_CALL_BLOCK_ROWS; }
+void launch_index_call_bits(const uint8_t *d_bits, const uint8_t *hmask, int64_t n, uint8_t *cmask, uint32_t *scratch, hipStream_t s);
+void launch_index_call_scatter(const uint8_t *cmask, int64_t n, const uint32_t *scratch, uint32_t *rowmap, hipStream_t s);
 // removal and compaction of the flat index (kernels_remove.hip).  live: a byte per row, non-zero = live, held in whole words;
 // mask: the index's effective mask.  Both lose the bytes of the rows a call removes; *removed (zero before the launch) gains the
 // number of rows that were live before it, each counted once however often it is named.

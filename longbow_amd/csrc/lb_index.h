@@ -21,6 +21,14 @@ struct LB_INTERNAL Event {
     int cls = 0;
 };
 
+// What a search walks: all corpus rows (optionally testing the mask per row), or the compacted
+// list of visible rows (rebuild_rowmap decides; build_call_view for a call that brings its own bitmap).
+struct IndexRowView { // (lb::RowView is the code handles': a list or nothing)
+    const uint8_t *mask;
+    const uint32_t *rowmap;
+    int64_t n;
+};
+
 struct LB_INTERNAL Workspace {
     int device = 0;
     Stream stream;
@@ -51,6 +59,14 @@ struct LB_INTERNAL Workspace {
     std::vector<Event> events;
     size_t ev_used = 0;
     const lb_cancel *ctx = nullptr; // the running call's cancellation context (or null)
+    // the view of a call that brought its own row bitmap (build_call_view, index_search.hip; kernels_index_call.hip): the call's
+    // effective mask (whole blocks of INDEX_CALL_BLOCK_ROWS bytes), its row list and the compaction scratch, grown on demand;
+    // call_view says that cv holds, and every search of the call then reads cv where it would read row_view(h)
+    DevBuf<uint8_t> d_cmask;
+    DevBuf<uint32_t> d_crows, d_cscratch;
+    PinnedBuf<uint32_t> h_ctotal; // the visible count, the four bytes the build brings back
+    bool call_view = false;
+    IndexRowView cv{nullptr, nullptr, 0};
 
     ~Workspace() { (void)hipSetDevice(device); }
 };
@@ -257,15 +273,10 @@ struct lb_gpu_index : HandleCore {
     int32_t *norm2_i8() const { return reinterpret_cast<int32_t *>(d_norm2.get()); }
 };
 
-// What a search walks: all corpus rows (optionally testing the mask per row), or the compacted
-// list of visible rows (rebuild_rowmap decides).
-struct IndexRowView { // (lb::RowView is the code handles': a list or nothing)
-    const uint8_t *mask;
-    const uint32_t *rowmap;
-    int64_t n;
-};
-static IndexRowView row_view(const lb_gpu_index *h)
+// the handle's view, or (w: the call's workspace) the view of a call that brought its own bitmap
+static IndexRowView row_view(const lb_gpu_index *h, const Workspace *w = nullptr)
 {
+    if (w && w->call_view) return w->cv;
     if (!h->has_mask) return {nullptr, nullptr, h->n};
     if (h->rowmap_on) return {nullptr, h->d_rowmap.get(), h->n_visible};
     return {h->d_mask.get(), nullptr, h->n};

@@ -11,6 +11,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import Canceled, DeadlineExceeded, GPUNotAvailable, LongbowGPUError  # noqa: F401
+from ._rowfilter import pack_bitmap  # noqa: F401  (gpu.pack_bitmap: a byte or bool mask -> the bits Search(bitmap=) takes)
 from .simd import MetricType, Order
 
 ErrGPUNotAvailable = GPUNotAvailable
@@ -107,13 +108,14 @@ class Index:
             idp = ids.ctypes.data
         _lib.check(self._entry("lb_gpu_index_add")(self._h, n, vectors.ctypes.data, idp), self._h, lib=self._lib)
 
-    def Search(self, vector, k, ctx=None):
-        """Search(vector []float32, k int) (ids []int64, distances []float32, err)  (faiss_gpu.go:107-144)"""
+    def Search(self, vector, k, ctx=None, bitmap=None):
+        """Search(vector []float32, k int) (ids []int64, distances []float32, err)  (faiss_gpu.go:107-144); bitmap: a row filter
+        of this call alone (SearchBatch)"""
         self._live()
         vector = self._as_elems(vector).reshape(-1)
         if vector.size != self.dim:
             raise ValueError(f"query vector dimension {vector.size} does not match index dimension {self.dim}")
-        ids, dist = self.SearchBatch(vector[None, :], k, ctx=ctx)
+        ids, dist = self.SearchBatch(vector[None, :], k, ctx=ctx, bitmap=bitmap)
         return ids[0], dist[0]
 
     def Close(self):
@@ -126,7 +128,11 @@ class Index:
             self._lib.lb_gpu_index_free(h)
 
     # -- superset ----------------------------------------------------------------
-    def SearchBatch(self, queries, k, ctx=None):
+    def SearchBatch(self, queries, k, ctx=None, bitmap=None):
+        """bitmap: None, or a row filter of THIS CALL alone, shared by its queries (SearchVectorsWithBitmap): the LSB-first bits
+        of the ntotal row positions as uint8 [ceil(ntotal / 8)] (pack_bitmap(mask)[0]).  The answer is what the index gives
+        after set_filter with that mask, ANDed with its own filter and removals; the index is left as it is, and calls with
+        different bitmaps run concurrently.  Such a call is never combined with others."""
         self._live()
         queries = self._as_elems(queries)
         if queries.ndim != 2 or queries.shape[1] != self.dim:
@@ -134,9 +140,20 @@ class Index:
         nq = queries.shape[0]
         dist = np.empty((nq, k), np.float32)
         labels = np.empty((nq, k), np.int64)
-        search = self._entry("lb_gpu_index_search", "_ctx")
-        _lib.check(search(self._h, nq, queries.ctypes.data, k, dist.ctypes.data,
-                          labels.ctypes.data, ctx._h if ctx is not None else None), self._h, lib=self._lib)
+        c = ctx._h if ctx is not None else None
+        if bitmap is None:
+            search = self._entry("lb_gpu_index_search", "_ctx")
+            _lib.check(search(self._h, nq, queries.ctypes.data, k, dist.ctypes.data, labels.ctypes.data, c), self._h, lib=self._lib)
+            return labels, dist
+        b = np.ascontiguousarray(bitmap, np.uint8).reshape(-1)
+        n = self.ntotal
+        if b.size != (n + 7) // 8:  # (the bits of ntotal rows, no more: an old length is caught)
+            raise ValueError(f"a bitmap of {b.size} bytes, {(n + 7) // 8} are read for {n} rows")
+        if b.size == 0:
+            b = np.zeros(1, np.uint8)  # (an empty index: a bitmap that is there, and of which nothing is read)
+        search = self._entry("lb_gpu_index_search", "_bitmap_ctx")
+        _lib.check(search(self._h, nq, queries.ctypes.data, k, b.ctypes.data, n, dist.ctypes.data, labels.ctypes.data, c),
+                   self._h, lib=self._lib)
         return labels, dist
 
     def _as_elems(self, a):
@@ -226,12 +243,17 @@ class Index:
         self._live()
         _lib.check(self._entry("lb_gpu_index_add", "_device")(self._h, n, d_vectors, d_ids), self._h, lib=self._lib)
 
-    def search_device(self, nq, d_queries, k, d_dist, d_labels, stream=None, ctx=None):
-        """d_queries: f32, fp16 on a float16 index, int8 on an int8 index"""
+    def search_device(self, nq, d_queries, k, d_dist, d_labels, stream=None, ctx=None, d_bitmap=None, nbits=0):
+        """d_queries: f32, fp16 on a float16 index, int8 on an int8 index; d_bitmap: None, or device memory at any byte address
+        with the LSB-first bits of nbits == ntotal row positions, a row filter of this call alone (SearchBatch)"""
         self._live()
-        search = self._entry("lb_gpu_index_search", "_device_ctx")
-        _lib.check(search(self._h, nq, d_queries, k, d_dist, d_labels, stream,
-                          ctx._h if ctx is not None else None), self._h, lib=self._lib)
+        c = ctx._h if ctx is not None else None
+        if d_bitmap is None:
+            search = self._entry("lb_gpu_index_search", "_device_ctx")
+            _lib.check(search(self._h, nq, d_queries, k, d_dist, d_labels, stream, c), self._h, lib=self._lib)
+        else:
+            search = self._entry("lb_gpu_index_search", "_bitmap_device_ctx")
+            _lib.check(search(self._h, nq, d_queries, k, d_bitmap, nbits, d_dist, d_labels, stream, c), self._h, lib=self._lib)
 
     def reserve(self, n_total):
         self._live()
@@ -278,6 +300,11 @@ class Index:
             return
         mask = np.ascontiguousarray(mask, np.uint8)
         _lib.check(self._lib.lb_gpu_index_set_filter(self._h, mask.ctypes.data, mask.size), self._h, lib=self._lib)
+
+    def nvisible(self):
+        """rows a plain search sees: the live rows that pass the index's filter; a bitmap given with a call does not move it"""
+        self._live()
+        return int(self._lib.lb_gpu_index_nvisible(self._h))
 
     def filter_column(self, column, operator, value, validity=None, validity_offset=0, combine=False):
         """Evaluate `column OP value` on the device into the row mask (query.Filter semantics,

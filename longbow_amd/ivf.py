@@ -25,7 +25,7 @@ import numpy as np
 
 from . import _lib, pq
 from ._ivfbase import IVFBase
-from ._rowfilter import RowFilterMixin
+from ._rowfilter import RowFilterMixin, pack_bitmap  # noqa: F401  (pack_bitmap: exported here as ivf.pack_bitmap)
 from .gpu import DataType
 
 FLT_MAX = np.float32(3.4028234663852886e38)
@@ -228,17 +228,6 @@ class IVFFlat(RemovalMixin, RowFilterMixin, IVFBase):
         out = C.c_float(0)
         self._check(self._lib.lb_gpu_ivf_last_build_timing(self._h, C.byref(out)))
         return float(out.value)
-
-
-def pack_bitmap(mask):
-    """A byte or bool mask over the row positions, [n] or [nq, n] (a row is visible iff its value is non-zero) -> (bits, stride):
-    the bits least significant first as in an Arrow validity buffer, row r at bits[r >> 3] >> (r & 7) & 1, as uint8 [ceil(n / 8)]
-    with stride 0, or [nq, ceil(n / 8)] with the bytes of one row as the stride.  What search(bitmap=, bitmap_stride=) takes."""
-    m = np.asarray(mask) != 0
-    if m.ndim not in (1, 2):
-        raise ValueError(f"a mask is [n] or [nq, n], got {m.ndim} dimensions")
-    bits = np.ascontiguousarray(np.packbits(m, axis=-1, bitorder="little"))
-    return bits, (0 if m.ndim == 1 else bits.shape[1])
 
 
 def rows_i8(vectors, dims):
