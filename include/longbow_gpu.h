@@ -266,7 +266,8 @@ int64_t lb_gpu_index_nvisible(const lb_gpu_index *h);
  *                 most 95 % visible and the search walks the list, above it tests the call's mask per row, and with every bit
  *                 set and no handle mask it is the unmasked search.  Under profiling these three launches fall into ms[1] /
  *                 n_launch[1] of lb_gpu_index_last_timing.
- * Not here: a bitmap per query, predicates (filter_int64 / _float32) given per call, the IVF code handles. */
+ * Not here: a bitmap per query, predicates (filter_int64 / _float32) given per call.  (The IVF-Flat, IVF-PQ and IVF-SQ8 handles
+ * have their own *_search_bitmap* entry points below; the IVF-BQ handle has none.) */
 int lb_gpu_index_search_bitmap_ctx(lb_gpu_index *h, int64_t nq, const float *queries, int k, const uint8_t *bitmap, int64_t nbits,
                                    float *dist, int64_t *labels, const lb_cancel *ctx);
 int lb_gpu_index_search_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, const uint8_t *d_bitmap,
@@ -843,7 +844,10 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     the call's own (over the handle's visible lists when it has a filter or removed rows, so the AND costs
  *                     nothing), which the plan, the scan and the selection then walk; scratch is sized by the handle's list sizes,
  *                     nothing returns to the host in between, and the cost of the scan and the selection follows the rows that
- *                     pass.  ctx is polled before these launches as before every other; under profiling they fall into ms[1].
+ *                     pass.  Under one bitmap (stride_bytes 0), when the call's queries times their largest probed lists exceed
+ *                     the rows the handle's lists hold, every list is compacted once for the call, in its first batch, and not
+ *                     once per query and probe; a host decision from the list sizes, and the result does not depend on it.
+ *                     ctx is polled before these launches as before every other; under profiling they fall into ms[1].
  * Not here: fp16 or int8 centroids, fp16 queries, f32 queries on an int8 handle, predicates (filter_int64 / _float32) given per
  * search call, search combining, lb_gpu_comm_*. */
 typedef struct lb_gpu_ivf lb_gpu_ivf;
@@ -1017,7 +1021,8 @@ int lb_gpu_ivf_compact(lb_gpu_ivf *p, int64_t *old_rows, int64_t cap);
  * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
  * refused call writes nothing.  Searches and reads share the handle; adds, reserve and the filter calls take it alone.  ctx
  * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here:
- * a filter given per search call, adding ready-made codes with caller-given lists, search combining, lb_gpu_comm_*, removing
+ * a filter given per search call as predicates (filter_int64 / _float32; as a row bitmap it is here:
+ * lb_gpu_ivfpq_search_bitmap_ctx below), adding ready-made codes with caller-given lists, search combining, lb_gpu_comm_*, removing
  * rows, Save / Load, and the Go and C++ mirrors.
  *
  * Residual codes.  lb_gpu_ivfpq_new_residual makes a RESIDUAL handle: its arguments, limits, order of checks and status codes
@@ -1070,6 +1075,34 @@ int lb_gpu_ivfpq_search_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, i
                             const lb_cancel *ctx);
 int lb_gpu_ivfpq_search_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist,
                                    int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* Call bitmap: the same searches under a row filter of THIS CALL alone, on a plain and on a residual handle alike.  The statement
+ * is lb_gpu_ivf_search_bitmap_ctx's ("call bitmap" above lb_gpu_ivf_new), word for word where it applies: they take what their
+ * plain counterparts take, and behind nprobe (bitmap, nbits, stride_bytes).  One bit per row POSITION, as the handle filter's mask
+ * is by position, least significant bit first as in an Arrow validity buffer: row r is visible to the call iff
+ * bitmap[r >> 3] >> (r & 7) & 1.  It is read byte by byte: no alignment is owed and no padding beyond ceil(nbits / 8) bytes, and
+ * nothing past bit nbits - 1 is read as a row.  stride_bytes 0: one bitmap serves every query of the call; otherwise query q reads
+ * bitmap + q * stride_bytes, and stride_bytes >= ceil(nbits / 8).  The result is the handle's exact k-NN (ADC on a plain handle,
+ * ADC under the table of each probed list on a residual one) among the rows of the probed lists that are live, pass the handle's
+ * filter if one is set AND have their bit set; order, labels (the ids where an add gave them), padding and distances as stated
+ * above.  It is bit for bit what the same handle answers after set_filter (combined with its own filter) with the mask
+ * bit(r) != 0, and last_search_stats agrees in all four values.  The probes do not change, and on a residual handle the table of a
+ * probed list is that of the list probed, whatever the bitmap hides.  The handle is not changed and is held shared, like any
+ * search: calls with different bitmaps run concurrently, and nvisible, the handle's filter and every later call are untouched.  A
+ * NULL bitmap is the plain search through the plain path with no launch added, and so is an empty handle; nbits and stride_bytes
+ * are then ignored.  A non-NULL bitmap with nbits != ntotal (the n != ntotal rule of set_filter), nbits < 0, a negative stride or
+ * a stride in (0, ceil(nbits / 8)) is LB_ERR_INVALID_ARG with the numbers in last_error, answered under the reader lock before any
+ * launch and with nothing written; the plain entry points' checks and their order come first.  A NULL handle is
+ * LB_ERR_INVALID_ARG before a device is touched.  On the device the probed lists are compacted under the bitmap into lists of the
+ * call's own, which hold POSITIONS into the list-major codes (over the handle's visible lists when it has a filter or removed
+ * rows: the bit is then looked up by the row at that position), and the plan, the scan and the selection walk those.  Under one
+ * bitmap (stride 0), when the call's queries times their largest probed lists exceed the handle's rows, every list is compacted
+ * once for the call and not once per query and probe; the result does not depend on which form ran.  ctx is polled before these
+ * launches as before every other; under profiling they fall into ms[1], in the second form into the first batch's. */
+int lb_gpu_ivfpq_search_bitmap_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap,
+                                   int64_t nbits, int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_ivfpq_search_bitmap_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                          int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
+                                          const lb_cancel *ctx);
 /* the row filter, as lb_gpu_ivf_set_filter / _filter_int64 / _filter_float32 / _nvisible */
 int lb_gpu_ivfpq_set_filter(lb_gpu_ivfpq *p, const uint8_t *mask, int64_t n);
 int lb_gpu_ivfpq_filter_int64(lb_gpu_ivfpq *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
@@ -1189,6 +1222,24 @@ int lb_gpu_ivfsq8_search_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries,
                              const lb_cancel *ctx);
 int lb_gpu_ivfsq8_search_device_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist,
                                     int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* Call bitmap: the same searches under a row filter of THIS CALL alone.  The statement is lb_gpu_ivf_search_bitmap_ctx's ("call
+ * bitmap" above lb_gpu_ivf_new) and lb_gpu_ivfpq_search_bitmap_ctx's, word for word where it applies: (bitmap, nbits,
+ * stride_bytes) behind nprobe, one bit per row POSITION, least significant bit first, read byte by byte at any address;
+ * stride_bytes 0 is one bitmap for every query, otherwise query q reads bitmap + q * stride_bytes and stride_bytes >=
+ * ceil(nbits / 8).  The result is the exact integer k-NN (ascending keys (S << 32) | row, reported as float32(S)) among the rows
+ * of the probed lists that are live, pass the handle's filter if one is set AND have their bit set, bit for bit what the same
+ * handle answers after set_filter (combined with its own filter) with the mask bit(r) != 0, labels (ids), distances and all four
+ * last_search_stats included.  The handle is not changed and is held shared: calls with different bitmaps run concurrently.  A
+ * NULL bitmap is the plain search with no launch added, and so is an empty handle.  nbits != ntotal, nbits < 0, a negative stride
+ * or a stride in (0, ceil(nbits / 8)) is LB_ERR_INVALID_ARG with the numbers in last_error, under the reader lock, before any
+ * launch, nothing written, behind the plain entry points' own checks; a NULL handle is LB_ERR_INVALID_ARG before a device is
+ * touched.  The lists of this handle hold rows and its scan gathers by row, so the compaction is the IVF-Flat handle's, in either
+ * of its two forms (per probe slot, or every list once under one bitmap); under profiling it falls into ms[1]. */
+int lb_gpu_ivfsq8_search_bitmap_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap,
+                                    int64_t nbits, int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_ivfsq8_search_bitmap_device_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                           int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
+                                           const lb_cancel *ctx);
 /* the row filter, as lb_gpu_ivf_set_filter / _filter_int64 / _filter_float32 / _nvisible */
 int lb_gpu_ivfsq8_set_filter(lb_gpu_ivfsq8 *p, const uint8_t *mask, int64_t n);
 int lb_gpu_ivfsq8_filter_int64(lb_gpu_ivfsq8 *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,

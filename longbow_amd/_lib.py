@@ -276,6 +276,8 @@ SIGNATURES = [
     ("lb_gpu_ivfpq_search", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     ("lb_gpu_ivfpq_search_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
     ("lb_gpu_ivfpq_search_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq_search_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq_search_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_ivfpq_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivfpq_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_ivfpq_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
@@ -309,6 +311,8 @@ SIGNATURES = [
     ("lb_gpu_ivfsq8_search", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     ("lb_gpu_ivfsq8_search_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
     ("lb_gpu_ivfsq8_search_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivfsq8_search_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_ivfsq8_search_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_ivfsq8_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivfsq8_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_ivfsq8_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),

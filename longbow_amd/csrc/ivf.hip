@@ -187,44 +187,7 @@ int ivf_search_i8_dev(lb_gpu_ivf *p, int64_t nq, const int8_t *d_q8, int k, int 
 }
 
 // ---- a row bitmap given with the call ----------------------------------------------------------------------------------------
-// The bitmap as an entry point got it: host or device memory, one bit per row position, least significant bit first.
-struct CallBitmap {
-    const uint8_t *bits;
-    int64_t nbits, stride;
-    bool on_device;
-};
-
-// The call's filter from its bitmap, under the reader lock and before anything is launched: the refusals (set_filter's n != ntotal
-// rule, and the stride), then a host bitmap's bytes go into `lease` (the caller's, declared outside its guard) ahead of the
-// search on s.  A NULL bitmap is no filter: the plain search.
-int call_filter(lb_gpu_ivf *p, int64_t nq, const CallBitmap &b, Lease &lease, hipStream_t s, IvfCallFilter &f)
-{
-    f = IvfCallFilter{};
-    if (!b.bits) return LB_OK;
-    if (b.nbits < 0 || b.nbits != p->n) {
-        p->set_error("a bitmap of %lld bits for %lld rows", (long long)b.nbits, (long long)p->n);
-        return LB_ERR_INVALID_ARG;
-    }
-    const int64_t bytes = (b.nbits + 7) / 8;
-    if (b.stride < 0 || (b.stride > 0 && b.stride < bytes)) {
-        p->set_error("bitmap stride %lld: 0 (one bitmap for every query) or at least the %lld bytes of %lld bits", (long long)b.stride,
-                     (long long)bytes, (long long)b.nbits);
-        return LB_ERR_INVALID_ARG;
-    }
-    if (bytes == 0) return LB_OK; // (an empty handle: all padding with or without it)
-    f.d_bits = b.bits;
-    if (!b.on_device) {
-        const size_t total = (size_t)(b.stride > 0 ? (nq - 1) * b.stride : 0) + (size_t)bytes;
-        lease.reset(p->device, total);
-        LB_HIP(hipMemcpyAsync(lease.p, b.bits, total, hipMemcpyHostToDevice, s));
-        f.d_bits = lease.as<uint8_t>();
-    }
-    f.stride = b.stride;
-    f.nbits = b.nbits;
-    f.on = true;
-    return LB_OK;
-}
-
+// CallBitmap and call_filter are lb_ivf_host.h's: the refusals and the host bitmap's copy, shared with the code handles.
 int ivf_search_bitmap_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
                           const lb_cancel *ctx, Lease &sc, const CallBitmap &b, Lease &bits)
 {

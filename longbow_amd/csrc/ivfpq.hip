@@ -121,8 +121,12 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
 // once.  Timing: slot 3 is the first round's residual queries and tables, slot 4 its scan and every further round whole.
 constexpr int64_t kTableLaunch = 65535; // pairs a launch_build_adc_table call takes: its queries are on grid.y
 
+// Under a call's bitmap (filter.on) the batch's lists and probes are the call's synthetic ones, whose entries are positions: the
+// scan takes its `_visible` form over them whether or not the handle has a filter, bounded by the entries of the call's row array,
+// and the residual queries are built from a copy of the batch whose lists and probes are the handle's and the coarse search's
+// (real_probes: where the batch pointed at layout time, the same buffer every batch), since a table belongs to the list probed.
 int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfBatch &a, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels,
-                      hipStream_t s, const lb_cancel *ctx, Lease &sc)
+                      hipStream_t s, const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter)
 {
     const IvfPartition &P = p->part;
     const uint8_t *lcodes = p->d_lcodes[P.cur].get();
@@ -130,9 +134,12 @@ int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfBatch &a, int64_t nq, const floa
     const IvfpqTablePlan tp = ivfpq_table_plan(np, p->M, kTableScratch);
     float *d_rq = nullptr, *d_tables = nullptr;
     uint32_t *d_items = nullptr; // the scan's work list, where it runs from one (ivfpq_rscan_plan)
+    const int64_t *real_probes = nullptr;
+    const IvfLists own = p->lists();
     return ivf_search(
-        p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
-        [&](Carve &c, IvfBatch &, int64_t nb) {
+        p, p->part, own, p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
+        [&](Carve &c, IvfBatch &b, int64_t nb) {
+            real_probes = b.probes;
             const size_t pairs = (size_t)nb * (size_t)tp.slots; // of a round
             d_rq = c.take<float>(pairs * p->dims * 4);
             d_tables = c.take<float>(pairs * p->M * 256 * 4);
@@ -144,27 +151,34 @@ int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfBatch &a, int64_t nq, const floa
                 const int ns = (int)std::min<int64_t>(tp.slots, np - s0);
                 const int64_t pairs = (int64_t)b.nq * ns;
                 if (s0 > 0 && !poll()) return false;
-                launch_ivfpq_residual_queries(b, s0, ns, p->d_cent.get(), d_rq, s);
+                IvfBatch rb = b;
+                rb.L = own;
+                rb.probes = real_probes;
+                launch_ivfpq_residual_queries(rb, s0, ns, p->d_cent.get(), d_rq, s);
                 for (int64_t p0 = 0; p0 < pairs; p0 += kTableLaunch) {
                     if (!poll()) return false;
                     launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, d_rq + (size_t)p0 * p->dims,
                                            (int)std::min(kTableLaunch, pairs - p0), d_tables + (size_t)p0 * p->M * 256, s);
                 }
                 if (s0 == 0 ? !next() : !poll()) return false;
-                if (p->filter.on)
+                if (filter.on)
+                    launch_ivfpq_rscan_visible(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, P.d_list[P.cur].get(), filter.call_rows, s);
+                else if (p->filter.on)
                     launch_ivfpq_rscan_visible(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, P.d_list[P.cur].get(),
                                                p->filter.n_visible, s);
                 else launch_ivfpq_rscan(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, s);
             }
             return true;
         },
-        tp.nb);
+        tp.nb, launch_ivf_select, filter);
 }
 
 // The handle's call of the search loop (lb_ivf_host.h): exact ADC k-NN; under a filter it walks the visible lists.  Its middle steps
 // are the queries' tables, a timing slot of their own, and the scan of the list-major codes.
+// filter: the call's own row bitmap (the *_bitmap entry points): the scan then takes its `_visible` form over the call's lists of
+// positions, as above.
 int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                     const lb_cancel *ctx, Lease &sc)
+                     const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter = IvfCallFilter{})
 {
     if (const int st = ivf_live_ok(p)) return st;
     const IvfPartition &P = p->part;
@@ -173,7 +187,7 @@ int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int n
     a.D = p->dims;
     const uint8_t *lcodes = p->d_lcodes[P.cur].get();
     float *d_tables = nullptr;
-    if (p->residual) return ivfpq_rsearch_dev(p, a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc);
+    if (p->residual) return ivfpq_rsearch_dev(p, a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, filter);
     return ivf_search(
         p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
         [&](Carve &c, IvfBatch &, int64_t nb) { d_tables = c.take<float>((size_t)nb * p->M * 256 * 4); },
@@ -181,10 +195,21 @@ int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int n
             if (!next()) return false; // (the plan's slot ends here)
             launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, b.Q, b.nq, d_tables, s);
             if (!next()) return false;
-            if (p->filter.on) launch_ivfpq_scan_visible(b, d_tables, p->M, lcodes, p->n, P.d_list[P.cur].get(), p->filter.n_visible, s);
+            if (filter.on) launch_ivfpq_scan_visible(b, d_tables, p->M, lcodes, p->n, P.d_list[P.cur].get(), filter.call_rows, s);
+            else if (p->filter.on) launch_ivfpq_scan_visible(b, d_tables, p->M, lcodes, p->n, P.d_list[P.cur].get(), p->filter.n_visible, s);
             else launch_ivfpq_scan(b, d_tables, p->M, lcodes, p->n, s);
             return true;
-        });
+        },
+        kQueryBatch, launch_ivf_select, filter);
+}
+
+// the search under a row bitmap given with the call: lb_ivf_host.h's refusals and copy, then the search above
+int ivfpq_search_bitmap_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
+                            const lb_cancel *ctx, Lease &sc, const CallBitmap &b, Lease &bits)
+{
+    IvfCallFilter f;
+    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
+    return ivfpq_search_dev(p, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, f);
 }
 
 // both constructors: the same arguments, limits, order of checks and status codes
@@ -307,16 +332,32 @@ int lb_gpu_ivfpq_assignments(lb_gpu_ivfpq *p, int64_t row0, int64_t n, int32_t *
 int lb_gpu_ivfpq_search_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                    void *stream, const lb_cancel *ctx)
 {
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivfpq_search_dev);
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, [](auto &&...args) { return ivfpq_search_dev(args...); });
 }
 int lb_gpu_ivfpq_search_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                             const lb_cancel *ctx)
 {
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivfpq_search_dev);
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [](auto &&...args) { return ivfpq_search_dev(args...); });
 }
 int lb_gpu_ivfpq_search(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
     return lb_gpu_ivfpq_search_ctx(p, nq, queries, k, nprobe, dist, labels, nullptr);
+}
+// the same searches under a row bitmap given with the call (a NULL bitmap: the plain search), plain and residual handles alike
+int lb_gpu_ivfpq_search_bitmap_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                          int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    Lease bits;
+    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
+                                 [&](auto &&...args) { return ivfpq_search_bitmap_dev(args..., b, bits); });
+}
+int lb_gpu_ivfpq_search_bitmap_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
+                                   int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    Lease bits;
+    const CallBitmap b{bitmap, nbits, stride_bytes, false};
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivfpq_search_bitmap_dev(args..., b, bits); });
 }
 int lb_gpu_ivfpq_last_search_stats(lb_gpu_ivfpq *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
 int lb_gpu_ivfpq_set_profiling(lb_gpu_ivfpq *p, int enable) { return ivf_set_profiling(p, enable); }

@@ -99,8 +99,10 @@ int add_impl(lb_gpu_ivfsq8 *p, int64_t n, const float *vectors, const int64_t *i
 // The handle's call of the search loop (lb_ivf_host.h): exact integer k-NN; under a filter it walks the visible lists.  Its middle
 // steps are the queries' codes and their norms, a timing slot of their own, and the scan of the probed lists' rows; the selection
 // is the one over integer keys.
+// filter: the call's own row bitmap (the *_bitmap entry points).  The lists hold rows and the scan gathers by row, so the call's
+// lists go through the search loop as the IVF-Flat handle's do and nothing here changes with them.
 int ivfsq8_search_dev(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                      const lb_cancel *ctx, Lease &sc)
+                      const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter = IvfCallFilter{})
 {
     if (const int st = ivf_live_ok(p)) return st;
     IvfBatch a{};
@@ -123,7 +125,16 @@ int ivfsq8_search_dev(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_Q, int k, int
             launch_ivfsq8_scan(IvfSq8Scan{b, p->d_codes.get(), p->n, p->stride, d_qc, d_qn}, maxlen, s);
             return true;
         },
-        kQueryBatch, launch_ivfsq8_select);
+        kQueryBatch, launch_ivfsq8_select, filter);
+}
+
+// the search under a row bitmap given with the call: lb_ivf_host.h's refusals and copy, then the search above
+int ivfsq8_search_bitmap_dev(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
+                             const lb_cancel *ctx, Lease &sc, const CallBitmap &b, Lease &bits)
+{
+    IvfCallFilter f;
+    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
+    return ivfsq8_search_dev(p, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, f);
 }
 
 } // namespace
@@ -247,16 +258,32 @@ int lb_gpu_ivfsq8_assignments(lb_gpu_ivfsq8 *p, int64_t row0, int64_t n, int32_t
 int lb_gpu_ivfsq8_search_device_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                     void *stream, const lb_cancel *ctx)
 {
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivfsq8_search_dev);
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, [](auto &&...args) { return ivfsq8_search_dev(args...); });
 }
 int lb_gpu_ivfsq8_search_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                              const lb_cancel *ctx)
 {
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivfsq8_search_dev);
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [](auto &&...args) { return ivfsq8_search_dev(args...); });
 }
 int lb_gpu_ivfsq8_search(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
     return lb_gpu_ivfsq8_search_ctx(p, nq, queries, k, nprobe, dist, labels, nullptr);
+}
+// the same searches under a row bitmap given with the call (a NULL bitmap: the plain search)
+int lb_gpu_ivfsq8_search_bitmap_device_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                           int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    Lease bits;
+    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
+                                 [&](auto &&...args) { return ivfsq8_search_bitmap_dev(args..., b, bits); });
+}
+int lb_gpu_ivfsq8_search_bitmap_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
+                                    int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    Lease bits;
+    const CallBitmap b{bitmap, nbits, stride_bytes, false};
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivfsq8_search_bitmap_dev(args..., b, bits); });
 }
 int lb_gpu_ivfsq8_last_search_stats(lb_gpu_ivfsq8 *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
 int lb_gpu_ivfsq8_set_profiling(lb_gpu_ivfsq8 *p, int enable) { return ivf_set_profiling(p, enable); }

@@ -62,8 +62,16 @@ hipError_t launch_ivf_visible(const uint8_t *mask, const IvfLists &L, int64_t n,
 //                          starts at q pmax + the sizes of the lists probed in the slots before p; list 2 (q np + p) + 1 is the
 //                          gap up to the next start and is never probed.  Monotone, soff[2 nq np] = nq pmax
 //   sprobes [nq][np]       2 (q np + p)
-//   srows   [nq][pmax]     the rows of the synthetic lists
+//   srows   [nq][pmax]     the entries of the synthetic lists
 // pmax: at least the rows of any np distinct lists of L, and nq pmax < 2^32.  An invalid probe gives an empty list.
+// What an entry of L.rows is, and with it what a synthetic list holds and which row's bit decides (`mode`):
+//   IVF_CALL_ROWS          a row: stored as it is, and its own bit is looked up (IVF-Flat, IVF-SQ8: their scans gather by row)
+//   IVF_CALL_POS_ALL       L is the lists of ALL rows of a handle whose scans read list-major codes by position (IVF-PQ): entry
+//                          `at` is the row at position `at`; the position is stored, the bit is that of L.rows[at]
+//   IVF_CALL_POS_VISIBLE   L is the visible lists of such a handle, whose entries are positions: the position is stored, the bit
+//                          is that of rowof[pos], rowof being the rows of the lists of all rows; pos < rowof_len before it indexes
+// In the two position modes the scans take their `_visible` forms over the synthetic lists, with rows = rowof.
+enum { IVF_CALL_ROWS = 0, IVF_CALL_POS_ALL = 1, IVF_CALL_POS_VISIBLE = 2 };
 struct IvfCallLists {
     IvfLists L;            // the handle's lists: the visible ones under a handle filter or removals
     uint32_t rows_len;     // entries of L.rows that may be read: at least L.off[L.nlist]
@@ -75,11 +83,18 @@ struct IvfCallLists {
     uint32_t *soff;
     int64_t *sprobes;
     uint32_t *srows;
+    int mode;              // IVF_CALL_*
+    const uint32_t *rowof; // [rowof_len] IVF_CALL_POS_VISIBLE: position -> row; else unused
+    uint32_t rowof_len;
     IvfLists lists() const { return IvfLists{soff, srows, 2 * nq * np}; }
 };
 constexpr int IVF_CALL_STEP_ROWS = 2048; // list positions a workgroup of the compaction takes per step
 // two launches: the starts and the synthetic probes (a wave per query), then the compaction (a workgroup per probe slot)
 void launch_ivf_call_lists(const IvfCallLists &a, hipStream_t s);
+// One compaction for a whole call under ONE bitmap: launch_ivf_call_lists over a single pseudo-query that probes every list in
+// order (probes = launch_ivf_all_probes(., 1, nlist), pmax = the rows of all lists) leaves list l of L as synthetic list 2 l.
+// Every batch then only renames its probes: out[i] = 2 probes[i] for a probe in [0, nlist), else -1 (no list of either numbering)
+void launch_ivf_call_shared_probes(const int64_t *probes, int64_t count, int nlist, int64_t *out, hipStream_t s);
 
 // Coarse-quantiser training (kernels_ivf_train.hip; host side ivf_train.hip).  st.M == 1, st.sub == st.D, st.K <= IVF_MAX_NLIST.
 // E-step: st.assign[row] = the first strict minimum of simd.L2Squared over st.cent (-1 and *st.bad: none below FLT_MAX),

@@ -572,11 +572,69 @@ template <class Rows, class Relist> int ivf_compact(IvfHandle *p, Rows &&rows, s
 // behind the probes of each batch launch_ivf_call_lists compacts the probed lists of L under the bitmap; the plan, the middle
 // steps and the selection are handed those lists and probes in place of L and the coarse search's.  Its launches fall into the
 // plan's timing slot, the host keeps sizing by `sizes`, and nothing comes back to it in between.
+// The shared form: under ONE bitmap (stride 0), when the call's nq * pmax exceeds the rows of all lists of L, the per-slot form
+// would walk more list positions than L holds.  Then every list of L is compacted once, in the first batch behind its probes (the
+// plan's slot of that batch): launch_ivf_call_lists over one pseudo-query that probes lists 0 .. nlist - 1, pmax being the rows of
+// all lists, which leaves list l as synthetic list 2 l; each batch only renames its probes (launch_ivf_call_shared_probes).  The
+// rule is the host's, from numbers it has; the synthetic list of a probe holds the same entries in the same order in both forms,
+// so the result does not depend on which ran.  extra() and a handle's middle steps still find the coarse search's probes where
+// the batch pointed at layout time (the residual IVF-PQ handle subtracts the centroid of the list probed).
+// mode, rowof, rowof_len: what the entries of L are (lb_ivf.h, IVF_CALL_*), filled by call_filter from the handle.
+// call_rows: set by ivf_search before each batch's middle steps to the entries of the synthetic lists' row array, for a handle
+// whose scan bounds a list entry by it (the `_visible` scans of IVF-PQ: nvis).
 struct IvfCallFilter {
     const uint8_t *d_bits = nullptr; // device memory; query q of the call reads d_bits + q stride
     int64_t stride = 0, nbits = 0;
     bool on = false;
+    int mode = IVF_CALL_ROWS;
+    const uint32_t *rowof = nullptr;
+    uint32_t rowof_len = 0;
+    mutable int64_t call_rows = 0;
 };
+
+// The bitmap as an entry point got it: host or device memory, one bit per row position, least significant bit first.
+struct CallBitmap {
+    const uint8_t *bits;
+    int64_t nbits, stride;
+    bool on_device;
+};
+
+// The call's filter from its bitmap, under the reader lock and before anything is launched: the refusals (set_filter's n != ntotal
+// rule, and the stride), then a host bitmap's bytes go into `lease` (the caller's, declared outside its guard) ahead of the
+// search on s.  A NULL bitmap is no filter: the plain search.
+inline int call_filter(IvfHandle *p, int64_t nq, const CallBitmap &b, Lease &lease, hipStream_t s, IvfCallFilter &f)
+{
+    f = IvfCallFilter{};
+    if (!b.bits) return LB_OK;
+    if (b.nbits < 0 || b.nbits != p->n) {
+        p->set_error("a bitmap of %lld bits for %lld rows", (long long)b.nbits, (long long)p->n);
+        return LB_ERR_INVALID_ARG;
+    }
+    const int64_t bytes = (b.nbits + 7) / 8;
+    if (b.stride < 0 || (b.stride > 0 && b.stride < bytes)) {
+        p->set_error("bitmap stride %lld: 0 (one bitmap for every query) or at least the %lld bytes of %lld bits", (long long)b.stride,
+                     (long long)bytes, (long long)b.nbits);
+        return LB_ERR_INVALID_ARG;
+    }
+    if (bytes == 0) return LB_OK; // (an empty handle: all padding with or without it)
+    f.d_bits = b.bits;
+    if (!b.on_device) {
+        const size_t total = (size_t)(b.stride > 0 ? (nq - 1) * b.stride : 0) + (size_t)bytes;
+        lease.reset(p->device, total);
+        LB_HIP(hipMemcpyAsync(lease.p, b.bits, total, hipMemcpyHostToDevice, s));
+        f.d_bits = lease.as<uint8_t>();
+    }
+    f.stride = b.stride;
+    f.nbits = b.nbits;
+    f.on = true;
+    if (p->positions) { // the lists of all rows hold rows, the visible ones positions into them (IvfHandle)
+        f.mode = p->filter.on ? IVF_CALL_POS_VISIBLE : IVF_CALL_POS_ALL;
+        f.rowof = p->part.d_list[p->part.cur].get();
+        f.rowof_len = (uint32_t)p->n;
+    }
+    return LB_OK;
+}
+
 using IvfSelectFn = void (*)(const IvfBatch &, int, const int64_t *, float *, int64_t *, hipStream_t);
 template <class Extra, class Middle>
 int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vector<int64_t> &sizes, IvfBatch a, int64_t nq, const float *d_Q,
@@ -612,12 +670,24 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
     float *d_pdist = nullptr;
     unsigned long long *d_stats = nullptr;
     IvfCallLists cl{};
+    // the shared form's rule, and the rows of all lists of L (at least 1: the pseudo-query's pmax)
+    int64_t all_rows = 0;
+    for (const int64_t v : sizes) all_rows += v;
+    const bool shared = filter.on && filter.stride == 0 && nq * pmax > all_rows;
+    all_rows = std::max<int64_t>(all_rows, 1);
+    int64_t *d_ident = nullptr, *d_probes2 = nullptr; // shared: the pseudo-query's probes; a batch's renamed probes
     auto layout = [&](Carve c) {
         a.probes = d_probes = c.take<int64_t>((size_t)nb * np * 8);
         d_pdist = c.take<float>((size_t)nb * np * 4);
         a.seg = c.take<uint32_t>((size_t)nb * (np + 1) * 4);
         d_stats = c.take<unsigned long long>(4 * 8);
-        if (filter.on) {
+        if (shared) {
+            cl.soff = c.take<uint32_t>(((size_t)P.nlist * 2 + 1) * 4);
+            cl.sprobes = c.take<int64_t>((size_t)P.nlist * 8);
+            d_ident = c.take<int64_t>((size_t)P.nlist * 8);
+            d_probes2 = c.take<int64_t>((size_t)nb * np * 8);
+            cl.srows = c.take<uint32_t>((size_t)all_rows * 4);
+        } else if (filter.on) {
             cl.soff = c.take<uint32_t>(((size_t)nb * np * 2 + 1) * 4);
             cl.sprobes = c.take<int64_t>((size_t)nb * np * 8);
             cl.srows = c.take<uint32_t>((size_t)nb * pmax * 4);
@@ -651,20 +721,39 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
         if (np == P.nlist && np > LB_MAX_K) launch_ivf_all_probes(d_probes, a.nq, np, s);
         else if (const int rc = lb_gpu_index_search_device_ctx(P.coarse, a.nq, a.Q, np, d_pdist, d_probes, s, ctx)) return coarse_fail(h, P, rc, s);
         if (!next()) break;
-        if (filter.on) { // the lists of this batch under the call's bitmap, then everything below walks those
+        if (filter.on) { // the lists under the call's bitmap, then everything below walks those
             cl.L = L;
             cl.rows_len = (uint32_t)h->n; // (both list arrays hold room for every row, all of it written or allocated)
-            cl.probes = d_probes;
-            cl.nq = a.nq;
-            cl.np = np;
-            cl.pmax = pmax;
-            cl.bits = filter.d_bits + (size_t)q0 * filter.stride;
+            cl.mode = filter.mode;
+            cl.rowof = filter.rowof;
+            cl.rowof_len = filter.rowof_len;
             cl.stride = filter.stride;
             cl.nbits = filter.nbits;
             if (!go()) break;
-            launch_ivf_call_lists(cl, s);
+            if (shared) { // every list once, in the first batch; then this batch's probes by the lists' new numbers
+                if (q0 == 0) {
+                    cl.probes = d_ident;
+                    cl.nq = 1;
+                    cl.np = P.nlist;
+                    cl.pmax = all_rows;
+                    cl.bits = filter.d_bits;
+                    launch_ivf_all_probes(d_ident, 1, P.nlist, s);
+                    launch_ivf_call_lists(cl, s);
+                }
+                launch_ivf_call_shared_probes(d_probes, (int64_t)a.nq * np, P.nlist, d_probes2, s);
+                a.probes = d_probes2;
+                filter.call_rows = all_rows;
+            } else { // the probed lists of this batch, slot by slot
+                cl.probes = d_probes;
+                cl.nq = a.nq;
+                cl.np = np;
+                cl.pmax = pmax;
+                cl.bits = filter.d_bits + (size_t)q0 * filter.stride;
+                launch_ivf_call_lists(cl, s);
+                a.probes = cl.sprobes;
+                filter.call_rows = (int64_t)a.nq * pmax;
+            }
             a.L = cl.lists();
-            a.probes = cl.sprobes;
         }
         launch_ivf_plan(a, d_stats, s);
         if (!middle(a, maxlen, go, next)) break;

@@ -7,7 +7,9 @@ include/longbow_gpu.h states the semantics.
 
   IVFSQ8  the handle: bounds and centroids given at creation, add / search / codes / bounds / list_sizes / assignments /
           last_search_stats, the row filter (set_filter / filter_column / nvisible), removal (remove / remove_rows /
-          remove_device / nlive / ndeleted) and compact()
+          remove_device / nlive / ndeleted) and compact().  search(..., bitmap=) and search_device(..., d_bitmap=) take a row
+          filter of that call alone, which leaves the handle as it is
+  pack_bitmap  a byte or bool mask [n] or [nq, n] -> the LSB-first bits such a call takes, and their stride
   train   (centroids, min, max) from ivf.train and sq8.train
 """
 import ctypes as C
@@ -16,7 +18,7 @@ import numpy as np
 
 from . import _lib, ivf, sq8
 from ._ivfbase import IVFBase
-from ._rowfilter import RowFilterMixin
+from ._rowfilter import RowFilterMixin, pack_bitmap  # noqa: F401  (pack_bitmap: exported here as ivfsq8.pack_bitmap)
 
 FLT_MAX = ivf.FLT_MAX
 
@@ -88,28 +90,38 @@ class IVFSQ8(ivf.RemovalMixin, RowFilterMixin, IVFBase):
         self._check(self._lib.lb_gpu_ivfsq8_get_bounds(self._h, mn.ctypes.data, mx.ctypes.data))
         return mn, mx
 
-    def search(self, queries, k, nprobe, ctx=None):
+    def search(self, queries, k, nprobe, ctx=None, bitmap=None, bitmap_stride=0):
         """-> (labels [nq, k], dist [nq, k] = float32(S)): ascending (S, row) of the integers among the rows of the probed lists,
-        padded -1 / FLT_MAX"""
-        return super().search(queries, k, nprobe, ctx)
+        padded -1 / FLT_MAX.  bitmap: a row filter of this call alone (lb_gpu_ivfsq8_search_bitmap_ctx), the LSB-first bits of
+        pack_bitmap over the ntotal row positions; bitmap_stride 0: one bitmap for every query, else query q's bits start at byte
+        q * bitmap_stride.  The handle, its own filter and nvisible() stay as they are; searches with different bitmaps may run
+        concurrently."""
+        return self._search_host("search", self._vectors(queries), k, nprobe, ctx, bitmap, bitmap_stride)
 
-    def search_refine(self, index, queries, k, shortlist, nprobe, order=None):
+    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None, d_bitmap=None, nbits=0, bitmap_stride=0):
+        """d_bitmap: the call's bitmap in device memory, of nbits == ntotal bits (any byte address)"""
+        self._search_dev("search", nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, d_bitmap, nbits, bitmap_stride)
+
+    def search_refine(self, index, queries, k, shortlist, nprobe, order=None, bitmap=None, bitmap_stride=0):
         """The two-stage use the codes exist for, composed as ivfpq.IVFPQ.search_refine: the integer k-NN of `shortlist` rows per
         query among the probed lists, then the exact top k of every shortlist on `index` in one call (gpu.Index.Refine; a
         float32 or float16 gpu.Index filled in the same row order).  -> (labels [nq, k], dist [nq, k]), padded with -1 /
         FLT_MAX.  The shortlist must hold row positions: a handle that was given ids raises ValueError.  A row filter on this
-        handle shapes the shortlist, so the result holds visible rows only; `index` needs no filter.
+        handle shapes the shortlist, so the result holds visible rows only; `index` needs no filter.  bitmap, bitmap_stride: a
+        row filter of this call alone, as search takes it; it goes to the shortlist search, so the refined result holds rows
+        with a set bit only.
         Removed rows never enter the shortlist (it holds live rows only), and `index` treats a position it has removed itself as outside the index.  After compact()
         the positions of this handle are the survivors' new ones: `index` must be compacted over the same removals
         (gpu.Index.Compact is stable too), or the positions no longer correspond."""
         if self._has_ids:
             raise ValueError("search_refine needs row positions: this handle was given ids, which its searches return instead")
         v = self._vectors(queries)
-        short, _ = self.search(v, shortlist, nprobe)
+        short, _ = self.search(v, shortlist, nprobe, bitmap=bitmap, bitmap_stride=bitmap_stride)
         return index.Refine(v, short, k, order)
 
     def last_timing(self):
-        """ms of the last profiled search, summed over its batches: (probes, plan, the queries' codes, scan, selection)"""
+        """ms of the last profiled search, summed over its batches: (probes, plan, the queries' codes, scan, selection).  The
+        compaction of the lists under a call's bitmap falls into the plan's."""
         return super().last_timing()
 
     def last_build_timing(self):
