@@ -15,16 +15,9 @@ enum { DT_F32 = 0, DT_F16 = 1, DT_I8 = 2 }; // simd.DataType, what lb_gpu_ivf_dt
 struct lb_gpu_ivf : IvfHandle { // the partition, and under a row filter the visible lists of rows (lb_ivf_host.h)
     int metric = 0, order = 0;
     int dtype = DT_F32;             // the rows' element type, fixed at creation (lb_gpu_ivf_new, _new_f16, _new_i8)
-    DevBuf<float> d_rows;           // [capacity][dims], insertion order (a float32 handle)
-    DevBuf<uint16_t> d_rows_f16;    // the same of a float16 handle (IEEE binary16), which holds no f32 copy of its rows
-    DevBuf<int8_t> d_rows_i8;       // the same of an int8 handle, which holds no wider copy of its rows either
-    size_t elem_bytes() const { return dtype == DT_I8 ? 1 : dtype == DT_F16 ? 2 : 4; }
-    char *rows() const // the buffer of the handle's element type
-    {
-        return dtype == DT_I8    ? reinterpret_cast<char *>(d_rows_i8.get())
-               : dtype == DT_F16 ? reinterpret_cast<char *>(d_rows_f16.get())
-                                 : reinterpret_cast<char *>(d_rows.get());
-    }
+    DevBuf<uint8_t> d_rows;         // [capacity][dims] of that type (float16: IEEE binary16), insertion order; no wider copy is held
+    size_t row_bytes() const { return (size_t)dims * (dtype == DT_I8 ? 1 : dtype == DT_F16 ? 2 : 4); }
+    template <class E> const E *rows() const { return reinterpret_cast<const E *>(d_rows.get()); }
     float timing[4] = {0, 0, 0, 0};  // of the last profiled search (under err_mu): probes, plan, scan, select; ms summed over its batches
 };
 
@@ -33,32 +26,7 @@ namespace {
 // rows of an add to a float16 or int8 handle that are widened to f32 and assigned at a time: an add never needs an f32 copy of itself
 constexpr int64_t IVF_WIDEN_ASSIGN_ROWS = 65536;
 
-// All or nothing: every new buffer is allocated and filled before the first one replaces an old one.
-void ivf_grow(lb_gpu_ivf *p, int64_t need, bool want_ids)
-{
-    const int64_t cap = ivf_grow_to(p, p->part, need, want_ids, (size_t)p->dims * p->elem_bytes()); // 1.
-    if (cap < 0) return;
-    IvfGrowth g;                                                                       // 2.
-    DevBuf<float> nr;
-    DevBuf<uint16_t> nh;
-    DevBuf<int8_t> nb;
-    g.stage(p, cap, want_ids);
-    if (g.resize) {
-        const size_t elems = (size_t)cap * p->dims;
-        if (p->dtype == DT_I8) nb.alloc(elems);
-        else if (p->dtype == DT_F16) nh.alloc(elems);
-        else nr.alloc(elems);
-        void *to = p->dtype == DT_I8 ? (void *)nb.get() : p->dtype == DT_F16 ? (void *)nh.get() : (void *)nr.get();
-        if (p->n > 0) LB_HIP(hipMemcpy(to, p->rows(), (size_t)p->n * p->dims * p->elem_bytes(), hipMemcpyDeviceToDevice));
-        p->filter.grow(p->n, cap);                                                     // 3. (the last step that can fail)
-    }
-    g.commit(p);                                                                       // 4.
-    if (!g.resize) return;
-    if (p->dtype == DT_I8) p->d_rows_i8 = std::move(nb);
-    else if (p->dtype == DT_F16) p->d_rows_f16 = std::move(nh);
-    else p->d_rows = std::move(nr);
-    p->capacity = cap;
-}
+void ivf_flat_grow(lb_gpu_ivf *p, int64_t need, bool want_ids) { ivf_grow(p, need, want_ids, {{&p->d_rows, p->row_bytes(), false}}); }
 
 // the error a handle reports to an entry point of another element type, as the flat index does (index.hip)
 int wrong_dtype(lb_gpu_ivf *p)
@@ -78,130 +46,66 @@ int query_mismatch(lb_gpu_ivf *p, bool i8)
     return (p->dtype == DT_I8) == i8 ? (int)LB_OK : wrong_dtype(p);
 }
 
-// vectors: n rows of the entry point's element type (DT_F16: uint16_t bit patterns), on the host or on the device
+// The handle's share of the add (lb_ivf_host.h: ivf_add).  vectors: n rows of the entry point's element type (DT_F16: uint16_t bit
+// patterns), on the host or on the device.  They are stored as they come, all of them ahead of the first piece; a float32 handle
+// assigns them in one piece from where they are stored, the others IVF_WIDEN_ASSIGN_ROWS at a time, each piece widened into an
+// f32 scratch that the coarse search reads.  Nothing else is stored and nothing is derived from the new lists.
 int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, bool on_device, int dtype)
 {
     if (!p || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
     if (const int st = dtype_mismatch(p, dtype)) return st;
-    if (n == 0) return LB_OK;
-    std::unique_lock<std::shared_mutex> g(p->mu);
-    IvfPartition &P = p->part;
-    if (const int st = ivf_ids_consistent(p, P, ids)) return st;
-    if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease lab, wide, hist, vis;
-    return guard(p, p->stream, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        hipStream_t s = p->stream;
-        const int64_t total = p->n + n;
-        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        std::vector<int64_t> sizes, vsizes;
-        const bool filtered = p->filter.on;
-        ivf_grow(p, total, ids != nullptr);
-        // 1. the rows
-        const size_t eb = p->elem_bytes();
-        char *d_new = p->rows() + (size_t)p->n * p->dims * eb;
-        LB_HIP(hipMemcpyAsync(d_new, vectors, (size_t)n * p->dims * eb, kind, s));
-        if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, kind, s));
-        // 2. their lists (float16 and int8 rows a piece at a time, each widened into an f32 scratch that the coarse search reads),
-        // 3. the lists of all rows, into the pair not in use
-        if (dtype != DT_F32) {
-            const int64_t piece = std::min(n, IVF_WIDEN_ASSIGN_ROWS);
-            lab.reset(p->device, ivf_assign_bytes(piece));
-            wide.reset(p->device, (size_t)piece * p->dims * 4);
-            for (int64_t r0 = 0; r0 < n; r0 += piece) {
-                const int64_t cnt = std::min(piece, n - r0);
-                (dtype == DT_I8 ? launch_widen_i8 : launch_widen_f16)(d_new + (size_t)r0 * p->dims * eb, wide.as<float>(), cnt * p->dims, s);
-                if (const int rc = ivf_assign(p, P, p->n + r0, cnt, wide.as<float>(), lab, s)) return rc;
-                if (r0 + piece < n) { // (the scratch and the labels are reused by the next piece)
-                    LB_LAUNCH_CHECK();
-                    LB_HIP(hipStreamSynchronize(s));
-                }
-            }
-        } else {
-            lab.reset(p->device, ivf_assign_bytes(n));
-            if (const int rc = ivf_assign(p, P, p->n, n, reinterpret_cast<const float *>(d_new), lab, s)) return rc;
-        }
-        ivf_add_live(p, total, s); // (a handle that has removed rows: the new ones are live)
-        ivf_sort_lists(p, P, total, hist, s);
-        if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
-        const int nxt = 1 - P.cur;
-        // 4. under a filter the new rows are visible: the visible lists of all rows, from the new lists, into the pair not in use
-        //    (the mask bytes behind the stored rows belong to nobody until the commit)
-        const int64_t nvis = filtered ? ivf_add_visible(p, total, vis, vsizes, s) : 0;
-        // 5. commit (nothing below throws)
-        if (filtered) ivf_commit_visible(p, vsizes, nvis);
-        P.h_sizes.swap(sizes);
-        P.cur = nxt;
-        P.has_ids = ids != nullptr;
-        p->n = total;
-        return LB_OK;
-    });
+    Lease wide;
+    const size_t rb = p->row_bytes();
+    return ivf_add(
+        p, n, vectors, ids, on_device, dtype == DT_F32 ? n : IVF_WIDEN_ASSIGN_ROWS,
+        [&](int64_t total, bool want_ids) { ivf_flat_grow(p, total, want_ids); },
+        [&](int64_t r0, int64_t cnt, int64_t piece, hipStream_t s) -> const float * {
+            uint8_t *d_new = p->d_rows.get() + (size_t)p->n * rb;
+            if (r0 == 0) LB_HIP(hipMemcpyAsync(d_new, vectors, (size_t)n * rb, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+            if (dtype == DT_F32) return reinterpret_cast<const float *>(d_new);
+            if (r0 == 0) wide.reset(p->device, (size_t)piece * p->dims * 4);
+            (dtype == DT_I8 ? launch_widen_i8 : launch_widen_f16)(d_new + (size_t)r0 * rb, wide.as<float>(), cnt * p->dims, s);
+            return wide.as<float>();
+        },
+        ivf_no_store, ivf_no_relist);
 }
 
-// The handle's call of the search loop (lb_ivf_host.h): under a filter it walks the visible lists; its middle steps are the
-// queries' norms under cosine, inside the plan's timing slot, and the scan of the rows.  d_q8: on an int8 handle the call's int8
-// queries, d_Q being those widened to f32; the scan reads the int8 ones, a batch's at the offset of its b.Q in d_Q.
-// filter: the call's own row bitmap (the *_bitmap entry points), compacted per batch over the lists walked here, so that it is
-// ANDed with the handle's filter and with liveness.
-int ivf_search_rows(lb_gpu_ivf *p, int64_t nq, const float *d_Q, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels,
-                    hipStream_t s, const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter = IvfCallFilter{})
+// The handle's call of the search loop (lb_ivf_host.h): its middle steps are the queries' norms under cosine, inside the plan's
+// timing slot, and the scan of the rows.  d_q8: on an int8 handle the call's int8 queries, c.queries being those widened to f32;
+// the scan reads the int8 ones, a batch's at the offset of its b.Q in c.queries.
+int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const int8_t *d_q8)
 {
-    if (const int st = ivf_live_ok(p)) return st;
-    IvfBatch a{};
-    a.X = p->dtype == DT_F32 ? p->d_rows.get() : nullptr; // (the plan and the selection read no rows)
-    a.D = p->dims;
     float *d_qna = nullptr;
     return ivf_search(
-        p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 4,
-        [&](Carve &c, IvfBatch &b, int64_t nb) { b.qna = d_qna = c.take<float>((size_t)nb * 4); },
-        [&](const IvfBatch &b, int64_t maxlen, auto &&poll, auto &&next) {
+        p, c, IvfSearchForm{p->timing, 4},
+        [&](Carve &cv, IvfBatch &b, int64_t nb) {
+            b.X = p->dtype == DT_F32 ? p->rows<float>() : nullptr; // (the plan and the selection read no rows)
+            b.qna = d_qna = cv.take<float>((size_t)nb * 4);
+        },
+        [&](const IvfBatch &b, const IvfWalk &w, auto &&poll, auto &&next) {
             if (p->metric == METRIC_COS) {
                 if (!poll()) return false;
-                launch_query_norms(p->order, b.Q, nullptr, b.nq, p->dims, d_qna, s);
+                launch_query_norms(p->order, b.Q, nullptr, b.nq, p->dims, d_qna, c.s);
             }
             if (!next()) return false;
-            if (p->dtype == DT_I8) launch_ivf_scan_i8(p->metric, IvfI8Scan{b, p->d_rows_i8.get(), d_q8 + (b.Q - d_Q)}, maxlen, s);
-            else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, reinterpret_cast<const _Float16 *>(p->d_rows_f16.get())}, maxlen, s);
-            else launch_ivf_scan(p->metric, p->order, b, maxlen, s);
+            if (p->dtype == DT_I8) launch_ivf_scan_i8(p->metric, IvfI8Scan{b, p->rows<int8_t>(), d_q8 + (b.Q - c.queries)}, w.maxlen, c.s);
+            else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, p->rows<_Float16>()}, w.maxlen, c.s);
+            else launch_ivf_scan(p->metric, p->order, b, w.maxlen, c.s);
             return true;
-        },
-        kQueryBatch, launch_ivf_select, filter);
+        });
 }
 
 // A float32 or float16 handle's search of f32 queries
-int ivf_search_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                   const lb_cancel *ctx, Lease &sc)
-{
-    return ivf_search_rows(p, nq, d_Q, nullptr, k, nprobe, d_dist, d_labels, s, ctx, sc);
-}
+int ivf_search_dev(lb_gpu_ivf *p, const IvfCall &c) { return ivf_search_rows(p, c, nullptr); }
 
 // An int8 handle's: the call's int8 queries are widened once into `wide` (the caller's lease, declared outside its guard), which
 // is what the coarse index probes with; ctx is polled before that launch as before every other.
-int ivf_search_i8_dev(lb_gpu_ivf *p, int64_t nq, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                      const lb_cancel *ctx, Lease &sc, Lease &wide, const IvfCallFilter &filter = IvfCallFilter{})
+int ivf_search_i8_dev(lb_gpu_ivf *p, const IvfCallOf<int8_t> &c, Lease &wide)
 {
-    wide.reset(p->device, (size_t)nq * p->dims * 4);
-    if (const int st = ctx_state(ctx)) return ctx_fail(p, st);
-    launch_widen_i8(d_q8, wide.as<float>(), nq * p->dims, s);
-    return ivf_search_rows(p, nq, wide.as<float>(), d_q8, k, nprobe, d_dist, d_labels, s, ctx, sc, filter);
-}
-
-// ---- a row bitmap given with the call ----------------------------------------------------------------------------------------
-// CallBitmap and call_filter are lb_ivf_host.h's: the refusals and the host bitmap's copy, shared with the code handles.
-int ivf_search_bitmap_dev(lb_gpu_ivf *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                          const lb_cancel *ctx, Lease &sc, const CallBitmap &b, Lease &bits)
-{
-    IvfCallFilter f;
-    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
-    return ivf_search_rows(p, nq, d_Q, nullptr, k, nprobe, d_dist, d_labels, s, ctx, sc, f);
-}
-
-int ivf_search_i8_bitmap_dev(lb_gpu_ivf *p, int64_t nq, const int8_t *d_q8, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                             const lb_cancel *ctx, Lease &sc, Lease &wide, const CallBitmap &b, Lease &bits)
-{
-    IvfCallFilter f;
-    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
-    return ivf_search_i8_dev(p, nq, d_q8, k, nprobe, d_dist, d_labels, s, ctx, sc, wide, f);
+    wide.reset(p->device, (size_t)c.nq * p->dims * 4);
+    if (const int st = ctx_state(c.ctx)) return ctx_fail(p, st);
+    launch_widen_i8(c.queries, wide.as<float>(), c.nq * p->dims, c.s);
+    return ivf_search_rows(p, IvfCall{c.nq, wide.as<float>(), c.k, c.nprobe, c.dist, c.labels, c.s, c.ctx, c.sc, c.filter}, c.queries);
 }
 
 } // namespace
@@ -248,12 +152,12 @@ int64_t lb_gpu_ivf_hbm_bytes(const lb_gpu_ivf *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivf *>(p)->mu);
-    return (int64_t)(p->d_rows.count() * 4 + p->d_rows_f16.count() * 2 + p->d_rows_i8.count()) + p->visible_bytes() + p->part.hbm_bytes();
+    return (int64_t)p->d_rows.count() + p->visible_bytes() + p->part.hbm_bytes();
 }
 
 int lb_gpu_ivf_reserve(lb_gpu_ivf *p, int64_t n_total)
 {
-    return handle_reserve(p, n_total, [](lb_gpu_ivf *h, int64_t need) { ivf_grow(h, need, h->part.has_ids); });
+    return handle_reserve(p, n_total, [](lb_gpu_ivf *h, int64_t need) { ivf_flat_grow(h, need, h->part.has_ids); });
 }
 
 // ---- the row filter (lb_handle.h) ---------------------------------------------------------------------------------------
@@ -280,11 +184,11 @@ int lb_gpu_ivf_remove_device(lb_gpu_ivf *p, int64_t n, const int64_t *d_labels, 
 int lb_gpu_ivf_remove_rows(lb_gpu_ivf *p, int64_t n, const int64_t *rows, int64_t *n_removed) { return ivf_remove_rows(p, n, rows, n_removed); }
 int64_t lb_gpu_ivf_nlive(const lb_gpu_ivf *p) { return ivf_nlive(p); }
 int64_t lb_gpu_ivf_ndeleted(const lb_gpu_ivf *p) { return ivf_ndeleted(p); }
-// (the rows of the handle's element type move as bytes; rows() is read under the lock that ivf_compact takes: through the getter)
+// (the rows of the handle's element type move as bytes; the buffer is read under the lock that ivf_compact takes: through the getter)
 int lb_gpu_ivf_compact(lb_gpu_ivf *p, int64_t *old_rows, int64_t cap)
 {
     if (!p) return LB_ERR_INVALID_ARG;
-    return ivf_compact(p, [p] { return static_cast<void *>(p->rows()); }, (size_t)p->dims * p->elem_bytes(), old_rows, cap, ivf_no_relist);
+    return ivf_compact(p, [p] { return static_cast<void *>(p->d_rows.get()); }, p->row_bytes(), old_rows, cap, ivf_no_relist);
 }
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
@@ -303,75 +207,82 @@ int lb_gpu_ivf_add_i8_device(lb_gpu_ivf *p, int64_t n, const int8_t *d_vectors, 
 int lb_gpu_ivf_get_centroids(lb_gpu_ivf *p, float *out) { return ivf_get_centroids(p, out); }
 int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes) { return ivf_list_sizes(p, sizes); }
 int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *lists) { return ivf_assignments(p, row0, n, lists); }
+// the searches, plain and under a row bitmap given with the call: one pair of bodies, a plain search being the one without a bitmap
+static int search_device(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels, void *stream,
+                         const lb_cancel *ctx, const CallBitmap &b)
+{
+    if (const int st = query_mismatch(p, false)) return st;
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivf_search_dev, b);
+}
+static int search_host(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx,
+                       const CallBitmap &b)
+{
+    if (const int st = query_mismatch(p, false)) return st;
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivf_search_dev, b);
+}
+// the int8 handle's: int8 queries, widened once for the coarse index
+static int search_i8_device(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels, void *stream,
+                            const lb_cancel *ctx, const CallBitmap &b)
+{
+    if (const int st = query_mismatch(p, true)) return st;
+    Lease wide;
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
+                                 [&](lb_gpu_ivf *h, const IvfCallOf<int8_t> &c) { return ivf_search_i8_dev(h, c, wide); }, b);
+}
+static int search_i8_host(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx,
+                          const CallBitmap &b)
+{
+    if (const int st = query_mismatch(p, true)) return st;
+    Lease wide;
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx,
+                          [&](lb_gpu_ivf *h, const IvfCallOf<int8_t> &c) { return ivf_search_i8_dev(h, c, wide); }, b);
+}
 int lb_gpu_ivf_search_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                  void *stream, const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, false)) return st;
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivf_search_dev);
+    return search_device(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, CallBitmap{});
 }
 int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, false)) return st;
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivf_search_dev);
+    return search_host(p, nq, queries, k, nprobe, dist, labels, ctx, CallBitmap{});
 }
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
     return lb_gpu_ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, nullptr);
 }
-// the int8 handle's searches: int8 queries, widened once for the coarse index
 int lb_gpu_ivf_search_i8_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                     void *stream, const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, true)) return st;
-    Lease wide;
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, [&](auto &&...args) { return ivf_search_i8_dev(args..., wide); });
+    return search_i8_device(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, CallBitmap{});
 }
 int lb_gpu_ivf_search_i8_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, true)) return st;
-    Lease wide;
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivf_search_i8_dev(args..., wide); });
+    return search_i8_host(p, nq, queries, k, nprobe, dist, labels, ctx, CallBitmap{});
 }
 int lb_gpu_ivf_search_i8(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
     return lb_gpu_ivf_search_i8_ctx(p, nq, queries, k, nprobe, dist, labels, nullptr);
 }
-// the same searches under a row bitmap given with the call (a NULL bitmap: the plain search)
 int lb_gpu_ivf_search_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
                                         int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, false)) return st;
-    Lease bits;
-    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
-                                 [&](auto &&...args) { return ivf_search_bitmap_dev(args..., b, bits); });
+    return search_device(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, CallBitmap{d_bitmap, nbits, stride_bytes, true});
 }
 int lb_gpu_ivf_search_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
                                  int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, false)) return st;
-    Lease bits;
-    const CallBitmap b{bitmap, nbits, stride_bytes, false};
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivf_search_bitmap_dev(args..., b, bits); });
+    return search_host(p, nq, queries, k, nprobe, dist, labels, ctx, CallBitmap{bitmap, nbits, stride_bytes, false});
 }
 int lb_gpu_ivf_search_i8_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
                                            int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
                                            const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, true)) return st;
-    Lease wide, bits;
-    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
-                                 [&](auto &&...args) { return ivf_search_i8_bitmap_dev(args..., wide, b, bits); });
+    return search_i8_device(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, CallBitmap{d_bitmap, nbits, stride_bytes, true});
 }
 int lb_gpu_ivf_search_i8_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
                                     int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
-    if (const int st = query_mismatch(p, true)) return st;
-    Lease wide, bits;
-    const CallBitmap b{bitmap, nbits, stride_bytes, false};
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx,
-                          [&](auto &&...args) { return ivf_search_i8_bitmap_dev(args..., wide, b, bits); });
+    return search_i8_host(p, nq, queries, k, nprobe, dist, labels, ctx, CallBitmap{bitmap, nbits, stride_bytes, false});
 }
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
 int lb_gpu_ivf_set_profiling(lb_gpu_ivf *p, int enable) { return ivf_set_profiling(p, enable); }

@@ -14,123 +14,61 @@ using namespace lb;
 
 struct lb_gpu_ivfbq : IvfHandle { // the partition (L2), and under a row filter the visible lists of positions (lb_ivf_host.h)
     int order = 0, W = 0;
-    DevBuf<uint64_t> d_codes;       // [capacity][W], insertion order: what get_codes returns
+    DevBuf<uint8_t> d_codes;        // [capacity][W] u64 words, insertion order: what get_codes returns
     // the list-major codes are built for all rows by every add, with the lists, into the pair that is not in use
-    DevBuf<uint64_t> d_lcodes[2];   // [capacity][W]: lcodes[pos] = codes[list[pos]]
+    DevBuf<uint8_t> d_lcodes[2];    // [capacity][W] u64 words: lcodes[pos] = codes[list[pos]]
     float timing[5] = {0, 0, 0, 0, 0}; // of the last profiled search (under err_mu): probes, plan, the queries' codes, scan, select; ms summed over its batches
-    size_t row_words(int64_t rows) const { return (size_t)rows * (size_t)W; }
+    size_t row_bytes(int64_t rows = 1) const { return (size_t)rows * (size_t)W * 8; }
 };
 
 namespace {
 
-// All or nothing: every new buffer is allocated and filled before the first one replaces an old one.
 void ivfbq_grow(lb_gpu_ivfbq *p, int64_t need, bool want_ids)
 {
-    const int64_t cap = ivf_grow_to(p, p->part, need, want_ids, (size_t)p->W * 8); // 1.
-    if (cap < 0) return;
-    IvfGrowth g;                                                                    // 2.
-    DevBuf<uint64_t> nc, nlc[2];
-    const int cur = p->part.cur;
-    g.stage(p, cap, want_ids);
-    if (g.resize) {
-        nc.alloc(p->row_words(cap));
-        for (DevBuf<uint64_t> &l : nlc) l.alloc(p->row_words(cap));
-        if (p->n > 0) {
-            LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), p->row_words(p->n) * 8, hipMemcpyDeviceToDevice));
-            LB_HIP(hipMemcpy(nlc[cur].get(), p->d_lcodes[cur].get(), p->row_words(p->n) * 8, hipMemcpyDeviceToDevice));
-        }
-        p->filter.grow(p->n, cap);                                                  // 3. (the last step that can fail)
-    }
-    g.commit(p);                                                                    // 4.
-    if (!g.resize) return;
-    p->d_codes = std::move(nc);
-    for (int i = 0; i < 2; i++) p->d_lcodes[i] = std::move(nlc[i]);
-    p->capacity = cap;
+    ivf_grow(p, need, want_ids, {{&p->d_codes, p->row_bytes(), false}, {p->d_lcodes, p->row_bytes(), true}});
 }
 
-// The vectors are assigned and encoded in pieces of piece_rows(dims) rows (64 Mi floats: 256 MB of host vectors staged at a time,
-// 12 bytes of labels and distances a row of a piece) and are not kept.  Codes and lists of the new rows are written behind the
-// stored ones, where they belong to nobody until the commit.
+// The handle's share of the add (lb_ivf_host.h: ivf_add).  The vectors are staged piece_rows(dims) rows at a time (64 Mi floats:
+// 256 MB of host vectors, 12 bytes of labels and distances a row of a piece) and are not kept: a piece's codes are stored, and
+// from the new lists the codes in list order are derived, into the pair not in use.
 int add_impl(lb_gpu_ivfbq *p, int64_t n, const float *vectors, const int64_t *ids, bool on_device)
 {
-    if (!p || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
-    if (n == 0) return LB_OK;
-    std::unique_lock<std::shared_mutex> g(p->mu);
-    IvfPartition &P = p->part;
-    if (const int st = ivf_ids_consistent(p, P, ids)) return st;
-    if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease vec, lab, hist, vis;
-    return guard(p, p->stream, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        hipStream_t s = p->stream;
-        const int64_t total = p->n + n;
-        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        std::vector<int64_t> sizes, vsizes;
-        const bool filtered = p->filter.on;
-        ivfbq_grow(p, total, ids != nullptr);
-        if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, kind, s));
-        // 1. the vectors, a piece at a time: 2. their lists, 3. their codes
-        const int64_t piece = std::min(n, piece_rows(p->dims));
-        lab.reset(p->device, ivf_assign_bytes(piece));
-        if (!on_device) vec.reset(p->device, (size_t)piece * p->dims * 4);
-        for (int64_t r0 = 0; r0 < n; r0 += piece) {
-            const int64_t cnt = std::min(piece, n - r0);
-            const float *d_new = vectors + (size_t)r0 * p->dims;
-            if (!on_device) {
-                LB_HIP(hipMemcpyAsync(vec.p, d_new, (size_t)cnt * p->dims * 4, hipMemcpyHostToDevice, s));
-                d_new = vec.as<float>();
-            }
-            if (const int rc = ivf_assign(p, P, p->n + r0, cnt, d_new, lab, s)) return rc;
-            launch_bq_encode(d_new, cnt, p->dims, p->d_codes.get() + p->row_words(p->n + r0), s);
-            LB_LAUNCH_CHECK();
-            LB_HIP(hipStreamSynchronize(s)); // (the staging buffer and the labels are reused by the next piece)
-        }
-        // 4. the lists of all rows and 5. their codes in list order, into the pair not in use
-        const int nxt = 1 - P.cur;
-        ivf_sort_lists(p, P, total, hist, s);
-        launch_ivfpq_permute(reinterpret_cast<const uint8_t *>(p->d_codes.get()), P.d_list[nxt].get(), total, 8 * p->W,
-                             reinterpret_cast<uint8_t *>(p->d_lcodes[nxt].get()), s);
-        if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
-        // 6. under a filter the new rows are visible: the visible lists of all rows, from the new lists (every position changes
-        //    with them), into the pair not in use
-        const int64_t nvis = filtered ? ivf_add_visible(p, total, vis, vsizes, s) : 0;
-        // 7. commit (nothing below throws)
-        if (filtered) ivf_commit_visible(p, vsizes, nvis);
-        P.h_sizes.swap(sizes);
-        P.cur = nxt;
-        P.has_ids = ids != nullptr;
-        p->n = total;
-        return LB_OK;
-    });
+    if (!p) return LB_ERR_INVALID_ARG;
+    IvfAddSource src{vectors, on_device, p->device, p->dims};
+    return ivf_add(
+        p, n, vectors, ids, on_device, piece_rows(p->dims), [&](int64_t total, bool want_ids) { ivfbq_grow(p, total, want_ids); }, src,
+        [&](const float *d_rows, int64_t r0, int64_t cnt, int64_t, hipStream_t s) {
+            launch_bq_encode(d_rows, cnt, p->dims, reinterpret_cast<uint64_t *>(p->d_codes.get() + p->row_bytes(p->n + r0)), s);
+        },
+        [&](int nxt, int64_t total, hipStream_t s) {
+            launch_ivfpq_permute(p->d_codes.get(), p->part.d_list[nxt].get(), total, (int)p->row_bytes(), p->d_lcodes[nxt].get(), s);
+        });
 }
 
-// The handle's call of the search loop (lb_ivf_host.h): exact Hamming k-NN; under a filter it walks the visible lists.  Its middle
-// steps are the queries' codes, a timing slot of their own, and the scan of the list-major codes; the selection is the one over
-// integer keys.
-int ivfbq_search_dev(lb_gpu_ivfbq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                     const lb_cancel *ctx, Lease &sc)
+// The handle's call of the search loop (lb_ivf_host.h): exact Hamming k-NN.  Its middle steps are the queries' codes, a timing
+// slot of their own, and the scan of the list-major codes, in its `_visible` form where the batch walks other lists than those of
+// all rows (w.subset: positions bounded by w.entries); the selection is the one over integer keys.
+int ivfbq_search_dev(lb_gpu_ivfbq *p, const IvfCall &c)
 {
     const IvfPartition &P = p->part;
-    IvfBatch a{};
-    a.X = nullptr; // (the plan and the selection take the batch as the IVF-Flat kernels do: neither reads rows)
-    a.D = p->dims;
-    const uint64_t *lcodes = p->d_lcodes[P.cur].get();
+    const uint64_t *lcodes = reinterpret_cast<const uint64_t *>(p->d_lcodes[P.cur].get());
     const uint32_t *rows = P.d_list[P.cur].get();
     uint64_t *d_qc = nullptr;
+    hipStream_t s = c.s;
     return ivf_search(
-        p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
-        [&](Carve &c, IvfBatch &, int64_t nb) { d_qc = c.take<uint64_t>(p->row_words(nb) * 8); },
-        [&](const IvfBatch &b, int64_t maxlen, auto &&, auto &&next) {
+        p, c, IvfSearchForm{p->timing, 5, kQueryBatch, launch_ivfsq8_select},
+        [&](Carve &cv, IvfBatch &, int64_t nb) { d_qc = cv.take<uint64_t>(p->row_bytes(nb)); },
+        [&](const IvfBatch &b, const IvfWalk &w, auto &&, auto &&next) {
             if (!next()) return false; // (the plan's slot ends here)
             launch_bq_encode(b.Q, b.nq, p->dims, d_qc, s);
             if (!next()) return false;
-            const IvfBqScan scan{b, lcodes, rows, p->n, p->W, d_qc, p->filter.on ? p->filter.n_visible : 0};
-            if (p->filter.on) launch_ivfbq_scan_visible(scan, maxlen, s);
-            else launch_ivfbq_scan(scan, maxlen, s);
+            const IvfBqScan scan{b, lcodes, rows, p->n, p->W, d_qc, w.subset ? w.entries : 0};
+            if (w.subset) launch_ivfbq_scan_visible(scan, w.maxlen, s);
+            else launch_ivfbq_scan(scan, w.maxlen, s);
             return true;
-        },
-        kQueryBatch, launch_ivfsq8_select);
+        });
 }
+
 
 } // namespace
 
@@ -160,7 +98,7 @@ int64_t lb_gpu_ivfbq_hbm_bytes(const lb_gpu_ivfbq *p)
 {
     if (!p) return 0;
     std::shared_lock<std::shared_mutex> g(const_cast<lb_gpu_ivfbq *>(p)->mu);
-    return (int64_t)((p->d_codes.count() + p->d_lcodes[0].count() + p->d_lcodes[1].count()) * 8) + p->visible_bytes() + p->part.hbm_bytes();
+    return (int64_t)(p->d_codes.count() + p->d_lcodes[0].count() + p->d_lcodes[1].count()) + p->visible_bytes() + p->part.hbm_bytes();
 }
 
 int lb_gpu_ivfbq_reserve(lb_gpu_ivfbq *p, int64_t n_total)
@@ -176,7 +114,7 @@ int lb_gpu_ivfbq_get_codes(lb_gpu_ivfbq *p, int64_t row0, int64_t n, uint64_t *c
     if (const int st = rows_in_range(p, row0, n)) return st;
     return guard(p, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
-        LB_HIP(hipMemcpy(codes, p->d_codes.get() + p->row_words(row0), p->row_words(n) * 8, hipMemcpyDeviceToHost));
+        LB_HIP(hipMemcpy(codes, p->d_codes.get() + p->row_bytes(row0), p->row_bytes(n), hipMemcpyDeviceToHost));
         return LB_OK;
     });
 }

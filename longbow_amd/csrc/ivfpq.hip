@@ -28,90 +28,38 @@ uint32_t rd_u32le(const uint8_t *p)
     return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
 }
 
-// All or nothing: every new buffer is allocated and filled before the first one replaces an old one.
 void ivfpq_grow(lb_gpu_ivfpq *p, int64_t need, bool want_ids)
 {
-    const int64_t cap = ivf_grow_to(p, p->part, need, want_ids, (size_t)p->M); // 1.
-    if (cap < 0) return;
-    IvfGrowth g;                                                                // 2.
-    DevBuf<uint8_t> nc, nlc[2];
-    const int cur = p->part.cur;
-    g.stage(p, cap, want_ids);
-    if (g.resize) {
-        nc.alloc((size_t)cap * p->M);
-        for (DevBuf<uint8_t> &l : nlc) l.alloc((size_t)cap * p->M);
-        if (p->n > 0) {
-            LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice));
-            LB_HIP(hipMemcpy(nlc[cur].get(), p->d_lcodes[cur].get(), (size_t)p->n * p->M, hipMemcpyDeviceToDevice));
-        }
-        p->filter.grow(p->n, cap);                                              // 3. (the last step that can fail)
-    }
-    g.commit(p);                                                                // 4.
-    if (!g.resize) return;
-    p->d_codes = std::move(nc);
-    for (int i = 0; i < 2; i++) p->d_lcodes[i] = std::move(nlc[i]);
-    p->capacity = cap;
+    ivf_grow(p, need, want_ids, {{&p->d_codes, (size_t)p->M, false}, {p->d_lcodes, (size_t)p->M, true}});
 }
 
-// The vectors are assigned and encoded in pieces of piece_rows(dims) rows (64 Mi floats: 256 MB of host vectors staged at a time,
-// 12 bytes of labels and distances a row of a piece) and are not kept.  Codes and lists of the new rows are written behind the
-// stored ones, where they belong to nobody until the commit.
+// what the handle derives from new lists (an add's, a compaction's): the codes in list order, into the pair not in use
+auto ivfpq_relist(lb_gpu_ivfpq *p)
+{
+    return [p](int nxt, int64_t total, hipStream_t s) {
+        launch_ivfpq_permute(p->d_codes.get(), p->part.d_list[nxt].get(), total, p->M, p->d_lcodes[nxt].get(), s);
+    };
+}
+
+// The handle's share of the add (lb_ivf_host.h: ivf_add).  The vectors are staged piece_rows(dims) rows at a time (64 Mi floats:
+// 256 MB of host vectors, 12 bytes of labels and distances a row of a piece) and are not kept: a piece's codes are stored, on a
+// residual handle those of the rows less their lists' centroids (`res`).
 int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *ids, bool on_device)
 {
-    if (!p || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
-    if (n == 0) return LB_OK;
-    std::unique_lock<std::shared_mutex> g(p->mu);
-    IvfPartition &P = p->part;
-    if (const int st = ivf_ids_consistent(p, P, ids)) return st;
-    if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease vec, lab, hist, vis, res;
-    return guard(p, p->stream, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        hipStream_t s = p->stream;
-        const int64_t total = p->n + n;
-        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        std::vector<int64_t> sizes, vsizes;
-        const bool filtered = p->filter.on;
-        ivfpq_grow(p, total, ids != nullptr);
-        if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, kind, s));
-        // 1. the vectors, a piece at a time: 2. their lists, 3. their codes
-        const int64_t piece = std::min(n, piece_rows(p->dims));
-        lab.reset(p->device, ivf_assign_bytes(piece));
-        if (!on_device) vec.reset(p->device, (size_t)piece * p->dims * 4);
-        if (p->residual) res.reset(p->device, (size_t)piece * p->dims * 4);
-        for (int64_t r0 = 0; r0 < n; r0 += piece) {
-            const int64_t cnt = std::min(piece, n - r0);
-            const float *d_new = vectors + (size_t)r0 * p->dims;
-            if (!on_device) {
-                LB_HIP(hipMemcpyAsync(vec.p, d_new, (size_t)cnt * p->dims * 4, hipMemcpyHostToDevice, s));
-                d_new = vec.as<float>();
+    if (!p) return LB_ERR_INVALID_ARG;
+    IvfAddSource src{vectors, on_device, p->device, p->dims};
+    Lease res;
+    return ivf_add(
+        p, n, vectors, ids, on_device, piece_rows(p->dims), [&](int64_t total, bool want_ids) { ivfpq_grow(p, total, want_ids); }, src,
+        [&](const float *d_rows, int64_t r0, int64_t cnt, int64_t piece, hipStream_t s) {
+            if (p->residual) {
+                if (r0 == 0) res.reset(p->device, (size_t)piece * p->dims * 4);
+                launch_ivfpq_residual_rows(d_rows, p->part.d_assign.get() + p->n + r0, p->d_cent.get(), cnt, p->dims, p->part.nlist, res.as<float>(), s);
+                d_rows = res.as<float>();
             }
-            if (const int rc = ivf_assign(p, P, p->n + r0, cnt, d_new, lab, s)) return rc;
-            if (p->residual) { // the piece's rows less their lists' centroids are what is encoded
-                launch_ivfpq_residual_rows(d_new, P.d_assign.get() + p->n + r0, p->d_cent.get(), cnt, p->dims, P.nlist, res.as<float>(), s);
-                d_new = res.as<float>();
-            }
-            launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_new, cnt, p->d_codes.get() + (size_t)(p->n + r0) * p->M, s);
-            LB_LAUNCH_CHECK();
-            LB_HIP(hipStreamSynchronize(s)); // (the staging buffer and the labels are reused by the next piece)
-        }
-        // 4. the lists of all rows and 5. their codes in list order, into the pair not in use
-        const int nxt = 1 - P.cur;
-        ivf_add_live(p, total, s); // (a handle that has removed rows: the new ones are live)
-        ivf_sort_lists(p, P, total, hist, s);
-        launch_ivfpq_permute(p->d_codes.get(), P.d_list[nxt].get(), total, p->M, p->d_lcodes[nxt].get(), s);
-        if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
-        // 6. under a filter the new rows are visible: the visible lists of all rows, from the new lists (every position changes
-        //    with them), into the pair not in use
-        const int64_t nvis = filtered ? ivf_add_visible(p, total, vis, vsizes, s) : 0;
-        // 7. commit (nothing below throws)
-        if (filtered) ivf_commit_visible(p, vsizes, nvis);
-        P.h_sizes.swap(sizes);
-        P.cur = nxt;
-        P.has_ids = ids != nullptr;
-        p->n = total;
-        return LB_OK;
-    });
+            launch_pq_encode(p->d_codebooks.get(), p->M, p->K, p->sub, d_rows, cnt, p->d_codes.get() + (size_t)(p->n + r0) * p->M, s);
+        },
+        ivfpq_relist(p));
 }
 
 // The residual handle's call of the search loop.  A query has a table per probed list, so the middle steps run over the pairs
@@ -121,39 +69,34 @@ int add_impl(lb_gpu_ivfpq *p, int64_t n, const float *vectors, const int64_t *id
 // once.  Timing: slot 3 is the first round's residual queries and tables, slot 4 its scan and every further round whole.
 constexpr int64_t kTableLaunch = 65535; // pairs a launch_build_adc_table call takes: its queries are on grid.y
 
-// Under a call's bitmap (filter.on) the batch's lists and probes are the call's synthetic ones, whose entries are positions: the
-// scan takes its `_visible` form over them whether or not the handle has a filter, bounded by the entries of the call's row array,
-// and the residual queries are built from a copy of the batch whose lists and probes are the handle's and the coarse search's
-// (real_probes: where the batch pointed at layout time, the same buffer every batch), since a table belongs to the list probed.
-int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfBatch &a, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels,
-                      hipStream_t s, const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter)
+// The residual queries are built from a copy of the batch whose lists and probes are the handle's and the coarse search's (w.own,
+// w.probes), whatever the batch walks, since a table belongs to the list probed.
+int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfCall &c)
 {
     const IvfPartition &P = p->part;
     const uint8_t *lcodes = p->d_lcodes[P.cur].get();
-    const int np = std::min(nprobe, P.nlist);
+    const int np = std::min(c.nprobe, P.nlist);
     const IvfpqTablePlan tp = ivfpq_table_plan(np, p->M, kTableScratch);
     float *d_rq = nullptr, *d_tables = nullptr;
     uint32_t *d_items = nullptr; // the scan's work list, where it runs from one (ivfpq_rscan_plan)
-    const int64_t *real_probes = nullptr;
-    const IvfLists own = p->lists();
+    hipStream_t s = c.s;
     return ivf_search(
-        p, p->part, own, p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
-        [&](Carve &c, IvfBatch &b, int64_t nb) {
-            real_probes = b.probes;
+        p, c, IvfSearchForm{p->timing, 5, tp.nb},
+        [&](Carve &cv, IvfBatch &, int64_t nb) {
             const size_t pairs = (size_t)nb * (size_t)tp.slots; // of a round
-            d_rq = c.take<float>(pairs * p->dims * 4);
-            d_tables = c.take<float>(pairs * p->M * 256 * 4);
-            d_items = c.take<uint32_t>((pairs + 1) * 4);
+            d_rq = cv.take<float>(pairs * p->dims * 4);
+            d_tables = cv.take<float>(pairs * p->M * 256 * 4);
+            d_items = cv.take<uint32_t>((pairs + 1) * 4);
         },
-        [&](const IvfBatch &b, int64_t maxlen, auto &&poll, auto &&next) {
+        [&](const IvfBatch &b, const IvfWalk &w, auto &&poll, auto &&next) {
             if (!next()) return false; // (the plan's slot ends here)
             for (int s0 = 0; s0 < np; s0 += (int)tp.slots) {
                 const int ns = (int)std::min<int64_t>(tp.slots, np - s0);
                 const int64_t pairs = (int64_t)b.nq * ns;
                 if (s0 > 0 && !poll()) return false;
                 IvfBatch rb = b;
-                rb.L = own;
-                rb.probes = real_probes;
+                rb.L = w.own;
+                rb.probes = w.probes;
                 launch_ivfpq_residual_queries(rb, s0, ns, p->d_cent.get(), d_rq, s);
                 for (int64_t p0 = 0; p0 < pairs; p0 += kTableLaunch) {
                     if (!poll()) return false;
@@ -161,55 +104,34 @@ int ivfpq_rsearch_dev(lb_gpu_ivfpq *p, const IvfBatch &a, int64_t nq, const floa
                                            (int)std::min(kTableLaunch, pairs - p0), d_tables + (size_t)p0 * p->M * 256, s);
                 }
                 if (s0 == 0 ? !next() : !poll()) return false;
-                if (filter.on)
-                    launch_ivfpq_rscan_visible(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, P.d_list[P.cur].get(), filter.call_rows, s);
-                else if (p->filter.on)
-                    launch_ivfpq_rscan_visible(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, P.d_list[P.cur].get(),
-                                               p->filter.n_visible, s);
-                else launch_ivfpq_rscan(b, s0, ns, d_tables, p->M, lcodes, p->n, maxlen, d_items, s);
+                if (w.subset) launch_ivfpq_rscan_visible(b, s0, ns, d_tables, p->M, lcodes, p->n, w.maxlen, d_items, P.d_list[P.cur].get(), w.entries, s);
+                else launch_ivfpq_rscan(b, s0, ns, d_tables, p->M, lcodes, p->n, w.maxlen, d_items, s);
             }
             return true;
-        },
-        tp.nb, launch_ivf_select, filter);
+        });
 }
 
-// The handle's call of the search loop (lb_ivf_host.h): exact ADC k-NN; under a filter it walks the visible lists.  Its middle steps
-// are the queries' tables, a timing slot of their own, and the scan of the list-major codes.
-// filter: the call's own row bitmap (the *_bitmap entry points): the scan then takes its `_visible` form over the call's lists of
-// positions, as above.
-int ivfpq_search_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                     const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter = IvfCallFilter{})
+// The handle's call of the search loop (lb_ivf_host.h): exact ADC k-NN.  Its middle steps are the queries' tables, a timing slot
+// of their own, and the scan of the list-major codes: over the lists of all rows by position, or, where the batch walks the
+// visible lists or a call's (w.subset), in its `_visible` form over their entries, positions bounded by w.entries.
+int ivfpq_search_dev(lb_gpu_ivfpq *p, const IvfCall &c)
 {
-    if (const int st = ivf_live_ok(p)) return st;
+    if (p->residual) return ivfpq_rsearch_dev(p, c);
     const IvfPartition &P = p->part;
-    IvfBatch a{};
-    a.X = nullptr; // (only the plan and the selection take the batch as the IVF-Flat kernels do: neither reads rows)
-    a.D = p->dims;
     const uint8_t *lcodes = p->d_lcodes[P.cur].get();
     float *d_tables = nullptr;
-    if (p->residual) return ivfpq_rsearch_dev(p, a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, filter);
+    hipStream_t s = c.s;
     return ivf_search(
-        p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
-        [&](Carve &c, IvfBatch &, int64_t nb) { d_tables = c.take<float>((size_t)nb * p->M * 256 * 4); },
-        [&](const IvfBatch &b, int64_t, auto &&, auto &&next) {
+        p, c, IvfSearchForm{p->timing, 5},
+        [&](Carve &cv, IvfBatch &, int64_t nb) { d_tables = cv.take<float>((size_t)nb * p->M * 256 * 4); },
+        [&](const IvfBatch &b, const IvfWalk &w, auto &&, auto &&next) {
             if (!next()) return false; // (the plan's slot ends here)
             launch_build_adc_table(p->d_codebooks.get(), p->M, p->K, p->sub, b.Q, b.nq, d_tables, s);
             if (!next()) return false;
-            if (filter.on) launch_ivfpq_scan_visible(b, d_tables, p->M, lcodes, p->n, P.d_list[P.cur].get(), filter.call_rows, s);
-            else if (p->filter.on) launch_ivfpq_scan_visible(b, d_tables, p->M, lcodes, p->n, P.d_list[P.cur].get(), p->filter.n_visible, s);
+            if (w.subset) launch_ivfpq_scan_visible(b, d_tables, p->M, lcodes, p->n, P.d_list[P.cur].get(), w.entries, s);
             else launch_ivfpq_scan(b, d_tables, p->M, lcodes, p->n, s);
             return true;
-        },
-        kQueryBatch, launch_ivf_select, filter);
-}
-
-// the search under a row bitmap given with the call: lb_ivf_host.h's refusals and copy, then the search above
-int ivfpq_search_bitmap_dev(lb_gpu_ivfpq *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                            const lb_cancel *ctx, Lease &sc, const CallBitmap &b, Lease &bits)
-{
-    IvfCallFilter f;
-    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
-    return ivfpq_search_dev(p, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, f);
+        });
 }
 
 // both constructors: the same arguments, limits, order of checks and status codes
@@ -318,9 +240,7 @@ int64_t lb_gpu_ivfpq_ndeleted(const lb_gpu_ivfpq *p) { return ivf_ndeleted(p); }
 int lb_gpu_ivfpq_compact(lb_gpu_ivfpq *p, int64_t *old_rows, int64_t cap)
 {
     if (!p) return LB_ERR_INVALID_ARG;
-    return ivf_compact(p, [p] { return static_cast<void *>(p->d_codes.get()); }, (size_t)p->M, old_rows, cap, [p](int nxt, int64_t nlive, hipStream_t s) {
-        launch_ivfpq_permute(p->d_codes.get(), p->part.d_list[nxt].get(), nlive, p->M, p->d_lcodes[nxt].get(), s);
-    });
+    return ivf_compact(p, [p] { return static_cast<void *>(p->d_codes.get()); }, (size_t)p->M, old_rows, cap, ivfpq_relist(p));
 }
 
 // ---- what the IVF handles share (lb_ivf_host.h) -------------------------------------------------------------------------
@@ -332,12 +252,12 @@ int lb_gpu_ivfpq_assignments(lb_gpu_ivfpq *p, int64_t row0, int64_t n, int32_t *
 int lb_gpu_ivfpq_search_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                    void *stream, const lb_cancel *ctx)
 {
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, [](auto &&...args) { return ivfpq_search_dev(args...); });
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivfpq_search_dev);
 }
 int lb_gpu_ivfpq_search_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                             const lb_cancel *ctx)
 {
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [](auto &&...args) { return ivfpq_search_dev(args...); });
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivfpq_search_dev);
 }
 int lb_gpu_ivfpq_search(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
@@ -347,17 +267,13 @@ int lb_gpu_ivfpq_search(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k
 int lb_gpu_ivfpq_search_bitmap_device_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
                                           int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
-    Lease bits;
-    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
-                                 [&](auto &&...args) { return ivfpq_search_bitmap_dev(args..., b, bits); });
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivfpq_search_dev,
+                                 CallBitmap{d_bitmap, nbits, stride_bytes, true});
 }
 int lb_gpu_ivfpq_search_bitmap_ctx(lb_gpu_ivfpq *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
                                    int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
-    Lease bits;
-    const CallBitmap b{bitmap, nbits, stride_bytes, false};
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivfpq_search_bitmap_dev(args..., b, bits); });
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivfpq_search_dev, CallBitmap{bitmap, nbits, stride_bytes, false});
 }
 int lb_gpu_ivfpq_last_search_stats(lb_gpu_ivfpq *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
 int lb_gpu_ivfpq_set_profiling(lb_gpu_ivfpq *p, int enable) { return ivf_set_profiling(p, enable); }

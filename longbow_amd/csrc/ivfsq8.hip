@@ -22,120 +22,48 @@ struct lb_gpu_ivfsq8 : IvfHandle { // the partition (L2), and under a row filter
 
 namespace {
 
-// All or nothing: every new buffer is allocated and filled before the first one replaces an old one.
-void ivfsq8_grow(lb_gpu_ivfsq8 *p, int64_t need, bool want_ids)
-{
-    const int64_t cap = ivf_grow_to(p, p->part, need, want_ids, (size_t)p->stride); // 1.
-    if (cap < 0) return;
-    IvfGrowth g;                                                                     // 2.
-    DevBuf<uint8_t> nc;
-    g.stage(p, cap, want_ids);
-    if (g.resize) {
-        nc.alloc((size_t)cap * p->stride);
-        if (p->n > 0) LB_HIP(hipMemcpy(nc.get(), p->d_codes.get(), (size_t)p->n * p->stride, hipMemcpyDeviceToDevice));
-        p->filter.grow(p->n, cap);                                                   // 3. (the last step that can fail)
-    }
-    g.commit(p);                                                                     // 4.
-    if (!g.resize) return;
-    p->d_codes = std::move(nc);
-    p->capacity = cap;
-}
+void ivfsq8_grow(lb_gpu_ivfsq8 *p, int64_t need, bool want_ids) { ivf_grow(p, need, want_ids, {{&p->d_codes, (size_t)p->stride, false}}); }
 
-// The vectors are assigned and encoded in pieces of piece_rows(dims) rows (64 Mi floats: 256 MB of host vectors staged at a time,
-// 12 bytes of labels and distances a row of a piece) and are not kept.  Codes and lists of the new rows are written behind the
-// stored ones, where they belong to nobody until the commit.
+// The handle's share of the add (lb_ivf_host.h: ivf_add).  The vectors are staged piece_rows(dims) rows at a time (64 Mi floats:
+// 256 MB of host vectors, 12 bytes of labels and distances a row of a piece) and are not kept: a piece's codes are stored, and
+// nothing is derived from the new lists.
 int add_impl(lb_gpu_ivfsq8 *p, int64_t n, const float *vectors, const int64_t *ids, bool on_device)
 {
-    if (!p || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
-    if (n == 0) return LB_OK;
-    std::unique_lock<std::shared_mutex> g(p->mu);
-    IvfPartition &P = p->part;
-    if (const int st = ivf_ids_consistent(p, P, ids)) return st;
-    if (const int st = rows_fit(p, p->n, n)) return st;
-    Lease vec, lab, hist, vis;
-    return guard(p, p->stream, [&]() -> int {
-        LB_HIP(hipSetDevice(p->device));
-        hipStream_t s = p->stream;
-        const int64_t total = p->n + n;
-        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-        std::vector<int64_t> sizes, vsizes;
-        const bool filtered = p->filter.on;
-        ivfsq8_grow(p, total, ids != nullptr);
-        if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, kind, s));
-        // 1. the vectors, a piece at a time: 2. their lists, 3. their codes
-        const int64_t piece = std::min(n, piece_rows(p->dims));
-        lab.reset(p->device, ivf_assign_bytes(piece));
-        if (!on_device) vec.reset(p->device, (size_t)piece * p->dims * 4);
-        for (int64_t r0 = 0; r0 < n; r0 += piece) {
-            const int64_t cnt = std::min(piece, n - r0);
-            const float *d_new = vectors + (size_t)r0 * p->dims;
-            if (!on_device) {
-                LB_HIP(hipMemcpyAsync(vec.p, d_new, (size_t)cnt * p->dims * 4, hipMemcpyHostToDevice, s));
-                d_new = vec.as<float>();
-            }
-            if (const int rc = ivf_assign(p, P, p->n + r0, cnt, d_new, lab, s)) return rc;
-            launch_sq8_encode(d_new, cnt, p->dims, p->dmin(), p->dmax(), p->dscale(), p->d_codes.get() + (size_t)(p->n + r0) * p->stride, s);
-            LB_LAUNCH_CHECK();
-            LB_HIP(hipStreamSynchronize(s)); // (the staging buffer and the labels are reused by the next piece)
-        }
-        // 4. the lists of all rows, into the pair not in use
-        ivf_add_live(p, total, s); // (a handle that has removed rows: the new ones are live)
-        ivf_sort_lists(p, P, total, hist, s);
-        if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
-        const int nxt = 1 - P.cur;
-        // 5. under a filter the new rows are visible: the visible lists of all rows, from the new lists, into the pair not in use
-        //    (the mask bytes behind the stored rows belong to nobody until the commit)
-        const int64_t nvis = filtered ? ivf_add_visible(p, total, vis, vsizes, s) : 0;
-        // 6. commit (nothing below throws)
-        if (filtered) ivf_commit_visible(p, vsizes, nvis);
-        P.h_sizes.swap(sizes);
-        P.cur = nxt;
-        P.has_ids = ids != nullptr;
-        p->n = total;
-        return LB_OK;
-    });
+    if (!p) return LB_ERR_INVALID_ARG;
+    IvfAddSource src{vectors, on_device, p->device, p->dims};
+    return ivf_add(
+        p, n, vectors, ids, on_device, piece_rows(p->dims), [&](int64_t total, bool want_ids) { ivfsq8_grow(p, total, want_ids); }, src,
+        [&](const float *d_rows, int64_t r0, int64_t cnt, int64_t, hipStream_t s) {
+            launch_sq8_encode(d_rows, cnt, p->dims, p->dmin(), p->dmax(), p->dscale(), p->d_codes.get() + (size_t)(p->n + r0) * p->stride, s);
+        },
+        ivf_no_relist);
 }
 
-// The handle's call of the search loop (lb_ivf_host.h): exact integer k-NN; under a filter it walks the visible lists.  Its middle
-// steps are the queries' codes and their norms, a timing slot of their own, and the scan of the probed lists' rows; the selection
-// is the one over integer keys.
-// filter: the call's own row bitmap (the *_bitmap entry points).  The lists hold rows and the scan gathers by row, so the call's
-// lists go through the search loop as the IVF-Flat handle's do and nothing here changes with them.
-int ivfsq8_search_dev(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                      const lb_cancel *ctx, Lease &sc, const IvfCallFilter &filter = IvfCallFilter{})
+// The handle's call of the search loop (lb_ivf_host.h): exact integer k-NN.  Its middle steps are the queries' codes and their
+// norms, a timing slot of their own, and the scan of the probed lists' rows; the selection is the one over integer keys.  The
+// lists hold rows and the scan gathers by row, so the visible lists and a call's go through the loop as the IVF-Flat handle's do.
+int ivfsq8_search_dev(lb_gpu_ivfsq8 *p, const IvfCall &c)
 {
-    if (const int st = ivf_live_ok(p)) return st;
-    IvfBatch a{};
-    a.X = nullptr; // (the plan and the selection take the batch as the IVF-Flat kernels do: neither reads rows)
-    a.D = p->dims;
     uint8_t *d_qc = nullptr;
     int32_t *d_qn = nullptr;
+    hipStream_t s = c.s;
     return ivf_search(
-        p, p->part, p->lists(), p->sizes(), a, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, p->timing, 5,
-        [&](Carve &c, IvfBatch &, int64_t nb) {
-            d_qc = c.take<uint8_t>((size_t)nb * p->stride);
-            d_qn = c.take<int32_t>((size_t)nb * 4);
+        p, c, IvfSearchForm{p->timing, 5, kQueryBatch, launch_ivfsq8_select},
+        [&](Carve &cv, IvfBatch &, int64_t nb) {
+            d_qc = cv.take<uint8_t>((size_t)nb * p->stride);
+            d_qn = cv.take<int32_t>((size_t)nb * 4);
         },
-        [&](const IvfBatch &b, int64_t maxlen, auto &&poll, auto &&next) {
+        [&](const IvfBatch &b, const IvfWalk &w, auto &&poll, auto &&next) {
             if (!next()) return false; // (the plan's slot ends here)
             launch_sq8_encode(b.Q, b.nq, p->dims, p->dmin(), p->dmax(), p->dscale(), d_qc, s);
             if (!poll()) return false;
             launch_sq8_norms(d_qc, b.nq, p->stride, d_qn, s);
             if (!next()) return false;
-            launch_ivfsq8_scan(IvfSq8Scan{b, p->d_codes.get(), p->n, p->stride, d_qc, d_qn}, maxlen, s);
+            launch_ivfsq8_scan(IvfSq8Scan{b, p->d_codes.get(), p->n, p->stride, d_qc, d_qn}, w.maxlen, s);
             return true;
-        },
-        kQueryBatch, launch_ivfsq8_select, filter);
+        });
 }
 
-// the search under a row bitmap given with the call: lb_ivf_host.h's refusals and copy, then the search above
-int ivfsq8_search_bitmap_dev(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_Q, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s,
-                             const lb_cancel *ctx, Lease &sc, const CallBitmap &b, Lease &bits)
-{
-    IvfCallFilter f;
-    if (const int st = call_filter(p, nq, b, bits, s, f)) return st;
-    return ivfsq8_search_dev(p, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc, f);
-}
 
 } // namespace
 
@@ -258,12 +186,12 @@ int lb_gpu_ivfsq8_assignments(lb_gpu_ivfsq8 *p, int64_t row0, int64_t n, int32_t
 int lb_gpu_ivfsq8_search_device_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels,
                                     void *stream, const lb_cancel *ctx)
 {
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, [](auto &&...args) { return ivfsq8_search_dev(args...); });
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivfsq8_search_dev);
 }
 int lb_gpu_ivfsq8_search_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                              const lb_cancel *ctx)
 {
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [](auto &&...args) { return ivfsq8_search_dev(args...); });
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivfsq8_search_dev);
 }
 int lb_gpu_ivfsq8_search(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels)
 {
@@ -273,17 +201,13 @@ int lb_gpu_ivfsq8_search(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int
 int lb_gpu_ivfsq8_search_bitmap_device_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
                                            int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
-    Lease bits;
-    const CallBitmap b{d_bitmap, nbits, stride_bytes, true};
-    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx,
-                                 [&](auto &&...args) { return ivfsq8_search_bitmap_dev(args..., b, bits); });
+    return ivf_search_device_ctx(p, nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, ivfsq8_search_dev,
+                                 CallBitmap{d_bitmap, nbits, stride_bytes, true});
 }
 int lb_gpu_ivfsq8_search_bitmap_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
                                     int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx)
 {
-    Lease bits;
-    const CallBitmap b{bitmap, nbits, stride_bytes, false};
-    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, [&](auto &&...args) { return ivfsq8_search_bitmap_dev(args..., b, bits); });
+    return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivfsq8_search_dev, CallBitmap{bitmap, nbits, stride_bytes, false});
 }
 int lb_gpu_ivfsq8_last_search_stats(lb_gpu_ivfsq8 *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
 int lb_gpu_ivfsq8_set_profiling(lb_gpu_ivfsq8 *p, int enable) { return ivf_set_profiling(p, enable); }

@@ -4,18 +4,20 @@
 //
 // The contract:
 //   * IvfPartition is the coarse partition of a handle's rows: the inner exact f32 index over the centroids, the list of each row
-//     and the inverted lists over them.  It is the member `part` of IvfHandle, which both handles derive from and which also
+//     and the inverted lists over them.  It is the member `part` of IvfHandle, which every handle derives from and which also
 //     holds what the row filter (lb_handle.h) adds to a partition: the visible lists.  The functions here take
 //     (CodeHandle *h, IvfPartition &P, ...) or an IvfHandle *p, the entry-point templates a T *p with p->part and p->timing;
 //   * the rules at the head of lb_handle.h hold: every pooled Lease that a function here enqueues work on is the caller's, declared
 //     outside its guard(); coarse_fail drains the stream before leases go back; searches and reads take `mu` shared, adds and
 //     reserve take it alone.  Everything that takes a stream runs inside the caller's guard() and throws as its body does;
-//   * growth is all or nothing (IvfGrowth): stage() allocates and fills and may throw, then the handle's own buffers, then
-//     filter.grow (the last step that can fail), then commit(), which moves and cannot throw;
-//   * an add writes behind the stored rows and into the pair of lists that is not in use, and commits last: sizes, pair, ids flag
-//     and n, by the handle's add_impl, with nothing that throws after it.  Under a filter the new rows are visible: the add also
-//     builds the visible lists of all rows into their pair not in use (ivf_add_visible) and commits them with the rest
-//     (ivf_commit_visible);
+//   * growth is all or nothing and is written once: ivf_grow, over the row arrays a handle names (IvfRowArray), in the order
+//     stated there.  A handle's *_grow is that call and nothing else;
+//   * the add is written once: ivf_add.  It writes behind the stored rows and into the pair of lists that is not in use, and
+//     commits last, in the order stated there, with nothing that throws after the first committed field.  Under a filter the new
+//     rows are visible and the visible lists of all rows are built and committed with the rest (ivf_add_visible,
+//     ivf_commit_visible); on a handle that has removed rows they are live (ivf_add_live).  A handle gives it its
+//     grow, the piece size, where a piece's f32 rows come from, what it stores from them and what it derives from the new lists;
+//     a lease of the handle's own is declared by the handle, ahead of the call and so outside ivf_add's guard();
 //   * the filter calls rebuild the visible lists through ivf_visible_builder, the `built` hook of filter_set / filter_column;
 //   * rows can be removed (ivf_remove_*, ivf_compact; entry points on lb_gpu_ivf, lb_gpu_ivfpq and lb_gpu_ivfsq8; lb_gpu_ivfbq has
 //     none yet and never holds a removed row).  IvfHandle::live is a second per-row state beside the caller's filter, allocated
@@ -29,9 +31,11 @@
 //     keeps a list-major copy of its codes beside the lists: a removal leaves that copy alone (the visible lists it builds hold
 //     positions into the copy of ALL rows), and compaction writes the copy of the pair not in use from the compacted codes and
 //     the new lists through ivf_compact's `relist` hook;
-//   * ivf_search is the one search loop.  A handle supplies its scratch pieces and the launches between the plan and the
-//     selection; ctx is polled before every launch, a cancelled search publishes no stats, and the events of a profiled search
-//     fall where the handle's timing slots say.
+//   * ivf_search is the one search loop.  A call travels as a record (IvfCall), a handle's fixed choices as another
+//     (IvfSearchForm); the handle supplies its scratch pieces and the launches between the plan and the selection, which are told
+//     about the lists the batch walks through IvfWalk; ctx is polled before every launch, a cancelled search publishes no stats,
+//     and the events of a profiled search fall where the handle's timing slots say.  A row bitmap given with the call is the
+//     entry-point templates' business (call_filter) and, in the loop, IvfCallWalk's; a plain search is that search without one.
 #pragma once
 #include "lb_handle.h"
 #include "lb_ivf.h"
@@ -39,6 +43,7 @@
 
 #include <atomic>
 #include <functional>
+#include <initializer_list>
 #include <stdexcept>
 #include <vector>
 
@@ -148,8 +153,8 @@ inline int64_t ivf_grow_to(const CodeHandle *h, const IvfPartition &P, int64_t n
     return need <= h->capacity ? h->capacity : grow_capacity(h->capacity, need, row_bytes);
 }
 
-// The share of the partition and of the visible lists in a handle's *_grow to `cap` rows.  The handle stages its own buffers beside
-// it, calls filter.grow and commits them with it: no old buffer is replaced before every new one is allocated and filled.
+// The share of the partition and of the visible lists in ivf_grow to `cap` rows: stage() allocates and fills and may throw,
+// commit() moves and cannot.
 constexpr size_t live_bytes(int64_t cap) { return ((size_t)cap + 3) & ~(size_t)3; } // (whole words: launch_remove_rows)
 
 struct IvfGrowth {
@@ -198,6 +203,43 @@ struct IvfGrowth {
             for (int i = 0; i < 2; i++) h->d_vlist[i] = std::move(vlist[i]);
     }
 };
+
+// One of a handle's own row arrays (rows or codes, of any element type, kept as bytes): a single buffer, or the pair indexed by
+// part.cur, which an add or a compaction writes whole into the half not in use.
+struct IvfRowArray {
+    DevBuf<uint8_t> *buf; // the buffer, or the first of the pair
+    size_t row_bytes;
+    bool pair;
+};
+
+// Room for `need` rows (and for ids, if wanted).  All or nothing: no old buffer is replaced before every new one is allocated and
+// filled.  The capacity grows by the first array's row.
+inline void ivf_grow(IvfHandle *p, int64_t need, bool want_ids, std::initializer_list<IvfRowArray> arrays)
+{
+    const int64_t cap = ivf_grow_to(p, p->part, need, want_ids, arrays.begin()->row_bytes); // 1. the capacity
+    if (cap < 0) return;
+    IvfGrowth g;
+    std::vector<DevBuf<uint8_t>> fresh(2 * arrays.size());
+    g.stage(p, cap, want_ids);                                                               // 2. the partition's share
+    if (g.resize) {                                                                          // 3. the handle's own arrays
+        size_t i = 0;
+        for (const IvfRowArray &a : arrays)
+            for (int j = 0; j < (a.pair ? 2 : 1); j++) fresh[i++].alloc((size_t)cap * a.row_bytes);
+        i = 0;
+        for (const IvfRowArray &a : arrays) { // (of a pair the half in use alone)
+            const int j = a.pair ? p->part.cur : 0;
+            if (p->n > 0) LB_HIP(hipMemcpy(fresh[i + j].get(), a.buf[j].get(), (size_t)p->n * a.row_bytes, hipMemcpyDeviceToDevice));
+            i += a.pair ? 2 : 1;
+        }
+        p->filter.grow(p->n, cap);                                                           // 4. the last step that can fail
+    }
+    g.commit(p);                                                                             // 5. nothing below throws
+    if (!g.resize) return;
+    size_t i = 0;
+    for (const IvfRowArray &a : arrays)
+        for (int j = 0; j < (a.pair ? 2 : 1); j++) a.buf[j] = std::move(fresh[i++]);
+    p->capacity = cap;
+}
 
 // ---- the steps of an add ----------------------------------------------------------------------------------------------------
 inline int ivf_ids_consistent(CodeHandle *h, const IvfPartition &P, const int64_t *ids)
@@ -344,6 +386,89 @@ inline int ivf_live_ok(IvfHandle *p)
     p->set_error("a failed call left the handle's %lld removed rows without their mask: set_filter puts it back", (long long)p->n_dead);
     return LB_ERR_INTERNAL;
 }
+
+// ---- the add ----------------------------------------------------------------------------------------------------------------
+// n rows (`vectors`: only looked at for being there), with ids or without, from host or device memory.  The handle gives:
+//   grow(total, want_ids)        its *_grow
+//   piece_cap                    rows assigned at a time at most
+//   rows(r0, cnt, piece, s)      -> the device-resident f32 rows [r0, r0 + cnt) of the add, for ivf_assign: enqueued on s, valid until
+//                                the piece's store has been enqueued.  The pieces come in order; at r0 == 0 it sizes whatever lease
+//                                it fills for pieces of up to `piece` rows
+//   store(d_rows, r0, cnt, piece, s)  enqueues what the handle keeps of them as rows [p->n + r0, ..) (codes; their lists are in
+//                                part.d_assign by then); ivf_no_store for a handle whose rows() has stored them
+//   relist(nxt, total, s)        what it derives from the new lists of all rows: ivf_compact's hook, called between the sort and
+//                                the read-back of the sizes
+// Leases that rows() and store() fill are the handle's, declared ahead of this call and so outside the guard() here.  Rows, codes
+// and lists of the new rows are written behind the stored ones, where they belong to nobody until the commit; the lists of all
+// rows go into the pair not in use.  Between pieces the stream is drained (a piece's leases are reused by the next); behind the
+// last one ivf_read_lists drains it.
+inline void ivf_no_store(const float *, int64_t, int64_t, int64_t, hipStream_t) {}
+template <class Grow, class Rows, class Store, class Relist>
+int ivf_add(IvfHandle *p, int64_t n, const void *vectors, const int64_t *ids, bool on_device, int64_t piece_cap, Grow &&grow, Rows &&rows,
+            Store &&store, Relist &&relist)
+{
+    if (!p || n < 0 || (n > 0 && !vectors)) return LB_ERR_INVALID_ARG;
+    if (n == 0) return LB_OK;
+    std::unique_lock<std::shared_mutex> g(p->mu);
+    IvfPartition &P = p->part;
+    if (const int st = ivf_ids_consistent(p, P, ids)) return st;
+    if (const int st = rows_fit(p, p->n, n)) return st;
+    Lease lab, hist, vis;
+    return guard(p, p->stream, [&]() -> int {
+        LB_HIP(hipSetDevice(p->device));
+        hipStream_t s = p->stream;
+        const int64_t total = p->n + n;
+        std::vector<int64_t> sizes, vsizes;
+        const bool filtered = p->filter.on;
+        grow(total, ids != nullptr);
+        if (ids) LB_HIP(hipMemcpyAsync(P.d_ids.get() + p->n, ids, (size_t)n * 8, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
+        // 1. the new rows, a piece at a time: their lists, and what the handle stores of them
+        const int64_t piece = std::min(n, piece_cap);
+        lab.reset(p->device, ivf_assign_bytes(piece));
+        for (int64_t r0 = 0; r0 < n; r0 += piece) {
+            const int64_t cnt = std::min(piece, n - r0);
+            const float *d_rows = rows(r0, cnt, piece, s);
+            if (const int rc = ivf_assign(p, P, p->n + r0, cnt, d_rows, lab, s)) return rc;
+            store(d_rows, r0, cnt, piece, s);
+            if (r0 + piece < n) {
+                LB_LAUNCH_CHECK();
+                LB_HIP(hipStreamSynchronize(s));
+            }
+        }
+        // 2. the lists of all rows, and what the handle derives from them, into the pair not in use
+        const int nxt = 1 - P.cur;
+        ivf_add_live(p, total, s); // (a handle that has removed rows: the new ones are live)
+        ivf_sort_lists(p, P, total, hist, s);
+        relist(nxt, total, s);
+        if (const int rc = ivf_read_lists(p, P, total, sizes, s)) return rc;
+        // 3. under a filter the new rows are visible: the visible lists of all rows, from the new lists, into the pair not in use
+        //    (the mask bytes behind the stored rows belong to nobody until the commit)
+        const int64_t nvis = filtered ? ivf_add_visible(p, total, vis, vsizes, s) : 0;
+        // 4. commit, in this order; nothing below throws
+        if (filtered) ivf_commit_visible(p, vsizes, nvis);
+        P.h_sizes.swap(sizes);
+        P.cur = nxt;
+        P.has_ids = ids != nullptr;
+        p->n = total;
+        return LB_OK;
+    });
+}
+
+// What a code handle's rows() is: the caller's device rows as they are, or its host rows staged a piece at a time.
+struct IvfAddSource {
+    const float *vectors;
+    bool on_device;
+    int device, dims;
+    Lease vec; // (outside ivf_add's guard with the struct)
+    const float *operator()(int64_t r0, int64_t cnt, int64_t piece, hipStream_t s)
+    {
+        const float *src = vectors + (size_t)r0 * dims;
+        if (on_device) return src;
+        if (r0 == 0) vec.reset(device, (size_t)piece * dims * 4);
+        LB_HIP(hipMemcpyAsync(vec.p, src, (size_t)cnt * dims * 4, hipMemcpyHostToDevice, s));
+        return vec.as<float>();
+    }
+};
 
 // lb_remove.h's `ready`: the live bytes (allocated by the first removal), the mask as the kernel will clear it (without one in
 // force, "every row" is written first) and every buffer of the rebuild behind the kernel, so that once bytes are cleared nothing
@@ -556,32 +681,17 @@ template <class Rows, class Relist> int ivf_compact(IvfHandle *p, Rows &&rows, s
     });
 }
 
-// ---- the search loop --------------------------------------------------------------------------------------------------------
-// Exact k-NN of nq device-resident queries among the rows of their probed lists, the lists being L with `sizes`; the caller holds
-// the reader lock, has made the device current and has checked the arguments.  `a` comes with the handle's own fields set.  The
-// scratch is leased into the caller's `sc`.  Per batch: the probes, launch_ivf_plan, the handle's middle steps, the selection.
-//   extra(c, a, nb)               take()s the handle's scratch pieces for a batch of nb queries from the Carve c (it runs twice)
-//   middle(a, maxlen, poll, next) enqueues what fills a.keys; poll() is false once ctx fired, next() ends a timing slot and then
-//                                 polls; after either's false it enqueues nothing more and returns false.  maxlen: the longest list
-// timing[slots] (under err_mu) gets the ms of a profiled search summed over its batches: probes, plan (up to middle's first next()),
-// a slot per further next(), selection.  Profiling costs a drain per batch.  batch_cap: queries per batch at most, for a handle
-// whose own scratch grows with the batch (the residual IVF-PQ handle's tables); the others leave it at kQueryBatch.  select: the
-// selection's launcher, for a handle whose keys are not pack_entry's (the IVF-SQ8 handle's integer keys); launch_ivf_select's
-// arguments and meaning.  filter: a row bitmap given with this call (IvfCallFilter; the IVF-Flat handle's *_bitmap entry points).
-// When it is on, the scratch also takes the synthetic lists of a batch (lb_ivf.h: offsets, probes and 4 bytes of rows per key), and
-// behind the probes of each batch launch_ivf_call_lists compacts the probed lists of L under the bitmap; the plan, the middle
-// steps and the selection are handed those lists and probes in place of L and the coarse search's.  Its launches fall into the
-// plan's timing slot, the host keeps sizing by `sizes`, and nothing comes back to it in between.
-// The shared form: under ONE bitmap (stride 0), when the call's nq * pmax exceeds the rows of all lists of L, the per-slot form
-// would walk more list positions than L holds.  Then every list of L is compacted once, in the first batch behind its probes (the
-// plan's slot of that batch): launch_ivf_call_lists over one pseudo-query that probes lists 0 .. nlist - 1, pmax being the rows of
-// all lists, which leaves list l as synthetic list 2 l; each batch only renames its probes (launch_ivf_call_shared_probes).  The
-// rule is the host's, from numbers it has; the synthetic list of a probe holds the same entries in the same order in both forms,
-// so the result does not depend on which ran.  extra() and a handle's middle steps still find the coarse search's probes where
-// the batch pointed at layout time (the residual IVF-PQ handle subtracts the centroid of the list probed).
-// mode, rowof, rowof_len: what the entries of L are (lb_ivf.h, IVF_CALL_*), filled by call_filter from the handle.
-// call_rows: set by ivf_search before each batch's middle steps to the entries of the synthetic lists' row array, for a handle
-// whose scan bounds a list entry by it (the `_visible` scans of IVF-PQ: nvis).
+// ---- a row bitmap given with the search call ------------------------------------------------------------------------------
+// The bitmap as an entry point got it: host or device memory, one bit per row position, least significant bit first.  Without
+// `bits` there is none: the plain search.
+struct CallBitmap {
+    const uint8_t *bits = nullptr;
+    int64_t nbits = 0, stride = 0;
+    bool on_device = false;
+};
+
+// The call's filter as the search loop takes it.  mode, rowof, rowof_len: what the entries of the handle's lists are (lb_ivf.h,
+// IVF_CALL_*), filled by call_filter from the handle.
 struct IvfCallFilter {
     const uint8_t *d_bits = nullptr; // device memory; query q of the call reads d_bits + q stride
     int64_t stride = 0, nbits = 0;
@@ -589,19 +699,11 @@ struct IvfCallFilter {
     int mode = IVF_CALL_ROWS;
     const uint32_t *rowof = nullptr;
     uint32_t rowof_len = 0;
-    mutable int64_t call_rows = 0;
-};
-
-// The bitmap as an entry point got it: host or device memory, one bit per row position, least significant bit first.
-struct CallBitmap {
-    const uint8_t *bits;
-    int64_t nbits, stride;
-    bool on_device;
 };
 
 // The call's filter from its bitmap, under the reader lock and before anything is launched: the refusals (set_filter's n != ntotal
 // rule, and the stride), then a host bitmap's bytes go into `lease` (the caller's, declared outside its guard) ahead of the
-// search on s.  A NULL bitmap is no filter: the plain search.
+// search on s.
 inline int call_filter(IvfHandle *p, int64_t nq, const CallBitmap &b, Lease &lease, hipStream_t s, IvfCallFilter &f)
 {
     f = IvfCallFilter{};
@@ -635,75 +737,187 @@ inline int call_filter(IvfHandle *p, int64_t nq, const CallBitmap &b, Lease &lea
     return LB_OK;
 }
 
+// The call's lists in the search loop: the probed lists of the handle's lists L, compacted under the bitmap into synthetic lists
+// (lb_ivf.h: offsets, probes and 4 bytes of rows per key) that the plan, the middle steps and the selection walk in place of L and
+// of the coarse search's probes.  The host keeps sizing by the sizes of L, and nothing comes back to it in between.
+// The per-slot form: behind the probes of each batch launch_ivf_call_lists compacts the lists that batch probes.
+// The shared form: under ONE bitmap (stride 0), when the call's nq * pmax exceeds the rows of all lists of L, the per-slot form
+// would walk more list positions than L holds.  Then every list of L is compacted once, in the first batch: launch_ivf_call_lists
+// over one pseudo-query that probes lists 0 .. nlist - 1, pmax being the rows of all lists (at least 1), which leaves list l as
+// synthetic list 2 l; each batch only renames its probes (launch_ivf_call_shared_probes).  The rule is the host's, from numbers it
+// has; the synthetic list of a probe holds the same entries in the same order in both forms, so the result does not depend on
+// which ran.
+struct IvfCallWalk {
+    const IvfCallFilter &f;
+    bool shared = false;
+    int64_t all_rows = 1;
+    IvfCallLists cl{};
+    int64_t *d_ident = nullptr, *d_renamed = nullptr; // shared: the pseudo-query's probes; a batch's renamed probes
+
+    // n: the handle's rows (both list arrays hold room for every row, all of it written or allocated)
+    IvfCallWalk(const IvfCallFilter &filter, const IvfLists &L, const std::vector<int64_t> &sizes, int64_t n, int64_t nq, int64_t pmax) : f(filter)
+    {
+        if (!f.on) return;
+        int64_t rows = 0;
+        for (const int64_t v : sizes) rows += v;
+        shared = f.stride == 0 && nq * pmax > rows;
+        all_rows = std::max<int64_t>(rows, 1);
+        cl.L = L;
+        cl.rows_len = (uint32_t)n;
+        cl.mode = f.mode;
+        cl.rowof = f.rowof;
+        cl.rowof_len = f.rowof_len;
+        cl.stride = f.stride;
+        cl.nbits = f.nbits;
+    }
+    // the synthetic lists' pieces of the scratch, for batches of nb queries at np probes
+    void layout(Carve &c, int64_t nb, int np, int64_t pmax)
+    {
+        const size_t nlist = (size_t)cl.L.nlist;
+        if (shared) {
+            cl.soff = c.take<uint32_t>((nlist * 2 + 1) * 4);
+            cl.sprobes = c.take<int64_t>(nlist * 8);
+            d_ident = c.take<int64_t>(nlist * 8);
+            d_renamed = c.take<int64_t>((size_t)nb * np * 8);
+            cl.srows = c.take<uint32_t>((size_t)all_rows * 4);
+        } else if (f.on) {
+            cl.soff = c.take<uint32_t>(((size_t)nb * np * 2 + 1) * 4);
+            cl.sprobes = c.take<int64_t>((size_t)nb * np * 8);
+            cl.srows = c.take<uint32_t>((size_t)nb * pmax * 4);
+        }
+    }
+    // Enqueues the lists of the batch `a` (its queries from q0 of the call on, d_probes the coarse search's) and points a.L and
+    // a.probes at them; -> the entries of their row array
+    int64_t batch(IvfBatch &a, int64_t q0, const int64_t *d_probes, hipStream_t s)
+    {
+        if (shared) { // every list once, in the first batch; then this batch's probes by the lists' new numbers
+            if (q0 == 0) {
+                cl.probes = d_ident;
+                cl.nq = 1;
+                cl.np = cl.L.nlist;
+                cl.pmax = all_rows;
+                cl.bits = f.d_bits;
+                launch_ivf_all_probes(d_ident, 1, cl.L.nlist, s);
+                launch_ivf_call_lists(cl, s);
+            }
+            launch_ivf_call_shared_probes(d_probes, (int64_t)a.nq * a.np, cl.L.nlist, d_renamed, s);
+            a.probes = d_renamed;
+        } else { // the probed lists of this batch, slot by slot
+            cl.probes = d_probes;
+            cl.nq = a.nq;
+            cl.np = a.np;
+            cl.pmax = a.pmax;
+            cl.bits = f.d_bits + (size_t)q0 * f.stride;
+            launch_ivf_call_lists(cl, s);
+            a.probes = cl.sprobes;
+        }
+        a.L = cl.lists();
+        return shared ? all_rows : (int64_t)a.nq * a.pmax;
+    }
+};
+
+// ---- the search loop --------------------------------------------------------------------------------------------------------
+// One search call: nq device-resident queries of element type Q, k, nprobe, where the results go, the stream, the context, the
+// lease the scratch goes into (the caller's, declared outside its guard) and the call's filter.
+template <class Q> struct IvfCallOf {
+    int64_t nq;
+    const Q *queries;
+    int k, nprobe;
+    float *dist;
+    int64_t *labels;
+    hipStream_t s;
+    const lb_cancel *ctx;
+    Lease &sc;
+    IvfCallFilter filter;
+};
+using IvfCall = IvfCallOf<float>; // what the loop takes: every handle's coarse search reads f32 queries
+
+// A handle's fixed choices.  timing[slots] (under err_mu) gets the ms of a profiled search summed over its batches: probes, plan
+// (up to middle's first next()), a slot per further next(), selection.  batch_cap: queries per batch at most, for a handle whose own
+// scratch grows with the batch (the residual IVF-PQ handle's tables).  select: the selection's launcher, for a handle whose keys
+// are not pack_entry's (the integer keys of IVF-SQ8 and IVF-BQ); launch_ivf_select's arguments and meaning.
 using IvfSelectFn = void (*)(const IvfBatch &, int, const int64_t *, float *, int64_t *, hipStream_t);
-template <class Extra, class Middle>
-int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vector<int64_t> &sizes, IvfBatch a, int64_t nq, const float *d_Q,
-               int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s, const lb_cancel *ctx, Lease &sc, float *timing, int slots,
-               Extra &&extra, Middle &&middle, int64_t batch_cap = kQueryBatch, IvfSelectFn select = launch_ivf_select,
-               const IvfCallFilter &filter = IvfCallFilter{})
+struct IvfSearchForm {
+    float *timing;
+    int slots;
+    int64_t batch_cap = kQueryBatch;
+    IvfSelectFn select = launch_ivf_select;
+};
+
+// What a batch's middle steps are told beside the batch itself
+struct IvfWalk {
+    int64_t maxlen;        // the longest list of the handle
+    bool subset;           // the batch walks other lists than those of all rows: the visible ones, or the call's
+    int64_t entries;       // the entries of the row array behind the lists it walks; with `positions` they are positions, which a
+                           // scan bounds by this (the `_visible` scans' nvis)
+    IvfLists own;          // the handle's lists and the coarse search's probes, whatever the batch walks (the residual IVF-PQ handle
+    const int64_t *probes; // subtracts the centroid of the list probed)
+};
+
+// Exact k-NN of the call's queries among the rows of their probed lists, the lists being h->lists(); the caller holds the reader
+// lock, has made the device current and has checked the arguments.  Per batch: the probes, the call's lists if it has a filter,
+// launch_ivf_plan, the handle's middle steps, the selection.
+//   extra(c, a, nb)           sets the handle's own fields of the batch a (a.D is set) and take()s its scratch pieces for a batch
+//                             of nb queries from the Carve c (it runs twice)
+//   middle(a, w, poll, next)  enqueues what fills a.keys; poll() is false once ctx fired, next() ends a timing slot and then polls;
+//                             after either's false it enqueues nothing more and returns false
+// Profiling costs a drain per batch.  The launches of the call's lists fall into the plan's timing slot.
+template <class Extra, class Middle> int ivf_search(IvfHandle *h, const IvfCall &c, const IvfSearchForm &form, Extra &&extra, Middle &&middle)
 {
+    if (const int st = ivf_live_ok(h)) return st;
+    IvfPartition &P = h->part;
+    const std::vector<int64_t> &sizes = h->sizes();
+    const int64_t nq = c.nq;
+    hipStream_t s = c.s;
     int64_t st[4] = {nq, 0, 0, 0};
     auto publish = [&]() {
         std::lock_guard<std::mutex> g(h->err_mu);
         std::copy(st, st + 4, P.stats);
     };
     if (h->n == 0) { // all padding, without a launch
-        LB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_dist), 0x7f7fffff /* FLT_MAX */, (size_t)nq * k, s));
-        LB_HIP(hipMemsetAsync(d_labels, 0xff, (size_t)nq * k * 8, s));
+        LB_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(c.dist), 0x7f7fffff /* FLT_MAX */, (size_t)nq * c.k, s));
+        LB_HIP(hipMemsetAsync(c.labels, 0xff, (size_t)nq * c.k * 8, s));
         LB_HIP(hipStreamSynchronize(s));
         publish();
         return LB_OK;
     }
-    const int np = std::min(nprobe, P.nlist);
+    const int np = std::min(c.nprobe, P.nlist);
     // pmax: the rows a query can scan at most, the sum of the np largest lists
     std::vector<int64_t> big(sizes);
     std::partial_sort(big.begin(), big.begin() + np, big.end(), std::greater<int64_t>());
     int64_t pmax = 0;
     for (int i = 0; i < np; i++) pmax += big[i];
-    const int64_t maxlen = big[0];
     pmax = std::max<int64_t>(pmax, 1);
-    const int64_t nb = std::min(std::min(nq, std::max<int64_t>(1, std::min(batch_cap, kQueryBatch))), std::max<int64_t>(1, kKeyScratch / 8 / pmax));
-    a.L = L;
+    const int64_t nb = std::min(std::min(nq, std::max<int64_t>(1, std::min(form.batch_cap, kQueryBatch))), std::max<int64_t>(1, kKeyScratch / 8 / pmax));
+    IvfBatch a{};
+    a.D = h->dims;
+    a.L = h->lists();
     a.np = np;
     a.pmax = pmax;
+    IvfWalk w{big[0], h->filter.on, h->filter.on ? h->filter.n_visible : h->n, a.L, nullptr};
+    IvfCallWalk calls(c.filter, a.L, sizes, h->n, nq, pmax);
     int64_t *d_probes = nullptr;
     float *d_pdist = nullptr;
     unsigned long long *d_stats = nullptr;
-    IvfCallLists cl{};
-    // the shared form's rule, and the rows of all lists of L (at least 1: the pseudo-query's pmax)
-    int64_t all_rows = 0;
-    for (const int64_t v : sizes) all_rows += v;
-    const bool shared = filter.on && filter.stride == 0 && nq * pmax > all_rows;
-    all_rows = std::max<int64_t>(all_rows, 1);
-    int64_t *d_ident = nullptr, *d_probes2 = nullptr; // shared: the pseudo-query's probes; a batch's renamed probes
-    auto layout = [&](Carve c) {
-        a.probes = d_probes = c.take<int64_t>((size_t)nb * np * 8);
-        d_pdist = c.take<float>((size_t)nb * np * 4);
-        a.seg = c.take<uint32_t>((size_t)nb * (np + 1) * 4);
-        d_stats = c.take<unsigned long long>(4 * 8);
-        if (shared) {
-            cl.soff = c.take<uint32_t>(((size_t)P.nlist * 2 + 1) * 4);
-            cl.sprobes = c.take<int64_t>((size_t)P.nlist * 8);
-            d_ident = c.take<int64_t>((size_t)P.nlist * 8);
-            d_probes2 = c.take<int64_t>((size_t)nb * np * 8);
-            cl.srows = c.take<uint32_t>((size_t)all_rows * 4);
-        } else if (filter.on) {
-            cl.soff = c.take<uint32_t>(((size_t)nb * np * 2 + 1) * 4);
-            cl.sprobes = c.take<int64_t>((size_t)nb * np * 8);
-            cl.srows = c.take<uint32_t>((size_t)nb * pmax * 4);
-        }
-        extra(c, a, nb);
-        a.keys = c.take<uint64_t>((size_t)nb * pmax * 8);
-        return c.off;
+    auto layout = [&](Carve cv) {
+        a.probes = w.probes = d_probes = cv.take<int64_t>((size_t)nb * np * 8);
+        d_pdist = cv.take<float>((size_t)nb * np * 4);
+        a.seg = cv.take<uint32_t>((size_t)nb * (np + 1) * 4);
+        d_stats = cv.take<unsigned long long>(4 * 8);
+        calls.layout(cv, nb, np, pmax);
+        extra(cv, a, nb);
+        a.keys = cv.take<uint64_t>((size_t)nb * pmax * 8);
+        return cv.off;
     };
-    lease_layout(sc, h->device, layout);
+    lease_layout(c.sc, h->device, layout);
     int cancelled = 0;
     auto go = [&]() { // false: the context fired, nothing more is enqueued
-        cancelled = ctx_state(ctx);
+        cancelled = ctx_state(c.ctx);
         return cancelled == 0;
     };
     if (go()) LB_HIP(hipMemsetAsync(d_stats, 0, 4 * 8, s));
     const bool prof = P.profiling.load();
+    const int slots = form.slots;
     EventH ev[kMaxTimingSlots + 1];
     float tms[kMaxTimingSlots] = {0, 0, 0, 0, 0};
     if (prof)
@@ -713,52 +927,23 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
     auto next = [&]() { mark(); return go(); };
     for (int64_t q0 = 0; q0 < nq && !cancelled; q0 += nb) {
         a.nq = (int)std::min(nb, nq - q0);
-        a.Q = d_Q + (size_t)q0 * h->dims;
+        a.Q = c.queries + (size_t)q0 * h->dims;
         e = 0;
         mark();
         // the probes (the inner index polls ctx before its own launches).  More than LB_MAX_K of them is more than the coarse
         // search returns: with every list probed they are all the lists, and their order does not reach the result
         if (np == P.nlist && np > LB_MAX_K) launch_ivf_all_probes(d_probes, a.nq, np, s);
-        else if (const int rc = lb_gpu_index_search_device_ctx(P.coarse, a.nq, a.Q, np, d_pdist, d_probes, s, ctx)) return coarse_fail(h, P, rc, s);
+        else if (const int rc = lb_gpu_index_search_device_ctx(P.coarse, a.nq, a.Q, np, d_pdist, d_probes, s, c.ctx)) return coarse_fail(h, P, rc, s);
         if (!next()) break;
-        if (filter.on) { // the lists under the call's bitmap, then everything below walks those
-            cl.L = L;
-            cl.rows_len = (uint32_t)h->n; // (both list arrays hold room for every row, all of it written or allocated)
-            cl.mode = filter.mode;
-            cl.rowof = filter.rowof;
-            cl.rowof_len = filter.rowof_len;
-            cl.stride = filter.stride;
-            cl.nbits = filter.nbits;
+        if (c.filter.on) { // the lists under the call's bitmap: everything below walks those
             if (!go()) break;
-            if (shared) { // every list once, in the first batch; then this batch's probes by the lists' new numbers
-                if (q0 == 0) {
-                    cl.probes = d_ident;
-                    cl.nq = 1;
-                    cl.np = P.nlist;
-                    cl.pmax = all_rows;
-                    cl.bits = filter.d_bits;
-                    launch_ivf_all_probes(d_ident, 1, P.nlist, s);
-                    launch_ivf_call_lists(cl, s);
-                }
-                launch_ivf_call_shared_probes(d_probes, (int64_t)a.nq * np, P.nlist, d_probes2, s);
-                a.probes = d_probes2;
-                filter.call_rows = all_rows;
-            } else { // the probed lists of this batch, slot by slot
-                cl.probes = d_probes;
-                cl.nq = a.nq;
-                cl.np = np;
-                cl.pmax = pmax;
-                cl.bits = filter.d_bits + (size_t)q0 * filter.stride;
-                launch_ivf_call_lists(cl, s);
-                a.probes = cl.sprobes;
-                filter.call_rows = (int64_t)a.nq * pmax;
-            }
-            a.L = cl.lists();
+            w.subset = true;
+            w.entries = calls.batch(a, q0, d_probes, s);
         }
         launch_ivf_plan(a, d_stats, s);
-        if (!middle(a, maxlen, go, next)) break;
+        if (!middle(a, w, go, next)) break;
         if (!next()) break;
-        select(a, k, P.has_ids ? P.d_ids.get() : nullptr, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, s);
+        form.select(a, c.k, P.has_ids ? P.d_ids.get() : nullptr, c.dist + (size_t)q0 * c.k, c.labels + (size_t)q0 * c.k, s);
         mark();
         if (prof) {
             LB_HIP(hipEventSynchronize(ev[slots]));
@@ -778,14 +963,14 @@ int ivf_search(CodeHandle *h, IvfPartition &P, const IvfLists &L, const std::vec
     publish();
     if (prof) {
         std::lock_guard<std::mutex> g(h->err_mu);
-        std::copy(tms, tms + slots, timing);
+        std::copy(tms, tms + slots, form.timing);
     }
     return LB_OK;
 }
 
 // ---- the entry points -------------------------------------------------------------------------------------------------------
-// T: a handle with `part` and `timing[]`.  dev(p, nq, d_Q, k, nprobe, d_dist, d_labels, s, ctx, sc) is the handle's call of
-// ivf_search.  Argument checks answer before a device is touched.
+// T: a handle with `part` and `timing[]`.  dev(p, c) is the handle's call of ivf_search for the call c (an IvfCallOf<Q>).  Argument
+// checks answer before a device is touched.
 template <class T>
 int ivf_search_args(T *p, int64_t nq, const void *queries, int k, int nprobe, const void *dist, const void *labels, const lb_cancel *ctx)
 {
@@ -803,31 +988,44 @@ int ivf_search_args(T *p, int64_t nq, const void *queries, int k, int nprobe, co
     });
 }
 
-template <class T, class Q, class Dev> // Q: the queries' element type, f32 but for the IVF-Flat handle over int8 rows
+// the call as a record, its filter from the bitmap (`bits`: the caller's lease, declared outside its guard), then the handle's search
+template <class T, class Q, class Dev>
+int ivf_search_call(T *p, int64_t nq, const Q *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels, hipStream_t s, const lb_cancel *ctx,
+                    Lease &sc, const CallBitmap &bitmap, Lease &bits, Dev &&dev)
+{
+    IvfCallOf<Q> c{nq, d_queries, k, nprobe, d_dist, d_labels, s, ctx, sc, {}};
+    if (const int st = call_filter(p, nq, bitmap, bits, s, c.filter)) return st;
+    return dev(p, c);
+}
+
+// Q: the queries' element type, f32 but for the IVF-Flat handle over int8 rows.  bitmap: a row bitmap given with the call, if any
+template <class T, class Q, class Dev>
 int ivf_search_device_ctx(T *p, int64_t nq, const Q *d_queries, int k, int nprobe, float *d_dist, int64_t *d_labels, void *stream,
-                          const lb_cancel *ctx, Dev &&dev)
+                          const lb_cancel *ctx, Dev &&dev, const CallBitmap &bitmap = CallBitmap{})
 {
     const int rc = ivf_search_args(p, nq, d_queries, k, nprobe, d_dist, d_labels, ctx);
     if (rc != LB_OK || nq == 0) return rc;
     std::shared_lock<std::shared_mutex> g(p->mu);
     hipStream_t s = stream ? (hipStream_t)stream : p->stream;
-    Lease sc;
+    Lease sc, bits;
     return guard(p, s, [&]() -> int {
         LB_HIP(hipSetDevice(p->device));
-        return dev(p, nq, d_queries, k, nprobe, d_dist, d_labels, s, ctx, sc);
+        return ivf_search_call(p, nq, d_queries, k, nprobe, d_dist, d_labels, s, ctx, sc, bitmap, bits, dev);
     });
 }
 
 template <class T, class Q, class Dev>
-int ivf_search_ctx(T *p, int64_t nq, const Q *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx, Dev &&dev)
+int ivf_search_ctx(T *p, int64_t nq, const Q *queries, int k, int nprobe, float *dist, int64_t *labels, const lb_cancel *ctx, Dev &&dev,
+                   const CallBitmap &bitmap = CallBitmap{})
 {
     const int rc = ivf_search_args(p, nq, queries, k, nprobe, dist, labels, ctx);
     if (rc != LB_OK || nq == 0) return rc;
+    Lease bits;
     return host_knn(
         p, nq, (size_t)p->dims * sizeof(Q), k, dist, labels,
         [&](Lease &dq, Lease &, hipStream_t s) { LB_HIP(hipMemcpyAsync(dq.p, queries, (size_t)nq * p->dims * sizeof(Q), hipMemcpyHostToDevice, s)); },
         [&](Lease &dq, float *d_dist, int64_t *d_labels, hipStream_t s, Lease &sc) {
-            return dev(p, nq, dq.as<Q>(), k, nprobe, d_dist, d_labels, s, ctx, sc);
+            return ivf_search_call(p, nq, dq.as<Q>(), k, nprobe, d_dist, d_labels, s, ctx, sc, bitmap, bits, dev);
         });
 }
 

@@ -10,6 +10,7 @@ import pytest
 
 from tests import bq_oracle as bo
 from tests import ivfbq_oracle as bqo
+from tests import ivf_piece_cases as pc
 from tests import refine_oracle as fo
 from tests import row_view_cases as rv
 from tests.gpu_util import assert_same, gpu_or_skip
@@ -470,3 +471,19 @@ def test_python_front_end(parity):
     assert_same(*t.search(Q, 5, 8), *enc.search(Q, 5), "trained, every list probed")
     enc.Close()
     t.Close()
+
+
+# the shared add across two pieces (tests/ivf_piece_cases.py) ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def two_pieces(oracle):
+    """the case, a maker of empty handles over it, the snapshot of one filled by small adds and the oracle's assignment"""
+    gpu_or_skip()
+    X, ids, C_, Q = pc.case()
+    new = lambda: _handle(X[:0], C_)
+    return X, ids, Q, new, pc.reference(new, X, ids, Q), bqo.assign(oracle, 0, X, C_)
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_one_add_across_pieces(two_pieces, device):
+    X, ids, Q, new, want, lists = two_pieces
+    pc.check_one_add(new, X, ids, Q, want, lists, device)

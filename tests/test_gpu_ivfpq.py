@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import ivfpq_oracle as pqo
+from tests import ivf_piece_cases as pc
 from tests.gpu_util import assert_same, gpu_or_skip
 
 pytestmark = pytest.mark.gpu
@@ -371,3 +372,21 @@ def test_python_front_end(parity):
     assert_same(*t.search(Q, 5, 8), *enc.Search(Q, 5), "trained, every list probed")
     enc.Close()
     t.Close()
+
+
+# the shared add across two pieces (tests/ivf_piece_cases.py) ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def two_pieces(oracle):
+    """the case with random codebooks (M = 128: the most subspaces that divide 8192 within the table limit), a maker of empty
+    handles over it, the snapshot of one filled by small adds and the oracle's assignment"""
+    gpu_or_skip()
+    X, ids, C_, Q = pc.case()
+    cb = np.random.default_rng(21).standard_normal((128, 256, pc.DIMS // 128)).astype(F) * F(0.3)
+    new = lambda: _handle(X[:0], C_, cb)
+    return X, ids, Q, new, pc.reference(new, X, ids, Q), pqo.assign(oracle, 0, X, C_)
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_one_add_across_pieces(two_pieces, device):
+    X, ids, Q, new, want, lists = two_pieces
+    pc.check_one_add(new, X, ids, Q, want, lists, device)

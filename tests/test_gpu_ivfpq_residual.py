@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import ivf_oracle as io
+from tests import ivf_piece_cases as pc
 from tests import ivfpq_oracle as pqo
 from tests import ivfpq_residual_oracle as ro
 from tests import row_view_cases as rv
@@ -404,3 +405,21 @@ def test_refusals_and_the_untouched_plain_path(oracle, parity):
     el, ed = e.search(Q, 7, 2)
     assert (el == -1).all() and (ed == pqo.FLT_MAX).all() and e.last_search_stats() == (Q.shape[0], 0, 0, 0)
     e.Close()
+
+
+# the shared add across two pieces (tests/ivf_piece_cases.py) ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def two_pieces(oracle):
+    """the case with random codebooks (M = 128: the most subspaces that divide 8192 within the table limit), a maker of empty
+    handles over it, the snapshot of one filled by small adds and the oracle's assignment"""
+    gpu_or_skip()
+    X, ids, C_, Q = pc.case()
+    cb = np.random.default_rng(21).standard_normal((128, 256, pc.DIMS // 128)).astype(F) * F(0.3)
+    new = lambda: _handle(X[:0], C_, cb)
+    return X, ids, Q, new, pc.reference(new, X, ids, Q), pqo.assign(oracle, 0, X, C_)
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_one_add_across_pieces(two_pieces, device):
+    X, ids, Q, new, want, lists = two_pieces
+    pc.check_one_add(new, X, ids, Q, want, lists, device)

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests import ivfsq8_oracle as sqo
+from tests import ivf_piece_cases as pc
 from tests import refine_oracle as fo
 from tests import row_view_cases as rv
 from tests import sq8_oracle as so
@@ -533,3 +534,45 @@ def test_python_front_end(parity):
     assert_same(*t.search(Q, 5, 8), *enc.search(Q, 5), "trained, every list probed")
     enc.Close()
     t.Close()
+
+
+# the shared add across two pieces (tests/ivf_piece_cases.py) ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def two_pieces(oracle):
+    """the case, a maker of empty handles over it, the snapshot of one filled by small adds and the oracle's assignment"""
+    gpu_or_skip()
+    X, ids, C_, Q = pc.case()
+    mn, mx = X.min(axis=0), X.max(axis=0)
+    new = lambda: _handle(X[:0], C_, mn, mx)
+    return X, ids, Q, new, pc.reference(new, X, ids, Q), sqo.assign(oracle, 0, X, C_)
+
+
+@pytest.mark.parametrize("device", [False, True])
+def test_one_add_across_pieces(two_pieces, device):
+    X, ids, Q, new, want, lists = two_pieces
+    pc.check_one_add(new, X, ids, Q, want, lists, device)
+
+
+def test_one_add_across_pieces_under_a_filter_and_removals(two_pieces):
+    """the add's tail is the shared one whatever the pieces: onto 300 rows under a filter that hides a third of them, three rows
+    removed, the one add of two pieces leaves what adds of single pieces leave"""
+    X, ids, Q, new, _, _ = two_pieces
+    first = ids[:300] + 1  # (ids of their own: those of the case are multiples of 3 above 2^40)
+    mask = (np.arange(300) % 3 != 0).astype(np.uint8)
+
+    def run(step):
+        h = new()
+        h.add(X[:300], first)
+        h.set_filter(mask)
+        assert h.remove(first[[4, 100, 299]]) == 3  # (rows the filter shows)
+        pc.fill(h, X, ids, step)
+        out = (h.ntotal, h.nvisible(), h.nlive(), h.ndeleted(), h.list_sizes(), *h.search(Q, pc.K, pc.NPROBE))
+        h.Close()
+        return out
+
+    got, want = run(pc.N), run(pc.SMALL)
+    assert got[:4] == want[:4] == (300 + pc.N, 200 - 3 + pc.N, 300 - 3 + pc.N, 3), (got[:4], want[:4])
+    assert np.array_equal(got[4], want[4])
+    assert_same(got[5], got[6], want[5], want[6], "one add against single pieces")
+    hidden = np.concatenate((first[::3], first[[4, 100, 299]]))
+    assert (got[5] >= 0).all() and not np.isin(got[5], hidden).any()
