@@ -168,7 +168,7 @@ int lb_gpu_index_search_device(lb_gpu_index *h, int64_t nq, const float *d_queri
  * return LB_ERR_UNSUPPORTED.  An f32 add / search on an F16 handle, or an _f16 call on an f32 handle, is LB_ERR_INVALID_ARG
  * with a last_error text.  _f16 host searches are not combined. */
 lb_gpu_index *lb_gpu_index_new_f16(int device, int dim, int metric, int *out_status);
-int lb_gpu_index_dtype(const lb_gpu_index *h); /* 0 float32, 1 float16, 2 int8 (simd.DataType, internal/simd/registry.go) */
+int lb_gpu_index_dtype(const lb_gpu_index *h); /* 0 float32, 1 float16, 2 int8, 3 uint8 (simd.DataType, internal/simd/registry.go) */
 int lb_gpu_index_add_f16(lb_gpu_index *h, int64_t n, const uint16_t *vectors, const int64_t *ids);
 int lb_gpu_index_add_f16_device(lb_gpu_index *h, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids);
 /* HBM the index holds now: rows (as mapped / allocated), the per-row side arrays, the row list and any accelerator image */
@@ -221,6 +221,39 @@ int lb_gpu_index_search_i8_ctx(lb_gpu_index *h, int64_t nq, const int8_t *querie
                                const lb_cancel *ctx);
 int lb_gpu_index_search_i8_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t *d_queries, int k, float *d_dist,
                                       int64_t *d_labels, void *stream, const lb_cancel *ctx);
+
+/* ---- uint8 indexes: VectorTypeUint8 (internal/store/types/types.go) -------------------------------------------------------
+ * Rows live in HBM as uint8, 1 byte per element, row-major; queries are uint8 too.  The one metric is Euclidean: the reference
+ * registers euclideanUint8Unrolled4x alone for the type (internal/simd/dispatch.go:250, simd_baseline.go:198-220), so cosine
+ * and dot are NULL / LB_ERR_UNSUPPORTED at creation (after the dimension checks, before the device is looked for).
+ *   arithmetic   four f32 chains over i mod 4, the tail elements into chain 0; each term d = float32(a_i) - float32(b_i), then
+ *                d * d, added without FMA; the chains added as ((s0 + s1) + s2) + s3 in f32; value float32(sqrt(float64(sum))).
+ *                Reported bit for bit, in ascending (distance, row) order like every flat index.
+ *   S <= 2^24    every term is an integer in [0, 65025], so every partial sum the reference forms is a non-negative integer no
+ *                larger than S = sum (a_i - b_i)^2.  While S <= 2^24 every f32 add is exact and the value is
+ *                sqrt_rn(float(S)); the kernels then work from the exact integer S = |x|^2 + |q|^2 - 2 x.q (v_dot4_u32_u8).
+ *                That is every pair for dim <= 258.  A pair with S > 2^24 is evaluated by the chain arithmetic itself, after a
+ *                test that drops it when even S (1 - (floor(dim / 4) + 6) 2^-24), a lower bound of the reference's sum, gives a
+ *                value that cannot enter the query's list.
+ * Searches take the exact uint8 scan for every batch size (last_route 82; dim % 16 != 0 or a misaligned base: one lane per
+ * pair, chain arithmetic throughout).  There is no matrix-core pass.  Everything else is the int8 handle's: reserve / ntotal /
+ * dim / set_filter / filter_* / nvisible / remove* / compact / last_* / profiling / hbm_bytes / free work as on an f32 handle;
+ * set_order is accepted and changes nothing; set_candidate_mode takes AUTO only (else LB_ERR_UNSUPPORTED); set_f16_image is
+ * accepted and has no effect; rerank, refine and comm searches return LB_ERR_UNSUPPORTED; dtype is 3.  A float32 / _f16 / _i8
+ * add or search on a uint8 handle, or a _u8 call on another, is LB_ERR_INVALID_ARG with a last_error text naming the handle's
+ * type.  _u8 host searches are not combined.  The two _bitmap forms are the call-bitmap searches described below. */
+lb_gpu_index *lb_gpu_index_new_u8(int device, int dim, int metric, int *out_status);
+int lb_gpu_index_add_u8(lb_gpu_index *h, int64_t n, const uint8_t *vectors, const int64_t *ids);
+int lb_gpu_index_add_u8_device(lb_gpu_index *h, int64_t n, const uint8_t *d_vectors, const int64_t *d_ids);
+int lb_gpu_index_search_u8(lb_gpu_index *h, int64_t nq, const uint8_t *queries, int k, float *dist, int64_t *labels);
+int lb_gpu_index_search_u8_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *queries, int k, float *dist, int64_t *labels,
+                               const lb_cancel *ctx);
+int lb_gpu_index_search_u8_device_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *d_queries, int k, float *d_dist,
+                                      int64_t *d_labels, void *stream, const lb_cancel *ctx);
+int lb_gpu_index_search_u8_bitmap_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                      float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_index_search_u8_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *d_queries, int k, const uint8_t *d_bitmap,
+                                             int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx);
 
 /* Metadata predicate mask for filtered search (SURVEY f-3; byte-per-row 0/1 as
  * internal/query/filter_evaluator.go:79-115 produces).  mask has ntotal bytes;

@@ -3,7 +3,8 @@
 Host-side mirror (Python, over ctypes) of the two reference interfaces the HIP
 library drops in behind:
 
-  longbow_amd.gpu   <->  internal/gpu   (Index{Add, Search, Close}, GPUConfig, NewIndex*)
+  longbow_amd.gpu   <->  internal/gpu   (Index{Add, Search, Close}, GPUConfig, NewIndex*); rows float32, float16, int8
+                         (GPUConfig.DataType) or uint8 (NewUint8Index)
   longbow_amd.simd  <->  internal/simd  (MetricType, *DistanceBatch*, ADCDistanceBatch)
   longbow_amd.pq    <->  internal/pq    (BuildADCTable, ADCDistanceBatch, codebook blob)
   longbow_amd.bq    <->  internal/store BQEncoder (sign-bit codes, Hamming distances) + exact Hamming k-NN

@@ -89,6 +89,14 @@ SIGNATURES = [
     ("lb_gpu_index_search_i8", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
     ("lb_gpu_index_search_i8_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
     ("lb_gpu_index_search_i8_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_index_new_u8", _vp, [_i, _i, _i, _ip]),
+    ("lb_gpu_index_add_u8", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_index_add_u8_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_index_search_u8", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_index_search_u8_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_u8_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_u8_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_index_search_u8_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_index_search_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp]),
     ("lb_gpu_index_search_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_index_search_f16_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _vp, _i64, _vp, _vp, _vp]),

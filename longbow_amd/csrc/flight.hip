@@ -33,8 +33,10 @@ namespace {
 #pragma weak lb_gpu_index_dtype
 #pragma weak lb_gpu_index_add_f16
 #pragma weak lb_gpu_index_add_i8
+#pragma weak lb_gpu_index_add_u8
 static bool index_is_f16(const lb_gpu_index *h) { return lb_gpu_index_dtype != nullptr && lb_gpu_index_dtype(h) == 1; }
 static bool index_is_i8(const lb_gpu_index *h) { return lb_gpu_index_dtype != nullptr && lb_gpu_index_dtype(h) == 2; }
+static bool index_is_u8(const lb_gpu_index *h) { return lb_gpu_index_dtype != nullptr && lb_gpu_index_dtype(h) == 3; }
 
 enum { GRPC_OK = 0, GRPC_INVALID_ARGUMENT = 3, GRPC_NOT_FOUND = 5, GRPC_FAILED_PRECONDITION = 9, GRPC_UNIMPLEMENTED = 12, GRPC_INTERNAL = 13,
        GRPC_UNAVAILABLE = 14 };
@@ -759,6 +761,7 @@ static int exchange_body(lb_flight_datasets *reg, const uint8_t *ipc_in, size_t 
     // (the exchange's query column is float32: a float16 or int8 dataset is not searched through it)
     if (index_is_f16(h)) return finish(err(GRPC_UNIMPLEMENTED, "vector search over a float16 dataset is not implemented"), errbuf, errcap);
     if (index_is_i8(h)) return finish(err(GRPC_UNIMPLEMENTED, "vector search over an int8 dataset is not implemented"), errbuf, errcap);
+    if (index_is_u8(h)) return finish(err(GRPC_UNIMPLEMENTED, "vector search over a uint8 dataset is not implemented"), errbuf, errcap);
     const int dim = lb_gpu_index_dim(h);
     if (qlen != dim) return finish(err(GRPC_INVALID_ARGUMENT, "dimension mismatch: expected %d, got %lld", dim, (long long)qlen), errbuf, errcap);
     if (k < 1) return finish(err(GRPC_INVALID_ARGUMENT, "k must be at least 1"), errbuf, errcap);
@@ -797,6 +800,7 @@ static int add_ipc_body(lb_gpu_index *h, const uint8_t *ipc, size_t len, int64_t
     const int dim = lb_gpu_index_dim(h);
     const bool f16 = index_is_f16(h);
     const bool i8 = index_is_i8(h);
+    const bool u8 = index_is_u8(h);
     std::vector<Field> fields;
     bool have_schema = false;
     int64_t added = 0;
@@ -831,6 +835,9 @@ static int add_ipc_body(lb_gpu_index *h, const uint8_t *ipc, size_t len, int64_t
         if (i8) {
             if (el.type != T_INT || el.bit_width != 8 || !el.is_signed)
                 return err(GRPC_INVALID_ARGUMENT, "'vector' elements must be int8 for an int8 index");
+        } else if (u8) {
+            if (el.type != T_INT || el.bit_width != 8 || el.is_signed)
+                return err(GRPC_INVALID_ARGUMENT, "'vector' elements must be uint8 for a uint8 index");
         } else if (el.type != T_FLOAT || el.precision != (f16 ? 0 : 1)) {
             return err(GRPC_INVALID_ARGUMENT, f16 ? "'vector' elements must be float16 for a float16 index"
                                                   : "'vector' elements must be float32 in this entry point");
@@ -838,7 +845,7 @@ static int add_ipc_body(lb_gpu_index *h, const uint8_t *ipc, size_t len, int64_t
         if (pos.node < b.nodes.size() && b.nodes[pos.node].nulls != 0) return err(GRPC_INVALID_ARGUMENT, "null vectors are not supported");
         // the column's FieldNodes must agree with the batch: `rows` lists, rows * dim child values
         int64_t nvals = 0, vbytes = 0;
-        if (!mul_i64(b.rows, dim, nvals) || !mul_i64(nvals, i8 ? 1 : f16 ? 2 : 4, vbytes)) return err(GRPC_INTERNAL, "'vector' values buffer is too short");
+        if (!mul_i64(b.rows, dim, nvals) || !mul_i64(nvals, (i8 || u8) ? 1 : f16 ? 2 : 4, vbytes)) return err(GRPC_INTERNAL, "'vector' values buffer is too short");
         if ((node_len(b, pos.node) >= 0 && node_len(b, pos.node) != b.rows) ||
             (node_len(b, pos.node + 1) >= 0 && node_len(b, pos.node + 1) != nvals))
             return err(GRPC_INTERNAL, "failed to read record: 'vector' lengths disagree with the batch");
@@ -866,7 +873,8 @@ static int add_ipc_body(lb_gpu_index *h, const uint8_t *ipc, size_t len, int64_t
         }
         // the values buffer goes to the library as it lies in the IPC body: no repacking
         const int64_t *idp = ids.empty() ? nullptr : ids.data();
-        const int rc = i8    ? lb_gpu_index_add_i8(h, b.rows, reinterpret_cast<const int8_t *>(vals), idp)
+        const int rc = u8    ? lb_gpu_index_add_u8(h, b.rows, vals, idp)
+                       : i8  ? lb_gpu_index_add_i8(h, b.rows, reinterpret_cast<const int8_t *>(vals), idp)
                        : f16 ? lb_gpu_index_add_f16(h, b.rows, reinterpret_cast<const uint16_t *>(vals), idp)
                              : lb_gpu_index_add(h, b.rows, reinterpret_cast<const float *>(vals), idp);
         if (rc != LB_OK) return err(rc == LB_ERR_NO_DEVICE ? GRPC_UNAVAILABLE : GRPC_INTERNAL, "add failed: %s (%s)", lb_gpu_status_string(rc), lb_gpu_last_error(h));

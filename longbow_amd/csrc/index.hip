@@ -195,7 +195,7 @@ static void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool 
     const int64_t start = h->n;
     if (h->i8_rows)
         launch_row_norms_i8(h->rows_i8() + (size_t)start * h->dim, n, h->dim, h->norm2_i8() + start, s);
-    else
+    else if (!h->u8_rows) // (a uint8 index keeps no norms: its scan forms |x|^2 as it reads the row)
         with_rows(h, [&](auto X) {
             launch_row_norms(X + (size_t)start * h->dim, n, h->dim, h->d_norm2.get() + start, h->d_rnorm.get() + start, h->d_maxnorm2.get(), s);
         });
@@ -237,7 +237,7 @@ static void finish_add(lb_gpu_index *h, int64_t n, const int64_t *ids_src, bool 
 // bring the split-bf16 mirror up to date with d_X (no-op unless the mode is enabled)
 void sync_split_image(lb_gpu_index *h)
 {
-    if (h->cand_mode.load() != 1 || h->dim % 32 != 0 || h->n == 0 || h->f16_rows || h->i8_rows) return;
+    if (h->cand_mode.load() != 1 || h->dim % 32 != 0 || h->n == 0 || h->f16_rows || h->byte_rows()) return;
     if (!h->d_Xs || h->xs_rows > h->n) {
         drop_split_image(h);
         h->d_Xs.alloc((size_t)h->capacity * h->dim);
@@ -264,8 +264,8 @@ void sync_f16_image(lb_gpu_index *h)
     const bool l2 = h->metric == LB_METRIC_EUCLIDEAN;
     // (L2: the image is centred, so what must fit fp16 are the centred norms -- known once the centre is)
     const bool range_ok = l2 ? (!h->nonfinite && (h->xh_declined_n == 0 || h->n >= 2 * h->xh_declined_n)) : h->f16_ok;
-    // (an int8 index has no image: its searches read the int8 rows)
-    const bool want = h->xh_mode.load() != 0 && !h->xh_failed && !h->i8_rows && range_ok && h->n > 0 &&
+    // (an int8 or uint8 index has no image: its searches read the one-byte rows)
+    const bool want = h->xh_mode.load() != 0 && !h->xh_failed && !h->byte_rows() && range_ok && h->n > 0 &&
                       (cm == LB_CAND_F16 || (cm == LB_CAND_AUTO && h->n >= f16_image_min_rows));
     try {
         if (!want || (h->d_Xh && (h->xh_cap < h->n || h->xh_rows > h->n))) {
@@ -389,9 +389,10 @@ static int filter_column(lb_gpu_index *h, const T *column, int64_t n, T value, i
 int dtype_mismatch(lb_gpu_index *h, int call)
 {
     if (h->dtype() == call) return LB_OK;
-    static const char *const what[3] = {"this index holds float32 rows: use the float32 entry point",
+    static const char *const what[4] = {"this index holds float32 rows: use the float32 entry point",
                                         "this index holds float16 rows: use the _f16 entry point",
-                                        "this index holds int8 rows: use the _i8 entry point"};
+                                        "this index holds int8 rows: use the _i8 entry point",
+                                        "this index holds uint8 rows: use the _u8 entry point"};
     h->set_error("%s", what[h->dtype()]);
     return LB_ERR_INVALID_ARG;
 }
@@ -427,7 +428,7 @@ const char *lb_gpu_status_string(int status)
     }
 }
 
-// dtype: 0 float32, 1 float16, 2 int8 (simd.DataType)
+// dtype: 0 float32, 1 float16, 2 int8, 3 uint8 (simd.DataType)
 static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status, int dtype)
 {
     auto st = [&](int v) { if (out_status) *out_status = v; };
@@ -441,15 +442,18 @@ static lb_gpu_index *index_new(int device, int dim, int metric, int *out_status,
         if (metric == LB_METRIC_COSINE) { st(LB_ERR_UNSUPPORTED); return nullptr; }
         if (metric == LB_METRIC_DOT && dim / 4 + dim % 4 > 1024) { st(LB_ERR_UNSUPPORTED); return nullptr; }
     }
+    // uint8: the reference registers the Euclidean kernel alone (internal/simd/dispatch.go:250)
+    if (dtype == 3 && metric != LB_METRIC_EUCLIDEAN) { st(LB_ERR_UNSUPPORTED); return nullptr; }
     if (!device_ok(device)) { st(LB_ERR_NO_DEVICE); return nullptr; }
     auto *h = new (std::nothrow) lb_gpu_index();
     if (!h) { st(LB_ERR_OOM); return nullptr; }
     h->device = device; h->dim = dim; h->metric = metric;
     h->f16_rows = dtype == 1;
     h->i8_rows = dtype == 2;
+    h->u8_rows = dtype == 3;
     // (fp16 rows: UNROLL4 is the only order of the reference's F16 functions, internal/simd/simd.go:767-848; int8 rows: the
-    // order is accepted and changes nothing, the int8 arithmetic has one form)
-    if (h->f16_rows || h->i8_rows) h->order.store(LB_ORDER_UNROLL4);
+    // order is accepted and changes nothing, the int8 arithmetic has one form; uint8 rows: the same)
+    if (h->f16_rows || h->byte_rows()) h->order.store(LB_ORDER_UNROLL4);
     const int rc = guard(h, nullptr, [&]() -> int {
         LB_HIP(hipSetDevice(device));
         LB_HIP(hipStreamCreateWithFlags(&h->add_stream.h, hipStreamNonBlocking));
@@ -477,6 +481,10 @@ lb_gpu_index *lb_gpu_index_new_f16(int device, int dim, int metric, int *out_sta
 lb_gpu_index *lb_gpu_index_new_i8(int device, int dim, int metric, int *out_status)
 {
     return index_new(device, dim, metric, out_status, 2);
+}
+lb_gpu_index *lb_gpu_index_new_u8(int device, int dim, int metric, int *out_status)
+{
+    return index_new(device, dim, metric, out_status, 3);
 }
 int lb_gpu_index_dtype(const lb_gpu_index *h) { return h ? h->dtype() : 0; }
 
@@ -527,8 +535,8 @@ int lb_gpu_index_set_candidate_mode(lb_gpu_index *h, int mode)
         h->set_error("candidate mode %d needs f32 rows; an fp16 index takes AUTO or F16", mode);
         return LB_ERR_UNSUPPORTED;
     }
-    if (h->i8_rows && mode != LB_CAND_AUTO) {
-        h->set_error("candidate mode %d needs f32 rows; an int8 index takes AUTO only", mode);
+    if (h->byte_rows() && mode != LB_CAND_AUTO) {
+        h->set_error("candidate mode %d needs f32 rows; %s index takes AUTO only", mode, h->u8_rows ? "a uint8" : "an int8");
         return LB_ERR_UNSUPPORTED;
     }
     if ((mode == LB_CAND_SPLIT_BF16 || mode == LB_CAND_SPLIT_BF16_INREG) && h->dim % 32 != 0) {
@@ -660,6 +668,10 @@ int lb_gpu_index_add_i8(lb_gpu_index *h, int64_t n, const int8_t *vectors, const
 {
     return add_host(h, n, vectors, ids, 2);
 }
+int lb_gpu_index_add_u8(lb_gpu_index *h, int64_t n, const uint8_t *vectors, const int64_t *ids)
+{
+    return add_host(h, n, vectors, ids, 3);
+}
 
 static int add_device(lb_gpu_index *h, int64_t n, const void *d_vectors, const int64_t *d_ids, int dtype)
 {
@@ -689,6 +701,10 @@ int lb_gpu_index_add_f16_device(lb_gpu_index *h, int64_t n, const uint16_t *d_ve
 int lb_gpu_index_add_i8_device(lb_gpu_index *h, int64_t n, const int8_t *d_vectors, const int64_t *d_ids)
 {
     return add_device(h, n, d_vectors, d_ids, 2);
+}
+int lb_gpu_index_add_u8_device(lb_gpu_index *h, int64_t n, const uint8_t *d_vectors, const int64_t *d_ids)
+{
+    return add_device(h, n, d_vectors, d_ids, 3);
 }
 
 int lb_gpu_index_set_filter(lb_gpu_index *h, const uint8_t *mask, int64_t n)

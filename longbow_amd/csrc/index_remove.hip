@@ -175,7 +175,7 @@ int lb_gpu_index_compact(lb_gpu_index *h, int64_t *old_rows, int64_t cap)
         LB_HIP(hipMemcpyAsync(h->d_maxnorm2.get(), norm_init, sizeof norm_init, hipMemcpyHostToDevice, s));
         if (h->i8_rows)
             launch_row_norms_i8(h->rows_i8(), nlive, h->dim, h->norm2_i8(), s);
-        else
+        else if (!h->u8_rows) // (a uint8 index keeps no norms)
             with_rows(h, [&](auto Xr) { launch_row_norms(Xr, nlive, h->dim, h->d_norm2.get(), h->d_rnorm.get(), h->d_maxnorm2.get(), s); });
         LB_HIP(hipMemcpyAsync(nbits, h->d_maxnorm2.get(), sizeof nbits, hipMemcpyDeviceToHost, s));
         if (nlive > 0) LB_HIP(hipMemsetAsync(h->d_live.get(), 0xff, (size_t)nlive, s));

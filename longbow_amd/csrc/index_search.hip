@@ -238,6 +238,8 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                 ProfScope p(w, s, prof, 1);
                 if (h->i8_rows)
                     launch_sample_scores_i8(metric, h->rows_i8(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel, gn, w->cs, s);
+                else if (h->u8_rows)
+                    launch_sample_scores_u8(h->rows_u8(), h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel, gn, w->cs, s);
                 else
                     with_rows(h, [&](auto X) {
                         launch_sample_scores(metric, order, X, h->dim, sp.span, sp.count, rv.rowmap, mask, d_q, use_sel, gn, w->cs,
@@ -250,6 +252,8 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                 if (h->i8_rows)
                     launch_scan_i8(metric, h->rows_i8(), 0, sp.span, h->dim, d_q, use_sel, gn, h->norm2_i8(), mask, rv.rowmap, w->cs,
                                    /*boot=*/false, s, /*striped=*/true);
+                else if (h->u8_rows)
+                    launch_scan_u8(h->rows_u8(), 0, sp.span, h->dim, d_q, use_sel, gn, mask, rv.rowmap, w->cs, /*boot=*/false, s, /*striped=*/true);
                 else
                     with_rows(h, [&](auto X) {
                         launch_scan(metric, order, false, X, 0, sp.span, h->dim, d_q, use_sel, gn, w->d_qna.get(), mask, rv.rowmap, w->cs,
@@ -277,6 +281,8 @@ bool run_scan_path(lb_gpu_index *h, Workspace *w, hipStream_t s, const float *d_
                 if (h->i8_rows)
                     launch_scan_i8(metric, h->rows_i8(), pos, end, h->dim, d_q, use_sel, gn, h->norm2_i8(), mask, rv.rowmap, w->cs,
                                    boot, s, /*striped=*/false);
+                else if (h->u8_rows)
+                    launch_scan_u8(h->rows_u8(), pos, end, h->dim, d_q, use_sel, gn, mask, rv.rowmap, w->cs, boot, s, /*striped=*/false);
                 else
                     with_rows(h, [&](auto X) {
                         launch_scan(metric, order, false, X, pos, end, h->dim, d_q, use_sel, gn, w->d_qna.get(), mask, rv.rowmap, w->cs,
@@ -553,6 +559,17 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
     std::vector<int> redo;
     if (collect_flagged(w, s, nq, 1u | 4u, nullptr, 0, redo, true) > 0)
         scan_with_retry(h, w, s, d_q, nq, &redo, k, d_dist, d_lab, prof);
+    return LB_OK;
+}
+
+// A uint8 index's batch (kernels_u8.hip): as an int8 index's, every entry is the exact reference value.
+//   route 82  the exact scan (run_scan_path): 8 queries a corpus pass, v_dot4_u32_u8, for every batch size
+//   (83 is kept for an i8 matrix-core pass over the bytes XORed with 0x80: not built)
+constexpr int kRouteU8Scan = 82;
+int search_batch_u8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, int k, float *d_dist, int64_t *d_lab, bool prof)
+{
+    note_route(h, kRouteU8Scan);
+    scan_with_retry(h, w, s, d_q, nq, nullptr, k, d_dist, d_lab, prof);
     return LB_OK;
 }
 
@@ -1117,9 +1134,11 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
             for (int64_t q0 = 0; q0 < nq; q0 += kMaxBatch) {
                 const int bq = (int)std::min<int64_t>(kMaxBatch, nq - q0);
                 const float *bq_f32 = nullptr;
-                if (dtype != 0) { // fp16 / int8 queries: widened exactly into the workspace's f32 batch, then searched as any other
+                if (dtype != 0) { // fp16 / int8 / uint8 queries: widened exactly into the workspace's f32 batch, then searched as any other
                     w->d_q.ensure((size_t)bq * h->dim);
-                    if (dtype == 2)
+                    if (dtype == 3)
+                        launch_widen_u8(static_cast<const uint8_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q.get(), (int64_t)bq * h->dim, s);
+                    else if (dtype == 2)
                         launch_widen_i8(static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q.get(), (int64_t)bq * h->dim, s);
                     else
                         launch_widen_f16(static_cast<const uint16_t *>(d_queries) + (size_t)q0 * h->dim, w->d_q.get(), (int64_t)bq * h->dim, s);
@@ -1127,7 +1146,8 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
                 } else {
                     bq_f32 = static_cast<const float *>(d_queries) + (size_t)q0 * h->dim;
                 }
-                const int brc = h->i8_rows ? search_batch_i8(h, w, s, bq, bq_f32, static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, k,
+                const int brc = h->u8_rows ? search_batch_u8(h, w, s, bq, bq_f32, k, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
+                              : h->i8_rows ? search_batch_i8(h, w, s, bq, bq_f32, static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, k,
                                                              d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
                                            : search_batch_device(h, w, s, bq, bq_f32, k, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k,
                                                                  kc, prof, fallbacks);
@@ -1169,6 +1189,11 @@ int lb_gpu_index_search_i8_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t 
                                       int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
     return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 2);
+}
+int lb_gpu_index_search_u8_device_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *d_queries, int k, float *d_dist,
+                                      int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 3);
 }
 
 int lb_gpu_index_search_device(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, float *d_dist,
@@ -1281,6 +1306,15 @@ int lb_gpu_index_search_i8(lb_gpu_index *h, int64_t nq, const int8_t *queries, i
 {
     return lb_gpu_index_search_i8_ctx(h, nq, queries, k, dist, labels, nullptr);
 }
+int lb_gpu_index_search_u8_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *queries, int k, float *dist, int64_t *labels,
+                               const lb_cancel *ctx)
+{
+    return host_search(h, nq, queries, k, dist, labels, ctx, 3);
+}
+int lb_gpu_index_search_u8(lb_gpu_index *h, int64_t nq, const uint8_t *queries, int k, float *dist, int64_t *labels)
+{
+    return lb_gpu_index_search_u8_ctx(h, nq, queries, k, dist, labels, nullptr);
+}
 
 // the same searches under a row bitmap given with the call (include/longbow_gpu.h, "call bitmap"); a NULL bitmap: the plain search
 // through the plain path.  The host forms' bitmap bytes travel in `bits`, declared here, outside every guard.
@@ -1306,6 +1340,11 @@ int lb_gpu_index_search_i8_bitmap_ctx(lb_gpu_index *h, int64_t nq, const int8_t 
 {
     return host_search_bitmap(h, nq, queries, k, bitmap, nbits, dist, labels, ctx, 2);
 }
+int lb_gpu_index_search_u8_bitmap_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *queries, int k, const uint8_t *bitmap, int64_t nbits,
+                                      float *dist, int64_t *labels, const lb_cancel *ctx)
+{
+    return host_search_bitmap(h, nq, queries, k, bitmap, nbits, dist, labels, ctx, 3);
+}
 int lb_gpu_index_search_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const float *d_queries, int k, const uint8_t *d_bitmap,
                                           int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
@@ -1320,6 +1359,11 @@ int lb_gpu_index_search_i8_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const 
                                              int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
 {
     return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 2, CallBits{d_bitmap, nbits, true, nullptr});
+}
+int lb_gpu_index_search_u8_bitmap_device_ctx(lb_gpu_index *h, int64_t nq, const uint8_t *d_queries, int k, const uint8_t *d_bitmap,
+                                             int64_t nbits, float *d_dist, int64_t *d_labels, void *stream, const lb_cancel *ctx)
+{
+    return search_device(h, nq, d_queries, k, d_dist, d_labels, stream, ctx, 3, CallBits{d_bitmap, nbits, true, nullptr});
 }
 
 int lb_gpu_index_set_search_combining(lb_gpu_index *h, int enable) { return combining_set(h, enable); }

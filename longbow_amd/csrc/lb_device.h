@@ -291,6 +291,16 @@ void launch_mfma_i8(int metric, const int8_t *X, int64_t npos, int D, const int8
                     hipStream_t s);
 // exact |q|^2 of nq int8 queries
 void launch_query_norms_i8(const int8_t *Q8, int nq, int D, int32_t *qn, hipStream_t s);
+
+// ---- the uint8 index (kernels_u8.hip): exact values of the reference's uint8 registry kernel (L2 only), entries as the scan's
+// n uint8 values -> f32, exactly
+void launch_widen_u8(const void *src, float *dst, int64_t n, hipStream_t s);
+// the scan over uint8 rows (launch_scan's contract; Q: uint8 queries widened to f32; no per-row side data)
+void launch_scan_u8(const uint8_t *X, int64_t row_begin, int64_t row_end, int D, const float *Q, const int *qsel, int nsel,
+                    const uint8_t *mask, const uint32_t *rowmap, CandState cs, bool boot, hipStream_t s, bool striped);
+// launch_sample_scores over uint8 rows: the sampled entries carry the exact values
+void launch_sample_scores_u8(const uint8_t *X, int D, int64_t span, uint32_t count, const uint32_t *rowmap, const uint8_t *mask,
+                             const float *Q, const int *qsel, int nsel, CandState cs, hipStream_t s);
 // column means of X[0 .. n) in a fixed order -> center[0 .. Dpad) (zero beyond D); partial: [256][D] scratch
 void launch_column_means(const float *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);
 void launch_column_means(const _Float16 *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);

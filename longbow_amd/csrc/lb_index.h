@@ -180,6 +180,7 @@ struct lb_gpu_index : HandleCore {
     float *d_X = nullptr; // vmm.base, or (vmm.ok false) a hipMalloc'd buffer this handle frees itself: lb_gpu_index_free
     bool f16_rows = false; // lb_gpu_index_new_f16: fixed for the handle's life
     bool i8_rows = false;  // lb_gpu_index_new_i8: signed int8 rows, fixed for the handle's life (searched by kernels_i8.hip only)
+    bool u8_rows = false;  // lb_gpu_index_new_u8: uint8 rows, fixed for the handle's life (searched by kernels_u8.hip only; no side data per row)
     VmmBuf vmm;             // backs d_X when vmm.ok (d_X == vmm.base): rows are appended in place
     int64_t x_rows_cap = 0; // rows d_X can hold (>= capacity of the side arrays when vmm.ok)
     int64_t n = 0, capacity = 0;
@@ -265,10 +266,12 @@ struct lb_gpu_index : HandleCore {
     int prof_n[5] = {0, 0, 0, 0, 0};
     float refine_ms[3] = {0, 0, 0}; // the last profiled refine, summed over its batches: prepare, scan (with the query norms), selection
 
-    size_t elem_bytes() const { return i8_rows ? 1 : f16_rows ? 2 : sizeof(float); }
-    int dtype() const { return i8_rows ? 2 : f16_rows ? 1 : 0; } // simd.DataType
+    size_t elem_bytes() const { return byte_rows() ? 1 : f16_rows ? 2 : sizeof(float); }
+    int dtype() const { return u8_rows ? 3 : i8_rows ? 2 : f16_rows ? 1 : 0; } // simd.DataType
+    bool byte_rows() const { return i8_rows || u8_rows; } // one byte an element: no f32 / fp16 route, image or re-rank reads these rows
     const _Float16 *rows_f16() const { return reinterpret_cast<const _Float16 *>(d_X); }
     const int8_t *rows_i8() const { return reinterpret_cast<const int8_t *>(d_X); }
+    const uint8_t *rows_u8() const { return reinterpret_cast<const uint8_t *>(d_X); }
     // an int8 index keeps its exact int32 row norms (the sum of x_i^2 over i < 16 floor(D / 16)) in d_norm2's words
     int32_t *norm2_i8() const { return reinterpret_cast<int32_t *>(d_norm2.get()); }
 };
@@ -311,5 +314,5 @@ LB_INTERNAL void drop_split_image(lb_gpu_index *h);
 LB_INTERNAL void sync_split_image(lb_gpu_index *h);
 LB_INTERNAL void sync_f16_image(lb_gpu_index *h);
 LB_INTERNAL void set_norm_flags(lb_gpu_index *h, const uint32_t nbits[2]);
-// call: the element type of the entry point (0 float32, 1 _f16, 2 _i8); LB_OK, or the error an index of another type reports (index.hip)
+// call: the element type of the entry point (0 float32, 1 _f16, 2 _i8, 3 _u8); LB_OK, or the error an index of another type reports (index.hip)
 LB_INTERNAL int dtype_mismatch(lb_gpu_index *h, int call);

@@ -32,8 +32,8 @@ int refine_args(lb_gpu_index *h, int64_t nq, const void *queries, int64_t c, con
     if (k > LB_MAX_K) { h->set_error("k=%d exceeds the supported maximum %d", k, LB_MAX_K); return LB_ERR_UNSUPPORTED; }
     if (nq == 0) return LB_OK;
     if (!queries || !rows || !dist || !labels) return LB_ERR_INVALID_ARG;
-    if (h->i8_rows) { // (fixed for the handle's life: no lock)
-        h->set_error("refine reads float32 or float16 rows: not available on an int8 index");
+    if (h->byte_rows()) { // (fixed for the handle's life: no lock)
+        h->set_error("refine reads float32 or float16 rows: not available on %s index", h->u8_rows ? "a uint8" : "an int8");
         return LB_ERR_UNSUPPORTED;
     }
     if (const int st = ctx_state(ctx)) return ctx_fail(h, st);

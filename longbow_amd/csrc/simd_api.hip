@@ -156,8 +156,8 @@ int lb_simd_and_bytes(int device, uint8_t *dst, const uint8_t *src, int64_t n)
 // ---- candidate re-rank (processChunkInternal) ------------------------------------------
 static int rerank_unsupported(lb_gpu_index *h)
 {
-    if (!h->f16_rows && !h->i8_rows) return LB_OK;
-    h->set_error("re-rank reads float32 rows: not available on a %s index", h->i8_rows ? "int8" : "float16");
+    if (!h->f16_rows && !h->byte_rows()) return LB_OK;
+    h->set_error("re-rank reads float32 rows: not available on a %s index", h->u8_rows ? "uint8" : h->i8_rows ? "int8" : "float16");
     return LB_ERR_UNSUPPORTED;
 }
 

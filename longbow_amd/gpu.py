@@ -22,6 +22,7 @@ class DataType:
     Float32 = 0
     Float16 = 1
     Int8 = 2
+    Uint8 = 3  # Euclidean only; such an index is made by NewUint8Index(cfg)
 
 
 class GPUConfig:
@@ -67,18 +68,21 @@ class Cancel:
 class Index:
     """gpu.Index backed by lb_gpu_index (HIP)."""
 
-    def __init__(self, cfg: GPUConfig, lib=None):
+    def __init__(self, cfg: GPUConfig, lib=None, _uint8=False):
         if cfg.Dimension <= 0:
             raise ValueError(f"dimension must be positive, got {cfg.Dimension}")  # faiss_gpu.go:46-48
         dtype = int(getattr(cfg, "DataType", DataType.Float32))
-        if dtype not in (DataType.Float32, DataType.Float16, DataType.Int8):
-            raise ValueError(f"unknown data type {dtype} (0 float32, 1 float16, 2 int8)")
+        if dtype == DataType.Uint8 and not _uint8:
+            raise ValueError("data type 3 (uint8) is not created through Index(cfg): use NewUint8Index(cfg)")
+        if dtype not in (DataType.Float32, DataType.Float16, DataType.Int8, DataType.Uint8):
+            raise ValueError(f"unknown data type {dtype} (0 float32, 1 float16, 2 int8, 3 uint8)")
         if lib is None:
             lib = _lib.require_gpu(cfg.DeviceID)
         elif lib.lb_gpu_device_count() <= cfg.DeviceID:
             raise GPUNotAvailable(3, f"device {cfg.DeviceID} requested")
         st = C.c_int(0)
-        new = {DataType.Float16: lib.lb_gpu_index_new_f16, DataType.Int8: lib.lb_gpu_index_new_i8}.get(dtype, lib.lb_gpu_index_new)
+        new = {DataType.Float16: lib.lb_gpu_index_new_f16, DataType.Int8: lib.lb_gpu_index_new_i8,
+               DataType.Uint8: lib.lb_gpu_index_new_u8}.get(dtype, lib.lb_gpu_index_new)
         h = new(cfg.DeviceID, cfg.Dimension, int(cfg.Metric), C.byref(st))
         if not h:
             _lib.check(st.value or 7)
@@ -88,7 +92,7 @@ class Index:
         self.device = cfg.DeviceID
         self.metric = MetricType(int(cfg.Metric))
         self.data_type = dtype
-        self._np = {DataType.Float16: np.float16, DataType.Int8: np.int8}.get(dtype, np.float32)  # element type of Add / Search arguments
+        self._np = {DataType.Float16: np.float16, DataType.Int8: np.int8, DataType.Uint8: np.uint8}.get(dtype, np.float32)  # element type of Add / Search arguments
         self._lock = threading.Lock()
         self._closed = False
 
@@ -158,8 +162,8 @@ class Index:
 
     def _as_elems(self, a):
         """The index's element type, contiguous.  A float16 index takes np.float16 arrays only, an int8 index np.int8 arrays
-        only: converting other data here would change the vectors silently."""
-        if self._np is np.float16 or self._np is np.int8:
+        only, a uint8 index np.uint8 arrays only: converting other data here would change the vectors silently."""
+        if self._np is not np.float32:
             a = np.asarray(a)
             if a.dtype != self._np:
                 raise TypeError(f"a {np.dtype(self._np).name} index takes np.{np.dtype(self._np).name} arrays, got {a.dtype}")
@@ -167,12 +171,12 @@ class Index:
         return np.ascontiguousarray(a, np.float32)
 
     def _entry(self, name, suffix=""):
-        """the C entry point for this index's element type: name + ("" | "_f16" | "_i8") + suffix"""
-        tag = "_f16" if self._np is np.float16 else "_i8" if self._np is np.int8 else ""
+        """the C entry point for this index's element type: name + ("" | "_f16" | "_i8" | "_u8") + suffix"""
+        tag = {np.float16: "_f16", np.int8: "_i8", np.uint8: "_u8"}.get(self._np, "")
         return getattr(self._lib, name + tag + suffix)
 
     def dtype(self):
-        """0 float32, 1 float16, 2 int8 (lb_gpu_index_dtype)"""
+        """0 float32, 1 float16, 2 int8, 3 uint8 (lb_gpu_index_dtype)"""
         self._live()
         return int(self._lib.lb_gpu_index_dtype(self._h))
 
@@ -439,3 +443,12 @@ def NewIndexWithConfig(cfg: GPUConfig, lib=None):
     """gpu.NewIndexWithConfig (gpu_enabled.go:17-21).  Raises ErrGPUNotAvailable without a device.
     lib: another build of the library (tests: _lib.load_diag())."""
     return Index(cfg, lib=lib)
+
+
+def NewUint8Index(cfg: GPUConfig, lib=None):
+    """A flat index over uint8 rows (lb_gpu_index_new_u8; cfg.DataType must be DataType.Uint8, cfg.Metric Euclidean): Add,
+    Search, SearchBatch and the bitmap searches take np.uint8 arrays, and the distances are the reference's
+    euclideanUint8Unrolled4x bit for bit.  Filters, removal, compaction and timing are the Index methods."""
+    if int(getattr(cfg, "DataType", DataType.Float32)) != DataType.Uint8:
+        raise ValueError("NewUint8Index takes GPUConfig(DataType=DataType.Uint8)")
+    return Index(cfg, lib=lib, _uint8=True)
