@@ -235,8 +235,10 @@ int lb_gpu_index_search_i8_device_ctx(lb_gpu_index *h, int64_t nq, const int8_t 
  *                That is every pair for dim <= 258.  A pair with S > 2^24 is evaluated by the chain arithmetic itself, after a
  *                test that drops it when even S (1 - (floor(dim / 4) + 6) 2^-24), a lower bound of the reference's sum, gives a
  *                value that cannot enter the query's list.
- * Searches take the exact uint8 scan for every batch size (last_route 82; dim % 16 != 0 or a misaligned base: one lane per
- * pair, chain arithmetic throughout).  There is no matrix-core pass.  Everything else is the int8 handle's: reserve / ntotal /
+ * Searches take the exact uint8 scan (last_route 82; dim % 16 != 0 or a misaligned base: one lane per pair, chain arithmetic
+ * throughout) or, for a batch of 16 or more queries with dim % 16 == 0, 16-B aligned corpus and query bases and at least
+ * 16,384 visible rows, the i8 matrix-core pass over the bytes shifted by 128 as they are staged (last_route 83: the same
+ * per-pair rule, the same results bit for bit).  Everything else is the int8 handle's: reserve / ntotal /
  * dim / set_filter / filter_* / nvisible / remove* / compact / last_* / profiling / hbm_bytes / free work as on an f32 handle;
  * set_order is accepted and changes nothing; set_candidate_mode takes AUTO only (else LB_ERR_UNSUPPORTED); set_f16_image is
  * accepted and has no effect; rerank, refine and comm searches return LB_ERR_UNSUPPORTED; dtype is 3.  A float32 / _f16 / _i8

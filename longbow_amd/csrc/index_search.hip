@@ -563,13 +563,46 @@ int search_batch_i8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const 
 }
 
 // A uint8 index's batch (kernels_u8.hip): as an int8 index's, every entry is the exact reference value.
-//   route 82  the exact scan (run_scan_path): 8 queries a corpus pass, v_dot4_u32_u8, for every batch size
-//   (83 is kept for an i8 matrix-core pass over the bytes XORed with 0x80: not built)
-constexpr int kRouteU8Scan = 82;
-int search_batch_u8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, int k, float *d_dist, int64_t *d_lab, bool prof)
+//   route 82  the exact scan (run_scan_path): 8 queries a corpus pass, v_dot4_u32_u8;
+//   route 83  the i8 MFMA pass over the bytes XORed with 0x80 as they are staged (kernels_u8_mfma.hip): 128 queries a corpus
+//             pass, the sequence of route 81.  Needs D % 16 == 0, 16-B aligned corpus and query bases and a sampled span that
+//             covers the row view; batches from LB_U8_MFMA_MINQ queries.
+// d_q: the batch widened to f32 (the scan's input), d_q8: the same queries as uint8 (the MFMA pass's).
+constexpr int kRouteU8Scan = 82, kRouteU8Mfma = 83;
+int search_batch_u8(lb_gpu_index *h, Workspace *w, hipStream_t s, int nq, const float *d_q, const uint8_t *d_q8, int k, float *d_dist,
+                    int64_t *d_lab, bool prof)
 {
-    note_route(h, kRouteU8Scan);
-    scan_with_retry(h, w, s, d_q, nq, nullptr, k, d_dist, d_lab, prof);
+    static const int mfma_minq = lb_tunable("LB_U8_MFMA_MINQ", 16);
+    const IndexRowView rv = row_view(h, w);
+    const int kkeep = std::max(k, 1);
+    SamplePlan sp;
+    if (nq >= mfma_minq && mfma_u8_supported(h->dim, h->d_X, d_q8)) sp = sample_plan(rv.n, kkeep, w->cap);
+    if (!sp.on || sp.span < rv.n) {
+        note_route(h, kRouteU8Scan);
+        scan_with_retry(h, w, s, d_q, nq, nullptr, k, d_dist, d_lab, prof);
+        return LB_OK;
+    }
+    note_route(h, kRouteU8Mfma);
+    int32_t *qn = reinterpret_cast<int32_t *>(w->d_qna.get()); // (nq_cap words: the exact int32 |q - 128|^2 here)
+    {
+        ProfScope p(w, s, prof, 1);
+        LB_HIP(hipMemsetAsync(w->cs.flags, 0, (size_t)nq * sizeof(uint32_t), s));
+        launch_query_norms_u8_shifted(d_q8, nq, h->dim, qn, s);
+        launch_mfma_u8(h->rows_u8(), sp.count, h->dim, d_q8, nq, qn, rv.mask, rv.rowmap, w->cs, /*sample=*/true, sp.span, s);
+        launch_sample_tau(w->cs, nullptr, nq, sp.count, sp.m, /*zero_stripes=*/false, s);
+    }
+    {
+        ProfScope p(w, s, prof, 3);
+        launch_mfma_u8(h->rows_u8(), rv.n, h->dim, d_q8, nq, qn, rv.mask, rv.rowmap, w->cs, /*sample=*/false, rv.n, s);
+    }
+    {
+        ProfScope p(w, s, prof, 1);
+        const EmitArgs em{k, h->has_ids ? h->d_ids.get() : nullptr, d_dist, d_lab, w->h_flags.get()};
+        launch_select(w->cs, nullptr, nq, kkeep, 0u, s, (uint32_t)kkeep, &em);
+    }
+    std::vector<int> redo;
+    if (collect_flagged(w, s, nq, 1u | 4u, nullptr, 0, redo, true) > 0)
+        scan_with_retry(h, w, s, d_q, nq, &redo, k, d_dist, d_lab, prof);
     return LB_OK;
 }
 
@@ -1146,7 +1179,8 @@ static int search_device(lb_gpu_index *h, int64_t nq, const void *d_queries, int
                 } else {
                     bq_f32 = static_cast<const float *>(d_queries) + (size_t)q0 * h->dim;
                 }
-                const int brc = h->u8_rows ? search_batch_u8(h, w, s, bq, bq_f32, k, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
+                const int brc = h->u8_rows ? search_batch_u8(h, w, s, bq, bq_f32, static_cast<const uint8_t *>(d_queries) + (size_t)q0 * h->dim, k,
+                                                             d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
                               : h->i8_rows ? search_batch_i8(h, w, s, bq, bq_f32, static_cast<const int8_t *>(d_queries) + (size_t)q0 * h->dim, k,
                                                              d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k, prof)
                                            : search_batch_device(h, w, s, bq, bq_f32, k, d_dist + (size_t)q0 * k, d_labels + (size_t)q0 * k,

@@ -301,6 +301,13 @@ void launch_scan_u8(const uint8_t *X, int64_t row_begin, int64_t row_end, int D,
 // launch_sample_scores over uint8 rows: the sampled entries carry the exact values
 void launch_sample_scores_u8(const uint8_t *X, int D, int64_t span, uint32_t count, const uint32_t *rowmap, const uint8_t *mask,
                              const float *Q, const int *qsel, int nsel, CandState cs, hipStream_t s);
+// the i8 MFMA pass over uint8 rows and uint8 queries Q8, both shifted by 128 as they are staged (kernels_u8_mfma.hip;
+// launch_mfma_i8's contract, L2 only, no stored row norms; qn: launch_query_norms_u8_shifted's)
+bool mfma_u8_supported(int D, const void *X, const void *Q8);
+void launch_mfma_u8(const uint8_t *X, int64_t npos, int D, const uint8_t *Q8, int nq, const int32_t *qn, const uint8_t *mask,
+                    const uint32_t *rowmap, CandState cs, bool sample, int64_t span, hipStream_t s);
+// exact sum of (q_i - 128)^2 of nq uint8 queries
+void launch_query_norms_u8_shifted(const uint8_t *Q8, int nq, int D, int32_t *qn, hipStream_t s);
 // column means of X[0 .. n) in a fixed order -> center[0 .. Dpad) (zero beyond D); partial: [256][D] scratch
 void launch_column_means(const float *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);
 void launch_column_means(const _Float16 *X, int64_t n, int D, float *partial, float *center, int Dpad, hipStream_t s);
