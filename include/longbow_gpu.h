@@ -856,9 +856,34 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     an exact int32 rounded once to f32, the tail added in f32 in order, sqrt correctly rounded; dot:
  *                     dotInt8Unrolled4x, negated).  Result, labels, padding, ids, filters and stats are as stated above, and
  *                     nprobe >= nlist gives lb_gpu_index_search_i8 of an int8 index (lb_gpu_index_new_i8) over the same rows,
- *                     bit for bit.  Every other lb_gpu_ivf_* entry point works on all three handle types.
+ *                     bit for bit.  Every other lb_gpu_ivf_* entry point works on all four handle types.
+ *   uint8 rows        lb_gpu_ivf_new_u8 makes a handle whose rows are uint8, one byte an element, row-major in insertion order,
+ *                     and no wider copy of them (VectorTypeUint8).  Euclidean only: cosine (1) and dot (2) are
+ *                     LB_ERR_UNSUPPORTED, the rule of lb_gpu_index_new_u8 for its reason (the reference registers
+ *                     euclideanUint8Unrolled4x alone for the type), answered with the other limits (after LB_ERR_INVALID_ARG,
+ *                     before LB_ERR_NO_DEVICE).  Rows go in through lb_gpu_ivf_add_u8 / _add_u8_device and the QUERIES are uint8
+ *                     too, through lb_gpu_ivf_search_u8 / _search_u8_ctx / _search_u8_device_ctx, each taking what its float32
+ *                     counterpart takes.  Every other add or search on such a handle, and the _u8 adds and searches on another
+ *                     handle, are LB_ERR_INVALID_ARG with a last_error text that names the handle's element type, and write
+ *                     nothing.  The centroids and the coarse index stay f32 and `order` is the coarse index's alone: the list of
+ *                     a row and the probes of a query are those of the row / query widened to f32, which is exact, so
+ *                     assignments, list sizes and search stats equal those of a float32 handle over the widened rows, bit for
+ *                     bit.  `order` does not reach the row distances: d(q, x) is the one lb_gpu_index_search_u8 reports, the
+ *                     arithmetic stated at "uint8 indexes" above (four f32 chains over i mod 4, the tail into chain 0, added as
+ *                     ((s0 + s1) + s2) + s3, sqrt correctly rounded), bit for bit.  A list scan writes a value for every row of
+ *                     a probed list, so it has no threshold to drop a pair against and works by the per-chain rule instead: every
+ *                     partial sum of chain j is an integer no larger than the chain's own exact sum S_j, so while every
+ *                     S_j <= 2^24 every add inside the chains is exact and the value is sqrt of
+ *                     ((f(S0) + f(S1)) + f(S2)) + f(S3), the S_j being exact integers (v_dot4_u32_u8 over the row's bytes masked
+ *                     to one residue).  That holds for every pair when dim <= 1032, and for totals up to 2^26; a pair with a chain
+ *                     beyond 2^24 is evaluated by the chain arithmetic itself.  dim <= 258: no pair exceeds 2^24 in total and the
+ *                     value is sqrt_rn(float(S)).  dim % 16 != 0 or a misaligned base: one lane per pair, chain arithmetic
+ *                     throughout.  Result, labels, padding, ids, filters, removal, compaction and stats are as stated above, and
+ *                     with every list probed (nprobe >= nlist) the result is lb_gpu_index_search_u8 of a flat uint8 index
+ *                     (lb_gpu_index_new_u8) over the same rows, bit for bit.
  *   call bitmap       lb_gpu_ivf_search_bitmap_ctx / _bitmap_device_ctx and, on an int8 handle, _search_i8_bitmap_ctx /
- *                     _i8_bitmap_device_ctx take what their plain counterparts take, and behind nprobe a row filter of THIS CALL
+ *                     _i8_bitmap_device_ctx, on a uint8 handle _search_u8_bitmap_ctx / _u8_bitmap_device_ctx, take what their
+ *                     plain counterparts take, and behind nprobe a row filter of THIS CALL
  *                     alone: (bitmap, nbits, stride_bytes).  One bit per row POSITION, as the handle filter's mask is by position,
  *                     least significant bit first as in an Arrow validity buffer: row r is visible to the call iff
  *                     bitmap[r >> 3] >> (r & 7) & 1.  It is read byte by byte: no alignment is owed and no padding beyond
@@ -883,13 +908,15 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     the rows the handle's lists hold, every list is compacted once for the call, in its first batch, and not
  *                     once per query and probe; a host decision from the list sizes, and the result does not depend on it.
  *                     ctx is polled before these launches as before every other; under profiling they fall into ms[1].
- * Not here: fp16 or int8 centroids, fp16 queries, f32 queries on an int8 handle, predicates (filter_int64 / _float32) given per
+ * Not here: fp16, int8 or uint8 centroids, fp16 queries, f32 queries on an int8 or uint8 handle, cosine or dot over uint8 rows,
+ * predicates (filter_int64 / _float32) given per
  * search call, search combining, lb_gpu_comm_*. */
 typedef struct lb_gpu_ivf lb_gpu_ivf;
 lb_gpu_ivf *lb_gpu_ivf_new(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
 lb_gpu_ivf *lb_gpu_ivf_new_f16(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
 lb_gpu_ivf *lb_gpu_ivf_new_i8(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
-int lb_gpu_ivf_dtype(const lb_gpu_ivf *p); /* 0 float32, 1 float16, 2 int8 (as lb_gpu_index_dtype); 0 on NULL */
+lb_gpu_ivf *lb_gpu_ivf_new_u8(int device, int dim, int metric, int order, int nlist, const float *centroids, int *out_status);
+int lb_gpu_ivf_dtype(const lb_gpu_ivf *p); /* 0 float32, 1 float16, 2 int8, 3 uint8 (as lb_gpu_index_dtype); 0 on NULL */
 void lb_gpu_ivf_free(lb_gpu_ivf *p);
 const char *lb_gpu_ivf_last_error(const lb_gpu_ivf *p);
 int lb_gpu_ivf_dim(const lb_gpu_ivf *p);
@@ -906,6 +933,8 @@ int lb_gpu_ivf_add_f16(lb_gpu_ivf *p, int64_t n, const uint16_t *vectors, const 
 int lb_gpu_ivf_add_f16_device(lb_gpu_ivf *p, int64_t n, const uint16_t *d_vectors, const int64_t *d_ids);
 int lb_gpu_ivf_add_i8(lb_gpu_ivf *p, int64_t n, const int8_t *vectors, const int64_t *ids); /* an int8 handle's add */
 int lb_gpu_ivf_add_i8_device(lb_gpu_ivf *p, int64_t n, const int8_t *d_vectors, const int64_t *d_ids);
+int lb_gpu_ivf_add_u8(lb_gpu_ivf *p, int64_t n, const uint8_t *vectors, const int64_t *ids); /* a uint8 handle's add */
+int lb_gpu_ivf_add_u8_device(lb_gpu_ivf *p, int64_t n, const uint8_t *d_vectors, const int64_t *d_ids);
 int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes); /* [nlist] */
 int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
@@ -919,6 +948,12 @@ int lb_gpu_ivf_search_i8_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, i
                              const lb_cancel *ctx);
 int lb_gpu_ivf_search_i8_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, float *d_dist,
                                     int64_t *d_labels, void *stream, const lb_cancel *ctx);
+/* a uint8 handle's searches: uint8 queries */
+int lb_gpu_ivf_search_u8(lb_gpu_ivf *p, int64_t nq, const uint8_t *queries, int k, int nprobe, float *dist, int64_t *labels);
+int lb_gpu_ivf_search_u8_ctx(lb_gpu_ivf *p, int64_t nq, const uint8_t *queries, int k, int nprobe, float *dist, int64_t *labels,
+                             const lb_cancel *ctx);
+int lb_gpu_ivf_search_u8_device_ctx(lb_gpu_ivf *p, int64_t nq, const uint8_t *d_queries, int k, int nprobe, float *d_dist,
+                                    int64_t *d_labels, void *stream, const lb_cancel *ctx);
 /* the same searches under a row bitmap given with the call ("call bitmap" above); d_bitmap is device memory */
 int lb_gpu_ivf_search_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap, int64_t nbits,
                                  int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
@@ -928,6 +963,11 @@ int lb_gpu_ivf_search_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const float *
 int lb_gpu_ivf_search_i8_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *queries, int k, int nprobe, const uint8_t *bitmap,
                                     int64_t nbits, int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
 int lb_gpu_ivf_search_i8_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const int8_t *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                           int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
+                                           const lb_cancel *ctx);
+int lb_gpu_ivf_search_u8_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const uint8_t *queries, int k, int nprobe, const uint8_t *bitmap,
+                                    int64_t nbits, int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_ivf_search_u8_bitmap_device_ctx(lb_gpu_ivf *p, int64_t nq, const uint8_t *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
                                            int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
                                            const lb_cancel *ctx);
 /* the row filter, as lb_gpu_bq_set_filter / _filter_int64 / _filter_float32 / _nvisible */
@@ -961,7 +1001,7 @@ int lb_gpu_ivf_last_build_timing(lb_gpu_ivf *p, float *ms);
  *   n_removed    nullable; the number of rows this call newly removed.
  *   errors       n == 0 is LB_OK; a NULL handle, n < 0, or n > 0 with a null pointer: LB_ERR_INVALID_ARG, answered before a device
  *                is touched and with nothing written.
- *   searches     every lb_gpu_ivf_search* entry point (host and device forms, _ctx, _i8; float32, float16 and int8 handles)
+ *   searches     every lb_gpu_ivf_search* entry point (host and device forms, _ctx, _i8, _u8; float32, float16, int8 and uint8 handles)
  *                answers the exact k-NN among the rows of the probed lists that are live AND pass the filter, in ascending
  *                (distance, row position) order: bit for bit what a fresh handle with the same centroids holding only the live
  *                rows, in their order, with ids = the old labels and the same filter restricted to them would answer (without ids

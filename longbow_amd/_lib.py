@@ -225,6 +225,9 @@ SIGNATURES = [
     ("lb_gpu_ivf_new_i8", _vp, [_i, _i, _i, _i, _i, _vp, _ip]),
     ("lb_gpu_ivf_add_i8", _i, [_vp, _i64, _vp, _vp]),
     ("lb_gpu_ivf_add_i8_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivf_new_u8", _vp, [_i, _i, _i, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivf_add_u8", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivf_add_u8_device", _i, [_vp, _i64, _vp, _vp]),
     ("lb_gpu_ivf_free", None, [_vp]),
     ("lb_gpu_ivf_last_error", C.c_char_p, [_vp]),
     ("lb_gpu_ivf_dim", _i, [_vp]),
@@ -245,10 +248,15 @@ SIGNATURES = [
     ("lb_gpu_ivf_search_i8", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
     ("lb_gpu_ivf_search_i8_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
     ("lb_gpu_ivf_search_i8_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_u8", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+    ("lb_gpu_ivf_search_u8_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_u8_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_ivf_search_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
     ("lb_gpu_ivf_search_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_ivf_search_i8_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
     ("lb_gpu_ivf_search_i8_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_u8_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_ivf_search_u8_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     ("lb_gpu_ivf_set_filter", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivf_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_ivf_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),

@@ -1,4 +1,5 @@
-// lb_u8_exact.h -- the uint8 arithmetic of one (row, query) pair, for kernels_u8.hip (the flat uint8 index).  It is the
+// lb_u8_exact.h -- the uint8 arithmetic of one (row, query) pair, for kernels_u8.hip (the flat uint8 index) and
+// kernels_ivf_u8.hip (the list scan of a uint8 IVF-Flat handle).  It is the
 // reference's only DataTypeUint8 registry kernel, euclideanUint8Unrolled4x (internal/simd/simd_baseline.go:198-220, reached
 // through internal/simd/dispatch.go:250):
 //   four f32 chains over the residues i mod 4 of i < 4 floor(D / 4), the tail elements into chain 0; each term is
@@ -22,6 +23,17 @@ constexpr uint32_t U8_EXACT_S = 1u << 24; // S up to here: every f32 add of the 
 
 // the value of a pair whose exact integer sum is S <= 2^24
 __device__ __forceinline__ float u8_value_of_s(uint32_t S) { return (float)sqrt((double)(float)S); }
+
+// The value of a pair whose four exact chain sums S_j = sum over i = j mod 4 of (a_i - b_i)^2 (the tail elements in S_0) are each
+// <= 2^24, whatever their total: every partial sum of chain j is an integer no larger than S_j, so every add inside every chain
+// is exact and s_j = float(S_j); the three adds of the chains then round as the reference's do.  That is every pair for
+// D <= 1032 (258 * 4), and S up to 2^26.  With the total <= 2^24 too the three adds are exact and this is u8_value_of_s(S).
+__device__ __forceinline__ float u8_value_of_chains(uint32_t S0, uint32_t S1, uint32_t S2, uint32_t S3)
+{
+#pragma clang fp contract(off)
+    const float sum = (((float)S0 + (float)S1) + (float)S2) + (float)S3;
+    return (float)sqrt((double)sum);
+}
 
 // a lower bound of the reference value of a pair with the exact sum S (any S): the float nearest the bound above is at most
 // the reference's sum, which is a float no smaller than the bound, and sqrt and the roundings are monotone

@@ -301,6 +301,77 @@ class IVFFlatInt8(RemovalMixin, RowFilterMixin, IVFBase):
         return float(out.value)
 
 
+def rows_u8(vectors, dims):
+    """rows or queries for a uint8 handle -> np.uint8 [n, dims], contiguous; np.uint8 arrays only"""
+    v = np.asarray(vectors)
+    if v.dtype != np.uint8:
+        raise TypeError(f"a uint8 index takes np.uint8 arrays, got {v.dtype}")
+    v = np.ascontiguousarray(v)
+    v = v.reshape(-1, v.shape[-1]) if v.size else v.reshape(0, dims)
+    if v.shape[1] != dims:
+        raise ValueError(f"vector dimension {v.shape[1]} does not match {dims}")
+    return v
+
+
+class IVFFlatUint8(RemovalMixin, RowFilterMixin, IVFBase):
+    """lb_gpu_ivf over uint8 rows (lb_gpu_ivf_new_u8): metric 0 (L2) alone, centroids f32 [nlist, dims]; order 0 SEQ / 1 UNROLL4
+    is the coarse index's and decides lists and probes alone.  add, search and their device-pointer forms take uint8 rows and
+    uint8 queries, np.uint8 arrays only (converting other data here would change the vectors silently).  The distances are the
+    flat uint8 index's (gpu.NewUint8Index), and with every list probed so is the result.  Row filters, call bitmaps, removal and
+    compaction as on IVFFlat."""
+    _prefix = "lb_gpu_ivf"
+    _timing_slots = 4
+
+    def __init__(self, centroids, metric=0, order=0, device=0, lib=None):
+        self._h = None  # (Close() and __del__ find this when creation fails below)
+        c = np.ascontiguousarray(centroids, np.float32)
+        if c.ndim != 2 or c.shape[0] == 0 or c.shape[1] == 0:
+            raise ValueError("centroids must be a non-empty [nlist, dims] array")
+        if metric != 0:
+            raise ValueError("a uint8 IVF-Flat handle takes metric 0 (L2): the reference has a Euclidean uint8 kernel alone")
+        lib = lib or _lib.require_gpu(device)
+        st = C.c_int(0)
+        h = lib.lb_gpu_ivf_new_u8(device, c.shape[1], metric, order, c.shape[0], c.ctypes.data, C.byref(st))
+        if not h:
+            _lib.check(st.value or 7)
+        self._lib = lib
+        self._h = C.c_void_p(h)
+        self.device = device
+        self.nlist, self.dims = c.shape
+        self.metric, self.order = metric, order
+
+    @property
+    def dtype(self):
+        """3 (lb_gpu_ivf_dtype)"""
+        return int(self._lib.lb_gpu_ivf_dtype(self._h))
+
+    def add(self, vectors, ids=None):
+        self._add(rows_u8(vectors, self.dims), ids, "add_u8")
+
+    def add_device(self, n, d_vectors, d_ids=None):
+        """d_vectors: uint8 rows"""
+        self._check(self._fn("add_u8_device")(self._h, n, d_vectors, d_ids))
+        self._has_ids = self._has_ids or d_ids is not None
+
+    def search(self, queries, k, nprobe, ctx=None, bitmap=None, bitmap_stride=0):
+        """uint8 queries -> (labels [nq, k], dist [nq, k]), as IVFFlat.search (bitmap: lb_gpu_ivf_search_u8_bitmap_ctx)"""
+        return self._search_host("search_u8", rows_u8(queries, self.dims), k, nprobe, ctx, bitmap, bitmap_stride)
+
+    def search_device(self, nq, d_queries, k, nprobe, d_dist, d_labels, stream=None, ctx=None, d_bitmap=None, nbits=0, bitmap_stride=0):
+        """d_queries: uint8 [nq, dims]; d_bitmap as IVFFlat.search_device"""
+        self._search_dev("search_u8", nq, d_queries, k, nprobe, d_dist, d_labels, stream, ctx, d_bitmap, nbits, bitmap_stride)
+
+    def last_timing(self):
+        """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
+        return super().last_timing()
+
+    def last_build_timing(self):
+        """ms of the last profiled build of the visible lists (a filter call or an add under a filter): its launches alone"""
+        out = C.c_float(0)
+        self._check(self._lib.lb_gpu_ivf_last_build_timing(self._h, C.byref(out)))
+        return float(out.value)
+
+
 @dataclass
 class IVFFlatConfig:
     """pluggable_index.go:100-104"""

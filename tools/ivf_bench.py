@@ -1,6 +1,6 @@
 """IVF-Flat index (exact k-NN over the probed lists) against the brute-force f32 index on the same rows: one JSON line.
 
-    python tools/ivf_bench.py [--rows 1000000] [--dim 768] [--nlist 256] [--k 100] [--dtype {f32,f16,both,int8}] [--profile-reps 1]
+    python tools/ivf_bench.py [--rows 1000000] [--dim 768] [--nlist 256] [--k 100] [--dtype {f32,f16,both,int8,uint8}] [--profile-reps 1]
 
 Rows and queries come from the seeded device fill (uniform in [-0.5, 0.5)); the centroids are nlist of the rows (ivf.train with
 max_iter = 0 returns its init rows).  Per cell (nprobe x nq): the p50 of the whole search through the device-pointer entry point
@@ -22,6 +22,13 @@ queries) beside the float32 handle over the same values widened, in one process,
 handles' distances are different arithmetic (the reference's DataTypeInt8 kernels against its f32 chains), so what is asserted in
 every cell is what must be equal: assignments, list sizes and search stats (the same lists probed).  For every nq the int8 handle
 with every list probed is also asserted equal, labels and distances, to a flat int8 index over the same rows.
+
+--dtype uint8 draws uniform bytes and runs the uint8 handle (lb_gpu_ivf_new_u8, uint8 queries) beside the int8 handle over the
+same bytes XOR 0x80 with the centroids shifted by 128, in one process: the same lists, the same bytes scanned.  First, for every
+nq, the uint8 handle with every list probed is asserted equal, labels and distances, to a flat uint8 index over the same rows.
+Then per cell each handle's profiled runs take turns, at least two each, and the scan slot of every run is printed beside the
+medians, so that the int8 handle's own run-to-run spread is known; hbm_bytes holds both handles' and a float32 handle's over the
+widened rows.
 """
 import argparse
 import ctypes as C
@@ -68,6 +75,79 @@ def measured(steps, rows_scanned, dim, elem_bytes):
             "scan_share_of_8tb": scan_bytes / max(float(med[2]), 1e-6) * 1e3 / HBM_BYTES_PER_S}
 
 
+def main_u8(a, lib):
+    """--dtype uint8: the uint8 handle against the int8 handle over the same bytes XOR 0x80 (every value less 128) and centroids
+    shifted by 128, so that both hold the same lists and scan the same bytes"""
+    reps = max(2, a.profile_reps)
+    out = {"rows": a.rows, "dim": a.dim, "nlist": a.nlist, "k": a.k, "dtype": a.dtype, "profile_reps": reps, "shader_clock_mhz_before": clock_mhz(lib)}
+    nqmax = max(a.nq)
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    XU = torch.randint(0, 256, (a.rows, a.dim), dtype=torch.uint8, device="cuda", generator=gen)
+    QU = torch.randint(0, 256, (nqmax, a.dim), dtype=torch.uint8, device="cuda", generator=gen)
+    XS, QS = (XU ^ 0x80).view(torch.int8), (QU ^ 0x80).view(torch.int8)
+    cent = XU[torch.arange(a.nlist, device="cuda") * (a.rows // a.nlist)].to(torch.float32).cpu().numpy()  # nlist of the rows
+    handles = {"u8": ivf.IVFFlatUint8(cent), "i8": ivf.IVFFlatInt8(cent - np.float32(128))}
+    for name, h in handles.items():
+        h.reserve(a.rows)
+        t0 = time.perf_counter()
+        h.add_device(a.rows, (XU if name == "u8" else XS).data_ptr())
+        add_s = time.perf_counter() - t0
+        out.setdefault("add", {})[name] = {"seconds": add_s, "rows_per_s": a.rows / add_s}
+        out.setdefault("hbm_bytes", {})[name] = h.hbm_bytes
+    sizes = handles["u8"].list_sizes()
+    assert np.array_equal(sizes, handles["i8"].list_sizes()), "the two handles' lists differ"
+    out["lists"] = {"min": int(sizes.min()), "median": int(np.median(sizes)), "max": int(sizes.max()), "empty": int((sizes == 0).sum())}
+    wide = ivf.IVFFlat(cent)  # (for its bytes alone)
+    wide.reserve(a.rows)
+    step = 65536
+    for r0 in range(0, a.rows, step):
+        W = XU[r0:r0 + step].to(torch.float32)
+        torch.cuda.synchronize()  # (an add returns with its stream drained)
+        wide.add_device(W.shape[0], W.data_ptr())
+    assert np.array_equal(sizes, wide.list_sizes()), "the float32 handle's lists differ"
+    out["hbm_bytes"]["f32"] = wide.hbm_bytes
+    wide.Close()
+    flat = gpu.NewUint8Index(gpu.GPUConfig(DeviceID=0, Dimension=a.dim, Metric=0, DataType=gpu.DataType.Uint8))
+    flat.reserve(a.rows)
+    flat.add_device(a.rows, XU.data_ptr())
+    D = torch.empty((nqmax, a.k), dtype=torch.float32, device="cuda")
+    L = torch.empty((nqmax, a.k), dtype=torch.int64, device="cuda")
+    FD, FL = torch.empty_like(D), torch.empty_like(L)
+    torch.cuda.synchronize()
+    for nq in a.nq:  # first: every list probed is the flat uint8 index, bit for bit
+        flat.search_device(nq, QU.data_ptr(), a.k, FD.data_ptr(), FL.data_ptr())
+        handles["u8"].search_device(nq, QU.data_ptr(), a.k, a.nlist, D.data_ptr(), L.data_ptr())
+        assert torch.equal(L[:nq], FL[:nq]), f"every list probed: labels differ from the flat uint8 index at nq {nq}"
+        assert torch.equal(D[:nq], FD[:nq]), f"every list probed: distances differ from the flat uint8 index at nq {nq}"
+    flat.Close()
+    out["equal_flat_u8"] = True
+    cells = []
+    for nq in a.nq:
+        for nprobe in a.nprobe:
+            run = {name: (lambda h=h, q=(QU if name == "u8" else QS): h.search_device(nq, q.data_ptr(), a.k, nprobe, D.data_ptr(), L.data_ptr()))
+                   for name, h in handles.items()}
+            ms = {name: p50_ms(run[name]) for name in handles}
+            steps = {name: [] for name in handles}
+            for _ in range(reps):  # the handles take turns
+                for name, h in handles.items():
+                    h.set_profiling(True)
+                    run[name]()
+                    h.set_profiling(False)
+                    steps[name].append(h.last_timing())
+            st = handles["u8"].last_search_stats()
+            assert handles["i8"].last_search_stats() == st, f"search stats differ at nq {nq} nprobe {nprobe}"
+            cell = {"nq": nq, "nprobe": nprobe, "rows_scanned": st[1], "max_rows_per_query": st[2]}
+            for name in handles:
+                cell[name] = dict(measured(steps[name], st[1], a.dim, 1), p50_ms=ms[name], scan_ms_runs=[float(s[2]) for s in steps[name]])
+            cell["scan_u8_over_i8"] = cell["u8"]["scan_ms"] / max(cell["i8"]["scan_ms"], 1e-9)
+            cells.append(cell)
+    out["cells"] = cells
+    out["shader_clock_mhz_after"] = clock_mhz(lib)
+    print(json.dumps(out))
+    for h in handles.values():
+        h.Close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=1_000_000)
@@ -77,10 +157,12 @@ def main():
     ap.add_argument("--nprobe", type=int, nargs="*", default=[1, 8, 32, 256])
     ap.add_argument("--nq", type=int, nargs="*", default=[1, 8, 64, 1024])
     ap.add_argument("--train-rows", type=int, default=100_000)
-    ap.add_argument("--dtype", choices=("f32", "f16", "both", "int8"), default="f32")
+    ap.add_argument("--dtype", choices=("f32", "f16", "both", "int8", "uint8"), default="f32")
     ap.add_argument("--profile-reps", type=int, default=1, help="profiled searches per cell and handle (the slots are their medians)")
     a = ap.parse_args()
     lib = _lib.require_gpu(0)  # (raises without a GPU: nothing here falls back)
+    if a.dtype == "uint8":
+        return main_u8(a, lib)
     out = {"rows": a.rows, "dim": a.dim, "nlist": a.nlist, "k": a.k, "dtype": a.dtype, "profile_reps": a.profile_reps,
            "shader_clock_mhz_before": clock_mhz(lib)}
     X = torch.empty((a.rows, a.dim), dtype=torch.float32, device="cuda")
