@@ -561,6 +561,54 @@ int64_t lb_gpu_pq_nvisible(const lb_gpu_pq *p);
 int lb_gpu_pq_set_profiling(lb_gpu_pq *p, int enable);
 int lb_gpu_pq_last_timing(const lb_gpu_pq *p, float ms[2]);
 
+/* ---- PQ4: 16-centroid codebooks, packed 4-bit codes, exact ADC k-NN ------------------------------
+ * The reference treats small K as a case of its own: Encode's K <= 16 branch (encodeSequential, internal/pq/encoder.go:87-120),
+ * BuildADCTable and ADCDistance at stride K (adc_table.go:46, 77-92).  This handle family is that case at K = 16.
+ *   codebooks   the reference's serialised blob, parsed and validated as by lb_gpu_pq_new.  A blob that does not parse is
+ *               LB_ERR_INVALID_ARG; one that parses needs K == 16, M in 1..1024 and dims <= LB_MAX_DIM, anything else is
+ *               LB_ERR_UNSUPPORTED.  Checked in the order LB_ERR_INVALID_ARG, LB_ERR_UNSUPPORTED, LB_ERR_NO_DEVICE, before a
+ *               device is touched; a refused call writes nothing but *out_status.
+ *   code        of a vector, per subspace: simd.L2Squared (UNROLL4 order, no sqrt) to the 16 centroids in order; bestDist starts
+ *               at FLT_MAX, the compare is strict <, the first winner is kept; when no distance is below FLT_MAX the code is 0.
+ *               (Not lb_gpu_pq_encode's rule, which compares the rounded square roots starting from centroid 0.)
+ *   ABI rows    across the ABI a code row is M bytes, one per subspace, each below 16: what the reference's Encode returns.
+ *               add_codes and add_codes_device refuse a batch that holds a byte of 16 or more with LB_ERR_INVALID_ARG and a
+ *               last_error text; a refused batch commits nothing.
+ *   memory      in HBM a row is P = ceil(M / 2) bytes at stride P: byte b holds code 2b in its low nibble and code 2b + 1 in its
+ *               high nibble, the spare high nibble of an odd M is 0.  hbm_bytes reports the rows allocated at that stride plus
+ *               the codebooks.  get_codes unpacks to M bytes a row.
+ *   table       pq.BuildADCTable: table[j * 16 + c] as float[M * 16].
+ *   distance    of a query and a row with codes c: float32(sqrt(float64(s))), s the f32 sum ((0 + table[0*16 + c_0]) +
+ *               table[1*16 + c_1]) + ... in j order, no reassociation and no FMA: ADCDistance's sum under the batch form's
+ *               square root.  adc_distance_batch: rows [row0, row0 + n) of the stored ones against a caller's table.
+ *   search      the first k rows in ascending (distance, row) order, every NaN after +inf; the label is the row.  With fewer
+ *               than k rows they come first, then label -1 with distance FLT_MAX.  k in 1..4096, above is LB_ERR_UNSUPPORTED;
+ *               nq at most 65536; a handle holds at most 2^32 - 1 rows.  ctx (nullable) is polled before every launch.
+ *   not here    row filters, call bitmaps and removal; search combining, rerank, decode and profiling; an IVF-PQ4 handle; a
+ *               byte-quantised prefilter; Go and C++ mirrors. */
+typedef struct lb_gpu_pq4 lb_gpu_pq4;
+lb_gpu_pq4 *lb_gpu_pq4_new(int device, const uint8_t *codebook_blob, size_t len, int *out_status);
+void lb_gpu_pq4_free(lb_gpu_pq4 *p);
+const char *lb_gpu_pq4_last_error(const lb_gpu_pq4 *p);
+int lb_gpu_pq4_m(const lb_gpu_pq4 *p);
+int lb_gpu_pq4_dims(const lb_gpu_pq4 *p);
+int64_t lb_gpu_pq4_ntotal(const lb_gpu_pq4 *p);
+int64_t lb_gpu_pq4_hbm_bytes(const lb_gpu_pq4 *p);
+int lb_gpu_pq4_reserve(lb_gpu_pq4 *p, int64_t n_total);
+int lb_gpu_pq4_add_codes(lb_gpu_pq4 *p, int64_t n, const uint8_t *codes);
+int lb_gpu_pq4_add_codes_device(lb_gpu_pq4 *p, int64_t n, const uint8_t *d_codes);
+int lb_gpu_pq4_add_vectors(lb_gpu_pq4 *p, int64_t n, const float *vectors);
+int lb_gpu_pq4_add_vectors_device(lb_gpu_pq4 *p, int64_t n, const float *d_vectors);
+int lb_gpu_pq4_get_codes(lb_gpu_pq4 *p, int64_t row0, int64_t n, uint8_t *codes);
+int lb_gpu_pq4_encode(lb_gpu_pq4 *p, int64_t n, const float *vectors, uint8_t *codes);
+int lb_gpu_pq4_encode_device(lb_gpu_pq4 *p, int64_t n, const float *d_vectors, uint8_t *d_codes, void *stream);
+int lb_gpu_pq4_build_adc_table(lb_gpu_pq4 *p, const float *query, float *table);
+int lb_gpu_pq4_adc_distance_batch(lb_gpu_pq4 *p, const float *table, int64_t row0, int64_t n, float *results);
+int lb_gpu_pq4_search(lb_gpu_pq4 *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels);
+int lb_gpu_pq4_search_ctx(lb_gpu_pq4 *p, int64_t nq, const float *queries, int k, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_pq4_search_device_ctx(lb_gpu_pq4 *p, int64_t nq, const float *d_queries, int k, float *d_dist, int64_t *d_labels,
+                                 void *stream, const lb_cancel *ctx);
+
 /* ---- PQ training --------------------------------------------------------------
  * pq.(*PQEncoder).Train (encoder.go:38-73): TrainKMeans (kmeans.go:64-151) per subspace.  vectors: n rows of f32[dims];
  * subspace m trains on the sub-vectors v_i = row_i[m*sub, (m+1)*sub), sub = dims / M, exactly as TrainKMeans(., n, sub, K,
@@ -583,7 +631,8 @@ int lb_gpu_pq_last_timing(const lb_gpu_pq *p, float ms[2]);
  *   empty cluster c in iteration it: row draw(seed, m, K + it*K + c) mod n
  * blob receives the persistence.go layout that lb_gpu_pq_new reads; blob_len must equal lb_gpu_pq_blob_bytes(dims, M, K)
  * (12 + M*K*(dims/M)*4; 0 for dims, M or K <= 0 or dims % M != 0).  K is a run-time bound in 1..256 (the reference's own
- * tests train k = 3): a blob with K != 256 serialises correctly and is still refused by lb_gpu_pq_new.
+ * tests train k = 3): a blob with K != 256 serialises correctly and is still refused by lb_gpu_pq_new
+ * (K = 16: lb_gpu_pq4_new takes it).
  * Checked before a device is touched, in this order: LB_ERR_INVALID_ARG (NULL vectors / blob, M <= 0, dims % M != 0, n < K,
  * max_iter < 0, blob_len, an init_rows entry outside [0, n)); LB_ERR_UNSUPPORTED (K outside 1..256, dims > LB_MAX_DIM,
  * n >= 2^31); LB_ERR_NO_DEVICE.  All rows stay resident for the iterations (n*dims*4 bytes, plus 8 bytes per row and

@@ -7,6 +7,7 @@ library drops in behind:
                          (GPUConfig.DataType) or uint8 (NewUint8Index)
   longbow_amd.simd  <->  internal/simd  (MetricType, *DistanceBatch*, ADCDistanceBatch)
   longbow_amd.pq    <->  internal/pq    (BuildADCTable, ADCDistanceBatch, codebook blob)
+  longbow_amd.pq4   <->  internal/pq at K = 16 (Encode's encodeSequential branch): 4-bit codes packed two to a byte + exact ADC k-NN
   longbow_amd.bq    <->  internal/store BQEncoder (sign-bit codes, Hamming distances) + exact Hamming k-NN
   longbow_amd.sq8   <->  internal/store SQ8Encoder (uint8 codes between per-dimension bounds) + exact integer k-NN
   longbow_amd.ivf   <->  internal/store IVFFlatConfig / "ivf_flat" (a stub there): exact k-NN over the probed lists
@@ -24,4 +25,4 @@ is missing.
 from . import _lib  # noqa: F401
 from .simd import MetricType  # noqa: F401
 
-__all__ = ["gpu", "simd", "pq", "bq", "sq8", "ivf", "ivfpq", "ivfsq8", "ivfbq", "sharded", "arrow_io", "hybrid", "MetricType"]
+__all__ = ["gpu", "simd", "pq", "pq4", "bq", "sq8", "ivf", "ivfpq", "ivfsq8", "ivfbq", "sharded", "arrow_io", "hybrid", "MetricType"]

@@ -154,6 +154,26 @@ SIGNATURES = [
     ("lb_gpu_pq_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
     ("lb_gpu_pq_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
     ("lb_gpu_pq_nvisible", _i64, [_vp]),
+    ("lb_gpu_pq4_new", _vp, [_i, _vp, _sz, _ip]),
+    ("lb_gpu_pq4_free", None, [_vp]),
+    ("lb_gpu_pq4_last_error", C.c_char_p, [_vp]),
+    ("lb_gpu_pq4_m", _i, [_vp]),
+    ("lb_gpu_pq4_dims", _i, [_vp]),
+    ("lb_gpu_pq4_ntotal", _i64, [_vp]),
+    ("lb_gpu_pq4_hbm_bytes", _i64, [_vp]),
+    ("lb_gpu_pq4_reserve", _i, [_vp, _i64]),
+    ("lb_gpu_pq4_add_codes", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_pq4_add_codes_device", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_pq4_add_vectors", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_pq4_add_vectors_device", _i, [_vp, _i64, _vp]),
+    ("lb_gpu_pq4_get_codes", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_pq4_encode", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_pq4_encode_device", _i, [_vp, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_pq4_build_adc_table", _i, [_vp, _vp, _vp]),
+    ("lb_gpu_pq4_adc_distance_batch", _i, [_vp, _vp, _i64, _i64, _vp]),
+    ("lb_gpu_pq4_search", _i, [_vp, _i64, _vp, _i, _vp, _vp]),
+    ("lb_gpu_pq4_search_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp]),
+    ("lb_gpu_pq4_search_device_ctx", _i, [_vp, _i64, _vp, _i, _vp, _vp, _vp, _vp]),
     ("lb_gpu_pq_train", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp]),
     ("lb_gpu_pq_train_device", _i, [_i, _i, _i, _i, _i64, _vp, _i, _u64, _vp, _vp, _sz, _vp, _vp, _vp]),
     ("lb_gpu_pq_blob_bytes", _sz, [_i, _i, _i]),

@@ -15,6 +15,7 @@
 #include "lb_host.h"
 
 #include <algorithm>
+#include <cmath>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -464,6 +465,35 @@ int filter_column(FilteredHandle *h, const T *column, int64_t n, T value, int op
         f.on = true;
         return LB_OK;
     });
+}
+
+// ---- the sampled threshold of an ADC search -------------------------------------------------------------------------------
+// Sampled admission threshold (same reasoning as index_search.hip: sample_plan): one row in `stride` is scored
+// exactly, the m-th best sample entry becomes tau, and the codes are walked once.  About m*stride rows
+// pass (4096 at stride 512); fewer than k or more than the list holds is detected by the select and
+// the query is redone by the bootstrap schedule.  Two-level m-th minimum: the sample (195k entries at
+// 100M rows) is larger than one list.  Stride 512 with a 16384-entry list (mean + 5 sigma = 11.3k
+// admitted rows) instead of stride 256 / 8192 halves the sampling pass (49 -> 25 us at 100M rows).
+// samp_count == 0: no sampled pass, the list keeps the `cap` given.  (tests/adc_bound.py: plan() restates this.)  The plan of the
+// ADC searches of pq.hip and pq4.hip; below kAdcSampleMinRows rows a search stays on the bootstrap schedule.
+constexpr int64_t kAdcSampleMinRows = 65536;
+struct AdcSamplePlan { uint32_t samp_count; int samp_m; uint32_t cap; };
+
+inline AdcSamplePlan adc_sample_plan(int64_t n_vis, int k, uint32_t cap)
+{
+    if (n_vis >= kAdcSampleMinRows && n_vis < ((int64_t)1 << 32)) {
+        const uint32_t cap_s = std::max<uint32_t>(16384u, cap);
+        const int64_t stride = n_vis >= ((int64_t)8192 * 512) ? 512 : 256;
+        const int64_t cnt = std::max<int64_t>(8192, (n_vis + stride - 1) / stride);
+        const double lambda = (double)k * (double)cnt / (double)n_vis;
+        const int m = std::max(8, (int)std::ceil(lambda + 5.0 * std::sqrt(lambda) + 4.0));
+        const double loose = (double)m * ((double)n_vis / (double)cnt) * (1.0 + 5.0 / std::sqrt((double)m));
+        // The last condition is launch_sample_topm's own: its groups of 8192 = ST_THREADS * ST_PER entries (kernels_scan.hip)
+        // number ceil(cnt / 8192) <= 8192 / m (cnt >= 8192, so at least one), hence groups * m <= 8192 <= 16384 <= cap_s.  A
+        // plan made here is never refused there; the searches' threshold() treats a refusal as an internal error.
+        if (m <= 32 && loose <= (double)(cap_s - (uint32_t)k) && cnt <= (int64_t)8192 * (8192 / m)) return {(uint32_t)cnt, m, cap_s};
+    }
+    return {0, 0, cap};
 }
 
 // ---- k-NN of host queries -----------------------------------------------------------------------------------------------

@@ -180,32 +180,6 @@ struct ScratchLoan {
     }
 };
 
-// Sampled admission threshold (same reasoning as index_search.hip: sample_plan): one row in `stride` is scored
-// exactly, the m-th best sample entry becomes tau, and the codes are walked once.  About m*stride rows
-// pass (4096 at stride 512); fewer than k or more than the list holds is detected by the select and
-// the query is redone by the bootstrap schedule.  Two-level m-th minimum: the sample (195k entries at
-// 100M rows) is larger than one list.  Stride 512 with a 16384-entry list (mean + 5 sigma = 11.3k
-// admitted rows) instead of stride 256 / 8192 halves the sampling pass (49 -> 25 us at 100M rows).
-// samp_count == 0: no sampled pass, the list keeps the `cap` given.  (tests/adc_bound.py: plan() restates this.)
-struct SamplePlan { uint32_t samp_count; int samp_m; uint32_t cap; };
-
-SamplePlan sample_plan(int64_t n_vis, int k, uint32_t cap)
-{
-    if (n_vis >= 65536 && n_vis < ((int64_t)1 << 32)) {
-        const uint32_t cap_s = std::max<uint32_t>(16384u, cap);
-        const int64_t stride = n_vis >= ((int64_t)8192 * 512) ? 512 : 256;
-        const int64_t cnt = std::max<int64_t>(8192, (n_vis + stride - 1) / stride);
-        const double lambda = (double)k * (double)cnt / (double)n_vis;
-        const int m = std::max(8, (int)std::ceil(lambda + 5.0 * std::sqrt(lambda) + 4.0));
-        const double loose = (double)m * ((double)n_vis / (double)cnt) * (1.0 + 5.0 / std::sqrt((double)m));
-        // The last condition is launch_sample_topm's own: its groups of 8192 = ST_THREADS * ST_PER entries (kernels_scan.hip)
-        // number ceil(cnt / 8192) <= 8192 / m (cnt >= 8192, so at least one), hence groups * m <= 8192 <= 16384 <= cap_s.  A
-        // plan made here is never refused there; PqSearch::threshold treats a refusal as an internal error.
-        if (m <= 32 && loose <= (double)(cap_s - (uint32_t)k) && cnt <= (int64_t)8192 * (8192 / m)) return {(uint32_t)cnt, m, cap_s};
-    }
-    return {0, 0, cap};
-}
-
 // One device batch: the passes of its queries in the order they are enqueued on s.  Under a row filter the search walks the
 // v.n positions of the ascending list of visible rows (kernels_pq_list.hip) instead of the p->n rows: the plan, the chunk
 // schedule and the selects count positions, the entries carry rows.
@@ -215,7 +189,7 @@ struct PqSearch {
     PqScratch &sc;
     hipStream_t s;
     int nq, k;
-    SamplePlan plan;
+    AdcSamplePlan plan;
     bool prefilter, prof; // prefilter: a sampled plan with the byte-table pass on
     EmitArgs em;          // the search's last select writes the k results AND the slot's status word into pinned host memory (no D2H copy)
     int64_t stats[6];     // {sampled plan, four-query pass, two-query pass, single prefilter pass, bootstrap redo, safe redo} (queries)
@@ -614,7 +588,7 @@ int lb_gpu_pq_search_device_ctx(lb_gpu_pq *p, int64_t nq, const float *d_queries
         LB_HIP(hipSetDevice(p->device));
         const RowView v = p->filter.view(p->n);
         // decided once, before the first launch: whether the queries take the sampled threshold and, with it, the prefilter
-        const SamplePlan plan = sample_plan(v.n, k, std::max<uint32_t>(8192u, 4u * next_pow2_host((uint32_t)k)));
+        const AdcSamplePlan plan = adc_sample_plan(v.n, k, std::max<uint32_t>(8192u, 4u * next_pow2_host((uint32_t)k)));
         loan.sc = acquire_scratch(p, (int)nq, plan.cap, plan.samp_count);
         PqSearch a{p, v, *loan.sc, s, (int)nq, k, plan, plan.samp_count != 0 && p->prefilter.load() != 0, p->profiling.load() != 0,
                    EmitArgs{k, nullptr, d_dist, d_labels, loan.sc->h_flags.get()}, {plan.samp_count ? nq : 0, 0, 0, 0, 0, 0}};
