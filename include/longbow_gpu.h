@@ -584,8 +584,8 @@ int lb_gpu_pq_last_timing(const lb_gpu_pq *p, float ms[2]);
  *   search      the first k rows in ascending (distance, row) order, every NaN after +inf; the label is the row.  With fewer
  *               than k rows they come first, then label -1 with distance FLT_MAX.  k in 1..4096, above is LB_ERR_UNSUPPORTED;
  *               nq at most 65536; a handle holds at most 2^32 - 1 rows.  ctx (nullable) is polled before every launch.
- *   not here    row filters, call bitmaps and removal; search combining, rerank, decode and profiling; an IVF-PQ4 handle; a
- *               byte-quantised prefilter; Go and C++ mirrors. */
+ *   not here    row filters, call bitmaps and removal; search combining, rerank, decode and profiling (an IVF-PQ4 handle: lb_gpu_ivfpq4_*,
+ *               below); a byte-quantised prefilter; Go and C++ mirrors. */
 typedef struct lb_gpu_pq4 lb_gpu_pq4;
 lb_gpu_pq4 *lb_gpu_pq4_new(int device, const uint8_t *codebook_blob, size_t len, int *out_status);
 void lb_gpu_pq4_free(lb_gpu_pq4 *p);
@@ -1264,6 +1264,82 @@ int lb_gpu_ivfpq_remove_rows(lb_gpu_ivfpq *p, int64_t n, const int64_t *rows, in
 int64_t lb_gpu_ivfpq_nlive(const lb_gpu_ivfpq *p);
 int64_t lb_gpu_ivfpq_ndeleted(const lb_gpu_ivfpq *p);
 int lb_gpu_ivfpq_compact(lb_gpu_ivfpq *p, int64_t *old_rows, int64_t cap);
+
+/* ---- IVF-PQ4: exact ADC k-NN over the packed 4-bit codes of the probed lists --------------------
+ * The coarse partition of lb_gpu_ivf_* over the codes of lb_gpu_pq4_*: what lb_gpu_ivfpq_* is at K = 256, at K = 16.  A row costs
+ * P = ceil(M / 2) bytes instead of M, and a query's table M * 64 bytes instead of M * 1024.  Nothing is approximate beyond the
+ * codes themselves and WHICH lists are probed: given the codes and the probed lists the result is the exact ADC k-NN among their
+ * live, visible rows, bit for bit in lb_gpu_pq4_*'s arithmetic.  Every call, the lists, probes, ids, padding, stats, filters, call
+ * bitmaps, removal, compaction, locking, limits (nlist, k, rows, nprobe) and the order of argument checks are lb_gpu_ivfpq_*'s,
+ * word for word, "lb_gpu_pq_search" reading "lb_gpu_pq4_search"; lb_gpu_ivfpq4_new_residual makes a residual handle as
+ * lb_gpu_ivfpq_new_residual does.  What differs:
+ *   codebooks         the reference's serialised blob, parsed as by lb_gpu_pq_new.  One that parses needs K == 16, M in 1..1024,
+ *                     dims <= LB_MAX_DIM and nlist <= 65536: anything else, a well-formed blob of K = 256 included, is
+ *                     LB_ERR_UNSUPPORTED, after LB_ERR_INVALID_ARG and before LB_ERR_NO_DEVICE.
+ *   code of a row     lb_gpu_pq4_encode's (encodeSequential: L2Squared in UNROLL4 order to the 16 centroids in order, strict <
+ *                     from FLT_MAX, first wins, code 0 when nothing is below FLT_MAX) of the row, on a residual handle of
+ *                     res(x, list(x)) (one f32 subtraction a component).
+ *   get_codes         M bytes a row, one per subspace, each below 16, as lb_gpu_pq4_get_codes; u8[n * M], insertion order.
+ *   distance          float32(sqrt(float64(s))), s the f32 sum ((0 + table[0*16 + c_0]) + table[1*16 + c_1]) + ... in j order, no
+ *                     reassociation and no FMA; table = BuildADCTable(query) at stride 16, on a residual handle
+ *                     BuildADCTable(res(q, l)) for a row of probed list l.  nprobe >= nlist gives lb_gpu_pq4_search over the same
+ *                     codes on a plain handle, bit for bit: labels, order and distances.
+ *   memory            the packed codes are held in insertion order and, beside each of the two pairs of lists, once more in list
+ *                     order: 3 * P bytes a row, plus 12 bytes a row of lists and 8 of ids (156 B a row at M = 96, where
+ *                     lb_gpu_ivfpq_* holds 300); the filter's terms and a residual handle's copy of the centroids as there.
+ *   scratch           a residual search holds one table (M * 64 bytes) per pair (query, probed list) of a batch, bounded by the
+ *                     same 1 GiB: at M = 96 room for 174,762 tables, so a batch of 1024 queries is cut only beyond 170 probes;
+ *                     at M = 1024 for 16,384.  Rounds of slots, where one query's tables do not fit, as there.
+ *   last_timing       the five slots of lb_gpu_ivfpq_last_timing: probes, plan, tables (residual: residual queries and tables),
+ *                     scan, selection.
+ * Not here: the Go and C++ mirrors, Save / Load, adding ready-made codes with caller-given lists. */
+typedef struct lb_gpu_ivfpq4 lb_gpu_ivfpq4;
+lb_gpu_ivfpq4 *lb_gpu_ivfpq4_new(int device, const uint8_t *codebook_blob, size_t len, int order, int nlist, const float *centroids,
+                               int *out_status);
+lb_gpu_ivfpq4 *lb_gpu_ivfpq4_new_residual(int device, const uint8_t *codebook_blob, size_t len, int order, int nlist,
+                                        const float *centroids, int *out_status);
+int lb_gpu_ivfpq4_residual(const lb_gpu_ivfpq4 *p);
+void lb_gpu_ivfpq4_free(lb_gpu_ivfpq4 *p);
+const char *lb_gpu_ivfpq4_last_error(const lb_gpu_ivfpq4 *p);
+int lb_gpu_ivfpq4_dims(const lb_gpu_ivfpq4 *p);
+int lb_gpu_ivfpq4_m(const lb_gpu_ivfpq4 *p);
+int lb_gpu_ivfpq4_order(const lb_gpu_ivfpq4 *p);
+int lb_gpu_ivfpq4_nlist(const lb_gpu_ivfpq4 *p);
+int64_t lb_gpu_ivfpq4_ntotal(const lb_gpu_ivfpq4 *p);
+int64_t lb_gpu_ivfpq4_hbm_bytes(const lb_gpu_ivfpq4 *p);
+int lb_gpu_ivfpq4_get_centroids(lb_gpu_ivfpq4 *p, float *out);
+int lb_gpu_ivfpq4_reserve(lb_gpu_ivfpq4 *p, int64_t n_total);
+int lb_gpu_ivfpq4_add(lb_gpu_ivfpq4 *p, int64_t n, const float *vectors, const int64_t *ids);
+int lb_gpu_ivfpq4_add_device(lb_gpu_ivfpq4 *p, int64_t n, const float *d_vectors, const int64_t *d_ids);
+int lb_gpu_ivfpq4_get_codes(lb_gpu_ivfpq4 *p, int64_t row0, int64_t n, uint8_t *codes);
+int lb_gpu_ivfpq4_list_sizes(lb_gpu_ivfpq4 *p, int64_t *sizes);
+int lb_gpu_ivfpq4_assignments(lb_gpu_ivfpq4 *p, int64_t row0, int64_t n, int32_t *lists);
+int lb_gpu_ivfpq4_search(lb_gpu_ivfpq4 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
+int lb_gpu_ivfpq4_search_ctx(lb_gpu_ivfpq4 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
+                            const lb_cancel *ctx);
+int lb_gpu_ivfpq4_search_device_ctx(lb_gpu_ivfpq4 *p, int64_t nq, const float *d_queries, int k, int nprobe, float *d_dist,
+                                   int64_t *d_labels, void *stream, const lb_cancel *ctx);
+int lb_gpu_ivfpq4_search_bitmap_ctx(lb_gpu_ivfpq4 *p, int64_t nq, const float *queries, int k, int nprobe, const uint8_t *bitmap,
+                                   int64_t nbits, int64_t stride_bytes, float *dist, int64_t *labels, const lb_cancel *ctx);
+int lb_gpu_ivfpq4_search_bitmap_device_ctx(lb_gpu_ivfpq4 *p, int64_t nq, const float *d_queries, int k, int nprobe, const uint8_t *d_bitmap,
+                                          int64_t nbits, int64_t stride_bytes, float *d_dist, int64_t *d_labels, void *stream,
+                                          const lb_cancel *ctx);
+int lb_gpu_ivfpq4_set_filter(lb_gpu_ivfpq4 *p, const uint8_t *mask, int64_t n);
+int lb_gpu_ivfpq4_filter_int64(lb_gpu_ivfpq4 *p, const int64_t *column, int64_t n, int64_t value, int op, const uint8_t *validity,
+                              int64_t validity_offset, int combine);
+int lb_gpu_ivfpq4_filter_float32(lb_gpu_ivfpq4 *p, const float *column, int64_t n, float value, int op, const uint8_t *validity,
+                                int64_t validity_offset, int combine);
+int64_t lb_gpu_ivfpq4_nvisible(const lb_gpu_ivfpq4 *p);
+int lb_gpu_ivfpq4_last_search_stats(lb_gpu_ivfpq4 *p, int64_t out[4]);
+int lb_gpu_ivfpq4_set_profiling(lb_gpu_ivfpq4 *p, int enable);
+int lb_gpu_ivfpq4_last_timing(lb_gpu_ivfpq4 *p, float ms[5]);
+int lb_gpu_ivfpq4_last_build_timing(lb_gpu_ivfpq4 *p, float *ms);
+int lb_gpu_ivfpq4_remove(lb_gpu_ivfpq4 *p, int64_t n, const int64_t *labels, int64_t *n_removed);
+int lb_gpu_ivfpq4_remove_device(lb_gpu_ivfpq4 *p, int64_t n, const int64_t *d_labels, int64_t *n_removed);
+int lb_gpu_ivfpq4_remove_rows(lb_gpu_ivfpq4 *p, int64_t n, const int64_t *rows, int64_t *n_removed);
+int64_t lb_gpu_ivfpq4_nlive(const lb_gpu_ivfpq4 *p);
+int64_t lb_gpu_ivfpq4_ndeleted(const lb_gpu_ivfpq4 *p);
+int lb_gpu_ivfpq4_compact(lb_gpu_ivfpq4 *p, int64_t *old_rows, int64_t cap);
 
 /* ---- IVF-SQ8: exact integer k-NN over the codes of the probed lists ----------------------------
  * The coarse partition of lb_gpu_ivf_* over the codes of lb_gpu_sq8_* (FAISS's "IVF...,SQ8"): a query skips most rows, and a row

@@ -328,6 +328,43 @@ SIGNATURES = [
     ("lb_gpu_ivfpq_nlive", _i64, [_vp]),
     ("lb_gpu_ivfpq_ndeleted", _i64, [_vp]),
     ("lb_gpu_ivfpq_compact", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_ivfpq4_new", _vp, [_i, _vp, _sz, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivfpq4_new_residual", _vp, [_i, _vp, _sz, _i, _i, _vp, _ip]),
+    ("lb_gpu_ivfpq4_residual", _i, [_vp]),
+    ("lb_gpu_ivfpq4_free", None, [_vp]),
+    ("lb_gpu_ivfpq4_last_error", C.c_char_p, [_vp]),
+    ("lb_gpu_ivfpq4_dims", _i, [_vp]),
+    ("lb_gpu_ivfpq4_m", _i, [_vp]),
+    ("lb_gpu_ivfpq4_order", _i, [_vp]),
+    ("lb_gpu_ivfpq4_nlist", _i, [_vp]),
+    ("lb_gpu_ivfpq4_ntotal", _i64, [_vp]),
+    ("lb_gpu_ivfpq4_hbm_bytes", _i64, [_vp]),
+    ("lb_gpu_ivfpq4_get_centroids", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq4_reserve", _i, [_vp, _i64]),
+    ("lb_gpu_ivfpq4_add", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivfpq4_add_device", _i, [_vp, _i64, _vp, _vp]),
+    ("lb_gpu_ivfpq4_get_codes", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_ivfpq4_list_sizes", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq4_assignments", _i, [_vp, _i64, _i64, _vp]),
+    ("lb_gpu_ivfpq4_search", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp]),
+    ("lb_gpu_ivfpq4_search_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq4_search_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq4_search_bitmap_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq4_search_bitmap_device_ctx", _i, [_vp, _i64, _vp, _i, _i, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
+    ("lb_gpu_ivfpq4_set_filter", _i, [_vp, _vp, _i64]),
+    ("lb_gpu_ivfpq4_filter_int64", _i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i]),
+    ("lb_gpu_ivfpq4_filter_float32", _i, [_vp, _vp, _i64, C.c_float, _i, _vp, _i64, _i]),
+    ("lb_gpu_ivfpq4_nvisible", _i64, [_vp]),
+    ("lb_gpu_ivfpq4_last_search_stats", _i, [_vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq4_set_profiling", _i, [_vp, _i]),
+    ("lb_gpu_ivfpq4_last_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq4_last_build_timing", _i, [_vp, _vp]),
+    ("lb_gpu_ivfpq4_remove", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq4_remove_device", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq4_remove_rows", _i, [_vp, _i64, _vp, C.POINTER(C.c_int64)]),
+    ("lb_gpu_ivfpq4_nlive", _i64, [_vp]),
+    ("lb_gpu_ivfpq4_ndeleted", _i64, [_vp]),
+    ("lb_gpu_ivfpq4_compact", _i, [_vp, _vp, _i64]),
     ("lb_gpu_ivfsq8_new", _vp, [_i, _i, _vp, _vp, _i, _i, _vp, _ip]),
     ("lb_gpu_ivfsq8_free", None, [_vp]),
     ("lb_gpu_ivfsq8_last_error", C.c_char_p, [_vp]),
