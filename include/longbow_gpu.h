@@ -986,6 +986,14 @@ int lb_gpu_ivf_add_u8(lb_gpu_ivf *p, int64_t n, const uint8_t *vectors, const in
 int lb_gpu_ivf_add_u8_device(lb_gpu_ivf *p, int64_t n, const uint8_t *d_vectors, const int64_t *d_ids);
 int lb_gpu_ivf_list_sizes(lb_gpu_ivf *p, int64_t *sizes); /* [nlist] */
 int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
+/* The scan of the probed lists has two forms on a float32 handle.  The per-pair scan gives every (query, probed list) pair
+ * workgroups of its own.  The list-major tile groups a batch's pairs by list and scores 64 rows of a list against up to 64 of
+ * the queries that probe it at a time; a batch (at most 1,024 queries) takes it when dim % 4 == 0, rows and queries are 16-byte
+ * aligned and nq * nprobe >= 4 * nlist, nlist counting the lists the batch walks: the handle's, the visible ones under a filter
+ * or removals, twice the handle's for the once-per-call lists of a bitmap shared by the call's queries (a bitmap's per-query
+ * lists are never shared and never qualify).  Both forms run the same arithmetic on every pair and leave the same keys, so the
+ * result does not depend on the form; lb_gpu_ivf_last_route tells which ran.  float16, int8 and uint8 handles have the per-pair
+ * scan alone. */
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
 int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                           const lb_cancel *ctx);
@@ -1029,6 +1037,9 @@ int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p);
 /* telemetry of the last search only: out[0] queries, out[1] rows scanned summed over the queries, out[2] the largest per-query
  * count, out[3] queries whose selection ran from LDS; under a row filter the rows are the visible ones of the probed lists */
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]);
+/* the scan form of the last search (see lb_gpu_ivf_search), published with its stats: 0 a null handle, no search yet or an empty
+ * handle; 1 every batch took the per-pair scan; 2 at least one batch took the list-major tile */
+int lb_gpu_ivf_last_route(const lb_gpu_ivf *p);
 /* instrumentation (tools/ivf_bench.py), as lb_gpu_pq_set_profiling: while on, a search records HIP events between its steps and
  * drains the stream after every batch; last_timing gives the last such search's ms summed over its batches: ms[0] the probes
  * (the coarse search), ms[1] the plan (and the query norms, cosine; and the compaction under a call's bitmap), ms[2] the list

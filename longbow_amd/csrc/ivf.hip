@@ -1,6 +1,6 @@
 // ivf.hip -- host side of the lb_gpu_ivf_* entry points of include/longbow_gpu.h: the IVF-Flat index the reference names as
 // a plug-point (internal/store/pluggable_index.go:18-25,100-104; its adapter, pluggable_index_adapters.go:116-223, is a stub).
-// The kernels are in kernels_ivf.hip, those of a row bitmap given with a search call in kernels_ivf_call.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
+// The kernels are in kernels_ivf.hip, the list-major tile of the float32 scan in kernels_ivf_group.hip, those of a row bitmap given with a search call in kernels_ivf_call.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
 // kernels_ivf_i8.hip, the one over uint8 rows in kernels_ivf_u8.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
@@ -22,6 +22,7 @@ struct lb_gpu_ivf : IvfHandle { // the partition, and under a row filter the vis
     size_t row_bytes() const { return (size_t)dims * (dtype == DT_I8 || dtype == DT_U8 ? 1 : dtype == DT_F16 ? 2 : 4); }
     template <class E> const E *rows() const { return reinterpret_cast<const E *>(d_rows.get()); }
     float timing[4] = {0, 0, 0, 0};  // of the last profiled search (under err_mu): probes, plan, scan, select; ms summed over its batches
+    int last_route = 0;             // of the last search (under err_mu, published beside part.stats): lb_gpu_ivf_last_route
 };
 
 namespace {
@@ -81,17 +82,44 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
         ivf_no_store, ivf_no_relist);
 }
 
+// Pairs (query, probe slot) per list the batch walks from which a float32 batch takes the list-major tile (kernels_ivf_group.hip)
+// in place of the per-pair scan: measured, DESIGN 3.27.  Below it the grouping's launches cost more than the sharing saves.
+constexpr int64_t IVF_TILE_PAIRS_PER_LIST = 4;
+
 // The handle's call of the search loop (lb_ivf_host.h): its middle steps are the queries' norms under cosine, inside the plan's
-// timing slot, and the scan of the rows.  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
+// timing slot, and the scan of the rows.  A float32 handle's scan has two forms, which leave the same keys: the per-pair scan
+// and, for a batch with D % 4 == 0, 16-byte aligned rows and queries and nq np >= IVF_TILE_PAIRS_PER_LIST nlist over the lists
+// it walks (at most IVF_MAX_NLIST of them, the grouping sort's buckets), the list-major tile.  The lists it walks are the
+// handle's, the visible ones, or a call bitmap's: the once-per-call lists of a shared bitmap count 2 nlist, the per-slot ones
+// 2 nq np, which no batch reaches.  The float16, int8 and uint8 scans are untouched.  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
 // widened to f32; the scan reads the narrow ones, a batch's at the offset of its b.Q in c.queries.
 int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
 {
     float *d_qna = nullptr;
-    return ivf_search(
+    IvfGroups groups{};
+    int route = 0; // 0: no batch scanned yet; 1: per-pair scans alone; 2: a batch took the tile
+    auto takes_tile = [&](int64_t pairs, int nlist, const float *X, const float *Q) {
+        return p->dtype == DT_F32 && p->dims % 4 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Q)) & 15) == 0 &&
+               nlist <= IVF_MAX_NLIST && pairs >= IVF_TILE_PAIRS_PER_LIST * nlist;
+    };
+    const int rc = ivf_search(
         p, c, IvfSearchForm{p->timing, 4},
         [&](Carve &cv, IvfBatch &b, int64_t nb) {
             b.X = p->dtype == DT_F32 ? p->rows<float>() : nullptr; // (the plan and the selection read no rows)
             b.qna = d_qna = cv.take<float>((size_t)nb * 4);
+            // the grouping's scratch, if a full batch can take the tile: over the handle's lists, or a shared call bitmap's
+            const int64_t pairs = nb * b.np;
+            const int nlist = c.filter.on ? 2 * b.L.nlist : b.L.nlist;
+            if (!takes_tile(pairs, nlist, nullptr, nullptr)) return;
+            groups.max_items = (uint32_t)ivf_group_max_items(pairs, nlist);
+            groups.bucket = cv.take<uint32_t>((size_t)pairs * 4);
+            groups.gpairs = cv.take<uint32_t>((size_t)pairs * 4);
+            groups.goff = cv.take<uint32_t>(((size_t)nlist + 1) * 4);
+            // (the sort's scratch is not monotone in the pairs: the call's two batch sizes are both asked)
+            const size_t words = std::max(ivf_sort_hist_words(pairs, nlist), ivf_sort_hist_words(std::max<int64_t>(c.nq % nb, 1) * b.np, nlist));
+            groups.hist = cv.take<uint32_t>(words * 4);
+            groups.items = cv.take<uint2>((size_t)groups.max_items * 8);
+            groups.nitems = cv.take<uint32_t>(4);
         },
         [&](const IvfBatch &b, const IvfWalk &w, auto &&poll, auto &&next) {
             if (p->metric == METRIC_COS) {
@@ -102,9 +130,22 @@ int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
             if (p->dtype == DT_I8) launch_ivf_scan_i8(p->metric, IvfI8Scan{b, p->rows<int8_t>(), static_cast<const int8_t *>(d_q8) + (b.Q - c.queries)}, w.maxlen, c.s);
             else if (p->dtype == DT_U8) launch_ivf_scan_u8(IvfU8Scan{b, p->rows<uint8_t>(), static_cast<const uint8_t *>(d_q8) + (b.Q - c.queries)}, w.maxlen, c.s);
             else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, p->rows<_Float16>()}, w.maxlen, c.s);
-            else launch_ivf_scan(p->metric, p->order, b, w.maxlen, c.s);
+            else if (groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist, b.X, b.Q)) {
+                // (a smaller last batch over the same lists fits the full batch's scratch: fewer pairs, the same nlist)
+                IvfGroups g = groups;
+                g.max_items = (uint32_t)ivf_group_max_items((int64_t)b.nq * b.np, b.L.nlist);
+                LB_HIP(launch_ivf_scan_tile(p->metric, p->order, b, g, w.maxlen, c.s));
+                route = 2;
+                return true;
+            } else launch_ivf_scan(p->metric, p->order, b, w.maxlen, c.s);
+            route = std::max(route, 1);
             return true;
         });
+    if (rc == LB_OK) { // (a search that failed or was cancelled publishes nothing, as with the stats)
+        std::lock_guard<std::mutex> g(p->err_mu);
+        p->last_route = route;
+    }
+    return rc;
 }
 
 // A float32 or float16 handle's search of f32 queries
@@ -336,6 +377,12 @@ int lb_gpu_ivf_search_u8_bitmap_ctx(lb_gpu_ivf *p, int64_t nq, const uint8_t *qu
     return search_bytes_host(p, nq, queries, k, nprobe, dist, labels, ctx, CallBitmap{bitmap, nbits, stride_bytes, false});
 }
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
+int lb_gpu_ivf_last_route(const lb_gpu_ivf *p)
+{
+    if (!p) return 0;
+    std::lock_guard<std::mutex> g(const_cast<lb_gpu_ivf *>(p)->err_mu);
+    return p->last_route;
+}
 int lb_gpu_ivf_set_profiling(lb_gpu_ivf *p, int enable) { return ivf_set_profiling(p, enable); }
 int lb_gpu_ivf_last_timing(lb_gpu_ivf *p, float ms[4]) { return ivf_last_timing(p, ms); }
 

@@ -1,4 +1,4 @@
-// lb_ivf.h -- what ivf.hip (host) and kernels_ivf.hip / kernels_ivf_call.hip (device) of the IVF-Flat index share: the argument
+// lb_ivf.h -- what ivf.hip (host) and kernels_ivf.hip / kernels_ivf_group.hip / kernels_ivf_call.hip (device) of the IVF-Flat index share: the argument
 // blocks of the kernels and their launchers.  The semantics are stated in include/longbow_gpu.h (lb_gpu_ivf_*).
 #pragma once
 #include "lb_device.h"
@@ -36,6 +36,27 @@ void launch_ivf_all_probes(int64_t *probes, int nq, int np, hipStream_t s);
 void launch_ivf_plan(const IvfBatch &a, unsigned long long *stats, hipStream_t s);
 // keys[q][seg[q][p] + i] = entry of the i-th row of the p-th probed list; maxlen: the longest list of the handle
 void launch_ivf_scan(int metric, int order, const IvfBatch &a, int64_t maxlen, hipStream_t s);
+// The list-major form of that scan (kernels_ivf_group.hip), for a batch whose queries share lists: the pairs (q, p) are grouped
+// by the list they probe, gpairs[goff[l], goff[l + 1]) being list l's (pair = q np + p; a probe outside [0, nlist) is in no run),
+// and cut into the work items (list, first pair of a group of at most IVF_GROUP_PAIRS); a workgroup scores 64-row tiles of the
+// list against its group.  The same keys in the same places, bit for bit.  Scratch of a batch of `pairs` pairs over nlist lists:
+struct IvfGroups {
+    uint32_t *bucket;   // [pairs] the list of each pair
+    uint32_t *gpairs;   // [pairs]
+    uint32_t *goff;     // [nlist + 1]
+    uint32_t *hist;     // [ivf_sort_hist_words(pairs, nlist)] launch_ivf_sort's
+    uint2 *items;       // [max_items]
+    uint32_t *nitems;   // [1] the items there are: read by the tile kernel alone, never by the host
+    uint32_t max_items; // ivf_group_max_items(pairs, nlist): what the grid is sized by
+};
+constexpr int IVF_GROUP_PAIRS = 64;
+static inline int64_t ivf_group_max_items(int64_t pairs, int nlist)
+{
+    return (pairs + IVF_GROUP_PAIRS - 1) / IVF_GROUP_PAIRS + (pairs < nlist ? pairs : (int64_t)nlist);
+}
+// a.D % 4 == 0, a.X and a.Q 16-byte aligned, a.L.nlist <= IVF_MAX_NLIST (the sort's buckets).  Seven launches: the buckets, the
+// sort's four (behind its memset, whose error is returned, nothing further being launched then), the items, the tile
+hipError_t launch_ivf_scan_tile(int metric, int order, const IvfBatch &a, const IvfGroups &g, int64_t maxlen, hipStream_t s);
 // the k smallest keys of each query, ascending -> dist / labels [nq][k] (ids nullable: the row itself), padded FLT_MAX / -1
 void launch_ivf_select(const IvfBatch &a, int k, const int64_t *ids, float *dist, int64_t *labels, hipStream_t s);
 

@@ -223,6 +223,11 @@ class IVFFlat(RemovalMixin, RowFilterMixin, IVFBase):
         call's bitmap falls into the plan's"""
         return super().last_timing()
 
+    def last_route(self):
+        """the scan form of the last search (lb_gpu_ivf_last_route): 0 none yet or an empty handle, 1 the per-pair scan in every
+        batch, 2 the list-major tile in at least one (float32 handles; the result does not depend on it)"""
+        return int(self._lib.lb_gpu_ivf_last_route(self._h))
+
     def last_build_timing(self):
         """ms of the last profiled build of the visible lists (a filter call or an add under a filter): its launches alone"""
         out = C.c_float(0)
@@ -476,6 +481,9 @@ class IVFFlatIndex:
 
     def last_search_stats(self):
         return self._built().last_search_stats()
+
+    def last_route(self):
+        return self._built().last_route()
 
     def set_filter(self, mask):
         self._built().set_filter(mask)

@@ -7,7 +7,8 @@ max_iter = 0 returns its init rows).  Per cell (nprobe x nq): the p50 of the who
 as the median of three wall-clock runs after a warm-up (the call returns when the results are on the device); the HIP-event time
 of each step (probes, plan, list scan, selection) as the median over --profile-reps further, profiled, runs; rows and bytes
 scanned (rows * dim * the element's bytes); the scan pass's bytes per second and its share of 8 TB/s; recall@k against
-lb_gpu_index_search on an f32 index with the same rows; and that index's own p50 for the same nq, in the same run.  Also: the add
+lb_gpu_index_search on an f32 index with the same rows; that index's own p50 for the same nq, in the same run; and last_route, the
+form of the first handle's list scan (lb_gpu_ivf_last_route: 1 per pair, 2 the list-major tile).  Also: the add
 rate in rows/s, and one ivf.train(nlist = 256, max_iter = 1) on 100k rows with its E-step time.  The shader clock is read before
 and after.  A run that finds no GPU fails.
 
@@ -260,8 +261,11 @@ def main():
             st = first.last_search_stats()
             got = res[names[0]][1][:nq].cpu().numpy()
             recall = float(np.mean([np.intersect1d(got[j], truth[j]).size / a.k for j in range(nq)]))
+            if a.dtype == "f32" and nprobe >= a.nlist:  # every list probed: the flat index, bit for bit
+                assert np.array_equal(got, truth), f"every list probed: labels differ from the flat index at nq {nq}"
+                assert torch.equal(res["f32"][0][:nq], FD[:nq]), f"every list probed: distances differ from the flat index at nq {nq}"
             cell = {"nq": nq, "nprobe": nprobe, "flat_p50_ms": flat_ms, "rows_scanned": st[1], "max_rows_per_query": st[2],
-                    "selected_from_lds": st[3], "recall_at_k": recall}
+                    "selected_from_lds": st[3], "recall_at_k": recall, "last_route": first.last_route()}
             if a.dtype == "both":
                 assert handles["f16"].last_search_stats() == st, f"search stats differ at nq {nq} nprobe {nprobe}"
                 assert torch.equal(res["f32"][1][:nq], res["f16"][1][:nq]), f"labels differ at nq {nq} nprobe {nprobe}"
