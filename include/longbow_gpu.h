@@ -905,7 +905,9 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     an exact int32 rounded once to f32, the tail added in f32 in order, sqrt correctly rounded; dot:
  *                     dotInt8Unrolled4x, negated).  Result, labels, padding, ids, filters and stats are as stated above, and
  *                     nprobe >= nlist gives lb_gpu_index_search_i8 of an int8 index (lb_gpu_index_new_i8) over the same rows,
- *                     bit for bit.  Every other lb_gpu_ivf_* entry point works on all four handle types.
+ *                     bit for bit.  A batch whose queries share probed lists scans them list by list on the i8 matrix cores
+ *                     (the rule is stated at lb_gpu_ivf_search; lb_gpu_ivf_last_route 2), with the same result.  Every other
+ *                     lb_gpu_ivf_* entry point works on all four handle types.
  *   uint8 rows        lb_gpu_ivf_new_u8 makes a handle whose rows are uint8, one byte an element, row-major in insertion order,
  *                     and no wider copy of them (VectorTypeUint8).  Euclidean only: cosine (1) and dot (2) are
  *                     LB_ERR_UNSUPPORTED, the rule of lb_gpu_index_new_u8 for its reason (the reference registers
@@ -992,8 +994,12 @@ int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *list
  * aligned and nq * nprobe >= 4 * nlist, nlist counting the lists the batch walks: the handle's, the visible ones under a filter
  * or removals, twice the handle's for the once-per-call lists of a bitmap shared by the call's queries (a bitmap's per-query
  * lists are never shared and never qualify).  Both forms run the same arithmetic on every pair and leave the same keys, so the
- * result does not depend on the form; lb_gpu_ivf_last_route tells which ran.  float16, int8 and uint8 handles have the per-pair
- * scan alone. */
+ * result does not depend on the form; lb_gpu_ivf_last_route tells which ran.  An int8 handle has the same two forms: its
+ * list-major tile scores 128 rows of a list against up to 64 of the queries that probe it on the i8 matrix cores, and a batch
+ * takes it when dim % 16 == 0, the metric is L2 or dim <= 1024 (dot), rows and queries are 16-byte aligned (the conditions under
+ * which every distance is one exact int32 total, rounded once, whatever the order of the sum) and nq * nprobe >= 4 * nlist, the
+ * lists counted as above; every other int8 batch takes the per-pair scan, and the keys are the same bit for bit.  float16 and
+ * uint8 handles have the per-pair scan alone. */
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
 int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                           const lb_cancel *ctx);
@@ -1038,7 +1044,8 @@ int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p);
  * count, out[3] queries whose selection ran from LDS; under a row filter the rows are the visible ones of the probed lists */
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]);
 /* the scan form of the last search (see lb_gpu_ivf_search), published with its stats: 0 a null handle, no search yet or an empty
- * handle; 1 every batch took the per-pair scan; 2 at least one batch took the list-major tile */
+ * handle; 1 every batch took the per-pair scan; 2 at least one batch took a list-major tile (a float32 handle's, or an int8
+ * handle's matrix-core one) */
 int lb_gpu_ivf_last_route(const lb_gpu_ivf *p);
 /* instrumentation (tools/ivf_bench.py), as lb_gpu_pq_set_profiling: while on, a search records HIP events between its steps and
  * drains the stream after every batch; last_timing gives the last such search's ms summed over its batches: ms[0] the probes

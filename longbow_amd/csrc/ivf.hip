@@ -1,7 +1,7 @@
 // ivf.hip -- host side of the lb_gpu_ivf_* entry points of include/longbow_gpu.h: the IVF-Flat index the reference names as
 // a plug-point (internal/store/pluggable_index.go:18-25,100-104; its adapter, pluggable_index_adapters.go:116-223, is a stub).
 // The kernels are in kernels_ivf.hip, the list-major tile of the float32 scan in kernels_ivf_group.hip, those of a row bitmap given with a search call in kernels_ivf_call.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
-// kernels_ivf_i8.hip, the one over uint8 rows in kernels_ivf_u8.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
+// kernels_ivf_i8.hip and its list-major matrix-core tile in kernels_ivf_i8_group.hip, the one over uint8 rows in kernels_ivf_u8.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
 #include "lb_ivf_f16.h"
@@ -85,22 +85,30 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
 // Pairs (query, probe slot) per list the batch walks from which a float32 batch takes the list-major tile (kernels_ivf_group.hip)
 // in place of the per-pair scan: measured, DESIGN 3.27.  Below it the grouping's launches cost more than the sharing saves.
 constexpr int64_t IVF_TILE_PAIRS_PER_LIST = 4;
+// The same ratio for an int8 batch and the i8 matrix-core tile (kernels_ivf_i8_group.hip): measured, DESIGN 3.28
+constexpr int64_t IVF_I8_TILE_PAIRS_PER_LIST = 4;
 
 // The handle's call of the search loop (lb_ivf_host.h): its middle steps are the queries' norms under cosine, inside the plan's
 // timing slot, and the scan of the rows.  A float32 handle's scan has two forms, which leave the same keys: the per-pair scan
 // and, for a batch with D % 4 == 0, 16-byte aligned rows and queries and nq np >= IVF_TILE_PAIRS_PER_LIST nlist over the lists
 // it walks (at most IVF_MAX_NLIST of them, the grouping sort's buckets), the list-major tile.  The lists it walks are the
 // handle's, the visible ones, or a call bitmap's: the once-per-call lists of a shared bitmap count 2 nlist, the per-slot ones
-// 2 nq np, which no batch reaches.  The float16, int8 and uint8 scans are untouched.  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
+// 2 nq np, which no batch reaches.  An int8 handle's scan has the same two forms: a batch takes the i8 matrix-core tile when the
+// per-pair scan would stage its rows (ivf_scan_i8_staged) and nq np >= IVF_I8_TILE_PAIRS_PER_LIST nlist, the lists counted
+// alike.  The float16 and uint8 scans are untouched.  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
 // widened to f32; the scan reads the narrow ones, a batch's at the offset of its b.Q in c.queries.
 int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
 {
     float *d_qna = nullptr;
     IvfGroups groups{};
     int route = 0; // 0: no batch scanned yet; 1: per-pair scans alone; 2: a batch took the tile
-    auto takes_tile = [&](int64_t pairs, int nlist, const float *X, const float *Q) {
+    const int8_t *q8 = static_cast<const int8_t *>(d_q8);
+    // X, Q: the rows and the batch's queries as the scan reads them (nullptr: before a batch exists, alignment not asked)
+    auto takes_tile = [&](int64_t pairs, int nlist, const void *X, const void *Q) {
+        if (nlist > IVF_MAX_NLIST) return false;
+        if (p->dtype == DT_I8) return ivf_scan_i8_staged(p->metric, p->dims, X, Q) && pairs >= IVF_I8_TILE_PAIRS_PER_LIST * nlist;
         return p->dtype == DT_F32 && p->dims % 4 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Q)) & 15) == 0 &&
-               nlist <= IVF_MAX_NLIST && pairs >= IVF_TILE_PAIRS_PER_LIST * nlist;
+               pairs >= IVF_TILE_PAIRS_PER_LIST * nlist;
     };
     const int rc = ivf_search(
         p, c, IvfSearchForm{p->timing, 4},
@@ -127,7 +135,17 @@ int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
                 launch_query_norms(p->order, b.Q, nullptr, b.nq, p->dims, d_qna, c.s);
             }
             if (!next()) return false;
-            if (p->dtype == DT_I8) launch_ivf_scan_i8(p->metric, IvfI8Scan{b, p->rows<int8_t>(), static_cast<const int8_t *>(d_q8) + (b.Q - c.queries)}, w.maxlen, c.s);
+            if (p->dtype == DT_I8) {
+                const IvfI8Scan a8{b, p->rows<int8_t>(), q8 + (b.Q - c.queries)};
+                if (groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist, a8.X, a8.Q)) {
+                    IvfGroups g = groups; // (as below)
+                    g.max_items = (uint32_t)ivf_group_max_items((int64_t)b.nq * b.np, b.L.nlist);
+                    LB_HIP(launch_ivf_scan_i8_tile(p->metric, a8, g, w.maxlen, c.s));
+                    route = 2;
+                    return true;
+                }
+                launch_ivf_scan_i8(p->metric, a8, w.maxlen, c.s);
+            }
             else if (p->dtype == DT_U8) launch_ivf_scan_u8(IvfU8Scan{b, p->rows<uint8_t>(), static_cast<const uint8_t *>(d_q8) + (b.Q - c.queries)}, w.maxlen, c.s);
             else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, p->rows<_Float16>()}, w.maxlen, c.s);
             else if (groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist, b.X, b.Q)) {

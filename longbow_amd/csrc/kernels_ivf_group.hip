@@ -241,15 +241,23 @@ __global__ __launch_bounds__(IG_THREADS, 2) void ivf_scan_tile_kernel(IvfBatch a
     }
 }
 
-hipError_t launch_ivf_scan_tile(int metric, int order, const IvfBatch &a, const IvfGroups &g, int64_t maxlen, hipStream_t s)
+hipError_t launch_ivf_group(const IvfBatch &a, const IvfGroups &g, hipStream_t s)
 {
     const int64_t pairs = (int64_t)a.nq * a.np;
-    if (pairs <= 0 || maxlen <= 0) return hipSuccess;
     hipLaunchKernelGGL(ivf_group_bucket_kernel, dim3((unsigned)std::min<int64_t>((pairs + 255) / 256, 4096)), dim3(256), 0, s, a.probes, pairs,
                        a.L.nlist, g.bucket);
     const hipError_t e = launch_ivf_sort(g.bucket, pairs, a.L.nlist, g.hist, g.goff, g.gpairs, s);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(ivf_group_items_kernel, dim3(1), dim3(1024), 0, s, g, a.L);
+    return hipSuccess;
+}
+
+hipError_t launch_ivf_scan_tile(int metric, int order, const IvfBatch &a, const IvfGroups &g, int64_t maxlen, hipStream_t s)
+{
+    const int64_t pairs = (int64_t)a.nq * a.np;
+    if (pairs <= 0 || maxlen <= 0) return hipSuccess;
+    const hipError_t e = launch_ivf_group(a, g, s);
+    if (e != hipSuccess) return e;
     const int64_t items = ivf_group_max_items(pairs, a.L.nlist), tiles = (maxlen + IG_ROWS - 1) / IG_ROWS;
     const unsigned gy = (unsigned)std::min<int64_t>(items, IVF_PAIRS_Y);
     const dim3 grid((unsigned)list_scan_gx(items, tiles), gy, (unsigned)((items + gy - 1) / gy));

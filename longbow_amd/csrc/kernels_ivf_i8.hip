@@ -166,8 +166,7 @@ void launch_ivf_scan_i8(int metric, const IvfI8Scan &a, int64_t maxlen, hipStrea
 {
     const int64_t pairs = (int64_t)a.b.nq * a.b.np;
     if (pairs <= 0 || maxlen <= 0) return;
-    const bool staged = a.b.D % 16 == 0 && (metric == METRIC_L2 || a.b.D <= 1024) &&
-                        ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.Q)) & 15) == 0;
+    const bool staged = ivf_scan_i8_staged(metric, a.b.D, a.X, a.Q);
     const dim3 grid = ivf_scan_grid(pairs, maxlen, staged ? I8L_ROWS : I8L_GEN_ROWS);
     if (metric == METRIC_L2) launch_ivf_scan_i8_m<METRIC_L2>(a, staged, grid, s);
     else launch_ivf_scan_i8_m<METRIC_DOT>(a, staged, grid, s);

@@ -54,8 +54,11 @@ static inline int64_t ivf_group_max_items(int64_t pairs, int nlist)
 {
     return (pairs + IVF_GROUP_PAIRS - 1) / IVF_GROUP_PAIRS + (pairs < nlist ? pairs : (int64_t)nlist);
 }
-// a.D % 4 == 0, a.X and a.Q 16-byte aligned, a.L.nlist <= IVF_MAX_NLIST (the sort's buckets).  Seven launches: the buckets, the
-// sort's four (behind its memset, whose error is returned, nothing further being launched then), the items, the tile
+// The grouping alone, which the float32 tile and the int8 one (lb_ivf_i8.h) share: gpairs, goff, items and nitems of the batch.
+// a.L.nlist <= IVF_MAX_NLIST (the sort's buckets), pairs > 0.  Six launches: the buckets, the sort's four (behind its memset,
+// whose error is returned, nothing further being launched then), the items
+hipError_t launch_ivf_group(const IvfBatch &a, const IvfGroups &g, hipStream_t s);
+// a.D % 4 == 0, a.X and a.Q 16-byte aligned, a.L.nlist <= IVF_MAX_NLIST.  Seven launches: launch_ivf_group's six, the tile
 hipError_t launch_ivf_scan_tile(int metric, int order, const IvfBatch &a, const IvfGroups &g, int64_t maxlen, hipStream_t s);
 // the k smallest keys of each query, ascending -> dist / labels [nq][k] (ids nullable: the row itself), padded FLT_MAX / -1
 void launch_ivf_select(const IvfBatch &a, int k, const int64_t *ids, float *dist, int64_t *labels, hipStream_t s);

@@ -18,5 +18,17 @@ struct IvfI8Scan {
 // distance being the flat int8 index's (kernels_i8.hip; lb_i8_exact.h), bit for bit.  metric: METRIC_L2 or METRIC_DOT.
 // maxlen: the longest list of the handle
 void launch_ivf_scan_i8(int metric, const IvfI8Scan &a, int64_t maxlen, hipStream_t s);
+// Whether that scan stages its rows (exact int32 totals, any summation order gives the same bits) or walks them one lane per
+// row: D % 16 == 0, L2 or dot up to 1,024 dimensions, rows and queries 16-byte aligned
+static inline bool ivf_scan_i8_staged(int metric, int D, const void *X, const void *Q)
+{
+    return D % 16 == 0 && (metric == METRIC_L2 || D <= 1024) && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Q)) & 15) == 0;
+}
+
+// The list-major form of the staged scan (kernels_ivf_i8_group.hip), for a batch whose queries share lists: the pairs are
+// grouped as for the float32 tile (launch_ivf_group, lb_ivf.h) and a workgroup scores 128-row tiles of an item's list against
+// its group of at most 64 queries on the i8 matrix cores.  The same keys in the same places, bit for bit.  Requires
+// ivf_scan_i8_staged(metric, a.b.D, a.X, a.Q) and a.b.L.nlist <= IVF_MAX_NLIST.  Seven launches: the grouping's six, the tile
+hipError_t launch_ivf_scan_i8_tile(int metric, const IvfI8Scan &a, const IvfGroups &g, int64_t maxlen, hipStream_t s);
 
 } // namespace lb

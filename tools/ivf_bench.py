@@ -22,7 +22,8 @@ handles' four timing slots with the spread (min, max) of the scan slot, and the 
 queries) beside the float32 handle over the same values widened, in one process, their profiled runs taking turns.  The two
 handles' distances are different arithmetic (the reference's DataTypeInt8 kernels against its f32 chains), so what is asserted in
 every cell is what must be equal: assignments, list sizes and search stats (the same lists probed).  For every nq the int8 handle
-with every list probed is also asserted equal, labels and distances, to a flat int8 index over the same rows.
+with every list probed is also asserted equal, labels and distances, to a flat int8 index over the same rows.  Each handle's cell
+carries its own last_route (the int8 handle's: 1 per pair, 2 the i8 matrix-core tile) and the scan slot of every profiled run.
 
 --dtype uint8 draws uniform bytes and runs the uint8 handle (lb_gpu_ivf_new_u8, uint8 queries) beside the int8 handle over the
 same bytes XOR 0x80 with the centroids shifted by 128, in one process: the same lists, the same bytes scanned.  First, for every
@@ -280,7 +281,8 @@ def main():
                 assert np.array_equal(handles["i8"].assignments(), first.assignments()), f"assignments differ at nq {nq} nprobe {nprobe}"
                 cell["equal_lists"] = cell["equal_flat_i8"] = True
                 for name in names:
-                    cell[name] = dict(measured(steps[name], st[1], a.dim, ELEM_BYTES[name]), p50_ms=ms[name])
+                    cell[name] = dict(measured(steps[name], st[1], a.dim, ELEM_BYTES[name]), p50_ms=ms[name],
+                                      scan_ms_runs=[float(s[2]) for s in steps[name]], last_route=handles[name].last_route())
                 cell["scan_i8_over_f32"] = cell["i8"]["scan_ms"] / max(cell["f32"]["scan_ms"], 1e-9)
             else:
                 m = measured(steps[names[0]], st[1], a.dim, ELEM_BYTES[names[0]])
