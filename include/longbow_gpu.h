@@ -931,7 +931,9 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     value is sqrt_rn(float(S)).  dim % 16 != 0 or a misaligned base: one lane per pair, chain arithmetic
  *                     throughout.  Result, labels, padding, ids, filters, removal, compaction and stats are as stated above, and
  *                     with every list probed (nprobe >= nlist) the result is lb_gpu_index_search_u8 of a flat uint8 index
- *                     (lb_gpu_index_new_u8) over the same rows, bit for bit.
+ *                     (lb_gpu_index_new_u8) over the same rows, bit for bit.  A batch whose queries share probed lists scans
+ *                     them list by list on the i8 matrix cores (the rule is stated at lb_gpu_ivf_search; lb_gpu_ivf_last_route
+ *                     2), with the same result.
  *   call bitmap       lb_gpu_ivf_search_bitmap_ctx / _bitmap_device_ctx and, on an int8 handle, _search_i8_bitmap_ctx /
  *                     _i8_bitmap_device_ctx, on a uint8 handle _search_u8_bitmap_ctx / _u8_bitmap_device_ctx, take what their
  *                     plain counterparts take, and behind nprobe a row filter of THIS CALL
@@ -998,8 +1000,13 @@ int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *list
  * list-major tile scores 128 rows of a list against up to 64 of the queries that probe it on the i8 matrix cores, and a batch
  * takes it when dim % 16 == 0, the metric is L2 or dim <= 1024 (dot), rows and queries are 16-byte aligned (the conditions under
  * which every distance is one exact int32 total, rounded once, whatever the order of the sum) and nq * nprobe >= 4 * nlist, the
- * lists counted as above; every other int8 batch takes the per-pair scan, and the keys are the same bit for bit.  float16 and
- * uint8 handles have the per-pair scan alone. */
+ * lists counted as above; every other int8 batch takes the per-pair scan, and the keys are the same bit for bit.  A uint8 handle
+ * has the two forms too: its tile runs on the i8 matrix cores over the bytes shifted by 128 as they are staged (the shift leaves
+ * every difference as it is), one exact integer total a pair for dim <= 258 and the four exact chain sums S_j beyond (the chunk's
+ * bytes de-interleaved by i mod 4 as they are staged, a K-step a chain), valued by the per-chain rule stated at "uint8 rows"; a
+ * batch takes it when dim % 16 == 0, rows and queries are 16-byte aligned and nq * nprobe >= 4 * nlist, the lists counted as
+ * above, every other uint8 batch takes the per-pair scan, and the keys are the same bit for bit.  A float16 handle has the
+ * per-pair scan alone. */
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
 int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                           const lb_cancel *ctx);
@@ -1045,7 +1052,7 @@ int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p);
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]);
 /* the scan form of the last search (see lb_gpu_ivf_search), published with its stats: 0 a null handle, no search yet or an empty
  * handle; 1 every batch took the per-pair scan; 2 at least one batch took a list-major tile (a float32 handle's, or an int8
- * handle's matrix-core one) */
+ * or uint8 handle's matrix-core one) */
 int lb_gpu_ivf_last_route(const lb_gpu_ivf *p);
 /* instrumentation (tools/ivf_bench.py), as lb_gpu_pq_set_profiling: while on, a search records HIP events between its steps and
  * drains the stream after every batch; last_timing gives the last such search's ms summed over its batches: ms[0] the probes

@@ -1,7 +1,7 @@
 // ivf.hip -- host side of the lb_gpu_ivf_* entry points of include/longbow_gpu.h: the IVF-Flat index the reference names as
 // a plug-point (internal/store/pluggable_index.go:18-25,100-104; its adapter, pluggable_index_adapters.go:116-223, is a stub).
 // The kernels are in kernels_ivf.hip, the list-major tile of the float32 scan in kernels_ivf_group.hip, those of a row bitmap given with a search call in kernels_ivf_call.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
-// kernels_ivf_i8.hip and its list-major matrix-core tile in kernels_ivf_i8_group.hip, the one over uint8 rows in kernels_ivf_u8.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
+// kernels_ivf_i8.hip and its list-major matrix-core tile in kernels_ivf_i8_group.hip, the one over uint8 rows in kernels_ivf_u8.hip and its tile in kernels_ivf_u8_group.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
 #include "lb_ivf_f16.h"
@@ -87,6 +87,8 @@ int add_impl(lb_gpu_ivf *p, int64_t n, const void *vectors, const int64_t *ids, 
 constexpr int64_t IVF_TILE_PAIRS_PER_LIST = 4;
 // The same ratio for an int8 batch and the i8 matrix-core tile (kernels_ivf_i8_group.hip): measured, DESIGN 3.28
 constexpr int64_t IVF_I8_TILE_PAIRS_PER_LIST = 4;
+// and for a uint8 batch and its tile over the shifted bytes (kernels_ivf_u8_group.hip): DESIGN 3.29
+constexpr int64_t IVF_U8_TILE_PAIRS_PER_LIST = 4;
 
 // The handle's call of the search loop (lb_ivf_host.h): its middle steps are the queries' norms under cosine, inside the plan's
 // timing slot, and the scan of the rows.  A float32 handle's scan has two forms, which leave the same keys: the per-pair scan
@@ -95,7 +97,8 @@ constexpr int64_t IVF_I8_TILE_PAIRS_PER_LIST = 4;
 // handle's, the visible ones, or a call bitmap's: the once-per-call lists of a shared bitmap count 2 nlist, the per-slot ones
 // 2 nq np, which no batch reaches.  An int8 handle's scan has the same two forms: a batch takes the i8 matrix-core tile when the
 // per-pair scan would stage its rows (ivf_scan_i8_staged) and nq np >= IVF_I8_TILE_PAIRS_PER_LIST nlist, the lists counted
-// alike.  The float16 and uint8 scans are untouched.  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
+// alike, and so has a uint8 handle's: ivf_scan_u8_staged and nq np >= IVF_U8_TILE_PAIRS_PER_LIST nlist.  The float16 scan is
+// untouched.  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
 // widened to f32; the scan reads the narrow ones, a batch's at the offset of its b.Q in c.queries.
 int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
 {
@@ -107,6 +110,7 @@ int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
     auto takes_tile = [&](int64_t pairs, int nlist, const void *X, const void *Q) {
         if (nlist > IVF_MAX_NLIST) return false;
         if (p->dtype == DT_I8) return ivf_scan_i8_staged(p->metric, p->dims, X, Q) && pairs >= IVF_I8_TILE_PAIRS_PER_LIST * nlist;
+        if (p->dtype == DT_U8) return ivf_scan_u8_staged(p->dims, X, Q) && pairs >= IVF_U8_TILE_PAIRS_PER_LIST * nlist;
         return p->dtype == DT_F32 && p->dims % 4 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Q)) & 15) == 0 &&
                pairs >= IVF_TILE_PAIRS_PER_LIST * nlist;
     };
@@ -146,7 +150,17 @@ int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
                 }
                 launch_ivf_scan_i8(p->metric, a8, w.maxlen, c.s);
             }
-            else if (p->dtype == DT_U8) launch_ivf_scan_u8(IvfU8Scan{b, p->rows<uint8_t>(), static_cast<const uint8_t *>(d_q8) + (b.Q - c.queries)}, w.maxlen, c.s);
+            else if (p->dtype == DT_U8) {
+                const IvfU8Scan a8{b, p->rows<uint8_t>(), static_cast<const uint8_t *>(d_q8) + (b.Q - c.queries)};
+                if (groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist, a8.X, a8.Q)) {
+                    IvfGroups g = groups; // (as below)
+                    g.max_items = (uint32_t)ivf_group_max_items((int64_t)b.nq * b.np, b.L.nlist);
+                    LB_HIP(launch_ivf_scan_u8_tile(a8, g, w.maxlen, c.s));
+                    route = 2;
+                    return true;
+                }
+                launch_ivf_scan_u8(a8, w.maxlen, c.s);
+            }
             else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, p->rows<_Float16>()}, w.maxlen, c.s);
             else if (groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist, b.X, b.Q)) {
                 // (a smaller last batch over the same lists fits the full batch's scratch: fewer pairs, the same nlist)

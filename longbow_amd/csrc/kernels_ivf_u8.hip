@@ -34,7 +34,7 @@ constexpr int U8L_ROWS = 128;          // rows per tile == threads per workgroup
 constexpr int U8L_CK = 256;            // bytes per row per stage
 constexpr int U8L_LD = U8L_CK + 16;    // LDS row stride (bytes): 17 16-byte slots, conflict-free ds_read_b128 by rows
 constexpr int U8L_GEN_ROWS = 256;      // rows per tile of the generic form
-constexpr int U8L_TOTALS_D = 258;      // the largest D at which no pair exceeds 2^24: the totals form up to here
+constexpr int U8L_TOTALS_D = IVF_U8_TOTALS_D; // the largest D at which no pair exceeds 2^24: the totals form up to here
 
 // one 4-byte word of the row against the query's: a[j] += x_j q_j, n[j] += x_j^2 for the word's four bytes j
 __device__ __forceinline__ void u8l_chain_word(uint32_t w, uint32_t v, uint32_t (&a)[4], uint32_t (&n)[4])
@@ -205,7 +205,7 @@ void launch_ivf_scan_u8(const IvfU8Scan &a, int64_t maxlen, hipStream_t s)
 {
     const int64_t pairs = (int64_t)a.b.nq * a.b.np;
     if (pairs <= 0 || maxlen <= 0) return;
-    const bool staged = a.b.D % 16 == 0 && ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.Q)) & 15) == 0;
+    const bool staged = ivf_scan_u8_staged(a.b.D, a.X, a.Q);
     const dim3 grid = ivf_scan_grid(pairs, maxlen, staged ? U8L_ROWS : U8L_GEN_ROWS);
     if (!staged) hipLaunchKernelGGL(ivf_scan_u8_generic_kernel, grid, dim3(U8L_GEN_ROWS), 0, s, a);
     else if (a.b.D <= U8L_TOTALS_D) hipLaunchKernelGGL((ivf_scan_u8_kernel<false>), grid, dim3(U8L_ROWS), 0, s, a);

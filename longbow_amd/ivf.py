@@ -376,6 +376,11 @@ class IVFFlatUint8(RemovalMixin, RowFilterMixin, IVFBase):
         """ms of the last profiled search, summed over its batches: (probes, plan, list scan, selection)"""
         return super().last_timing()
 
+    def last_route(self):
+        """the scan form of the last search (lb_gpu_ivf_last_route): 0 none yet or an empty handle, 1 the per-pair scan in every
+        batch, 2 the list-major matrix-core tile over the shifted bytes in at least one (the result does not depend on it)"""
+        return int(self._lib.lb_gpu_ivf_last_route(self._h))
+
     def last_build_timing(self):
         """ms of the last profiled build of the visible lists (a filter call or an add under a filter): its launches alone"""
         out = C.c_float(0)

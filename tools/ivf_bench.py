@@ -29,7 +29,8 @@ carries its own last_route (the int8 handle's: 1 per pair, 2 the i8 matrix-core 
 same bytes XOR 0x80 with the centroids shifted by 128, in one process: the same lists, the same bytes scanned.  First, for every
 nq, the uint8 handle with every list probed is asserted equal, labels and distances, to a flat uint8 index over the same rows.
 Then per cell each handle's profiled runs take turns, at least two each, and the scan slot of every run is printed beside the
-medians, so that the int8 handle's own run-to-run spread is known; hbm_bytes holds both handles' and a float32 handle's over the
+medians, so that the int8 handle's own run-to-run spread is known, and each handle's last_route (1 per pair, 2 its matrix-core
+tile); hbm_bytes holds both handles' and a float32 handle's over the
 widened rows.
 """
 import argparse
@@ -140,7 +141,8 @@ def main_u8(a, lib):
             assert handles["i8"].last_search_stats() == st, f"search stats differ at nq {nq} nprobe {nprobe}"
             cell = {"nq": nq, "nprobe": nprobe, "rows_scanned": st[1], "max_rows_per_query": st[2]}
             for name in handles:
-                cell[name] = dict(measured(steps[name], st[1], a.dim, 1), p50_ms=ms[name], scan_ms_runs=[float(s[2]) for s in steps[name]])
+                cell[name] = dict(measured(steps[name], st[1], a.dim, 1), p50_ms=ms[name], scan_ms_runs=[float(s[2]) for s in steps[name]],
+                                  last_route=handles[name].last_route())
             cell["scan_u8_over_i8"] = cell["u8"]["scan_ms"] / max(cell["i8"]["scan_ms"], 1e-9)
             cells.append(cell)
     out["cells"] = cells
