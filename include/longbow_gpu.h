@@ -888,7 +888,9 @@ int64_t lb_gpu_sq8_nvisible(const lb_gpu_sq8 *p);
  *                     gives on a float32 handle that holds the widened rows, bit for bit: labels, distances, assignments, list
  *                     sizes, search stats.  With fp16-representable queries the distances are the reference's F16 functions',
  *                     and nprobe >= nlist gives lb_gpu_index_search of a float16 index (lb_gpu_index_new_f16) over the same
- *                     rows.  Every other lb_gpu_ivf_* entry point works on both handle types.
+ *                     rows.  A batch whose queries share probed lists scans them list by list, the rows float16 up to the
+ *                     lane that widens them (the rule is stated at lb_gpu_ivf_search; lb_gpu_ivf_last_route 2), with the same
+ *                     result.  Every other lb_gpu_ivf_* entry point works on both handle types.
  *   int8 rows         lb_gpu_ivf_new_i8 makes a handle whose rows are signed int8, one byte an element, row-major in insertion
  *                     order, and no wider copy of them (simd.VectorTypeInt8).  Metrics L2 (0) and dot (2) only: cosine, and dot
  *                     with floor(dim / 4) + dim mod 4 > 1024, are LB_ERR_UNSUPPORTED, the rules of lb_gpu_index_new_i8 for its
@@ -1005,8 +1007,12 @@ int lb_gpu_ivf_assignments(lb_gpu_ivf *p, int64_t row0, int64_t n, int32_t *list
  * every difference as it is), one exact integer total a pair for dim <= 258 and the four exact chain sums S_j beyond (the chunk's
  * bytes de-interleaved by i mod 4 as they are staged, a K-step a chain), valued by the per-chain rule stated at "uint8 rows"; a
  * batch takes it when dim % 16 == 0, rows and queries are 16-byte aligned and nq * nprobe >= 4 * nlist, the lists counted as
- * above, every other uint8 batch takes the per-pair scan, and the keys are the same bit for bit.  A float16 handle has the
- * per-pair scan alone. */
+ * above, every other uint8 batch takes the per-pair scan, and the keys are the same bit for bit.  A float16 handle has the two
+ * forms as well: its tile is the float32 handle's (64 rows against up to 64 queries, the same f32 chains in the same order) over
+ * rows that stay float16 until a lane widens them, which is exact; a batch takes it when dim % 8 == 0, rows and queries are
+ * 16-byte aligned and nq * nprobe >= 8 * nlist, the lists counted as above (twice the other types' ratio: the float16 per-pair
+ * scan moves half the bytes and holds its ground longer); every other float16 batch takes the per-pair scan, and the keys are
+ * the same bit for bit. */
 int lb_gpu_ivf_search(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
 int lb_gpu_ivf_search_ctx(lb_gpu_ivf *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                           const lb_cancel *ctx);
@@ -1051,8 +1057,8 @@ int64_t lb_gpu_ivf_nvisible(const lb_gpu_ivf *p);
  * count, out[3] queries whose selection ran from LDS; under a row filter the rows are the visible ones of the probed lists */
 int lb_gpu_ivf_last_search_stats(lb_gpu_ivf *p, int64_t out[4]);
 /* the scan form of the last search (see lb_gpu_ivf_search), published with its stats: 0 a null handle, no search yet or an empty
- * handle; 1 every batch took the per-pair scan; 2 at least one batch took a list-major tile (a float32 handle's, or an int8
- * or uint8 handle's matrix-core one) */
+ * handle; 1 every batch took the per-pair scan; 2 at least one batch took a list-major tile (a float32 or float16 handle's, or
+ * an int8 or uint8 handle's matrix-core one) */
 int lb_gpu_ivf_last_route(const lb_gpu_ivf *p);
 /* instrumentation (tools/ivf_bench.py), as lb_gpu_pq_set_profiling: while on, a search records HIP events between its steps and
  * drains the stream after every batch; last_timing gives the last such search's ms summed over its batches: ms[0] the probes

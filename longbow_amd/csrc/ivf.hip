@@ -1,6 +1,6 @@
 // ivf.hip -- host side of the lb_gpu_ivf_* entry points of include/longbow_gpu.h: the IVF-Flat index the reference names as
 // a plug-point (internal/store/pluggable_index.go:18-25,100-104; its adapter, pluggable_index_adapters.go:116-223, is a stub).
-// The kernels are in kernels_ivf.hip, the list-major tile of the float32 scan in kernels_ivf_group.hip, those of a row bitmap given with a search call in kernels_ivf_call.hip, the list scan over float16 rows in kernels_ivf_f16.hip, the one over int8 rows in
+// The kernels are in kernels_ivf.hip, the list-major tile of the float32 scan in kernels_ivf_group.hip, those of a row bitmap given with a search call in kernels_ivf_call.hip, the list scan over float16 rows in kernels_ivf_f16.hip and its list-major tile in kernels_ivf_f16_group.hip, the one over int8 rows in
 // kernels_ivf_i8.hip and its list-major matrix-core tile in kernels_ivf_i8_group.hip, the one over uint8 rows in kernels_ivf_u8.hip and its tile in kernels_ivf_u8_group.hip; the coarse quantiser is an inner exact f32 index over the centroids, whatever the rows' element type.
 #include "../../include/longbow_gpu.h"
 #include "lb_device.h"
@@ -89,6 +89,9 @@ constexpr int64_t IVF_TILE_PAIRS_PER_LIST = 4;
 constexpr int64_t IVF_I8_TILE_PAIRS_PER_LIST = 4;
 // and for a uint8 batch and its tile over the shifted bytes (kernels_ivf_u8_group.hip): DESIGN 3.29
 constexpr int64_t IVF_U8_TILE_PAIRS_PER_LIST = 4;
+// and for a float16 batch and its tile over rows kept fp16 in LDS (kernels_ivf_f16_group.hip): measured, DESIGN 3.30.  Twice the
+// others': the fp16 per-pair scan moves half the bytes, and at 4 pairs a list (1,024 queries x 1 probe) it beat the tile
+constexpr int64_t IVF_F16_TILE_PAIRS_PER_LIST = 8;
 
 // The handle's call of the search loop (lb_ivf_host.h): its middle steps are the queries' norms under cosine, inside the plan's
 // timing slot, and the scan of the rows.  A float32 handle's scan has two forms, which leave the same keys: the per-pair scan
@@ -97,8 +100,9 @@ constexpr int64_t IVF_U8_TILE_PAIRS_PER_LIST = 4;
 // handle's, the visible ones, or a call bitmap's: the once-per-call lists of a shared bitmap count 2 nlist, the per-slot ones
 // 2 nq np, which no batch reaches.  An int8 handle's scan has the same two forms: a batch takes the i8 matrix-core tile when the
 // per-pair scan would stage its rows (ivf_scan_i8_staged) and nq np >= IVF_I8_TILE_PAIRS_PER_LIST nlist, the lists counted
-// alike, and so has a uint8 handle's: ivf_scan_u8_staged and nq np >= IVF_U8_TILE_PAIRS_PER_LIST nlist.  The float16 scan is
-// untouched.  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
+// alike, and so has a uint8 handle's: ivf_scan_u8_staged and nq np >= IVF_U8_TILE_PAIRS_PER_LIST nlist, and a float16 handle's:
+// ivf_scan_f16_staged and nq np >= IVF_F16_TILE_PAIRS_PER_LIST nlist (the float32 tile's chains over rows that stay fp16 up to
+// the lane's registers).  d_q8: on an int8 or uint8 handle the call's queries of that type, c.queries being those
 // widened to f32; the scan reads the narrow ones, a batch's at the offset of its b.Q in c.queries.
 int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
 {
@@ -111,6 +115,7 @@ int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
         if (nlist > IVF_MAX_NLIST) return false;
         if (p->dtype == DT_I8) return ivf_scan_i8_staged(p->metric, p->dims, X, Q) && pairs >= IVF_I8_TILE_PAIRS_PER_LIST * nlist;
         if (p->dtype == DT_U8) return ivf_scan_u8_staged(p->dims, X, Q) && pairs >= IVF_U8_TILE_PAIRS_PER_LIST * nlist;
+        if (p->dtype == DT_F16) return ivf_scan_f16_staged(p->dims, X, Q) && pairs >= IVF_F16_TILE_PAIRS_PER_LIST * nlist;
         return p->dtype == DT_F32 && p->dims % 4 == 0 && ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Q)) & 15) == 0 &&
                pairs >= IVF_TILE_PAIRS_PER_LIST * nlist;
     };
@@ -161,7 +166,17 @@ int ivf_search_rows(lb_gpu_ivf *p, const IvfCall &c, const void *d_q8)
                 }
                 launch_ivf_scan_u8(a8, w.maxlen, c.s);
             }
-            else if (p->dtype == DT_F16) launch_ivf_scan_f16(p->metric, p->order, IvfF16Scan{b, p->rows<_Float16>()}, w.maxlen, c.s);
+            else if (p->dtype == DT_F16) {
+                const IvfF16Scan a16{b, p->rows<_Float16>()};
+                if (groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist, a16.X, b.Q)) {
+                    IvfGroups g = groups; // (as below)
+                    g.max_items = (uint32_t)ivf_group_max_items((int64_t)b.nq * b.np, b.L.nlist);
+                    LB_HIP(launch_ivf_scan_f16_tile(p->metric, p->order, a16, g, w.maxlen, c.s));
+                    route = 2;
+                    return true;
+                }
+                launch_ivf_scan_f16(p->metric, p->order, a16, w.maxlen, c.s);
+            }
             else if (groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist, b.X, b.Q)) {
                 // (a smaller last batch over the same lists fits the full batch's scratch: fewer pairs, the same nlist)
                 IvfGroups g = groups;

@@ -132,7 +132,7 @@ void launch_ivf_scan_f16(int metric, int order, const IvfF16Scan &a, int64_t max
 {
     const int64_t pairs = (int64_t)a.b.nq * a.b.np;
     if (pairs <= 0 || maxlen <= 0) return;
-    const bool staged = a.b.D % 8 == 0 && ((reinterpret_cast<uintptr_t>(a.X) | reinterpret_cast<uintptr_t>(a.b.Q)) & 15) == 0;
+    const bool staged = ivf_scan_f16_staged(a.b.D, a.X, a.b.Q);
     const dim3 grid = ivf_scan_grid(pairs, maxlen, staged ? IH_ROWS : IH_GEN_ROWS);
     with_metric_order(metric, order, [&](auto m, auto o) {
         if (staged) hipLaunchKernelGGL((ivf_scan_f16_kernel<decltype(m)::value, decltype(o)::value>), grid, dim3(IH_ROWS), 0, s, a);

@@ -14,9 +14,12 @@ and after.  A run that finds no GPU fails.
 
 --dtype f32 (the default) measures the float32 handle and prints what this tool always printed.  With f16 or both the rows are
 rounded to float16 first (and widened again for the f32 handle, the flat index and the centroids), so every handle holds the same
-values.  f16 measures the float16 handle (lb_gpu_ivf_new_f16) alone.  both fills a float32 and a float16 handle in one process,
-alternates their profiled runs, asserts that their labels and distances are equal in every cell, and prints per cell both
-handles' four timing slots with the spread (min, max) of the scan slot, and the scan's bytes per second on each.
+values.  f16 measures the float16 handle (lb_gpu_ivf_new_f16) alone; its last_route is 2 where the batch took the float16
+list-major tile (kernels_ivf_f16_group.hip), which is how two builds' scan slots are compared cell by cell.  both fills a float32
+and a float16 handle in one process, alternates their profiled runs, asserts that their labels and distances are equal in every
+cell, and prints per cell both handles' four timing slots with the spread (min, max) of the scan slot, the scan's bytes per
+second on each and scan_f16_over_f32; last_route there is the float32 handle's, whose tile starts at 4 pairs a list where the
+float16 handle's starts at 8, so at a cell between the two the ratio sets a per-pair fp16 scan beside the float32 tile.
 
 --dtype int8 rounds rows and queries into int8 (254 steps over [-0.5, 0.5)) and runs the int8 handle (lb_gpu_ivf_new_i8, int8
 queries) beside the float32 handle over the same values widened, in one process, their profiled runs taking turns.  The two
