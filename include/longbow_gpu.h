@@ -1427,8 +1427,7 @@ int lb_gpu_ivfpq4_compact(lb_gpu_ivfpq4 *p, int64_t *old_rows, int64_t cap);
  * Argument checks answer before a device is touched, LB_ERR_INVALID_ARG before LB_ERR_UNSUPPORTED before LB_ERR_NO_DEVICE, and a
  * refused call writes nothing.  Searches and reads share the handle; adds, reserve and the filter calls take it alone.  ctx
  * (nullable) is polled before every launch.  Host pointers are borrowed for the call; d_ pointers are device memory.  Not here:
- * adding ready-made codes, a list-major copy of the codes, a multi-query tile that shares a list's rows between the queries
- * that probe it, the i8 matrix-core pass, residual SQ8, SQ8EuclideanDistance as a reported distance, search combining,
+ * adding ready-made codes, a list-major copy of the codes, residual SQ8, SQ8EuclideanDistance as a reported distance, search combining,
  * lb_gpu_comm_*, removing rows, Save / Load, and the Go and C++ mirrors. */
 typedef struct lb_gpu_ivfsq8 lb_gpu_ivfsq8;
 lb_gpu_ivfsq8 *lb_gpu_ivfsq8_new(int device, int dims, const float *min, const float *max, int order, int nlist, const float *centroids,
@@ -1448,6 +1447,14 @@ int lb_gpu_ivfsq8_add_device(lb_gpu_ivfsq8 *p, int64_t n, const float *d_vectors
 int lb_gpu_ivfsq8_get_codes(lb_gpu_ivfsq8 *p, int64_t row0, int64_t n, uint8_t *codes); /* u8[n*dims], insertion order, pads stripped */
 int lb_gpu_ivfsq8_list_sizes(lb_gpu_ivfsq8 *p, int64_t *sizes); /* [nlist] */
 int lb_gpu_ivfsq8_assignments(lb_gpu_ivfsq8 *p, int64_t row0, int64_t n, int32_t *lists); /* the lists of rows [row0, row0 + n) */
+/* The scan of the probed lists has two forms, as on the IVF-Flat handles (lb_gpu_ivf_search).  The per-pair scan gives every
+ * (query, probed list) pair workgroups of its own.  The list-major tile groups a batch's pairs by list and scores 128 rows of a
+ * list against up to 64 of the queries that probe it on the i8 matrix cores, over the codes shifted by 128 as they are staged
+ * (the shift leaves every difference as it is) with one exact int32 total a pair at every dims; a batch (at most 1,024 queries)
+ * takes it when nq * nprobe >= 4 * nlist, nlist counting the lists the batch walks: the handle's, the visible ones under a
+ * filter or removals, twice the handle's for the once-per-call lists of a bitmap shared by the call's queries (a bitmap's
+ * per-query lists are never shared and never qualify).  It has no condition on dims or alignment.  Both forms leave the same
+ * integer keys, so the result does not depend on the form; lb_gpu_ivfsq8_last_route tells which ran. */
 int lb_gpu_ivfsq8_search(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels);
 int lb_gpu_ivfsq8_search_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *queries, int k, int nprobe, float *dist, int64_t *labels,
                              const lb_cancel *ctx);
@@ -1482,6 +1489,9 @@ int64_t lb_gpu_ivfsq8_nvisible(const lb_gpu_ivfsq8 *p);
  * queries, out[2] the largest per-query count, out[3] queries whose selection ran from LDS; under a row filter the rows are the
  * visible ones of the probed lists */
 int lb_gpu_ivfsq8_last_search_stats(lb_gpu_ivfsq8 *p, int64_t out[4]);
+/* the scan form of the last search (see lb_gpu_ivfsq8_search), published with its stats: 0 a null handle, no search yet or an
+ * empty handle; 1 every batch took the per-pair scan; 2 at least one batch took the list-major matrix-core tile */
+int lb_gpu_ivfsq8_last_route(const lb_gpu_ivfsq8 *p);
 /* instrumentation (tools/ivfsq8_bench.py), as lb_gpu_ivf_set_profiling: ms[0] the probes (the coarse search), ms[1] the plan,
  * ms[2] the queries' codes and their norms, ms[3] the scan of the probed lists' rows, ms[4] the selection; summed over the
  * search's batches */

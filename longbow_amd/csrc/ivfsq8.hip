@@ -1,5 +1,6 @@
 // ivfsq8.hip -- host side of the lb_gpu_ivfsq8_* entry points of include/longbow_gpu.h: the IVF-SQ8 index, the coarse partition of
-// the IVF-Flat handle (ivf.hip) over the codes of the SQ8 handle (sq8.hip).  The new kernels are in kernels_ivfsq8.hip; the coarse
+// the IVF-Flat handle (ivf.hip) over the codes of the SQ8 handle (sq8.hip).  The new kernels are in kernels_ivfsq8.hip, the list-major
+// matrix-core tile of the scan in kernels_ivfsq8_group.hip; the coarse
 // quantiser is an inner exact f32 index over the centroids, the lists are kernels_ivf.hip's, the codec and the norms
 // kernels_sq8.hip's.  The codes stay in insertion order, so under a row filter the visible lists hold rows, as on IVF-Flat.
 #include "../../include/longbow_gpu.h"
@@ -15,6 +16,7 @@ struct lb_gpu_ivfsq8 : IvfHandle { // the partition (L2), and under a row filter
     std::vector<float> h_min, h_max; // [dims], fixed at creation
     DevBuf<float> d_par;            // [3][dims]: min, max, scale
     float timing[5] = {0, 0, 0, 0, 0}; // of the last profiled search (under err_mu): probes, plan, the queries' codes, scan, select; ms summed over its batches
+    int last_route = 0;             // of the last search (under err_mu, published beside part.stats): lb_gpu_ivfsq8_last_route
     const float *dmin() const { return d_par.get(); }
     const float *dmax() const { return d_par.get() + dims; }
     const float *dscale() const { return d_par.get() + 2 * (size_t)dims; }
@@ -39,29 +41,73 @@ int add_impl(lb_gpu_ivfsq8 *p, int64_t n, const float *vectors, const int64_t *i
         ivf_no_relist);
 }
 
+// Pairs (query, probe slot) per list the batch walks from which a batch takes the list-major i8 matrix-core tile
+// (kernels_ivfsq8_group.hip) in place of the per-pair scan: DESIGN 3.31.  Below it the grouping's launches cost more than the
+// sharing saves.
+constexpr int64_t IVF_SQ8_TILE_PAIRS_PER_LIST = 4;
+
 // The handle's call of the search loop (lb_ivf_host.h): exact integer k-NN.  Its middle steps are the queries' codes and their
 // norms, a timing slot of their own, and the scan of the probed lists' rows; the selection is the one over integer keys.  The
 // lists hold rows and the scan gathers by row, so the visible lists and a call's go through the loop as the IVF-Flat handle's do.
+// The scan has two forms, which leave the same keys (ivf.hip: ivf_search_rows states the rule for the IVF-Flat handles): the
+// per-pair scan and, for a batch with nq np >= IVF_SQ8_TILE_PAIRS_PER_LIST nlist over the lists it walks (at most IVF_MAX_NLIST
+// of them, the grouping sort's buckets), the list-major tile.  The lists it walks are the handle's, the visible ones, or a call
+// bitmap's: the once-per-call lists of a shared bitmap count 2 nlist, the per-slot ones 2 nq np, which no batch reaches.  The
+// tile takes its norms from the codes it stages, so a batch that takes it skips the queries' norms.
 int ivfsq8_search_dev(lb_gpu_ivfsq8 *p, const IvfCall &c)
 {
     uint8_t *d_qc = nullptr;
     int32_t *d_qn = nullptr;
+    IvfGroups groups{};
+    int route = 0; // 0: no batch scanned yet; 1: per-pair scans alone; 2: a batch took the tile
     hipStream_t s = c.s;
-    return ivf_search(
+    auto takes_tile = [](int64_t pairs, int nlist) { return nlist <= IVF_MAX_NLIST && pairs >= IVF_SQ8_TILE_PAIRS_PER_LIST * nlist; };
+    const int rc = ivf_search(
         p, c, IvfSearchForm{p->timing, 5, kQueryBatch, launch_ivfsq8_select},
-        [&](Carve &cv, IvfBatch &, int64_t nb) {
+        [&](Carve &cv, IvfBatch &b, int64_t nb) {
             d_qc = cv.take<uint8_t>((size_t)nb * p->stride);
             d_qn = cv.take<int32_t>((size_t)nb * 4);
+            // the grouping's scratch, if a full batch can take the tile: over the handle's lists, or a shared call bitmap's
+            const int64_t pairs = nb * b.np;
+            const int nlist = c.filter.on ? 2 * b.L.nlist : b.L.nlist;
+            if (!takes_tile(pairs, nlist)) return;
+            groups.max_items = (uint32_t)ivf_group_max_items(pairs, nlist);
+            groups.bucket = cv.take<uint32_t>((size_t)pairs * 4);
+            groups.gpairs = cv.take<uint32_t>((size_t)pairs * 4);
+            groups.goff = cv.take<uint32_t>(((size_t)nlist + 1) * 4);
+            // (the sort's scratch is not monotone in the pairs: the call's two batch sizes are both asked)
+            const size_t words = std::max(ivf_sort_hist_words(pairs, nlist), ivf_sort_hist_words(std::max<int64_t>(c.nq % nb, 1) * b.np, nlist));
+            groups.hist = cv.take<uint32_t>(words * 4);
+            groups.items = cv.take<uint2>((size_t)groups.max_items * 8);
+            groups.nitems = cv.take<uint32_t>(4);
         },
         [&](const IvfBatch &b, const IvfWalk &w, auto &&poll, auto &&next) {
             if (!next()) return false; // (the plan's slot ends here)
             launch_sq8_encode(b.Q, b.nq, p->dims, p->dmin(), p->dmax(), p->dscale(), d_qc, s);
-            if (!poll()) return false;
-            launch_sq8_norms(d_qc, b.nq, p->stride, d_qn, s);
+            // (a smaller last batch over the same lists fits the full batch's scratch: fewer pairs, the same nlist)
+            const bool tile = groups.bucket && takes_tile((int64_t)b.nq * b.np, b.L.nlist);
+            if (!tile) {
+                if (!poll()) return false;
+                launch_sq8_norms(d_qc, b.nq, p->stride, d_qn, s);
+            }
             if (!next()) return false;
-            launch_ivfsq8_scan(IvfSq8Scan{b, p->d_codes.get(), p->n, p->stride, d_qc, d_qn}, w.maxlen, s);
+            const IvfSq8Scan a{b, p->d_codes.get(), p->n, p->stride, d_qc, d_qn};
+            if (tile) {
+                IvfGroups g = groups;
+                g.max_items = (uint32_t)ivf_group_max_items((int64_t)b.nq * b.np, b.L.nlist);
+                LB_HIP(launch_ivfsq8_scan_tile(a, g, w.maxlen, s));
+                route = 2;
+                return true;
+            }
+            launch_ivfsq8_scan(a, w.maxlen, s);
+            route = std::max(route, 1);
             return true;
         });
+    if (rc == LB_OK) { // (a search that failed or was cancelled publishes nothing, as with the stats)
+        std::lock_guard<std::mutex> g(p->err_mu);
+        p->last_route = route;
+    }
+    return rc;
 }
 
 
@@ -210,6 +256,12 @@ int lb_gpu_ivfsq8_search_bitmap_ctx(lb_gpu_ivfsq8 *p, int64_t nq, const float *q
     return ivf_search_ctx(p, nq, queries, k, nprobe, dist, labels, ctx, ivfsq8_search_dev, CallBitmap{bitmap, nbits, stride_bytes, false});
 }
 int lb_gpu_ivfsq8_last_search_stats(lb_gpu_ivfsq8 *p, int64_t out[4]) { return ivf_last_search_stats(p, out); }
+int lb_gpu_ivfsq8_last_route(const lb_gpu_ivfsq8 *p)
+{
+    if (!p) return 0;
+    std::lock_guard<std::mutex> g(const_cast<lb_gpu_ivfsq8 *>(p)->err_mu);
+    return p->last_route;
+}
 int lb_gpu_ivfsq8_set_profiling(lb_gpu_ivfsq8 *p, int enable) { return ivf_set_profiling(p, enable); }
 int lb_gpu_ivfsq8_last_timing(lb_gpu_ivfsq8 *p, float ms[5]) { return ivf_last_timing(p, ms); }
 

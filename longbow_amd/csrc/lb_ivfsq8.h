@@ -1,4 +1,4 @@
-// lb_ivfsq8.h -- what ivfsq8.hip (host) and kernels_ivfsq8.hip (device) of the IVF-SQ8 index share: the argument block of the
+// lb_ivfsq8.h -- what ivfsq8.hip (host) and kernels_ivfsq8.hip / kernels_ivfsq8_group.hip (device) of the IVF-SQ8 index share: the argument block of the
 // list scan and the launchers.  The semantics are stated in include/longbow_gpu.h (lb_gpu_ivfsq8_*).  The plan of a batch and
 // the probes are the IVF-Flat index's (lb_ivf.h): IvfBatch is taken as it is, and the scan's own fields lie beside it here, so
 // that the argument blocks of the kernels in kernels_ivf.hip and kernels_ivfpq.hip stay byte for byte what they were.
@@ -21,6 +21,11 @@ struct IvfSq8Scan {
 
 // keys[q][seg[q][p] + i] = ((uint64_t)S << 32) | row of the i-th row of the p-th probed list; maxlen: the longest list of the handle
 void launch_ivfsq8_scan(const IvfSq8Scan &a, int64_t maxlen, hipStream_t s);
+// The list-major form of that scan (kernels_ivfsq8_group.hip), for a batch whose queries share lists: the pairs grouped by list
+// as launch_ivf_group leaves them (lb_ivf.h: IvfGroups, the scratch of a batch of nq np pairs over a.b.L.nlist <= IVF_MAX_NLIST
+// lists), a workgroup scoring 128-row tiles of a list against up to IVF_GROUP_PAIRS of its pairs on the i8 matrix cores.  The
+// same keys in the same places, bit for bit; a.qnorms is not read.  Seven launches: launch_ivf_group's six, the tile
+hipError_t launch_ivfsq8_scan_tile(const IvfSq8Scan &a, const IvfGroups &g, int64_t maxlen, hipStream_t s);
 // launch_ivf_select over such keys: the k smallest of each query, ascending as integers -> dist = float32(S) / labels [nq][k]
 // (ids nullable: the row itself), padded FLT_MAX / -1
 void launch_ivfsq8_select(const IvfBatch &a, int k, const int64_t *ids, float *dist, int64_t *labels, hipStream_t s);

@@ -119,6 +119,11 @@ class IVFSQ8(ivf.RemovalMixin, RowFilterMixin, IVFBase):
         short, _ = self.search(v, shortlist, nprobe, bitmap=bitmap, bitmap_stride=bitmap_stride)
         return index.Refine(v, short, k, order)
 
+    def last_route(self):
+        """the scan form of the last search (lb_gpu_ivfsq8_last_route): 0 none yet or an empty handle, 1 the per-pair scan in every
+        batch, 2 the list-major i8 matrix-core tile in at least one"""
+        return int(self._lib.lb_gpu_ivfsq8_last_route(self._h))
+
     def last_timing(self):
         """ms of the last profiled search, summed over its batches: (probes, plan, the queries' codes, scan, selection).  The
         compaction of the lists under a call's bitmap falls into the plan's."""

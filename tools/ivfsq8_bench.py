@@ -8,7 +8,8 @@ with add_device and never held together; the bounds are -0.5 / 0.5 in every dime
 (evenly spaced).  The same vectors go to an sq8.SQ8Encoder with the same bounds, so it holds the same codes.  Per cell
 (nq x nprobe): the median of three runs, each the p50 of ten searches after a warm-up, through the device-pointer entry point by
 wall clock (the call returns when the results are on the device); the HIP-event time of each step as the median of three more,
-profiled, runs (probes, plan, the queries' codes, scan, selection); rows scanned and the scan's bytes (rows * stride for the
+profiled, runs (probes, plan, the queries' codes, scan, selection) with the scan slot of each run beside it ("scan_ms_runs") and
+last_route, the form of the list scan (lb_gpu_ivfsq8_last_route: 1 per pair, 2 the list-major matrix-core tile); rows scanned and the scan's bytes (rows * stride for the
 codes, nothing for norms, which are not kept, plus 8 per key written) over its time; recall@k against lb_gpu_sq8_search over the
 same codes, which is the full integer ranking, not the exact f32 one; and that search's own p50 at the same nq, in the same run.
 Also: the add rate in rows/s and hbm_bytes against its per-row terms.  The shader clock is read before and after.  A run that
@@ -198,8 +199,9 @@ def main():
             got = L[:nq].cpu().numpy()
             recall = float(np.mean([np.intersect1d(got[j], truth[j]).size / a.k for j in range(nq)]))
             scan_bytes = st[1] * (stride + 8)
-            cell = {"nq": nq, "nprobe": nprobe, "p50_ms": ms, "flat_sq8_p50_ms": flat_ms}
+            cell = {"nq": nq, "nprobe": nprobe, "p50_ms": ms, "flat_sq8_p50_ms": flat_ms, "last_route": h.last_route()}
             cell.update(dict(zip(STEPS, steps)))
+            cell["scan_ms_runs"] = [float(p[3]) for p in prof]
             cell.update({"rows_scanned": st[1], "max_rows_per_query": st[2], "selected_from_lds": st[3], "scan_bytes": scan_bytes,
                          "scan_gb_per_s": scan_bytes / max(steps[3], 1e-6) / 1e6, "recall_at_k_vs_full_sq8": recall})
             if nprobe >= a.nlist:  # every list probed: the flat SQ8 search's own result, bit for bit
